@@ -1,6 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE.json's metric on its headline config, one process per GPU.
 
+  plain  : `bench.py --gpus 1 --steps K --warmup W` measures the headline and nothing else: the clocks are primed on a context of
+           its own (so that the timed context's state depends on W and K alone), then W untimed warm-up ticks and ONE region of
+           exactly K ticks bracketed by synchronisations; `ms_per_step` = that region / K, `value` = maps/s over it.  With
+           --dump-outputs DIR the maps the last timed tick produced are written to DIR as float32 .npy files (a fixed, seeded
+           sample of texels where all of them would exceed 64 MB): the same arguments give the same inputs, run after run.
+  --full : everything described below as well -- the repeated and interleaved timing, roofline, kernel probes, CPU baselines,
+           the scene's cadence, the other configurations, the measured traffic and (N > 1) the scaling references.
+
   metric : displacement+normal maps/sec, 1024^2 x 4 cascades (1 "map" = one cascade update = one
            displacement layer + one normal/foam layer); achieved HBM GB/s vs peak in `roofline`
   step   : one simulation tick = time-modulate + 2-D IFFT + unpack/foam of all 4 cascades of this rank
@@ -45,7 +53,7 @@
            own roofline and CPU baseline, to --sweep-out (profiles/) and prints the headline line last; --sweep-grid does the same
            over north_star's whole grid, 256^2 .. 2048^2 x {1, 4, 8} cascades.
 
-Launch:  python bench.py [--gpus 1] [--steps K] [--warmup W]
+Launch:  python bench.py [--gpus 1] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
          python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
                 bench.py --gpus N --steps K --warmup W
 """
@@ -60,7 +68,7 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-HBM_PEAK_GBPS = 8000.0   # MI355X HBM3E spec peak, /opt/skills/guides/MI355X_MICROARCH.md:35
+HBM_PEAK_GBPS = 8000.0   # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 SINGLE_STREAM = False  # --single-stream (A/B)
 COPY_CEILING_GBPS = 6290.0  # the same guide's measured copy rate (profiles/r01_membench_copy_ceiling.txt reproduces it)
 # SURVEY.md 8d's contract: algorithmic bytes per texel per cascade-update of a two-pass transform with a four-layer FP32
@@ -89,8 +97,8 @@ def parse():
     ap.add_argument("--cascades", type=int, default=None, help="cascades per GPU (default: 4 at --gpus 1 = the headline config; at --gpus N > 1 --total-cascades / N)")
     ap.add_argument("--total-cascades", type=int, default=None, help="cascades of the whole job, shared out evenly over the GPUs (strong scaling; default 8 at "
                                                                      "--gpus N > 1 = BASELINE config C4: 4 / 2 / 1 per GPU at N = 2 / 4 / 8)")
-    ap.add_argument("--min-time", type=float, default=2.5, help="repeat the K-tick timed region until this many seconds have been timed (median reported)")
-    ap.add_argument("--max-repeats", type=int, default=4000)
+    ap.add_argument("--min-time", type=float, default=2.5, help="--full: repeat the K-tick timed region until this many seconds have been timed (median reported)")
+    ap.add_argument("--max-repeats", type=int, default=4000, help="--full: the most regions --min-time may repeat")
     ap.add_argument("--gather-every", type=int, default=-1, help="gather the maps every k ticks inside the timed region (0 = once, after it; "
                                                                    "-1 = auto: the smallest k whose gather hides under k ticks of compute)")
     ap.add_argument("--gather", choices=("all", "root"), default="root", help="gather to rank 0 (the consumer GPU), or all_gather to every rank")
@@ -101,25 +109,32 @@ def parse():
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL; gloo only for rehearsing the "
                                                      "multi-rank control flow on a box with fewer GPUs than ranks)")
     ap.add_argument("--share-gpu", action="store_true", help="rehearsal only: every rank uses GPU 0 (numbers are meaningless)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--single-stream", action="store_true", help="A/B: every context with OW_FLAG_SINGLE_STREAM (the tick-pair launches stay whole, on the one stream: no two chains)")
-    ap.add_argument("--no-unmerged", action="store_true", help="time ow_run's regions only: no roofline.unmerged / update_all_calls / reference_schedule beside them")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU baseline sample size in seconds of host work (runs BEFORE the GPU regions, so that the "
+    ap.add_argument("--no-unmerged", action="store_true", help="--full: time ow_run's regions only: no roofline.unmerged / update_all_calls / reference_schedule beside them")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="--full: CPU baseline sample size in seconds of host work (runs BEFORE the GPU regions, so that the "
                                                                     "GPU is busy for one contiguous stretch afterwards)")
-    ap.add_argument("--no-measure-traffic", action="store_true", help="do not run the two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) behind roofline.traffic; "
+    ap.add_argument("--no-measure-traffic", action="store_true", help="--full: do not run the two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) behind roofline.traffic; "
                                                                       "the figure of an earlier profiling visit (profiles/pmc_traffic.json) is quoted instead")
-    ap.add_argument("--no-references", action="store_true", help="N > 1: skip per_gpu_alone / one_gpu_whole_job (the in-line scaling references)")
-    ap.add_argument("--block-ms", type=float, default=40.0, help="N = 1: the timed regions of the four ways of driving the boundary alternate in blocks of about this long")
-    ap.add_argument("--secondary-time", type=float, default=0.7, help="N = 1: seconds of timed regions for each of roofline.update_all_calls / unmerged / reference_schedule "
+    ap.add_argument("--no-references", action="store_true", help="--full: N > 1: skip per_gpu_alone / one_gpu_whole_job (the in-line scaling references)")
+    ap.add_argument("--block-ms", type=float, default=40.0, help="--full: N = 1: the timed regions of the four ways of driving the boundary alternate in blocks of about this long")
+    ap.add_argument("--secondary-time", type=float, default=0.7, help="--full: N = 1: seconds of timed regions for each of roofline.update_all_calls / unmerged / reference_schedule "
                                                                        "(and x 1.5 for each of roofline.other_configs)")
-    ap.add_argument("--no-scene", action="store_true", help="skip roofline.scene_schedule (the reference scene's rate-limited, one-cascade-per-frame cadence)")
-    ap.add_argument("--grid-time", type=float, default=0.5, help="N = 1: seconds of timed regions for each of the nine further grid configurations of roofline.other_configs")
-    ap.add_argument("--no-grid", action="store_true", help="roofline.other_configs: BASELINE configs C5 and C2 only, not the rest of north_star's 256^2 .. 2048^2 x {1, 4, 8} grid")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip roofline.other_configs (2048^2 x 4 and 256^2 x 4 timed in the same process after the headline)")
+    ap.add_argument("--no-scene", action="store_true", help="--full: skip roofline.scene_schedule (the reference scene's rate-limited, one-cascade-per-frame cadence)")
+    ap.add_argument("--grid-time", type=float, default=0.5, help="--full: N = 1: seconds of timed regions for each of the nine further grid configurations of roofline.other_configs")
+    ap.add_argument("--no-grid", action="store_true", help="--full: roofline.other_configs: BASELINE configs C5 and C2 only, not the rest of north_star's 256^2 .. 2048^2 x {1, 4, 8} grid")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full: skip roofline.other_configs (2048^2 x 4 and 256^2 x 4 timed in the same process after the headline)")
     ap.add_argument("--sweep", action="store_true", help="one line per BASELINE configuration, appended to --sweep-out")
     ap.add_argument("--sweep-grid", action="store_true", help="like --sweep, over the whole grid 256^2 .. 2048^2 x {1, 4, 8} cascades")
     ap.add_argument("--sweep-out", default=os.path.join(ROOT, "profiles", "sweep.jsonl"))
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="measure everything beyond the headline as well (see the module docstring); "
+                                                        "--sweep / --sweep-grid imply it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the maps of the last timed tick to DIR/<name>.npy (float32, at most 64 MB)")
+    args = ap.parse_args()
+    if args.sweep or args.sweep_grid:
+        args.full = True
+    return args
 
 
 def cpu_baseline(n, cascades, seconds):
@@ -224,8 +239,10 @@ class Sensors:
     """sclk / mclk / socket power / temperatures of the device, one amdsmi call per sample (the bench line recorded no clock, so a
     slow region could not be told from a slow box).  Every failure is swallowed: the sensors must not cost the line."""
 
-    def __init__(self, index=0):
+    def __init__(self, index=0, enabled=True):
         self.h, self.source, self.error = None, None, None
+        if not enabled:   # (a plain run records no clocks: sample() returns None)
+            return
         try:
             import amdsmi
             self.smi = amdsmi
@@ -446,6 +463,26 @@ def grid_scalars(other_configs, headline_frac):
     return out
 
 
+DUMP_TEXELS = 1 << 20   # texels per map in a --dump-outputs sample: 2 maps x 16 MB of float32 + 8 MB of indices
+DUMP_SEED = 20261015
+
+
+def dump_outputs(out_dir, torch, disp, norm):
+    """The two maps (C x n x n RGBA16F) as float32 .npy: whole where the texels fit DUMP_TEXELS, otherwise the same seeded sample
+    of texels of both (`sample_texel_index.npy`: flat indices into C x n x n, as float64)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    texels = disp.shape[0] * disp.shape[1] * disp.shape[2]
+    idx = None
+    if texels > DUMP_TEXELS:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(texels, DUMP_TEXELS, replace=False))
+        np.save(os.path.join(out_dir, "sample_texel_index.npy"), idx.astype(np.float64))
+        idx_dev = torch.from_numpy(idx).to(disp.device)
+    for name, m in (("displacement", disp), ("normal", norm)):
+        v = m.reshape(texels, 4)[idx_dev] if idx is not None else m
+        np.save(os.path.join(out_dir, f"{name}.npy"), v.float().cpu().numpy())
+
+
 def measure(args, torch, dist, world, rank, local_rank, n, C, sensors):
     from godotoceanwaves_amd import WaveCascadeParameters, WaveGenerator, cascade_preset, UPDATE_DELTA
     from godotoceanwaves_amd import sharding
@@ -458,13 +495,14 @@ def measure(args, torch, dist, world, rank, local_rank, n, C, sensors):
     norm = torch.zeros((layers, n, n, 4), dtype=torch.float16, device="cuda")
     torch.cuda.synchronize()
 
-    def make_driver(**attrs):
-        """a context on the shared stream and map arrays, with FRESH parameter objects: their dirty flags make THIS context generate its spectra
-        (a context fed with consumed flags would run on all-zero spectra, and zeros run measurably FASTER: 52.0 against 55.4 us per tick at
-        1024^2 x 4, less switching power, higher clock; round 3 fell for that once)"""
+    def make_driver(own_maps=False, **attrs):
+        """a context on the shared stream and map arrays (own_maps: maps of its own), with FRESH parameter objects: their dirty flags make THIS
+        context generate its spectra (a context fed with consumed flags would run on all-zero spectra, and zeros run measurably FASTER: 52.0
+        against 55.4 us per tick at 1024^2 x 4, less switching power, higher clock; round 3 fell for that once)"""
         g = WaveGenerator()
         g.map_size, g.device_id, g.stream = n, local_rank, compute.cuda_stream
-        g.external_maps = (disp.data_ptr(), norm.data_ptr())
+        if not own_maps:
+            g.external_maps = (disp.data_ptr(), norm.data_ptr())
         g.single_stream = SINGLE_STREAM
         for k, v in attrs.items():
             setattr(g, k, v)
@@ -528,7 +566,7 @@ def measure(args, torch, dist, world, rank, local_rank, n, C, sensors):
     # the other ways of driving the boundary (N = 1), created and warmed BEFORE the priming: all timed regions then alternate on warm contexts
     others = {}
     other_errors = {}
-    if world == 1 and not args.no_unmerged:
+    if world == 1 and args.full and not args.no_unmerged:
         ways = [("update_all_calls", {"run_as_calls": True}), ("unmerged", {"tick_groups": False}), ("reference_schedule", {"run_as_reference": True})]
         if not SINGLE_STREAM and ((n == 1024 and C in (4, 8)) or (n == 512 and C == 8)):
             # same-lease A/B of round 6's launch shape: the same ow_run regions with every tick-pair launch whole, on the one stream (OW_FLAG_SINGLE_STREAM)
@@ -545,13 +583,16 @@ def measure(args, torch, dist, world, rank, local_rank, n, C, sensors):
     # ---- clock priming, untimed (not part of W or K): the chip's DVFS needs load to reach its steady state, and a region timed on the ramp -- or
     #      right after the 128-thread CPU leg -- is not the kernel's rate.  Until two consecutive 200-tick probes agree within 1 % (at least
     #      --prime-ms, at most 4 s) ----
+    #      A plain run primes on a context of its own (same shape, maps of its own), so that what the timed context computes does not depend
+    #      on how many probes that took (--dump-outputs)
     priming = {"ms": 0.0, "ticks": 0, "probes": 0, "stable": None, "first_probe_ms_per_step": None, "last_probe_ms_per_step": None}
     if args.prime_ms > 0:
+        prime_drv = main_drv if args.full else make_driver(own_maps=True)
         tp, prev = time.perf_counter(), None
         while True:
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            main_drv.run(UPDATE_DELTA, 200)
+            prime_drv.run(UPDATE_DELTA, 200)
             torch.cuda.synchronize()
             cur = (time.perf_counter() - t0) / 200
             priming["ticks"] += 200
@@ -565,6 +606,8 @@ def measure(args, torch, dist, world, rank, local_rank, n, C, sensors):
                 priming["stable"] = bool(stable)
                 break
         priming["ms"] = round((time.perf_counter() - tp) * 1e3, 1)
+        if prime_drv is not main_drv:
+            prime_drv.free()
     if args.warmup > 1:
         main_drv.run(UPDATE_DELTA, args.warmup - 1)
     if gat is not None:
@@ -605,7 +648,7 @@ def measure(args, torch, dist, world, rank, local_rank, n, C, sensors):
 
     # ---- references for the scaling question (N > 1), measured in this run, before the timed regions ----
     alone = whole_job = None
-    if world > 1 and not args.no_references:
+    if world > 1 and args.full and not args.no_references:
         # (i) every rank on its own: the same ticks timed locally -- no barrier, no gather, no process-group traffic inside the region
         torch.cuda.synchronize()
         mine = []
@@ -648,7 +691,10 @@ def measure(args, torch, dist, world, rank, local_rank, n, C, sensors):
     # ---- timed regions ----
     block_clocks, hit_base, block_medians = {}, {}, []
     samples_of = {"run": []}
-    if world == 1:
+    if not args.full:
+        # a plain run: exactly K ticks (R x K for a gather cadence, N > 1), one region
+        elapsed, samples = timed(main_drv, gather_every, 0.0)
+    elif world == 1:
         # INTERLEAVED (the headline region was the slowest merged region of its own process): blocks of R regions each, ~--block-ms
         # long, alternate between the ways of driving the boundary -- run X run Y run Z ... -- until the headline has --min-time seconds of timed
         # regions and every other way --secondary-time.  A region is exactly K ticks between two synchronisations; every figure is the MEDIAN of
@@ -691,8 +737,12 @@ def measure(args, torch, dist, world, rank, local_rank, n, C, sensors):
         elapsed, samples = timed(main_drv, gather_every, args.min_time)
     group_depth = gen.tick_group_depth()
     launch_mode = gen.last_kernel_family()  # "tick_groups_compact": ow_run launched pass 2 of tick k with pass 1 of tick k + 1 (small batches)
+    if args.dump_outputs and rank == 0:
+        if args.full and others:   # (the interleaved contexts write the same maps: one further tick of the headline context)
+            main_drv.run(UPDATE_DELTA, 1)
+        dump_outputs(args.dump_outputs, torch, disp[:C], norm[:C])
     no_gather = every_tick = None
-    if world > 1 and gather_every > 0:
+    if args.full and world > 1 and gather_every > 0:
         no_gather, _ = timed(main_drv, 0, args.min_time)
         every_tick = elapsed if gather_every == 1 else timed(main_drv, 1, args.min_time)[0]
 
@@ -709,8 +759,59 @@ def measure(args, torch, dist, world, rank, local_rank, n, C, sensors):
             assert torch.equal(got[0][rank * C:(rank + 1) * C], disp[:C]) and bool(torch.isfinite(got[0].float()).all())
     assert bool(torch.isfinite(disp[:C].float()).all()) and float(disp[:C].float().abs().max()) > 0.0
 
-    # ---- the other ways' figures (N = 1) ----
     ticks = state["ticks"]               # ticks per timed region (K, or R x K: see regions_per_sync)
+    maps = ticks * C * world
+    headline = (n, C) == (1024, 4)
+    metric = ("displacement+normal maps/sec, 1024^2 x 4 cascades; achieved HBM GB/s vs peak" if (headline and world == 1) else
+              (f"displacement+normal maps/sec, {n}^2 x {C} cascades; achieved HBM GB/s vs peak" if world == 1 else
+               f"displacement+normal maps/sec, {n}^2 x {C * world} cascades sharded {C} per GPU over {world} GPUs, maps gathered to the consumer GPU; "
+               f"achieved HBM GB/s vs peak (per GPU)"))
+    merged = grouped = launch_mode in MERGED_KERNEL
+    # two chains (round 6): did the timed regions' tick-pair launches go out as two launches of half the cascades on two streams?  (asked BEFORE the
+    # probes below: a launch that carries timing events stays whole)
+    chains = 2 if (merged and gen.chain_stats() > 0) else 1
+    config = {"workload": f"{n}^2 x {C} cascades per GPU, steady-state tick (modulate + 2-D IFFT + unpack/foam), "
+                          f"delta=1/50 s, SURVEY 8d cascade table",
+              "map_size": n, "cascades_per_gpu": C, **({"single_stream": True} if SINGLE_STREAM else {}), "parallelism": f"cascade-sharded x{world}",
+              "launches": (f"tick groups: pass 2 of {group_depth} ticks and pass 1 of the next {group_depth} in one launch (k_tick_group_c_lp)"
+                           if launch_mode == "tick_groups_compact" else
+                           "tick pairs: pass 2 of one batch and pass 1 of the next in one launch (k_tick_pair_c)" +
+                           (", as two chains: two launches of two cascades each on two streams" if chains > 1 else "")) if grouped
+                          else "one pair of launches per batch and tick",
+              "gather": (f"{args.gather}, every {gather_every} ticks (timed), " + ("serialised" if args.no_overlap else "snapshot + side stream"))
+                        if (world > 1 and gather_every) else (f"{args.gather}, final, untimed" if world > 1 else "none"),
+              **({"rehearsal": f"backend={args.backend}, share_gpu={args.share_gpu}: NOT a measurement"}
+                 if (args.share_gpu or (world > 1 and args.backend != "nccl")) else {})}
+    links = None
+    if world > 1:
+        # what lies between each rank's device and the consumer's, as the HIP runtime reports it (ow_query_link: peer access, link type, hops), so
+        # that the line says by itself whether a rank's 16 B/texel went over xGMI (the model's 153 GB/s per link), PCIe, or a staged path
+        try:
+            from godotoceanwaves_amd import _lib as _L
+            import ctypes as _C
+            lk = _L.ow_group_link()
+            _L.check(_L.load().ow_query_link(int(local_rank), 0, _C.byref(lk)))
+            mine = {"rank": rank, **lk.as_dict()}
+        except Exception as e:  # noqa: BLE001  (never the reason a scaling run fails)
+            mine = {"rank": rank, "error": str(e)[:200]}
+        links = [None] * world
+        dist.all_gather_object(links, mine)
+    if not args.full:
+        sync_all()
+        main_drv.free()
+        if rank != 0:
+            return None
+        return {"metric": metric, "value": round(maps / elapsed, 2), "unit": "maps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+                "ms_per_step": round(elapsed / ticks * 1e3, 5), "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
+                "dtype": "f32", "data": "synthetic", "repeats": len(samples), "timed_seconds": round(sum(samples), 4),
+                "timed_ticks_per_region": ticks, "regions_per_sync": ticks // args.steps, "config": config,
+                "frames_per_s": round(ticks * world / elapsed, 2), "spectrum_init_ms": round(spectrum_ms, 3), "clock_priming": priming,
+                **({"links_to_root": links, "final_gather_ms": round(gather_ms, 3),
+                    "gather": {"mode": gat.mode, **({"fallback": gat.fallback} if gat.fallback else {}), "every_ticks": gather_every,
+                               "overlap": not args.no_overlap, **(cadence or {}), "regions_per_sync": ticks // args.steps}} if gat is not None else {}),
+                "full": False}
+
+    # ---- the other ways' figures (N = 1) ----
     unmerged = unmerged_samples = calls = calls_hits = one_stream = None
     refsched = {}
     for nm, d in others.items():
@@ -735,10 +836,6 @@ def measure(args, torch, dist, world, rank, local_rank, n, C, sensors):
     #      to its own dispatch packet on the generator's stream (hipExtLaunchKernel): begin -> end of the kernel itself,
     #      the quantity a rocprofv3 kernel trace reports ----
     probe = 400  # (independent of --steps: a 50-tick probe right after an idle moment measured the clock ramp, 33 us where 400 ticks give 27.7)
-    merged = launch_mode in MERGED_KERNEL
-    # two chains (round 6): did the timed regions' tick-pair launches go out as two launches of half the cascades on two streams?  (asked BEFORE the
-    # probes below: a launch that carries timing events stays whole)
-    chains = 2 if (merged and gen.chain_stats() > 0) else 1
     gl_ms = gl_n = 0
     if merged:  # ow_run's merged launches (tick groups / tick pairs), each timed on its own
         gen.timing(2)
@@ -781,24 +878,9 @@ def measure(args, torch, dist, world, rank, local_rank, n, C, sensors):
             except Exception as e:  # noqa: BLE001
                 other_configs.append({"workload": f"{on}^2 x {oc}", "error": f"{type(e).__name__}: {str(e)[:200]}"})
         other_configs.sort(key=lambda e: [int(v) for v in e["workload"].replace("^2 x", "").split()])
-    links = None
-    if world > 1:
-        # what lies between each rank's device and the consumer's, as the HIP runtime reports it (ow_query_link: peer access, link type, hops), so
-        # that the line says by itself whether a rank's 16 B/texel went over xGMI (the model's 153 GB/s per link), PCIe, or a staged path
-        try:
-            from godotoceanwaves_amd import _lib as _L
-            import ctypes as _C
-            lk = _L.ow_group_link()
-            _L.check(_L.load().ow_query_link(int(local_rank), 0, _C.byref(lk)))
-            mine = {"rank": rank, **lk.as_dict()}
-        except Exception as e:  # noqa: BLE001  (never the reason a scaling run fails)
-            mine = {"rank": rank, "error": str(e)[:200]}
-        links = [None] * world
-        dist.all_gather_object(links, mine)
     if rank != 0:
         return None
 
-    maps = ticks * C * world
     pairs_per_tick = launches / probe                   # the runtime may split a tick into several launch pairs (ow_runtime.hip batch_size)
     per_launch = C / pairs_per_tick                     # average cascades per launch (7 cascades go as 4 + 3 -> 3.5)
     per_launch = int(per_launch) if float(per_launch).is_integer() else round(per_launch, 3)
@@ -811,7 +893,6 @@ def measure(args, torch, dist, world, rank, local_rank, n, C, sensors):
     dom_ms = max(p1_ms, p2_ms)
     dom_bpt, dom_contract = (k1, CONTRACT_BYTES[0]) if first else (k2, CONTRACT_BYTES[1])
     gbps = lambda nbytes, ms: nbytes / (ms * 1e-3) / 1e9 if ms > 0 else 0.0
-    grouped = merged
     if grouped:
         # ow_run launched the timed ticks merged across ticks -- tick groups (k_tick_group_c_lp: pass 2 of GROUP ticks + pass 1 of the next
         # GROUP per launch) or tick pairs (k_tick_pair_c: pass 2 of one batch + pass 1 of the next, GROUP = 1): that kernel IS the timed
@@ -862,12 +943,8 @@ def measure(args, torch, dist, world, rank, local_rank, n, C, sensors):
         clocks = {"source": sensors.source, **({"error": sensors.error} if sensors.error and not sensors.source else {}),
                   "idle_before": idle_clocks, **{("run" if nm == "run" else nm): Sensors.summary(v) for nm, v in block_clocks.items()},
                   "sampled": "after every block of regions (~%g ms)" % args.block_ms}
-    headline = (n, C) == (1024, 4)
     out = {
-        "metric": "displacement+normal maps/sec, 1024^2 x 4 cascades; achieved HBM GB/s vs peak" if (headline and world == 1) else
-                  (f"displacement+normal maps/sec, {n}^2 x {C} cascades; achieved HBM GB/s vs peak" if world == 1 else
-                   f"displacement+normal maps/sec, {n}^2 x {C * world} cascades sharded {C} per GPU over {world} GPUs, maps gathered to the consumer GPU; "
-                   f"achieved HBM GB/s vs peak (per GPU)"),
+        "metric": metric,
         "value": round(maps / elapsed, 2),
         "unit": "maps/s",
         "n_gpus": world,
@@ -888,18 +965,7 @@ def measure(args, torch, dist, world, rank, local_rank, n, C, sensors):
                              "block_medians_ms_per_step": [round(b / ticks * 1e3, 5) for b in (block_medians if len(block_medians) <= 12 else
                                                                                                    block_medians[:6] + block_medians[-6:])],
                              "value_is": "the median region of ow_run over all its blocks"}} if world == 1 else {}),
-        "config": {"workload": f"{n}^2 x {C} cascades per GPU, steady-state tick (modulate + 2-D IFFT + unpack/foam), "
-                               f"delta=1/50 s, SURVEY 8d cascade table",
-                   "map_size": n, "cascades_per_gpu": C, **({"single_stream": True} if SINGLE_STREAM else {}), "parallelism": f"cascade-sharded x{world}",
-                   "launches": (f"tick groups: pass 2 of {group_depth} ticks and pass 1 of the next {group_depth} in one launch (k_tick_group_c_lp)"
-                                if launch_mode == "tick_groups_compact" else
-                                "tick pairs: pass 2 of one batch and pass 1 of the next in one launch (k_tick_pair_c)" +
-                                (", as two chains: two launches of two cascades each on two streams" if chains > 1 else "")) if grouped
-                               else "one pair of launches per batch and tick",
-                   "gather": (f"{args.gather}, every {gather_every} ticks (timed), " + ("serialised" if args.no_overlap else "snapshot + side stream"))
-                             if (world > 1 and gather_every) else (f"{args.gather}, final, untimed" if world > 1 else "none"),
-                   **({"rehearsal": f"backend={args.backend}, share_gpu={args.share_gpu}: NOT a measurement"}
-                      if (args.share_gpu or (world > 1 and args.backend != "nccl")) else {})},
+        "config": config,
         "roofline": {
             "bound": "hbm", "kernel": dom, "kernel_family": family,
             # bytes this kernel must move (its family's design bytes) / its average launch duration
@@ -957,6 +1023,7 @@ def measure(args, torch, dist, world, rank, local_rank, n, C, sensors):
         "frames_per_s": round(ticks * world / elapsed, 2),
         "spectrum_init_ms": round(spectrum_ms, 3),
         "clock_priming": priming,
+        "full": True,
     }
     if gat is not None:
         out["links_to_root"] = links
@@ -1041,13 +1108,13 @@ def main():
     if args.sweep_grid:
         args.sweep = True
     configs = SWEEP_GRID if args.sweep_grid else (SWEEP if args.sweep else [(args.map_size, args.cascades)])
-    sensors = Sensors(local_rank)
+    sensors = Sensors(local_rank, enabled=args.full)
     for n, C in configs:
         # The CPU leg runs FIRST (rank 0, N = 1): everything after it is GPU work in one contiguous stretch -- clock priming, warm-up, the
         # timed regions, the kernel probes, the one-launch-per-pass region -- so that a monitor sampling the device every few seconds sees it
         # busy (round 3's run had its < 3 s of GPU time in front of 15 s of host-only baseline and was sampled as idle four times out of four)
         cpu = None
-        if rank == 0 and not args.no_cpu_baseline and world == 1:
+        if rank == 0 and args.full and not args.no_cpu_baseline and world == 1:
             try:  # (the CPU leg must not cost the line; the oracle is test infrastructure and may be absent from a deployment)
                 cpu = cpu_baseline(n, C, args.cpu_seconds if not args.sweep else min(args.cpu_seconds, 8.0))
             except Exception as e:  # noqa: BLE001
@@ -1056,7 +1123,7 @@ def main():
         out = measure(args, torch, dist, world, rank, local_rank, n, C, sensors)
         if rank == 0:
             out["gpu_phase_s"] = round(time.perf_counter() - t_gpu0, 2)   # contiguous GPU activity of this configuration (priming .. last region)
-            if world == 1 and not args.no_measure_traffic and not args.sweep:
+            if world == 1 and args.full and not args.no_measure_traffic and not args.sweep:
                 # roofline.traffic measured by THIS run (after the timed work: the profiled child process shares the GPU with nothing)
                 rf = out["roofline"]
                 try:

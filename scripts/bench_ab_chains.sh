@@ -1,5 +1,5 @@
 cd "$GRAFT_REPO_ROOT"; O=gpurun_out/r06_s3; mkdir -p $O
-F="--no-cpu-baseline --no-measure-traffic --no-scene --no-other-configs --no-unmerged --min-time 1.0"
+F="--full --no-cpu-baseline --no-measure-traffic --no-scene --no-other-configs --no-unmerged --min-time 1.0"
 for rep in 1 2; do
 for cfg in "512 8" "1024 8"; do set -- $cfg
 for ss in "" "--single-stream"; do

@@ -10,7 +10,7 @@ if want tests; then
 timeout 1800 python -m pytest tests -m gpu -q --timeout 900 > $O/pytest.log 2>&1; echo "pytest rc=$?" >> $O/pytest.log; tail -4 $O/pytest.log
 fi
 if want bench; then
-timeout 600 python bench.py > $O/bench_default.json 2> $O/bench_default.err; tail -c 400 $O/bench_default.json; echo
+timeout 600 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; tail -c 400 $O/bench_default.json; echo
 timeout 300 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err; tail -c 300 $O/bench_driver_cmd.json; echo
 fi
 rm -rf $O/trace $O/trace2048 $O/trace256 $O/pmc
@@ -20,11 +20,11 @@ if want trace; then
 python scripts/rocprof_summary.py $O/trace $O/kernel_trace_1024x4.txt; head -12 $O/kernel_trace_1024x4.txt | cut -c1-150
 fi
 if want trace2048; then
-(cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats -d "$GRAFT_REPO_ROOT/$O/trace2048" -o t -- python "$GRAFT_REPO_ROOT/bench.py" --no-cpu-baseline --no-measure-traffic --map-size 2048 --steps 200 --warmup 30 --min-time 0.5 --no-scene) > $O/trace2048.log 2>&1
+(top=$PWD; cd "$TMPDIR" && timeout 900 rocprofv3 --kernel-trace --stats -d "$top/$O/trace2048" -o t -- python "$top/bench.py" --full --no-cpu-baseline --no-measure-traffic --map-size 2048 --steps 200 --warmup 30 --min-time 0.5 --no-scene) > $O/trace2048.log 2>&1
 python scripts/rocprof_summary.py $O/trace2048 $O/kernel_trace_2048x4.txt; head -8 $O/kernel_trace_2048x4.txt | cut -c1-150
 fi
 if want trace256; then
-(cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats -d "$GRAFT_REPO_ROOT/$O/trace256" -o t -- python "$GRAFT_REPO_ROOT/bench.py" --no-cpu-baseline --no-measure-traffic --map-size 256 --steps 1000 --warmup 100 --min-time 0.5 --no-scene) > $O/trace256.log 2>&1
+(top=$PWD; cd "$TMPDIR" && timeout 900 rocprofv3 --kernel-trace --stats -d "$top/$O/trace256" -o t -- python "$top/bench.py" --full --no-cpu-baseline --no-measure-traffic --map-size 256 --steps 1000 --warmup 100 --min-time 0.5 --no-scene) > $O/trace256.log 2>&1
 python scripts/rocprof_summary.py $O/trace256 $O/kernel_trace_256x4.txt; head -8 $O/kernel_trace_256x4.txt | cut -c1-150
 fi
 if want pmc; then
@@ -68,7 +68,7 @@ python scripts/rocprof_summary.py $O/scene_trace $O/scene_kernel_trace_144hz.txt
 fi
 if want rehearsal; then
 # the N > 1 rank code on the one GPU of the box (gloo, both ranks on GPU 0: control flow only, the numbers mean nothing)
-timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 20 --warmup 5 --backend gloo --share-gpu > $O/rehearsal_2rank.json 2> $O/rehearsal_2rank.err; tail -c 600 $O/rehearsal_2rank.json
+timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 2 --steps 20 --warmup 5 --backend gloo --share-gpu > $O/rehearsal_2rank.json 2> $O/rehearsal_2rank.err; tail -c 600 $O/rehearsal_2rank.json
 fi
 if want hosts; then
 # the compiled C99 host of the device group: two and four shards on the one device, every shard through the peer path; prints the model next to the measurement

@@ -1,6 +1,9 @@
 """Shared helpers of the test-suite: error metrics and oracle drivers."""
 import ctypes as C
+import hashlib
+import json
 import math
+import os
 
 import numpy as np
 
@@ -14,6 +17,20 @@ TOL_F32 = 1e-4
 # foam is RECURRENT FP16 state (fft_unpack.glsl:61): a 1e-7 difference in the Jacobian can flip one FP16
 # rounding, so the pre-quantisation foam may differ by one FP16 ulp of the [0,1] state
 TOL_FOAM_ABS = 2.0 ** -10
+# SHA-256 digests of what the reference's own shaders computed (oracle/_ref), written by tests/golden/make_ref_digests.py: the
+# bit-exact pins hold where the reference checkout is absent too
+REF_DIGESTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_digests.json")
+
+
+def digest(a):
+    """dtype, shape and every byte of an array: two arrays with the same digest are bit-identical"""
+    a = np.ascontiguousarray(a)
+    return hashlib.sha256(f"{a.dtype.str}{a.shape}".encode() + a.tobytes()).hexdigest()
+
+
+def ref_digests(section):
+    with open(REF_DIGESTS) as f:
+        return json.load(f)[section]
 
 
 def relmax(a, b):

@@ -43,12 +43,12 @@ def test_header_is_plain_c():
     assert r.returncode == 0, r.stderr
 
 
-def test_struct_layout_matches_ctypes(lib):
+def test_struct_layout_matches_ctypes(lib, tmp_path):
     src = ('#include <stdio.h>\n#include <stddef.h>\n#include "ocean_waves.h"\nint main(void){printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %d\\n",'
            'sizeof(ow_cascade_params), offsetof(ow_cascade_params, spectrum_seed), offsetof(ow_cascade_params, time),'
            'sizeof(ow_config), offsetof(ow_config, stream), offsetof(ow_config, flags), offsetof(ow_cascade_params, displacement_scale),'
            'offsetof(ow_cascade_params, wind_speed), offsetof(ow_cascade_params, foam_amount), OW_ABI_VERSION);return 0;}\n')
-    exe = "/tmp/ow_layout_check"
+    exe = str(tmp_path / "ow_layout_check")
     subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), "-x", "c", "-", "-o", exe], input=src, text=True, check=True)
     got = [int(v) for v in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split()]
     P, Cfg = _lib.ow_cascade_params, _lib.ow_config

@@ -1,5 +1,6 @@
-"""bench.py's output contract (the driver parses it): ONE JSON line with the keys the task statement names, `roofline` on the bytes the
-launched kernels move, `cpu_baseline` on request; and a loud failure without a GPU."""
+"""bench.py's output contract (the driver parses it): ONE JSON line with the keys the task statement names; a plain run times exactly
+--steps ticks and can dump the maps of its last tick, reproducibly; with --full, `roofline` on the bytes the launched kernels move,
+`cpu_baseline` on request; and a loud failure without a GPU."""
 import json
 import os
 import subprocess
@@ -8,8 +9,8 @@ import sys
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REQUIRED = ["metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config",
-            "roofline"]
+PLAIN = ["metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config"]
+REQUIRED = PLAIN + ["roofline"]
 ROOFLINE = ["bound", "achieved", "peak", "unit", "frac", "traffic", "kernel", "bytes_per_texel", "frac_of_copy_ceiling", "frac_contract_104", "tick"]
 
 
@@ -29,7 +30,7 @@ def test_bench_needs_a_gpu_and_says_so():
 @pytest.mark.parametrize("flags,kernel", [((), "k_tick_pair_c"), (("--map-size", "256"), "k_tick_group_c_lp"), (("--map-size", "2048", "--cascades", "1"), "k_tick_pair_c_split")])
 def test_one_json_line_with_the_contract_keys(flags, kernel):
     # (the headline configuration also measures roofline.traffic itself -- two rocprofv3 --pmc passes; the other two quote the profiling visit's figure)
-    r = run_bench("--steps", "40", "--warmup", "5", "--min-time", "0.05", "--cpu-seconds", "1", *flags, *(() if not flags else ("--no-measure-traffic",)))
+    r = run_bench("--full", "--steps", "40", "--warmup", "5", "--min-time", "0.05", "--cpu-seconds", "1", *flags, *(() if not flags else ("--no-measure-traffic",)))
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -100,6 +101,37 @@ def test_one_json_line_with_the_contract_keys(flags, kernel):
 
 
 @pytest.mark.gpu
+def test_plain_run_times_exactly_the_steps_and_dumps_the_same_maps_every_time(tmp_path):
+    """A plain run: one region of exactly --steps ticks, the headline keys and nothing measured beside them; --dump-outputs writes the maps
+    of the last timed tick as float32 (a seeded sample of 2^20 texels at 1024^2 x 4, within 64 MB), the same bytes from run to run."""
+    import numpy as np
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"out{i}"
+        r = run_bench("--gpus", "1", "--steps", "300", "--warmup", "20", "--dump-outputs", str(d))
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        j = json.loads(lines[0])
+        for k in PLAIN:
+            assert k in j, k
+        assert j["steps"] == 300 and j["warmup"] == 20 and j["repeats"] == 1 and j["timed_ticks_per_region"] == 300 and j["full"] is False
+        assert j["unit"] == "maps/s" and j["higher_is_better"] is True and j["dtype"] == "f32" and j["value"] > 0
+        assert abs(j["value"] - 4 * 1000.0 / j["ms_per_step"]) / j["value"] < 1e-3
+        assert abs(j["timed_seconds"] - 300 * j["ms_per_step"] * 1e-3) < 1e-3 * j["timed_seconds"] + 1e-4
+        for k in ("roofline", "cpu_baseline", "interleaving", "gpu_vs_cpu"):
+            assert k not in j, k
+        files = {f: np.load(d / f) for f in sorted(os.listdir(d))}
+        assert set(files) == {"displacement.npy", "normal.npy", "sample_texel_index.npy"}
+        assert sum((d / f).stat().st_size for f in files) <= 64 << 20
+        assert files["displacement.npy"].shape == files["normal.npy"].shape == (1 << 20, 4) and files["normal.npy"].dtype == np.float32
+        assert np.isfinite(files["displacement.npy"]).all() and np.abs(files["displacement.npy"]).max() > 0
+        dumps.append(files)
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f
+
+
+@pytest.mark.gpu
 def test_two_rank_rehearsal_carries_the_scaling_references(tmp_path):
     """The N > 1 rank code on the ONE GPU of the box (gloo, both ranks on GPU 0: control flow only, the numbers mean nothing): the default
     is the strong-scaling series of BASELINE config C4 (8 cascades shared out: 4 per GPU at N = 2), the gather keeps its cadence inside a
@@ -109,7 +141,7 @@ def test_two_rank_rehearsal_carries_the_scaling_references(tmp_path):
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-                        os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--min-time", "0.05", "--backend", "gloo", "--share-gpu",
+                        os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "20", "--warmup", "5", "--min-time", "0.05", "--backend", "gloo", "--share-gpu",
                         "--prime-ms", "50"], capture_output=True, text=True, cwd=ROOT, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

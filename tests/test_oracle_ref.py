@@ -1,8 +1,10 @@
 """Pins the hand-written CPU oracle (oracle/ow_oracle.c) to the reference itself.
 
 1. against oracle/_ref/libglsl_ref.so -- the reference's OWN six compute shaders compiled as C++ through
-   oracle/glsl_shim.h (built only where /root/reference exists; the .so travels with the working tree):
-   every stage BIT-exact (spectrum texture, butterfly table, fft_buffer, RGBA16F maps, foam recurrence);
+   oracle/glsl_shim.h (built only where the reference checkout exists): every stage BIT-exact (spectrum texture,
+   butterfly table, fft_buffer, RGBA16F maps, foam recurrence) -- against the SHA-256 digests of those stages
+   committed in tests/golden/ref_digests.json (tests/golden/make_ref_digests.py) always, and against the live
+   build as well where it is there;
 2. against tests/golden/*.npz, generated from (1) by tests/golden/make_golden.py and committed: BIT-exact;
 3. against identities that share no code with either (NumPy FP64): the row pass is N*ifft, the two passes
    are (N^2 * ifft2)^T, the f16 conversion is IEEE RTE.
@@ -21,22 +23,46 @@ from oracle import ref as R
 GOLDEN = sorted(glob.glob(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_*.npz")))
 
 
-@pytest.mark.skipif(not R.available(), reason="oracle/_ref/libglsl_ref.so not built (needs the reference checkout)")
+def ref_stages(c):
+    """the stages test 1 pins, of an oracle generator (cascade 0) or of a RefCascade: the same arrays either way"""
+    if isinstance(c, R.RefCascade):
+        return {"spectrum": c.spectrum, "fft1": c.fft[1], "displacement": c.displacement, "normal": c.normal}
+    return {"spectrum": c.spectrum(0), "fft1": c.fft_half1(0), "displacement": c.displacement(0), "normal": c.normal(0)}
+
+
+def assert_bit_exact(got, want):
+    assert np.array_equal(got["spectrum"].view(np.uint32), want["spectrum"].view(np.uint32))    # spectrum_compute.glsl
+    assert np.array_equal(got["fft1"].view(np.uint32), want["fft1"].view(np.uint32))            # modulate + fft + transpose + fft
+    assert np.array_equal(got["displacement"], want["displacement"])                            # fft_unpack.glsl
+    assert np.array_equal(got["normal"], want["normal"])                                        # incl. the FP16 foam recurrence
+
+
+def stage_digests(c):
+    return {k: H.digest(v) for k, v in ref_stages(c).items()}
+
+
 # 512^2 and 1024^2 (the reference's default size, water.gd:38; 10 stages of fft_compute.glsl:47-58): the 1024-invocation
-# workgroups run as fibers, ~15 s and ~40 s per frame -- one frame each
-@pytest.mark.parametrize("n,ci,frames", [(128, 0, 3), (128, 3, 2), (256, 2, 1), (512, 1, 1), (1024, 2, 1)])
+# workgroups run as fibers, ~15 s and ~40 s per frame -- one frame each (where the live build is there)
+CASCADE_CASES = [(128, 0, 3), (128, 3, 2), (256, 2, 1), (512, 1, 1), (1024, 2, 1)]
+
+
+@pytest.mark.parametrize("n,ci,frames", CASCADE_CASES)
 def test_oracle_is_bit_exact_against_the_reference_shaders(n, ci, frames):
-    rc = R.RefCascade(n, cascade_preset(ci))
+    want = H.ref_digests("cascade")[f"n{n}_c{ci}"]
+    rc = R.RefCascade(n, cascade_preset(ci)) if R.available() else None
     g = H.oracle_generator(n, [ci])
-    assert np.array_equal(rc.butterfly.view(np.uint32), O.fft_butterfly(n).view(np.uint32))  # fft_butterfly.glsl
-    for _ in range(frames):
-        rc.update(UPDATE_DELTA)
+    assert H.digest(O.fft_butterfly(n)) == want["butterfly"]                                    # fft_butterfly.glsl
+    if rc is not None:
+        assert np.array_equal(rc.butterfly.view(np.uint32), O.fft_butterfly(n).view(np.uint32))
+    assert len(want["frames"]) == frames
+    for f in range(frames):
         g.update_all(UPDATE_DELTA)
-        assert rc.time == g.params[0].time
-        assert np.array_equal(rc.spectrum.view(np.uint32), g.spectrum(0).view(np.uint32))      # spectrum_compute.glsl
-        assert np.array_equal(rc.fft[1].view(np.uint32), g.fft_half1(0).view(np.uint32))       # modulate + fft + transpose + fft
-        assert np.array_equal(rc.displacement, g.displacement(0))                                # fft_unpack.glsl
-        assert np.array_equal(rc.normal, g.normal(0))                                            # incl. the FP16 foam recurrence
+        assert g.params[0].time == want["frames"][f]["time"]
+        assert stage_digests(g) == {k: v for k, v in want["frames"][f].items() if k != "time"}
+        if rc is not None:
+            rc.update(UPDATE_DELTA)
+            assert rc.time == g.params[0].time
+            assert_bit_exact(ref_stages(g), ref_stages(rc))
 
 
 def _edge_cases():
@@ -44,21 +70,24 @@ def _edge_cases():
     return sorted(edge_presets().items())
 
 
-@pytest.mark.skipif(not R.available(), reason="oracle/_ref/libglsl_ref.so not built (needs the reference checkout)")
+EDGE_FRAMES = 2
+
+
 @pytest.mark.parametrize("name,preset", _edge_cases(), ids=[k for k, _ in _edge_cases()])
 def test_oracle_is_bit_exact_at_the_edges_of_the_parameter_ranges(name, preset):
     """range ends of every exported parameter, non-square tiles, wrapping seeds, t = 0 and the largest phases"""
     n = 128
-    rc = R.RefCascade(n, preset)
+    want = H.ref_digests("edge")[name]
+    rc = R.RefCascade(n, preset) if R.available() else None
     g = O.Generator(n, 1, DEPTH)
     H.set_params(g.params[0], preset)
-    for _ in range(2):
-        rc.update(UPDATE_DELTA)
+    for _ in range(EDGE_FRAMES):
         g.update_all(UPDATE_DELTA)
-    assert np.array_equal(rc.spectrum.view(np.uint32), g.spectrum(0).view(np.uint32))
-    assert np.array_equal(rc.fft[1].view(np.uint32), g.fft_half1(0).view(np.uint32))
-    assert np.array_equal(rc.displacement, g.displacement(0))
-    assert np.array_equal(rc.normal, g.normal(0))
+        if rc is not None:
+            rc.update(UPDATE_DELTA)
+    assert stage_digests(g) == want
+    if rc is not None:
+        assert_bit_exact(ref_stages(g), ref_stages(rc))
     assert np.isfinite(g.spectrum(0)).all()
 
 

@@ -41,13 +41,8 @@ FIELDS_PINNED = ["displacement", "gradient", "foam", "normal_factor", "foam_fact
                  "gradient_fragment", "foam_fragment"]
 
 
-@pytest.mark.skipif(not R.available(), reason="oracle/_ref/libglsl_ref.so not built (needs the reference checkout)")
-@pytest.mark.parametrize("case", ["random_maps", "generated_maps", "spray_active", "fine_cascades"])
-def test_oracle_sampling_is_bit_exact_against_the_reference_shader_text(case):
-    """owo_sample_surface against the reference's OWN statements: cubic_weights / texture_bicubic (water.gdshader:41-68), the
-    cascade loops of vertex() (:31-37) and fragment() (:72-82), the particle shader's spawn decision
-    (sea_spray_particle.gdshader:80-89) and displacement sum (:103-107), compiled from the .gdshader files through
-    oracle/glsl_shim.h (texture() = GL_LINEAR + GL_REPEAT with exact weights, defined there)."""
+def sampling_case(case):
+    """maps, scales and query points of one case of the test below (tests/golden/make_ref_digests.py samples the same)"""
     sc = SCALES3
     if case == "random_maps":
         d, m = random_maps(3, 64)
@@ -63,18 +58,38 @@ def test_oracle_sampling_is_bit_exact_against_the_reference_shader_text(case):
             g.update_all(UPDATE_DELTA)
         d = np.stack([g.displacement(i) for i in range(3)])
         m = np.stack([g.normal(i) for i in range(3)])
-    xz = query_points(3000, seed=11)
+    return d, m, sc, query_points(3000, seed=11)
+
+
+def ref_sampling_digests(r, dp):
+    """what the reference's shader text computed for one case: FIELDS_PINNED and the particle shader's displacement sum"""
+    return {**{f: H.digest(r[f]) for f in FIELDS_PINNED}, "particle_displacement": H.digest(dp)}
+
+
+@pytest.mark.parametrize("case", ["random_maps", "generated_maps", "spray_active", "fine_cascades"])
+def test_oracle_sampling_is_bit_exact_against_the_reference_shader_text(case):
+    """owo_sample_surface against the reference's OWN statements: cubic_weights / texture_bicubic (water.gdshader:41-68), the
+    cascade loops of vertex() (:31-37) and fragment() (:72-82), the particle shader's spawn decision
+    (sea_spray_particle.gdshader:80-89) and displacement sum (:103-107), compiled from the .gdshader files through
+    oracle/glsl_shim.h (texture() = GL_LINEAR + GL_REPEAT with exact weights, defined there).  Held to the digests of that
+    build's results committed in tests/golden/ref_digests.json, and to the live build where the reference checkout exists."""
+    d, m, sc, xz = sampling_case(case)
     o = O.sample_surface(d, m, sc, xz)
-    r, dp = R.sample_surface(d, m, sc, xz)
-    for f in FIELDS_PINNED:
-        assert np.array_equal(o[f].view(np.uint32), r[f].view(np.uint32)), f
+    want = H.ref_digests("sampling")[case]
     # the particle shader's own displacement sum (:103-107) is the vertex shader's (:31-37)
-    assert np.array_equal(dp.view(np.uint32), o["displacement"].view(np.uint32))
+    assert ref_sampling_digests(o, o["displacement"]) == want
+    if R.available():
+        r, dp = R.sample_surface(d, m, sc, xz)
+        for f in FIELDS_PINNED:
+            assert np.array_equal(o[f].view(np.uint32), r[f].view(np.uint32)), f
+        assert np.array_equal(dp.view(np.uint32), o["displacement"].view(np.uint32))
     if case == "spray_active":
         assert 0 < o["spray_active"].sum() < len(xz)
     if case == "fine_cascades":  # gradient_scaled = the bilinear operand of water.gdshader:81's mix: pinned where the mix factor is 1
-        assert np.array_equal(o["gradient_scaled"].view(np.uint32), r["gradient_fragment"].view(np.uint32))
-        assert np.array_equal(o["foam"].view(np.uint32), r["foam_fragment"].view(np.uint32))
+        assert H.digest(o["gradient_scaled"]) == want["gradient_fragment"] and H.digest(o["foam"]) == want["foam_fragment"]
+        if R.available():
+            assert np.array_equal(o["gradient_scaled"].view(np.uint32), r["gradient_fragment"].view(np.uint32))
+            assert np.array_equal(o["foam"].view(np.uint32), r["foam_fragment"].view(np.uint32))
 
 
 def test_oracle_sampling_agrees_with_fp64_consumer_view():
