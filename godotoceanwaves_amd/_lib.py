@@ -20,6 +20,7 @@ OW_FLAG_GROUP_P1_LP, OW_FLAG_GROUP_P1_COMPACT, OW_FLAG_GROUP_P2_PLAIN, OW_FLAG_G
 OW_FLAG_ALWAYS_REGENERATE_SPECTRUM = 0x1000
 OW_FLAG_LAZY_SCRATCH = 0x2000
 OW_FLAG_SINGLE_STREAM = 0x4000
+OW_QUERY_DISTANCE_FALLOFF = 1
 OW_OK, OW_ERR_INVALID, OW_ERR_NO_DEVICE, OW_ERR_HIP, OW_ERR_NOMEM, OW_ERR_STATE = range(6)
 
 
@@ -69,6 +70,26 @@ class ow_group_link(C.Structure):
                 "link": self.LINK_TYPES.get(self.link_type, str(self.link_type)), "hops": self.hops, "staged_path": bool(self.staged_path)}
 
 
+class ow_surface_sample(C.Structure):
+    """struct ow_surface_sample (64 bytes): what the water / spray shaders read at a world point"""
+    _fields_ = [("displacement", C.c_float * 3), ("gradient", C.c_float * 2), ("gradient_scaled", C.c_float * 2), ("foam", C.c_float),
+                ("normal_factor", C.c_float), ("foam_factor", C.c_float), ("scale_factor", C.c_float), ("spray_active", C.c_int32),
+                ("gradient_fragment", C.c_float * 2), ("foam_fragment", C.c_float), ("reserved", C.c_float)]
+
+
+class ow_query_options(C.Structure):
+    """struct ow_query_options (32 bytes); zeros = the defaults (16 iterations, 1e-3 m, no distance falloff)"""
+    _fields_ = [("max_iterations", C.c_int32), ("tolerance", C.c_float), ("flags", C.c_uint32), ("falloff_center_xz", C.c_float * 2),
+                ("reserved", C.c_uint32 * 3)]
+
+
+class ow_surface_query(C.Structure):
+    """struct ow_surface_query (128 bytes): the water above a world point, ow_surface_sample embedded at offset 64"""
+    _fields_ = [("p", C.c_float * 2), ("residual", C.c_float), ("iterations", C.c_int32), ("evaluations", C.c_int32),
+                ("converged", C.c_int32), ("falloff", C.c_float), ("height", C.c_float), ("normal", C.c_float * 3),
+                ("world_xz", C.c_float * 2), ("reserved", C.c_int32 * 3), ("sample", ow_surface_sample)]
+
+
 # every symbol include/ocean_waves.h declares: (restype, argtypes)
 _P = C.POINTER
 SIGNATURES = {
@@ -97,6 +118,8 @@ SIGNATURES = {
     "ow_readback_begin": (C.c_int, [C.c_void_p, C.c_uint32]),
     "ow_readback_wait": (C.c_int, [C.c_void_p, C.c_int32, _P(C.c_void_p), _P(C.c_void_p)]),
     "ow_sample_surface": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "ow_query_surface": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, _P(ow_query_options), C.c_void_p]),
+    "ow_query_surface_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, _P(ow_query_options), C.c_void_p]),
     "ow_get_maps_f32": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
     "ow_get_spectrum": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "ow_get_intermediate": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
@@ -124,6 +147,7 @@ SIGNATURES = {
     "ow_group_get_device_ptrs": (C.c_int, [C.c_void_p, _P(C.c_void_p), _P(C.c_void_p), _P(C.c_size_t)]),
     "ow_group_get_maps": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "ow_group_sample_surface": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "ow_group_query_surface": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, _P(ow_query_options), C.c_void_p]),
     "ow_export_maps": (C.c_int, [C.c_void_p, _P(C.c_int32), _P(C.c_int32), _P(C.c_size_t)]),
     "ow_import_buffer": (C.c_int, [C.c_int32, C.c_int32, C.c_size_t, C.c_size_t, _P(C.c_void_p), _P(C.c_void_p)]),
     "ow_release_buffer": (None, [C.c_void_p]),

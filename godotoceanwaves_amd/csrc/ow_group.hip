@@ -111,7 +111,7 @@ struct ow_group {
     uint32_t faulted_shards = 0;
     float last_copy_ms = 0.0f;
     float *query_xz = nullptr;
-    ow::SurfaceSample *query_out = nullptr;
+    void *query_out = nullptr;  // query_capacity records of either kind (ow_group_sample_surface / ow_group_query_surface)
     int query_capacity = 0;
 };
 
@@ -483,8 +483,11 @@ ow_status ow_group_get_maps(ow_group *g, int32_t cascade, void *disp, void *norm
     return st;
 }
 
-ow_status ow_group_sample_surface(ow_group *g, const float *xz, int32_t count, const float *map_scales, int32_t num_cascades, ow_surface_sample *out) {
-    static_assert(sizeof(ow_surface_sample) == sizeof(ow::SurfaceSample), "record layout");
+namespace {
+// the common body of ow_group_sample_surface / ow_group_query_surface: checks, grow-only scratch on the root device, one launch on the
+// root stream over the gathered arrays, the records back to the host.  qp == nullptr: the sampling kernel.
+ow_status group_point_query(ow_group *g, const float *xz, int32_t count, const float *map_scales, int32_t num_cascades, const ow::QueryParams *qp,
+                            void *out) {
     if (!g) return fail(OW_ERR_INVALID, "null group");
     if (count < 0) return fail(OW_ERR_INVALID, "count must be >= 0");
     if (num_cascades < 1 || num_cascades > std::min(g->total, OW_MAX_CASCADES))
@@ -494,6 +497,7 @@ ow_status ow_group_sample_surface(ow_group *g, const float *xz, int32_t count, c
     if (ow_status st = refuse_faulted_layers(g, 0, num_cascades); st != OW_OK) return st;
     if (count == 0) return OW_OK;
     if (!xz || !map_scales || !out) return fail(OW_ERR_INVALID, "null argument");
+    const size_t rec = qp ? sizeof(ow::SurfaceQuery) : sizeof(ow::SurfaceSample);
     int caller_dev = -1;
     (void)hipGetDevice(&caller_dev);
     auto run = [&]() -> ow_status {
@@ -505,7 +509,7 @@ ow_status ow_group_sample_surface(ow_group *g, const float *xz, int32_t count, c
             g->query_out = nullptr;
             g->query_capacity = 0;
             const int cap = std::max(count, 4096);
-            if (hipMalloc((void **)&g->query_xz, (size_t)cap * 2 * sizeof(float)) != hipSuccess || hipMalloc((void **)&g->query_out, (size_t)cap * sizeof(ow::SurfaceSample)) != hipSuccess)
+            if (hipMalloc((void **)&g->query_xz, (size_t)cap * 2 * sizeof(float)) != hipSuccess || hipMalloc(&g->query_out, (size_t)cap * sizeof(ow::SurfaceQuery)) != hipSuccess)
                 return fail(OW_ERR_NOMEM, "hipMalloc failed for %d query points", cap);
             g->query_capacity = cap;
         }
@@ -514,17 +518,36 @@ ow_status ow_group_sample_surface(ow_group *g, const float *xz, int32_t count, c
         std::memcpy(sc.s, map_scales, (size_t)num_cascades * 4 * sizeof(float));
         ow::DeviceBuffers buf;
         std::memset(&buf, 0, sizeof(buf));
-        buf.disp = (ow::u16x4 *)g->gdisp;  // the sampling kernel reads the two array textures only
+        buf.disp = (ow::u16x4 *)g->gdisp;  // the point kernels read the two array textures only
         buf.norm = (ow::u16x4 *)g->gnorm;
         OW_HIP(hipMemcpyAsync(g->query_xz, xz, (size_t)count * 2 * sizeof(float), hipMemcpyHostToDevice, g->root_stream));
-        OW_HIP(ow::launch_sample_surface(g->n, num_cascades, buf, g->query_xz, count, sc, g->query_out, g->root_stream));
-        OW_HIP(hipMemcpyAsync(out, g->query_out, (size_t)count * sizeof(ow::SurfaceSample), hipMemcpyDeviceToHost, g->root_stream));
+        if (qp)
+            OW_HIP(ow::launch_query_surface(g->n, num_cascades, buf, g->query_xz, count, sc, *qp, (ow::SurfaceQuery *)g->query_out, g->root_stream));
+        else
+            OW_HIP(ow::launch_sample_surface(g->n, num_cascades, buf, g->query_xz, count, sc, (ow::SurfaceSample *)g->query_out, g->root_stream));
+        OW_HIP(hipMemcpyAsync(out, g->query_out, (size_t)count * rec, hipMemcpyDeviceToHost, g->root_stream));
         OW_HIP(hipStreamSynchronize(g->root_stream));
         return OW_OK;
     };
     const ow_status st = run();
     if (caller_dev >= 0) (void)hipSetDevice(caller_dev);
     return st;
+}
+}  // namespace
+
+ow_status ow_group_sample_surface(ow_group *g, const float *xz, int32_t count, const float *map_scales, int32_t num_cascades, ow_surface_sample *out) {
+    static_assert(sizeof(ow_surface_sample) == sizeof(ow::SurfaceSample), "record layout");
+    return group_point_query(g, xz, count, map_scales, num_cascades, nullptr, out);
+}
+
+ow_status ow_group_query_surface(ow_group *g, const float *xz, int32_t count, const float *map_scales, int32_t num_cascades,
+                                 const ow_query_options *opts, ow_surface_query *out) {
+    static_assert(sizeof(ow_surface_query) == sizeof(ow::SurfaceQuery), "record layout");
+    ow::QueryParams qp;
+    if (g) {  // a null group is reported first, as by the sampling form
+        if (ow_status st = ow::resolve_query_options(opts, &qp); st != OW_OK) return st;
+    }
+    return group_point_query(g, xz, count, map_scales, num_cascades, &qp, out);
 }
 
 }  // extern "C"

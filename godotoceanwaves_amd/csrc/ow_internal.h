@@ -17,6 +17,9 @@ void set_last_error(const char *message);
 ow_status validate_records(const ow_cascade_params *params, int count, double delta);
 // the context's device status word without synchronising (ow_runtime.hip)
 ow_status poll_status(ow_context *c);
+// ow_query_options (NULL = defaults) -> the solver's settings, OW_ERR_INVALID for a value out of range (ow_runtime.hip)
+struct QueryParams;
+ow_status resolve_query_options(const ow_query_options *opts, QueryParams *qp);
 
 }  // namespace ow
 

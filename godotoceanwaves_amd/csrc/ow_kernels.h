@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "ow_device.h"
+#include "ow_surface.h"
 
 namespace ow {
 
@@ -30,23 +31,11 @@ struct LaunchTiming {
     hipEvent_t start = nullptr, stop = nullptr;
 };
 
-// consumer-side sampling (ow_consumer.hip); SurfaceSample is layout-identical to ow_surface_sample in include/ocean_waves.h
-struct SurfaceScales {
-    float s[8][4];  // map_scales[i] = (1/tile_length.x, 1/tile_length.y, displacement_scale, normal_scale), water.gd:105-109
-};
-struct SurfaceSample {
-    float displacement[3];
-    float gradient[2];
-    float gradient_scaled[2];
-    float foam;
-    float normal_factor, foam_factor, scale_factor;
-    int32_t spray_active;
-    float gradient_fragment[2];
-    float foam_fragment;
-    float reserved;
-};
+// consumer-side sampling and the inverse query (ow_consumer.hip; per-point code and records in ow_surface.h)
 hipError_t launch_sample_surface(int n, int cascades, const DeviceBuffers &buf, const float *xz_dev, int count,
                                  const SurfaceScales &scales, SurfaceSample *out_dev, hipStream_t s);
+hipError_t launch_query_surface(int n, int cascades, const DeviceBuffers &buf, const float *xz_dev, int count, const SurfaceScales &scales,
+                                const QueryParams &qp, SurfaceQuery *out_dev, hipStream_t s);
 
 bool supported_map_size(int n);
 int kernel_family(int n, int slots, int mode);  // 1 standard, 2 layer-parallel, 3 compact: what launch_pass1/2 will use

@@ -156,9 +156,9 @@ struct ow_context {
     ow::u16x4 *snap_dev = nullptr, *snap_host = nullptr;  // [2 maps][layers][N][N]
     hipEvent_t snap_ready[OW_MAX_CASCADES] = {}, copy_done[OW_MAX_CASCADES] = {};
     bool copy_pending[OW_MAX_CASCADES] = {};
-    // ow_sample_surface scratch (grow-only)
+    // ow_sample_surface / ow_query_surface scratch (grow-only): query_capacity points in, as many records of the larger kind out
     float *query_xz = nullptr;
-    ow::SurfaceSample *query_out = nullptr;
+    void *query_out = nullptr;
     int query_capacity = 0;
 };
 
@@ -1983,34 +1983,115 @@ ow_status ow_readback_wait(ow_context *c, int32_t cascade, const void **disp, co
     return OW_OK;
 }
 
-ow_status ow_sample_surface(ow_context *c, const float *xz, int32_t count, const float *map_scales, int32_t num_cascades,
-                            ow_surface_sample *out) {
-    static_assert(sizeof(ow_surface_sample) == sizeof(ow::SurfaceSample) && sizeof(ow_surface_sample) == 64, "record layout");
+}  // extern "C"
+
+namespace {
+// the grow-only scratch of the synchronous point queries: `count` points in, `count` records of either kind out
+ow_status query_scratch(ow_context *c, int count) {
+    if (count <= c->query_capacity) return OW_OK;
+    (void)hipFree(c->query_xz);
+    (void)hipFree(c->query_out);
+    c->query_xz = nullptr;
+    c->query_out = nullptr;
+    c->query_capacity = 0;
+    const int cap = std::max(count, 4096);
+    static_assert(sizeof(ow::SurfaceQuery) >= sizeof(ow::SurfaceSample), "the record buffer holds either kind");
+    if (hipMalloc((void **)&c->query_xz, (size_t)cap * 2 * sizeof(float)) != hipSuccess ||
+        hipMalloc(&c->query_out, (size_t)cap * sizeof(ow::SurfaceQuery)) != hipSuccess)
+        return fail(OW_ERR_NOMEM, "hipMalloc failed for %d query points", cap);
+    c->query_capacity = cap;
+    return OW_OK;
+}
+
+// the argument checks ow_sample_surface makes, shared by the two forms of ow_query_surface (count == 0 is fine and does nothing)
+ow_status check_point_query(const ow_context *c, int32_t count, int32_t num_cascades) {
     if (!c) return fail(OW_ERR_INVALID, "null context");
     if (count < 0) return fail(OW_ERR_INVALID, "count must be >= 0");
     if (num_cascades < 1 || num_cascades > c->cascades) return fail(OW_ERR_INVALID, "num_cascades %d outside [1,%d]", num_cascades, c->cascades);
-    if (count == 0) return OW_OK;
-    if (!xz || !map_scales || !out) return fail(OW_ERR_INVALID, "null argument");
-    OW_HIP(hipSetDevice(c->device));
-    if (count > c->query_capacity) {
-        (void)hipFree(c->query_xz);
-        (void)hipFree(c->query_out);
-        c->query_xz = nullptr;
-        c->query_out = nullptr;
-        c->query_capacity = 0;
-        const int cap = std::max(count, 4096);
-        if (hipMalloc((void **)&c->query_xz, (size_t)cap * 2 * sizeof(float)) != hipSuccess ||
-            hipMalloc((void **)&c->query_out, (size_t)cap * sizeof(ow::SurfaceSample)) != hipSuccess)
-            return fail(OW_ERR_NOMEM, "hipMalloc failed for %d query points", cap);
-        c->query_capacity = cap;
-    }
+    return OW_OK;
+}
+
+ow::SurfaceScales surface_scales(const float *map_scales, int num_cascades) {
     ow::SurfaceScales sc;
     std::memset(&sc, 0, sizeof(sc));
     std::memcpy(sc.s, map_scales, (size_t)num_cascades * 4 * sizeof(float));
+    return sc;
+}
+}  // namespace
+
+namespace ow {
+ow_status resolve_query_options(const ow_query_options *o, QueryParams *qp) {
+    qp->max_iterations = kQueryDefaultIterations;
+    qp->tolerance = kQueryDefaultTolerance;
+    qp->falloff = 0;
+    qp->center[0] = qp->center[1] = 0.0f;
+    if (!o) return OW_OK;
+    if (o->max_iterations < 0 || o->max_iterations > kQueryMaxIterations)
+        return fail(OW_ERR_INVALID, "max_iterations %d outside [0,%d]", o->max_iterations, kQueryMaxIterations);
+    if (o->flags & ~OW_QUERY_DISTANCE_FALLOFF) return fail(OW_ERR_INVALID, "unknown query flags 0x%x", o->flags);
+    if (!std::isfinite(o->tolerance)) return fail(OW_ERR_INVALID, "tolerance is not finite");
+    if (o->max_iterations > 0) qp->max_iterations = o->max_iterations;
+    if (o->tolerance > 0.0f) qp->tolerance = o->tolerance;
+    if (o->flags & OW_QUERY_DISTANCE_FALLOFF) {
+        if (!std::isfinite(o->falloff_center_xz[0]) || !std::isfinite(o->falloff_center_xz[1]))
+            return fail(OW_ERR_INVALID, "falloff_center_xz is not finite");
+        qp->falloff = 1;
+        qp->center[0] = o->falloff_center_xz[0];
+        qp->center[1] = o->falloff_center_xz[1];
+    }
+    return OW_OK;
+}
+}  // namespace ow
+
+extern "C" {
+
+ow_status ow_sample_surface(ow_context *c, const float *xz, int32_t count, const float *map_scales, int32_t num_cascades,
+                            ow_surface_sample *out) {
+    static_assert(sizeof(ow_surface_sample) == sizeof(ow::SurfaceSample) && sizeof(ow_surface_sample) == 64, "record layout");
+    if (ow_status st = check_point_query(c, count, num_cascades); st != OW_OK) return st;
+    if (count == 0) return OW_OK;
+    if (!xz || !map_scales || !out) return fail(OW_ERR_INVALID, "null argument");
+    OW_HIP(hipSetDevice(c->device));
+    if (ow_status st = query_scratch(c, count); st != OW_OK) return st;
+    const ow::SurfaceScales sc = surface_scales(map_scales, num_cascades);
     OW_HIP(hipMemcpyAsync(c->query_xz, xz, (size_t)count * 2 * sizeof(float), hipMemcpyHostToDevice, main_stream(c)));
-    OW_HIP(ow::launch_sample_surface(c->n, num_cascades, c->buf, c->query_xz, count, sc, c->query_out, main_stream(c)));
+    OW_HIP(ow::launch_sample_surface(c->n, num_cascades, c->buf, c->query_xz, count, sc, (ow::SurfaceSample *)c->query_out, main_stream(c)));
     OW_HIP(hipMemcpyAsync(out, c->query_out, (size_t)count * sizeof(ow::SurfaceSample), hipMemcpyDeviceToHost, main_stream(c)));
     return sync_stream(c, (1u << num_cascades) - 1u);
+}
+
+ow_status ow_query_surface(ow_context *c, const float *xz, int32_t count, const float *map_scales, int32_t num_cascades,
+                           const ow_query_options *opts, ow_surface_query *out) {
+    static_assert(sizeof(ow_surface_query) == sizeof(ow::SurfaceQuery) && offsetof(ow_surface_query, sample) == offsetof(ow::SurfaceQuery, sample) &&
+                      offsetof(ow_surface_query, world_xz) == offsetof(ow::SurfaceQuery, world_xz),
+                  "record layout");
+    if (ow_status st = check_point_query(c, count, num_cascades); st != OW_OK) return st;
+    ow::QueryParams qp;
+    if (ow_status st = ow::resolve_query_options(opts, &qp); st != OW_OK) return st;
+    if (count == 0) return OW_OK;
+    if (!xz || !map_scales || !out) return fail(OW_ERR_INVALID, "null argument");
+    OW_HIP(hipSetDevice(c->device));
+    if (ow_status st = query_scratch(c, count); st != OW_OK) return st;
+    const ow::SurfaceScales sc = surface_scales(map_scales, num_cascades);
+    OW_HIP(hipMemcpyAsync(c->query_xz, xz, (size_t)count * 2 * sizeof(float), hipMemcpyHostToDevice, main_stream(c)));
+    OW_HIP(ow::launch_query_surface(c->n, num_cascades, c->buf, c->query_xz, count, sc, qp, (ow::SurfaceQuery *)c->query_out, main_stream(c)));
+    OW_HIP(hipMemcpyAsync(out, c->query_out, (size_t)count * sizeof(ow::SurfaceQuery), hipMemcpyDeviceToHost, main_stream(c)));
+    return sync_stream(c, (1u << num_cascades) - 1u);
+}
+
+ow_status ow_query_surface_async(ow_context *c, const float *xz_dev, int32_t count, const float *map_scales, int32_t num_cascades,
+                                 const ow_query_options *opts, ow_surface_query *out_dev) {
+    if (ow_status st = check_point_query(c, count, num_cascades); st != OW_OK) return st;
+    ow::QueryParams qp;
+    if (ow_status st = ow::resolve_query_options(opts, &qp); st != OW_OK) return st;
+    if (count == 0) return OW_OK;
+    if (!xz_dev || !map_scales || !out_dev) return fail(OW_ERR_INVALID, "null argument");
+    if (ow_status st = refuse_faulted(c, (1u << num_cascades) - 1u); st != OW_OK) return st;
+    OW_HIP(hipSetDevice(c->device));
+    const ow::SurfaceScales sc = surface_scales(map_scales, num_cascades);
+    // main_stream(): behind the second chain's join as well as everything on the context's (or the caller's) stream
+    OW_HIP(ow::launch_query_surface(c->n, num_cascades, c->buf, xz_dev, count, sc, qp, (ow::SurfaceQuery *)out_dev, main_stream(c)));
+    return OW_OK;
 }
 
 ow_status ow_set_normal_map(ow_context *c, int32_t cascade, const void *norm) {

@@ -141,6 +141,16 @@ class WaveGeneratorGroup:
         _lib.check(self._lib.ow_group_sample_surface(self.group, xz.ctypes.data, len(xz), sc.ctypes.data, len(sc), out.ctypes.data))
         return out
 
+    def query_surface(self, world_xz, map_scales, options=None):
+        """WaveGenerator.query_surface over the gathered arrays on the root device"""
+        xz = np.ascontiguousarray(world_xz, np.float32).reshape(-1, 2)
+        sc = np.ascontiguousarray(map_scales, np.float32).reshape(-1, 4)
+        out = np.zeros(len(xz), WaveGenerator.SURFACE_QUERY)
+        o = WaveGenerator.query_options(options)
+        _lib.check(self._lib.ow_group_query_surface(self.group, xz.ctypes.data, len(xz), sc.ctypes.data, len(sc),
+                                                    C.byref(o) if o is not None else None, out.ctypes.data))
+        return out
+
     def free(self):
         if self.group:
             self._lib.ow_group_destroy(self.group)

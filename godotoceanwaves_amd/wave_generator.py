@@ -263,6 +263,54 @@ class WaveGenerator:
         _lib.check(self._lib.ow_sample_surface(self.context, xz.ctypes.data, len(xz), sc.ctypes.data, len(sc), out.ctypes.data))
         return out
 
+    # ---- the water above a world point: p + f(p) D(p) = q solved on the device (include/ocean_waves.h ow_query_surface) ----
+    SURFACE_QUERY = np.dtype([("p", np.float32, 2), ("residual", np.float32), ("iterations", np.int32), ("evaluations", np.int32),
+                              ("converged", np.int32), ("falloff", np.float32), ("height", np.float32), ("normal", np.float32, 3),
+                              ("world_xz", np.float32, 2), ("reserved", np.int32, 3), ("sample", SURFACE_SAMPLE)])
+
+    @staticmethod
+    def query_options(options=None):
+        """None, an _lib.ow_query_options, or a dict of max_iterations / tolerance / falloff_center ((x, z): the camera position
+        of water.gdshader:29's distance falloff) -> ow_query_options, or None for the defaults"""
+        if options is None or isinstance(options, _lib.ow_query_options):
+            return options
+        unknown = set(options) - {"max_iterations", "tolerance", "falloff_center"}
+        if unknown:
+            raise ValueError(f"unknown query options {sorted(unknown)}")
+        o = _lib.ow_query_options(max_iterations=int(options.get("max_iterations", 0)), tolerance=float(options.get("tolerance", 0.0)))
+        if options.get("falloff_center") is not None:
+            o.flags = _lib.OW_QUERY_DISTANCE_FALLOFF
+            o.falloff_center_xz[0], o.falloff_center_xz[1] = (float(v) for v in options["falloff_center"])
+        return o
+
+    def query_surface(self, world_xz, map_scales, options=None):
+        """Where the rendered water is above world points [P][2] (x, z): the undisplaced point p, the residual, convergence, the
+        rendered height and normal, and the full sample_surface record at p.  Returns a structured array (SURFACE_QUERY)."""
+        xz = np.ascontiguousarray(world_xz, np.float32).reshape(-1, 2)
+        sc = np.ascontiguousarray(map_scales, np.float32).reshape(-1, 4)
+        out = np.zeros(len(xz), self.SURFACE_QUERY)
+        o = self.query_options(options)
+        _lib.check(self._lib.ow_query_surface(self.context, xz.ctypes.data, len(xz), sc.ctypes.data, len(sc),
+                                              C.byref(o) if o is not None else None, out.ctypes.data))
+        return out
+
+    def query_surface_async(self, xz_device, map_scales, out_device, options=None, count=None):
+        """The query over DEVICE buffers, enqueued in the generator's stream order without synchronising: xz_device holds 2 * count
+        float32 (x, z pairs), out_device room for count 128-byte records.  Each is anything with a data_ptr() (a torch tensor) or an
+        integer address; count defaults to xz_device.numel() // 2."""
+        def addr(b):
+            return int(b.data_ptr()) if hasattr(b, "data_ptr") else int(b)
+        if count is None:
+            if not hasattr(xz_device, "numel"):
+                raise ValueError("count is needed for a raw device address")
+            count = int(xz_device.numel()) // 2
+        if hasattr(out_device, "numel") and hasattr(out_device, "element_size") and out_device.numel() * out_device.element_size() < count * self.SURFACE_QUERY.itemsize:
+            raise ValueError(f"out_device holds fewer than {count} records of {self.SURFACE_QUERY.itemsize} bytes")
+        sc = np.ascontiguousarray(map_scales, np.float32).reshape(-1, 4)
+        o = self.query_options(options)
+        _lib.check(self._lib.ow_query_surface_async(self.context, addr(xz_device), int(count), sc.ctypes.data, len(sc),
+                                                    C.byref(o) if o is not None else None, addr(out_device)))
+
     def get_push_constants(self, cascade):
         """(spectrum[16], modulate[8], unpack[4]) uint32 words: the reference's push-constant blocks of this cascade's most recent launch"""
         pc = _lib.ow_push_constants()

@@ -315,6 +315,65 @@ typedef struct ow_surface_sample {
 ow_status ow_sample_surface(ow_context *ctx, const float *world_xz, int32_t count, const float *map_scales,
                             int32_t num_cascades, ow_surface_sample *out);
 
+/* Water height at world points: where the RENDERED surface lies above (x, z).  ow_sample_surface reads the maps at the undisplaced
+ * lattice point; the vertex that starts at p is drawn at p + f(p) * D(p) (water.gdshader:27-39), so the surface above q belongs to the p
+ * that solves
+ *     F(p) = p + f(p) * sum_i D_xz,i(p) - q = 0,
+ * D_i the bilinear lookup of layer i at p * map_scales_i.xy times map_scales_i.z, f = 1 or, with OW_QUERY_DISTANCE_FALLOFF, the vertex
+ * shader's min(exp(-(|p - c| - 150) * 0.007), 1) around c = falloff_center_xz (CAMERA_POSITION_WORLD.xz; the water mesh at the origin,
+ * untransformed).  Damped Newton from p = q, the Jacobian from the texels each lookup loads, a steepest-descent (Cauchy) step where the
+ * map folds over (|det J| small); the iterate of smallest |F| is returned.  Nothing returned is NaN or Inf. */
+#define OW_QUERY_DISTANCE_FALLOFF 1u
+typedef struct ow_query_options {
+    int32_t max_iterations;     /* Newton iterations, 0 = the default 16, at most 64 */
+    float tolerance;            /* metres: converged = |F(p)| <= tolerance; <= 0 selects 1e-3 */
+    uint32_t flags;             /* OW_QUERY_* */
+    float falloff_center_xz[2]; /* c of the distance falloff (read with OW_QUERY_DISTANCE_FALLOFF) */
+    uint32_t reserved[3];       /* 0 */
+} ow_query_options;             /* 32 bytes; a NULL pointer = all defaults */
+
+/* One record per query point, 128 bytes, 8-byte aligned:
+ *   offset  0  p[2]            the solved undisplaced point (metres)
+ *           8  residual        |F(p)| in FP32 (metres)
+ *          12  iterations      Newton iterations taken
+ *          16  evaluations     evaluations of F (each reads one bilinear tap per cascade of the displacement array)
+ *          20  converged       1: residual <= tolerance
+ *          24  falloff         f(p) (1 without OW_QUERY_DISTANCE_FALLOFF)
+ *          28  height          f(p) * sample.displacement[1]: the rendered water height above q
+ *          32  normal[3]       normalize(-g.x, 1, -g.y), g = sample.gradient_scaled (water.gdshader:83,90, bilinear, before :89's blend)
+ *          44  world_xz[2]     q as given
+ *          52  reserved[3]
+ *          64  sample          ow_sample_surface at p, the same bits */
+typedef struct ow_surface_query {
+    float p[2];
+    float residual;
+    int32_t iterations;
+    int32_t evaluations;
+    int32_t converged;
+    float falloff;
+    float height;
+    float normal[3];
+    float world_xz[2];
+    int32_t reserved[3];
+    ow_surface_sample sample;
+} ow_surface_query;
+/* the layouts above, checked by the compiler (a static assertion that C99 accepts too) */
+typedef char ow_layout_check_query_options[(sizeof(ow_query_options) == 32) ? 1 : -1];
+typedef char ow_layout_check_surface_query[(sizeof(ow_surface_query) == 128 && offsetof(ow_surface_query, sample) == 64 &&
+                                            offsetof(ow_surface_query, normal) == 32 && offsetof(ow_surface_query, world_xz) == 44) ? 1 : -1];
+
+/* The query at `count` points (host pointers, as ow_sample_surface: world_xz = x0,z0,x1,z1,...; map_scales = 4 floats per cascade),
+ * after everything enqueued so far.  Synchronises; a faulted batch's layers are refused as by ow_sample_surface. */
+ow_status ow_query_surface(ow_context *ctx, const float *world_xz, int32_t count, const float *map_scales, int32_t num_cascades,
+                           const ow_query_options *opts, ow_surface_query *out);
+/* The same with DEVICE pointers on the context's device (world_xz_dev: 2 * count floats, out_dev: count records; map_scales and opts
+ * are host values): enqueued in the context's stream order behind everything enqueued so far -- both chains -- and ahead of whatever
+ * the context enqueues next.  Returns without synchronising, copies nothing and allocates nothing.  On a caller's stream
+ * (ow_config.stream) work the caller enqueues on that stream afterwards sees the records.  Layers already known to be faulted are
+ * refused (OW_ERR_HIP); a device-side failure of a batch the query read is reported by the next synchronising call. */
+ow_status ow_query_surface_async(ow_context *ctx, const float *world_xz_dev, int32_t count, const float *map_scales, int32_t num_cascades,
+                                 const ow_query_options *opts, ow_surface_query *out_dev);
+
 /* ---- several devices: cascades sharded inside one process ---------------------------------------- */
 
 /* Cascades share nothing (wave_generator.gd:65-85 touches no state of another cascade; README.md:77-80), so a node's GPUs
@@ -405,6 +464,9 @@ ow_status ow_group_get_maps(ow_group *group, int32_t cascade, void *displacement
 /* ow_sample_surface over the gathered arrays on the root device: what the consumer's shaders see (num_cascades <= 8 layers from 0). */
 ow_status ow_group_sample_surface(ow_group *group, const float *world_xz, int32_t count, const float *map_scales, int32_t num_cascades,
                                   ow_surface_sample *out);
+/* ow_query_surface over the gathered arrays on the root device (the preconditions of ow_group_sample_surface). */
+ow_status ow_group_query_surface(ow_group *group, const float *world_xz, int32_t count, const float *map_scales, int32_t num_cascades,
+                                 const ow_query_options *opts, ow_surface_query *out);
 
 /* ---- zero-copy hand-off: the maps as dma-buf file descriptors ------------------------------------------------------ */
 

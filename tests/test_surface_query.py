@@ -1,0 +1,470 @@
+"""The water-height query (include/ocean_waves.h ow_query_surface, ow_query_surface_async, ow_group_query_surface): where the rendered
+surface lies above a world point q, i.e. the undisplaced p with p + f(p) D_xz(p) = q, solved per point by damped Newton
+(godotoceanwaves_amd/csrc/ow_surface.h query_point).
+
+CPU: the ABI (header, exports, ctypes, C and C# layouts) and the argument checks without a device; the solver header compiled as plain C++
+(tests/query/query_harness.cpp, g++ -ffp-contract=off) held to an FP64 NumPy twin (tests/query_twin.py) on synthetic and oracle-generated
+maps.  GPU: the device records are those of the CPU build on the same maps, bit for bit (both sides FP32 with contraction off; divide and
+square root correctly rounded; no library transcendental), the embedded sample is ow_sample_surface's, and the asynchronous form is ordered
+behind both chains of a context and ahead of its next work."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import helpers as H
+import query_twin as T
+from godotoceanwaves_amd import _lib, build
+from godotoceanwaves_amd.presets import UPDATE_DELTA, cascade_preset
+from godotoceanwaves_amd.wave_generator import WaveGenerator
+from test_surface_sampling import SCALES3, query_points, random_maps
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "godotoceanwaves_amd", "csrc")
+HERE = os.path.dirname(os.path.abspath(__file__))
+REC = WaveGenerator.SURFACE_QUERY
+NEW_FUNCTIONS = ("ow_query_surface", "ow_query_surface_async", "ow_group_query_surface")
+
+
+# ---- the CPU build of the solver header ---------------------------------------------------------------------------------------------
+
+@pytest.fixture(scope="module")
+def harness(tmp_path_factory):
+    so = str(tmp_path_factory.mktemp("query") / "libquery_harness.so")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unknown-pragmas", "-I", CSRC,
+                    os.path.join(HERE, "query", "query_harness.cpp"), "-o", so], check=True)
+    L = C.CDLL(so)
+    V = C.c_void_p
+    L.harness_record_sizes.argtypes = [C.POINTER(C.c_int)] * 3
+    L.harness_sample.argtypes = [V, V, C.c_int, C.c_int, V, V, C.c_int, V]
+    L.harness_query.argtypes = [V, V, C.c_int, C.c_int, V, V, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.c_float, V]
+    L.harness_exp.argtypes = [V, C.c_int, V]
+    return L
+
+
+def maps_u16(maps):
+    m = np.ascontiguousarray(np.asarray(maps))
+    return m.view(np.uint16) if m.dtype != np.uint16 else m
+
+
+def cpu_query(L, disp, norm, scales, xz, max_iterations=0, tolerance=0.0, falloff_center=None):
+    """the records the CPU build writes, with the options resolved as the runtime resolves ow_query_options"""
+    d, m = maps_u16(disp), maps_u16(norm)
+    sc = np.ascontiguousarray(scales, np.float32)
+    xz = np.ascontiguousarray(xz, np.float32).reshape(-1, 2)
+    out = np.zeros(len(xz), REC)
+    it = max_iterations if max_iterations > 0 else 16
+    tol = tolerance if tolerance > 0 else 1e-3
+    cx, cz = falloff_center if falloff_center is not None else (0.0, 0.0)
+    L.harness_query(d.ctypes.data, m.ctypes.data, d.shape[1], len(sc), sc.ctypes.data, xz.ctypes.data, len(xz), it, tol,
+                    int(falloff_center is not None), cx, cz, out.ctypes.data)
+    return out
+
+
+def cpu_sample(L, disp, norm, scales, xz):
+    d, m = maps_u16(disp), maps_u16(norm)
+    sc = np.ascontiguousarray(scales, np.float32)
+    xz = np.ascontiguousarray(xz, np.float32).reshape(-1, 2)
+    out = np.zeros(len(xz), WaveGenerator.SURFACE_SAMPLE)
+    L.harness_sample(d.ctypes.data, m.ctypes.data, d.shape[1], len(sc), sc.ctypes.data, xz.ctypes.data, len(xz), out.ctypes.data)
+    return out
+
+
+def fp32_slack(disp, scales, p):
+    """how far an FP32 evaluation of |p + f D_xz(p) - q| may sit from the FP64 one at the same p: the texture coordinate p * s * N is
+    rounded twice (2^-23 relative), which moves each cascade's interpolant by that many texels times its largest texel step, plus the
+    rounding of the position and of the sums (a few ulp of |p| and of |D|)"""
+    d = T.as_f64(disp)
+    sc = np.asarray(scales, np.float64)
+    n = d.shape[1]
+    r = np.abs(np.asarray(p, np.float64)).max(axis=1)
+    per_texel = sum(sc[i, 2] * max(np.abs(np.diff(d[i][..., [0, 2]], axis=a)).max() for a in (0, 1)) for i in range(len(sc)))
+    return 2e-5 + r * 2.0 ** -21 + r * sc[:, :2].max() * n * 2.0 ** -22 * per_texel
+
+
+def generated_maps(n, ids, ticks=2):
+    g = H.oracle_generator(n, ids, native=True)
+    for _ in range(ticks):
+        g.update_all(UPDATE_DELTA)
+    d = np.stack([np.asarray(g.displacement(i)) for i in range(len(ids))])
+    m = np.stack([np.asarray(g.normal(i)) for i in range(len(ids))])
+    sc = np.array([(1 / cascade_preset(ci)["tile_length"][0], 1 / cascade_preset(ci)["tile_length"][1], 1.0, 1.0) for ci in ids], np.float32)
+    return maps_u16(d), maps_u16(m), sc
+
+
+def check_against_twin(out, disp, scales, xz, tol=1e-3, center=None):
+    assert all(np.isfinite(out[f]).all() for f in ("p", "residual", "falloff", "height", "normal"))
+    assert all(np.isfinite(out["sample"][f]).all() for f in ("displacement", "gradient", "gradient_scaled", "foam", "gradient_fragment"))
+    r64 = T.residual(disp, scales, out["p"], xz, center)
+    slack = fp32_slack(disp, scales, out["p"])
+    c = out["converged"].astype(bool)
+    assert (r64[c] <= tol + slack[c]).all(), (r64[c] - tol - slack[c]).max()
+    assert (out["residual"][c] <= tol).all()
+    assert (out["residual"][~c] > tol).all()
+    assert (np.abs(out["residual"][~c] - r64[~c]) <= slack[~c]).all()
+    assert np.array_equal(out["world_xz"], np.asarray(xz, np.float32))
+    return c
+
+
+# ---- 1. the ABI ----------------------------------------------------------------------------------------------------------------------
+
+HEADER = open(os.path.join(ROOT, "include", "ocean_waves.h")).read()
+
+
+def test_header_declares_the_query_and_the_library_exports_it():
+    build.build_library()
+    lib = _lib.load()
+    text = re.sub(r"/\*.*?\*/", "", HEADER, flags=re.S)
+    for name in NEW_FUNCTIONS:
+        assert re.search(r"\b%s\s*\(" % name, text), name
+        assert name in _lib.SIGNATURES
+        assert getattr(lib, name)
+    for struct in ("ow_query_options", "ow_surface_query"):
+        assert re.search(r"typedef struct %s \{" % struct, text), struct
+    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    assert set(NEW_FUNCTIONS) <= set(re.findall(r" T (ow_[a-z0-9_]+)", out))
+    assert lib.ow_abi_version() == 4
+
+
+def test_query_structs_agree_in_c_ctypes_numpy_and_the_solver(tmp_path, harness):
+    src = ('#include <stdio.h>\n#include <stddef.h>\n#include "ocean_waves.h"\nint main(void){printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu '
+           '%zu %zu %zu %zu %zu %zu %u\\n", sizeof(ow_query_options), offsetof(ow_query_options, tolerance), offsetof(ow_query_options, flags),'
+           'offsetof(ow_query_options, falloff_center_xz), offsetof(ow_query_options, reserved), sizeof(ow_surface_query), _Alignof(ow_surface_query),'
+           'offsetof(ow_surface_query, residual), offsetof(ow_surface_query, iterations), offsetof(ow_surface_query, evaluations),'
+           'offsetof(ow_surface_query, converged), offsetof(ow_surface_query, falloff), offsetof(ow_surface_query, height),'
+           'offsetof(ow_surface_query, normal), offsetof(ow_surface_query, world_xz), offsetof(ow_surface_query, reserved),'
+           'offsetof(ow_surface_query, sample), OW_QUERY_DISTANCE_FALLOFF);return 0;}\n')
+    exe = str(tmp_path / "query_layout")
+    subprocess.run(["gcc", "-std=c11", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-x", "c", "-", "-o", exe], input=src, text=True, check=True)
+    got = [int(v) for v in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split()]
+    O, Q = _lib.ow_query_options, _lib.ow_surface_query
+    want = [C.sizeof(O), O.tolerance.offset, O.flags.offset, O.falloff_center_xz.offset, O.reserved.offset, C.sizeof(Q), C.alignment(Q),
+            Q.residual.offset, Q.iterations.offset, Q.evaluations.offset, Q.converged.offset, Q.falloff.offset, Q.height.offset,
+            Q.normal.offset, Q.world_xz.offset, Q.reserved.offset, Q.sample.offset, _lib.OW_QUERY_DISTANCE_FALLOFF]
+    assert got == want
+    assert got[0] == 32 and got[5] == 128 and got[5] % 64 == 0 and got[16] == 64 and got[6] <= 8
+    assert REC.itemsize == 128 and REC.fields["sample"][1] == 64 and all(REC.fields[f][1] == getattr(Q, f).offset for f in REC.names)
+    assert C.sizeof(_lib.ow_surface_sample) == 64 and WaveGenerator.SURFACE_SAMPLE.itemsize == 64
+    sizes = [C.c_int() for _ in range(3)]
+    harness.harness_record_sizes(*[C.byref(s) for s in sizes])
+    assert [s.value for s in sizes] == [64, 128, 64]
+
+
+def test_the_csharp_binding_shows_the_query_structs_and_functions():
+    """the two new [StructLayout] structs list the C fields in order with the same sizes (the embedded record counted as
+    its 64 bytes), and the three functions are bound; §7 names them"""
+    import test_integration_shim as S
+    c_sizes = dict(S.C_SIZES, ow_surface_sample=64)
+    cs_sizes = dict(S.CS_SIZES, OwSurfaceSample=64)
+
+    def fields(body, sizes, strip):
+        out = []
+        for decl in body.split(";"):
+            decl = " ".join(strip(decl).split())
+            if not decl:
+                continue
+            decl = decl[len("fixed "):] if decl.startswith("fixed ") else decl
+            typ, names = decl.split(" ", 1)
+            for n in names.split(","):
+                m = re.match(r"\s*([A-Za-z_]\w*)(\[(\d+)\])?\s*$", n)
+                out.append((m.group(1), sizes[typ] * int(m.group(3) or 1)))
+        return out
+
+    for cs, c in (("OwQueryOptions", "ow_query_options"), ("OwSurfaceQuery", "ow_surface_query")):
+        cbody = re.search(r"typedef struct %s \{(.*?)\}\s*%s\s*;" % (c, c), S.strip_comments(S.HEADER), flags=re.S).group(1)
+        csbody = re.search(r"struct %s \{(.*?)\n\}" % cs, S.strip_comments(S.SHIM), flags=re.S).group(1)
+        want = fields(cbody, c_sizes, lambda d: d)
+        got = fields(csbody, cs_sizes, lambda d: d.replace("public", ""))
+        assert got == want, (cs, got, want)
+    assert sum(s for _, s in fields(re.search(r"typedef struct ow_surface_query \{(.*?)\}", S.strip_comments(S.HEADER), flags=re.S).group(1),
+                                     c_sizes, lambda d: d)) == 128
+    for name in NEW_FUNCTIONS:
+        assert re.search(r"\[DllImport\(Lib\)\]\s*public static extern int %s\(" % name, S.SHIM), name
+        assert "`%s`" % name in S.DOC.split("## 7. Index")[1], name
+
+
+# ---- 2. argument checks without a device ---------------------------------------------------------------------------------------------
+
+def test_query_argument_errors_without_a_device():
+    lib = _lib.load()
+    xz = np.zeros((4, 2), np.float32)
+    sc = np.ones((1, 4), np.float32)
+    out = np.zeros(4, REC)
+    for count, cascades in ((4, 1), (-1, 1), (4, 0), (4, 9)):
+        assert lib.ow_query_surface(None, xz.ctypes.data, count, sc.ctypes.data, cascades, None, out.ctypes.data) == _lib.OW_ERR_INVALID
+        assert lib.ow_query_surface_async(None, 0, count, sc.ctypes.data, cascades, None, 0) == _lib.OW_ERR_INVALID
+        assert lib.ow_group_query_surface(None, xz.ctypes.data, count, sc.ctypes.data, cascades, None, out.ctypes.data) == _lib.OW_ERR_INVALID
+    assert b"null" in lib.ow_last_error()
+    with pytest.raises(ValueError):
+        WaveGenerator.query_options({"iterations": 3})
+    o = WaveGenerator.query_options({"max_iterations": 8, "tolerance": 1e-4, "falloff_center": (3.0, -2.0)})
+    assert (o.max_iterations, o.flags, tuple(o.falloff_center_xz)) == (8, _lib.OW_QUERY_DISTANCE_FALLOFF, (3.0, -2.0))
+
+
+# ---- 3. the solver header on the CPU, against the FP64 twin ---------------------------------------------------------------------------
+
+@pytest.mark.parametrize("case", ["random_maps", "generated_maps"])
+def test_solver_against_the_fp64_twin(harness, case):
+    if case == "random_maps":   # rough synthetic maps: many folds, many misses
+        d, m = random_maps(3, 64)
+        sc = SCALES3
+    else:
+        d, m, sc = generated_maps(128, [0, 1, 2])
+    xz = query_points(4000, seed=3)
+    out = cpu_query(harness, d, m, sc, xz)
+    c = check_against_twin(out, d, sc, xz)
+    if case == "random_maps":
+        assert 0.3 < c.mean() < 1.0
+    else:
+        assert c.mean() > 0.9
+    assert (out["iterations"] <= 16).all() and (out["evaluations"] >= 1).all()
+    # the height and the normal are the embedded sample's, and the sample is sample_point's at p
+    assert np.array_equal(out["height"], out["falloff"] * out["sample"]["displacement"][:, 1])
+    s = cpu_sample(harness, d, m, sc, out["p"])
+    assert out["sample"].tobytes() == s.tobytes()
+    g = s["gradient_scaled"].astype(np.float64)
+    nrm = np.stack([-g[:, 0], np.ones(len(g)), -g[:, 1]], axis=1)
+    assert np.abs(out["normal"] - nrm / np.linalg.norm(nrm, axis=1)[:, None]).max() < 1e-6
+
+
+def test_no_nan_or_inf_on_awkward_points(harness):
+    d, m, sc = generated_maps(128, [0, 1, 2])
+    n, tile = 128, 88.0
+    edges = np.arange(-3, 4) * tile / n                                   # texel edges of cascade 0
+    centres = (np.arange(-3, 4) + 0.5) * tile / n                         # and centres
+    pts = [(x, z) for x in np.concatenate([edges, centres]) for z in (edges[1], centres[2])]
+    pts += [(1e4, 1e4), (-1e4, 1e4), (-1e4, -1e4), (1e4, -1e4), (0.0, 0.0), (-0.0, -0.001)]
+    xz = np.concatenate([np.array(pts, np.float32), query_points(200, seed=5)])
+    for center in (None, (0.0, 0.0), (1e4, -1e4)):
+        out = cpu_query(harness, d, m, sc, xz, falloff_center=center)
+        check_against_twin(out, d, sc, xz, center=center)
+    bad = np.array([[np.nan, 1.0], [np.inf, 0.0], [5.0, -np.inf]], np.float32)
+    out = cpu_query(harness, d, m, sc, bad)
+    assert (out["converged"] == 0).all() and np.isfinite(out["residual"]).all() and np.isfinite(out["height"]).all()
+    assert (out["p"] == 0).all()
+
+
+def test_no_displacement_means_p_is_q(harness):
+    d, m, sc = generated_maps(128, [0, 1])
+    sc = sc.copy()
+    sc[:, 2] = 0.0
+    xz = query_points(500, seed=9)
+    out = cpu_query(harness, d, m, sc, xz)
+    assert np.array_equal(out["p"], xz) and (out["height"] == 0).all() and (out["converged"] == 1).all()
+    assert (out["iterations"] == 0).all() and (out["residual"] == 0).all()
+
+
+def test_distance_falloff(harness):
+    d, m, sc = generated_maps(128, [0, 1, 2])
+    center = (40.0, -25.0)
+    rng = np.random.default_rng(4)
+    xz = (rng.uniform(-600, 600, (3000, 2)) + center).astype(np.float32)
+    out = cpu_query(harness, d, m, sc, xz, falloff_center=center)
+    check_against_twin(out, d, sc, xz, center=center)
+    f64 = T.falloff(out["p"], center)
+    assert np.abs(out["falloff"] - f64).max() <= 4e-7 * f64.max() + 1e-30
+    inside = np.hypot(out["p"][:, 0] - center[0], out["p"][:, 1] - center[1]) < 150.0
+    assert inside.any() and (out["falloff"][inside] == 1.0).all() and (out["falloff"][~inside] < 1.0).all()
+    assert np.array_equal(out["height"], out["falloff"] * out["sample"]["displacement"][:, 1])
+    # the falloff's exponential: a few ulp from FP64 exp over the whole range the shader reaches, 0 where FP32 leaves the normal range
+    a = np.concatenate([np.linspace(-87.0, 0.0, 200001), [-0.0, -1e-30, -90.0, -1e4]]).astype(np.float32)
+    e = np.zeros_like(a)
+    harness.harness_exp(a.ctypes.data, len(a), e.ctypes.data)
+    ref = np.exp(a.astype(np.float64))
+    ok = a > -87.0
+    assert (np.abs(e[ok] - ref[ok]) <= 4e-7 * ref[ok]).all() and (e[~ok] == 0).all()
+
+
+# ---- 4. round trip on a calm sea --------------------------------------------------------------------------------------------------------
+
+def test_round_trip_on_a_calm_sea(harness):
+    """cascade 1 of the demo scene (5 m/s wind) at half its displacement: the forward map p -> p + D_xz(p) does not fold (det(I + J) > 0
+    everywhere on the lattice), so q = forward(p0) has exactly one preimage and the query has to find p0"""
+    d, m, sc = generated_maps(256, [1])
+    sc = sc.copy()
+    sc[:, 2] = 0.5
+    assert T.min_det_on_lattice(d, sc) > 0.25
+    rng = np.random.default_rng(7)
+    p0 = rng.uniform(-300, 300, (10000, 2))
+    q64, h64 = T.forward(d, sc, p0)
+    q = q64.astype(np.float32)
+    out = cpu_query(harness, d, m, sc, q, tolerance=1e-4)
+    assert (out["converged"] == 1).all()
+    err = np.hypot(*(out["p"] - p0).T)
+    assert err.max() <= 1e-3, err.max()
+    assert np.abs(out["height"] - h64).max() <= 1e-4   # FP32 lookup at p vs FP64 at p0 (|p - p0| <= 1e-3, heights O(1 m), slopes < 1)
+
+
+# ---- 5. convergence rate on the demo scene -----------------------------------------------------------------------------------------------
+
+def test_convergence_rate_on_the_demo_scene(harness):
+    """cascades 0-2 of the demo scene at 1024^2 after two ticks, 100 k points in [-500, 500]^2, default options (16 iterations, 1e-3 m):
+    at least 95 % converge (97.4 % when this was written; the misses sit on folded crests)"""
+    d, m, sc = generated_maps(1024, [0, 1, 2])
+    rng = np.random.default_rng(0)
+    xz = rng.uniform(-500, 500, (100000, 2)).astype(np.float32)
+    out = cpu_query(harness, d, m, sc, xz)
+    c = check_against_twin(out, d, sc, xz)
+    print(f"demo scene: {c.mean():.4f} converged, {out['iterations'].mean():.2f} iterations, {out['evaluations'].mean():.2f} evaluations per point")
+    assert c.mean() >= 0.95
+
+
+# ---- 6-9. on the GPU -------------------------------------------------------------------------------------------------------------------
+
+def make_gen(n, ids, stream=None):
+    from godotoceanwaves_amd import WaveCascadeParameters
+    gen = WaveGenerator()
+    gen.map_size = n
+    if stream is not None:
+        gen.stream = stream
+    gen.init_gpu(max(2, len(ids)))
+    return gen, [WaveCascadeParameters(**cascade_preset(ci)) for ci in ids]
+
+
+def scales_of(params):
+    return np.array([(1 / p.tile_length[0], 1 / p.tile_length[1], p.displacement_scale, p.normal_scale) for p in params], np.float32)
+
+
+def gpu_maps(gen, count):
+    maps = [gen.get_maps(i) for i in range(count)]
+    return np.stack([mp[0] for mp in maps]), np.stack([mp[1] for mp in maps])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n,ids", [(1024, [0, 1, 2]), (256, [0, 1, 2, 3]), (2048, [0])])
+def test_gpu_records_are_the_cpu_builds_bit_for_bit(harness, n, ids):
+    gen, params = make_gen(n, ids)
+    gen.run(UPDATE_DELTA, params, 3)
+    sc = scales_of(params)
+    d, m = gpu_maps(gen, len(ids))
+    rng = np.random.default_rng(n)
+    xz = np.concatenate([query_points(2000, seed=n), rng.uniform(-500, 500, (20000, 2)).astype(np.float32)])
+    for opts in (None, {"falloff_center": (12.5, -40.0)}, {"max_iterations": 3, "tolerance": 1e-4}):
+        got = gen.query_surface(xz, sc, opts)
+        kw = {} if opts is None else {"falloff_center": opts.get("falloff_center"), "max_iterations": opts.get("max_iterations", 0),
+                                      "tolerance": opts.get("tolerance", 0.0)}
+        want = cpu_query(harness, d, m, sc, xz, **kw)
+        for f in REC.names:
+            if f != "sample":
+                assert got[f].tobytes() == want[f].tobytes(), (opts, f)
+        assert got["sample"].tobytes() == want["sample"].tobytes(), opts
+        assert np.isfinite(got["height"]).all() and np.isfinite(got["residual"]).all()
+    c = got["converged"].astype(bool)   # last options: 3 iterations -- misses exist and are reported, not hidden
+    assert 0 < c.sum() < len(c)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n,ids", [(1024, [0, 1, 2]), (256, [0, 1, 2, 3])])
+def test_embedded_sample_is_ow_sample_surface_at_p(n, ids):
+    gen, params = make_gen(n, ids)
+    gen.run(UPDATE_DELTA, params, 5)
+    sc = scales_of(params)
+    xz = query_points(20000, seed=21, span=500.0)
+    q = gen.query_surface(xz, sc)
+    s = gen.sample_surface(q["p"], sc)
+    assert q["sample"].tobytes() == s.tobytes()
+    assert np.array_equal(q["height"], q["falloff"] * s["displacement"][:, 1])
+    assert q["converged"].mean() > 0.9
+
+
+def _async_case(drive, stream=None, torch_stream=None):
+    """drive(gen, params, 8) / query_surface_async / drive again / sync, against the synchronous query of a context that stopped after the
+    first drive: the asynchronous query read the maps of exactly that point of the stream"""
+    import torch
+    n, ids = 1024, [0, 1, 2, 3]
+    a, pa = make_gen(n, ids, stream=stream)
+    b, pb = make_gen(n, ids)
+    sc = scales_of(pa)
+    rng = np.random.default_rng(5)
+    xz = np.concatenate([query_points(1000, seed=2, span=400.0), rng.uniform(-400, 400, (15000, 2)).astype(np.float32)])
+    xz_dev = torch.from_numpy(xz).to("cuda:0")
+    out_dev = torch.zeros((len(xz), REC.itemsize), dtype=torch.uint8, device="cuda:0")
+    torch.cuda.synchronize()
+    drive(a, pa, 8)
+    if torch_stream is not None:
+        with torch.cuda.stream(torch_stream):
+            a.query_surface_async(xz_dev, sc, out_dev)
+            copy = out_dev.to("cpu", non_blocking=False)   # the caller's own work, ordered by its stream alone
+        torch_stream.synchronize()
+    else:
+        a.query_surface_async(xz_dev, sc, out_dev)
+    drive(a, pa, 8)
+    a.sync()
+    got = np.frombuffer(out_dev.cpu().numpy().tobytes(), REC)
+    drive(b, pb, 8)
+    want = b.query_surface(xz, sc)
+    assert got.tobytes() == want.tobytes()
+    if torch_stream is not None:
+        assert np.frombuffer(copy.numpy().tobytes(), REC).tobytes() == want.tobytes()
+    # ... and the second half moved the maps: a query now reads other bits
+    assert a.query_surface(xz[:1000], sc).tobytes() != want[:1000].tobytes()
+    return a
+
+
+@pytest.mark.gpu
+def test_async_query_is_ordered_behind_both_chains_on_the_contexts_stream():
+    a = _async_case(lambda g, p, k: g.run(UPDATE_DELTA, p, k))
+    assert a.chain_stats() > 0   # tick-pair launches of 1024^2 x 4 went out as two chains: the query had both to wait for
+
+
+@pytest.mark.gpu
+def test_async_query_on_a_callers_stream():
+    import torch
+    s = torch.cuda.Stream()
+    _async_case(lambda g, p, k: g.run(UPDATE_DELTA, p, k), stream=s.cuda_stream, torch_stream=s)
+
+
+@pytest.mark.gpu
+def test_async_query_between_look_ahead_ticks():
+    def ticks(g, p, k):
+        for _ in range(k):
+            g.update_all(UPDATE_DELTA, p)
+    a = _async_case(ticks)
+    hits, _ = a.lookahead_stats()
+    assert hits > 0   # the ticks ran with pass 1 of the next tick speculated: the query sat between a speculation and its use
+
+
+@pytest.mark.gpu
+def test_async_query_argument_errors():
+    import torch
+    gen, params = make_gen(256, [0, 1])
+    sc = scales_of(params)
+    xz_dev = torch.zeros((8, 2), device="cuda:0")
+    out_dev = torch.zeros((8, REC.itemsize), dtype=torch.uint8, device="cuda:0")
+    for bad in ({"max_iterations": -1}, {"max_iterations": 65}, {"tolerance": float("nan")}, {"falloff_center": (float("inf"), 0.0)}):
+        with pytest.raises(_lib.OceanWavesError) as e:
+            gen.query_surface_async(xz_dev, sc, out_dev, bad)
+        assert e.value.status == _lib.OW_ERR_INVALID
+        with pytest.raises(_lib.OceanWavesError):
+            gen.query_surface(np.zeros((8, 2), np.float32), sc, bad)
+    with pytest.raises(_lib.OceanWavesError) as e:
+        gen.query_surface(np.zeros((8, 2), np.float32), np.ones((3, 4), np.float32))
+    assert e.value.status == _lib.OW_ERR_INVALID
+    with pytest.raises(ValueError):
+        gen.query_surface_async(xz_dev, sc, out_dev[:4])
+    assert len(gen.query_surface(np.zeros((0, 2), np.float32), sc)) == 0
+
+
+@pytest.mark.gpu
+def test_group_query_equals_a_single_context():
+    from godotoceanwaves_amd import WaveCascadeParameters, WaveGeneratorGroup
+    n, ids = 512, [0, 1, 2, 3]
+    grp = WaveGeneratorGroup()
+    grp.map_size = n
+    grp.init_gpu([0, 0], 2)
+    pg = [WaveCascadeParameters(**cascade_preset(ci)) for ci in ids]
+    single, ps = make_gen(n, ids)
+    xz = query_points(10000, seed=8, span=400.0)
+    sc = scales_of(ps)
+    with pytest.raises(_lib.OceanWavesError) as e:   # nothing gathered yet
+        grp.query_surface(xz, sc)
+    assert e.value.status == _lib.OW_ERR_STATE
+    grp.run(UPDATE_DELTA, pg, 4)
+    single.run(UPDATE_DELTA, ps, 4)
+    grp.gather_begin()
+    grp.gather_wait()
+    for opts in (None, {"falloff_center": (-30.0, 60.0)}):
+        assert grp.query_surface(xz, sc, opts).tobytes() == single.query_surface(xz, sc, opts).tobytes()
