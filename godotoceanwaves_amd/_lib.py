@@ -21,6 +21,7 @@ OW_FLAG_ALWAYS_REGENERATE_SPECTRUM = 0x1000
 OW_FLAG_LAZY_SCRATCH = 0x2000
 OW_FLAG_SINGLE_STREAM = 0x4000
 OW_QUERY_DISTANCE_FALLOFF = 1
+OW_BUOYANCY_WARM_START = 1
 OW_OK, OW_ERR_INVALID, OW_ERR_NO_DEVICE, OW_ERR_HIP, OW_ERR_NOMEM, OW_ERR_STATE = range(6)
 
 
@@ -90,6 +91,38 @@ class ow_surface_query(C.Structure):
                 ("world_xz", C.c_float * 2), ("reserved", C.c_int32 * 3), ("sample", ow_surface_sample)]
 
 
+class ow_buoyancy_body(C.Structure):
+    """struct ow_buoyancy_body (96 bytes): a pose in Godot's Transform3D layout (basis rows, then origin), velocities, the hull range, drag"""
+    _fields_ = [("transform", C.c_float * 12), ("linear_velocity", C.c_float * 3), ("angular_velocity", C.c_float * 3),
+                ("point_offset", C.c_int32), ("point_count", C.c_int32), ("linear_drag", C.c_float), ("quadratic_drag", C.c_float),
+                ("reserved", C.c_uint32 * 2)]
+
+
+class ow_hull_point(C.Structure):
+    """struct ow_hull_point (32 bytes)"""
+    _fields_ = [("local", C.c_float * 3), ("volume", C.c_float), ("half_height", C.c_float), ("body", C.c_int32), ("reserved", C.c_uint32 * 2)]
+
+
+class ow_buoyancy_options(C.Structure):
+    """struct ow_buoyancy_options (64 bytes); zeros = the defaults (the query's, 1025 kg/m^3, 9.81 m/s^2, water level 0, cold start)"""
+    _fields_ = [("query", ow_query_options), ("density", C.c_float), ("gravity", C.c_float), ("water_level", C.c_float), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32 * 4)]
+
+
+class ow_buoyancy_point(C.Structure):
+    """struct ow_buoyancy_point (64 bytes): one hull point's evaluation, also the warm start's state"""
+    _fields_ = [("world", C.c_float * 3), ("height", C.c_float), ("depth", C.c_float), ("submerged", C.c_float), ("force", C.c_float * 3),
+                ("p", C.c_float * 2), ("residual", C.c_float), ("iterations", C.c_int32), ("evaluations", C.c_int32), ("converged", C.c_int32),
+                ("body", C.c_int32)]
+
+
+class ow_buoyancy_result(C.Structure):
+    """struct ow_buoyancy_result (64 bytes): one body's force, torque about its origin, submerged volume and centre of buoyancy"""
+    _fields_ = [("force", C.c_float * 3), ("torque", C.c_float * 3), ("submerged_volume", C.c_float), ("center_of_buoyancy", C.c_float * 3),
+                ("wetted_points", C.c_int32), ("unconverged_points", C.c_int32), ("invalid_points", C.c_int32), ("max_residual", C.c_float),
+                ("reserved", C.c_uint32 * 2)]
+
+
 # every symbol include/ocean_waves.h declares: (restype, argtypes)
 _P = C.POINTER
 SIGNATURES = {
@@ -120,6 +153,10 @@ SIGNATURES = {
     "ow_sample_surface": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     "ow_query_surface": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, _P(ow_query_options), C.c_void_p]),
     "ow_query_surface_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, _P(ow_query_options), C.c_void_p]),
+    "ow_buoyancy": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, _P(ow_buoyancy_options),
+                              C.c_void_p, C.c_void_p]),
+    "ow_buoyancy_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, _P(ow_buoyancy_options),
+                                    C.c_void_p, C.c_void_p]),
     "ow_get_maps_f32": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
     "ow_get_spectrum": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "ow_get_intermediate": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
@@ -148,6 +185,8 @@ SIGNATURES = {
     "ow_group_get_maps": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "ow_group_sample_surface": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     "ow_group_query_surface": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, _P(ow_query_options), C.c_void_p]),
+    "ow_group_buoyancy": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, _P(ow_buoyancy_options),
+                                    C.c_void_p, C.c_void_p]),
     "ow_export_maps": (C.c_int, [C.c_void_p, _P(C.c_int32), _P(C.c_int32), _P(C.c_size_t)]),
     "ow_import_buffer": (C.c_int, [C.c_int32, C.c_int32, C.c_size_t, C.c_size_t, _P(C.c_void_p), _P(C.c_void_p)]),
     "ow_release_buffer": (None, [C.c_void_p]),

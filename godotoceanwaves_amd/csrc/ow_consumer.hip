@@ -33,6 +33,50 @@ __global__ void __launch_bounds__(256) k_query_surface(const u16x4 *disp, const 
     out[i] = query_point(disp, norm, n, cascades, scales, qp, xz[2 * i], xz[2 * i + 1]);
 }
 
+// One lane per hull point (ow_buoyancy.h buoyancy_point), the shape of k_query_surface: a lane's cost is the dependent chain of its Newton
+// iterations, which the warm start shortens.  The lane reads its own previous record before it overwrites it.
+__global__ void __launch_bounds__(256) k_buoyancy_points(const u16x4 *disp, int n, int cascades, const BuoyancyBody *bodies, int num_bodies,
+                                                         const HullPoint *hull, int num_points, SurfaceScales scales, QueryParams qp,
+                                                         BuoyancyParams bp, BuoyancyPoint *pts) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= num_points) return;
+    BuoyancyPoint prev;
+    if (bp.warm_start) {
+        prev = pts[i];
+    } else {
+        prev.world[0] = prev.world[2] = prev.p[0] = prev.p[1] = 0.0f;
+        prev.converged = 0;
+    }
+    pts[i] = buoyancy_point(disp, n, cascades, scales, qp, bp, bodies, num_bodies, hull, i, prev);
+}
+
+__device__ inline BodySum shfl_xor_sum(const BodySum &a, int m) {
+    BodySum o;
+    for (int k = 0; k < 3; ++k) {
+        o.F[k] = __shfl_xor(a.F[k], m, 64);
+        o.T[k] = __shfl_xor(a.T[k], m, 64);
+        o.M[k] = __shfl_xor(a.M[k], m, 64);
+    }
+    o.SV = __shfl_xor(a.SV, m, 64);
+    o.wetted = __shfl_xor(a.wetted, m, 64);
+    o.unconverged = __shfl_xor(a.unconverged, m, 64);
+    o.invalid = __shfl_xor(a.invalid, m, 64);
+    o.max_residual = __shfl_xor(a.max_residual, m, 64);
+    return o;
+}
+
+// One 64-lane wave per body, four bodies per block: the lanes sum the body's records in the order ow_buoyancy.h fixes, then the xor tree
+// 32, 16, 8, 4, 2, 1 combines them; lane 0 writes the result.
+__global__ void __launch_bounds__(256) k_buoyancy_bodies(const BuoyancyBody *bodies, int num_bodies, const HullPoint *hull, int num_points,
+                                                         const BuoyancyPoint *pts, BuoyancyResult *results) {
+    const int bi = blockIdx.x * 4 + (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63);
+    if (bi >= num_bodies) return;  // wave-uniform
+    const BuoyancyBody b = bodies[bi];
+    BodySum a = body_sum_lane(b, bi, hull, pts, num_points, lane);
+    for (int m = 32; m >= 1; m >>= 1) a = body_sum_combine(a, shfl_xor_sum(a, m));
+    if (lane == 0) results[bi] = body_result(a, b);
+}
+
 }  // namespace
 
 hipError_t launch_sample_surface(int n, int cascades, const DeviceBuffers &buf, const float *xz_dev, int count,
@@ -51,6 +95,23 @@ hipError_t launch_query_surface(int n, int cascades, const DeviceBuffers &buf, c
     hipLaunchKernelGGL(k_query_surface, dim3((count + threads - 1) / threads), dim3(threads), 0, s, buf.disp, buf.norm, n, cascades, xz_dev,
                        count, scales, qp, out_dev);
     return hipGetLastError();
+}
+
+hipError_t launch_buoyancy(int n, int cascades, const DeviceBuffers &buf, const BuoyancyBody *bodies_dev, int num_bodies, const HullPoint *hull_dev,
+                           int num_points, const SurfaceScales &scales, const QueryParams &qp, const BuoyancyParams &bp, BuoyancyPoint *pts_dev,
+                           BuoyancyResult *results_dev, hipStream_t s) {
+    const int threads = 256;
+    if (num_points > 0) {
+        hipLaunchKernelGGL(k_buoyancy_points, dim3((num_points + threads - 1) / threads), dim3(threads), 0, s, buf.disp, n, cascades, bodies_dev,
+                           num_bodies, hull_dev, num_points, scales, qp, bp, pts_dev);
+        if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    }
+    if (num_bodies > 0) {
+        hipLaunchKernelGGL(k_buoyancy_bodies, dim3((num_bodies + 3) / 4), dim3(threads), 0, s, bodies_dev, num_bodies, hull_dev, num_points,
+                           pts_dev, results_dev);
+        return hipGetLastError();
+    }
+    return hipSuccess;
 }
 
 }  // namespace ow

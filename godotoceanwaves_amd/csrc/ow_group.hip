@@ -113,6 +113,8 @@ struct ow_group {
     float *query_xz = nullptr;
     void *query_out = nullptr;  // query_capacity records of either kind (ow_group_sample_surface / ow_group_query_surface)
     int query_capacity = 0;
+    void *buoy_scratch = nullptr;  // ow_group_buoyancy (grow-only, root device)
+    size_t buoy_bytes = 0;
 };
 
 namespace {
@@ -379,6 +381,7 @@ void ow_group_destroy(ow_group *g) {
     if (g->own_gnorm) (void)hipFree(g->gnorm);
     (void)hipFree(g->query_xz);
     (void)hipFree(g->query_out);
+    (void)hipFree(g->buoy_scratch);
     delete g;
     if (caller_dev >= 0) (void)hipSetDevice(caller_dev);
 }
@@ -548,6 +551,47 @@ ow_status ow_group_query_surface(ow_group *g, const float *xz, int32_t count, co
         if (ow_status st = ow::resolve_query_options(opts, &qp); st != OW_OK) return st;
     }
     return group_point_query(g, xz, count, map_scales, num_cascades, &qp, out);
+}
+
+ow_status ow_group_buoyancy(ow_group *g, const ow_buoyancy_body *bodies, int32_t num_bodies, const ow_hull_point *hull, int32_t num_points,
+                            const float *map_scales, int32_t num_cascades, const ow_buoyancy_options *opts, ow_buoyancy_result *results,
+                            ow_buoyancy_point *points_inout) {
+    // the host arrays and options are checked first, as by ow_buoyancy
+    if (num_bodies < 0 || num_points < 0) return fail(OW_ERR_INVALID, "num_bodies and num_points must be >= 0");
+    ow::QueryParams qp;
+    ow::BuoyancyParams bp;
+    if (ow_status st = ow::resolve_buoyancy_options(opts, &qp, &bp); st != OW_OK) return st;
+    if (!map_scales || (num_bodies > 0 && (!bodies || !results)) || (num_points > 0 && !hull)) return fail(OW_ERR_INVALID, "null argument");
+    if (num_points > 0 && bp.warm_start && !points_inout) return fail(OW_ERR_INVALID, "OW_BUOYANCY_WARM_START needs points_inout");
+    if (ow_status st = ow::check_buoyancy_arrays(bodies, num_bodies, hull, num_points); st != OW_OK) return st;
+    if (!g) return fail(OW_ERR_INVALID, "null group");
+    if (num_cascades < 1 || num_cascades > std::min(g->total, OW_MAX_CASCADES))
+        return fail(OW_ERR_INVALID, "num_cascades %d outside [1,%d]", num_cascades, std::min(g->total, OW_MAX_CASCADES));
+    if (!g->gathered) return fail(OW_ERR_STATE, "the gathered arrays are empty: ow_group_gather_begin / ow_group_gather_wait first");
+    if (gather_in_flight(g)) return fail(OW_ERR_STATE, "a gather is in flight (the arrays are being written): ow_group_gather_wait first");
+    if (ow_status st = refuse_faulted_layers(g, 0, num_cascades); st != OW_OK) return st;
+    if (num_bodies == 0 && num_points == 0) return OW_OK;
+    int caller_dev = -1;
+    (void)hipGetDevice(&caller_dev);
+    auto run = [&]() -> ow_status {
+        OW_HIP(hipSetDevice(g->root_device));
+        ow::SurfaceScales sc;
+        std::memset(&sc, 0, sizeof(sc));
+        std::memcpy(sc.s, map_scales, (size_t)num_cascades * 4 * sizeof(float));
+        ow::DeviceBuffers buf;
+        std::memset(&buf, 0, sizeof(buf));
+        buf.disp = (ow::u16x4 *)g->gdisp;  // the buoyancy kernels read the displacement array only
+        buf.norm = (ow::u16x4 *)g->gnorm;
+        if (ow_status st = ow::buoyancy_enqueue_host(g->n, num_cascades, buf, g->root_stream, &g->buoy_scratch, &g->buoy_bytes, bodies, num_bodies, hull,
+                                                     num_points, sc, qp, bp, results, points_inout);
+            st != OW_OK)
+            return st;
+        OW_HIP(hipStreamSynchronize(g->root_stream));
+        return OW_OK;
+    };
+    const ow_status st = run();
+    if (caller_dev >= 0) (void)hipSetDevice(caller_dev);
+    return st;
 }
 
 }  // extern "C"

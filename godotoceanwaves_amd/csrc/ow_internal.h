@@ -20,6 +20,18 @@ ow_status poll_status(ow_context *c);
 // ow_query_options (NULL = defaults) -> the solver's settings, OW_ERR_INVALID for a value out of range (ow_runtime.hip)
 struct QueryParams;
 ow_status resolve_query_options(const ow_query_options *opts, QueryParams *qp);
+// ow_buoyancy_options (NULL = defaults) -> the solver's settings and the model's constants (ow_runtime.hip)
+struct BuoyancyParams;
+ow_status resolve_buoyancy_options(const ow_buoyancy_options *opts, QueryParams *qp, BuoyancyParams *bp);
+// the host-side checks of ow_buoyancy / ow_group_buoyancy on host arrays: ranges, body indices, volumes, half heights (ow_runtime.hip)
+ow_status check_buoyancy_arrays(const ow_buoyancy_body *bodies, int num_bodies, const ow_hull_point *hull, int num_points);
+// The synchronous buoyancy's device half on `s` (ow_runtime.hip): grow-only scratch (*scratch, *scratch_bytes; on the current device), the
+// arrays in, both kernels, the results (and, with points_inout, the records) out.  The caller synchronises.
+struct DeviceBuffers;
+struct SurfaceScales;
+ow_status buoyancy_enqueue_host(int n, int cascades, const DeviceBuffers &buf, hipStream_t s, void **scratch, size_t *scratch_bytes,
+                                const ow_buoyancy_body *bodies, int num_bodies, const ow_hull_point *hull, int num_points, const SurfaceScales &sc,
+                                const QueryParams &qp, const BuoyancyParams &bp, ow_buoyancy_result *results, ow_buoyancy_point *points_inout);
 
 }  // namespace ow
 

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "ow_device.h"
+#include "ow_buoyancy.h"
 #include "ow_surface.h"
 
 namespace ow {
@@ -36,6 +37,11 @@ hipError_t launch_sample_surface(int n, int cascades, const DeviceBuffers &buf, 
                                  const SurfaceScales &scales, SurfaceSample *out_dev, hipStream_t s);
 hipError_t launch_query_surface(int n, int cascades, const DeviceBuffers &buf, const float *xz_dev, int count, const SurfaceScales &scales,
                                 const QueryParams &qp, SurfaceQuery *out_dev, hipStream_t s);
+// buoyancy (ow_consumer.hip; per-point code, records and the summation order in ow_buoyancy.h): the per-point kernel over num_points hull
+// points, then the per-body sums over num_bodies bodies, both on `s`.  pts_dev: the per-point records (read first with bp.warm_start).
+hipError_t launch_buoyancy(int n, int cascades, const DeviceBuffers &buf, const BuoyancyBody *bodies_dev, int num_bodies, const HullPoint *hull_dev,
+                           int num_points, const SurfaceScales &scales, const QueryParams &qp, const BuoyancyParams &bp, BuoyancyPoint *pts_dev,
+                           BuoyancyResult *results_dev, hipStream_t s);
 
 bool supported_map_size(int n);
 int kernel_family(int n, int slots, int mode);  // 1 standard, 2 layer-parallel, 3 compact: what launch_pass1/2 will use

@@ -160,6 +160,9 @@ struct ow_context {
     float *query_xz = nullptr;
     void *query_out = nullptr;
     int query_capacity = 0;
+    // ow_buoyancy scratch (grow-only): bodies, hull points, per-point records, results
+    void *buoy_scratch = nullptr;
+    size_t buoy_bytes = 0;
 };
 
 // The stream everything but a first-chain launch is enqueued on or synchronised through: joins the second chain first (a no-op when none is in flight).
@@ -1183,6 +1186,7 @@ void ow_destroy(ow_context *c) {
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     (void)hipFree(c->query_xz);
     (void)hipFree(c->query_out);
+    (void)hipFree(c->buoy_scratch);
     for (auto &e : c->ev)
         if (e) (void)hipEventDestroy(e);
     if (c->side_fork_ev) (void)hipEventDestroy(c->side_fork_ev);
@@ -2091,6 +2095,139 @@ ow_status ow_query_surface_async(ow_context *c, const float *xz_dev, int32_t cou
     const ow::SurfaceScales sc = surface_scales(map_scales, num_cascades);
     // main_stream(): behind the second chain's join as well as everything on the context's (or the caller's) stream
     OW_HIP(ow::launch_query_surface(c->n, num_cascades, c->buf, xz_dev, count, sc, qp, (ow::SurfaceQuery *)out_dev, main_stream(c)));
+    return OW_OK;
+}
+
+}  // extern "C"
+
+namespace ow {
+ow_status resolve_buoyancy_options(const ow_buoyancy_options *o, QueryParams *qp, BuoyancyParams *bp) {
+    if (ow_status st = resolve_query_options(o ? &o->query : nullptr, qp); st != OW_OK) return st;
+    bp->density = kDefaultDensity;
+    bp->water_level = 0.0f;
+    bp->warm_start = 0;
+    float gravity = kDefaultGravity;
+    if (o) {
+        if (!std::isfinite(o->density) || !std::isfinite(o->gravity) || !std::isfinite(o->water_level))
+            return fail(OW_ERR_INVALID, "density, gravity and water_level must be finite");
+        if (o->flags & ~OW_BUOYANCY_WARM_START) return fail(OW_ERR_INVALID, "unknown buoyancy flags 0x%x", o->flags);
+        if (o->density > 0.0f) bp->density = o->density;
+        if (o->gravity > 0.0f) gravity = o->gravity;
+        bp->water_level = o->water_level;
+        bp->warm_start = (o->flags & OW_BUOYANCY_WARM_START) ? 1 : 0;
+    }
+    bp->rho_g = bp->density * gravity;
+    if (!std::isfinite(bp->rho_g)) return fail(OW_ERR_INVALID, "density * gravity overflows");
+    return OW_OK;
+}
+
+ow_status check_buoyancy_arrays(const ow_buoyancy_body *bodies, int num_bodies, const ow_hull_point *hull, int num_points) {
+    for (int b = 0; b < num_bodies; ++b) {
+        const ow_buoyancy_body &B = bodies[b];
+        if (B.point_offset < 0 || B.point_count < 0 || (int64_t)B.point_offset + B.point_count > num_points)
+            return fail(OW_ERR_INVALID, "body %d: point range [%d, %d + %d) outside [0, %d)", b, B.point_offset, B.point_offset, B.point_count, num_points);
+        for (int i = B.point_offset; i < B.point_offset + B.point_count; ++i)
+            if (hull[i].body != b) return fail(OW_ERR_INVALID, "hull point %d lies in body %d's range but names body %d", i, b, hull[i].body);
+    }
+    for (int i = 0; i < num_points; ++i) {
+        const ow_hull_point &h = hull[i];
+        if (h.body < 0 || h.body >= num_bodies) return fail(OW_ERR_INVALID, "hull point %d: body %d outside [0, %d)", i, h.body, num_bodies);
+        const ow_buoyancy_body &B = bodies[h.body];
+        if (i < B.point_offset || i >= B.point_offset + B.point_count)
+            return fail(OW_ERR_INVALID, "hull point %d names body %d, whose range does not hold it", i, h.body);
+        if (!(h.volume >= 0.0f) || !(h.half_height >= 0.0f))
+            return fail(OW_ERR_INVALID, "hull point %d: volume and half_height must be >= 0", i);
+    }
+    return OW_OK;
+}
+
+ow_status buoyancy_enqueue_host(int n, int cascades, const DeviceBuffers &buf, hipStream_t s, void **scratch, size_t *scratch_bytes,
+                                const ow_buoyancy_body *bodies, int num_bodies, const ow_hull_point *hull, int num_points, const SurfaceScales &sc,
+                                const QueryParams &qp, const BuoyancyParams &bp, ow_buoyancy_result *results, ow_buoyancy_point *points_inout) {
+    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t b_bytes = up((size_t)num_bodies * sizeof(BuoyancyBody)), h_bytes = up((size_t)num_points * sizeof(HullPoint));
+    const size_t p_bytes = up((size_t)num_points * sizeof(BuoyancyPoint)), r_bytes = up((size_t)num_bodies * sizeof(BuoyancyResult));
+    const size_t need = b_bytes + h_bytes + p_bytes + r_bytes;
+    if (need > *scratch_bytes) {
+        (void)hipFree(*scratch);
+        *scratch = nullptr;
+        *scratch_bytes = 0;
+        const size_t cap = std::max(need, (size_t)1 << 20);
+        if (hipMalloc(scratch, cap) != hipSuccess) return fail(OW_ERR_NOMEM, "hipMalloc failed for %zu bytes of buoyancy scratch", cap);
+        *scratch_bytes = cap;
+    }
+    char *base = (char *)*scratch;
+    BuoyancyBody *bd = (BuoyancyBody *)base;
+    HullPoint *hd = (HullPoint *)(base + b_bytes);
+    BuoyancyPoint *pd = (BuoyancyPoint *)(base + b_bytes + h_bytes);
+    BuoyancyResult *rd = (BuoyancyResult *)(base + b_bytes + h_bytes + p_bytes);
+    if (num_bodies > 0) OW_HIP(hipMemcpyAsync(bd, bodies, (size_t)num_bodies * sizeof(BuoyancyBody), hipMemcpyHostToDevice, s));
+    if (num_points > 0) OW_HIP(hipMemcpyAsync(hd, hull, (size_t)num_points * sizeof(HullPoint), hipMemcpyHostToDevice, s));
+    if (bp.warm_start && num_points > 0) OW_HIP(hipMemcpyAsync(pd, points_inout, (size_t)num_points * sizeof(BuoyancyPoint), hipMemcpyHostToDevice, s));
+    OW_HIP(launch_buoyancy(n, cascades, buf, bd, num_bodies, hd, num_points, sc, qp, bp, pd, rd, s));
+    if (num_bodies > 0) OW_HIP(hipMemcpyAsync(results, rd, (size_t)num_bodies * sizeof(BuoyancyResult), hipMemcpyDeviceToHost, s));
+    if (points_inout && num_points > 0) OW_HIP(hipMemcpyAsync(points_inout, pd, (size_t)num_points * sizeof(BuoyancyPoint), hipMemcpyDeviceToHost, s));
+    return OW_OK;
+}
+}  // namespace ow
+
+namespace {
+// what both context forms check before they touch the context's device: counts, options, pointers (host arrays: ranges and indices)
+ow_status check_buoyancy_call(const ow_buoyancy_body *bodies, int32_t num_bodies, const ow_hull_point *hull, int32_t num_points,
+                              const float *map_scales, const ow_buoyancy_options *opts, const void *results, const void *points, bool host,
+                              ow::QueryParams *qp, ow::BuoyancyParams *bp) {
+    if (num_bodies < 0 || num_points < 0) return fail(OW_ERR_INVALID, "num_bodies and num_points must be >= 0");
+    if (ow_status st = ow::resolve_buoyancy_options(opts, qp, bp); st != OW_OK) return st;
+    if (!map_scales || (num_bodies > 0 && (!bodies || !results)) || (num_points > 0 && !hull)) return fail(OW_ERR_INVALID, "null argument");
+    if (num_points > 0 && !points && (bp->warm_start || !host))
+        return fail(OW_ERR_INVALID, host ? "OW_BUOYANCY_WARM_START needs points_inout" : "points_dev is required");
+    if (host) return ow::check_buoyancy_arrays(bodies, num_bodies, hull, num_points);
+    return OW_OK;
+}
+}  // namespace
+
+extern "C" {
+
+ow_status ow_buoyancy(ow_context *c, const ow_buoyancy_body *bodies, int32_t num_bodies, const ow_hull_point *hull, int32_t num_points,
+                      const float *map_scales, int32_t num_cascades, const ow_buoyancy_options *opts, ow_buoyancy_result *results,
+                      ow_buoyancy_point *points_inout) {
+    static_assert(sizeof(ow_buoyancy_body) == sizeof(ow::BuoyancyBody) && sizeof(ow_hull_point) == sizeof(ow::HullPoint) &&
+                      sizeof(ow_buoyancy_point) == sizeof(ow::BuoyancyPoint) && sizeof(ow_buoyancy_result) == sizeof(ow::BuoyancyResult) &&
+                      offsetof(ow_buoyancy_point, body) == offsetof(ow::BuoyancyPoint, body) &&
+                      offsetof(ow_buoyancy_result, max_residual) == offsetof(ow::BuoyancyResult, max_residual) &&
+                      offsetof(ow_buoyancy_body, point_offset) == offsetof(ow::BuoyancyBody, point_offset),
+                  "record layout");
+    ow::QueryParams qp;
+    ow::BuoyancyParams bp;
+    if (ow_status st = check_buoyancy_call(bodies, num_bodies, hull, num_points, map_scales, opts, results, points_inout, true, &qp, &bp); st != OW_OK)
+        return st;
+    if (ow_status st = check_point_query(c, 0, num_cascades); st != OW_OK) return st;
+    if (num_bodies == 0 && num_points == 0) return OW_OK;
+    OW_HIP(hipSetDevice(c->device));
+    const ow::SurfaceScales sc = surface_scales(map_scales, num_cascades);
+    if (ow_status st = ow::buoyancy_enqueue_host(c->n, num_cascades, c->buf, main_stream(c), &c->buoy_scratch, &c->buoy_bytes, bodies, num_bodies, hull,
+                                                 num_points, sc, qp, bp, results, points_inout);
+        st != OW_OK)
+        return st;
+    return sync_stream(c, (1u << num_cascades) - 1u);
+}
+
+ow_status ow_buoyancy_async(ow_context *c, const ow_buoyancy_body *bodies_dev, int32_t num_bodies, const ow_hull_point *hull_dev,
+                            int32_t num_points, const float *map_scales, int32_t num_cascades, const ow_buoyancy_options *opts,
+                            ow_buoyancy_result *results_dev, ow_buoyancy_point *points_dev) {
+    ow::QueryParams qp;
+    ow::BuoyancyParams bp;
+    if (ow_status st = check_buoyancy_call(bodies_dev, num_bodies, hull_dev, num_points, map_scales, opts, results_dev, points_dev, false, &qp, &bp);
+        st != OW_OK)
+        return st;
+    if (ow_status st = check_point_query(c, 0, num_cascades); st != OW_OK) return st;
+    if (num_bodies == 0 && num_points == 0) return OW_OK;
+    if (ow_status st = refuse_faulted(c, (1u << num_cascades) - 1u); st != OW_OK) return st;
+    OW_HIP(hipSetDevice(c->device));
+    const ow::SurfaceScales sc = surface_scales(map_scales, num_cascades);
+    // main_stream(): behind the second chain's join as well as everything on the context's (or the caller's) stream
+    OW_HIP(ow::launch_buoyancy(c->n, num_cascades, c->buf, (const ow::BuoyancyBody *)bodies_dev, num_bodies, (const ow::HullPoint *)hull_dev, num_points,
+                               sc, qp, bp, (ow::BuoyancyPoint *)points_dev, (ow::BuoyancyResult *)results_dev, main_stream(c)));
     return OW_OK;
 }
 

@@ -305,14 +305,18 @@ OW_DEV bool query_line_search(const u16x4 *disp, int n, int cascades, const Surf
     }
     return false;
 }
-OW_DEV SurfaceQuery query_point(const u16x4 *disp, const u16x4 *norm, int n, int cascades, const SurfaceScales &scales, const QueryParams &qp,
-                                float qx, float qz) {
-    SurfaceQuery out;
-    out.world_xz[0] = qx;
-    out.world_xz[1] = qz;
-    out.reserved[0] = out.reserved[1] = out.reserved[2] = 0;
+// The Newton loop of query_point from a given start p0 (query_point: p0 = q; the buoyancy kernel's warm start: the previous step's p
+// moved with q).  A non-finite q (or one beyond 3e38) gives p = (0, 0) and no iteration; p0 must be finite.
+struct QuerySolution {
+    float p[2];
+    QueryEval e;  // F at p
+    int iterations, evaluations;
+    bool finite;  // q was finite: converged = finite && e.r <= tolerance
+};
+OW_DEV QuerySolution query_solve(const u16x4 *disp, int n, int cascades, const SurfaceScales &scales, const QueryParams &qp, float qx, float qz,
+                                 float p0x, float p0z) {
     const bool finite = fabsf(qx) <= 3.0e38f && fabsf(qz) <= 3.0e38f;
-    float px = finite ? qx : 0.0f, pz = finite ? qz : 0.0f;
+    float px = finite ? p0x : 0.0f, pz = finite ? p0z : 0.0f;
     QueryEval e = query_eval(disp, n, cascades, scales, qp, px, pz, qx, qz);
     int it = 0, evals = 1;
     if (finite) {
@@ -331,6 +335,27 @@ OW_DEV SurfaceQuery query_point(const u16x4 *disp, const u16x4 *norm, int n, int
             }
         }
     }
+    QuerySolution sol;
+    sol.p[0] = px;
+    sol.p[1] = pz;
+    sol.e = e;
+    sol.iterations = it;
+    sol.evaluations = evals;
+    sol.finite = finite;
+    return sol;
+}
+
+OW_DEV SurfaceQuery query_point(const u16x4 *disp, const u16x4 *norm, int n, int cascades, const SurfaceScales &scales, const QueryParams &qp,
+                                float qx, float qz) {
+    SurfaceQuery out;
+    out.world_xz[0] = qx;
+    out.world_xz[1] = qz;
+    out.reserved[0] = out.reserved[1] = out.reserved[2] = 0;
+    const QuerySolution sol = query_solve(disp, n, cascades, scales, qp, qx, qz, qx, qz);
+    const float px = sol.p[0], pz = sol.p[1];
+    const QueryEval &e = sol.e;
+    const int it = sol.iterations, evals = sol.evaluations;
+    const bool finite = sol.finite;
     out.p[0] = px;
     out.p[1] = pz;
     out.residual = e.r;

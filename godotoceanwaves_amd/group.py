@@ -151,6 +151,21 @@ class WaveGeneratorGroup:
                                                     C.byref(o) if o is not None else None, out.ctypes.data))
         return out
 
+    def buoyancy(self, bodies, hull, map_scales, options=None, points=None):
+        """WaveGenerator.buoyancy over the gathered arrays on the root device"""
+        b = np.ascontiguousarray(bodies, WaveGenerator.BUOYANCY_BODY)
+        h = np.ascontiguousarray(hull, WaveGenerator.HULL_POINT)
+        sc = np.ascontiguousarray(map_scales, np.float32).reshape(-1, 4)
+        if points is not None and (not isinstance(points, np.ndarray) or points.dtype != WaveGenerator.BUOYANCY_POINT or len(points) != len(h)
+                                   or not points.flags.c_contiguous):
+            raise ValueError(f"points must be a contiguous BUOYANCY_POINT array of {len(h)} records")
+        out = np.zeros(len(b), WaveGenerator.BUOYANCY_RESULT)
+        o = WaveGenerator.buoyancy_options(options)
+        _lib.check(self._lib.ow_group_buoyancy(self.group, b.ctypes.data, len(b), h.ctypes.data, len(h), sc.ctypes.data, len(sc),
+                                               C.byref(o) if o is not None else None, out.ctypes.data,
+                                               points.ctypes.data if points is not None else None))
+        return out
+
     def free(self):
         if self.group:
             self._lib.ow_group_destroy(self.group)

@@ -311,6 +311,93 @@ class WaveGenerator:
         _lib.check(self._lib.ow_query_surface_async(self.context, addr(xz_device), int(count), sc.ctypes.data, len(sc),
                                                     C.byref(o) if o is not None else None, addr(out_device)))
 
+    # ---- buoyancy: per-body force and torque from hull points, on the device (include/ocean_waves.h ow_buoyancy) ----
+    BUOYANCY_BODY = np.dtype([("transform", np.float32, 12), ("linear_velocity", np.float32, 3), ("angular_velocity", np.float32, 3),
+                              ("point_offset", np.int32), ("point_count", np.int32), ("linear_drag", np.float32), ("quadratic_drag", np.float32),
+                              ("reserved", np.uint32, 2)])
+    HULL_POINT = np.dtype([("local", np.float32, 3), ("volume", np.float32), ("half_height", np.float32), ("body", np.int32),
+                           ("reserved", np.uint32, 2)])
+    BUOYANCY_OPTIONS = np.dtype([("query", [("max_iterations", np.int32), ("tolerance", np.float32), ("flags", np.uint32),
+                                            ("falloff_center_xz", np.float32, 2), ("reserved", np.uint32, 3)]),
+                                 ("density", np.float32), ("gravity", np.float32), ("water_level", np.float32), ("flags", np.uint32),
+                                 ("reserved", np.uint32, 4)])
+    BUOYANCY_POINT = np.dtype([("world", np.float32, 3), ("height", np.float32), ("depth", np.float32), ("submerged", np.float32),
+                               ("force", np.float32, 3), ("p", np.float32, 2), ("residual", np.float32), ("iterations", np.int32),
+                               ("evaluations", np.int32), ("converged", np.int32), ("body", np.int32)])
+    BUOYANCY_RESULT = np.dtype([("force", np.float32, 3), ("torque", np.float32, 3), ("submerged_volume", np.float32),
+                                ("center_of_buoyancy", np.float32, 3), ("wetted_points", np.int32), ("unconverged_points", np.int32),
+                                ("invalid_points", np.int32), ("max_residual", np.float32), ("reserved", np.uint32, 2)])
+
+    @classmethod
+    def buoyancy_options(cls, options=None):
+        """None, an _lib.ow_buoyancy_options, or a dict of density / gravity / water_level / warm_start (bool) and the query_options keys
+        -> ow_buoyancy_options, or None for the defaults"""
+        if options is None or isinstance(options, _lib.ow_buoyancy_options):
+            return options
+        own = {"density", "gravity", "water_level", "warm_start"}
+        q = cls.query_options({k: v for k, v in options.items() if k not in own})
+        o = _lib.ow_buoyancy_options(density=float(options.get("density", 0.0)), gravity=float(options.get("gravity", 0.0)),
+                                     water_level=float(options.get("water_level", 0.0)),
+                                     flags=_lib.OW_BUOYANCY_WARM_START if options.get("warm_start") else 0)
+        if q is not None:
+            o.query = q
+        return o
+
+    @classmethod
+    def box_hull(cls, size, divisions, body=0, center=(0.0, 0.0, 0.0)):
+        """A box of size (x, y, z) metres centred at `center` (body space) voxelised into divisions (i, j, k) cells: one hull point per
+        cell at its centre, volume = the cell's volume, half_height = half the cell's height.  Returns HULL_POINT records of `body`."""
+        size = np.asarray(size, np.float64)
+        div = np.asarray(divisions, np.int64)
+        cell = size / div
+        axes = [(np.arange(d) + 0.5) * c - s / 2 + o for d, c, s, o in zip(div, cell, size, center)]
+        X, Y, Z = np.meshgrid(*axes, indexing="ij")
+        out = np.zeros(X.size, cls.HULL_POINT)
+        out["local"] = np.stack([X.ravel(), Y.ravel(), Z.ravel()], axis=1)
+        out["volume"] = np.prod(cell)
+        out["half_height"] = cell[1] / 2
+        out["body"] = body
+        return out
+
+    def buoyancy(self, bodies, hull, map_scales, options=None, points=None):
+        """Force, torque, submerged volume and centre of buoyancy per body (BUOYANCY_RESULT records) for BUOYANCY_BODY records over
+        HULL_POINT records, on the device.  points: None, or a BUOYANCY_POINT array of len(hull) that receives the per-point records
+        (and holds the previous step's for the warm start, options {"warm_start": True})."""
+        b = np.ascontiguousarray(bodies, self.BUOYANCY_BODY)
+        h = np.ascontiguousarray(hull, self.HULL_POINT)
+        sc = np.ascontiguousarray(map_scales, np.float32).reshape(-1, 4)
+        if points is not None and (not isinstance(points, np.ndarray) or points.dtype != self.BUOYANCY_POINT or len(points) != len(h)
+                                   or not points.flags.c_contiguous):
+            raise ValueError(f"points must be a contiguous BUOYANCY_POINT array of {len(h)} records")
+        out = np.zeros(len(b), self.BUOYANCY_RESULT)
+        o = self.buoyancy_options(options)
+        _lib.check(self._lib.ow_buoyancy(self.context, b.ctypes.data, len(b), h.ctypes.data, len(h), sc.ctypes.data, len(sc),
+                                         C.byref(o) if o is not None else None, out.ctypes.data, points.ctypes.data if points is not None else None))
+        return out
+
+    def buoyancy_async(self, bodies_device, hull_device, map_scales, results_device, points_device, options=None, num_bodies=None,
+                       num_points=None):
+        """ow_buoyancy_async over DEVICE buffers (torch tensors or integer addresses), enqueued in the generator's stream order without
+        synchronising.  The counts default to the tensors' byte sizes over the record sizes."""
+        def addr(x):
+            return int(x.data_ptr()) if hasattr(x, "data_ptr") else int(x)
+
+        def records(x, dtype, given, name):
+            if given is not None:
+                return int(given)
+            if not hasattr(x, "numel"):
+                raise ValueError(f"{name} is needed for a raw device address")
+            return int(x.numel() * x.element_size()) // dtype.itemsize
+        nb = records(bodies_device, self.BUOYANCY_BODY, num_bodies, "num_bodies")
+        npts = records(hull_device, self.HULL_POINT, num_points, "num_points")
+        for x, n, dt, name in ((results_device, nb, self.BUOYANCY_RESULT, "results_device"), (points_device, npts, self.BUOYANCY_POINT, "points_device")):
+            if hasattr(x, "numel") and hasattr(x, "element_size") and x.numel() * x.element_size() < n * dt.itemsize:
+                raise ValueError(f"{name} holds fewer than {n} records of {dt.itemsize} bytes")
+        sc = np.ascontiguousarray(map_scales, np.float32).reshape(-1, 4)
+        o = self.buoyancy_options(options)
+        _lib.check(self._lib.ow_buoyancy_async(self.context, addr(bodies_device), nb, addr(hull_device), npts, sc.ctypes.data, len(sc),
+                                               C.byref(o) if o is not None else None, addr(results_device), addr(points_device)))
+
     def get_push_constants(self, cascade):
         """(spectrum[16], modulate[8], unpack[4]) uint32 words: the reference's push-constant blocks of this cascade's most recent launch"""
         pc = _lib.ow_push_constants()

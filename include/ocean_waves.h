@@ -374,6 +374,95 @@ ow_status ow_query_surface(ow_context *ctx, const float *world_xz, int32_t count
 ow_status ow_query_surface_async(ow_context *ctx, const float *world_xz_dev, int32_t count, const float *map_scales, int32_t num_cascades,
                                  const ow_query_options *opts, ow_surface_query *out_dev);
 
+/* Buoyancy: per-body force and torque from hull points, on the device.  Each hull point of a body is placed in the world, the water height
+ * above it is found as ow_query_surface finds it (the same bits), and the point's buoyancy and drag are summed per body.  Per point (FP32):
+ *     r = B * local (the lever arm), w = r + o, H = the rendered height above (w.x, w.z), d = water_level + H - w.y (depth),
+ *     s = clamp((d + h) / (2 h), 0, 1) (h = 0: d > 0 ? 1 : 0), u = v + omega x r,
+ *     F = (0, density * gravity * V * s, 0) - density * V * s * (linear_drag * u + quadratic_drag * |u| * u);
+ * per body (FP64, in a fixed order, so that every build gives the same bits): sum F, the torque sum r x F about o in world axes, the
+ * submerged volume sum V s and the centre of buoyancy o + sum V s r / sum V s (o when nothing is submerged).  The water is taken at rest:
+ * the generator makes no velocity maps.  A point with a non-finite input or world position, or one whose body index does not name the
+ * body whose range holds it, contributes nothing and is counted invalid.  Nothing returned is NaN or Inf.  The exact operation order is
+ * godotoceanwaves_amd/csrc/ow_buoyancy.h's. */
+#define OW_BUOYANCY_WARM_START 1u  /* start each point's Newton solve from its previous record: p_prev + (q - q_prev) */
+typedef struct ow_buoyancy_body {
+    float transform[12];        /* Godot's Transform3D: basis rows [0..8], origin [9..11]; world = B * local + o */
+    float linear_velocity[3];   /* m/s */
+    float angular_velocity[3];  /* rad/s, world axes */
+    int32_t point_offset;       /* the body's hull points: [point_offset, point_offset + point_count) */
+    int32_t point_count;
+    float linear_drag;          /* k_lin, 1/s */
+    float quadratic_drag;       /* k_quad, 1/m */
+    uint32_t reserved[2];       /* 0 */
+} ow_buoyancy_body;             /* 96 bytes */
+typedef struct ow_hull_point {
+    float local[3];             /* body space, metres */
+    float volume;               /* m^3, >= 0 */
+    float half_height;          /* metres, >= 0: the point is submerged linearly over [-h, h] around its depth 0 */
+    int32_t body;               /* the index of the body whose range holds this point */
+    uint32_t reserved[2];       /* 0 */
+} ow_hull_point;                /* 32 bytes */
+typedef struct ow_buoyancy_options {
+    ow_query_options query;     /* the height solve (NULL options = all defaults; the falloff flag as for ow_query_surface) */
+    float density;              /* kg/m^3; <= 0 selects 1025 */
+    float gravity;              /* m/s^2; <= 0 selects 9.81 (wave_generator.gd's G) */
+    float water_level;          /* metres: the height of the undisplaced surface (the water mesh's y) */
+    uint32_t flags;             /* OW_BUOYANCY_* */
+    uint32_t reserved[4];       /* 0 */
+} ow_buoyancy_options;          /* 64 bytes */
+/* One record per hull point, 64 bytes: also the warm start's state (the previous step's p and q = (world.x, world.z)). */
+typedef struct ow_buoyancy_point {
+    float world[3];             /* w */
+    float height;               /* H: the rendered water height above (w.x, w.z) */
+    float depth;                /* d */
+    float submerged;            /* s */
+    float force[3];             /* F */
+    float p[2];                 /* the solved undisplaced point */
+    float residual;             /* as ow_surface_query */
+    int32_t iterations;
+    int32_t evaluations;
+    int32_t converged;
+    int32_t body;               /* the body the point counted for; -1: invalid (the record is zeros otherwise) */
+} ow_buoyancy_point;
+/* One record per body, 64 bytes. */
+typedef struct ow_buoyancy_result {
+    float force[3];             /* N, world axes */
+    float torque[3];            /* N m, about the body's origin, world axes */
+    float submerged_volume;     /* m^3 */
+    float center_of_buoyancy[3];
+    int32_t wetted_points;      /* s > 0 */
+    int32_t unconverged_points; /* valid points whose height solve did not converge (they still count, at the residual's minimum) */
+    int32_t invalid_points;
+    float max_residual;         /* the largest residual of a valid point */
+    uint32_t reserved[2];
+} ow_buoyancy_result;
+typedef char ow_layout_check_buoyancy_body[(sizeof(ow_buoyancy_body) == 96 && offsetof(ow_buoyancy_body, point_offset) == 72 &&
+                                            offsetof(ow_buoyancy_body, linear_drag) == 80) ? 1 : -1];
+typedef char ow_layout_check_hull_point[(sizeof(ow_hull_point) == 32 && offsetof(ow_hull_point, body) == 20) ? 1 : -1];
+typedef char ow_layout_check_buoyancy_options[(sizeof(ow_buoyancy_options) == 64 && offsetof(ow_buoyancy_options, density) == 32 &&
+                                               offsetof(ow_buoyancy_options, flags) == 44) ? 1 : -1];
+typedef char ow_layout_check_buoyancy_point[(sizeof(ow_buoyancy_point) == 64 && offsetof(ow_buoyancy_point, p) == 36 &&
+                                             offsetof(ow_buoyancy_point, body) == 60) ? 1 : -1];
+typedef char ow_layout_check_buoyancy_result[(sizeof(ow_buoyancy_result) == 64 && offsetof(ow_buoyancy_result, wetted_points) == 40 &&
+                                              offsetof(ow_buoyancy_result, max_residual) == 52) ? 1 : -1];
+
+/* Buoyancy of num_bodies bodies over num_points hull points (host pointers), after everything enqueued so far.  Synchronises.
+ * points_inout: NULL, or num_points records that receive the per-point records -- and, with OW_BUOYANCY_WARM_START (where they are
+ * required), hold the previous step's on the way in (zeros make a cold start).  The host checks every body's range (inside
+ * [0, num_points)), every hull point's body index (the body whose range holds it), non-negative volumes and half heights and finite
+ * options: a bad argument is OW_ERR_INVALID and nothing is written.  Faulted layers are refused as by ow_query_surface. */
+ow_status ow_buoyancy(ow_context *ctx, const ow_buoyancy_body *bodies, int32_t num_bodies, const ow_hull_point *hull, int32_t num_points,
+                      const float *map_scales, int32_t num_cascades, const ow_buoyancy_options *opts, ow_buoyancy_result *results,
+                      ow_buoyancy_point *points_inout);
+/* The same with DEVICE pointers on the context's device (map_scales and opts are host values).  points_dev is required (when num_points
+ * > 0): it is the per-point scratch and the warm start's state.  Enqueued in the context's stream order behind everything enqueued so far --
+ * both chains -- and ahead of whatever the context enqueues next, as ow_query_surface_async (a caller's stream included).  Copies nothing,
+ * allocates nothing.  The device data is not checked by the host: a range outside [0, num_points) or a body index that does not match is
+ * counted invalid, never read. */
+ow_status ow_buoyancy_async(ow_context *ctx, const ow_buoyancy_body *bodies_dev, int32_t num_bodies, const ow_hull_point *hull_dev,
+                            int32_t num_points, const float *map_scales, int32_t num_cascades, const ow_buoyancy_options *opts,
+                            ow_buoyancy_result *results_dev, ow_buoyancy_point *points_dev);
+
 /* ---- several devices: cascades sharded inside one process ---------------------------------------- */
 
 /* Cascades share nothing (wave_generator.gd:65-85 touches no state of another cascade; README.md:77-80), so a node's GPUs
@@ -467,6 +556,10 @@ ow_status ow_group_sample_surface(ow_group *group, const float *world_xz, int32_
 /* ow_query_surface over the gathered arrays on the root device (the preconditions of ow_group_sample_surface). */
 ow_status ow_group_query_surface(ow_group *group, const float *world_xz, int32_t count, const float *map_scales, int32_t num_cascades,
                                  const ow_query_options *opts, ow_surface_query *out);
+/* ow_buoyancy over the gathered arrays on the root device (the preconditions of ow_group_sample_surface). */
+ow_status ow_group_buoyancy(ow_group *group, const ow_buoyancy_body *bodies, int32_t num_bodies, const ow_hull_point *hull, int32_t num_points,
+                            const float *map_scales, int32_t num_cascades, const ow_buoyancy_options *opts, ow_buoyancy_result *results,
+                            ow_buoyancy_point *points_inout);
 
 /* ---- zero-copy hand-off: the maps as dma-buf file descriptors ------------------------------------------------------ */
 

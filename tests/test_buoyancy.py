@@ -1,0 +1,655 @@
+"""Buoyancy (include/ocean_waves.h ow_buoyancy, ow_buoyancy_async, ow_group_buoyancy): per-body force and torque from hull points, the
+water height above each point found by the query's solver (godotoceanwaves_amd/csrc/ow_buoyancy.h).
+
+CPU: the ABI (header, exports, ctypes, NumPy, C and C# layouts), the host's argument checks without a device, the example's C99 build;
+ow_buoyancy.h compiled as plain C++ (tests/buoyancy/buoyancy_harness.cpp, g++ -ffp-contract=off) held to hydrostatics on a calm sea, to an
+FP64 NumPy restatement of the model on demo-scene maps, to the query's heights bit for bit, and to the warm start's savings.  GPU: the
+device records and per-body results are those of the CPU build bit for bit (FP32 per point and FP64 per body with contraction off, the
+summation order fixed), the asynchronous form is ordered like ow_query_surface_async, bad device data is counted and not read, the group
+form equals a single context, and examples/buoyancy_host.c floats a box."""
+import ctypes as C
+import math
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import query_twin as T
+from godotoceanwaves_amd import _lib, build
+from godotoceanwaves_amd.presets import UPDATE_DELTA, cascade_preset
+from godotoceanwaves_amd.wave_generator import WaveGenerator as W
+from test_surface_query import cpu_query, generated_maps, gpu_maps, harness as query_harness, make_gen, maps_u16, scales_of  # noqa: F401
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "godotoceanwaves_amd", "csrc")
+HERE = os.path.dirname(os.path.abspath(__file__))
+PKG = os.path.join(ROOT, "godotoceanwaves_amd")
+NEW_FUNCTIONS = ("ow_buoyancy", "ow_buoyancy_async", "ow_group_buoyancy")
+STRUCTS = {"OwBuoyancyBody": "ow_buoyancy_body", "OwHullPoint": "ow_hull_point", "OwBuoyancyOptions": "ow_buoyancy_options",
+           "OwBuoyancyPoint": "ow_buoyancy_point", "OwBuoyancyResult": "ow_buoyancy_result"}
+RHO, G = 1025.0, 9.81
+RHO_G = float(np.float32(RHO) * np.float32(G))
+
+
+# ---- the CPU build of ow_buoyancy.h --------------------------------------------------------------------------------------------------
+
+@pytest.fixture(scope="module")
+def harness(tmp_path_factory):
+    so = str(tmp_path_factory.mktemp("buoyancy") / "libbuoyancy_harness.so")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unknown-pragmas", "-I", CSRC,
+                    os.path.join(HERE, "buoyancy", "buoyancy_harness.cpp"), "-o", so], check=True)
+    L = C.CDLL(so)
+    V = C.c_void_p
+    L.harness_buoyancy_sizes.argtypes = [V]
+    L.harness_buoyancy.argtypes = [V, C.c_int, C.c_int, V, V, C.c_int, V, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.c_float,
+                                   C.c_float, C.c_float, C.c_float, C.c_int, V, V]
+    return L
+
+
+def cpu_buoyancy(L, disp, scales, bodies, hull, options=None, points=None):
+    """(results, points) of the CPU build, the options resolved as the runtime resolves ow_buoyancy_options; points: the previous step's
+    records (read with warm_start), updated in place"""
+    o = dict(options or {})
+    d = maps_u16(disp)
+    sc = np.ascontiguousarray(scales, np.float32)
+    b = np.ascontiguousarray(bodies, W.BUOYANCY_BODY)
+    h = np.ascontiguousarray(hull, W.HULL_POINT)
+    pts = points if points is not None else np.zeros(len(h), W.BUOYANCY_POINT)
+    res = np.zeros(len(b), W.BUOYANCY_RESULT)
+    rho = np.float32(o.get("density", 0.0) or RHO)
+    g = np.float32(o.get("gravity", 0.0) or G)
+    center = o.get("falloff_center")
+    cx, cz = center if center is not None else (0.0, 0.0)
+    L.harness_buoyancy(d.ctypes.data, d.shape[1], len(sc), sc.ctypes.data, b.ctypes.data, len(b), h.ctypes.data, len(h),
+                       o.get("max_iterations", 0) or 16, o.get("tolerance", 0.0) or 1e-3, int(center is not None), cx, cz, float(rho),
+                       float(np.float32(rho * g)), o.get("water_level", 0.0), int(bool(o.get("warm_start"))), pts.ctypes.data, res.ctypes.data)
+    return res, pts
+
+
+def rotation(axis, angle):
+    a = np.asarray(axis, np.float64) / np.linalg.norm(axis)
+    K = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
+    return np.eye(3) + math.sin(angle) * K + (1 - math.cos(angle)) * K @ K
+
+
+def make_scene(boxes):
+    """boxes: dicts of origin, basis (3x3), size, divisions and optional v / w / kl / kq -> (bodies, hull)"""
+    bodies = np.zeros(len(boxes), W.BUOYANCY_BODY)
+    hulls, off = [], 0
+    for i, bx in enumerate(boxes):
+        h = W.box_hull(bx["size"], bx["divisions"], body=i)
+        bodies[i]["transform"][:9] = np.asarray(bx.get("basis", np.eye(3)), np.float32).ravel()
+        bodies[i]["transform"][9:] = bx["origin"]
+        bodies[i]["linear_velocity"] = bx.get("v", (0, 0, 0))
+        bodies[i]["angular_velocity"] = bx.get("w", (0, 0, 0))
+        bodies[i]["linear_drag"] = bx.get("kl", 0.0)
+        bodies[i]["quadratic_drag"] = bx.get("kq", 0.0)
+        bodies[i]["point_offset"], bodies[i]["point_count"] = off, len(h)
+        hulls.append(h)
+        off += len(h)
+    return bodies, np.concatenate(hulls) if hulls else np.zeros(0, W.HULL_POINT)
+
+
+def twin(disp, scales, bodies, hull, p, options=None):
+    """The model restated in FP64 with NumPy at the undisplaced points p the solver found: per-body force, torque and submerged volume"""
+    o = dict(options or {})
+    rho, g, wl = o.get("density", RHO), o.get("gravity", G), o.get("water_level", 0.0)
+    F = np.zeros((len(bodies), 3))
+    Tq = np.zeros((len(bodies), 3))
+    SV = np.zeros(len(bodies))
+    H = T.displacement(disp, scales, p)[:, 1] * T.falloff(p, o.get("falloff_center"))
+    for b, body in enumerate(bodies):
+        sl = slice(body["point_offset"], body["point_offset"] + body["point_count"])
+        B = body["transform"][:9].astype(np.float64).reshape(3, 3)
+        org = body["transform"][9:].astype(np.float64)
+        r = hull[sl]["local"].astype(np.float64) @ B.T
+        w = r + org
+        d = wl + H[sl] - w[:, 1]
+        hh = hull[sl]["half_height"].astype(np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            s = np.where(hh > 0, np.clip((d + hh) / (2 * hh), 0, 1), (d > 0).astype(np.float64))
+        sv = hull[sl]["volume"].astype(np.float64) * s
+        u = body["linear_velocity"].astype(np.float64) + np.cross(body["angular_velocity"].astype(np.float64), r)
+        un = np.linalg.norm(u, axis=1)
+        drag = (rho * sv)[:, None] * (float(body["linear_drag"]) * u + float(body["quadratic_drag"]) * un[:, None] * u)
+        f = -drag
+        f[:, 1] += rho * g * sv
+        F[b], Tq[b], SV[b] = f.sum(0), np.cross(r, f).sum(0), sv.sum()
+    return F, Tq, SV
+
+
+def calm(n=64, cascades=1):
+    """maps of any content with map_scales.z = 0: no displacement, the surface is the plane y = water_level"""
+    rng = np.random.default_rng(0)
+    d = rng.normal(0, 1, (cascades, n, n, 4)).astype(np.float16)
+    sc = np.array([(1 / 50.0, 1 / 50.0, 0.0, 1.0)] * cascades, np.float32)
+    return maps_u16(d), sc
+
+
+# ---- 1. the ABI ----------------------------------------------------------------------------------------------------------------------
+
+HEADER = open(os.path.join(ROOT, "include", "ocean_waves.h")).read()
+
+
+def test_header_declares_buoyancy_and_the_library_exports_it():
+    build.build_library()
+    lib = _lib.load()
+    text = re.sub(r"/\*.*?\*/", "", HEADER, flags=re.S)
+    for name in NEW_FUNCTIONS:
+        assert re.search(r"\b%s\s*\(" % name, text), name
+        assert name in _lib.SIGNATURES
+        assert getattr(lib, name)
+    for struct in STRUCTS.values():
+        assert re.search(r"typedef struct %s \{" % struct, text), struct
+    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    assert set(NEW_FUNCTIONS) <= set(re.findall(r" T (ow_[a-z0-9_]+)", out))
+    assert lib.ow_abi_version() == 4
+
+
+def test_buoyancy_structs_agree_in_c_ctypes_numpy_and_the_harness(tmp_path, harness):
+    fields = []
+    for c in STRUCTS.values():
+        ct = getattr(_lib, c)
+        fields += [(c, None)] + [(c, f) for f, _ in ct._fields_]
+    src = '#include <stdio.h>\n#include <stddef.h>\n#include "ocean_waves.h"\nint main(void){\n'
+    for c, f in fields:
+        src += '    printf("%%zu\\n", %s);\n' % (f"sizeof({c})" if f is None else f"offsetof({c}, {f})")
+    src += '    printf("%u\\n", OW_BUOYANCY_WARM_START);\n    return 0;\n}\n'
+    exe = str(tmp_path / "buoyancy_layout")
+    subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-x", "c", "-", "-o", exe],
+                   input=src, text=True, check=True)
+    got = [int(v) for v in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split()]
+    want = []
+    for c, f in fields:
+        ct = getattr(_lib, c)
+        want.append(C.sizeof(ct) if f is None else getattr(ct, f).offset)
+    want.append(_lib.OW_BUOYANCY_WARM_START)
+    assert got == want
+    dtypes = {"ow_buoyancy_body": W.BUOYANCY_BODY, "ow_hull_point": W.HULL_POINT, "ow_buoyancy_options": W.BUOYANCY_OPTIONS,
+              "ow_buoyancy_point": W.BUOYANCY_POINT, "ow_buoyancy_result": W.BUOYANCY_RESULT}
+    for c, dt in dtypes.items():
+        ct = getattr(_lib, c)
+        assert dt.itemsize == C.sizeof(ct) and dt.names == tuple(f for f, _ in ct._fields_), c
+        assert all(dt.fields[f][1] == getattr(ct, f).offset for f in dt.names), c
+    assert [C.sizeof(getattr(_lib, c)) for c in STRUCTS.values()] == [96, 32, 64, 64, 64]
+    sizes = (C.c_int * 6)()
+    harness.harness_buoyancy_sizes(sizes)
+    assert list(sizes) == [96, 32, 64, 64, _lib.ow_buoyancy_point.body.offset, _lib.ow_buoyancy_result.max_residual.offset]
+
+
+def test_the_csharp_binding_shows_the_buoyancy_structs_and_functions():
+    """the five [StructLayout] structs list the C fields in order with the same sizes (the embedded options counted as
+    their 32 bytes), the three functions are bound with the header's argument counts, and §7 names them"""
+    import test_integration_shim as S
+    c_sizes = dict(S.C_SIZES, ow_query_options=32)
+    cs_sizes = dict(S.CS_SIZES, OwQueryOptions=32)
+
+    def fields(body, sizes, strip):
+        out = []
+        for decl in body.split(";"):
+            decl = " ".join(strip(decl).split())
+            if not decl:
+                continue
+            decl = decl[len("fixed "):] if decl.startswith("fixed ") else decl
+            typ, names = decl.split(" ", 1)
+            for n in names.split(","):
+                m = re.match(r"\s*([A-Za-z_]\w*)(\[(\d+)\])?\s*$", n)
+                out.append((m.group(1), sizes[typ] * int(m.group(3) or 1)))
+        return out
+
+    for cs, c in STRUCTS.items():
+        cbody = re.search(r"typedef struct %s \{(.*?)\}\s*%s\s*;" % (c, c), S.strip_comments(S.HEADER), flags=re.S).group(1)
+        csbody = re.search(r"struct %s \{(.*?)\n\}" % cs, S.strip_comments(S.SHIM), flags=re.S).group(1)
+        want = fields(cbody, c_sizes, lambda d: d)
+        got = fields(csbody, cs_sizes, lambda d: d.replace("public", ""))
+        assert got == want, (cs, got, want)
+        assert sum(s for _, s in want) == C.sizeof(getattr(_lib, c)), c
+    cfun = S.c_functions()
+    for name in NEW_FUNCTIONS:
+        m = re.search(r"\[DllImport\(Lib\)\]\s*public static extern int %s\((.*?)\);" % name, S.SHIM)
+        assert m, name
+        assert m.group(1).count(",") + 1 == cfun[name][1], name
+        assert "`%s`" % name in S.DOC.split("## 7. Index")[1], name
+
+
+# ---- 2. argument checks without a device ---------------------------------------------------------------------------------------------
+
+def test_buoyancy_argument_errors_without_a_device():
+    """the host checks run before the context is looked at: each bad argument is named, and nothing is written"""
+    lib = _lib.load()
+    bodies, hull = make_scene([dict(origin=(0, 0, 0), size=(1, 1, 1), divisions=(2, 2, 2)), dict(origin=(5, 0, 0), size=(1, 1, 1), divisions=(2, 1, 2))])
+    sc = np.ones((1, 4), np.float32)
+
+    def call(fn, b, h, opts=None, points=None, cascades=1):
+        res = np.frombuffer(np.full(len(b) * 64, 0xA5, np.uint8).tobytes(), W.BUOYANCY_RESULT).copy()
+        before = res.tobytes()
+        st = fn(None, b.ctypes.data, len(b), h.ctypes.data, len(h), sc.ctypes.data, cascades, C.byref(opts) if opts is not None else None,
+                res.ctypes.data, points.ctypes.data if points is not None else None)
+        assert res.tobytes() == before
+        return st, lib.ow_last_error()
+
+    def bad(fn, b, h, word, **kw):
+        st, msg = call(fn, b, h, **kw)
+        assert st == _lib.OW_ERR_INVALID and word in msg, msg
+
+    for fn in (lib.ow_buoyancy, lib.ow_group_buoyancy):
+        h = hull.copy()
+        h["volume"][3] = -1.0
+        bad(fn, bodies, h, b"volume")
+        h = hull.copy()
+        h["half_height"][0] = np.nan
+        bad(fn, bodies, h, b"half_height")
+        h = hull.copy()
+        h["body"][2] = 1
+        bad(fn, bodies, h, b"names body")
+        b = bodies.copy()
+        b["point_count"][1] += 1
+        bad(fn, b, hull, b"outside")
+        b = bodies.copy()
+        b["point_offset"][0] = -1
+        bad(fn, b, hull, b"outside")
+        b = bodies.copy()
+        b["point_count"][1] = 0   # its points are left without a body whose range holds them
+        bad(fn, b, hull, b"range does not hold")
+        bad(fn, bodies, hull, b"points_inout", opts=W.buoyancy_options({"warm_start": True}))
+        bad(fn, bodies, hull, b"finite", opts=W.buoyancy_options({"density": float("nan")}))
+        o = W.buoyancy_options({"water_level": 1.0})
+        o.flags = 0x10
+        bad(fn, bodies, hull, b"flags", opts=o)
+        bad(fn, bodies, hull, b"max_iterations", opts=W.buoyancy_options({"max_iterations": 99}))
+        st, msg = call(fn, bodies, hull)   # everything checkable is fine: only the missing context / group is left
+        assert st == _lib.OW_ERR_INVALID and b"null" in msg, msg
+    res = np.zeros(1, W.BUOYANCY_RESULT)
+    assert lib.ow_buoyancy_async(None, bodies.ctypes.data, len(bodies), hull.ctypes.data, len(hull), sc.ctypes.data, 1, None, res.ctypes.data,
+                                 None) == _lib.OW_ERR_INVALID
+    assert b"points_dev" in lib.ow_last_error()
+    assert lib.ow_buoyancy(None, bodies.ctypes.data, -1, hull.ctypes.data, len(hull), sc.ctypes.data, 1, None, res.ctypes.data, None) == _lib.OW_ERR_INVALID
+    with pytest.raises(ValueError):
+        W.buoyancy_options({"warm": True})
+    o = W.buoyancy_options({"density": 1000.0, "water_level": -2.0, "warm_start": True, "max_iterations": 4})
+    assert (o.density, o.gravity, o.water_level, o.flags, o.query.max_iterations) == (1000.0, 0.0, -2.0, _lib.OW_BUOYANCY_WARM_START, 4)
+
+
+def build_example(tmp_path):
+    exe = str(tmp_path / "buoyancy_host")
+    subprocess.run(["gcc", "-O2", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-I", os.path.join(ROOT, "include"),
+                    os.path.join(ROOT, "examples", "buoyancy_host.c"), "-o", exe, "-L", PKG, "-locean_waves", "-L", "/opt/rocm/lib", "-lamdhip64",
+                    f"-Wl,-rpath,{PKG}", "-Wl,-rpath,/opt/rocm/lib", "-Wl,-rpath-link,/opt/rocm/lib", "-lm"], check=True)
+    return exe
+
+
+def test_example_builds_as_pedantic_c99(tmp_path):
+    build.build_library()
+    exe = build_example(tmp_path)
+    import torch
+    if not torch.cuda.is_available():
+        r = subprocess.run([exe, "calm", "10"], capture_output=True, text=True)
+        assert r.returncode == 1 and "no CPU fallback" in r.stderr
+
+
+# ---- 3. hydrostatics on a calm sea ------------------------------------------------------------------------------------------------------
+
+def test_fully_submerged_box_at_rest(harness):
+    d, sc = calm()
+    V = 2.0 * 1.0 * 2.0
+    bodies, hull = make_scene([dict(origin=(3.0, -5.0, 7.0), size=(2, 1, 2), divisions=(4, 4, 4))])
+    res, pts = cpu_buoyancy(harness, d, sc, bodies, hull, {"water_level": 0.0})
+    r = res[0]
+    assert (pts["submerged"] == 1).all() and (pts["converged"] == 1).all() and (pts["iterations"] == 0).all() and (pts["height"] == 0).all()
+    assert r["force"][1] == pytest.approx(RHO_G * V, rel=1e-6) and r["force"][0] == 0 and r["force"][2] == 0
+    assert np.abs(r["torque"]).max() <= 1e-6 * RHO_G * V
+    assert r["submerged_volume"] == pytest.approx(V, rel=1e-6)
+    assert np.allclose(r["center_of_buoyancy"], (3.0, -5.0, 7.0), atol=1e-6)
+    assert (r["wetted_points"], r["unconverged_points"], r["invalid_points"]) == (64, 0, 0)
+
+
+def test_box_centred_at_the_water_level_gets_half(harness):
+    """even divisions in y and half_height = half a cell: the lower layers are exactly submerged, the upper ones exactly dry"""
+    d, sc = calm()
+    wl = 1.5
+    bodies, hull = make_scene([dict(origin=(-20.0, wl, 4.0), size=(2, 1, 2), divisions=(4, 4, 4))])
+    res, pts = cpu_buoyancy(harness, d, sc, bodies, hull, {"water_level": wl})
+    r = res[0]
+    assert r["force"][1] == pytest.approx(RHO_G * 2.0, rel=1e-6)
+    assert r["submerged_volume"] == pytest.approx(2.0, rel=1e-6) and r["wetted_points"] == 32
+    assert np.allclose(r["center_of_buoyancy"], (-20.0, wl - 0.25, 4.0), atol=1e-6)   # the centroid of the lower half
+    assert np.abs(r["torque"]).max() <= 1e-6 * RHO_G * 2.0
+
+
+@pytest.mark.parametrize("angle", [0.1, -0.2])
+def test_tilted_wide_box_gets_a_righting_torque(harness, angle):
+    """a 4 x 1 x 4 box half in the water, rolled about z: the side that went down displaces more, the torque about its centre turns it
+    back, and its size is the FP64 voxel sum's"""
+    d, sc = calm()
+    R = rotation((0, 0, 1), angle)
+    bodies, hull = make_scene([dict(origin=(10.0, 0.0, -3.0), basis=R, size=(4, 1, 4), divisions=(16, 8, 16))])
+    res, pts = cpu_buoyancy(harness, d, sc, bodies, hull)
+    tz = float(res[0]["torque"][2])
+    assert np.sign(tz) == -np.sign(angle)
+    p = pts["world"][:, [0, 2]]
+    F, Tq, SV = twin(d, sc, bodies, hull, p)
+    assert tz == pytest.approx(Tq[0, 2], rel=1e-5)
+    assert abs(res[0]["torque"][0]) <= 1e-5 * abs(tz) and abs(res[0]["torque"][1]) <= 1e-5 * abs(tz)
+    assert res[0]["force"][1] == pytest.approx(F[0, 1], rel=1e-6) and res[0]["submerged_volume"] == pytest.approx(SV[0], rel=1e-6)
+
+
+def test_drag_opposes_the_motion_and_scales_as_specified(harness):
+    d, sc = calm()
+    V = 2.0 * 1.0 * 2.0
+    v = np.array([2.0, 0.0, -1.0])
+    kl, kq = 0.5, 0.2
+    bodies, hull = make_scene([dict(origin=(0, -3, 0), size=(2, 1, 2), divisions=(4, 2, 4), v=v, kl=kl, kq=kq),
+                               dict(origin=(0, -3, 0), size=(2, 1, 2), divisions=(4, 2, 4), v=2 * v, kl=kl, kq=0.0),
+                               dict(origin=(0, -3, 0), size=(2, 1, 2), divisions=(4, 2, 4), w=(0, 1.5, 0), kl=kl, kq=kq)])
+    res, pts = cpu_buoyancy(harness, d, sc, bodies, hull)
+    want = -RHO * V * (kl * v + kq * np.linalg.norm(v) * v)
+    assert np.allclose(res[0]["force"][[0, 2]], want[[0, 2]], rtol=1e-5)
+    assert res[0]["force"][1] == pytest.approx(RHO_G * V, rel=1e-6)
+    assert np.dot(res[0]["force"], v) < 0
+    # linear drag alone is linear in the velocity
+    assert np.allclose(res[1]["force"][[0, 2]], -RHO * V * kl * 2 * v[[0, 2]], rtol=1e-5)
+    # spinning in place: no net drag force on a symmetric box, a torque against the spin, as the FP64 sum has it
+    F, Tq, _ = twin(d, sc, bodies, hull, pts["world"][:, [0, 2]])
+    assert abs(res[2]["force"][0]) < 1e-3 and abs(res[2]["force"][2]) < 1e-3
+    assert res[2]["torque"][1] < 0 and res[2]["torque"][1] == pytest.approx(Tq[2, 1], rel=1e-5)
+
+
+# ---- 4. the FP64 twin on the demo scene ------------------------------------------------------------------------------------------------
+
+def demo_scene(count=12, seed=0, spread=300.0, divisions=(4, 3, 6)):
+    rng = np.random.default_rng(seed)
+    boxes = []
+    for i in range(count):
+        R = rotation(rng.normal(size=3), rng.uniform(-0.6, 0.6))
+        boxes.append(dict(origin=(rng.uniform(-spread, spread), rng.uniform(-1.5, 1.0), rng.uniform(-spread, spread)), basis=R,
+                          size=(rng.uniform(2, 8), rng.uniform(1, 3), rng.uniform(4, 15)), divisions=divisions,
+                          v=rng.normal(0, 1, 3), w=rng.normal(0, 0.2, 3), kl=0.3, kq=0.1))
+    return make_scene(boxes)
+
+
+@pytest.fixture(scope="module")
+def demo_maps():
+    d, _, sc = generated_maps(1024, [0, 1, 2])
+    return d, sc
+
+
+def test_per_body_sums_against_the_fp64_twin(harness, demo_maps):
+    """Cascades 0-2 of the demo scene at 1024^2: per-body force, torque and submerged volume equal the FP64 restatement at the solver's p
+    within 2e-5 of the body's full buoyancy rho g sum V (torque: times the body's largest lever arm).  What separates the two is FP32
+    against FP64 per point -- positions, heights, the submerged fraction of the partly wet points -- not the sums."""
+    d, sc = demo_maps
+    bodies, hull = demo_scene()
+    for opts in ({}, {"water_level": 0.4, "density": 1000.0, "gravity": 9.8}, {"falloff_center": (30.0, -60.0)}):
+        res, pts = cpu_buoyancy(harness, d, sc, bodies, hull, opts)
+        F, Tq, SV = twin(d, sc, bodies, hull, pts["p"], opts)
+        for b, body in enumerate(bodies):
+            sl = slice(body["point_offset"], body["point_offset"] + body["point_count"])
+            full = opts.get("density", RHO) * opts.get("gravity", G) * hull[sl]["volume"].astype(np.float64).sum()
+            arm = np.linalg.norm(hull[sl]["local"], axis=1).max()
+            assert np.abs(res[b]["force"] - F[b]).max() <= 2e-5 * full, (b, res[b]["force"], F[b])
+            assert np.abs(res[b]["torque"] - Tq[b]).max() <= 2e-5 * full * arm, (b, res[b]["torque"], Tq[b])
+            assert abs(res[b]["submerged_volume"] - SV[b]) <= 2e-5 * hull[sl]["volume"].sum()
+        assert (res["invalid_points"] == 0).all() and res["wetted_points"].sum() > 0
+        assert 0 < (SV > 0).sum() and ((SV > 0) & (SV < hull["volume"].sum())).any()
+
+
+def test_cold_heights_are_the_querys_bit_for_bit(harness, query_harness, demo_maps):
+    """a point's height, p, residual and iteration counts are what ow_query_surface reports at (w.x, w.z): one displacement tap per cascade
+    gives the bits of sample_point's whole sum"""
+    d, sc = demo_maps
+    bodies, hull = demo_scene(count=40, seed=3, divisions=(5, 3, 5))
+    norm = np.zeros_like(d)
+    for opts, kw in (({}, {}), ({"falloff_center": (-40.0, 25.0), "max_iterations": 5}, {"falloff_center": (-40.0, 25.0), "max_iterations": 5})):
+        _, pts = cpu_buoyancy(harness, d, sc, bodies, hull, opts)
+        q = cpu_query(query_harness, d, norm, sc, pts["world"][:, [0, 2]], **kw)
+        for f in ("height", "p", "residual", "iterations", "evaluations", "converged"):
+            assert pts[f].tobytes() == q[f].tobytes(), f
+
+
+# ---- 5. the warm start ---------------------------------------------------------------------------------------------------------------
+
+def test_warm_start_saves_evaluations(harness):
+    """30 ticks of the demo scene's cascades 0-2 at 256^2 (the maps move with time), 64 bodies of 4 x 3 x 6 points moving 0.5 m per tick
+    and turning slowly.  Measured on the CPU build when this was written: 5.84 evaluations per point cold, 3.93 warm (iterations 4.38 /
+    2.72); converged 98.46 % cold, 98.59 % warm; where both converge, heights agree to 1e-2 m on 99.85 % of points (the rest sit on
+    folded crests, where the two starts may find different sheets)."""
+    from godotoceanwaves_amd.presets import cascade_preset as cp
+    import helpers as H
+    ids = [0, 1, 2]
+    g = H.oracle_generator(256, ids, native=True)
+    sc = np.array([(1 / cp(ci)["tile_length"][0], 1 / cp(ci)["tile_length"][1], 1.0, 1.0) for ci in ids], np.float32)
+    bodies, hull = demo_scene(count=64, seed=5, spread=200.0)
+    rng = np.random.default_rng(1)
+    heading = rng.uniform(0, 2 * np.pi, len(bodies))
+    step = 0.5 * np.stack([np.cos(heading), np.zeros_like(heading), np.sin(heading)], axis=1)
+    spin = [rotation(rng.normal(size=3), 0.01) for _ in bodies]
+    warm_pts = np.zeros(len(hull), W.BUOYANCY_POINT)
+    ev_c, ev_w, it_c, it_w, cv_c, cv_w, agree, both = [], [], [], [], [], [], 0, 0
+    for tick in range(30):
+        g.update_all(UPDATE_DELTA)
+        d = maps_u16(np.stack([np.asarray(g.displacement(i)) for i in range(len(ids))]))
+        _, cold = cpu_buoyancy(harness, d, sc, bodies, hull)
+        _, warm = cpu_buoyancy(harness, d, sc, bodies, hull, {"warm_start": True}, points=warm_pts)
+        if tick > 0:   # the first warm step starts from zeros: a cold start
+            ev_c.append(cold["evaluations"].mean())
+            ev_w.append(warm["evaluations"].mean())
+            it_c.append(cold["iterations"].mean())
+            it_w.append(warm["iterations"].mean())
+            cv_c.append(cold["converged"].mean())
+            cv_w.append(warm["converged"].mean())
+            m = (cold["converged"] == 1) & (warm["converged"] == 1)
+            both += m.sum()
+            agree += (np.abs(cold["height"][m] - warm["height"][m]) <= 1e-2).sum()
+        else:
+            assert warm.tobytes() == cold.tobytes()
+        bodies["transform"][:, 9:] += step.astype(np.float32)
+        for b in range(len(bodies)):
+            bodies[b]["transform"][:9] = (spin[b] @ bodies[b]["transform"][:9].astype(np.float64).reshape(3, 3)).astype(np.float32).ravel()
+    ec, ew, ic, iw, cc, cw = (float(np.mean(x)) for x in (ev_c, ev_w, it_c, it_w, cv_c, cv_w))
+    print(f"evaluations cold {ec:.2f} warm {ew:.2f}; iterations cold {ic:.2f} warm {iw:.2f}; converged cold {cc:.4f} warm {cw:.4f}; "
+          f"heights within 1e-2 m {agree / both:.5f}")
+    assert ew < ec
+    assert cw >= cc
+    assert agree >= 0.99 * both
+
+
+# ---- 6. no NaN or Inf --------------------------------------------------------------------------------------------------------------------
+
+def test_no_nan_or_inf_from_awkward_inputs(harness, demo_maps):
+    d, sc = demo_maps
+    bodies, hull = make_scene([dict(origin=(0, 0, 0), size=(2, 2, 2), divisions=(2, 2, 2)) for _ in range(8)])
+    bodies["transform"][0, 9] = np.nan                    # 0: a non-finite origin
+    bodies["transform"][1, 4] = np.inf                    # 1: a non-finite basis
+    bodies["linear_velocity"][2, 0] = 3e38                # 2: finite, but its drag overflows
+    bodies["linear_drag"][2] = 1.0
+    hull["half_height"][bodies[3]["point_offset"]:][:8] = 0.0   # 3: step submersion
+    hull["volume"][bodies[4]["point_offset"]:][:4] = 0.0        # 4: some points without volume
+    hull["body"][bodies[5]["point_offset"] + 1] = 6             # 5: a point naming the wrong body (the CPU build does not check)
+    bodies[6]["point_count"] = 0                          # 6: empty (its points now lie in no range)
+    bodies[7]["point_offset"] = len(hull) - 3             # 7: a range reaching past the end
+    bodies["transform"][7, 10] = -0.5
+    res, pts = cpu_buoyancy(harness, d, sc, bodies, hull)
+    for f in W.BUOYANCY_RESULT.names:
+        if res[f].dtype.kind == "f":
+            assert np.isfinite(res[f]).all(), f
+    for f in W.BUOYANCY_POINT.names:
+        if pts[f].dtype.kind == "f":
+            assert np.isfinite(pts[f]).all(), f
+    assert list(res["invalid_points"]) == [8, 8, 8, 0, 0, 1, 0, 5]   # 7: five indices past the end
+    assert (res["force"][:3] == 0).all() and (res["center_of_buoyancy"][0] == 0).all()
+    assert np.array_equal(res["center_of_buoyancy"][1], bodies["transform"][1, 9:])   # nothing submerged: o
+    assert (pts["body"][pts["body"] >= 0] == hull["body"][pts["body"] >= 0]).all()
+    assert (pts[pts["body"] < 0]["force"] == 0).all()
+    step = pts[bodies[3]["point_offset"]:][:8]
+    assert set(np.unique(step["submerged"])) <= {0.0, 1.0}
+    assert res[7]["wetted_points"] <= 3 and res[6]["wetted_points"] == 0
+    # a point beyond the FP32 range in its world position is invalid too
+    bodies, hull = make_scene([dict(origin=(3e38, 0, 0), size=(2, 2, 2), divisions=(2, 2, 2), basis=np.eye(3) * 2e38)])
+    res, pts = cpu_buoyancy(harness, d, sc, bodies, hull)
+    assert res[0]["invalid_points"] == 8 and np.isfinite(res[0]["center_of_buoyancy"]).all()
+
+
+# ---- 7-11. on the GPU --------------------------------------------------------------------------------------------------------------------
+
+def drive_scene(count, divisions, seed, spread=200.0):
+    return demo_scene(count=count, seed=seed, spread=spread, divisions=divisions)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n,ids", [(256, [0, 1, 2, 3]), (1024, [0, 1, 2])])
+def test_gpu_records_are_the_cpu_builds_bit_for_bit(harness, n, ids):
+    gen, params = make_gen(n, ids)
+    gen.run(UPDATE_DELTA, params, 3)
+    sc = scales_of(params)
+    d, _ = gpu_maps(gen, len(ids))
+    bodies, hull = drive_scene(300, (5, 3, 6), seed=n)
+    rng = np.random.default_rng(n)
+    step = rng.normal(0, 0.4, (len(bodies), 3)).astype(np.float32)
+    for opts in (None, {"falloff_center": (12.5, -40.0), "water_level": 0.3}, {"max_iterations": 3, "tolerance": 1e-4}):
+        o = opts or {}
+        got_pts = np.zeros(len(hull), W.BUOYANCY_POINT)
+        got = gen.buoyancy(bodies, hull, sc, opts, points=got_pts)
+        want, want_pts = cpu_buoyancy(harness, d, sc, bodies, hull, o)
+        assert got_pts.tobytes() == want_pts.tobytes(), opts
+        assert got.tobytes() == want.tobytes(), opts
+        # a warm step from those records, the bodies moved
+        moved = bodies.copy()
+        moved["transform"][:, 9:] += step
+        wo = dict(o, warm_start=True)
+        got_w = gen.buoyancy(moved, hull, sc, wo, points=got_pts)
+        want_w, want_pts = cpu_buoyancy(harness, d, sc, moved, hull, wo, points=want_pts)
+        assert got_pts.tobytes() == want_pts.tobytes(), opts
+        assert got_w.tobytes() == want_w.tobytes(), opts
+    assert np.isfinite(got["force"]).all() and (got["invalid_points"] == 0).all()
+    assert 0 < got["unconverged_points"].sum()   # last options: 3 iterations -- misses exist and are reported
+
+
+def _async_case(drive, stream=None, torch_stream=None):
+    """drive(gen, params, 8) / buoyancy_async / drive again / sync, against the synchronous call of a context that stopped after the first
+    drive: the asynchronous call read the maps of exactly that point of the stream"""
+    import torch
+    n, ids = 1024, [0, 1, 2, 3]
+    a, pa = make_gen(n, ids, stream=stream)
+    b, pb = make_gen(n, ids)
+    sc = scales_of(pa)
+    bodies, hull = drive_scene(200, (4, 3, 6), seed=11)
+    dev = lambda x: torch.from_numpy(np.frombuffer(x.tobytes(), np.uint8).copy()).to("cuda:0")   # noqa: E731
+    bodies_dev, hull_dev = dev(bodies), dev(hull)
+    res_dev = torch.zeros(len(bodies) * 64, dtype=torch.uint8, device="cuda:0")
+    pts_dev = torch.zeros(len(hull) * 64, dtype=torch.uint8, device="cuda:0")
+    torch.cuda.synchronize()
+    drive(a, pa, 8)
+    if torch_stream is not None:
+        with torch.cuda.stream(torch_stream):
+            a.buoyancy_async(bodies_dev, hull_dev, sc, res_dev, pts_dev)
+            copy = res_dev.to("cpu", non_blocking=False)   # the caller's own work, ordered by its stream alone
+        torch_stream.synchronize()
+    else:
+        a.buoyancy_async(bodies_dev, hull_dev, sc, res_dev, pts_dev)
+    drive(a, pa, 8)
+    a.sync()
+    got = np.frombuffer(res_dev.cpu().numpy().tobytes(), W.BUOYANCY_RESULT)
+    got_pts = np.frombuffer(pts_dev.cpu().numpy().tobytes(), W.BUOYANCY_POINT)
+    drive(b, pb, 8)
+    want_pts = np.zeros(len(hull), W.BUOYANCY_POINT)
+    want = b.buoyancy(bodies, hull, sc, points=want_pts)
+    assert got.tobytes() == want.tobytes()
+    assert got_pts.tobytes() == want_pts.tobytes()
+    if torch_stream is not None:
+        assert np.frombuffer(copy.numpy().tobytes(), W.BUOYANCY_RESULT).tobytes() == want.tobytes()
+    assert a.buoyancy(bodies, hull, sc).tobytes() != want.tobytes()   # the second half moved the maps
+    return a
+
+
+@pytest.mark.gpu
+def test_async_buoyancy_is_ordered_behind_both_chains_on_the_contexts_stream():
+    a = _async_case(lambda g, p, k: g.run(UPDATE_DELTA, p, k))
+    assert a.chain_stats() > 0
+
+
+@pytest.mark.gpu
+def test_async_buoyancy_on_a_callers_stream():
+    import torch
+    s = torch.cuda.Stream()
+    _async_case(lambda g, p, k: g.run(UPDATE_DELTA, p, k), stream=s.cuda_stream, torch_stream=s)
+
+
+@pytest.mark.gpu
+def test_async_buoyancy_between_look_ahead_ticks():
+    def ticks(g, p, k):
+        for _ in range(k):
+            g.update_all(UPDATE_DELTA, p)
+    a = _async_case(ticks)
+    hits, _ = a.lookahead_stats()
+    assert hits > 0
+
+
+@pytest.mark.gpu
+def test_device_side_range_and_body_mismatch_are_counted_not_read(harness):
+    """the async form cannot check device data: a range past the end, a negative offset and a point naming another body are counted invalid,
+    and nothing outside the arrays is read (the result equals the CPU build's, which never dereferences those indices)"""
+    import torch
+    n, ids = 256, [0, 1, 2]
+    gen, params = make_gen(n, ids)
+    gen.run(UPDATE_DELTA, params, 2)
+    sc = scales_of(params)
+    d, _ = gpu_maps(gen, len(ids))
+    bodies, hull = drive_scene(6, (4, 2, 4), seed=2, spread=50.0)
+    bodies[1]["point_offset"] = len(hull) - 10            # 32 points named, 22 past the end
+    bodies[2]["point_offset"] = -1000                     # all of it before the start
+    hull["body"][bodies[3]["point_offset"] + 4] = 5       # names body 5, which does not hold it
+    hull["body"][bodies[4]["point_offset"] + 2] = 1000    # names no body at all
+    dev = lambda x: torch.from_numpy(np.frombuffer(x.tobytes(), np.uint8).copy()).to("cuda:0")   # noqa: E731
+    res_dev = torch.zeros(len(bodies) * 64, dtype=torch.uint8, device="cuda:0")
+    pts_dev = torch.zeros(len(hull) * 64, dtype=torch.uint8, device="cuda:0")
+    gen.buoyancy_async(dev(bodies), dev(hull), sc, res_dev, pts_dev)
+    gen.sync()
+    got = np.frombuffer(res_dev.cpu().numpy().tobytes(), W.BUOYANCY_RESULT)
+    want, want_pts = cpu_buoyancy(harness, d, sc, bodies, hull)
+    assert got.tobytes() == want.tobytes()
+    assert np.frombuffer(pts_dev.cpu().numpy().tobytes(), W.BUOYANCY_POINT).tobytes() == want_pts.tobytes()
+    assert got[1]["invalid_points"] >= 22 and got[2]["invalid_points"] == 32 and got[3]["invalid_points"] == 1 and got[4]["invalid_points"] == 1
+    with pytest.raises(_lib.OceanWavesError) as e:   # the synchronous form refuses the same arrays on the host
+        gen.buoyancy(bodies, hull, sc)
+    assert e.value.status == _lib.OW_ERR_INVALID
+
+
+@pytest.mark.gpu
+def test_group_buoyancy_equals_a_single_context():
+    from godotoceanwaves_amd import WaveCascadeParameters, WaveGeneratorGroup
+    n, ids = 512, [0, 1, 2, 3]
+    grp = WaveGeneratorGroup()
+    grp.map_size = n
+    grp.init_gpu([0, 0], 2)
+    pg = [WaveCascadeParameters(**cascade_preset(ci)) for ci in ids]
+    single, ps = make_gen(n, ids)
+    sc = scales_of(ps)
+    bodies, hull = drive_scene(100, (4, 3, 5), seed=4)
+    with pytest.raises(_lib.OceanWavesError) as e:   # nothing gathered yet
+        grp.buoyancy(bodies, hull, sc)
+    assert e.value.status == _lib.OW_ERR_STATE
+    grp.run(UPDATE_DELTA, pg, 4)
+    single.run(UPDATE_DELTA, ps, 4)
+    grp.gather_begin()
+    grp.gather_wait()
+    for opts in (None, {"falloff_center": (-30.0, 60.0), "warm_start": True}):
+        pg_pts = np.zeros(len(hull), W.BUOYANCY_POINT)
+        ps_pts = np.zeros(len(hull), W.BUOYANCY_POINT)
+        assert grp.buoyancy(bodies, hull, sc, opts, points=pg_pts).tobytes() == single.buoyancy(bodies, hull, sc, opts, points=ps_pts).tobytes()
+        assert pg_pts.tobytes() == ps_pts.tobytes()
+
+
+@pytest.mark.gpu
+def test_example_floats_a_box(tmp_path):
+    exe = build_example(tmp_path)
+    r = subprocess.run([exe, "calm", "400"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr
+    out = dict(kv.split("=") for kv in r.stdout.split())
+    draft, want = float(out["draft"]), float(out["expected_draft"])
+    assert abs(draft - want) <= 0.02 * want, r.stdout
+    r = subprocess.run([exe, "demo", "400"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr
+    out = dict(kv.split("=") for kv in r.stdout.split())
+    assert out["finite"] == "1" and out["afloat"] == "1", r.stdout
