@@ -87,10 +87,11 @@ struct ow_context {
     bool spectrum_resident[OW_MAX_CASCADES] = {};
     bool always_regenerate = false;  // OW_FLAG_ALWAYS_REGENERATE_SPECTRUM: every dirty flag launches k_spectrum, as the reference does
     uint64_t spectra_generated = 0, spectra_skipped = 0;  // ow_spectrum_stats
-    // ow_update_all's adaptive look-ahead (lookahead_tick below): a pass 1 of the NEXT tick, speculated with the caller's last delta
+    // ow_update_all's adaptive look-ahead (lookahead_tick below): a pass 1 of the NEXT tick, speculated with the caller's last delta.
+    // Invariant: queued > 0 exactly while the scratch holds pass 1 of `queued` ticks that nothing has disturbed since; whatever else
+    // writes the scratch (or may have corrupted it) sets queued = 0, and no field below is read while it is 0.
     struct Lookahead {
         static constexpr int kMaxAhead = 4;  // ticks of pass 1 one launch may compute ahead (group kernel; the pair kernel takes one)
-        bool armed = false;            // the scratch holds pass 1 of `queued` ticks that nothing has disturbed since
         int count = 0, mode = 0;       // cascades per tick; 1 = compact family (pair kernel), 2 = layer-parallel compact family (group kernel)
         int queued = 0, head = 0;      // ring of ticks computed ahead: entries head, head + 1, .. (mod kMaxAhead)
         int group[kMaxAhead] = {};     // scratch group (of `stride` launch slots) that holds each entry's intermediate
@@ -335,7 +336,7 @@ ow_status ensure_scratch(ow_context *c, int slots) {
     c->buf.pcol = pcol;
     c->buf.rrow = rrow;
     c->scratch_slots = slots;
-    c->la.armed = false;                 // (a speculated pass 1 went with the old buffer, too)
+    c->la.queued = 0;                    // (a speculated pass 1 went with the old buffer, too)
     c->ra.armed = false;
     for (int &sl : c->slot_of) sl = -1;  // (the reference-layout view of the last batch's intermediate went with the old buffer)
     return OW_OK;
@@ -399,7 +400,6 @@ ow_status consume_status(ow_context *c) {
     // ... and so does whatever those launches computed AHEAD: a speculated pass 1 (of cascades that are not even enqueued yet, or of the same
     // cascade one tick later at 2048^2, where pass 1 has a bounded wait of its own) may be as corrupt as the maps.  The queue is dropped: the
     // ticks after a fault recompute their pass 1.
-    c->la.armed = false;
     c->la.queued = 0;
     c->ra.armed = false;
     for (int i = 0; i < OW_MAX_CASCADES; ++i)
@@ -450,6 +450,11 @@ ow_status validate_record(const ow_cascade_params &p, int index) {
     if (!(p.tile_length[0] > 0.0f) || !(p.tile_length[1] > 0.0f)) return fail(OW_ERR_INVALID, "cascade %d: tile_length must be positive", index);
     return OW_OK;
 }
+// A record the merged launches and the look-ahead queue can take as it is: one validate_record accepts, with no spectrum to generate.  Asks
+// without reporting: a record that fails here takes the ordinary path, whose own checks report it.
+bool launchable(const ow_cascade_params &p) {
+    return !p.should_generate_spectrum && finite_record(p) && p.tile_length[0] > 0.0f && p.tile_length[1] > 0.0f;
+}
 }  // namespace
 namespace ow {
 // what ow_update checks before it changes anything (a group checks ALL shards' records with it before any shard starts)
@@ -499,19 +504,29 @@ void pack_spectrum(const ow_context *c, int cascade, const ow_cascade_params &p,
 // spectrum is a deterministic function of the thirteen packed words (and the map size), so when a dirty record packs to exactly the words
 // layer `cascade`'s resident spectrum was generated from, regenerating would write the same bits: the flag is simply consumed.  That also
 // keeps such a record on the merged launches and the look-ahead, which step aside for a spectrum that has to be generated.
-bool spectrum_is_resident(const ow_context *c, int cascade, const ow_cascade_params &p) {
-    if (c->always_regenerate || cascade < 0 || cascade >= OW_MAX_CASCADES || !c->spectrum_resident[cascade]) return false;
+// (pc, w: the pack of p, for a spectrum launch.)  Asked of validated, dirty records only.
+bool spectrum_is_resident(const ow_context *c, int cascade, const ow_cascade_params &p, ow::SpectrumPC &pc, uint32_t (&w)[16]) {
+    pack_spectrum(c, cascade, p, pc, w);
+    return !c->always_regenerate && c->spectrum_resident[cascade] && std::memcmp(w, c->pc_words[cascade].spectrum, sizeof(w)) == 0;
+}
+// The dirty flag of validated record p of layer `cascade` (wave_generator.gd:68-72): consumed where the spectrum is resident; otherwise, with
+// `generate` (enqueue), k_spectrum regenerates the layer first -- without it the flag stays and the caller takes the ordinary path.
+ow_status settle_spectrum(ow_context *c, int cascade, ow_cascade_params &p, bool generate) {
+    if (!p.should_generate_spectrum) return OW_OK;
     ow::SpectrumPC pc;
     uint32_t w[16];
-    pack_spectrum(c, cascade, p, pc, w);
-    return std::memcmp(w, c->pc_words[cascade].spectrum, sizeof(w)) == 0;
-}
-// consumes the dirty flag of armed record `cascade` if its spectrum is resident (where a record ENTERS the context: ow_update, ow_set_cascade_params)
-void settle_dirty_flag(ow_context *c, int cascade, ow_cascade_params &p) {
-    if (p.should_generate_spectrum && finite_record(p) && spectrum_is_resident(c, cascade, p)) {
-        p.should_generate_spectrum = 0;
+    if (spectrum_is_resident(c, cascade, p, pc, w)) {
         ++c->spectra_skipped;
+    } else {
+        if (!generate) return OW_OK;
+        c->spectrum_resident[cascade] = false;
+        OW_HIP(ow::launch_spectrum(c->n, cascade, pc, c->buf, main_stream(c)));
+        std::memcpy(c->pc_words[cascade].spectrum, w, sizeof(w));  // wave_generator.gd:71, in the reference's order
+        c->spectrum_resident[cascade] = true;
+        ++c->spectra_generated;
     }
+    p.should_generate_spectrum = 0;
+    return OW_OK;
 }
 
 // render_context.gd:122-135 for the modulate and unpack blocks of one cascade (wave_generator.gd:73,85)
@@ -531,6 +546,13 @@ void record_frame_constants(ow_context *c, int cascade, const ow_cascade_params 
     c->pc_valid[cascade] = true;
 }
 
+// the foam rates one update with this delta arms (wave_generator.gd:104-106)
+inline void set_foam_rates(ow_cascade_params &p, double delta) {
+    p.foam_grow_rate = delta * p.foam_amount * 7.5;
+    const double d = 10.0 - p.foam_amount;
+    p.foam_decay_rate = delta * (d > 0.5 ? d : 0.5) * 1.15;
+}
+
 // _update() for a batch of cascade indices (wave_generator.gd:65-85)
 ow::CascadeFrame frame_of(const ow_cascade_params &p, int cascade) {
     ow::CascadeFrame cf;
@@ -545,9 +567,30 @@ ow::CascadeFrame frame_of(const ow_cascade_params &p, int cascade) {
     return cf;
 }
 
+// A new batch recomputes THESE layers' maps (the foam state a faulted batch left behind is the caller's to restore); the other layers keep
+// what they hold, marks included.
+void mark_recomputed(ow_context *c, uint32_t layers) {
+    c->maps_faulted &= ~layers;
+    c->enqueued_since_sync |= layers;
+}
+// launch slot `slot` of a batch being started recomputes layer `cascade` from record p
+void start_slot(ow_context *c, ow::FrameArgs &args, int slot, int cascade, const ow_cascade_params &p) {
+    mark_recomputed(c, 1u << cascade);
+    record_frame_constants(c, cascade, p);
+    args.c[slot] = frame_of(p, cascade);
+}
+// the batch just started is the most recent one (ow_last_kernel_family, ow_last_batch_cascades, ow_probe_kernel_times relaunches it);
+// family -1: the one kernel_family picks for `count` cascades.  Its intermediate is not in the reference's layout (enqueue says otherwise).
+void note_batch(ow_context *c, const ow::FrameArgs &args, int count, int family = -1) {
+    c->last_args = args;
+    c->last_count = count;
+    c->last_family = family >= 0 ? family : ow::kernel_family(c->n, count, c->kernel_mode);
+    for (int &sl : c->slot_of) sl = -1;
+}
+
 ow_status enqueue(ow_context *c, ow_cascade_params *params, const int *idx, int count) {
     if (count <= 0) return OW_OK;
-    c->la.armed = false;  // this path uses the scratch intermediate from slot 0 on: a speculated pass 1 (lookahead_tick) does not survive it
+    c->la.queued = 0;     // this path uses the scratch intermediate from slot 0 on: a speculated pass 1 (lookahead_tick) does not survive it
     c->ra.armed = false;  // ... nor does what a run computed ahead for the next run
     ow::FrameArgs args;
     std::memset(&args, 0, sizeof(args));
@@ -555,28 +598,9 @@ ow_status enqueue(ow_context *c, ow_cascade_params *params, const int *idx, int 
     for (int i = 0; i < count; ++i)
         if (ow_status st = validate_record(params[idx[i]], idx[i]); st != OW_OK) return st;
     for (int i = 0; i < count; ++i) {
-        // a new batch recomputes THESE layers' maps (the foam state a faulted batch left behind is the caller's to restore); the other
-        // layers keep what they hold, marks included
-        c->maps_faulted &= ~(1u << idx[i]);
-        c->enqueued_since_sync |= 1u << idx[i];
-        ow_cascade_params &p = params[idx[i]];
-        if (p.should_generate_spectrum) {  // :68-72
-            ow::SpectrumPC pc;
-            uint32_t w[16];
-            pack_spectrum(c, idx[i], p, pc, w);
-            if (!c->always_regenerate && c->spectrum_resident[idx[i]] && std::memcmp(w, c->pc_words[idx[i]].spectrum, sizeof(w)) == 0) {
-                ++c->spectra_skipped;  // the same thirteen words: the resident spectrum IS what the dispatch would write (spectrum_is_resident)
-            } else {
-                c->spectrum_resident[idx[i]] = false;
-                OW_HIP(ow::launch_spectrum(c->n, idx[i], pc, c->buf, main_stream(c)));
-                std::memcpy(c->pc_words[idx[i]].spectrum, w, sizeof(w));  // wave_generator.gd:71, in the reference's order
-                c->spectrum_resident[idx[i]] = true;
-                ++c->spectra_generated;
-            }
-            p.should_generate_spectrum = 0;
-        }
-        record_frame_constants(c, idx[i], p);
-        args.c[i] = frame_of(p, idx[i]);
+        mark_recomputed(c, 1u << idx[i]);  // (before its spectrum launch, too: a launch that fails there leaves the layer marked)
+        if (ow_status st = settle_spectrum(c, idx[i], params[idx[i]], true); st != OW_OK) return st;
+        start_slot(c, args, i, idx[i], params[idx[i]]);
     }
     // Launch in batches of batch_size() cascades (see there).  Cascades are independent, so batching does not change any result.
     const int per_batch = batch_size(c, count);
@@ -587,11 +611,8 @@ ow_status enqueue(ow_context *c, ow_cascade_params *params, const int *idx, int 
         for (int i = 0; i < nb; ++i) part.c[i] = args.c[b0 + i];
         part.c[0].fault = (int32_t)c->inject_fault;  // debug hook (ow_debug_inject_fault): this batch only
         c->inject_fault = 0;
-        c->last_args = part;
+        note_batch(c, part, nb);
         c->last_args.c[0].fault = 0;
-        c->last_count = nb;
-        c->last_family = ow::kernel_family(c->n, nb, c->kernel_mode);
-        for (int &sl : c->slot_of) sl = -1;
         for (int i = 0; i < nb; ++i) c->slot_of[part.c[i].cascade] = i;
         hipEvent_t *ev = nullptr;
         if (c->timing) {
@@ -654,22 +675,38 @@ struct LookaheadPlan {
     int next[ow_context::Lookahead::kMaxAhead][OW_MAX_CASCADES];  // their cascades: the same ones a tick later each (ow_update_all), or the ones after `now` (ow_process)
     float next_time[ow_context::Lookahead::kMaxAhead][OW_MAX_CASCADES];
 };
+// FP32 times are compared bit for bit
+bool same_f32(float a, float b) { return std::memcmp(&a, &b, 4) == 0; }
+// does queue entry e hold, in launch slot `slot`, pass 1 of `cascade` as record p asks for it: its FP32 time and tile lengths?
+bool entry_serves(const ow_context::Lookahead &la, int e, int slot, int cascade, const ow_cascade_params &p) {
+    return la.cascade[e][slot] == cascade && same_f32((float)p.time, la.time[e][slot]) && p.tile_length[0] == la.tile_x[e][slot] && p.tile_length[1] == la.tile_y[e][slot];
+}
+// queue entry k, launch slot `slot`: pass 1 of `cascade` (tile lengths from record p) at FP32 time t, which the refilling launch computes in its
+// pass-1 launch slot first1 + slot of tick k
+void fill_entry(ow_context::Lookahead &la, ow::TickGroupArgs &ga, int k, int slot, int first1, int cascade, float t, const ow_cascade_params &p) {
+    la.time[k][slot] = ga.time1[k][first1 + slot] = t;
+    la.cascade[k][slot] = cascade;
+    la.tile_x[k][slot] = p.tile_length[0];
+    la.tile_y[k][slot] = p.tile_length[1];
+}
+// The look-ahead's pass-1 items (group kernel, `ticks` x n^2 texels of pass 1 per launch).  The layer-parallel form: with ONE tick of pass 2 per
+// launch the launch is as empty as a lone tick, where more and smaller blocks win (measured, us per tick, one launch per pass | look-ahead with lp
+// items | with k_pass1c-shaped items: 256^2 x 4 15.3 | 11.1 | 15.9; 512^2 x 1 15.6 | 11.4 | 17.0; 512^2 x 4 27.3 | 26.2 | 28.4; 1024^2 x 1 29.9 |
+// 25.8 | 28.1; profiles/r04_lookahead.txt) ... and k_pass1c's form from 512 Ki texels per tick on, where the several ticks of pass 1 of one launch
+// are enough work for the fewer, larger items (us per tick at four ticks ahead, lp | compact: 256^2 x 4 9.7 | 10.5, 512^2 x 1 10.2 | 11.2, 256^2 x 8
+// 13.3 | 12.2, 512^2 x 2 13.7 | 12.7, 512^2 x 4 23.9 | 19.7, 1024^2 x 1 23.0 | 19.7; profiles/r04_lookahead_depth.txt)
+int lookahead_p1_compact(const ow_context *c, int ticks) {
+    return c->group_p1_form >= 0 ? c->group_p1_form : ((size_t)ticks * c->n * c->n >= ((size_t)2 << 20) ? 1 : 0);
+}
 // returns true if the launch has been made here (status in *out); false: the caller takes the ordinary path
 bool lookahead_launch(ow_context *c, const LookaheadPlan &pl, ow_status *out) {
     ow_context::Lookahead &la = c->la;
     constexpr int kRing = ow_context::Lookahead::kMaxAhead;
     const int count = pl.now_count, mode = lookahead_mode(c, count);
     bool eligible = mode != 0;
-    for (int i = 0; eligible && i < count; ++i) {
-        const ow_cascade_params &p = c->pass_parameters[pl.now[i]];
-        eligible = !p.should_generate_spectrum && validate_record(p, pl.now[i]) == OW_OK;
-    }
-    bool hit = la.armed && la.queued > 0 && eligible && la.count == count && la.mode == mode;
-    for (int i = 0; hit && i < count; ++i) {
-        const ow_cascade_params &p = c->pass_parameters[pl.now[i]];
-        const float t = (float)p.time;
-        hit = la.cascade[la.head][i] == pl.now[i] && std::memcmp(&t, &la.time[la.head][i], 4) == 0 && p.tile_length[0] == la.tile_x[la.head][i] && p.tile_length[1] == la.tile_y[la.head][i];
-    }
+    for (int i = 0; eligible && i < count; ++i) eligible = launchable(c->pass_parameters[pl.now[i]]);
+    bool hit = la.queued > 0 && eligible && la.count == count && la.mode == mode;
+    for (int i = 0; hit && i < count; ++i) hit = entry_serves(la, la.head, i, pl.now[i], c->pass_parameters[pl.now[i]]);
     // the launch slots of the cascades computed ahead: the very slots of `now` where they are the same cascades (the next ticks of an
     // ow_update_all), slots of their own behind them otherwise (the cascades the next ow_process calls will take)
     bool ahead = eligible && pl.next_count == count && pl.ahead_ticks >= 1 && !la.hold;
@@ -685,39 +722,23 @@ bool lookahead_launch(ow_context *c, const LookaheadPlan &pl, ow_status *out) {
     int depth = !ahead ? 0 : std::min(pl.ahead_ticks, mode == 2 ? c->ahead_depth : 1);
     if (!same) depth = std::min(depth, (OW_MAX_CASCADES - count) / count);
     for (int k = 0; k < depth; ++k)
-        for (int i = 0; i < count; ++i) {
-            const ow_cascade_params &p = c->pass_parameters[pl.next[k][i]];
-            if (p.should_generate_spectrum || validate_record(p, pl.next[k][i]) != OW_OK || !std::isfinite(pl.next_time[k][i])) depth = k;
-        }
+        for (int i = 0; i < count; ++i)
+            if (!launchable(c->pass_parameters[pl.next[k][i]]) || !std::isfinite(pl.next_time[k][i])) depth = k;
     ahead = depth >= 1;
     const int first1 = (ahead && !same) ? count : 0, step1 = first1;
     const int stride = mode == 1 ? c->pair_slots : count, groups = (mode == 2 ? kRing : 1) + 1;
-    if (ahead && ensure_scratch(c, groups * stride) != OW_OK) ahead = false;  // (growing the scratch disarms: checked before `hit` is used)
-    hit = hit && la.armed;
+    if (ahead && ensure_scratch(c, groups * stride) != OW_OK) ahead = false;  // (growing the scratch empties the queue: checked before `hit` is used)
+    hit = hit && la.queued > 0;
     if (!hit) la.queued = 0;  // whatever was computed ahead was computed for something else
     const bool refill = ahead && (hit ? la.queued == 1 : true);  // (a hit that leaves entries queued launches its pass 2 alone)
-    if (!hit && !refill) {
-        la.armed = false;
-        return false;
-    }
+    if (!hit && !refill) return false;
     c->ra.armed = false;  // (the launches below write the scratch: whatever a run had computed ahead for a next run is gone)
     ow::FrameArgs args;
     std::memset(&args, 0, sizeof(args));
-    for (int i = 0; i < count; ++i) {
-        const int cascade = pl.now[i];
-        const ow_cascade_params &p = c->pass_parameters[cascade];
-        c->maps_faulted &= ~(1u << cascade);
-        c->enqueued_since_sync |= 1u << cascade;
-        record_frame_constants(c, cascade, p);
-        args.c[i] = frame_of(p, cascade);
-    }
-    c->last_args = args;  // (the probe relaunches THIS tick's cascades)
-    c->last_count = count;
-    c->last_family = ow::kernel_family(c->n, count, c->kernel_mode);
-    for (int &sl : c->slot_of) sl = -1;
+    for (int i = 0; i < count; ++i) start_slot(c, args, i, pl.now[i], c->pass_parameters[pl.now[i]]);
+    note_batch(c, args, count);  // (the probe relaunches THIS tick's cascades)
     auto launched = [&](hipError_t e) {
         if (e == hipSuccess) return true;
-        la.armed = false;
         la.queued = 0;
         *out = fail(OW_ERR_HIP, "look-ahead launch failed: %s", hipGetErrorString(e));
         return false;
@@ -741,10 +762,7 @@ bool lookahead_launch(ow_context *c, const LookaheadPlan &pl, ow_status *out) {
             for (int i = 0; i < count; ++i) {
                 const ow_cascade_params &p = c->pass_parameters[pl.next[k][i]];
                 if (!same) args.c[first1 + k * step1 + i] = frame_of(p, pl.next[k][i]);  // (pass 1 takes the tile lengths and the layer from it; the times from time1)
-                la.time[k][i] = ga.time1[k][first1 + i] = pl.next_time[k][i];
-                la.cascade[k][i] = pl.next[k][i];
-                la.tile_x[k][i] = p.tile_length[0];
-                la.tile_y[k][i] = p.tile_length[1];
+                fill_entry(la, ga, k, i, first1, pl.next[k][i], pl.next_time[k][i], p);
             }
         }
         la.queued = depth;
@@ -760,16 +778,9 @@ bool lookahead_launch(ow_context *c, const LookaheadPlan &pl, ow_status *out) {
         ga.slots1 = refill ? count : 0;
     } else {
         ga.slots = count;
-        // pass-1 items in the layer-parallel form: with ONE tick of pass 2 per launch the launch is as empty as a lone tick, where more and smaller
-        // blocks win (measured, us per tick, one launch per pass | look-ahead with lp items | with k_pass1c-shaped items: 256^2 x 4 15.3 | 11.1 |
-        // 15.9; 512^2 x 1 15.6 | 11.4 | 17.0; 512^2 x 4 27.3 | 26.2 | 28.4; 1024^2 x 1 29.9 | 25.8 | 28.1; profiles/r04_lookahead.txt)
-        // ... and in k_pass1c's form from 512 Ki texels per tick on, where the several ticks of pass 1 of one launch are enough work for the fewer,
-        // larger items (us per tick at four ticks ahead, lp | compact: 256^2 x 4 9.7 | 10.5, 512^2 x 1 10.2 | 11.2, 256^2 x 8 13.3 | 12.2,
-        // 512^2 x 2 13.7 | 12.7, 512^2 x 4 23.9 | 19.7, 1024^2 x 1 23.0 | 19.7; profiles/r04_lookahead_depth.txt)
-        ga.p1_compact = c->group_p1_form >= 0 ? c->group_p1_form : ((size_t)count * depth * c->n * c->n >= ((size_t)2 << 20) ? 1 : 0);
+        ga.p1_compact = lookahead_p1_compact(c, count * depth);
     }
     if (!launched(launch_group(c, args, ga))) return true;
-    la.armed = la.queued > 0;
     la.count = count;
     la.mode = mode;
     la.cur_group = cur;
@@ -852,19 +863,14 @@ int prearm_depth(const ow_context *c, const ow_cascade_params *records, int coun
     if (lookahead_mode(c, 1) != 2) return 0;  // the group kernel's form only (a cascade of the layer-parallel compact family: <= 1 Mi texels)
     const int idx = count - 1;
     int depth = std::min(idx + 1, std::min(kRing, c->ahead_depth));
-    for (int k = 0; k < depth; ++k) {
-        const ow_cascade_params &p = records[idx - k];
-        if (p.should_generate_spectrum || validate_record(p, idx - k) != OW_OK) depth = k;
-    }
+    for (int k = 0; k < depth; ++k)
+        if (!launchable(records[idx - k])) depth = k;
     return depth;
 }
 // does the head of the queue hold pass 1 of `cascade` as record p asks for it (one cascade per entry: the reference's schedule)?
 bool queue_head_serves(const ow_context *c, int cascade, const ow_cascade_params &p) {
     const ow_context::Lookahead &la = c->la;
-    if (!la.armed || la.queued < 1 || la.count != 1 || la.mode != 2) return false;
-    const float t = (float)p.time;
-    const int h = la.head;
-    return la.cascade[h][0] == cascade && std::memcmp(&t, &la.time[h][0], 4) == 0 && p.tile_length[0] == la.tile_x[h][0] && p.tile_length[1] == la.tile_y[h][0];
+    return la.queued >= 1 && la.count == 1 && la.mode == 2 && entry_serves(la, la.head, 0, cascade, p);
 }
 // THE LEFTOVER RIDES WITH THE NEXT UPDATE'S PASS 1 (round 6).  On the scene's own cadence (144 Hz frames, an update every third frame, one ow_process per
 // frame) every update finds ONE cascade of the previous arm unprocessed, its pass 1 waiting at the head of the queue, and used to launch its pass 2 alone
@@ -878,12 +884,11 @@ int prearm_launch(ow_context *c, const ow_cascade_params *records, int count, co
     const int idx = count - 1;
     if (lookahead_mode(c, 1) != 2) return 0;  // the group kernel's form only; a context whose single cascades take the pair kernel (2048^2 x 1) keeps whatever
                                               // its last ow_process computed ahead for this update -- that call's own check decides
-    if (!flush && la.armed && la.queued > 0) {
+    if (!flush && la.queued > 0) {
         // Work computed ahead is waiting already.  If its head is what the first ow_process of this update will ask for (a regular cadence: the previous
         // update's last ow_process guessed right), leave it.  If it cannot hit -- pair-kernel entries left by ow_update_all, a guess made with another
         // delta -- that call would miss, launch a lone pass 1 and refill: the round-4 path.  Drop the stale queue and pre-arm instead.
         if (queue_head_serves(c, idx, records[idx])) return 0;
-        la.armed = false;
         la.queued = 0;
     }
     const int depth = prearm_depth(c, records, count);
@@ -900,14 +905,8 @@ int prearm_launch(ow_context *c, const ow_cascade_params *records, int count, co
     std::memset(&args, 0, sizeof(args));
     std::memset(&ga, 0, sizeof(ga));
     if (flush) {  // launch slot 0: pass 2 of cascade 0 of the previous arm, exactly as flush_from_queue would have launched it
-        c->maps_faulted &= ~1u;
-        c->enqueued_since_sync |= 1u;
-        record_frame_constants(c, 0, *flush);
-        args.c[0] = frame_of(*flush, 0);
-        c->last_args = args;
-        c->last_count = 1;
-        c->last_family = ow::kernel_family(c->n, 1, c->kernel_mode);
-        for (int &sl : c->slot_of) sl = -1;
+        start_slot(c, args, 0, 0, *flush);
+        note_batch(c, args, 1);
         ga.d2 = 1;
         ga.tbase2[0] = cur * stride;
         ++la.hits;
@@ -918,24 +917,19 @@ int prearm_launch(ow_context *c, const ow_cascade_params *records, int count, co
         la.group[k] = (cur + 1 + k) % groups;
         ga.tbase1[k] = la.group[k] * stride;
         args.c[first1 + k] = frame_of(p, idx - k);   // pass-1 "tick" k = launch slot first1 + k (step1 = 1): tile lengths and layer from it, the time from time1
-        la.time[k][0] = ga.time1[k][first1] = (float)p.time;
-        la.cascade[k][0] = idx - k;
-        la.tile_x[k][0] = p.tile_length[0];
-        la.tile_y[k][0] = p.tile_length[1];
+        fill_entry(la, ga, k, 0, first1, idx - k, (float)p.time, p);
     }
     ga.d1 = depth;
     ga.first1 = first1;
     ga.step1 = 1;
     ga.slots = 1;
-    ga.p1_compact = c->group_p1_form >= 0 ? c->group_p1_form : ((size_t)depth * c->n * c->n >= ((size_t)2 << 20) ? 1 : 0);
+    ga.p1_compact = lookahead_p1_compact(c, depth);
     if (ow::launch_tick_group(c->n, args, ga, c->buf, main_stream(c)) != hipSuccess) {
         (void)hipGetLastError();
-        la.armed = false;
         la.queued = 0;
         return -1;  // (without `flush` nothing is lost: the ow_process calls take the ordinary path -- and report the device's state themselves)
     }
     la.queued = depth;
-    la.armed = true;
     la.count = 1;
     la.mode = 2;
     la.cur_group = cur;
@@ -951,31 +945,18 @@ int prearm_launch(ow_context *c, const ow_cascade_params *records, int count, co
 bool flush_from_queue(ow_context *c, int left, ow_status *out) {
     ow_context::Lookahead &la = c->la;
     constexpr int kRing = ow_context::Lookahead::kMaxAhead;
-    if (!la.armed || la.count != 1 || la.mode != 2 || left < 1 || left > kRing || la.queued < left) return false;
+    if (la.count != 1 || la.mode != 2 || left < 1 || left > kRing || la.queued < left) return false;
     if (lookahead_mode(c, 1) != 2 || batch_size(c, left) != left) return false;  // (timing, fault injection, no merging, pinned families: the ordinary path)
     const int g0 = la.group[la.head];
     for (int j = 0; j < left; ++j) {  // launch slot j = cascade left - 1 - j, the order ow_process would have taken them = the queue's order
         const int e = (la.head + j) % kRing, cascade = left - 1 - j;
         const ow_cascade_params &p = c->pass_parameters[cascade];
-        const float t = (float)p.time;
-        if (p.should_generate_spectrum || validate_record(p, cascade) != OW_OK || la.cascade[e][0] != cascade || std::memcmp(&t, &la.time[e][0], 4) != 0 ||
-            p.tile_length[0] != la.tile_x[e][0] || p.tile_length[1] != la.tile_y[e][0] || la.group[e] != g0 + j)  // (consecutive slots: no wrap of the ring)
-            return false;
+        if (!launchable(p) || !entry_serves(la, e, 0, cascade, p) || la.group[e] != g0 + j) return false;  // (consecutive slots: no wrap of the ring)
     }
     ow::FrameArgs args;
     std::memset(&args, 0, sizeof(args));
-    for (int j = 0; j < left; ++j) {
-        const int cascade = left - 1 - j;
-        const ow_cascade_params &p = c->pass_parameters[cascade];
-        c->maps_faulted &= ~(1u << cascade);
-        c->enqueued_since_sync |= 1u << cascade;
-        record_frame_constants(c, cascade, p);
-        args.c[j] = frame_of(p, cascade);
-    }
-    c->last_args = args;
-    c->last_count = left;
-    c->last_family = ow::kernel_family(c->n, left, c->kernel_mode);
-    for (int &sl : c->slot_of) sl = -1;
+    for (int j = 0; j < left; ++j) start_slot(c, args, j, left - 1 - j, c->pass_parameters[left - 1 - j]);
+    note_batch(c, args, left);
     ow::DeviceBuffers b = c->buf;  // the batch's intermediate starts at scratch slot g0 (a queue entry of one cascade = one slot)
     const size_t pl = (size_t)c->n * c->n;
     b.T += (size_t)g0 * pl * ow::kLayers;
@@ -983,7 +964,6 @@ bool flush_from_queue(ow_context *c, int left, ow_status *out) {
     b.rrow += (size_t)g0 * c->n * 4;
     const hipError_t e = ow::launch_pass2(c->n, left, c->kernel_mode, args, b, main_stream(c));
     if (e != hipSuccess) {
-        la.armed = false;
         la.queued = 0;
         *out = fail(OW_ERR_HIP, "flush from the look-ahead queue failed: %s", hipGetErrorString(e));
         return true;
@@ -991,7 +971,6 @@ bool flush_from_queue(ow_context *c, int left, ow_status *out) {
     la.hits += (uint64_t)left;
     la.head = (la.head + left) % kRing;
     la.queued -= left;
-    la.armed = la.queued > 0;
     la.cur_group = g0 + left - 1;
     *out = OW_OK;
     return true;
@@ -1224,22 +1203,21 @@ ow_status update_impl(ow_context *c, double delta, ow_cascade_params *params, in
     // the new records are checked BEFORE anything changes: a refused call has advanced no time, consumed no dirty flag, armed nothing
     if (ow_status st = ow::validate_records(params, count, delta); st != OW_OK) return st;
     OW_HIP(hipSetDevice(c->device));
-    // what this update arms, computed aside first (:101-106; GDScript floats are FP64): nothing of `params` or of the context changes before the
-    // leftovers' flush has been launched -- a call that fails there can simply be repeated
+    // what this update arms, computed aside first (:101-106; GDScript floats are FP64): nothing of `params` changes before the leftovers'
+    // flush has been launched
     ow_cascade_params next[OW_MAX_CASCADES], armed[OW_MAX_CASCADES];
     for (int i = 0; i < count; ++i) {
         ow_cascade_params &p = next[i];
         p = params[i];
         p.time += delta;
-        p.foam_grow_rate = delta * p.foam_amount * 7.5;
-        const double d = 10.0 - p.foam_amount;
-        p.foam_decay_rate = delta * (d > 0.5 ? d : 0.5) * 1.15;
+        set_foam_rates(p, delta);
         armed[i] = p;                     // :108 -- a copy: `params` is not touched after this call returns
         p.should_generate_spectrum = 0;   // consumed: the armed copy carries it until the cascade is processed (:72)
     }
     // ... unless the spectrum it asks for is the one that is there (spectrum_is_resident) -- asked AFTER the flush, which may itself regenerate a layer
     auto settle_armed = [&]() {
-        for (int i = 0; i < count; ++i) settle_dirty_flag(c, i, armed[i]);
+        for (int i = 0; i < count; ++i)
+            if (finite_record(armed[i])) (void)settle_spectrum(c, i, armed[i], false);  // (foam rates of a huge delta may overflow: enqueue reports them)
     };
     bool prearmed = false;
     if (c->pass_num_cascades_remaining != 0) {  // :94-98: leftovers of the previous arm, with the previous records
@@ -1247,15 +1225,17 @@ ow_status update_impl(ow_context *c, double delta, ow_cascade_params *params, in
         const int left = c->pass_num_cascades_remaining;
         for (int i = 0; i < left; ++i) idx[i] = i;
         // Whatever happens to them, the leftovers do not survive this call: were a failed flush to stay armed, every later
-        // ow_update would run into it again.  (Armed records were validated on the way in, so only a HIP failure can end up here;
-        // nothing of `params` has been touched yet, so the call can simply be repeated.)
+        // ow_update would run into it again.  (Armed records were validated on the way in, so only a HIP failure can end up here.
+        // `params` is untouched then, but repeating the call does not bring the leftovers back: their pass 2 is lost.  Where the failed
+        // launch is the pre-arm's, it has also counted its hit and the skipped spectra already, which a repeated call counts again --
+        // ADVICE.md, finding 2.)
         c->pass_num_cascades_remaining = 0;
         ow_status st = OW_OK;
         const ow_cascade_params leftover = c->pass_parameters[0];
         // ONE leftover whose pass 1 waits alone at the head of the queue, and an update whose cascades can be pre-armed: its pass 2 rides in the pre-arm launch
         // (the leftover has no spectrum to regenerate, so the resident spectra the new records are settled against are already the ones they will meet)
-        if (process_calls_follow && left == 1 && c->la.queued == 1 && !leftover.should_generate_spectrum && validate_record(leftover, 0) == OW_OK &&
-            lookahead_mode(c, 1) == 2 && batch_size(c, 1) == 1 && queue_head_serves(c, 0, leftover) && (settle_armed(), prearm_depth(c, armed, count) >= 1)) {
+        if (process_calls_follow && left == 1 && c->la.queued == 1 && launchable(leftover) && lookahead_mode(c, 1) == 2 && batch_size(c, 1) == 1 &&
+            queue_head_serves(c, 0, leftover) && (settle_armed(), prearm_depth(c, armed, count) >= 1)) {
             const int r = prearm_launch(c, armed, count, &leftover);
             if (r < 0) return fail(OW_ERR_HIP, "the launch that flushes the previous update's leftover failed");
             prearmed = r > 0;
@@ -1283,7 +1263,7 @@ ow_status ow_set_cascade_params(ow_context *c, int32_t index, const ow_cascade_p
     if (index < 0 || index >= c->pass_count) return fail(OW_ERR_INVALID, "index %d outside the %d records of the last ow_update", index, c->pass_count);
     if (ow_status st = validate_record(*p, index); st != OW_OK) return st;  // a refused record leaves the armed copy as it was
     c->pass_parameters[index] = *p;
-    settle_dirty_flag(c, index, c->pass_parameters[index]);
+    (void)settle_spectrum(c, index, c->pass_parameters[index], false);
     return OW_OK;
 }
 
@@ -1363,8 +1343,7 @@ int tick_groups_usable(const ow_context *c, const ow_cascade_params *params, int
     const bool pairs = !groups && c->pair_slots > 0 && pair_batches(c, count, sizes) > 0;
     if (!groups && !pairs) return 0;
     for (int i = 0; i < count; ++i)
-        if (params[i].should_generate_spectrum || !finite_record(params[i]) || !(params[i].tile_length[0] > 0.0f) || !(params[i].tile_length[1] > 0.0f))
-            return 0;  // (the ordinary path regenerates / reports)
+        if (!launchable(params[i])) return 0;  // (the ordinary path regenerates / reports)
     return groups ? tick_group_depth_for(c, count) : -1;
 }
 
@@ -1374,9 +1353,7 @@ void advance_tick(double delta, ow_cascade_params *params, int count, float *tim
     for (int i = 0; i < count; ++i) {
         ow_cascade_params &p = params[count - 1 - i];
         p.time += delta;
-        p.foam_grow_rate = delta * p.foam_amount * 7.5;
-        const double d = 10.0 - p.foam_amount;
-        p.foam_decay_rate = delta * (d > 0.5 ? d : 0.5) * 1.15;
+        set_foam_rates(p, delta);
         time_out[i] = (float)p.time;
     }
 }
@@ -1386,14 +1363,8 @@ ow::FrameArgs run_frame_args(const ow_cascade_params *params, int count) {
     ow::FrameArgs args;
     std::memset(&args, 0, sizeof(args));
     for (int i = 0; i < count; ++i) {
-        const ow_cascade_params &p = params[count - 1 - i];
-        ow::CascadeFrame &cf = args.c[i];
-        cf.tile_x = p.tile_length[0];
-        cf.tile_y = p.tile_length[1];
-        cf.whitecap = (float)p.whitecap;
-        cf.foam_grow_rate = (float)p.foam_grow_rate;
-        cf.foam_decay = expf(-(float)p.foam_decay_rate);
-        cf.cascade = count - 1 - i;
+        args.c[i] = frame_of(params[count - 1 - i], count - 1 - i);
+        args.c[i].time = 0.0f;  // (per tick: TickGroupArgs.time1; finish_merged_run sets the last tick's)
     }
     return args;
 }
@@ -1414,13 +1385,9 @@ void finish_merged_run(ow_context *c, ow::FrameArgs &args, const ow_cascade_para
     }
     c->pass_count = count;
     c->pass_num_cascades_remaining = 0;
-    c->maps_faulted &= ~((1u << count) - 1u);  // (as enqueue(): the run recomputed layers 0 .. count - 1)
-    c->enqueued_since_sync |= (1u << count) - 1u;
-    c->last_args = args;
-    c->last_count = last_batch;
-    c->last_family = family;
+    mark_recomputed(c, (1u << count) - 1u);  // (the run recomputed layers 0 .. count - 1)
+    note_batch(c, args, last_batch, family);
     c->last_group_depth = depth;
-    for (int &sl : c->slot_of) sl = -1;  // (no reference-layout intermediate to inspect after such a run)
 }
 
 // RUNS THAT FOLLOW RUNS (round 6).  A host that calls ow_run again and again -- bench.py's timed regions, a headless simulation in chunks -- used to
@@ -1443,8 +1410,10 @@ int run_resume_usable(ow_context *c, double delta, const ow_cascade_params *para
     ow_cascade_params tmp[OW_MAX_CASCADES];
     for (int i = 0; i < count; ++i) {
         tmp[i] = params[i];
-        if (tmp[i].should_generate_spectrum) {  // a dirty record whose spectrum is resident is as good as a clean one (spectrum_is_resident)
-            if (!spectrum_is_resident(c, i, tmp[i])) return 0;
+        if (tmp[i].should_generate_spectrum) {  // a dirty record whose spectrum is resident is as good as a clean one (run_impl consumes the flag)
+            ow::SpectrumPC pc;
+            uint32_t w[16];
+            if (!spectrum_is_resident(c, i, tmp[i], pc, w)) return 0;
             tmp[i].should_generate_spectrum = 0;
         }
     }
@@ -1457,8 +1426,7 @@ int run_resume_usable(ow_context *c, double delta, const ow_cascade_params *para
     auto time_is = [&](int slot, int adds, float expect) {
         double t = tmp[count - 1 - slot].time;
         for (int j = 0; j < adds; ++j) t += delta;  // wave_generator.gd:103: one FP64 add per update, narrowed by the pack
-        const float ft = (float)t;
-        return std::memcmp(&ft, &expect, 4) == 0;
+        return same_f32((float)t, expect);
     };
     if (ra.kind == 1) {
         if (depth != ra.D || ra.ticks < 1) return 0;
@@ -1479,14 +1447,23 @@ int run_resume_usable(ow_context *c, double delta, const ow_cascade_params *para
     return depth;
 }
 
+// the run's last launch has computed pass 1 ahead for a next run like it (c->ra: which ticks, where, at what times): and the tile lengths it took
+void arm_run_ahead(ow_context *c, const ow_cascade_params *params, int count) {
+    for (int i = 0; i < count; ++i) {  // launch slot i = cascade count - 1 - i
+        c->ra.tile_x[i] = params[count - 1 - i].tile_length[0];
+        c->ra.tile_y[i] = params[count - 1 - i].tile_length[1];
+    }
+    c->ra.armed = true;
+    ++c->la.speculated;
+}
+
 // `ticks` >= 1 consecutive ow_update_all() ticks in groups of D = group_depth:
 //   [pass 1 of group 0] [pass 2 of group 0 + pass 1 of group 1] ... [pass 2 of the last group (+ pass 1 of the next run's first group)]
 // The scratch is a ring of 2 D ticks (tick at ring position r lives in slots (r mod 2D) * count ...); a launch reads one group and writes the next,
 // each at most D ticks.  resume: group 0's pass 1 is in the ring already (c->ra: the previous run's last launch), no first launch.
 ow_status run_tick_groups(ow_context *c, double delta, ow_cascade_params *params, int count, int ticks, int D, bool resume, bool speculate) {
     ow_context::RunAhead &ra = c->ra;
-    c->la.armed = false;  // (the run uses the whole scratch its own way)
-    c->la.queued = 0;
+    c->la.queued = 0;  // (the run uses the whole scratch its own way)
     const int ring = 2 * D;
     const int pos = resume ? ra.pos : 0;
     const int g0 = resume ? std::min(ra.ticks, ticks) : std::min(D, ticks);
@@ -1541,18 +1518,11 @@ ow_status run_tick_groups(ow_context *c, double delta, ow_cascade_params *params
                 ga.tbase1[j] = slot_of(ticks + j);
                 for (int i = 0; i < count; ++i) ra.time[j][i] = ga.time1[j][i];
             }
-            for (int i = 0; i < count; ++i) {
-                ra.tile_x[i] = params[count - 1 - i].tile_length[0];
-                ra.tile_y[i] = params[count - 1 - i].tile_length[1];
-            }
             ra.kind = 1, ra.count = count, ra.D = D, ra.ticks = S, ra.pos = (pos + ticks) % ring;
             arming = true;
         }
         if (ow_status st = launch_merged(c, args, ga); st != OW_OK) return st;
-        if (arming) {
-            ra.armed = true;
-            ++c->la.speculated;
-        }
+        if (arming) arm_run_ahead(c, params, count);
         done += size;
         size = next;
     }
@@ -1585,8 +1555,7 @@ void advance_slots(double delta, ow_cascade_params *params, int count, int first
 }
 ow_status run_tick_pairs(ow_context *c, double delta, ow_cascade_params *params, int count, int ticks, bool resume, bool speculate) {
     ow_context::RunAhead &ra = c->ra;
-    c->la.armed = false;  // (the run uses the whole scratch its own way)
-    c->la.queued = 0;
+    c->la.queued = 0;  // (the run uses the whole scratch its own way)
     int sizes[OW_MAX_CASCADES], first[OW_MAX_CASCADES];
     const int B = pair_batches(c, count, sizes);
     for (int b = 0, at = 0; b < B; ++b) {
@@ -1609,13 +1578,7 @@ ow_status run_tick_pairs(ow_context *c, double delta, ow_cascade_params *params,
     ow::TickGroupArgs ga;
     std::memset(&ga, 0, sizeof(ga));
     ga.pair_compact = 1;
-    // the foam rates of this delta (wave_generator.gd:104-106): the same for every tick of the run
-    for (int i = 0; i < count; ++i) {
-        ow_cascade_params &p = params[i];
-        p.foam_grow_rate = delta * p.foam_amount * 7.5;
-        const double d = 10.0 - p.foam_amount;
-        p.foam_decay_rate = delta * (d > 0.5 ? d : 0.5) * 1.15;
-    }
+    for (int i = 0; i < count; ++i) set_foam_rates(params[i], delta);  // (the same for every tick of the run)
     ow::FrameArgs args = run_frame_args(params, count);
     const int total = (int)order.size();
     {   // pass 1 of the stream's first entry: launched alone here, or by the previous run's last launch
@@ -1647,10 +1610,6 @@ ow_status run_tick_pairs(ow_context *c, double delta, ow_cascade_params *params,
                 const ow_cascade_params &p = params[count - 1 - s];
                 ga.time1[0][s] = ra.time[0][s] = (float)(p.time + delta);
             }
-            for (int s = 0; s < count; ++s) {
-                ra.tile_x[s] = params[count - 1 - s].tile_length[0];
-                ra.tile_y[s] = params[count - 1 - s].tile_length[1];
-            }
             ga.first1 = first[b];
             ga.slots1 = sizes[b];
             ra.kind = 2, ra.count = count, ra.batch = b, ra.first = first[b], ra.size = sizes[b], ra.parity = (q0 + i + 1) & 1;
@@ -1660,10 +1619,7 @@ ow_status run_tick_pairs(ow_context *c, double delta, ow_cascade_params *params,
         ga.d2 = 1;
         ga.d1 = ga.slots1 > 0;
         if (ow_status st = launch_merged(c, args, ga); st != OW_OK) return st;
-        if (arming) {
-            ra.armed = true;
-            ++c->la.speculated;
-        }
+        if (arming) arm_run_ahead(c, params, count);
     }
     c->pair_dir = dir;
     finish_merged_run(c, args, params, count, sizes[order[total - 1]], 6, 1);
@@ -1682,14 +1638,14 @@ ow_status run_impl(ow_context *c, double delta, ow_cascade_params *params, int32
         return OW_OK;
     }
     int f = 0;
+    const bool may_merge = !c->run_as_calls && !c->no_merge && std::isfinite(delta) && count >= 1 && count <= c->cascades;
     // SINGLE-BATCH ticks of the compact family (1024^2 x 2 .. 4, 512^2 x 7 .. 8, 2048^2 x 1): the run is a tick-by-tick caller of ow_update_all whose
     // next ticks are CERTAIN -- every tick launches its pass 2 together with pass 1 of the next one (k_tick_pair_c), the last tick of the run with
     // a speculated pass 1 of the tick a NEXT run would start with (the cadence rule of ow_update_all: after a run of equal deltas, one more).
     // Back-to-back runs are then one seamless stream of full pair launches: no ordinary first tick, no half-filled launches at the two ends of
     // every run -- round 5 found the driver's 20-tick regions paying 2 us per tick for those (profiles/r05_run_overhead.txt).  Every tick is
     // checked like any ow_update_all (records, dirty spectra, leftovers: the ordinary path takes what does not qualify); results bit-identical.
-    if (frames >= 3 && !c->run_as_calls && !c->no_merge && c->timing == 0 && std::isfinite(delta) && count >= 1 && count <= c->cascades &&
-        lookahead_mode(c, count) == 1) {
+    if (frames >= 3 && may_merge && c->timing == 0 && lookahead_mode(c, count) == 1) {
         const uint64_t before = c->la.hits + c->la.speculated;
         ow_status st = OW_OK;
         for (; f < frames && st == OW_OK; ++f) {
@@ -1704,7 +1660,6 @@ ow_status run_impl(ow_context *c, double delta, ow_cascade_params *params, int32
         }
         return OW_OK;
     }
-    const bool may_merge = !c->run_as_calls && !c->no_merge && std::isfinite(delta) && count >= 1 && count <= c->cascades;
     // a run that follows a run (same delta, same cascades, nothing in between) lets its last launch work ahead for the next one
     const bool speculate = may_merge && c->ra.run_streak >= 1 && c->timing == 0 && !c->inject_fault;
     // ... and the next one starts in the middle of the stream: no ordinary first tick, no launch of pass 1 alone
@@ -1712,11 +1667,7 @@ ow_status run_impl(ow_context *c, double delta, ow_cascade_params *params, int32
         const int depth = run_resume_usable(c, delta, params, count, frames);
         if (depth != 0) {
             OW_HIP(hipSetDevice(c->device));
-            for (int i = 0; i < count; ++i)
-                if (params[i].should_generate_spectrum) {  // (resident: checked)
-                    params[i].should_generate_spectrum = 0;
-                    ++c->spectra_skipped;
-                }
+            for (int i = 0; i < count; ++i) (void)settle_spectrum(c, i, params[i], false);  // (resident: checked)
             note_cadence(c, delta);  // (what the first tick's ow_update_all would have noted)
             return depth > 0 ? run_tick_groups(c, delta, params, count, frames, depth, true, speculate) : run_tick_pairs(c, delta, params, count, frames, true, speculate);
         }
@@ -2327,7 +2278,7 @@ ow_status ow_probe_kernel_times(ow_context *c, int32_t reps, float *p1_ms, float
     if (!c) return fail(OW_ERR_INVALID, "null context");
     if (reps < 1 || c->last_count < 1) return fail(OW_ERR_STATE, "nothing has been launched yet (or reps < 1)");
     OW_HIP(hipSetDevice(c->device));
-    c->la.armed = false;  // (the probe launches write the scratch intermediate from slot 0 on)
+    c->la.queued = 0;     // (the probe launches write the scratch intermediate from slot 0 on)
     c->ra.armed = false;
     hipEvent_t e[3] = {};
     float a = 0, b = 0;
