@@ -22,6 +22,7 @@ OW_FLAG_LAZY_SCRATCH = 0x2000
 OW_FLAG_SINGLE_STREAM = 0x4000
 OW_QUERY_DISTANCE_FALLOFF = 1
 OW_BUOYANCY_WARM_START = 1
+OW_RAY_HIT, OW_RAY_FROM_BELOW, OW_RAY_TRUNCATED, OW_RAY_INVALID = 1, 2, 4, 8
 OW_OK, OW_ERR_INVALID, OW_ERR_NO_DEVICE, OW_ERR_HIP, OW_ERR_NOMEM, OW_ERR_STATE = range(6)
 
 
@@ -123,6 +124,24 @@ class ow_buoyancy_result(C.Structure):
                 ("reserved", C.c_uint32 * 2)]
 
 
+class ow_ray(C.Structure):
+    """struct ow_ray (32 bytes)"""
+    _fields_ = [("origin", C.c_float * 3), ("max_distance", C.c_float), ("direction", C.c_float * 3), ("reserved", C.c_uint32)]
+
+
+class ow_raycast_options(C.Structure):
+    """struct ow_raycast_options (64 bytes); zeros = the defaults (the query's, water level 0, 0.25 m spacing, 1e-3 m, 4096 samples)"""
+    _fields_ = [("query", ow_query_options), ("water_level", C.c_float), ("sample_spacing", C.c_float), ("tolerance", C.c_float),
+                ("max_samples", C.c_int32), ("reserved", C.c_uint32 * 4)]
+
+
+class ow_raycast_hit(C.Structure):
+    """struct ow_raycast_hit (192 bytes): where a ray meets the water, the slab it searched, and the query record at the hit"""
+    _fields_ = [("t", C.c_float), ("position", C.c_float * 3), ("residual", C.c_float), ("status", C.c_int32), ("samples", C.c_int32),
+                ("rounds", C.c_int32), ("slab_half_height", C.c_float), ("t_enter", C.c_float), ("t_exit", C.c_float),
+                ("reserved", C.c_uint32 * 5), ("query", ow_surface_query)]
+
+
 # every symbol include/ocean_waves.h declares: (restype, argtypes)
 _P = C.POINTER
 SIGNATURES = {
@@ -157,6 +176,8 @@ SIGNATURES = {
                               C.c_void_p, C.c_void_p]),
     "ow_buoyancy_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, _P(ow_buoyancy_options),
                                     C.c_void_p, C.c_void_p]),
+    "ow_raycast_surface": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, _P(ow_raycast_options), C.c_void_p]),
+    "ow_raycast_surface_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, _P(ow_raycast_options), C.c_void_p]),
     "ow_get_maps_f32": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
     "ow_get_spectrum": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "ow_get_intermediate": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
@@ -187,6 +208,7 @@ SIGNATURES = {
     "ow_group_query_surface": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, _P(ow_query_options), C.c_void_p]),
     "ow_group_buoyancy": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, _P(ow_buoyancy_options),
                                     C.c_void_p, C.c_void_p]),
+    "ow_group_raycast_surface": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, _P(ow_raycast_options), C.c_void_p]),
     "ow_export_maps": (C.c_int, [C.c_void_p, _P(C.c_int32), _P(C.c_int32), _P(C.c_size_t)]),
     "ow_import_buffer": (C.c_int, [C.c_int32, C.c_int32, C.c_size_t, C.c_size_t, _P(C.c_void_p), _P(C.c_void_p)]),
     "ow_release_buffer": (None, [C.c_void_p]),

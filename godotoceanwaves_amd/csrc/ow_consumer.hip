@@ -12,6 +12,8 @@
 // lives in ow_surface.h, which tests/query/ also compiles as plain C++: k_query_surface is held to that build bit for bit.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+
 #include "ow_kernels.h"
 
 namespace ow {
@@ -77,6 +79,57 @@ __global__ void __launch_bounds__(256) k_buoyancy_bodies(const BuoyancyBody *bod
     if (lane == 0) results[bi] = body_result(a, b);
 }
 
+// Step 1 of a ray cast (ow_raycast.h): the largest FP16 magnitude of D_y per cascade, as bits, into bound[c], which the caller clears in
+// stream order before the launch.  blockIdx.y is the cascade; a grid-stride loop reads two texels (16 B) per lane and step, the wave's
+// max goes out in one atomicMax.  A max of integers: the same bits in any order.
+__global__ void __launch_bounds__(256) k_height_bound(const u16x4 *disp, int n, uint32_t *bound) {
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    const int c = blockIdx.y;
+    const size_t pairs = (size_t)n * n / 2;
+    const u32x4 *layer = (const u32x4 *)(disp + (size_t)c * n * n);
+    uint32_t m = 0;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < pairs; i += (size_t)gridDim.x * blockDim.x) {
+        const u32x4 v = layer[i];  // (x, y) (z, w) of texel 2i, then of texel 2i + 1: D_y is the high half of words 0 and 2
+        const uint32_t a = (v.x >> 16) & 0x7fffu, b = (v.z >> 16) & 0x7fffu;
+        m = max(m, max(a, b));
+    }
+    for (int s = 32; s >= 1; s >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, s, 64));
+    if ((threadIdx.x & 63) == 0) atomicMax(bound + c, m);
+}
+
+// the 64 lanes of one wave as ow_raycast.h's raycast_ray sees them: lane j evaluates its own sample; ballots and shuffles make the
+// outcome of a round wave-uniform
+struct DeviceWave {
+    int lane;
+    float my_t = 0.0f, my_g = 0.0f;
+    template <class Pred, class Fn>
+    __device__ void round(const Pred &pred, const Fn &fn, uint64_t &took, uint64_t &above) {
+        const bool p = pred(lane);
+        RaySample s{0.0f, 0.0f, 0.0f};
+        if (p) s = fn(lane);
+        my_t = s.t;
+        my_g = s.g;
+        took = __ballot(p);
+        above = __ballot(p && s.g > 0.0f);
+    }
+    __device__ float t(int j) const { return __shfl(my_t, j, 64); }
+    __device__ float g(int j) const { return __shfl(my_g, j, 64); }
+};
+
+// One 64-lane wave per ray, one ray per block of 64, no LDS.  Lane j takes sample 64 r + j of round r, each with its own cold solve:
+// a ray costs about one dependent-load chain per round (one march round for a steep ray, up to four refine rounds and the record)
+// instead of one per sample.  64-thread blocks spread a few rays over as many CUs (a 256-thread block would put four rays on one CU and
+// leave the rest of the chip idle); tens of thousands of rays still fill every SIMD.  Lane 0 writes the record.
+__global__ void __launch_bounds__(64) k_raycast_surface(const u16x4 *disp, const u16x4 *norm, int n, int cascades, const Ray *rays,
+                                                        const uint32_t *bound, SurfaceScales scales, RaycastParams rp, RaycastHit *out) {
+    const int i = blockIdx.x;
+    DeviceWave wave;
+    wave.lane = (int)threadIdx.x;
+    const float hw = slab_half_height(bound, cascades, scales);
+    const RaycastHit h = raycast_ray(wave, disp, norm, n, cascades, scales, rp, rays[i], hw);
+    if (wave.lane == 0) out[i] = h;
+}
+
 }  // namespace
 
 hipError_t launch_sample_surface(int n, int cascades, const DeviceBuffers &buf, const float *xz_dev, int count,
@@ -112,6 +165,18 @@ hipError_t launch_buoyancy(int n, int cascades, const DeviceBuffers &buf, const 
         return hipGetLastError();
     }
     return hipSuccess;
+}
+
+hipError_t launch_raycast(int n, int cascades, const DeviceBuffers &buf, const Ray *rays_dev, int count, const SurfaceScales &scales,
+                          const RaycastParams &rp, uint32_t *bound_dev, RaycastHit *out_dev, hipStream_t s) {
+    if (count <= 0) return hipSuccess;
+    if (hipError_t e = hipMemsetAsync(bound_dev, 0, (size_t)cascades * sizeof(uint32_t), s); e != hipSuccess) return e;
+    const int threads = 256;
+    const int pairs = n * n / 2, blocks = std::min((pairs + threads - 1) / threads, 256);
+    hipLaunchKernelGGL(k_height_bound, dim3(blocks, cascades), dim3(threads), 0, s, buf.disp, n, bound_dev);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_raycast_surface, dim3(count), dim3(64), 0, s, buf.disp, buf.norm, n, cascades, rays_dev, bound_dev, scales, rp, out_dev);
+    return hipGetLastError();
 }
 
 }  // namespace ow

@@ -115,6 +115,10 @@ struct ow_group {
     int query_capacity = 0;
     void *buoy_scratch = nullptr;  // ow_group_buoyancy (grow-only, root device)
     size_t buoy_bytes = 0;
+    ow::Ray *ray_in = nullptr;  // ow_group_raycast_surface (grow-only, root device)
+    ow::RaycastHit *ray_out = nullptr;
+    int ray_capacity = 0;
+    uint32_t *ray_bound = nullptr;
 };
 
 namespace {
@@ -382,6 +386,9 @@ void ow_group_destroy(ow_group *g) {
     (void)hipFree(g->query_xz);
     (void)hipFree(g->query_out);
     (void)hipFree(g->buoy_scratch);
+    (void)hipFree(g->ray_in);
+    (void)hipFree(g->ray_out);
+    (void)hipFree(g->ray_bound);
     delete g;
     if (caller_dev >= 0) (void)hipSetDevice(caller_dev);
 }
@@ -586,6 +593,43 @@ ow_status ow_group_buoyancy(ow_group *g, const ow_buoyancy_body *bodies, int32_t
                                                      num_points, sc, qp, bp, results, points_inout);
             st != OW_OK)
             return st;
+        OW_HIP(hipStreamSynchronize(g->root_stream));
+        return OW_OK;
+    };
+    const ow_status st = run();
+    if (caller_dev >= 0) (void)hipSetDevice(caller_dev);
+    return st;
+}
+
+ow_status ow_group_raycast_surface(ow_group *g, const ow_ray *rays, int32_t count, const float *map_scales, int32_t num_cascades,
+                                   const ow_raycast_options *opts, ow_raycast_hit *out) {
+    static_assert(sizeof(ow_raycast_hit) == sizeof(ow::RaycastHit) && sizeof(ow_ray) == sizeof(ow::Ray), "record layout");
+    if (!g) return fail(OW_ERR_INVALID, "null group");
+    if (count < 0) return fail(OW_ERR_INVALID, "count must be >= 0");
+    if (num_cascades < 1 || num_cascades > std::min(g->total, OW_MAX_CASCADES))
+        return fail(OW_ERR_INVALID, "num_cascades %d outside [1,%d]", num_cascades, std::min(g->total, OW_MAX_CASCADES));
+    ow::RaycastParams rp;
+    if (ow_status st = ow::resolve_raycast_options(opts, &rp); st != OW_OK) return st;
+    if (!g->gathered) return fail(OW_ERR_STATE, "the gathered arrays are empty: ow_group_gather_begin / ow_group_gather_wait first");
+    if (gather_in_flight(g)) return fail(OW_ERR_STATE, "a gather is in flight (the arrays are being written): ow_group_gather_wait first");
+    if (ow_status st = refuse_faulted_layers(g, 0, num_cascades); st != OW_OK) return st;
+    if (count == 0) return OW_OK;
+    if (!rays || !map_scales || !out) return fail(OW_ERR_INVALID, "null argument");
+    int caller_dev = -1;
+    (void)hipGetDevice(&caller_dev);
+    auto run = [&]() -> ow_status {
+        OW_HIP(hipSetDevice(g->root_device));
+        if (ow_status st = ow::raycast_scratch(count, &g->ray_in, &g->ray_out, &g->ray_capacity, &g->ray_bound); st != OW_OK) return st;
+        ow::SurfaceScales sc;
+        std::memset(&sc, 0, sizeof(sc));
+        std::memcpy(sc.s, map_scales, (size_t)num_cascades * 4 * sizeof(float));
+        ow::DeviceBuffers buf;
+        std::memset(&buf, 0, sizeof(buf));
+        buf.disp = (ow::u16x4 *)g->gdisp;  // the ray-cast kernels read the two array textures only
+        buf.norm = (ow::u16x4 *)g->gnorm;
+        OW_HIP(hipMemcpyAsync(g->ray_in, rays, (size_t)count * sizeof(ow::Ray), hipMemcpyHostToDevice, g->root_stream));
+        OW_HIP(ow::launch_raycast(g->n, num_cascades, buf, g->ray_in, count, sc, rp, g->ray_bound, g->ray_out, g->root_stream));
+        OW_HIP(hipMemcpyAsync(out, g->ray_out, (size_t)count * sizeof(ow::RaycastHit), hipMemcpyDeviceToHost, g->root_stream));
         OW_HIP(hipStreamSynchronize(g->root_stream));
         return OW_OK;
     };

@@ -23,6 +23,13 @@ ow_status resolve_query_options(const ow_query_options *opts, QueryParams *qp);
 // ow_buoyancy_options (NULL = defaults) -> the solver's settings and the model's constants (ow_runtime.hip)
 struct BuoyancyParams;
 ow_status resolve_buoyancy_options(const ow_buoyancy_options *opts, QueryParams *qp, BuoyancyParams *bp);
+// ow_raycast_options (NULL = defaults) -> the ray cast's settings, OW_ERR_INVALID for a value out of range (ow_runtime.hip)
+struct RaycastParams;
+ow_status resolve_raycast_options(const ow_raycast_options *opts, RaycastParams *rp);
+// the grow-only ray-cast scratch on the current device: `count` rays in, `count` records out, and the bound words (allocated once)
+struct Ray;
+struct RaycastHit;
+ow_status raycast_scratch(int count, Ray **in, RaycastHit **out, int *capacity, uint32_t **bound);
 // the host-side checks of ow_buoyancy / ow_group_buoyancy on host arrays: ranges, body indices, volumes, half heights (ow_runtime.hip)
 ow_status check_buoyancy_arrays(const ow_buoyancy_body *bodies, int num_bodies, const ow_hull_point *hull, int num_points);
 // The synchronous buoyancy's device half on `s` (ow_runtime.hip): grow-only scratch (*scratch, *scratch_bytes; on the current device), the

@@ -4,6 +4,7 @@
 
 #include "ow_device.h"
 #include "ow_buoyancy.h"
+#include "ow_raycast.h"
 #include "ow_surface.h"
 
 namespace ow {
@@ -42,6 +43,10 @@ hipError_t launch_query_surface(int n, int cascades, const DeviceBuffers &buf, c
 hipError_t launch_buoyancy(int n, int cascades, const DeviceBuffers &buf, const BuoyancyBody *bodies_dev, int num_bodies, const HullPoint *hull_dev,
                            int num_points, const SurfaceScales &scales, const QueryParams &qp, const BuoyancyParams &bp, BuoyancyPoint *pts_dev,
                            BuoyancyResult *results_dev, hipStream_t s);
+// ray casts (ow_consumer.hip; the rounds, records and the slab in ow_raycast.h): bound_dev (cascades words) is cleared, k_height_bound
+// fills it, then k_raycast_surface casts `count` rays, all on `s`
+hipError_t launch_raycast(int n, int cascades, const DeviceBuffers &buf, const Ray *rays_dev, int count, const SurfaceScales &scales,
+                          const RaycastParams &rp, uint32_t *bound_dev, RaycastHit *out_dev, hipStream_t s);
 
 bool supported_map_size(int n);
 int kernel_family(int n, int slots, int mode);  // 1 standard, 2 layer-parallel, 3 compact: what launch_pass1/2 will use

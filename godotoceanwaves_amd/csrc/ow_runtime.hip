@@ -164,6 +164,11 @@ struct ow_context {
     // ow_buoyancy scratch (grow-only): bodies, hull points, per-point records, results
     void *buoy_scratch = nullptr;
     size_t buoy_bytes = 0;
+    // ow_raycast_surface scratch (grow-only): ray_capacity rays in and records out, and the per-cascade bound words of the slab
+    ow::Ray *ray_in = nullptr;
+    ow::RaycastHit *ray_out = nullptr;
+    int ray_capacity = 0;
+    uint32_t *ray_bound = nullptr;
 };
 
 // The stream everything but a first-chain launch is enqueued on or synchronised through: joins the second chain first (a no-op when none is in flight).
@@ -1166,6 +1171,9 @@ void ow_destroy(ow_context *c) {
     (void)hipFree(c->query_xz);
     (void)hipFree(c->query_out);
     (void)hipFree(c->buoy_scratch);
+    (void)hipFree(c->ray_in);
+    (void)hipFree(c->ray_out);
+    (void)hipFree(c->ray_bound);
     for (auto &e : c->ev)
         if (e) (void)hipEventDestroy(e);
     if (c->side_fork_ev) (void)hipEventDestroy(c->side_fork_ev);
@@ -2179,6 +2187,88 @@ ow_status ow_buoyancy_async(ow_context *c, const ow_buoyancy_body *bodies_dev, i
     // main_stream(): behind the second chain's join as well as everything on the context's (or the caller's) stream
     OW_HIP(ow::launch_buoyancy(c->n, num_cascades, c->buf, (const ow::BuoyancyBody *)bodies_dev, num_bodies, (const ow::HullPoint *)hull_dev, num_points,
                                sc, qp, bp, (ow::BuoyancyPoint *)points_dev, (ow::BuoyancyResult *)results_dev, main_stream(c)));
+    return OW_OK;
+}
+
+}  // extern "C"
+
+namespace ow {
+ow_status resolve_raycast_options(const ow_raycast_options *o, RaycastParams *rp) {
+    if (ow_status st = resolve_query_options(o ? &o->query : nullptr, &rp->qp); st != OW_OK) return st;
+    rp->water_level = 0.0f;
+    rp->spacing = kRayDefaultSpacing;
+    rp->tolerance = kRayDefaultTolerance;
+    rp->max_samples = kRayDefaultMaxSamples;
+    if (!o) return OW_OK;
+    if (!std::isfinite(o->water_level) || !std::isfinite(o->sample_spacing) || !std::isfinite(o->tolerance))
+        return fail(OW_ERR_INVALID, "water_level, sample_spacing and tolerance must be finite");
+    if (o->max_samples < 0 || o->max_samples > kRayMaxSamples)
+        return fail(OW_ERR_INVALID, "max_samples %d outside [0,%d]", o->max_samples, kRayMaxSamples);
+    for (uint32_t r : o->reserved)
+        if (r != 0u) return fail(OW_ERR_INVALID, "ow_raycast_options.reserved must be 0");
+    rp->water_level = o->water_level;
+    if (o->sample_spacing > 0.0f) rp->spacing = o->sample_spacing;
+    if (o->tolerance > 0.0f) rp->tolerance = o->tolerance;
+    if (o->max_samples > 0) rp->max_samples = o->max_samples;
+    return OW_OK;
+}
+
+ow_status raycast_scratch(int count, Ray **in, RaycastHit **out, int *capacity, uint32_t **bound) {
+    if (!*bound && hipMalloc((void **)bound, OW_MAX_CASCADES * sizeof(uint32_t)) != hipSuccess) {
+        *bound = nullptr;
+        return fail(OW_ERR_NOMEM, "hipMalloc failed for the ray-cast bound words");
+    }
+    if (count <= *capacity) return OW_OK;
+    (void)hipFree(*in);
+    (void)hipFree(*out);
+    *in = nullptr;
+    *out = nullptr;
+    *capacity = 0;
+    const int cap = std::max(count, 1024);
+    if (hipMalloc((void **)in, (size_t)cap * sizeof(Ray)) != hipSuccess || hipMalloc((void **)out, (size_t)cap * sizeof(RaycastHit)) != hipSuccess)
+        return fail(OW_ERR_NOMEM, "hipMalloc failed for %d rays", cap);
+    *capacity = cap;
+    return OW_OK;
+}
+}  // namespace ow
+
+extern "C" {
+
+ow_status ow_raycast_surface(ow_context *c, const ow_ray *rays, int32_t count, const float *map_scales, int32_t num_cascades,
+                             const ow_raycast_options *opts, ow_raycast_hit *out) {
+    static_assert(sizeof(ow_ray) == sizeof(ow::Ray) && sizeof(ow_raycast_hit) == sizeof(ow::RaycastHit) &&
+                      offsetof(ow_raycast_hit, query) == offsetof(ow::RaycastHit, query) &&
+                      offsetof(ow_raycast_hit, slab_half_height) == offsetof(ow::RaycastHit, slab_half_height) &&
+                      offsetof(ow_ray, direction) == offsetof(ow::Ray, direction),
+                  "record layout");
+    if (ow_status st = check_point_query(c, count, num_cascades); st != OW_OK) return st;
+    ow::RaycastParams rp;
+    if (ow_status st = ow::resolve_raycast_options(opts, &rp); st != OW_OK) return st;
+    if (count == 0) return OW_OK;
+    if (!rays || !map_scales || !out) return fail(OW_ERR_INVALID, "null argument");
+    OW_HIP(hipSetDevice(c->device));
+    if (ow_status st = ow::raycast_scratch(count, &c->ray_in, &c->ray_out, &c->ray_capacity, &c->ray_bound); st != OW_OK) return st;
+    const ow::SurfaceScales sc = surface_scales(map_scales, num_cascades);
+    OW_HIP(hipMemcpyAsync(c->ray_in, rays, (size_t)count * sizeof(ow::Ray), hipMemcpyHostToDevice, main_stream(c)));
+    OW_HIP(ow::launch_raycast(c->n, num_cascades, c->buf, c->ray_in, count, sc, rp, c->ray_bound, c->ray_out, main_stream(c)));
+    OW_HIP(hipMemcpyAsync(out, c->ray_out, (size_t)count * sizeof(ow::RaycastHit), hipMemcpyDeviceToHost, main_stream(c)));
+    return sync_stream(c, (1u << num_cascades) - 1u);
+}
+
+ow_status ow_raycast_surface_async(ow_context *c, const ow_ray *rays_dev, int32_t count, const float *map_scales, int32_t num_cascades,
+                                   const ow_raycast_options *opts, ow_raycast_hit *out_dev) {
+    if (ow_status st = check_point_query(c, count, num_cascades); st != OW_OK) return st;
+    ow::RaycastParams rp;
+    if (ow_status st = ow::resolve_raycast_options(opts, &rp); st != OW_OK) return st;
+    if (count == 0) return OW_OK;
+    if (!rays_dev || !map_scales || !out_dev) return fail(OW_ERR_INVALID, "null argument");
+    if (ow_status st = refuse_faulted(c, (1u << num_cascades) - 1u); st != OW_OK) return st;
+    OW_HIP(hipSetDevice(c->device));
+    if (ow_status st = ow::raycast_scratch(0, &c->ray_in, &c->ray_out, &c->ray_capacity, &c->ray_bound); st != OW_OK) return st;
+    const ow::SurfaceScales sc = surface_scales(map_scales, num_cascades);
+    // main_stream(): behind the second chain's join as well as everything on the context's (or the caller's) stream
+    OW_HIP(ow::launch_raycast(c->n, num_cascades, c->buf, (const ow::Ray *)rays_dev, count, sc, rp, c->ray_bound, (ow::RaycastHit *)out_dev,
+                              main_stream(c)));
     return OW_OK;
 }
 

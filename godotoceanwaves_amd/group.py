@@ -166,6 +166,16 @@ class WaveGeneratorGroup:
                                                points.ctypes.data if points is not None else None))
         return out
 
+    def raycast_surface(self, rays, map_scales, options=None):
+        """WaveGenerator.raycast_surface over the gathered arrays on the root device"""
+        r = np.ascontiguousarray(rays, WaveGenerator.RAY)
+        sc = np.ascontiguousarray(map_scales, np.float32).reshape(-1, 4)
+        out = np.zeros(len(r), WaveGenerator.RAYCAST_HIT)
+        o = WaveGenerator.raycast_options(options)
+        _lib.check(self._lib.ow_group_raycast_surface(self.group, r.ctypes.data, len(r), sc.ctypes.data, len(sc),
+                                                      C.byref(o) if o is not None else None, out.ctypes.data))
+        return out
+
     def free(self):
         if self.group:
             self._lib.ow_group_destroy(self.group)

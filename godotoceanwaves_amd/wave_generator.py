@@ -398,6 +398,70 @@ class WaveGenerator:
         _lib.check(self._lib.ow_buoyancy_async(self.context, addr(bodies_device), nb, addr(hull_device), npts, sc.ctypes.data, len(sc),
                                                C.byref(o) if o is not None else None, addr(results_device), addr(points_device)))
 
+    # ---- ray casts against the rendered water, on the device (include/ocean_waves.h ow_raycast_surface) ----
+    RAY = np.dtype([("origin", np.float32, 3), ("max_distance", np.float32), ("direction", np.float32, 3), ("reserved", np.uint32)])
+    RAYCAST_OPTIONS = np.dtype([("query", BUOYANCY_OPTIONS.fields["query"][0]), ("water_level", np.float32), ("sample_spacing", np.float32),
+                                ("tolerance", np.float32), ("max_samples", np.int32), ("reserved", np.uint32, 4)])
+    RAYCAST_HIT = np.dtype([("t", np.float32), ("position", np.float32, 3), ("residual", np.float32), ("status", np.int32),
+                            ("samples", np.int32), ("rounds", np.int32), ("slab_half_height", np.float32), ("t_enter", np.float32),
+                            ("t_exit", np.float32), ("reserved", np.uint32, 5), ("query", SURFACE_QUERY)])
+
+    @classmethod
+    def rays(cls, origins, directions, max_distance):
+        """RAY records from origins [R][3], directions [R][3] (any non-zero length) and max_distance (a scalar or [R]).  Godot's
+        intersect_ray(from, to): origin = from, direction = to - from, max_distance = |to - from|."""
+        o = np.asarray(origins, np.float32).reshape(-1, 3)
+        out = np.zeros(len(o), cls.RAY)
+        out["origin"] = o
+        out["direction"] = np.asarray(directions, np.float32).reshape(-1, 3)
+        out["max_distance"] = max_distance
+        return out
+
+    @classmethod
+    def raycast_options(cls, options=None):
+        """None, an _lib.ow_raycast_options, or a dict of water_level / sample_spacing / tolerance / max_samples and the query_options
+        keys (query_tolerance for the query's own tolerance) -> ow_raycast_options, or None for the defaults"""
+        if options is None or isinstance(options, _lib.ow_raycast_options):
+            return options
+        own = {"water_level", "sample_spacing", "tolerance", "max_samples", "query_tolerance"}
+        q = {k: v for k, v in options.items() if k not in own}
+        if "query_tolerance" in options:
+            q["tolerance"] = options["query_tolerance"]
+        qo = cls.query_options(q) if q else None
+        o = _lib.ow_raycast_options(water_level=float(options.get("water_level", 0.0)), sample_spacing=float(options.get("sample_spacing", 0.0)),
+                                    tolerance=float(options.get("tolerance", 0.0)), max_samples=int(options.get("max_samples", 0)))
+        if qo is not None:
+            o.query = qo
+        return o
+
+    def raycast_surface(self, rays, map_scales, options=None):
+        """Where each RAY record first meets the rendered water: t, the position, the status bits (_lib.OW_RAY_*), the slab searched
+        and the SURFACE_QUERY record at the hit.  Returns a structured array (RAYCAST_HIT)."""
+        r = np.ascontiguousarray(rays, self.RAY)
+        sc = np.ascontiguousarray(map_scales, np.float32).reshape(-1, 4)
+        out = np.zeros(len(r), self.RAYCAST_HIT)
+        o = self.raycast_options(options)
+        _lib.check(self._lib.ow_raycast_surface(self.context, r.ctypes.data, len(r), sc.ctypes.data, len(sc),
+                                                C.byref(o) if o is not None else None, out.ctypes.data))
+        return out
+
+    def raycast_surface_async(self, rays_device, map_scales, out_device, options=None, count=None):
+        """The ray casts over DEVICE buffers, enqueued in the generator's stream order without synchronising: rays_device holds count
+        32-byte RAY records, out_device room for count 192-byte records.  Each is anything with a data_ptr() (a torch tensor) or an
+        integer address; count defaults to the byte size of rays_device over 32."""
+        def addr(b):
+            return int(b.data_ptr()) if hasattr(b, "data_ptr") else int(b)
+        if count is None:
+            if not hasattr(rays_device, "numel"):
+                raise ValueError("count is needed for a raw device address")
+            count = int(rays_device.numel() * rays_device.element_size()) // self.RAY.itemsize
+        if hasattr(out_device, "numel") and hasattr(out_device, "element_size") and out_device.numel() * out_device.element_size() < count * self.RAYCAST_HIT.itemsize:
+            raise ValueError(f"out_device holds fewer than {count} records of {self.RAYCAST_HIT.itemsize} bytes")
+        sc = np.ascontiguousarray(map_scales, np.float32).reshape(-1, 4)
+        o = self.raycast_options(options)
+        _lib.check(self._lib.ow_raycast_surface_async(self.context, addr(rays_device), int(count), sc.ctypes.data, len(sc),
+                                                      C.byref(o) if o is not None else None, addr(out_device)))
+
     def get_push_constants(self, cascade):
         """(spectrum[16], modulate[8], unpack[4]) uint32 words: the reference's push-constant blocks of this cascade's most recent launch"""
         pc = _lib.ow_push_constants()
