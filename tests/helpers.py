@@ -4,6 +4,8 @@ import hashlib
 import json
 import math
 import os
+import subprocess
+import sys
 
 import numpy as np
 
@@ -89,3 +91,175 @@ def spectrum_pc(preset):
     return O.make_pc(preset["spectrum_seed"], preset["tile_length"], np.float32(O.jonswap_alpha(U, F)),
                      np.float32(O.jonswap_peak(U, F)), U, np.float32(math.radians(preset["wind_direction"])), DEPTH,
                      preset["swell"], preset["detail"], preset["spread"])
+
+
+def record_pc(rec, depth=DEPTH):
+    """The spectrum push constants of one parameter record, packed as the runtime packs them (ow_runtime.hip pack_spectrum, after
+    wave_generator.gd:69-71): wind speed and fetch clamped to 1e-4 (the exported setters), alpha and the peak frequency from the FP64 values,
+    deg_to_rad in FP64, every scalar narrowed to FP32 only at the pack."""
+    U, F = max(rec["wind_speed"], 1e-4), max(rec["fetch_length"], 1e-4) * 1e3
+    return O.make_pc(rec["spectrum_seed"], rec["tile_length"], O.jonswap_alpha(U, F), O.jonswap_peak(U, F), U,
+                     rec["wind_direction"] * (math.pi / 180.0), depth, rec["swell"], rec["detail"], rec["spread"])
+
+
+def pc_words(pc):
+    """the first twelve words of the spectrum push-constant block (ow_get_push_constants), as uint32"""
+    f = [pc.tile_length[0], pc.tile_length[1], pc.alpha, pc.peak_frequency, pc.wind_speed, pc.angle, pc.depth, pc.swell, pc.detail, pc.spread]
+    return np.concatenate([np.array([pc.seed[0], pc.seed[1]], np.int64).astype(np.uint32), np.array(f, np.float32).view(np.uint32)])
+
+
+def twin_params(pc):
+    """the same push constants as the FP64 truth twin's parameters (tests/np_twin.py): the FP32 values, widened"""
+    return dict(seed=(pc.seed[0], pc.seed[1]), tile_length=(pc.tile_length[0], pc.tile_length[1]), alpha=pc.alpha,
+                peak_frequency=pc.peak_frequency, wind_speed=pc.wind_speed, angle=pc.angle, depth=pc.depth, swell=pc.swell,
+                detail=pc.detail, spread=pc.spread)
+
+
+def spectrum_records(fuzzed=14, seed=20261016):
+    """(name, record) of the spectrum texel tests (tests/test_spectrum_texels.py, scripts/spectrum_margins.py): the eight presets, the ten
+    range-edge presets (tests/edge_presets.py) and `fuzzed` records drawn by scripts/fuzz_parity.draw_case (FP64 scalars, random seeds,
+    non-square tiles in about 40 % of them) -- 32 in all, four contexts of eight cascades."""
+    from edge_presets import edge_presets
+    scripts = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "scripts")
+    if scripts not in sys.path:
+        sys.path.insert(0, scripts)
+    import fuzz_parity
+    out = [(f"preset{i}", cascade_preset(i)) for i in range(8)] + sorted(edge_presets().items())
+    rng = np.random.default_rng(seed)
+    recs = []
+    while len(recs) < fuzzed:
+        recs += fuzz_parity.draw_case(rng)["records"]
+    return out + [(f"fuzz{i}", r) for i, r in enumerate(recs[:fuzzed])]
+
+
+def spectrum_references(n, pcs, workers=4):
+    """per push-constant block: (the oracle's texels [n][n][4] FP32, the FP64 twin's h0 [n][n] complex128, the oracle's omega [n][n] FP32,
+    np_twin.direction_ulp_sensitivity [n][n]),
+    computed in parallel (the oracle's ctypes calls and NumPy's array operations release the interpreter lock)"""
+    import np_twin
+    from concurrent.futures import ThreadPoolExecutor
+
+    def one(pc):
+        tp = twin_params(pc)
+        return (O.spectrum_compute(n, pc), np_twin.amplitude(n, tp), O.omega(n, (pc.tile_length[0], pc.tile_length[1]), pc.depth),
+                np_twin.direction_ulp_sensitivity(n, tp))
+    with ThreadPoolExecutor(max_workers=workers) as ex:
+        return list(ex.map(one, pcs))
+
+
+def device_spectra(n, recs):
+    """one context of len(recs) cascades, one update_all: per slot (h0 texels [n][n][4] through ow_get_spectrum, omega [n][n], the spectrum
+    push-constant words of the launch)"""
+    from godotoceanwaves_amd import WaveCascadeParameters, WaveGenerator
+    gen = WaveGenerator()
+    gen.map_size = n
+    gen.init_gpu(max(2, len(recs)))
+    try:
+        gen.update_all(UPDATE_DELTA, [WaveCascadeParameters(**r) for r in recs])
+        gen.sync()
+        return [gen.get_spectrum(i) + (gen.get_push_constants(i)[0],) for i in range(len(recs))]
+    finally:
+        gen.free()
+
+
+# ---- per-texel metric (the spectrum spans tens of orders of magnitude: a max-norm is set by the few texels at the peak) ----
+# The spectrum's bounds (tests/test_spectrum_texels.py, tests/test_emul.py, scripts/spectrum_margins.py).  Each is about four times the worst
+# value measured on the MI355X over every size and record of spectrum_records (profiles/spectrum_margins.txt); the measured value is noted.
+SPEC_PHI = 1e-7             # the floor, relative to the plane's maximum (tests/test_spectrum_texels.py says why)
+SPEC_ABS_FLOOR = float(np.sqrt(np.finfo(np.float32).tiny))   # 1.1e-19: the amplitude is the square root of an FP32 energy, subnormal below this
+SPEC_RHO_ORACLE = 3e-6      # k_spectrum vs the oracle, per texel (measured 6.7e-7)
+SPEC_KAPPA = 2.0            # k_spectrum vs the FP64 twin: this many times the literal form's own error ...
+SPEC_RHO_TWIN = 1.5e-6      # ... plus this much of |twin| (measured 3.9e-7)
+SPEC_RHO_LITERAL = 5e-6     # the oracle vs the FP64 twin (measured 1.2e-6)
+SPEC_ARG_ULPS = 4.0         # ulps of theta - angle allowed on top, times np_twin.direction_ulp_sensitivity (the wind's null direction; measured 0.98)
+def texel_margins(a, r, rho, phi, extra=0.0, per_ulp=None, ulps=0.0, abs_floor=0.0):
+    """a, r: planes with the channel on the last axis (complex channels compare as complex numbers).  Per texel and channel
+        ratio = |a - r| / (extra + (rho + ulps per_ulp) |r| + phi max|r|)      (max over the channel's plane)
+    over the texels with |r| >= phi max|r| (and >= abs_floor) -- the ones below the floor may differ freely (they must be finite: checked by
+    the caller).
+    extra: an absolute allowance per texel (or 0); per_ulp: a relative allowance per texel and ulp of something the formulas cannot
+    evaluate more closely in FP32 (np_twin.direction_ulp_sensitivity), of which `ulps` are allowed.
+    Returns dict(worst: max ratio, at: its index, floor_share: share of all texel-channels that need the floor term,
+    over_share: share of all texel-channels with a ratio above 1, rho_needed: the smallest rho with every ratio <= 1 at this phi,
+    ulps_needed: the smallest `ulps` with every ratio <= 1 at this rho and phi)."""
+    a = np.asarray(a)
+    r = np.asarray(r)
+    kind = np.complex128 if (np.iscomplexobj(a) or np.iscomplexobj(r)) else np.float64
+    err = np.abs(a.astype(kind) - r.astype(kind))
+    mag = np.abs(r.astype(kind))
+    floor = np.maximum(phi * mag.reshape(-1, mag.shape[-1]).max(axis=0), abs_floor)
+    live = (mag >= floor) & (mag > 0)
+    cond = 0.0 if per_ulp is None else per_ulp * mag
+    rel = extra + (rho * mag + ulps * cond)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ratio = np.where(live, err / (rel + floor), 0.0)
+        need = np.where(live, (err - extra - ulps * cond - floor) / mag, 0.0)
+        need_ulps = np.where(live & (cond > 0), (err - extra - rho * mag - floor) / cond, 0.0) if per_ulp is not None else np.zeros(1)
+    i = int(np.argmax(ratio))
+    return dict(worst=float(ratio.flat[i]), at=np.unravel_index(i, ratio.shape), floor_share=float((live & (err > rel)).sum() / err.size),
+                over_share=float((ratio > 1.0).sum() / err.size), rho_needed=max(0.0, float(need.max())),
+                ulps_needed=max(0.0, float(need_ulps.max())))
+
+
+def spectrum_margins(a, r, rho, sens, extra=0.0):
+    """texel_margins with the spectrum's floor (SPEC_PHI of the plane's maximum, and SPEC_ABS_FLOOR) and SPEC_ARG_ULPS ulps of theta - angle
+    (sens: np_twin.direction_ulp_sensitivity, per texel and channel)"""
+    return texel_margins(a, r, rho, SPEC_PHI, extra=extra, per_ulp=sens, ulps=SPEC_ARG_ULPS, abs_floor=SPEC_ABS_FLOOR)
+
+
+def zero_where_reference_is_not_finite(r, *planes):
+    """The reference's own Box-Muller draws log(0) at a texel whose hash gives u1 = 0 (spectrum_compute.glsl:44-49; one texel of 2^31 --
+    fuzz2 of spectrum_records at 2048^2): there its amplitude is not finite, and so must every other evaluation's be.  Asserts that each
+    plane is non-finite exactly where r is, and returns r and the planes with those texels set to 0."""
+    bad = ~np.isfinite(r)
+    out = [np.where(bad, 0, r)]
+    for a in planes:
+        assert np.array_equal(~np.isfinite(a), bad), "non-finite texels where the reference has finite ones (or the other way round)"
+        out.append(np.where(bad, 0, a))
+    return out
+
+
+def h0_complex(h0):
+    """[n][n][4] FP32 spectrum texels -> [n][n][2] complex: (h0(k), conj(h0(-k)))"""
+    h0 = np.asarray(h0, np.float32)
+    return h0[..., 0::2] + 1j * h0[..., 1::2].astype(np.float64)
+
+
+def mirror(plane):
+    """plane[(N - y) % N][(N - x) % N]"""
+    return np.roll(plane[::-1, ::-1], 1, axis=(0, 1))
+
+
+# ---- the CPU emulation of the device code (tests/emul/emul.cpp over godotoceanwaves_amd/csrc/*.h) ----
+class EmulSpectrumPC(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("seed_x", "seed_y")] + \
+               [(n, C.c_float) for n in ("tile_x", "tile_y", "alpha", "peak_frequency", "wind_speed", "angle", "depth", "swell", "detail", "spread")]
+
+
+def emul_pc(pc):
+    """an oracle SpectrumPC as the device struct"""
+    return EmulSpectrumPC(pc.seed[0], pc.seed[1], pc.tile_length[0], pc.tile_length[1], pc.alpha, pc.peak_frequency, pc.wind_speed,
+                          pc.angle, pc.depth, pc.swell, pc.detail, pc.spread)
+
+
+def emul_library():
+    """tests/emul/libemul.so, rebuilt when emul.cpp or a device header is newer"""
+    here = os.path.dirname(os.path.abspath(__file__))
+    csrc = os.path.join(here, "..", "godotoceanwaves_amd", "csrc")
+    so = os.path.join(here, "emul", "libemul.so")
+    srcs = [os.path.join(here, "emul", "emul.cpp")] + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h")]
+    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
+        subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unknown-pragmas",
+                        "-I", csrc, srcs[0], "-o", so], check=True)
+    E = C.CDLL(so)
+    f32p = np.ctypeslib.ndpointer(np.float32, flags="C")
+    E.emul_spectrum.argtypes = [C.c_int, C.POINTER(EmulSpectrumPC), f32p, f32p, f32p]
+    E.emul_spectrum_fast.argtypes = [C.c_int, C.POINTER(EmulSpectrumPC), f32p]
+    return E
+
+
+def emul_fast_h0(E, n, pc):
+    """the kernel's form of the amplitude (spectrum_amplitude_fast) on the CPU: [n][n] complex"""
+    out = np.zeros((n, n, 2), np.float32)
+    E.emul_spectrum_fast(n, C.byref(emul_pc(pc)), out)
+    return out[..., 0] + 1j * out[..., 1].astype(np.float64)

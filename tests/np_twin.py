@@ -37,8 +37,8 @@ def jonswap_peak(U, F):
     return 22.0 * (G * G / (U * F)) ** (1.0 / 3.0)
 
 
-def _amplitude(idx, idy, n, p):
-    """get_spectrum_amplitude (spectrum_compute.glsl:103-115), complex128."""
+def _amplitude(idx, idy, n, p, terms=None):
+    """get_spectrum_amplitude (spectrum_compute.glsl:103-115), complex128.  `terms` (a dict): receives the directional factor's parts."""
     Lx, Ly = p["tile_length"]
     dkx, dky = 2 * PI / Lx, 2 * PI / Ly
     kx = (idx - n * 0.5) * dkx
@@ -68,12 +68,36 @@ def _amplitude(idx, idy, n, p):
                         (1 / np.sqrt(PI)) * (sq * 0.5 + (1 / sq) * 0.0625))
         D = norm * np.abs(np.cos((theta - p["angle"]) * 0.5)) ** (2 * s)
         d = ((0.5 / PI) * p["spread"] + D * (1 - p["spread"])) * np.exp(-(1 - p["detail"]) ** 2 * k * k)
+    if terms is not None:
+        terms.update(theta=theta, s=s, D=D, d_dir=(0.5 / PI) * p["spread"] + D * (1 - p["spread"]))
     u1, u2 = hash_uniform((idx + p["seed"][0]).astype(np.int64), (idy + p["seed"][1]).astype(np.int64))
     with np.errstate(divide="ignore"):
         rr = np.sqrt(-2.0 * np.log(u1))
     th = 2 * PI * u2
     gauss = rr * np.cos(th) + 1j * rr * np.sin(th)
     return gauss * np.sqrt(2 * S * d * w_norm)
+
+
+def amplitude(n, p):
+    """h0(k) alone: the [y][x] complex128 plane of get_spectrum_amplitude (the device stores this half; the other is its mirror)."""
+    idy, idx = np.meshgrid(np.arange(n), np.arange(n), indexing="ij")
+    return _amplitude(idx, idy, n, p)
+
+
+def direction_ulp_sensitivity(n, p):
+    """Per texel, the relative change of |h0(k)| that ONE FP32 ulp of theta - angle causes (spectrum_compute.glsl:75,111): |cos((theta - angle)/2)|
+    raised to 2 s has the logarithmic derivative s |tan((theta - angle)/2)|, unbounded at the wind's null direction, where the cosine passes
+    zero; the directional factor weighs in by its share of (spread / 2 pi + D (1 - spread)), and the amplitude is its square root.  An FP32
+    evaluation -- any: atan2f's ulp, the rounding of the difference -- is off by a few of these there, and the formulas are to blame."""
+    idy, idx = np.meshgrid(np.arange(n), np.arange(n), indexing="ij")
+    t = {}
+    _amplitude(idx, idy, n, p, terms=t)
+    arg = t["theta"] - p["angle"]
+    ulp = np.spacing(np.abs(arg).astype(np.float32)).astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        share = np.where(t["d_dir"] > 0, t["D"] * (1 - p["spread"]) / t["d_dir"], 0.0)
+        sens = 0.5 * share * t["s"] * np.abs(np.tan(arg * 0.5)) * ulp
+    return np.nan_to_num(sens, nan=0.0, posinf=0.0)
 
 
 def spectrum(n, p):

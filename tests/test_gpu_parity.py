@@ -21,7 +21,7 @@ def make_gen(n, cascade_ids, debug=True, kernels=None):
     return gen, params
 
 
-@pytest.mark.parametrize("n", [128, 256, 512, 1024])
+@pytest.mark.parametrize("n", [128, 256, 512, 1024, 2048])
 def test_spectrum_and_omega(n):
     """spectrum_compute.glsl: h0 within 2e-5 (max-norm relative; libm vs device libm ulps), omega BIT-exact."""
     ids = [0, 2]
