@@ -22,6 +22,7 @@ OW_FLAG_LAZY_SCRATCH = 0x2000
 OW_FLAG_SINGLE_STREAM = 0x4000
 OW_QUERY_DISTANCE_FALLOFF = 1
 OW_BUOYANCY_WARM_START = 1
+OW_BUOYANCY_WATER_VELOCITY = 2
 OW_RAY_HIT, OW_RAY_FROM_BELOW, OW_RAY_TRUNCATED, OW_RAY_INVALID = 1, 2, 4, 8
 OW_OK, OW_ERR_INVALID, OW_ERR_NO_DEVICE, OW_ERR_HIP, OW_ERR_NOMEM, OW_ERR_STATE = range(6)
 
@@ -90,6 +91,11 @@ class ow_surface_query(C.Structure):
     _fields_ = [("p", C.c_float * 2), ("residual", C.c_float), ("iterations", C.c_int32), ("evaluations", C.c_int32),
                 ("converged", C.c_int32), ("falloff", C.c_float), ("height", C.c_float), ("normal", C.c_float * 3),
                 ("world_xz", C.c_float * 2), ("reserved", C.c_int32 * 3), ("sample", ow_surface_sample)]
+
+
+class ow_surface_velocity(C.Structure):
+    """struct ow_surface_velocity (32 bytes): the velocity of the rendered surface above a world point, with the query's height and p"""
+    _fields_ = [("velocity", C.c_float * 3), ("height", C.c_float), ("p", C.c_float * 2), ("converged", C.c_int32), ("reserved", C.c_uint32)]
 
 
 class ow_buoyancy_body(C.Structure):
@@ -178,6 +184,12 @@ SIGNATURES = {
                                     C.c_void_p, C.c_void_p]),
     "ow_raycast_surface": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, _P(ow_raycast_options), C.c_void_p]),
     "ow_raycast_surface_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, _P(ow_raycast_options), C.c_void_p]),
+    "ow_update_velocity": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "ow_get_velocity_ptrs": (C.c_int, [C.c_void_p, _P(C.c_void_p), _P(C.c_size_t)]),
+    "ow_get_velocity_map": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
+    "ow_velocity_stats": (C.c_int, [C.c_void_p, _P(C.c_uint64), _P(C.c_uint64)]),
+    "ow_query_velocity": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, _P(ow_query_options), C.c_void_p]),
+    "ow_query_velocity_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, _P(ow_query_options), C.c_void_p]),
     "ow_get_maps_f32": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
     "ow_get_spectrum": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "ow_get_intermediate": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),

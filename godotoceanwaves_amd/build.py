@@ -19,6 +19,7 @@ UNITS = {
     "ow_runtime.hip": [],
     "ow_consumer.hip": ["-ffp-contract=off"],
     "ow_group.hip": [],
+    "ow_velocity.hip": [],
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-fno-fast-math", "-fvisibility=hidden", "-Wall", "-Wno-unused-function"]
 

@@ -18,8 +18,10 @@
 //   d_i  = (water_level + H_i) - w.y             depth below the surface (negative above it)
 //   s_i  = clamp((d_i + h_i) / (h_i + h_i), 0, 1), or (d_i > 0 ? 1 : 0) where h_i = 0     submerged fraction
 //   sv_i = V_i * s_i                             submerged volume
-//   u_i  = v + w x r_i                           the point's velocity; the water is taken at rest (the generator makes no velocity
-//                                                maps, so water-particle velocity is not modelled)
+//   u_i  = v + w x r_i                           the point's velocity relative to the water; the water is taken at rest, or, with
+//                                                OW_BUOYANCY_WATER_VELOCITY, u_i = (v + w x r_i) - v_w with v_w the velocity of the
+//                                                rendered surface above the point (ow_velocity.h velocity_sum at p; a point below the
+//                                                surface gets the surface's velocity: there is no decay with depth)
 //   c_i  = density * sv_i,  m_i = k_quad * |u_i|  (|u| = sqrt((u.x^2 + u.y^2) + u.z^2))
 //   drag = c_i * (k_lin * u_i + m_i * u_i)       per component
 //   F_i  = (-drag.x, (density * gravity) * sv_i - drag.y, -drag.z)
@@ -84,6 +86,7 @@ struct BuoyancyParams {
     float rho_g;        // density * gravity in FP32
     float water_level;  // metres
     int warm_start;     // 1: start Newton from the lane's previous record
+    int water_velocity; // 1: drag relative to the moving surface (OW_BUOYANCY_WATER_VELOCITY; the runtime picks the kernel by it)
 };
 
 OW_DEV bool finite_f32(float x) { return fabsf(x) <= 3.4028235e38f; }
@@ -120,10 +123,18 @@ OW_DEV BuoyancyPoint invalid_point() {
     return o;
 }
 
+// The water of the model: at rest (StillWater), or moving with the velocity maps (ow_velocity.h MovingWater: kMoving, and
+// water(px, pz, f, vw) writes the surface velocity v_w at the solved point p with falloff f).
+struct StillWater {
+    static constexpr bool kMoving = false;
+    OW_DEV void operator()(float, float, float, float *) const {}
+};
+
 // Hull point i.  prev: the lane's record of the previous step (read only with bp.warm_start: world, p, converged; zeros make a cold start).
-OW_DEV BuoyancyPoint buoyancy_point(const u16x4 *disp, int n, int cascades, const SurfaceScales &scales, const QueryParams &qp,
-                                    const BuoyancyParams &bp, const BuoyancyBody *bodies, int num_bodies, const HullPoint *hull, int i,
-                                    const BuoyancyPoint &prev) {
+template <class Water>
+OW_DEV BuoyancyPoint buoyancy_point_in(const u16x4 *disp, int n, int cascades, const SurfaceScales &scales, const QueryParams &qp,
+                                       const BuoyancyParams &bp, const BuoyancyBody *bodies, int num_bodies, const HullPoint *hull, int i,
+                                       const BuoyancyPoint &prev, const Water &water) {
     const HullPoint hp = hull[i];
     const int bi = hp.body;
     if (bi < 0 || bi >= num_bodies) return invalid_point();
@@ -162,7 +173,12 @@ OW_DEV BuoyancyPoint buoyancy_point(const u16x4 *disp, int n, int cascades, cons
     }
     const float sv = hp.volume * s;
     const float *v = b.linear_velocity, *om = b.angular_velocity;
-    const float u[3] = {v[0] + (om[1] * r[2] - om[2] * r[1]), v[1] + (om[2] * r[0] - om[0] * r[2]), v[2] + (om[0] * r[1] - om[1] * r[0])};
+    float u[3] = {v[0] + (om[1] * r[2] - om[2] * r[1]), v[1] + (om[2] * r[0] - om[0] * r[2]), v[2] + (om[0] * r[1] - om[1] * r[0])};
+    if constexpr (Water::kMoving) {
+        float vw[3];
+        water(sol.p[0], sol.p[1], sol.e.f, vw);
+        for (int k = 0; k < 3; ++k) u[k] = u[k] - vw[k];
+    }
     const float un = sqrtf((u[0] * u[0] + u[1] * u[1]) + u[2] * u[2]);
     const float c = bp.density * sv, m = b.quadratic_drag * un;
     float drag[3];
@@ -187,6 +203,11 @@ OW_DEV BuoyancyPoint buoyancy_point(const u16x4 *disp, int n, int cascades, cons
     o.converged = (sol.finite && sol.e.r <= qp.tolerance) ? 1 : 0;
     o.body = bi;
     return o;
+}
+OW_DEV BuoyancyPoint buoyancy_point(const u16x4 *disp, int n, int cascades, const SurfaceScales &scales, const QueryParams &qp,
+                                    const BuoyancyParams &bp, const BuoyancyBody *bodies, int num_bodies, const HullPoint *hull, int i,
+                                    const BuoyancyPoint &prev) {
+    return buoyancy_point_in(disp, n, cascades, scales, qp, bp, bodies, num_bodies, hull, i, prev, StillWater{});
 }
 
 // ---- the per-body sum ----------------------------------------------------------------------------------------------------------------

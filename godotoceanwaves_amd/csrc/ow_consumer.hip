@@ -52,6 +52,30 @@ __global__ void __launch_bounds__(256) k_buoyancy_points(const u16x4 *disp, int 
     pts[i] = buoyancy_point(disp, n, cascades, scales, qp, bp, bodies, num_bodies, hull, i, prev);
 }
 
+// k_buoyancy_points with OW_BUOYANCY_WATER_VELOCITY: the drag is taken relative to the surface's velocity (ow_velocity.h)
+__global__ void __launch_bounds__(256) k_buoyancy_points_moving(const u16x4 *disp, const u16x4 *vel, int n, int cascades, const BuoyancyBody *bodies,
+                                                                int num_bodies, const HullPoint *hull, int num_points, SurfaceScales scales,
+                                                                QueryParams qp, BuoyancyParams bp, BuoyancyPoint *pts) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= num_points) return;
+    BuoyancyPoint prev;
+    if (bp.warm_start) {
+        prev = pts[i];
+    } else {
+        prev.world[0] = prev.world[2] = prev.p[0] = prev.p[1] = 0.0f;
+        prev.converged = 0;
+    }
+    pts[i] = buoyancy_point_moving(disp, vel, n, cascades, scales, qp, bp, bodies, num_bodies, hull, i, prev);
+}
+
+// One lane per query point (ow_velocity.h velocity_point), the shape of k_query_surface
+__global__ void __launch_bounds__(256) k_query_velocity(const u16x4 *disp, const u16x4 *vel, int n, int cascades, const float *xz, int count,
+                                                        SurfaceScales scales, QueryParams qp, SurfaceVelocity *out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    out[i] = velocity_point(disp, vel, n, cascades, scales, qp, xz[2 * i], xz[2 * i + 1]);
+}
+
 __device__ inline BodySum shfl_xor_sum(const BodySum &a, int m) {
     BodySum o;
     for (int k = 0; k < 3; ++k) {
@@ -152,11 +176,15 @@ hipError_t launch_query_surface(int n, int cascades, const DeviceBuffers &buf, c
 
 hipError_t launch_buoyancy(int n, int cascades, const DeviceBuffers &buf, const BuoyancyBody *bodies_dev, int num_bodies, const HullPoint *hull_dev,
                            int num_points, const SurfaceScales &scales, const QueryParams &qp, const BuoyancyParams &bp, BuoyancyPoint *pts_dev,
-                           BuoyancyResult *results_dev, hipStream_t s) {
+                           BuoyancyResult *results_dev, hipStream_t s, const u16x4 *vel) {
     const int threads = 256;
     if (num_points > 0) {
-        hipLaunchKernelGGL(k_buoyancy_points, dim3((num_points + threads - 1) / threads), dim3(threads), 0, s, buf.disp, n, cascades, bodies_dev,
-                           num_bodies, hull_dev, num_points, scales, qp, bp, pts_dev);
+        if (vel)
+            hipLaunchKernelGGL(k_buoyancy_points_moving, dim3((num_points + threads - 1) / threads), dim3(threads), 0, s, buf.disp, vel, n, cascades,
+                               bodies_dev, num_bodies, hull_dev, num_points, scales, qp, bp, pts_dev);
+        else
+            hipLaunchKernelGGL(k_buoyancy_points, dim3((num_points + threads - 1) / threads), dim3(threads), 0, s, buf.disp, n, cascades, bodies_dev,
+                               num_bodies, hull_dev, num_points, scales, qp, bp, pts_dev);
         if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
     }
     if (num_bodies > 0) {
@@ -165,6 +193,15 @@ hipError_t launch_buoyancy(int n, int cascades, const DeviceBuffers &buf, const 
         return hipGetLastError();
     }
     return hipSuccess;
+}
+
+hipError_t launch_query_velocity(int n, int cascades, const DeviceBuffers &buf, const u16x4 *vel, const float *xz_dev, int count,
+                                 const SurfaceScales &scales, const QueryParams &qp, SurfaceVelocity *out_dev, hipStream_t s) {
+    if (count <= 0) return hipSuccess;
+    const int threads = 256;
+    hipLaunchKernelGGL(k_query_velocity, dim3((count + threads - 1) / threads), dim3(threads), 0, s, buf.disp, vel, n, cascades, xz_dev, count,
+                       scales, qp, out_dev);
+    return hipGetLastError();
 }
 
 hipError_t launch_raycast(int n, int cascades, const DeviceBuffers &buf, const Ray *rays_dev, int count, const SurfaceScales &scales,

@@ -568,6 +568,8 @@ ow_status ow_group_buoyancy(ow_group *g, const ow_buoyancy_body *bodies, int32_t
     ow::QueryParams qp;
     ow::BuoyancyParams bp;
     if (ow_status st = ow::resolve_buoyancy_options(opts, &qp, &bp); st != OW_OK) return st;
+    // the group gathers no velocity layers: the flag the context path accepts (resolve_buoyancy_options) is refused here
+    if (bp.water_velocity) return fail(OW_ERR_INVALID, "OW_BUOYANCY_WATER_VELOCITY is not available on a group (it gathers no velocity layers)");
     if (!map_scales || (num_bodies > 0 && (!bodies || !results)) || (num_points > 0 && !hull)) return fail(OW_ERR_INVALID, "null argument");
     if (num_points > 0 && bp.warm_start && !points_inout) return fail(OW_ERR_INVALID, "OW_BUOYANCY_WARM_START needs points_inout");
     if (ow_status st = ow::check_buoyancy_arrays(bodies, num_bodies, hull, num_points); st != OW_OK) return st;

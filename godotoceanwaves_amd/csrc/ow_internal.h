@@ -36,9 +36,11 @@ ow_status check_buoyancy_arrays(const ow_buoyancy_body *bodies, int num_bodies, 
 // arrays in, both kernels, the results (and, with points_inout, the records) out.  The caller synchronises.
 struct DeviceBuffers;
 struct SurfaceScales;
+struct u16x4;
 ow_status buoyancy_enqueue_host(int n, int cascades, const DeviceBuffers &buf, hipStream_t s, void **scratch, size_t *scratch_bytes,
                                 const ow_buoyancy_body *bodies, int num_bodies, const ow_hull_point *hull, int num_points, const SurfaceScales &sc,
-                                const QueryParams &qp, const BuoyancyParams &bp, ow_buoyancy_result *results, ow_buoyancy_point *points_inout);
+                                const QueryParams &qp, const BuoyancyParams &bp, ow_buoyancy_result *results, ow_buoyancy_point *points_inout,
+                                const u16x4 *vel = nullptr);  // vel: the velocity layers (OW_BUOYANCY_WATER_VELOCITY)
 
 }  // namespace ow
 

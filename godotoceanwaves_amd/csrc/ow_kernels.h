@@ -6,6 +6,8 @@
 #include "ow_buoyancy.h"
 #include "ow_raycast.h"
 #include "ow_surface.h"
+#include "ow_velocity.h"
+#include "ow_velocity_kernels.h"
 
 namespace ow {
 
@@ -42,7 +44,14 @@ hipError_t launch_query_surface(int n, int cascades, const DeviceBuffers &buf, c
 // points, then the per-body sums over num_bodies bodies, both on `s`.  pts_dev: the per-point records (read first with bp.warm_start).
 hipError_t launch_buoyancy(int n, int cascades, const DeviceBuffers &buf, const BuoyancyBody *bodies_dev, int num_bodies, const HullPoint *hull_dev,
                            int num_points, const SurfaceScales &scales, const QueryParams &qp, const BuoyancyParams &bp, BuoyancyPoint *pts_dev,
-                           BuoyancyResult *results_dev, hipStream_t s);
+                           BuoyancyResult *results_dev, hipStream_t s, const u16x4 *vel = nullptr);  // vel: the velocity layers (OW_BUOYANCY_WATER_VELOCITY)
+// the velocity of the surface above each point (ow_consumer.hip; per-point code and the record in ow_velocity.h)
+hipError_t launch_query_velocity(int n, int cascades, const DeviceBuffers &buf, const u16x4 *vel, const float *xz_dev, int count,
+                                 const SurfaceScales &scales, const QueryParams &qp, SurfaceVelocity *out_dev, hipStream_t s);
+// the velocity layers (ow_velocity.hip; kernels in ow_velocity_kernels.h): twiddle table tw (n entries exp(2 pi i m / n)) once, then per batch
+// of args.count <= vel_batch(n) cascades pass 1 into `scratch` (args.count * vel_scratch_bytes(n)) and pass 2 into vel, both on `s`
+hipError_t launch_velocity_twiddles(int n, cplx *tw, hipStream_t s);
+hipError_t launch_velocity(int n, const VelocityArgs &args, const DeviceBuffers &buf, const cplx *tw, cplx *scratch, u16x4 *vel, hipStream_t s);
 // ray casts (ow_consumer.hip; the rounds, records and the slab in ow_raycast.h): bound_dev (cascades words) is cleared, k_height_bound
 // fills it, then k_raycast_surface casts `count` rays, all on `s`
 hipError_t launch_raycast(int n, int cascades, const DeviceBuffers &buf, const Ray *rays_dev, int count, const SurfaceScales &scales,

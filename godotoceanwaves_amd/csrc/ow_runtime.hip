@@ -169,6 +169,16 @@ struct ow_context {
     ow::RaycastHit *ray_out = nullptr;
     int ray_capacity = 0;
     uint32_t *ray_bound = nullptr;
+    // the velocity layers (ow_update_velocity; ow_velocity_kernels.h): V in the displacement array's layout, the pipeline's own intermediate
+    // (vel_slots cascades of one launch pair) and twiddle table, all allocated by the first velocity call
+    ow::u16x4 *vel = nullptr;
+    ow::cplx *vel_scratch = nullptr, *vel_tw = nullptr;
+    int vel_slots = 0;
+    // Layers whose V no longer belongs to their maps: set by mark_recomputed (every batch that recomputes a layer), cleared by the velocity
+    // launch that computes them.  spectrum_ahead: layers whose resident spectrum was regenerated by a batch that did not get as far as
+    // launching their pass 2 (enqueue); their h0 is newer than their maps, and their velocity is refused until a batch recomputes them.
+    uint32_t velocity_stale = 0, spectrum_ahead = 0;
+    uint64_t vel_computed = 0, vel_skipped = 0;  // ow_velocity_stats
 };
 
 // The stream everything but a first-chain launch is enqueued on or synchronised through: joins the second chain first (a no-op when none is in flight).
@@ -525,6 +535,7 @@ ow_status settle_spectrum(ow_context *c, int cascade, ow_cascade_params &p, bool
     } else {
         if (!generate) return OW_OK;
         c->spectrum_resident[cascade] = false;
+        c->spectrum_ahead |= 1u << cascade;  // (until enqueue has launched the layer's pass 2 from it)
         OW_HIP(ow::launch_spectrum(c->n, cascade, pc, c->buf, main_stream(c)));
         std::memcpy(c->pc_words[cascade].spectrum, w, sizeof(w));  // wave_generator.gd:71, in the reference's order
         c->spectrum_resident[cascade] = true;
@@ -577,6 +588,7 @@ ow::CascadeFrame frame_of(const ow_cascade_params &p, int cascade) {
 void mark_recomputed(ow_context *c, uint32_t layers) {
     c->maps_faulted &= ~layers;
     c->enqueued_since_sync |= layers;
+    c->velocity_stale |= layers;  // (V follows the maps lazily: ow_update_velocity)
 }
 // launch slot `slot` of a batch being started recomputes layer `cascade` from record p
 void start_slot(ow_context *c, ow::FrameArgs &args, int slot, int cascade, const ow_cascade_params &p) {
@@ -628,6 +640,7 @@ ow_status enqueue(ow_context *c, ow_cascade_params *params, const int *idx, int 
         OW_HIP(ow::launch_pass1(c->n, nb, c->kernel_mode, part, c->buf, main_stream(c), t1));  // modulate + rows + transpose (:73-80)
         OW_HIP(ow::launch_pass2(c->n, nb, c->kernel_mode, part, c->buf, main_stream(c), t2));  // rows + unpack (:82-85)
     }
+    for (int i = 0; i < count; ++i) c->spectrum_ahead &= ~(1u << idx[i]);  // the maps are made from the resident spectrum again
     return OW_OK;
 }
 
@@ -1174,6 +1187,9 @@ void ow_destroy(ow_context *c) {
     (void)hipFree(c->ray_in);
     (void)hipFree(c->ray_out);
     (void)hipFree(c->ray_bound);
+    (void)hipFree(c->vel);
+    (void)hipFree(c->vel_scratch);
+    (void)hipFree(c->vel_tw);
     for (auto &e : c->ev)
         if (e) (void)hipEventDestroy(e);
     if (c->side_fork_ev) (void)hipEventDestroy(c->side_fork_ev);
@@ -2065,15 +2081,17 @@ ow_status resolve_buoyancy_options(const ow_buoyancy_options *o, QueryParams *qp
     bp->density = kDefaultDensity;
     bp->water_level = 0.0f;
     bp->warm_start = 0;
+    bp->water_velocity = 0;
     float gravity = kDefaultGravity;
     if (o) {
         if (!std::isfinite(o->density) || !std::isfinite(o->gravity) || !std::isfinite(o->water_level))
             return fail(OW_ERR_INVALID, "density, gravity and water_level must be finite");
-        if (o->flags & ~OW_BUOYANCY_WARM_START) return fail(OW_ERR_INVALID, "unknown buoyancy flags 0x%x", o->flags);
+        if (o->flags & ~(OW_BUOYANCY_WARM_START | OW_BUOYANCY_WATER_VELOCITY)) return fail(OW_ERR_INVALID, "unknown buoyancy flags 0x%x", o->flags);
         if (o->density > 0.0f) bp->density = o->density;
         if (o->gravity > 0.0f) gravity = o->gravity;
         bp->water_level = o->water_level;
         bp->warm_start = (o->flags & OW_BUOYANCY_WARM_START) ? 1 : 0;
+        bp->water_velocity = (o->flags & OW_BUOYANCY_WATER_VELOCITY) ? 1 : 0;
     }
     bp->rho_g = bp->density * gravity;
     if (!std::isfinite(bp->rho_g)) return fail(OW_ERR_INVALID, "density * gravity overflows");
@@ -2102,7 +2120,8 @@ ow_status check_buoyancy_arrays(const ow_buoyancy_body *bodies, int num_bodies, 
 
 ow_status buoyancy_enqueue_host(int n, int cascades, const DeviceBuffers &buf, hipStream_t s, void **scratch, size_t *scratch_bytes,
                                 const ow_buoyancy_body *bodies, int num_bodies, const ow_hull_point *hull, int num_points, const SurfaceScales &sc,
-                                const QueryParams &qp, const BuoyancyParams &bp, ow_buoyancy_result *results, ow_buoyancy_point *points_inout) {
+                                const QueryParams &qp, const BuoyancyParams &bp, ow_buoyancy_result *results, ow_buoyancy_point *points_inout,
+                                const u16x4 *vel) {
     auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t b_bytes = up((size_t)num_bodies * sizeof(BuoyancyBody)), h_bytes = up((size_t)num_points * sizeof(HullPoint));
     const size_t p_bytes = up((size_t)num_points * sizeof(BuoyancyPoint)), r_bytes = up((size_t)num_bodies * sizeof(BuoyancyResult));
@@ -2123,7 +2142,7 @@ ow_status buoyancy_enqueue_host(int n, int cascades, const DeviceBuffers &buf, h
     if (num_bodies > 0) OW_HIP(hipMemcpyAsync(bd, bodies, (size_t)num_bodies * sizeof(BuoyancyBody), hipMemcpyHostToDevice, s));
     if (num_points > 0) OW_HIP(hipMemcpyAsync(hd, hull, (size_t)num_points * sizeof(HullPoint), hipMemcpyHostToDevice, s));
     if (bp.warm_start && num_points > 0) OW_HIP(hipMemcpyAsync(pd, points_inout, (size_t)num_points * sizeof(BuoyancyPoint), hipMemcpyHostToDevice, s));
-    OW_HIP(launch_buoyancy(n, cascades, buf, bd, num_bodies, hd, num_points, sc, qp, bp, pd, rd, s));
+    OW_HIP(launch_buoyancy(n, cascades, buf, bd, num_bodies, hd, num_points, sc, qp, bp, pd, rd, s, vel));
     if (num_bodies > 0) OW_HIP(hipMemcpyAsync(results, rd, (size_t)num_bodies * sizeof(BuoyancyResult), hipMemcpyDeviceToHost, s));
     if (points_inout && num_points > 0) OW_HIP(hipMemcpyAsync(points_inout, pd, (size_t)num_points * sizeof(BuoyancyPoint), hipMemcpyDeviceToHost, s));
     return OW_OK;
@@ -2131,6 +2150,83 @@ ow_status buoyancy_enqueue_host(int n, int cascades, const DeviceBuffers &buf, h
 }  // namespace ow
 
 namespace {
+// ---- the velocity layers (ow_velocity_kernels.h) -------------------------------------------------------------------------------------
+// V, its intermediate and its twiddle table, on first use (on the context's device; V starts zeroed, in stream order)
+ow_status velocity_buffers(ow_context *c) {
+    if (c->vel) return OW_OK;
+    const size_t pl = plane(c);
+    const int slots = std::min(ow::vel_batch(c->n), c->cascades);
+    if (hipMalloc((void **)&c->vel_tw, (size_t)c->n * sizeof(ow::cplx)) != hipSuccess ||
+        hipMalloc((void **)&c->vel_scratch, (size_t)slots * ow::vel_scratch_bytes(c->n)) != hipSuccess ||
+        hipMalloc((void **)&c->vel, (size_t)c->cascades * pl * sizeof(ow::u16x4)) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipFree(c->vel_tw);
+        (void)hipFree(c->vel_scratch);
+        (void)hipFree(c->vel);
+        c->vel_tw = c->vel_scratch = nullptr;
+        c->vel = nullptr;
+        return fail(OW_ERR_NOMEM, "hipMalloc failed for the velocity layers (%d x %d^2) and their intermediate", c->cascades, c->n);
+    }
+    c->vel_slots = slots;
+    OW_HIP(ow::launch_velocity_twiddles(c->n, c->vel_tw, main_stream(c)));
+    OW_HIP(hipMemsetAsync(c->vel, 0, (size_t)c->cascades * pl * sizeof(ow::u16x4), main_stream(c)));
+    return OW_OK;
+}
+
+// The layers of `mask` (inside [0, cascades)) whose velocity is stale are recomputed, in stream order behind everything the context has
+// enqueued, from the resident spectrum and the words their current maps were made with (pc_words[i].modulate); the others are skipped.
+// A layer never computed is OW_ERR_STATE, a faulted one is refused as its maps are, and so is one whose spectrum is newer than its maps.
+ow_status velocity_refresh(ow_context *c, uint32_t mask) {
+    for (int i = 0; i < c->cascades; ++i)
+        if ((mask >> i & 1u) && !c->pc_valid[i]) return fail(OW_ERR_STATE, "cascade %d has not been computed yet: it has no velocity", i);
+    if (ow_status st = refuse_faulted(c, mask); st != OW_OK) return st;
+    if (c->spectrum_ahead & mask)
+        return fail(OW_ERR_STATE, "layer mask 0x%x: the resident spectrum is newer than the maps (a failed batch regenerated it): recompute the layers first",
+                    c->spectrum_ahead & mask);
+    if (ow_status st = velocity_buffers(c); st != OW_OK) return st;
+    const uint32_t todo = mask & c->velocity_stale;
+    c->vel_skipped += (uint64_t)__builtin_popcount(mask & ~todo);
+    ow::VelocityArgs args;
+    std::memset(&args, 0, sizeof(args));
+    auto word = [](uint32_t w) {
+        float f;
+        std::memcpy(&f, &w, 4);
+        return f;
+    };
+    auto flush = [&]() -> ow_status {
+        if (args.count == 0) return OW_OK;
+        OW_HIP(ow::launch_velocity(c->n, args, c->buf, c->vel_tw, c->vel_scratch, c->vel, main_stream(c)));
+        for (int k = 0; k < args.count; ++k) c->velocity_stale &= ~(1u << args.cascade[k]);
+        c->vel_computed += (uint64_t)args.count;
+        args.count = 0;
+        return OW_OK;
+    };
+    for (int i = 0; i < c->cascades; ++i) {
+        if (!(todo >> i & 1u)) continue;
+        const uint32_t *m = c->pc_words[i].modulate;
+        args.cascade[args.count] = i;
+        args.tile_x[args.count] = word(m[0]);
+        args.tile_y[args.count] = word(m[1]);
+        args.time[args.count] = word(m[3]);
+        if (++args.count == c->vel_slots)
+            if (ow_status st = flush(); st != OW_OK) return st;
+    }
+    return flush();
+}
+
+ow_status check_velocity_mask(const ow_context *c, uint32_t mask) {
+    if (!c) return fail(OW_ERR_INVALID, "null context");
+    if (mask & ~((1u << c->cascades) - 1u)) return fail(OW_ERR_INVALID, "cascade_mask 0x%x names layers outside [0,%d)", mask, c->cascades);
+    return OW_OK;
+}
+// every layer that has been computed
+uint32_t computed_layers(const ow_context *c) {
+    uint32_t m = 0;
+    for (int i = 0; i < c->cascades; ++i)
+        if (c->pc_valid[i]) m |= 1u << i;
+    return m;
+}
+
 // what both context forms check before they touch the context's device: counts, options, pointers (host arrays: ranges and indices)
 ow_status check_buoyancy_call(const ow_buoyancy_body *bodies, int32_t num_bodies, const ow_hull_point *hull, int32_t num_points,
                               const float *map_scales, const ow_buoyancy_options *opts, const void *results, const void *points, bool host,
@@ -2163,9 +2259,11 @@ ow_status ow_buoyancy(ow_context *c, const ow_buoyancy_body *bodies, int32_t num
     if (ow_status st = check_point_query(c, 0, num_cascades); st != OW_OK) return st;
     if (num_bodies == 0 && num_points == 0) return OW_OK;
     OW_HIP(hipSetDevice(c->device));
+    if (bp.water_velocity)  // the velocity layers the drag is taken against, refreshed in stream order first
+        if (ow_status st = velocity_refresh(c, (1u << num_cascades) - 1u); st != OW_OK) return st;
     const ow::SurfaceScales sc = surface_scales(map_scales, num_cascades);
     if (ow_status st = ow::buoyancy_enqueue_host(c->n, num_cascades, c->buf, main_stream(c), &c->buoy_scratch, &c->buoy_bytes, bodies, num_bodies, hull,
-                                                 num_points, sc, qp, bp, results, points_inout);
+                                                 num_points, sc, qp, bp, results, points_inout, bp.water_velocity ? c->vel : nullptr);
         st != OW_OK)
         return st;
     return sync_stream(c, (1u << num_cascades) - 1u);
@@ -2183,10 +2281,13 @@ ow_status ow_buoyancy_async(ow_context *c, const ow_buoyancy_body *bodies_dev, i
     if (num_bodies == 0 && num_points == 0) return OW_OK;
     if (ow_status st = refuse_faulted(c, (1u << num_cascades) - 1u); st != OW_OK) return st;
     OW_HIP(hipSetDevice(c->device));
+    if (bp.water_velocity)
+        if (ow_status st = velocity_refresh(c, (1u << num_cascades) - 1u); st != OW_OK) return st;
     const ow::SurfaceScales sc = surface_scales(map_scales, num_cascades);
     // main_stream(): behind the second chain's join as well as everything on the context's (or the caller's) stream
     OW_HIP(ow::launch_buoyancy(c->n, num_cascades, c->buf, (const ow::BuoyancyBody *)bodies_dev, num_bodies, (const ow::HullPoint *)hull_dev, num_points,
-                               sc, qp, bp, (ow::BuoyancyPoint *)points_dev, (ow::BuoyancyResult *)results_dev, main_stream(c)));
+                               sc, qp, bp, (ow::BuoyancyPoint *)points_dev, (ow::BuoyancyResult *)results_dev, main_stream(c),
+                               bp.water_velocity ? c->vel : nullptr));
     return OW_OK;
 }
 
@@ -2269,6 +2370,76 @@ ow_status ow_raycast_surface_async(ow_context *c, const ow_ray *rays_dev, int32_
     // main_stream(): behind the second chain's join as well as everything on the context's (or the caller's) stream
     OW_HIP(ow::launch_raycast(c->n, num_cascades, c->buf, (const ow::Ray *)rays_dev, count, sc, rp, c->ray_bound, (ow::RaycastHit *)out_dev,
                               main_stream(c)));
+    return OW_OK;
+}
+
+ow_status ow_update_velocity(ow_context *c, uint32_t cascade_mask) {
+    if (ow_status st = check_velocity_mask(c, cascade_mask); st != OW_OK) return st;
+    if (cascade_mask == 0) return OW_OK;
+    OW_HIP(hipSetDevice(c->device));
+    return velocity_refresh(c, cascade_mask);
+}
+
+ow_status ow_get_velocity_ptrs(ow_context *c, void **velocity_map, size_t *layer_stride_bytes) {
+    if (!c) return fail(OW_ERR_INVALID, "null context");
+    if (!velocity_map && !layer_stride_bytes) return fail(OW_ERR_INVALID, "null output");
+    OW_HIP(hipSetDevice(c->device));
+    if (ow_status st = velocity_buffers(c); st != OW_OK) return st;
+    if (ow_status st = velocity_refresh(c, computed_layers(c)); st != OW_OK) return st;
+    if (velocity_map) *velocity_map = c->vel;
+    if (layer_stride_bytes) *layer_stride_bytes = plane(c) * sizeof(ow::u16x4);
+    return OW_OK;
+}
+
+ow_status ow_get_velocity_map(ow_context *c, int32_t cascade, void *velocity_rgba16f) {
+    if (ow_status st = check_cascade(c, cascade); st != OW_OK) return st;
+    if (!velocity_rgba16f) return fail(OW_ERR_INVALID, "null output");
+    OW_HIP(hipSetDevice(c->device));
+    if (ow_status st = velocity_refresh(c, 1u << cascade); st != OW_OK) return st;
+    OW_HIP(hipMemcpyAsync(velocity_rgba16f, c->vel + cascade * plane(c), plane(c) * sizeof(ow::u16x4), hipMemcpyDeviceToHost, main_stream(c)));
+    return sync_stream(c, 1u << cascade);
+}
+
+ow_status ow_velocity_stats(const ow_context *c, uint64_t *layers_computed, uint64_t *layers_skipped) {
+    if (!c) return fail(OW_ERR_INVALID, "null context");
+    if (layers_computed) *layers_computed = c->vel_computed;
+    if (layers_skipped) *layers_skipped = c->vel_skipped;
+    return OW_OK;
+}
+
+ow_status ow_query_velocity(ow_context *c, const float *xz, int32_t count, const float *map_scales, int32_t num_cascades,
+                            const ow_query_options *opts, ow_surface_velocity *out) {
+    static_assert(sizeof(ow_surface_velocity) == sizeof(ow::SurfaceVelocity) && offsetof(ow_surface_velocity, converged) == offsetof(ow::SurfaceVelocity, converged),
+                  "record layout");
+    static_assert(sizeof(ow::SurfaceQuery) >= sizeof(ow::SurfaceVelocity), "the record buffer holds either kind");
+    if (ow_status st = check_point_query(c, count, num_cascades); st != OW_OK) return st;
+    ow::QueryParams qp;
+    if (ow_status st = ow::resolve_query_options(opts, &qp); st != OW_OK) return st;
+    if (count == 0) return OW_OK;
+    if (!xz || !map_scales || !out) return fail(OW_ERR_INVALID, "null argument");
+    OW_HIP(hipSetDevice(c->device));
+    if (ow_status st = velocity_refresh(c, (1u << num_cascades) - 1u); st != OW_OK) return st;
+    if (ow_status st = query_scratch(c, count); st != OW_OK) return st;
+    const ow::SurfaceScales sc = surface_scales(map_scales, num_cascades);
+    OW_HIP(hipMemcpyAsync(c->query_xz, xz, (size_t)count * 2 * sizeof(float), hipMemcpyHostToDevice, main_stream(c)));
+    OW_HIP(ow::launch_query_velocity(c->n, num_cascades, c->buf, c->vel, c->query_xz, count, sc, qp, (ow::SurfaceVelocity *)c->query_out, main_stream(c)));
+    OW_HIP(hipMemcpyAsync(out, c->query_out, (size_t)count * sizeof(ow::SurfaceVelocity), hipMemcpyDeviceToHost, main_stream(c)));
+    return sync_stream(c, (1u << num_cascades) - 1u);
+}
+
+ow_status ow_query_velocity_async(ow_context *c, const float *xz_dev, int32_t count, const float *map_scales, int32_t num_cascades,
+                                  const ow_query_options *opts, ow_surface_velocity *out_dev) {
+    if (ow_status st = check_point_query(c, count, num_cascades); st != OW_OK) return st;
+    ow::QueryParams qp;
+    if (ow_status st = ow::resolve_query_options(opts, &qp); st != OW_OK) return st;
+    if (count == 0) return OW_OK;
+    if (!xz_dev || !map_scales || !out_dev) return fail(OW_ERR_INVALID, "null argument");
+    if (ow_status st = refuse_faulted(c, (1u << num_cascades) - 1u); st != OW_OK) return st;
+    OW_HIP(hipSetDevice(c->device));
+    if (ow_status st = velocity_refresh(c, (1u << num_cascades) - 1u); st != OW_OK) return st;
+    const ow::SurfaceScales sc = surface_scales(map_scales, num_cascades);
+    // main_stream(): behind the second chain's join as well as everything on the context's (or the caller's) stream
+    OW_HIP(ow::launch_query_velocity(c->n, num_cascades, c->buf, c->vel, xz_dev, count, sc, qp, (ow::SurfaceVelocity *)out_dev, main_stream(c)));
     return OW_OK;
 }
 

@@ -330,15 +330,15 @@ class WaveGenerator:
 
     @classmethod
     def buoyancy_options(cls, options=None):
-        """None, an _lib.ow_buoyancy_options, or a dict of density / gravity / water_level / warm_start (bool) and the query_options keys
-        -> ow_buoyancy_options, or None for the defaults"""
+        """None, an _lib.ow_buoyancy_options, or a dict of density / gravity / water_level / warm_start (bool) / water_velocity (bool: drag
+        relative to the moving surface) and the query_options keys -> ow_buoyancy_options, or None for the defaults"""
         if options is None or isinstance(options, _lib.ow_buoyancy_options):
             return options
-        own = {"density", "gravity", "water_level", "warm_start"}
+        own = {"density", "gravity", "water_level", "warm_start", "water_velocity"}
         q = cls.query_options({k: v for k, v in options.items() if k not in own})
+        flags = (_lib.OW_BUOYANCY_WARM_START if options.get("warm_start") else 0) | (_lib.OW_BUOYANCY_WATER_VELOCITY if options.get("water_velocity") else 0)
         o = _lib.ow_buoyancy_options(density=float(options.get("density", 0.0)), gravity=float(options.get("gravity", 0.0)),
-                                     water_level=float(options.get("water_level", 0.0)),
-                                     flags=_lib.OW_BUOYANCY_WARM_START if options.get("warm_start") else 0)
+                                     water_level=float(options.get("water_level", 0.0)), flags=flags)
         if q is not None:
             o.query = q
         return o
@@ -461,6 +461,60 @@ class WaveGenerator:
         o = self.raycast_options(options)
         _lib.check(self._lib.ow_raycast_surface_async(self.context, addr(rays_device), int(count), sc.ctypes.data, len(sc),
                                                       C.byref(o) if o is not None else None, addr(out_device)))
+
+    # ---- the water's velocity: V = dD/dt per layer, and the surface's velocity above world points (include/ocean_waves.h ow_update_velocity) ----
+    SURFACE_VELOCITY = np.dtype([("velocity", np.float32, 3), ("height", np.float32), ("p", np.float32, 2), ("converged", np.int32),
+                                 ("reserved", np.uint32)])
+
+    def update_velocity(self, cascades=None):
+        """enqueue the refresh of the stale velocity layers among `cascades` (indices; None = all), without synchronising"""
+        mask = (1 << self.num_cascades) - 1 if cascades is None else sum(1 << int(i) for i in cascades)
+        _lib.check(self._lib.ow_update_velocity(self.context, mask))
+
+    def velocity_ptrs(self):
+        """(device address of the velocity array, layer stride in bytes), every computed layer refreshed first"""
+        p, st = C.c_void_p(), C.c_size_t()
+        _lib.check(self._lib.ow_get_velocity_ptrs(self.context, C.byref(p), C.byref(st)))
+        return p.value, st.value
+
+    def velocity_map(self, cascade):
+        """layer `cascade` of the velocity array as FP16 [N][N][4]: (dD_x/dt, dD_y/dt, dD_z/dt, 0) in m/s, before displacement_scale"""
+        n = self.map_size
+        out = np.empty((n, n, 4), np.float16)
+        _lib.check(self._lib.ow_get_velocity_map(self.context, int(cascade), out.ctypes.data))
+        return out
+
+    def velocity_stats(self):
+        """(computed, skipped): velocity layers computed, and layers asked for that were current already"""
+        a, b = C.c_uint64(), C.c_uint64()
+        _lib.check(self._lib.ow_velocity_stats(self.context, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def query_velocity(self, world_xz, map_scales, options=None):
+        """The velocity of the rendered surface above world points [P][2] (x, z), with ow_query_surface's height, p and convergence.
+        Returns a structured array (SURFACE_VELOCITY)."""
+        xz = np.ascontiguousarray(world_xz, np.float32).reshape(-1, 2)
+        sc = np.ascontiguousarray(map_scales, np.float32).reshape(-1, 4)
+        out = np.zeros(len(xz), self.SURFACE_VELOCITY)
+        o = self.query_options(options)
+        _lib.check(self._lib.ow_query_velocity(self.context, xz.ctypes.data, len(xz), sc.ctypes.data, len(sc),
+                                               C.byref(o) if o is not None else None, out.ctypes.data))
+        return out
+
+    def query_velocity_async(self, xz_device, map_scales, out_device, options=None, count=None):
+        """query_velocity over DEVICE buffers, as query_surface_async (out_device: room for count 32-byte records)"""
+        def addr(b):
+            return int(b.data_ptr()) if hasattr(b, "data_ptr") else int(b)
+        if count is None:
+            if not hasattr(xz_device, "numel"):
+                raise ValueError("count is needed for a raw device address")
+            count = int(xz_device.numel()) // 2
+        if hasattr(out_device, "numel") and hasattr(out_device, "element_size") and out_device.numel() * out_device.element_size() < count * self.SURFACE_VELOCITY.itemsize:
+            raise ValueError(f"out_device holds fewer than {count} records of {self.SURFACE_VELOCITY.itemsize} bytes")
+        sc = np.ascontiguousarray(map_scales, np.float32).reshape(-1, 4)
+        o = self.query_options(options)
+        _lib.check(self._lib.ow_query_velocity_async(self.context, addr(xz_device), int(count), sc.ctypes.data, len(sc),
+                                                     C.byref(o) if o is not None else None, addr(out_device)))
 
     def get_push_constants(self, cascade):
         """(spectrum[16], modulate[8], unpack[4]) uint32 words: the reference's push-constant blocks of this cascade's most recent launch"""

@@ -380,11 +380,14 @@ ow_status ow_query_surface_async(ow_context *ctx, const float *world_xz_dev, int
  *     s = clamp((d + h) / (2 h), 0, 1) (h = 0: d > 0 ? 1 : 0), u = v + omega x r,
  *     F = (0, density * gravity * V * s, 0) - density * V * s * (linear_drag * u + quadratic_drag * |u| * u);
  * per body (FP64, in a fixed order, so that every build gives the same bits): sum F, the torque sum r x F about o in world axes, the
- * submerged volume sum V s and the centre of buoyancy o + sum V s r / sum V s (o when nothing is submerged).  The water is taken at rest:
- * the generator makes no velocity maps.  A point with a non-finite input or world position, or one whose body index does not name the
+ * submerged volume sum V s and the centre of buoyancy o + sum V s r / sum V s (o when nothing is submerged).  The water is taken at rest,
+ * or, with OW_BUOYANCY_WATER_VELOCITY, moving: u = (v + omega x r) - v_w, v_w the velocity of the rendered surface above (w.x, w.z)
+ * (ow_query_velocity's velocity, the same bits; a point below the surface gets the surface's velocity).  A point with a non-finite input or world position, or one whose body index does not name the
  * body whose range holds it, contributes nothing and is counted invalid.  Nothing returned is NaN or Inf.  The exact operation order is
  * godotoceanwaves_amd/csrc/ow_buoyancy.h's. */
 #define OW_BUOYANCY_WARM_START 1u  /* start each point's Newton solve from its previous record: p_prev + (q - q_prev) */
+#define OW_BUOYANCY_WATER_VELOCITY 2u  /* drag relative to the moving surface: velocity layers 0 .. num_cascades - 1 are refreshed first
+                                          (ow_update_velocity); not available on a group (ow_group_buoyancy: OW_ERR_INVALID) */
 typedef struct ow_buoyancy_body {
     float transform[12];        /* Godot's Transform3D: basis rows [0..8], origin [9..11]; world = B * local + o */
     float linear_velocity[3];   /* m/s */
@@ -462,6 +465,47 @@ ow_status ow_buoyancy(ow_context *ctx, const ow_buoyancy_body *bodies, int32_t n
 ow_status ow_buoyancy_async(ow_context *ctx, const ow_buoyancy_body *bodies_dev, int32_t num_bodies, const ow_hull_point *hull_dev,
                             int32_t num_points, const float *map_scales, int32_t num_cascades, const ow_buoyancy_options *opts,
                             ow_buoyancy_result *results_dev, ow_buoyancy_point *points_dev);
+
+/* The water's velocity.  A context-owned array V (layers x N x N RGBA16F, the displacement array's layout): texel (x, y) of layer i holds
+ * (dD_x/dt, dD_y/dt, dD_z/dt, 0) in m/s, before displacement_scale -- the exact time derivatives of channels hx, hy, hz of layer i's current
+ * displacement map, from the resident spectrum and the FP32 tile_length / time words those maps were made with (ow_get_push_constants).
+ * V follows the maps lazily: a layer whose maps have been recomputed since its velocity was is stale, and each call below recomputes the
+ * stale layers it selects (in the context's stream order, both chains joined, a caller's stream included) and skips the others.  A
+ * selected layer that has never been computed is OW_ERR_STATE; faulted layers are refused as by ow_query_surface.  The buffers are
+ * allocated by the first velocity call.  ow_update_velocity enqueues the refresh of the stale layers of cascade_mask (bit i = layer i)
+ * and does not synchronise.  ow_get_velocity_ptrs refreshes every computed layer, then hands out the device array and its layer stride
+ * (valid until ow_destroy).  ow_get_velocity_map copies layer `cascade` (N * N * 8 bytes) to host memory; synchronises.
+ * ow_velocity_stats: layers computed and layers skipped (current already) by this context. */
+ow_status ow_update_velocity(ow_context *ctx, uint32_t cascade_mask);
+ow_status ow_get_velocity_ptrs(ow_context *ctx, void **velocity_map, size_t *layer_stride_bytes);
+ow_status ow_get_velocity_map(ow_context *ctx, int32_t cascade, void *velocity_rgba16f);
+ow_status ow_velocity_stats(const ow_context *ctx, uint64_t *layers_computed, uint64_t *layers_skipped);
+
+/* The velocity of the rendered surface above world point q: the vertex p + f(p) D(p, t) at the query's solved p moves with
+ *     velocity = f(p) * sum_i map_scales_i.z * bilinear(V_i, p * map_scales_i.xy).xyz   (FP32, cascades in order 0, 1, ...),
+ * the water's velocity at the surface there.  There is no decay with depth.  One record per point, 32 bytes:
+ *   offset  0  velocity[3]   m/s
+ *          12  height        the same bits as ow_surface_query.height for the same point and options
+ *          16  p[2]          the same bits as ow_surface_query.p
+ *          24  converged     as ow_surface_query.converged
+ *          28  reserved */
+typedef struct ow_surface_velocity {
+    float velocity[3];
+    float height;
+    float p[2];
+    int32_t converged;
+    uint32_t reserved;
+} ow_surface_velocity;
+typedef char ow_layout_check_surface_velocity[(sizeof(ow_surface_velocity) == 32 && offsetof(ow_surface_velocity, height) == 12 &&
+                                               offsetof(ow_surface_velocity, converged) == 24) ? 1 : -1];
+/* The query at `count` points (host pointers, as ow_query_surface); velocity layers 0 .. num_cascades - 1 are refreshed first.
+ * Synchronises.  Bad arguments are OW_ERR_INVALID and nothing is written. */
+ow_status ow_query_velocity(ow_context *ctx, const float *world_xz, int32_t count, const float *map_scales, int32_t num_cascades,
+                            const ow_query_options *opts, ow_surface_velocity *out);
+/* The same with DEVICE pointers, as ow_query_surface_async: stream order, no copy, no synchronisation, no allocation beyond the velocity
+ * buffers' first use. */
+ow_status ow_query_velocity_async(ow_context *ctx, const float *world_xz_dev, int32_t count, const float *map_scales, int32_t num_cascades,
+                                  const ow_query_options *opts, ow_surface_velocity *out_dev);
 
 /* Ray casts against the rendered water: where a ray first meets the height field ow_query_surface reports (ow_surface_query.height at
  * (x, z), water_level added).  For ray i, d^ = direction / |direction| (FP32) and t is metres along d^; g(t) = (o + t d^).y - (water_level +

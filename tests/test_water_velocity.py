@@ -1,0 +1,510 @@
+"""The water's velocity (include/ocean_waves.h ow_update_velocity, ow_get_velocity_map, ow_query_velocity, OW_BUOYANCY_WATER_VELOCITY):
+V = dD/dt per layer on the device (godotoceanwaves_amd/csrc/ow_velocity_kernels.h), the surface's velocity above world points and the
+drag relative to it (ow_velocity.h).
+
+CPU: the ABI (plain C99 header, exports, ctypes / NumPy layouts), the argument checks without a device, and ow_velocity.h compiled as plain
+C++ (tests/velocity/velocity_harness.cpp, g++ -ffp-contract=off) against an FP64 restatement on synthetic layers.  GPU: the layers against
+an FP64 NumPy twin of the derivative at every map size, against a central difference of the FP32 maps, after every schedule; the laziness;
+the device records against the CPU build bit for bit; buoyancy with and without the flag."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import helpers as H
+import np_twin as NT
+from godotoceanwaves_amd import _lib, build
+from godotoceanwaves_amd.presets import UPDATE_DELTA
+from godotoceanwaves_amd.wave_generator import WaveGenerator as W
+from test_buoyancy import RHO, RHO_G, cpu_buoyancy, harness as buoyancy_harness, make_scene  # noqa: F401
+from test_surface_query import gpu_maps, make_gen, maps_u16, scales_of
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "godotoceanwaves_amd", "csrc")
+HERE = os.path.dirname(os.path.abspath(__file__))
+HEADER = open(os.path.join(ROOT, "include", "ocean_waves.h")).read()
+NEW_FUNCTIONS = ("ow_update_velocity", "ow_get_velocity_ptrs", "ow_get_velocity_map", "ow_velocity_stats", "ow_query_velocity",
+                 "ow_query_velocity_async")
+REC = W.SURFACE_VELOCITY
+# The twin's floor relative to a channel's largest |v| (helpers.fp16_close): the layers are FP32 transforms of an FP32 spectrum, like the
+# maps, but the derivative weighs every mode by omega, so the high wave numbers -- where the FP32 wave-vector and phase arithmetic is least
+# exact relative to the mode -- carry more of the sum than in D.  2e-5 of max|v| is still five times tighter than FP16's own 2^-11.
+FLOOR = 2e-5
+
+
+@pytest.fixture(scope="module")
+def harness(tmp_path_factory):
+    so = str(tmp_path_factory.mktemp("velocity") / "libvelocity_harness.so")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unknown-pragmas", "-I", CSRC,
+                    os.path.join(HERE, "velocity", "velocity_harness.cpp"), "-o", so], check=True)
+    L = C.CDLL(so)
+    V = C.c_void_p
+    L.harness_velocity_sizes.argtypes = [V]
+    L.harness_query_velocity.argtypes = [V, V, C.c_int, C.c_int, V, V, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.c_float, V]
+    L.harness_buoyancy_moving.argtypes = [V, V, C.c_int, C.c_int, V, V, C.c_int, V, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float,
+                                          C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, V, V]
+    return L
+
+
+def cpu_query_velocity(L, disp, vel, scales, xz, falloff_center=None):
+    d, v = maps_u16(disp), maps_u16(vel)
+    sc = np.ascontiguousarray(scales, np.float32)
+    xz = np.ascontiguousarray(xz, np.float32).reshape(-1, 2)
+    out = np.zeros(len(xz), REC)
+    cx, cz = falloff_center if falloff_center is not None else (0.0, 0.0)
+    L.harness_query_velocity(d.ctypes.data, v.ctypes.data, d.shape[1], len(sc), sc.ctypes.data, xz.ctypes.data, len(xz), 16, 1e-3,
+                             int(falloff_center is not None), cx, cz, out.ctypes.data)
+    return out
+
+
+def cpu_buoyancy_moving(L, disp, vel, scales, bodies, hull, water_level=0.0):
+    d, v = maps_u16(disp), maps_u16(vel)
+    sc = np.ascontiguousarray(scales, np.float32)
+    b = np.ascontiguousarray(bodies, W.BUOYANCY_BODY)
+    h = np.ascontiguousarray(hull, W.HULL_POINT)
+    pts = np.zeros(len(h), W.BUOYANCY_POINT)
+    res = np.zeros(len(b), W.BUOYANCY_RESULT)
+    L.harness_buoyancy_moving(d.ctypes.data, v.ctypes.data, d.shape[1], len(sc), sc.ctypes.data, b.ctypes.data, len(b), h.ctypes.data, len(h),
+                              16, 1e-3, 0, 0.0, 0.0, RHO, RHO_G, water_level, 0, pts.ctypes.data, res.ctypes.data)
+    return res, pts
+
+
+# ---- the FP64 twin of the derivative --------------------------------------------------------------------------------------------------
+
+def velocity_twin(h0_texel, omega, modulate_words):
+    """V of one layer, FP64, written from np_twin's modulate / ifft2_ref / unpack conventions with hdot in place of h: the inputs are the
+    resident spectrum (ow_get_spectrum's texel (h0(k), conj(h0(-k))) and omega) and the layer's FP32 push-constant words, the phase the FP32
+    product omega * t"""
+    n = omega.shape[0]
+    f = np.asarray(modulate_words, np.uint32).view(np.float32)
+    tile = (float(f[0]), float(f[1]))
+    ph = (omega.astype(np.float32) * f[3]).astype(np.float64)
+    om = omega.astype(np.float64)
+    h0 = h0_texel[..., 0].astype(np.float64) + 1j * h0_texel[..., 1]
+    h0m = h0_texel[..., 2].astype(np.float64) + 1j * h0_texel[..., 3]
+    m = np.exp(1j * ph)
+    hdot = 1j * om * (h0 * m - h0m * np.conj(m))
+    idy, idx = np.meshgrid(np.arange(n), np.arange(n), indexing="ij")
+    kx = (idx - n * 0.5) * 2 * np.pi / tile[0]
+    ky = (idy - n * 0.5) * 2 * np.pi / tile[1]
+    k = np.hypot(kx, ky) + 1e-6
+    ux, uy = kx / k, ky / k
+    hi = 1j * hdot
+    out = NT.ifft2_ref(np.stack([hi * uy + 1j * hdot, hi * ux + 1j * (hi * ky)]))  # modulate's layers 0 and 1
+    iy, ix = np.meshgrid(np.arange(n), np.arange(n), indexing="ij")
+    sign = 1.0 - 2.0 * ((ix & 1) ^ (iy & 1))
+    o = out * sign
+    return np.stack([o[0].real, o[0].imag, o[1].real], axis=-1)
+
+
+def check_layer(gen, i):
+    """layer i of V against the twin at the layer's own words; returns the worst ratio to the allowance"""
+    got = gen.velocity_map(i)
+    h0, om = gen.get_spectrum(i)
+    _, mod, _ = gen.get_push_constants(i)
+    want = velocity_twin(h0, om, mod)
+    assert np.all(got[..., 3].view(np.uint16) == 0)
+    assert np.isfinite(got.astype(np.float32)).all()
+    r = H.fp16_close(got[..., :3], want.astype(np.float16), ulps=1, rel_floor=FLOOR)
+    assert r <= 1.0, (i, r)
+    assert np.abs(want).max() > 1e-3  # the layer is not trivially zero
+    return r
+
+
+# ---- CPU ---------------------------------------------------------------------------------------------------------------------------
+
+def test_header_is_plain_c99_and_declares_the_velocity_entry_points(tmp_path):
+    text = re.sub(r"/\*.*?\*/", "", HEADER, flags=re.S)
+    for name in NEW_FUNCTIONS:
+        assert re.search(r"\b%s\s*\(" % name, text), name
+    assert "#define OW_BUOYANCY_WATER_VELOCITY 2u" in HEADER
+    src = tmp_path / "v.c"
+    src.write_text('#include "ocean_waves.h"\n#include <stdio.h>\nint main(void){printf("%d %d %d %d\\n",(int)sizeof(ow_surface_velocity),'
+                   '(int)offsetof(ow_surface_velocity,height),(int)offsetof(ow_surface_velocity,p),(int)offsetof(ow_surface_velocity,converged));'
+                   'return 0;}\n')
+    exe = str(tmp_path / "v")
+    subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", exe], check=True)
+    got = [int(v) for v in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split()]
+    assert got == [32, 12, 16, 24]
+
+
+def test_record_layouts_agree_in_c_ctypes_numpy_and_the_harness(harness):
+    sizes = (C.c_int * 4)()
+    harness.harness_velocity_sizes(sizes)
+    assert list(sizes) == [32, 12, 16, 24]
+    assert C.sizeof(_lib.ow_surface_velocity) == REC.itemsize == 32
+    assert _lib.ow_surface_velocity.height.offset == REC.fields["height"][1] == 12
+    assert _lib.ow_surface_velocity.converged.offset == REC.fields["converged"][1] == 24
+
+
+def test_every_new_export_is_in_the_library_and_the_ctypes_table():
+    build.build_library()
+    lib = _lib.load()
+    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    for name in NEW_FUNCTIONS:
+        assert re.search(r"\b%s\b" % name, out), name
+        assert name in _lib.SIGNATURES
+        assert hasattr(lib, name)
+
+
+def test_argument_errors_without_a_device():
+    lib = _lib.load()
+    xz = np.zeros(2, np.float32)
+    sc = np.ones(4, np.float32)
+    out = np.zeros(1, REC)
+    a, b = C.c_uint64(), C.c_uint64()
+    p, st = C.c_void_p(), C.c_size_t()
+    assert lib.ow_update_velocity(None, 1) == _lib.OW_ERR_INVALID
+    assert lib.ow_get_velocity_ptrs(None, C.byref(p), C.byref(st)) == _lib.OW_ERR_INVALID
+    assert lib.ow_get_velocity_map(None, 0, out.ctypes.data) == _lib.OW_ERR_INVALID
+    assert lib.ow_velocity_stats(None, C.byref(a), C.byref(b)) == _lib.OW_ERR_INVALID
+    for fn in (lib.ow_query_velocity, lib.ow_query_velocity_async):
+        assert fn(None, xz.ctypes.data, 1, sc.ctypes.data, 1, None, out.ctypes.data) == _lib.OW_ERR_INVALID
+    # the buoyancy flags: 0x2 is known now, 0x10 (and any other unknown bit) is still refused -- before the context is looked at
+    bodies, hull = make_scene([{"origin": (0, 0, 0), "size": (1, 1, 1), "divisions": (1, 1, 1)}])
+    res = np.zeros(1, W.BUOYANCY_RESULT)
+    for flags in (0x10, 0x4, 0x80000000):
+        o = _lib.ow_buoyancy_options(flags=flags)
+        assert lib.ow_buoyancy(None, bodies.ctypes.data, 1, hull.ctypes.data, len(hull), sc.ctypes.data, 1, C.byref(o), res.ctypes.data,
+                               None) == _lib.OW_ERR_INVALID
+    o = W.buoyancy_options({"water_velocity": True})
+    assert o.flags == _lib.OW_BUOYANCY_WATER_VELOCITY == 2
+    assert W.buoyancy_options({"water_velocity": True, "warm_start": True}).flags == 3
+    # the group refuses the flag (it gathers no velocity layers), whatever else is right
+    pts = np.zeros(len(hull), W.BUOYANCY_POINT)
+    assert lib.ow_group_buoyancy(None, bodies.ctypes.data, 1, hull.ctypes.data, len(hull), sc.ctypes.data, 1, C.byref(o), res.ctypes.data,
+                                 pts.ctypes.data) == _lib.OW_ERR_INVALID
+    assert "OW_BUOYANCY_WATER_VELOCITY" in (lib.ow_last_error() or b"").decode()
+
+
+def synthetic(n=64, cascades=3, seed=0):
+    rng = np.random.default_rng(seed)
+    disp = rng.normal(0, 0.5, (cascades, n, n, 4)).astype(np.float16)
+    vel = rng.normal(0, 2.0, (cascades, n, n, 4)).astype(np.float16)
+    vel[..., 3] = 0
+    sc = np.array([(1 / (40.0 + 30 * i), 1 / (35.0 + 20 * i), 0.8 + 0.1 * i, 1.0) for i in range(cascades)], np.float32)
+    return disp, vel, sc
+
+
+def bilinear64(layer, u, v):
+    n = layer.shape[0]
+    fx, fy = u * n - 0.5, v * n - 0.5
+    x0, y0 = np.floor(fx), np.floor(fy)
+    wx, wy = (fx - x0)[:, None], (fy - y0)[:, None]
+    c0, r0 = x0.astype(np.int64) % n, y0.astype(np.int64) % n
+    c1, r1 = (c0 + 1) % n, (r0 + 1) % n
+    L = layer.astype(np.float64)
+    return (L[r0, c0] * (1 - wx) + L[r0, c1] * wx) * (1 - wy) + (L[r1, c0] * (1 - wx) + L[r1, c1] * wx) * wy
+
+
+def test_host_velocity_and_moving_drag_against_the_fp64_twin(harness):
+    disp, vel, sc = synthetic()
+    rng = np.random.default_rng(1)
+    xz = rng.uniform(-300, 300, (3000, 2)).astype(np.float32)
+    for center in (None, (30.0, -80.0)):
+        got = cpu_query_velocity(harness, disp, vel, sc, xz, center)
+        assert all(np.isfinite(got[f]).all() for f in ("velocity", "height", "p"))
+        p = got["p"].astype(np.float64)
+        f = np.ones(len(p))
+        if center is not None:
+            dist = np.hypot(p[:, 0] - center[0], p[:, 1] - center[1])
+            f = np.minimum(np.exp(-(dist - 150.0) * 0.007), 1.0)
+        want = sum(bilinear64(vel[i], p[:, 0] * sc[i, 0], p[:, 1] * sc[i, 1])[:, :3] * sc[i, 2] for i in range(len(sc))) * f[:, None]
+        # FP32: the texture coordinate p s N is rounded (2^-22 of it, in texels) times each layer's largest texel step, and the sums
+        step = sum(sc[i, 2] * max(np.abs(np.diff(vel[i][..., :3].astype(np.float64), axis=a)).max() for a in (0, 1)) for i in range(len(sc)))
+        coord = np.abs(p).max() * sc[:, :2].max() * disp.shape[1] * 2.0 ** -22
+        err = np.abs(got["velocity"] - want)
+        assert err.max() <= 1e-6 * np.abs(want).max() + coord * step, (err.max(), coord * step)
+    # the flagged drag: u = (v + w x r) - v_w with v_w = the query's velocity at (w.x, w.z) (cold start: the same p, the same bits)
+    bodies, hull = make_scene([{"origin": (3.0, -0.2, -7.0), "size": (4, 1, 2), "divisions": (3, 2, 2), "v": (1.5, 0.2, -0.7),
+                                "w": (0.1, 0.3, -0.2), "kl": 0.4, "kq": 0.2},
+                               {"origin": (-40.0, 0.1, 25.0), "size": (2, 2, 2), "divisions": (2, 2, 2), "v": (0, 0, 0), "kl": 0.7, "kq": 0.0}])
+    res, pts = cpu_buoyancy_moving(harness, disp, vel, sc, bodies, hull)
+    assert (pts["body"] >= 0).all()
+    q = cpu_query_velocity(harness, disp, vel, sc, pts["world"][:, [0, 2]])
+    assert np.array_equal(q["p"], pts["p"]) and np.array_equal(q["height"], pts["height"])
+    for b, body in enumerate(bodies):
+        sl = slice(body["point_offset"], body["point_offset"] + body["point_count"])
+        B = body["transform"][:9].astype(np.float64).reshape(3, 3)
+        r = hull[sl]["local"].astype(np.float64) @ B.T
+        u = body["linear_velocity"].astype(np.float64) + np.cross(body["angular_velocity"].astype(np.float64), r) - q["velocity"][sl]
+        sv = hull[sl]["volume"].astype(np.float64) * pts[sl]["submerged"]
+        drag = (RHO * sv)[:, None] * (float(body["linear_drag"]) * u + float(body["quadratic_drag"]) * np.linalg.norm(u, axis=1)[:, None] * u)
+        F = -drag
+        F[:, 1] += RHO_G * sv
+        scale = np.abs(F).max() + 1.0
+        assert np.abs(pts[sl]["force"] - F).max() <= 1e-5 * scale
+        assert np.abs(res[b]["force"] - F.sum(0)).max() <= 1e-5 * scale * len(F)
+
+
+# ---- GPU: the layers ---------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [128, 256, 512, 1024, 2048])
+@pytest.mark.parametrize("count", [1, 4, 8])
+def test_layers_against_the_fp64_twin(n, count):
+    if n == 2048 and count == 8:
+        count = 6  # 2048^2 x 8 would hold 2 GiB of frame scratch beside the twin; 6 still runs two launch pairs (4 + 2)
+    gen, params = make_gen(n, list(range(count)))
+    gen.run(UPDATE_DELTA, params, 2)
+    worst = max(check_layer(gen, i) for i in range(count))
+    computed, skipped = gen.velocity_stats()
+    assert computed == count and skipped == 0
+    assert worst <= 1.0
+
+
+@pytest.mark.gpu
+def test_central_difference_of_the_fp32_maps():
+    """(D(t + d) - D(t - d)) / 2d of the FP32 maps against V at t, with t and d exact in FP32; no use of the twin's algebra"""
+    from godotoceanwaves_amd import WaveCascadeParameters
+    from godotoceanwaves_amd.presets import cascade_preset
+    n, ids, t, d = 256, [0, 1, 2], 8.0, 2.0 ** -9
+    gen = W()
+    gen.map_size = n
+    gen.debug_f32 = True
+    gen.init_gpu(len(ids))
+    params = [WaveCascadeParameters(**cascade_preset(ci)) for ci in ids]
+    for p in params:
+        p.time = t - 2 * d
+    gen.update_all(d, params)
+    lo = [gen.get_maps_f32(i)[..., :3].astype(np.float64) for i in range(len(ids))]
+    gen.update_all(d, params)
+    v = [gen.velocity_map(i).astype(np.float64)[..., :3] for i in range(len(ids))]
+    om = [gen.get_spectrum(i)[1] for i in range(len(ids))]
+    gen.update_all(d, params)
+    hi = [gen.get_maps_f32(i)[..., :3].astype(np.float64) for i in range(len(ids))]
+    for i in range(len(ids)):
+        fd = (hi[i] - lo[i]) / (2 * d)
+        dmax = max(np.abs(hi[i]).max(), np.abs(lo[i]).max())
+        wmax = float(np.abs(om[i]).max())
+        # FP32 maps: each within ~1e-6 of max|D| of the exact transform (test_gpu_parity's bound), so their difference over 2d within
+        # 2e-6 max|D| / 2d; the central difference of e^{i w t} is sin(w d) / (w d) times the derivative, off by at most (w d)^2 / 6 of
+        # each mode's velocity, bounded by (w_max d)^2 / 6 times the sum of the layer's mode velocities (<= N^2 max|hdot|: taken as
+        # 4 max|V| here, the modes do not add up in phase); V itself is FP16: half an ulp
+        tol = 2e-6 * dmax / (2 * d) + (wmax * d) ** 2 / 6 * 4 * np.abs(v[i]).max() + 0.5 * np.spacing(np.abs(v[i]).astype(np.float16)).astype(np.float64)
+        assert (np.abs(fd - v[i]) <= tol).all(), (i, (np.abs(fd - v[i]) - tol).max())
+        assert np.abs(v[i]).max() > 1e-2
+
+
+# ---- GPU: every schedule -----------------------------------------------------------------------------------------------------------
+
+@pytest.mark.gpu
+def test_update_all_with_the_look_ahead_armed():
+    gen, params = make_gen(1024, [0, 1, 2, 3])
+    for _ in range(6):
+        gen.update_all(UPDATE_DELTA, params)
+        gen.update_velocity()
+    assert gen.lookahead_stats()[0] > 0
+    for i in range(4):
+        check_layer(gen, i)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n,count", [(256, 4), (1024, 4), (512, 8), (1024, 8), (2048, 4)])
+def test_run_after_run(n, count):
+    gen, params = make_gen(n, list(range(count)))
+    for k in (3, 4):
+        gen.run(UPDATE_DELTA, params, k)
+        for i in range(count):
+            check_layer(gen, i)
+
+
+@pytest.mark.gpu
+def test_reference_schedule_mid_update_and_an_edited_record():
+    gen, params = make_gen(512, [0, 1, 2, 3])
+    gen.update_all(UPDATE_DELTA, params)
+    t0 = [gen.get_push_constants(i)[1][3] for i in range(4)]
+    gen.update(UPDATE_DELTA, params)  # arms the next tick; each _process recomputes one cascade (the last index first)
+    gen._process(UPDATE_DELTA)
+    assert gen.pass_num_cascades_remaining == 3  # layer 3 holds the new tick, layers 0-2 the previous one
+    t1 = [gen.get_push_constants(i)[1][3] for i in range(4)]
+    assert t1[:3] == t0[:3] and t1[3] != t0[3]
+    before = [gen.velocity_map(i) for i in range(4)]
+    for i in range(4):
+        check_layer(gen, i)
+    # an edited record regenerates its spectrum when, and only when, its layer is processed: mid-update the resident spectrum of the
+    # layers still waiting is the one their maps were made from, so their velocity stays exactly what it was
+    params[1].wind_speed = params[1].wind_speed * 1.5
+    params[2].wind_speed = params[2].wind_speed * 0.7
+    gen._process(UPDATE_DELTA)  # layer 2 with its edited record: its spectrum is regenerated now
+    assert gen.pass_num_cascades_remaining == 2
+    assert np.array_equal(gen.velocity_map(1), before[1]) and np.array_equal(gen.velocity_map(0), before[0])
+    for i in range(4):
+        check_layer(gen, i)
+    while gen.pass_num_cascades_remaining:
+        gen._process(UPDATE_DELTA)
+        for i in range(4):
+            check_layer(gen, i)
+    assert not np.array_equal(gen.velocity_map(1), before[1])
+    assert gen.spectrum_stats()[0] > 0
+    # ... and a flush of leftovers by the next update, with its pre-armed look-ahead
+    gen.update(UPDATE_DELTA, params)
+    gen._process(UPDATE_DELTA)
+    params[0].wind_speed = params[0].wind_speed * 1.2
+    gen.update(UPDATE_DELTA, params)
+    for i in range(4):
+        check_layer(gen, i)
+
+
+@pytest.mark.gpu
+def test_async_forms_on_a_callers_stream_without_a_host_sync():
+    import torch
+    s = torch.cuda.Stream()
+    gen, params = make_gen(1024, [0, 1, 2, 3], stream=s.cuda_stream)
+    ref, pref = make_gen(1024, [0, 1, 2, 3])
+    sc = scales_of(params)
+    rng = np.random.default_rng(3)
+    xz = rng.uniform(-400, 400, (8000, 2)).astype(np.float32)
+    xz_dev = torch.from_numpy(xz).to("cuda:0")
+    out_dev = torch.zeros((len(xz), REC.itemsize), dtype=torch.uint8, device="cuda:0")
+    torch.cuda.synchronize()
+    with torch.cuda.stream(s):
+        gen.run(UPDATE_DELTA, params, 5)
+        gen.query_velocity_async(xz_dev, sc, out_dev)
+        copy = out_dev.to("cpu", non_blocking=False)
+        gen.run(UPDATE_DELTA, params, 5)
+    s.synchronize()
+    ref.run(UPDATE_DELTA, pref, 5)
+    want = ref.query_velocity(xz, sc)
+    assert np.frombuffer(copy.numpy().tobytes(), REC).tobytes() == want.tobytes()
+    for i in range(4):
+        check_layer(gen, i)
+
+
+# ---- GPU: laziness -----------------------------------------------------------------------------------------------------------------
+
+def _digest(gen, count):
+    d, m = gpu_maps(gen, count)
+    return d.tobytes() + m.tobytes()
+
+
+@pytest.mark.gpu
+def test_laziness_and_no_effect_on_the_maps():
+    def schedule(gen, params, with_velocity):
+        for k in range(5):
+            gen.update_all(UPDATE_DELTA, params)
+            if with_velocity:
+                gen.update_velocity([k % 4])
+        gen.run(UPDATE_DELTA, params, 4)
+        if with_velocity:
+            gen.update_velocity()
+        gen.update(UPDATE_DELTA, params)
+        if with_velocity:
+            gen.velocity_map(3)
+        while gen.pass_num_cascades_remaining:
+            gen._process(UPDATE_DELTA)
+    a, pa = make_gen(1024, [0, 1, 2, 3])
+    b, pb = make_gen(1024, [0, 1, 2, 3])
+    schedule(a, pa, True)
+    schedule(b, pb, False)
+    assert _digest(a, 4) == _digest(b, 4)
+    assert a.lookahead_stats() == b.lookahead_stats()
+    # a second refresh with no tick in between computes nothing
+    a.update_velocity()
+    c0, s0 = a.velocity_stats()
+    a.update_velocity()
+    c1, s1 = a.velocity_stats()
+    assert c1 == c0 and s1 == s0 + 4
+    # a tick makes exactly the recomputed layers stale: the reference schedule recomputes one layer per call
+    a.update(UPDATE_DELTA, pa)  # arms only
+    a.update_velocity()
+    c2, s2 = a.velocity_stats()
+    assert c2 == c1 and s2 == s1 + 4
+    a._process(UPDATE_DELTA)  # layer 3
+    a.update_velocity()
+    c3, s3 = a.velocity_stats()
+    assert c3 == c2 + 1 and s3 == s2 + 3
+    a._process(UPDATE_DELTA)  # layer 2
+    a.update_velocity([0, 1])
+    c4, s4 = a.velocity_stats()
+    assert c4 == c3 and s4 == s3 + 2
+    a.update_velocity([2, 3])
+    c5, s5 = a.velocity_stats()
+    assert c5 == c4 + 1 and s5 == s4 + 1
+
+
+@pytest.mark.gpu
+def test_never_computed_layers_are_refused():
+    gen, params = make_gen(256, [0, 1, 2])
+    with pytest.raises(_lib.OceanWavesError) as e:
+        gen.update_velocity()
+    assert e.value.status == _lib.OW_ERR_STATE
+    with pytest.raises(_lib.OceanWavesError) as e:
+        gen.update_velocity([5])
+    assert e.value.status == _lib.OW_ERR_INVALID
+    gen.update(UPDATE_DELTA, params)
+    gen._process(UPDATE_DELTA)  # only layer 2 has maps
+    gen.update_velocity([2])
+    with pytest.raises(_lib.OceanWavesError) as e:
+        gen.velocity_map(0)
+    assert e.value.status == _lib.OW_ERR_STATE
+    with pytest.raises(_lib.OceanWavesError) as e:
+        gen.query_velocity(np.zeros((4, 2), np.float32), scales_of(params))
+    assert e.value.status == _lib.OW_ERR_STATE
+
+
+# ---- GPU: the query and buoyancy ---------------------------------------------------------------------------------------------------
+
+def _vel_layers(gen, count):
+    return np.stack([gen.velocity_map(i) for i in range(count)])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n,ids", [(1024, [0, 1, 2, 3]), (256, [0, 1, 2])])
+def test_query_records_are_the_cpu_builds_and_the_surface_querys(harness, n, ids):
+    gen, params = make_gen(n, ids)
+    gen.run(UPDATE_DELTA, params, 3)
+    sc = scales_of(params)
+    d, _ = gpu_maps(gen, len(ids))
+    v = _vel_layers(gen, len(ids))
+    rng = np.random.default_rng(n)
+    xz = rng.uniform(-500, 500, (20000, 2)).astype(np.float32)
+    for opts, center in ((None, None), ({"falloff_center": (12.5, -40.0)}, (12.5, -40.0))):
+        got = gen.query_velocity(xz, sc, opts)
+        want = cpu_query_velocity(harness, d, v, sc, xz, center)
+        assert got.tobytes() == want.tobytes()
+        q = gen.query_surface(xz, sc, opts)
+        for f in ("p", "height", "converged"):
+            assert got[f].tobytes() == q[f].tobytes(), f
+        assert np.isfinite(got["velocity"]).all() and np.abs(got["velocity"]).max() > 1e-2
+
+
+@pytest.mark.gpu
+def test_buoyancy_with_and_without_the_flag(harness, buoyancy_harness):
+    n, ids = 1024, [0, 1, 2, 3]
+    gen, params = make_gen(n, ids)
+    gen.run(UPDATE_DELTA, params, 3)
+    sc = scales_of(params)
+    d, _ = gpu_maps(gen, len(ids))
+    bodies, hull = make_scene([{"origin": (3.0, -0.3, -7.0), "size": (6, 1.5, 3), "divisions": (6, 3, 4), "v": (1.5, 0.2, -0.7),
+                                "w": (0.1, 0.3, -0.2), "kl": 0.4, "kq": 0.2},
+                               {"origin": (-60.0, 0.0, 25.0), "size": (2, 2, 2), "divisions": (3, 3, 3), "kl": 0.7, "kq": 0.1}])
+    # without the flag: today's records, bit for bit (the CPU build of ow_buoyancy.h as tests/test_buoyancy.py holds it)
+    pts = np.zeros(len(hull), W.BUOYANCY_POINT)
+    got = gen.buoyancy(bodies, hull, sc, None, pts)
+    want, wpts = cpu_buoyancy(buoyancy_harness, d, sc, bodies, hull)
+    assert got.tobytes() == want.tobytes() and pts.tobytes() == wpts.tobytes()
+    # with it: the CPU build of the moving-water model, bit for bit
+    pts2 = np.zeros(len(hull), W.BUOYANCY_POINT)
+    got2 = gen.buoyancy(bodies, hull, sc, {"water_velocity": True}, pts2)
+    v = _vel_layers(gen, len(ids))
+    want2, wpts2 = cpu_buoyancy_moving(harness, d, v, sc, bodies, hull)
+    assert got2.tobytes() == want2.tobytes() and pts2.tobytes() == wpts2.tobytes()
+    assert got2.tobytes() != got.tobytes()
+    # a one-point body moving with the water at its point feels no drag
+    q = gen.query_velocity(np.array([[3.0, -7.0]], np.float32), sc)
+    one, hp = make_scene([{"origin": (3.0, float(q["height"][0]) - 0.2, -7.0), "size": (0, 0, 0), "divisions": (1, 1, 1), "kl": 0.9, "kq": 0.5}])
+    hp = hp[:1].copy()
+    one[0]["point_count"] = 1
+    hp["local"] = 0.0
+    hp["volume"], hp["half_height"] = 0.125, 0.5
+    one[0]["linear_velocity"] = q["velocity"][0]
+    p1 = np.zeros(1, W.BUOYANCY_POINT)
+    r1 = gen.buoyancy(one, hp, sc, {"water_velocity": True}, p1)
+    s = p1["submerged"][0]
+    assert 0 < s <= 1
+    assert r1["force"][0][0] == 0.0 and r1["force"][0][2] == 0.0
+    assert r1["force"][0][1] == np.float32(np.float32(RHO_G) * np.float32(np.float32(0.125) * s))
