@@ -20,6 +20,8 @@ OW_FLAG_GROUP_P1_LP, OW_FLAG_GROUP_P1_COMPACT, OW_FLAG_GROUP_P2_PLAIN, OW_FLAG_G
 OW_FLAG_ALWAYS_REGENERATE_SPECTRUM = 0x1000
 OW_FLAG_LAZY_SCRATCH = 0x2000
 OW_FLAG_SINGLE_STREAM = 0x4000
+OW_FLAG_BODIES_FUSED, OW_FLAG_BODIES_SPLIT = 0x8000, 0x20000
+OW_BODIES_MAX_SUBSTEPS = 64
 OW_QUERY_DISTANCE_FALLOFF = 1
 OW_BUOYANCY_WARM_START = 1
 OW_BUOYANCY_WATER_VELOCITY = 2
@@ -130,6 +132,19 @@ class ow_buoyancy_result(C.Structure):
                 ("reserved", C.c_uint32 * 2)]
 
 
+class ow_rigid_body(C.Structure):
+    """struct ow_rigid_body (208 bytes): the FP64 state of a floating body (ow_bodies_create / ow_bodies_get_state / ow_bodies_set_state)"""
+    _fields_ = [("position", C.c_double * 3), ("orientation", C.c_double * 4), ("linear_velocity", C.c_double * 3),
+                ("angular_velocity", C.c_double * 3), ("mass", C.c_double), ("inverse_inertia", C.c_double * 3),
+                ("applied_force", C.c_double * 3), ("applied_torque", C.c_double * 3), ("linear_drag", C.c_float), ("quadratic_drag", C.c_float),
+                ("point_offset", C.c_int32), ("point_count", C.c_int32), ("reserved", C.c_uint32 * 2)]
+
+
+class ow_bodies_options(C.Structure):
+    """struct ow_bodies_options (80 bytes); zeros = the defaults of ow_buoyancy_options"""
+    _fields_ = [("buoyancy", ow_buoyancy_options), ("reserved", C.c_uint32 * 4)]
+
+
 class ow_ray(C.Structure):
     """struct ow_ray (32 bytes)"""
     _fields_ = [("origin", C.c_float * 3), ("max_distance", C.c_float), ("direction", C.c_float * 3), ("reserved", C.c_uint32)]
@@ -182,6 +197,15 @@ SIGNATURES = {
                               C.c_void_p, C.c_void_p]),
     "ow_buoyancy_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, _P(ow_buoyancy_options),
                                     C.c_void_p, C.c_void_p]),
+    "ow_bodies_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, _P(C.c_void_p)]),
+    "ow_bodies_destroy": (None, [C.c_void_p, C.c_void_p]),
+    "ow_bodies_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, _P(ow_bodies_options), C.c_int32, C.c_double]),
+    "ow_bodies_get_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "ow_bodies_set_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "ow_bodies_get_results": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "ow_bodies_get_device_ptrs": (C.c_int, [C.c_void_p, C.c_void_p, _P(C.c_void_p), _P(C.c_void_p), _P(C.c_void_p)]),
+    "ow_bodies_stats": (C.c_int, [C.c_void_p, C.c_void_p, _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64)]),
+    "ow_sync_stats": (C.c_int, [C.c_void_p, _P(C.c_uint64)]),
     "ow_raycast_surface": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, _P(ow_raycast_options), C.c_void_p]),
     "ow_raycast_surface_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, _P(ow_raycast_options), C.c_void_p]),
     "ow_update_velocity": (C.c_int, [C.c_void_p, C.c_uint32]),

@@ -86,6 +86,7 @@ struct BuoyancyParams {
     float rho_g;        // density * gravity in FP32
     float water_level;  // metres
     int warm_start;     // 1: start Newton from the lane's previous record
+    float gravity;      // m/s^2, as resolved (rho_g = density * gravity); the integrator of ow_rigid.h widens it
     int water_velocity; // 1: drag relative to the moving surface (OW_BUOYANCY_WATER_VELOCITY; the runtime picks the kernel by it)
 };
 
@@ -243,6 +244,27 @@ OW_DEV BodySum body_sum_combine(const BodySum &a, const BodySum &b) {
     return s;
 }
 
+// one valid record added to a lane's sums: the operations and their order (shared with ow_rigid.h's fused substep)
+OW_DEV void body_sum_add(BodySum &a, const BuoyancyBody &b, const HullPoint &hp, const BuoyancyPoint &rec) {
+    float r[3];
+    lever_arm(b, hp.local, r);  // the bits the point kernel used
+    const double rx = r[0], ry = r[1], rz = r[2], fx = rec.force[0], fy = rec.force[1], fz = rec.force[2];
+    const double svi = (double)(hp.volume * rec.submerged);
+    a.F[0] += fx;
+    a.F[1] += fy;
+    a.F[2] += fz;
+    a.T[0] += ry * fz - rz * fy;
+    a.T[1] += rz * fx - rx * fz;
+    a.T[2] += rx * fy - ry * fx;
+    a.SV += svi;
+    a.M[0] += svi * rx;
+    a.M[1] += svi * ry;
+    a.M[2] += svi * rz;
+    a.wetted += rec.submerged > 0.0f ? 1 : 0;
+    a.unconverged += rec.converged ? 0 : 1;
+    if (rec.residual > a.max_residual) a.max_residual = rec.residual;
+}
+
 // lane l's share of body bi: the points off + l, off + l + 64, ... in sequence
 OW_DEV BodySum body_sum_lane(const BuoyancyBody &b, int bi, const HullPoint *hull, const BuoyancyPoint *pts, int num_points, int lane) {
     BodySum a = body_sum_zero();
@@ -258,24 +280,7 @@ OW_DEV BodySum body_sum_lane(const BuoyancyBody &b, int bi, const HullPoint *hul
             ++a.invalid;
             continue;
         }
-        const HullPoint hp = hull[i];
-        float r[3];
-        lever_arm(b, hp.local, r);  // the bits the point kernel used
-        const double rx = r[0], ry = r[1], rz = r[2], fx = rec.force[0], fy = rec.force[1], fz = rec.force[2];
-        const double svi = (double)(hp.volume * rec.submerged);
-        a.F[0] += fx;
-        a.F[1] += fy;
-        a.F[2] += fz;
-        a.T[0] += ry * fz - rz * fy;
-        a.T[1] += rz * fx - rx * fz;
-        a.T[2] += rx * fy - ry * fx;
-        a.SV += svi;
-        a.M[0] += svi * rx;
-        a.M[1] += svi * ry;
-        a.M[2] += svi * rz;
-        a.wetted += rec.submerged > 0.0f ? 1 : 0;
-        a.unconverged += rec.converged ? 0 : 1;
-        if (rec.residual > a.max_residual) a.max_residual = rec.residual;
+        body_sum_add(a, b, hull[i], rec);
     }
     return a;
 }

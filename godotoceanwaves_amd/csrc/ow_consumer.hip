@@ -103,6 +103,77 @@ __global__ void __launch_bounds__(256) k_buoyancy_bodies(const BuoyancyBody *bod
     if (lane == 0) results[bi] = body_result(a, b);
 }
 
+// ---- floating bodies (ow_rigid.h) ------------------------------------------------------------------------------------------------------
+// Fused: one 64-lane wave per body, four bodies per block, the shape of k_buoyancy_bodies, all substeps of the call inside the kernel.  The
+// wave keeps the body's FP64 state in registers; per substep every lane forms the pose record (lane 0 writes it), evaluates its hull points
+// and adds them up as it goes (rigid_lane: body_sum_lane's order), the xor tree leaves the sums in every lane, and every lane integrates the
+// same state from them: nothing is broadcast and nothing but the lane's own point records is read back from memory.  Bodies do not interact:
+// no synchronisation beyond the wave's shuffles.
+template <bool Moving>
+__global__ void __launch_bounds__(256) k_bodies_step(const u16x4 *disp, const u16x4 *vel, int n, int cascades, BodiesArrays A, SurfaceScales scales,
+                                                     QueryParams qp, BuoyancyParams bp, RigidParams rp, int substeps) {
+    const int bi = blockIdx.x * 4 + (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63);
+    if (bi >= A.num_bodies) return;  // wave-uniform
+    RigidBody s = A.state[bi];
+    int32_t flag = A.flags[bi];
+    for (int step = 0; step < substeps; ++step) {
+        const bool ok = rigid_ok(s);
+        const BuoyancyBody b = rigid_pose(s, ok);
+        if (lane == 0) A.records[bi] = b;
+        BodySum a;
+        if constexpr (Moving) {
+            const MovingWater water{vel, n, cascades, &scales};
+            a = rigid_lane(disp, n, cascades, scales, qp, bp, b, bi, s.point_offset, s.point_count, A.hull, A.pts, A.num_points, lane, water);
+        } else {
+            a = rigid_lane(disp, n, cascades, scales, qp, bp, b, bi, s.point_offset, s.point_count, A.hull, A.pts, A.num_points, lane, StillWater{});
+        }
+        for (int m = 32; m >= 1; m >>= 1) a = body_sum_combine(a, shfl_xor_sum(a, m));
+        const BuoyancyResult r = rigid_finish(s, ok, flag, a, b, rp);
+        if (lane == 0 && step == substeps - 1) A.results[bi] = r;
+    }
+    if (lane == 0) {
+        A.records[bi] = rigid_pose(s, rigid_ok(s));  // the pose after the last substep
+        A.state[bi] = s;
+        A.flags[bi] = flag;
+    }
+}
+
+// Split: k_buoyancy_bodies plus the integration and the next pose record, behind a k_buoyancy_points[_moving] launch over the set's points.
+__global__ void __launch_bounds__(256) k_bodies_integrate(BodiesArrays A, RigidParams rp) {
+    const int bi = blockIdx.x * 4 + (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63);
+    if (bi >= A.num_bodies) return;  // wave-uniform
+    const BuoyancyBody b = A.records[bi];
+    RigidBody s = A.state[bi];
+    int32_t flag = A.flags[bi];
+    BodySum a = body_sum_lane(b, bi, A.hull, A.pts, A.num_points, lane);
+    for (int m = 32; m >= 1; m >>= 1) a = body_sum_combine(a, shfl_xor_sum(a, m));
+    const BuoyancyResult r = rigid_finish(s, rigid_ok(s), flag, a, b, rp);
+    if (lane == 0) {
+        A.results[bi] = r;
+        A.records[bi] = rigid_pose(s, rigid_ok(s));
+        A.state[bi] = s;
+        A.flags[bi] = flag;
+    }
+}
+
+// The pose records of bodies [first, first + count) from their states, their fault flags lowered and their point records zeroed (a cold
+// start): after ow_bodies_create and ow_bodies_set_state.  One wave per body.
+__global__ void __launch_bounds__(256) k_bodies_pose(BodiesArrays A, int first, int count) {
+    const int k = blockIdx.x * 4 + (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63);
+    if (k >= count) return;  // wave-uniform
+    const int bi = first + k;
+    const RigidBody s = A.state[bi];
+    const int64_t off = s.point_offset, end = off + (int64_t)(s.point_count > 0 ? s.point_count : 0);
+    const int64_t lo = off > 0 ? off : 0, hi = end < (int64_t)A.num_points ? end : (int64_t)A.num_points;
+    BuoyancyPoint zero = invalid_point();
+    zero.body = 0;
+    for (int64_t i = lo + lane; i < hi; i += 64) A.pts[i] = zero;
+    if (lane == 0) {
+        A.records[bi] = rigid_pose(s, rigid_ok(s));
+        A.flags[bi] = 0;
+    }
+}
+
 // Step 1 of a ray cast (ow_raycast.h): the largest FP16 magnitude of D_y per cascade, as bits, into bound[c], which the caller clears in
 // stream order before the launch.  blockIdx.y is the cascade; a grid-stride loop reads two texels (16 B) per lane and step, the wave's
 // max goes out in one atomicMax.  A max of integers: the same bits in any order.
@@ -191,6 +262,41 @@ hipError_t launch_buoyancy(int n, int cascades, const DeviceBuffers &buf, const 
         hipLaunchKernelGGL(k_buoyancy_bodies, dim3((num_bodies + 3) / 4), dim3(threads), 0, s, bodies_dev, num_bodies, hull_dev, num_points,
                            pts_dev, results_dev);
         return hipGetLastError();
+    }
+    return hipSuccess;
+}
+
+hipError_t launch_bodies_pose(const BodiesArrays &A, int first, int count, hipStream_t s) {
+    if (count <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_bodies_pose, dim3((count + 3) / 4), dim3(256), 0, s, A, first, count);
+    return hipGetLastError();
+}
+
+hipError_t launch_bodies_step(int n, int cascades, const DeviceBuffers &buf, const BodiesArrays &A, const SurfaceScales &scales, const QueryParams &qp,
+                              const BuoyancyParams &bp, const RigidParams &rp, int substeps, bool fused, hipStream_t s, const u16x4 *vel) {
+    if (A.num_bodies <= 0 || substeps <= 0) return hipSuccess;
+    const int threads = 256;
+    const dim3 body_grid((A.num_bodies + 3) / 4);
+    if (fused) {
+        if (vel)
+            hipLaunchKernelGGL(k_bodies_step<true>, body_grid, dim3(threads), 0, s, buf.disp, vel, n, cascades, A, scales, qp, bp, rp, substeps);
+        else
+            hipLaunchKernelGGL(k_bodies_step<false>, body_grid, dim3(threads), 0, s, buf.disp, vel, n, cascades, A, scales, qp, bp, rp, substeps);
+        return hipGetLastError();
+    }
+    for (int step = 0; step < substeps; ++step) {
+        if (A.num_points > 0) {
+            const dim3 point_grid((A.num_points + threads - 1) / threads);
+            if (vel)
+                hipLaunchKernelGGL(k_buoyancy_points_moving, point_grid, dim3(threads), 0, s, buf.disp, vel, n, cascades, A.records, A.num_bodies, A.hull,
+                                   A.num_points, scales, qp, bp, A.pts);
+            else
+                hipLaunchKernelGGL(k_buoyancy_points, point_grid, dim3(threads), 0, s, buf.disp, n, cascades, A.records, A.num_bodies, A.hull, A.num_points,
+                                   scales, qp, bp, A.pts);
+            if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+        }
+        hipLaunchKernelGGL(k_bodies_integrate, body_grid, dim3(threads), 0, s, A, rp);
+        if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
     }
     return hipSuccess;
 }

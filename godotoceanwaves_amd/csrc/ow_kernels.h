@@ -5,6 +5,7 @@
 #include "ow_device.h"
 #include "ow_buoyancy.h"
 #include "ow_raycast.h"
+#include "ow_rigid.h"
 #include "ow_surface.h"
 #include "ow_velocity.h"
 #include "ow_velocity_kernels.h"
@@ -45,6 +46,21 @@ hipError_t launch_query_surface(int n, int cascades, const DeviceBuffers &buf, c
 hipError_t launch_buoyancy(int n, int cascades, const DeviceBuffers &buf, const BuoyancyBody *bodies_dev, int num_bodies, const HullPoint *hull_dev,
                            int num_points, const SurfaceScales &scales, const QueryParams &qp, const BuoyancyParams &bp, BuoyancyPoint *pts_dev,
                            BuoyancyResult *results_dev, hipStream_t s, const u16x4 *vel = nullptr);  // vel: the velocity layers (OW_BUOYANCY_WATER_VELOCITY)
+// floating bodies (ow_consumer.hip; the state, the substep and its operation order in ow_rigid.h): the device arrays of one body set
+struct BodiesArrays {
+    RigidBody *state;        // [num_bodies]
+    BuoyancyBody *records;   // [num_bodies] the pose records, formed from the states
+    const HullPoint *hull;   // [num_points]
+    BuoyancyPoint *pts;      // [num_points] per-point records: diagnostics and the warm start's state
+    BuoyancyResult *results; // [num_bodies] of the last substep
+    int32_t *flags;          // [num_bodies] 1: faulted (ow_rigid.h)
+    int num_bodies, num_points;
+};
+// pose records, lowered flags and zeroed point records of bodies [first, first + count)
+hipError_t launch_bodies_pose(const BodiesArrays &A, int first, int count, hipStream_t s);
+// `substeps` substeps on `s`: fused, one k_bodies_step launch; otherwise substeps x (k_buoyancy_points[_moving], k_bodies_integrate).  The same bits.
+hipError_t launch_bodies_step(int n, int cascades, const DeviceBuffers &buf, const BodiesArrays &A, const SurfaceScales &scales, const QueryParams &qp,
+                              const BuoyancyParams &bp, const RigidParams &rp, int substeps, bool fused, hipStream_t s, const u16x4 *vel = nullptr);
 // the velocity of the surface above each point (ow_consumer.hip; per-point code and the record in ow_velocity.h)
 hipError_t launch_query_velocity(int n, int cascades, const DeviceBuffers &buf, const u16x4 *vel, const float *xz_dev, int count,
                                  const SurfaceScales &scales, const QueryParams &qp, SurfaceVelocity *out_dev, hipStream_t s);

@@ -46,11 +46,22 @@ using ow::fail;
 constexpr double kHostG = 9.81;  // wave_generator.gd:5
 }  // namespace
 
+// a body set (ow_bodies_create; the entry points are further down)
+struct ow_bodies {
+    ow_context *ctx = nullptr;  // nullptr: orphaned by ow_destroy (the device block is gone, the handle is still the caller's to destroy)
+    void *block = nullptr;  // one allocation: states, pose records, hull points, point records, results, fault flags
+    ow::BodiesArrays A{};
+    int max_points = 0;     // the largest point_count of the set
+    std::vector<int32_t> range;  // per body point_offset, point_count as created: ow_bodies_set_state may not change them
+    uint64_t substeps = 0, fused_launches = 0, split_calls = 0;
+};
+
 struct ow_context {
     int n = 0, cascades = 0, layers = 0, device = 0;
     float depth = 20.0f;
     int kernel_mode = 0;  // 0 = by batch size, 1 = standard, 2 = layer-parallel, 3 = compact-intermediate kernels (OW_FLAG_KERNELS_*)
     int last_family = 0;  // kernel family of the most recent batch
+    int bodies_mode = 0;  // ow_bodies_step: 0 = by the set's shape, 1 = fused, 2 = split (OW_FLAG_BODIES_*)
     hipStream_t stream = nullptr;
     bool own_stream = false, own_disp = false, own_norm = false;
     // TWO CHAINS (ow_kernels.h): tick-pair launches of four 1024^2 cascades a side go out as two launches of two cascades, the second halves on side_stream.
@@ -179,6 +190,8 @@ struct ow_context {
     // launching their pass 2 (enqueue); their h0 is newer than their maps, and their velocity is refused until a batch recomputes them.
     uint32_t velocity_stale = 0, spectrum_ahead = 0;
     uint64_t vel_computed = 0, vel_skipped = 0;  // ow_velocity_stats
+    std::vector<ow_bodies *> body_sets;  // the live sets of this context: ow_destroy orphans what the caller has not destroyed
+    uint64_t host_syncs = 0;  // stream synchronisations made on the caller's thread since ow_create (ow_sync_stats)
 };
 
 // The stream everything but a first-chain launch is enqueued on or synchronised through: joins the second chain first (a no-op when none is in flight).
@@ -431,6 +444,7 @@ ow_status refuse_faulted(const ow_context *c, uint32_t layer_mask) {
 // hipStreamSynchronize + the device status word.  layer_mask: the array layers whose bytes the caller is about to hand to ITS caller (0 for a
 // bare ow_sync), refused while they are those of a faulted batch.
 ow_status sync_stream(ow_context *c, uint32_t layer_mask) {
+    ++c->host_syncs;
     OW_HIP(hipStreamSynchronize(main_stream(c)));
     if (ow_status st = consume_status(c); st != OW_OK) return st;
     c->enqueued_since_sync = 0;  // everything enqueued so far has finished cleanly
@@ -1071,6 +1085,8 @@ ow_status ow_create(const ow_config *cfg, ow_context **out) {
         c->kernel_mode = (cfg->flags & OW_FLAG_KERNELS_STANDARD) ? 1 : (lp && cp) ? 4 : lp ? 2 : cp ? 3 : 0;
     }
 
+    c->bodies_mode = (cfg->flags & OW_FLAG_BODIES_FUSED) ? 1 : (cfg->flags & OW_FLAG_BODIES_SPLIT) ? 2 : 0;
+
     auto bail = [&](ow_status st) {
         ow_destroy(c);
         return st;
@@ -1160,6 +1176,11 @@ void ow_destroy(ow_context *c) {
     (void)hipSetDevice(c->device);
     if (c->side_stream) (void)hipStreamSynchronize(c->side_stream);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
+    for (ow_bodies *set : c->body_sets) {  // sets the caller has not destroyed: their memory goes with the context, the handles stay valid to destroy
+        (void)hipFree(set->block);
+        set->block = nullptr;
+        set->ctx = nullptr;
+    }
     (void)hipFree(c->buf.h0);
     (void)hipFree(c->buf.omega);
     (void)hipFree(c->buf.T);
@@ -2093,6 +2114,7 @@ ow_status resolve_buoyancy_options(const ow_buoyancy_options *o, QueryParams *qp
         bp->warm_start = (o->flags & OW_BUOYANCY_WARM_START) ? 1 : 0;
         bp->water_velocity = (o->flags & OW_BUOYANCY_WATER_VELOCITY) ? 1 : 0;
     }
+    bp->gravity = gravity;
     bp->rho_g = bp->density * gravity;
     if (!std::isfinite(bp->rho_g)) return fail(OW_ERR_INVALID, "density * gravity overflows");
     return OW_OK;
@@ -2288,6 +2310,237 @@ ow_status ow_buoyancy_async(ow_context *c, const ow_buoyancy_body *bodies_dev, i
     OW_HIP(ow::launch_buoyancy(c->n, num_cascades, c->buf, (const ow::BuoyancyBody *)bodies_dev, num_bodies, (const ow::HullPoint *)hull_dev, num_points,
                                sc, qp, bp, (ow::BuoyancyPoint *)points_dev, (ow::BuoyancyResult *)results_dev, main_stream(c),
                                bp.water_velocity ? c->vel : nullptr));
+    return OW_OK;
+}
+
+}  // extern "C"
+
+// ---- floating bodies (ow_rigid.h; kernels in ow_consumer.hip) ---------------------------------------------------------------------------
+
+namespace {
+// THE SELECTION RULE.  The fused kernel serialises ceil(point_count / 64) height solves per lane and substep and fills the chip with one wave
+// per body; the split form runs one lane per hull point and pays two launches per substep.  Measured per frame of 4 substeps on 1024^2 x 4 maps
+// (profiles/bodies_step.txt): with hulls of 16 points fused takes 0.72 - 0.80 of split's time for 1 .. 4096 bodies, with 64 points 0.84 - 0.96
+// (inside the run-to-run spread for most counts); from 256 points on split takes 0.59 down to 0.05 of fused's time at every body count; at
+// 16384 bodies split is ahead at 16 and 64 points too (0.86, 0.82).  The table has no rows between 64 and 256 points nor between 4096 and
+// 16384 bodies: the thresholds are the last rows where fused was not behind.
+constexpr int kBodiesFusedMaxPoints = 64;    // largest hull of the set, in points
+constexpr int kBodiesFusedMaxBodies = 4096;  // body count
+bool bodies_fused(const ow_context *c, const ow_bodies *set) {
+    if (c->bodies_mode) return c->bodies_mode == 1;
+    return set->max_points <= kBodiesFusedMaxPoints && set->A.num_bodies <= kBodiesFusedMaxBodies;
+}
+
+// the checks of ow_bodies_create / ow_bodies_set_state on the states themselves; range: per body offset, count to hold them to (or nullptr)
+ow_status check_rigid_records(const ow_rigid_body *bodies, int first, int count, const int32_t *range) {
+    for (int k = 0; k < count; ++k) {
+        const ow_rigid_body &B = bodies[k];
+        const int b = first + k;
+        const double *groups[] = {B.position, B.linear_velocity, B.angular_velocity, B.inverse_inertia, B.applied_force, B.applied_torque};
+        for (const double *g : groups)
+            for (int i = 0; i < 3; ++i)
+                if (!std::isfinite(g[i])) return fail(OW_ERR_INVALID, "body %d: state, mass properties and applied loads must be finite", b);
+        if (!std::isfinite(B.mass) || !std::isfinite(B.linear_drag) || !std::isfinite(B.quadratic_drag))
+            return fail(OW_ERR_INVALID, "body %d: mass and drag must be finite", b);
+        for (int i = 0; i < 3; ++i)
+            if (B.inverse_inertia[i] < 0.0) return fail(OW_ERR_INVALID, "body %d: inverse_inertia must be >= 0", b);
+        double n2 = 0.0;
+        for (int i = 0; i < 4; ++i) {
+            if (!std::isfinite(B.orientation[i])) return fail(OW_ERR_INVALID, "body %d: orientation must be a finite unit quaternion", b);
+            n2 += B.orientation[i] * B.orientation[i];
+        }
+        if (!(std::fabs(std::sqrt(n2) - 1.0) <= 1e-6)) return fail(OW_ERR_INVALID, "body %d: orientation must be a unit quaternion (|q| = %.9g)", b, std::sqrt(n2));
+        if (B.reserved[0] != 0u || B.reserved[1] != 0u) return fail(OW_ERR_INVALID, "body %d: ow_rigid_body.reserved must be 0", b);
+        if (range && (B.point_offset != range[2 * b] || B.point_count != range[2 * b + 1]))
+            return fail(OW_ERR_INVALID, "body %d: the hull range [%d, %d + %d) is fixed at ow_bodies_create", b, range[2 * b], range[2 * b], range[2 * b + 1]);
+    }
+    return OW_OK;
+}
+
+ow_status check_bodies_handle(const ow_context *c, const ow_bodies *set) {
+    if (!c) return fail(OW_ERR_INVALID, "null context");
+    if (!set) return fail(OW_ERR_INVALID, "null body set");
+    if (!set->ctx) return fail(OW_ERR_STATE, "the body set's context has been destroyed");
+    if (set->ctx != c) return fail(OW_ERR_INVALID, "the body set belongs to another context");
+    return OW_OK;
+}
+ow_status check_bodies_span(const ow_context *c, const ow_bodies *set, int32_t first, int32_t count, const void *records) {
+    if (ow_status st = check_bodies_handle(c, set); st != OW_OK) return st;
+    if (first < 0 || count < 0 || (int64_t)first + count > set->A.num_bodies)
+        return fail(OW_ERR_INVALID, "bodies [%d, %d + %d) outside [0, %d)", first, first, count, set->A.num_bodies);
+    if (count > 0 && !records) return fail(OW_ERR_INVALID, "null argument");
+    return OW_OK;
+}
+}  // namespace
+
+extern "C" {
+
+ow_status ow_bodies_create(ow_context *c, const ow_rigid_body *bodies, int32_t num_bodies, const ow_hull_point *hull, int32_t num_points, ow_bodies **out) {
+    static_assert(sizeof(ow_rigid_body) == sizeof(ow::RigidBody) && offsetof(ow_rigid_body, orientation) == offsetof(ow::RigidBody, orientation) &&
+                      offsetof(ow_rigid_body, mass) == offsetof(ow::RigidBody, mass) &&
+                      offsetof(ow_rigid_body, inverse_inertia) == offsetof(ow::RigidBody, inverse_inertia) &&
+                      offsetof(ow_rigid_body, applied_torque) == offsetof(ow::RigidBody, applied_torque) &&
+                      offsetof(ow_rigid_body, linear_drag) == offsetof(ow::RigidBody, linear_drag) &&
+                      offsetof(ow_rigid_body, point_offset) == offsetof(ow::RigidBody, point_offset),
+                  "record layout");
+    if (!out) return fail(OW_ERR_INVALID, "null argument");
+    *out = nullptr;
+    if (num_bodies < 1 || num_points < 0) return fail(OW_ERR_INVALID, "num_bodies must be >= 1 and num_points >= 0");
+    if (!bodies || (num_points > 0 && !hull)) return fail(OW_ERR_INVALID, "null argument");
+    std::vector<ow_buoyancy_body> ranges((size_t)num_bodies);
+    std::vector<int32_t> range((size_t)num_bodies * 2);
+    int max_points = 0;
+    for (int b = 0; b < num_bodies; ++b) {
+        std::memset(&ranges[b], 0, sizeof(ow_buoyancy_body));
+        ranges[b].point_offset = range[2 * b] = bodies[b].point_offset;
+        ranges[b].point_count = range[2 * b + 1] = bodies[b].point_count;
+        max_points = std::max(max_points, bodies[b].point_count);
+    }
+    if (ow_status st = ow::check_buoyancy_arrays(ranges.data(), num_bodies, hull, num_points); st != OW_OK) return st;
+    for (int i = 0; i < num_points; ++i)
+        if (!std::isfinite(hull[i].volume) || !std::isfinite(hull[i].half_height) || !std::isfinite(hull[i].local[0]) || !std::isfinite(hull[i].local[1]) ||
+            !std::isfinite(hull[i].local[2]))
+            return fail(OW_ERR_INVALID, "hull point %d: local, volume and half_height must be finite", i);
+    if (ow_status st = check_rigid_records(bodies, 0, num_bodies, nullptr); st != OW_OK) return st;
+    if (!c) return fail(OW_ERR_INVALID, "null context");
+    OW_HIP(hipSetDevice(c->device));
+    ow_bodies *set = new (std::nothrow) ow_bodies();
+    if (!set) return fail(OW_ERR_NOMEM, "out of host memory");
+    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t nb = (size_t)num_bodies, np = (size_t)num_points;
+    const size_t s_bytes = up(nb * sizeof(ow::RigidBody)), b_bytes = up(nb * sizeof(ow::BuoyancyBody)), h_bytes = up(np * sizeof(ow::HullPoint));
+    const size_t p_bytes = up(np * sizeof(ow::BuoyancyPoint)), r_bytes = up(nb * sizeof(ow::BuoyancyResult)), f_bytes = up(nb * sizeof(int32_t));
+    const size_t total = s_bytes + b_bytes + h_bytes + p_bytes + r_bytes + f_bytes;
+    if (hipMalloc(&set->block, total) != hipSuccess) {
+        (void)hipGetLastError();
+        delete set;
+        return fail(OW_ERR_NOMEM, "hipMalloc failed for %zu bytes of body set", total);
+    }
+    char *base = (char *)set->block;
+    set->ctx = c;
+    set->A.state = (ow::RigidBody *)base;
+    set->A.records = (ow::BuoyancyBody *)(base + s_bytes);
+    set->A.hull = (const ow::HullPoint *)(base + s_bytes + b_bytes);
+    set->A.pts = (ow::BuoyancyPoint *)(base + s_bytes + b_bytes + h_bytes);
+    set->A.results = (ow::BuoyancyResult *)(base + s_bytes + b_bytes + h_bytes + p_bytes);
+    set->A.flags = (int32_t *)(base + s_bytes + b_bytes + h_bytes + p_bytes + r_bytes);
+    set->A.num_bodies = num_bodies;
+    set->A.num_points = num_points;
+    set->max_points = max_points;
+    set->range = std::move(range);
+    hipStream_t s = main_stream(c);
+    if (hipMemsetAsync(set->block, 0, total, s) != hipSuccess ||
+        hipMemcpyAsync(set->A.state, bodies, nb * sizeof(ow::RigidBody), hipMemcpyHostToDevice, s) != hipSuccess ||
+        (np > 0 && hipMemcpyAsync((void *)set->A.hull, hull, np * sizeof(ow::HullPoint), hipMemcpyHostToDevice, s) != hipSuccess) ||
+        ow::launch_bodies_pose(set->A, 0, num_bodies, s) != hipSuccess || (++c->host_syncs, hipStreamSynchronize(s)) != hipSuccess) {
+        const ow_status st = fail(OW_ERR_HIP, "body set upload failed: %s", hipGetErrorString(hipGetLastError()));
+        (void)hipFree(set->block);
+        delete set;
+        return st;
+    }
+    c->body_sets.push_back(set);
+    *out = set;
+    return OW_OK;
+}
+
+void ow_bodies_destroy(ow_context *, ow_bodies *set) {
+    if (!set) return;
+    if (ow_context *c = set->ctx) {  // its own context, still alive (ow_destroy clears this field of the sets it outlives)
+        (void)hipSetDevice(c->device);
+        ++c->host_syncs;
+        (void)hipStreamSynchronize(main_stream(c));
+        c->body_sets.erase(std::remove(c->body_sets.begin(), c->body_sets.end(), set), c->body_sets.end());
+        (void)hipFree(set->block);
+    }
+    delete set;
+}
+
+ow_status ow_bodies_step(ow_context *c, ow_bodies *set, const float *map_scales, int32_t num_cascades, const ow_bodies_options *opts, int32_t substeps,
+                         double dt) {
+    if (substeps < 1 || substeps > OW_BODIES_MAX_SUBSTEPS) return fail(OW_ERR_INVALID, "substeps %d outside [1,%d]", substeps, OW_BODIES_MAX_SUBSTEPS);
+    if (!std::isfinite(dt) || !(dt > 0.0)) return fail(OW_ERR_INVALID, "dt must be finite and > 0");
+    ow::QueryParams qp;
+    ow::BuoyancyParams bp;
+    if (ow_status st = ow::resolve_buoyancy_options(opts ? &opts->buoyancy : nullptr, &qp, &bp); st != OW_OK) return st;
+    if (opts)
+        for (uint32_t r : opts->reserved)
+            if (r != 0u) return fail(OW_ERR_INVALID, "ow_bodies_options.reserved must be 0");
+    if (!map_scales) return fail(OW_ERR_INVALID, "null argument");
+    if (ow_status st = check_bodies_handle(c, set); st != OW_OK) return st;
+    if (ow_status st = check_point_query(c, 0, num_cascades); st != OW_OK) return st;
+    if (ow_status st = refuse_faulted(c, (1u << num_cascades) - 1u); st != OW_OK) return st;
+    OW_HIP(hipSetDevice(c->device));
+    if (bp.water_velocity)  // once per call: the maps do not move between the substeps of a call
+        if (ow_status st = velocity_refresh(c, (1u << num_cascades) - 1u); st != OW_OK) return st;
+    ow::RigidParams rp;
+    rp.dt = dt;
+    rp.gravity = (double)bp.gravity;  // the g of rho_g: weight and buoyancy use the same one
+    const ow::SurfaceScales sc = surface_scales(map_scales, num_cascades);
+    const bool fused = bodies_fused(c, set);
+    // main_stream(): behind the second chain's join as well as everything on the context's (or the caller's) stream
+    OW_HIP(ow::launch_bodies_step(c->n, num_cascades, c->buf, set->A, sc, qp, bp, rp, substeps, fused, main_stream(c), bp.water_velocity ? c->vel : nullptr));
+    set->substeps += (uint64_t)substeps;
+    (fused ? set->fused_launches : set->split_calls) += 1;
+    return OW_OK;
+}
+
+ow_status ow_bodies_get_state(ow_context *c, ow_bodies *set, int32_t first, int32_t count, ow_rigid_body *records) {
+    if (ow_status st = check_bodies_span(c, set, first, count, records); st != OW_OK) return st;
+    OW_HIP(hipSetDevice(c->device));
+    if (ow_status st = sync_stream(c, 0); st != OW_OK) return st;
+    if (count > 0) OW_HIP(hipMemcpy(records, set->A.state + first, (size_t)count * sizeof(ow::RigidBody), hipMemcpyDeviceToHost));
+    return OW_OK;
+}
+
+ow_status ow_bodies_set_state(ow_context *c, ow_bodies *set, int32_t first, int32_t count, const ow_rigid_body *records) {
+    if (ow_status st = check_bodies_span(c, set, first, count, records); st != OW_OK) return st;
+    if (ow_status st = check_rigid_records(records, first, count, set->range.data()); st != OW_OK) return st;
+    OW_HIP(hipSetDevice(c->device));
+    if (ow_status st = sync_stream(c, 0); st != OW_OK) return st;
+    if (count == 0) return OW_OK;
+    OW_HIP(hipMemcpy(set->A.state + first, records, (size_t)count * sizeof(ow::RigidBody), hipMemcpyHostToDevice));
+    OW_HIP(ow::launch_bodies_pose(set->A, first, count, main_stream(c)));
+    ++c->host_syncs;
+    OW_HIP(hipStreamSynchronize(main_stream(c)));
+    return OW_OK;
+}
+
+ow_status ow_bodies_get_results(ow_context *c, ow_bodies *set, int32_t first, int32_t count, ow_buoyancy_result *results) {
+    if (ow_status st = check_bodies_span(c, set, first, count, results); st != OW_OK) return st;
+    OW_HIP(hipSetDevice(c->device));
+    if (ow_status st = sync_stream(c, 0); st != OW_OK) return st;
+    if (count > 0) OW_HIP(hipMemcpy(results, set->A.results + first, (size_t)count * sizeof(ow::BuoyancyResult), hipMemcpyDeviceToHost));
+    return OW_OK;
+}
+
+ow_status ow_bodies_get_device_ptrs(ow_context *c, ow_bodies *set, void **bodies_dev, void **results_dev, void **points_dev) {
+    if (ow_status st = check_bodies_handle(c, set); st != OW_OK) return st;
+    if (bodies_dev) *bodies_dev = set->A.records;
+    if (results_dev) *results_dev = set->A.results;
+    if (points_dev) *points_dev = set->A.pts;
+    return OW_OK;
+}
+
+ow_status ow_sync_stats(const ow_context *c, uint64_t *host_syncs) {
+    if (!c || !host_syncs) return fail(OW_ERR_INVALID, "null argument");
+    *host_syncs = c->host_syncs;
+    return OW_OK;
+}
+
+ow_status ow_bodies_stats(ow_context *c, ow_bodies *set, uint64_t *substeps, uint64_t *fused_launches, uint64_t *split_calls, uint64_t *faulted_bodies) {
+    if (ow_status st = check_bodies_handle(c, set); st != OW_OK) return st;
+    if (faulted_bodies) {
+        OW_HIP(hipSetDevice(c->device));
+        if (ow_status st = sync_stream(c, 0); st != OW_OK) return st;
+        std::vector<int32_t> flags((size_t)set->A.num_bodies);
+        OW_HIP(hipMemcpy(flags.data(), set->A.flags, flags.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        uint64_t n = 0;
+        for (int32_t f : flags) n += f != 0;
+        *faulted_bodies = n;
+    }
+    if (substeps) *substeps = set->substeps;
+    if (fused_launches) *fused_launches = set->fused_launches;
+    if (split_calls) *split_calls = set->split_calls;
     return OW_OK;
 }
 

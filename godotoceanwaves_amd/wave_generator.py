@@ -85,6 +85,13 @@ class _Descriptor:
         self.rid, self.layer_stride = rid, layer_stride
 
 
+class _BodySet:
+    """an ow_bodies handle with the counts it was created with (WaveGenerator.bodies_create)"""
+
+    def __init__(self, handle, num_bodies, num_points):
+        self.handle, self.num_bodies, self.num_points = handle, num_bodies, num_points
+
+
 class WaveGenerator:
     """assets/water/wave_generator.gd.  Typical use, as in water.gd:89-91,112-114:
 
@@ -107,6 +114,7 @@ class WaveGenerator:
         self.run_as_reference = False  # True: run() issues update() + one _process() per cascade, tick by tick (OW_FLAG_RUN_AS_REFERENCE_SCHEDULE)
         self.always_regenerate_spectrum = False  # True: every dirty flag launches the spectrum kernel, as the reference does (OW_FLAG_ALWAYS_REGENERATE_SPECTRUM)
         self.lazy_scratch = False      # True: ow_create allocates one batch of scratch, the look-ahead's share on first use (OW_FLAG_LAZY_SCRATCH)
+        self.bodies_kernels = None     # None = the runtime picks per bodies_step() call; "fused" / "split" pin the shape (OW_FLAG_BODIES_FUSED / _SPLIT)
         self.single_stream = False     # True: tick-pair launches of four 1024^2 cascades stay whole, on the one stream (OW_FLAG_SINGLE_STREAM; default: two chains on two streams)
         self.group_forms = (None, None)  # tests: pin the tick groups' work-item forms -- ("lp" | "compact", "plain" | "pipe"); None = the runtime's choice
         self.device_id = -1
@@ -128,6 +136,7 @@ class WaveGenerator:
                         normal_map=self.external_maps[1], flags=(OW_FLAG_DEBUG_F32 if self.debug_f32 else 0) | {None: 0, "lp": OW_FLAG_GROUP_P1_LP, "compact": OW_FLAG_GROUP_P1_COMPACT}[self.group_forms[0]] |
                         {None: 0, "plain": OW_FLAG_GROUP_P2_PLAIN, "pipe": OW_FLAG_GROUP_P2_PIPE}[self.group_forms[1]] | (0 if self.tick_groups else OW_FLAG_NO_TICK_GROUPS) | (OW_FLAG_RUN_AS_CALLS if self.run_as_calls else 0) | (OW_FLAG_RUN_AS_REFERENCE_SCHEDULE if self.run_as_reference else 0) |
                         (OW_FLAG_ALWAYS_REGENERATE_SPECTRUM if self.always_regenerate_spectrum else 0) | (OW_FLAG_LAZY_SCRATCH if self.lazy_scratch else 0) | (OW_FLAG_SINGLE_STREAM if self.single_stream else 0) |
+                        {None: 0, "fused": _lib.OW_FLAG_BODIES_FUSED, "split": _lib.OW_FLAG_BODIES_SPLIT}[self.bodies_kernels] |
                         {None: 0, "standard": OW_FLAG_KERNELS_STANDARD, "layer_parallel": OW_FLAG_KERNELS_LAYER_PARALLEL,
                                "compact": OW_FLAG_KERNELS_COMPACT,
                                "layer_parallel_compact": OW_FLAG_KERNELS_LAYER_PARALLEL | OW_FLAG_KERNELS_COMPACT}[self.kernels])
@@ -397,6 +406,91 @@ class WaveGenerator:
         o = self.buoyancy_options(options)
         _lib.check(self._lib.ow_buoyancy_async(self.context, addr(bodies_device), nb, addr(hull_device), npts, sc.ctypes.data, len(sc),
                                                C.byref(o) if o is not None else None, addr(results_device), addr(points_device)))
+
+    # ---- floating bodies stepped on the device (include/ocean_waves.h ow_bodies_step) ----
+    RIGID_BODY = np.dtype([("position", np.float64, 3), ("orientation", np.float64, 4), ("linear_velocity", np.float64, 3),
+                           ("angular_velocity", np.float64, 3), ("mass", np.float64), ("inverse_inertia", np.float64, 3),
+                           ("applied_force", np.float64, 3), ("applied_torque", np.float64, 3), ("linear_drag", np.float32),
+                           ("quadratic_drag", np.float32), ("point_offset", np.int32), ("point_count", np.int32), ("reserved", np.uint32, 2)])
+    BODIES_OPTIONS = np.dtype([("buoyancy", BUOYANCY_OPTIONS), ("reserved", np.uint32, 4)])
+
+    @staticmethod
+    def box_mass_properties(size, density):
+        """(mass, inverse principal inertia) of a solid box of size (x, y, z) metres and uniform density (kg/m^3) about its centre"""
+        sx, sy, sz = (float(v) for v in size)
+        mass = density * sx * sy * sz
+        inertia = (mass / 12.0 * (sy * sy + sz * sz), mass / 12.0 * (sx * sx + sz * sz), mass / 12.0 * (sx * sx + sy * sy))
+        return mass, tuple(1.0 / i for i in inertia)
+
+    @classmethod
+    def bodies_options(cls, options=None):
+        """None, an _lib.ow_bodies_options, or what buoyancy_options() takes -> ow_bodies_options, or None for the defaults"""
+        if options is None or isinstance(options, _lib.ow_bodies_options):
+            return options
+        o = _lib.ow_bodies_options()
+        o.buoyancy = cls.buoyancy_options(options)
+        return o
+
+    def bodies_create(self, bodies, hull):
+        """A device-resident body set from RIGID_BODY records and HULL_POINT records; returns a _BodySet (bodies_destroy() it before free())"""
+        b = np.ascontiguousarray(bodies, self.RIGID_BODY)
+        h = np.ascontiguousarray(hull, self.HULL_POINT)
+        out = C.c_void_p()
+        _lib.check(self._lib.ow_bodies_create(self.context, b.ctypes.data, len(b), h.ctypes.data, len(h), C.byref(out)))
+        return _BodySet(out, len(b), len(h))
+
+    def bodies_destroy(self, bodies_set):
+        if bodies_set.handle:
+            self._lib.ow_bodies_destroy(self.context, bodies_set.handle)
+            bodies_set.handle = None
+
+    def bodies_step(self, bodies_set, map_scales, substeps, dt, options=None):
+        """`substeps` substeps of dt seconds, enqueued in the generator's stream order without synchronising"""
+        sc = np.ascontiguousarray(map_scales, np.float32).reshape(-1, 4)
+        o = self.bodies_options(options)
+        _lib.check(self._lib.ow_bodies_step(self.context, bodies_set.handle, sc.ctypes.data, len(sc), C.byref(o) if o is not None else None, int(substeps),
+                                            float(dt)))
+
+    def bodies_state(self, bodies_set, first=0, count=None):
+        """RIGID_BODY records of bodies [first, first + count) (count None: up to the last one); synchronises"""
+        if count is None:
+            count = bodies_set.num_bodies - first
+        out = np.zeros(count, self.RIGID_BODY)
+        _lib.check(self._lib.ow_bodies_get_state(self.context, bodies_set.handle, int(first), int(count), out.ctypes.data))
+        return out
+
+    def bodies_set_state(self, bodies_set, records, first=0):
+        r = np.ascontiguousarray(records, self.RIGID_BODY)
+        _lib.check(self._lib.ow_bodies_set_state(self.context, bodies_set.handle, int(first), len(r), r.ctypes.data))
+
+    def bodies_results(self, bodies_set, first=0, count=None):
+        """BUOYANCY_RESULT records of the last substep; synchronises"""
+        if count is None:
+            count = bodies_set.num_bodies - first
+        out = np.zeros(count, self.BUOYANCY_RESULT)
+        _lib.check(self._lib.ow_bodies_get_results(self.context, bodies_set.handle, int(first), int(count), out.ctypes.data))
+        return out
+
+    def bodies_device_ptrs(self, bodies_set):
+        """device addresses of the pose records (BUOYANCY_BODY, Transform3D layout), the results and the per-point records"""
+        b, r, p = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _lib.check(self._lib.ow_bodies_get_device_ptrs(self.context, bodies_set.handle, C.byref(b), C.byref(r), C.byref(p)))
+        return b.value, r.value, p.value
+
+    def bodies_stats(self, bodies_set, faulted=True):
+        """dict of substeps, fused_launches, split_calls and (synchronising) faulted_bodies"""
+        v = [C.c_uint64() for _ in range(4)]
+        _lib.check(self._lib.ow_bodies_stats(self.context, bodies_set.handle, C.byref(v[0]), C.byref(v[1]), C.byref(v[2]), C.byref(v[3]) if faulted else None))
+        out = {"substeps": v[0].value, "fused_launches": v[1].value, "split_calls": v[2].value}
+        if faulted:
+            out["faulted_bodies"] = v[3].value
+        return out
+
+    def sync_stats(self):
+        """stream synchronisations the library has made on this thread since init_gpu (ow_sync_stats); does not synchronise"""
+        v = C.c_uint64()
+        _lib.check(self._lib.ow_sync_stats(self.context, C.byref(v)))
+        return v.value
 
     # ---- ray casts against the rendered water, on the device (include/ocean_waves.h ow_raycast_surface) ----
     RAY = np.dtype([("origin", np.float32, 3), ("max_distance", np.float32), ("direction", np.float32, 3), ("reserved", np.uint32)])

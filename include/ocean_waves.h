@@ -144,6 +144,13 @@ typedef struct ow_config {
  * chains. */
 #define OW_FLAG_SINGLE_STREAM 0x4000u
 
+/* Floating bodies (ow_bodies_step): by default the runtime picks per call between the FUSED kernel (one wave per body, every substep of the call
+ * in one launch) and the SPLIT form (per substep one lane per hull point, then one wave per body) from the set's body count and largest hull;
+ * these flags pin the choice (tests, measurements).  Both forms give the same bits.  Both flags together: the fused form.  The default
+ * rule: fused for sets of at most 4096 bodies whose largest hull has at most 64 points, split otherwise (profiles/bodies_step.txt). */
+#define OW_FLAG_BODIES_FUSED 0x8000u
+#define OW_FLAG_BODIES_SPLIT 0x20000u
+
 typedef struct ow_context ow_context;
 
 /* ---- lifetime ------------------------------------------------------------------------------ */
@@ -465,6 +472,78 @@ ow_status ow_buoyancy(ow_context *ctx, const ow_buoyancy_body *bodies, int32_t n
 ow_status ow_buoyancy_async(ow_context *ctx, const ow_buoyancy_body *bodies_dev, int32_t num_bodies, const ow_hull_point *hull_dev,
                             int32_t num_points, const float *map_scales, int32_t num_cascades, const ow_buoyancy_options *opts,
                             ow_buoyancy_result *results_dev, ow_buoyancy_point *points_dev);
+
+/* Floating rigid bodies, stepped on the device from the buoyancy forces.  A body set lives on the context's device: per body an FP64 state
+ * (ow_rigid_body), the ow_buoyancy_body pose record formed from it, its result and its hull points' records.  One substep of length dt forms
+ * the pose record (the basis from the quaternion in FP64, narrowed to FP32), evaluates ow_buoyancy at that pose -- the point and result
+ * records are the bits ow_buoyancy_async writes for it -- and integrates with semi-implicit Euler from the result record:
+ *     v += dt * ((F + applied_force) / mass + (0, -gravity, 0)),  w += dt * R diag(inverse_inertia) R^T (T + applied_torque),
+ *     o += dt * v,  q += (dt / 2) * (w, 0) (x) q,  q /= |q|.
+ * There is no gyroscopic term.  mass <= 0 makes a body kinematic: its forces are computed, its state is not integrated.  A body whose state
+ * or inputs are not finite is faulted: it gets the null pose record (identity, an empty hull range), zero forces, and its state is left as
+ * given; a body whose state would become non-finite in a substep keeps its last finite state; both are counted (ow_bodies_stats) and stay
+ * unintegrated until ow_bodies_set_state.  The exact operations, identical in every build, are godotoceanwaves_amd/csrc/ow_rigid.h's.
+ * There is no group form (ow_group_*) of these calls: a body set belongs to one context. */
+#define OW_BODIES_MAX_SUBSTEPS 64
+typedef struct ow_rigid_body {
+    double position[3];         /* o, world metres */
+    double orientation[4];      /* q: a unit quaternion, Godot's x, y, z, w order; world = R(q) * local + o */
+    double linear_velocity[3];  /* m/s */
+    double angular_velocity[3]; /* rad/s, world axes */
+    double mass;                /* kg; <= 0: kinematic */
+    double inverse_inertia[3];  /* 1 / (kg m^2) about the principal (body) axes; 0 locks an axis */
+    double applied_force[3];    /* N, world axes, constant over a call (thrust, tow lines) */
+    double applied_torque[3];   /* N m, world axes */
+    float linear_drag;          /* as ow_buoyancy_body */
+    float quadratic_drag;
+    int32_t point_offset;       /* the body's hull points: [point_offset, point_offset + point_count), fixed at ow_bodies_create */
+    int32_t point_count;
+    uint32_t reserved[2];       /* 0 */
+} ow_rigid_body;                /* 208 bytes */
+typedef struct ow_bodies_options {
+    ow_buoyancy_options buoyancy; /* the force model and the height solve, as for ow_buoyancy_async (OW_BUOYANCY_WARM_START: each substep starts
+                                     from the records of the one before) */
+    uint32_t reserved[4];       /* 0 */
+} ow_bodies_options;            /* 80 bytes; a NULL pointer = all defaults */
+typedef char ow_layout_check_rigid_body[(sizeof(ow_rigid_body) == 208 && offsetof(ow_rigid_body, orientation) == 24 &&
+                                         offsetof(ow_rigid_body, mass) == 104 && offsetof(ow_rigid_body, applied_force) == 136 &&
+                                         offsetof(ow_rigid_body, linear_drag) == 184 && offsetof(ow_rigid_body, point_offset) == 192) ? 1 : -1];
+typedef char ow_layout_check_bodies_options[(sizeof(ow_bodies_options) == 80 && offsetof(ow_bodies_options, reserved) == 64) ? 1 : -1];
+typedef struct ow_bodies ow_bodies;
+
+/* A body set of num_bodies >= 1 bodies over num_points hull points (host pointers).  The checks of ow_buoyancy on the ranges and the hull, and
+ * every state field finite, |q| within 1e-6 of 1: a bad argument is OW_ERR_INVALID and nothing is created.  Uploads everything, forms the pose
+ * records and zeroes the point records (the first substep starts cold).  Allocates and synchronises.  The set is destroyed with
+ * ow_bodies_destroy, before its context; a set that outlives its context loses its device memory with it, every call on it but
+ * ow_bodies_destroy is OW_ERR_STATE, and the handle is still to be destroyed. */
+ow_status ow_bodies_create(ow_context *ctx, const ow_rigid_body *bodies, int32_t num_bodies, const ow_hull_point *hull, int32_t num_points,
+                           ow_bodies **out);
+void ow_bodies_destroy(ow_context *ctx, ow_bodies *set);
+/* `substeps` (1 .. OW_BODIES_MAX_SUBSTEPS) substeps of dt seconds (finite, > 0) each against the maps as they are at this point of the
+ * context's stream: enqueued behind everything enqueued so far -- both chains -- and ahead of whatever the context enqueues next, exactly as
+ * ow_buoyancy_async (a caller's stream included).  Does not synchronise, copy or allocate (the velocity buffers' first use apart).  With
+ * OW_BUOYANCY_WATER_VELOCITY velocity layers 0 .. num_cascades - 1 are refreshed once first.  Faulted layers are refused as by
+ * ow_query_surface.  Bad arguments (substeps, dt, options, reserved words not 0) are OW_ERR_INVALID and nothing is enqueued. */
+ow_status ow_bodies_step(ow_context *ctx, ow_bodies *set, const float *map_scales, int32_t num_cascades, const ow_bodies_options *opts,
+                         int32_t substeps, double dt);
+/* The states of bodies [first, first + count).  Both synchronise.  ow_bodies_set_state teleports: the records are checked as by
+ * ow_bodies_create (the hull range must be the body's own), the bodies' fault flags are lowered and their point records zeroed (a cold start). */
+ow_status ow_bodies_get_state(ow_context *ctx, ow_bodies *set, int32_t first, int32_t count, ow_rigid_body *records);
+ow_status ow_bodies_set_state(ow_context *ctx, ow_bodies *set, int32_t first, int32_t count, const ow_rigid_body *records);
+/* The results of the last substep (the forces at the pose BEFORE its integration) of bodies [first, first + count).  Synchronises. */
+ow_status ow_bodies_get_results(ow_context *ctx, ow_bodies *set, int32_t first, int32_t count, ow_buoyancy_result *results);
+/* The set's device arrays (any pointer may be NULL): num_bodies ow_buoyancy_body records -- the latest pose in Transform3D layout, for a
+ * renderer's instance buffer --, num_bodies ow_buoyancy_result records and num_points ow_buoyancy_point records.  Valid until
+ * ow_bodies_destroy; updated in the context's stream order. */
+ow_status ow_bodies_get_device_ptrs(ow_context *ctx, ow_bodies *set, void **bodies_dev, void **results_dev, void **points_dev);
+/* Substeps taken, launches of the fused kernel, calls served by the split form, bodies flagged as faulted now (any pointer may be NULL;
+ * synchronises when faulted_bodies is asked for). */
+ow_status ow_bodies_stats(ow_context *ctx, ow_bodies *set, uint64_t *substeps, uint64_t *fused_launches, uint64_t *split_calls,
+                          uint64_t *faulted_bodies);
+/* How many times the library has synchronised the context's stream on the caller's thread since ow_create (ow_sync, the synchronous
+ * queries and read-backs, ow_bodies_get_state, ...).  Reads a counter; does not synchronise.  A frame loop that is meant to enqueue only
+ * (ow_update_all, ow_bodies_step, the _async forms) reads it before and after. */
+ow_status ow_sync_stats(const ow_context *ctx, uint64_t *host_syncs);
 
 /* The water's velocity.  A context-owned array V (layers x N x N RGBA16F, the displacement array's layout): texel (x, y) of layer i holds
  * (dD_x/dt, dD_y/dt, dD_z/dt, 0) in m/s, before displacement_scale -- the exact time derivatives of channels hx, hy, hz of layer i's current
