@@ -26,6 +26,7 @@ OW_QUERY_DISTANCE_FALLOFF = 1
 OW_BUOYANCY_WARM_START = 1
 OW_BUOYANCY_WATER_VELOCITY = 2
 OW_RAY_HIT, OW_RAY_FROM_BELOW, OW_RAY_TRUNCATED, OW_RAY_INVALID = 1, 2, 4, 8
+OW_RENDER_MAX_SIDE = 8192
 OW_OK, OW_ERR_INVALID, OW_ERR_NO_DEVICE, OW_ERR_HIP, OW_ERR_NOMEM, OW_ERR_STATE = range(6)
 
 
@@ -163,6 +164,27 @@ class ow_raycast_hit(C.Structure):
                 ("reserved", C.c_uint32 * 5), ("query", ow_surface_query)]
 
 
+class ow_camera(C.Structure):
+    """struct ow_camera (80 bytes): position, Godot Transform3D basis rows (looking down -Z, +Y up), vertical fov in degrees, image size"""
+    _fields_ = [("position", C.c_float * 3), ("max_distance", C.c_float), ("basis", C.c_float * 9), ("fov_y_degrees", C.c_float),
+                ("width", C.c_int32), ("height", C.c_int32), ("reserved", C.c_uint32 * 4)]
+
+
+class ow_render_options(C.Structure):
+    """struct ow_render_options (192 bytes); a NULL pointer = ow_render_options_default's values, a given record is taken field by field"""
+    _fields_ = [("raycast", ow_raycast_options), ("water_color", C.c_float * 3), ("roughness", C.c_float), ("foam_color", C.c_float * 3),
+                ("normal_strength", C.c_float), ("light_direction", C.c_float * 3), ("flags", C.c_uint32), ("light_color", C.c_float * 3),
+                ("ambient_color", C.c_float * 3), ("sky_color", C.c_float * 3), ("reserved", C.c_uint32 * 11)]
+
+
+class ow_render_pixel(C.Structure):
+    """struct ow_render_pixel (128 bytes): the hit, the shader's inputs at it, fragment()'s and light()'s outputs and the composite"""
+    _fields_ = [("t", C.c_float), ("status", C.c_int32), ("position", C.c_float * 3), ("p", C.c_float * 2), ("wave_height", C.c_float),
+                ("gradient_fragment", C.c_float * 2), ("foam_fragment", C.c_float), ("dist", C.c_float), ("foam_factor", C.c_float),
+                ("albedo", C.c_float * 3), ("normal", C.c_float * 3), ("fresnel", C.c_float), ("roughness", C.c_float),
+                ("diffuse", C.c_float * 3), ("specular", C.c_float), ("color", C.c_float * 3), ("reserved", C.c_uint32 * 4)]
+
+
 # every symbol include/ocean_waves.h declares: (restype, argtypes)
 _P = C.POINTER
 SIGNATURES = {
@@ -214,6 +236,9 @@ SIGNATURES = {
     "ow_velocity_stats": (C.c_int, [C.c_void_p, _P(C.c_uint64), _P(C.c_uint64)]),
     "ow_query_velocity": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, _P(ow_query_options), C.c_void_p]),
     "ow_query_velocity_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, _P(ow_query_options), C.c_void_p]),
+    "ow_render_options_default": (None, [_P(ow_render_options)]),
+    "ow_render_view": (C.c_int, [C.c_void_p, _P(ow_camera), C.c_void_p, C.c_int32, _P(ow_render_options), C.c_void_p, C.c_void_p]),
+    "ow_render_view_async": (C.c_int, [C.c_void_p, _P(ow_camera), C.c_void_p, C.c_int32, _P(ow_render_options), C.c_void_p, C.c_void_p]),
     "ow_get_maps_f32": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
     "ow_get_spectrum": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "ow_get_intermediate": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),

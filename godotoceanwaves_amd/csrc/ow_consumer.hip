@@ -225,6 +225,37 @@ __global__ void __launch_bounds__(64) k_raycast_surface(const u16x4 *disp, const
     if (wave.lane == 0) out[i] = h;
 }
 
+// One 64-lane wave per 8 x 8 pixel tile of a camera view (ow_render.h), one lane per pixel, one tile per block of 64, no LDS: lane l is
+// pixel (8 tx + (l & 7), 8 ty + (l >> 3)).  Each lane marches its own ray sample by sample (march_pixel: the ray cast's samples in order,
+// up to the first class change), embeds the query at the hit and shades it.  Neighbouring rays leave the slab after nearly the same number
+// of samples, so a wave stays converged but for tiles the horizon crosses; lanes outside the image are inactive.  The record leaves as
+// eight 16-byte vector stores and the RGBA8 pixel as one word.  __launch_bounds__(64) states the block size and asks for no occupancy: the
+// kernel is a chain of dependent loads per sample, hidden by waves per SIMD, and the compiler's own allocation is 96 VGPRs -- 5 waves per
+// SIMD -- with no scratch (profiles/render_view_1024x4.txt); the measured limit is the longest lane's chain, not residency.
+template <bool kRecords>
+__global__ void __launch_bounds__(64) k_render_view(const u16x4 *disp, const u16x4 *norm, int n, int cascades, const uint32_t *bound,
+                                                    SurfaceScales scales, RaycastParams rp, CameraParams cam, ShadeParams sp, int tiles_x,
+                                                    uint32_t *rgba, RenderPixel *pixels) {
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    const int lane = (int)threadIdx.x;
+    const int tx = (int)blockIdx.x % tiles_x, ty = (int)blockIdx.x / tiles_x;
+    const int i = 8 * tx + (lane & 7), j = 8 * ty + (lane >> 3);
+    if (i >= cam.width || j >= cam.height) return;
+    const float hw = slab_half_height(bound, cascades, scales);
+    uint32_t word;
+    const RenderPixel px = render_pixel(disp, norm, n, cascades, scales, rp, cam, sp, hw, i, j, &word);
+    const size_t at = (size_t)j * cam.width + i;
+    if (rgba) rgba[at] = word;
+    if (kRecords) {
+        struct Words {
+            u32x4 v[sizeof(RenderPixel) / 16];
+        };
+        const Words w = __builtin_bit_cast(Words, px);
+        u32x4 *dst = (u32x4 *)(pixels + at);
+        for (int k = 0; k < (int)(sizeof(RenderPixel) / 16); ++k) dst[k] = w.v[k];
+    }
+}
+
 }  // namespace
 
 hipError_t launch_sample_surface(int n, int cascades, const DeviceBuffers &buf, const float *xz_dev, int count,
@@ -319,6 +350,25 @@ hipError_t launch_raycast(int n, int cascades, const DeviceBuffers &buf, const R
     hipLaunchKernelGGL(k_height_bound, dim3(blocks, cascades), dim3(threads), 0, s, buf.disp, n, bound_dev);
     if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
     hipLaunchKernelGGL(k_raycast_surface, dim3(count), dim3(64), 0, s, buf.disp, buf.norm, n, cascades, rays_dev, bound_dev, scales, rp, out_dev);
+    return hipGetLastError();
+}
+
+hipError_t launch_render_view(int n, int cascades, const DeviceBuffers &buf, const CameraParams &cam, const SurfaceScales &scales,
+                              const RaycastParams &rp, const ShadeParams &sp, uint32_t *bound_dev, uint32_t *rgba_dev, RenderPixel *pixels_dev,
+                              hipStream_t s) {
+    if (cam.width <= 0 || cam.height <= 0 || (!rgba_dev && !pixels_dev)) return hipSuccess;
+    if (hipError_t e = hipMemsetAsync(bound_dev, 0, (size_t)cascades * sizeof(uint32_t), s); e != hipSuccess) return e;
+    const int threads = 256;
+    const int pairs = n * n / 2, blocks = std::min((pairs + threads - 1) / threads, 256);
+    hipLaunchKernelGGL(k_height_bound, dim3(blocks, cascades), dim3(threads), 0, s, buf.disp, n, bound_dev);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    const int tiles_x = (cam.width + 7) / 8, tiles_y = (cam.height + 7) / 8;
+    if (pixels_dev)
+        hipLaunchKernelGGL(k_render_view<true>, dim3(tiles_x * tiles_y), dim3(64), 0, s, buf.disp, buf.norm, n, cascades, bound_dev, scales, rp, cam,
+                           sp, tiles_x, rgba_dev, pixels_dev);
+    else
+        hipLaunchKernelGGL(k_render_view<false>, dim3(tiles_x * tiles_y), dim3(64), 0, s, buf.disp, buf.norm, n, cascades, bound_dev, scales, rp, cam,
+                           sp, tiles_x, rgba_dev, pixels_dev);
     return hipGetLastError();
 }
 

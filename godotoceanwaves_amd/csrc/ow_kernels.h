@@ -5,6 +5,7 @@
 #include "ow_device.h"
 #include "ow_buoyancy.h"
 #include "ow_raycast.h"
+#include "ow_render.h"
 #include "ow_rigid.h"
 #include "ow_surface.h"
 #include "ow_velocity.h"
@@ -72,6 +73,11 @@ hipError_t launch_velocity(int n, const VelocityArgs &args, const DeviceBuffers 
 // fills it, then k_raycast_surface casts `count` rays, all on `s`
 hipError_t launch_raycast(int n, int cascades, const DeviceBuffers &buf, const Ray *rays_dev, int count, const SurfaceScales &scales,
                           const RaycastParams &rp, uint32_t *bound_dev, RaycastHit *out_dev, hipStream_t s);
+// a camera view (ow_consumer.hip; the pixel rays, the march, the record and the composite in ow_render.h, the shading in ow_shading.h):
+// bound_dev as for launch_raycast, then k_render_view writes cam.width x cam.height RGBA8 words and / or records (either may be null)
+hipError_t launch_render_view(int n, int cascades, const DeviceBuffers &buf, const CameraParams &cam, const SurfaceScales &scales,
+                              const RaycastParams &rp, const ShadeParams &sp, uint32_t *bound_dev, uint32_t *rgba_dev, RenderPixel *pixels_dev,
+                              hipStream_t s);
 
 bool supported_map_size(int n);
 int kernel_family(int n, int slots, int mode);  // 1 standard, 2 layer-parallel, 3 compact: what launch_pass1/2 will use

@@ -180,6 +180,10 @@ struct ow_context {
     ow::RaycastHit *ray_out = nullptr;
     int ray_capacity = 0;
     uint32_t *ray_bound = nullptr;
+    // ow_render_view scratch (grow-only): RGBA8 words and per-pixel records (the bound words are the ray cast's)
+    uint32_t *render_rgba = nullptr;
+    ow::RenderPixel *render_pixels = nullptr;
+    size_t render_rgba_capacity = 0, render_pixels_capacity = 0;
     // the velocity layers (ow_update_velocity; ow_velocity_kernels.h): V in the displacement array's layout, the pipeline's own intermediate
     // (vel_slots cascades of one launch pair) and twiddle table, all allocated by the first velocity call
     ow::u16x4 *vel = nullptr;
@@ -1208,6 +1212,8 @@ void ow_destroy(ow_context *c) {
     (void)hipFree(c->ray_in);
     (void)hipFree(c->ray_out);
     (void)hipFree(c->ray_bound);
+    (void)hipFree(c->render_rgba);
+    (void)hipFree(c->render_pixels);
     (void)hipFree(c->vel);
     (void)hipFree(c->vel_scratch);
     (void)hipFree(c->vel_tw);
@@ -2623,6 +2629,151 @@ ow_status ow_raycast_surface_async(ow_context *c, const ow_ray *rays_dev, int32_
     // main_stream(): behind the second chain's join as well as everything on the context's (or the caller's) stream
     OW_HIP(ow::launch_raycast(c->n, num_cascades, c->buf, (const ow::Ray *)rays_dev, count, sc, rp, c->ray_bound, (ow::RaycastHit *)out_dev,
                               main_stream(c)));
+    return OW_OK;
+}
+
+}  // extern "C"
+
+namespace {
+// the reference scene's material and sun (ow_render_options_default)
+void render_defaults(ow_render_options *o) {
+    std::memset(o, 0, sizeof(*o));
+    const float water[3] = {0.0100228256f, 0.019606648f, 0.0272117816f};  // Color(0.1, 0.15, 0.18).srgb_to_linear(), water.gd:14-15
+    const float foam[3] = {0.491905034f, 0.406448305f, 0.34239164f};      // Color(0.73, 0.67, 0.62).srgb_to_linear(), water.gd:17-18
+    const float sun[3] = {0.321197f, 0.18296f, 0.929171f};                // the basis' +Z column, main.tscn:113
+    const float ambient[3] = {0.05f, 0.08f, 0.10f}, sky[3] = {0.25f, 0.40f, 0.60f};
+    for (int k = 0; k < 3; ++k) {
+        o->water_color[k] = water[k];
+        o->foam_color[k] = foam[k];
+        o->light_direction[k] = sun[k];
+        o->light_color[k] = 1.0f;
+        o->ambient_color[k] = ambient[k];
+        o->sky_color[k] = sky[k];
+    }
+    o->roughness = 0.65f;       // mat_water.tres:8
+    o->normal_strength = 1.0f;  // mat_water.tres:9
+}
+
+// ow_camera -> the kernel's camera; OW_ERR_INVALID for a size out of range or reserved words.  Non-finite values pass: they make every ray invalid.
+ow_status resolve_camera(const ow_camera *cam, ow::CameraParams *cp) {
+    if (!cam) return fail(OW_ERR_INVALID, "null camera");
+    if (cam->width < 1 || cam->width > OW_RENDER_MAX_SIDE || cam->height < 1 || cam->height > OW_RENDER_MAX_SIDE)
+        return fail(OW_ERR_INVALID, "camera size %d x %d outside [1,%d]", cam->width, cam->height, OW_RENDER_MAX_SIDE);
+    for (uint32_t r : cam->reserved)
+        if (r != 0u) return fail(OW_ERR_INVALID, "ow_camera.reserved must be 0");
+    for (int k = 0; k < 3; ++k) cp->o[k] = cam->position[k];
+    for (int k = 0; k < 9; ++k) cp->B[k] = cam->basis[k];
+    cp->tan_half_fov = (float)std::tan((double)cam->fov_y_degrees * (3.14159265358979323846 / 360.0));
+    cp->aspect = (float)cam->width / (float)cam->height;
+    cp->max_distance = cam->max_distance;
+    cp->width = cam->width;
+    cp->height = cam->height;
+    return OW_OK;
+}
+
+// ow_render_options (NULL = the defaults) -> the hit's settings and the shading's; the uniform-only constants in FP64, narrowed once
+ow_status resolve_render_options(const ow_render_options *opts, ow::RaycastParams *rp, ow::ShadeParams *sp) {
+    ow_render_options def;
+    if (!opts) {
+        render_defaults(&def);
+        opts = &def;
+    }
+    if (ow_status st = ow::resolve_raycast_options(&opts->raycast, rp); st != OW_OK) return st;
+    const float *vec[6] = {opts->water_color, opts->foam_color, opts->light_direction, opts->light_color, opts->ambient_color, opts->sky_color};
+    for (const float *v : vec)
+        for (int k = 0; k < 3; ++k)
+            if (!std::isfinite(v[k])) return fail(OW_ERR_INVALID, "ow_render_options: a colour or the light direction is not finite");
+    if (!(opts->roughness >= 0.0f && opts->roughness <= 1.0f)) return fail(OW_ERR_INVALID, "roughness outside [0,1]");
+    if (!(opts->normal_strength >= 0.0f && opts->normal_strength <= 1.0f)) return fail(OW_ERR_INVALID, "normal_strength outside [0,1]");
+    if (opts->flags != 0u) return fail(OW_ERR_INVALID, "unknown render flags 0x%x", opts->flags);
+    for (uint32_t r : opts->reserved)
+        if (r != 0u) return fail(OW_ERR_INVALID, "ow_render_options.reserved must be 0");
+    const double lx = opts->light_direction[0], ly = opts->light_direction[1], lz = opts->light_direction[2];
+    const double len = std::sqrt(lx * lx + ly * ly + lz * lz);
+    if (!(len > 0.0)) return fail(OW_ERR_INVALID, "light_direction has zero length");
+    const double r = opts->roughness;
+    for (int k = 0; k < 3; ++k) {
+        sp->water_color[k] = opts->water_color[k];
+        sp->foam_color[k] = opts->foam_color[k];
+        sp->light[k] = (float)((double)opts->light_direction[k] / len);
+        sp->light_color[k] = opts->light_color[k];
+        sp->ambient_color[k] = opts->ambient_color[k];
+        sp->sky_color[k] = opts->sky_color[k];
+    }
+    sp->roughness = opts->roughness;
+    sp->normal_strength = opts->normal_strength;
+    sp->fresnel_power = (float)(5.0 * std::exp(-2.69 * r));            // water.gdshader:92
+    sp->fresnel_divisor = (float)(1.0 + 22.7 * std::pow(r, 1.5));      // water.gdshader:92
+    return OW_OK;
+}
+
+// the argument checks both forms of ow_render_view share, in this order: pointers, camera, options, context
+ow_status check_render(const ow_context *c, const ow_camera *camera, const float *map_scales, int32_t num_cascades, const ow_render_options *opts,
+                       const void *rgba, const void *pixels, ow::CameraParams *cp, ow::RaycastParams *rp, ow::ShadeParams *sp) {
+    static_assert(sizeof(ow_render_pixel) == sizeof(ow::RenderPixel) && offsetof(ow_render_pixel, dist) == offsetof(ow::RenderPixel, dist) &&
+                      offsetof(ow_render_pixel, normal) == offsetof(ow::RenderPixel, normal) &&
+                      offsetof(ow_render_pixel, color) == offsetof(ow::RenderPixel, color) && OW_RENDER_MAX_SIDE == ow::kRenderMaxSide,
+                  "record layout");
+    if (!rgba && !pixels) return fail(OW_ERR_INVALID, "null argument: both outputs");
+    if (!map_scales) return fail(OW_ERR_INVALID, "null argument");
+    if (ow_status st = resolve_camera(camera, cp); st != OW_OK) return st;
+    if (ow_status st = resolve_render_options(opts, rp, sp); st != OW_OK) return st;
+    return check_point_query(c, 0, num_cascades);
+}
+}  // namespace
+
+extern "C" {
+
+void ow_render_options_default(ow_render_options *out) {
+    if (out) render_defaults(out);
+}
+
+ow_status ow_render_view(ow_context *c, const ow_camera *camera, const float *map_scales, int32_t num_cascades, const ow_render_options *opts,
+                         void *rgba8_out, ow_render_pixel *pixels_out) {
+    ow::CameraParams cp;
+    ow::RaycastParams rp;
+    ow::ShadeParams sp;
+    if (ow_status st = check_render(c, camera, map_scales, num_cascades, opts, rgba8_out, pixels_out, &cp, &rp, &sp); st != OW_OK) return st;
+    OW_HIP(hipSetDevice(c->device));
+    if (ow_status st = ow::raycast_scratch(0, &c->ray_in, &c->ray_out, &c->ray_capacity, &c->ray_bound); st != OW_OK) return st;
+    const size_t count = (size_t)cp.width * cp.height;
+    if (rgba8_out && count > c->render_rgba_capacity) {
+        (void)hipFree(c->render_rgba);
+        c->render_rgba = nullptr;
+        c->render_rgba_capacity = 0;
+        if (hipMalloc((void **)&c->render_rgba, count * sizeof(uint32_t)) != hipSuccess) return fail(OW_ERR_NOMEM, "hipMalloc failed for %zu pixels", count);
+        c->render_rgba_capacity = count;
+    }
+    if (pixels_out && count > c->render_pixels_capacity) {
+        (void)hipFree(c->render_pixels);
+        c->render_pixels = nullptr;
+        c->render_pixels_capacity = 0;
+        if (hipMalloc((void **)&c->render_pixels, count * sizeof(ow::RenderPixel)) != hipSuccess)
+            return fail(OW_ERR_NOMEM, "hipMalloc failed for %zu pixel records", count);
+        c->render_pixels_capacity = count;
+    }
+    const ow::SurfaceScales sc = surface_scales(map_scales, num_cascades);
+    OW_HIP(ow::launch_render_view(c->n, num_cascades, c->buf, cp, sc, rp, sp, c->ray_bound, rgba8_out ? c->render_rgba : nullptr,
+                                  pixels_out ? c->render_pixels : nullptr, main_stream(c)));
+    if (rgba8_out) OW_HIP(hipMemcpyAsync(rgba8_out, c->render_rgba, count * sizeof(uint32_t), hipMemcpyDeviceToHost, main_stream(c)));
+    if (pixels_out) OW_HIP(hipMemcpyAsync(pixels_out, c->render_pixels, count * sizeof(ow::RenderPixel), hipMemcpyDeviceToHost, main_stream(c)));
+    return sync_stream(c, (1u << num_cascades) - 1u);
+}
+
+ow_status ow_render_view_async(ow_context *c, const ow_camera *camera, const float *map_scales, int32_t num_cascades, const ow_render_options *opts,
+                               void *rgba8_dev, ow_render_pixel *pixels_dev) {
+    ow::CameraParams cp;
+    ow::RaycastParams rp;
+    ow::ShadeParams sp;
+    if (ow_status st = check_render(c, camera, map_scales, num_cascades, opts, rgba8_dev, pixels_dev, &cp, &rp, &sp); st != OW_OK) return st;
+    if (((uintptr_t)rgba8_dev & 3u) || ((uintptr_t)pixels_dev & 15u)) return fail(OW_ERR_INVALID, "rgba8_dev must be 4-byte and pixels_dev 16-byte aligned");
+    if (ow_status st = refuse_faulted(c, (1u << num_cascades) - 1u); st != OW_OK) return st;
+    OW_HIP(hipSetDevice(c->device));
+    if (ow_status st = ow::raycast_scratch(0, &c->ray_in, &c->ray_out, &c->ray_capacity, &c->ray_bound); st != OW_OK) return st;
+    const ow::SurfaceScales sc = surface_scales(map_scales, num_cascades);
+    // main_stream(): behind the second chain's join as well as everything on the context's (or the caller's) stream
+    OW_HIP(ow::launch_render_view(c->n, num_cascades, c->buf, cp, sc, rp, sp, c->ray_bound, (uint32_t *)rgba8_dev, (ow::RenderPixel *)pixels_dev,
+                                  main_stream(c)));
     return OW_OK;
 }
 

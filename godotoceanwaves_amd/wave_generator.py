@@ -610,6 +610,74 @@ class WaveGenerator:
         _lib.check(self._lib.ow_query_velocity_async(self.context, addr(xz_device), int(count), sc.ctypes.data, len(sc),
                                                      C.byref(o) if o is not None else None, addr(out_device)))
 
+    # ---- camera views of the water, on the device (include/ocean_waves.h ow_render_view) ----
+    RENDER_PIXEL = np.dtype([("t", np.float32), ("status", np.int32), ("position", np.float32, 3), ("p", np.float32, 2), ("wave_height", np.float32),
+                             ("gradient_fragment", np.float32, 2), ("foam_fragment", np.float32), ("dist", np.float32), ("foam_factor", np.float32),
+                             ("albedo", np.float32, 3), ("normal", np.float32, 3), ("fresnel", np.float32), ("roughness", np.float32),
+                             ("diffuse", np.float32, 3), ("specular", np.float32), ("color", np.float32, 3), ("reserved", np.uint32, 4)])
+    _RENDER_OWN = ("water_color", "foam_color", "roughness", "normal_strength", "light_direction", "light_color", "ambient_color", "sky_color")
+
+    @staticmethod
+    def camera(position, basis, fov_y_degrees, width, height, max_distance):
+        """an _lib.ow_camera from a position, Godot Transform3D basis rows (9 values or 3 x 3; the camera looks down its -Z, +Y is up),
+        the vertical field of view in degrees, the image size and the length of each pixel's ray"""
+        cam = _lib.ow_camera(max_distance=float(max_distance), fov_y_degrees=float(fov_y_degrees), width=int(width), height=int(height))
+        cam.position[:] = [float(v) for v in position]
+        cam.basis[:] = [float(v) for v in np.asarray(basis, np.float64).reshape(9)]
+        return cam
+
+    @classmethod
+    def render_options(cls, options=None, camera=None):
+        """None, an _lib.ow_render_options, or a dict -> ow_render_options, or None for the defaults.  The dict starts from
+        ow_render_options_default's values and may set water_color / foam_color / roughness / normal_strength / light_direction /
+        light_color / ambient_color / sky_color and the raycast_options keys.  "falloff": True turns the shader's distance falloff on
+        around the camera's x and z (falloff_center names another centre)."""
+        if options is None or isinstance(options, _lib.ow_render_options):
+            return options
+        o = _lib.ow_render_options()
+        _lib.load().ow_render_options_default(C.byref(o))
+        ray = {k: v for k, v in options.items() if k not in cls._RENDER_OWN and k != "falloff"}
+        if options.get("falloff") and ray.get("falloff_center") is None:
+            if camera is None:
+                raise ValueError("falloff without a falloff_center needs the camera")
+            ray["falloff_center"] = (camera.position[0], camera.position[2])
+        if ray:
+            o.raycast = cls.raycast_options(ray)
+        for k in cls._RENDER_OWN:
+            if k in options:
+                if k in ("roughness", "normal_strength"):
+                    setattr(o, k, float(options[k]))
+                else:
+                    getattr(o, k)[:] = [float(v) for v in options[k]]
+        return o
+
+    def render_view(self, camera, map_scales, options=None, pixels=True):
+        """The view of an ow_camera (WaveGenerator.camera): ((H, W, 4) uint8 RGBA, (H, W) structured RENDER_PIXEL records, or None with
+        pixels=False), rows from the top."""
+        sc = np.ascontiguousarray(map_scales, np.float32).reshape(-1, 4)
+        o = self.render_options(options, camera)
+        h, w = max(int(camera.height), 0), max(int(camera.width), 0)
+        big = h > _lib.OW_RENDER_MAX_SIDE or w > _lib.OW_RENDER_MAX_SIDE   # refused by the library: do not allocate for it
+        rgba = np.zeros((1, 1, 4) if big else (h, w, 4), np.uint8)
+        rec = np.zeros((1, 1) if big else (h, w), self.RENDER_PIXEL) if pixels else None
+        _lib.check(self._lib.ow_render_view(self.context, C.byref(camera), sc.ctypes.data, len(sc), C.byref(o) if o is not None else None,
+                                            rgba.ctypes.data, rec.ctypes.data if pixels else None))
+        return rgba, rec
+
+    def render_view_async(self, camera, map_scales, rgba_device, pixels_device=None, options=None):
+        """The view over DEVICE buffers, enqueued in the generator's stream order without synchronising: rgba_device holds H * W * 4 bytes,
+        pixels_device H * W 128-byte records; each is anything with a data_ptr() (a torch tensor), an integer address, or None (not both)."""
+        def addr(b):
+            return None if b is None else (int(b.data_ptr()) if hasattr(b, "data_ptr") else int(b))
+        count = int(camera.width) * int(camera.height)
+        for buf, size in ((rgba_device, 4), (pixels_device, self.RENDER_PIXEL.itemsize)):
+            if hasattr(buf, "numel") and hasattr(buf, "element_size") and buf.numel() * buf.element_size() < count * size:
+                raise ValueError(f"a device buffer holds fewer than {count} pixels of {size} bytes")
+        sc = np.ascontiguousarray(map_scales, np.float32).reshape(-1, 4)
+        o = self.render_options(options, camera)
+        _lib.check(self._lib.ow_render_view_async(self.context, C.byref(camera), sc.ctypes.data, len(sc), C.byref(o) if o is not None else None,
+                                                  addr(rgba_device), addr(pixels_device)))
+
     def get_push_constants(self, cascade):
         """(spectrum[16], modulate[8], unpack[4]) uint32 words: the reference's push-constant blocks of this cascade's most recent launch"""
         pc = _lib.ow_push_constants()

@@ -654,6 +654,105 @@ ow_status ow_raycast_surface(ow_context *ctx, const ow_ray *rays, int32_t count,
 ow_status ow_raycast_surface_async(ow_context *ctx, const ow_ray *rays_dev, int32_t count, const float *map_scales, int32_t num_cascades,
                                    const ow_raycast_options *opts, ow_raycast_hit *out_dev);
 
+/* Camera views of the water: per pixel of a width x height image, the ray through the pixel centre, the hit ow_raycast_surface defines for
+ * that ray, the rest of assets/shaders/spatial/water.gdshader at the hit -- fragment() lines 73-93 (foam factor, ALBEDO, the
+ * distance-blended NORMAL, fresnel, ROUGHNESS) and light() lines 96-127 for one directional light with ATTENUATION 1 -- and a composite.
+ * Pixel (i, j), i from the left, j from the top, looks along basis * ((2 (i + 0.5) / width - 1) * aspect * tan(fov_y / 2),
+ * (1 - 2 (j + 0.5) / height) * tan(fov_y / 2), -1), aspect = width / height, from the camera's position; t, position, status and the
+ * query of a pixel are the bits ow_raycast_surface returns for that ray with options.raycast (its samples / rounds counters are not part
+ * of a pixel).  The shader's distance falloff is the query's own flag and centre (options.raycast.query): rendering as the reference does
+ * means OW_QUERY_DISTANCE_FALLOFF with the centre at the camera's x and z.  The composite is this library's choice -- Godot's is engine
+ * code outside the reference: color = ALBEDO * (DIFFUSE_LIGHT + ambient_color) + SPECULAR_LIGHT in linear FP32 for a hit (from below
+ * alike); sky_color for a pixel without one (a miss, OW_RAY_TRUNCATED, OW_RAY_INVALID).  No sky model, fog, tonemapping or
+ * anti-aliasing.  RGBA8 is (int)(clamp(c, 0, 1) * 255 + 0.5) per channel, bytes R, G, B, A = 255, rows top to bottom, no transfer
+ * curve.  NORMAL is in world space.  The exact operations, identical in every build, are godotoceanwaves_amd/csrc/ow_render.h's and
+ * ow_shading.h's.  Nothing returned is NaN or Inf.  There is no group form (ow_group_*) of these calls: render on the context that holds
+ * the maps (ow_group_context of the root after a gather). */
+#define OW_RENDER_MAX_SIDE 8192 /* the largest width or height */
+typedef struct ow_camera {
+    float position[3];          /* world metres */
+    float max_distance;         /* metres along each pixel's ray, > 0 */
+    float basis[9];             /* Godot's Transform3D basis rows (world = B * local): the camera looks down its -Z, +Y is up */
+    float fov_y_degrees;        /* vertical field of view, as Camera3D.fov */
+    int32_t width;              /* 1 .. OW_RENDER_MAX_SIDE */
+    int32_t height;             /* 1 .. OW_RENDER_MAX_SIDE */
+    uint32_t reserved[4];       /* 0 */
+} ow_camera;                    /* 80 bytes */
+typedef struct ow_render_options {
+    ow_raycast_options raycast; /* the hit (zeros = its defaults) and, in raycast.query, the distance falloff */
+    float water_color[3];       /* linear (water.gd:14-15 converts its sRGB colour) */
+    float roughness;            /* water.gdshader:14, 0 .. 1 */
+    float foam_color[3];        /* linear (water.gd:17-18) */
+    float normal_strength;      /* water.gdshader:15, 0 .. 1 */
+    float light_direction[3];   /* towards the light, world space, any non-zero length (a DirectionalLight3D's +Z axis) */
+    uint32_t flags;             /* 0 */
+    float light_color[3];       /* LIGHT_COLOR: colour times energy, linear */
+    float ambient_color[3];     /* linear */
+    float sky_color[3];         /* linear */
+    uint32_t reserved[11];      /* 0 */
+} ow_render_options;            /* 192 bytes; a NULL pointer = ow_render_options_default's values; a given record is taken field by field */
+/* One record per pixel, 128 bytes, row-major from the top-left pixel.  Without a hit: status, sky_color in color, zeros elsewhere.
+ *   offset   0  t                     metres along the pixel's normalised ray
+ *            4  status                OW_RAY_* bits
+ *            8  position[3]           the hit
+ *           20  p[2]                  the undisplaced point drawn there (ow_surface_query.p): the shader's UV
+ *           28  wave_height           the vertex stage's displacement.y at p, before the distance factor (water.gdshader:38)
+ *           32  gradient_fragment[2]  fragment()'s gradient.xy at p before the distance blend (ow_surface_sample.gradient_fragment)
+ *           40  foam_fragment         fragment()'s gradient.z at p (ow_surface_sample.foam_fragment)
+ *           44  dist                  length(VERTEX.xz) in view space (:74)
+ *           48  foam_factor           (:86)
+ *           52  albedo[3]             ALBEDO (:87)
+ *           64  normal[3]             NORMAL (:90), world space
+ *           76  fresnel               (:92)
+ *           80  roughness             ROUGHNESS (:93)
+ *           84  diffuse[3]            DIFFUSE_LIGHT (:126)
+ *           96  specular              SPECULAR_LIGHT (:119), the same in every channel
+ *          100  color[3]              the composite, linear, before the clamp
+ *          112  reserved[4] */
+typedef struct ow_render_pixel {
+    float t;
+    int32_t status;
+    float position[3];
+    float p[2];
+    float wave_height;
+    float gradient_fragment[2];
+    float foam_fragment;
+    float dist;
+    float foam_factor;
+    float albedo[3];
+    float normal[3];
+    float fresnel;
+    float roughness;
+    float diffuse[3];
+    float specular;
+    float color[3];
+    uint32_t reserved[4];
+} ow_render_pixel;
+typedef char ow_layout_check_camera[(sizeof(ow_camera) == 80 && offsetof(ow_camera, basis) == 16 && offsetof(ow_camera, width) == 56) ? 1 : -1];
+typedef char ow_layout_check_render_options[(sizeof(ow_render_options) == 192 && offsetof(ow_render_options, water_color) == 64 &&
+                                             offsetof(ow_render_options, flags) == 108 && offsetof(ow_render_options, sky_color) == 136) ? 1 : -1];
+typedef char ow_layout_check_render_pixel[(sizeof(ow_render_pixel) == 128 && offsetof(ow_render_pixel, dist) == 44 &&
+                                           offsetof(ow_render_pixel, normal) == 64 && offsetof(ow_render_pixel, color) == 100) ? 1 : -1];
+
+/* The reference scene's material and sun, and this library's ambient and sky: water_color and foam_color of water.gd:14-18 in linear,
+ * roughness 0.65 and normal_strength 1 (mat_water.tres:8-9), the +Z axis of main.tscn:113's sun, a white light of energy 1, ambient
+ * (0.05, 0.08, 0.10), sky (0.25, 0.40, 0.60); raycast all zeros (its defaults, no falloff). */
+void ow_render_options_default(ow_render_options *out);
+/* Renders camera's view after everything enqueued so far.  rgba8_out: width * height * 4 bytes; pixels_out: width * height records; host
+ * pointers, either may be NULL, not both.  Synchronises.  A bad argument -- width or height outside 1 .. OW_RENDER_MAX_SIDE, an option that
+ * is not finite, roughness or normal_strength outside [0, 1], a light direction of zero length, flags or reserved words not 0 (the
+ * camera's included), what ow_raycast_surface refuses -- is OW_ERR_INVALID and nothing is written.  A camera whose position, basis,
+ * field of view or max_distance is not finite (or whose max_distance is not positive) is not an error: every pixel is sky_color with
+ * OW_RAY_INVALID.  Faulted layers are refused as by ow_query_surface. */
+ow_status ow_render_view(ow_context *ctx, const ow_camera *camera, const float *map_scales, int32_t num_cascades,
+                         const ow_render_options *opts, void *rgba8_out, ow_render_pixel *pixels_out);
+/* The same with DEVICE pointers on the context's device (rgba8_dev 4-byte aligned, pixels_dev 16-byte aligned; camera, map_scales and
+ * opts are host values), enqueued in the context's stream order behind everything enqueued so far -- both chains -- and ahead of whatever
+ * the context enqueues next, as ow_query_surface_async (a caller's stream included).  Copies nothing and does not synchronise; the first
+ * call allocates the context's few words of bound scratch. */
+ow_status ow_render_view_async(ow_context *ctx, const ow_camera *camera, const float *map_scales, int32_t num_cascades,
+                               const ow_render_options *opts, void *rgba8_dev, ow_render_pixel *pixels_dev);
+
 /* ---- several devices: cascades sharded inside one process ---------------------------------------- */
 
 /* Cascades share nothing (wave_generator.gd:65-85 touches no state of another cascade; README.md:77-80), so a node's GPUs

@@ -1,0 +1,686 @@
+"""Camera views of the water (include/ocean_waves.h ow_render_view, ow_render_view_async): per pixel the ray through its centre, the ray
+cast's hit, water.gdshader's fragment() and light() at the hit and a composite (godotoceanwaves_amd/csrc/ow_render.h, ow_shading.h).
+
+CPU: the ABI (header, exports, ctypes, NumPy, C, the harness and C# layouts) and the argument checks without a device; the two headers
+compiled as plain C++ (tests/render/render_harness.cpp, g++ -ffp-contract=off) held to the analytic picture of a calm sea, to an FP64
+twin of the pixel rays, to the FP64 library's log, to the ray cast's records bit for bit, to an FP64 twin of the shading
+(tests/render_twin.py, written from the shader text) and to finite records on awkward inputs; the C example compiles.  GPU: the device
+records and RGBA8 words (one lane per pixel) are the CPU build's bit for bit, the asynchronous form is ordered like
+ow_raycast_surface_async, and examples/render_host.c writes the picture the Python wrapper returns."""
+import ctypes as C
+import math
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import helpers as H
+import render_twin as RT
+from godotoceanwaves_amd import _lib, build
+from godotoceanwaves_amd.presets import UPDATE_DELTA
+from godotoceanwaves_amd.wave_generator import WaveGenerator as W
+from test_raycast import SPACING, TOL, calm_maps, cpu_raycast, harness as ray_harness, swell_maps  # noqa: F401
+from test_surface_query import generated_maps, gpu_maps, make_gen, maps_u16, scales_of
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "godotoceanwaves_amd", "csrc")
+PKG = os.path.join(ROOT, "godotoceanwaves_amd")
+HERE = os.path.dirname(os.path.abspath(__file__))
+NEW_FUNCTIONS = ("ow_render_options_default", "ow_render_view", "ow_render_view_async")
+STRUCTS = {"OwCamera": "ow_camera", "OwRenderOptions": "ow_render_options", "OwRenderPixel": "ow_render_pixel"}
+HIT, BELOW, TRUNC, INVALID = _lib.OW_RAY_HIT, _lib.OW_RAY_FROM_BELOW, _lib.OW_RAY_TRUNCATED, _lib.OW_RAY_INVALID
+SHADE_KEYS = ("water_color", "foam_color", "roughness", "normal_strength", "light_direction", "light_color", "ambient_color", "sky_color")
+# ow_render_options_default's values (the reference scene's material and sun; ambient and sky are the library's)
+DEFAULTS = dict(water_color=(0.0100228256, 0.019606648, 0.0272117816), foam_color=(0.491905034, 0.406448305, 0.34239164), roughness=0.65,
+                normal_strength=1.0, light_direction=(0.321197, 0.18296, 0.929171), light_color=(1.0, 1.0, 1.0),
+                ambient_color=(0.05, 0.08, 0.10), sky_color=(0.25, 0.40, 0.60))
+SUN_LOW = (0.321197, 0.18296, 0.929171)      # main.tscn:113: 10.5 degrees above the horizon, ahead of a camera that looks towards +z
+SUN_BEHIND = (0.2, 0.5, -0.84)               # behind that camera
+
+
+# ---- the CPU build of ow_render.h / ow_shading.h -------------------------------------------------------------------------------------
+
+@pytest.fixture(scope="module")
+def harness(tmp_path_factory):
+    so = str(tmp_path_factory.mktemp("render") / "librender_harness.so")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unknown-pragmas", "-I", CSRC,
+                    os.path.join(HERE, "render", "render_harness.cpp"), "-o", so], check=True)
+    L = C.CDLL(so)
+    V = C.c_void_p
+    L.harness_render_sizes.argtypes = [V]
+    L.harness_log.argtypes = [V, C.c_int, V]
+    L.harness_pixel_rays.argtypes = [V, C.c_int, C.c_int, V]
+    L.harness_render.argtypes = [V, V, C.c_int, C.c_int, V, V, C.c_int, C.c_int, V, C.c_int, C.c_float, C.c_int, C.c_float, C.c_float, C.c_float,
+                                 C.c_float, C.c_float, C.c_int, V, V]
+    return L
+
+
+def look(position, yaw_deg, pitch_deg, fov=75.0, width=20, height=12, max_distance=4000.0):
+    """an ow_camera at `position` looking along yaw (0 = +z, towards +x as it grows) and pitch (degrees, negative = down), +Y up: the
+    basis columns are right, up and back, written as Godot's rows"""
+    yaw, pitch = math.radians(yaw_deg), math.radians(pitch_deg)
+    f = np.array([math.sin(yaw) * math.cos(pitch), math.sin(pitch), math.cos(yaw) * math.cos(pitch)])
+    right = np.cross(f, [0.0, 1.0, 0.0])
+    right /= np.linalg.norm(right)
+    up = np.cross(right, f)
+    return W.camera(position, np.stack([right, up, -f], axis=1), fov, width, height, max_distance)
+
+
+def camera_words(cam):
+    """the 15 floats the runtime resolves from an ow_camera: position, basis, tan(fov / 2) in FP64 narrowed, aspect, max_distance"""
+    th = np.float32(math.tan(float(cam.fov_y_degrees) * (3.14159265358979323846 / 360.0)))
+    aspect = np.float32(cam.width) / np.float32(cam.height)
+    return np.array(list(cam.position) + list(cam.basis) + [th, aspect, cam.max_distance], np.float32)
+
+
+def shade_words(options):
+    """the 22 floats of ow::ShadeParams as the runtime resolves them from ow_render_options (the uniform-only constants in FP64)"""
+    o = dict(DEFAULTS, **{k: v for k, v in (options or {}).items() if k in SHADE_KEYS})
+    f32 = lambda v: [float(np.float32(x)) for x in v]   # noqa: E731
+    r = float(np.float32(o["roughness"]))
+    lx, ly, lz = f32(o["light_direction"])
+    ln = math.sqrt(lx * lx + ly * ly + lz * lz)
+    words = f32(o["water_color"]) + f32(o["foam_color"]) + [r, o["normal_strength"], 5.0 * math.exp(-2.69 * r), 1.0 + 22.7 * math.pow(r, 1.5)]
+    words += [lx / ln, ly / ln, lz / ln] + f32(o["light_color"]) + f32(o["ambient_color"]) + f32(o["sky_color"])
+    return np.array(words, np.float32)
+
+
+def uniforms_of(options):
+    """what the twin is given: the FP32 values of the options"""
+    o = dict(DEFAULTS, **{k: v for k, v in (options or {}).items() if k in SHADE_KEYS})
+    return {k: (np.float32(v).astype(np.float64) if np.ndim(v) == 0 else np.asarray(v, np.float32).astype(np.float64)) for k, v in o.items()}
+
+
+def ray_options(options, cam):
+    """the ray cast's share of render options, as W.render_options splits them ("falloff": True = around the camera)"""
+    o = {k: v for k, v in (options or {}).items() if k not in SHADE_KEYS and k != "falloff"}
+    if (options or {}).get("falloff") and o.get("falloff_center") is None:
+        o["falloff_center"] = (cam.position[0], cam.position[2])
+    return o
+
+
+def cpu_render(L, disp, norm, scales, cam, options=None):
+    """(rgba [H][W][4], records [H][W]) of the CPU build, the options resolved as the runtime resolves them"""
+    o = ray_options(options, cam)
+    d, m = maps_u16(disp), maps_u16(norm)
+    sc = np.ascontiguousarray(scales, np.float32)
+    cw, sw = camera_words(cam), shade_words(options)
+    rgba = np.zeros((cam.height, cam.width, 4), np.uint8)
+    rec = np.zeros((cam.height, cam.width), W.RENDER_PIXEL)
+    center = o.get("falloff_center")
+    cx, cz = center if center is not None else (0.0, 0.0)
+    L.harness_render(d.ctypes.data, m.ctypes.data, d.shape[1], len(sc), sc.ctypes.data, cw.ctypes.data, cam.width, cam.height, sw.ctypes.data,
+                     o.get("max_iterations", 0) or 16, o.get("query_tolerance", 0.0) or 1e-3, int(center is not None), cx, cz,
+                     o.get("water_level", 0.0), o.get("sample_spacing", 0.0) or SPACING, o.get("tolerance", 0.0) or TOL,
+                     o.get("max_samples", 0) or 4096, rgba.ctypes.data, rec.ctypes.data)
+    return rgba, rec
+
+
+def pixel_rays(L, cam):
+    cw = camera_words(cam)
+    rays = np.zeros(cam.width * cam.height, W.RAY)
+    L.harness_pixel_rays(cw.ctypes.data, cam.width, cam.height, rays.ctypes.data)
+    return rays
+
+
+def check_composite(rgba, rec, options=None):
+    """what every image holds: finite records, sky without a hit, the composite and the RGBA8 rule"""
+    for f in W.RENDER_PIXEL.names:
+        if f not in ("status", "reserved"):
+            assert np.isfinite(rec[f]).all(), f
+    hit = (rec["status"] & HIT) != 0
+    sky = np.asarray(dict(DEFAULTS, **(options or {}))["sky_color"], np.float32)
+    amb = np.asarray(dict(DEFAULTS, **(options or {}))["ambient_color"], np.float32)
+    assert (rec["color"][~hit] == sky).all()
+    zeroed = rec[~hit].copy()
+    zeroed["status"] = 0
+    zeroed["color"] = 0
+    assert not zeroed.tobytes().strip(b"\0")
+    want = rec["albedo"] * (rec["diffuse"] + amb) + rec["specular"][..., None]
+    assert np.array_equal(rec["color"][hit], want[hit])
+    assert np.array_equal(rgba, RT.rgba8(rec["color"]))
+    assert not rec["reserved"].any()
+    return hit
+
+
+# ---- 1. the ABI ----------------------------------------------------------------------------------------------------------------------
+
+HEADER = open(os.path.join(ROOT, "include", "ocean_waves.h")).read()
+
+
+def test_header_declares_the_render_calls_and_the_library_exports_them():
+    build.build_library()
+    lib = _lib.load()
+    text = re.sub(r"/\*.*?\*/", "", HEADER, flags=re.S)
+    for name in NEW_FUNCTIONS:
+        assert re.search(r"\b%s\s*\(" % name, text), name
+        assert name in _lib.SIGNATURES
+        assert getattr(lib, name)
+    for struct in STRUCTS.values():
+        assert re.search(r"typedef struct %s \{" % struct, text), struct
+    assert re.search(r"#define OW_RENDER_MAX_SIDE %d\b" % _lib.OW_RENDER_MAX_SIDE, HEADER)
+    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    exported = set(re.findall(r" T (ow_[a-z0-9_]+)", out))
+    assert set(NEW_FUNCTIONS) <= exported
+    assert sorted(s for s in exported if "render" in s) == sorted(NEW_FUNCTIONS)      # no group form
+    assert "no group form" in HEADER.split("ow_render_options_default")[0].split("Camera views of the water")[1]
+    assert lib.ow_abi_version() == 4
+    o = _lib.ow_render_options()
+    lib.ow_render_options_default(C.byref(o))
+    for k, v in DEFAULTS.items():
+        got = getattr(o, k)
+        assert np.array_equal(np.float32(v), np.float32(got if np.ndim(v) == 0 else list(got))), k
+    assert o.flags == 0 and not any(o.reserved) and not bytes(o.raycast).strip(b"\0")
+
+
+def test_render_structs_agree_in_c_ctypes_numpy_and_the_harness(tmp_path, harness):
+    fields = [("ow_camera", f) for f in ("position", "max_distance", "basis", "fov_y_degrees", "width", "height", "reserved")]
+    fields += [("ow_render_options", f) for f in ("raycast", "water_color", "roughness", "foam_color", "normal_strength", "light_direction", "flags",
+                                                  "light_color", "ambient_color", "sky_color", "reserved")]
+    fields += [("ow_render_pixel", f) for f in W.RENDER_PIXEL.names]
+    names = ("ow_camera", "ow_render_options", "ow_render_pixel")
+    expr = ", ".join(["sizeof(%s)" % s for s in names] + ["offsetof(%s, %s)" % f for f in fields])
+    src = ('#include <stdio.h>\n#include <stddef.h>\n#include "ocean_waves.h"\nint main(void){printf("%s\\n", ' % " ".join(["%zu"] * (3 + len(fields)))
+           + expr + ");return 0;}\n")
+    exe = str(tmp_path / "render_layout")
+    subprocess.run(["gcc", "-std=c11", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-x", "c", "-", "-o", exe], input=src, text=True, check=True)
+    got = [int(v) for v in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split()]
+    ctypes_of = {"ow_camera": _lib.ow_camera, "ow_render_options": _lib.ow_render_options, "ow_render_pixel": _lib.ow_render_pixel}
+    want = [C.sizeof(ctypes_of[s]) for s in names] + [getattr(ctypes_of[s], f).offset for s, f in fields]
+    assert got == want
+    assert got[:3] == [80, 192, 128] and 128 & 127 == 0
+    px = dict((f, o) for (s, f), o in zip(fields, got[3:]) if s == "ow_render_pixel")
+    assert [W.RENDER_PIXEL.fields[f][1] for f in W.RENDER_PIXEL.names] == [px[f] for f in W.RENDER_PIXEL.names] and W.RENDER_PIXEL.itemsize == 128
+    sizes = (C.c_int * 8)()
+    harness.harness_render_sizes(sizes)
+    assert list(sizes) == [128, px["status"], px["p"], px["dist"], px["normal"], px["color"], 22 * 4, 17 * 4]
+
+
+def test_the_csharp_binding_shows_the_render_structs_and_functions():
+    """the three new [StructLayout] structs list the C fields in order with the same sizes (an embedded record counted
+    as its bytes), the calls are bound, and §7 names them"""
+    import test_integration_shim as S
+    c_sizes = dict(S.C_SIZES, ow_raycast_options=64)
+    cs_sizes = dict(S.CS_SIZES, OwRaycastOptions=64)
+
+    def fields(body, sizes, strip):
+        out = []
+        for decl in body.split(";"):
+            decl = " ".join(strip(decl).split())
+            if not decl:
+                continue
+            decl = decl[len("fixed "):] if decl.startswith("fixed ") else decl
+            typ, names = decl.split(" ", 1)
+            for n in names.split(","):
+                m = re.match(r"\s*([A-Za-z_]\w*)(\[(\d+)\])?\s*$", n)
+                out.append((m.group(1), sizes[typ] * int(m.group(3) or 1)))
+        return out
+
+    for cs, c in STRUCTS.items():
+        cbody = re.search(r"typedef struct %s \{(.*?)\}\s*%s\s*;" % (c, c), S.strip_comments(S.HEADER), flags=re.S).group(1)
+        csbody = re.search(r"struct %s \{(.*?)\n\}" % cs, S.strip_comments(S.SHIM), flags=re.S).group(1)
+        want = fields(cbody, c_sizes, lambda d: d)
+        got = fields(csbody, cs_sizes, lambda d: d.replace("public", ""))
+        assert got == want, (cs, got, want)
+        assert sum(s for _, s in want) == {"ow_camera": 80, "ow_render_options": 192, "ow_render_pixel": 128}[c]
+    for name in NEW_FUNCTIONS:
+        assert re.search(r"\[DllImport\(Lib\)\]\s*public static extern \w+ %s\(" % name, S.SHIM), name
+        assert "`%s`" % name in S.DOC.split("## 7. Index")[1], name
+
+
+# ---- 2. argument checks without a device ---------------------------------------------------------------------------------------------
+
+def test_render_argument_errors_without_a_device():
+    lib = _lib.load()
+    sc = np.ones((1, 4), np.float32)
+    rgba = np.zeros((12, 20, 4), np.uint8)
+    rec = np.zeros((12, 20), W.RENDER_PIXEL)
+
+    def both(cam, opts, rgba_p=rgba.ctypes.data, rec_p=rec.ctypes.data, scales=sc.ctypes.data):
+        out = []
+        for fn in (lib.ow_render_view, lib.ow_render_view_async):
+            assert fn(None, C.byref(cam) if cam is not None else None, scales, 1, C.byref(opts) if opts is not None else None, rgba_p,
+                      rec_p) == _lib.OW_ERR_INVALID
+            out.append(lib.ow_last_error().decode())
+        assert out[0] == out[1]
+        return out[0]
+
+    def options(**kw):
+        return W.render_options(kw)
+
+    good = look((0, 10, 0), 0, -10)
+    assert "null context" in both(good, None)                                  # everything else is in order: only the context is missing
+    assert "null context" in both(good, options(roughness=0.0, sky_color=(0, 0, 0), foam_color=(0, 0, 0)))
+    assert "both outputs" in both(good, None, None, None)
+    assert "null argument" in both(good, None, scales=None)
+    assert "null camera" in both(None, None)
+    for w, h in ((0, 12), (20, 0), (-3, 12), (_lib.OW_RENDER_MAX_SIDE + 1, 12), (20, _lib.OW_RENDER_MAX_SIDE + 1)):
+        assert "camera size" in both(look((0, 10, 0), 0, -10, width=w, height=h), None)
+    cam = look((0, 10, 0), 0, -10)
+    cam.reserved[3] = 1
+    assert "ow_camera.reserved" in both(cam, None)
+    for k in ("water_color", "foam_color", "light_direction", "light_color", "ambient_color", "sky_color"):
+        for bad in (float("nan"), float("inf")):
+            assert "not finite" in both(good, options(**{k: (0.5, bad, 0.5)})), k
+    for bad in (-0.01, 1.01, float("nan")):
+        assert "roughness" in both(good, options(roughness=bad))
+        assert "normal_strength" in both(good, options(normal_strength=bad))
+    assert "zero length" in both(good, options(light_direction=(0.0, 0.0, 0.0)))
+    o = options()
+    o.flags = 1
+    assert "flags" in both(good, o)
+    o = options()
+    o.reserved[10] = 7
+    assert "ow_render_options.reserved" in both(good, o)
+    o = options()
+    o.raycast.reserved[1] = 1
+    assert "ow_raycast_options.reserved" in both(good, o)
+    assert "max_samples" in both(good, options(max_samples=-1))
+    assert "finite" in both(good, options(tolerance=float("nan")))
+    assert "finite" in both(good, options(falloff_center=(float("inf"), 0.0)))
+    assert not rgba.any() and not rec.tobytes().strip(b"\0")
+    # the Python options: unknown keys, the falloff around the camera
+    with pytest.raises(ValueError):
+        W.render_options({"spacing": 1.0})
+    with pytest.raises(ValueError):
+        W.render_options({"falloff": True})
+    o = W.render_options({"falloff": True, "roughness": 0.4, "max_samples": 64, "sky_color": (0.1, 0.2, 0.3)}, look((3, 10, -7), 0, -10))
+    assert (o.raycast.query.flags, tuple(o.raycast.query.falloff_center_xz), o.raycast.max_samples) == (_lib.OW_QUERY_DISTANCE_FALLOFF, (3.0, -7.0), 64)
+    assert o.roughness == np.float32(0.4) and tuple(o.sky_color) == tuple(np.float32((0.1, 0.2, 0.3))) and o.normal_strength == 1.0
+    assert tuple(W.render_options({"falloff_center": (1.0, 2.0)}).raycast.query.falloff_center_xz) == (1.0, 2.0)
+
+
+# ---- 3. the CPU build: a calm sea ----------------------------------------------------------------------------------------------------
+
+def test_calm_sea_is_the_analytic_picture(harness):
+    """Zero maps, the camera 10 m up and pitched 10 degrees down: the horizon crosses the frame between two pixel rows.  Below it every
+    pixel hits the plane at t = h / -d.y; above it every pixel is sky."""
+    d, m, sc = calm_maps()
+    cam = look((3.0, 10.0, -4.0), 20.0, -10.0, max_distance=1e5)
+    rgba, rec = cpu_render(harness, d, m, sc, cam)
+    hit = check_composite(rgba, rec)
+    dirs = RT.pixel_directions(list(cam.basis), cam.fov_y_degrees, cam.width, cam.height)
+    below = dirs[..., 1] < 0
+    assert below.any() and (~below).any() and below[-1].all() and not below[0].any()
+    assert np.array_equal(hit, below) and (rec["status"][below] == HIT).all() and (rec["status"][~below] == 0).all()
+    assert np.array_equal(rgba[~below], np.broadcast_to(RT.rgba8(np.float32(DEFAULTS["sky_color"])), rgba[~below].shape))
+    t_star = 10.0 / -dirs[..., 1][below]
+    assert np.abs(rec["t"][below] - t_star).max() <= TOL + 1e-6 * t_star.max()
+    assert (rec["normal"][below] == np.float32((0, 1, 0))).all() and (rec["foam_factor"][below] == 0).all()
+    assert (rec["albedo"][below] == np.float32(DEFAULTS["water_color"])).all() and (rec["wave_height"][below] == 0).all()
+    r = rec[below]
+    twin = RT.shade(r["gradient_fragment"], r["foam_fragment"], r["wave_height"], r["position"], list(cam.position), list(cam.basis), uniforms_of(None))
+    assert np.abs(r["color"] - twin["color"]).max() <= 1e-4
+    assert np.abs(r["dist"] - twin["dist"]).max() <= 1e-6 * twin["dist"].max()
+
+
+# ---- 4. pixel rays against the FP64 twin ----------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("fov", [20.0, 75.0, 120.0])
+@pytest.mark.parametrize("size", [(20, 12), (37, 21), (13, 50)])
+def test_pixel_rays_against_the_fp64_twin(harness, fov, size):
+    """a handful of FP32 operations on unit-scale numbers: a few ulp, 1e-6 per component"""
+    cam = look((1.0, 5.0, -2.0), 33.0, -17.0, fov=fov, width=size[0], height=size[1])
+    rays = pixel_rays(harness, cam)
+    assert (rays["origin"] == np.float32(list(cam.position))).all() and (rays["max_distance"] == cam.max_distance).all() and not rays["reserved"].any()
+    want = RT.pixel_directions(list(cam.basis), cam.fov_y_degrees, cam.width, cam.height).reshape(-1, 3)
+    d = rays["direction"]   # normalised as ray_setup normalises it
+    got = d / np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2])[:, None]
+    assert got.dtype == np.float32 and np.abs(got - want).max() <= 1e-6
+    # the corners look where the formula says: the first pixel up and to the left of the axis
+    fwd = -np.asarray(list(cam.basis), np.float64).reshape(3, 3)[:, 2]
+    right = np.asarray(list(cam.basis), np.float64).reshape(3, 3)[:, 0]
+    assert want[0] @ right < 0 < want[cam.width - 1] @ right and want[0, 1] > want[-1, 1] and (want @ fwd > 0).all()
+
+
+# ---- 5. log_f32 against the FP64 library ----------------------------------------------------------------------------------------------
+
+LOG_F32_MAX_ULP = 1.94   # measured on the CPU build over this sweep (1.939 at x = 1.03112); csrc/ow_shading.h states it beside exp_f32's
+
+
+def test_log_f32_against_the_fp64_library(harness):
+    tiny, one = np.float32(1.17549435e-38), np.float32(1.0)
+    x = np.concatenate([np.geomspace(float(tiny), 4.0, 400001).astype(np.float32),
+                        np.linspace(0.5, 2.0, 100001).astype(np.float32),
+                        [tiny, np.nextafter(tiny, one), np.nextafter(one, np.float32(0)), one, np.nextafter(one, np.float32(2)), np.float32(4.0)],
+                        np.float32(2.0) ** np.arange(-126, 3), np.nextafter(np.float32(2.0) ** np.arange(-125, 3), np.float32(0)),
+                        np.float32(np.sqrt(2.0)) * np.float32(2.0) ** np.arange(-20, 2)]).astype(np.float32)
+    x = x[(x >= tiny) & (x <= 4.0)]
+    got = np.zeros(len(x), np.float32)
+    harness.harness_log(x.ctypes.data, len(x), got.ctypes.data)
+    want = np.log(x.astype(np.float64))
+    assert np.isfinite(got).all()
+    assert (got[x == 1.0] == 0).all()
+    nz = want != 0
+    ulp = np.spacing(np.abs(want[nz]).astype(np.float32)).astype(np.float64)
+    err = np.abs(got[nz].astype(np.float64) - want[nz]) / ulp
+    print(f"log_f32: largest error {err.max():.3f} ulp at x = {x[nz][err.argmax()]!r}, mean {err.mean():.3f}")
+    assert err.max() <= LOG_F32_MAX_ULP
+    # outside the domain the guard's values, not NaN or Inf; subnormals through the scaling
+    odd = np.array([0.0, -1.0, np.nan, np.inf, 1e-45, 1e-40], np.float32)
+    out = np.zeros(len(odd), np.float32)
+    harness.harness_log(odd.ctypes.data, len(odd), out.ctypes.data)
+    assert list(out[:4]) == [np.float32(-3.4028235e38)] * 3 + [np.float32(3.4028235e38)]
+    assert np.abs(out[4:] - np.log(odd[4:].astype(np.float64))).max() <= 1e-5
+
+
+# ---- 6. pixels are the ray cast's -----------------------------------------------------------------------------------------------------
+
+@pytest.fixture(scope="module")
+def demo_maps():
+    return generated_maps(256, [0, 1, 2, 3])
+
+
+def maps_named(name, demo):
+    return {"calm": calm_maps, "swell": swell_maps}[name]() if name != "demo" else demo
+
+
+VIEWS = {
+    "down": (dict(position=(5.0, 30.0, -8.0), yaw_deg=40.0, pitch_deg=-80.0), None),
+    "horizon": (dict(position=(0.0, 10.0, -25.0), yaw_deg=5.0, pitch_deg=-10.0), None),
+    "under_water": (dict(position=(2.0, -6.0, 3.0), yaw_deg=-60.0, pitch_deg=25.0), None),
+    "truncated": (dict(position=(0.0, 6.0, 0.0), yaw_deg=100.0, pitch_deg=-12.0), {"max_samples": 24, "sample_spacing": 0.5}),
+}
+
+
+@pytest.mark.parametrize("maps", ["calm", "swell", "demo"])
+@pytest.mark.parametrize("view", list(VIEWS))
+def test_pixels_are_the_ray_casts(harness, ray_harness, demo_maps, maps, view):
+    """every pixel of a 20 x 12 image: t, position, status and p are the bits of the ray cast of the pixel's ray (the 64-lane rounds of
+    ow_raycast.h stepped in sequence) -- the one-lane walk reaches the same bracket, the same refinement and the same truncation"""
+    d, m, sc = maps_named(maps, demo_maps)
+    kw, opts = VIEWS[view]
+    cam = look(max_distance=3000.0, **kw)
+    opts = dict(opts or {}, falloff=True) if maps == "demo" and view == "horizon" else opts
+    rgba, rec = cpu_render(harness, d, m, sc, cam, opts)
+    hit = check_composite(rgba, rec, opts)
+    want = cpu_raycast(ray_harness, d, m, sc, pixel_rays(harness, cam), ray_options(opts, cam)).reshape(rec.shape)
+    assert np.array_equal(rec["status"], want["status"])
+    assert rec["t"].tobytes() == want["t"].tobytes() and rec["position"].tobytes() == want["position"].tobytes()
+    assert rec["p"].tobytes() == want["query"]["p"].tobytes()
+    s = want["query"]["sample"]
+    assert rec["gradient_fragment"].tobytes() == s["gradient_fragment"].tobytes() and rec["foam_fragment"].tobytes() == s["foam_fragment"].tobytes()
+    assert rec["wave_height"].tobytes() == s["displacement"][..., 1].tobytes()
+    st = rec["status"]
+    print(f"{maps}/{view}: hit {hit.mean():.2f}, from below {((st & BELOW) != 0).mean():.2f}, truncated {((st & TRUNC) != 0).mean():.2f}")
+    assert hit.any()
+    if view == "under_water":
+        assert ((st & BELOW) != 0).all()
+    if view == "truncated" and maps != "calm":   # a calm sea's slab is 2 cm thick: no pixel's ray stays in it for 24 samples
+        assert ((st & TRUNC) != 0).any() and not (st[(st & TRUNC) != 0] & HIT).any()
+    if view == "horizon":
+        assert hit[-1].all() and not hit[0].any()
+
+
+# ---- 7. the shading against the FP64 twin -----------------------------------------------------------------------------------------------
+
+SHADE_TOL = H.TOL_F32   # 1e-4: the project's FP32 parity tolerance
+
+
+def compare_with_twin(rec, cam, options):
+    """every hit pixel against the twin fed the record's own inputs; absolute for the terms bounded by 1, relative to max(1, |twin|) for
+    diffuse and specular.  Returns the largest error per term."""
+    hit = (rec["status"] & HIT) != 0
+    r = rec[hit]
+    twin = RT.shade(r["gradient_fragment"], r["foam_fragment"], r["wave_height"], r["position"], list(cam.position), list(cam.basis),
+                    uniforms_of(options))
+    worst = {}
+    for k in ("foam_factor", "albedo", "normal", "fresnel", "roughness", "color", "diffuse", "specular"):
+        assert np.isfinite(twin[k]).all(), k
+        err = np.abs(r[k].astype(np.float64) - twin[k])
+        if k in ("diffuse", "specular"):
+            err = err / np.maximum(1.0, np.abs(twin[k]))
+        worst[k] = float(err.max())
+    return worst, int(hit.sum())
+
+
+@pytest.mark.parametrize("sun", [SUN_LOW, SUN_BEHIND], ids=["low_sun", "sun_behind"])
+@pytest.mark.parametrize("normal_strength", [0.0, 1.0])
+@pytest.mark.parametrize("roughness", [0.0, 0.4, 0.65, 1.0])
+def test_shading_against_the_fp64_twin(harness, demo_maps, roughness, normal_strength, sun):
+    assert SHADE_TOL == 1e-4
+    d, m, sc = demo_maps
+    opts = dict(roughness=roughness, normal_strength=normal_strength, light_direction=sun, light_color=(1.0, 0.95, 0.9), falloff=True)
+    worst_all = {}
+    hits = 0
+    for cam in (look((0.0, 10.0, -25.0), 5.0, -10.0, width=24, height=16), look((10.0, 4.0, 5.0), -130.0, -35.0, width=12, height=8)):
+        rgba, rec = cpu_render(harness, d, m, sc, cam, opts)
+        check_composite(rgba, rec, opts)
+        worst, n = compare_with_twin(rec, cam, opts)
+        hits += n
+        for k, v in worst.items():
+            worst_all[k] = max(worst_all.get(k, 0.0), v)
+    print(f"roughness {roughness}, normal_strength {normal_strength}: {hits} hit pixels, largest errors " +
+          ", ".join(f"{k} {v:.1e}" for k, v in worst_all.items()))
+    assert hits > 200
+    for k, v in worst_all.items():
+        assert v <= SHADE_TOL, (k, v)
+
+
+# ---- 8. nothing NaN or Inf ------------------------------------------------------------------------------------------------------------
+
+def test_no_nan_or_inf_on_awkward_inputs(harness, demo_maps):
+    d, m, sc = demo_maps
+    calm = calm_maps()
+    nan = float("nan")
+    cases = [
+        ("camera on the surface", calm, look((0.0, 0.0, 0.0), 0.0, -30.0), None),
+        ("camera on the surface, looking along it", calm, look((0.0, 0.0, 0.0), 0.0, 0.0), None),
+        ("camera on the demo surface", (d, m, sc), look((0.0, 0.3, 0.0), 10.0, -20.0), {"falloff": True}),
+        ("looking straight up", (d, m, sc), look((0.0, 5.0, 0.0), 0.0, 89.999), None),
+        ("looking straight up from below", (d, m, sc), look((0.0, -30.0, 0.0), 0.0, 89.999), None),
+        ("looking straight down, the light along the view", calm, look((0.0, 8.0, 0.0), 0.0, -89.999, fov=1.0, width=9, height=9),
+         {"light_direction": (0.0, 1.0, 0.0)}),
+        ("the light against the view", calm, look((0.0, 8.0, 0.0), 0.0, -45.0, fov=1.0, width=9, height=9),
+         {"light_direction": (0.0, -math.sin(math.radians(45.0)), math.cos(math.radians(45.0)))}),
+        ("the light from below", (d, m, sc), look((0.0, 10.0, -25.0), 5.0, -10.0), {"light_direction": (0.0, -1.0, 0.0)}),
+        ("roughness 0", (d, m, sc), look((0.0, 10.0, -25.0), 5.0, -10.0), {"roughness": 0.0}),
+        ("roughness 0 on a mirror", calm, look((0.0, 8.0, 0.0), 0.0, -45.0, fov=1.0, width=9, height=9),
+         {"roughness": 0.0, "light_direction": (0.0, math.sin(math.radians(45.0)), math.cos(math.radians(45.0)))}),
+        ("roughness 1", (d, m, sc), look((0.0, 10.0, -25.0), 5.0, -10.0), {"roughness": 1.0}),
+        ("zero foam colour", (d, m, sc), look((0.0, 10.0, -25.0), 5.0, -10.0), {"foam_color": (0.0, 0.0, 0.0)}),
+        ("everything black", (d, m, sc), look((0.0, 10.0, -25.0), 5.0, -10.0),
+         {"foam_color": (0, 0, 0), "water_color": (0, 0, 0), "light_color": (0, 0, 0), "ambient_color": (0, 0, 0), "sky_color": (0, 0, 0)}),
+        ("a huge light", (d, m, sc), look((0.0, 10.0, -25.0), 5.0, -10.0), {"light_color": (3e37, 3e37, 3e37), "light_direction": (1e-20, 1e-19, 0)}),
+    ]
+    for name, (dd, mm, ss), cam, opts in cases:
+        rgba, rec = cpu_render(harness, dd, mm, ss, cam, opts)
+        for f in W.RENDER_PIXEL.names:
+            if f not in ("status", "reserved"):
+                assert np.isfinite(rec[f]).all(), (name, f)
+        assert (rgba[..., 3] == 255).all(), name
+        assert not (rec["status"] & INVALID).any(), name
+    # a camera that is not finite is no error: all sky, OW_RAY_INVALID in every pixel
+    for field, value in (("position", (nan, 0, 0)), ("basis", [float("inf")] + [0.0] * 8), ("fov", nan), ("max_distance", nan), ("max_distance", -1.0),
+                         ("max_distance", 0.0)):
+        cam = look((0.0, 10.0, 0.0), 0.0, -10.0)
+        if field == "position":
+            cam.position[:] = value
+        elif field == "basis":
+            cam.basis[:] = value
+        elif field == "fov":
+            cam.fov_y_degrees = value
+        else:
+            cam.max_distance = value
+        rgba, rec = cpu_render(harness, d, m, sc, cam, None)
+        assert (rec["status"] == INVALID).all(), field
+        assert np.array_equal(rgba, np.broadcast_to(RT.rgba8(np.float32(DEFAULTS["sky_color"])), rgba.shape)), field
+        check_composite(rgba, rec)
+
+
+# ---- 9. the C example -----------------------------------------------------------------------------------------------------------------
+
+def build_example(tmp_path):
+    exe = str(tmp_path / "render_host")
+    subprocess.run(["gcc", "-O2", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "examples", "render_host.c"),
+                    "-o", exe, "-L", PKG, "-locean_waves", f"-Wl,-rpath,{PKG}", "-Wl,-rpath,/opt/rocm/lib", "-Wl,-rpath-link,/opt/rocm/lib", "-lm"],
+                   check=True)
+    return exe
+
+
+def test_example_builds_as_c99(tmp_path):
+    build.build_library()
+    build_example(tmp_path)
+
+
+# ---- 10-13. on the GPU ------------------------------------------------------------------------------------------------------------------
+
+GPU_CAM = dict(position=(0.0, 10.0, -25.0), yaw_deg=5.0, pitch_deg=-10.0)
+
+
+def assert_same_image(got, want, what):
+    (g_rgba, g_rec), (w_rgba, w_rec) = got, want
+    for f in W.RENDER_PIXEL.names:
+        assert g_rec[f].tobytes() == w_rec[f].tobytes(), (what, f)
+    assert g_rgba.tobytes() == w_rgba.tobytes(), what
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n,ids", [(256, [0, 1, 2, 3]), (1024, [0, 1, 2]), (2048, [0])])
+def test_gpu_image_is_the_cpu_builds_bit_for_bit(harness, n, ids):
+    """20 x 12: the smallest image with two tile rows, three tile columns and partial tiles on both edges"""
+    gen, params = make_gen(n, ids)
+    gen.run(UPDATE_DELTA, params, 3)
+    sc = scales_of(params)
+    d, m = gpu_maps(gen, len(ids))
+    cam = look(**GPU_CAM)
+    cases = [("defaults", cam, None), ("falloff", cam, {"falloff": True, "roughness": 0.4, "light_direction": SUN_BEHIND})]
+    if n == 256:
+        cases.append(("truncating", look((0.0, 6.0, 0.0), 100.0, -12.0), {"max_samples": 24, "sample_spacing": 0.5, "water_level": 0.3}))
+        cases.append(("under water", look((2.0, -6.0, 3.0), -60.0, 25.0), None))
+        cases.append(("64 x 40", look(width=64, height=40, **GPU_CAM), {"falloff": True}))
+    for what, c, opts in cases:
+        got = gen.render_view(c, sc, opts)
+        want = cpu_render(harness, d, m, sc, c, opts)
+        assert_same_image(got, want, what)
+        assert ((got[1]["status"] & HIT) != 0).mean() > 0.3, what
+        only_rgba, none = gen.render_view(c, sc, opts, pixels=False)
+        assert none is None and only_rgba.tobytes() == want[0].tobytes(), what
+    assert n != 256 or ((gen.render_view(cases[2][1], sc, cases[2][2])[1]["status"] & TRUNC) != 0).any()
+
+
+def _async_case(drive, stream=None, torch_stream=None):
+    """drive(gen, params, 8) / render_view_async / drive again / sync, against the synchronous render of a context that stopped after the
+    first drive: the asynchronous render read the maps of exactly that point of the stream (test_raycast.py's _async_case)"""
+    import torch
+    n, ids = 1024, [0, 1, 2, 3]
+    a, pa = make_gen(n, ids, stream=stream)
+    b, pb = make_gen(n, ids)
+    sc = scales_of(pa)
+    cam = look(**GPU_CAM)
+    opts = {"falloff": True}
+    count = cam.width * cam.height
+    rgba_dev = torch.zeros((count, 4), dtype=torch.uint8, device="cuda:0")
+    rec_dev = torch.zeros((count, W.RENDER_PIXEL.itemsize), dtype=torch.uint8, device="cuda:0")
+    torch.cuda.synchronize()
+    drive(a, pa, 8)
+    if torch_stream is not None:
+        with torch.cuda.stream(torch_stream):
+            a.render_view_async(cam, sc, rgba_dev, rec_dev, opts)
+            copy = rgba_dev.to("cpu", non_blocking=False)   # the caller's own work, ordered by its stream alone
+        torch_stream.synchronize()
+    else:
+        a.render_view_async(cam, sc, rgba_dev, rec_dev, opts)
+    drive(a, pa, 8)
+    a.sync()
+    got_rgba = rgba_dev.cpu().numpy().reshape(cam.height, cam.width, 4)
+    got_rec = np.frombuffer(rec_dev.cpu().numpy().tobytes(), W.RENDER_PIXEL).reshape(cam.height, cam.width)
+    drive(b, pb, 8)
+    want = b.render_view(cam, sc, opts)
+    assert_same_image((got_rgba, got_rec), want, "async")
+    if torch_stream is not None:
+        assert copy.numpy().tobytes() == want[0].tobytes()
+    # ... and the second half moved the maps: a render now reads other bits
+    assert a.render_view(cam, sc, opts)[1].tobytes() != want[1].tobytes()
+    return a
+
+
+@pytest.mark.gpu
+def test_async_render_is_ordered_behind_both_chains_on_the_contexts_stream():
+    a = _async_case(lambda g, p, k: g.run(UPDATE_DELTA, p, k))
+    assert a.chain_stats() > 0
+
+
+@pytest.mark.gpu
+def test_async_render_on_a_callers_stream():
+    import torch
+    s = torch.cuda.Stream()
+    _async_case(lambda g, p, k: g.run(UPDATE_DELTA, p, k), stream=s.cuda_stream, torch_stream=s)
+
+
+@pytest.mark.gpu
+def test_async_render_between_look_ahead_ticks():
+    def ticks(g, p, k):
+        for _ in range(k):
+            g.update_all(UPDATE_DELTA, p)
+    a = _async_case(ticks)
+    hits, _ = a.lookahead_stats()
+    assert hits > 0
+
+
+@pytest.mark.gpu
+def test_async_render_argument_errors():
+    import torch
+    gen, params = make_gen(256, [0, 1])
+    sc = scales_of(params)
+    cam = look(**GPU_CAM)
+    count = cam.width * cam.height
+    rgba_dev = torch.zeros((count, 4), dtype=torch.uint8, device="cuda:0")
+    rec_dev = torch.zeros((count, W.RENDER_PIXEL.itemsize), dtype=torch.uint8, device="cuda:0")
+    reserved = W.render_options({})
+    reserved.reserved[0] = 1
+    flags = W.render_options({})
+    flags.flags = 2
+    bad_cam = look(width=0, **{k: v for k, v in GPU_CAM.items()})
+    big_cam = look(width=_lib.OW_RENDER_MAX_SIDE + 1, height=1, **{k: v for k, v in GPU_CAM.items()})
+    for c, bad in [(cam, {"roughness": 1.5}), (cam, {"roughness": float("nan")}), (cam, {"normal_strength": -0.5}), (cam, {"light_direction": (0, 0, 0)}),
+                   (cam, {"sky_color": (0, float("inf"), 0)}), (cam, {"max_samples": -1}), (cam, {"tolerance": float("nan")}), (cam, reserved),
+                   (cam, flags), (bad_cam, None), (big_cam, None)]:
+        with pytest.raises(_lib.OceanWavesError) as e:
+            gen.render_view_async(c, sc, rgba_dev if c is not big_cam else rgba_dev.data_ptr(), rec_dev if c is not big_cam else rec_dev.data_ptr(), bad)
+        assert e.value.status == _lib.OW_ERR_INVALID
+        with pytest.raises(_lib.OceanWavesError) as e:
+            gen.render_view(c, sc, bad)
+        assert e.value.status == _lib.OW_ERR_INVALID
+    with pytest.raises(_lib.OceanWavesError) as e:
+        gen.render_view_async(cam, sc, None, None)
+    assert e.value.status == _lib.OW_ERR_INVALID
+    with pytest.raises(_lib.OceanWavesError) as e:
+        gen.render_view_async(cam, sc, rgba_dev, rec_dev.data_ptr() + 4)   # records are written as 16-byte vectors
+    assert e.value.status == _lib.OW_ERR_INVALID
+    with pytest.raises(_lib.OceanWavesError) as e:
+        gen.render_view(cam, np.ones((3, 4), np.float32))                   # more cascades than the context has
+    assert e.value.status == _lib.OW_ERR_INVALID
+    with pytest.raises(ValueError):
+        gen.render_view_async(cam, sc, rgba_dev[:10], rec_dev)
+    torch.cuda.synchronize()
+    assert not rgba_dev.any() and not rec_dev.any()
+    # a camera that is not finite is no error: sky everywhere
+    cam.position[1] = float("nan")
+    rgba, rec = gen.render_view(cam, sc)
+    assert (rec["status"] == INVALID).all() and np.array_equal(rgba, np.broadcast_to(RT.rgba8(np.float32(DEFAULTS["sky_color"])), rgba.shape))
+
+
+@pytest.mark.gpu
+def test_the_c_example_writes_the_python_wrappers_image(tmp_path):
+    """examples/render_host.c at 256^2, 40 x 24, five ticks, against the wrapper on the same scene: the reference camera (main.tscn:120),
+    the default options, the falloff around the camera"""
+    exe = build_example(tmp_path)
+    ppm = str(tmp_path / "water.ppm")
+    r = subprocess.run([exe, ppm, "40", "24", "5", "256"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr
+    kv = dict(p.split("=") for p in r.stdout.split())
+    assert kv["finite"] == "1" and 0.3 < float(kv["hit_share"]) < 0.9
+    raw = open(ppm, "rb").read()
+    head = b"P6\n40 24\n255\n"
+    assert raw.startswith(head) and len(raw) == len(head) + 40 * 24 * 3
+    gen, params = make_gen(256, [0, 1, 2])
+    for _ in range(5):
+        gen.update_all(UPDATE_DELTA, params)
+    cam = W.camera((0.0, 10.0, -25.0), (-0.996195, -0.0151344, 0.0858316, 0.0, 0.984807, 0.173648, -0.0871557, 0.172987, -0.981061), 75.0, 40, 24,
+                   4000.0)
+    rgba, rec = gen.render_view(cam, scales_of(params), {"falloff": True})
+    assert np.frombuffer(raw[len(head):], np.uint8).reshape(24, 40, 3).tobytes() == rgba[..., :3].tobytes()
+    assert abs(((rec["status"] & HIT) != 0).mean() - float(kv["hit_share"])) < 1e-3
