@@ -100,6 +100,52 @@ struct VelStage {
     static constexpr int R = R_, NS = NS_;
 };
 
+// ---- pass 1, per element: spectrum texel (ky, kx) -> the two packed values -------------------------------------------------------------
+struct VelPair {
+    cplx va, vb;  // layer A = hx + i hy, layer B = hz + i dhy_dx
+};
+// The two packed values of spectrum texel (ky, kx) of one layer: h0c / omc are the layer's resident planes, tile_x / tile_y / time the FP32
+// words of its modulate push constants.  (Plain C++ as well: tests/velocity/velocity_emul.cpp steps the lanes of a block through it.)
+template <int N>
+OW_DEV VelPair vel_load(int ky, int kx, const cplx *h0c, const float *omc, float tile_x, float tile_y, float time) {
+    const cplx *a_row = h0c + (size_t)ky * N;
+    const cplx *b_row = h0c + (size_t)((N - ky) % N) * N;  // the mirrored texel's row
+    const float *o_row = omc + (size_t)ky * N;
+    const float kyf = modulate_kcomp(ky, N, tile_y);
+    const cplx a = a_row[kx], b = b_row[(N - kx) % N];
+    const float om = o_row[kx];
+    const cplx e = expi_phase(mul_rn(om, time));  // (cos, sin) of the maps' own FP32 phase (Pass1::modulate)
+    // h0 m - conj(h0(-k)) conj(m) with the stored texel a = h0(k), b = h0(-k):
+    //   g.re = (a.re - b.re) cos - (a.im - b.im) sin,  g.im = (a.re + b.re) sin + (a.im + b.im) cos;  hdot = i omega g
+    const cplx pp = cadd(a, b), qq = csub(a, b);
+    const float gre = qq.x * e.x - qq.y * e.y, gim = pp.x * e.y + pp.y * e.x;
+    const cplx hd = cplx{-om * gim, om * gre};
+    const float kxf = modulate_kcomp(kx, N, tile_x);
+    const float k = sqrtf(kxf * kxf + kyf * kyf) + 1e-6f;  // spectrum_modulate.glsl:61-62
+    const float ux = kxf / k, uy = kyf / k;
+    const cplx ihd = cmuli(hd);
+    const cplx hx = cscale(ihd, uy), hz = cscale(ihd, ux), gx = cscale(ihd, kyf);
+    VelPair r;
+    r.va = cplx{hx.x - hd.y, hx.y + hd.x};  // hx + i hy, hy = hdot
+    r.vb = cplx{hz.x - gx.y, hz.y + gx.x};  // hz + i dhy_dx, dhy_dx = i ky hdot: the maps' layer 1, whose real part is hz
+    return r;
+}
+
+// ---- pass 2, per texel -----------------------------------------------------------------------------------------------------------------
+// texel (x, y) of the layer from the two transforms' values there: the sign, the three channels as halves, w = 0
+OW_DEV u16x4 vel_texel(cplx A, cplx B, int x, int y) {
+    const float s = ((x ^ y) & 1) ? -1.0f : 1.0f;  // fft_unpack.glsl:50
+    const uint32_t w0 = f2h2(A.x * s, A.y * s), w1 = f2h2(B.x * s, 0.0f);
+    u16x4 t;
+    t.x = (uint16_t)(w0 & 0xffffu);
+    t.y = (uint16_t)(w0 >> 16);
+    t.z = (uint16_t)(w1 & 0xffffu);
+    t.w = (uint16_t)(w1 >> 16);
+    return t;
+}
+
+// ---- device only from here: the barriers of the row transform and the two kernels (the CPU emulation steps the stage functions itself) ----
+#if OW_DEVICE_BUILD
 // The row transform of both layers (a, b) of lane j: first stage R0 (NS = 1), then radix 16 until NS = N / 16.  After it, element
 // j + k T of the result is in slot vel_slot<16>(k).  lds: this row's N (+ padding) complex, shared by the two layers in turn; every lane
 // of the block runs this (barriers).
@@ -141,29 +187,13 @@ __global__ __launch_bounds__(VelPlan<N>::THREADS) void k_velocity_pass1(Velocity
     const int c = args.cascade[slot];
     const float time = args.time[slot];
     const size_t plane = (size_t)N * N;
-    const cplx *a_row = h0 + c * plane + (size_t)ky * N;
-    const cplx *b_row = h0 + c * plane + (size_t)((N - ky) % N) * N;  // the mirrored texel's row
-    const float *o_row = omega + c * plane + (size_t)ky * N;
-    const float kyf = modulate_kcomp(ky, N, args.tile_y[slot]);
     cplx va[16], vb[16];
 #pragma unroll
     for (int m = 0; m < 16; ++m) {
         const int kx = j + m * T;
-        const cplx a = a_row[kx], b = b_row[(N - kx) % N];
-        const float om = o_row[kx];
-        const cplx e = expi_phase(mul_rn(om, time));  // (cos, sin) of the maps' own FP32 phase (Pass1::modulate)
-        // h0 m - conj(h0(-k)) conj(m) with the stored texel a = h0(k), b = h0(-k):
-        //   g.re = (a.re - b.re) cos - (a.im - b.im) sin,  g.im = (a.re + b.re) sin + (a.im + b.im) cos;  hdot = i omega g
-        const cplx pp = cadd(a, b), qq = csub(a, b);
-        const float gre = qq.x * e.x - qq.y * e.y, gim = pp.x * e.y + pp.y * e.x;
-        const cplx hd = cplx{-om * gim, om * gre};
-        const float kxf = modulate_kcomp(kx, N, args.tile_x[slot]);
-        const float k = sqrtf(kxf * kxf + kyf * kyf) + 1e-6f;  // spectrum_modulate.glsl:61-62
-        const float ux = kxf / k, uy = kyf / k;
-        const cplx ihd = cmuli(hd);
-        const cplx hx = cscale(ihd, uy), hz = cscale(ihd, ux), gx = cscale(ihd, kyf);
-        va[m] = cplx{hx.x - hd.y, hx.y + hd.x};  // hx + i hy, hy = hdot
-        vb[m] = cplx{hz.x - gx.y, hz.y + gx.x};  // hz + i dhy_dx, dhy_dx = i ky hdot: the maps' layer 1, whose real part is hz
+        const VelPair v = vel_load<N>(ky, kx, h0 + c * plane, omega + c * plane, args.tile_x[slot], args.tile_y[slot], time);
+        va[m] = v.va;
+        vb[m] = v.vb;
     }
     vel_row_fft<N>(va, vb, j, lds + w * P::STRIDE, tw);
     cplx *sa = scratch + (size_t)(2 * slot) * plane, *sb = sa + plane;
@@ -201,16 +231,9 @@ __global__ __launch_bounds__(VelPlan<N>::THREADS) void k_velocity_pass2(Velocity
 #pragma unroll
     for (int k = 0; k < 16; ++k) {
         const int x = j + k * T;
-        const float s = ((x ^ y) & 1) ? -1.0f : 1.0f;  // fft_unpack.glsl:50
-        const cplx A = va[vel_slot<16>(k)], B = vb[vel_slot<16>(k)];
-        const uint32_t w0 = f2h2(A.x * s, A.y * s), w1 = f2h2(B.x * s, 0.0f);
-        u16x4 t;
-        t.x = (uint16_t)(w0 & 0xffffu);
-        t.y = (uint16_t)(w0 >> 16);
-        t.z = (uint16_t)(w1 & 0xffffu);
-        t.w = (uint16_t)(w1 >> 16);
-        row[x] = t;
+        row[x] = vel_texel(va[vel_slot<16>(k)], vb[vel_slot<16>(k)], x, y);
     }
 }
+#endif
 
 }  // namespace ow

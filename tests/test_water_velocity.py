@@ -15,12 +15,12 @@ import numpy as np
 import pytest
 
 import helpers as H
-import np_twin as NT
 from godotoceanwaves_amd import _lib, build
-from godotoceanwaves_amd.presets import UPDATE_DELTA
+from godotoceanwaves_amd.presets import UPDATE_DELTA, cascade_preset
 from godotoceanwaves_amd.wave_generator import WaveGenerator as W
 from test_buoyancy import RHO, RHO_G, cpu_buoyancy, harness as buoyancy_harness, make_scene  # noqa: F401
 from test_surface_query import gpu_maps, make_gen, maps_u16, scales_of
+from velocity_twin import phases, velocity_twin
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "godotoceanwaves_amd", "csrc")
@@ -72,45 +72,21 @@ def cpu_buoyancy_moving(L, disp, vel, scales, bodies, hull, water_level=0.0):
     return res, pts
 
 
-# ---- the FP64 twin of the derivative --------------------------------------------------------------------------------------------------
+# ---- the FP64 twin of the derivative: tests/velocity_twin.py ---------------------------------------------------------------------------
 
-def velocity_twin(h0_texel, omega, modulate_words):
-    """V of one layer, FP64, written from np_twin's modulate / ifft2_ref / unpack conventions with hdot in place of h: the inputs are the
-    resident spectrum (ow_get_spectrum's texel (h0(k), conj(h0(-k))) and omega) and the layer's FP32 push-constant words, the phase the FP32
-    product omega * t"""
-    n = omega.shape[0]
-    f = np.asarray(modulate_words, np.uint32).view(np.float32)
-    tile = (float(f[0]), float(f[1]))
-    ph = (omega.astype(np.float32) * f[3]).astype(np.float64)
-    om = omega.astype(np.float64)
-    h0 = h0_texel[..., 0].astype(np.float64) + 1j * h0_texel[..., 1]
-    h0m = h0_texel[..., 2].astype(np.float64) + 1j * h0_texel[..., 3]
-    m = np.exp(1j * ph)
-    hdot = 1j * om * (h0 * m - h0m * np.conj(m))
-    idy, idx = np.meshgrid(np.arange(n), np.arange(n), indexing="ij")
-    kx = (idx - n * 0.5) * 2 * np.pi / tile[0]
-    ky = (idy - n * 0.5) * 2 * np.pi / tile[1]
-    k = np.hypot(kx, ky) + 1e-6
-    ux, uy = kx / k, ky / k
-    hi = 1j * hdot
-    out = NT.ifft2_ref(np.stack([hi * uy + 1j * hdot, hi * ux + 1j * (hi * ky)]))  # modulate's layers 0 and 1
-    iy, ix = np.meshgrid(np.arange(n), np.arange(n), indexing="ij")
-    sign = 1.0 - 2.0 * ((ix & 1) ^ (iy & 1))
-    o = out * sign
-    return np.stack([o[0].real, o[0].imag, o[1].real], axis=-1)
-
-
-def check_layer(gen, i):
-    """layer i of V against the twin at the layer's own words; returns the worst ratio to the allowance"""
+def check_layer(gen, i, floor=FLOOR, m=None, calm=False):
+    """layer i of V against the twin at the layer's own words; returns the worst ratio to the allowance.
+    floor: the record's floor where it is not FLOOR (tests/test_velocity_layers.py); m: the twin's unit phasors as a function of the FP32
+    phases (the long-session cases); calm: a sea whose layer may lie below FP16's range -- no non-triviality check"""
     got = gen.velocity_map(i)
     h0, om = gen.get_spectrum(i)
     _, mod, _ = gen.get_push_constants(i)
-    want = velocity_twin(h0, om, mod)
+    want = velocity_twin(h0, om, mod, m=None if m is None else m(phases(om, mod)))
     assert np.all(got[..., 3].view(np.uint16) == 0)
     assert np.isfinite(got.astype(np.float32)).all()
-    r = H.fp16_close(got[..., :3], want.astype(np.float16), ulps=1, rel_floor=FLOOR)
+    r = H.fp16_close(got[..., :3], want.astype(np.float16), ulps=1, rel_floor=floor)
     assert r <= 1.0, (i, r)
-    assert np.abs(want).max() > 1e-3  # the layer is not trivially zero
+    assert calm or np.abs(want).max() > 1e-3  # the layer is not trivially zero
     return r
 
 
@@ -256,17 +232,26 @@ def test_layers_against_the_fp64_twin(n, count):
     assert worst <= 1.0
 
 
+def _central_difference_records():
+    from edge_presets import edge_presets
+    e = edge_presets()
+    return [cascade_preset(0), cascade_preset(1), cascade_preset(2)], [e["non_square_tile"], cascade_preset(1), e["whitecap_foam_extremes"]]
+
+
 @pytest.mark.gpu
-def test_central_difference_of_the_fp32_maps():
-    """(D(t + d) - D(t - d)) / 2d of the FP32 maps against V at t, with t and d exact in FP32; no use of the twin's algebra"""
+@pytest.mark.parametrize("records", [0, 1], ids=["presets", "off_the_square"])
+def test_central_difference_of_the_fp32_maps(records):
+    """(D(t + d) - D(t - d)) / 2d of the FP32 maps against V at t, with t and d exact in FP32; no use of the twin's algebra.
+    Second set: a non-square tile (tile_x and tile_y exchanged anywhere between the record and the kernel fails here), a preset beside it
+    and the smallest tile of the range-edge presets"""
     from godotoceanwaves_amd import WaveCascadeParameters
-    from godotoceanwaves_amd.presets import cascade_preset
+    recs = _central_difference_records()[records]
     n, ids, t, d = 256, [0, 1, 2], 8.0, 2.0 ** -9
     gen = W()
     gen.map_size = n
     gen.debug_f32 = True
     gen.init_gpu(len(ids))
-    params = [WaveCascadeParameters(**cascade_preset(ci)) for ci in ids]
+    params = [WaveCascadeParameters(**r) for r in recs]
     for p in params:
         p.time = t - 2 * d
     gen.update_all(d, params)
