@@ -27,7 +27,8 @@
 //   F_i  = (-drag.x, (density * gravity) * sv_i - drag.y, -drag.z)
 // A point is INVALID -- its record is zeros with body = -1, it contributes nothing and is counted -- when its body index is outside
 // [0, num_bodies), it lies outside the range its body names, any input of it or of its body is not finite, V_i or h_i is negative, or
-// its world position, depth or force is not finite.  No input produces NaN or Inf in any output.
+// its world position, depth or force is not finite, or its world position lies beyond what the query solves (ow_surface.h query_solve: 3e38,
+// or kCoordMax tile lengths of a cascade).  No input produces NaN or Inf in any output.
 //
 // Per body, in FP64, one 64-lane wave: lane l visits the points off + l, off + l + 64, ... of its range in sequence (indices outside
 // [0, num_points) are counted invalid and not read; records whose body is not b are counted invalid) and adds, for each valid point,
@@ -189,7 +190,7 @@ OW_DEV BuoyancyPoint buoyancy_point_in(const u16x4 *disp, int n, int cascades, c
     o.force[0] = -drag[0];
     o.force[1] = bp.rho_g * sv - drag[1];
     o.force[2] = -drag[2];
-    if (!(finite_f32(depth) && finite_f32(o.force[0]) && finite_f32(o.force[1]) && finite_f32(o.force[2]))) return invalid_point();
+    if (!(sol.finite && finite_f32(depth) && finite_f32(o.force[0]) && finite_f32(o.force[1]) && finite_f32(o.force[2]))) return invalid_point();
     o.world[0] = w[0];
     o.world[1] = w[1];
     o.world[2] = w[2];

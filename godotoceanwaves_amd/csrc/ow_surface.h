@@ -3,8 +3,8 @@
 // (query_point: the rendered vertex p + f(p) D(p) that lands on (x, z), found by damped Newton).
 //
 // Compiles as device code (ow_consumer.hip, built with -ffp-contract=off) and as plain C++ (tests/query/, g++ -ffp-contract=off), like
-// ow_device.h: every operation is an IEEE-754 FP32 add, multiply, divide or square root, a floor, a min or a compare, so both builds
-// produce the same bits.  There is no library exp(): the distance falloff uses exp_f32 below, written out in those operations.
+// ow_device.h: every operation is an IEEE-754 FP32 add, multiply, divide or square root, a floor, a min, a max or a compare, and the one
+// conversion to an integer (wrap_texel) has an operand in [0, N), so both builds produce the same bits for every input.  There is no library exp(): the distance falloff uses exp_f32 below, written out in those operations.
 #pragma once
 
 #include "ow_device.h"
@@ -54,17 +54,29 @@ struct Tap {
     float wx, wy;
 };
 
-// texel coordinates and weights of one bilinear lookup at normalised (u, v); u runs along columns
+// x0 mod N for an integer-valued x0 of any magnitude, in float: N is a power of two, so x0 / N, its floor and the product back are
+// exact, and the difference is an integer in [0, N) (0 from 2^24 N on, where every float is a multiple of N).  Equal to (int)x0 & (N - 1)
+// wherever that conversion is defined; unlike it, defined -- and the same on the device and on the host -- for every finite x0.
+OW_DEV int wrap_texel(float x0, float fn) { return (int)(x0 - fn * floorf(x0 * (1.0f / fn))); }
+
+// A normalised texture coordinate (in tiles) is used up to kCoordMax in magnitude: u N - 0.5 is then finite for every map size, so a
+// lookup never forms Inf - Inf.  sample_point clamps to it (a point further out reads texel 0 with weight 0, as every coordinate from
+// 2^24 tiles on does); query_solve treats a q beyond it like a non-finite q.
+constexpr float kCoordMax = 1.0e34f;
+OW_DEV float clamp_coord(float u) { return fminf(fmaxf(u, -kCoordMax), kCoordMax); }  // a NaN reads as -kCoordMax
+
+// texel coordinates and weights of one bilinear lookup at normalised (u, v), |u|, |v| <= kCoordMax; u runs along columns
 OW_DEV Tap make_tap(float u, float v, int n) {
-    const float fx = u * (float)n - 0.5f, fy = v * (float)n - 0.5f;
+    const float fn = (float)n;
+    const float fx = u * fn - 0.5f, fy = v * fn - 0.5f;
     const float x0 = floorf(fx), y0 = floorf(fy);
     Tap t;
     t.wx = fx - x0;
     t.wy = fy - y0;
-    const int mask = n - 1;  // N is a power of two: two's-complement AND is the positive modulus
-    t.c0 = (int)x0 & mask;
+    const int mask = n - 1;  // N is a power of two
+    t.c0 = wrap_texel(x0, fn);
     t.c1 = (t.c0 + 1) & mask;
-    t.r0 = (int)y0 & mask;
+    t.r0 = wrap_texel(y0, fn);
     t.r1 = (t.r0 + 1) & mask;
     return t;
 }
@@ -143,14 +155,17 @@ OW_DEV void bicubic(const u16x4 *layer, int n, float u, float v, float out[4]) {
     for (int k = 0; k < 4; ++k) out[k] = glsl_mix(glsl_mix(t_yw[k], t_xw[k], wgx), glsl_mix(t_yz[k], t_xz[k], wgx), wgy);
 }
 
-// One record of ow_sample_surface at world point (x, z): k_sample_surface's per-point body.
-OW_DEV SurfaceSample sample_point(const u16x4 *disp, const u16x4 *norm, int n, int cascades, const SurfaceScales &scales, float x, float z) {
+// One record of ow_sample_surface at world point (x, z).  kClamp: hold each cascade's coordinate to kCoordMax (any x and z, the entry
+// point's case); without it the caller vouches for that (query_point: the solved p, which lies beside a q that query_solve admitted).
+template <bool kClamp>
+OW_DEV SurfaceSample sample_point_in(const u16x4 *disp, const u16x4 *norm, int n, int cascades, const SurfaceScales &scales, float x, float z) {
     float dsum[3] = {0.0f, 0.0f, 0.0f}, g[2] = {0.0f, 0.0f}, gs[2] = {0.0f, 0.0f}, foam = 0.0f;
     float gf[2] = {0.0f, 0.0f}, foam_f = 0.0f;
     const size_t plane = (size_t)n * n;
     for (int c = 0; c < cascades; ++c) {
         const float sx = scales.s[c][0], sy = scales.s[c][1], sz = scales.s[c][2], sw = scales.s[c][3];
-        const Tap t = make_tap(x * sx, z * sy, n);
+        const float u = kClamp ? clamp_coord(x * sx) : x * sx, v = kClamp ? clamp_coord(z * sy) : z * sy;
+        const Tap t = make_tap(u, v, n);
         float d[4], m[4];
         bilinear(disp + c * plane, n, t, d);
         bilinear(norm + c * plane, n, t, m);
@@ -164,7 +179,7 @@ OW_DEV SurfaceSample sample_point(const u16x4 *disp, const u16x4 *norm, int n, i
             float bc[4];
             const float ppm = (float)n * fminf(sx, sy);
             const float a = fminf(1.0f, ppm * 0.1f);
-            bicubic(norm + c * plane, n, x * sx, z * sy, bc);
+            bicubic(norm + c * plane, n, u, v, bc);
             gf[0] += glsl_mix(bc[0], m[0], a) * sw;
             gf[1] += glsl_mix(bc[1], m[1], a) * sw;
             foam_f += glsl_mix(bc[3], m[3], a) * 1.0f;
@@ -192,6 +207,10 @@ OW_DEV SurfaceSample sample_point(const u16x4 *disp, const u16x4 *norm, int n, i
     s.foam_fragment = foam_f;
     s.reserved = 0.0f;
     return s;
+}
+// k_sample_surface's per-point body: finite in every field for any (x, z)
+OW_DEV SurfaceSample sample_point(const u16x4 *disp, const u16x4 *norm, int n, int cascades, const SurfaceScales &scales, float x, float z) {
+    return sample_point_in<true>(disp, norm, n, cascades, scales, x, z);
 }
 
 // ---- the inverse query: where is the water above (x, z)? ----------------------------------------------------------------------------
@@ -282,7 +301,7 @@ OW_DEV QueryEval query_eval(const u16x4 *disp, int n, int cascades, const Surfac
 // is the fixed-point step -F instead (p <- q - f(p) D(p): the Newton step with J taken as the identity, a descent direction wherever
 // the map does not fold).  Only decreases are accepted, so the iterate held is the one of smallest |F| so far; the loop ends at the
 // tolerance, after max_iterations, or when neither step decreases |F|.  converged = that |F| is within the tolerance.  A non-finite q
-// (or one beyond 3e38) gives p = (0, 0), converged = 0.
+// (or one beyond 3e38, or beyond kCoordMax tiles of a cascade) gives p = (0, 0), converged = 0: no q puts a NaN or an Inf in a record.
 //
 // On the demo scene (cascades 0-2 at 1024^2, two ticks, q uniform in [-500, 500]^2) 97.4 % of points converge to 1e-3 m with the
 // defaults, after 5.6 iterations and 7.7 evaluations of F on average (tests/test_surface_query.py); the misses sit on folded crests.
@@ -306,7 +325,7 @@ OW_DEV bool query_line_search(const u16x4 *disp, int n, int cascades, const Surf
     return false;
 }
 // The Newton loop of query_point from a given start p0 (query_point: p0 = q; the buoyancy kernel's warm start: the previous step's p
-// moved with q).  A non-finite q (or one beyond 3e38) gives p = (0, 0) and no iteration; p0 must be finite.
+// moved with q).  A non-finite q (or one beyond 3e38 or kCoordMax tiles) gives p = (0, 0) and no iteration; p0 must be finite.
 struct QuerySolution {
     float p[2];
     QueryEval e;  // F at p
@@ -315,7 +334,9 @@ struct QuerySolution {
 };
 OW_DEV QuerySolution query_solve(const u16x4 *disp, int n, int cascades, const SurfaceScales &scales, const QueryParams &qp, float qx, float qz,
                                  float p0x, float p0z) {
-    const bool finite = fabsf(qx) <= 3.0e38f && fabsf(qz) <= 3.0e38f;
+    bool finite = fabsf(qx) <= 3.0e38f && fabsf(qz) <= 3.0e38f;
+    for (int c = 0; c < cascades; ++c)  // ... or whose texture coordinate in some cascade is beyond kCoordMax
+        finite = finite && fabsf(qx * scales.s[c][0]) <= kCoordMax && fabsf(qz * scales.s[c][1]) <= kCoordMax;
     float px = finite ? p0x : 0.0f, pz = finite ? p0z : 0.0f;
     QueryEval e = query_eval(disp, n, cascades, scales, qp, px, pz, qx, qz);
     int it = 0, evals = 1;
@@ -363,7 +384,7 @@ OW_DEV SurfaceQuery query_point(const u16x4 *disp, const u16x4 *norm, int n, int
     out.evaluations = evals;
     out.converged = (finite && e.r <= qp.tolerance) ? 1 : 0;
     out.falloff = e.f;
-    out.sample = sample_point(disp, norm, n, cascades, scales, px, pz);
+    out.sample = sample_point_in<false>(disp, norm, n, cascades, scales, px, pz);
     out.height = e.f * out.sample.displacement[1];
     // water.gdshader:83,90: normalize(vec3(-gradient.x, 1, -gradient.y)) of the bilinear scaled gradient
     const float gx = out.sample.gradient_scaled[0], gz = out.sample.gradient_scaled[1];

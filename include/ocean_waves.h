@@ -370,7 +370,11 @@ typedef char ow_layout_check_surface_query[(sizeof(ow_surface_query) == 128 && o
                                             offsetof(ow_surface_query, normal) == 32 && offsetof(ow_surface_query, world_xz) == 44) ? 1 : -1];
 
 /* The query at `count` points (host pointers, as ow_sample_surface: world_xz = x0,z0,x1,z1,...; map_scales = 4 floats per cascade),
- * after everything enqueued so far.  Synchronises; a faulted batch's layers are refused as by ow_sample_surface. */
+ * after everything enqueued so far.  Synchronises; a faulted batch's layers are refused as by ow_sample_surface.
+ * Far points: no q leaves a NaN or an Inf in a record (world_xz, the echo of q, apart).  A q that is not finite, lies beyond 3e38, or
+ * lies more than 1e34 tile lengths of any cascade from the origin (where q * map_scales.xy * map_size would leave the FP32 range) gives
+ * p = (0, 0), converged = 0 and no iteration; every other q is solved, however far away.  ow_sample_surface holds each cascade's
+ * texture coordinate to +-1e34 tiles the same way and reads texel 0 there: its records are finite for every point. */
 ow_status ow_query_surface(ow_context *ctx, const float *world_xz, int32_t count, const float *map_scales, int32_t num_cascades,
                            const ow_query_options *opts, ow_surface_query *out);
 /* The same with DEVICE pointers on the context's device (world_xz_dev: 2 * count floats, out_dev: count records; map_scales and opts

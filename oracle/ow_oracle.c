@@ -501,12 +501,13 @@ void owo_generator_set_normal(owo_generator *g, int c, const uint16_t *normal) {
  * spec 8.14.2 / Vulkan spec 16.8: unnormalised coordinate u*n - 0.5, i0 = floor, weights = fract, exact FP32
  * weights -- real texture units quantise them to 8 bits, which the reference does not pin) */
 static void texture_linear_repeat(const uint16_t *layer, int n, float u, float v, float out[4]) {
-    float un = u * (float)n - 0.5f, vn = v * (float)n - 0.5f;
+    /* the repeat is taken in float: n is a power of two, so fi - n floor(fi / n) is exact for every finite fi, where a conversion to an
+     * integer type is defined only inside that type's range (csrc/ow_surface.h wrap_texel does the same) */
+    const float fn = (float)n;
+    float un = u * fn - 0.5f, vn = v * fn - 0.5f;
     float fi = floorf(un), fj = floorf(vn);
     float a = un - fi, b = vn - fj;
-    long i0 = (long)fi % n, j0 = (long)fj % n;
-    if (i0 < 0) i0 += n;
-    if (j0 < 0) j0 += n;
+    long i0 = (long)(fi - fn * floorf(fi * (1.0f / fn))), j0 = (long)(fj - fn * floorf(fj * (1.0f / fn)));
     long i1 = (i0 + 1) % n, j1 = (j0 + 1) % n;
     for (int k = 0; k < 4; ++k) {
         float t00 = owo_f16_to_f32(layer[((size_t)j0 * n + i0) * 4 + k]), t10 = owo_f16_to_f32(layer[((size_t)j0 * n + i1) * 4 + k]);
@@ -553,12 +554,15 @@ void owo_sample_surface(int n, int num_cascades, const uint16_t *displacements, 
         memset(&s, 0, sizeof(s));
         for (int i = 0; i < num_cascades; ++i) {
             const float *scales = map_scales + 4 * i;
+            /* the specifications leave a lookup at a coordinate that is not finite undefined: the coordinate is held to +-1e34 tiles (texel
+             * 0, weight 0, as from 2^24 tiles on), so that u * n stays finite (csrc/ow_surface.h clamp_coord does the same) */
+            const float u = fminf(fmaxf(x * scales[0], -1.0e34f), 1.0e34f), v = fminf(fmaxf(z * scales[1], -1.0e34f), 1.0e34f);
             float d[4], g[4];
             /* water.gdshader:33-36 and sea_spray_particle.gdshader:104-107 */
-            texture_linear_repeat(displacements + layer * i, n, x * scales[0], z * scales[1], d);
+            texture_linear_repeat(displacements + layer * i, n, u, v, d);
             for (int k = 0; k < 3; ++k) s.displacement[k] += d[k] * scales[2];
             /* sea_spray_particle.gdshader:81-82 (.xyw, unscaled); water.gdshader:81 (.xyw * vec3(scales.ww, 1)) */
-            texture_linear_repeat(normals + layer * i, n, x * scales[0], z * scales[1], g);
+            texture_linear_repeat(normals + layer * i, n, u, v, g);
             s.gradient[0] += g[0];
             s.gradient[1] += g[1];
             s.gradient_scaled[0] += g[0] * scales[3];
@@ -569,7 +573,7 @@ void owo_sample_surface(int n, int num_cascades, const uint16_t *displacements, 
                 float bc[4];
                 const float ppm = (float)n * fminf(scales[0], scales[1]);
                 const float a = fminf(1.0f, ppm * 0.1f);
-                texture_bicubic(normals + layer * i, n, x * scales[0], z * scales[1], bc);
+                texture_bicubic(normals + layer * i, n, u, v, bc);
                 s.gradient_fragment[0] += mixf(bc[0], g[0], a) * scales[3];
                 s.gradient_fragment[1] += mixf(bc[1], g[1], a) * scales[3];
                 s.foam_fragment += mixf(bc[3], g[3], a) * 1.0f;

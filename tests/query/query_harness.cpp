@@ -47,6 +47,35 @@ void harness_query(const uint16_t *disp, const uint16_t *norm, int n, int cascad
         out[i] = ow::query_point((const ow::u16x4 *)disp, (const ow::u16x4 *)norm, n, cascades, sc, qp, xz[2 * i], xz[2 * i + 1]);
 }
 
+// query_eval at count (p, q) pairs, pq = (px, pz, qx, qz) each: out = (F[2], J[2][2] row-major, f, r), eight floats per pair
+void harness_eval(const uint16_t *disp, int n, int cascades, const float *map_scales, const float *pq, int count, int falloff, float cx,
+                  float cz, float *out) {
+    const ow::SurfaceScales sc = scales_of(map_scales, cascades);
+    ow::QueryParams qp;
+    qp.max_iterations = ow::kQueryDefaultIterations;
+    qp.tolerance = ow::kQueryDefaultTolerance;
+    qp.falloff = falloff;
+    qp.center[0] = cx;
+    qp.center[1] = cz;
+    for (int i = 0; i < count; ++i) {
+        const float *a = pq + 4 * i;
+        const ow::QueryEval e = ow::query_eval((const ow::u16x4 *)disp, n, cascades, sc, qp, a[0], a[1], a[2], a[3]);
+        const float rec[8] = {e.F[0], e.F[1], e.J[0][0], e.J[0][1], e.J[1][0], e.J[1][1], e.f, e.r};
+        memcpy(out + 8 * i, rec, sizeof(rec));
+    }
+}
+
+// make_tap's integers and weights at count normalised (u, v) pairs: taps = (r0, r1, c0, c1) each, weights = (wx, wy) each
+void harness_tap(const float *uv, int count, int n, int32_t *taps, float *weights) {
+    for (int i = 0; i < count; ++i) {
+        const ow::Tap t = ow::make_tap(uv[2 * i], uv[2 * i + 1], n);
+        const int32_t v[4] = {t.r0, t.r1, t.c0, t.c1};
+        memcpy(taps + 4 * i, v, sizeof(v));
+        weights[2 * i] = t.wx;
+        weights[2 * i + 1] = t.wy;
+    }
+}
+
 void harness_exp(const float *a, int count, float *out) {
     for (int i = 0; i < count; ++i) out[i] = ow::exp_f32(a[i]);
 }

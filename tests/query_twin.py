@@ -45,20 +45,57 @@ def forward(disp, scales, p, center=None):
     return p + f[:, None] * d[:, [0, 2]], f * d[:, 1]
 
 
+def jacobian(disp, scales, p, center=None):
+    """d(p + f(p) S(p)) / dp in FP64 at the points p [P][2], S the (x, z) part of the displacement sum: (J [P][2][2] with J[:, k, j] =
+    d(forward_k) / dp_j, border [P]).  Written from water.gdshader:27-37: UV = p, each cascade reads texture(displacements, UV * scales.xy)
+    -- GL_LINEAR + GL_REPEAT, so inside the cell of texel coordinates (x, y) = UV * scales.xy * N - 0.5 the value is bilinear in the
+    fractions (wx, wy) and its derivative is that of the bilinear form times d(x, y)/dp = N * scales.xy -- times scales.z, summed, and
+    scaled by the distance factor f of :29: J = I + f dS + S (x) grad f.  The derivative jumps at a cell border; `border` is the point's
+    least distance to one, in texels, over every cascade and both axes."""
+    d = as_f64(disp)
+    sc = np.asarray(scales, np.float64)
+    p = np.asarray(p, np.float64)
+    n = d.shape[1]
+    S = np.zeros((len(p), 2))
+    dS = np.zeros((len(p), 2, 2))
+    border = np.full(len(p), 0.5)
+    for i in range(len(sc)):
+        x, y = p[:, 0] * sc[i, 0] * n - 0.5, p[:, 1] * sc[i, 1] * n - 0.5
+        x0, y0 = np.floor(x), np.floor(y)
+        wx, wy = x - x0, y - y0
+        c0, r0 = x0.astype(np.int64) % n, y0.astype(np.int64) % n
+        c1, r1 = (c0 + 1) % n, (r0 + 1) % n
+        L = d[i][..., [0, 2]]
+        a, b, c, e = L[r0, c0], L[r0, c1], L[r1, c0], L[r1, c1]
+        WX, WY = wx[:, None], wy[:, None]
+        S += ((a * (1 - WX) + b * WX) * (1 - WY) + (c * (1 - WX) + e * WX) * WY) * sc[i, 2]
+        dS[:, :, 0] += ((b - a) * (1 - WY) + (e - c) * WY) * (n * sc[i, 0] * sc[i, 2])
+        dS[:, :, 1] += ((c - a) * (1 - WX) + (e - b) * WX) * (n * sc[i, 1] * sc[i, 2])
+        border = np.minimum(border, np.minimum(np.minimum(wx, 1 - wx), np.minimum(wy, 1 - wy)))
+    f = falloff(p, center)
+    grad = np.zeros((len(p), 2))
+    if center is not None:
+        rel = p - np.asarray(center, np.float64)
+        dist = np.hypot(rel[:, 0], rel[:, 1])
+        far = dist > 150.0
+        grad[far] = (f[far] * -0.007 / dist[far])[:, None] * rel[far]
+    J = np.eye(2)[None] + f[:, None, None] * dS + S[:, :, None] * grad[:, None, :]
+    return J, border
+
+
 def min_det_on_lattice(disp, scales):
     """min over every texel corner of every cascade's cell of det(I + J), J the Jacobian of the displacement sum's (x, z) part, each
-    cascade's bilinear derivative taken on a common world lattice (the finest tile's texel spacing over the largest tile): > 0 means the
-    forward map p -> p + D_xz(p) does not fold"""
+    cascade's bilinear derivative taken on a common world lattice (per axis: the finest tile's texel spacing over the largest tile): > 0
+    means the forward map p -> p + D_xz(p) does not fold"""
     d = as_f64(disp)
     sc = np.asarray(scales, np.float64)
     n = d.shape[1]
-    span = 1.0 / sc[:, 0].min()
-    step = 1.0 / (n * sc[:, 0].max())
-    g = np.arange(0.0, span, step)
-    X, Z = np.meshgrid(g, g)
+    spans = [1.0 / sc[:, a].min() for a in (0, 1)]
+    steps = [1.0 / (n * sc[:, a].max()) for a in (0, 1)]
+    X, Z = np.meshgrid(np.arange(0.0, spans[0], steps[0]), np.arange(0.0, spans[1], steps[1]))
     p = np.stack([X.ravel(), Z.ravel()], axis=1)
-    h = 1e-3 * step
-    dx = (displacement(disp, scales, p + [h, 0]) - displacement(disp, scales, p - [h, 0])) / (2 * h)
-    dz = (displacement(disp, scales, p + [0, h]) - displacement(disp, scales, p - [0, h])) / (2 * h)
+    hx, hz = 1e-3 * steps[0], 1e-3 * steps[1]
+    dx = (displacement(disp, scales, p + [hx, 0]) - displacement(disp, scales, p - [hx, 0])) / (2 * hx)
+    dz = (displacement(disp, scales, p + [0, hz]) - displacement(disp, scales, p - [0, hz])) / (2 * hz)
     det = (1 + dx[:, 0]) * (1 + dz[:, 2]) - dz[:, 0] * dx[:, 2]
     return det.min()

@@ -42,6 +42,8 @@ def harness(tmp_path_factory):
     L.harness_sample.argtypes = [V, V, C.c_int, C.c_int, V, V, C.c_int, V]
     L.harness_query.argtypes = [V, V, C.c_int, C.c_int, V, V, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.c_float, V]
     L.harness_exp.argtypes = [V, C.c_int, V]
+    L.harness_eval.argtypes = [V, C.c_int, C.c_int, V, V, C.c_int, C.c_int, C.c_float, C.c_float, V]
+    L.harness_tap.argtypes = [V, C.c_int, C.c_int, V, V]
     return L
 
 
