@@ -27,6 +27,8 @@ OW_BUOYANCY_WARM_START = 1
 OW_BUOYANCY_WATER_VELOCITY = 2
 OW_RAY_HIT, OW_RAY_FROM_BELOW, OW_RAY_TRUNCATED, OW_RAY_INVALID = 1, 2, 4, 8
 OW_RENDER_MAX_SIDE = 8192
+OW_MESH_CULL_BACK = 1
+OW_MESH_VERTEX_NOT_FINITE = 1
 OW_OK, OW_ERR_INVALID, OW_ERR_NO_DEVICE, OW_ERR_HIP, OW_ERR_NOMEM, OW_ERR_STATE = range(6)
 
 
@@ -177,6 +179,20 @@ class ow_render_options(C.Structure):
                 ("ambient_color", C.c_float * 3), ("sky_color", C.c_float * 3), ("reserved", C.c_uint32 * 11)]
 
 
+class ow_mesh_options(C.Structure):
+    """struct ow_mesh_options (128 bytes); a NULL pointer = ow_mesh_options_default's values"""
+    _fields_ = [("query_flags", C.c_uint32), ("falloff_center_xz", C.c_float * 2), ("near", C.c_float), ("water_color", C.c_float * 3),
+                ("roughness", C.c_float), ("foam_color", C.c_float * 3), ("normal_strength", C.c_float), ("light_direction", C.c_float * 3),
+                ("flags", C.c_uint32), ("light_color", C.c_float * 3), ("ambient_color", C.c_float * 3), ("sky_color", C.c_float * 3),
+                ("lane_box", C.c_int32), ("reserved", C.c_uint32 * 6)]
+
+
+class ow_mesh_vertex(C.Structure):
+    """struct ow_mesh_vertex (48 bytes): the vertex stage's record of a mesh draw"""
+    _fields_ = [("position", C.c_float * 3), ("wave_height", C.c_float), ("uv", C.c_float * 2), ("distance_factor", C.c_float),
+                ("reserved", C.c_uint32), ("view_position", C.c_float * 3), ("flags", C.c_uint32)]
+
+
 class ow_render_pixel(C.Structure):
     """struct ow_render_pixel (128 bytes): the hit, the shader's inputs at it, fragment()'s and light()'s outputs and the composite"""
     _fields_ = [("t", C.c_float), ("status", C.c_int32), ("position", C.c_float * 3), ("p", C.c_float * 2), ("wave_height", C.c_float),
@@ -239,6 +255,15 @@ SIGNATURES = {
     "ow_render_options_default": (None, [_P(ow_render_options)]),
     "ow_render_view": (C.c_int, [C.c_void_p, _P(ow_camera), C.c_void_p, C.c_int32, _P(ow_render_options), C.c_void_p, C.c_void_p]),
     "ow_render_view_async": (C.c_int, [C.c_void_p, _P(ow_camera), C.c_void_p, C.c_int32, _P(ow_render_options), C.c_void_p, C.c_void_p]),
+    "ow_mesh_options_default": (None, [_P(ow_mesh_options)]),
+    "ow_mesh_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, _P(C.c_void_p)]),
+    "ow_mesh_destroy": (None, [C.c_void_p, C.c_void_p]),
+    "ow_mesh_displace": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, _P(ow_mesh_options), _P(ow_camera), C.c_void_p]),
+    "ow_mesh_get_device_ptrs": (C.c_int, [C.c_void_p, C.c_void_p, _P(C.c_void_p), _P(C.c_void_p)]),
+    "ow_mesh_draw": (C.c_int, [C.c_void_p, C.c_void_p, _P(ow_camera), C.c_void_p, C.c_void_p, C.c_int32, _P(ow_mesh_options), C.c_void_p, C.c_void_p]),
+    "ow_mesh_draw_async": (C.c_int, [C.c_void_p, C.c_void_p, _P(ow_camera), C.c_void_p, C.c_void_p, C.c_int32, _P(ow_mesh_options), C.c_void_p,
+                                     C.c_void_p]),
+    "ow_mesh_stats": (C.c_int, [C.c_void_p, C.c_void_p, _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64)]),
     "ow_get_maps_f32": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
     "ow_get_spectrum": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "ow_get_intermediate": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),

@@ -5,6 +5,7 @@
 #include "ow_device.h"
 #include "ow_buoyancy.h"
 #include "ow_raycast.h"
+#include "ow_mesh.h"
 #include "ow_render.h"
 #include "ow_rigid.h"
 #include "ow_surface.h"
@@ -78,6 +79,22 @@ hipError_t launch_raycast(int n, int cascades, const DeviceBuffers &buf, const R
 hipError_t launch_render_view(int n, int cascades, const DeviceBuffers &buf, const CameraParams &cam, const SurfaceScales &scales,
                               const RaycastParams &rp, const ShadeParams &sp, uint32_t *bound_dev, uint32_t *rgba_dev, RenderPixel *pixels_dev,
                               hipStream_t s);
+// a mesh draw (ow_mesh.hip; the vertex stage, the coverage rule and the per-pixel record in ow_mesh.h).  MeshArrays: a mesh's device block.
+struct MeshArrays {
+    const float *local;      // [num_vertices][3] as uploaded
+    const int32_t *indices;  // [num_triangles][3]
+    MeshVertex *verts;       // [num_vertices] the resident vertex records of the last displace / draw
+    uint32_t *counters;      // [4] triangles of the last draw by class (kTriSkipped .. kTriWave)
+    int num_vertices, num_triangles;
+};
+// k_mesh_vertices alone: the records of M.verts (view positions only with a camera)
+hipError_t launch_mesh_vertices(int n, int cascades, const DeviceBuffers &buf, const MeshArrays &M, const SurfaceScales &scales, const MeshParams &mp,
+                                const CameraParams &cam, bool has_camera, const float origin[3], hipStream_t s);
+// the whole draw: vertices, the clear of vis_dev (cam.width x cam.height words) and of the counters, raster, shade into RGBA8 words and / or
+// records (either may be null), all on `s`
+hipError_t launch_mesh_draw(int n, int cascades, const DeviceBuffers &buf, const MeshArrays &M, const SurfaceScales &scales, const MeshParams &mp,
+                            const CameraParams &cam, const ShadeParams &sp, const float origin[3], uint64_t *vis_dev, uint32_t *rgba_dev,
+                            RenderPixel *pixels_dev, hipStream_t s);
 
 bool supported_map_size(int n);
 int kernel_family(int n, int slots, int mode);  // 1 standard, 2 layer-parallel, 3 compact: what launch_pass1/2 will use

@@ -56,6 +56,14 @@ struct ow_bodies {
     uint64_t substeps = 0, fused_launches = 0, split_calls = 0;
 };
 
+// a mesh (ow_mesh_create; the entry points are further down)
+struct ow_mesh {
+    ow_context *ctx = nullptr;  // nullptr: orphaned by ow_destroy, as a body set
+    void *block = nullptr;      // one allocation: local positions, indices, vertex records, counters
+    ow::MeshArrays A{};
+    uint64_t draws = 0;
+};
+
 struct ow_context {
     int n = 0, cascades = 0, layers = 0, device = 0;
     float depth = 20.0f;
@@ -184,6 +192,9 @@ struct ow_context {
     uint32_t *render_rgba = nullptr;
     ow::RenderPixel *render_pixels = nullptr;
     size_t render_rgba_capacity = 0, render_pixels_capacity = 0;
+    // ow_mesh_draw scratch (grow-only): the visibility words; the synchronous form's RGBA8 words and records are ow_render_view's
+    uint64_t *mesh_vis = nullptr;
+    size_t mesh_vis_capacity = 0;
     // the velocity layers (ow_update_velocity; ow_velocity_kernels.h): V in the displacement array's layout, the pipeline's own intermediate
     // (vel_slots cascades of one launch pair) and twiddle table, all allocated by the first velocity call
     ow::u16x4 *vel = nullptr;
@@ -195,6 +206,7 @@ struct ow_context {
     uint32_t velocity_stale = 0, spectrum_ahead = 0;
     uint64_t vel_computed = 0, vel_skipped = 0;  // ow_velocity_stats
     std::vector<ow_bodies *> body_sets;  // the live sets of this context: ow_destroy orphans what the caller has not destroyed
+    std::vector<ow_mesh *> meshes;       // likewise the live meshes
     uint64_t host_syncs = 0;  // stream synchronisations made on the caller's thread since ow_create (ow_sync_stats)
 };
 
@@ -1180,6 +1192,11 @@ void ow_destroy(ow_context *c) {
     (void)hipSetDevice(c->device);
     if (c->side_stream) (void)hipStreamSynchronize(c->side_stream);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
+    for (ow_mesh *m : c->meshes) {
+        (void)hipFree(m->block);
+        m->block = nullptr;
+        m->ctx = nullptr;
+    }
     for (ow_bodies *set : c->body_sets) {  // sets the caller has not destroyed: their memory goes with the context, the handles stay valid to destroy
         (void)hipFree(set->block);
         set->block = nullptr;
@@ -1214,6 +1231,7 @@ void ow_destroy(ow_context *c) {
     (void)hipFree(c->ray_bound);
     (void)hipFree(c->render_rgba);
     (void)hipFree(c->render_pixels);
+    (void)hipFree(c->mesh_vis);
     (void)hipFree(c->vel);
     (void)hipFree(c->vel_scratch);
     (void)hipFree(c->vel_tw);
@@ -2774,6 +2792,276 @@ ow_status ow_render_view_async(ow_context *c, const ow_camera *camera, const flo
     // main_stream(): behind the second chain's join as well as everything on the context's (or the caller's) stream
     OW_HIP(ow::launch_render_view(c->n, num_cascades, c->buf, cp, sc, rp, sp, c->ray_bound, (uint32_t *)rgba8_dev, (ow::RenderPixel *)pixels_dev,
                                   main_stream(c)));
+    return OW_OK;
+}
+
+}  // extern "C"
+
+namespace {
+// ow_mesh_options (NULL = the defaults) -> the draw's settings and the shading's: the shared fields go through resolve_render_options
+ow_status resolve_mesh_options(const ow_mesh_options *opts, ow::MeshParams *mp, ow::ShadeParams *sp) {
+    static_assert(sizeof(ow_mesh_vertex) == sizeof(ow::MeshVertex) && offsetof(ow_mesh_vertex, uv) == offsetof(ow::MeshVertex, uv) &&
+                      offsetof(ow_mesh_vertex, distance_factor) == offsetof(ow::MeshVertex, falloff) &&
+                      offsetof(ow_mesh_vertex, view_position) == offsetof(ow::MeshVertex, view) &&
+                      offsetof(ow_mesh_vertex, flags) == offsetof(ow::MeshVertex, flags) && OW_MESH_VERTEX_NOT_FINITE == ow::kMeshVertexNotFinite,
+                  "record layout");
+    ow_render_options ro;
+    render_defaults(&ro);
+    ow_query_options qo;
+    std::memset(&qo, 0, sizeof(qo));
+    mp->near = ow::kMeshDefaultNear;
+    mp->cull_back = 0;
+    mp->lane_box = ow::kMeshLaneBox;
+    mp->camera_ok = 1;
+    if (opts) {
+        for (int k = 0; k < 3; ++k) {
+            ro.water_color[k] = opts->water_color[k];
+            ro.foam_color[k] = opts->foam_color[k];
+            ro.light_direction[k] = opts->light_direction[k];
+            ro.light_color[k] = opts->light_color[k];
+            ro.ambient_color[k] = opts->ambient_color[k];
+            ro.sky_color[k] = opts->sky_color[k];
+        }
+        ro.roughness = opts->roughness;
+        ro.normal_strength = opts->normal_strength;
+        qo.flags = opts->query_flags;
+        qo.falloff_center_xz[0] = opts->falloff_center_xz[0];
+        qo.falloff_center_xz[1] = opts->falloff_center_xz[1];
+    }
+    ow::RaycastParams unused;
+    if (ow_status st = resolve_render_options(&ro, &unused, sp); st != OW_OK) return st;
+    if (ow_status st = ow::resolve_query_options(&qo, &mp->qp); st != OW_OK) return st;
+    if (!opts) return OW_OK;
+    if (!std::isfinite(opts->near)) return fail(OW_ERR_INVALID, "near is not finite");
+    if (opts->flags & ~OW_MESH_CULL_BACK) return fail(OW_ERR_INVALID, "unknown mesh flags 0x%x", opts->flags);
+    if (opts->lane_box < -1 || opts->lane_box > 64) return fail(OW_ERR_INVALID, "lane_box %d outside [-1,64]", opts->lane_box);
+    for (uint32_t r : opts->reserved)
+        if (r != 0u) return fail(OW_ERR_INVALID, "ow_mesh_options.reserved must be 0");
+    if (opts->near > 0.0f) mp->near = opts->near;
+    mp->cull_back = (opts->flags & OW_MESH_CULL_BACK) ? 1 : 0;
+    mp->lane_box = opts->lane_box == 0 ? ow::kMeshLaneBox : (opts->lane_box < 0 ? 0 : opts->lane_box);
+    return OW_OK;
+}
+
+// ow_mesh.h's mesh_camera_ok, on the host
+bool mesh_camera_ok_host(const ow::CameraParams &cp) {
+    bool ok = std::isfinite(cp.tan_half_fov) && std::isfinite(cp.aspect) && std::isfinite(cp.max_distance) && cp.max_distance > 0.0f &&
+              cp.tan_half_fov > 0.0f && cp.aspect > 0.0f;
+    for (float v : cp.o) ok = ok && std::isfinite(v);
+    for (float v : cp.B) ok = ok && std::isfinite(v);
+    return ok;
+}
+
+ow_status check_mesh_handle(const ow_context *c, const ow_mesh *m) {
+    if (!c) return fail(OW_ERR_INVALID, "null context");
+    if (!m) return fail(OW_ERR_INVALID, "null mesh");
+    if (!m->ctx) return fail(OW_ERR_STATE, "the mesh's context has been destroyed");
+    if (m->ctx != c) return fail(OW_ERR_INVALID, "the mesh belongs to another context");
+    return OW_OK;
+}
+
+// the argument checks both forms of ow_mesh_draw share: ow_render_view's, in its order, then the mesh and the origin
+ow_status check_mesh_draw(const ow_context *c, const ow_mesh *m, const ow_camera *camera, const float *origin, const float *map_scales,
+                          int32_t num_cascades, const ow_mesh_options *opts, const void *rgba, const void *pixels, ow::CameraParams *cp,
+                          ow::MeshParams *mp, ow::ShadeParams *sp) {
+    if (!rgba && !pixels) return fail(OW_ERR_INVALID, "null argument: both outputs");
+    if (!map_scales) return fail(OW_ERR_INVALID, "null argument");
+    if (ow_status st = resolve_camera(camera, cp); st != OW_OK) return st;
+    if (ow_status st = resolve_mesh_options(opts, mp, sp); st != OW_OK) return st;
+    if (ow_status st = check_point_query(c, 0, num_cascades); st != OW_OK) return st;
+    if (ow_status st = check_mesh_handle(c, m); st != OW_OK) return st;
+    if (!origin) return fail(OW_ERR_INVALID, "null origin");
+    mp->camera_ok = mesh_camera_ok_host(*cp) ? 1 : 0;
+    return OW_OK;
+}
+
+ow_status mesh_vis_scratch(ow_context *c, size_t count) {
+    if (count <= c->mesh_vis_capacity) return OW_OK;
+    if (c->mesh_vis) {  // launches already enqueued may still read the old words
+        ++c->host_syncs;
+        OW_HIP(hipStreamSynchronize(main_stream(c)));
+    }
+    (void)hipFree(c->mesh_vis);
+    c->mesh_vis = nullptr;
+    c->mesh_vis_capacity = 0;
+    if (hipMalloc((void **)&c->mesh_vis, count * sizeof(uint64_t)) != hipSuccess) return fail(OW_ERR_NOMEM, "hipMalloc failed for %zu visibility words", count);
+    c->mesh_vis_capacity = count;
+    return OW_OK;
+}
+}  // namespace
+
+extern "C" {
+
+void ow_mesh_options_default(ow_mesh_options *out) {
+    if (!out) return;
+    ow_render_options ro;
+    render_defaults(&ro);
+    std::memset(out, 0, sizeof(*out));
+    for (int k = 0; k < 3; ++k) {
+        out->water_color[k] = ro.water_color[k];
+        out->foam_color[k] = ro.foam_color[k];
+        out->light_direction[k] = ro.light_direction[k];
+        out->light_color[k] = ro.light_color[k];
+        out->ambient_color[k] = ro.ambient_color[k];
+        out->sky_color[k] = ro.sky_color[k];
+    }
+    out->roughness = ro.roughness;
+    out->normal_strength = ro.normal_strength;
+    out->near = ow::kMeshDefaultNear;
+}
+
+ow_status ow_mesh_create(ow_context *c, const float *vertices_xyz, int32_t num_vertices, const int32_t *indices, int32_t num_triangles, ow_mesh **out) {
+    if (!out) return fail(OW_ERR_INVALID, "null argument");
+    *out = nullptr;
+    if (num_vertices < 1 || num_triangles < 1) return fail(OW_ERR_INVALID, "num_vertices and num_triangles must be >= 1");
+    if (!vertices_xyz || !indices) return fail(OW_ERR_INVALID, "null argument");
+    for (size_t i = 0; i < (size_t)num_triangles * 3; ++i)
+        if (indices[i] < 0 || indices[i] >= num_vertices)
+            return fail(OW_ERR_INVALID, "triangle %zu: index %d outside [0,%d)", i / 3, indices[i], num_vertices);
+    if (!c) return fail(OW_ERR_INVALID, "null context");
+    OW_HIP(hipSetDevice(c->device));
+    ow_mesh *m = new (std::nothrow) ow_mesh();
+    if (!m) return fail(OW_ERR_NOMEM, "out of host memory");
+    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t nv = (size_t)num_vertices, nt = (size_t)num_triangles;
+    const size_t l_bytes = up(nv * 3 * sizeof(float)), i_bytes = up(nt * 3 * sizeof(int32_t)), v_bytes = up(nv * sizeof(ow::MeshVertex));
+    const size_t total = l_bytes + i_bytes + v_bytes + 256;
+    if (hipMalloc(&m->block, total) != hipSuccess) {
+        (void)hipGetLastError();
+        delete m;
+        return fail(OW_ERR_NOMEM, "hipMalloc failed for %zu bytes of mesh", total);
+    }
+    char *base = (char *)m->block;
+    m->ctx = c;
+    m->A.local = (const float *)base;
+    m->A.indices = (const int32_t *)(base + l_bytes);
+    m->A.verts = (ow::MeshVertex *)(base + l_bytes + i_bytes);
+    m->A.counters = (uint32_t *)(base + l_bytes + i_bytes + v_bytes);
+    m->A.num_vertices = num_vertices;
+    m->A.num_triangles = num_triangles;
+    hipStream_t s = main_stream(c);
+    if (hipMemsetAsync(m->block, 0, total, s) != hipSuccess ||
+        hipMemcpyAsync((void *)m->A.local, vertices_xyz, nv * 3 * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipMemcpyAsync((void *)m->A.indices, indices, nt * 3 * sizeof(int32_t), hipMemcpyHostToDevice, s) != hipSuccess ||
+        (++c->host_syncs, hipStreamSynchronize(s)) != hipSuccess) {
+        const ow_status st = fail(OW_ERR_HIP, "mesh upload failed: %s", hipGetErrorString(hipGetLastError()));
+        (void)hipFree(m->block);
+        delete m;
+        return st;
+    }
+    c->meshes.push_back(m);
+    *out = m;
+    return OW_OK;
+}
+
+void ow_mesh_destroy(ow_context *, ow_mesh *m) {
+    if (!m) return;
+    if (ow_context *c = m->ctx) {  // its own context, still alive (ow_destroy clears this field of the meshes it outlives)
+        (void)hipSetDevice(c->device);
+        ++c->host_syncs;
+        (void)hipStreamSynchronize(main_stream(c));
+        c->meshes.erase(std::remove(c->meshes.begin(), c->meshes.end(), m), c->meshes.end());
+        (void)hipFree(m->block);
+    }
+    delete m;
+}
+
+ow_status ow_mesh_displace(ow_context *c, ow_mesh *m, const float *origin, const float *map_scales, int32_t num_cascades, const ow_mesh_options *opts,
+                           const ow_camera *camera, ow_mesh_vertex *vertices_out) {
+    if (!map_scales) return fail(OW_ERR_INVALID, "null argument");
+    ow::CameraParams cp;
+    std::memset(&cp, 0, sizeof(cp));
+    if (camera) {
+        ow_camera sized = *camera;  // the image size is not read here
+        sized.width = sized.height = 1;
+        if (ow_status st = resolve_camera(&sized, &cp); st != OW_OK) return st;
+    }
+    ow::MeshParams mp;
+    ow::ShadeParams sp;
+    if (ow_status st = resolve_mesh_options(opts, &mp, &sp); st != OW_OK) return st;
+    if (ow_status st = check_point_query(c, 0, num_cascades); st != OW_OK) return st;
+    if (ow_status st = check_mesh_handle(c, m); st != OW_OK) return st;
+    if (!origin) return fail(OW_ERR_INVALID, "null origin");
+    mp.camera_ok = camera && mesh_camera_ok_host(cp) ? 1 : 0;  // a camera that is not finite: view positions are zeros, as without one
+    OW_HIP(hipSetDevice(c->device));
+    const ow::SurfaceScales sc = surface_scales(map_scales, num_cascades);
+    OW_HIP(ow::launch_mesh_vertices(c->n, num_cascades, c->buf, m->A, sc, mp, cp, camera != nullptr, origin, main_stream(c)));
+    if (vertices_out)
+        OW_HIP(hipMemcpyAsync(vertices_out, m->A.verts, (size_t)m->A.num_vertices * sizeof(ow::MeshVertex), hipMemcpyDeviceToHost, main_stream(c)));
+    return sync_stream(c, (1u << num_cascades) - 1u);
+}
+
+ow_status ow_mesh_get_device_ptrs(ow_context *c, ow_mesh *m, void **vertices_dev, void **visibility_dev) {
+    if (ow_status st = check_mesh_handle(c, m); st != OW_OK) return st;
+    if (vertices_dev) *vertices_dev = m->A.verts;
+    if (visibility_dev) *visibility_dev = c->mesh_vis;
+    return OW_OK;
+}
+
+ow_status ow_mesh_draw(ow_context *c, ow_mesh *m, const ow_camera *camera, const float *origin, const float *map_scales, int32_t num_cascades,
+                       const ow_mesh_options *opts, void *rgba8_out, ow_render_pixel *pixels_out) {
+    ow::CameraParams cp;
+    ow::MeshParams mp;
+    ow::ShadeParams sp;
+    if (ow_status st = check_mesh_draw(c, m, camera, origin, map_scales, num_cascades, opts, rgba8_out, pixels_out, &cp, &mp, &sp); st != OW_OK) return st;
+    OW_HIP(hipSetDevice(c->device));
+    const size_t count = (size_t)cp.width * cp.height;
+    if (ow_status st = mesh_vis_scratch(c, count); st != OW_OK) return st;
+    if (rgba8_out && count > c->render_rgba_capacity) {
+        (void)hipFree(c->render_rgba);
+        c->render_rgba = nullptr;
+        c->render_rgba_capacity = 0;
+        if (hipMalloc((void **)&c->render_rgba, count * sizeof(uint32_t)) != hipSuccess) return fail(OW_ERR_NOMEM, "hipMalloc failed for %zu pixels", count);
+        c->render_rgba_capacity = count;
+    }
+    if (pixels_out && count > c->render_pixels_capacity) {
+        (void)hipFree(c->render_pixels);
+        c->render_pixels = nullptr;
+        c->render_pixels_capacity = 0;
+        if (hipMalloc((void **)&c->render_pixels, count * sizeof(ow::RenderPixel)) != hipSuccess)
+            return fail(OW_ERR_NOMEM, "hipMalloc failed for %zu pixel records", count);
+        c->render_pixels_capacity = count;
+    }
+    const ow::SurfaceScales sc = surface_scales(map_scales, num_cascades);
+    OW_HIP(ow::launch_mesh_draw(c->n, num_cascades, c->buf, m->A, sc, mp, cp, sp, origin, c->mesh_vis, rgba8_out ? c->render_rgba : nullptr,
+                                pixels_out ? c->render_pixels : nullptr, main_stream(c)));
+    ++m->draws;
+    if (rgba8_out) OW_HIP(hipMemcpyAsync(rgba8_out, c->render_rgba, count * sizeof(uint32_t), hipMemcpyDeviceToHost, main_stream(c)));
+    if (pixels_out) OW_HIP(hipMemcpyAsync(pixels_out, c->render_pixels, count * sizeof(ow::RenderPixel), hipMemcpyDeviceToHost, main_stream(c)));
+    return sync_stream(c, (1u << num_cascades) - 1u);
+}
+
+ow_status ow_mesh_draw_async(ow_context *c, ow_mesh *m, const ow_camera *camera, const float *origin, const float *map_scales, int32_t num_cascades,
+                             const ow_mesh_options *opts, void *rgba8_dev, ow_render_pixel *pixels_dev) {
+    ow::CameraParams cp;
+    ow::MeshParams mp;
+    ow::ShadeParams sp;
+    if (ow_status st = check_mesh_draw(c, m, camera, origin, map_scales, num_cascades, opts, rgba8_dev, pixels_dev, &cp, &mp, &sp); st != OW_OK) return st;
+    if (((uintptr_t)rgba8_dev & 3u) || ((uintptr_t)pixels_dev & 15u)) return fail(OW_ERR_INVALID, "rgba8_dev must be 4-byte and pixels_dev 16-byte aligned");
+    if (ow_status st = refuse_faulted(c, (1u << num_cascades) - 1u); st != OW_OK) return st;
+    OW_HIP(hipSetDevice(c->device));
+    if (ow_status st = mesh_vis_scratch(c, (size_t)cp.width * cp.height); st != OW_OK) return st;
+    const ow::SurfaceScales sc = surface_scales(map_scales, num_cascades);
+    // main_stream(): behind the second chain's join as well as everything on the context's (or the caller's) stream
+    OW_HIP(ow::launch_mesh_draw(c->n, num_cascades, c->buf, m->A, sc, mp, cp, sp, origin, c->mesh_vis, (uint32_t *)rgba8_dev, (ow::RenderPixel *)pixels_dev,
+                                main_stream(c)));
+    ++m->draws;
+    return OW_OK;
+}
+
+ow_status ow_mesh_stats(ow_context *c, ow_mesh *m, uint64_t *draws, uint64_t *skipped, uint64_t *culled, uint64_t *per_lane, uint64_t *cooperative) {
+    if (ow_status st = check_mesh_handle(c, m); st != OW_OK) return st;
+    if (skipped || culled || per_lane || cooperative) {
+        OW_HIP(hipSetDevice(c->device));
+        if (ow_status st = sync_stream(c, 0); st != OW_OK) return st;
+        uint32_t w[4] = {0, 0, 0, 0};
+        OW_HIP(hipMemcpy(w, m->A.counters, sizeof(w), hipMemcpyDeviceToHost));
+        if (skipped) *skipped = w[ow::kTriSkipped];
+        if (culled) *culled = w[ow::kTriCulled];
+        if (per_lane) *per_lane = w[ow::kTriLane];
+        if (cooperative) *cooperative = w[ow::kTriWave];
+    }
+    if (draws) *draws = m->draws;
     return OW_OK;
 }
 

@@ -85,10 +85,11 @@ constexpr float kMaskCap = 1e30f;  // stands for GLSL's +Inf in G3 / G4: 1 / (1 
 
 // water.gdshader:73-93.  `s` is the sample at the solved undisplaced point p (the shader's UV); view_x / view_z are the surface
 // position's view-space components along the camera's right and back axes; `view` is the world-space unit vector to the camera.
-OW_DEV Fragment shade_fragment(const ShadeParams &sp, const SurfaceSample &s, float view_x, float view_z, const float view[3]) {
+// This form takes the wave_height varying from the caller (ow_mesh.h: the rasteriser's interpolation of the vertex stage's values).
+OW_DEV Fragment shade_fragment(const ShadeParams &sp, const SurfaceSample &s, float wave_height, float view_x, float view_z, const float view[3]) {
     Fragment f;
     f.dist = sqrtf(view_x * view_x + view_z * view_z);                    // :74 length(VERTEX.xz), VERTEX in view space
-    f.wave_height = s.displacement[1];                                    // :38 displacement.y, before the distance factor
+    f.wave_height = wave_height;                                          // :38 displacement.y, before the distance factor
     float gx = s.gradient_fragment[0], gy = s.gradient_fragment[1];       // :76-84 gradient.xy
     const float gz = s.foam_fragment;                                     //        gradient.z
     const float u = gz * 0.75f, t = u > 0.0f ? (u < 1.0f ? u : 1.0f) : 0.0f;   // :86 smoothstep(0, 1, x): t = clamp(x, 0, 1) ...
@@ -106,6 +107,10 @@ OW_DEV Fragment shade_fragment(const ShadeParams &sp, const SurfaceSample &s, fl
     f.fresnel = glsl_mix(pow_f32(base, sp.fresnel_power) / sp.fresnel_divisor, 1.0f, 0.02f);   // :92, REFLECTANCE 0.02 (:9)
     f.roughness = (1.0f - f.fresnel) * f.foam_factor + 0.4f;              // :93
     return f;
+}
+// ... and this one from the sample at the same point: the vertex stage's displacement.y there
+OW_DEV Fragment shade_fragment(const ShadeParams &sp, const SurfaceSample &s, float view_x, float view_z, const float view[3]) {
+    return shade_fragment(sp, s, s.displacement[1], view_x, view_z, view);
 }
 
 // water.gdshader:96-100

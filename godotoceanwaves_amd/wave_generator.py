@@ -92,6 +92,13 @@ class _BodySet:
         self.handle, self.num_bodies, self.num_points = handle, num_bodies, num_points
 
 
+class _Mesh:
+    """an ow_mesh handle with the counts it was created with (WaveGenerator.mesh_create)"""
+
+    def __init__(self, handle, num_vertices, num_triangles):
+        self.handle, self.num_vertices, self.num_triangles = handle, num_vertices, num_triangles
+
+
 class WaveGenerator:
     """assets/water/wave_generator.gd.  Typical use, as in water.gd:89-91,112-114:
 
@@ -677,6 +684,116 @@ class WaveGenerator:
         o = self.render_options(options, camera)
         _lib.check(self._lib.ow_render_view_async(self.context, C.byref(camera), sc.ctypes.data, len(sc), C.byref(o) if o is not None else None,
                                                   addr(rgba_device), addr(pixels_device)))
+
+    # ---- a displaced water mesh drawn for a camera, on the device (include/ocean_waves.h ow_mesh_*) ----
+    MESH_VERTEX = np.dtype([("position", np.float32, 3), ("wave_height", np.float32), ("uv", np.float32, 2), ("distance_factor", np.float32),
+                            ("reserved", np.uint32), ("view_position", np.float32, 3), ("flags", np.uint32)])
+    _MESH_OWN = _RENDER_OWN + ("near", "cull_back", "lane_box", "falloff", "falloff_center")
+
+    @staticmethod
+    def clipmap_origin(camera_position, tile_size):
+        """main.gd:34-37: where the water mesh is put for a camera -- ceil(camera.xz / tile) * tile, y = 0 -- as float32 (x, 0, z)"""
+        xz = np.array([camera_position[0], camera_position[2]], np.float32)   # Vector3 is FP32
+        t = np.float32(tile_size)
+        out = np.ceil(xz / t) * t
+        return np.array([out[0], 0.0, out[1]], np.float32)
+
+    @classmethod
+    def mesh_options(cls, options=None, camera=None):
+        """None, an _lib.ow_mesh_options, or a dict -> ow_mesh_options, or None for the defaults.  The dict starts from
+        ow_mesh_options_default's values and may set the shading keys of render_options, near, cull_back, lane_box and falloff_center;
+        "falloff": True turns the shader's distance falloff on around the camera's x and z."""
+        if options is None or isinstance(options, _lib.ow_mesh_options):
+            return options
+        unknown = [k for k in options if k not in cls._MESH_OWN]
+        if unknown:
+            raise ValueError(f"unknown mesh options {unknown}")
+        o = _lib.ow_mesh_options()
+        _lib.load().ow_mesh_options_default(C.byref(o))
+        center = options.get("falloff_center")
+        if options.get("falloff") and center is None:
+            if camera is None:
+                raise ValueError("falloff without a falloff_center needs the camera")
+            center = (camera.position[0], camera.position[2])
+        if center is not None:
+            o.query_flags = _lib.OW_QUERY_DISTANCE_FALLOFF
+            o.falloff_center_xz[:] = [float(v) for v in center]
+        for k in cls._RENDER_OWN:
+            if k in options:
+                if k in ("roughness", "normal_strength"):
+                    setattr(o, k, float(options[k]))
+                else:
+                    getattr(o, k)[:] = [float(v) for v in options[k]]
+        if "near" in options:
+            o.near = float(options["near"])
+        if options.get("cull_back"):
+            o.flags |= _lib.OW_MESH_CULL_BACK
+        if "lane_box" in options:
+            o.lane_box = int(options["lane_box"])
+        return o
+
+    def mesh_create(self, vertices, triangles):
+        """A device-resident mesh from [V][3] local positions and [T][3] vertex indices; returns a _Mesh (mesh_destroy() it before free())"""
+        v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
+        t = np.ascontiguousarray(triangles, np.int32).reshape(-1, 3)
+        out = C.c_void_p()
+        _lib.check(self._lib.ow_mesh_create(self.context, v.ctypes.data, len(v), t.ctypes.data, len(t), C.byref(out)))
+        return _Mesh(out, len(v), len(t))
+
+    def mesh_destroy(self, mesh):
+        if mesh.handle:
+            self._lib.ow_mesh_destroy(self.context, mesh.handle)
+            mesh.handle = None
+
+    def mesh_displace(self, mesh, origin, map_scales, options=None, camera=None):
+        """The vertex stage alone: MESH_VERTEX records of every vertex (view_position only with a camera); synchronises"""
+        sc = np.ascontiguousarray(map_scales, np.float32).reshape(-1, 4)
+        org = np.ascontiguousarray(origin, np.float32).reshape(3)
+        o = self.mesh_options(options, camera)
+        out = np.zeros(mesh.num_vertices, self.MESH_VERTEX)
+        _lib.check(self._lib.ow_mesh_displace(self.context, mesh.handle, org.ctypes.data, sc.ctypes.data, len(sc), C.byref(o) if o is not None else None,
+                                              C.byref(camera) if camera is not None else None, out.ctypes.data))
+        return out
+
+    def mesh_device_ptrs(self, mesh):
+        """device addresses of the mesh's resident MESH_VERTEX records and of the context's visibility words (None before the first draw)"""
+        v, w = C.c_void_p(), C.c_void_p()
+        _lib.check(self._lib.ow_mesh_get_device_ptrs(self.context, mesh.handle, C.byref(v), C.byref(w)))
+        return v.value, w.value
+
+    def mesh_draw(self, mesh, camera, origin, map_scales, options=None, pixels=True):
+        """The mesh as an ow_camera sees it: ((H, W, 4) uint8 RGBA, (H, W) RENDER_PIXEL records or None with pixels=False), rows from the
+        top; a record's reserved[0] is the drawn triangle's index + 1."""
+        sc = np.ascontiguousarray(map_scales, np.float32).reshape(-1, 4)
+        org = np.ascontiguousarray(origin, np.float32).reshape(3)
+        o = self.mesh_options(options, camera)
+        h, w = max(int(camera.height), 0), max(int(camera.width), 0)
+        big = h > _lib.OW_RENDER_MAX_SIDE or w > _lib.OW_RENDER_MAX_SIDE   # refused by the library: do not allocate for it
+        rgba = np.zeros((1, 1, 4) if big else (h, w, 4), np.uint8)
+        rec = np.zeros((1, 1) if big else (h, w), self.RENDER_PIXEL) if pixels else None
+        _lib.check(self._lib.ow_mesh_draw(self.context, mesh.handle, C.byref(camera), org.ctypes.data, sc.ctypes.data, len(sc),
+                                          C.byref(o) if o is not None else None, rgba.ctypes.data, rec.ctypes.data if pixels else None))
+        return rgba, rec
+
+    def mesh_draw_async(self, mesh, camera, origin, map_scales, rgba_device, pixels_device=None, options=None):
+        """The draw over DEVICE buffers, enqueued in the generator's stream order without synchronising (render_view_async's buffers)"""
+        def addr(b):
+            return None if b is None else (int(b.data_ptr()) if hasattr(b, "data_ptr") else int(b))
+        count = int(camera.width) * int(camera.height)
+        for buf, size in ((rgba_device, 4), (pixels_device, self.RENDER_PIXEL.itemsize)):
+            if hasattr(buf, "numel") and hasattr(buf, "element_size") and buf.numel() * buf.element_size() < count * size:
+                raise ValueError(f"a device buffer holds fewer than {count} pixels of {size} bytes")
+        sc = np.ascontiguousarray(map_scales, np.float32).reshape(-1, 4)
+        org = np.ascontiguousarray(origin, np.float32).reshape(3)
+        o = self.mesh_options(options, camera)
+        _lib.check(self._lib.ow_mesh_draw_async(self.context, mesh.handle, C.byref(camera), org.ctypes.data, sc.ctypes.data, len(sc),
+                                                C.byref(o) if o is not None else None, addr(rgba_device), addr(pixels_device)))
+
+    def mesh_stats(self, mesh):
+        """dict of draws and, of the last draw (synchronising), the triangles skipped, culled, per_lane and cooperative"""
+        v = [C.c_uint64() for _ in range(5)]
+        _lib.check(self._lib.ow_mesh_stats(self.context, mesh.handle, *[C.byref(x) for x in v]))
+        return dict(zip(("draws", "skipped", "culled", "per_lane", "cooperative"), (x.value for x in v)))
 
     def get_push_constants(self, cascade):
         """(spectrum[16], modulate[8], unpack[4]) uint32 words: the reference's push-constant blocks of this cascade's most recent launch"""

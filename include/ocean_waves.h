@@ -757,6 +757,112 @@ ow_status ow_render_view(ow_context *ctx, const ow_camera *camera, const float *
 ow_status ow_render_view_async(ow_context *ctx, const ow_camera *camera, const float *map_scales, int32_t num_cascades,
                                const ow_render_options *opts, void *rgba8_dev, ow_render_pixel *pixels_dev);
 
+/* A displaced water mesh drawn for a camera: what the reference draws -- water.gd:8-9,46 puts a clipmap mesh on a MeshInstance3D,
+ * water.gdshader:27-39 displaces each vertex and the rasteriser interpolates UV, wave_height and VERTEX across each triangle into
+ * fragment() and light() -- where ow_render_view draws the limit surface.  The definition, independent of how it is computed:
+ *   mesh      num_vertices local positions and num_triangles index triples; origin is the node's global_position (the shader is
+ *             world_vertex_coords; no rotation, no scale)
+ *   vertex    w = local + origin, UV = w.xz, D = the bits of ow_sample_surface's displacement at UV, f = the query's distance factor
+ *             around falloff_center_xz (1 without OW_QUERY_DISTANCE_FALLOFF); position = w + D f, wave_height = D.y before the factor (:38)
+ *   coverage  pixel (i, j) of the camera looks along ow_render_view's ray through its centre (no anti-aliasing).  The triangle drawn is the
+ *             one whose displaced triangle the ray meets at the smallest view depth (the distance along the camera's -Z) inside
+ *             (near, camera.max_distance].  Edges are inclusive; a centre on an edge two triangles share goes to the lower
+ *             (depth bits, triangle index) pair and is never left uncovered.  A triangle that crosses the near plane or reaches behind
+ *             the camera is drawn exactly where this says (homogeneous edge functions, nothing is clipped or projected)
+ *   varyings  perspective-correct barycentric interpolation of UV, wave_height, the world position and the view-space position
+ *   fragment  fragment() lines 73-93 at the interpolated UV (gradient_fragment, foam_fragment of ow_sample_surface there), dist the length
+ *             of the view-space position's xz, wave_height the interpolated varying, VIEW from the interpolated position to the camera;
+ *             light() and the composite are ow_render_view's; sky_color without a hit
+ *   facing    a triangle's upper side is the one it winds counter-clockwise seen from (the OBJ convention, the upper side of the
+ *             reference's clipmap_low.obj).  Both sides are drawn; a triangle seen from its underside carries OW_RAY_FROM_BELOW next to
+ *             OW_RAY_HIT.  OW_MESH_CULL_BACK (Godot's default for this material) drops those before coverage.
+ * The camera's basis is taken as orthonormal.  Nothing returned is NaN or Inf.  The exact operations, identical in every build, are
+ * godotoceanwaves_amd/csrc/ow_mesh.h's.  There is no group form (ow_group_*) of these calls: draw on the context that holds the maps
+ * (ow_group_context of the root after a gather). */
+#define OW_MESH_CULL_BACK 1u          /* ow_mesh_options.flags */
+#define OW_MESH_VERTEX_NOT_FINITE 1u  /* ow_mesh_vertex.flags */
+typedef struct ow_mesh ow_mesh;       /* opaque; belongs to the context it was created on */
+typedef struct ow_mesh_options {
+    uint32_t query_flags;       /* OW_QUERY_DISTANCE_FALLOFF or 0 (ow_query_options.flags) */
+    float falloff_center_xz[2]; /* read with OW_QUERY_DISTANCE_FALLOFF: CAMERA_POSITION_WORLD.xz to draw as the reference does */
+    float near;                 /* the near plane's view depth, metres; <= 0 selects 0.05 (Camera3D.near) */
+    float water_color[3];       /* from here to sky_color: ow_render_options' fields, ow_render_options_default's values */
+    float roughness;
+    float foam_color[3];
+    float normal_strength;
+    float light_direction[3];
+    uint32_t flags;             /* OW_MESH_* */
+    float light_color[3];
+    float ambient_color[3];
+    float sky_color[3];
+    int32_t lane_box;           /* measurement: triangles whose pixel box is at most this many centres a side are walked by one lane,
+                                   larger ones by the wave; 0 = the default (4), -1 = every triangle by the wave, at most 64.  The
+                                   picture does not depend on it */
+    uint32_t reserved[6];       /* 0 */
+} ow_mesh_options;              /* 128 bytes; a NULL pointer = ow_mesh_options_default's values */
+/* One record per vertex, 48 bytes, 16-byte aligned on the device:
+ *   offset  0  position[3]       the displaced world position w + D f
+ *          12  wave_height       D.y before the factor
+ *          16  uv[2]             w.xz
+ *          24  distance_factor   f
+ *          28  reserved
+ *          32  view_position[3]  camera space: x right, y up, z back (zeros from ow_mesh_displace without a camera)
+ *          44  flags             OW_MESH_VERTEX_NOT_FINITE: the local position, origin or a result was not finite; the other fields are
+ *                                zeros then (distance_factor 1) and every triangle that uses the vertex is skipped */
+typedef struct ow_mesh_vertex {
+    float position[3];
+    float wave_height;
+    float uv[2];
+    float distance_factor;
+    uint32_t reserved;
+    float view_position[3];
+    uint32_t flags;
+} ow_mesh_vertex;
+typedef char ow_layout_check_mesh_options[(sizeof(ow_mesh_options) == 128 && offsetof(ow_mesh_options, water_color) == 16 &&
+                                           offsetof(ow_mesh_options, flags) == 60 && offsetof(ow_mesh_options, lane_box) == 100) ? 1 : -1];
+typedef char ow_layout_check_mesh_vertex[(sizeof(ow_mesh_vertex) == 48 && sizeof(ow_mesh_vertex) % 16 == 0 && offsetof(ow_mesh_vertex, uv) == 16 &&
+                                          offsetof(ow_mesh_vertex, view_position) == 32) ? 1 : -1];
+
+/* ow_render_options_default's material, sun, ambient and sky; no falloff, near 0.05, no flags. */
+void ow_mesh_options_default(ow_mesh_options *out);
+/* Uploads a mesh once: vertices_xyz holds num_vertices * 3 floats, indices num_triangles * 3 indices into them.  A count below 1, a null
+ * pointer or an index outside [0, num_vertices) is OW_ERR_INVALID and nothing is kept.  A vertex that is not finite is kept: the triangles
+ * that use it are skipped at draw time and counted.  Synchronises.  Destroy the mesh before its context (a mesh that outlives it can
+ * still be destroyed; every other call on it is OW_ERR_STATE). */
+ow_status ow_mesh_create(ow_context *ctx, const float *vertices_xyz, int32_t num_vertices, const int32_t *indices, int32_t num_triangles,
+                         ow_mesh **out);
+void ow_mesh_destroy(ow_context *ctx, ow_mesh *mesh);
+/* The vertex stage alone, after everything enqueued so far: the mesh's resident records are rewritten and, unless vertices_out is NULL,
+ * copied to host memory (num_vertices records).  origin: 3 floats.  camera may be NULL (view_position is zeros then; its size is not
+ * read).  Synchronises. */
+ow_status ow_mesh_displace(ow_context *ctx, ow_mesh *mesh, const float *origin, const float *map_scales, int32_t num_cascades,
+                           const ow_mesh_options *opts, const ow_camera *camera, ow_mesh_vertex *vertices_out);
+/* The device addresses of the mesh's resident vertex records (num_vertices ow_mesh_vertex, as the last ow_mesh_displace or ow_mesh_draw
+ * left them: an external rasteriser's vertex buffer, valid until ow_mesh_destroy) and of the context's visibility words (one 64-bit word
+ * per pixel of the context's last draw, row-major: (depth's FP32 bits << 32) | triangle index, all ones where nothing was drawn; NULL
+ * before the first draw, valid until a larger image is drawn).  Either output may be NULL.  Does not synchronise. */
+ow_status ow_mesh_get_device_ptrs(ow_context *ctx, ow_mesh *mesh, void **vertices_dev, void **visibility_dev);
+/* The whole draw into host memory, after everything enqueued so far.  rgba8_out: width * height * 4 bytes; pixels_out: width * height
+ * ow_render_pixel records -- t is the distance along the pixel's normalised ray, p the interpolated UV, reserved[0] the drawn triangle's
+ * index + 1 (0: none); host pointers, either may be NULL, not both.  Synchronises.  The argument checks are ow_render_view's, in its
+ * order: outputs, map_scales, camera, options (what ow_render_view refuses in the shared fields; unknown query_flags or flags, a
+ * falloff centre or near that is not finite, lane_box outside [-1, 64], reserved words not 0), then the context, the mesh and origin;
+ * OW_ERR_INVALID writes nothing.  A camera that is not finite (or whose max_distance or field of view is not positive) is not an error:
+ * every pixel is sky_color with OW_RAY_INVALID.  Faulted layers are refused as by ow_query_surface. */
+ow_status ow_mesh_draw(ow_context *ctx, ow_mesh *mesh, const ow_camera *camera, const float *origin, const float *map_scales,
+                       int32_t num_cascades, const ow_mesh_options *opts, void *rgba8_out, ow_render_pixel *pixels_out);
+/* The same with DEVICE pointers on the context's device (rgba8_dev 4-byte aligned, pixels_dev 16-byte aligned; camera, origin, map_scales
+ * and opts are host values), ordered exactly as ow_render_view_async: behind everything enqueued so far -- both chains, a caller's stream
+ * included -- and ahead of whatever the context enqueues next.  Copies nothing and does not synchronise; the only allocation is the
+ * context's grow-only visibility scratch, on first use or growth. */
+ow_status ow_mesh_draw_async(ow_context *ctx, ow_mesh *mesh, const ow_camera *camera, const float *origin, const float *map_scales,
+                             int32_t num_cascades, const ow_mesh_options *opts, void *rgba8_dev, ow_render_pixel *pixels_dev);
+/* Counters (each output may be NULL): draws enqueued on this mesh, and of its last draw the triangles skipped (a vertex not finite),
+ * culled (back-facing under OW_MESH_CULL_BACK, edge-on or of zero area, wholly outside the image, the near or the far distance), walked by
+ * their own lane and swept by the whole wave; the four add up to num_triangles.  Synchronises when one of the four is asked for. */
+ow_status ow_mesh_stats(ow_context *ctx, ow_mesh *mesh, uint64_t *draws, uint64_t *skipped, uint64_t *culled, uint64_t *per_lane,
+                        uint64_t *cooperative);
+
 /* ---- several devices: cascades sharded inside one process ---------------------------------------- */
 
 /* Cascades share nothing (wave_generator.gd:65-85 touches no state of another cascade; README.md:77-80), so a node's GPUs

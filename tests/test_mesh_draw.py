@@ -1,0 +1,813 @@
+"""A displaced water mesh drawn for a camera (include/ocean_waves.h ow_mesh_*): water.gdshader's vertex() over a caller's mesh, a
+visibility-buffer rasteriser and the existing fragment() / light() on the interpolated varyings (godotoceanwaves_amd/csrc/ow_mesh.h).
+
+CPU: the ABI and the argument checks without a device; ow_mesh.h compiled as plain C++ (tests/mesh/mesh_harness.cpp, g++
+-ffp-contract=off) held to ow_sample_surface's displacement bit for bit, to the analytic picture of a calm sea (and to ow_render_view's
+there), to an FP64 brute-force twin written from the definition (tests/mesh_twin.py) and to finite, consistent records on awkward
+inputs; the stand-alone harness runs under the sanitizers; the C example compiles.  GPU: the device's vertex records, visibility words,
+RGBA8 words and pixel records are the CPU build's bit for bit, a draw repeats to the byte, the asynchronous form is ordered like
+ow_render_view_async, and examples/mesh_host.c writes the picture the Python wrapper returns."""
+import ctypes as C
+import math
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import helpers as H
+import mesh_twin as MT
+import render_twin as RT
+from godotoceanwaves_amd import _lib, build
+from godotoceanwaves_amd.presets import UPDATE_DELTA
+from godotoceanwaves_amd.wave_generator import WaveGenerator as W
+from edge_presets import edge_presets
+from test_raycast import calm_maps
+from test_render_view import (BELOW, DEFAULTS, HIT, INVALID, camera_words, cpu_render, look, shade_words, uniforms_of,  # noqa: F401
+                              harness as render_harness)
+from test_surface_query import cpu_sample, generated_maps, gpu_maps, harness as query_harness, make_gen, maps_u16, scales_of  # noqa: F401
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "godotoceanwaves_amd", "csrc")
+PKG = os.path.join(ROOT, "godotoceanwaves_amd")
+HERE = os.path.dirname(os.path.abspath(__file__))
+HARNESS_SRC = os.path.join(HERE, "mesh", "mesh_harness.cpp")
+NEW_FUNCTIONS = ("ow_mesh_options_default", "ow_mesh_create", "ow_mesh_destroy", "ow_mesh_displace", "ow_mesh_get_device_ptrs", "ow_mesh_draw",
+                 "ow_mesh_draw_async", "ow_mesh_stats")
+PARENT_RENDER = ("ow_render_options_default", "ow_render_view", "ow_render_view_async")
+PARENT_RAYCAST = ("ow_raycast_surface", "ow_raycast_surface_async", "ow_group_raycast_surface")
+NO_TRIANGLE = np.uint64(0xFFFFFFFFFFFFFFFF)
+NEAR = 0.05
+TOL = H.TOL_F32    # 1e-4: the project's FP32 parity tolerance (test_render_view.py's shading tolerance)
+REF_BASIS = (-0.996195, -0.0151344, 0.0858316, 0.0, 0.984807, 0.173648, -0.0871557, 0.172987, -0.981061)   # main.tscn:120
+
+
+# ---- meshes and the CPU build --------------------------------------------------------------------------------------------------------
+
+def grid(cells=16, cell=4.0, y=0.0):
+    """(cells + 1)^2 vertices around the origin, two triangles a cell, counter-clockwise seen from above"""
+    half = 0.5 * cells * cell
+    c = np.arange(cells + 1, dtype=np.float32) * np.float32(cell) - np.float32(half)
+    x, z = np.meshgrid(c, c)
+    v = np.stack([x.ravel(), np.full(x.size, y, np.float32), z.ravel()], axis=1).astype(np.float32)
+    r, q = np.meshgrid(np.arange(cells), np.arange(cells), indexing="ij")
+    a = (r * (cells + 1) + q).ravel()
+    b, d, e = a + 1, a + cells + 1, a + cells + 2
+    t = np.stack([np.stack([a, d, b], 1), np.stack([b, d, e], 1)], 1).reshape(-1, 3).astype(np.int32)
+    return v, t
+
+
+def clipmap():
+    z = np.load(os.path.join(HERE, "golden", "clipmap_low_inner.npz"))
+    return z["vertices"], z["triangles"]
+
+
+@pytest.fixture(scope="module")
+def harness(tmp_path_factory):
+    so = str(tmp_path_factory.mktemp("mesh") / "libmesh_harness.so")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unknown-pragmas", "-I", CSRC, HARNESS_SRC, "-o", so], check=True)
+    L = C.CDLL(so)
+    V, I, F = C.c_void_p, C.c_int, C.c_float
+    L.harness_mesh_sizes.argtypes = [V]
+    L.harness_mesh_vertices.argtypes = [V, I, I, V, V, I, V, I, F, F, V, V]
+    L.harness_mesh_draw.argtypes = [V, V, I, I, V, V, I, V, I, V, V, I, I, V, I, F, F, F, I, I, V, V, V, V, V]
+    return L
+
+
+def center_of(options, cam):
+    o = options or {}
+    if o.get("falloff_center") is not None:
+        return tuple(o["falloff_center"])
+    return (cam.position[0], cam.position[2]) if o.get("falloff") and cam is not None else None
+
+
+def cpu_vertices(L, disp, scales, local, origin, options=None, cam=None):
+    d = maps_u16(disp)
+    sc = np.ascontiguousarray(scales, np.float32)
+    v = np.ascontiguousarray(local, np.float32).reshape(-1, 3)
+    org = np.ascontiguousarray(origin, np.float32)
+    center = center_of(options, cam)
+    cx, cz = center if center is not None else (0.0, 0.0)
+    cw = camera_words(cam) if cam is not None else None
+    out = np.zeros(len(v), W.MESH_VERTEX)
+    L.harness_mesh_vertices(d.ctypes.data, d.shape[1], len(sc), sc.ctypes.data, v.ctypes.data, len(v), org.ctypes.data, int(center is not None), cx, cz,
+                            cw.ctypes.data if cw is not None else None, out.ctypes.data)
+    return out
+
+
+def cpu_draw(L, disp, norm, scales, mesh, origin, cam, options=None):
+    """the CPU build's draw: dict of vertices, vis [H][W] uint64, rgba [H][W][4], rec [H][W], counters (skipped, culled, per_lane, cooperative)"""
+    o = options or {}
+    d, m = maps_u16(disp), maps_u16(norm)
+    sc = np.ascontiguousarray(scales, np.float32)
+    v = np.ascontiguousarray(mesh[0], np.float32).reshape(-1, 3)
+    t = np.ascontiguousarray(mesh[1], np.int32).reshape(-1, 3)
+    org = np.ascontiguousarray(origin, np.float32)
+    center = center_of(o, cam)
+    cx, cz = center if center is not None else (0.0, 0.0)
+    cw, sw = camera_words(cam), shade_words(o)
+    out = dict(vertices=np.zeros(len(v), W.MESH_VERTEX), vis=np.zeros((cam.height, cam.width), np.uint64),
+               rgba=np.zeros((cam.height, cam.width, 4), np.uint8), rec=np.zeros((cam.height, cam.width), W.RENDER_PIXEL), counters=np.zeros(4, np.uint32))
+    L.harness_mesh_draw(d.ctypes.data, m.ctypes.data, d.shape[1], len(sc), sc.ctypes.data, v.ctypes.data, len(v), t.ctypes.data, len(t), org.ctypes.data,
+                        cw.ctypes.data, cam.width, cam.height, sw.ctypes.data, int(center is not None), cx, cz, float(o.get("near", 0.0)),
+                        int(bool(o.get("cull_back"))), int(o.get("lane_box", 0)), out["vertices"].ctypes.data, out["vis"].ctypes.data,
+                        out["rgba"].ctypes.data, out["rec"].ctypes.data, out["counters"].ctypes.data)
+    return out
+
+
+def check_picture(pic, num_triangles, options=None):
+    """test_render_view.py's check_composite rules -- finite records, sky and zeros without a hit, the composite, the RGBA8 rule -- with
+    reserved[0] the triangle's index + 1, and the counters adding up"""
+    rgba, rec, vis = pic["rgba"], pic["rec"], pic["vis"]
+    for f in W.RENDER_PIXEL.names:
+        if f not in ("status", "reserved"):
+            assert np.isfinite(rec[f]).all(), f
+    hit = (rec["status"] & HIT) != 0
+    o = dict(DEFAULTS, **{k: v for k, v in (options or {}).items() if k in DEFAULTS})
+    sky, amb = np.asarray(o["sky_color"], np.float32), np.asarray(o["ambient_color"], np.float32)
+    assert (rec["color"][~hit] == sky).all()
+    zeroed = rec[~hit].copy()
+    zeroed["status"] = 0
+    zeroed["color"] = 0
+    assert not zeroed.tobytes().strip(b"\0")
+    want = rec["albedo"] * (rec["diffuse"] + amb) + rec["specular"][..., None]
+    assert np.array_equal(rec["color"][hit], want[hit])
+    assert np.array_equal(rgba, RT.rgba8(rec["color"]))
+    assert not rec["reserved"][..., 1:].any()
+    assert np.array_equal(hit, vis != NO_TRIANGLE)
+    assert np.array_equal(rec["reserved"][..., 0][hit], (vis[hit] & np.uint64(0xFFFFFFFF)).astype(np.uint32) + 1) and not rec["reserved"][..., 0][~hit].any()
+    assert (rec["reserved"][..., 0] <= num_triangles).all()
+    assert int(pic["counters"].sum()) == num_triangles, pic["counters"]
+    return hit
+
+
+@pytest.fixture(scope="module")
+def oracle_maps():
+    return generated_maps(128, [0, 1, 2])
+
+
+# ---- 1. the ABI ----------------------------------------------------------------------------------------------------------------------
+
+HEADER = open(os.path.join(ROOT, "include", "ocean_waves.h")).read()
+
+
+def test_header_declares_the_mesh_calls_and_the_library_exports_them():
+    build.build_library()
+    lib = _lib.load()
+    text = re.sub(r"/\*.*?\*/", "", HEADER, flags=re.S)
+    for name in NEW_FUNCTIONS:
+        assert re.search(r"\b%s\s*\(" % name, text), name
+        assert name in _lib.SIGNATURES
+        assert getattr(lib, name)
+    for struct in ("ow_mesh_options", "ow_mesh_vertex"):
+        assert re.search(r"typedef struct %s \{" % struct, text), struct
+    assert re.search(r"#define OW_MESH_CULL_BACK %du\b" % _lib.OW_MESH_CULL_BACK, HEADER)
+    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    exported = set(re.findall(r" T (ow_[a-z0-9_]+)", out))
+    assert set(NEW_FUNCTIONS) <= exported
+    assert sorted(s for s in exported if "mesh" in s) == sorted(NEW_FUNCTIONS)
+    assert sorted(s for s in exported if "render" in s) == sorted(PARENT_RENDER)      # the names other tests pin are the parent's
+    assert sorted(s for s in exported if "raycast" in s) == sorted(PARENT_RAYCAST)
+    assert "no group form" in HEADER.split("ow_mesh_options_default")[0].split("A displaced water mesh drawn for a camera")[1]
+    assert lib.ow_abi_version() == 4 and re.search(r"#define OW_ABI_VERSION 4\b", HEADER)
+    o = _lib.ow_mesh_options()
+    lib.ow_mesh_options_default(C.byref(o))
+    for k, v in DEFAULTS.items():
+        got = getattr(o, k)
+        assert np.array_equal(np.float32(v), np.float32(got if np.ndim(v) == 0 else list(got))), k
+    assert o.flags == 0 and o.query_flags == 0 and o.lane_box == 0 and not any(o.reserved) and o.near == np.float32(NEAR)
+
+
+def test_mesh_structs_agree_in_c_ctypes_numpy_and_the_harness(tmp_path, harness):
+    fields = [("ow_mesh_options", f) for f, _ in _lib.ow_mesh_options._fields_] + [("ow_mesh_vertex", f) for f in W.MESH_VERTEX.names]
+    names = ("ow_mesh_options", "ow_mesh_vertex")
+    expr = ", ".join(["sizeof(%s)" % s for s in names] + ["offsetof(%s, %s)" % f for f in fields])
+    src = ('#include <stdio.h>\n#include <stddef.h>\n#include "ocean_waves.h"\nint main(void){printf("%s\\n", ' % " ".join(["%zu"] * (2 + len(fields)))
+           + expr + ");return 0;}\n")
+    exe = str(tmp_path / "mesh_layout")
+    subprocess.run(["gcc", "-std=c11", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-x", "c", "-", "-o", exe], input=src, text=True, check=True)
+    got = [int(v) for v in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split()]
+    ctypes_of = {"ow_mesh_options": _lib.ow_mesh_options, "ow_mesh_vertex": _lib.ow_mesh_vertex}
+    want = [C.sizeof(ctypes_of[s]) for s in names] + [getattr(ctypes_of[s], f).offset for s, f in fields]
+    assert got == want
+    assert got[:2] == [128, 48] and 48 % 16 == 0
+    vx = dict((f, o) for (s, f), o in zip(fields, got[2:]) if s == "ow_mesh_vertex")
+    assert [W.MESH_VERTEX.fields[f][1] for f in W.MESH_VERTEX.names] == [vx[f] for f in W.MESH_VERTEX.names] and W.MESH_VERTEX.itemsize == 48
+    sizes = (C.c_int * 8)()
+    harness.harness_mesh_sizes(sizes)
+    assert list(sizes) == [48, vx["wave_height"], vx["uv"], vx["distance_factor"], vx["view_position"], vx["flags"], 9 * 4, 128]
+
+
+def test_the_csharp_binding_and_the_index_show_the_mesh_calls():
+    import test_integration_shim as S
+    for name in NEW_FUNCTIONS:
+        assert re.search(r"\[DllImport\(Lib\)\]\s*public static extern \w+ %s\(" % name, S.SHIM), name
+        assert "`%s`" % name in S.DOC.split("## 7. Index")[1], name
+    for cs, c, size in (("OwMeshOptions", "ow_mesh_options", 128), ("OwMeshVertex", "ow_mesh_vertex", 48)):
+        want, got = S.c_struct_fields(c), S.cs_struct_fields(cs)
+        assert got == want, (cs, got, want)
+        assert sum(s for _, s in want) == size
+
+
+def test_mesh_argument_errors_without_a_device():
+    lib = _lib.load()
+    sc = np.ones((1, 4), np.float32)
+    rgba = np.zeros((12, 20, 4), np.uint8)
+    rec = np.zeros((12, 20), W.RENDER_PIXEL)
+    org = np.zeros(3, np.float32)
+    fake = C.c_void_p(16)   # never read: every case fails before the mesh is looked at
+
+    def both(cam, opts, rgba_p=rgba.ctypes.data, rec_p=rec.ctypes.data, scales=sc.ctypes.data):
+        out = []
+        for fn in (lib.ow_mesh_draw, lib.ow_mesh_draw_async):
+            assert fn(None, fake, C.byref(cam) if cam is not None else None, org.ctypes.data, scales, 1, C.byref(opts) if opts is not None else None,
+                      rgba_p, rec_p) == _lib.OW_ERR_INVALID
+            out.append(lib.ow_last_error().decode())
+        assert out[0] == out[1]
+        return out[0]
+
+    good = look((0, 10, 0), 0, -10)
+    opt = lambda **kw: W.mesh_options(kw)   # noqa: E731
+    assert "null context" in both(good, None)                                  # everything else is in order: only the context is missing
+    assert "null context" in both(good, opt(roughness=0.0, near=2.0, cull_back=True, lane_box=-1))
+    assert "both outputs" in both(good, None, None, None)
+    assert "null argument" in both(good, None, scales=None)
+    assert "null camera" in both(None, None)
+    for w, h in ((0, 12), (20, 0), (_lib.OW_RENDER_MAX_SIDE + 1, 12)):
+        assert "camera size" in both(look((0, 10, 0), 0, -10, width=w, height=h), None)
+    cam = look((0, 10, 0), 0, -10)
+    cam.reserved[3] = 1
+    assert "ow_camera.reserved" in both(cam, None)
+    for k in ("water_color", "foam_color", "light_direction", "light_color", "ambient_color", "sky_color"):
+        assert "not finite" in both(good, opt(**{k: (0.5, float("nan"), 0.5)})), k
+    for bad in (-0.01, 1.01, float("nan")):
+        assert "roughness" in both(good, opt(roughness=bad))
+        assert "normal_strength" in both(good, opt(normal_strength=bad))
+    assert "zero length" in both(good, opt(light_direction=(0.0, 0.0, 0.0)))
+    assert "near" in both(good, opt(near=float("nan")))
+    assert "lane_box" in both(good, opt(lane_box=65))
+    assert "finite" in both(good, opt(falloff_center=(float("inf"), 0.0)))
+    o = opt()
+    o.flags = 2
+    assert "mesh flags" in both(good, o)
+    o = opt()
+    o.query_flags = 4
+    assert "query flags" in both(good, o)
+    o = opt()
+    o.reserved[5] = 7
+    assert "ow_mesh_options.reserved" in both(good, o)
+    assert not rgba.any() and not rec.tobytes().strip(b"\0")
+    # create and displace
+    out = C.c_void_p(5)
+    v, t = grid(2)
+    assert lib.ow_mesh_create(None, v.ctypes.data, 0, t.ctypes.data, len(t), C.byref(out)) == _lib.OW_ERR_INVALID and out.value is None
+    assert lib.ow_mesh_create(None, v.ctypes.data, len(v), t.ctypes.data, 0, C.byref(out)) == _lib.OW_ERR_INVALID
+    bad = t.copy()
+    bad[3, 1] = len(v)
+    assert lib.ow_mesh_create(None, v.ctypes.data, len(v), bad.ctypes.data, len(t), C.byref(out)) == _lib.OW_ERR_INVALID
+    assert "index" in lib.ow_last_error().decode()
+    bad[3, 1] = -1
+    assert lib.ow_mesh_create(None, v.ctypes.data, len(v), bad.ctypes.data, len(t), C.byref(out)) == _lib.OW_ERR_INVALID
+    assert lib.ow_mesh_create(None, v.ctypes.data, len(v), t.ctypes.data, len(t), C.byref(out)) == _lib.OW_ERR_INVALID
+    assert "null context" in lib.ow_last_error().decode()
+    assert lib.ow_mesh_displace(None, fake, org.ctypes.data, sc.ctypes.data, 1, None, None, None) == _lib.OW_ERR_INVALID
+    assert lib.ow_mesh_stats(None, fake, None, None, None, None, None) == _lib.OW_ERR_INVALID
+    lib.ow_mesh_destroy(None, None)
+    with pytest.raises(ValueError):
+        W.mesh_options({"spacing": 1.0})
+    with pytest.raises(ValueError):
+        W.mesh_options({"falloff": True})
+    o = W.mesh_options({"falloff": True, "roughness": 0.4, "cull_back": True}, look((3, 10, -7), 0, -10))
+    assert (o.query_flags, tuple(o.falloff_center_xz), o.flags) == (_lib.OW_QUERY_DISTANCE_FALLOFF, (3.0, -7.0), _lib.OW_MESH_CULL_BACK)
+
+
+# ---- 2. the vertex stage ---------------------------------------------------------------------------------------------------------------
+
+def test_vertex_stage_is_the_sampled_displacement_bit_for_bit(harness, query_harness, oracle_maps):
+    """wave_height is ow_sample_surface's displacement.y at UV to the bit, and so are D.x and D.z: without the factor the position is
+    fl(w + D), formed here from the sample's own D.  The factor is falloff_at's bits (exp_f32 of the same FP32 argument).  With it
+    position = fl(w + fl(D f)): three roundings against the FP64 value of w + D f -- half an ulp of D f, half an ulp of the sum, and f's own
+    error is not one (the record's f is the input) -- so |error| <= ulp(D f) / 2 + ulp(w + D f) / 2, asserted as one ulp of the larger."""
+    d, m, _ = oracle_maps
+    square = np.array([(1 / 88.0, 1 / 88.0, 1.0, 1.0), (1 / 57.0, 1 / 57.0, 1.3, 1.0), (1 / 16.0, 1 / 16.0, 0.9, 1.0)], np.float32)
+    tl = edge_presets()["non_square_tile"]["tile_length"]
+    odd = np.array([(1 / tl[0], 1 / tl[1], 1.0, 1.0), (1 / 57.0, 1 / 31.0, 1.3, 1.0), (1 / 16.0, 1 / 9.0, 0.9, 1.0)], np.float32)
+    rng = np.random.default_rng(7)
+    local = np.zeros((4000, 3), np.float32)
+    local[:, [0, 2]] = rng.uniform(-400, 400, (4000, 2))
+    local[:, 1] = rng.uniform(-1, 1, 4000)
+    seams = np.array([(0, 0, 0), (88, 0, 33), (-88, 0, 66), (176, 0, -33), (57, 0, 31), (16, 0, 9), (44, 0, 16.5), (1e6, 0, -1e6), (-1e6, 0.5, 1e6),
+                      (1e6, 0, 0), (88.0 * 3, 0, 57.0 * 2)], np.float32)
+    local = np.concatenate([local, seams])
+    for sc in (square, odd):
+        for origin in ((0.0, 0.0, 0.0), (12.0, 0.25, -8.0)):
+            org = np.float32(origin)
+            w = local + org
+            s = cpu_sample(query_harness, d, m, sc, w[:, [0, 2]])
+            D = s["displacement"]
+            rec = cpu_vertices(harness, d, sc, local, org)
+            assert not rec["flags"].any() and not rec["reserved"].any() and not rec["view_position"].any()
+            assert rec["wave_height"].tobytes() == D[:, 1].tobytes()
+            assert rec["uv"].tobytes() == w[:, [0, 2]].tobytes()
+            assert rec["position"].tobytes() == (w + D).astype(np.float32).tobytes()
+            assert (rec["distance_factor"] == 1).all()
+            # the factor around a centre
+            center = (30.0, -20.0)
+            rec = cpu_vertices(harness, d, sc, local, org, {"falloff_center": center})
+            dx, dz = w[:, 0] - np.float32(center[0]), w[:, 2] - np.float32(center[1])
+            dist = np.sqrt(dx * dx + dz * dz)
+            a = (-(dist - np.float32(150.0)) * np.float32(0.007)).astype(np.float32)
+            f = np.zeros(len(a), np.float32)
+            query_harness.harness_exp(a.ctypes.data, len(a), f.ctypes.data)
+            f = np.where(a < 0, f, np.float32(1.0)).astype(np.float32)
+            assert rec["distance_factor"].tobytes() == f.tobytes() and (f < 1).any() and (f == 1).any()
+            assert rec["wave_height"].tobytes() == D[:, 1].tobytes()
+            exact = w.astype(np.float64) + D.astype(np.float64) * f.astype(np.float64)[:, None]
+            ulp = np.maximum(np.spacing(np.abs(exact).astype(np.float32)), np.spacing(np.abs(D * f[:, None]).astype(np.float32))).astype(np.float64)
+            assert (np.abs(rec["position"].astype(np.float64) - exact) <= ulp).all()
+    # a camera gives the view-space position: B^T (position - camera), a few ulp of the distance
+    cam = look((3.0, 10.0, -4.0), 20.0, -10.0)
+    rec = cpu_vertices(harness, d, square, local[:4000], (0, 0, 0), None, cam)
+    B = np.asarray(list(cam.basis), np.float64).reshape(3, 3)
+    rel = rec["position"].astype(np.float64) - np.asarray(list(cam.position), np.float64)
+    assert np.abs(rec["view_position"] - rel @ B).max() <= 1e-6 * np.abs(rel).max()
+    # a vertex that is not finite is flagged and its record is zeros
+    bad = np.array([(np.nan, 0, 0), (0, np.inf, 0), (0, 0, -np.inf), (1, 2, 3)], np.float32)
+    rec = cpu_vertices(harness, d, square, bad, (0, 0, 0))
+    assert list(rec["flags"]) == [1, 1, 1, 0] and not rec["position"][:3].any() and np.isfinite(rec["wave_height"]).all()
+
+
+def test_clipmap_origin_is_main_gds_rule():
+    """main.gd:34-37: (camera.xz / tile).ceil() * tile, y = 0"""
+    for tile in (1.0, 4.0):
+        for cam, want in (((0.3, 10.0, 7.9), (math.ceil(0.3 / tile) * tile, math.ceil(7.9 / tile) * tile)),
+                          ((-0.3, 2.0, -7.9), (math.ceil(-0.3 / tile) * tile, math.ceil(-7.9 / tile) * tile)),
+                          ((8.0, 0.0, -12.0), (8.0, -12.0)), ((0.0, 5.0, 0.0), (0.0, 0.0)), ((1234.5, 1.0, -4321.25), None)):
+            got = W.clipmap_origin(cam, tile)
+            if want is None:
+                want = (math.ceil(cam[0] / tile) * tile, math.ceil(cam[2] / tile) * tile)
+            assert got.dtype == np.float32 and tuple(got) == (want[0], 0.0, want[1]), (tile, cam, got)
+            assert got[0] >= cam[0] and got[0] - cam[0] < tile and got[2] >= cam[2] and got[2] - cam[2] < tile
+    assert tuple(W.clipmap_origin((-0.3, 0, -3.9), 4.0)) == (0.0, 0.0, 0.0) and tuple(W.clipmap_origin((4.0, 0, -4.0), 4.0)) == (4.0, 0.0, -4.0)
+
+
+# ---- 3. a calm sea -----------------------------------------------------------------------------------------------------------------------
+
+def grid_with_a_fan():
+    """the 17 x 17 grid with one cell drawn as a pentagon: an extra vertex in the middle of an edge, fanned from the cell's first corner, so
+    that one of its triangles has zero area and its neighbour keeps the long edge (a T-junction, as at the clipmap's ring transitions)"""
+    v, t = grid()
+    cell = 8 * 16 + 5
+    a, d, b = t[2 * cell]
+    e = t[2 * cell + 1][2]
+    mid = len(v)
+    v = np.concatenate([v, [(v[a] + v[d]) / 2]]).astype(np.float32)
+    fan = np.array([(a, mid, d), (a, d, e), (a, e, b), (a, a, mid)], np.int32)   # (a, mid, d) is collinear; (a, a, mid) has two equal corners
+    return v, np.concatenate([t[:2 * cell], t[2 * cell + 2:], fan]).astype(np.int32)
+
+
+CALM_CAMERAS = {
+    "down": (dict(position=(1.0, 20.0, -2.0), yaw_deg=0.0, pitch_deg=-89.9, max_distance=200.0), {}),
+    "pitched": (dict(position=(0.0, 12.0, -20.0), yaw_deg=10.0, pitch_deg=-25.0, max_distance=40.0), {}),
+    "near_plane": (dict(position=(0.3, 0.5, 0.2), yaw_deg=30.0, pitch_deg=0.0, max_distance=200.0), {}),
+    "near_plane_far_cut": (dict(position=(0.3, 0.5, 0.2), yaw_deg=30.0, pitch_deg=0.0, max_distance=25.0), {"near": 3.0}),
+}
+
+
+@pytest.mark.parametrize("name", list(CALM_CAMERAS))
+def test_calm_sea_is_the_analytic_plane(harness, render_harness, name):
+    """Zero maps: the mesh is the square |x|, |z| <= 32 of the plane y = 0.  A pixel has a hit exactly when its ray meets the plane inside
+    the square at a view depth in (near, max_distance] (pixels whose ray passes within 1e-4 m of one of those limits are not asked);
+    t, position and p are the analytic ones to 1e-5; where ow_render_view hits too, its t and colour are the same to 1e-4."""
+    d, m, sc = calm_maps()
+    kw, opts = CALM_CAMERAS[name]
+    cam = look(width=64, height=40, **kw)
+    near = opts.get("near", NEAR)
+    mesh = grid_with_a_fan()
+    pic = cpu_draw(harness, d, m, sc, mesh, (0, 0, 0), cam, opts)
+    hit = check_picture(pic, len(mesh[1]), opts)
+    rec = pic["rec"]
+    o = np.asarray(list(cam.position), np.float64)
+    dirs = RT.pixel_directions(list(cam.basis), cam.fov_y_degrees, cam.width, cam.height)
+    fwd = -np.asarray(list(cam.basis), np.float64).reshape(3, 3)[:, 2]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        t = np.where(dirs[..., 1] < 0, -o[1] / dirs[..., 1], np.inf)
+        pos = o + t[..., None] * dirs
+        depth = t * (dirs @ fwd)
+    finite = np.isfinite(t)
+    margin = np.where(finite, np.minimum.reduce([32 - np.abs(pos[..., 0]), 32 - np.abs(pos[..., 2]), depth - near, cam.max_distance - depth]), -1.0)
+    asked = ~finite | (np.abs(margin) > 1e-4)
+    want = finite & (margin > 0)
+    assert np.array_equal(hit[asked], want[asked]) and want.any() and asked.mean() > 0.98
+    both = hit & want
+    rel = lambda got, ref: np.abs(got - ref) / np.maximum(1.0, np.abs(ref))   # noqa: E731
+    assert rel(rec["t"][both], t[both]).max() <= 1e-5
+    assert rel(rec["position"][both], pos[both]).max() <= 1e-5 and rel(rec["p"][both], pos[both][:, [0, 2]]).max() <= 1e-5
+    assert (rec["wave_height"][hit] == 0).all() and (rec["normal"][hit] == np.float32((0, 1, 0))).all() and (rec["status"][hit] == HIT).all()
+    vis_depth = (pic["vis"][hit] >> np.uint64(32)).astype(np.uint32).view(np.float32)
+    assert (vis_depth > near).all() and (vis_depth <= cam.max_distance).all()      # nothing before near or beyond max_distance
+    if name == "near_plane":
+        v = pic["vertices"]["view_position"][mesh[1]]
+        assert ((-v[..., 2] < near).any(axis=1) & (-v[..., 2] > near).any(axis=1)).any()   # triangles cross the near plane ...
+        assert (-v[..., 2] < 0).all(axis=1).any()                                            # ... and lie behind the camera
+    # ow_render_view on the same sea (its max_distance runs along the ray: given room, it does not cut first)
+    far = look(width=64, height=40, **dict(kw, max_distance=1e4))
+    _, view = cpu_render(render_harness, d, m, sc, far)
+    same = hit & ((view["status"] & HIT) != 0)
+    assert same.sum() > 0.5 * hit.sum()
+    assert rel(rec["t"][same], view["t"][same].astype(np.float64)).max() <= 1e-4
+    assert np.abs(rec["color"][same] - view["color"][same]).max() <= 1e-4
+
+
+# ---- 4. the FP64 twin --------------------------------------------------------------------------------------------------------------------
+
+TWIN_CAM = dict(position=(2.0, 9.0, -30.0), yaw_deg=8.0, pitch_deg=-22.0, width=64, height=40, max_distance=500.0)
+MARGINS = {}
+
+
+def compare_with_twin(pic, mesh, cam, options, near=NEAR):
+    """the picture against mesh_twin.draw on the picture's own vertex records; returns (share set aside, largest differences)"""
+    o = options or {}
+    twin = MT.draw(pic["vertices"], mesh[1], list(cam.position), list(cam.basis), cam.fov_y_degrees, cam.width, cam.height, near, cam.max_distance,
+                   bool(o.get("cull_back")))
+    rec = pic["rec"]
+    hit = (rec["status"] & HIT) != 0
+    clear = twin["hit"] & (twin["min_bary"] >= 1e-3) & (twin["gap"] >= 1e-3)
+    aside = 1.0 - clear.sum() / max(int(twin["hit"].sum()), 1)
+    assert hit[clear].all()
+    assert np.array_equal(rec["reserved"][..., 0][clear].astype(np.int64) - 1, twin["tri"][clear])
+    assert np.array_equal((rec["status"][clear] & BELOW) != 0, twin["below"][clear])
+    worst = {}
+    for k, ref in (("p", twin["uv"]), ("wave_height", twin["wave_height"]), ("t", twin["t"]), ("position", twin["position"])):
+        err = np.abs(rec[k][clear].astype(np.float64) - ref[clear]) / np.maximum(1.0, np.abs(ref[clear]))
+        worst[k] = float(err.max())
+    r = rec[hit]
+    shade = RT.shade(r["gradient_fragment"], r["foam_fragment"], r["wave_height"], r["position"], list(cam.position), list(cam.basis), uniforms_of(o))
+    for k in ("dist", "foam_factor", "albedo", "normal", "fresnel", "roughness", "color", "diffuse", "specular"):
+        err = np.abs(r[k].astype(np.float64) - shade[k])
+        if k in ("diffuse", "specular", "dist"):
+            err = err / np.maximum(1.0, np.abs(shade[k]))
+        worst[k] = float(err.max())
+    return aside, worst
+
+
+@pytest.mark.parametrize("falloff", [False, True], ids=["no_falloff", "falloff"])
+def test_picture_against_the_fp64_twin(harness, query_harness, oracle_maps, falloff):
+    """The 17 x 17 grid on oracle maps, 64 x 40.  The triangle agrees on every pixel the twin calls unambiguous (smallest barycentric
+    >= 1e-3, next-nearest hit >= 1e-3 m deeper); the twin sets aside 0.86 % of its hit pixels on this camera and grid without the falloff
+    and 0.49 % with it (measured on the CPU build; the condition asserted is at most 5 %).  On the agreeing pixels p, wave_height, t and position are within
+    1e-4 max(1, |value|); the shading fields against render_twin's FP64 shading of the record's own inputs at 1e-4.  The largest
+    differences measured are in profiles/mesh_margins.txt.  gradient_fragment and foam_fragment are ow_sample_surface's at p, bit for bit."""
+    d, m, sc = oracle_maps
+    cam = look(**TWIN_CAM)
+    opts = {"falloff_center": (0.0, -200.0), "roughness": 0.4} if falloff else {}   # the centre is far enough for f < 1 on the grid
+    mesh = grid()
+    pic = cpu_draw(harness, d, m, sc, mesh, (1.0, 0.0, 2.0), cam, opts)
+    hit = check_picture(pic, len(mesh[1]), opts)
+    assert hit.mean() > 0.3 and (not falloff or (pic["vertices"]["distance_factor"] < 1).all())
+    aside, worst = compare_with_twin(pic, mesh, cam, opts)
+    MARGINS["falloff" if falloff else "no_falloff"] = (aside, worst)
+    print(f"twin set aside {aside:.4f} of its hit pixels; largest differences " + ", ".join(f"{k} {v:.2e}" for k, v in worst.items()))
+    assert aside <= 0.05
+    for k, v in worst.items():
+        assert v <= TOL, (k, v)
+    r = pic["rec"][hit]
+    s = cpu_sample(query_harness, d, m, sc, r["p"])
+    assert r["gradient_fragment"].tobytes() == s["gradient_fragment"].tobytes() and r["foam_fragment"].tobytes() == s["foam_fragment"].tobytes()
+    # the picture does not depend on which raster path a triangle takes
+    for lane_box in (-1, 1, 64):
+        other = cpu_draw(harness, d, m, sc, mesh, (1.0, 0.0, 2.0), cam, dict(opts, lane_box=lane_box))
+        assert other["vis"].tobytes() == pic["vis"].tobytes() and other["rec"].tobytes() == pic["rec"].tobytes()
+        assert other["counters"][2:].sum() == pic["counters"][2:].sum()
+
+
+# ---- 5. awkward inputs -------------------------------------------------------------------------------------------------------------------
+
+def test_awkward_inputs_give_finite_consistent_pictures(harness, oracle_maps):
+    d, m, sc = oracle_maps
+    calm = calm_maps()
+    over = look((0.0, 12.0, -20.0), 10.0, -25.0, width=37, height=21, max_distance=500.0)
+    steep = look((0.0, 12.0, -20.0), 10.0, -60.0, fov=40.0, width=37, height=21, max_distance=500.0)
+    one = (np.float32([(-5, 0, -5), (5, 0, 5), (5, 0, -5)]), np.int32([(0, 1, 2)]))
+    flat = (np.float32([(-5, 0, -5), (5, 0, 5), (5, 0, -5), (0, 0, 0)]), np.int32([(0, 3, 1), (0, 0, 1), (2, 2, 2), (0, 1, 2)]))
+    huge = (np.float32([(-1e4, 0, -1e4), (0, 0, 2e4), (1e4, 0, -1e4)]), np.int32([(0, 1, 2)]))
+    g = grid()
+    pic = cpu_draw(harness, d, m, sc, one, (0, 0, 0), over)
+    assert check_picture(pic, 1).sum() > 0 and list(pic["counters"]) == [0, 0, 0, 1]
+    pic = cpu_draw(harness, *calm, flat, (0, 0, 0), over)
+    hit = check_picture(pic, 4)
+    assert hit.sum() > 0 and (pic["rec"]["reserved"][..., 0][hit] == 4).all() and pic["counters"][1] >= 2      # only the real one is drawn
+    pic = cpu_draw(harness, *calm, huge, (0, 0, 0), steep)
+    assert check_picture(pic, 1).all() and list(pic["counters"]) == [0, 0, 0, 1]
+    for what, cam in (("behind", look((0.0, 5.0, 60.0), 0.0, -10.0, width=37, height=21)), ("off-screen", look((0.0, 5.0, -60.0), 120.0, 0.0, fov=40.0, width=37, height=21))):
+        pic = cpu_draw(harness, d, m, sc, g, (0, 0, 0), cam)
+        assert not check_picture(pic, len(g[1])).any() and pic["counters"][1] == len(g[1]), what
+    fine = grid(128, 0.5)
+    pic = cpu_draw(harness, d, m, sc, fine, (0, 0, 0), look((0.0, 60.0, -150.0), 0.0, -20.0, width=37, height=21, max_distance=500.0), {"falloff": True})
+    assert check_picture(pic, len(fine[1])).sum() > 0 and pic["counters"][2] > 0 and pic["counters"][3] == 0     # sub-pixel triangles: every one by its lane
+    bad = (g[0].copy(), g[1])
+    bad[0][40, 1] = np.nan
+    bad[0][100, 0] = np.inf
+    pic = cpu_draw(harness, d, m, sc, bad, (0, 0, 0), over)
+    hit = check_picture(pic, len(g[1]))
+    uses = np.isin(g[1], (40, 100)).any(axis=1)
+    assert pic["counters"][0] == uses.sum() and hit.any() and not np.isin(pic["rec"]["reserved"][..., 0][hit] - 1, np.flatnonzero(uses)).any()
+    assert list(pic["vertices"]["flags"][[40, 100]]) == [1, 1] and pic["vertices"]["flags"].sum() == 2
+    # a folded mesh: the displacement scaled until crests overlap; depth picks the near layer, as the twin does
+    folded = np.array(sc, np.float32)
+    folded[:, 2] = 6.0
+    dense = grid(64, 0.5)
+    cam = look((0.0, 9.0, -22.0), 5.0, -30.0, width=37, height=21, max_distance=500.0)
+    pic = cpu_draw(harness, d, m, folded, dense, (0, 0, 0), cam)
+    hit = check_picture(pic, len(dense[1]))
+    twin = MT.draw(pic["vertices"], dense[1], list(cam.position), list(cam.basis), cam.fov_y_degrees, cam.width, cam.height, NEAR, cam.max_distance)
+    layered = twin["hit"] & np.isfinite(twin["gap"])
+    assert layered.sum() > 20 and ((pic["rec"]["status"] & BELOW) != 0).any()          # rays that meet the sheet more than once; undersides of crests
+    clear = twin["hit"] & (twin["min_bary"] >= 1e-3) & (twin["gap"] >= 1e-3)
+    assert (clear & layered).sum() > 10 and np.array_equal(pic["rec"]["reserved"][..., 0][clear].astype(np.int64) - 1, twin["tri"][clear])
+    # from below: both faces are drawn and say so; OW_MESH_CULL_BACK drops them
+    below = look((0.0, -6.0, -10.0), 0.0, 30.0, width=37, height=21)
+    pic = cpu_draw(harness, *calm, g, (0, 0, 0), below)
+    hit = check_picture(pic, len(g[1]))
+    assert hit.sum() > 100 and (pic["rec"]["status"][hit] == HIT | BELOW).all()
+    pic = cpu_draw(harness, *calm, g, (0, 0, 0), below, {"cull_back": True})
+    assert not check_picture(pic, len(g[1]), {"cull_back": True}).any() and pic["counters"][1] == len(g[1])
+    pic = cpu_draw(harness, *calm, g, (0, 0, 0), over, {"cull_back": True})
+    assert check_picture(pic, len(g[1])).sum() > 100
+    # image sizes
+    for w, h in ((1, 1), (37, 21)):
+        pic = cpu_draw(harness, d, m, sc, g, (0, 0, 0), look((0.0, 12.0, -20.0), 10.0, -25.0, width=w, height=h), {"falloff": True})
+        assert check_picture(pic, len(g[1])).any()
+    # a camera that is not finite is no error: all sky, OW_RAY_INVALID in every pixel
+    for field, value in (("position", (float("nan"), 0, 0)), ("basis", [float("inf")] + [0.0] * 8), ("fov", float("nan")), ("max_distance", -1.0)):
+        cam = look((0.0, 12.0, -20.0), 10.0, -25.0, width=37, height=21)
+        if field == "position":
+            cam.position[:] = value
+        elif field == "basis":
+            cam.basis[:] = value
+        elif field == "fov":
+            cam.fov_y_degrees = value
+        else:
+            cam.max_distance = value
+        pic = cpu_draw(harness, d, m, sc, g, (0, 0, 0), cam)
+        assert (pic["rec"]["status"] == INVALID).all() and (pic["vis"] == NO_TRIANGLE).all(), field
+        assert np.array_equal(pic["rgba"], np.broadcast_to(RT.rgba8(np.float32(DEFAULTS["sky_color"])), pic["rgba"].shape)), field
+        assert pic["counters"][1] == len(g[1]) and np.isfinite(pic["vertices"]["position"]).all()
+
+
+# ---- 6. the sanitizers, 7. the C example ---------------------------------------------------------------------------------------------------
+
+def test_stand_alone_harness_runs_clean_under_the_sanitizers(tmp_path):
+    """the harness as a program of its own (-DMESH_HARNESS_MAIN), built with -fsanitize=address,undefined: the calm-sea cameras and the
+    awkward inputs, on maps it makes itself"""
+    exe = str(tmp_path / "mesh_harness_main")
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                    "-Wno-unknown-pragmas", "-DMESH_HARNESS_MAIN", "-I", CSRC, HARNESS_SRC, "-o", exe], check=True)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "ok (0 failures)" in r.stdout and "runtime error" not in r.stderr and "Sanitizer" not in r.stderr
+
+
+def build_example(tmp_path):
+    exe = str(tmp_path / "mesh_host")
+    subprocess.run(["gcc", "-O2", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "examples", "mesh_host.c"),
+                    "-o", exe, "-L", PKG, "-locean_waves", f"-Wl,-rpath,{PKG}", "-Wl,-rpath,/opt/rocm/lib", "-Wl,-rpath-link,/opt/rocm/lib", "-lm"],
+                   check=True)
+    return exe
+
+
+def test_example_builds_as_c99(tmp_path):
+    build.build_library()
+    build_example(tmp_path)
+
+
+def test_clipmap_fixture_is_the_inner_rings():
+    v, t = clipmap()
+    assert v.dtype == np.float32 and t.dtype == np.int32 and t.min() == 0 and t.max() == len(v) - 1 and len(np.unique(t)) == len(v)
+    assert np.abs(v[:, [0, 2]]).max() <= 128 and not v[:, 1].any()
+    e1, e2 = v[t[:, 1]] - v[t[:, 0]], v[t[:, 2]] - v[t[:, 0]]
+    ny = np.cross(e1.astype(np.float64), e2.astype(np.float64))[:, 1]
+    assert (ny >= 0).all() and 0 < (ny == 0).sum() < 0.01 * len(t)       # wound upwards; the fans' zero-area triangles at the T-junctions are there
+    assert os.path.getsize(os.path.join(HERE, "golden", "clipmap_low_inner.npz")) < 935671
+
+
+# ---- 8-11. on the GPU ----------------------------------------------------------------------------------------------------------------------
+
+def hip():
+    h = C.CDLL("libamdhip64.so")
+    h.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    return h
+
+
+def device_array(ptr, shape, dtype):
+    out = np.zeros(shape, dtype)
+    assert hip().hipMemcpy(out.ctypes.data, ptr, out.nbytes, 2) == 0   # hipMemcpyDeviceToHost
+    return out
+
+
+def gpu_draw(gen, mesh_handle, cam, origin, sc, options=None):
+    rgba, rec = gen.mesh_draw(mesh_handle, cam, origin, sc, options)
+    vptr, wptr = gen.mesh_device_ptrs(mesh_handle)
+    stats = gen.mesh_stats(mesh_handle)
+    return dict(rgba=rgba, rec=rec, vertices=device_array(vptr, mesh_handle.num_vertices, W.MESH_VERTEX),
+                vis=device_array(wptr, (cam.height, cam.width), np.uint64),
+                counters=np.array([stats[k] for k in ("skipped", "culled", "per_lane", "cooperative")], np.uint32))
+
+
+def assert_same_picture(got, want, what):
+    for f in W.MESH_VERTEX.names:
+        assert got["vertices"][f].tobytes() == want["vertices"][f].tobytes(), (what, "vertex", f)
+    assert got["vis"].tobytes() == want["vis"].tobytes(), (what, "visibility words")
+    for f in W.RENDER_PIXEL.names:
+        assert got["rec"][f].tobytes() == want["rec"][f].tobytes(), (what, f)
+    assert got["rgba"].tobytes() == want["rgba"].tobytes(), what
+    assert list(got["counters"]) == list(want["counters"]), what
+
+
+@pytest.mark.gpu
+def test_gpu_draw_is_the_cpu_builds_bit_for_bit_256(harness):
+    """256^2 x 4: the grid at 64 x 40, meshes of 1, 63, 64, 65 and 200 triangles (a partial wave, one wave, one wave plus one), images of
+    37 x 21 and 8 x 8, the near-plane camera, culling, a vertex that is not finite, and a draw repeated"""
+    gen, params = make_gen(256, [0, 1, 2, 3])
+    gen.run(UPDATE_DELTA, params, 3)
+    sc = scales_of(params)
+    d, m = gpu_maps(gen, 4)
+    g = grid()
+    cam = look(**TWIN_CAM)
+    low = look(width=64, height=40, **CALM_CAMERAS["near_plane"][0])
+    cases = [("grid", g, cam, (1.0, 0.0, 2.0), {"falloff": True}), ("grid, defaults", g, cam, (0, 0, 0), None),
+             ("near plane", g, low, (0, 0, 0), None), ("near plane, near 3 m, culled", g, low, (0, 0, 0), {"near": 3.0, "cull_back": True}),
+             ("37 x 21", g, look(**dict(TWIN_CAM, width=37, height=21)), (0, 0, 0), {"falloff": True}),
+             ("8 x 8", g, look(**dict(TWIN_CAM, width=8, height=8)), (0, 0, 0), None),
+             ("every triangle by the wave", g, cam, (0, 0, 0), {"lane_box": -1}), ("every triangle by its lane", g, cam, (0, 0, 0), {"lane_box": 64})]
+    for count in (1, 63, 64, 65, 200):
+        cases.append((f"{count} triangles", (g[0], g[1][272:272 + count]), cam, (0, 0, 0), None))
+    bad = (g[0].copy(), g[1])
+    bad[0][150, 2] = np.nan
+    cases.append(("a vertex that is not finite", bad, cam, (0, 0, 0), None))
+    for what, mesh, c, origin, opts in cases:
+        handle = gen.mesh_create(*mesh)
+        got = gpu_draw(gen, handle, c, origin, sc, opts)
+        want = cpu_draw(harness, d, m, sc, mesh, origin, c, opts)
+        assert_same_picture(got, want, what)
+        check_picture(got, len(mesh[1]), opts)
+        assert ((got["rec"]["status"] & HIT) != 0).any(), what
+        if what == "grid":     # 9. the same draw twice gives the same bytes; ow_mesh_displace's records are the bytes the draw left resident
+            again = gpu_draw(gen, handle, c, origin, sc, opts)
+            assert_same_picture(again, got, "repeat")
+            rec = gen.mesh_displace(handle, origin, sc, opts, c)
+            assert rec.tobytes() == got["vertices"].tobytes()
+            assert rec.tobytes() == device_array(gen.mesh_device_ptrs(handle)[0], handle.num_vertices, W.MESH_VERTEX).tobytes()
+            no_cam = gen.mesh_displace(handle, origin, sc, {"falloff_center": (c.position[0], c.position[2])})
+            assert not no_cam["view_position"].any() and no_cam["position"].tobytes() == rec["position"].tobytes()
+            only_rgba, none = gen.mesh_draw(handle, c, origin, sc, opts, pixels=False)
+            assert none is None and only_rgba.tobytes() == got["rgba"].tobytes()
+            assert gen.mesh_stats(handle)["draws"] == 3
+        gen.mesh_destroy(handle)
+    # a camera that is not finite is no error
+    handle = gen.mesh_create(*g)
+    cam.position[1] = float("nan")
+    rgba, rec = gen.mesh_draw(handle, cam, (0, 0, 0), sc)
+    assert (rec["status"] == INVALID).all() and np.array_equal(rgba, np.broadcast_to(RT.rgba8(np.float32(DEFAULTS["sky_color"])), rgba.shape))
+    with pytest.raises(_lib.OceanWavesError) as e:
+        gen.mesh_draw(handle, look(**TWIN_CAM), (0, 0, 0), np.ones((5, 4), np.float32))     # more cascades than the context has
+    assert e.value.status == _lib.OW_ERR_INVALID
+    gen.mesh_destroy(handle)
+
+
+@pytest.mark.gpu
+def test_gpu_clipmap_from_the_reference_camera_is_the_cpu_builds_bit_for_bit(harness):
+    """the clipmap fixture at 1024^2 x 3, the falloff around the camera, 160 x 96 from main.tscn:120's pose, the mesh where main.gd puts it:
+    both raster paths run"""
+    gen, params = make_gen(1024, [0, 1, 2])
+    gen.run(UPDATE_DELTA, params, 3)
+    sc = scales_of(params)
+    d, m = gpu_maps(gen, 3)
+    mesh = clipmap()
+    cam = W.camera((0.0, 10.0, -25.0), REF_BASIS, 75.0, 160, 96, 4000.0)
+    origin = W.clipmap_origin(cam.position, 4.0)
+    handle = gen.mesh_create(*mesh)
+    got = gpu_draw(gen, handle, cam, origin, sc, {"falloff": True})
+    want = cpu_draw(harness, d, m, sc, mesh, origin, cam, {"falloff": True})
+    assert_same_picture(got, want, "clipmap")
+    hit = check_picture(got, len(mesh[1]))
+    stats = gen.mesh_stats(handle)
+    print(stats, f"hit share {hit.mean():.3f}")
+    assert stats["per_lane"] > 0 and stats["cooperative"] > 0 and hit.mean() > 0.3
+    gen.mesh_destroy(handle)
+
+
+def _async_case(drive, stream=None, torch_stream=None):
+    """drive / mesh_draw_async / drive again / sync, against the synchronous draw of a context that stopped after the first drive
+    (test_render_view.py's _async_case); no host synchronisation between the two drives"""
+    import torch
+    n, ids = 1024, [0, 1, 2, 3]
+    a, pa = make_gen(n, ids, stream=stream)
+    b, pb = make_gen(n, ids)
+    sc = scales_of(pa)
+    cam = look(**TWIN_CAM)
+    mesh = grid()
+    ha, hb = a.mesh_create(*mesh), b.mesh_create(*mesh)
+    opts = {"falloff": True}
+    count = cam.width * cam.height
+    rgba_dev = torch.zeros((count, 4), dtype=torch.uint8, device="cuda:0")
+    rec_dev = torch.zeros((count, W.RENDER_PIXEL.itemsize), dtype=torch.uint8, device="cuda:0")
+    a.mesh_draw(ha, cam, (0, 0, 0), sc, opts)     # the visibility scratch exists from here on
+    torch.cuda.synchronize()
+    drive(a, pa, 8)
+    syncs = a.sync_stats()
+    if torch_stream is not None:
+        with torch.cuda.stream(torch_stream):
+            a.mesh_draw_async(ha, cam, (0, 0, 0), sc, rgba_dev, rec_dev, opts)
+            copy = rgba_dev.to("cpu", non_blocking=False)   # the caller's own work, ordered by its stream alone
+        torch_stream.synchronize()
+    else:
+        a.mesh_draw_async(ha, cam, (0, 0, 0), sc, rgba_dev, rec_dev, opts)
+    assert a.sync_stats() == syncs                   # the draw itself synchronised nothing
+    drive(a, pa, 8)
+    a.sync()
+    got_rgba = rgba_dev.cpu().numpy().reshape(cam.height, cam.width, 4)
+    got_rec = np.frombuffer(rec_dev.cpu().numpy().tobytes(), W.RENDER_PIXEL).reshape(cam.height, cam.width)
+    drive(b, pb, 8)
+    want_rgba, want_rec = b.mesh_draw(hb, cam, (0, 0, 0), sc, opts)
+    assert got_rec.tobytes() == want_rec.tobytes() and got_rgba.tobytes() == want_rgba.tobytes()
+    if torch_stream is not None:
+        assert copy.numpy().tobytes() == want_rgba.tobytes()
+    assert a.mesh_draw(ha, cam, (0, 0, 0), sc, opts)[1].tobytes() != want_rec.tobytes()     # the second half moved the maps
+    a.mesh_destroy(ha)
+    b.mesh_destroy(hb)
+    return a
+
+
+def _ticks(g, p, k):
+    for _ in range(k):
+        g.update_all(UPDATE_DELTA, p)
+
+
+@pytest.mark.gpu
+def test_async_draw_between_ticks_on_the_contexts_stream():
+    a = _async_case(_ticks)
+    assert a.lookahead_stats()[0] > 0
+
+
+@pytest.mark.gpu
+def test_async_draw_between_ticks_on_a_callers_stream():
+    import torch
+    s = torch.cuda.Stream()
+    _async_case(_ticks, stream=s.cuda_stream, torch_stream=s)
+
+
+@pytest.mark.gpu
+def test_async_draw_argument_errors_write_nothing():
+    import torch
+    gen, params = make_gen(256, [0, 1])
+    sc = scales_of(params)
+    cam = look(**TWIN_CAM)
+    handle = gen.mesh_create(*grid())
+    count = cam.width * cam.height
+    rgba_dev = torch.zeros((count, 4), dtype=torch.uint8, device="cuda:0")
+    rec_dev = torch.zeros((count, W.RENDER_PIXEL.itemsize), dtype=torch.uint8, device="cuda:0")
+    for bad in ({"roughness": 1.5}, {"near": float("inf")}, {"lane_box": 99}, {"sky_color": (0, float("inf"), 0)}):
+        with pytest.raises(_lib.OceanWavesError) as e:
+            gen.mesh_draw_async(handle, cam, (0, 0, 0), sc, rgba_dev, rec_dev, bad)
+        assert e.value.status == _lib.OW_ERR_INVALID
+    with pytest.raises(_lib.OceanWavesError) as e:
+        gen.mesh_draw_async(handle, cam, (0, 0, 0), sc, None, None)
+    assert e.value.status == _lib.OW_ERR_INVALID
+    with pytest.raises(_lib.OceanWavesError) as e:
+        gen.mesh_draw_async(handle, cam, (0, 0, 0), sc, rgba_dev, rec_dev.data_ptr() + 4)   # records are written as 16-byte vectors
+    assert e.value.status == _lib.OW_ERR_INVALID
+    other, _ = make_gen(256, [0, 1])
+    with pytest.raises(_lib.OceanWavesError) as e:
+        other.mesh_draw_async(handle, cam, (0, 0, 0), sc, rgba_dev, rec_dev)                  # another context's mesh
+    assert e.value.status == _lib.OW_ERR_INVALID
+    torch.cuda.synchronize()
+    assert not rgba_dev.any() and not rec_dev.any()
+    gen.mesh_destroy(handle)
+
+
+@pytest.mark.gpu
+def test_the_c_example_writes_the_python_wrappers_image(tmp_path):
+    """examples/mesh_host.c at 256^2, 40 x 24, five ticks, against the wrapper on the same scene and the grid the example generates"""
+    exe = build_example(tmp_path)
+    ppm = str(tmp_path / "mesh.ppm")
+    r = subprocess.run([exe, ppm, "40", "24", "5", "256"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr
+    kv = dict(p.split("=") for p in r.stdout.split())
+    assert kv["finite"] == "1" and 0.3 < float(kv["hit_share"]) < 0.9
+    raw = open(ppm, "rb").read()
+    head = b"P6\n40 24\n255\n"
+    assert raw.startswith(head) and len(raw) == len(head) + 40 * 24 * 3
+    gen, params = make_gen(256, [0, 1, 2])
+    for _ in range(5):
+        gen.update_all(UPDATE_DELTA, params)
+    cam = W.camera((0.0, 10.0, -25.0), REF_BASIS, 75.0, 40, 24, 4000.0)
+    mesh = grid(128, 4.0)
+    handle = gen.mesh_create(*mesh)
+    rgba, rec = gen.mesh_draw(handle, cam, W.clipmap_origin(cam.position, 4.0), scales_of(params), {"falloff": True, "cull_back": True})
+    assert np.frombuffer(raw[len(head):], np.uint8).reshape(24, 40, 3).tobytes() == rgba[..., :3].tobytes()
+    assert abs(((rec["status"] & HIT) != 0).mean() - float(kv["hit_share"])) < 1e-3
+    stats = gen.mesh_stats(handle)
+    assert int(kv["triangles"]) == len(mesh[1]) == sum(stats[k] for k in ("skipped", "culled", "per_lane", "cooperative"))
+    gen.mesh_destroy(handle)
