@@ -23,7 +23,6 @@
 #include <vector>
 
 #include "ow_internal.h"
-#include "ow_kernels.h"
 
 namespace {
 
@@ -110,14 +109,8 @@ struct ow_group {
     // ow_sync, carried over to the group's readers).
     uint32_t faulted_shards = 0;
     float last_copy_ms = 0.0f;
-    float *query_xz = nullptr;
-    void *query_out = nullptr;  // query_capacity records of either kind (ow_group_sample_surface / ow_group_query_surface)
-    int query_capacity = 0;
-    void *buoy_scratch = nullptr;  // ow_group_buoyancy (grow-only, root device)
-    size_t buoy_bytes = 0;
-    ow::Ray *ray_in = nullptr;  // ow_group_raycast_surface (grow-only, root device)
-    ow::RaycastHit *ray_out = nullptr;
-    int ray_capacity = 0;
+    // the readers' grow-only scratch on the root device: ow_group_sample_surface / ow_group_query_surface, ow_group_buoyancy, ow_group_raycast_surface
+    ow::DeviceScratch query_scratch, buoy_scratch, ray_scratch;
     uint32_t *ray_bound = nullptr;
 };
 
@@ -230,6 +223,40 @@ ow_status refuse_faulted_layers(const ow_group *g, int first, int count) {
             return fail(OW_ERR_HIP, "gathered layer %d belongs to shard %d, whose kernels had reported a device-side failure when its layers were "
                                     "gathered: the bytes are not maps until a later gather of that shard has landed cleanly", layer, layer / g->per);
     return OW_OK;
+}
+// what every reader of layers [first, first + count) of the gathered arrays checks
+ow_status check_gathered(const ow_group *g, int first, int count) {
+    if (!g->gathered) return fail(OW_ERR_STATE, "the gathered arrays are empty: ow_group_gather_begin / ow_group_gather_wait first");
+    if (gather_in_flight(g)) return fail(OW_ERR_STATE, "a gather is in flight (the arrays are being written): ow_group_gather_wait first");
+    return refuse_faulted_layers(g, first, count);
+}
+ow_status check_num_cascades(const ow_group *g, int num_cascades) {
+    if (num_cascades < 1 || num_cascades > std::min(g->total, OW_MAX_CASCADES))
+        return fail(OW_ERR_INVALID, "num_cascades %d outside [1,%d]", num_cascades, std::min(g->total, OW_MAX_CASCADES));
+    return OW_OK;
+}
+
+// the gathered arrays on the root device (the consumer kernels read the two array textures only)
+ow::MapsView gathered_view(const ow_group *g) {
+    ow::MapsView v{g->n, {}, g->root_stream, g->root_device};
+    v.buf.disp = (ow::u16x4 *)g->gdisp;
+    v.buf.norm = (ow::u16x4 *)g->gnorm;
+    return v;
+}
+// fn() with `device` current, followed by a synchronisation of `stream`; the caller's device is put back on every way out
+template <class Fn>
+ow_status run_on_device(int device, hipStream_t stream, Fn &&fn) {
+    int caller_dev = -1;
+    (void)hipGetDevice(&caller_dev);
+    auto run = [&]() -> ow_status {
+        OW_HIP(hipSetDevice(device));
+        if (ow_status st = fn(); st != OW_OK) return st;
+        OW_HIP(hipStreamSynchronize(stream));
+        return OW_OK;
+    };
+    const ow_status st = run();
+    if (caller_dev >= 0) (void)hipSetDevice(caller_dev);
+    return st;
 }
 
 }  // namespace
@@ -383,11 +410,7 @@ void ow_group_destroy(ow_group *g) {
     }
     if (g->own_gdisp) (void)hipFree(g->gdisp);
     if (g->own_gnorm) (void)hipFree(g->gnorm);
-    (void)hipFree(g->query_xz);
-    (void)hipFree(g->query_out);
-    (void)hipFree(g->buoy_scratch);
-    (void)hipFree(g->ray_in);
-    (void)hipFree(g->ray_out);
+    for (ow::DeviceScratch *s : {&g->query_scratch, &g->buoy_scratch, &g->ray_scratch}) s->release();
     (void)hipFree(g->ray_bound);
     delete g;
     if (caller_dev >= 0) (void)hipSetDevice(caller_dev);
@@ -476,72 +499,27 @@ ow_status ow_group_get_device_ptrs(ow_group *g, void **disp, void **norm, size_t
 ow_status ow_group_get_maps(ow_group *g, int32_t cascade, void *disp, void *norm) {
     if (!g) return fail(OW_ERR_INVALID, "null group");
     if (cascade < 0 || cascade >= g->layers) return fail(OW_ERR_INVALID, "cascade %d out of range [0,%d)", cascade, g->layers);
-    if (!g->gathered) return fail(OW_ERR_STATE, "the gathered arrays are empty: ow_group_gather_begin / ow_group_gather_wait first");
-    if (gather_in_flight(g)) return fail(OW_ERR_STATE, "a gather is in flight (the arrays are being written): ow_group_gather_wait first");
-    if (ow_status st = refuse_faulted_layers(g, cascade, 1); st != OW_OK) return st;
-    int caller_dev = -1;
-    (void)hipGetDevice(&caller_dev);
-    auto run = [&]() -> ow_status {
-        OW_HIP(hipSetDevice(g->root_device));
+    if (ow_status st = check_gathered(g, cascade, 1); st != OW_OK) return st;
+    return run_on_device(g->root_device, g->root_stream, [&]() -> ow_status {
         if (disp) OW_HIP(hipMemcpyAsync(disp, g->gdisp + (size_t)cascade * g->plane_bytes, g->plane_bytes, hipMemcpyDeviceToHost, g->root_stream));
         if (norm) OW_HIP(hipMemcpyAsync(norm, g->gnorm + (size_t)cascade * g->plane_bytes, g->plane_bytes, hipMemcpyDeviceToHost, g->root_stream));
-        OW_HIP(hipStreamSynchronize(g->root_stream));
         return OW_OK;
-    };
-    const ow_status st = run();
-    if (caller_dev >= 0) (void)hipSetDevice(caller_dev);
-    return st;
+    });
 }
 
 namespace {
-// the common body of ow_group_sample_surface / ow_group_query_surface: checks, grow-only scratch on the root device, one launch on the
-// root stream over the gathered arrays, the records back to the host.  qp == nullptr: the sampling kernel.
+// the common body of ow_group_sample_surface / ow_group_query_surface: checks, then the context calls' round trip on the root device over the
+// gathered arrays.  qp == nullptr: the sampling kernel.
 ow_status group_point_query(ow_group *g, const float *xz, int32_t count, const float *map_scales, int32_t num_cascades, const ow::QueryParams *qp,
                             void *out) {
     if (!g) return fail(OW_ERR_INVALID, "null group");
     if (count < 0) return fail(OW_ERR_INVALID, "count must be >= 0");
-    if (num_cascades < 1 || num_cascades > std::min(g->total, OW_MAX_CASCADES))
-        return fail(OW_ERR_INVALID, "num_cascades %d outside [1,%d]", num_cascades, std::min(g->total, OW_MAX_CASCADES));
-    if (!g->gathered) return fail(OW_ERR_STATE, "the gathered arrays are empty: ow_group_gather_begin / ow_group_gather_wait first");
-    if (gather_in_flight(g)) return fail(OW_ERR_STATE, "a gather is in flight (the arrays are being written): ow_group_gather_wait first");
-    if (ow_status st = refuse_faulted_layers(g, 0, num_cascades); st != OW_OK) return st;
+    if (ow_status st = check_num_cascades(g, num_cascades); st != OW_OK) return st;
+    if (ow_status st = check_gathered(g, 0, num_cascades); st != OW_OK) return st;
     if (count == 0) return OW_OK;
     if (!xz || !map_scales || !out) return fail(OW_ERR_INVALID, "null argument");
-    const size_t rec = qp ? sizeof(ow::SurfaceQuery) : sizeof(ow::SurfaceSample);
-    int caller_dev = -1;
-    (void)hipGetDevice(&caller_dev);
-    auto run = [&]() -> ow_status {
-        OW_HIP(hipSetDevice(g->root_device));
-        if (count > g->query_capacity) {
-            (void)hipFree(g->query_xz);
-            (void)hipFree(g->query_out);
-            g->query_xz = nullptr;
-            g->query_out = nullptr;
-            g->query_capacity = 0;
-            const int cap = std::max(count, 4096);
-            if (hipMalloc((void **)&g->query_xz, (size_t)cap * 2 * sizeof(float)) != hipSuccess || hipMalloc(&g->query_out, (size_t)cap * sizeof(ow::SurfaceQuery)) != hipSuccess)
-                return fail(OW_ERR_NOMEM, "hipMalloc failed for %d query points", cap);
-            g->query_capacity = cap;
-        }
-        ow::SurfaceScales sc;
-        std::memset(&sc, 0, sizeof(sc));
-        std::memcpy(sc.s, map_scales, (size_t)num_cascades * 4 * sizeof(float));
-        ow::DeviceBuffers buf;
-        std::memset(&buf, 0, sizeof(buf));
-        buf.disp = (ow::u16x4 *)g->gdisp;  // the point kernels read the two array textures only
-        buf.norm = (ow::u16x4 *)g->gnorm;
-        OW_HIP(hipMemcpyAsync(g->query_xz, xz, (size_t)count * 2 * sizeof(float), hipMemcpyHostToDevice, g->root_stream));
-        if (qp)
-            OW_HIP(ow::launch_query_surface(g->n, num_cascades, buf, g->query_xz, count, sc, *qp, (ow::SurfaceQuery *)g->query_out, g->root_stream));
-        else
-            OW_HIP(ow::launch_sample_surface(g->n, num_cascades, buf, g->query_xz, count, sc, (ow::SurfaceSample *)g->query_out, g->root_stream));
-        OW_HIP(hipMemcpyAsync(out, g->query_out, (size_t)count * rec, hipMemcpyDeviceToHost, g->root_stream));
-        OW_HIP(hipStreamSynchronize(g->root_stream));
-        return OW_OK;
-    };
-    const ow_status st = run();
-    if (caller_dev >= 0) (void)hipSetDevice(caller_dev);
-    return st;
+    const ow::MapsView v = gathered_view(g);
+    return run_on_device(v.device, v.stream, [&] { return ow::points_round_trip(v, g->query_scratch, xz, count, map_scales, num_cascades, qp, nullptr, out); });
 }
 }  // namespace
 
@@ -574,33 +552,13 @@ ow_status ow_group_buoyancy(ow_group *g, const ow_buoyancy_body *bodies, int32_t
     if (num_points > 0 && bp.warm_start && !points_inout) return fail(OW_ERR_INVALID, "OW_BUOYANCY_WARM_START needs points_inout");
     if (ow_status st = ow::check_buoyancy_arrays(bodies, num_bodies, hull, num_points); st != OW_OK) return st;
     if (!g) return fail(OW_ERR_INVALID, "null group");
-    if (num_cascades < 1 || num_cascades > std::min(g->total, OW_MAX_CASCADES))
-        return fail(OW_ERR_INVALID, "num_cascades %d outside [1,%d]", num_cascades, std::min(g->total, OW_MAX_CASCADES));
-    if (!g->gathered) return fail(OW_ERR_STATE, "the gathered arrays are empty: ow_group_gather_begin / ow_group_gather_wait first");
-    if (gather_in_flight(g)) return fail(OW_ERR_STATE, "a gather is in flight (the arrays are being written): ow_group_gather_wait first");
-    if (ow_status st = refuse_faulted_layers(g, 0, num_cascades); st != OW_OK) return st;
+    if (ow_status st = check_num_cascades(g, num_cascades); st != OW_OK) return st;
+    if (ow_status st = check_gathered(g, 0, num_cascades); st != OW_OK) return st;
     if (num_bodies == 0 && num_points == 0) return OW_OK;
-    int caller_dev = -1;
-    (void)hipGetDevice(&caller_dev);
-    auto run = [&]() -> ow_status {
-        OW_HIP(hipSetDevice(g->root_device));
-        ow::SurfaceScales sc;
-        std::memset(&sc, 0, sizeof(sc));
-        std::memcpy(sc.s, map_scales, (size_t)num_cascades * 4 * sizeof(float));
-        ow::DeviceBuffers buf;
-        std::memset(&buf, 0, sizeof(buf));
-        buf.disp = (ow::u16x4 *)g->gdisp;  // the buoyancy kernels read the displacement array only
-        buf.norm = (ow::u16x4 *)g->gnorm;
-        if (ow_status st = ow::buoyancy_enqueue_host(g->n, num_cascades, buf, g->root_stream, &g->buoy_scratch, &g->buoy_bytes, bodies, num_bodies, hull,
-                                                     num_points, sc, qp, bp, results, points_inout);
-            st != OW_OK)
-            return st;
-        OW_HIP(hipStreamSynchronize(g->root_stream));
-        return OW_OK;
-    };
-    const ow_status st = run();
-    if (caller_dev >= 0) (void)hipSetDevice(caller_dev);
-    return st;
+    const ow::MapsView v = gathered_view(g);
+    return run_on_device(v.device, v.stream, [&] {
+        return ow::buoyancy_round_trip(v, g->buoy_scratch, bodies, num_bodies, hull, num_points, map_scales, num_cascades, qp, bp, results, points_inout);
+    });
 }
 
 ow_status ow_group_raycast_surface(ow_group *g, const ow_ray *rays, int32_t count, const float *map_scales, int32_t num_cascades,
@@ -608,36 +566,14 @@ ow_status ow_group_raycast_surface(ow_group *g, const ow_ray *rays, int32_t coun
     static_assert(sizeof(ow_raycast_hit) == sizeof(ow::RaycastHit) && sizeof(ow_ray) == sizeof(ow::Ray), "record layout");
     if (!g) return fail(OW_ERR_INVALID, "null group");
     if (count < 0) return fail(OW_ERR_INVALID, "count must be >= 0");
-    if (num_cascades < 1 || num_cascades > std::min(g->total, OW_MAX_CASCADES))
-        return fail(OW_ERR_INVALID, "num_cascades %d outside [1,%d]", num_cascades, std::min(g->total, OW_MAX_CASCADES));
+    if (ow_status st = check_num_cascades(g, num_cascades); st != OW_OK) return st;
     ow::RaycastParams rp;
     if (ow_status st = ow::resolve_raycast_options(opts, &rp); st != OW_OK) return st;
-    if (!g->gathered) return fail(OW_ERR_STATE, "the gathered arrays are empty: ow_group_gather_begin / ow_group_gather_wait first");
-    if (gather_in_flight(g)) return fail(OW_ERR_STATE, "a gather is in flight (the arrays are being written): ow_group_gather_wait first");
-    if (ow_status st = refuse_faulted_layers(g, 0, num_cascades); st != OW_OK) return st;
+    if (ow_status st = check_gathered(g, 0, num_cascades); st != OW_OK) return st;
     if (count == 0) return OW_OK;
     if (!rays || !map_scales || !out) return fail(OW_ERR_INVALID, "null argument");
-    int caller_dev = -1;
-    (void)hipGetDevice(&caller_dev);
-    auto run = [&]() -> ow_status {
-        OW_HIP(hipSetDevice(g->root_device));
-        if (ow_status st = ow::raycast_scratch(count, &g->ray_in, &g->ray_out, &g->ray_capacity, &g->ray_bound); st != OW_OK) return st;
-        ow::SurfaceScales sc;
-        std::memset(&sc, 0, sizeof(sc));
-        std::memcpy(sc.s, map_scales, (size_t)num_cascades * 4 * sizeof(float));
-        ow::DeviceBuffers buf;
-        std::memset(&buf, 0, sizeof(buf));
-        buf.disp = (ow::u16x4 *)g->gdisp;  // the ray-cast kernels read the two array textures only
-        buf.norm = (ow::u16x4 *)g->gnorm;
-        OW_HIP(hipMemcpyAsync(g->ray_in, rays, (size_t)count * sizeof(ow::Ray), hipMemcpyHostToDevice, g->root_stream));
-        OW_HIP(ow::launch_raycast(g->n, num_cascades, buf, g->ray_in, count, sc, rp, g->ray_bound, g->ray_out, g->root_stream));
-        OW_HIP(hipMemcpyAsync(out, g->ray_out, (size_t)count * sizeof(ow::RaycastHit), hipMemcpyDeviceToHost, g->root_stream));
-        OW_HIP(hipStreamSynchronize(g->root_stream));
-        return OW_OK;
-    };
-    const ow_status st = run();
-    if (caller_dev >= 0) (void)hipSetDevice(caller_dev);
-    return st;
+    const ow::MapsView v = gathered_view(g);
+    return run_on_device(v.device, v.stream, [&] { return ow::rays_round_trip(v, g->ray_scratch, &g->ray_bound, rays, count, map_scales, num_cascades, rp, out); });
 }
 
 }  // extern "C"

@@ -20,8 +20,7 @@
 #include <string>
 #include <vector>
 
-#include "ow_internal.h"
-#include "ow_kernels.h"
+#include "ow_context.h"
 #include "ow_tables.h"
 
 namespace {
@@ -42,177 +41,12 @@ void set_last_error(const char *message) { g_last_error = message ? message : ""
 }  // namespace ow
 
 namespace {
-using ow::fail;
+using ow::check_cascade, ow::fail, ow::main_stream, ow::plane, ow::refuse_faulted, ow::sync_stream;
 constexpr double kHostG = 9.81;  // wave_generator.gd:5
 }  // namespace
 
-// a body set (ow_bodies_create; the entry points are further down)
-struct ow_bodies {
-    ow_context *ctx = nullptr;  // nullptr: orphaned by ow_destroy (the device block is gone, the handle is still the caller's to destroy)
-    void *block = nullptr;  // one allocation: states, pose records, hull points, point records, results, fault flags
-    ow::BodiesArrays A{};
-    int max_points = 0;     // the largest point_count of the set
-    std::vector<int32_t> range;  // per body point_offset, point_count as created: ow_bodies_set_state may not change them
-    uint64_t substeps = 0, fused_launches = 0, split_calls = 0;
-};
-
-// a mesh (ow_mesh_create; the entry points are further down)
-struct ow_mesh {
-    ow_context *ctx = nullptr;  // nullptr: orphaned by ow_destroy, as a body set
-    void *block = nullptr;      // one allocation: local positions, indices, vertex records, counters
-    ow::MeshArrays A{};
-    uint64_t draws = 0;
-};
-
-struct ow_context {
-    int n = 0, cascades = 0, layers = 0, device = 0;
-    float depth = 20.0f;
-    int kernel_mode = 0;  // 0 = by batch size, 1 = standard, 2 = layer-parallel, 3 = compact-intermediate kernels (OW_FLAG_KERNELS_*)
-    int last_family = 0;  // kernel family of the most recent batch
-    int bodies_mode = 0;  // ow_bodies_step: 0 = by the set's shape, 1 = fused, 2 = split (OW_FLAG_BODIES_*)
-    hipStream_t stream = nullptr;
-    bool own_stream = false, own_disp = false, own_norm = false;
-    // TWO CHAINS (ow_kernels.h): tick-pair launches of four 1024^2 cascades a side go out as two launches of two cascades, the second halves on side_stream.
-    // side_active: work of the second chain is in flight that `stream` has not been made to wait for -- since the fork NOTHING but first-chain launches has
-    // been enqueued on `stream` (everything else goes through main_stream(), which joins first).
-    hipStream_t side_stream = nullptr;
-    hipEvent_t side_fork_ev = nullptr, side_join_ev = nullptr;
-    bool side_active = false;
-    uint64_t split_launches = 0;  // launches that went out as two chains (ow_chain_stats)
-    ow::DeviceBuffers buf{};
-    ow::cplx *tw_dev = nullptr, *tw_split_dev = nullptr, *tw_half_dev = nullptr;
-    // generator state per invocation of update() (wave_generator.gd:13-15).  The reference keeps a reference to the caller's
-    // Array; a C caller's memory is only borrowed for the duration of a call, so the context keeps COPIES of the armed records
-    // (ow_set_cascade_params / ow_get_cascade_params are the explicit form of "the parameter objects are live")
-    ow_cascade_params pass_parameters[OW_MAX_CASCADES] = {};
-    int pass_count = 0;
-    int pass_num_cascades_remaining = 0;
-    // device status word: page-locked host memory mapped into the device; kernels OR error bits into it (a bounded
-    // device-side spin that gave up), every synchronising entry point turns a non-zero word into OW_ERR_HIP
-    uint32_t *status_host = nullptr;
-    uint32_t inject_fault = 0;  // ow_debug_inject_fault: applied to the next batch only
-    // The status word is consumed by the first synchronising call that sees it; the failure itself is sticky: until the next batch
-    // is enqueued every call that hands out map bytes (ow_get_maps, ow_get_maps_f32, ow_sample_surface) keeps failing, and so does
-    // the ow_readback_wait of every layer whose copy was in flight when the word was consumed (readback_faulted).
-    // Both are bit masks over the array layers: a synchronising call that finds the word set marks the layers recomputed by the batches
-    // enqueued since the previous synchronisation (enqueued_since_sync); a layer's mark is lifted only by a later batch that recomputes
-    // THAT layer (the reference's schedule enqueues one cascade per call: the other layers keep the faulted batch's bytes).
-    uint32_t maps_faulted = 0, enqueued_since_sync = 0;
-    uint32_t readback_faulted = 0;
-    ow_push_constants pc_words[OW_MAX_CASCADES] = {};  // what the reference would have packed for each cascade's most recent launch (ow_get_push_constants)
-    bool pc_valid[OW_MAX_CASCADES] = {};
-    // pc_words[i].spectrum are the constants layer i's RESIDENT spectrum (h0, omega) was generated from -- k_spectrum is a deterministic function
-    // of those thirteen words and the map size, so a dirty record that packs to the same words is served by what is there (spectrum_is_resident)
-    bool spectrum_resident[OW_MAX_CASCADES] = {};
-    bool always_regenerate = false;  // OW_FLAG_ALWAYS_REGENERATE_SPECTRUM: every dirty flag launches k_spectrum, as the reference does
-    uint64_t spectra_generated = 0, spectra_skipped = 0;  // ow_spectrum_stats
-    // ow_update_all's adaptive look-ahead (lookahead_tick below): a pass 1 of the NEXT tick, speculated with the caller's last delta.
-    // Invariant: queued > 0 exactly while the scratch holds pass 1 of `queued` ticks that nothing has disturbed since; whatever else
-    // writes the scratch (or may have corrupted it) sets queued = 0, and no field below is read while it is 0.
-    struct Lookahead {
-        static constexpr int kMaxAhead = 4;  // ticks of pass 1 one launch may compute ahead (group kernel; the pair kernel takes one)
-        int count = 0, mode = 0;       // cascades per tick; 1 = compact family (pair kernel), 2 = layer-parallel compact family (group kernel)
-        int queued = 0, head = 0;      // ring of ticks computed ahead: entries head, head + 1, .. (mod kMaxAhead)
-        int group[kMaxAhead] = {};     // scratch group (of `stride` launch slots) that holds each entry's intermediate
-        float time[kMaxAhead][OW_MAX_CASCADES] = {};  // the FP32 times each entry was computed with, per launch slot
-        int cascade[kMaxAhead][OW_MAX_CASCADES] = {};  // which cascades (per launch slot of the launch that will use the entry), and
-        float tile_x[kMaxAhead][OW_MAX_CASCADES] = {}, tile_y[kMaxAhead][OW_MAX_CASCADES] = {};  // the tile lengths their pass 1 was computed with
-        int cur_group = 0;             // group that held the most recent launch's own intermediate
-        double last_delta = -1.0;      // the previous ow_update's delta, and for how many calls in a row it has been the same
-        double streak_delta = -1.0;    // ... "the same" = equal to the delta that STARTED the streak (a slowly ramping delta is not one unbroken streak)
-        int streak = 0;
-        int prev_run = 1;              // updates in the caller's previous run of equal deltas (1: none that says anything)
-        uint64_t hits = 0, speculated = 0;
-        bool hold = false;             // ow_run is about to merge the following ticks itself: its first tick must not speculate for them
-        int certain = 0;               // ticks the caller GUARANTEES will follow with the same delta (ow_run's own remaining ticks): speculated without evidence
-    } la;
-    // ow_run after ow_run (run_impl): what the last launch of a run computed ahead for the first launch of the NEXT run like it
-    struct RunAhead {
-        bool armed = false;          // the scratch holds that pass 1 and nothing has disturbed it since
-        int kind = 0;                // 1 = tick groups: pass 1 of `ticks` consecutive ticks of all `count` cascades; 2 = tick pairs: pass 1 of one batch, one tick
-        int count = 0;               // cascades per tick of the run that computed it
-        int D = 0, ticks = 0, pos = 0;  // kind 1: ticks per group of that run, ticks computed ahead, ring position (in ticks, mod 2 D) of the first of them
-        int batch = 0, first = 0, size = 0, parity = 0;  // kind 2: the batch (its first launch slot, its cascades) and the half of the scratch its intermediate is in
-        float time[ow::kMaxTickGroup][OW_MAX_CASCADES] = {};  // the FP32 times it was computed with, per tick (kind 2: entry 0) and launch slot
-        float tile_x[OW_MAX_CASCADES] = {}, tile_y[OW_MAX_CASCADES] = {};  // ... and the tile lengths, per launch slot
-        bool last_was_run = false;   // the most recent tick-advancing call was an ow_run (lowered by ow_update / ow_update_all / ow_process from outside a run)
-        int last_count = 0;
-        double last_delta = 0.0;
-        int run_streak = 0;          // how many runs like this one (same delta, same count) have preceded it without anything in between
-    } ra;
-    bool inside_run = false;    // ow_run is executing (its own ow_update_all calls are not "something in between")
-    int run_frames = 0;         // ... with this many ticks (may_split)
-    int pair_dir = 0;           // direction of the next block of the cascade-major pair stream (batches 0 .. B-1 or B-1 .. 0): alternates, across runs too
-    bool run_as_calls = false;  // OW_FLAG_RUN_AS_CALLS
-    bool run_as_reference = false;  // OW_FLAG_RUN_AS_REFERENCE_SCHEDULE
-    bool no_merge = false;      // OW_FLAG_NO_TICK_GROUPS
-    int group_depth_forced = 0;  // OW_DEBUG_TICK_GROUP_DEPTH (measurements; read once)
-    int run_delta_period = 0;    // OW_DEBUG_RUN_DELTA_CHANGE_EVERY: the call-by-call forms of ow_run (OW_FLAG_RUN_AS_CALLS / _AS_REFERENCE_SCHEDULE) switch
-                                 // between delta and 1.25 delta every that many ticks -- an irregular caller for the look-ahead to miss on (measurements)
-    int ahead_depth = 0;      // ticks of pass 1 ow_update_all's look-ahead computes per launch once the deltas keep repeating (OW_DEBUG_LOOKAHEAD_DEPTH, read once)
-    int pair_tick_block = 0;  // ticks a batch runs through before the stream of tick pairs moves on to the next batch (0: by map size; OW_DEBUG_PAIR_TICK_BLOCK, read once)
-    size_t pair_texels = 0;  // batch size of ow_run's tick pairs, in texels (kPairTexels; OW_DEBUG_PAIR_TEXELS is read ONCE, by ow_create)
-    // ow_run's tick groups (k_tick_group_c_lp): the largest cascade count they serve (0 = not available) and how many ticks go
-    // into one group; the scratch buffers hold 2 * depth * count cascades then
-    int group_p1_form = -1, group_p2_form = -1;
-    int group_max_count = 0, group_depth = 0;  // (group_depth: the depth of a run of group_max_count cascades; a run's own depth follows its count)
-    int scratch_slots = 0;  // launch slots the scratch intermediate (T, pcol, rrow) holds now: one batch at create, grown by the first ow_run that merges launches
-    // ow_run's tick pairs on the compact family (k_tick_pair_c): the largest batch they launch (0 = never); scratch two batches deep
-    int pair_slots = 0;
-    int last_group_depth = 0;  // ticks per launch of the most recent ow_run that went out in groups / pairs
-    // timing: a pool of events so that timed ticks stay enqueued back to back
-    int timing = 0;  // 0 off, 1 per pass (ow_run stays on one launch per pass), 2 as launched (tick groups / pairs stay on, timed per launch)
-    std::vector<char> ev_single;  // per 4-event record: 1 = one launch (events 0, 1 only): a tick group / pair
-    std::vector<hipEvent_t> ev;  // 4 per timed batch: start/stop of the pass-1 dispatch, start/stop of the pass-2 dispatch
-    size_t ev_used = 0;
-    double t1_ms = 0, t2_ms = 0, tg_ms = 0;
-    int t_launches = 0, tg_launches = 0;
-    int slot_of[OW_MAX_CASCADES];  // launch slot of each cascade in the most recent batch, -1 if it was not in it
-    // last batch that was launched (for ow_probe_kernel_times)
-    ow::FrameArgs last_args{};
-    int last_count = 0;
-    // hand-off to a host consumer (ow_readback_*): device snapshot + page-locked staging, one slot per layer and map
-    hipStream_t copy_stream = nullptr;
-    ow::u16x4 *snap_dev = nullptr, *snap_host = nullptr;  // [2 maps][layers][N][N]
-    hipEvent_t snap_ready[OW_MAX_CASCADES] = {}, copy_done[OW_MAX_CASCADES] = {};
-    bool copy_pending[OW_MAX_CASCADES] = {};
-    // ow_sample_surface / ow_query_surface scratch (grow-only): query_capacity points in, as many records of the larger kind out
-    float *query_xz = nullptr;
-    void *query_out = nullptr;
-    int query_capacity = 0;
-    // ow_buoyancy scratch (grow-only): bodies, hull points, per-point records, results
-    void *buoy_scratch = nullptr;
-    size_t buoy_bytes = 0;
-    // ow_raycast_surface scratch (grow-only): ray_capacity rays in and records out, and the per-cascade bound words of the slab
-    ow::Ray *ray_in = nullptr;
-    ow::RaycastHit *ray_out = nullptr;
-    int ray_capacity = 0;
-    uint32_t *ray_bound = nullptr;
-    // ow_render_view scratch (grow-only): RGBA8 words and per-pixel records (the bound words are the ray cast's)
-    uint32_t *render_rgba = nullptr;
-    ow::RenderPixel *render_pixels = nullptr;
-    size_t render_rgba_capacity = 0, render_pixels_capacity = 0;
-    // ow_mesh_draw scratch (grow-only): the visibility words; the synchronous form's RGBA8 words and records are ow_render_view's
-    uint64_t *mesh_vis = nullptr;
-    size_t mesh_vis_capacity = 0;
-    // the velocity layers (ow_update_velocity; ow_velocity_kernels.h): V in the displacement array's layout, the pipeline's own intermediate
-    // (vel_slots cascades of one launch pair) and twiddle table, all allocated by the first velocity call
-    ow::u16x4 *vel = nullptr;
-    ow::cplx *vel_scratch = nullptr, *vel_tw = nullptr;
-    int vel_slots = 0;
-    // Layers whose V no longer belongs to their maps: set by mark_recomputed (every batch that recomputes a layer), cleared by the velocity
-    // launch that computes them.  spectrum_ahead: layers whose resident spectrum was regenerated by a batch that did not get as far as
-    // launching their pass 2 (enqueue); their h0 is newer than their maps, and their velocity is refused until a batch recomputes them.
-    uint32_t velocity_stale = 0, spectrum_ahead = 0;
-    uint64_t vel_computed = 0, vel_skipped = 0;  // ow_velocity_stats
-    std::vector<ow_bodies *> body_sets;  // the live sets of this context: ow_destroy orphans what the caller has not destroyed
-    std::vector<ow_mesh *> meshes;       // likewise the live meshes
-    uint64_t host_syncs = 0;  // stream synchronisations made on the caller's thread since ow_create (ow_sync_stats)
-};
-
-// The stream everything but a first-chain launch is enqueued on or synchronised through: joins the second chain first (a no-op when none is in flight).
-// A failing event call leaves side_active set and hands back the stream all the same: the enqueue that follows reports the device's state itself.
-static hipStream_t main_stream(ow_context *c) {
+// (ow_context.h) A failing event call leaves side_active set and hands back the stream all the same: the enqueue that follows reports the device's state itself.
+hipStream_t ow::main_stream(ow_context *c) {
     if (c->side_active && hipEventRecord(c->side_join_ev, c->side_stream) == hipSuccess && hipStreamWaitEvent(c->stream, c->side_join_ev, 0) == hipSuccess)
         c->side_active = false;
     return c->stream;
@@ -250,8 +84,6 @@ static void join_for_caller(ow_context *c) {
 }
 
 namespace {
-
-size_t plane(const ow_context *c) { return (size_t)c->n * c->n; }
 
 // Cascades per pair of launches (measured at 1024^2, scripts/mode_bench.py): a tick of up to 6 Mi texels goes in ONE pair
 // (x 5: 82 us against 84.5 as 4 + 1; x 6: 88.5 against 96); beyond that the intermediate and the inputs of a pair no
@@ -451,15 +283,14 @@ ow_status consume_status(ow_context *c) {
     return fail(OW_ERR_HIP, "device-side failure reported by a frame kernel (status 0x%x%s): the maps of the batches enqueued since "
                             "the last synchronisation are invalid", bits, (bits & ow::kStatusRowSyncTimeout) ? ": wave-pair rendezvous timed out" : "");
 }
-ow_status refuse_faulted(const ow_context *c, uint32_t layer_mask) {
+}  // namespace
+ow_status ow::refuse_faulted(const ow_context *c, uint32_t layer_mask) {
     if (c->maps_faulted & layer_mask)
         return fail(OW_ERR_HIP, "layer mask 0x%x holds maps of a batch that reported a device-side failure (already returned by an earlier call); "
                                 "they stay invalid until a later batch has recomputed those layers (faulted: 0x%x)", layer_mask, c->maps_faulted);
     return OW_OK;
 }
-// hipStreamSynchronize + the device status word.  layer_mask: the array layers whose bytes the caller is about to hand to ITS caller (0 for a
-// bare ow_sync), refused while they are those of a faulted batch.
-ow_status sync_stream(ow_context *c, uint32_t layer_mask) {
+ow_status ow::sync_stream(ow_context *c, uint32_t layer_mask) {
     ++c->host_syncs;
     OW_HIP(hipStreamSynchronize(main_stream(c)));
     if (ow_status st = consume_status(c); st != OW_OK) return st;
@@ -467,13 +298,12 @@ ow_status sync_stream(ow_context *c, uint32_t layer_mask) {
     return refuse_faulted(c, layer_mask);
 }
 
-}  // namespace
 namespace ow {
 // The device status word WITHOUT synchronising: for a caller that has waited by other means (the group's gather waits on its own
 // copy events) and is about to hand out map bytes.  Same consumption / stickiness as sync_stream.
 ow_status poll_status(ow_context *c) {
     if (ow_status st = consume_status(c); st != OW_OK) return st;
-    return refuse_faulted(c, (1u << c->cascades) - 1u);
+    return refuse_faulted(c, layer_mask(c->cascades));
 }
 }  // namespace ow
 namespace {
@@ -1024,13 +854,13 @@ bool flush_from_queue(ow_context *c, int left, ow_status *out) {
     return true;
 }
 
-ow_status check_cascade(const ow_context *c, int cascade) {
+}  // namespace
+
+ow_status ow::check_cascade(const ow_context *c, int cascade) {
     if (!c) return fail(OW_ERR_INVALID, "null context");
     if (cascade < 0 || cascade >= c->layers) return fail(OW_ERR_INVALID, "cascade %d out of range [0,%d)", cascade, c->layers);
     return OW_OK;
 }
-
-}  // namespace
 
 extern "C" {
 
@@ -1223,15 +1053,8 @@ void ow_destroy(ow_context *c) {
     for (auto &e : c->copy_done)
         if (e) (void)hipEventDestroy(e);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
-    (void)hipFree(c->query_xz);
-    (void)hipFree(c->query_out);
-    (void)hipFree(c->buoy_scratch);
-    (void)hipFree(c->ray_in);
-    (void)hipFree(c->ray_out);
+    for (ow::DeviceScratch *s : {&c->query_scratch, &c->buoy_scratch, &c->ray_scratch, &c->render_rgba, &c->render_pixels, &c->mesh_vis}) s->release();
     (void)hipFree(c->ray_bound);
-    (void)hipFree(c->render_rgba);
-    (void)hipFree(c->render_pixels);
-    (void)hipFree(c->mesh_vis);
     (void)hipFree(c->vel);
     (void)hipFree(c->vel_scratch);
     (void)hipFree(c->vel_tw);
@@ -2004,1134 +1827,6 @@ ow_status ow_readback_wait(ow_context *c, int32_t cascade, const void **disp, co
     const size_t pl = plane(c), L = (size_t)c->layers;
     if (disp) *disp = c->snap_host + (size_t)cascade * pl;
     if (norm) *norm = c->snap_host + (L + cascade) * pl;
-    return OW_OK;
-}
-
-}  // extern "C"
-
-namespace {
-// the grow-only scratch of the synchronous point queries: `count` points in, `count` records of either kind out
-ow_status query_scratch(ow_context *c, int count) {
-    if (count <= c->query_capacity) return OW_OK;
-    (void)hipFree(c->query_xz);
-    (void)hipFree(c->query_out);
-    c->query_xz = nullptr;
-    c->query_out = nullptr;
-    c->query_capacity = 0;
-    const int cap = std::max(count, 4096);
-    static_assert(sizeof(ow::SurfaceQuery) >= sizeof(ow::SurfaceSample), "the record buffer holds either kind");
-    if (hipMalloc((void **)&c->query_xz, (size_t)cap * 2 * sizeof(float)) != hipSuccess ||
-        hipMalloc(&c->query_out, (size_t)cap * sizeof(ow::SurfaceQuery)) != hipSuccess)
-        return fail(OW_ERR_NOMEM, "hipMalloc failed for %d query points", cap);
-    c->query_capacity = cap;
-    return OW_OK;
-}
-
-// the argument checks ow_sample_surface makes, shared by the two forms of ow_query_surface (count == 0 is fine and does nothing)
-ow_status check_point_query(const ow_context *c, int32_t count, int32_t num_cascades) {
-    if (!c) return fail(OW_ERR_INVALID, "null context");
-    if (count < 0) return fail(OW_ERR_INVALID, "count must be >= 0");
-    if (num_cascades < 1 || num_cascades > c->cascades) return fail(OW_ERR_INVALID, "num_cascades %d outside [1,%d]", num_cascades, c->cascades);
-    return OW_OK;
-}
-
-ow::SurfaceScales surface_scales(const float *map_scales, int num_cascades) {
-    ow::SurfaceScales sc;
-    std::memset(&sc, 0, sizeof(sc));
-    std::memcpy(sc.s, map_scales, (size_t)num_cascades * 4 * sizeof(float));
-    return sc;
-}
-}  // namespace
-
-namespace ow {
-ow_status resolve_query_options(const ow_query_options *o, QueryParams *qp) {
-    qp->max_iterations = kQueryDefaultIterations;
-    qp->tolerance = kQueryDefaultTolerance;
-    qp->falloff = 0;
-    qp->center[0] = qp->center[1] = 0.0f;
-    if (!o) return OW_OK;
-    if (o->max_iterations < 0 || o->max_iterations > kQueryMaxIterations)
-        return fail(OW_ERR_INVALID, "max_iterations %d outside [0,%d]", o->max_iterations, kQueryMaxIterations);
-    if (o->flags & ~OW_QUERY_DISTANCE_FALLOFF) return fail(OW_ERR_INVALID, "unknown query flags 0x%x", o->flags);
-    if (!std::isfinite(o->tolerance)) return fail(OW_ERR_INVALID, "tolerance is not finite");
-    if (o->max_iterations > 0) qp->max_iterations = o->max_iterations;
-    if (o->tolerance > 0.0f) qp->tolerance = o->tolerance;
-    if (o->flags & OW_QUERY_DISTANCE_FALLOFF) {
-        if (!std::isfinite(o->falloff_center_xz[0]) || !std::isfinite(o->falloff_center_xz[1]))
-            return fail(OW_ERR_INVALID, "falloff_center_xz is not finite");
-        qp->falloff = 1;
-        qp->center[0] = o->falloff_center_xz[0];
-        qp->center[1] = o->falloff_center_xz[1];
-    }
-    return OW_OK;
-}
-}  // namespace ow
-
-extern "C" {
-
-ow_status ow_sample_surface(ow_context *c, const float *xz, int32_t count, const float *map_scales, int32_t num_cascades,
-                            ow_surface_sample *out) {
-    static_assert(sizeof(ow_surface_sample) == sizeof(ow::SurfaceSample) && sizeof(ow_surface_sample) == 64, "record layout");
-    if (ow_status st = check_point_query(c, count, num_cascades); st != OW_OK) return st;
-    if (count == 0) return OW_OK;
-    if (!xz || !map_scales || !out) return fail(OW_ERR_INVALID, "null argument");
-    OW_HIP(hipSetDevice(c->device));
-    if (ow_status st = query_scratch(c, count); st != OW_OK) return st;
-    const ow::SurfaceScales sc = surface_scales(map_scales, num_cascades);
-    OW_HIP(hipMemcpyAsync(c->query_xz, xz, (size_t)count * 2 * sizeof(float), hipMemcpyHostToDevice, main_stream(c)));
-    OW_HIP(ow::launch_sample_surface(c->n, num_cascades, c->buf, c->query_xz, count, sc, (ow::SurfaceSample *)c->query_out, main_stream(c)));
-    OW_HIP(hipMemcpyAsync(out, c->query_out, (size_t)count * sizeof(ow::SurfaceSample), hipMemcpyDeviceToHost, main_stream(c)));
-    return sync_stream(c, (1u << num_cascades) - 1u);
-}
-
-ow_status ow_query_surface(ow_context *c, const float *xz, int32_t count, const float *map_scales, int32_t num_cascades,
-                           const ow_query_options *opts, ow_surface_query *out) {
-    static_assert(sizeof(ow_surface_query) == sizeof(ow::SurfaceQuery) && offsetof(ow_surface_query, sample) == offsetof(ow::SurfaceQuery, sample) &&
-                      offsetof(ow_surface_query, world_xz) == offsetof(ow::SurfaceQuery, world_xz),
-                  "record layout");
-    if (ow_status st = check_point_query(c, count, num_cascades); st != OW_OK) return st;
-    ow::QueryParams qp;
-    if (ow_status st = ow::resolve_query_options(opts, &qp); st != OW_OK) return st;
-    if (count == 0) return OW_OK;
-    if (!xz || !map_scales || !out) return fail(OW_ERR_INVALID, "null argument");
-    OW_HIP(hipSetDevice(c->device));
-    if (ow_status st = query_scratch(c, count); st != OW_OK) return st;
-    const ow::SurfaceScales sc = surface_scales(map_scales, num_cascades);
-    OW_HIP(hipMemcpyAsync(c->query_xz, xz, (size_t)count * 2 * sizeof(float), hipMemcpyHostToDevice, main_stream(c)));
-    OW_HIP(ow::launch_query_surface(c->n, num_cascades, c->buf, c->query_xz, count, sc, qp, (ow::SurfaceQuery *)c->query_out, main_stream(c)));
-    OW_HIP(hipMemcpyAsync(out, c->query_out, (size_t)count * sizeof(ow::SurfaceQuery), hipMemcpyDeviceToHost, main_stream(c)));
-    return sync_stream(c, (1u << num_cascades) - 1u);
-}
-
-ow_status ow_query_surface_async(ow_context *c, const float *xz_dev, int32_t count, const float *map_scales, int32_t num_cascades,
-                                 const ow_query_options *opts, ow_surface_query *out_dev) {
-    if (ow_status st = check_point_query(c, count, num_cascades); st != OW_OK) return st;
-    ow::QueryParams qp;
-    if (ow_status st = ow::resolve_query_options(opts, &qp); st != OW_OK) return st;
-    if (count == 0) return OW_OK;
-    if (!xz_dev || !map_scales || !out_dev) return fail(OW_ERR_INVALID, "null argument");
-    if (ow_status st = refuse_faulted(c, (1u << num_cascades) - 1u); st != OW_OK) return st;
-    OW_HIP(hipSetDevice(c->device));
-    const ow::SurfaceScales sc = surface_scales(map_scales, num_cascades);
-    // main_stream(): behind the second chain's join as well as everything on the context's (or the caller's) stream
-    OW_HIP(ow::launch_query_surface(c->n, num_cascades, c->buf, xz_dev, count, sc, qp, (ow::SurfaceQuery *)out_dev, main_stream(c)));
-    return OW_OK;
-}
-
-}  // extern "C"
-
-namespace ow {
-ow_status resolve_buoyancy_options(const ow_buoyancy_options *o, QueryParams *qp, BuoyancyParams *bp) {
-    if (ow_status st = resolve_query_options(o ? &o->query : nullptr, qp); st != OW_OK) return st;
-    bp->density = kDefaultDensity;
-    bp->water_level = 0.0f;
-    bp->warm_start = 0;
-    bp->water_velocity = 0;
-    float gravity = kDefaultGravity;
-    if (o) {
-        if (!std::isfinite(o->density) || !std::isfinite(o->gravity) || !std::isfinite(o->water_level))
-            return fail(OW_ERR_INVALID, "density, gravity and water_level must be finite");
-        if (o->flags & ~(OW_BUOYANCY_WARM_START | OW_BUOYANCY_WATER_VELOCITY)) return fail(OW_ERR_INVALID, "unknown buoyancy flags 0x%x", o->flags);
-        if (o->density > 0.0f) bp->density = o->density;
-        if (o->gravity > 0.0f) gravity = o->gravity;
-        bp->water_level = o->water_level;
-        bp->warm_start = (o->flags & OW_BUOYANCY_WARM_START) ? 1 : 0;
-        bp->water_velocity = (o->flags & OW_BUOYANCY_WATER_VELOCITY) ? 1 : 0;
-    }
-    bp->gravity = gravity;
-    bp->rho_g = bp->density * gravity;
-    if (!std::isfinite(bp->rho_g)) return fail(OW_ERR_INVALID, "density * gravity overflows");
-    return OW_OK;
-}
-
-ow_status check_buoyancy_arrays(const ow_buoyancy_body *bodies, int num_bodies, const ow_hull_point *hull, int num_points) {
-    for (int b = 0; b < num_bodies; ++b) {
-        const ow_buoyancy_body &B = bodies[b];
-        if (B.point_offset < 0 || B.point_count < 0 || (int64_t)B.point_offset + B.point_count > num_points)
-            return fail(OW_ERR_INVALID, "body %d: point range [%d, %d + %d) outside [0, %d)", b, B.point_offset, B.point_offset, B.point_count, num_points);
-        for (int i = B.point_offset; i < B.point_offset + B.point_count; ++i)
-            if (hull[i].body != b) return fail(OW_ERR_INVALID, "hull point %d lies in body %d's range but names body %d", i, b, hull[i].body);
-    }
-    for (int i = 0; i < num_points; ++i) {
-        const ow_hull_point &h = hull[i];
-        if (h.body < 0 || h.body >= num_bodies) return fail(OW_ERR_INVALID, "hull point %d: body %d outside [0, %d)", i, h.body, num_bodies);
-        const ow_buoyancy_body &B = bodies[h.body];
-        if (i < B.point_offset || i >= B.point_offset + B.point_count)
-            return fail(OW_ERR_INVALID, "hull point %d names body %d, whose range does not hold it", i, h.body);
-        if (!(h.volume >= 0.0f) || !(h.half_height >= 0.0f))
-            return fail(OW_ERR_INVALID, "hull point %d: volume and half_height must be >= 0", i);
-    }
-    return OW_OK;
-}
-
-ow_status buoyancy_enqueue_host(int n, int cascades, const DeviceBuffers &buf, hipStream_t s, void **scratch, size_t *scratch_bytes,
-                                const ow_buoyancy_body *bodies, int num_bodies, const ow_hull_point *hull, int num_points, const SurfaceScales &sc,
-                                const QueryParams &qp, const BuoyancyParams &bp, ow_buoyancy_result *results, ow_buoyancy_point *points_inout,
-                                const u16x4 *vel) {
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t b_bytes = up((size_t)num_bodies * sizeof(BuoyancyBody)), h_bytes = up((size_t)num_points * sizeof(HullPoint));
-    const size_t p_bytes = up((size_t)num_points * sizeof(BuoyancyPoint)), r_bytes = up((size_t)num_bodies * sizeof(BuoyancyResult));
-    const size_t need = b_bytes + h_bytes + p_bytes + r_bytes;
-    if (need > *scratch_bytes) {
-        (void)hipFree(*scratch);
-        *scratch = nullptr;
-        *scratch_bytes = 0;
-        const size_t cap = std::max(need, (size_t)1 << 20);
-        if (hipMalloc(scratch, cap) != hipSuccess) return fail(OW_ERR_NOMEM, "hipMalloc failed for %zu bytes of buoyancy scratch", cap);
-        *scratch_bytes = cap;
-    }
-    char *base = (char *)*scratch;
-    BuoyancyBody *bd = (BuoyancyBody *)base;
-    HullPoint *hd = (HullPoint *)(base + b_bytes);
-    BuoyancyPoint *pd = (BuoyancyPoint *)(base + b_bytes + h_bytes);
-    BuoyancyResult *rd = (BuoyancyResult *)(base + b_bytes + h_bytes + p_bytes);
-    if (num_bodies > 0) OW_HIP(hipMemcpyAsync(bd, bodies, (size_t)num_bodies * sizeof(BuoyancyBody), hipMemcpyHostToDevice, s));
-    if (num_points > 0) OW_HIP(hipMemcpyAsync(hd, hull, (size_t)num_points * sizeof(HullPoint), hipMemcpyHostToDevice, s));
-    if (bp.warm_start && num_points > 0) OW_HIP(hipMemcpyAsync(pd, points_inout, (size_t)num_points * sizeof(BuoyancyPoint), hipMemcpyHostToDevice, s));
-    OW_HIP(launch_buoyancy(n, cascades, buf, bd, num_bodies, hd, num_points, sc, qp, bp, pd, rd, s, vel));
-    if (num_bodies > 0) OW_HIP(hipMemcpyAsync(results, rd, (size_t)num_bodies * sizeof(BuoyancyResult), hipMemcpyDeviceToHost, s));
-    if (points_inout && num_points > 0) OW_HIP(hipMemcpyAsync(points_inout, pd, (size_t)num_points * sizeof(BuoyancyPoint), hipMemcpyDeviceToHost, s));
-    return OW_OK;
-}
-}  // namespace ow
-
-namespace {
-// ---- the velocity layers (ow_velocity_kernels.h) -------------------------------------------------------------------------------------
-// V, its intermediate and its twiddle table, on first use (on the context's device; V starts zeroed, in stream order)
-ow_status velocity_buffers(ow_context *c) {
-    if (c->vel) return OW_OK;
-    const size_t pl = plane(c);
-    const int slots = std::min(ow::vel_batch(c->n), c->cascades);
-    if (hipMalloc((void **)&c->vel_tw, (size_t)c->n * sizeof(ow::cplx)) != hipSuccess ||
-        hipMalloc((void **)&c->vel_scratch, (size_t)slots * ow::vel_scratch_bytes(c->n)) != hipSuccess ||
-        hipMalloc((void **)&c->vel, (size_t)c->cascades * pl * sizeof(ow::u16x4)) != hipSuccess) {
-        (void)hipGetLastError();
-        (void)hipFree(c->vel_tw);
-        (void)hipFree(c->vel_scratch);
-        (void)hipFree(c->vel);
-        c->vel_tw = c->vel_scratch = nullptr;
-        c->vel = nullptr;
-        return fail(OW_ERR_NOMEM, "hipMalloc failed for the velocity layers (%d x %d^2) and their intermediate", c->cascades, c->n);
-    }
-    c->vel_slots = slots;
-    OW_HIP(ow::launch_velocity_twiddles(c->n, c->vel_tw, main_stream(c)));
-    OW_HIP(hipMemsetAsync(c->vel, 0, (size_t)c->cascades * pl * sizeof(ow::u16x4), main_stream(c)));
-    return OW_OK;
-}
-
-// The layers of `mask` (inside [0, cascades)) whose velocity is stale are recomputed, in stream order behind everything the context has
-// enqueued, from the resident spectrum and the words their current maps were made with (pc_words[i].modulate); the others are skipped.
-// A layer never computed is OW_ERR_STATE, a faulted one is refused as its maps are, and so is one whose spectrum is newer than its maps.
-ow_status velocity_refresh(ow_context *c, uint32_t mask) {
-    for (int i = 0; i < c->cascades; ++i)
-        if ((mask >> i & 1u) && !c->pc_valid[i]) return fail(OW_ERR_STATE, "cascade %d has not been computed yet: it has no velocity", i);
-    if (ow_status st = refuse_faulted(c, mask); st != OW_OK) return st;
-    if (c->spectrum_ahead & mask)
-        return fail(OW_ERR_STATE, "layer mask 0x%x: the resident spectrum is newer than the maps (a failed batch regenerated it): recompute the layers first",
-                    c->spectrum_ahead & mask);
-    if (ow_status st = velocity_buffers(c); st != OW_OK) return st;
-    const uint32_t todo = mask & c->velocity_stale;
-    c->vel_skipped += (uint64_t)__builtin_popcount(mask & ~todo);
-    ow::VelocityArgs args;
-    std::memset(&args, 0, sizeof(args));
-    auto word = [](uint32_t w) {
-        float f;
-        std::memcpy(&f, &w, 4);
-        return f;
-    };
-    auto flush = [&]() -> ow_status {
-        if (args.count == 0) return OW_OK;
-        OW_HIP(ow::launch_velocity(c->n, args, c->buf, c->vel_tw, c->vel_scratch, c->vel, main_stream(c)));
-        for (int k = 0; k < args.count; ++k) c->velocity_stale &= ~(1u << args.cascade[k]);
-        c->vel_computed += (uint64_t)args.count;
-        args.count = 0;
-        return OW_OK;
-    };
-    for (int i = 0; i < c->cascades; ++i) {
-        if (!(todo >> i & 1u)) continue;
-        const uint32_t *m = c->pc_words[i].modulate;
-        args.cascade[args.count] = i;
-        args.tile_x[args.count] = word(m[0]);
-        args.tile_y[args.count] = word(m[1]);
-        args.time[args.count] = word(m[3]);
-        if (++args.count == c->vel_slots)
-            if (ow_status st = flush(); st != OW_OK) return st;
-    }
-    return flush();
-}
-
-ow_status check_velocity_mask(const ow_context *c, uint32_t mask) {
-    if (!c) return fail(OW_ERR_INVALID, "null context");
-    if (mask & ~((1u << c->cascades) - 1u)) return fail(OW_ERR_INVALID, "cascade_mask 0x%x names layers outside [0,%d)", mask, c->cascades);
-    return OW_OK;
-}
-// every layer that has been computed
-uint32_t computed_layers(const ow_context *c) {
-    uint32_t m = 0;
-    for (int i = 0; i < c->cascades; ++i)
-        if (c->pc_valid[i]) m |= 1u << i;
-    return m;
-}
-
-// what both context forms check before they touch the context's device: counts, options, pointers (host arrays: ranges and indices)
-ow_status check_buoyancy_call(const ow_buoyancy_body *bodies, int32_t num_bodies, const ow_hull_point *hull, int32_t num_points,
-                              const float *map_scales, const ow_buoyancy_options *opts, const void *results, const void *points, bool host,
-                              ow::QueryParams *qp, ow::BuoyancyParams *bp) {
-    if (num_bodies < 0 || num_points < 0) return fail(OW_ERR_INVALID, "num_bodies and num_points must be >= 0");
-    if (ow_status st = ow::resolve_buoyancy_options(opts, qp, bp); st != OW_OK) return st;
-    if (!map_scales || (num_bodies > 0 && (!bodies || !results)) || (num_points > 0 && !hull)) return fail(OW_ERR_INVALID, "null argument");
-    if (num_points > 0 && !points && (bp->warm_start || !host))
-        return fail(OW_ERR_INVALID, host ? "OW_BUOYANCY_WARM_START needs points_inout" : "points_dev is required");
-    if (host) return ow::check_buoyancy_arrays(bodies, num_bodies, hull, num_points);
-    return OW_OK;
-}
-}  // namespace
-
-extern "C" {
-
-ow_status ow_buoyancy(ow_context *c, const ow_buoyancy_body *bodies, int32_t num_bodies, const ow_hull_point *hull, int32_t num_points,
-                      const float *map_scales, int32_t num_cascades, const ow_buoyancy_options *opts, ow_buoyancy_result *results,
-                      ow_buoyancy_point *points_inout) {
-    static_assert(sizeof(ow_buoyancy_body) == sizeof(ow::BuoyancyBody) && sizeof(ow_hull_point) == sizeof(ow::HullPoint) &&
-                      sizeof(ow_buoyancy_point) == sizeof(ow::BuoyancyPoint) && sizeof(ow_buoyancy_result) == sizeof(ow::BuoyancyResult) &&
-                      offsetof(ow_buoyancy_point, body) == offsetof(ow::BuoyancyPoint, body) &&
-                      offsetof(ow_buoyancy_result, max_residual) == offsetof(ow::BuoyancyResult, max_residual) &&
-                      offsetof(ow_buoyancy_body, point_offset) == offsetof(ow::BuoyancyBody, point_offset),
-                  "record layout");
-    ow::QueryParams qp;
-    ow::BuoyancyParams bp;
-    if (ow_status st = check_buoyancy_call(bodies, num_bodies, hull, num_points, map_scales, opts, results, points_inout, true, &qp, &bp); st != OW_OK)
-        return st;
-    if (ow_status st = check_point_query(c, 0, num_cascades); st != OW_OK) return st;
-    if (num_bodies == 0 && num_points == 0) return OW_OK;
-    OW_HIP(hipSetDevice(c->device));
-    if (bp.water_velocity)  // the velocity layers the drag is taken against, refreshed in stream order first
-        if (ow_status st = velocity_refresh(c, (1u << num_cascades) - 1u); st != OW_OK) return st;
-    const ow::SurfaceScales sc = surface_scales(map_scales, num_cascades);
-    if (ow_status st = ow::buoyancy_enqueue_host(c->n, num_cascades, c->buf, main_stream(c), &c->buoy_scratch, &c->buoy_bytes, bodies, num_bodies, hull,
-                                                 num_points, sc, qp, bp, results, points_inout, bp.water_velocity ? c->vel : nullptr);
-        st != OW_OK)
-        return st;
-    return sync_stream(c, (1u << num_cascades) - 1u);
-}
-
-ow_status ow_buoyancy_async(ow_context *c, const ow_buoyancy_body *bodies_dev, int32_t num_bodies, const ow_hull_point *hull_dev,
-                            int32_t num_points, const float *map_scales, int32_t num_cascades, const ow_buoyancy_options *opts,
-                            ow_buoyancy_result *results_dev, ow_buoyancy_point *points_dev) {
-    ow::QueryParams qp;
-    ow::BuoyancyParams bp;
-    if (ow_status st = check_buoyancy_call(bodies_dev, num_bodies, hull_dev, num_points, map_scales, opts, results_dev, points_dev, false, &qp, &bp);
-        st != OW_OK)
-        return st;
-    if (ow_status st = check_point_query(c, 0, num_cascades); st != OW_OK) return st;
-    if (num_bodies == 0 && num_points == 0) return OW_OK;
-    if (ow_status st = refuse_faulted(c, (1u << num_cascades) - 1u); st != OW_OK) return st;
-    OW_HIP(hipSetDevice(c->device));
-    if (bp.water_velocity)
-        if (ow_status st = velocity_refresh(c, (1u << num_cascades) - 1u); st != OW_OK) return st;
-    const ow::SurfaceScales sc = surface_scales(map_scales, num_cascades);
-    // main_stream(): behind the second chain's join as well as everything on the context's (or the caller's) stream
-    OW_HIP(ow::launch_buoyancy(c->n, num_cascades, c->buf, (const ow::BuoyancyBody *)bodies_dev, num_bodies, (const ow::HullPoint *)hull_dev, num_points,
-                               sc, qp, bp, (ow::BuoyancyPoint *)points_dev, (ow::BuoyancyResult *)results_dev, main_stream(c),
-                               bp.water_velocity ? c->vel : nullptr));
-    return OW_OK;
-}
-
-}  // extern "C"
-
-// ---- floating bodies (ow_rigid.h; kernels in ow_consumer.hip) ---------------------------------------------------------------------------
-
-namespace {
-// THE SELECTION RULE.  The fused kernel serialises ceil(point_count / 64) height solves per lane and substep and fills the chip with one wave
-// per body; the split form runs one lane per hull point and pays two launches per substep.  Measured per frame of 4 substeps on 1024^2 x 4 maps
-// (profiles/bodies_step.txt): with hulls of 16 points fused takes 0.72 - 0.80 of split's time for 1 .. 4096 bodies, with 64 points 0.84 - 0.96
-// (inside the run-to-run spread for most counts); from 256 points on split takes 0.59 down to 0.05 of fused's time at every body count; at
-// 16384 bodies split is ahead at 16 and 64 points too (0.86, 0.82).  The table has no rows between 64 and 256 points nor between 4096 and
-// 16384 bodies: the thresholds are the last rows where fused was not behind.
-constexpr int kBodiesFusedMaxPoints = 64;    // largest hull of the set, in points
-constexpr int kBodiesFusedMaxBodies = 4096;  // body count
-bool bodies_fused(const ow_context *c, const ow_bodies *set) {
-    if (c->bodies_mode) return c->bodies_mode == 1;
-    return set->max_points <= kBodiesFusedMaxPoints && set->A.num_bodies <= kBodiesFusedMaxBodies;
-}
-
-// the checks of ow_bodies_create / ow_bodies_set_state on the states themselves; range: per body offset, count to hold them to (or nullptr)
-ow_status check_rigid_records(const ow_rigid_body *bodies, int first, int count, const int32_t *range) {
-    for (int k = 0; k < count; ++k) {
-        const ow_rigid_body &B = bodies[k];
-        const int b = first + k;
-        const double *groups[] = {B.position, B.linear_velocity, B.angular_velocity, B.inverse_inertia, B.applied_force, B.applied_torque};
-        for (const double *g : groups)
-            for (int i = 0; i < 3; ++i)
-                if (!std::isfinite(g[i])) return fail(OW_ERR_INVALID, "body %d: state, mass properties and applied loads must be finite", b);
-        if (!std::isfinite(B.mass) || !std::isfinite(B.linear_drag) || !std::isfinite(B.quadratic_drag))
-            return fail(OW_ERR_INVALID, "body %d: mass and drag must be finite", b);
-        for (int i = 0; i < 3; ++i)
-            if (B.inverse_inertia[i] < 0.0) return fail(OW_ERR_INVALID, "body %d: inverse_inertia must be >= 0", b);
-        double n2 = 0.0;
-        for (int i = 0; i < 4; ++i) {
-            if (!std::isfinite(B.orientation[i])) return fail(OW_ERR_INVALID, "body %d: orientation must be a finite unit quaternion", b);
-            n2 += B.orientation[i] * B.orientation[i];
-        }
-        if (!(std::fabs(std::sqrt(n2) - 1.0) <= 1e-6)) return fail(OW_ERR_INVALID, "body %d: orientation must be a unit quaternion (|q| = %.9g)", b, std::sqrt(n2));
-        if (B.reserved[0] != 0u || B.reserved[1] != 0u) return fail(OW_ERR_INVALID, "body %d: ow_rigid_body.reserved must be 0", b);
-        if (range && (B.point_offset != range[2 * b] || B.point_count != range[2 * b + 1]))
-            return fail(OW_ERR_INVALID, "body %d: the hull range [%d, %d + %d) is fixed at ow_bodies_create", b, range[2 * b], range[2 * b], range[2 * b + 1]);
-    }
-    return OW_OK;
-}
-
-ow_status check_bodies_handle(const ow_context *c, const ow_bodies *set) {
-    if (!c) return fail(OW_ERR_INVALID, "null context");
-    if (!set) return fail(OW_ERR_INVALID, "null body set");
-    if (!set->ctx) return fail(OW_ERR_STATE, "the body set's context has been destroyed");
-    if (set->ctx != c) return fail(OW_ERR_INVALID, "the body set belongs to another context");
-    return OW_OK;
-}
-ow_status check_bodies_span(const ow_context *c, const ow_bodies *set, int32_t first, int32_t count, const void *records) {
-    if (ow_status st = check_bodies_handle(c, set); st != OW_OK) return st;
-    if (first < 0 || count < 0 || (int64_t)first + count > set->A.num_bodies)
-        return fail(OW_ERR_INVALID, "bodies [%d, %d + %d) outside [0, %d)", first, first, count, set->A.num_bodies);
-    if (count > 0 && !records) return fail(OW_ERR_INVALID, "null argument");
-    return OW_OK;
-}
-}  // namespace
-
-extern "C" {
-
-ow_status ow_bodies_create(ow_context *c, const ow_rigid_body *bodies, int32_t num_bodies, const ow_hull_point *hull, int32_t num_points, ow_bodies **out) {
-    static_assert(sizeof(ow_rigid_body) == sizeof(ow::RigidBody) && offsetof(ow_rigid_body, orientation) == offsetof(ow::RigidBody, orientation) &&
-                      offsetof(ow_rigid_body, mass) == offsetof(ow::RigidBody, mass) &&
-                      offsetof(ow_rigid_body, inverse_inertia) == offsetof(ow::RigidBody, inverse_inertia) &&
-                      offsetof(ow_rigid_body, applied_torque) == offsetof(ow::RigidBody, applied_torque) &&
-                      offsetof(ow_rigid_body, linear_drag) == offsetof(ow::RigidBody, linear_drag) &&
-                      offsetof(ow_rigid_body, point_offset) == offsetof(ow::RigidBody, point_offset),
-                  "record layout");
-    if (!out) return fail(OW_ERR_INVALID, "null argument");
-    *out = nullptr;
-    if (num_bodies < 1 || num_points < 0) return fail(OW_ERR_INVALID, "num_bodies must be >= 1 and num_points >= 0");
-    if (!bodies || (num_points > 0 && !hull)) return fail(OW_ERR_INVALID, "null argument");
-    std::vector<ow_buoyancy_body> ranges((size_t)num_bodies);
-    std::vector<int32_t> range((size_t)num_bodies * 2);
-    int max_points = 0;
-    for (int b = 0; b < num_bodies; ++b) {
-        std::memset(&ranges[b], 0, sizeof(ow_buoyancy_body));
-        ranges[b].point_offset = range[2 * b] = bodies[b].point_offset;
-        ranges[b].point_count = range[2 * b + 1] = bodies[b].point_count;
-        max_points = std::max(max_points, bodies[b].point_count);
-    }
-    if (ow_status st = ow::check_buoyancy_arrays(ranges.data(), num_bodies, hull, num_points); st != OW_OK) return st;
-    for (int i = 0; i < num_points; ++i)
-        if (!std::isfinite(hull[i].volume) || !std::isfinite(hull[i].half_height) || !std::isfinite(hull[i].local[0]) || !std::isfinite(hull[i].local[1]) ||
-            !std::isfinite(hull[i].local[2]))
-            return fail(OW_ERR_INVALID, "hull point %d: local, volume and half_height must be finite", i);
-    if (ow_status st = check_rigid_records(bodies, 0, num_bodies, nullptr); st != OW_OK) return st;
-    if (!c) return fail(OW_ERR_INVALID, "null context");
-    OW_HIP(hipSetDevice(c->device));
-    ow_bodies *set = new (std::nothrow) ow_bodies();
-    if (!set) return fail(OW_ERR_NOMEM, "out of host memory");
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t nb = (size_t)num_bodies, np = (size_t)num_points;
-    const size_t s_bytes = up(nb * sizeof(ow::RigidBody)), b_bytes = up(nb * sizeof(ow::BuoyancyBody)), h_bytes = up(np * sizeof(ow::HullPoint));
-    const size_t p_bytes = up(np * sizeof(ow::BuoyancyPoint)), r_bytes = up(nb * sizeof(ow::BuoyancyResult)), f_bytes = up(nb * sizeof(int32_t));
-    const size_t total = s_bytes + b_bytes + h_bytes + p_bytes + r_bytes + f_bytes;
-    if (hipMalloc(&set->block, total) != hipSuccess) {
-        (void)hipGetLastError();
-        delete set;
-        return fail(OW_ERR_NOMEM, "hipMalloc failed for %zu bytes of body set", total);
-    }
-    char *base = (char *)set->block;
-    set->ctx = c;
-    set->A.state = (ow::RigidBody *)base;
-    set->A.records = (ow::BuoyancyBody *)(base + s_bytes);
-    set->A.hull = (const ow::HullPoint *)(base + s_bytes + b_bytes);
-    set->A.pts = (ow::BuoyancyPoint *)(base + s_bytes + b_bytes + h_bytes);
-    set->A.results = (ow::BuoyancyResult *)(base + s_bytes + b_bytes + h_bytes + p_bytes);
-    set->A.flags = (int32_t *)(base + s_bytes + b_bytes + h_bytes + p_bytes + r_bytes);
-    set->A.num_bodies = num_bodies;
-    set->A.num_points = num_points;
-    set->max_points = max_points;
-    set->range = std::move(range);
-    hipStream_t s = main_stream(c);
-    if (hipMemsetAsync(set->block, 0, total, s) != hipSuccess ||
-        hipMemcpyAsync(set->A.state, bodies, nb * sizeof(ow::RigidBody), hipMemcpyHostToDevice, s) != hipSuccess ||
-        (np > 0 && hipMemcpyAsync((void *)set->A.hull, hull, np * sizeof(ow::HullPoint), hipMemcpyHostToDevice, s) != hipSuccess) ||
-        ow::launch_bodies_pose(set->A, 0, num_bodies, s) != hipSuccess || (++c->host_syncs, hipStreamSynchronize(s)) != hipSuccess) {
-        const ow_status st = fail(OW_ERR_HIP, "body set upload failed: %s", hipGetErrorString(hipGetLastError()));
-        (void)hipFree(set->block);
-        delete set;
-        return st;
-    }
-    c->body_sets.push_back(set);
-    *out = set;
-    return OW_OK;
-}
-
-void ow_bodies_destroy(ow_context *, ow_bodies *set) {
-    if (!set) return;
-    if (ow_context *c = set->ctx) {  // its own context, still alive (ow_destroy clears this field of the sets it outlives)
-        (void)hipSetDevice(c->device);
-        ++c->host_syncs;
-        (void)hipStreamSynchronize(main_stream(c));
-        c->body_sets.erase(std::remove(c->body_sets.begin(), c->body_sets.end(), set), c->body_sets.end());
-        (void)hipFree(set->block);
-    }
-    delete set;
-}
-
-ow_status ow_bodies_step(ow_context *c, ow_bodies *set, const float *map_scales, int32_t num_cascades, const ow_bodies_options *opts, int32_t substeps,
-                         double dt) {
-    if (substeps < 1 || substeps > OW_BODIES_MAX_SUBSTEPS) return fail(OW_ERR_INVALID, "substeps %d outside [1,%d]", substeps, OW_BODIES_MAX_SUBSTEPS);
-    if (!std::isfinite(dt) || !(dt > 0.0)) return fail(OW_ERR_INVALID, "dt must be finite and > 0");
-    ow::QueryParams qp;
-    ow::BuoyancyParams bp;
-    if (ow_status st = ow::resolve_buoyancy_options(opts ? &opts->buoyancy : nullptr, &qp, &bp); st != OW_OK) return st;
-    if (opts)
-        for (uint32_t r : opts->reserved)
-            if (r != 0u) return fail(OW_ERR_INVALID, "ow_bodies_options.reserved must be 0");
-    if (!map_scales) return fail(OW_ERR_INVALID, "null argument");
-    if (ow_status st = check_bodies_handle(c, set); st != OW_OK) return st;
-    if (ow_status st = check_point_query(c, 0, num_cascades); st != OW_OK) return st;
-    if (ow_status st = refuse_faulted(c, (1u << num_cascades) - 1u); st != OW_OK) return st;
-    OW_HIP(hipSetDevice(c->device));
-    if (bp.water_velocity)  // once per call: the maps do not move between the substeps of a call
-        if (ow_status st = velocity_refresh(c, (1u << num_cascades) - 1u); st != OW_OK) return st;
-    ow::RigidParams rp;
-    rp.dt = dt;
-    rp.gravity = (double)bp.gravity;  // the g of rho_g: weight and buoyancy use the same one
-    const ow::SurfaceScales sc = surface_scales(map_scales, num_cascades);
-    const bool fused = bodies_fused(c, set);
-    // main_stream(): behind the second chain's join as well as everything on the context's (or the caller's) stream
-    OW_HIP(ow::launch_bodies_step(c->n, num_cascades, c->buf, set->A, sc, qp, bp, rp, substeps, fused, main_stream(c), bp.water_velocity ? c->vel : nullptr));
-    set->substeps += (uint64_t)substeps;
-    (fused ? set->fused_launches : set->split_calls) += 1;
-    return OW_OK;
-}
-
-ow_status ow_bodies_get_state(ow_context *c, ow_bodies *set, int32_t first, int32_t count, ow_rigid_body *records) {
-    if (ow_status st = check_bodies_span(c, set, first, count, records); st != OW_OK) return st;
-    OW_HIP(hipSetDevice(c->device));
-    if (ow_status st = sync_stream(c, 0); st != OW_OK) return st;
-    if (count > 0) OW_HIP(hipMemcpy(records, set->A.state + first, (size_t)count * sizeof(ow::RigidBody), hipMemcpyDeviceToHost));
-    return OW_OK;
-}
-
-ow_status ow_bodies_set_state(ow_context *c, ow_bodies *set, int32_t first, int32_t count, const ow_rigid_body *records) {
-    if (ow_status st = check_bodies_span(c, set, first, count, records); st != OW_OK) return st;
-    if (ow_status st = check_rigid_records(records, first, count, set->range.data()); st != OW_OK) return st;
-    OW_HIP(hipSetDevice(c->device));
-    if (ow_status st = sync_stream(c, 0); st != OW_OK) return st;
-    if (count == 0) return OW_OK;
-    OW_HIP(hipMemcpy(set->A.state + first, records, (size_t)count * sizeof(ow::RigidBody), hipMemcpyHostToDevice));
-    OW_HIP(ow::launch_bodies_pose(set->A, first, count, main_stream(c)));
-    ++c->host_syncs;
-    OW_HIP(hipStreamSynchronize(main_stream(c)));
-    return OW_OK;
-}
-
-ow_status ow_bodies_get_results(ow_context *c, ow_bodies *set, int32_t first, int32_t count, ow_buoyancy_result *results) {
-    if (ow_status st = check_bodies_span(c, set, first, count, results); st != OW_OK) return st;
-    OW_HIP(hipSetDevice(c->device));
-    if (ow_status st = sync_stream(c, 0); st != OW_OK) return st;
-    if (count > 0) OW_HIP(hipMemcpy(results, set->A.results + first, (size_t)count * sizeof(ow::BuoyancyResult), hipMemcpyDeviceToHost));
-    return OW_OK;
-}
-
-ow_status ow_bodies_get_device_ptrs(ow_context *c, ow_bodies *set, void **bodies_dev, void **results_dev, void **points_dev) {
-    if (ow_status st = check_bodies_handle(c, set); st != OW_OK) return st;
-    if (bodies_dev) *bodies_dev = set->A.records;
-    if (results_dev) *results_dev = set->A.results;
-    if (points_dev) *points_dev = set->A.pts;
-    return OW_OK;
-}
-
-ow_status ow_sync_stats(const ow_context *c, uint64_t *host_syncs) {
-    if (!c || !host_syncs) return fail(OW_ERR_INVALID, "null argument");
-    *host_syncs = c->host_syncs;
-    return OW_OK;
-}
-
-ow_status ow_bodies_stats(ow_context *c, ow_bodies *set, uint64_t *substeps, uint64_t *fused_launches, uint64_t *split_calls, uint64_t *faulted_bodies) {
-    if (ow_status st = check_bodies_handle(c, set); st != OW_OK) return st;
-    if (faulted_bodies) {
-        OW_HIP(hipSetDevice(c->device));
-        if (ow_status st = sync_stream(c, 0); st != OW_OK) return st;
-        std::vector<int32_t> flags((size_t)set->A.num_bodies);
-        OW_HIP(hipMemcpy(flags.data(), set->A.flags, flags.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-        uint64_t n = 0;
-        for (int32_t f : flags) n += f != 0;
-        *faulted_bodies = n;
-    }
-    if (substeps) *substeps = set->substeps;
-    if (fused_launches) *fused_launches = set->fused_launches;
-    if (split_calls) *split_calls = set->split_calls;
-    return OW_OK;
-}
-
-}  // extern "C"
-
-namespace ow {
-ow_status resolve_raycast_options(const ow_raycast_options *o, RaycastParams *rp) {
-    if (ow_status st = resolve_query_options(o ? &o->query : nullptr, &rp->qp); st != OW_OK) return st;
-    rp->water_level = 0.0f;
-    rp->spacing = kRayDefaultSpacing;
-    rp->tolerance = kRayDefaultTolerance;
-    rp->max_samples = kRayDefaultMaxSamples;
-    if (!o) return OW_OK;
-    if (!std::isfinite(o->water_level) || !std::isfinite(o->sample_spacing) || !std::isfinite(o->tolerance))
-        return fail(OW_ERR_INVALID, "water_level, sample_spacing and tolerance must be finite");
-    if (o->max_samples < 0 || o->max_samples > kRayMaxSamples)
-        return fail(OW_ERR_INVALID, "max_samples %d outside [0,%d]", o->max_samples, kRayMaxSamples);
-    for (uint32_t r : o->reserved)
-        if (r != 0u) return fail(OW_ERR_INVALID, "ow_raycast_options.reserved must be 0");
-    rp->water_level = o->water_level;
-    if (o->sample_spacing > 0.0f) rp->spacing = o->sample_spacing;
-    if (o->tolerance > 0.0f) rp->tolerance = o->tolerance;
-    if (o->max_samples > 0) rp->max_samples = o->max_samples;
-    return OW_OK;
-}
-
-ow_status raycast_scratch(int count, Ray **in, RaycastHit **out, int *capacity, uint32_t **bound) {
-    if (!*bound && hipMalloc((void **)bound, OW_MAX_CASCADES * sizeof(uint32_t)) != hipSuccess) {
-        *bound = nullptr;
-        return fail(OW_ERR_NOMEM, "hipMalloc failed for the ray-cast bound words");
-    }
-    if (count <= *capacity) return OW_OK;
-    (void)hipFree(*in);
-    (void)hipFree(*out);
-    *in = nullptr;
-    *out = nullptr;
-    *capacity = 0;
-    const int cap = std::max(count, 1024);
-    if (hipMalloc((void **)in, (size_t)cap * sizeof(Ray)) != hipSuccess || hipMalloc((void **)out, (size_t)cap * sizeof(RaycastHit)) != hipSuccess)
-        return fail(OW_ERR_NOMEM, "hipMalloc failed for %d rays", cap);
-    *capacity = cap;
-    return OW_OK;
-}
-}  // namespace ow
-
-extern "C" {
-
-ow_status ow_raycast_surface(ow_context *c, const ow_ray *rays, int32_t count, const float *map_scales, int32_t num_cascades,
-                             const ow_raycast_options *opts, ow_raycast_hit *out) {
-    static_assert(sizeof(ow_ray) == sizeof(ow::Ray) && sizeof(ow_raycast_hit) == sizeof(ow::RaycastHit) &&
-                      offsetof(ow_raycast_hit, query) == offsetof(ow::RaycastHit, query) &&
-                      offsetof(ow_raycast_hit, slab_half_height) == offsetof(ow::RaycastHit, slab_half_height) &&
-                      offsetof(ow_ray, direction) == offsetof(ow::Ray, direction),
-                  "record layout");
-    if (ow_status st = check_point_query(c, count, num_cascades); st != OW_OK) return st;
-    ow::RaycastParams rp;
-    if (ow_status st = ow::resolve_raycast_options(opts, &rp); st != OW_OK) return st;
-    if (count == 0) return OW_OK;
-    if (!rays || !map_scales || !out) return fail(OW_ERR_INVALID, "null argument");
-    OW_HIP(hipSetDevice(c->device));
-    if (ow_status st = ow::raycast_scratch(count, &c->ray_in, &c->ray_out, &c->ray_capacity, &c->ray_bound); st != OW_OK) return st;
-    const ow::SurfaceScales sc = surface_scales(map_scales, num_cascades);
-    OW_HIP(hipMemcpyAsync(c->ray_in, rays, (size_t)count * sizeof(ow::Ray), hipMemcpyHostToDevice, main_stream(c)));
-    OW_HIP(ow::launch_raycast(c->n, num_cascades, c->buf, c->ray_in, count, sc, rp, c->ray_bound, c->ray_out, main_stream(c)));
-    OW_HIP(hipMemcpyAsync(out, c->ray_out, (size_t)count * sizeof(ow::RaycastHit), hipMemcpyDeviceToHost, main_stream(c)));
-    return sync_stream(c, (1u << num_cascades) - 1u);
-}
-
-ow_status ow_raycast_surface_async(ow_context *c, const ow_ray *rays_dev, int32_t count, const float *map_scales, int32_t num_cascades,
-                                   const ow_raycast_options *opts, ow_raycast_hit *out_dev) {
-    if (ow_status st = check_point_query(c, count, num_cascades); st != OW_OK) return st;
-    ow::RaycastParams rp;
-    if (ow_status st = ow::resolve_raycast_options(opts, &rp); st != OW_OK) return st;
-    if (count == 0) return OW_OK;
-    if (!rays_dev || !map_scales || !out_dev) return fail(OW_ERR_INVALID, "null argument");
-    if (ow_status st = refuse_faulted(c, (1u << num_cascades) - 1u); st != OW_OK) return st;
-    OW_HIP(hipSetDevice(c->device));
-    if (ow_status st = ow::raycast_scratch(0, &c->ray_in, &c->ray_out, &c->ray_capacity, &c->ray_bound); st != OW_OK) return st;
-    const ow::SurfaceScales sc = surface_scales(map_scales, num_cascades);
-    // main_stream(): behind the second chain's join as well as everything on the context's (or the caller's) stream
-    OW_HIP(ow::launch_raycast(c->n, num_cascades, c->buf, (const ow::Ray *)rays_dev, count, sc, rp, c->ray_bound, (ow::RaycastHit *)out_dev,
-                              main_stream(c)));
-    return OW_OK;
-}
-
-}  // extern "C"
-
-namespace {
-// the reference scene's material and sun (ow_render_options_default)
-void render_defaults(ow_render_options *o) {
-    std::memset(o, 0, sizeof(*o));
-    const float water[3] = {0.0100228256f, 0.019606648f, 0.0272117816f};  // Color(0.1, 0.15, 0.18).srgb_to_linear(), water.gd:14-15
-    const float foam[3] = {0.491905034f, 0.406448305f, 0.34239164f};      // Color(0.73, 0.67, 0.62).srgb_to_linear(), water.gd:17-18
-    const float sun[3] = {0.321197f, 0.18296f, 0.929171f};                // the basis' +Z column, main.tscn:113
-    const float ambient[3] = {0.05f, 0.08f, 0.10f}, sky[3] = {0.25f, 0.40f, 0.60f};
-    for (int k = 0; k < 3; ++k) {
-        o->water_color[k] = water[k];
-        o->foam_color[k] = foam[k];
-        o->light_direction[k] = sun[k];
-        o->light_color[k] = 1.0f;
-        o->ambient_color[k] = ambient[k];
-        o->sky_color[k] = sky[k];
-    }
-    o->roughness = 0.65f;       // mat_water.tres:8
-    o->normal_strength = 1.0f;  // mat_water.tres:9
-}
-
-// ow_camera -> the kernel's camera; OW_ERR_INVALID for a size out of range or reserved words.  Non-finite values pass: they make every ray invalid.
-ow_status resolve_camera(const ow_camera *cam, ow::CameraParams *cp) {
-    if (!cam) return fail(OW_ERR_INVALID, "null camera");
-    if (cam->width < 1 || cam->width > OW_RENDER_MAX_SIDE || cam->height < 1 || cam->height > OW_RENDER_MAX_SIDE)
-        return fail(OW_ERR_INVALID, "camera size %d x %d outside [1,%d]", cam->width, cam->height, OW_RENDER_MAX_SIDE);
-    for (uint32_t r : cam->reserved)
-        if (r != 0u) return fail(OW_ERR_INVALID, "ow_camera.reserved must be 0");
-    for (int k = 0; k < 3; ++k) cp->o[k] = cam->position[k];
-    for (int k = 0; k < 9; ++k) cp->B[k] = cam->basis[k];
-    cp->tan_half_fov = (float)std::tan((double)cam->fov_y_degrees * (3.14159265358979323846 / 360.0));
-    cp->aspect = (float)cam->width / (float)cam->height;
-    cp->max_distance = cam->max_distance;
-    cp->width = cam->width;
-    cp->height = cam->height;
-    return OW_OK;
-}
-
-// ow_render_options (NULL = the defaults) -> the hit's settings and the shading's; the uniform-only constants in FP64, narrowed once
-ow_status resolve_render_options(const ow_render_options *opts, ow::RaycastParams *rp, ow::ShadeParams *sp) {
-    ow_render_options def;
-    if (!opts) {
-        render_defaults(&def);
-        opts = &def;
-    }
-    if (ow_status st = ow::resolve_raycast_options(&opts->raycast, rp); st != OW_OK) return st;
-    const float *vec[6] = {opts->water_color, opts->foam_color, opts->light_direction, opts->light_color, opts->ambient_color, opts->sky_color};
-    for (const float *v : vec)
-        for (int k = 0; k < 3; ++k)
-            if (!std::isfinite(v[k])) return fail(OW_ERR_INVALID, "ow_render_options: a colour or the light direction is not finite");
-    if (!(opts->roughness >= 0.0f && opts->roughness <= 1.0f)) return fail(OW_ERR_INVALID, "roughness outside [0,1]");
-    if (!(opts->normal_strength >= 0.0f && opts->normal_strength <= 1.0f)) return fail(OW_ERR_INVALID, "normal_strength outside [0,1]");
-    if (opts->flags != 0u) return fail(OW_ERR_INVALID, "unknown render flags 0x%x", opts->flags);
-    for (uint32_t r : opts->reserved)
-        if (r != 0u) return fail(OW_ERR_INVALID, "ow_render_options.reserved must be 0");
-    const double lx = opts->light_direction[0], ly = opts->light_direction[1], lz = opts->light_direction[2];
-    const double len = std::sqrt(lx * lx + ly * ly + lz * lz);
-    if (!(len > 0.0)) return fail(OW_ERR_INVALID, "light_direction has zero length");
-    const double r = opts->roughness;
-    for (int k = 0; k < 3; ++k) {
-        sp->water_color[k] = opts->water_color[k];
-        sp->foam_color[k] = opts->foam_color[k];
-        sp->light[k] = (float)((double)opts->light_direction[k] / len);
-        sp->light_color[k] = opts->light_color[k];
-        sp->ambient_color[k] = opts->ambient_color[k];
-        sp->sky_color[k] = opts->sky_color[k];
-    }
-    sp->roughness = opts->roughness;
-    sp->normal_strength = opts->normal_strength;
-    sp->fresnel_power = (float)(5.0 * std::exp(-2.69 * r));            // water.gdshader:92
-    sp->fresnel_divisor = (float)(1.0 + 22.7 * std::pow(r, 1.5));      // water.gdshader:92
-    return OW_OK;
-}
-
-// the argument checks both forms of ow_render_view share, in this order: pointers, camera, options, context
-ow_status check_render(const ow_context *c, const ow_camera *camera, const float *map_scales, int32_t num_cascades, const ow_render_options *opts,
-                       const void *rgba, const void *pixels, ow::CameraParams *cp, ow::RaycastParams *rp, ow::ShadeParams *sp) {
-    static_assert(sizeof(ow_render_pixel) == sizeof(ow::RenderPixel) && offsetof(ow_render_pixel, dist) == offsetof(ow::RenderPixel, dist) &&
-                      offsetof(ow_render_pixel, normal) == offsetof(ow::RenderPixel, normal) &&
-                      offsetof(ow_render_pixel, color) == offsetof(ow::RenderPixel, color) && OW_RENDER_MAX_SIDE == ow::kRenderMaxSide,
-                  "record layout");
-    if (!rgba && !pixels) return fail(OW_ERR_INVALID, "null argument: both outputs");
-    if (!map_scales) return fail(OW_ERR_INVALID, "null argument");
-    if (ow_status st = resolve_camera(camera, cp); st != OW_OK) return st;
-    if (ow_status st = resolve_render_options(opts, rp, sp); st != OW_OK) return st;
-    return check_point_query(c, 0, num_cascades);
-}
-}  // namespace
-
-extern "C" {
-
-void ow_render_options_default(ow_render_options *out) {
-    if (out) render_defaults(out);
-}
-
-ow_status ow_render_view(ow_context *c, const ow_camera *camera, const float *map_scales, int32_t num_cascades, const ow_render_options *opts,
-                         void *rgba8_out, ow_render_pixel *pixels_out) {
-    ow::CameraParams cp;
-    ow::RaycastParams rp;
-    ow::ShadeParams sp;
-    if (ow_status st = check_render(c, camera, map_scales, num_cascades, opts, rgba8_out, pixels_out, &cp, &rp, &sp); st != OW_OK) return st;
-    OW_HIP(hipSetDevice(c->device));
-    if (ow_status st = ow::raycast_scratch(0, &c->ray_in, &c->ray_out, &c->ray_capacity, &c->ray_bound); st != OW_OK) return st;
-    const size_t count = (size_t)cp.width * cp.height;
-    if (rgba8_out && count > c->render_rgba_capacity) {
-        (void)hipFree(c->render_rgba);
-        c->render_rgba = nullptr;
-        c->render_rgba_capacity = 0;
-        if (hipMalloc((void **)&c->render_rgba, count * sizeof(uint32_t)) != hipSuccess) return fail(OW_ERR_NOMEM, "hipMalloc failed for %zu pixels", count);
-        c->render_rgba_capacity = count;
-    }
-    if (pixels_out && count > c->render_pixels_capacity) {
-        (void)hipFree(c->render_pixels);
-        c->render_pixels = nullptr;
-        c->render_pixels_capacity = 0;
-        if (hipMalloc((void **)&c->render_pixels, count * sizeof(ow::RenderPixel)) != hipSuccess)
-            return fail(OW_ERR_NOMEM, "hipMalloc failed for %zu pixel records", count);
-        c->render_pixels_capacity = count;
-    }
-    const ow::SurfaceScales sc = surface_scales(map_scales, num_cascades);
-    OW_HIP(ow::launch_render_view(c->n, num_cascades, c->buf, cp, sc, rp, sp, c->ray_bound, rgba8_out ? c->render_rgba : nullptr,
-                                  pixels_out ? c->render_pixels : nullptr, main_stream(c)));
-    if (rgba8_out) OW_HIP(hipMemcpyAsync(rgba8_out, c->render_rgba, count * sizeof(uint32_t), hipMemcpyDeviceToHost, main_stream(c)));
-    if (pixels_out) OW_HIP(hipMemcpyAsync(pixels_out, c->render_pixels, count * sizeof(ow::RenderPixel), hipMemcpyDeviceToHost, main_stream(c)));
-    return sync_stream(c, (1u << num_cascades) - 1u);
-}
-
-ow_status ow_render_view_async(ow_context *c, const ow_camera *camera, const float *map_scales, int32_t num_cascades, const ow_render_options *opts,
-                               void *rgba8_dev, ow_render_pixel *pixels_dev) {
-    ow::CameraParams cp;
-    ow::RaycastParams rp;
-    ow::ShadeParams sp;
-    if (ow_status st = check_render(c, camera, map_scales, num_cascades, opts, rgba8_dev, pixels_dev, &cp, &rp, &sp); st != OW_OK) return st;
-    if (((uintptr_t)rgba8_dev & 3u) || ((uintptr_t)pixels_dev & 15u)) return fail(OW_ERR_INVALID, "rgba8_dev must be 4-byte and pixels_dev 16-byte aligned");
-    if (ow_status st = refuse_faulted(c, (1u << num_cascades) - 1u); st != OW_OK) return st;
-    OW_HIP(hipSetDevice(c->device));
-    if (ow_status st = ow::raycast_scratch(0, &c->ray_in, &c->ray_out, &c->ray_capacity, &c->ray_bound); st != OW_OK) return st;
-    const ow::SurfaceScales sc = surface_scales(map_scales, num_cascades);
-    // main_stream(): behind the second chain's join as well as everything on the context's (or the caller's) stream
-    OW_HIP(ow::launch_render_view(c->n, num_cascades, c->buf, cp, sc, rp, sp, c->ray_bound, (uint32_t *)rgba8_dev, (ow::RenderPixel *)pixels_dev,
-                                  main_stream(c)));
-    return OW_OK;
-}
-
-}  // extern "C"
-
-namespace {
-// ow_mesh_options (NULL = the defaults) -> the draw's settings and the shading's: the shared fields go through resolve_render_options
-ow_status resolve_mesh_options(const ow_mesh_options *opts, ow::MeshParams *mp, ow::ShadeParams *sp) {
-    static_assert(sizeof(ow_mesh_vertex) == sizeof(ow::MeshVertex) && offsetof(ow_mesh_vertex, uv) == offsetof(ow::MeshVertex, uv) &&
-                      offsetof(ow_mesh_vertex, distance_factor) == offsetof(ow::MeshVertex, falloff) &&
-                      offsetof(ow_mesh_vertex, view_position) == offsetof(ow::MeshVertex, view) &&
-                      offsetof(ow_mesh_vertex, flags) == offsetof(ow::MeshVertex, flags) && OW_MESH_VERTEX_NOT_FINITE == ow::kMeshVertexNotFinite,
-                  "record layout");
-    ow_render_options ro;
-    render_defaults(&ro);
-    ow_query_options qo;
-    std::memset(&qo, 0, sizeof(qo));
-    mp->near = ow::kMeshDefaultNear;
-    mp->cull_back = 0;
-    mp->lane_box = ow::kMeshLaneBox;
-    mp->camera_ok = 1;
-    if (opts) {
-        for (int k = 0; k < 3; ++k) {
-            ro.water_color[k] = opts->water_color[k];
-            ro.foam_color[k] = opts->foam_color[k];
-            ro.light_direction[k] = opts->light_direction[k];
-            ro.light_color[k] = opts->light_color[k];
-            ro.ambient_color[k] = opts->ambient_color[k];
-            ro.sky_color[k] = opts->sky_color[k];
-        }
-        ro.roughness = opts->roughness;
-        ro.normal_strength = opts->normal_strength;
-        qo.flags = opts->query_flags;
-        qo.falloff_center_xz[0] = opts->falloff_center_xz[0];
-        qo.falloff_center_xz[1] = opts->falloff_center_xz[1];
-    }
-    ow::RaycastParams unused;
-    if (ow_status st = resolve_render_options(&ro, &unused, sp); st != OW_OK) return st;
-    if (ow_status st = ow::resolve_query_options(&qo, &mp->qp); st != OW_OK) return st;
-    if (!opts) return OW_OK;
-    if (!std::isfinite(opts->near)) return fail(OW_ERR_INVALID, "near is not finite");
-    if (opts->flags & ~OW_MESH_CULL_BACK) return fail(OW_ERR_INVALID, "unknown mesh flags 0x%x", opts->flags);
-    if (opts->lane_box < -1 || opts->lane_box > 64) return fail(OW_ERR_INVALID, "lane_box %d outside [-1,64]", opts->lane_box);
-    for (uint32_t r : opts->reserved)
-        if (r != 0u) return fail(OW_ERR_INVALID, "ow_mesh_options.reserved must be 0");
-    if (opts->near > 0.0f) mp->near = opts->near;
-    mp->cull_back = (opts->flags & OW_MESH_CULL_BACK) ? 1 : 0;
-    mp->lane_box = opts->lane_box == 0 ? ow::kMeshLaneBox : (opts->lane_box < 0 ? 0 : opts->lane_box);
-    return OW_OK;
-}
-
-// ow_mesh.h's mesh_camera_ok, on the host
-bool mesh_camera_ok_host(const ow::CameraParams &cp) {
-    bool ok = std::isfinite(cp.tan_half_fov) && std::isfinite(cp.aspect) && std::isfinite(cp.max_distance) && cp.max_distance > 0.0f &&
-              cp.tan_half_fov > 0.0f && cp.aspect > 0.0f;
-    for (float v : cp.o) ok = ok && std::isfinite(v);
-    for (float v : cp.B) ok = ok && std::isfinite(v);
-    return ok;
-}
-
-ow_status check_mesh_handle(const ow_context *c, const ow_mesh *m) {
-    if (!c) return fail(OW_ERR_INVALID, "null context");
-    if (!m) return fail(OW_ERR_INVALID, "null mesh");
-    if (!m->ctx) return fail(OW_ERR_STATE, "the mesh's context has been destroyed");
-    if (m->ctx != c) return fail(OW_ERR_INVALID, "the mesh belongs to another context");
-    return OW_OK;
-}
-
-// the argument checks both forms of ow_mesh_draw share: ow_render_view's, in its order, then the mesh and the origin
-ow_status check_mesh_draw(const ow_context *c, const ow_mesh *m, const ow_camera *camera, const float *origin, const float *map_scales,
-                          int32_t num_cascades, const ow_mesh_options *opts, const void *rgba, const void *pixels, ow::CameraParams *cp,
-                          ow::MeshParams *mp, ow::ShadeParams *sp) {
-    if (!rgba && !pixels) return fail(OW_ERR_INVALID, "null argument: both outputs");
-    if (!map_scales) return fail(OW_ERR_INVALID, "null argument");
-    if (ow_status st = resolve_camera(camera, cp); st != OW_OK) return st;
-    if (ow_status st = resolve_mesh_options(opts, mp, sp); st != OW_OK) return st;
-    if (ow_status st = check_point_query(c, 0, num_cascades); st != OW_OK) return st;
-    if (ow_status st = check_mesh_handle(c, m); st != OW_OK) return st;
-    if (!origin) return fail(OW_ERR_INVALID, "null origin");
-    mp->camera_ok = mesh_camera_ok_host(*cp) ? 1 : 0;
-    return OW_OK;
-}
-
-ow_status mesh_vis_scratch(ow_context *c, size_t count) {
-    if (count <= c->mesh_vis_capacity) return OW_OK;
-    if (c->mesh_vis) {  // launches already enqueued may still read the old words
-        ++c->host_syncs;
-        OW_HIP(hipStreamSynchronize(main_stream(c)));
-    }
-    (void)hipFree(c->mesh_vis);
-    c->mesh_vis = nullptr;
-    c->mesh_vis_capacity = 0;
-    if (hipMalloc((void **)&c->mesh_vis, count * sizeof(uint64_t)) != hipSuccess) return fail(OW_ERR_NOMEM, "hipMalloc failed for %zu visibility words", count);
-    c->mesh_vis_capacity = count;
-    return OW_OK;
-}
-}  // namespace
-
-extern "C" {
-
-void ow_mesh_options_default(ow_mesh_options *out) {
-    if (!out) return;
-    ow_render_options ro;
-    render_defaults(&ro);
-    std::memset(out, 0, sizeof(*out));
-    for (int k = 0; k < 3; ++k) {
-        out->water_color[k] = ro.water_color[k];
-        out->foam_color[k] = ro.foam_color[k];
-        out->light_direction[k] = ro.light_direction[k];
-        out->light_color[k] = ro.light_color[k];
-        out->ambient_color[k] = ro.ambient_color[k];
-        out->sky_color[k] = ro.sky_color[k];
-    }
-    out->roughness = ro.roughness;
-    out->normal_strength = ro.normal_strength;
-    out->near = ow::kMeshDefaultNear;
-}
-
-ow_status ow_mesh_create(ow_context *c, const float *vertices_xyz, int32_t num_vertices, const int32_t *indices, int32_t num_triangles, ow_mesh **out) {
-    if (!out) return fail(OW_ERR_INVALID, "null argument");
-    *out = nullptr;
-    if (num_vertices < 1 || num_triangles < 1) return fail(OW_ERR_INVALID, "num_vertices and num_triangles must be >= 1");
-    if (!vertices_xyz || !indices) return fail(OW_ERR_INVALID, "null argument");
-    for (size_t i = 0; i < (size_t)num_triangles * 3; ++i)
-        if (indices[i] < 0 || indices[i] >= num_vertices)
-            return fail(OW_ERR_INVALID, "triangle %zu: index %d outside [0,%d)", i / 3, indices[i], num_vertices);
-    if (!c) return fail(OW_ERR_INVALID, "null context");
-    OW_HIP(hipSetDevice(c->device));
-    ow_mesh *m = new (std::nothrow) ow_mesh();
-    if (!m) return fail(OW_ERR_NOMEM, "out of host memory");
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t nv = (size_t)num_vertices, nt = (size_t)num_triangles;
-    const size_t l_bytes = up(nv * 3 * sizeof(float)), i_bytes = up(nt * 3 * sizeof(int32_t)), v_bytes = up(nv * sizeof(ow::MeshVertex));
-    const size_t total = l_bytes + i_bytes + v_bytes + 256;
-    if (hipMalloc(&m->block, total) != hipSuccess) {
-        (void)hipGetLastError();
-        delete m;
-        return fail(OW_ERR_NOMEM, "hipMalloc failed for %zu bytes of mesh", total);
-    }
-    char *base = (char *)m->block;
-    m->ctx = c;
-    m->A.local = (const float *)base;
-    m->A.indices = (const int32_t *)(base + l_bytes);
-    m->A.verts = (ow::MeshVertex *)(base + l_bytes + i_bytes);
-    m->A.counters = (uint32_t *)(base + l_bytes + i_bytes + v_bytes);
-    m->A.num_vertices = num_vertices;
-    m->A.num_triangles = num_triangles;
-    hipStream_t s = main_stream(c);
-    if (hipMemsetAsync(m->block, 0, total, s) != hipSuccess ||
-        hipMemcpyAsync((void *)m->A.local, vertices_xyz, nv * 3 * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess ||
-        hipMemcpyAsync((void *)m->A.indices, indices, nt * 3 * sizeof(int32_t), hipMemcpyHostToDevice, s) != hipSuccess ||
-        (++c->host_syncs, hipStreamSynchronize(s)) != hipSuccess) {
-        const ow_status st = fail(OW_ERR_HIP, "mesh upload failed: %s", hipGetErrorString(hipGetLastError()));
-        (void)hipFree(m->block);
-        delete m;
-        return st;
-    }
-    c->meshes.push_back(m);
-    *out = m;
-    return OW_OK;
-}
-
-void ow_mesh_destroy(ow_context *, ow_mesh *m) {
-    if (!m) return;
-    if (ow_context *c = m->ctx) {  // its own context, still alive (ow_destroy clears this field of the meshes it outlives)
-        (void)hipSetDevice(c->device);
-        ++c->host_syncs;
-        (void)hipStreamSynchronize(main_stream(c));
-        c->meshes.erase(std::remove(c->meshes.begin(), c->meshes.end(), m), c->meshes.end());
-        (void)hipFree(m->block);
-    }
-    delete m;
-}
-
-ow_status ow_mesh_displace(ow_context *c, ow_mesh *m, const float *origin, const float *map_scales, int32_t num_cascades, const ow_mesh_options *opts,
-                           const ow_camera *camera, ow_mesh_vertex *vertices_out) {
-    if (!map_scales) return fail(OW_ERR_INVALID, "null argument");
-    ow::CameraParams cp;
-    std::memset(&cp, 0, sizeof(cp));
-    if (camera) {
-        ow_camera sized = *camera;  // the image size is not read here
-        sized.width = sized.height = 1;
-        if (ow_status st = resolve_camera(&sized, &cp); st != OW_OK) return st;
-    }
-    ow::MeshParams mp;
-    ow::ShadeParams sp;
-    if (ow_status st = resolve_mesh_options(opts, &mp, &sp); st != OW_OK) return st;
-    if (ow_status st = check_point_query(c, 0, num_cascades); st != OW_OK) return st;
-    if (ow_status st = check_mesh_handle(c, m); st != OW_OK) return st;
-    if (!origin) return fail(OW_ERR_INVALID, "null origin");
-    mp.camera_ok = camera && mesh_camera_ok_host(cp) ? 1 : 0;  // a camera that is not finite: view positions are zeros, as without one
-    OW_HIP(hipSetDevice(c->device));
-    const ow::SurfaceScales sc = surface_scales(map_scales, num_cascades);
-    OW_HIP(ow::launch_mesh_vertices(c->n, num_cascades, c->buf, m->A, sc, mp, cp, camera != nullptr, origin, main_stream(c)));
-    if (vertices_out)
-        OW_HIP(hipMemcpyAsync(vertices_out, m->A.verts, (size_t)m->A.num_vertices * sizeof(ow::MeshVertex), hipMemcpyDeviceToHost, main_stream(c)));
-    return sync_stream(c, (1u << num_cascades) - 1u);
-}
-
-ow_status ow_mesh_get_device_ptrs(ow_context *c, ow_mesh *m, void **vertices_dev, void **visibility_dev) {
-    if (ow_status st = check_mesh_handle(c, m); st != OW_OK) return st;
-    if (vertices_dev) *vertices_dev = m->A.verts;
-    if (visibility_dev) *visibility_dev = c->mesh_vis;
-    return OW_OK;
-}
-
-ow_status ow_mesh_draw(ow_context *c, ow_mesh *m, const ow_camera *camera, const float *origin, const float *map_scales, int32_t num_cascades,
-                       const ow_mesh_options *opts, void *rgba8_out, ow_render_pixel *pixels_out) {
-    ow::CameraParams cp;
-    ow::MeshParams mp;
-    ow::ShadeParams sp;
-    if (ow_status st = check_mesh_draw(c, m, camera, origin, map_scales, num_cascades, opts, rgba8_out, pixels_out, &cp, &mp, &sp); st != OW_OK) return st;
-    OW_HIP(hipSetDevice(c->device));
-    const size_t count = (size_t)cp.width * cp.height;
-    if (ow_status st = mesh_vis_scratch(c, count); st != OW_OK) return st;
-    if (rgba8_out && count > c->render_rgba_capacity) {
-        (void)hipFree(c->render_rgba);
-        c->render_rgba = nullptr;
-        c->render_rgba_capacity = 0;
-        if (hipMalloc((void **)&c->render_rgba, count * sizeof(uint32_t)) != hipSuccess) return fail(OW_ERR_NOMEM, "hipMalloc failed for %zu pixels", count);
-        c->render_rgba_capacity = count;
-    }
-    if (pixels_out && count > c->render_pixels_capacity) {
-        (void)hipFree(c->render_pixels);
-        c->render_pixels = nullptr;
-        c->render_pixels_capacity = 0;
-        if (hipMalloc((void **)&c->render_pixels, count * sizeof(ow::RenderPixel)) != hipSuccess)
-            return fail(OW_ERR_NOMEM, "hipMalloc failed for %zu pixel records", count);
-        c->render_pixels_capacity = count;
-    }
-    const ow::SurfaceScales sc = surface_scales(map_scales, num_cascades);
-    OW_HIP(ow::launch_mesh_draw(c->n, num_cascades, c->buf, m->A, sc, mp, cp, sp, origin, c->mesh_vis, rgba8_out ? c->render_rgba : nullptr,
-                                pixels_out ? c->render_pixels : nullptr, main_stream(c)));
-    ++m->draws;
-    if (rgba8_out) OW_HIP(hipMemcpyAsync(rgba8_out, c->render_rgba, count * sizeof(uint32_t), hipMemcpyDeviceToHost, main_stream(c)));
-    if (pixels_out) OW_HIP(hipMemcpyAsync(pixels_out, c->render_pixels, count * sizeof(ow::RenderPixel), hipMemcpyDeviceToHost, main_stream(c)));
-    return sync_stream(c, (1u << num_cascades) - 1u);
-}
-
-ow_status ow_mesh_draw_async(ow_context *c, ow_mesh *m, const ow_camera *camera, const float *origin, const float *map_scales, int32_t num_cascades,
-                             const ow_mesh_options *opts, void *rgba8_dev, ow_render_pixel *pixels_dev) {
-    ow::CameraParams cp;
-    ow::MeshParams mp;
-    ow::ShadeParams sp;
-    if (ow_status st = check_mesh_draw(c, m, camera, origin, map_scales, num_cascades, opts, rgba8_dev, pixels_dev, &cp, &mp, &sp); st != OW_OK) return st;
-    if (((uintptr_t)rgba8_dev & 3u) || ((uintptr_t)pixels_dev & 15u)) return fail(OW_ERR_INVALID, "rgba8_dev must be 4-byte and pixels_dev 16-byte aligned");
-    if (ow_status st = refuse_faulted(c, (1u << num_cascades) - 1u); st != OW_OK) return st;
-    OW_HIP(hipSetDevice(c->device));
-    if (ow_status st = mesh_vis_scratch(c, (size_t)cp.width * cp.height); st != OW_OK) return st;
-    const ow::SurfaceScales sc = surface_scales(map_scales, num_cascades);
-    // main_stream(): behind the second chain's join as well as everything on the context's (or the caller's) stream
-    OW_HIP(ow::launch_mesh_draw(c->n, num_cascades, c->buf, m->A, sc, mp, cp, sp, origin, c->mesh_vis, (uint32_t *)rgba8_dev, (ow::RenderPixel *)pixels_dev,
-                                main_stream(c)));
-    ++m->draws;
-    return OW_OK;
-}
-
-ow_status ow_mesh_stats(ow_context *c, ow_mesh *m, uint64_t *draws, uint64_t *skipped, uint64_t *culled, uint64_t *per_lane, uint64_t *cooperative) {
-    if (ow_status st = check_mesh_handle(c, m); st != OW_OK) return st;
-    if (skipped || culled || per_lane || cooperative) {
-        OW_HIP(hipSetDevice(c->device));
-        if (ow_status st = sync_stream(c, 0); st != OW_OK) return st;
-        uint32_t w[4] = {0, 0, 0, 0};
-        OW_HIP(hipMemcpy(w, m->A.counters, sizeof(w), hipMemcpyDeviceToHost));
-        if (skipped) *skipped = w[ow::kTriSkipped];
-        if (culled) *culled = w[ow::kTriCulled];
-        if (per_lane) *per_lane = w[ow::kTriLane];
-        if (cooperative) *cooperative = w[ow::kTriWave];
-    }
-    if (draws) *draws = m->draws;
-    return OW_OK;
-}
-
-ow_status ow_update_velocity(ow_context *c, uint32_t cascade_mask) {
-    if (ow_status st = check_velocity_mask(c, cascade_mask); st != OW_OK) return st;
-    if (cascade_mask == 0) return OW_OK;
-    OW_HIP(hipSetDevice(c->device));
-    return velocity_refresh(c, cascade_mask);
-}
-
-ow_status ow_get_velocity_ptrs(ow_context *c, void **velocity_map, size_t *layer_stride_bytes) {
-    if (!c) return fail(OW_ERR_INVALID, "null context");
-    if (!velocity_map && !layer_stride_bytes) return fail(OW_ERR_INVALID, "null output");
-    OW_HIP(hipSetDevice(c->device));
-    if (ow_status st = velocity_buffers(c); st != OW_OK) return st;
-    if (ow_status st = velocity_refresh(c, computed_layers(c)); st != OW_OK) return st;
-    if (velocity_map) *velocity_map = c->vel;
-    if (layer_stride_bytes) *layer_stride_bytes = plane(c) * sizeof(ow::u16x4);
-    return OW_OK;
-}
-
-ow_status ow_get_velocity_map(ow_context *c, int32_t cascade, void *velocity_rgba16f) {
-    if (ow_status st = check_cascade(c, cascade); st != OW_OK) return st;
-    if (!velocity_rgba16f) return fail(OW_ERR_INVALID, "null output");
-    OW_HIP(hipSetDevice(c->device));
-    if (ow_status st = velocity_refresh(c, 1u << cascade); st != OW_OK) return st;
-    OW_HIP(hipMemcpyAsync(velocity_rgba16f, c->vel + cascade * plane(c), plane(c) * sizeof(ow::u16x4), hipMemcpyDeviceToHost, main_stream(c)));
-    return sync_stream(c, 1u << cascade);
-}
-
-ow_status ow_velocity_stats(const ow_context *c, uint64_t *layers_computed, uint64_t *layers_skipped) {
-    if (!c) return fail(OW_ERR_INVALID, "null context");
-    if (layers_computed) *layers_computed = c->vel_computed;
-    if (layers_skipped) *layers_skipped = c->vel_skipped;
-    return OW_OK;
-}
-
-ow_status ow_query_velocity(ow_context *c, const float *xz, int32_t count, const float *map_scales, int32_t num_cascades,
-                            const ow_query_options *opts, ow_surface_velocity *out) {
-    static_assert(sizeof(ow_surface_velocity) == sizeof(ow::SurfaceVelocity) && offsetof(ow_surface_velocity, converged) == offsetof(ow::SurfaceVelocity, converged),
-                  "record layout");
-    static_assert(sizeof(ow::SurfaceQuery) >= sizeof(ow::SurfaceVelocity), "the record buffer holds either kind");
-    if (ow_status st = check_point_query(c, count, num_cascades); st != OW_OK) return st;
-    ow::QueryParams qp;
-    if (ow_status st = ow::resolve_query_options(opts, &qp); st != OW_OK) return st;
-    if (count == 0) return OW_OK;
-    if (!xz || !map_scales || !out) return fail(OW_ERR_INVALID, "null argument");
-    OW_HIP(hipSetDevice(c->device));
-    if (ow_status st = velocity_refresh(c, (1u << num_cascades) - 1u); st != OW_OK) return st;
-    if (ow_status st = query_scratch(c, count); st != OW_OK) return st;
-    const ow::SurfaceScales sc = surface_scales(map_scales, num_cascades);
-    OW_HIP(hipMemcpyAsync(c->query_xz, xz, (size_t)count * 2 * sizeof(float), hipMemcpyHostToDevice, main_stream(c)));
-    OW_HIP(ow::launch_query_velocity(c->n, num_cascades, c->buf, c->vel, c->query_xz, count, sc, qp, (ow::SurfaceVelocity *)c->query_out, main_stream(c)));
-    OW_HIP(hipMemcpyAsync(out, c->query_out, (size_t)count * sizeof(ow::SurfaceVelocity), hipMemcpyDeviceToHost, main_stream(c)));
-    return sync_stream(c, (1u << num_cascades) - 1u);
-}
-
-ow_status ow_query_velocity_async(ow_context *c, const float *xz_dev, int32_t count, const float *map_scales, int32_t num_cascades,
-                                  const ow_query_options *opts, ow_surface_velocity *out_dev) {
-    if (ow_status st = check_point_query(c, count, num_cascades); st != OW_OK) return st;
-    ow::QueryParams qp;
-    if (ow_status st = ow::resolve_query_options(opts, &qp); st != OW_OK) return st;
-    if (count == 0) return OW_OK;
-    if (!xz_dev || !map_scales || !out_dev) return fail(OW_ERR_INVALID, "null argument");
-    if (ow_status st = refuse_faulted(c, (1u << num_cascades) - 1u); st != OW_OK) return st;
-    OW_HIP(hipSetDevice(c->device));
-    if (ow_status st = velocity_refresh(c, (1u << num_cascades) - 1u); st != OW_OK) return st;
-    const ow::SurfaceScales sc = surface_scales(map_scales, num_cascades);
-    // main_stream(): behind the second chain's join as well as everything on the context's (or the caller's) stream
-    OW_HIP(ow::launch_query_velocity(c->n, num_cascades, c->buf, c->vel, xz_dev, count, sc, qp, (ow::SurfaceVelocity *)out_dev, main_stream(c)));
     return OW_OK;
 }
 

@@ -10,6 +10,9 @@ hipcc $F "$@" -ffp-contract=off -c $C/ow_spectrum.hip -o $out/$name/ow_spectrum.
 hipcc $F "$@" -c $C/ow_runtime.hip -o $out/$name/ow_runtime.o &
 hipcc $F "$@" -ffp-contract=off -c $C/ow_consumer.hip -o $out/$name/ow_consumer.o &
 hipcc $F "$@" -c $C/ow_group.hip -o $out/$name/ow_group.o &
+hipcc $F "$@" -c $C/ow_consumer_host.hip -o $out/$name/ow_consumer_host.o &
+hipcc $F "$@" -c $C/ow_velocity.hip -o $out/$name/ow_velocity.o &
+hipcc $F "$@" -ffp-contract=off -c $C/ow_mesh.hip -o $out/$name/ow_mesh.o &
 wait
 hipcc --offload-arch=gfx950 -shared -o $out/$name.so $out/$name/*.o
 echo $out/$name.so

@@ -20,7 +20,8 @@ import query_twin as T
 from godotoceanwaves_amd import _lib, build
 from godotoceanwaves_amd.presets import UPDATE_DELTA, cascade_preset
 from godotoceanwaves_amd.wave_generator import WaveGenerator as W
-from test_surface_query import cpu_query, generated_maps, gpu_maps, harness as query_harness, make_gen, maps_u16, scales_of  # noqa: F401
+from test_surface_query import (cpu_query, generated_maps, gpu_maps, harness as query_harness, make_gen, maps_u16, scales_of,  # noqa: F401
+                                smallest_context)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "godotoceanwaves_amd", "csrc")
@@ -653,3 +654,41 @@ def test_example_floats_a_box(tmp_path):
     assert r.returncode == 0, r.stderr
     out = dict(kv.split("=") for kv in r.stdout.split())
     assert out["finite"] == "1" and out["afloat"] == "1", r.stdout
+
+
+def scratch_bytes(num_bodies, num_points):
+    """what ow_buoyancy's device scratch holds for a call: its four arrays, each rounded up to 256 bytes"""
+    def up(x):
+        return (x + 255) & ~255
+    return (up(num_bodies * W.BUOYANCY_BODY.itemsize) + up(num_points * W.HULL_POINT.itemsize) + up(num_points * W.BUOYANCY_POINT.itemsize) +
+            up(num_bodies * W.BUOYANCY_RESULT.itemsize))
+
+
+@pytest.mark.gpu
+def test_buoyancy_scratch_grows_past_its_floor_and_stays(harness):
+    """A small scene, one hull whose arrays need one hull point more than the scratch's floor of 1 MiB (the block is replaced), the small scene
+    again: cold and warm, every call returns the CPU build's results and per-point records"""
+    gen, sc, d, _ = smallest_context()
+    floor = 1 << 20
+    big = next(k for k in range(1, floor) if scratch_bytes(1, k) > floor)
+    assert scratch_bytes(1, big - 1) <= floor < scratch_bytes(1, big)
+    side = math.ceil(big ** (1.0 / 3.0))
+    wide = np.zeros(1, W.BUOYANCY_BODY)
+    wide["transform"][0, :9] = np.eye(3, dtype=np.float32).ravel()
+    wide["transform"][0, 9:] = (3.0, -0.4, -7.0)
+    wide["point_offset"], wide["point_count"] = 0, big
+    wide_hull = W.box_hull((60.0, 2.0, 45.0), (side, side, side))[:big]
+    assert len(wide_hull) == big
+    small = drive_scene(3, (3, 2, 4), seed=5, spread=100.0)
+    for what, (bodies, hull) in (("small", small), ("one record past 1 MiB", (wide, wide_hull)), ("small again", small)):
+        got_pts = np.zeros(len(hull), W.BUOYANCY_POINT)
+        got = gen.buoyancy(bodies, hull, sc, None, points=got_pts)
+        want, want_pts = cpu_buoyancy(harness, d, sc, bodies, hull)
+        assert got_pts.tobytes() == want_pts.tobytes() and got.tobytes() == want.tobytes(), what
+        moved = bodies.copy()
+        moved["transform"][:, 9:] += np.float32(0.3)
+        got_w = gen.buoyancy(moved, hull, sc, {"warm_start": True}, points=got_pts)
+        want_w, want_pts = cpu_buoyancy(harness, d, sc, moved, hull, {"warm_start": True}, points=want_pts)
+        assert got_pts.tobytes() == want_pts.tobytes() and got_w.tobytes() == want_w.tobytes(), (what, "warm")
+        assert np.isfinite(got["force"]).all() and got["submerged_volume"].max() > 0.0, what
+    gen.free()

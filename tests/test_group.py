@@ -14,6 +14,8 @@ import helpers as H
 from godotoceanwaves_amd import WaveCascadeParameters, WaveGenerator, WaveGeneratorGroup, _lib
 from godotoceanwaves_amd.presets import UPDATE_DELTA, cascade_preset
 from oracle import oracle as O
+from test_raycast import camera_rays, cpu_raycast, harness as ray_harness  # noqa: F401
+from test_surface_query import GROW_POINTS, assert_same_records, cpu_query, cpu_sample, harness as query_harness, scales_of  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -349,4 +351,28 @@ def test_link_info_says_how_each_shard_reaches_the_root(force_peer):
     assert lib.ow_query_link(0, 0, C.byref(lk)) == _lib.OW_OK and lk.same_device == 1
     assert lib.ow_query_link(0, 99, C.byref(lk)) == _lib.OW_ERR_INVALID      # no such device
     assert lib.ow_group_link_info(grp.group, 7, C.byref(lk)) == _lib.OW_ERR_INVALID
+    grp.free()
+
+
+def test_group_scratch_on_the_root_device_grows_past_its_floors_and_stays(query_harness, ray_harness):
+    """A two-shard group on one device: points at 16, 4 097 and 16 (ow_group_sample_surface and ow_group_query_surface share the scratch) and
+    rays at 8, 1 025 and 8, against the CPU builds over the gathered arrays"""
+    grp = WaveGeneratorGroup()
+    grp.map_size = 128
+    grp.init_gpu([0, 0], 1)
+    params = [WaveCascadeParameters(**cascade_preset(ci)) for ci in (0, 1)]
+    grp.run(UPDATE_DELTA, params, 3)
+    grp.gather_begin()
+    grp.gather_wait()
+    sc = scales_of(params)
+    maps = [grp.get_maps(c) for c in range(2)]
+    d, m = np.stack([mp[0] for mp in maps]), np.stack([mp[1] for mp in maps])
+    for k, count in enumerate(GROW_POINTS):
+        xz = np.random.default_rng(90 + k).uniform(-300, 300, (count, 2)).astype(np.float32)
+        assert_same_records(grp.sample_surface(xz, sc), cpu_sample(query_harness, d, m, sc, xz), ("sample", count))
+        assert_same_records(grp.query_surface(xz, sc), cpu_query(query_harness, d, m, sc, xz), ("query", count))
+        assert_same_records(grp.sample_surface(xz[::-1], sc), cpu_sample(query_harness, d, m, sc, xz[::-1]), ("sample again", count))
+    for k, count in enumerate((8, 1025, 8)):
+        rays = camera_rays(count, (2, 300), (2, 80), seed=95 + k)
+        assert_same_records(grp.raycast_surface(rays, sc), cpu_raycast(ray_harness, d, m, sc, rays), ("rays", count))
     grp.free()

@@ -24,9 +24,10 @@ from godotoceanwaves_amd.presets import UPDATE_DELTA
 from godotoceanwaves_amd.wave_generator import WaveGenerator as W
 from edge_presets import edge_presets
 from test_raycast import calm_maps
-from test_render_view import (BELOW, DEFAULTS, HIT, INVALID, camera_words, cpu_render, look, shade_words, uniforms_of,  # noqa: F401
-                              harness as render_harness)
-from test_surface_query import cpu_sample, generated_maps, gpu_maps, harness as query_harness, make_gen, maps_u16, scales_of  # noqa: F401
+from test_render_view import (BELOW, DEFAULTS, GPU_CAM, GROW_SIZES, HIT, INVALID, assert_same_image, camera_words, cpu_render, look,  # noqa: F401
+                              render_outputs, shade_words, uniforms_of, harness as render_harness)
+from test_surface_query import (cpu_sample, generated_maps, gpu_maps, harness as query_harness, make_gen, maps_u16, scales_of,  # noqa: F401
+                                smallest_context)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "godotoceanwaves_amd", "csrc")
@@ -811,3 +812,72 @@ def test_the_c_example_writes_the_python_wrappers_image(tmp_path):
     stats = gen.mesh_stats(handle)
     assert int(kv["triangles"]) == len(mesh[1]) == sum(stats[k] for k in ("skipped", "culled", "per_lane", "cooperative"))
     gen.mesh_destroy(handle)
+
+
+# ---- 12. the grow-only scratch: the visibility words, and the pixel blocks shared with ow_render_view -------------------------------------------
+
+def draw_outputs(gen, handle, cam, origin, sc, rgba=True, pixels=True):
+    """ow_mesh_draw with either output left out (the wrapper always asks for the RGBA words)"""
+    sc = np.ascontiguousarray(sc, np.float32).reshape(-1, 4)
+    org = np.ascontiguousarray(origin, np.float32).reshape(3)
+    o = gen.mesh_options(None, cam)
+    img = np.zeros((cam.height, cam.width, 4), np.uint8) if rgba else None
+    rec = np.zeros((cam.height, cam.width), W.RENDER_PIXEL) if pixels else None
+    _lib.check(gen._lib.ow_mesh_draw(gen.context, handle.handle, C.byref(cam), org.ctypes.data, sc.ctypes.data, len(sc),
+                                     C.byref(o) if o is not None else None, img.ctypes.data if rgba else None, rec.ctypes.data if pixels else None))
+    return img, rec
+
+
+@pytest.mark.gpu
+def test_draw_scratch_grows_and_stays_and_is_shared_with_the_view(harness, render_harness):
+    """One context: draws of 8 x 8, 40 x 24 and 8 x 8 with both outputs, the RGBA words alone and the records alone; then a view and a draw
+    of different sizes in turn (they share the pixel blocks): the CPU build's picture every time"""
+    gen, sc, d, m = smallest_context()
+    mesh, origin = grid(), (1.0, 0.0, 2.0)
+    handle = gen.mesh_create(*mesh)
+    for k, (w, h) in enumerate(GROW_SIZES):
+        cam = look(**dict(TWIN_CAM, width=w, height=h))
+        want = cpu_draw(harness, d, m, sc, mesh, origin, cam)
+        assert_same_picture(gpu_draw(gen, handle, cam, origin, sc), want, (k, w, h))
+        assert draw_outputs(gen, handle, cam, origin, sc, pixels=False)[0].tobytes() == want["rgba"].tobytes(), (k, w, h)
+        rec = draw_outputs(gen, handle, cam, origin, sc, rgba=False)[1]
+        for f in W.RENDER_PIXEL.names:
+            assert rec[f].tobytes() == want["rec"][f].tobytes(), (k, w, h, f)
+    for view_size, draw_size in (((52, 30), (8, 8)), ((8, 8), (52, 30))):
+        vcam = look(width=view_size[0], height=view_size[1], **GPU_CAM)
+        dcam = look(**dict(TWIN_CAM, width=draw_size[0], height=draw_size[1]))
+        assert_same_image(render_outputs(gen, vcam, sc), cpu_render(render_harness, d, m, sc, vcam), ("view", view_size))
+        assert_same_picture(gpu_draw(gen, handle, dcam, origin, sc), cpu_draw(harness, d, m, sc, mesh, origin, dcam), ("draw", draw_size))
+        assert_same_image(render_outputs(gen, vcam, sc), cpu_render(render_harness, d, m, sc, vcam), ("view again", view_size))
+    gen.mesh_destroy(handle)
+    gen.free()
+
+
+@pytest.mark.gpu
+def test_async_draw_regrows_the_visibility_words_behind_one_synchronisation(harness):
+    """An asynchronous draw of 8 x 8 and, with nothing in between, one of 40 x 24: the first allocation synchronises nothing, the regrow
+    synchronises once (the first draw may still be reading the old words), and both pictures are the CPU build's"""
+    import torch
+    gen, sc, d, m = smallest_context()
+    mesh, origin = grid(), (0.0, 0.0, 0.0)
+    handle = gen.mesh_create(*mesh)
+    cams = [look(**dict(TWIN_CAM, width=w, height=h)) for w, h in GROW_SIZES[:2]]
+    bufs = [(torch.zeros((c.width * c.height, 4), dtype=torch.uint8, device="cuda:0"),
+             torch.zeros((c.width * c.height, W.RENDER_PIXEL.itemsize), dtype=torch.uint8, device="cuda:0")) for c in cams]
+    torch.cuda.synchronize()
+    syncs = gen.sync_stats()
+    gen.mesh_draw_async(handle, cams[0], origin, sc, bufs[0][0], bufs[0][1])
+    assert gen.sync_stats() == syncs
+    gen.mesh_draw_async(handle, cams[1], origin, sc, bufs[1][0], bufs[1][1])
+    assert gen.sync_stats() == syncs + 1
+    gen.mesh_draw_async(handle, cams[0], origin, sc, bufs[0][0], bufs[0][1])     # fits what is there: nothing more
+    assert gen.sync_stats() == syncs + 1
+    gen.sync()
+    for cam, (rgba_dev, rec_dev) in zip(cams, bufs):
+        want = cpu_draw(harness, d, m, sc, mesh, origin, cam)
+        got_rec = np.frombuffer(rec_dev.cpu().numpy().tobytes(), W.RENDER_PIXEL).reshape(cam.height, cam.width)
+        for f in W.RENDER_PIXEL.names:
+            assert got_rec[f].tobytes() == want["rec"][f].tobytes(), (cam.width, f)
+        assert rgba_dev.cpu().numpy().tobytes() == want["rgba"].tobytes(), cam.width
+    gen.mesh_destroy(handle)
+    gen.free()

@@ -18,7 +18,8 @@ import raycast_twin as RT
 from godotoceanwaves_amd import _lib, build
 from godotoceanwaves_amd.presets import UPDATE_DELTA
 from godotoceanwaves_amd.wave_generator import WaveGenerator as W
-from test_surface_query import cpu_query, generated_maps, gpu_maps, harness as query_harness, make_gen, maps_u16, scales_of  # noqa: F401
+from test_surface_query import (cpu_query, generated_maps, gpu_maps, harness as query_harness, make_gen, maps_u16, scales_of,  # noqa: F401
+                                smallest_context)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "godotoceanwaves_amd", "csrc")
@@ -483,3 +484,16 @@ def test_group_ray_cast_equals_a_single_context():
     grp.gather_wait()
     for opts in (None, {"falloff_center": (-30.0, 60.0), "water_level": 0.25}):
         assert grp.raycast_surface(rays, sc, opts).tobytes() == single.raycast_surface(rays, sc, opts).tobytes()
+
+
+@pytest.mark.gpu
+def test_ray_scratch_grows_past_its_floor_and_stays(harness):
+    """8 rays, 1 025 (one past the scratch's floor of 1 024: the block is replaced), 8 again on one context: the CPU build's records each time"""
+    gen, sc, d, m = smallest_context()
+    for k, count in enumerate((8, 1025, 8)):
+        rays = camera_rays(count, (2, 300), (2, 80), seed=50 + k)
+        got, want = gen.raycast_surface(rays, sc), cpu_raycast(harness, d, m, sc, rays)
+        for f in W.RAYCAST_HIT.names:
+            assert got[f].tobytes() == want[f].tobytes(), (count, f)
+        assert ((got["status"] & HIT) != 0).any(), count
+    gen.free()

@@ -22,7 +22,7 @@ from godotoceanwaves_amd import _lib, build
 from godotoceanwaves_amd.presets import UPDATE_DELTA
 from godotoceanwaves_amd.wave_generator import WaveGenerator as W
 from test_raycast import SPACING, TOL, calm_maps, cpu_raycast, harness as ray_harness, swell_maps  # noqa: F401
-from test_surface_query import generated_maps, gpu_maps, make_gen, maps_u16, scales_of
+from test_surface_query import generated_maps, gpu_maps, make_gen, maps_u16, scales_of, smallest_context
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "godotoceanwaves_amd", "csrc")
@@ -684,3 +684,43 @@ def test_the_c_example_writes_the_python_wrappers_image(tmp_path):
     rgba, rec = gen.render_view(cam, scales_of(params), {"falloff": True})
     assert np.frombuffer(raw[len(head):], np.uint8).reshape(24, 40, 3).tobytes() == rgba[..., :3].tobytes()
     assert abs(((rec["status"] & HIT) != 0).mean() - float(kv["hit_share"])) < 1e-3
+
+
+# ---- 14. the grow-only pixel scratch -------------------------------------------------------------------------------------------------------
+
+GROW_SIZES = ((8, 8), (40, 24), (8, 8))   # the scratch is sized exactly: the second image replaces both blocks, the third fits what is there
+
+
+def render_outputs(gen, cam, sc, rgba=True, pixels=True):
+    """ow_render_view with either output left out (the wrapper always asks for the RGBA words)"""
+    sc = np.ascontiguousarray(sc, np.float32).reshape(-1, 4)
+    o = gen.render_options(None, cam)
+    img = np.zeros((cam.height, cam.width, 4), np.uint8) if rgba else None
+    rec = np.zeros((cam.height, cam.width), W.RENDER_PIXEL) if pixels else None
+    _lib.check(gen._lib.ow_render_view(gen.context, C.byref(cam), sc.ctypes.data, len(sc), C.byref(o) if o is not None else None,
+                                       img.ctypes.data if rgba else None, rec.ctypes.data if pixels else None))
+    return img, rec
+
+
+@pytest.mark.gpu
+def test_pixel_scratch_grows_and_stays_with_either_output(harness):
+    """8 x 8, 40 x 24, 8 x 8 on one context, each with both outputs, the RGBA words alone and the records alone (the two blocks grow
+    independently): the CPU build's image every time"""
+    gen, sc, d, m = smallest_context()
+    for k, (w, h) in enumerate(GROW_SIZES):
+        cam = look(width=w, height=h, **GPU_CAM)
+        want = cpu_render(harness, d, m, sc, cam)
+        assert_same_image(render_outputs(gen, cam, sc), want, (k, w, h))
+        assert render_outputs(gen, cam, sc, pixels=False)[0].tobytes() == want[0].tobytes(), (k, w, h)
+        rec = render_outputs(gen, cam, sc, rgba=False)[1]
+        for f in W.RENDER_PIXEL.names:
+            assert rec[f].tobytes() == want[1][f].tobytes(), (k, w, h, f)
+    # the other order on a fresh context: the records' block first, then the RGBA words', then both at a larger size
+    gen.free()
+    gen, sc, d, m = smallest_context()
+    small, large = look(width=8, height=8, **GPU_CAM), look(width=40, height=24, **GPU_CAM)
+    want = cpu_render(harness, d, m, sc, small)
+    assert render_outputs(gen, small, sc, rgba=False)[1].tobytes() == want[1].tobytes()
+    assert render_outputs(gen, small, sc, pixels=False)[0].tobytes() == want[0].tobytes()
+    assert_same_image(render_outputs(gen, large, sc), cpu_render(harness, d, m, sc, large), "40 x 24")
+    gen.free()

@@ -470,3 +470,40 @@ def test_group_query_equals_a_single_context():
     grp.gather_wait()
     for opts in (None, {"falloff_center": (-30.0, 60.0)}):
         assert grp.query_surface(xz, sc, opts).tobytes() == single.query_surface(xz, sc, opts).tobytes()
+
+
+# ---- 10. the grow-only scratch of the synchronous calls ------------------------------------------------------------------------------------
+
+GROW_POINTS = (16, 4097, 16)   # under the scratch's floor of 4 096 points, one past it (the block is replaced), under it again (the larger block stays)
+
+
+def smallest_context():
+    """128^2 x 2, three ticks in: (generator, map scales, displacement, normal maps)"""
+    gen, params = make_gen(128, [0, 1])
+    gen.run(UPDATE_DELTA, params, 3)
+    return (gen, scales_of(params)) + gpu_maps(gen, 2)
+
+
+def assert_same_records(got, want, what):
+    for f in got.dtype.names:
+        assert got[f].tobytes() == want[f].tobytes(), (what, f)
+
+
+@pytest.mark.gpu
+def test_point_scratch_grows_past_its_floor_and_stays(harness):
+    """ow_sample_surface and ow_query_surface share one scratch: interleaved, across a regrow, every call returns the CPU build's records"""
+    gen, sc, d, m = smallest_context()
+    for k, count in enumerate(GROW_POINTS):
+        xz = query_points(count, seed=40 + k, span=300.0)
+        assert_same_records(gen.sample_surface(xz, sc), cpu_sample(harness, d, m, sc, xz), ("sample", count))
+        assert_same_records(gen.query_surface(xz, sc), cpu_query(harness, d, m, sc, xz), ("query", count))
+        assert_same_records(gen.sample_surface(xz[::-1], sc), cpu_sample(harness, d, m, sc, xz[::-1]), ("sample again", count))
+    gen.free()
+
+
+@pytest.mark.gpu
+def test_a_context_that_never_made_a_consumer_call_is_destroyed():
+    gen, params = make_gen(128, [0, 1])
+    gen.run(UPDATE_DELTA, params, 1)
+    gen.sync()
+    gen.free()

@@ -19,7 +19,8 @@ from godotoceanwaves_amd import _lib, build
 from godotoceanwaves_amd.presets import UPDATE_DELTA, cascade_preset
 from godotoceanwaves_amd.wave_generator import WaveGenerator as W
 from test_buoyancy import RHO, RHO_G, cpu_buoyancy, harness as buoyancy_harness, make_scene  # noqa: F401
-from test_surface_query import gpu_maps, make_gen, maps_u16, scales_of
+from test_surface_query import (GROW_POINTS, assert_same_records, cpu_query, cpu_sample, gpu_maps, harness as query_harness, make_gen, maps_u16,  # noqa: F401
+                                scales_of, smallest_context)
 from velocity_twin import phases, velocity_twin
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -493,3 +494,18 @@ def test_buoyancy_with_and_without_the_flag(harness, buoyancy_harness):
     assert 0 < s <= 1
     assert r1["force"][0][0] == 0.0 and r1["force"][0][2] == 0.0
     assert r1["force"][0][1] == np.float32(np.float32(RHO_G) * np.float32(np.float32(0.125) * s))
+
+
+@pytest.mark.gpu
+def test_velocity_query_shares_the_point_scratch_across_a_regrow(harness, query_harness):
+    """ow_query_velocity, ow_query_surface and ow_sample_surface use one grow-only scratch: interleaved at 16, 4 097 (past the floor) and 16
+    points on one context, each returns the CPU build's records"""
+    gen, sc, d, m = smallest_context()
+    v = _vel_layers(gen, 2)
+    for k, count in enumerate(GROW_POINTS):
+        xz = np.random.default_rng(70 + k).uniform(-300, 300, (count, 2)).astype(np.float32)
+        assert_same_records(gen.sample_surface(xz, sc), cpu_sample(query_harness, d, m, sc, xz), ("sample", count))
+        assert gen.query_velocity(xz, sc).tobytes() == cpu_query_velocity(harness, d, v, sc, xz).tobytes(), count
+        assert_same_records(gen.query_surface(xz, sc), cpu_query(query_harness, d, m, sc, xz), ("query", count))
+        assert gen.query_velocity(xz[::-1], sc).tobytes() == cpu_query_velocity(harness, d, v, sc, xz[::-1]).tobytes(), count
+    gen.free()
