@@ -211,6 +211,7 @@ SIGNATURES = {
     "ow_set_cascade_params": (C.c_int, [C.c_void_p, C.c_int32, _P(ow_cascade_params)]),
     "ow_get_cascade_params": (C.c_int, [C.c_void_p, C.c_int32, _P(ow_cascade_params)]),
     "ow_debug_inject_fault": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "ow_debug_set_spectrum": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "ow_get_push_constants": (C.c_int, [C.c_void_p, C.c_int32, _P(ow_push_constants)]),
     "ow_process": (C.c_int, [C.c_void_p]),
     "ow_update_all": (C.c_int, [C.c_void_p, C.c_double, _P(ow_cascade_params), C.c_int32]),

@@ -1884,6 +1884,26 @@ ow_status ow_get_spectrum(ow_context *c, int32_t cascade, float *h0, float *omeg
     return OW_OK;
 }
 
+ow_status ow_debug_set_spectrum(ow_context *c, int32_t cascade, const float *h0, const float *omega) {
+    ow_status st = check_cascade(c, cascade);
+    if (st != OW_OK) return st;
+    if (!h0) return fail(OW_ERR_INVALID, "null spectrum");
+    if (cascade >= OW_MAX_CASCADES || !c->spectrum_resident[cascade])
+        return fail(OW_ERR_STATE, "cascade %d has no resident spectrum yet: its push-constant words exist only after its first generation", cascade);
+    OW_HIP(hipSetDevice(c->device));
+    // everything launched so far read the old planes: drained first (both chains: main_stream joins the second one) ...
+    if (st = sync_stream(c, 0u); st != OW_OK) return st;
+    // ... and whatever was computed AHEAD from them does not survive -- the look-ahead queue (a pre-armed ow_process queue is the same queue), what a
+    // run armed for the next run -- exactly as where a batch regenerates a spectrum (enqueue)
+    c->la.queued = 0;
+    c->ra.armed = false;
+    c->velocity_stale |= 1u << cascade;  // (V is made from the resident spectrum)
+    OW_HIP(hipMemcpyAsync(c->buf.h0 + cascade * plane(c), h0, plane(c) * sizeof(ow::cplx), hipMemcpyHostToDevice, main_stream(c)));
+    if (omega) OW_HIP(hipMemcpyAsync(c->buf.omega + cascade * plane(c), omega, plane(c) * sizeof(float), hipMemcpyHostToDevice, main_stream(c)));
+    OW_HIP(hipStreamSynchronize(main_stream(c)));
+    return OW_OK;  // spectrum_resident and pc_words stay: a clean record, or a dirty one that packs to the resident words, keeps these planes
+}
+
 ow_status ow_get_push_constants(const ow_context *c, int32_t cascade, ow_push_constants *out) {
     ow_status st = check_cascade(c, cascade);
     if (st != OW_OK) return st;

@@ -812,6 +812,19 @@ class WaveGenerator:
         _lib.check(self._lib.ow_get_spectrum(self.context, cascade, h0.ctypes.data, om.ctypes.data))
         return h0, om
 
+    def debug_set_spectrum(self, cascade, h0, omega=None):
+        """test hook (ow_debug_set_spectrum): h0 complex64 [n][n] = h0(k) as [y][x] replaces the resident spectrum of `cascade`; omega float32
+        [n][n] replaces its dispersion plane (None keeps it)"""
+        n = self.map_size
+        h0 = np.ascontiguousarray(h0, np.complex64)
+        if h0.shape != (n, n):
+            raise ValueError(f"h0 must be [{n}][{n}], got {h0.shape}")
+        if omega is not None:
+            omega = np.ascontiguousarray(omega, np.float32)
+            if omega.shape != (n, n):
+                raise ValueError(f"omega must be [{n}][{n}], got {omega.shape}")
+        _lib.check(self._lib.ow_debug_set_spectrum(self.context, cascade, h0.ctypes.data, omega.ctypes.data if omega is not None else None))
+
     def get_intermediate(self, cascade):
         out = np.empty((4, self.map_size, self.map_size, 2), np.float32)
         _lib.check(self._lib.ow_get_intermediate(self.context, cascade, out.ctypes.data))

@@ -999,6 +999,16 @@ ow_status ow_get_maps_f32(ow_context *ctx, int32_t cascade, float *out);
  * FP32 dispersion plane omega(k) (N*N floats) the frame kernels consume.  Either may be NULL. */
 ow_status ow_get_spectrum(ow_context *ctx, int32_t cascade, float *h0, float *omega);
 
+/* Test hook: replaces the resident spectrum of `cascade` with planes of the caller's -- h0: N*N*2 floats, h0(k) as [y][x] (re, im), the half
+ * the context stores (ow_get_spectrum afterwards returns (h0(k), conj(h0(-k))) built from it); omega: N*N floats, or NULL to keep the layer's
+ * dispersion plane.  OW_ERR_STATE before the layer's first generation.  Synchronises, and drops everything computed ahead from the old
+ * spectrum (the look-ahead queue, what a run armed for the next run).  The layer still counts as generated from its last spectrum push
+ * constants: a record with should_generate_spectrum == 0, and a dirty record that packs to those very words, use the injected planes on every
+ * path (ow_update / ow_process, ow_update_all, ow_run); they are lost to the next generation -- a dirty record with other words, or any dirty
+ * record under OW_FLAG_ALWAYS_REGENERATE_SPECTRUM.  The frame kernels are linear in h0: the tests feed them spectra that weigh every wave
+ * number alike (tests/frame_bins.py).  Never called in normal operation. */
+ow_status ow_debug_set_spectrum(ow_context *ctx, int32_t cascade, const float *h0, const float *omega);
+
 /* The transposed intermediate after the first row pass, converted to the reference's layout
  * fft_buffer half 0 after transpose.glsl: [layer][row][col] complex, 4*N*N*2 floats.  The intermediate is scratch
  * shared by all batches: only cascades of the most recent pair of launches can be read (OW_ERR_STATE otherwise). */

@@ -172,6 +172,22 @@ SPEC_KAPPA = 2.0            # k_spectrum vs the FP64 twin: this many times the l
 SPEC_RHO_TWIN = 1.5e-6      # ... plus this much of |twin| (measured 3.9e-7)
 SPEC_RHO_LITERAL = 5e-6     # the oracle vs the FP64 twin (measured 1.2e-6)
 SPEC_ARG_ULPS = 4.0         # ulps of theta - angle allowed on top, times np_twin.direction_ulp_sensitivity (the wind's null direction; measured 0.98)
+# The frame kernels' bounds on injected spectra (tests/frame_bins.py, tests/test_frame_bins.py, tests/test_frame_bins_gpu.py): per size, FOUR times the
+# ORACLE's own worst error against the FP64 twin (the measured value is noted; profiles/frame_bin_margins.txt) over all seven non-foam channels,
+# every input of the kind and both tiles -- the factor covers a transform of another radix, another summation order and the Cody-Waite sincos_phase
+# (2e-7).  spatial_*: max|a - twin| over the maximum of the channel's group; bin_white: the per-bin ratio (phi = frame_bins.PHI_BIN).
+# tests/test_frame_bins.py holds the oracle within a quarter of each, so the constants cannot drift from their source.
+FRAME_BIN_BOUNDS = {
+    128: dict(spatial_white=2.4e-6, spatial_sparse=5.8e-6, bin_white=4.3e-4),    # measured 5.79e-7, 1.43e-6, 1.07e-4
+    256: dict(spatial_white=2.5e-6, spatial_sparse=6.9e-6, bin_white=4.9e-4),    # measured 6.19e-7, 1.71e-6, 1.22e-4
+    512: dict(spatial_white=2.8e-6, spatial_sparse=7.6e-6, bin_white=5.5e-4),    # measured 7.00e-7, 1.88e-6, 1.37e-4
+    1024: dict(spatial_white=3.2e-6, spatial_sparse=8.9e-6, bin_white=8.6e-4),   # measured 7.79e-7, 2.21e-6, 2.13e-4
+    2048: dict(spatial_white=3.9e-6, spatial_sparse=1.7e-6, bin_white=1.15e-3),  # measured 9.58e-7, 4.09e-7, 2.86e-4 (white and lines only; bins of hy, hz, dhx_dx)
+}
+# a kernel family whose legitimate rounding needs more than a bound gets a factor here, with its error model in profiles/frame_bin_margins.txt
+FRAME_BIN_FAMILY_MARGIN = {}
+
+
 def texel_margins(a, r, rho, phi, extra=0.0, per_ulp=None, ulps=0.0, abs_floor=0.0):
     """a, r: planes with the channel on the last axis (complex channels compare as complex numbers).  Per texel and channel
         ratio = |a - r| / (extra + (rho + ulps per_ulp) |r| + phi max|r|)      (max over the channel's plane)

@@ -96,6 +96,15 @@ def test_create_argument_errors(lib):
     lib.ow_destroy(None)  # allowed
 
 
+def test_debug_set_spectrum_argument_errors(lib):
+    """ow_debug_set_spectrum without a context: refused before anything is touched, whatever the cascade"""
+    h0 = (C.c_float * 8)()
+    for cascade in (0, -1, 8):
+        assert lib.ow_debug_set_spectrum(None, cascade, h0, None) == _lib.OW_ERR_INVALID and b"null context" in lib.ow_last_error()
+    assert lib.ow_debug_set_spectrum(None, 0, None, None) == _lib.OW_ERR_INVALID
+    assert lib.ow_abi_version() == 4   # an addition only
+
+
 def test_no_device_is_a_loud_error(lib):
     import torch
     if torch.cuda.is_available():
