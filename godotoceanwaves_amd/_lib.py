@@ -29,6 +29,8 @@ OW_RAY_HIT, OW_RAY_FROM_BELOW, OW_RAY_TRUNCATED, OW_RAY_INVALID = 1, 2, 4, 8
 OW_RENDER_MAX_SIDE = 8192
 OW_MESH_CULL_BACK = 1
 OW_MESH_VERTEX_NOT_FINITE = 1
+OW_SPRAY_ACTIVE, OW_SPRAY_HAS_STARTED, OW_SPRAY_RESTARTED = 1, 2, 4
+OW_SPRAY_MIN_AMOUNT, OW_SPRAY_MAX_AMOUNT = 4, 1048576
 OW_OK, OW_ERR_INVALID, OW_ERR_NO_DEVICE, OW_ERR_HIP, OW_ERR_NOMEM, OW_ERR_STATE = range(6)
 
 
@@ -187,6 +189,24 @@ class ow_mesh_options(C.Structure):
                 ("lane_box", C.c_int32), ("reserved", C.c_uint32 * 6)]
 
 
+class ow_spray_options(C.Structure):
+    """struct ow_spray_options (128 bytes)"""
+    _fields_ = [("amount", C.c_uint32), ("num_particles", C.c_uint32), ("emitter_lifetime", C.c_float), ("lifetime", C.c_float),
+                ("lifetime_randomness", C.c_float), ("particle_scale", C.c_float * 3), ("random_seed", C.c_uint32), ("reserved0", C.c_uint32),
+                ("emission_transform", C.c_float * 12), ("start_time", C.c_double), ("reserved", C.c_uint32 * 8)]
+
+
+class ow_spray_instance(C.Structure):
+    """struct ow_spray_instance (64 bytes): a particle's transform rows and custom data"""
+    _fields_ = [("transform", C.c_float * 12), ("custom", C.c_float * 4)]
+
+
+class ow_spray_particle(C.Structure):
+    """struct ow_spray_particle (48 bytes): a particle's state"""
+    _fields_ = [("start_pos", C.c_float * 3), ("start_time", C.c_float), ("particle_scale", C.c_float * 3), ("particle_lifetime", C.c_float),
+                ("custom_z", C.c_float), ("scale_factor", C.c_float), ("flags", C.c_uint32), ("number", C.c_uint32)]
+
+
 class ow_mesh_vertex(C.Structure):
     """struct ow_mesh_vertex (48 bytes): the vertex stage's record of a mesh draw"""
     _fields_ = [("position", C.c_float * 3), ("wave_height", C.c_float), ("uv", C.c_float * 2), ("distance_factor", C.c_float),
@@ -265,6 +285,13 @@ SIGNATURES = {
     "ow_mesh_draw_async": (C.c_int, [C.c_void_p, C.c_void_p, _P(ow_camera), C.c_void_p, C.c_void_p, C.c_int32, _P(ow_mesh_options), C.c_void_p,
                                      C.c_void_p]),
     "ow_mesh_stats": (C.c_int, [C.c_void_p, C.c_void_p, _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64)]),
+    "ow_spray_options_default": (None, [_P(ow_spray_options)]),
+    "ow_spray_create": (C.c_int, [C.c_void_p, _P(ow_spray_options), _P(C.c_void_p)]),
+    "ow_spray_destroy": (None, [C.c_void_p, C.c_void_p]),
+    "ow_spray_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_int32]),
+    "ow_spray_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _P(C.c_uint32)]),
+    "ow_spray_get_device_ptrs": (C.c_int, [C.c_void_p, C.c_void_p, _P(C.c_void_p), _P(C.c_void_p), _P(C.c_void_p), _P(C.c_void_p)]),
+    "ow_spray_stats": (C.c_int, [C.c_void_p, C.c_void_p, _P(C.c_double), _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64)]),
     "ow_get_maps_f32": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
     "ow_get_spectrum": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "ow_get_intermediate": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),

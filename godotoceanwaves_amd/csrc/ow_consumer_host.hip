@@ -1,5 +1,6 @@
-// ow_consumer_host.hip -- the read side of include/ocean_waves.h: host wrappers around the kernels of ow_consumer.hip, ow_velocity.hip and
-// ow_mesh.hip (surface samples and queries, buoyancy, floating bodies, ray casts, camera views, mesh draws, the velocity layers).  Plain C++ over
+// ow_consumer_host.hip -- the read side of include/ocean_waves.h: host wrappers around the kernels of ow_consumer.hip, ow_velocity.hip,
+// ow_mesh.hip and ow_spray.hip (surface samples and queries, buoyancy, floating bodies, ray casts, camera views, mesh draws, the velocity
+// layers, the sea-spray emitter).  Plain C++ over
 // the HIP runtime API; the context and the scheduler's services come from ow_context.h.  The synchronous calls' device halves (ow_internal.h
 // *_round_trip) also serve a group's gathered arrays (ow_group.hip).
 #include <hip/hip_runtime.h>
@@ -1059,6 +1060,134 @@ ow_status ow_mesh_stats(ow_context *c, ow_mesh *m, uint64_t *draws, uint64_t *sk
         if (cooperative) *cooperative = w[ow::kTriWave];
     }
     if (draws) *draws = m->draws;
+    return OW_OK;
+}
+
+/* ---- the sea-spray emitter (ow_spray.h, ow_spray.hip) ---- */
+
+void ow_spray_options_default(ow_spray_options *out) {
+    static_assert(sizeof(ow_spray_options) == sizeof(ow::SprayOptions) && offsetof(ow_spray_options, particle_scale) == offsetof(ow::SprayOptions, particle_scale) &&
+                      offsetof(ow_spray_options, emission_transform) == offsetof(ow::SprayOptions, emission_transform) &&
+                      offsetof(ow_spray_options, start_time) == offsetof(ow::SprayOptions, start_time) &&
+                      offsetof(ow_spray_options, reserved) == offsetof(ow::SprayOptions, reserved) &&
+                      sizeof(ow_spray_instance) == sizeof(ow::SprayInstance) && offsetof(ow_spray_instance, custom) == offsetof(ow::SprayInstance, custom) &&
+                      sizeof(ow_spray_particle) == sizeof(ow::SprayParticle) && offsetof(ow_spray_particle, particle_lifetime) == offsetof(ow::SprayParticle, particle_lifetime) &&
+                      offsetof(ow_spray_particle, flags) == offsetof(ow::SprayParticle, flags) && OW_SPRAY_ACTIVE == ow::kSprayActive &&
+                      OW_SPRAY_HAS_STARTED == ow::kSprayHasStarted && OW_SPRAY_RESTARTED == ow::kSprayRestarted &&
+                      OW_SPRAY_MIN_AMOUNT == ow::kSprayMinAmount && OW_SPRAY_MAX_AMOUNT == ow::kSprayMaxAmount,
+                  "record layout");
+    if (!out) return;
+    ow::spray_default_options((ow::SprayOptions *)out);
+}
+
+ow_status ow_spray_create(ow_context *c, const ow_spray_options *opts, ow_spray **out) {
+    if (!opts || !out) return fail(OW_ERR_INVALID, "null argument");
+    ow::SprayOptions o;
+    std::memcpy(&o, opts, sizeof(o));
+    ow::SprayParams P;
+    ow::SprayHostState H;
+    if (const char *why = ow::spray_resolve(o, &P, &H)) return fail(OW_ERR_INVALID, "ow_spray_options: %s", why);
+    if (!c) return fail(OW_ERR_INVALID, "null context");
+    OW_HIP(hipSetDevice(c->device));
+    ow_spray *e = new (std::nothrow) ow_spray();
+    if (!e) return fail(OW_ERR_NOMEM, "out of host memory");
+    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t amount = P.amount, blocks = (amount + ow::kSprayBlock - 1) / ow::kSprayBlock;
+    const size_t p_bytes = up(amount * sizeof(ow::SprayParticle)), i_bytes = up(amount * sizeof(ow::SprayInstance)), d_bytes = up(amount * sizeof(uint32_t));
+    const size_t b_bytes = up(blocks * ow::kSprayBlockWords * sizeof(uint32_t));
+    const size_t total = p_bytes + i_bytes + d_bytes + b_bytes + 256;
+    if (hipMalloc(&e->block, total) != hipSuccess) {
+        (void)hipGetLastError();
+        delete e;
+        return fail(OW_ERR_NOMEM, "hipMalloc failed for %zu bytes of particles", total);
+    }
+    char *base = (char *)e->block;
+    e->ctx = c;
+    e->P = P;
+    e->H = H;
+    e->A.particles = (ow::SprayParticle *)base;
+    e->A.instances = (ow::SprayInstance *)(base + p_bytes);
+    e->A.draw_list = (uint32_t *)(base + p_bytes + i_bytes);
+    e->A.block_words = (uint32_t *)(base + p_bytes + i_bytes + d_bytes);
+    e->A.totals = (uint64_t *)(base + p_bytes + i_bytes + d_bytes + b_bytes);
+    e->A.live_count = (uint32_t *)(base + p_bytes + i_bytes + d_bytes + b_bytes + 2 * sizeof(uint64_t));
+    hipStream_t s = main_stream(c);
+    if (hipMemsetAsync(e->block, 0, total, s) != hipSuccess || (++c->host_syncs, hipStreamSynchronize(s)) != hipSuccess) {
+        const ow_status st = fail(OW_ERR_HIP, "particle set-up failed: %s", hipGetErrorString(hipGetLastError()));
+        (void)hipFree(e->block);
+        delete e;
+        return st;
+    }
+    c->sprays.push_back(e);
+    *out = e;
+    return OW_OK;
+}
+
+void ow_spray_destroy(ow_context *, ow_spray *e) {
+    if (!e) return;
+    if (ow_context *c = e->ctx) {  // its own context, still alive (ow_destroy clears this field of the emitters it outlives)
+        (void)hipSetDevice(c->device);
+        ++c->host_syncs;
+        (void)hipStreamSynchronize(main_stream(c));
+        c->sprays.erase(std::remove(c->sprays.begin(), c->sprays.end(), e), c->sprays.end());
+        (void)hipFree(e->block);
+    }
+    delete e;
+}
+
+ow_status ow_spray_step(ow_context *c, ow_spray *e, double delta, const float *map_scales, int32_t num_cascades) {
+    if (!std::isfinite(delta) || !(delta > 0.0)) return fail(OW_ERR_INVALID, "delta must be finite and > 0");
+    if (num_cascades < 1 || num_cascades > OW_MAX_CASCADES) return fail(OW_ERR_INVALID, "num_cascades %d outside [1,%d]", num_cascades, OW_MAX_CASCADES);
+    if (!map_scales) return fail(OW_ERR_INVALID, "null argument");
+    if (ow_status st = check_handle(c, e, "spray emitter"); st != OW_OK) return st;
+    if (!ow::spray_delta_ok(e->P, delta)) return fail(OW_ERR_INVALID, "delta %g outside (0, emitter_lifetime = %g)", delta, (double)e->P.emitter_lifetime);
+    if (ow_status st = check_point_query(c, 0, num_cascades); st != OW_OK) return st;
+    if (ow_status st = begin_async(c, num_cascades); st != OW_OK) return st;
+    ow::SprayHostState H = e->H;  // advanced only once the launches are in
+    const ow::SprayClock K = ow::spray_advance(e->P, H, delta);
+    const ow::MapsView v = view_of(c);
+    OW_HIP(ow::launch_spray_step(v.n, num_cascades, v.buf, e->A, surface_scales(map_scales, num_cascades), e->P, K, v.stream));
+    e->H = H;
+    return OW_OK;
+}
+
+ow_status ow_spray_read(ow_context *c, ow_spray *e, ow_spray_instance *instances, ow_spray_particle *particles, uint32_t *draw_list, uint32_t *live_count) {
+    if (ow_status st = check_handle(c, e, "spray emitter"); st != OW_OK) return st;
+    OW_HIP(hipSetDevice(c->device));
+    hipStream_t s = main_stream(c);
+    uint32_t live = 0;
+    if (instances) OW_HIP(hipMemcpyAsync(instances, e->A.instances, (size_t)e->P.amount * sizeof(ow::SprayInstance), hipMemcpyDeviceToHost, s));
+    if (particles) OW_HIP(hipMemcpyAsync(particles, e->A.particles, (size_t)e->P.amount * sizeof(ow::SprayParticle), hipMemcpyDeviceToHost, s));
+    OW_HIP(hipMemcpyAsync(&live, e->A.live_count, sizeof(live), hipMemcpyDeviceToHost, s));
+    if (ow_status st = sync_stream(c, 0); st != OW_OK) return st;
+    if (live > e->P.amount) return fail(OW_ERR_HIP, "live count %u beyond amount %u", live, e->P.amount);
+    if (draw_list && live > 0) OW_HIP(hipMemcpy(draw_list, e->A.draw_list, (size_t)live * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (live_count) *live_count = live;
+    return OW_OK;
+}
+
+ow_status ow_spray_get_device_ptrs(ow_context *c, ow_spray *e, void **instances, void **particles, void **draw_list, void **live_count) {
+    if (ow_status st = check_handle(c, e, "spray emitter"); st != OW_OK) return st;
+    if (instances) *instances = e->A.instances;
+    if (particles) *particles = e->A.particles;
+    if (draw_list) *draw_list = e->A.draw_list;
+    if (live_count) *live_count = e->A.live_count;
+    return OW_OK;
+}
+
+ow_status ow_spray_stats(ow_context *c, ow_spray *e, double *time, uint64_t *steps, uint64_t *restarts, uint64_t *spawned, uint64_t *rejected) {
+    if (ow_status st = check_handle(c, e, "spray emitter"); st != OW_OK) return st;
+    if (spawned || rejected) {
+        OW_HIP(hipSetDevice(c->device));
+        if (ow_status st = sync_stream(c, 0); st != OW_OK) return st;
+        uint64_t w[2] = {0, 0};
+        OW_HIP(hipMemcpy(w, e->A.totals, sizeof(w), hipMemcpyDeviceToHost));
+        if (spawned) *spawned = w[0];
+        if (rejected) *rejected = w[1];
+    }
+    if (time) *time = e->H.time;
+    if (steps) *steps = e->H.steps;
+    if (restarts) *restarts = e->H.restarts;
     return OW_OK;
 }
 

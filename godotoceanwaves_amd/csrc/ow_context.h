@@ -25,6 +25,15 @@ struct ow_mesh {
     uint64_t draws = 0;
 };
 
+// a sea-spray emitter (ow_spray_create, ow_consumer_host.hip)
+struct ow_spray {
+    ow_context *ctx = nullptr;  // nullptr: orphaned by ow_destroy, as a body set
+    void *block = nullptr;      // one allocation: states, instances, draw list, per-block words, live count, totals
+    ow::SprayArrays A{};
+    ow::SprayParams P{};
+    ow::SprayHostState H{};     // the FP64 clock and the host's bookkeeping
+};
+
 struct ow_context {
     int n = 0, cascades = 0, layers = 0, device = 0;
     float depth = 20.0f;
@@ -154,6 +163,7 @@ struct ow_context {
     uint64_t vel_computed = 0, vel_skipped = 0;  // ow_velocity_stats
     std::vector<ow_bodies *> body_sets;  // the live sets of this context: ow_destroy orphans what the caller has not destroyed
     std::vector<ow_mesh *> meshes;       // likewise the live meshes
+    std::vector<ow_spray *> sprays;      // ... and the live spray emitters
     uint64_t host_syncs = 0;  // stream synchronisations made on the caller's thread since ow_create (ow_sync_stats)
 };
 

@@ -9,6 +9,7 @@
 #include "ow_mesh.h"
 #include "ow_render.h"
 #include "ow_rigid.h"
+#include "ow_spray.h"
 #include "ow_surface.h"
 #include "ow_velocity.h"
 #include "ow_velocity_kernels.h"
@@ -97,6 +98,18 @@ hipError_t launch_mesh_vertices(int n, int cascades, const DeviceBuffers &buf, c
 hipError_t launch_mesh_draw(int n, int cascades, const DeviceBuffers &buf, const MeshArrays &M, const SurfaceScales &scales, const MeshParams &mp,
                             const CameraParams &cam, const ShadeParams &sp, const float origin[3], uint64_t *vis_dev, uint32_t *rgba_dev,
                             RenderPixel *pixels_dev, hipStream_t s);
+// a sea-spray step (ow_spray.hip; the schedule, start(), process() and the records in ow_spray.h).  SprayArrays: an emitter's device block.
+struct SprayArrays {
+    SprayParticle *particles;  // [amount]
+    SprayInstance *instances;  // [amount]
+    uint32_t *draw_list;       // [amount] the first *live_count entries: the live particles' indices, ascending
+    uint32_t *block_words;     // [blocks][kSprayBlockWords] of the last step
+    uint32_t *live_count;      // [1]
+    uint64_t *totals;          // [2] particles :89 has spawned and rejected since creation
+};
+// k_spray_step, then k_spray_compact, both on `s`
+hipError_t launch_spray_step(int n, int cascades, const DeviceBuffers &buf, const SprayArrays &A, const SurfaceScales &scales, const SprayParams &P,
+                             const SprayClock &K, hipStream_t s);
 
 bool supported_map_size(int n);
 int kernel_family(int n, int slots, int mode);  // 1 standard, 2 layer-parallel, 3 compact: what launch_pass1/2 will use

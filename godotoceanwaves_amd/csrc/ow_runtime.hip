@@ -1027,6 +1027,11 @@ void ow_destroy(ow_context *c) {
         m->block = nullptr;
         m->ctx = nullptr;
     }
+    for (ow_spray *e : c->sprays) {
+        (void)hipFree(e->block);
+        e->block = nullptr;
+        e->ctx = nullptr;
+    }
     for (ow_bodies *set : c->body_sets) {  // sets the caller has not destroyed: their memory goes with the context, the handles stay valid to destroy
         (void)hipFree(set->block);
         set->block = nullptr;

@@ -99,6 +99,13 @@ class _Mesh:
         self.handle, self.num_vertices, self.num_triangles = handle, num_vertices, num_triangles
 
 
+class _Spray:
+    """an ow_spray handle with the amount it was created with (WaveGenerator.spray_create)"""
+
+    def __init__(self, handle, amount):
+        self.handle, self.amount = handle, amount
+
+
 class WaveGenerator:
     """assets/water/wave_generator.gd.  Typical use, as in water.gd:89-91,112-114:
 
@@ -794,6 +801,79 @@ class WaveGenerator:
         v = [C.c_uint64() for _ in range(5)]
         _lib.check(self._lib.ow_mesh_stats(self.context, mesh.handle, *[C.byref(x) for x in v]))
         return dict(zip(("draws", "skipped", "culled", "per_lane", "cooperative"), (x.value for x in v)))
+
+    # ---- the sea-spray particle emitter on the device (include/ocean_waves.h ow_spray_*) ----
+    SPRAY_INSTANCE = np.dtype([("transform", np.float32, 12), ("custom", np.float32, 4)])
+    SPRAY_PARTICLE = np.dtype([("start_pos", np.float32, 3), ("start_time", np.float32), ("particle_scale", np.float32, 3),
+                               ("particle_lifetime", np.float32), ("custom_z", np.float32), ("scale_factor", np.float32), ("flags", np.uint32),
+                               ("number", np.uint32)])
+    _SPRAY_OWN = ("amount", "num_particles", "emitter_lifetime", "lifetime", "lifetime_randomness", "particle_scale", "random_seed",
+                  "emission_transform", "start_time")
+
+    @classmethod
+    def spray_options(cls, options=None):
+        """None, an _lib.ow_spray_options, or a dict -> ow_spray_options.  The dict starts from ow_spray_options_default's values (the
+        reference scene's emitter) and may set amount, num_particles, emitter_lifetime, lifetime, lifetime_randomness, particle_scale,
+        random_seed, emission_transform (3 x 4) and start_time."""
+        if isinstance(options, _lib.ow_spray_options):
+            return options
+        options = options or {}
+        unknown = [k for k in options if k not in cls._SPRAY_OWN]
+        if unknown:
+            raise ValueError(f"unknown spray options {unknown}")
+        o = _lib.ow_spray_options()
+        _lib.load().ow_spray_options_default(C.byref(o))
+        for k, v in options.items():
+            if k == "particle_scale":
+                o.particle_scale[:] = [float(x) for x in np.asarray(v, np.float32).reshape(3)]
+            elif k == "emission_transform":
+                o.emission_transform[:] = [float(x) for x in np.asarray(v, np.float32).reshape(12)]
+            elif k in ("amount", "num_particles", "random_seed"):
+                setattr(o, k, int(v))
+            else:
+                setattr(o, k, float(v))
+        return o
+
+    def spray_create(self, options=None):
+        """A device-resident emitter, every particle dormant; returns a _Spray (spray_destroy() it before free())"""
+        o = self.spray_options(options)
+        out = C.c_void_p()
+        _lib.check(self._lib.ow_spray_create(self.context, C.byref(o), C.byref(out)))
+        return _Spray(out, int(o.amount))
+
+    def spray_destroy(self, spray):
+        if spray.handle:
+            self._lib.ow_spray_destroy(self.context, spray.handle)
+            spray.handle = None
+
+    def spray_step(self, spray, delta, map_scales):
+        """One frame of the emitter on the maps as they stand in the generator's stream order; enqueues and returns"""
+        sc = np.ascontiguousarray(map_scales, np.float32).reshape(-1, 4)
+        _lib.check(self._lib.ow_spray_step(self.context, spray.handle, float(delta), sc.ctypes.data, len(sc)))
+
+    def spray_read(self, spray):
+        """(SPRAY_INSTANCE[amount], SPRAY_PARTICLE[amount], draw list uint32[live_count]) as the last step left them; synchronises"""
+        inst, part = np.zeros(spray.amount, self.SPRAY_INSTANCE), np.zeros(spray.amount, self.SPRAY_PARTICLE)
+        draw, live = np.zeros(spray.amount, np.uint32), C.c_uint32()
+        _lib.check(self._lib.ow_spray_read(self.context, spray.handle, inst.ctypes.data, part.ctypes.data, draw.ctypes.data, C.byref(live)))
+        return inst, part, draw[:live.value].copy()
+
+    def spray_live_count(self, spray):
+        live = C.c_uint32()
+        _lib.check(self._lib.ow_spray_read(self.context, spray.handle, None, None, None, C.byref(live)))
+        return live.value
+
+    def spray_device_ptrs(self, spray):
+        """device addresses of the instances, the state records, the draw list and the live count"""
+        v = [C.c_void_p() for _ in range(4)]
+        _lib.check(self._lib.ow_spray_get_device_ptrs(self.context, spray.handle, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def spray_stats(self, spray):
+        """dict of time, steps, restarts (the host's bookkeeping) and spawned, rejected (summed on the device; synchronises)"""
+        v = [C.c_double()] + [C.c_uint64() for _ in range(4)]
+        _lib.check(self._lib.ow_spray_stats(self.context, spray.handle, *[C.byref(x) for x in v]))
+        return dict(zip(("time", "steps", "restarts", "spawned", "rejected"), (x.value for x in v)))
 
     def get_push_constants(self, cascade):
         """(spectrum[16], modulate[8], unpack[4]) uint32 words: the reference's push-constant blocks of this cascade's most recent launch"""

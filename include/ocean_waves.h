@@ -863,6 +863,109 @@ ow_status ow_mesh_draw_async(ow_context *ctx, ow_mesh *mesh, const ow_camera *ca
 ow_status ow_mesh_stats(ow_context *ctx, ow_mesh *mesh, uint64_t *draws, uint64_t *skipped, uint64_t *culled, uint64_t *per_lane,
                         uint64_t *cooperative);
 
+/* The sea-spray particle emitter: the scene's WaterSprayEmitter (main.tscn:133-140, a GPUParticles3D whose process material runs
+ * sea_spray_particle.gdshader), as a device-resident particle set stepped in the context's stream order.  start() :45-66 and process()
+ * :74-126 run as written for every particle on every step; the spawn decision :80-89 and the displacement sum :105-109 are
+ * ow_sample_surface's at START_POS.xz, to the bit.  What the shader text does not contain is decided as follows:
+ *   clock     the emitter holds `time` in FP64.  A step sets time_new = time + delta, TIME = (float)time_new, uint(TIME) on the host,
+ *             cycle = floor(time_new / L) with L = emitter_lifetime, phase = (float)(fmod(time_new, L) / L); prev is the previous step's
+ *             phase (0 at creation); wrapped = cycle > the previous cycle, in FP64
+ *   restart   the engine's schedule at explosiveness 0 and randomness 0, no fixed FPS, no interpolation: rp = (float)i / (float)amount,
+ *             particle i restarts iff wrapped ? (rp >= prev || rp < phase) : (rp >= prev && rp < phase).  NUMBER = (uint32)(cycle *
+ *             amount + i), minus amount when wrapped && rp >= prev, modulo 2^32.  A particle is not ACTIVE before its first restart
+ *   start()   ACTIVE = true; hash32 as written on (NUMBER + uint(TIME) + random_seed, 1 + uint(TIME) + random_seed), the uint -> float
+ *             conversions rounding to nearest and float(0x7FFFFFFF) = 2^31 (a component may be exactly 1); t = (uint32)sqrtf((float)
+ *             num_particles); START_POS_r = (E_r0 cx + E_r2 cz) + E_r3 with :52's coords; :56-59 as written with LIFETIME = L;
+ *             HAS_STARTED = 0, CUSTOM.w = 0, position (0, -1e10, 0), scale 1e-3
+ *   basis     (G1) the shader's set_scale re-normalises the columns it stored last step, and :122-123 store a zero column at t = 0: the
+ *             next normalize is 0/0.  Here the three unit axes are the emission basis' columns, normalised once in FP64 and narrowed, and
+ *             every set_scale is axis_k * scale_k: the shader's value wherever it is defined, never NaN
+ *   process() runs in the step of a restart too, and not at all for a particle that is not ACTIVE; its branches compare FP32 values as
+ *             written (START_TIME + PARTICLE_LIFETIME one FP32 add); exp and log are written out in FP32 adds, multiplies and divides, so
+ *             every build computes the same bits
+ *   finite    (G2) finite maps give finite records; where a texel is not finite and a result is not, the particle's instance is zeros, it
+ *             stops being ACTIVE and leaves the draw list
+ * The exact operations, identical in every build, are godotoceanwaves_amd/csrc/ow_spray.h's.  There is no group form (ow_group_*) of these
+ * calls: step the emitter on the context that holds the maps. */
+#define OW_SPRAY_ACTIVE 1u       /* ow_spray_particle.flags: ACTIVE */
+#define OW_SPRAY_HAS_STARTED 2u  /*   HAS_STARTED: :78-96 has run since the last restart */
+#define OW_SPRAY_RESTARTED 4u    /*   restarted at least once */
+#define OW_SPRAY_MIN_AMOUNT 4u
+#define OW_SPRAY_MAX_AMOUNT 1048576u
+typedef struct ow_spray ow_spray; /* opaque; belongs to the context it was created on */
+typedef struct ow_spray_options {
+    uint32_t amount;               /* particles, OW_SPRAY_MIN_AMOUNT .. OW_SPRAY_MAX_AMOUNT (GPUParticles3D.amount) */
+    uint32_t num_particles;        /* the shader's uniform (:19); 0 = amount */
+    float emitter_lifetime;        /* GPUParticles3D.lifetime, seconds: the restart cycle, LIFETIME in the shader */
+    float lifetime;                /* :21 */
+    float lifetime_randomness;     /* :22, [0, 1] */
+    float particle_scale[3];       /* :20 */
+    uint32_t random_seed;          /* RANDOM_SEED */
+    uint32_t reserved0;            /* 0 */
+    float emission_transform[12];  /* EMISSION_TRANSFORM: three rows of four (basis row, then the origin's component) */
+    double start_time;             /* the clock at creation, seconds, >= 0 */
+    uint32_t reserved[8];          /* 0 */
+} ow_spray_options;                /* 128 bytes */
+/* One instance per particle, 64 bytes: what a MultiMesh with custom data takes.  transform: rows 0..2 of the particle's transform, each
+ * three basis components followed by that row's origin component; custom = (0, 0, CUSTOM.z, CUSTOM.w), the two values
+ * sea_spray.gdshader:22-23 read.  A particle that is not ACTIVE carries twelve zeros, as the engine's copy pass leaves it, and
+ * custom = (0, 0, CUSTOM.z, 0). */
+typedef struct ow_spray_instance {
+    float transform[12];
+    float custom[4];
+} ow_spray_instance;
+/* One state record per particle, 48 bytes: USERDATA1..3 of the shader (:12-17) and the engine's own words. */
+typedef struct ow_spray_particle {
+    float start_pos[3];
+    float start_time;
+    float particle_scale[3];
+    float particle_lifetime;
+    float custom_z;
+    float scale_factor;
+    uint32_t flags;   /* OW_SPRAY_* */
+    uint32_t number;  /* NUMBER of the last restart */
+} ow_spray_particle;
+typedef char ow_layout_check_spray_options[(sizeof(ow_spray_options) == 128 && offsetof(ow_spray_options, particle_scale) == 20 &&
+                                            offsetof(ow_spray_options, emission_transform) == 40 && offsetof(ow_spray_options, start_time) == 88 &&
+                                            offsetof(ow_spray_options, reserved) == 96) ? 1 : -1];
+typedef char ow_layout_check_spray_instance[(sizeof(ow_spray_instance) == 64 && offsetof(ow_spray_instance, custom) == 48) ? 1 : -1];
+typedef char ow_layout_check_spray_particle[(sizeof(ow_spray_particle) == 48 && offsetof(ow_spray_particle, particle_scale) == 16 &&
+                                             offsetof(ow_spray_particle, custom_z) == 32 && offsetof(ow_spray_particle, flags) == 40) ? 1 : -1];
+
+/* mat_spray.tres and main.tscn:133-140: 32 768 particles, emitter lifetime 6 s, lifetime 3 s, randomness 0.25, particle_scale
+ * (20, 8.5, 20), seed 0, the emission transform of scale 15 at (-1, 0, -25) -- the emitter's local transform composed with the Water
+ * node's --, start_time 0. */
+void ow_spray_options_default(ow_spray_options *out);
+/* A device-resident emitter with every particle dormant (the GPUParticles3D of main.tscn:133-140 before its first frame).  The options are
+ * checked before anything else is looked at: a value that is not finite, amount out of range, num_particles in 1..3, emitter_lifetime or
+ * lifetime <= 0, lifetime_randomness outside [0, 1], start_time < 0, an emission basis with a zero column or a reserved word that is not 0
+ * is OW_ERR_INVALID, and nothing is written, *out included.  Synchronises.  Destroy the emitter before its context (one that outlives
+ * it can still be destroyed; every other call on it is OW_ERR_STATE). */
+ow_status ow_spray_create(ow_context *ctx, const ow_spray_options *opts, ow_spray **out);
+void ow_spray_destroy(ow_context *ctx, ow_spray *spray);
+/* One frame of the emitter (the engine's restart pass, then start() :45-66 and process() :74-126 of every particle, then the copy into
+ * the instance buffer) on the maps as everything enqueued so far leaves them: ordered as ow_mesh_draw_async and ow_bodies_step, behind
+ * both chains -- a caller's stream included -- and ahead of whatever the context enqueues next.  Enqueues two launches; no
+ * synchronisation, no host traffic, no allocation.  delta outside (0, emitter_lifetime) or not finite, num_cascades outside [1, 8] or the
+ * context's cascades, or a null argument is OW_ERR_INVALID and nothing is written or advanced.  Faulted layers are refused as by
+ * ow_query_surface_async. */
+ow_status ow_spray_step(ow_context *ctx, ow_spray *spray, double delta, const float *map_scales, int32_t num_cascades);
+/* What the last step left, into host memory: amount instances, amount state records, the draw list -- the indices of the particles that
+ * are ACTIVE and HAS_STARTED (:98's test, the ones with a non-zero transform), in ascending index order; only the first *live_count
+ * entries are written, the array holds up to amount -- and their number.  Both depend on the inputs alone, never on scheduling.  Any
+ * output may be NULL.  Synchronises. */
+ow_status ow_spray_read(ow_context *ctx, ow_spray *spray, ow_spray_instance *instances, ow_spray_particle *particles, uint32_t *draw_list,
+                        uint32_t *live_count);
+/* The device addresses of the same four arrays (a MultiMesh buffer and an indirect draw's count, valid until ow_spray_destroy).  Any
+ * output may be NULL.  Does not synchronise. */
+ow_status ow_spray_get_device_ptrs(ow_context *ctx, ow_spray *spray, void **instances, void **particles, void **draw_list,
+                                   void **live_count);
+/* Counters (each output may be NULL): the emitter's clock, the steps taken and the restarts the schedule has made, from the host's own
+ * bookkeeping; the particles :89 has let spawn and has rejected, summed on the device.  Synchronises when one of the last two is asked
+ * for. */
+ow_status ow_spray_stats(ow_context *ctx, ow_spray *spray, double *time, uint64_t *steps, uint64_t *restarts, uint64_t *spawned,
+                         uint64_t *rejected);
+
 /* ---- several devices: cascades sharded inside one process ---------------------------------------- */
 
 /* Cascades share nothing (wave_generator.gd:65-85 touches no state of another cascade; README.md:77-80), so a node's GPUs
