@@ -31,6 +31,7 @@ OW_MESH_CULL_BACK = 1
 OW_MESH_VERTEX_NOT_FINITE = 1
 OW_SPRAY_ACTIVE, OW_SPRAY_HAS_STARTED, OW_SPRAY_RESTARTED = 1, 2, 4
 OW_SPRAY_MIN_AMOUNT, OW_SPRAY_MAX_AMOUNT = 4, 1048576
+OW_BILLBOARD_TEXTURE_MAX_SIDE = 4096
 OW_OK, OW_ERR_INVALID, OW_ERR_NO_DEVICE, OW_ERR_HIP, OW_ERR_NOMEM, OW_ERR_STATE = range(6)
 
 
@@ -207,6 +208,18 @@ class ow_spray_particle(C.Structure):
                 ("custom_z", C.c_float), ("scale_factor", C.c_float), ("flags", C.c_uint32), ("number", C.c_uint32)]
 
 
+class ow_billboard_material_options(C.Structure):
+    """struct ow_billboard_material_options (64 bytes): sea_spray.gdshader's uniforms and the textures' sRGB flags"""
+    _fields_ = [("foam_color", C.c_float * 3), ("max_alpha", C.c_float), ("albedo_srgb", C.c_uint32), ("dissolve_srgb", C.c_uint32),
+                ("reserved", C.c_uint32 * 10)]
+
+
+class ow_billboard_draw_options(C.Structure):
+    """struct ow_billboard_draw_options (64 bytes); a NULL pointer = near 0.05, a black background"""
+    _fields_ = [("near", C.c_float), ("background_color", C.c_float * 3), ("bin_side", C.c_int32), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32 * 10)]
+
+
 class ow_mesh_vertex(C.Structure):
     """struct ow_mesh_vertex (48 bytes): the vertex stage's record of a mesh draw"""
     _fields_ = [("position", C.c_float * 3), ("wave_height", C.c_float), ("uv", C.c_float * 2), ("distance_factor", C.c_float),
@@ -292,6 +305,15 @@ SIGNATURES = {
     "ow_spray_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _P(C.c_uint32)]),
     "ow_spray_get_device_ptrs": (C.c_int, [C.c_void_p, C.c_void_p, _P(C.c_void_p), _P(C.c_void_p), _P(C.c_void_p), _P(C.c_void_p)]),
     "ow_spray_stats": (C.c_int, [C.c_void_p, C.c_void_p, _P(C.c_double), _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64)]),
+    "ow_billboard_material_options_default": (None, [_P(ow_billboard_material_options)]),
+    "ow_billboard_material_create": (C.c_int, [C.c_void_p, _P(ow_billboard_material_options), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
+                                               C.c_int32, _P(C.c_void_p)]),
+    "ow_billboard_material_destroy": (None, [C.c_void_p, C.c_void_p]),
+    "ow_billboard_draw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, _P(ow_camera), _P(ow_billboard_draw_options), C.c_void_p, C.c_void_p]),
+    "ow_billboard_draw_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, _P(ow_camera), _P(ow_billboard_draw_options), C.c_void_p, C.c_void_p]),
+    "ow_billboard_draw_instances": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, _P(ow_camera), _P(ow_billboard_draw_options),
+                                              C.c_void_p, C.c_void_p]),
+    "ow_billboard_draw_stats": (C.c_int, [C.c_void_p, _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64)]),
     "ow_get_maps_f32": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
     "ow_get_spectrum": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "ow_get_intermediate": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),

@@ -1,6 +1,6 @@
 // ow_consumer_host.hip -- the read side of include/ocean_waves.h: host wrappers around the kernels of ow_consumer.hip, ow_velocity.hip,
-// ow_mesh.hip and ow_spray.hip (surface samples and queries, buoyancy, floating bodies, ray casts, camera views, mesh draws, the velocity
-// layers, the sea-spray emitter).  Plain C++ over
+// ow_mesh.hip, ow_spray.hip and ow_spray_draw.hip (surface samples and queries, buoyancy, floating bodies, ray casts, camera views, mesh draws, the velocity
+// layers, the sea-spray emitter and its billboards).  Plain C++ over
 // the HIP runtime API; the context and the scheduler's services come from ow_context.h.  The synchronous calls' device halves (ow_internal.h
 // *_round_trip) also serve a group's gathered arrays (ow_group.hip).
 #include <hip/hip_runtime.h>
@@ -1188,6 +1188,245 @@ ow_status ow_spray_stats(ow_context *c, ow_spray *e, double *time, uint64_t *ste
     if (time) *time = e->H.time;
     if (steps) *steps = e->H.steps;
     if (restarts) *restarts = e->H.restarts;
+    return OW_OK;
+}
+
+}  // extern "C"
+
+/* ---- the spray billboards (ow_spray_draw.h, ow_spray_draw.hip) ---- */
+
+namespace {
+constexpr size_t kBillboardHead = 16;                    // the two counters (and two words of padding) ahead of the masks
+
+// where a draw's arrays lie in the context's scratch block
+struct BillboardPlan {
+    ow::BillboardBins bins;
+    size_t sprites_off, instances_off, total;
+};
+BillboardPlan billboard_plan(int width, int height, uint32_t slots, int bin_side, bool upload) {
+    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    BillboardPlan p;
+    p.bins = ow::billboard_bins(width, height, slots, bin_side);
+    p.sprites_off = up(kBillboardHead + (size_t)p.bins.nx * p.bins.ny * p.bins.words * sizeof(uint64_t));
+    p.instances_off = p.sprites_off + up((size_t)slots * sizeof(ow::SpraySprite));
+    p.total = p.instances_off + (upload ? up((size_t)slots * sizeof(ow::SprayInstance)) : 0);
+    return p;
+}
+
+// ow_billboard_draw_options (NULL = the defaults) -> the draw's own constants
+ow_status resolve_billboard_options(const ow_billboard_draw_options *o, ow::SprayDrawParams *dp, int *bin_side) {
+    static_assert(sizeof(ow_billboard_draw_options) == sizeof(ow::BillboardDrawOptions) && offsetof(ow_billboard_draw_options, bin_side) == offsetof(ow::BillboardDrawOptions, bin_side) &&
+                      sizeof(ow_billboard_material_options) == sizeof(ow::BillboardMaterialOptions) &&
+                      offsetof(ow_billboard_material_options, albedo_srgb) == offsetof(ow::BillboardMaterialOptions, albedo_srgb) &&
+                      OW_BILLBOARD_TEXTURE_MAX_SIDE == ow::kBillboardTexMaxSide,
+                  "record layout");
+    dp->near = ow::kMeshDefaultNear;
+    dp->background[0] = dp->background[1] = dp->background[2] = 0.0f;
+    *bin_side = ow::kBillboardBinSide;
+    if (!o) return OW_OK;
+    if (!std::isfinite(o->near)) return fail(OW_ERR_INVALID, "near is not finite");
+    for (float v : o->background_color)
+        if (!std::isfinite(v)) return fail(OW_ERR_INVALID, "background_color is not finite");
+    if (o->bin_side != 0 && (o->bin_side < 8 || o->bin_side > ow::kBillboardBinMax || o->bin_side % 8 != 0))
+        return fail(OW_ERR_INVALID, "bin_side %d is not 0 or a multiple of 8 in [8,%d]", o->bin_side, ow::kBillboardBinMax);
+    if (o->flags != 0u) return fail(OW_ERR_INVALID, "unknown billboard flags 0x%x", o->flags);
+    for (uint32_t r : o->reserved)
+        if (r != 0u) return fail(OW_ERR_INVALID, "ow_billboard_draw_options.reserved must be 0");
+    if (o->near > 0.0f) dp->near = o->near;
+    for (int k = 0; k < 3; ++k) dp->background[k] = o->background_color[k];
+    if (o->bin_side > 0) *bin_side = o->bin_side;
+    return OW_OK;
+}
+
+// the argument checks every form of the draw shares: ow_mesh_draw's, in its order, then the context and the material
+ow_status check_billboard_draw(const ow_context *c, const ow_billboard_material *m, const ow_camera *camera, const ow_billboard_draw_options *opts,
+                               const void *pixels, const void *rgba, ow::CameraParams *cp, ow::SprayDrawParams *dp, int *bin_side) {
+    if (!rgba && !pixels) return fail(OW_ERR_INVALID, "null argument: both outputs");
+    if (ow_status st = resolve_camera(camera, cp); st != OW_OK) return st;
+    if (ow_status st = resolve_billboard_options(opts, dp, bin_side); st != OW_OK) return st;
+    if (ow_status st = check_handle(c, m, "billboard material"); st != OW_OK) return st;
+    dp->camera_ok = mesh_camera_ok_host(*cp) ? 1 : 0;
+    for (int k = 0; k < 3; ++k) dp->foam[k] = m->foam[k];
+    dp->max_alpha = m->max_alpha;
+    dp->albedo = m->albedo;
+    dp->dissolve = m->dissolve;
+    dp->srgb = m->srgb;
+    dp->time = 0.0f;
+    return OW_OK;
+}
+
+// The scratch of a draw and its launches on the context's stream.  Sources: an emitter's resident arrays, or `upload` (host instances, copied
+// into the scratch first).  A block that has to grow while launches already enqueued may still read it is replaced behind one synchronisation.
+ow_status billboard_enqueue(ow_context *c, const ow::CameraParams &cp, const ow::SprayDrawParams &dp, int bin_side, const ow_spray *e,
+                            const ow_spray_instance *upload, uint32_t slots, ow::RenderPixel *pixels_dev, uint32_t *rgba_dev) {
+    const BillboardPlan p = billboard_plan(cp.width, cp.height, slots, bin_side, upload != nullptr);
+    if (c->billboard.ptr && p.total > c->billboard.bytes) {
+        ++c->host_syncs;
+        OW_HIP(hipStreamSynchronize(main_stream(c)));
+    }
+    if (ow_status st = c->billboard.ensure(p.total, 0, 1, "bytes of billboard scratch"); st != OW_OK) return st;
+    char *base = (char *)c->billboard.ptr;
+    hipStream_t s = main_stream(c);
+    ow::BillboardArrays A;
+    A.slots = slots;
+    A.counters = (uint32_t *)base;
+    A.masks = (uint64_t *)(base + kBillboardHead);
+    A.clear_bytes = kBillboardHead + (size_t)p.bins.nx * p.bins.ny * p.bins.words * sizeof(uint64_t);
+    A.sprites = (ow::SpraySprite *)(base + p.sprites_off);
+    if (e) {
+        A.instances = e->A.instances;
+        A.draw_list = e->A.draw_list;
+        A.live_count = e->A.live_count;
+    } else {
+        A.instances = (const ow::SprayInstance *)(base + p.instances_off);
+        A.draw_list = nullptr;
+        A.live_count = nullptr;
+        if (slots > 0) OW_HIP(hipMemcpyAsync(base + p.instances_off, upload, (size_t)slots * sizeof(ow::SprayInstance), hipMemcpyHostToDevice, s));
+    }
+    OW_HIP(ow::launch_billboard_draw(A, cp, dp, p.bins, rgba_dev, pixels_dev, s));
+    ++c->billboard_draws;
+    return OW_OK;
+}
+
+// the synchronous forms: the picture goes through the context's pixel blocks (shared with ow_render_view and ow_mesh_draw)
+ow_status billboard_round_trip(ow_context *c, const ow::CameraParams &cp, const ow::SprayDrawParams &dp, int bin_side, const ow_spray *e,
+                               const ow_spray_instance *upload, uint32_t slots, ow_render_pixel *pixels_inout, void *rgba8_out) {
+    OW_HIP(hipSetDevice(c->device));
+    const size_t count = (size_t)cp.width * cp.height;
+    uint32_t *rgba_dev;
+    ow::RenderPixel *pixels_dev;
+    if (ow_status st = pixel_scratch(c, count, rgba8_out, pixels_inout, &rgba_dev, &pixels_dev); st != OW_OK) return st;
+    if (pixels_inout) OW_HIP(hipMemcpyAsync(pixels_dev, pixels_inout, count * sizeof(ow::RenderPixel), hipMemcpyHostToDevice, main_stream(c)));
+    if (ow_status st = billboard_enqueue(c, cp, dp, bin_side, e, upload, slots, pixels_dev, rgba_dev); st != OW_OK) return st;
+    return pixel_download(c, count, rgba8_out, pixels_inout, 0);
+}
+}  // namespace
+
+extern "C" {
+
+void ow_billboard_material_options_default(ow_billboard_material_options *out) {
+    if (!out) return;
+    ow_render_options ro;
+    render_defaults(&ro);
+    std::memset(out, 0, sizeof(*out));
+    for (int k = 0; k < 3; ++k) out->foam_color[k] = ro.foam_color[k];
+    out->max_alpha = ow::kBillboardMaxAlpha;
+    out->albedo_srgb = out->dissolve_srgb = 1u;
+}
+
+ow_status ow_billboard_material_create(ow_context *c, const ow_billboard_material_options *opts, const void *albedo_rgba8, int32_t albedo_width,
+                                       int32_t albedo_height, const void *dissolve_rgba8, int32_t dissolve_width, int32_t dissolve_height,
+                                       ow_billboard_material **out) {
+    if (!opts || !out) return fail(OW_ERR_INVALID, "null argument");
+    for (float v : opts->foam_color)
+        if (!(std::fabs(v) <= 1e38f)) return fail(OW_ERR_INVALID, "ow_billboard_material_options: foam_color is not finite (or beyond 1e38)");
+    if (!(opts->max_alpha >= 0.0f && opts->max_alpha <= 1.0f)) return fail(OW_ERR_INVALID, "ow_billboard_material_options: max_alpha outside [0,1]");
+    if (opts->albedo_srgb > 1u || opts->dissolve_srgb > 1u) return fail(OW_ERR_INVALID, "ow_billboard_material_options: an sRGB flag is not 0 or 1");
+    for (uint32_t r : opts->reserved)
+        if (r != 0u) return fail(OW_ERR_INVALID, "ow_billboard_material_options.reserved must be 0");
+    const int32_t sides[4] = {albedo_width, albedo_height, dissolve_width, dissolve_height};
+    for (int32_t v : sides)
+        if (v < 1 || v > OW_BILLBOARD_TEXTURE_MAX_SIDE) return fail(OW_ERR_INVALID, "texture side %d outside [1,%d]", v, OW_BILLBOARD_TEXTURE_MAX_SIDE);
+    if (!albedo_rgba8 || !dissolve_rgba8) return fail(OW_ERR_INVALID, "null argument");
+    if (!c) return fail(OW_ERR_INVALID, "null context");
+    OW_HIP(hipSetDevice(c->device));
+    ow_billboard_material *m = new (std::nothrow) ow_billboard_material();
+    if (!m) return fail(OW_ERR_NOMEM, "out of host memory");
+    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    float table[256];
+    ow::spray_srgb_table(table);
+    const size_t a_bytes = (size_t)albedo_width * albedo_height * 4, d_bytes = (size_t)dissolve_width * dissolve_height * 4;
+    const size_t t_bytes = up(sizeof(table)), total = t_bytes + up(a_bytes) + up(d_bytes);
+    if (hipMalloc(&m->block, total) != hipSuccess) {
+        (void)hipGetLastError();
+        delete m;
+        return fail(OW_ERR_NOMEM, "hipMalloc failed for %zu bytes of textures", total);
+    }
+    char *base = (char *)m->block;
+    m->ctx = c;
+    m->srgb = (const float *)base;
+    m->albedo = ow::SprayTexture{(const uint32_t *)(base + t_bytes), albedo_width, albedo_height, (int)opts->albedo_srgb};
+    m->dissolve = ow::SprayTexture{(const uint32_t *)(base + t_bytes + up(a_bytes)), dissolve_width, dissolve_height, (int)opts->dissolve_srgb};
+    for (int k = 0; k < 3; ++k) m->foam[k] = opts->foam_color[k];
+    m->max_alpha = opts->max_alpha;
+    hipStream_t s = main_stream(c);
+    if (hipMemcpyAsync(base, table, sizeof(table), hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipMemcpyAsync((void *)m->albedo.texels, albedo_rgba8, a_bytes, hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipMemcpyAsync((void *)m->dissolve.texels, dissolve_rgba8, d_bytes, hipMemcpyHostToDevice, s) != hipSuccess ||
+        (++c->host_syncs, hipStreamSynchronize(s)) != hipSuccess) {
+        const ow_status st = fail(OW_ERR_HIP, "texture upload failed: %s", hipGetErrorString(hipGetLastError()));
+        (void)hipFree(m->block);
+        delete m;
+        return st;
+    }
+    c->materials.push_back(m);
+    *out = m;
+    return OW_OK;
+}
+
+void ow_billboard_material_destroy(ow_context *, ow_billboard_material *m) {
+    if (!m) return;
+    if (ow_context *c = m->ctx) {  // its own context, still alive (ow_destroy clears this field of the materials it outlives)
+        (void)hipSetDevice(c->device);
+        ++c->host_syncs;
+        (void)hipStreamSynchronize(main_stream(c));
+        c->materials.erase(std::remove(c->materials.begin(), c->materials.end(), m), c->materials.end());
+        (void)hipFree(m->block);
+    }
+    delete m;
+}
+
+ow_status ow_billboard_draw(ow_context *c, ow_spray *e, ow_billboard_material *m, const ow_camera *camera, const ow_billboard_draw_options *opts,
+                            ow_render_pixel *pixels_inout, void *rgba8_out) {
+    ow::CameraParams cp;
+    ow::SprayDrawParams dp;
+    int bin_side;
+    if (ow_status st = check_billboard_draw(c, m, camera, opts, pixels_inout, rgba8_out, &cp, &dp, &bin_side); st != OW_OK) return st;
+    if (ow_status st = check_handle(c, e, "spray emitter"); st != OW_OK) return st;
+    dp.time = (float)e->H.time;
+    return billboard_round_trip(c, cp, dp, bin_side, e, nullptr, e->P.amount, pixels_inout, rgba8_out);
+}
+
+ow_status ow_billboard_draw_async(ow_context *c, ow_spray *e, ow_billboard_material *m, const ow_camera *camera, const ow_billboard_draw_options *opts,
+                                  ow_render_pixel *pixels_dev, void *rgba8_dev) {
+    ow::CameraParams cp;
+    ow::SprayDrawParams dp;
+    int bin_side;
+    if (ow_status st = check_billboard_draw(c, m, camera, opts, pixels_dev, rgba8_dev, &cp, &dp, &bin_side); st != OW_OK) return st;
+    if (ow_status st = check_handle(c, e, "spray emitter"); st != OW_OK) return st;
+    if (ow_status st = check_pixel_alignment(rgba8_dev, pixels_dev); st != OW_OK) return st;
+    OW_HIP(hipSetDevice(c->device));
+    dp.time = (float)e->H.time;
+    return billboard_enqueue(c, cp, dp, bin_side, e, nullptr, e->P.amount, (ow::RenderPixel *)pixels_dev, (uint32_t *)rgba8_dev);
+}
+
+ow_status ow_billboard_draw_instances(ow_context *c, ow_billboard_material *m, const ow_spray_instance *instances, int32_t count, float time,
+                                      const ow_camera *camera, const ow_billboard_draw_options *opts, ow_render_pixel *pixels_inout, void *rgba8_out) {
+    if (count < 0 || (uint32_t)count > OW_SPRAY_MAX_AMOUNT) return fail(OW_ERR_INVALID, "count %d outside [0,%u]", count, OW_SPRAY_MAX_AMOUNT);
+    if (count > 0 && !instances) return fail(OW_ERR_INVALID, "null argument");
+    if (!std::isfinite(time)) return fail(OW_ERR_INVALID, "time is not finite");
+    ow::CameraParams cp;
+    ow::SprayDrawParams dp;
+    int bin_side;
+    if (ow_status st = check_billboard_draw(c, m, camera, opts, pixels_inout, rgba8_out, &cp, &dp, &bin_side); st != OW_OK) return st;
+    dp.time = time;
+    return billboard_round_trip(c, cp, dp, bin_side, nullptr, instances, (uint32_t)count, pixels_inout, rgba8_out);
+}
+
+ow_status ow_billboard_draw_stats(ow_context *c, uint64_t *draws, uint64_t *culled, uint64_t *drawn, uint64_t *scratch_bytes) {
+    if (!c) return fail(OW_ERR_INVALID, "null context");
+    if (culled || drawn) {
+        uint32_t w[2] = {0, 0};
+        if (c->billboard.ptr) {
+            OW_HIP(hipSetDevice(c->device));
+            if (ow_status st = sync_stream(c, 0); st != OW_OK) return st;
+            OW_HIP(hipMemcpy(w, c->billboard.ptr, sizeof(w), hipMemcpyDeviceToHost));
+        }
+        if (drawn) *drawn = w[0];
+        if (culled) *culled = w[1];
+    }
+    if (draws) *draws = c->billboard_draws;
+    if (scratch_bytes) *scratch_bytes = c->billboard.bytes;
     return OW_OK;
 }
 

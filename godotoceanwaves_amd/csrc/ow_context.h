@@ -34,6 +34,15 @@ struct ow_spray {
     ow::SprayHostState H{};     // the FP64 clock and the host's bookkeeping
 };
 
+// a billboard material (ow_billboard_material_create, ow_consumer_host.hip)
+struct ow_billboard_material {
+    ow_context *ctx = nullptr;  // nullptr: orphaned by ow_destroy, as a body set
+    void *block = nullptr;      // one allocation: the sRGB table, the albedo texels, the dissolve texels
+    ow::SprayTexture albedo{}, dissolve{};
+    const float *srgb = nullptr;
+    float foam[3] = {0.0f, 0.0f, 0.0f}, max_alpha = 0.0f;
+};
+
 struct ow_context {
     int n = 0, cascades = 0, layers = 0, device = 0;
     float depth = 20.0f;
@@ -148,8 +157,10 @@ struct ow_context {
     bool copy_pending[OW_MAX_CASCADES] = {};
     // The consumers' grow-only scratch (ow_consumer_host.hip).  query: the synchronous point calls' points in and records out (of the largest kind);
     // buoy: bodies, hull points, per-point records, results; ray: rays in, records out; render_rgba / render_pixels: the RGBA8 words and per-pixel
-    // records of the synchronous ow_render_view and ow_mesh_draw; mesh_vis: the draw's visibility words (both forms).
-    ow::DeviceScratch query_scratch, buoy_scratch, ray_scratch, render_rgba, render_pixels, mesh_vis;
+    // records of the synchronous ow_render_view, ow_mesh_draw and ow_billboard_draw; mesh_vis: the draw's visibility words (both forms);
+    // billboard: a billboard draw's counters, bin masks, sprite records and (ow_billboard_draw_instances) the uploaded instances.
+    ow::DeviceScratch query_scratch, buoy_scratch, ray_scratch, render_rgba, render_pixels, mesh_vis, billboard;
+    uint64_t billboard_draws = 0;  // ow_billboard_draw_stats
     uint32_t *ray_bound = nullptr;  // the per-cascade bound words of the slab (ray casts and views), allocated once
     // the velocity layers (ow_update_velocity; ow_velocity_kernels.h): V in the displacement array's layout, the pipeline's own intermediate
     // (vel_slots cascades of one launch pair) and twiddle table, all allocated by the first velocity call
@@ -164,6 +175,7 @@ struct ow_context {
     std::vector<ow_bodies *> body_sets;  // the live sets of this context: ow_destroy orphans what the caller has not destroyed
     std::vector<ow_mesh *> meshes;       // likewise the live meshes
     std::vector<ow_spray *> sprays;      // ... and the live spray emitters
+    std::vector<ow_billboard_material *> materials;  // ... and billboard materials
     uint64_t host_syncs = 0;  // stream synchronisations made on the caller's thread since ow_create (ow_sync_stats)
 };
 

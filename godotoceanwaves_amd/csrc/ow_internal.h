@@ -31,8 +31,9 @@ ow_status resolve_raycast_options(const ow_raycast_options *opts, RaycastParams 
 // the host-side checks of ow_buoyancy / ow_group_buoyancy on host arrays: ranges, body indices, volumes, half heights
 ow_status check_buoyancy_arrays(const ow_buoyancy_body *bodies, int num_bodies, const ow_hull_point *hull, int num_points);
 
-// A grow-only device allocation on the current device.  Nothing that reads the old block may be in flight when it grows: every user but one
-// synchronises before it returns (the mesh draw's visibility words are the exception, ow_consumer_host.hip mesh_vis_scratch).
+// A grow-only device allocation on the current device.  Nothing that reads the old block may be in flight when it grows: every user but two
+// synchronises before it returns (the exceptions synchronise before they grow: the mesh draw's visibility words and the billboard draw's
+// block, ow_consumer_host.hip mesh_vis_scratch and billboard_enqueue).
 struct DeviceScratch {
     void *ptr = nullptr;
     size_t bytes = 0;  // capacity

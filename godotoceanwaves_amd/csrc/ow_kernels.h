@@ -10,6 +10,7 @@
 #include "ow_render.h"
 #include "ow_rigid.h"
 #include "ow_spray.h"
+#include "ow_spray_draw.h"
 #include "ow_surface.h"
 #include "ow_velocity.h"
 #include "ow_velocity_kernels.h"
@@ -110,6 +111,22 @@ struct SprayArrays {
 // k_spray_step, then k_spray_compact, both on `s`
 hipError_t launch_spray_step(int n, int cascades, const DeviceBuffers &buf, const SprayArrays &A, const SurfaceScales &scales, const SprayParams &P,
                              const SprayClock &K, hipStream_t s);
+
+// a billboard draw (ow_spray_draw.hip; the billboard, the coverage rule, fragment() and the blend in ow_spray_draw.h)
+struct BillboardArrays {
+    const SprayInstance *instances;  // [slots]
+    const uint32_t *draw_list;       // [slots] or nullptr: slot k draws instance k
+    const uint32_t *live_count;      // [1] or nullptr: every slot is live
+    uint32_t slots;                  // an emitter's amount, or the caller's count
+    SpraySprite *sprites;            // [slots] scratch
+    uint32_t *counters;              // [2] billboards drawn and culled by the last draw; the masks lie behind them
+    uint64_t *masks;                 // [ny][nx][words] scratch
+    size_t clear_bytes;              // from counters to the end of the masks
+};
+// the clear of the counters and the masks, k_billboard_setup over A.slots slots, k_billboard_blend into the records (read and rewritten) and / or
+// the RGBA8 words (either may be null), all on `s`
+hipError_t launch_billboard_draw(const BillboardArrays &A, const CameraParams &cam, const SprayDrawParams &dp, const BillboardBins &bins, uint32_t *rgba_dev,
+                                 RenderPixel *pixels_dev, hipStream_t s);
 
 bool supported_map_size(int n);
 int kernel_family(int n, int slots, int mode);  // 1 standard, 2 layer-parallel, 3 compact: what launch_pass1/2 will use

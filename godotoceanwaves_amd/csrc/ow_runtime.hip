@@ -1032,6 +1032,11 @@ void ow_destroy(ow_context *c) {
         e->block = nullptr;
         e->ctx = nullptr;
     }
+    for (ow_billboard_material *m : c->materials) {
+        (void)hipFree(m->block);
+        m->block = nullptr;
+        m->ctx = nullptr;
+    }
     for (ow_bodies *set : c->body_sets) {  // sets the caller has not destroyed: their memory goes with the context, the handles stay valid to destroy
         (void)hipFree(set->block);
         set->block = nullptr;
@@ -1058,7 +1063,7 @@ void ow_destroy(ow_context *c) {
     for (auto &e : c->copy_done)
         if (e) (void)hipEventDestroy(e);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
-    for (ow::DeviceScratch *s : {&c->query_scratch, &c->buoy_scratch, &c->ray_scratch, &c->render_rgba, &c->render_pixels, &c->mesh_vis}) s->release();
+    for (ow::DeviceScratch *s : {&c->query_scratch, &c->buoy_scratch, &c->ray_scratch, &c->render_rgba, &c->render_pixels, &c->mesh_vis, &c->billboard}) s->release();
     (void)hipFree(c->ray_bound);
     (void)hipFree(c->vel);
     (void)hipFree(c->vel_scratch);

@@ -106,6 +106,13 @@ class _Spray:
         self.handle, self.amount = handle, amount
 
 
+class _SprayMaterial:
+    """a billboard material on the device (WaveGenerator.spray_material_create)"""
+
+    def __init__(self, handle):
+        self.handle = handle
+
+
 class WaveGenerator:
     """assets/water/wave_generator.gd.  Typical use, as in water.gd:89-91,112-114:
 
@@ -874,6 +881,118 @@ class WaveGenerator:
         v = [C.c_double()] + [C.c_uint64() for _ in range(4)]
         _lib.check(self._lib.ow_spray_stats(self.context, spray.handle, *[C.byref(x) for x in v]))
         return dict(zip(("time", "steps", "restarts", "spawned", "rejected"), (x.value for x in v)))
+
+    # ---- the spray billboards drawn into a camera view (include/ocean_waves.h ow_billboard_*) ----
+    _SPRAY_MATERIAL_OWN = ("foam_color", "max_alpha", "albedo_srgb", "dissolve_srgb")
+    _SPRAY_DRAW_OWN = ("near", "background_color", "bin_side")
+
+    @classmethod
+    def spray_material_options(cls, options=None):
+        """None, an _lib.ow_billboard_material_options, or a dict over ow_billboard_material_options_default's values (the reference scene's
+        foam colour, max_alpha 0.666, both textures sRGB) that may set foam_color, max_alpha, albedo_srgb and dissolve_srgb"""
+        if isinstance(options, _lib.ow_billboard_material_options):
+            return options
+        options = options or {}
+        unknown = [k for k in options if k not in cls._SPRAY_MATERIAL_OWN]
+        if unknown:
+            raise ValueError(f"unknown spray material options {unknown}")
+        o = _lib.ow_billboard_material_options()
+        _lib.load().ow_billboard_material_options_default(C.byref(o))
+        if "foam_color" in options:
+            o.foam_color[:] = [float(v) for v in options["foam_color"]]
+        if "max_alpha" in options:
+            o.max_alpha = float(options["max_alpha"])
+        for k in ("albedo_srgb", "dissolve_srgb"):
+            if k in options:
+                setattr(o, k, int(options[k]))
+        return o
+
+    @classmethod
+    def spray_draw_options(cls, options=None):
+        """None, an _lib.ow_billboard_draw_options, or a dict of near, background_color and bin_side -> ow_billboard_draw_options or None"""
+        if options is None or isinstance(options, _lib.ow_billboard_draw_options):
+            return options
+        unknown = [k for k in options if k not in cls._SPRAY_DRAW_OWN]
+        if unknown:
+            raise ValueError(f"unknown spray draw options {unknown}")
+        o = _lib.ow_billboard_draw_options()
+        if "near" in options:
+            o.near = float(options["near"])
+        if "background_color" in options:
+            o.background_color[:] = [float(v) for v in options["background_color"]]
+        if "bin_side" in options:
+            o.bin_side = int(options["bin_side"])
+        return o
+
+    def spray_material_create(self, albedo_rgba8, dissolve_rgba8, options=None):
+        """A billboard material from two (H, W, 4) uint8 textures, uploaded once; returns a _SprayMaterial (spray_material_destroy() it
+        before free())"""
+        a, d = (np.ascontiguousarray(t, np.uint8) for t in (albedo_rgba8, dissolve_rgba8))
+        for t in (a, d):
+            if t.ndim != 3 or t.shape[2] != 4:
+                raise ValueError("a texture is (height, width, 4) uint8")
+        o = self.spray_material_options(options)
+        out = C.c_void_p()
+        _lib.check(self._lib.ow_billboard_material_create(self.context, C.byref(o), a.ctypes.data, a.shape[1], a.shape[0], d.ctypes.data, d.shape[1],
+                                                          d.shape[0], C.byref(out)))
+        return _SprayMaterial(out)
+
+    def spray_material_destroy(self, material):
+        if material.handle:
+            self._lib.ow_billboard_material_destroy(self.context, material.handle)
+            material.handle = None
+
+    def _spray_picture(self, camera, pixels, want_rgba):
+        h, w = max(int(camera.height), 0), max(int(camera.width), 0)
+        big = h > _lib.OW_RENDER_MAX_SIDE or w > _lib.OW_RENDER_MAX_SIDE   # refused by the library: do not allocate for it
+        rec = None
+        if pixels is not None:
+            rec = np.array(pixels, self.RENDER_PIXEL, copy=True, order="C")
+            if not big and rec.shape != (h, w):
+                raise ValueError(f"pixels is {rec.shape}, the camera's image {(h, w)}")
+        rgba = np.zeros((1, 1, 4) if big else (h, w, 4), np.uint8) if want_rgba or rec is None else None
+        return rgba, rec
+
+    def spray_draw(self, spray, material, camera, options=None, pixels=None, rgba=True):
+        """The emitter's live particles blended over `pixels` ((H, W) RENDER_PIXEL records of mesh_draw or render_view; None: the options'
+        background colour, no depth): ((H, W, 4) uint8 RGBA, the records rewritten or None); a record's reserved[1] counts the fragments
+        blended, reserved[2] is the last one's particle index + 1.  Synchronises."""
+        o = self.spray_draw_options(options)
+        img, rec = self._spray_picture(camera, pixels, rgba)
+        _lib.check(self._lib.ow_billboard_draw(self.context, spray.handle, material.handle, C.byref(camera), C.byref(o) if o is not None else None,
+                                               rec.ctypes.data if rec is not None else None, img.ctypes.data if img is not None else None))
+        return img, rec
+
+    def spray_draw_instances(self, material, instances, time, camera, options=None, pixels=None, rgba=True):
+        """spray_draw over a host array of SPRAY_INSTANCE records, drawn in array order, with TIME = time"""
+        inst = np.ascontiguousarray(instances, self.SPRAY_INSTANCE).reshape(-1)
+        o = self.spray_draw_options(options)
+        img, rec = self._spray_picture(camera, pixels, rgba)
+        _lib.check(self._lib.ow_billboard_draw_instances(self.context, material.handle, inst.ctypes.data if len(inst) else None, len(inst), float(time),
+                                                         C.byref(camera), C.byref(o) if o is not None else None,
+                                                         rec.ctypes.data if rec is not None else None, img.ctypes.data if img is not None else None))
+        return img, rec
+
+    def spray_draw_async(self, spray, material, camera, rgba_device, pixels_device=None, options=None):
+        """The draw over DEVICE buffers (mesh_draw_async's), enqueued in the generator's stream order without synchronising; the records are
+        read and rewritten in place"""
+        def addr(b):
+            return None if b is None else (int(b.data_ptr()) if hasattr(b, "data_ptr") else int(b))
+        count = int(camera.width) * int(camera.height)
+        for buf, size in ((rgba_device, 4), (pixels_device, self.RENDER_PIXEL.itemsize)):
+            if hasattr(buf, "numel") and hasattr(buf, "element_size") and buf.numel() * buf.element_size() < count * size:
+                raise ValueError(f"a device buffer holds fewer than {count} pixels of {size} bytes")
+        o = self.spray_draw_options(options)
+        _lib.check(self._lib.ow_billboard_draw_async(self.context, spray.handle, material.handle, C.byref(camera), C.byref(o) if o is not None else None,
+                                                     addr(pixels_device), addr(rgba_device)))
+
+    def spray_draw_stats(self, counters=True):
+        """dict of draws, the scratch bytes held and, with counters (synchronising), the billboards the last draw culled and drawn"""
+        v = [C.c_uint64() for _ in range(4)]
+        _lib.check(self._lib.ow_billboard_draw_stats(self.context, C.byref(v[0]), C.byref(v[1]) if counters else None, C.byref(v[2]) if counters else None,
+                                                     C.byref(v[3])))
+        keys = ("draws", "culled", "drawn", "scratch_bytes")
+        return {k: x.value for k, x in zip(keys, v) if counters or k in ("draws", "scratch_bytes")}
 
     def get_push_constants(self, cascade):
         """(spectrum[16], modulate[8], unpack[4]) uint32 words: the reference's push-constant blocks of this cascade's most recent launch"""

@@ -966,6 +966,101 @@ ow_status ow_spray_get_device_ptrs(ow_context *ctx, ow_spray *spray, void **inst
 ow_status ow_spray_stats(ow_context *ctx, ow_spray *spray, double *time, uint64_t *steps, uint64_t *restarts, uint64_t *spawned,
                          uint64_t *rejected);
 
+/* The spray billboards drawn into a camera view: assets/shaders/spatial/sea_spray.gdshader over the instances an ow_spray emitter keeps
+ * resident -- vertex() :18-24 (billboarding) and fragment() :26-34 (albedo x foam colour, distance fade, dissolve) -- alpha-blended into a
+ * picture that ow_mesh_draw or ow_render_view produced and depth-tested against it, in the context's stream order.  (The calls are named
+ * ow_billboard_*: ow_spray_* is the emitter's own family.)  The definition, independent of how it is computed:
+ *   billboard  a QuadMesh of size 1 x 1 facing +Z.  :20-21 put it at the instance's origin with the camera's axes, scaled by the lengths of
+ *              the instance's basis columns.  In view space (x right, y up, z back) its centre is C = B^T (origin - camera.position), with
+ *              ow_mesh_vertex.view_position's operations in their order; its half extents are hx = |column 0| / 2 and hy = |column 1| / 2,
+ *              |column k| = sqrtf((c0 c0 + c1 c1) + c2 c2) in FP32 over rows 0, 1, 2, an IEEE square root.  The whole quad lies at view
+ *              depth s = -C.z
+ *   coverage   pixel (i, j)'s ray is ow_render_view's (x, y, -1); it meets the quad's plane at (s x, s y, -s).  The pixel is covered when
+ *              |s x - C.x| <= hx, |s y - C.y| <= hy, hx > 0, hy > 0 and near < s <= camera.max_distance.  Edges are inclusive, there is no
+ *              anti-aliasing.  A billboard behind the camera or before the near plane covers nothing; it lies at one depth, so nothing is
+ *              clipped
+ *   varyings   UV = ((s x - C.x) / (2 hx) + 0.5, 0.5 - (s y - C.y) / (2 hy)): (0, 0) at the quad's top-left.  VERTEX.xz = (s x, -s)
+ *   fragment() :27-33 as written, products left to right: ALBEDO = (albedo.rgb foam_color) (1.65, 1.75, 1.65), distance_fade =
+ *              1 - exp(-length(VERTEX.xz) 0.04) with exp written out in FP32 adds and multiplies (ow_surface.h's exp_f32), ALPHA =
+ *              ((albedo.a max_alpha) distance_fade) max((custom.w + custom.z) 0.5 - dissolve.x, 0), the dissolve texture read at
+ *              UV + TIME 0.35.  foam_color and max_alpha are the material's.  TIME is the emitter's clock after its last step, narrowed as
+ *              the step narrows it (ow_billboard_draw_instances takes it as an argument).  The material is unshaded: the fragment's colour
+ *              is ALBEDO
+ *   texture()  this library's choice -- Godot's sampler is engine code: level 0 only, no mip maps; repeat in both directions, u - floor(u)
+ *              first; bilinear on texel centres (f = u W - 0.5, floor, fraction, the two indices wrapped into [0, W)) in FP32 in a fixed
+ *              order.  Textures are the caller's RGBA8 arrays.  Both uniforms are source_color: the R, G and B bytes go through a 256-entry
+ *              sRGB -> linear table computed once on the host in FP64 and narrowed, unless the texture's flag turns it off (byte / 255);
+ *              A is a / 255.  The scene's dissolve texture is an engine-generated NoiseTexture2D: always the caller's to supply
+ *   depth      against the background pixel's record: a fragment passes when the record has no OW_RAY_HIT, or when its distance along the
+ *              pixel's normalised ray, s sqrtf((x x + y y) + 1) in FP32, is <= the record's t.  Spray writes no depth
+ *   blend      dst = dst (1 - ALPHA) + ALBEDO ALPHA (GLSL's mix) per channel in linear FP32; a channel whose result is not finite takes
+ *              ALBEDO.  Per pixel, fragments are blended in ascending particle index over the emitter's draw list (a MultiMesh draws its
+ *              instances in that order; the reference sets no depth sort).  A fragment whose ALPHA is not > 0 is not counted and changes
+ *              nothing
+ *   outputs    every pixel's record keeps all but three fields: color is replaced, reserved[1] is the number of fragments blended,
+ *              reserved[2] the particle index + 1 of the last one (0: none).  RGBA8 is written as ow_render_view writes it
+ *   finite     an instance with a value that is not finite is skipped, as is one whose centre, extents or (custom.w + custom.z) 0.5 are
+ *              not finite.  A camera that is not finite (ow_mesh_draw's rule) leaves every colour as it was, the two counters 0
+ * The picture depends on the inputs alone, never on scheduling.  Nothing returned is NaN or Inf for a finite background.  The exact
+ * operations, identical in every build, are godotoceanwaves_amd/csrc/ow_spray_draw.h's.  There is no group form (ow_group_*) of these
+ * calls. */
+#define OW_BILLBOARD_TEXTURE_MAX_SIDE 4096 /* the largest width or height of a material's texture */
+typedef struct ow_billboard_material ow_billboard_material; /* opaque; belongs to the context it was created on */
+typedef struct ow_billboard_material_options {
+    float foam_color[3];        /* linear: the global uniform of sea_spray.gdshader:9 (water.gd:17-18 converts its sRGB colour); |v| <= 1e38 */
+    float max_alpha;            /* sea_spray.gdshader:11, 0 .. 1 */
+    uint32_t albedo_srgb;       /* 1: albedo_texture's R, G, B are sRGB (source_color); 0: linear bytes */
+    uint32_t dissolve_srgb;     /* the same for dissolve_texture */
+    uint32_t reserved[10];      /* 0 */
+} ow_billboard_material_options; /* 64 bytes */
+typedef struct ow_billboard_draw_options {
+    float near;                 /* the near plane's view depth, metres; <= 0 selects 0.05 (Camera3D.near) */
+    float background_color[3];  /* linear; the colour of every pixel when pixels_inout is NULL */
+    int32_t bin_side;           /* measurement: pixels a side of the coarse bins the billboards are sorted into, a multiple of 8 up to
+                                   8192; 0 = the default (64).  The picture does not depend on it */
+    uint32_t flags;             /* 0 */
+    uint32_t reserved[10];      /* 0 */
+} ow_billboard_draw_options;    /* 64 bytes; a NULL pointer = near 0.05, a black background */
+typedef char ow_layout_check_billboard_material_options[(sizeof(ow_billboard_material_options) == 64 &&
+                                                         offsetof(ow_billboard_material_options, albedo_srgb) == 16) ? 1 : -1];
+typedef char ow_layout_check_billboard_draw_options[(sizeof(ow_billboard_draw_options) == 64 && offsetof(ow_billboard_draw_options, bin_side) == 16 &&
+                                                     offsetof(ow_billboard_draw_options, reserved) == 24) ? 1 : -1];
+
+/* foam_color as ow_render_options_default's, max_alpha 0.666 (main.tscn:94), sRGB on for both textures. */
+void ow_billboard_material_options_default(ow_billboard_material_options *out);
+/* Uploads the two textures once: width * height RGBA8 texels each, rows from the top, every side 1 .. OW_BILLBOARD_TEXTURE_MAX_SIDE.  The
+ * options and the sizes are checked before anything else is looked at: a value that is not finite, max_alpha outside [0, 1], an sRGB flag
+ * above 1, a reserved word that is not 0, a side out of range or a null pointer is OW_ERR_INVALID and nothing is written, *out included.
+ * Synchronises.  Destroy the material before its context (one that outlives it can still be destroyed; every other call on it is
+ * OW_ERR_STATE). */
+ow_status ow_billboard_material_create(ow_context *ctx, const ow_billboard_material_options *opts, const void *albedo_rgba8, int32_t albedo_width,
+                                       int32_t albedo_height, const void *dissolve_rgba8, int32_t dissolve_width, int32_t dissolve_height,
+                                       ow_billboard_material **out);
+void ow_billboard_material_destroy(ow_context *ctx, ow_billboard_material *material);
+/* Draws the emitter's live particles over a picture in host memory, after everything enqueued so far.  pixels_inout: width * height
+ * ow_render_pixel records as ow_mesh_draw or ow_render_view wrote them, read and rewritten; it may be NULL: every pixel is then
+ * opts->background_color with no depth, and rgba8_out is required.  rgba8_out: width * height * 4 bytes, may be NULL with records.
+ * Synchronises.  The argument checks are ow_mesh_draw's, in its order: outputs, camera, options (near not finite, a background colour not
+ * finite, bin_side not 0 or a multiple of 8 in [8, 8192], flags or reserved words not 0), then the context, the material and the emitter
+ * (one of another context is refused); OW_ERR_INVALID writes nothing. */
+ow_status ow_billboard_draw(ow_context *ctx, ow_spray *spray, ow_billboard_material *material, const ow_camera *camera,
+                            const ow_billboard_draw_options *opts, ow_render_pixel *pixels_inout, void *rgba8_out);
+/* The same with DEVICE pointers on the context's device (rgba8_dev 4-byte aligned, pixels_dev 16-byte aligned; camera and opts are host
+ * values), ordered exactly as ow_mesh_draw_async: behind everything enqueued so far -- both chains, a caller's stream included -- and ahead
+ * of whatever the context enqueues next.  It reads the emitter's resident instances, draw list and live count on the device: the host never
+ * learns the live count.  No synchronisation and no host traffic; the only allocation is the context's grow-only scratch (the sprite
+ * records and the bins' masks, sized on the host from the emitter's amount and the image size), on first use or growth. */
+ow_status ow_billboard_draw_async(ow_context *ctx, ow_spray *spray, ow_billboard_material *material, const ow_camera *camera,
+                                  const ow_billboard_draw_options *opts, ow_render_pixel *pixels_dev, void *rgba8_dev);
+/* The same kernels over a caller's host array of count instances (0 .. OW_SPRAY_MAX_AMOUNT), drawn in array order, with TIME = time
+ * (finite): for hosts with their own particle systems.  Host pointers as ow_billboard_draw.  Synchronises. */
+ow_status ow_billboard_draw_instances(ow_context *ctx, ow_billboard_material *material, const ow_spray_instance *instances, int32_t count, float time,
+                                      const ow_camera *camera, const ow_billboard_draw_options *opts, ow_render_pixel *pixels_inout,
+                                      void *rgba8_out);
+/* Counters (each output may be NULL): draws enqueued on this context; of its last draw the billboards culled (skipped, or covering no
+ * pixel centre) and drawn; the scratch bytes the context holds for these draws.  Synchronises when culled or drawn is asked for. */
+ow_status ow_billboard_draw_stats(ow_context *ctx, uint64_t *draws, uint64_t *culled, uint64_t *drawn, uint64_t *scratch_bytes);
+
 /* ---- several devices: cascades sharded inside one process ---------------------------------------- */
 
 /* Cascades share nothing (wave_generator.gd:65-85 touches no state of another cascade; README.md:77-80), so a node's GPUs
