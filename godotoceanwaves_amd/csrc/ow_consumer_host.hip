@@ -3,6 +3,11 @@
 // layers, the sea-spray emitter and its billboards).  Plain C++ over
 // the HIP runtime API; the context and the scheduler's services come from ow_context.h.  The synchronous calls' device halves (ow_internal.h
 // *_round_trip) also serve a group's gathered arrays (ow_group.hip).
+//
+// Each repeated thing has one owner here.  The four handle kinds (body sets, meshes, emitters, billboard materials) share one life cycle:
+// Layout places a block's arrays, new_handle allocates, finish_create synchronises and registers, release_handle is the device half of a
+// destroy, check_handle the one ownership check.  The three picture kinds (views, mesh draws, billboard draws) keep their launch in one
+// *_enqueue each, used by the asynchronous form directly and by the synchronous form through picture_round_trip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -34,6 +39,32 @@ ow_status check_point_call(const ow_context *c, const void *in, int32_t count, c
     if (ow_status st = check_point_query(c, count, num_cascades); st != OW_OK) return st;
     if (ow_status st = resolve(opts, params); st != OW_OK) return st;
     if (count > 0 && (!in || !map_scales || !out)) return fail(OW_ERR_INVALID, "null argument");
+    return OW_OK;
+}
+
+// an option struct's reserved words (`name`: the struct's)
+template <size_t N>
+ow_status check_reserved(const uint32_t (&reserved)[N], const char *name) {
+    for (uint32_t r : reserved)
+        if (r != 0u) return fail(OW_ERR_INVALID, "%s.reserved must be 0", name);
+    return OW_OK;
+}
+
+// Where the arrays of one device block lie: each starts 256-byte aligned, in the order they are taken.
+struct Layout {
+    size_t total = 0;
+    size_t take(size_t bytes) {  // the offset of the next array of `bytes`
+        const size_t off = total;
+        total += (bytes + 255) & ~(size_t)255;
+        return off;
+    }
+};
+
+// a synchronising read of device memory: everything the context has enqueued has finished, and has not faulted, first
+ow_status read_back(ow_context *c, void *dst, const void *src, size_t bytes) {
+    OW_HIP(hipSetDevice(c->device));
+    if (ow_status st = sync_stream(c, 0); st != OW_OK) return st;
+    if (bytes > 0) OW_HIP(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
     return OW_OK;
 }
 
@@ -208,16 +239,16 @@ ow_status check_buoyancy_arrays(const ow_buoyancy_body *bodies, int num_bodies, 
 ow_status buoyancy_round_trip(const MapsView &v, DeviceScratch &scratch, const ow_buoyancy_body *bodies, int num_bodies, const ow_hull_point *hull,
                               int num_points, const float *map_scales, int num_cascades, const QueryParams &qp, const BuoyancyParams &bp,
                               ow_buoyancy_result *results, ow_buoyancy_point *points_inout, const u16x4 *vel) {
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t b_bytes = up((size_t)num_bodies * sizeof(BuoyancyBody)), h_bytes = up((size_t)num_points * sizeof(HullPoint));
-    const size_t p_bytes = up((size_t)num_points * sizeof(BuoyancyPoint)), r_bytes = up((size_t)num_bodies * sizeof(BuoyancyResult));
-    if (ow_status st = scratch.ensure(b_bytes + h_bytes + p_bytes + r_bytes, (size_t)1 << 20, 1, "bytes of buoyancy scratch"); st != OW_OK) return st;
+    Layout L;
+    const size_t b_off = L.take((size_t)num_bodies * sizeof(BuoyancyBody)), h_off = L.take((size_t)num_points * sizeof(HullPoint));
+    const size_t p_off = L.take((size_t)num_points * sizeof(BuoyancyPoint)), r_off = L.take((size_t)num_bodies * sizeof(BuoyancyResult));
+    if (ow_status st = scratch.ensure(L.total, (size_t)1 << 20, 1, "bytes of buoyancy scratch"); st != OW_OK) return st;
     hipStream_t s = v.stream;
     char *base = (char *)scratch.ptr;
-    BuoyancyBody *bd = (BuoyancyBody *)base;
-    HullPoint *hd = (HullPoint *)(base + b_bytes);
-    BuoyancyPoint *pd = (BuoyancyPoint *)(base + b_bytes + h_bytes);
-    BuoyancyResult *rd = (BuoyancyResult *)(base + b_bytes + h_bytes + p_bytes);
+    BuoyancyBody *bd = (BuoyancyBody *)(base + b_off);
+    HullPoint *hd = (HullPoint *)(base + h_off);
+    BuoyancyPoint *pd = (BuoyancyPoint *)(base + p_off);
+    BuoyancyResult *rd = (BuoyancyResult *)(base + r_off);
     if (num_bodies > 0) OW_HIP(hipMemcpyAsync(bd, bodies, (size_t)num_bodies * sizeof(BuoyancyBody), hipMemcpyHostToDevice, s));
     if (num_points > 0) OW_HIP(hipMemcpyAsync(hd, hull, (size_t)num_points * sizeof(HullPoint), hipMemcpyHostToDevice, s));
     if (bp.warm_start && num_points > 0) OW_HIP(hipMemcpyAsync(pd, points_inout, (size_t)num_points * sizeof(BuoyancyPoint), hipMemcpyHostToDevice, s));
@@ -411,14 +442,53 @@ ow_status check_rigid_records(const ow_rigid_body *bodies, int first, int count,
     return OW_OK;
 }
 
+// ---- the handles' one life cycle (ow_context.h ow::Handle) ------------------------------------------------------------------------------
 // a handle (`what`: a body set, a mesh) that belongs to this context
-template <class Handle>
-ow_status check_handle(const ow_context *c, const Handle *h, const char *what) {
+ow_status check_handle(const ow_context *c, const ow::Handle *h, const char *what) {
     if (!c) return fail(OW_ERR_INVALID, "null context");
     if (!h) return fail(OW_ERR_INVALID, "null %s", what);
     if (!h->ctx) return fail(OW_ERR_STATE, "the %s's context has been destroyed", what);
     if (h->ctx != c) return fail(OW_ERR_INVALID, "the %s belongs to another context", what);
     return OW_OK;
+}
+// A handle of c with a block of `total` bytes of `what` on c's device (made current).  On failure there is no handle.
+template <class H>
+ow_status new_handle(ow_context *c, size_t total, const char *what, H **out) {
+    OW_HIP(hipSetDevice(c->device));
+    H *h = new (std::nothrow) H();
+    if (!h) return fail(OW_ERR_NOMEM, "out of host memory");
+    if (hipMalloc(&h->block, total) != hipSuccess) {
+        (void)hipGetLastError();
+        delete h;
+        return fail(OW_ERR_NOMEM, "hipMalloc failed for %zu bytes of %s", total, what);
+    }
+    h->ctx = c;
+    *out = h;
+    return OW_OK;
+}
+// The end of a create whose set-up went onto stream s (`enqueued`: all of it did): one counted synchronisation, then the handle is on the
+// context's list and the caller's.  On failure "<what> failed: <the HIP error>", and the handle and its block are gone.
+template <class H>
+ow_status finish_create(ow_context *c, H *h, hipStream_t s, bool enqueued, const char *what, H **out) {
+    if (!enqueued || (++c->host_syncs, hipStreamSynchronize(s)) != hipSuccess) {
+        const ow_status st = fail(OW_ERR_HIP, "%s failed: %s", what, hipGetErrorString(hipGetLastError()));
+        (void)hipFree(h->block);
+        delete h;
+        return st;
+    }
+    c->handles.push_back(h);
+    *out = h;
+    return OW_OK;
+}
+// The device half of a destroy; the caller deletes its own type.  An orphan (ow_destroy cleared ctx and freed the block) has none.
+void release_handle(ow::Handle *h) {
+    ow_context *c = h->ctx;
+    if (!c) return;
+    (void)hipSetDevice(c->device);
+    ++c->host_syncs;
+    (void)hipStreamSynchronize(main_stream(c));
+    c->handles.erase(std::remove(c->handles.begin(), c->handles.end(), h), c->handles.end());
+    (void)hipFree(h->block);
 }
 ow_status check_bodies_handle(const ow_context *c, const ow_bodies *set) { return check_handle(c, set, "body set"); }
 ow_status check_bodies_span(const ow_context *c, const ow_bodies *set, int32_t first, int32_t count, const void *records) {
@@ -460,55 +530,33 @@ ow_status ow_bodies_create(ow_context *c, const ow_rigid_body *bodies, int32_t n
             return fail(OW_ERR_INVALID, "hull point %d: local, volume and half_height must be finite", i);
     if (ow_status st = check_rigid_records(bodies, 0, num_bodies, nullptr); st != OW_OK) return st;
     if (!c) return fail(OW_ERR_INVALID, "null context");
-    OW_HIP(hipSetDevice(c->device));
-    ow_bodies *set = new (std::nothrow) ow_bodies();
-    if (!set) return fail(OW_ERR_NOMEM, "out of host memory");
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t nb = (size_t)num_bodies, np = (size_t)num_points;
-    const size_t s_bytes = up(nb * sizeof(ow::RigidBody)), b_bytes = up(nb * sizeof(ow::BuoyancyBody)), h_bytes = up(np * sizeof(ow::HullPoint));
-    const size_t p_bytes = up(np * sizeof(ow::BuoyancyPoint)), r_bytes = up(nb * sizeof(ow::BuoyancyResult)), f_bytes = up(nb * sizeof(int32_t));
-    const size_t total = s_bytes + b_bytes + h_bytes + p_bytes + r_bytes + f_bytes;
-    if (hipMalloc(&set->block, total) != hipSuccess) {
-        (void)hipGetLastError();
-        delete set;
-        return fail(OW_ERR_NOMEM, "hipMalloc failed for %zu bytes of body set", total);
-    }
+    Layout L;
+    const size_t s_off = L.take(nb * sizeof(ow::RigidBody)), b_off = L.take(nb * sizeof(ow::BuoyancyBody)), h_off = L.take(np * sizeof(ow::HullPoint));
+    const size_t p_off = L.take(np * sizeof(ow::BuoyancyPoint)), r_off = L.take(nb * sizeof(ow::BuoyancyResult)), f_off = L.take(nb * sizeof(int32_t));
+    ow_bodies *set;
+    if (ow_status st = new_handle(c, L.total, "body set", &set); st != OW_OK) return st;
     char *base = (char *)set->block;
-    set->ctx = c;
-    set->A.state = (ow::RigidBody *)base;
-    set->A.records = (ow::BuoyancyBody *)(base + s_bytes);
-    set->A.hull = (const ow::HullPoint *)(base + s_bytes + b_bytes);
-    set->A.pts = (ow::BuoyancyPoint *)(base + s_bytes + b_bytes + h_bytes);
-    set->A.results = (ow::BuoyancyResult *)(base + s_bytes + b_bytes + h_bytes + p_bytes);
-    set->A.flags = (int32_t *)(base + s_bytes + b_bytes + h_bytes + p_bytes + r_bytes);
+    set->A.state = (ow::RigidBody *)(base + s_off);
+    set->A.records = (ow::BuoyancyBody *)(base + b_off);
+    set->A.hull = (const ow::HullPoint *)(base + h_off);
+    set->A.pts = (ow::BuoyancyPoint *)(base + p_off);
+    set->A.results = (ow::BuoyancyResult *)(base + r_off);
+    set->A.flags = (int32_t *)(base + f_off);
     set->A.num_bodies = num_bodies;
     set->A.num_points = num_points;
     set->max_points = max_points;
     set->range = std::move(range);
     hipStream_t s = main_stream(c);
-    if (hipMemsetAsync(set->block, 0, total, s) != hipSuccess ||
-        hipMemcpyAsync(set->A.state, bodies, nb * sizeof(ow::RigidBody), hipMemcpyHostToDevice, s) != hipSuccess ||
-        (np > 0 && hipMemcpyAsync((void *)set->A.hull, hull, np * sizeof(ow::HullPoint), hipMemcpyHostToDevice, s) != hipSuccess) ||
-        ow::launch_bodies_pose(set->A, 0, num_bodies, s) != hipSuccess || (++c->host_syncs, hipStreamSynchronize(s)) != hipSuccess) {
-        const ow_status st = fail(OW_ERR_HIP, "body set upload failed: %s", hipGetErrorString(hipGetLastError()));
-        (void)hipFree(set->block);
-        delete set;
-        return st;
-    }
-    c->body_sets.push_back(set);
-    *out = set;
-    return OW_OK;
+    const bool enqueued = hipMemsetAsync(set->block, 0, L.total, s) == hipSuccess &&
+                          hipMemcpyAsync(set->A.state, bodies, nb * sizeof(ow::RigidBody), hipMemcpyHostToDevice, s) == hipSuccess &&
+                          (np == 0 || hipMemcpyAsync((void *)set->A.hull, hull, np * sizeof(ow::HullPoint), hipMemcpyHostToDevice, s) == hipSuccess) &&
+                          ow::launch_bodies_pose(set->A, 0, num_bodies, s) == hipSuccess;
+    return finish_create(c, set, s, enqueued, "body set upload", out);
 }
 
 void ow_bodies_destroy(ow_context *, ow_bodies *set) {
-    if (!set) return;
-    if (ow_context *c = set->ctx) {  // its own context, still alive (ow_destroy clears this field of the sets it outlives)
-        (void)hipSetDevice(c->device);
-        ++c->host_syncs;
-        (void)hipStreamSynchronize(main_stream(c));
-        c->body_sets.erase(std::remove(c->body_sets.begin(), c->body_sets.end(), set), c->body_sets.end());
-        (void)hipFree(set->block);
-    }
+    if (set) release_handle(set);
     delete set;
 }
 
@@ -520,8 +568,7 @@ ow_status ow_bodies_step(ow_context *c, ow_bodies *set, const float *map_scales,
     ow::BuoyancyParams bp;
     if (ow_status st = ow::resolve_buoyancy_options(opts ? &opts->buoyancy : nullptr, &qp, &bp); st != OW_OK) return st;
     if (opts)
-        for (uint32_t r : opts->reserved)
-            if (r != 0u) return fail(OW_ERR_INVALID, "ow_bodies_options.reserved must be 0");
+        if (ow_status st = check_reserved(opts->reserved, "ow_bodies_options"); st != OW_OK) return st;
     if (!map_scales) return fail(OW_ERR_INVALID, "null argument");
     if (ow_status st = check_bodies_handle(c, set); st != OW_OK) return st;
     if (ow_status st = check_point_query(c, 0, num_cascades); st != OW_OK) return st;
@@ -542,10 +589,7 @@ ow_status ow_bodies_step(ow_context *c, ow_bodies *set, const float *map_scales,
 
 ow_status ow_bodies_get_state(ow_context *c, ow_bodies *set, int32_t first, int32_t count, ow_rigid_body *records) {
     if (ow_status st = check_bodies_span(c, set, first, count, records); st != OW_OK) return st;
-    OW_HIP(hipSetDevice(c->device));
-    if (ow_status st = sync_stream(c, 0); st != OW_OK) return st;
-    if (count > 0) OW_HIP(hipMemcpy(records, set->A.state + first, (size_t)count * sizeof(ow::RigidBody), hipMemcpyDeviceToHost));
-    return OW_OK;
+    return read_back(c, records, set->A.state + first, (size_t)count * sizeof(ow::RigidBody));
 }
 
 ow_status ow_bodies_set_state(ow_context *c, ow_bodies *set, int32_t first, int32_t count, const ow_rigid_body *records) {
@@ -563,10 +607,7 @@ ow_status ow_bodies_set_state(ow_context *c, ow_bodies *set, int32_t first, int3
 
 ow_status ow_bodies_get_results(ow_context *c, ow_bodies *set, int32_t first, int32_t count, ow_buoyancy_result *results) {
     if (ow_status st = check_bodies_span(c, set, first, count, results); st != OW_OK) return st;
-    OW_HIP(hipSetDevice(c->device));
-    if (ow_status st = sync_stream(c, 0); st != OW_OK) return st;
-    if (count > 0) OW_HIP(hipMemcpy(results, set->A.results + first, (size_t)count * sizeof(ow::BuoyancyResult), hipMemcpyDeviceToHost));
-    return OW_OK;
+    return read_back(c, results, set->A.results + first, (size_t)count * sizeof(ow::BuoyancyResult));
 }
 
 ow_status ow_bodies_get_device_ptrs(ow_context *c, ow_bodies *set, void **bodies_dev, void **results_dev, void **points_dev) {
@@ -586,10 +627,8 @@ ow_status ow_sync_stats(const ow_context *c, uint64_t *host_syncs) {
 ow_status ow_bodies_stats(ow_context *c, ow_bodies *set, uint64_t *substeps, uint64_t *fused_launches, uint64_t *split_calls, uint64_t *faulted_bodies) {
     if (ow_status st = check_bodies_handle(c, set); st != OW_OK) return st;
     if (faulted_bodies) {
-        OW_HIP(hipSetDevice(c->device));
-        if (ow_status st = sync_stream(c, 0); st != OW_OK) return st;
         std::vector<int32_t> flags((size_t)set->A.num_bodies);
-        OW_HIP(hipMemcpy(flags.data(), set->A.flags, flags.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        if (ow_status st = read_back(c, flags.data(), set->A.flags, flags.size() * sizeof(int32_t)); st != OW_OK) return st;
         uint64_t n = 0;
         for (int32_t f : flags) n += f != 0;
         *faulted_bodies = n;
@@ -614,8 +653,7 @@ ow_status resolve_raycast_options(const ow_raycast_options *o, RaycastParams *rp
         return fail(OW_ERR_INVALID, "water_level, sample_spacing and tolerance must be finite");
     if (o->max_samples < 0 || o->max_samples > kRayMaxSamples)
         return fail(OW_ERR_INVALID, "max_samples %d outside [0,%d]", o->max_samples, kRayMaxSamples);
-    for (uint32_t r : o->reserved)
-        if (r != 0u) return fail(OW_ERR_INVALID, "ow_raycast_options.reserved must be 0");
+    if (ow_status st = check_reserved(o->reserved, "ow_raycast_options"); st != OW_OK) return st;
     rp->water_level = o->water_level;
     if (o->sample_spacing > 0.0f) rp->spacing = o->sample_spacing;
     if (o->tolerance > 0.0f) rp->tolerance = o->tolerance;
@@ -717,8 +755,7 @@ ow_status resolve_camera(const ow_camera *cam, ow::CameraParams *cp) {
     if (!cam) return fail(OW_ERR_INVALID, "null camera");
     if (cam->width < 1 || cam->width > OW_RENDER_MAX_SIDE || cam->height < 1 || cam->height > OW_RENDER_MAX_SIDE)
         return fail(OW_ERR_INVALID, "camera size %d x %d outside [1,%d]", cam->width, cam->height, OW_RENDER_MAX_SIDE);
-    for (uint32_t r : cam->reserved)
-        if (r != 0u) return fail(OW_ERR_INVALID, "ow_camera.reserved must be 0");
+    if (ow_status st = check_reserved(cam->reserved, "ow_camera"); st != OW_OK) return st;
     for (int k = 0; k < 3; ++k) cp->o[k] = cam->position[k];
     for (int k = 0; k < 9; ++k) cp->B[k] = cam->basis[k];
     cp->tan_half_fov = (float)std::tan((double)cam->fov_y_degrees * (3.14159265358979323846 / 360.0));
@@ -744,8 +781,7 @@ ow_status resolve_render_options(const ow_render_options *opts, ow::RaycastParam
     if (!(opts->roughness >= 0.0f && opts->roughness <= 1.0f)) return fail(OW_ERR_INVALID, "roughness outside [0,1]");
     if (!(opts->normal_strength >= 0.0f && opts->normal_strength <= 1.0f)) return fail(OW_ERR_INVALID, "normal_strength outside [0,1]");
     if (opts->flags != 0u) return fail(OW_ERR_INVALID, "unknown render flags 0x%x", opts->flags);
-    for (uint32_t r : opts->reserved)
-        if (r != 0u) return fail(OW_ERR_INVALID, "ow_render_options.reserved must be 0");
+    if (ow_status st = check_reserved(opts->reserved, "ow_render_options"); st != OW_OK) return st;
     const double lx = opts->light_direction[0], ly = opts->light_direction[1], lz = opts->light_direction[2];
     const double len = std::sqrt(lx * lx + ly * ly + lz * lz);
     if (!(len > 0.0)) return fail(OW_ERR_INVALID, "light_direction has zero length");
@@ -783,21 +819,40 @@ ow_status check_pixel_alignment(const void *rgba8_dev, const void *pixels_dev) {
     return OW_OK;
 }
 
-// The synchronous ow_render_view and ow_mesh_draw write `count` RGBA8 words and / or records into the context's scratch (exact size) and copy what
-// was asked for to the host behind the launch.
-ow_status pixel_scratch(ow_context *c, size_t count, bool rgba, bool pixels, uint32_t **rgba_dev, ow::RenderPixel **pixels_dev) {
-    if (rgba)
+// Every synchronous picture call (views, mesh draws, billboard draws), on the context's device: `enqueue(rgba_dev, pixels_dev)` writes `count`
+// RGBA8 words and / or records into the context's pixel blocks (exact size; a null output's pointer is null), what was asked for is copied to
+// the host behind it, and the stream is synchronised for the layers of `mask`.  upload_records: the records go up first (the billboards blend
+// over them).
+template <class Enqueue>
+ow_status picture_round_trip(ow_context *c, size_t count, void *rgba8_out, ow_render_pixel *pixels_out, bool upload_records, uint32_t mask, Enqueue enqueue) {
+    if (rgba8_out)
         if (ow_status st = c->render_rgba.ensure(count * sizeof(uint32_t), 0, sizeof(uint32_t), "pixels"); st != OW_OK) return st;
-    if (pixels)
+    if (pixels_out)
         if (ow_status st = c->render_pixels.ensure(count * sizeof(ow::RenderPixel), 0, sizeof(ow::RenderPixel), "pixel records"); st != OW_OK) return st;
-    *rgba_dev = rgba ? (uint32_t *)c->render_rgba.ptr : nullptr;
-    *pixels_dev = pixels ? (ow::RenderPixel *)c->render_pixels.ptr : nullptr;
+    uint32_t *rgba_dev = rgba8_out ? (uint32_t *)c->render_rgba.ptr : nullptr;
+    ow::RenderPixel *pixels_dev = pixels_out ? (ow::RenderPixel *)c->render_pixels.ptr : nullptr;
+    if (upload_records && pixels_out) OW_HIP(hipMemcpyAsync(pixels_dev, pixels_out, count * sizeof(ow::RenderPixel), hipMemcpyHostToDevice, main_stream(c)));
+    if (ow_status st = enqueue(rgba_dev, pixels_dev); st != OW_OK) return st;
+    if (rgba8_out) OW_HIP(hipMemcpyAsync(rgba8_out, rgba_dev, count * sizeof(uint32_t), hipMemcpyDeviceToHost, main_stream(c)));
+    if (pixels_out) OW_HIP(hipMemcpyAsync(pixels_out, pixels_dev, count * sizeof(ow::RenderPixel), hipMemcpyDeviceToHost, main_stream(c)));
+    return sync_stream(c, mask);
+}
+// Launches already enqueued (the asynchronous forms) may still read a scratch block that exists and has to grow to `need` bytes: one counted
+// synchronisation through main_stream before DeviceScratch::ensure replaces it.
+ow_status sync_before_growth(ow_context *c, const ow::DeviceScratch &scratch, size_t need) {
+    if (scratch.ptr && need > scratch.bytes) {
+        ++c->host_syncs;
+        OW_HIP(hipStreamSynchronize(main_stream(c)));
+    }
     return OW_OK;
 }
-ow_status pixel_download(ow_context *c, size_t count, void *rgba8_out, ow_render_pixel *pixels_out, int num_cascades) {
-    if (rgba8_out) OW_HIP(hipMemcpyAsync(rgba8_out, c->render_rgba.ptr, count * sizeof(uint32_t), hipMemcpyDeviceToHost, main_stream(c)));
-    if (pixels_out) OW_HIP(hipMemcpyAsync(pixels_out, c->render_pixels.ptr, count * sizeof(ow::RenderPixel), hipMemcpyDeviceToHost, main_stream(c)));
-    return sync_stream(c, layer_mask(num_cascades));
+
+// a view's launch on the context's stream (the bound words are there: ray_bound_words)
+ow_status view_enqueue(ow_context *c, const ow::CameraParams &cp, const float *map_scales, int num_cascades, const ow::RaycastParams &rp,
+                       const ow::ShadeParams &sp, uint32_t *rgba_dev, ow::RenderPixel *pixels_dev) {
+    const ow::MapsView v = view_of(c);
+    OW_HIP(ow::launch_render_view(v.n, num_cascades, v.buf, cp, surface_scales(map_scales, num_cascades), rp, sp, c->ray_bound, rgba_dev, pixels_dev, v.stream));
+    return OW_OK;
 }
 }  // namespace
 
@@ -815,13 +870,8 @@ ow_status ow_render_view(ow_context *c, const ow_camera *camera, const float *ma
     if (ow_status st = check_render(c, camera, map_scales, num_cascades, opts, rgba8_out, pixels_out, &cp, &rp, &sp); st != OW_OK) return st;
     OW_HIP(hipSetDevice(c->device));
     if (ow_status st = ow::ray_bound_words(&c->ray_bound); st != OW_OK) return st;
-    const size_t count = (size_t)cp.width * cp.height;
-    uint32_t *rgba_dev;
-    ow::RenderPixel *pixels_dev;
-    if (ow_status st = pixel_scratch(c, count, rgba8_out, pixels_out, &rgba_dev, &pixels_dev); st != OW_OK) return st;
-    const ow::MapsView v = view_of(c);
-    OW_HIP(ow::launch_render_view(v.n, num_cascades, v.buf, cp, surface_scales(map_scales, num_cascades), rp, sp, c->ray_bound, rgba_dev, pixels_dev, v.stream));
-    return pixel_download(c, count, rgba8_out, pixels_out, num_cascades);
+    return picture_round_trip(c, (size_t)cp.width * cp.height, rgba8_out, pixels_out, false, layer_mask(num_cascades),
+                              [&](uint32_t *rgba_dev, ow::RenderPixel *px_dev) { return view_enqueue(c, cp, map_scales, num_cascades, rp, sp, rgba_dev, px_dev); });
 }
 
 ow_status ow_render_view_async(ow_context *c, const ow_camera *camera, const float *map_scales, int32_t num_cascades, const ow_render_options *opts,
@@ -833,10 +883,7 @@ ow_status ow_render_view_async(ow_context *c, const ow_camera *camera, const flo
     if (ow_status st = check_pixel_alignment(rgba8_dev, pixels_dev); st != OW_OK) return st;
     if (ow_status st = begin_async(c, num_cascades); st != OW_OK) return st;
     if (ow_status st = ow::ray_bound_words(&c->ray_bound); st != OW_OK) return st;
-    const ow::MapsView v = view_of(c);
-    OW_HIP(ow::launch_render_view(v.n, num_cascades, v.buf, cp, surface_scales(map_scales, num_cascades), rp, sp, c->ray_bound, (uint32_t *)rgba8_dev,
-                                  (ow::RenderPixel *)pixels_dev, v.stream));
-    return OW_OK;
+    return view_enqueue(c, cp, map_scales, num_cascades, rp, sp, (uint32_t *)rgba8_dev, (ow::RenderPixel *)pixels_dev);
 }
 
 }  // extern "C"
@@ -870,21 +917,11 @@ ow_status resolve_mesh_options(const ow_mesh_options *opts, ow::MeshParams *mp, 
     if (!std::isfinite(opts->near)) return fail(OW_ERR_INVALID, "near is not finite");
     if (opts->flags & ~OW_MESH_CULL_BACK) return fail(OW_ERR_INVALID, "unknown mesh flags 0x%x", opts->flags);
     if (opts->lane_box < -1 || opts->lane_box > 64) return fail(OW_ERR_INVALID, "lane_box %d outside [-1,64]", opts->lane_box);
-    for (uint32_t r : opts->reserved)
-        if (r != 0u) return fail(OW_ERR_INVALID, "ow_mesh_options.reserved must be 0");
+    if (ow_status st = check_reserved(opts->reserved, "ow_mesh_options"); st != OW_OK) return st;
     if (opts->near > 0.0f) mp->near = opts->near;
     mp->cull_back = (opts->flags & OW_MESH_CULL_BACK) ? 1 : 0;
     mp->lane_box = opts->lane_box == 0 ? ow::kMeshLaneBox : (opts->lane_box < 0 ? 0 : opts->lane_box);
     return OW_OK;
-}
-
-// ow_mesh.h's mesh_camera_ok, on the host
-bool mesh_camera_ok_host(const ow::CameraParams &cp) {
-    bool ok = std::isfinite(cp.tan_half_fov) && std::isfinite(cp.aspect) && std::isfinite(cp.max_distance) && cp.max_distance > 0.0f &&
-              cp.tan_half_fov > 0.0f && cp.aspect > 0.0f;
-    for (float v : cp.o) ok = ok && std::isfinite(v);
-    for (float v : cp.B) ok = ok && std::isfinite(v);
-    return ok;
 }
 
 ow_status check_mesh_handle(const ow_context *c, const ow_mesh *m) { return check_handle(c, m, "mesh"); }
@@ -900,17 +937,23 @@ ow_status check_mesh_draw(const ow_context *c, const ow_mesh *m, const ow_camera
     if (ow_status st = check_point_query(c, 0, num_cascades); st != OW_OK) return st;
     if (ow_status st = check_mesh_handle(c, m); st != OW_OK) return st;
     if (!origin) return fail(OW_ERR_INVALID, "null origin");
-    mp->camera_ok = mesh_camera_ok_host(*cp) ? 1 : 0;
+    mp->camera_ok = ow::mesh_camera_ok(*cp) ? 1 : 0;
     return OW_OK;
 }
 
 // the visibility words of a draw of `count` pixels (exact size)
 ow_status mesh_vis_scratch(ow_context *c, size_t count) {
-    if (c->mesh_vis.ptr && count * sizeof(uint64_t) > c->mesh_vis.bytes) {  // launches already enqueued (the asynchronous draw) may still read the old words
-        ++c->host_syncs;
-        OW_HIP(hipStreamSynchronize(main_stream(c)));
-    }
+    if (ow_status st = sync_before_growth(c, c->mesh_vis, count * sizeof(uint64_t)); st != OW_OK) return st;
     return c->mesh_vis.ensure(count * sizeof(uint64_t), 0, sizeof(uint64_t), "visibility words");
+}
+// a draw's launch on the context's stream (the visibility words are there: mesh_vis_scratch)
+ow_status mesh_enqueue(ow_context *c, ow_mesh *m, const ow::CameraParams &cp, const float *origin, const float *map_scales, int num_cascades,
+                       const ow::MeshParams &mp, const ow::ShadeParams &sp, uint32_t *rgba_dev, ow::RenderPixel *pixels_dev) {
+    const ow::MapsView v = view_of(c);
+    OW_HIP(ow::launch_mesh_draw(v.n, num_cascades, v.buf, m->A, surface_scales(map_scales, num_cascades), mp, cp, sp, origin, (uint64_t *)c->mesh_vis.ptr, rgba_dev,
+                                pixels_dev, v.stream));
+    ++m->draws;
+    return OW_OK;
 }
 }  // namespace
 
@@ -934,50 +977,28 @@ ow_status ow_mesh_create(ow_context *c, const float *vertices_xyz, int32_t num_v
         if (indices[i] < 0 || indices[i] >= num_vertices)
             return fail(OW_ERR_INVALID, "triangle %zu: index %d outside [0,%d)", i / 3, indices[i], num_vertices);
     if (!c) return fail(OW_ERR_INVALID, "null context");
-    OW_HIP(hipSetDevice(c->device));
-    ow_mesh *m = new (std::nothrow) ow_mesh();
-    if (!m) return fail(OW_ERR_NOMEM, "out of host memory");
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t nv = (size_t)num_vertices, nt = (size_t)num_triangles;
-    const size_t l_bytes = up(nv * 3 * sizeof(float)), i_bytes = up(nt * 3 * sizeof(int32_t)), v_bytes = up(nv * sizeof(ow::MeshVertex));
-    const size_t total = l_bytes + i_bytes + v_bytes + 256;
-    if (hipMalloc(&m->block, total) != hipSuccess) {
-        (void)hipGetLastError();
-        delete m;
-        return fail(OW_ERR_NOMEM, "hipMalloc failed for %zu bytes of mesh", total);
-    }
+    Layout L;
+    const size_t l_off = L.take(nv * 3 * sizeof(float)), i_off = L.take(nt * 3 * sizeof(int32_t)), v_off = L.take(nv * sizeof(ow::MeshVertex));
+    const size_t c_off = L.take(4 * sizeof(uint32_t));  // kTriSkipped .. kTriWave
+    ow_mesh *m;
+    if (ow_status st = new_handle(c, L.total, "mesh", &m); st != OW_OK) return st;
     char *base = (char *)m->block;
-    m->ctx = c;
-    m->A.local = (const float *)base;
-    m->A.indices = (const int32_t *)(base + l_bytes);
-    m->A.verts = (ow::MeshVertex *)(base + l_bytes + i_bytes);
-    m->A.counters = (uint32_t *)(base + l_bytes + i_bytes + v_bytes);
+    m->A.local = (const float *)(base + l_off);
+    m->A.indices = (const int32_t *)(base + i_off);
+    m->A.verts = (ow::MeshVertex *)(base + v_off);
+    m->A.counters = (uint32_t *)(base + c_off);
     m->A.num_vertices = num_vertices;
     m->A.num_triangles = num_triangles;
     hipStream_t s = main_stream(c);
-    if (hipMemsetAsync(m->block, 0, total, s) != hipSuccess ||
-        hipMemcpyAsync((void *)m->A.local, vertices_xyz, nv * 3 * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess ||
-        hipMemcpyAsync((void *)m->A.indices, indices, nt * 3 * sizeof(int32_t), hipMemcpyHostToDevice, s) != hipSuccess ||
-        (++c->host_syncs, hipStreamSynchronize(s)) != hipSuccess) {
-        const ow_status st = fail(OW_ERR_HIP, "mesh upload failed: %s", hipGetErrorString(hipGetLastError()));
-        (void)hipFree(m->block);
-        delete m;
-        return st;
-    }
-    c->meshes.push_back(m);
-    *out = m;
-    return OW_OK;
+    const bool enqueued = hipMemsetAsync(m->block, 0, L.total, s) == hipSuccess &&
+                          hipMemcpyAsync((void *)m->A.local, vertices_xyz, nv * 3 * sizeof(float), hipMemcpyHostToDevice, s) == hipSuccess &&
+                          hipMemcpyAsync((void *)m->A.indices, indices, nt * 3 * sizeof(int32_t), hipMemcpyHostToDevice, s) == hipSuccess;
+    return finish_create(c, m, s, enqueued, "mesh upload", out);
 }
 
 void ow_mesh_destroy(ow_context *, ow_mesh *m) {
-    if (!m) return;
-    if (ow_context *c = m->ctx) {  // its own context, still alive (ow_destroy clears this field of the meshes it outlives)
-        (void)hipSetDevice(c->device);
-        ++c->host_syncs;
-        (void)hipStreamSynchronize(main_stream(c));
-        c->meshes.erase(std::remove(c->meshes.begin(), c->meshes.end(), m), c->meshes.end());
-        (void)hipFree(m->block);
-    }
+    if (m) release_handle(m);
     delete m;
 }
 
@@ -997,7 +1018,7 @@ ow_status ow_mesh_displace(ow_context *c, ow_mesh *m, const float *origin, const
     if (ow_status st = check_point_query(c, 0, num_cascades); st != OW_OK) return st;
     if (ow_status st = check_mesh_handle(c, m); st != OW_OK) return st;
     if (!origin) return fail(OW_ERR_INVALID, "null origin");
-    mp.camera_ok = camera && mesh_camera_ok_host(cp) ? 1 : 0;  // a camera that is not finite: view positions are zeros, as without one
+    mp.camera_ok = camera && ow::mesh_camera_ok(cp) ? 1 : 0;  // a camera that is not finite: view positions are zeros, as without one
     OW_HIP(hipSetDevice(c->device));
     OW_HIP(ow::launch_mesh_vertices(c->n, num_cascades, c->buf, m->A, surface_scales(map_scales, num_cascades), mp, cp, camera != nullptr, origin, main_stream(c)));
     if (vertices_out)
@@ -1021,14 +1042,9 @@ ow_status ow_mesh_draw(ow_context *c, ow_mesh *m, const ow_camera *camera, const
     OW_HIP(hipSetDevice(c->device));
     const size_t count = (size_t)cp.width * cp.height;
     if (ow_status st = mesh_vis_scratch(c, count); st != OW_OK) return st;
-    uint32_t *rgba_dev;
-    ow::RenderPixel *pixels_dev;
-    if (ow_status st = pixel_scratch(c, count, rgba8_out, pixels_out, &rgba_dev, &pixels_dev); st != OW_OK) return st;
-    const ow::MapsView v = view_of(c);
-    OW_HIP(ow::launch_mesh_draw(v.n, num_cascades, v.buf, m->A, surface_scales(map_scales, num_cascades), mp, cp, sp, origin, (uint64_t *)c->mesh_vis.ptr, rgba_dev,
-                                pixels_dev, v.stream));
-    ++m->draws;
-    return pixel_download(c, count, rgba8_out, pixels_out, num_cascades);
+    return picture_round_trip(c, count, rgba8_out, pixels_out, false, layer_mask(num_cascades), [&](uint32_t *rgba_dev, ow::RenderPixel *px_dev) {
+        return mesh_enqueue(c, m, cp, origin, map_scales, num_cascades, mp, sp, rgba_dev, px_dev);
+    });
 }
 
 ow_status ow_mesh_draw_async(ow_context *c, ow_mesh *m, const ow_camera *camera, const float *origin, const float *map_scales, int32_t num_cascades,
@@ -1040,20 +1056,14 @@ ow_status ow_mesh_draw_async(ow_context *c, ow_mesh *m, const ow_camera *camera,
     if (ow_status st = check_pixel_alignment(rgba8_dev, pixels_dev); st != OW_OK) return st;
     if (ow_status st = begin_async(c, num_cascades); st != OW_OK) return st;
     if (ow_status st = mesh_vis_scratch(c, (size_t)cp.width * cp.height); st != OW_OK) return st;
-    const ow::MapsView v = view_of(c);
-    OW_HIP(ow::launch_mesh_draw(v.n, num_cascades, v.buf, m->A, surface_scales(map_scales, num_cascades), mp, cp, sp, origin, (uint64_t *)c->mesh_vis.ptr,
-                                (uint32_t *)rgba8_dev, (ow::RenderPixel *)pixels_dev, v.stream));
-    ++m->draws;
-    return OW_OK;
+    return mesh_enqueue(c, m, cp, origin, map_scales, num_cascades, mp, sp, (uint32_t *)rgba8_dev, (ow::RenderPixel *)pixels_dev);
 }
 
 ow_status ow_mesh_stats(ow_context *c, ow_mesh *m, uint64_t *draws, uint64_t *skipped, uint64_t *culled, uint64_t *per_lane, uint64_t *cooperative) {
     if (ow_status st = check_mesh_handle(c, m); st != OW_OK) return st;
     if (skipped || culled || per_lane || cooperative) {
-        OW_HIP(hipSetDevice(c->device));
-        if (ow_status st = sync_stream(c, 0); st != OW_OK) return st;
         uint32_t w[4] = {0, 0, 0, 0};
-        OW_HIP(hipMemcpy(w, m->A.counters, sizeof(w), hipMemcpyDeviceToHost));
+        if (ow_status st = read_back(c, w, m->A.counters, sizeof(w)); st != OW_OK) return st;
         if (skipped) *skipped = w[ow::kTriSkipped];
         if (culled) *culled = w[ow::kTriCulled];
         if (per_lane) *per_lane = w[ow::kTriLane];
@@ -1088,50 +1098,28 @@ ow_status ow_spray_create(ow_context *c, const ow_spray_options *opts, ow_spray 
     ow::SprayHostState H;
     if (const char *why = ow::spray_resolve(o, &P, &H)) return fail(OW_ERR_INVALID, "ow_spray_options: %s", why);
     if (!c) return fail(OW_ERR_INVALID, "null context");
-    OW_HIP(hipSetDevice(c->device));
-    ow_spray *e = new (std::nothrow) ow_spray();
-    if (!e) return fail(OW_ERR_NOMEM, "out of host memory");
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t amount = P.amount, blocks = (amount + ow::kSprayBlock - 1) / ow::kSprayBlock;
-    const size_t p_bytes = up(amount * sizeof(ow::SprayParticle)), i_bytes = up(amount * sizeof(ow::SprayInstance)), d_bytes = up(amount * sizeof(uint32_t));
-    const size_t b_bytes = up(blocks * ow::kSprayBlockWords * sizeof(uint32_t));
-    const size_t total = p_bytes + i_bytes + d_bytes + b_bytes + 256;
-    if (hipMalloc(&e->block, total) != hipSuccess) {
-        (void)hipGetLastError();
-        delete e;
-        return fail(OW_ERR_NOMEM, "hipMalloc failed for %zu bytes of particles", total);
-    }
+    Layout L;
+    const size_t p_off = L.take(amount * sizeof(ow::SprayParticle)), i_off = L.take(amount * sizeof(ow::SprayInstance)), d_off = L.take(amount * sizeof(uint32_t));
+    const size_t b_off = L.take(blocks * ow::kSprayBlockWords * sizeof(uint32_t));
+    const size_t t_off = L.take(2 * sizeof(uint64_t) + sizeof(uint32_t));  // the two totals, the live count behind them
+    ow_spray *e;
+    if (ow_status st = new_handle(c, L.total, "particles", &e); st != OW_OK) return st;
     char *base = (char *)e->block;
-    e->ctx = c;
     e->P = P;
     e->H = H;
-    e->A.particles = (ow::SprayParticle *)base;
-    e->A.instances = (ow::SprayInstance *)(base + p_bytes);
-    e->A.draw_list = (uint32_t *)(base + p_bytes + i_bytes);
-    e->A.block_words = (uint32_t *)(base + p_bytes + i_bytes + d_bytes);
-    e->A.totals = (uint64_t *)(base + p_bytes + i_bytes + d_bytes + b_bytes);
-    e->A.live_count = (uint32_t *)(base + p_bytes + i_bytes + d_bytes + b_bytes + 2 * sizeof(uint64_t));
+    e->A.particles = (ow::SprayParticle *)(base + p_off);
+    e->A.instances = (ow::SprayInstance *)(base + i_off);
+    e->A.draw_list = (uint32_t *)(base + d_off);
+    e->A.block_words = (uint32_t *)(base + b_off);
+    e->A.totals = (uint64_t *)(base + t_off);
+    e->A.live_count = (uint32_t *)(base + t_off + 2 * sizeof(uint64_t));
     hipStream_t s = main_stream(c);
-    if (hipMemsetAsync(e->block, 0, total, s) != hipSuccess || (++c->host_syncs, hipStreamSynchronize(s)) != hipSuccess) {
-        const ow_status st = fail(OW_ERR_HIP, "particle set-up failed: %s", hipGetErrorString(hipGetLastError()));
-        (void)hipFree(e->block);
-        delete e;
-        return st;
-    }
-    c->sprays.push_back(e);
-    *out = e;
-    return OW_OK;
+    return finish_create(c, e, s, hipMemsetAsync(e->block, 0, L.total, s) == hipSuccess, "particle set-up", out);
 }
 
 void ow_spray_destroy(ow_context *, ow_spray *e) {
-    if (!e) return;
-    if (ow_context *c = e->ctx) {  // its own context, still alive (ow_destroy clears this field of the emitters it outlives)
-        (void)hipSetDevice(c->device);
-        ++c->host_syncs;
-        (void)hipStreamSynchronize(main_stream(c));
-        c->sprays.erase(std::remove(c->sprays.begin(), c->sprays.end(), e), c->sprays.end());
-        (void)hipFree(e->block);
-    }
+    if (e) release_handle(e);
     delete e;
 }
 
@@ -1178,10 +1166,8 @@ ow_status ow_spray_get_device_ptrs(ow_context *c, ow_spray *e, void **instances,
 ow_status ow_spray_stats(ow_context *c, ow_spray *e, double *time, uint64_t *steps, uint64_t *restarts, uint64_t *spawned, uint64_t *rejected) {
     if (ow_status st = check_handle(c, e, "spray emitter"); st != OW_OK) return st;
     if (spawned || rejected) {
-        OW_HIP(hipSetDevice(c->device));
-        if (ow_status st = sync_stream(c, 0); st != OW_OK) return st;
         uint64_t w[2] = {0, 0};
-        OW_HIP(hipMemcpy(w, e->A.totals, sizeof(w), hipMemcpyDeviceToHost));
+        if (ow_status st = read_back(c, w, e->A.totals, sizeof(w)); st != OW_OK) return st;
         if (spawned) *spawned = w[0];
         if (rejected) *rejected = w[1];
     }
@@ -1204,12 +1190,13 @@ struct BillboardPlan {
     size_t sprites_off, instances_off, total;
 };
 BillboardPlan billboard_plan(int width, int height, uint32_t slots, int bin_side, bool upload) {
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
     BillboardPlan p;
     p.bins = ow::billboard_bins(width, height, slots, bin_side);
-    p.sprites_off = up(kBillboardHead + (size_t)p.bins.nx * p.bins.ny * p.bins.words * sizeof(uint64_t));
-    p.instances_off = p.sprites_off + up((size_t)slots * sizeof(ow::SpraySprite));
-    p.total = p.instances_off + (upload ? up((size_t)slots * sizeof(ow::SprayInstance)) : 0);
+    Layout L;
+    L.take(kBillboardHead + (size_t)p.bins.nx * p.bins.ny * p.bins.words * sizeof(uint64_t));  // the counters and the masks, at 0
+    p.sprites_off = L.take((size_t)slots * sizeof(ow::SpraySprite));
+    p.instances_off = L.take(upload ? (size_t)slots * sizeof(ow::SprayInstance) : 0);
+    p.total = L.total;
     return p;
 }
 
@@ -1230,8 +1217,7 @@ ow_status resolve_billboard_options(const ow_billboard_draw_options *o, ow::Spra
     if (o->bin_side != 0 && (o->bin_side < 8 || o->bin_side > ow::kBillboardBinMax || o->bin_side % 8 != 0))
         return fail(OW_ERR_INVALID, "bin_side %d is not 0 or a multiple of 8 in [8,%d]", o->bin_side, ow::kBillboardBinMax);
     if (o->flags != 0u) return fail(OW_ERR_INVALID, "unknown billboard flags 0x%x", o->flags);
-    for (uint32_t r : o->reserved)
-        if (r != 0u) return fail(OW_ERR_INVALID, "ow_billboard_draw_options.reserved must be 0");
+    if (ow_status st = check_reserved(o->reserved, "ow_billboard_draw_options"); st != OW_OK) return st;
     if (o->near > 0.0f) dp->near = o->near;
     for (int k = 0; k < 3; ++k) dp->background[k] = o->background_color[k];
     if (o->bin_side > 0) *bin_side = o->bin_side;
@@ -1245,7 +1231,7 @@ ow_status check_billboard_draw(const ow_context *c, const ow_billboard_material 
     if (ow_status st = resolve_camera(camera, cp); st != OW_OK) return st;
     if (ow_status st = resolve_billboard_options(opts, dp, bin_side); st != OW_OK) return st;
     if (ow_status st = check_handle(c, m, "billboard material"); st != OW_OK) return st;
-    dp->camera_ok = mesh_camera_ok_host(*cp) ? 1 : 0;
+    dp->camera_ok = ow::mesh_camera_ok(*cp) ? 1 : 0;
     for (int k = 0; k < 3; ++k) dp->foam[k] = m->foam[k];
     dp->max_alpha = m->max_alpha;
     dp->albedo = m->albedo;
@@ -1256,14 +1242,12 @@ ow_status check_billboard_draw(const ow_context *c, const ow_billboard_material 
 }
 
 // The scratch of a draw and its launches on the context's stream.  Sources: an emitter's resident arrays, or `upload` (host instances, copied
-// into the scratch first).  A block that has to grow while launches already enqueued may still read it is replaced behind one synchronisation.
+// into the scratch first).  A block that has to grow while launches already enqueued may still read it is replaced behind one synchronisation
+// (sync_before_growth).
 ow_status billboard_enqueue(ow_context *c, const ow::CameraParams &cp, const ow::SprayDrawParams &dp, int bin_side, const ow_spray *e,
                             const ow_spray_instance *upload, uint32_t slots, ow::RenderPixel *pixels_dev, uint32_t *rgba_dev) {
     const BillboardPlan p = billboard_plan(cp.width, cp.height, slots, bin_side, upload != nullptr);
-    if (c->billboard.ptr && p.total > c->billboard.bytes) {
-        ++c->host_syncs;
-        OW_HIP(hipStreamSynchronize(main_stream(c)));
-    }
+    if (ow_status st = sync_before_growth(c, c->billboard, p.total); st != OW_OK) return st;
     if (ow_status st = c->billboard.ensure(p.total, 0, 1, "bytes of billboard scratch"); st != OW_OK) return st;
     char *base = (char *)c->billboard.ptr;
     hipStream_t s = main_stream(c);
@@ -1288,17 +1272,13 @@ ow_status billboard_enqueue(ow_context *c, const ow::CameraParams &cp, const ow:
     return OW_OK;
 }
 
-// the synchronous forms: the picture goes through the context's pixel blocks (shared with ow_render_view and ow_mesh_draw)
+// the synchronous forms: picture_round_trip with the records uploaded first and no layer to refuse (the draw reads no map)
 ow_status billboard_round_trip(ow_context *c, const ow::CameraParams &cp, const ow::SprayDrawParams &dp, int bin_side, const ow_spray *e,
                                const ow_spray_instance *upload, uint32_t slots, ow_render_pixel *pixels_inout, void *rgba8_out) {
     OW_HIP(hipSetDevice(c->device));
-    const size_t count = (size_t)cp.width * cp.height;
-    uint32_t *rgba_dev;
-    ow::RenderPixel *pixels_dev;
-    if (ow_status st = pixel_scratch(c, count, rgba8_out, pixels_inout, &rgba_dev, &pixels_dev); st != OW_OK) return st;
-    if (pixels_inout) OW_HIP(hipMemcpyAsync(pixels_dev, pixels_inout, count * sizeof(ow::RenderPixel), hipMemcpyHostToDevice, main_stream(c)));
-    if (ow_status st = billboard_enqueue(c, cp, dp, bin_side, e, upload, slots, pixels_dev, rgba_dev); st != OW_OK) return st;
-    return pixel_download(c, count, rgba8_out, pixels_inout, 0);
+    return picture_round_trip(c, (size_t)cp.width * cp.height, rgba8_out, pixels_inout, true, 0, [&](uint32_t *rgba_dev, ow::RenderPixel *pixels_dev) {
+        return billboard_enqueue(c, cp, dp, bin_side, e, upload, slots, pixels_dev, rgba_dev);
+    });
 }
 }  // namespace
 
@@ -1322,57 +1302,34 @@ ow_status ow_billboard_material_create(ow_context *c, const ow_billboard_materia
         if (!(std::fabs(v) <= 1e38f)) return fail(OW_ERR_INVALID, "ow_billboard_material_options: foam_color is not finite (or beyond 1e38)");
     if (!(opts->max_alpha >= 0.0f && opts->max_alpha <= 1.0f)) return fail(OW_ERR_INVALID, "ow_billboard_material_options: max_alpha outside [0,1]");
     if (opts->albedo_srgb > 1u || opts->dissolve_srgb > 1u) return fail(OW_ERR_INVALID, "ow_billboard_material_options: an sRGB flag is not 0 or 1");
-    for (uint32_t r : opts->reserved)
-        if (r != 0u) return fail(OW_ERR_INVALID, "ow_billboard_material_options.reserved must be 0");
+    if (ow_status st = check_reserved(opts->reserved, "ow_billboard_material_options"); st != OW_OK) return st;
     const int32_t sides[4] = {albedo_width, albedo_height, dissolve_width, dissolve_height};
     for (int32_t v : sides)
         if (v < 1 || v > OW_BILLBOARD_TEXTURE_MAX_SIDE) return fail(OW_ERR_INVALID, "texture side %d outside [1,%d]", v, OW_BILLBOARD_TEXTURE_MAX_SIDE);
     if (!albedo_rgba8 || !dissolve_rgba8) return fail(OW_ERR_INVALID, "null argument");
     if (!c) return fail(OW_ERR_INVALID, "null context");
-    OW_HIP(hipSetDevice(c->device));
-    ow_billboard_material *m = new (std::nothrow) ow_billboard_material();
-    if (!m) return fail(OW_ERR_NOMEM, "out of host memory");
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
     float table[256];
     ow::spray_srgb_table(table);
     const size_t a_bytes = (size_t)albedo_width * albedo_height * 4, d_bytes = (size_t)dissolve_width * dissolve_height * 4;
-    const size_t t_bytes = up(sizeof(table)), total = t_bytes + up(a_bytes) + up(d_bytes);
-    if (hipMalloc(&m->block, total) != hipSuccess) {
-        (void)hipGetLastError();
-        delete m;
-        return fail(OW_ERR_NOMEM, "hipMalloc failed for %zu bytes of textures", total);
-    }
+    Layout L;
+    const size_t t_off = L.take(sizeof(table)), a_off = L.take(a_bytes), d_off = L.take(d_bytes);
+    ow_billboard_material *m;
+    if (ow_status st = new_handle(c, L.total, "textures", &m); st != OW_OK) return st;
     char *base = (char *)m->block;
-    m->ctx = c;
-    m->srgb = (const float *)base;
-    m->albedo = ow::SprayTexture{(const uint32_t *)(base + t_bytes), albedo_width, albedo_height, (int)opts->albedo_srgb};
-    m->dissolve = ow::SprayTexture{(const uint32_t *)(base + t_bytes + up(a_bytes)), dissolve_width, dissolve_height, (int)opts->dissolve_srgb};
+    m->srgb = (const float *)(base + t_off);
+    m->albedo = ow::SprayTexture{(const uint32_t *)(base + a_off), albedo_width, albedo_height, (int)opts->albedo_srgb};
+    m->dissolve = ow::SprayTexture{(const uint32_t *)(base + d_off), dissolve_width, dissolve_height, (int)opts->dissolve_srgb};
     for (int k = 0; k < 3; ++k) m->foam[k] = opts->foam_color[k];
     m->max_alpha = opts->max_alpha;
     hipStream_t s = main_stream(c);
-    if (hipMemcpyAsync(base, table, sizeof(table), hipMemcpyHostToDevice, s) != hipSuccess ||
-        hipMemcpyAsync((void *)m->albedo.texels, albedo_rgba8, a_bytes, hipMemcpyHostToDevice, s) != hipSuccess ||
-        hipMemcpyAsync((void *)m->dissolve.texels, dissolve_rgba8, d_bytes, hipMemcpyHostToDevice, s) != hipSuccess ||
-        (++c->host_syncs, hipStreamSynchronize(s)) != hipSuccess) {
-        const ow_status st = fail(OW_ERR_HIP, "texture upload failed: %s", hipGetErrorString(hipGetLastError()));
-        (void)hipFree(m->block);
-        delete m;
-        return st;
-    }
-    c->materials.push_back(m);
-    *out = m;
-    return OW_OK;
+    const bool enqueued = hipMemcpyAsync((void *)m->srgb, table, sizeof(table), hipMemcpyHostToDevice, s) == hipSuccess &&
+                          hipMemcpyAsync((void *)m->albedo.texels, albedo_rgba8, a_bytes, hipMemcpyHostToDevice, s) == hipSuccess &&
+                          hipMemcpyAsync((void *)m->dissolve.texels, dissolve_rgba8, d_bytes, hipMemcpyHostToDevice, s) == hipSuccess;
+    return finish_create(c, m, s, enqueued, "texture upload", out);
 }
 
 void ow_billboard_material_destroy(ow_context *, ow_billboard_material *m) {
-    if (!m) return;
-    if (ow_context *c = m->ctx) {  // its own context, still alive (ow_destroy clears this field of the materials it outlives)
-        (void)hipSetDevice(c->device);
-        ++c->host_syncs;
-        (void)hipStreamSynchronize(main_stream(c));
-        c->materials.erase(std::remove(c->materials.begin(), c->materials.end(), m), c->materials.end());
-        (void)hipFree(m->block);
-    }
+    if (m) release_handle(m);
     delete m;
 }
 
@@ -1417,11 +1374,8 @@ ow_status ow_billboard_draw_stats(ow_context *c, uint64_t *draws, uint64_t *cull
     if (!c) return fail(OW_ERR_INVALID, "null context");
     if (culled || drawn) {
         uint32_t w[2] = {0, 0};
-        if (c->billboard.ptr) {
-            OW_HIP(hipSetDevice(c->device));
-            if (ow_status st = sync_stream(c, 0); st != OW_OK) return st;
-            OW_HIP(hipMemcpy(w, c->billboard.ptr, sizeof(w), hipMemcpyDeviceToHost));
-        }
+        if (c->billboard.ptr)  // no draw yet: zeros, and the device is not touched
+            if (ow_status st = read_back(c, w, c->billboard.ptr, sizeof(w)); st != OW_OK) return st;
         if (drawn) *drawn = w[0];
         if (culled) *culled = w[1];
     }

@@ -1,5 +1,7 @@
 // ow_context.h -- the context behind include/ocean_waves.h and the handles that hang off it, for the two host units that work on them:
-// ow_runtime.hip (the frame scheduler, create / destroy, hand-off, readback) and ow_consumer_host.hip (the read side).
+// ow_runtime.hip (the frame scheduler, create / destroy, hand-off, readback) and ow_consumer_host.hip (the read side).  Every handle kind
+// derives from ow::Handle and the context keeps ONE list of them: ow_consumer_host.hip holds their one life cycle, ow_destroy orphans
+// whatever is still on the list.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -7,37 +9,37 @@
 
 #include "ow_internal.h"
 
-// a body set (ow_bodies_create, ow_consumer_host.hip)
-struct ow_bodies {
+namespace ow {
+// What every device-resident handle of a context starts with.  No virtual destructor: the typed entry points delete their own type.
+struct Handle {
     ow_context *ctx = nullptr;  // nullptr: orphaned by ow_destroy (the device block is gone, the handle is still the caller's to destroy)
-    void *block = nullptr;  // one allocation: states, pose records, hull points, point records, results, fault flags
+    void *block = nullptr;      // the handle's one device allocation
+};
+}  // namespace ow
+
+// a body set (ow_bodies_create): the block holds states, pose records, hull points, point records, results, fault flags
+struct ow_bodies : ow::Handle {
     ow::BodiesArrays A{};
     int max_points = 0;     // the largest point_count of the set
     std::vector<int32_t> range;  // per body point_offset, point_count as created: ow_bodies_set_state may not change them
     uint64_t substeps = 0, fused_launches = 0, split_calls = 0;
 };
 
-// a mesh (ow_mesh_create, ow_consumer_host.hip)
-struct ow_mesh {
-    ow_context *ctx = nullptr;  // nullptr: orphaned by ow_destroy, as a body set
-    void *block = nullptr;      // one allocation: local positions, indices, vertex records, counters
+// a mesh (ow_mesh_create): the block holds local positions, indices, vertex records, counters
+struct ow_mesh : ow::Handle {
     ow::MeshArrays A{};
     uint64_t draws = 0;
 };
 
-// a sea-spray emitter (ow_spray_create, ow_consumer_host.hip)
-struct ow_spray {
-    ow_context *ctx = nullptr;  // nullptr: orphaned by ow_destroy, as a body set
-    void *block = nullptr;      // one allocation: states, instances, draw list, per-block words, live count, totals
+// a sea-spray emitter (ow_spray_create): the block holds states, instances, draw list, per-block words, totals and live count
+struct ow_spray : ow::Handle {
     ow::SprayArrays A{};
     ow::SprayParams P{};
     ow::SprayHostState H{};     // the FP64 clock and the host's bookkeeping
 };
 
-// a billboard material (ow_billboard_material_create, ow_consumer_host.hip)
-struct ow_billboard_material {
-    ow_context *ctx = nullptr;  // nullptr: orphaned by ow_destroy, as a body set
-    void *block = nullptr;      // one allocation: the sRGB table, the albedo texels, the dissolve texels
+// a billboard material (ow_billboard_material_create): the block holds the sRGB table, the albedo texels, the dissolve texels
+struct ow_billboard_material : ow::Handle {
     ow::SprayTexture albedo{}, dissolve{};
     const float *srgb = nullptr;
     float foam[3] = {0.0f, 0.0f, 0.0f}, max_alpha = 0.0f;
@@ -172,10 +174,7 @@ struct ow_context {
     // launching their pass 2 (enqueue); their h0 is newer than their maps, and their velocity is refused until a batch recomputes them.
     uint32_t velocity_stale = 0, spectrum_ahead = 0;
     uint64_t vel_computed = 0, vel_skipped = 0;  // ow_velocity_stats
-    std::vector<ow_bodies *> body_sets;  // the live sets of this context: ow_destroy orphans what the caller has not destroyed
-    std::vector<ow_mesh *> meshes;       // likewise the live meshes
-    std::vector<ow_spray *> sprays;      // ... and the live spray emitters
-    std::vector<ow_billboard_material *> materials;  // ... and billboard materials
+    std::vector<ow::Handle *> handles;  // the live handles of this context, of every kind: ow_destroy orphans what the caller has not destroyed
     uint64_t host_syncs = 0;  // stream synchronisations made on the caller's thread since ow_create (ow_sync_stats)
 };
 

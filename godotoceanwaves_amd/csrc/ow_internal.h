@@ -32,8 +32,8 @@ ow_status resolve_raycast_options(const ow_raycast_options *opts, RaycastParams 
 ow_status check_buoyancy_arrays(const ow_buoyancy_body *bodies, int num_bodies, const ow_hull_point *hull, int num_points);
 
 // A grow-only device allocation on the current device.  Nothing that reads the old block may be in flight when it grows: every user but two
-// synchronises before it returns (the exceptions synchronise before they grow: the mesh draw's visibility words and the billboard draw's
-// block, ow_consumer_host.hip mesh_vis_scratch and billboard_enqueue).
+// synchronises before it returns (the exceptions, the mesh draw's visibility words and the billboard draw's block, synchronise before
+// they grow: ow_consumer_host.hip sync_before_growth).
 struct DeviceScratch {
     void *ptr = nullptr;
     size_t bytes = 0;  // capacity

@@ -61,10 +61,10 @@ struct MeshParams {
 // what the four counters of a draw add up over: every triangle is exactly one of these
 enum : int { kTriSkipped = 0, kTriCulled = 1, kTriLane = 2, kTriWave = 3 };
 
-OW_DEV bool mesh_finite(float v) { return fabsf(v) <= 3.4028235e38f; }  // false for a NaN
+OW_HD bool mesh_finite(float v) { return fabsf(v) <= 3.4028235e38f; }  // false for a NaN
 
 // the camera as the draw needs it: finite, a positive far distance and field of view
-OW_DEV bool mesh_camera_ok(const CameraParams &cam) {
+OW_HD bool mesh_camera_ok(const CameraParams &cam) {
     bool ok = mesh_finite(cam.tan_half_fov) && mesh_finite(cam.aspect) && mesh_finite(cam.max_distance) && cam.max_distance > 0.0f &&
               cam.tan_half_fov > 0.0f && cam.aspect > 0.0f;
     for (int k = 0; k < 3; ++k) ok = ok && mesh_finite(cam.o[k]);

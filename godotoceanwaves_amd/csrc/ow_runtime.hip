@@ -1022,25 +1022,10 @@ void ow_destroy(ow_context *c) {
     (void)hipSetDevice(c->device);
     if (c->side_stream) (void)hipStreamSynchronize(c->side_stream);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    for (ow_mesh *m : c->meshes) {
-        (void)hipFree(m->block);
-        m->block = nullptr;
-        m->ctx = nullptr;
-    }
-    for (ow_spray *e : c->sprays) {
-        (void)hipFree(e->block);
-        e->block = nullptr;
-        e->ctx = nullptr;
-    }
-    for (ow_billboard_material *m : c->materials) {
-        (void)hipFree(m->block);
-        m->block = nullptr;
-        m->ctx = nullptr;
-    }
-    for (ow_bodies *set : c->body_sets) {  // sets the caller has not destroyed: their memory goes with the context, the handles stay valid to destroy
-        (void)hipFree(set->block);
-        set->block = nullptr;
-        set->ctx = nullptr;
+    for (ow::Handle *h : c->handles) {  // handles the caller has not destroyed: their memory goes with the context, they stay valid to destroy
+        (void)hipFree(h->block);
+        h->block = nullptr;
+        h->ctx = nullptr;
     }
     (void)hipFree(c->buf.h0);
     (void)hipFree(c->buf.omega);

@@ -10,7 +10,7 @@ from . import _lib
 from ._lib import (OW_FLAG_DEBUG_F32, OW_FLAG_NO_TICK_GROUPS, OW_GROUP_FLAG_FORCE_PEER_PATH, OW_MAX_DEVICES, ow_cascade_params,
                    ow_group_config)
 from .presets import DEPTH
-from .wave_generator import WaveGenerator
+from .wave_generator import WaveGenerator, _ref, _scales
 
 
 class WaveGeneratorGroup:
@@ -136,7 +136,7 @@ class WaveGeneratorGroup:
 
     def sample_surface(self, world_xz, map_scales):
         xz = np.ascontiguousarray(world_xz, np.float32).reshape(-1, 2)
-        sc = np.ascontiguousarray(map_scales, np.float32).reshape(-1, 4)
+        sc = _scales(map_scales)
         out = np.zeros(len(xz), WaveGenerator.SURFACE_SAMPLE)
         _lib.check(self._lib.ow_group_sample_surface(self.group, xz.ctypes.data, len(xz), sc.ctypes.data, len(sc), out.ctypes.data))
         return out
@@ -144,36 +144,36 @@ class WaveGeneratorGroup:
     def query_surface(self, world_xz, map_scales, options=None):
         """WaveGenerator.query_surface over the gathered arrays on the root device"""
         xz = np.ascontiguousarray(world_xz, np.float32).reshape(-1, 2)
-        sc = np.ascontiguousarray(map_scales, np.float32).reshape(-1, 4)
+        sc = _scales(map_scales)
         out = np.zeros(len(xz), WaveGenerator.SURFACE_QUERY)
         o = WaveGenerator.query_options(options)
         _lib.check(self._lib.ow_group_query_surface(self.group, xz.ctypes.data, len(xz), sc.ctypes.data, len(sc),
-                                                    C.byref(o) if o is not None else None, out.ctypes.data))
+                                                    _ref(o), out.ctypes.data))
         return out
 
     def buoyancy(self, bodies, hull, map_scales, options=None, points=None):
         """WaveGenerator.buoyancy over the gathered arrays on the root device"""
         b = np.ascontiguousarray(bodies, WaveGenerator.BUOYANCY_BODY)
         h = np.ascontiguousarray(hull, WaveGenerator.HULL_POINT)
-        sc = np.ascontiguousarray(map_scales, np.float32).reshape(-1, 4)
+        sc = _scales(map_scales)
         if points is not None and (not isinstance(points, np.ndarray) or points.dtype != WaveGenerator.BUOYANCY_POINT or len(points) != len(h)
                                    or not points.flags.c_contiguous):
             raise ValueError(f"points must be a contiguous BUOYANCY_POINT array of {len(h)} records")
         out = np.zeros(len(b), WaveGenerator.BUOYANCY_RESULT)
         o = WaveGenerator.buoyancy_options(options)
         _lib.check(self._lib.ow_group_buoyancy(self.group, b.ctypes.data, len(b), h.ctypes.data, len(h), sc.ctypes.data, len(sc),
-                                               C.byref(o) if o is not None else None, out.ctypes.data,
+                                               _ref(o), out.ctypes.data,
                                                points.ctypes.data if points is not None else None))
         return out
 
     def raycast_surface(self, rays, map_scales, options=None):
         """WaveGenerator.raycast_surface over the gathered arrays on the root device"""
         r = np.ascontiguousarray(rays, WaveGenerator.RAY)
-        sc = np.ascontiguousarray(map_scales, np.float32).reshape(-1, 4)
+        sc = _scales(map_scales)
         out = np.zeros(len(r), WaveGenerator.RAYCAST_HIT)
         o = WaveGenerator.raycast_options(options)
         _lib.check(self._lib.ow_group_raycast_surface(self.group, r.ctypes.data, len(r), sc.ctypes.data, len(sc),
-                                                      C.byref(o) if o is not None else None, out.ctypes.data))
+                                                      _ref(o), out.ctypes.data))
         return out
 
     def free(self):

@@ -19,6 +19,30 @@ G = 9.81       # wave_generator.gd:5
 DEPTH = 20.0   # wave_generator.gd:6
 
 
+def _scales(map_scales):
+    """map_scales [C][4] (water.gd:105-109) as the contiguous float32 array the C-ABI reads; len() is num_cascades"""
+    return np.ascontiguousarray(map_scales, np.float32).reshape(-1, 4)
+
+
+def _addr(buf, optional=False):
+    """the device address of anything with a data_ptr() (a torch tensor) or of an integer address; optional: None passes (an output a
+    picture call is not asked for)"""
+    if buf is None and optional:
+        return None
+    return int(buf.data_ptr()) if hasattr(buf, "data_ptr") else int(buf)
+
+
+def _ref(o):
+    """an optional struct argument: NULL for None"""
+    return C.byref(o) if o is not None else None
+
+
+def _check_device_size(buf, count, size, name="out_device", unit="records"):
+    """ValueError for a device buffer that knows its size and holds fewer than `count` units of `size` bytes; a bare address passes"""
+    if hasattr(buf, "numel") and hasattr(buf, "element_size") and buf.numel() * buf.element_size() < count * size:
+        raise ValueError(f"{name} holds fewer than {count} {unit} of {size} bytes")
+
+
 def _dirty(name, clamp=None):
     """@export var with `set(value): ...; should_generate_spectrum = true` (wave_cascade_parameters.gd:7-35)"""
     attr = "_" + name
@@ -288,7 +312,7 @@ class WaveGenerator:
         """Evaluate the water vertex/fragment sums and the sea-spray spawn mask at world points [P][2] (x, z);
         map_scales [C][4] as built by Water.map_scales() (water.gd:105-109).  Returns a structured array."""
         xz = np.ascontiguousarray(world_xz, np.float32).reshape(-1, 2)
-        sc = np.ascontiguousarray(map_scales, np.float32).reshape(-1, 4)
+        sc = _scales(map_scales)
         out = np.zeros(len(xz), self.SURFACE_SAMPLE)
         _lib.check(self._lib.ow_sample_surface(self.context, xz.ctypes.data, len(xz), sc.ctypes.data, len(sc), out.ctypes.data))
         return out
@@ -317,29 +341,26 @@ class WaveGenerator:
         """Where the rendered water is above world points [P][2] (x, z): the undisplaced point p, the residual, convergence, the
         rendered height and normal, and the full sample_surface record at p.  Returns a structured array (SURFACE_QUERY)."""
         xz = np.ascontiguousarray(world_xz, np.float32).reshape(-1, 2)
-        sc = np.ascontiguousarray(map_scales, np.float32).reshape(-1, 4)
+        sc = _scales(map_scales)
         out = np.zeros(len(xz), self.SURFACE_QUERY)
         o = self.query_options(options)
         _lib.check(self._lib.ow_query_surface(self.context, xz.ctypes.data, len(xz), sc.ctypes.data, len(sc),
-                                              C.byref(o) if o is not None else None, out.ctypes.data))
+                                              _ref(o), out.ctypes.data))
         return out
 
     def query_surface_async(self, xz_device, map_scales, out_device, options=None, count=None):
         """The query over DEVICE buffers, enqueued in the generator's stream order without synchronising: xz_device holds 2 * count
         float32 (x, z pairs), out_device room for count 128-byte records.  Each is anything with a data_ptr() (a torch tensor) or an
         integer address; count defaults to xz_device.numel() // 2."""
-        def addr(b):
-            return int(b.data_ptr()) if hasattr(b, "data_ptr") else int(b)
         if count is None:
             if not hasattr(xz_device, "numel"):
                 raise ValueError("count is needed for a raw device address")
             count = int(xz_device.numel()) // 2
-        if hasattr(out_device, "numel") and hasattr(out_device, "element_size") and out_device.numel() * out_device.element_size() < count * self.SURFACE_QUERY.itemsize:
-            raise ValueError(f"out_device holds fewer than {count} records of {self.SURFACE_QUERY.itemsize} bytes")
-        sc = np.ascontiguousarray(map_scales, np.float32).reshape(-1, 4)
+        _check_device_size(out_device, count, self.SURFACE_QUERY.itemsize)
+        sc = _scales(map_scales)
         o = self.query_options(options)
-        _lib.check(self._lib.ow_query_surface_async(self.context, addr(xz_device), int(count), sc.ctypes.data, len(sc),
-                                                    C.byref(o) if o is not None else None, addr(out_device)))
+        _lib.check(self._lib.ow_query_surface_async(self.context, _addr(xz_device), int(count), sc.ctypes.data, len(sc),
+                                                    _ref(o), _addr(out_device)))
 
     # ---- buoyancy: per-body force and torque from hull points, on the device (include/ocean_waves.h ow_buoyancy) ----
     BUOYANCY_BODY = np.dtype([("transform", np.float32, 12), ("linear_velocity", np.float32, 3), ("angular_velocity", np.float32, 3),
@@ -395,23 +416,20 @@ class WaveGenerator:
         (and holds the previous step's for the warm start, options {"warm_start": True})."""
         b = np.ascontiguousarray(bodies, self.BUOYANCY_BODY)
         h = np.ascontiguousarray(hull, self.HULL_POINT)
-        sc = np.ascontiguousarray(map_scales, np.float32).reshape(-1, 4)
+        sc = _scales(map_scales)
         if points is not None and (not isinstance(points, np.ndarray) or points.dtype != self.BUOYANCY_POINT or len(points) != len(h)
                                    or not points.flags.c_contiguous):
             raise ValueError(f"points must be a contiguous BUOYANCY_POINT array of {len(h)} records")
         out = np.zeros(len(b), self.BUOYANCY_RESULT)
         o = self.buoyancy_options(options)
         _lib.check(self._lib.ow_buoyancy(self.context, b.ctypes.data, len(b), h.ctypes.data, len(h), sc.ctypes.data, len(sc),
-                                         C.byref(o) if o is not None else None, out.ctypes.data, points.ctypes.data if points is not None else None))
+                                         _ref(o), out.ctypes.data, points.ctypes.data if points is not None else None))
         return out
 
     def buoyancy_async(self, bodies_device, hull_device, map_scales, results_device, points_device, options=None, num_bodies=None,
                        num_points=None):
         """ow_buoyancy_async over DEVICE buffers (torch tensors or integer addresses), enqueued in the generator's stream order without
         synchronising.  The counts default to the tensors' byte sizes over the record sizes."""
-        def addr(x):
-            return int(x.data_ptr()) if hasattr(x, "data_ptr") else int(x)
-
         def records(x, dtype, given, name):
             if given is not None:
                 return int(given)
@@ -421,12 +439,11 @@ class WaveGenerator:
         nb = records(bodies_device, self.BUOYANCY_BODY, num_bodies, "num_bodies")
         npts = records(hull_device, self.HULL_POINT, num_points, "num_points")
         for x, n, dt, name in ((results_device, nb, self.BUOYANCY_RESULT, "results_device"), (points_device, npts, self.BUOYANCY_POINT, "points_device")):
-            if hasattr(x, "numel") and hasattr(x, "element_size") and x.numel() * x.element_size() < n * dt.itemsize:
-                raise ValueError(f"{name} holds fewer than {n} records of {dt.itemsize} bytes")
-        sc = np.ascontiguousarray(map_scales, np.float32).reshape(-1, 4)
+            _check_device_size(x, n, dt.itemsize, name)
+        sc = _scales(map_scales)
         o = self.buoyancy_options(options)
-        _lib.check(self._lib.ow_buoyancy_async(self.context, addr(bodies_device), nb, addr(hull_device), npts, sc.ctypes.data, len(sc),
-                                               C.byref(o) if o is not None else None, addr(results_device), addr(points_device)))
+        _lib.check(self._lib.ow_buoyancy_async(self.context, _addr(bodies_device), nb, _addr(hull_device), npts, sc.ctypes.data, len(sc),
+                                               _ref(o), _addr(results_device), _addr(points_device)))
 
     # ---- floating bodies stepped on the device (include/ocean_waves.h ow_bodies_step) ----
     RIGID_BODY = np.dtype([("position", np.float64, 3), ("orientation", np.float64, 4), ("linear_velocity", np.float64, 3),
@@ -460,16 +477,20 @@ class WaveGenerator:
         _lib.check(self._lib.ow_bodies_create(self.context, b.ctypes.data, len(b), h.ctypes.data, len(h), C.byref(out)))
         return _BodySet(out, len(b), len(h))
 
+    def _destroy(self, obj, fn):
+        """what every *_destroy does: the handle object is spent afterwards, a second destroy of it does nothing"""
+        if obj.handle:
+            fn(self.context, obj.handle)
+            obj.handle = None
+
     def bodies_destroy(self, bodies_set):
-        if bodies_set.handle:
-            self._lib.ow_bodies_destroy(self.context, bodies_set.handle)
-            bodies_set.handle = None
+        self._destroy(bodies_set, self._lib.ow_bodies_destroy)
 
     def bodies_step(self, bodies_set, map_scales, substeps, dt, options=None):
         """`substeps` substeps of dt seconds, enqueued in the generator's stream order without synchronising"""
-        sc = np.ascontiguousarray(map_scales, np.float32).reshape(-1, 4)
+        sc = _scales(map_scales)
         o = self.bodies_options(options)
-        _lib.check(self._lib.ow_bodies_step(self.context, bodies_set.handle, sc.ctypes.data, len(sc), C.byref(o) if o is not None else None, int(substeps),
+        _lib.check(self._lib.ow_bodies_step(self.context, bodies_set.handle, sc.ctypes.data, len(sc), _ref(o), int(substeps),
                                             float(dt)))
 
     def bodies_state(self, bodies_set, first=0, count=None):
@@ -553,29 +574,26 @@ class WaveGenerator:
         """Where each RAY record first meets the rendered water: t, the position, the status bits (_lib.OW_RAY_*), the slab searched
         and the SURFACE_QUERY record at the hit.  Returns a structured array (RAYCAST_HIT)."""
         r = np.ascontiguousarray(rays, self.RAY)
-        sc = np.ascontiguousarray(map_scales, np.float32).reshape(-1, 4)
+        sc = _scales(map_scales)
         out = np.zeros(len(r), self.RAYCAST_HIT)
         o = self.raycast_options(options)
         _lib.check(self._lib.ow_raycast_surface(self.context, r.ctypes.data, len(r), sc.ctypes.data, len(sc),
-                                                C.byref(o) if o is not None else None, out.ctypes.data))
+                                                _ref(o), out.ctypes.data))
         return out
 
     def raycast_surface_async(self, rays_device, map_scales, out_device, options=None, count=None):
         """The ray casts over DEVICE buffers, enqueued in the generator's stream order without synchronising: rays_device holds count
         32-byte RAY records, out_device room for count 192-byte records.  Each is anything with a data_ptr() (a torch tensor) or an
         integer address; count defaults to the byte size of rays_device over 32."""
-        def addr(b):
-            return int(b.data_ptr()) if hasattr(b, "data_ptr") else int(b)
         if count is None:
             if not hasattr(rays_device, "numel"):
                 raise ValueError("count is needed for a raw device address")
             count = int(rays_device.numel() * rays_device.element_size()) // self.RAY.itemsize
-        if hasattr(out_device, "numel") and hasattr(out_device, "element_size") and out_device.numel() * out_device.element_size() < count * self.RAYCAST_HIT.itemsize:
-            raise ValueError(f"out_device holds fewer than {count} records of {self.RAYCAST_HIT.itemsize} bytes")
-        sc = np.ascontiguousarray(map_scales, np.float32).reshape(-1, 4)
+        _check_device_size(out_device, count, self.RAYCAST_HIT.itemsize)
+        sc = _scales(map_scales)
         o = self.raycast_options(options)
-        _lib.check(self._lib.ow_raycast_surface_async(self.context, addr(rays_device), int(count), sc.ctypes.data, len(sc),
-                                                      C.byref(o) if o is not None else None, addr(out_device)))
+        _lib.check(self._lib.ow_raycast_surface_async(self.context, _addr(rays_device), int(count), sc.ctypes.data, len(sc),
+                                                      _ref(o), _addr(out_device)))
 
     # ---- the water's velocity: V = dD/dt per layer, and the surface's velocity above world points (include/ocean_waves.h ow_update_velocity) ----
     SURFACE_VELOCITY = np.dtype([("velocity", np.float32, 3), ("height", np.float32), ("p", np.float32, 2), ("converged", np.int32),
@@ -609,27 +627,24 @@ class WaveGenerator:
         """The velocity of the rendered surface above world points [P][2] (x, z), with ow_query_surface's height, p and convergence.
         Returns a structured array (SURFACE_VELOCITY)."""
         xz = np.ascontiguousarray(world_xz, np.float32).reshape(-1, 2)
-        sc = np.ascontiguousarray(map_scales, np.float32).reshape(-1, 4)
+        sc = _scales(map_scales)
         out = np.zeros(len(xz), self.SURFACE_VELOCITY)
         o = self.query_options(options)
         _lib.check(self._lib.ow_query_velocity(self.context, xz.ctypes.data, len(xz), sc.ctypes.data, len(sc),
-                                               C.byref(o) if o is not None else None, out.ctypes.data))
+                                               _ref(o), out.ctypes.data))
         return out
 
     def query_velocity_async(self, xz_device, map_scales, out_device, options=None, count=None):
         """query_velocity over DEVICE buffers, as query_surface_async (out_device: room for count 32-byte records)"""
-        def addr(b):
-            return int(b.data_ptr()) if hasattr(b, "data_ptr") else int(b)
         if count is None:
             if not hasattr(xz_device, "numel"):
                 raise ValueError("count is needed for a raw device address")
             count = int(xz_device.numel()) // 2
-        if hasattr(out_device, "numel") and hasattr(out_device, "element_size") and out_device.numel() * out_device.element_size() < count * self.SURFACE_VELOCITY.itemsize:
-            raise ValueError(f"out_device holds fewer than {count} records of {self.SURFACE_VELOCITY.itemsize} bytes")
-        sc = np.ascontiguousarray(map_scales, np.float32).reshape(-1, 4)
+        _check_device_size(out_device, count, self.SURFACE_VELOCITY.itemsize)
+        sc = _scales(map_scales)
         o = self.query_options(options)
-        _lib.check(self._lib.ow_query_velocity_async(self.context, addr(xz_device), int(count), sc.ctypes.data, len(sc),
-                                                     C.byref(o) if o is not None else None, addr(out_device)))
+        _lib.check(self._lib.ow_query_velocity_async(self.context, _addr(xz_device), int(count), sc.ctypes.data, len(sc),
+                                                     _ref(o), _addr(out_device)))
 
     # ---- camera views of the water, on the device (include/ocean_waves.h ow_render_view) ----
     RENDER_PIXEL = np.dtype([("t", np.float32), ("status", np.int32), ("position", np.float32, 3), ("p", np.float32, 2), ("wave_height", np.float32),
@@ -648,6 +663,40 @@ class WaveGenerator:
         return cam
 
     @classmethod
+    def _set_material(cls, o, options):
+        """the material and light keys render_options and mesh_options share (_RENDER_OWN), from the dict into the struct"""
+        for k in cls._RENDER_OWN:
+            if k in options:
+                if k in ("roughness", "normal_strength"):
+                    setattr(o, k, float(options[k]))
+                else:
+                    getattr(o, k)[:] = [float(v) for v in options[k]]
+
+    @classmethod
+    def _picture(cls, camera, pixels, want_rgba):
+        """The host arrays of a synchronous picture call: ((H, W, 4) uint8 RGBA or None, (H, W) RENDER_PIXEL records or None).  pixels: None
+        (no records), True (zeroed ones) or records to start from (copied; ValueError unless they have the image's shape).  The RGBA image is
+        left out only where there are records and want_rgba is false."""
+        h, w = max(int(camera.height), 0), max(int(camera.width), 0)
+        big = h > _lib.OW_RENDER_MAX_SIDE or w > _lib.OW_RENDER_MAX_SIDE   # refused by the library: do not allocate for it
+        shape = (1, 1) if big else (h, w)
+        rec = None
+        if pixels is True:
+            rec = np.zeros(shape, cls.RENDER_PIXEL)
+        elif pixels is not None:
+            rec = np.array(pixels, cls.RENDER_PIXEL, copy=True, order="C")
+            if not big and rec.shape != (h, w):
+                raise ValueError(f"pixels is {rec.shape}, the camera's image {(h, w)}")
+        rgba = np.zeros(shape + (4,), np.uint8) if want_rgba or rec is None else None
+        return rgba, rec
+
+    def _check_picture_buffers(self, camera, rgba_device, pixels_device):
+        """the size checks of the asynchronous picture calls' device buffers"""
+        count = int(camera.width) * int(camera.height)
+        for buf, size in ((rgba_device, 4), (pixels_device, self.RENDER_PIXEL.itemsize)):
+            _check_device_size(buf, count, size, "a device buffer", "pixels")
+
+    @classmethod
     def render_options(cls, options=None, camera=None):
         """None, an _lib.ow_render_options, or a dict -> ow_render_options, or None for the defaults.  The dict starts from
         ow_render_options_default's values and may set water_color / foam_color / roughness / normal_strength / light_direction /
@@ -664,40 +713,27 @@ class WaveGenerator:
             ray["falloff_center"] = (camera.position[0], camera.position[2])
         if ray:
             o.raycast = cls.raycast_options(ray)
-        for k in cls._RENDER_OWN:
-            if k in options:
-                if k in ("roughness", "normal_strength"):
-                    setattr(o, k, float(options[k]))
-                else:
-                    getattr(o, k)[:] = [float(v) for v in options[k]]
+        cls._set_material(o, options)
         return o
 
     def render_view(self, camera, map_scales, options=None, pixels=True):
         """The view of an ow_camera (WaveGenerator.camera): ((H, W, 4) uint8 RGBA, (H, W) structured RENDER_PIXEL records, or None with
         pixels=False), rows from the top."""
-        sc = np.ascontiguousarray(map_scales, np.float32).reshape(-1, 4)
+        sc = _scales(map_scales)
         o = self.render_options(options, camera)
-        h, w = max(int(camera.height), 0), max(int(camera.width), 0)
-        big = h > _lib.OW_RENDER_MAX_SIDE or w > _lib.OW_RENDER_MAX_SIDE   # refused by the library: do not allocate for it
-        rgba = np.zeros((1, 1, 4) if big else (h, w, 4), np.uint8)
-        rec = np.zeros((1, 1) if big else (h, w), self.RENDER_PIXEL) if pixels else None
-        _lib.check(self._lib.ow_render_view(self.context, C.byref(camera), sc.ctypes.data, len(sc), C.byref(o) if o is not None else None,
+        rgba, rec = self._picture(camera, True if pixels else None, True)
+        _lib.check(self._lib.ow_render_view(self.context, C.byref(camera), sc.ctypes.data, len(sc), _ref(o),
                                             rgba.ctypes.data, rec.ctypes.data if pixels else None))
         return rgba, rec
 
     def render_view_async(self, camera, map_scales, rgba_device, pixels_device=None, options=None):
         """The view over DEVICE buffers, enqueued in the generator's stream order without synchronising: rgba_device holds H * W * 4 bytes,
         pixels_device H * W 128-byte records; each is anything with a data_ptr() (a torch tensor), an integer address, or None (not both)."""
-        def addr(b):
-            return None if b is None else (int(b.data_ptr()) if hasattr(b, "data_ptr") else int(b))
-        count = int(camera.width) * int(camera.height)
-        for buf, size in ((rgba_device, 4), (pixels_device, self.RENDER_PIXEL.itemsize)):
-            if hasattr(buf, "numel") and hasattr(buf, "element_size") and buf.numel() * buf.element_size() < count * size:
-                raise ValueError(f"a device buffer holds fewer than {count} pixels of {size} bytes")
-        sc = np.ascontiguousarray(map_scales, np.float32).reshape(-1, 4)
+        self._check_picture_buffers(camera, rgba_device, pixels_device)
+        sc = _scales(map_scales)
         o = self.render_options(options, camera)
-        _lib.check(self._lib.ow_render_view_async(self.context, C.byref(camera), sc.ctypes.data, len(sc), C.byref(o) if o is not None else None,
-                                                  addr(rgba_device), addr(pixels_device)))
+        _lib.check(self._lib.ow_render_view_async(self.context, C.byref(camera), sc.ctypes.data, len(sc), _ref(o),
+                                                  _addr(rgba_device, True), _addr(pixels_device, True)))
 
     # ---- a displaced water mesh drawn for a camera, on the device (include/ocean_waves.h ow_mesh_*) ----
     MESH_VERTEX = np.dtype([("position", np.float32, 3), ("wave_height", np.float32), ("uv", np.float32, 2), ("distance_factor", np.float32),
@@ -732,12 +768,7 @@ class WaveGenerator:
         if center is not None:
             o.query_flags = _lib.OW_QUERY_DISTANCE_FALLOFF
             o.falloff_center_xz[:] = [float(v) for v in center]
-        for k in cls._RENDER_OWN:
-            if k in options:
-                if k in ("roughness", "normal_strength"):
-                    setattr(o, k, float(options[k]))
-                else:
-                    getattr(o, k)[:] = [float(v) for v in options[k]]
+        cls._set_material(o, options)
         if "near" in options:
             o.near = float(options["near"])
         if options.get("cull_back"):
@@ -755,18 +786,16 @@ class WaveGenerator:
         return _Mesh(out, len(v), len(t))
 
     def mesh_destroy(self, mesh):
-        if mesh.handle:
-            self._lib.ow_mesh_destroy(self.context, mesh.handle)
-            mesh.handle = None
+        self._destroy(mesh, self._lib.ow_mesh_destroy)
 
     def mesh_displace(self, mesh, origin, map_scales, options=None, camera=None):
         """The vertex stage alone: MESH_VERTEX records of every vertex (view_position only with a camera); synchronises"""
-        sc = np.ascontiguousarray(map_scales, np.float32).reshape(-1, 4)
+        sc = _scales(map_scales)
         org = np.ascontiguousarray(origin, np.float32).reshape(3)
         o = self.mesh_options(options, camera)
         out = np.zeros(mesh.num_vertices, self.MESH_VERTEX)
-        _lib.check(self._lib.ow_mesh_displace(self.context, mesh.handle, org.ctypes.data, sc.ctypes.data, len(sc), C.byref(o) if o is not None else None,
-                                              C.byref(camera) if camera is not None else None, out.ctypes.data))
+        _lib.check(self._lib.ow_mesh_displace(self.context, mesh.handle, org.ctypes.data, sc.ctypes.data, len(sc), _ref(o),
+                                              _ref(camera), out.ctypes.data))
         return out
 
     def mesh_device_ptrs(self, mesh):
@@ -778,30 +807,22 @@ class WaveGenerator:
     def mesh_draw(self, mesh, camera, origin, map_scales, options=None, pixels=True):
         """The mesh as an ow_camera sees it: ((H, W, 4) uint8 RGBA, (H, W) RENDER_PIXEL records or None with pixels=False), rows from the
         top; a record's reserved[0] is the drawn triangle's index + 1."""
-        sc = np.ascontiguousarray(map_scales, np.float32).reshape(-1, 4)
+        sc = _scales(map_scales)
         org = np.ascontiguousarray(origin, np.float32).reshape(3)
         o = self.mesh_options(options, camera)
-        h, w = max(int(camera.height), 0), max(int(camera.width), 0)
-        big = h > _lib.OW_RENDER_MAX_SIDE or w > _lib.OW_RENDER_MAX_SIDE   # refused by the library: do not allocate for it
-        rgba = np.zeros((1, 1, 4) if big else (h, w, 4), np.uint8)
-        rec = np.zeros((1, 1) if big else (h, w), self.RENDER_PIXEL) if pixels else None
+        rgba, rec = self._picture(camera, True if pixels else None, True)
         _lib.check(self._lib.ow_mesh_draw(self.context, mesh.handle, C.byref(camera), org.ctypes.data, sc.ctypes.data, len(sc),
-                                          C.byref(o) if o is not None else None, rgba.ctypes.data, rec.ctypes.data if pixels else None))
+                                          _ref(o), rgba.ctypes.data, rec.ctypes.data if pixels else None))
         return rgba, rec
 
     def mesh_draw_async(self, mesh, camera, origin, map_scales, rgba_device, pixels_device=None, options=None):
         """The draw over DEVICE buffers, enqueued in the generator's stream order without synchronising (render_view_async's buffers)"""
-        def addr(b):
-            return None if b is None else (int(b.data_ptr()) if hasattr(b, "data_ptr") else int(b))
-        count = int(camera.width) * int(camera.height)
-        for buf, size in ((rgba_device, 4), (pixels_device, self.RENDER_PIXEL.itemsize)):
-            if hasattr(buf, "numel") and hasattr(buf, "element_size") and buf.numel() * buf.element_size() < count * size:
-                raise ValueError(f"a device buffer holds fewer than {count} pixels of {size} bytes")
-        sc = np.ascontiguousarray(map_scales, np.float32).reshape(-1, 4)
+        self._check_picture_buffers(camera, rgba_device, pixels_device)
+        sc = _scales(map_scales)
         org = np.ascontiguousarray(origin, np.float32).reshape(3)
         o = self.mesh_options(options, camera)
         _lib.check(self._lib.ow_mesh_draw_async(self.context, mesh.handle, C.byref(camera), org.ctypes.data, sc.ctypes.data, len(sc),
-                                                C.byref(o) if o is not None else None, addr(rgba_device), addr(pixels_device)))
+                                                _ref(o), _addr(rgba_device, True), _addr(pixels_device, True)))
 
     def mesh_stats(self, mesh):
         """dict of draws and, of the last draw (synchronising), the triangles skipped, culled, per_lane and cooperative"""
@@ -849,13 +870,11 @@ class WaveGenerator:
         return _Spray(out, int(o.amount))
 
     def spray_destroy(self, spray):
-        if spray.handle:
-            self._lib.ow_spray_destroy(self.context, spray.handle)
-            spray.handle = None
+        self._destroy(spray, self._lib.ow_spray_destroy)
 
     def spray_step(self, spray, delta, map_scales):
         """One frame of the emitter on the maps as they stand in the generator's stream order; enqueues and returns"""
-        sc = np.ascontiguousarray(map_scales, np.float32).reshape(-1, 4)
+        sc = _scales(map_scales)
         _lib.check(self._lib.ow_spray_step(self.context, spray.handle, float(delta), sc.ctypes.data, len(sc)))
 
     def spray_read(self, spray):
@@ -938,28 +957,15 @@ class WaveGenerator:
         return _SprayMaterial(out)
 
     def spray_material_destroy(self, material):
-        if material.handle:
-            self._lib.ow_billboard_material_destroy(self.context, material.handle)
-            material.handle = None
-
-    def _spray_picture(self, camera, pixels, want_rgba):
-        h, w = max(int(camera.height), 0), max(int(camera.width), 0)
-        big = h > _lib.OW_RENDER_MAX_SIDE or w > _lib.OW_RENDER_MAX_SIDE   # refused by the library: do not allocate for it
-        rec = None
-        if pixels is not None:
-            rec = np.array(pixels, self.RENDER_PIXEL, copy=True, order="C")
-            if not big and rec.shape != (h, w):
-                raise ValueError(f"pixels is {rec.shape}, the camera's image {(h, w)}")
-        rgba = np.zeros((1, 1, 4) if big else (h, w, 4), np.uint8) if want_rgba or rec is None else None
-        return rgba, rec
+        self._destroy(material, self._lib.ow_billboard_material_destroy)
 
     def spray_draw(self, spray, material, camera, options=None, pixels=None, rgba=True):
         """The emitter's live particles blended over `pixels` ((H, W) RENDER_PIXEL records of mesh_draw or render_view; None: the options'
         background colour, no depth): ((H, W, 4) uint8 RGBA, the records rewritten or None); a record's reserved[1] counts the fragments
         blended, reserved[2] is the last one's particle index + 1.  Synchronises."""
         o = self.spray_draw_options(options)
-        img, rec = self._spray_picture(camera, pixels, rgba)
-        _lib.check(self._lib.ow_billboard_draw(self.context, spray.handle, material.handle, C.byref(camera), C.byref(o) if o is not None else None,
+        img, rec = self._picture(camera, pixels, rgba)
+        _lib.check(self._lib.ow_billboard_draw(self.context, spray.handle, material.handle, C.byref(camera), _ref(o),
                                                rec.ctypes.data if rec is not None else None, img.ctypes.data if img is not None else None))
         return img, rec
 
@@ -967,24 +973,19 @@ class WaveGenerator:
         """spray_draw over a host array of SPRAY_INSTANCE records, drawn in array order, with TIME = time"""
         inst = np.ascontiguousarray(instances, self.SPRAY_INSTANCE).reshape(-1)
         o = self.spray_draw_options(options)
-        img, rec = self._spray_picture(camera, pixels, rgba)
+        img, rec = self._picture(camera, pixels, rgba)
         _lib.check(self._lib.ow_billboard_draw_instances(self.context, material.handle, inst.ctypes.data if len(inst) else None, len(inst), float(time),
-                                                         C.byref(camera), C.byref(o) if o is not None else None,
+                                                         C.byref(camera), _ref(o),
                                                          rec.ctypes.data if rec is not None else None, img.ctypes.data if img is not None else None))
         return img, rec
 
     def spray_draw_async(self, spray, material, camera, rgba_device, pixels_device=None, options=None):
         """The draw over DEVICE buffers (mesh_draw_async's), enqueued in the generator's stream order without synchronising; the records are
         read and rewritten in place"""
-        def addr(b):
-            return None if b is None else (int(b.data_ptr()) if hasattr(b, "data_ptr") else int(b))
-        count = int(camera.width) * int(camera.height)
-        for buf, size in ((rgba_device, 4), (pixels_device, self.RENDER_PIXEL.itemsize)):
-            if hasattr(buf, "numel") and hasattr(buf, "element_size") and buf.numel() * buf.element_size() < count * size:
-                raise ValueError(f"a device buffer holds fewer than {count} pixels of {size} bytes")
+        self._check_picture_buffers(camera, rgba_device, pixels_device)
         o = self.spray_draw_options(options)
-        _lib.check(self._lib.ow_billboard_draw_async(self.context, spray.handle, material.handle, C.byref(camera), C.byref(o) if o is not None else None,
-                                                     addr(pixels_device), addr(rgba_device)))
+        _lib.check(self._lib.ow_billboard_draw_async(self.context, spray.handle, material.handle, C.byref(camera), _ref(o),
+                                                     _addr(pixels_device, True), _addr(rgba_device, True)))
 
     def spray_draw_stats(self, counters=True):
         """dict of draws, the scratch bytes held and, with counters (synchronising), the billboards the last draw culled and drawn"""

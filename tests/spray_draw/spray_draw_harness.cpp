@@ -62,13 +62,6 @@ CameraParams camera_of(const CaseHeader &h) {
     cam.height = h.height;
     return cam;
 }
-bool camera_ok_host(const CameraParams &cp) {  // mesh_camera_ok as the runtime evaluates it
-    bool ok = std::isfinite(cp.tan_half_fov) && std::isfinite(cp.aspect) && std::isfinite(cp.max_distance) && cp.max_distance > 0.0f &&
-              cp.tan_half_fov > 0.0f && cp.aspect > 0.0f;
-    for (float v : cp.o) ok = ok && std::isfinite(v);
-    for (float v : cp.B) ok = ok && std::isfinite(v);
-    return ok;
-}
 SprayDrawParams params_of(const CaseHeader &h, const CameraParams &cam, const void *albedo, const void *dissolve, const float *table) {
     SprayDrawParams dp;
     for (int k = 0; k < 3; ++k) {
@@ -78,7 +71,7 @@ SprayDrawParams params_of(const CaseHeader &h, const CameraParams &cam, const vo
     dp.max_alpha = h.max_alpha;
     dp.near = h.near > 0.0f ? h.near : kMeshDefaultNear;
     dp.time = h.time;
-    dp.camera_ok = camera_ok_host(cam) ? 1 : 0;
+    dp.camera_ok = mesh_camera_ok(cam) ? 1 : 0;  // as the runtime evaluates it
     dp.albedo = SprayTexture{(const uint32_t *)albedo, h.aw, h.ah, h.asrgb};
     dp.dissolve = SprayTexture{(const uint32_t *)dissolve, h.dw, h.dh, h.dsrgb};
     dp.srgb = table;
