@@ -26,6 +26,9 @@ OW_QUERY_DISTANCE_FALLOFF = 1
 OW_BUOYANCY_WARM_START = 1
 OW_BUOYANCY_WATER_VELOCITY = 2
 OW_RAY_HIT, OW_RAY_FROM_BELOW, OW_RAY_TRUNCATED, OW_RAY_INVALID = 1, 2, 4, 8
+OW_RAY_SOLID = 16
+OW_SOLID_TWO_SIDED = 1
+OW_SOLID_MAX_INSTANCES, OW_SOLID_MAX_TRIANGLES = 65536, 65536
 OW_RENDER_MAX_SIDE = 8192
 OW_MESH_CULL_BACK = 1
 OW_MESH_VERTEX_NOT_FINITE = 1
@@ -220,6 +223,13 @@ class ow_billboard_draw_options(C.Structure):
                 ("reserved", C.c_uint32 * 10)]
 
 
+class ow_solid_options(C.Structure):
+    """struct ow_solid_options (128 bytes); a NULL pointer = ow_solid_options_default's values"""
+    _fields_ = [("near", C.c_float), ("color", C.c_float * 3), ("light_direction", C.c_float * 3), ("flags", C.c_uint32),
+                ("light_color", C.c_float * 3), ("ambient_color", C.c_float * 3), ("background_color", C.c_float * 3), ("lane_box", C.c_int32),
+                ("reserved", C.c_uint32 * 14)]
+
+
 class ow_mesh_vertex(C.Structure):
     """struct ow_mesh_vertex (48 bytes): the vertex stage's record of a mesh draw"""
     _fields_ = [("position", C.c_float * 3), ("wave_height", C.c_float), ("uv", C.c_float * 2), ("distance_factor", C.c_float),
@@ -314,6 +324,14 @@ SIGNATURES = {
     "ow_billboard_draw_instances": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, _P(ow_camera), _P(ow_billboard_draw_options),
                                               C.c_void_p, C.c_void_p]),
     "ow_billboard_draw_stats": (C.c_int, [C.c_void_p, _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64)]),
+    "ow_solid_options_default": (None, [_P(ow_solid_options)]),
+    "ow_solid_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, _P(C.c_void_p)]),
+    "ow_solid_destroy": (None, [C.c_void_p, C.c_void_p]),
+    "ow_solid_draw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, _P(ow_camera), _P(ow_solid_options), C.c_void_p, C.c_void_p]),
+    "ow_solid_draw_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, _P(ow_camera), _P(ow_solid_options), C.c_void_p,
+                                      C.c_void_p]),
+    "ow_solid_draw_instances": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, _P(ow_camera), _P(ow_solid_options), C.c_void_p, C.c_void_p]),
+    "ow_solid_draw_stats": (C.c_int, [C.c_void_p, _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64)]),
     "ow_get_maps_f32": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
     "ow_get_spectrum": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "ow_get_intermediate": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),

@@ -1,12 +1,12 @@
 // ow_consumer_host.hip -- the read side of include/ocean_waves.h: host wrappers around the kernels of ow_consumer.hip, ow_velocity.hip,
-// ow_mesh.hip, ow_spray.hip and ow_spray_draw.hip (surface samples and queries, buoyancy, floating bodies, ray casts, camera views, mesh draws, the velocity
-// layers, the sea-spray emitter and its billboards).  Plain C++ over
+// ow_mesh.hip, ow_spray.hip, ow_spray_draw.hip and ow_solid.hip (surface samples and queries, buoyancy, floating bodies, ray casts, camera views, mesh draws,
+// the velocity layers, the sea-spray emitter and its billboards, the solids).  Plain C++ over
 // the HIP runtime API; the context and the scheduler's services come from ow_context.h.  The synchronous calls' device halves (ow_internal.h
 // *_round_trip) also serve a group's gathered arrays (ow_group.hip).
 //
-// Each repeated thing has one owner here.  The four handle kinds (body sets, meshes, emitters, billboard materials) share one life cycle:
+// Each repeated thing has one owner here.  The five handle kinds (body sets, meshes, emitters, billboard materials, solid shapes) share one life cycle:
 // Layout places a block's arrays, new_handle allocates, finish_create synchronises and registers, release_handle is the device half of a
-// destroy, check_handle the one ownership check.  The three picture kinds (views, mesh draws, billboard draws) keep their launch in one
+// destroy, check_handle the one ownership check.  The four picture kinds (views, mesh draws, billboard draws, solid draws) keep their launch in one
 // *_enqueue each, used by the asynchronous form directly and by the synchronous form through picture_round_trip.
 #include <hip/hip_runtime.h>
 
@@ -819,10 +819,10 @@ ow_status check_pixel_alignment(const void *rgba8_dev, const void *pixels_dev) {
     return OW_OK;
 }
 
-// Every synchronous picture call (views, mesh draws, billboard draws), on the context's device: `enqueue(rgba_dev, pixels_dev)` writes `count`
+// Every synchronous picture call (views, mesh draws, billboard draws, solid draws), on the context's device: `enqueue(rgba_dev, pixels_dev)` writes `count`
 // RGBA8 words and / or records into the context's pixel blocks (exact size; a null output's pointer is null), what was asked for is copied to
 // the host behind it, and the stream is synchronised for the layers of `mask`.  upload_records: the records go up first (the billboards blend
-// over them).
+// over them, the solids are tested against them).
 template <class Enqueue>
 ow_status picture_round_trip(ow_context *c, size_t count, void *rgba8_out, ow_render_pixel *pixels_out, bool upload_records, uint32_t mask, Enqueue enqueue) {
     if (rgba8_out)
@@ -1383,6 +1383,231 @@ ow_status ow_billboard_draw_stats(ow_context *c, uint64_t *draws, uint64_t *cull
     if (scratch_bytes) *scratch_bytes = c->billboard.bytes;
     return OW_OK;
 }
+
+}  // extern "C"
+
+/* ---- the solids (ow_solid.h, ow_solid.hip) ---- */
+
+namespace {
+constexpr size_t kSolidHead = 256;  // the four counters, at the head of the scratch block
+
+// the reference scene's sun and ambient (ow_render_options_default), near 0.05, a wooden brown
+void solid_defaults(ow_solid_options *o) {
+    ow_render_options ro;
+    render_defaults(&ro);
+    std::memset(o, 0, sizeof(*o));
+    const float color[3] = {0.45f, 0.30f, 0.15f};
+    for (int k = 0; k < 3; ++k) {
+        o->color[k] = color[k];
+        o->light_direction[k] = ro.light_direction[k];
+        o->light_color[k] = ro.light_color[k];
+        o->ambient_color[k] = ro.ambient_color[k];
+    }
+    o->near = ow::kMeshDefaultNear;
+}
+
+// ow_solid_options (NULL = the defaults) -> the draw's constants
+ow_status resolve_solid_options(const ow_solid_options *opts, ow::SolidParams *sp) {
+    static_assert(sizeof(ow_solid_options) == sizeof(ow::SolidOptions) && offsetof(ow_solid_options, flags) == offsetof(ow::SolidOptions, flags) &&
+                      offsetof(ow_solid_options, background_color) == offsetof(ow::SolidOptions, background_color) &&
+                      offsetof(ow_solid_options, lane_box) == offsetof(ow::SolidOptions, lane_box) &&
+                      offsetof(ow_solid_options, reserved) == offsetof(ow::SolidOptions, reserved) && OW_RAY_SOLID == ow::kRaySolid &&
+                      OW_SOLID_TWO_SIDED == ow::kSolidTwoSided && OW_SOLID_MAX_INSTANCES == ow::kSolidMaxInstances &&
+                      OW_SOLID_MAX_TRIANGLES == ow::kSolidMaxTriangles && sizeof(ow_buoyancy_body) % sizeof(float) == 0 &&
+                      offsetof(ow_buoyancy_body, transform) == 0,
+                  "record layout");
+    ow_solid_options def;
+    if (!opts) {
+        solid_defaults(&def);
+        opts = &def;
+    }
+    std::memset(sp, 0, sizeof(*sp));
+    const float *vec[5] = {opts->color, opts->light_direction, opts->light_color, opts->ambient_color, opts->background_color};
+    for (const float *v : vec)
+        for (int k = 0; k < 3; ++k)
+            if (!(std::fabs(v[k]) <= ow::kSolidColorMax)) return fail(OW_ERR_INVALID, "ow_solid_options: a colour or the light direction is not finite (or beyond 1e12)");
+    if (!std::isfinite(opts->near)) return fail(OW_ERR_INVALID, "near is not finite");
+    if (opts->lane_box < -1 || opts->lane_box > 64) return fail(OW_ERR_INVALID, "lane_box %d outside [-1,64]", opts->lane_box);
+    if (opts->flags & ~OW_SOLID_TWO_SIDED) return fail(OW_ERR_INVALID, "unknown solid flags 0x%x", opts->flags);
+    if (ow_status st = check_reserved(opts->reserved, "ow_solid_options"); st != OW_OK) return st;
+    const double lx = opts->light_direction[0], ly = opts->light_direction[1], lz = opts->light_direction[2];
+    const double len = std::sqrt(lx * lx + ly * ly + lz * lz);
+    if (!(len > 0.0)) return fail(OW_ERR_INVALID, "light_direction has zero length");
+    for (int k = 0; k < 3; ++k) {
+        sp->albedo[k] = opts->color[k];
+        sp->light[k] = (float)((double)opts->light_direction[k] / len);
+        sp->light_color[k] = opts->light_color[k];
+        sp->ambient_color[k] = opts->ambient_color[k];
+        sp->background[k] = opts->background_color[k];
+    }
+    sp->two_sided = (opts->flags & OW_SOLID_TWO_SIDED) ? 1 : 0;
+    sp->mp.near = opts->near > 0.0f ? opts->near : ow::kMeshDefaultNear;
+    sp->mp.cull_back = sp->two_sided ? 0 : 1;
+    sp->mp.lane_box = opts->lane_box == 0 ? ow::kMeshLaneBox : (opts->lane_box < 0 ? 0 : opts->lane_box);
+    sp->mp.camera_ok = 1;
+    return OW_OK;
+}
+
+// the argument checks every form of the draw shares: ow_billboard_draw's, in its order, then the context and the shape
+ow_status check_solid_draw(const ow_context *c, const ow_solid *solid, const ow_camera *camera, const ow_solid_options *opts, const void *pixels,
+                           const void *rgba, ow::CameraParams *cp, ow::SolidParams *sp) {
+    if (!rgba && !pixels) return fail(OW_ERR_INVALID, "null argument: both outputs");
+    if (ow_status st = resolve_camera(camera, cp); st != OW_OK) return st;
+    if (ow_status st = resolve_solid_options(opts, sp); st != OW_OK) return st;
+    if (ow_status st = check_handle(c, solid, "solid"); st != OW_OK) return st;
+    sp->mp.camera_ok = ow::mesh_camera_ok(*cp) ? 1 : 0;
+    return OW_OK;
+}
+// the number of instances of one draw against the shape
+ow_status check_solid_count(const ow_solid *solid, int64_t count) {
+    if (count < 0 || count > OW_SOLID_MAX_INSTANCES) return fail(OW_ERR_INVALID, "%lld instances outside [0,%d]", (long long)count, OW_SOLID_MAX_INSTANCES);
+    if (count * solid->num_triangles > ow::kSolidMaxProduct || count * solid->num_vertices > ow::kSolidMaxProduct)
+        return fail(OW_ERR_INVALID, "%lld instances of %d triangles and %d vertices: more than 2^24 per draw", (long long)count, solid->num_triangles,
+                    solid->num_vertices);
+    return OW_OK;
+}
+ow_status check_solid_bodies(const ow_context *c, const ow_solid *solid, const ow_bodies *set, int32_t first, int32_t count) {
+    if (ow_status st = check_bodies_handle(c, set); st != OW_OK) return st;
+    if (first < 0 || count < 0 || (int64_t)first + count > set->A.num_bodies)
+        return fail(OW_ERR_INVALID, "bodies [%d, %d + %d) outside [0, %d)", first, first, count, set->A.num_bodies);
+    return check_solid_count(solid, count);
+}
+
+// The scratch of a draw and its launches on the context's stream.  Sources: a body set's resident pose records and fault flags, or `upload`
+// (host transforms, copied into the scratch first).  A block that has to grow while launches already enqueued may still read it is replaced
+// behind one synchronisation (sync_before_growth).
+ow_status solid_enqueue(ow_context *c, const ow_solid *solid, const ow::CameraParams &cp, const ow::SolidParams &sp, const ow_bodies *set, int first,
+                        const float *upload, int count, ow::RenderPixel *pixels_dev, uint32_t *rgba_dev) {
+    Layout L;
+    L.take(kSolidHead);  // the counters, at 0
+    const size_t v_off = L.take((size_t)count * solid->num_vertices * sizeof(ow::MeshVertex));
+    const size_t w_off = L.take((size_t)cp.width * cp.height * sizeof(uint64_t));
+    const size_t t_off = L.take(upload ? (size_t)count * ow::kSolidTransformFloats * sizeof(float) : 0);
+    if (ow_status st = sync_before_growth(c, c->solid, L.total); st != OW_OK) return st;
+    if (ow_status st = c->solid.ensure(L.total, 0, 1, "bytes of solid scratch"); st != OW_OK) return st;
+    char *base = (char *)c->solid.ptr;
+    hipStream_t s = main_stream(c);
+    ow::SolidArrays A;
+    A.local = solid->local;
+    A.indices = solid->indices;
+    A.num_vertices = solid->num_vertices;
+    A.num_triangles = solid->num_triangles;
+    A.counters = (uint32_t *)base;
+    A.verts = (ow::MeshVertex *)(base + v_off);
+    A.vis = (uint64_t *)(base + w_off);
+    ow::SolidInstances in;
+    in.count = count;
+    if (set) {
+        in.transforms = (const float *)(set->A.records + first);
+        in.flags = set->A.flags + first;
+        in.stride = (int)(sizeof(ow::BuoyancyBody) / sizeof(float));
+    } else {
+        in.transforms = (const float *)(base + t_off);
+        in.flags = nullptr;
+        in.stride = ow::kSolidTransformFloats;
+        if (count > 0) OW_HIP(hipMemcpyAsync(base + t_off, upload, (size_t)count * ow::kSolidTransformFloats * sizeof(float), hipMemcpyHostToDevice, s));
+    }
+    OW_HIP(ow::launch_solid_draw(A, in, cp, sp, rgba_dev, pixels_dev, s));
+    ++c->solid_draws;
+    return OW_OK;
+}
+
+// the synchronous forms: picture_round_trip with the records uploaded first and no layer to refuse (the draw reads no map)
+ow_status solid_round_trip(ow_context *c, const ow_solid *solid, const ow::CameraParams &cp, const ow::SolidParams &sp, const ow_bodies *set, int first,
+                           const float *upload, int count, ow_render_pixel *pixels_inout, void *rgba8_out) {
+    OW_HIP(hipSetDevice(c->device));
+    return picture_round_trip(c, (size_t)cp.width * cp.height, rgba8_out, pixels_inout, true, 0, [&](uint32_t *rgba_dev, ow::RenderPixel *pixels_dev) {
+        return solid_enqueue(c, solid, cp, sp, set, first, upload, count, pixels_dev, rgba_dev);
+    });
+}
+}  // namespace
+
+extern "C" {
+
+void ow_solid_options_default(ow_solid_options *out) {
+    if (out) solid_defaults(out);
+}
+
+ow_status ow_solid_create(ow_context *c, const float *vertices_xyz, int32_t num_vertices, const int32_t *indices, int32_t num_triangles, ow_solid **out) {
+    if (!out) return fail(OW_ERR_INVALID, "null argument");
+    *out = nullptr;
+    if (num_vertices < 1 || num_triangles < 1 || num_triangles > OW_SOLID_MAX_TRIANGLES || (int64_t)num_vertices > ow::kSolidMaxProduct)
+        return fail(OW_ERR_INVALID, "num_vertices must be in [1,2^24] and num_triangles in [1,%d]", OW_SOLID_MAX_TRIANGLES);
+    if (!vertices_xyz || !indices) return fail(OW_ERR_INVALID, "null argument");
+    for (size_t i = 0; i < (size_t)num_triangles * 3; ++i)
+        if (indices[i] < 0 || indices[i] >= num_vertices)
+            return fail(OW_ERR_INVALID, "triangle %zu: index %d outside [0,%d)", i / 3, indices[i], num_vertices);
+    if (!c) return fail(OW_ERR_INVALID, "null context");
+    const size_t nv = (size_t)num_vertices, nt = (size_t)num_triangles;
+    Layout L;
+    const size_t l_off = L.take(nv * 3 * sizeof(float)), i_off = L.take(nt * 3 * sizeof(int32_t));
+    ow_solid *m;
+    if (ow_status st = new_handle(c, L.total, "solid", &m); st != OW_OK) return st;
+    char *base = (char *)m->block;
+    m->local = (const float *)(base + l_off);
+    m->indices = (const int32_t *)(base + i_off);
+    m->num_vertices = num_vertices;
+    m->num_triangles = num_triangles;
+    hipStream_t s = main_stream(c);
+    const bool enqueued = hipMemcpyAsync((void *)m->local, vertices_xyz, nv * 3 * sizeof(float), hipMemcpyHostToDevice, s) == hipSuccess &&
+                          hipMemcpyAsync((void *)m->indices, indices, nt * 3 * sizeof(int32_t), hipMemcpyHostToDevice, s) == hipSuccess;
+    return finish_create(c, m, s, enqueued, "solid upload", out);
+}
+
+void ow_solid_destroy(ow_context *, ow_solid *solid) {
+    if (solid) release_handle(solid);
+    delete solid;
+}
+
+ow_status ow_solid_draw(ow_context *c, ow_solid *solid, ow_bodies *bodies, int32_t first_body, int32_t body_count, const ow_camera *camera,
+                        const ow_solid_options *opts, ow_render_pixel *pixels_inout, void *rgba8_out) {
+    ow::CameraParams cp;
+    ow::SolidParams sp;
+    if (ow_status st = check_solid_draw(c, solid, camera, opts, pixels_inout, rgba8_out, &cp, &sp); st != OW_OK) return st;
+    if (ow_status st = check_solid_bodies(c, solid, bodies, first_body, body_count); st != OW_OK) return st;
+    return solid_round_trip(c, solid, cp, sp, bodies, first_body, nullptr, body_count, pixels_inout, rgba8_out);
+}
+
+ow_status ow_solid_draw_async(ow_context *c, ow_solid *solid, ow_bodies *bodies, int32_t first_body, int32_t body_count, const ow_camera *camera,
+                              const ow_solid_options *opts, ow_render_pixel *pixels_dev, void *rgba8_dev) {
+    ow::CameraParams cp;
+    ow::SolidParams sp;
+    if (ow_status st = check_solid_draw(c, solid, camera, opts, pixels_dev, rgba8_dev, &cp, &sp); st != OW_OK) return st;
+    if (ow_status st = check_solid_bodies(c, solid, bodies, first_body, body_count); st != OW_OK) return st;
+    if (ow_status st = check_pixel_alignment(rgba8_dev, pixels_dev); st != OW_OK) return st;
+    OW_HIP(hipSetDevice(c->device));
+    return solid_enqueue(c, solid, cp, sp, bodies, first_body, nullptr, body_count, (ow::RenderPixel *)pixels_dev, (uint32_t *)rgba8_dev);
+}
+
+ow_status ow_solid_draw_instances(ow_context *c, ow_solid *solid, const float *transforms, int32_t count, const ow_camera *camera,
+                                  const ow_solid_options *opts, ow_render_pixel *pixels_inout, void *rgba8_out) {
+    if (count < 0 || count > OW_SOLID_MAX_INSTANCES) return fail(OW_ERR_INVALID, "count %d outside [0,%d]", count, OW_SOLID_MAX_INSTANCES);
+    if (count > 0 && !transforms) return fail(OW_ERR_INVALID, "null argument");
+    ow::CameraParams cp;
+    ow::SolidParams sp;
+    if (ow_status st = check_solid_draw(c, solid, camera, opts, pixels_inout, rgba8_out, &cp, &sp); st != OW_OK) return st;
+    if (ow_status st = check_solid_count(solid, count); st != OW_OK) return st;
+    return solid_round_trip(c, solid, cp, sp, nullptr, 0, transforms, count, pixels_inout, rgba8_out);
+}
+
+ow_status ow_solid_draw_stats(ow_context *c, uint64_t *draws, uint64_t *skipped_instances, uint64_t *culled, uint64_t *drawn, uint64_t *scratch_bytes) {
+    if (!c) return fail(OW_ERR_INVALID, "null context");
+    if (skipped_instances || culled || drawn) {
+        uint32_t w[4] = {0, 0, 0, 0};
+        if (c->solid.ptr)  // no draw yet: zeros, and the device is not touched
+            if (ow_status st = read_back(c, w, c->solid.ptr, sizeof(w)); st != OW_OK) return st;
+        if (skipped_instances) *skipped_instances = w[ow::kSolidSkippedInstances];
+        if (culled) *culled = w[ow::kSolidCulled];
+        if (drawn) *drawn = (uint64_t)w[ow::kSolidLane] + w[ow::kSolidWave];
+    }
+    if (draws) *draws = c->solid_draws;
+    if (scratch_bytes) *scratch_bytes = c->solid.bytes;
+    return OW_OK;
+}
+
+}  // extern "C"
+
+extern "C" {
 
 ow_status ow_update_velocity(ow_context *c, uint32_t cascade_mask) {
     if (ow_status st = check_velocity_mask(c, cascade_mask); st != OW_OK) return st;

@@ -45,6 +45,13 @@ struct ow_billboard_material : ow::Handle {
     float foam[3] = {0.0f, 0.0f, 0.0f}, max_alpha = 0.0f;
 };
 
+// a solid shape (ow_solid_create): the block holds local positions and indices
+struct ow_solid : ow::Handle {
+    const float *local = nullptr;
+    const int32_t *indices = nullptr;
+    int num_vertices = 0, num_triangles = 0;
+};
+
 struct ow_context {
     int n = 0, cascades = 0, layers = 0, device = 0;
     float depth = 20.0f;
@@ -160,9 +167,11 @@ struct ow_context {
     // The consumers' grow-only scratch (ow_consumer_host.hip).  query: the synchronous point calls' points in and records out (of the largest kind);
     // buoy: bodies, hull points, per-point records, results; ray: rays in, records out; render_rgba / render_pixels: the RGBA8 words and per-pixel
     // records of the synchronous ow_render_view, ow_mesh_draw and ow_billboard_draw; mesh_vis: the draw's visibility words (both forms);
-    // billboard: a billboard draw's counters, bin masks, sprite records and (ow_billboard_draw_instances) the uploaded instances.
-    ow::DeviceScratch query_scratch, buoy_scratch, ray_scratch, render_rgba, render_pixels, mesh_vis, billboard;
+    // billboard: a billboard draw's counters, bin masks, sprite records and (ow_billboard_draw_instances) the uploaded instances;
+    // solid: a solid draw's counters, transformed vertex records, visibility words and (ow_solid_draw_instances) the uploaded transforms.
+    ow::DeviceScratch query_scratch, buoy_scratch, ray_scratch, render_rgba, render_pixels, mesh_vis, billboard, solid;
     uint64_t billboard_draws = 0;  // ow_billboard_draw_stats
+    uint64_t solid_draws = 0;      // ow_solid_draw_stats
     uint32_t *ray_bound = nullptr;  // the per-cascade bound words of the slab (ray casts and views), allocated once
     // the velocity layers (ow_update_velocity; ow_velocity_kernels.h): V in the displacement array's layout, the pipeline's own intermediate
     // (vel_slots cascades of one launch pair) and twiddle table, all allocated by the first velocity call

@@ -31,8 +31,8 @@ ow_status resolve_raycast_options(const ow_raycast_options *opts, RaycastParams 
 // the host-side checks of ow_buoyancy / ow_group_buoyancy on host arrays: ranges, body indices, volumes, half heights
 ow_status check_buoyancy_arrays(const ow_buoyancy_body *bodies, int num_bodies, const ow_hull_point *hull, int num_points);
 
-// A grow-only device allocation on the current device.  Nothing that reads the old block may be in flight when it grows: every user but two
-// synchronises before it returns (the exceptions, the mesh draw's visibility words and the billboard draw's block, synchronise before
+// A grow-only device allocation on the current device.  Nothing that reads the old block may be in flight when it grows: every user but three
+// synchronises before it returns (the exceptions, the mesh draw's visibility words and the billboard and solid draws' blocks, synchronise before
 // they grow: ow_consumer_host.hip sync_before_growth).
 struct DeviceScratch {
     void *ptr = nullptr;

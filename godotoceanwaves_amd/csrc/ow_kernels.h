@@ -9,6 +9,7 @@
 #include "ow_mesh.h"
 #include "ow_render.h"
 #include "ow_rigid.h"
+#include "ow_solid.h"
 #include "ow_spray.h"
 #include "ow_spray_draw.h"
 #include "ow_surface.h"
@@ -127,6 +128,20 @@ struct BillboardArrays {
 // the RGBA8 words (either may be null), all on `s`
 hipError_t launch_billboard_draw(const BillboardArrays &A, const CameraParams &cam, const SprayDrawParams &dp, const BillboardBins &bins, uint32_t *rgba_dev,
                                  RenderPixel *pixels_dev, hipStream_t s);
+
+// a solid draw (ow_solid.hip; the vertex stage, the winner, the depth test and the shading in ow_solid.h, the coverage rule in ow_mesh.h)
+struct SolidArrays {
+    const float *local;      // [num_vertices][3] the shape, as uploaded
+    const int32_t *indices;  // [num_triangles][3]
+    int num_vertices, num_triangles;
+    uint32_t *counters;      // [4] scratch: kSolidSkippedInstances .. kSolidWave of the last draw
+    MeshVertex *verts;       // [instances][num_vertices] scratch
+    uint64_t *vis;           // [cam.width x cam.height] scratch: the visibility words
+};
+// k_solid_clear, k_solid_vertices over in.count instances, k_solid_raster, k_solid_resolve into the records (read, rewritten where a solid is
+// drawn) and / or the RGBA8 words (either may be null), all on `s`
+hipError_t launch_solid_draw(const SolidArrays &A, const SolidInstances &in, const CameraParams &cam, const SolidParams &sp, uint32_t *rgba_dev,
+                             RenderPixel *pixels_dev, hipStream_t s);
 
 bool supported_map_size(int n);
 int kernel_family(int n, int slots, int mode);  // 1 standard, 2 layer-parallel, 3 compact: what launch_pass1/2 will use

@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 
 #include "ow_kernels.h"
+#include "ow_raster.h"
 
 namespace ow {
 namespace {
@@ -38,15 +39,6 @@ __global__ void __launch_bounds__(256) k_mesh_clear(uint64_t *vis, size_t pixels
     if (i < 4) counters[i] = 0u;
 }
 
-__device__ __forceinline__ void vis_min(uint64_t *vis, size_t at, uint64_t word) {
-    // the word only ever decreases: a stale read is at worst larger than what is there, and then the atomic is merely not spared
-    if (word < vis[at]) atomicMin((unsigned long long *)(vis + at), (unsigned long long)word);
-}
-
-// the value lane `src` holds, src wave-uniform: one v_readlane_b32, no LDS crossbar
-__device__ __forceinline__ int lane_read(int v, int src) { return __builtin_amdgcn_readlane(v, src); }
-__device__ __forceinline__ float lane_read(float v, int src) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src)); }
-
 // One 64-lane wave per 64 triangles, one wave per block.  A clipmap seen from eye height has triangles hundreds of pixels wide beside the
 // camera and sub-pixel ones towards the horizon in the same draw: each lane sets its own triangle up (tri_setup: class, planes, pixel
 // box); a lane whose box is at most lane_box centres a side walks it alone; the triangles with larger boxes are found by a ballot and
@@ -67,32 +59,7 @@ __global__ void __launch_bounds__(64) k_mesh_raster(const int32_t *indices, int 
         const uint64_t m = __ballot(s.kind == k);
         if (lane == 0 && m) atomicAdd(counters + k, (uint32_t)__popcll(m));
     }
-    if (s.kind == kTriLane) {
-        for (int j = s.y0; j <= s.y1; ++j)
-            for (int i = s.x0; i <= s.x1; ++i) {
-                const TriCover c = tri_cover(s.p, cam, mp.near, i, j);
-                if (c.hit) vis_min(vis, (size_t)j * cam.width + i, mesh_word(c.depth, tri));
-            }
-    }
-    uint64_t big = __ballot(s.kind == kTriWave);
-    while (big) {
-        const int src = __builtin_ctzll(big);
-        big &= big - 1;
-        TriPlanes p;
-        for (int a = 0; a < 3; ++a)
-            for (int b = 0; b < 3; ++b) p.n[a][b] = lane_read(s.p.n[a][b], src);
-        for (int b = 0; b < 3; ++b) p.N[b] = lane_read(s.p.N[b], src);
-        p.det = lane_read(s.p.det, src);
-        const int x0 = lane_read(s.x0, src), x1 = lane_read(s.x1, src), y0 = lane_read(s.y0, src), y1 = lane_read(s.y1, src);
-        const int t = (int)blockIdx.x * 64 + src;
-        for (int ty = y0 >> 3; ty <= y1 >> 3; ++ty)
-            for (int tx = x0 >> 3; tx <= x1 >> 3; ++tx) {
-                const int i = 8 * tx + (lane & 7), j = 8 * ty + (lane >> 3);
-                if (i < x0 || i > x1 || j < y0 || j > y1) continue;
-                const TriCover c = tri_cover(p, cam, mp.near, i, j);
-                if (c.hit) vis_min(vis, (size_t)j * cam.width + i, mesh_word(c.depth, t));
-            }
-    }
+    raster_wave(s, lane, tri, (int)blockIdx.x * 64, cam, mp, vis);
 }
 
 // One lane per pixel, one 8 x 8 tile per wave, as k_render_view: lane l is pixel (8 tx + (l & 7), 8 ty + (l >> 3)).  The barycentrics come

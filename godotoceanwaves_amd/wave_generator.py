@@ -137,6 +137,13 @@ class _SprayMaterial:
         self.handle = handle
 
 
+class _Solid:
+    """a solid shape (WaveGenerator.solid_create)"""
+
+    def __init__(self, handle, num_vertices, num_triangles):
+        self.handle, self.num_vertices, self.num_triangles = handle, num_vertices, num_triangles
+
+
 class WaveGenerator:
     """assets/water/wave_generator.gd.  Typical use, as in water.gd:89-91,112-114:
 
@@ -993,6 +1000,81 @@ class WaveGenerator:
         _lib.check(self._lib.ow_billboard_draw_stats(self.context, C.byref(v[0]), C.byref(v[1]) if counters else None, C.byref(v[2]) if counters else None,
                                                      C.byref(v[3])))
         keys = ("draws", "culled", "drawn", "scratch_bytes")
+        return {k: x.value for k, x in zip(keys, v) if counters or k in ("draws", "scratch_bytes")}
+
+    # ---- solids drawn into a camera view, on the device (include/ocean_waves.h ow_solid_*) ----
+    _SOLID_OWN = ("near", "color", "light_direction", "light_color", "ambient_color", "background_color", "two_sided", "lane_box")
+
+    @classmethod
+    def solid_options(cls, options=None):
+        """None, an _lib.ow_solid_options, or a dict over ow_solid_options_default's values (the reference scene's sun and ambient, a brown
+        albedo) that may set near, color, light_direction, light_color, ambient_color, background_color, two_sided and lane_box"""
+        if options is None or isinstance(options, _lib.ow_solid_options):
+            return options
+        unknown = [k for k in options if k not in cls._SOLID_OWN]
+        if unknown:
+            raise ValueError(f"unknown solid options {unknown}")
+        o = _lib.ow_solid_options()
+        _lib.load().ow_solid_options_default(C.byref(o))
+        for k in ("color", "light_direction", "light_color", "ambient_color", "background_color"):
+            if k in options:
+                getattr(o, k)[:] = [float(v) for v in options[k]]
+        if "near" in options:
+            o.near = float(options["near"])
+        if options.get("two_sided"):
+            o.flags |= _lib.OW_SOLID_TWO_SIDED
+        if "lane_box" in options:
+            o.lane_box = int(options["lane_box"])
+        return o
+
+    def solid_create(self, vertices, triangles):
+        """A device-resident shape from [V][3] local positions and [T][3] vertex indices (counter-clockwise seen from outside); returns a
+        _Solid (solid_destroy() it before free())"""
+        v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
+        t = np.ascontiguousarray(triangles, np.int32).reshape(-1, 3)
+        out = C.c_void_p()
+        _lib.check(self._lib.ow_solid_create(self.context, v.ctypes.data, len(v), t.ctypes.data, len(t), C.byref(out)))
+        return _Solid(out, len(v), len(t))
+
+    def solid_destroy(self, solid):
+        self._destroy(solid, self._lib.ow_solid_destroy)
+
+    def solid_draw(self, solid, bodies_set, camera, options=None, pixels=None, rgba=True, first=0, count=None):
+        """The shape at the resident poses of bodies [first, first + count) of a body set, drawn over `pixels` ((H, W) RENDER_PIXEL records of
+        mesh_draw or render_view; None: the options' background colour, no depth): ((H, W, 4) uint8 RGBA, the records rewritten or None).  A
+        record a solid wins carries OW_RAY_SOLID, reserved[0] the triangle's index + 1 and reserved[3] the instance's index + 1.
+        Synchronises."""
+        count = bodies_set.num_bodies - first if count is None else count
+        o = self.solid_options(options)
+        img, rec = self._picture(camera, pixels, rgba)
+        _lib.check(self._lib.ow_solid_draw(self.context, solid.handle, bodies_set.handle, int(first), int(count), C.byref(camera), _ref(o),
+                                           rec.ctypes.data if rec is not None else None, img.ctypes.data if img is not None else None))
+        return img, rec
+
+    def solid_draw_instances(self, solid, transforms, camera, options=None, pixels=None, rgba=True):
+        """solid_draw over a host array of [count][12] transforms (basis rows, then the origin)"""
+        t = np.ascontiguousarray(transforms, np.float32).reshape(-1, 12)
+        o = self.solid_options(options)
+        img, rec = self._picture(camera, pixels, rgba)
+        _lib.check(self._lib.ow_solid_draw_instances(self.context, solid.handle, t.ctypes.data if len(t) else None, len(t), C.byref(camera), _ref(o),
+                                                     rec.ctypes.data if rec is not None else None, img.ctypes.data if img is not None else None))
+        return img, rec
+
+    def solid_draw_async(self, solid, bodies_set, camera, rgba_device, pixels_device=None, options=None, first=0, count=None):
+        """The draw over DEVICE buffers (mesh_draw_async's), enqueued in the generator's stream order without synchronising; the records are
+        read and rewritten in place"""
+        self._check_picture_buffers(camera, rgba_device, pixels_device)
+        count = bodies_set.num_bodies - first if count is None else count
+        o = self.solid_options(options)
+        _lib.check(self._lib.ow_solid_draw_async(self.context, solid.handle, bodies_set.handle, int(first), int(count), C.byref(camera), _ref(o),
+                                                 _addr(pixels_device, True), _addr(rgba_device, True)))
+
+    def solid_draw_stats(self, counters=True):
+        """dict of draws, the scratch bytes held and, with counters (synchronising), the instances the last draw skipped and the triangles
+        it culled and drew"""
+        v = [C.c_uint64() for _ in range(5)]
+        _lib.check(self._lib.ow_solid_draw_stats(self.context, C.byref(v[0]), *(C.byref(x) if counters else None for x in v[1:4]), C.byref(v[4])))
+        keys = ("draws", "skipped_instances", "culled", "drawn", "scratch_bytes")
         return {k: x.value for k, x in zip(keys, v) if counters or k in ("draws", "scratch_bytes")}
 
     def get_push_constants(self, cascade):

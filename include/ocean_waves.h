@@ -1061,6 +1061,96 @@ ow_status ow_billboard_draw_instances(ow_context *ctx, ow_billboard_material *ma
  * pixel centre) and drawn; the scratch bytes the context holds for these draws.  Synchronises when culled or drawn is asked for. */
 ow_status ow_billboard_draw_stats(ow_context *ctx, uint64_t *draws, uint64_t *culled, uint64_t *drawn, uint64_t *scratch_bytes);
 
+/* Solids drawn into a camera view: opaque triangle meshes at instance transforms -- the resident poses of an ow_bodies set, or a caller's
+ * array -- over a picture that ow_mesh_draw or ow_render_view produced, depth-tested against it and writing depth into it, in the
+ * context's stream order.  Draw order for a frame: water, then solids, then billboards -- the billboards' depth test reads the t a solid
+ * wrote, so spray behind a crate is hidden.  The definition, independent of how it is computed:
+ *   shape      num_vertices local positions and num_triangles index triples, uploaded once.  The outward side of a triangle is the one it
+ *              winds counter-clockwise seen from, as for ow_mesh_*
+ *   instance   twelve floats in ow_buoyancy_body.transform's layout (basis rows [0..8], origin [9..11]).  World vertex
+ *              w_k = ((B_k0 l_0 + B_k1 l_1) + B_k2 l_2) + o_k in FP32, in that order; view position V = Bcam^T (w - camera.position) with
+ *              ow_mesh_vertex.view_position's operations in their order
+ *   coverage   ow_mesh_*'s, to the bit, on V: the pixel's ray is (x, y, -1), homogeneous edge functions from FP64 cross products rounded
+ *              once, inclusive edges, near < s <= camera.max_distance, nothing clipped or projected
+ *   facing     det < 0 is the outward side.  Back faces are dropped before coverage; OW_SOLID_TWO_SIDED draws them with the normal negated
+ *   winner     of all (instance, triangle) pairs that cover a pixel the smallest 64-bit word (depth bits << 32) |
+ *              (instance * num_triangles + triangle) wins: the picture does not depend on order and is the same bytes on every run
+ *   depth      the winner's distance along the pixel's normalised ray is d = s sqrtf((x x + y y) + 1) in FP32 (ow_billboard_draw's
+ *              expression).  It is drawn when the background record has no OW_RAY_HIT or d <= record.t.  The water is opaque in this
+ *              composite: the submerged part of a hull is hidden, and the waterline falls out of the test
+ *   shading    this library's choice, like the composite: n = the unit normal of the world triangle (edges w1 - w0 and w2 - w0 in FP32;
+ *              the cross product, the length and the division in FP64, narrowed once), l^ = light_direction normalised as
+ *              ow_render_view normalises it, diffuse = light_color max(n . l^, 0), color = albedo (diffuse + ambient_color) in linear
+ *              FP32.  No specular, no textures
+ *   record     of a pixel a solid wins: t = d, status = OW_RAY_HIT | OW_RAY_SOLID, position = the perspective-correct interpolated world
+ *              position, normal = n, albedo, diffuse and color as above, reserved[0] = triangle index + 1, reserved[3] = instance
+ *              index + 1, reserved[1] = reserved[2] = 0, every other field 0.  A pixel no solid wins keeps its whole record.  RGBA8 is
+ *              written for every pixel from the record's color, as ow_render_view packs it
+ *   no records pixels is NULL: every pixel is background_color with no depth, and rgba8 is required
+ *   finite     an instance with a value that is not finite is skipped and counted; a triangle with a vertex or a plane that is not finite
+ *              is culled; a camera that is not finite (ow_mesh_draw's rule) leaves the picture as it was, the counters 0.  Nothing
+ *              written is NaN or Inf for a finite background
+ *   body sets  instance i is body first_body + i of the set: its transform is the pose record the last ow_bodies_step, ow_bodies_create
+ *              or ow_bodies_set_state left on the device.  A body whose fault flag is raised is skipped and counted.  The host never
+ *              reads the poses
+ * The exact operations, identical in every build, are godotoceanwaves_amd/csrc/ow_solid.h's (the coverage rule: ow_mesh.h's).  There is
+ * no group form (ow_group_*) of these calls, as for every draw. */
+#define OW_RAY_SOLID 16                   /* ow_render_pixel.status: the pixel shows a solid (set with OW_RAY_HIT) */
+#define OW_SOLID_TWO_SIDED 1u             /* ow_solid_options.flags */
+#define OW_SOLID_MAX_INSTANCES 65536
+#define OW_SOLID_MAX_TRIANGLES 65536      /* per shape; instances * triangles and instances * vertices <= 2^24 per draw */
+typedef struct ow_solid ow_solid;         /* opaque; belongs to the context it was created on */
+typedef struct ow_solid_options {
+    float near;                 /* the near plane's view depth, metres; <= 0 selects 0.05 (Camera3D.near) */
+    float color[3];             /* the albedo, linear */
+    float light_direction[3];   /* towards the light, world space, any length > 0 */
+    uint32_t flags;             /* OW_SOLID_TWO_SIDED */
+    float light_color[3];       /* linear */
+    float ambient_color[3];     /* linear */
+    float background_color[3];  /* linear; the colour of every pixel no solid wins when pixels is NULL */
+    int32_t lane_box;           /* measurement, as ow_mesh_options.lane_box: 0 = the default (4), -1 = every triangle goes to the wave,
+                                   up to 64.  The picture does not depend on it */
+    uint32_t reserved[14];      /* 0 */
+} ow_solid_options;             /* 128 bytes; a NULL pointer = ow_solid_options_default's values.  Colours and the light direction: |v| <= 1e12 */
+typedef char ow_layout_check_solid_options[(sizeof(ow_solid_options) == 128 && offsetof(ow_solid_options, flags) == 28 &&
+                                            offsetof(ow_solid_options, background_color) == 56 && offsetof(ow_solid_options, lane_box) == 68 &&
+                                            offsetof(ow_solid_options, reserved) == 72) ? 1 : -1];
+
+/* ow_render_options_default's sun and ambient, near 0.05, colour (0.45, 0.30, 0.15), a black background, one-sided. */
+void ow_solid_options_default(ow_solid_options *out);
+/* Uploads a shape once: num_vertices >= 1 positions (x, y, z), num_triangles in [1, OW_SOLID_MAX_TRIANGLES] index triples, every index in
+ * [0, num_vertices).  Anything else, or a null pointer, is OW_ERR_INVALID and nothing is written, *out included.  Synchronises.  Destroy
+ * the shape before its context (one that outlives it can still be destroyed; every other call on it is OW_ERR_STATE). */
+ow_status ow_solid_create(ow_context *ctx, const float *vertices_xyz, int32_t num_vertices, const int32_t *indices, int32_t num_triangles,
+                          ow_solid **out);
+void ow_solid_destroy(ow_context *ctx, ow_solid *solid);
+/* Draws the shape at bodies [first_body, first_body + body_count) of the set over a picture in host memory, after everything enqueued so
+ * far.  pixels_inout: width * height ow_render_pixel records as ow_mesh_draw or ow_render_view wrote them, read and rewritten; it may be
+ * NULL (see above), and rgba8_out is then required.  rgba8_out: width * height * 4 bytes, may be NULL with records.  Synchronises.  The
+ * argument checks follow ow_billboard_draw's order: outputs, camera, options (a value that is not finite or beyond 1e12, a light direction
+ * of zero length, lane_box outside [-1, 64], unknown flags, reserved words not 0), then the context, the shape and the body set (one of
+ * another context is refused), the range (outside the set, more than OW_SOLID_MAX_INSTANCES, or beyond the 2^24 products);
+ * OW_ERR_INVALID writes nothing.  The first three groups are checked without a device. */
+ow_status ow_solid_draw(ow_context *ctx, ow_solid *solid, ow_bodies *bodies, int32_t first_body, int32_t body_count, const ow_camera *camera,
+                        const ow_solid_options *opts, ow_render_pixel *pixels_inout, void *rgba8_out);
+/* The same with DEVICE pointers on the context's device (rgba8_dev 4-byte aligned, pixels_dev 16-byte aligned; camera and opts are host
+ * values), ordered exactly as ow_mesh_draw_async: behind everything enqueued so far -- both chains, a caller's stream included -- and ahead
+ * of whatever the context enqueues next.  It reads the set's pose records and fault flags on the device.  No synchronisation, no copy and
+ * no host traffic; the only allocation is the context's grow-only scratch (the transformed vertex records, the visibility words and the
+ * counters -- its own, not the words ow_mesh_get_device_ptrs hands out), on first use or growth. */
+ow_status ow_solid_draw_async(ow_context *ctx, ow_solid *solid, ow_bodies *bodies, int32_t first_body, int32_t body_count, const ow_camera *camera,
+                              const ow_solid_options *opts, ow_render_pixel *pixels_dev, void *rgba8_dev);
+/* The same kernels over a caller's host array of count transforms (count x 12 floats, 0 .. OW_SOLID_MAX_INSTANCES): for hosts with their
+ * own rigid bodies.  Host pointers as ow_solid_draw.  Synchronises. */
+ow_status ow_solid_draw_instances(ow_context *ctx, ow_solid *solid, const float *transforms, int32_t count, const ow_camera *camera,
+                                  const ow_solid_options *opts, ow_render_pixel *pixels_inout, void *rgba8_out);
+/* Counters (each output may be NULL): draws enqueued on this context; of its last draw the instances skipped, and of the other instances
+ * the triangles culled (back-facing, edge-on, not finite, outside the view or covering no pixel centre) and drawn --
+ * skipped_instances * num_triangles + culled + drawn = instances * num_triangles --; the scratch bytes the context holds for these draws.
+ * Synchronises when one of the three middle counters is asked for. */
+ow_status ow_solid_draw_stats(ow_context *ctx, uint64_t *draws, uint64_t *skipped_instances, uint64_t *culled, uint64_t *drawn,
+                              uint64_t *scratch_bytes);
+
 /* ---- several devices: cascades sharded inside one process ---------------------------------------- */
 
 /* Cascades share nothing (wave_generator.gd:65-85 touches no state of another cascade; README.md:77-80), so a node's GPUs

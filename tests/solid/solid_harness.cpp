@@ -1,0 +1,214 @@
+// solid_harness.cpp -- godotoceanwaves_amd/csrc/ow_solid.h compiled as plain C++ (g++ -ffp-contract=off): the CPU build of the solid draw
+// that tests/test_solid_draw.py holds to an FP64 twin written from the definition (tests/solid_twin.py) and that the GPU kernels are held
+// to bit for bit.  The draw here takes the kernels' route -- the clear, a vertex record per (instance, vertex), the set-up and the box walk
+// of every (instance, triangle) pair with a min over 64-bit words, then the resolve of every pixel.  With -DSOLID_HARNESS_MAIN it is a
+// stand-alone program that reads a case file (the header below, then the arrays), draws it and writes the picture: the form the
+// sanitizers run.
+#include <math.h>
+#include <stddef.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <string.h>
+
+#include <vector>
+
+#include "ow_solid.h"
+
+using namespace ow;
+
+extern "C" {
+
+// one draw, every field four bytes: what the runtime resolves from its arguments (near <= 0 and lane_box 0 select the defaults here too)
+struct SolidCase {
+    int32_t width, height;
+    float cam[15];  // position, basis rows, tan(fov / 2), aspect, max_distance
+    int32_t num_vertices, num_triangles;
+    int32_t count;      // instances
+    int32_t stride;     // floats between two transforms (12: a plain array; 24: ow_buoyancy_body records)
+    int32_t has_flags;  // a fault flag per instance follows the transforms
+    float near;
+    float color[3], light_direction[3], light_color[3], ambient_color[3], background_color[3];
+    int32_t two_sided, lane_box;
+    int32_t has_pixels;
+};
+
+// sizeof and the offsets the Python side mirrors
+void harness_solid_sizes(int *out) {
+    out[0] = (int)sizeof(SolidOptions);
+    out[1] = (int)offsetof(SolidOptions, color);
+    out[2] = (int)offsetof(SolidOptions, light_direction);
+    out[3] = (int)offsetof(SolidOptions, flags);
+    out[4] = (int)offsetof(SolidOptions, light_color);
+    out[5] = (int)offsetof(SolidOptions, ambient_color);
+    out[6] = (int)offsetof(SolidOptions, background_color);
+    out[7] = (int)offsetof(SolidOptions, lane_box);
+    out[8] = (int)offsetof(SolidOptions, reserved);
+    out[9] = (int)sizeof(SolidCase);
+    out[10] = (int)sizeof(MeshVertex);
+    out[11] = (int)sizeof(BuoyancyBody);
+}
+
+}  // extern "C"
+
+namespace {
+CameraParams camera_of(const SolidCase &h) {
+    CameraParams cam;
+    memcpy(cam.o, h.cam, 3 * sizeof(float));
+    memcpy(cam.B, h.cam + 3, 9 * sizeof(float));
+    cam.tan_half_fov = h.cam[12];
+    cam.aspect = h.cam[13];
+    cam.max_distance = h.cam[14];
+    cam.width = h.width;
+    cam.height = h.height;
+    return cam;
+}
+// as the runtime resolves ow_solid_options (ow_consumer_host.hip resolve_solid_options)
+SolidParams params_of(const SolidCase &h, const CameraParams &cam) {
+    SolidParams sp;
+    memset(&sp, 0, sizeof(sp));
+    const double lx = h.light_direction[0], ly = h.light_direction[1], lz = h.light_direction[2];
+    const double len = sqrt(lx * lx + ly * ly + lz * lz);
+    for (int k = 0; k < 3; ++k) {
+        sp.albedo[k] = h.color[k];
+        sp.light[k] = len > 0.0 ? (float)((double)h.light_direction[k] / len) : 0.0f;
+        sp.light_color[k] = h.light_color[k];
+        sp.ambient_color[k] = h.ambient_color[k];
+        sp.background[k] = h.background_color[k];
+    }
+    sp.two_sided = h.two_sided ? 1 : 0;
+    sp.mp.near = h.near > 0.0f ? h.near : kMeshDefaultNear;
+    sp.mp.cull_back = sp.two_sided ? 0 : 1;
+    sp.mp.lane_box = h.lane_box == 0 ? kMeshLaneBox : (h.lane_box < 0 ? 0 : h.lane_box);
+    sp.mp.camera_ok = mesh_camera_ok(cam) ? 1 : 0;
+    return sp;
+}
+}  // namespace
+
+extern "C" {
+
+// The draw.  pixels_inout: width x height records or null (background_color, no depth); rgba_out: width x height words or null; counters:
+// skipped instances, culled, per-lane and per-wave triangles; vis_out: width x height words or null.
+void harness_solid_draw(const SolidCase *hp, const float *local, const int32_t *indices, const float *transforms, const int32_t *flags,
+                        void *pixels_inout, void *rgba_out, uint32_t *counters, uint64_t *vis_out) {
+    const SolidCase &h = *hp;
+    const CameraParams cam = camera_of(h);
+    const SolidParams sp = params_of(h, cam);
+    const int nv = h.num_vertices, nt = h.num_triangles;
+    const size_t pixels_n = (size_t)h.width * h.height;
+    RenderPixel *pixels = h.has_pixels ? (RenderPixel *)pixels_inout : nullptr;
+    uint32_t *rgba = (uint32_t *)rgba_out;
+    // k_solid_clear
+    std::vector<uint64_t> vis(pixels_n, kMeshNoTriangle);
+    uint32_t cnt[4] = {0, 0, 0, 0};
+    std::vector<MeshVertex> verts((size_t)h.count * nv);
+    if (sp.mp.camera_ok && h.count > 0) {
+        // k_solid_vertices
+        for (int inst = 0; inst < h.count; ++inst) {
+            const float *t = transforms + (size_t)inst * h.stride;
+            const bool ok = solid_instance_ok(t, h.has_flags ? flags + inst : nullptr);
+            if (!ok) ++cnt[kSolidSkippedInstances];
+            for (int v = 0; v < nv; ++v) verts[(size_t)inst * nv + v] = solid_vertex(t, ok, local + 3 * (size_t)v, cam, sp.mp);
+        }
+        // k_solid_raster: a lane's walk and the wave's sweep visit the same centres of the same box
+        const int pairs = h.count * nt;
+        for (int pair = 0; pair < pairs; ++pair) {
+            int counter = -1;
+            const TriSetup s = solid_setup(solid_triangle(indices, nv, nt, verts.data(), pair), cam, sp.mp, counter);
+            if (counter >= 0) ++cnt[counter];
+            if (s.kind != kTriLane && s.kind != kTriWave) continue;
+            for (int j = s.y0; j <= s.y1; ++j)
+                for (int i = s.x0; i <= s.x1; ++i) {
+                    const TriCover c = tri_cover(s.p, cam, sp.mp.near, i, j);
+                    if (!c.hit) continue;
+                    const uint64_t word = mesh_word(c.depth, pair);
+                    uint64_t &at = vis[(size_t)j * h.width + i];
+                    if (word < at) at = word;
+                }
+        }
+    }
+    // k_solid_resolve
+    for (int j = 0; j < h.height; ++j)
+        for (int i = 0; i < h.width; ++i) {
+            const size_t at = (size_t)j * h.width + i;
+            float t = 0.0f, color[3] = {sp.background[0], sp.background[1], sp.background[2]};
+            int32_t status = 0;
+            if (pixels) {
+                t = pixels[at].t;
+                status = pixels[at].status;
+                for (int k = 0; k < 3; ++k) color[k] = pixels[at].color[k];
+            }
+            bool drawn;
+            const RenderPixel px = solid_pixel(sp, cam, vis[at], indices, nv, nt, verts.data(), i, j, t, status, drawn);
+            if (drawn) {
+                for (int k = 0; k < 3; ++k) color[k] = px.color[k];
+                if (pixels) pixels[at] = px;
+            }
+            if (rgba) rgba[at] = pack_rgba8(color);
+        }
+    if (counters) memcpy(counters, cnt, sizeof(cnt));
+    if (vis_out) memcpy(vis_out, vis.data(), pixels_n * sizeof(uint64_t));
+}
+
+}  // extern "C"
+
+#ifdef SOLID_HARNESS_MAIN
+namespace {
+bool read_all(FILE *f, void *dst, size_t bytes) { return bytes == 0 || (dst && fread(dst, 1, bytes, f) == bytes); }
+}  // namespace
+
+// solid_harness_main CASE OUT: reads the header and the arrays (local positions, indices, transforms, flags, records), draws, and writes the
+// records (if any), the RGBA8 words and the four counters
+int main(int argc, char **argv) {
+    if (argc != 3) {
+        fprintf(stderr, "usage: %s CASE OUT\n", argv[0]);
+        return 2;
+    }
+    FILE *f = fopen(argv[1], "rb");
+    if (!f) return 2;
+    SolidCase h;
+    if (!read_all(f, &h, sizeof(h)) || h.width < 1 || h.height < 1 || h.width > 8192 || h.height > 8192 || h.count < 0 || h.count > kSolidMaxInstances ||
+        h.num_vertices < 1 || h.num_triangles < 1 || h.num_triangles > kSolidMaxTriangles || h.stride < kSolidTransformFloats || h.stride > 64 ||
+        (int64_t)h.count * h.num_vertices > kSolidMaxProduct || (int64_t)h.count * h.num_triangles > kSolidMaxProduct ||
+        (int64_t)h.num_vertices > kSolidMaxProduct) {
+        fprintf(stderr, "bad case header\n");
+        return 2;
+    }
+    const size_t count = (size_t)h.width * h.height;
+    std::vector<float> local((size_t)h.num_vertices * 3), transforms((size_t)h.count * h.stride);
+    std::vector<int32_t> indices((size_t)h.num_triangles * 3), flags(h.has_flags ? (size_t)h.count : 0);
+    std::vector<uint32_t> rgba(count);
+    std::vector<RenderPixel> pixels(h.has_pixels ? count : 0);
+    if (!read_all(f, local.data(), local.size() * 4) || !read_all(f, indices.data(), indices.size() * 4) ||
+        !read_all(f, transforms.data(), transforms.size() * 4) || !read_all(f, flags.data(), flags.size() * 4) ||
+        !read_all(f, pixels.data(), pixels.size() * sizeof(RenderPixel))) {
+        fprintf(stderr, "short case file\n");
+        return 2;
+    }
+    fclose(f);
+    for (int32_t i : indices)
+        if (i < 0 || i >= h.num_vertices) {
+            fprintf(stderr, "index out of range\n");
+            return 2;
+        }
+    uint32_t counters[4] = {0, 0, 0, 0};
+    harness_solid_draw(&h, local.data(), indices.data(), transforms.data(), flags.data(), pixels.data(), rgba.data(), counters, nullptr);
+    int bad = 0, solid = 0;
+    for (const RenderPixel &p : pixels) {
+        if (!(p.status & kRaySolid)) continue;
+        ++solid;
+        const float *groups[] = {&p.t, p.position, p.normal, p.albedo, p.diffuse, p.color};
+        const int sizes[] = {1, 3, 3, 3, 3, 3};
+        for (int g = 0; g < 6; ++g)
+            for (int k = 0; k < sizes[g]; ++k) bad += !(fabsf(groups[g][k]) <= 3.4028235e38f);
+    }
+    FILE *o = fopen(argv[2], "wb");
+    if (!o) return 2;
+    if (!pixels.empty()) fwrite(pixels.data(), sizeof(RenderPixel), pixels.size(), o);
+    fwrite(rgba.data(), 4, rgba.size(), o);
+    fwrite(counters, 4, 4, o);
+    fclose(o);
+    printf("skipped=%u culled=%u lane=%u wave=%u solid_pixels=%d not_finite=%d\n", counters[0], counters[1], counters[2], counters[3], solid, bad);
+    printf("ok\n");
+    return bad ? 1 : 0;
+}
+#endif

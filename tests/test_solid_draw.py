@@ -1,0 +1,1083 @@
+"""Solids drawn into a camera view (include/ocean_waves.h ow_solid_*): opaque triangle meshes at the resident poses of a body set, or at a
+caller's transforms, over a picture of ow_mesh_draw, depth-tested against it and writing depth into it
+(godotoceanwaves_amd/csrc/ow_solid.h; the coverage rule is ow_mesh.h's).
+
+CPU: the ABI, the documents and the argument checks without a device; ow_solid.h compiled as plain C++ (tests/solid/solid_harness.cpp, g++
+-ffp-contract=off) held to the analytic picture of one triangle and one cube, to the shared-edge and near-plane rules, to the winner rule,
+to the depth test over a calm sea (with a billboard drawn afterwards), to culling and lane_box independence, to an FP64 twin written from
+the definition (tests/solid_twin.py) on seven tumbled cubes, and to finite pictures on awkward inputs; the stand-alone harness runs under
+the sanitizers on the same inputs; the C example compiles.  GPU: the device's records and RGBA8 words are the CPU build's bit for bit, from
+hand-made instances and from a stepped body set between a mesh draw and a billboard draw, a draw repeats to the byte, the asynchronous
+form is ordered like ow_mesh_draw_async, the scratch grows once and stays, orphaned and foreign handles are refused, and
+examples/solid_draw_host.c writes the picture the Python wrapper returns."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import helpers as H
+import solid_twin as ST
+from godotoceanwaves_amd import _lib, build
+from godotoceanwaves_amd.presets import UPDATE_DELTA
+from godotoceanwaves_amd.wave_generator import WaveGenerator as W
+from test_bodies_step import crate, device_read, make_bodies, quaternion
+from test_mesh_draw import cpu_draw as cpu_mesh_draw, grid, harness as mesh_harness  # noqa: F401
+from test_raycast import calm_maps
+from test_render_view import HIT, camera_words, look
+from test_spray_draw import (blank_records, cpu_draw as cpu_billboard_draw, device_buffers, buffers_to_host, flat_texture, harness as billboard_harness,  # noqa: F401
+                             instances as billboards, level_camera, material, same_picture)
+from test_surface_query import gpu_maps, make_gen, scales_of
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "godotoceanwaves_amd", "csrc")
+PKG = os.path.join(ROOT, "godotoceanwaves_amd")
+HERE = os.path.dirname(os.path.abspath(__file__))
+HARNESS_SRC = os.path.join(HERE, "solid", "solid_harness.cpp")
+MARGINS = os.path.join(ROOT, "profiles", "solid_draw_margins.txt")
+NEW_FUNCTIONS = ("ow_solid_options_default", "ow_solid_create", "ow_solid_destroy", "ow_solid_draw", "ow_solid_draw_async", "ow_solid_draw_instances",
+                 "ow_solid_draw_stats")
+TOL = H.TOL_F32     # 1e-4: the project's FP32 parity tolerance
+SOLID = _lib.OW_RAY_SOLID
+SUN = (0.321197, 0.18296, 0.929171)
+DEFAULTS = dict(color=(0.45, 0.30, 0.15), light_direction=SUN, light_color=(1.0, 1.0, 1.0), ambient_color=(0.05, 0.08, 0.10), background_color=(0.0, 0.0, 0.0))
+CASE = np.dtype([("width", np.int32), ("height", np.int32), ("cam", np.float32, 15), ("num_vertices", np.int32), ("num_triangles", np.int32),
+                 ("count", np.int32), ("stride", np.int32), ("has_flags", np.int32), ("near", np.float32), ("color", np.float32, 3),
+                 ("light_direction", np.float32, 3), ("light_color", np.float32, 3), ("ambient_color", np.float32, 3),
+                 ("background_color", np.float32, 3), ("two_sided", np.int32), ("lane_box", np.int32), ("has_pixels", np.int32)])
+
+
+# ---- shapes, transforms and the CPU build ------------------------------------------------------------------------------------------------
+
+def cube(side=1.0):
+    """8 vertices, 12 triangles, counter-clockwise seen from outside; triangles 2 f and 2 f + 1 are face f (-x, +x, -y, +y, -z, +z)"""
+    h = 0.5 * side
+    v = np.array([[x, y, z] for x in (-h, h) for y in (-h, h) for z in (-h, h)], np.float32)   # index = 4 ix + 2 iy + iz
+    quads = [(0, 1, 3, 2), (4, 6, 7, 5), (0, 4, 5, 1), (2, 3, 7, 6), (0, 2, 6, 4), (1, 5, 7, 3)]
+    t = np.array([tri for a, b, c, d in quads for tri in ((a, b, c), (a, c, d))], np.int32)
+    return v, t
+
+
+def box(size):
+    v, t = cube(1.0)
+    return (v * np.float32(size)).astype(np.float32), t
+
+
+def transform(origin=(0.0, 0.0, 0.0), q=(0.0, 0.0, 0.0, 1.0), scale=1.0):
+    """twelve floats: the rotation of unit quaternion q (x, y, z, w) as basis rows, times scale, then the origin"""
+    x, y, z, w = np.asarray(q, np.float64) / np.linalg.norm(q)
+    r = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                  [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                  [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]]) * scale
+    return np.concatenate([r.ravel(), np.asarray(origin, np.float64)]).astype(np.float32)
+
+
+def transforms(rows):
+    return np.stack([transform(*r) if not isinstance(r, np.ndarray) else r for r in rows]).astype(np.float32) if len(rows) else np.zeros((0, 12), np.float32)
+
+
+@pytest.fixture(scope="module")
+def harness(tmp_path_factory):
+    so = str(tmp_path_factory.mktemp("solid") / "libsolid_harness.so")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unknown-pragmas", "-I", CSRC, HARNESS_SRC, "-o", so], check=True)
+    L = C.CDLL(so)
+    V = C.c_void_p
+    L.harness_solid_sizes.argtypes = [V]
+    L.harness_solid_draw.argtypes = [V] * 9
+    return L
+
+
+def case_of(cam, shape, count, opts=None, records=None, stride=12, flags=None):
+    o = dict(DEFAULTS)
+    o.update(opts or {})
+    h = np.zeros(1, CASE)
+    h["width"], h["height"], h["cam"] = cam.width, cam.height, camera_words(cam)
+    h["num_vertices"], h["num_triangles"], h["count"], h["stride"], h["has_flags"] = len(shape[0]), len(shape[1]), count, stride, int(flags is not None)
+    h["near"], h["two_sided"], h["lane_box"] = o.get("near", 0.0), int(bool(o.get("two_sided"))), o.get("lane_box", 0)
+    for k in ("color", "light_direction", "light_color", "ambient_color", "background_color"):
+        h[k] = o[k]
+    h["has_pixels"] = int(records is not None)
+    return h
+
+
+def case_arrays(shape, tf, records, flags=None):
+    v = np.ascontiguousarray(shape[0], np.float32).reshape(-1, 3)
+    t = np.ascontiguousarray(shape[1], np.int32).reshape(-1, 3)
+    tf = np.ascontiguousarray(tf, np.float32)
+    fl = np.ascontiguousarray(flags, np.int32) if flags is not None else None
+    rec = np.array(records, W.RENDER_PIXEL, copy=True, order="C") if records is not None else None
+    return v, t, tf, fl, rec
+
+
+def cpu_draw(L, shape, tf, cam, opts=None, records=None, stride=12, flags=None):
+    """the CPU build's draw: dict of rgba [H][W][4], rec [H][W] or None, vis [H][W], skipped, culled, lane, wave, drawn"""
+    v, t, tf, fl, rec = case_arrays(shape, tf, records, flags)
+    count = tf.size // stride
+    h = case_of(cam, (v, t), count, opts, records, stride, fl)
+    rgba = np.zeros((cam.height, cam.width, 4), np.uint8)
+    vis = np.zeros((cam.height, cam.width), np.uint64)
+    counters = np.zeros(4, np.uint32)
+    L.harness_solid_draw(h.ctypes.data, v.ctypes.data, t.ctypes.data, tf.ctypes.data if tf.size else None, fl.ctypes.data if fl is not None else None,
+                         rec.ctypes.data if rec is not None else None, rgba.ctypes.data, counters.ctypes.data, vis.ctypes.data)
+    s, c, ln, wv = (int(x) for x in counters)
+    return dict(rgba=rgba, rec=rec, vis=vis, skipped=s, culled=c, lane=ln, wave=wv, drawn=ln + wv)
+
+
+def twin_of(shape, tf, cam, opts=None, records=None):
+    return ST.draw(shape[0], shape[1], tf, cam, opts, records)
+
+
+def check_against_twin(got, tw, what):
+    """exact agreement of the indices and the solid bit, TOL agreement of color, position and t (the last two relative to t) on every pixel
+    the twin does not set aside; returns (share of the covered pixels set aside, covered pixels that remain, worst color, position / t, t / t)"""
+    rec = got["rec"]
+    ok = ~tw["ambiguous"]
+    solid = (rec["status"] & SOLID) != 0
+    for f in ("t", "position", "normal", "albedo", "diffuse", "color"):
+        assert np.isfinite(rec[f]).all(), (what, f)
+    assert np.array_equal(solid[ok], tw["solid"][ok]), what
+    assert np.array_equal(np.where(solid, rec["reserved"][..., 0], 0)[ok], tw["triangle"][ok]), what
+    assert np.array_equal(np.where(solid, rec["reserved"][..., 3], 0)[ok], tw["instance"][ok]), what
+    both = ok & solid
+    t = np.maximum(tw["t"], 1e-30)
+    e_color = np.abs(rec["color"].astype(np.float64) - tw["color"])[ok]
+    e_pos = (np.abs(rec["position"].astype(np.float64) - tw["position"]).max(axis=-1) / t)[both]
+    e_t = (np.abs(rec["t"].astype(np.float64) - tw["t"]) / t)[both]
+    worst = [float(e.max()) if e.size else 0.0 for e in (e_color, e_pos, e_t)]
+    assert max(worst) <= TOL, (what, worst)
+    assert np.array_equal(got["rgba"], ST.rgba8(rec["color"])), what
+    covered = int(tw["covered"].sum())
+    aside = float((tw["ambiguous"] & tw["covered"]).sum() / covered) if covered else 0.0
+    return aside, int((tw["covered"] & ok).sum()), worst[0], worst[1], worst[2]
+
+
+def solid_mask(rec):
+    return (rec["status"] & SOLID) != 0
+
+
+# ---- 1. the interface and the documents --------------------------------------------------------------------------------------------------
+
+HEADER = open(os.path.join(ROOT, "include", "ocean_waves.h")).read()
+
+
+def test_header_declares_the_solid_calls_and_the_library_exports_them():
+    build.build_library()
+    lib = _lib.load()
+    text = re.sub(r"/\*.*?\*/", "", HEADER, flags=re.S)
+    for name in NEW_FUNCTIONS:
+        assert re.search(r"\b%s\s*\(" % name, text), name
+        assert name in _lib.SIGNATURES
+        assert getattr(lib, name)
+    assert re.search(r"typedef struct ow_solid_options \{", text) and "ow_layout_check_solid_options" in HEADER
+    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    exported = set(re.findall(r" T (ow_[a-z0-9_]+)", out))
+    assert sorted(s for s in exported if "solid" in s) == sorted(NEW_FUNCTIONS)      # no group form
+    assert lib.ow_abi_version() == 4 and re.search(r"#define OW_ABI_VERSION 4\b", HEADER)
+    for define, value in (("OW_RAY_SOLID", 16), ("OW_SOLID_TWO_SIDED", 1), ("OW_SOLID_MAX_INSTANCES", 65536), ("OW_SOLID_MAX_TRIANGLES", 65536)):
+        assert re.search(r"#define %s %du?\b" % (define, value), HEADER) and getattr(_lib, define) == value, define
+    section = HEADER.split("Solids drawn into a camera view")[1].split("several devices")[0]
+    for cite in ("water, then solids, then billboards", "no group form", "ow_solid.h", "ow_mesh.h", "OW_RAY_HIT | OW_RAY_SOLID", "reserved[3]"):
+        assert cite in section, cite
+    o = _lib.ow_solid_options()
+    lib.ow_solid_options_default(C.byref(o))
+    r = _lib.ow_render_options()
+    lib.ow_render_options_default(C.byref(r))
+    assert list(o.light_direction) == list(r.light_direction) and list(o.light_color) == list(r.light_color) and list(o.ambient_color) == list(r.ambient_color)
+    assert o.near == np.float32(0.05) and np.array_equal(np.float32(list(o.color)), np.float32(DEFAULTS["color"]))
+    assert (o.flags, o.lane_box) == (0, 0) and not any(o.reserved) and not any(o.background_color)
+    assert np.allclose(list(o.light_direction), DEFAULTS["light_direction"]) and np.allclose(list(o.ambient_color), DEFAULTS["ambient_color"])
+    lib.ow_solid_options_default(None)
+
+
+def test_solid_structs_agree_in_c_ctypes_and_the_harness(tmp_path, harness):
+    S = _lib.ow_solid_options
+    fields = [f for f, _ in S._fields_]
+    expr = ", ".join(["sizeof(ow_solid_options)"] + ["offsetof(ow_solid_options, %s)" % f for f in fields])
+    src = ('#include <stdio.h>\n#include <stddef.h>\n#include "ocean_waves.h"\nint main(void){printf("%s\\n", ' % " ".join(["%zu"] * (1 + len(fields)))
+           + expr + ");return 0;}\n")
+    exe = str(tmp_path / "solid_layout")
+    subprocess.run(["gcc", "-std=c11", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-x", "c", "-", "-o", exe], input=src, text=True, check=True)
+    got = [int(v) for v in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split()]
+    want = [C.sizeof(S)] + [getattr(S, f).offset for f in fields]
+    assert got == want and got[0] == 128
+    off = dict(zip(fields, got[1:]))
+    sizes = (C.c_int * 12)()
+    harness.harness_solid_sizes(sizes)
+    assert list(sizes) == [128] + [off[f] for f in ("color", "light_direction", "flags", "light_color", "ambient_color", "background_color", "lane_box",
+                                                    "reserved")] + [CASE.itemsize, W.MESH_VERTEX.itemsize, C.sizeof(_lib.ow_buoyancy_body)]
+    assert _lib.ow_buoyancy_body.transform.offset == 0 and C.sizeof(_lib.ow_buoyancy_body) == 96
+
+
+def test_the_documents_and_the_csharp_binding_name_the_solid_calls():
+    import test_integration_shim as S
+    for name in NEW_FUNCTIONS:
+        assert re.search(r"\[DllImport\(Lib\)\]\s*public static extern \w+ %s\(" % name, S.SHIM), name
+        assert "`%s`" % name in S.DOC.split("## 7. Index")[1], name
+    want, got = S.c_struct_fields("ow_solid_options"), S.cs_struct_fields("OwSolidOptions")
+    assert got == want and sum(s for _, s in want) == 128, (got, want)
+    for doc, words in (("README.md", ("ow_solid_draw",)), ("DESIGN.md", ("k_solid_vertices", "k_solid_clear", "k_solid_raster", "k_solid_resolve")),
+                       ("INTEGRATION.md", ("ow_solid_draw_async", "OW_RAY_SOLID"))):
+        text = open(os.path.join(ROOT, doc)).read()
+        for w in words:
+            assert w in text, (doc, w)
+
+
+def build_example(tmp_path):
+    exe = str(tmp_path / "solid_draw_host")
+    subprocess.run(["gcc", "-O2", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "examples", "solid_draw_host.c"),
+                    "-o", exe, "-L", PKG, "-locean_waves", "-L", "/opt/rocm/lib", "-lamdhip64", f"-Wl,-rpath,{PKG}", "-Wl,-rpath,/opt/rocm/lib", "-lm"],
+                   check=True)
+    return exe
+
+
+def test_example_builds_as_c99(tmp_path):
+    build.build_library()
+    build_example(tmp_path)
+
+
+# ---- 2. argument errors without a device ---------------------------------------------------------------------------------------------------
+
+def test_solid_argument_errors_without_a_device():
+    lib = _lib.load()
+    cam = level_camera(20, 12)
+    rgba = np.zeros((12, 20, 4), np.uint8)
+    rec = np.zeros((12, 20), W.RENDER_PIXEL)
+    tf = transforms([((0, 0, -10),)])
+    fake = C.c_void_p(16)   # never read: every case fails before a handle is looked at
+
+    def all_forms(camera, opts, rec_p=rec.ctypes.data, rgba_p=rgba.ctypes.data):
+        cp, op = (C.byref(camera) if camera is not None else None), (C.byref(opts) if opts is not None else None)
+        out = []
+        for call in (lambda: lib.ow_solid_draw(None, fake, fake, 0, 1, cp, op, rec_p, rgba_p),
+                     lambda: lib.ow_solid_draw_async(None, fake, fake, 0, 1, cp, op, rec_p, rgba_p),
+                     lambda: lib.ow_solid_draw_instances(None, fake, tf.ctypes.data, 1, cp, op, rec_p, rgba_p)):
+            assert call() == _lib.OW_ERR_INVALID
+            out.append(lib.ow_last_error().decode())
+        assert out[0] == out[1] == out[2]
+        return out[0]
+
+    opt = lambda **kw: W.solid_options(kw)   # noqa: E731
+    assert "null context" in all_forms(cam, None)                      # everything else is in order: only the context is missing
+    assert "null context" in all_forms(cam, opt(near=2.0, lane_box=64, two_sided=True, background_color=(0.1, 0.2, 0.3)))
+    assert "both outputs" in all_forms(cam, None, None, None)
+    assert "null camera" in all_forms(None, None)
+    for w, h in ((0, 12), (20, 0), (_lib.OW_RENDER_MAX_SIDE + 1, 12)):
+        assert "camera size" in all_forms(level_camera(w, h), None)
+    bad = level_camera(20, 12)
+    bad.reserved[2] = 1
+    assert "ow_camera.reserved" in all_forms(bad, None)
+    assert "near" in all_forms(cam, opt(near=float("nan")))
+    for key in ("color", "light_direction", "light_color", "ambient_color", "background_color"):
+        for v in (float("nan"), float("inf"), 3e38):
+            assert "not finite" in all_forms(cam, opt(**{key: (0.5, v, 0.5)})), (key, v)
+    assert "zero length" in all_forms(cam, opt(light_direction=(0.0, 0.0, 0.0)))
+    for lb in (-2, 65):
+        assert "lane_box" in all_forms(cam, opt(lane_box=lb)), lb
+    o = opt()
+    o.flags = 2
+    assert "solid flags" in all_forms(cam, o)
+    o = opt()
+    o.reserved[13] = 3
+    assert "ow_solid_options.reserved" in all_forms(cam, o)
+    for count in (-1, _lib.OW_SOLID_MAX_INSTANCES + 1):
+        assert lib.ow_solid_draw_instances(None, fake, tf.ctypes.data, count, C.byref(cam), None, rec.ctypes.data, rgba.ctypes.data) == _lib.OW_ERR_INVALID
+        assert "count" in lib.ow_last_error().decode()
+    assert lib.ow_solid_draw_instances(None, fake, None, 1, C.byref(cam), None, rec.ctypes.data, rgba.ctypes.data) == _lib.OW_ERR_INVALID
+    assert lib.ow_solid_draw(None, None, fake, 0, 1, C.byref(cam), None, rec.ctypes.data, rgba.ctypes.data) == _lib.OW_ERR_INVALID
+    assert not rgba.any() and not rec.tobytes().strip(b"\0")
+    # the shape
+    v, t = cube()
+
+    def create(vp=v.ctypes.data, nv=8, tp=t.ctypes.data, nt=12):
+        out = C.c_void_p(0x5EED)
+        assert lib.ow_solid_create(None, vp, nv, tp, nt, C.byref(out)) == _lib.OW_ERR_INVALID
+        return out.value, lib.ow_last_error().decode()
+
+    assert create() == (None, "null context") or "null context" in create()[1]
+    for kw in (dict(nv=0), dict(nt=0), dict(nt=_lib.OW_SOLID_MAX_TRIANGLES + 1), dict(nv=(1 << 24) + 1)):
+        assert "num_vertices" in create(**kw)[1], kw
+    assert "null argument" in create(vp=None)[1] and "null argument" in create(tp=None)[1]
+    assert "index" in create(nv=7)[1]
+    neg = t.copy()
+    neg[3, 1] = -1
+    assert "index" in create(tp=neg.ctypes.data)[1]
+    assert lib.ow_solid_create(None, v.ctypes.data, 8, t.ctypes.data, 12, None) == _lib.OW_ERR_INVALID
+    lib.ow_solid_destroy(None, None)
+    assert lib.ow_solid_draw_stats(None, None, None, None, None, None) == _lib.OW_ERR_INVALID
+    with pytest.raises(ValueError):
+        W.solid_options({"bin_side": 8})
+
+
+# ---- 3. one triangle and one cube, analytically ------------------------------------------------------------------------------------------
+
+def pixel_xy32(cam):
+    """mesh_pixel_xy in FP32, operation for operation"""
+    cw = camera_words(cam)
+    th, aspect = cw[12], cw[13]
+    i, j = np.meshgrid(np.arange(cam.width, dtype=np.float32), np.arange(cam.height, dtype=np.float32))
+    two, half, one = np.float32(2), np.float32(0.5), np.float32(1)
+    x = ((two * (i + half)) / np.float32(cam.width) - one) * aspect * th
+    y = (one - (two * (j + half)) / np.float32(cam.height)) * th
+    return x, y
+
+
+def lit_color(normal, opts=None):
+    """albedo (light_color max(n . l^, 0) + ambient_color) in FP32, operation for operation"""
+    o = dict(DEFAULTS)
+    o.update(opts or {})
+    l64 = np.float32(o["light_direction"]).astype(np.float64)
+    light = (l64 / np.sqrt((l64 * l64).sum())).astype(np.float32)
+    n = np.float32(normal)
+    ndl = max((n[0] * light[0] + n[1] * light[1]) + n[2] * light[2], np.float32(0))
+    diffuse = np.float32(o["light_color"]) * ndl
+    return np.float32(o["color"]) * (diffuse + np.float32(o["ambient_color"])), diffuse
+
+
+def test_one_triangle_is_the_analytic_picture(harness):
+    """A level camera with fov 90 at 64 x 40: at depth s = 16 a pixel is 0.8 m wide and high, pixel centre (i, j) lies at ((i - 31.5) 0.8,
+    (19.5 - j) 0.8).  The right triangle (-4.2, -3.0), (6.2, -3.0), (-4.2, 5.0) in the plane z = -16 has its legs a quarter of a pixel off the
+    centres; its depth is exactly 16 at every centre, its normal exactly +z."""
+    cam = level_camera()
+    shape = (np.float32([(-4.2, -3.0, -16.0), (6.2, -3.0, -16.0), (-4.2, 5.0, -16.0)]), np.int32([(0, 1, 2)]))
+    tf = transforms([()])
+    bg = blank_records(cam)
+    got = cpu_draw(harness, shape, tf, cam, records=bg)
+    rec = got["rec"]
+    i, j = np.meshgrid(np.arange(64), np.arange(40))
+    x, y = (i - 31.5) * 0.8, (19.5 - j) * 0.8
+    hyp = (x + 4.2) / 10.4 + (y + 3.0) / 8.0
+    assert np.abs(hyp - 1.0).min() > 1e-3                      # no centre on the hypotenuse
+    want = (x > -4.2) & (y > -3.0) & (hyp < 1.0)
+    solid = solid_mask(rec)
+    assert np.array_equal(solid, want) and want.sum() > 50
+    assert (got["skipped"], got["culled"], got["drawn"]) == (0, 0, 1)
+    assert (rec["status"][solid] == (HIT | SOLID)).all()
+    x32, y32 = pixel_xy32(cam)
+    t = np.float32(16.0) * np.sqrt((x32 * x32 + y32 * y32) + np.float32(1))
+    assert rec["t"][solid].tobytes() == t[solid].tobytes()
+    assert (rec["normal"][solid] == np.float32((0, 0, 1))).all()
+    color, diffuse = lit_color((0, 0, 1))
+    assert (rec["color"][solid] == color).all() and (rec["diffuse"][solid] == diffuse).all() and (rec["albedo"][solid] == np.float32(DEFAULTS["color"])).all()
+    assert np.abs(rec["position"][solid] - np.stack([x, y, np.full_like(x, -16.0)], -1)[solid]).max() < 2e-5
+    assert (rec["reserved"][solid] == np.uint32((1, 0, 0, 1))).all()
+    for f in W.RENDER_PIXEL.names:                             # a solid's record: every other field is 0; every other pixel keeps its record
+        if f not in ("t", "status", "position", "normal", "albedo", "diffuse", "color", "reserved"):
+            assert not rec[f][solid].any(), f
+        assert rec[f][~solid].tobytes() == bg[f][~solid].tobytes(), f
+    assert np.array_equal(got["rgba"], ST.rgba8(rec["color"]))
+    flipped = (shape[0], np.int32([(0, 2, 1)]))               # wound the other way: a back face
+    back = cpu_draw(harness, flipped, tf, cam, records=bg)
+    assert not solid_mask(back["rec"]).any() and back["culled"] == 1 and back["rec"].tobytes() == bg.tobytes()
+    two = cpu_draw(harness, flipped, tf, cam, {"two_sided": True}, bg)
+    assert np.array_equal(solid_mask(two["rec"]), want) and (two["rec"]["normal"][want] == np.float32((0, 0, 1))).all()
+    assert two["rec"]["color"].tobytes() == rec["color"].tobytes() and two["rec"]["t"].tobytes() == rec["t"].tobytes()
+    tw = twin_of(shape, tf, cam, None, bg)
+    assert not tw["ambiguous"].any() and np.array_equal(tw["solid"], want)
+    check_against_twin(got, tw, "triangle")
+
+
+def test_one_cube_is_the_analytic_picture(harness):
+    """A cube of side 4.4 centred on the axis at z = -18.2: only its front face (z = -16, triangles 10 and 11) faces the camera and covers the
+    centres |x|, |y| <= 2.2: columns 29 .. 34, rows 17 .. 22.  Rotated by a quarter turn about y the face seen is -x (triangles 0 and 1)."""
+    cam = level_camera()
+    shape = cube(4.4)
+    bg = blank_records(cam)
+    got = cpu_draw(harness, shape, transforms([((0.0, 0.0, -18.2),)]), cam, records=bg)
+    rec = got["rec"]
+    want = np.zeros((40, 64), bool)
+    want[17:23, 29:35] = True
+    solid = solid_mask(rec)
+    assert np.array_equal(solid, want)
+    assert set(np.unique(rec["reserved"][..., 0][solid])) == {11, 12} and (rec["reserved"][..., 3][solid] == 1).all()
+    assert (got["skipped"], got["culled"], got["drawn"]) == (0, 10, 2)
+    x32, y32 = pixel_xy32(cam)
+    t = np.float32(16.0) * np.sqrt((x32 * x32 + y32 * y32) + np.float32(1))
+    assert np.abs(rec["t"][solid] / t[solid] - 1).max() < 1e-6
+    assert (rec["normal"][solid] == np.float32((0, 0, 1))).all() and (rec["color"][solid] == lit_color((0, 0, 1))[0]).all()
+    turned = cpu_draw(harness, shape, transforms([((0.0, 0.0, -18.2), quaternion((0, 1, 0), np.pi / 2))]), cam, records=bg)
+    rt = turned["rec"]
+    assert np.array_equal(solid_mask(rt), want) and set(np.unique(rt["reserved"][..., 0][want])) == {1, 2}
+    assert np.abs(rt["normal"][want] - np.float32((0, 0, 1))).max() < 1e-6
+    none = cpu_draw(harness, shape, transforms([((0.0, 0.0, -18.2),)]), cam, {"background_color": (0.2, 0.3, 0.4)})      # no records
+    assert none["rec"] is None
+    flat = np.where(want[..., None], lit_color((0, 0, 1))[0], np.float32((0.2, 0.3, 0.4)))
+    assert np.array_equal(none["rgba"], ST.rgba8(flat))
+
+
+# ---- 4. shared edges, the near plane, behind the camera ------------------------------------------------------------------------------------
+
+def test_shared_edge_near_plane_and_behind_the_camera(harness):
+    cam = level_camera()
+    # a square whose diagonal runs through pixel centres: corners a quarter of a pixel outside centres (24 .. 35, 12 .. 23) at depth 16
+    x0, x1, y0, y1 = (24 - 31.5) * 0.8 - 0.2, (35 - 31.5) * 0.8 + 0.2, (19.5 - 23) * 0.8 - 0.2, (19.5 - 12) * 0.8 + 0.2
+    shape = (np.float32([(x0, y0, -16), (x1, y0, -16), (x1, y1, -16), (x0, y1, -16)]), np.int32([(0, 1, 2), (0, 2, 3)]))
+    got = cpu_draw(harness, shape, transforms([()]), cam, records=blank_records(cam))
+    want = np.zeros((40, 64), bool)
+    want[12:24, 24:36] = True
+    solid = solid_mask(got["rec"])
+    assert np.array_equal(solid, want)                        # no centre on the diagonal is left out
+    tri = got["rec"]["reserved"][..., 0]
+    j, i = np.nonzero(want)
+    above = (i - 24) < (23 - j)                               # strictly on triangle 1's side of the diagonal (0, 2, 3)
+    below = (i - 24) > (23 - j)
+    assert (tri[j[above], i[above]] == 2).all() and (tri[j[below], i[below]] == 1).all()
+    assert set(tri[j[~above & ~below], i[~above & ~below]]) <= {1, 2}   # on it: either, once
+    # a floor triangle from behind the camera to far ahead, one metre below it: drawn where the ray meets it beyond the near plane, nothing
+    # is clipped; and one wholly behind the camera: culled
+    floor = (np.float32([(-30, -1, 8), (30, -1, 8), (0, -1, -60)]), np.int32([(0, 1, 2)]))
+    bg = blank_records(cam)
+    f = cpu_draw(harness, floor, transforms([()]), cam, {"near": 0.5}, bg)
+    tw = twin_of(floor, transforms([()]), cam, {"near": 0.5}, bg)
+    aside, remain, *_ = check_against_twin(f, tw, "floor")
+    s = solid_mask(f["rec"])
+    assert s.sum() > 500 and not s[:20].any() and aside < 0.02
+    assert (f["rec"]["position"][s][:, 2] < -0.5).all() and np.abs(f["rec"]["position"][s][:, 1] + 1).max() < 1e-4
+    behind = (np.float32([(-3, -1, 8), (3, -1, 8), (0, 2, 3)]), np.int32([(0, 1, 2), (0, 2, 1)]))
+    b = cpu_draw(harness, behind, transforms([()]), cam, {"two_sided": True}, bg)
+    assert b["rec"].tobytes() == bg.tobytes() and (b["culled"], b["drawn"]) == (2, 0)
+
+
+# ---- 5. the winner ---------------------------------------------------------------------------------------------------------------------------
+
+def tumbled(count, seed=5, x=(-4.7, 4.7), y=(-0.9, 1.6), z=(4.3, 9.7)):
+    rng = np.random.default_rng(seed)
+    rows = []
+    for _ in range(count):
+        q = rng.normal(size=4)
+        rows.append(((rng.uniform(*x), rng.uniform(*y), rng.uniform(*z)), q / np.linalg.norm(q)))
+    return transforms(rows)
+
+
+TWIN_CAM = dict(position=(0.37, 3.1, -1.3), yaw_deg=4.0, pitch_deg=-14.0, fov=75.0, width=96, height=64, max_distance=500.0)
+
+
+def test_the_winner_is_the_nearest_then_the_lowest_index(harness):
+    cam = level_camera()
+    shape = cube(4.4)
+    bg = blank_records(cam)
+    near_far = cpu_draw(harness, shape, transforms([((6.0, 0.0, -30.0),), ((0.5, 0.0, -18.2),)]), cam, records=bg)["rec"]
+    both = solid_mask(near_far)
+    inst = near_far["reserved"][..., 3]
+    assert set(np.unique(inst[both])) == {1, 2} and (inst[17:23, 30:35] == 2).all()          # the nearer one wherever both cover
+    same = cpu_draw(harness, shape, transforms([((0.0, 0.0, -18.2),)] * 3), cam, records=bg)["rec"]
+    assert (same["reserved"][..., 3][solid_mask(same)] == 1).all() and solid_mask(same).sum() == 36     # equal depth: the lowest index
+    look_cam = look(**TWIN_CAM)
+    tf = tumbled(7)
+    shape = box((2.5, 2.5, 2.5))
+    base = cpu_draw(harness, shape, tf, look_cam, records=blank_records(look_cam))
+    perm = np.array([3, 0, 6, 1, 5, 2, 4])
+    moved = cpu_draw(harness, shape, tf[perm], look_cam, records=blank_records(look_cam))
+    s = solid_mask(base["rec"])
+    assert s.sum() > 1000 and np.array_equal(s, solid_mask(moved["rec"])) and moved["rgba"].tobytes() == base["rgba"].tobytes()
+    for f in W.RENDER_PIXEL.names:
+        if f != "reserved":
+            assert moved["rec"][f].tobytes() == base["rec"][f].tobytes(), f
+    assert np.array_equal(moved["rec"]["reserved"][..., :3], base["rec"]["reserved"][..., :3])
+    assert np.array_equal(perm[moved["rec"]["reserved"][..., 3][s] - 1] + 1, base["rec"]["reserved"][..., 3][s])
+
+
+# ---- 6. depth against a calm sea -------------------------------------------------------------------------------------------------------------
+
+def calm_picture(mesh_harness, cam):
+    d, m, sc = calm_maps()
+    return cpu_mesh_draw(mesh_harness, d, m, sc, grid(16, 8.0), (0.0, 0.0, 0.0), cam)["rec"]
+
+
+def test_depth_against_a_calm_sea_and_a_billboard_afterwards(harness, mesh_harness, billboard_harness):
+    """The calm sea is the plane y = 0.  A pixel's ray comes down from a camera 6 m up: it meets a point of the crate with y > 0 before the
+    water and one with y < 0 after it, so the crate is drawn exactly where its own surface point is above the waterline."""
+    cam = look((0.0, 6.0, 0.0), 0.0, -20.0, width=64, height=40, max_distance=500.0)
+    bg = calm_picture(mesh_harness, cam)
+    assert 0.3 < ((bg["status"] & HIT) != 0).mean() < 0.9
+    shape = box((6.0, 4.0, 6.0))
+    tf = transforms([((0.3, 0.0, 14.0), quaternion((0, 1, 0), 0.5))])
+    free = cpu_draw(harness, shape, tf, cam, records=blank_records(cam))["rec"]       # no depth under it: everything the crate covers
+    got = cpu_draw(harness, shape, tf, cam, records=bg)
+    rec = got["rec"]
+    covered, solid = solid_mask(free), solid_mask(rec)
+    y = free["position"][..., 1]
+    clear = np.abs(y) > 1e-3
+    assert covered.sum() > 60 and np.array_equal(solid[covered & clear], (y > 0)[covered & clear]) and not solid[~covered].any()
+    assert 0 < solid.sum() < covered.sum()
+    assert (rec["t"][solid] <= bg["t"][solid]).all() or not ((bg["status"][solid] & HIT) != 0).all()
+    for f in W.RENDER_PIXEL.names:
+        assert rec[f][~solid].tobytes() == bg[f][~solid].tobytes(), f                # hidden or not covered: the whole record stays
+        if f != "reserved":
+            assert rec[f][solid].tobytes() == free[f][solid].tobytes(), f
+    check_against_twin(got, twin_of(shape, tf, cam, None, bg), "waterline")
+    sunk = cpu_draw(harness, shape, transforms([((0.3, -4.5, 14.0),)]), cam, records=bg)
+    assert sunk["rec"].tobytes() == bg.tobytes() and sunk["drawn"] > 0                 # wholly under water: nothing changes
+    # a billboard 6 m behind the crate, drawn afterwards: hidden where the crate is nearer, blended elsewhere
+    mat = material(dissolve=flat_texture((0, 0, 0, 255)))
+    spray = billboards([((0.3, 1.0, 20.0), 8.0, 4.0, 0.9, 0.7)])
+    spray["transform"][:, 8], spray["transform"][:, 0] = spray["transform"][:, 0].copy(), 0.0    # the camera looks along +z: column 0 along z
+    spray["transform"][:, 2], spray["transform"][:, 10] = 1.0, 0.0
+    over_water = cpu_billboard_draw(billboard_harness, spray, cam, mat, records=bg)["rec"]["reserved"][..., 1]
+    over_crate = cpu_billboard_draw(billboard_harness, spray, cam, mat, records=rec)["rec"]["reserved"][..., 1]
+    assert (over_water[solid] > 0).any()                        # the billboard would be seen there ...
+    assert not over_crate[solid].any()                          # ... and is hidden behind the crate
+    assert np.array_equal(over_crate[~solid], over_water[~solid]) and over_crate.sum() > 0
+
+
+# ---- 7. culling, two sides, lane_box ---------------------------------------------------------------------------------------------------------
+
+def mixed_cubes(count, seed=9):
+    """cube 0 fills much of the view (the wave's sweep), the others shrink with their index down to sub-pixel ones 400 m out (a lane's walk)"""
+    rng = np.random.default_rng(seed)
+    rows = []
+    for k in range(count):
+        q = rng.normal(size=4)
+        z = 3.2 if k == 0 else 6.0 + 394.0 * (k / max(count - 1, 1)) ** 2
+        rows.append(((rng.uniform(-0.45, 0.45) * z, rng.uniform(-0.3, 0.3) * z, -z), q / np.linalg.norm(q), 1.0 if k else 1.6))
+    return transforms(rows)
+
+
+def test_back_faces_two_sides_and_lane_box(harness):
+    cam = level_camera()
+    bg = blank_records(cam)
+    inside = transforms([((0.0, 0.0, 0.0), quaternion((1, 2, 3), 0.7), 30.0)])           # the camera sits inside a cube of side 30
+    one = cpu_draw(harness, cube(), inside, cam, records=bg)
+    assert one["rec"].tobytes() == bg.tobytes() and one["drawn"] == 0
+    two = cpu_draw(harness, cube(), inside, cam, {"two_sided": True}, bg)
+    rec = two["rec"]
+    assert solid_mask(rec).all() and two["drawn"] > 0
+    assert ((rec["normal"] * rec["position"]).sum(-1) < 0).all()                          # the normals of back faces point at the camera
+    tf = mixed_cubes(70)
+    base = cpu_draw(harness, cube(), tf, cam, records=bg)
+    assert base["lane"] > 0 and base["wave"] > 0 and base["skipped"] * 12 + base["culled"] + base["drawn"] == 70 * 12
+    assert solid_mask(base["rec"]).sum() > 200
+    seen = {}
+    for lb in (-1, 1, 64):
+        other = cpu_draw(harness, cube(), tf, cam, {"lane_box": lb}, bg)
+        same_picture(other, base, lb)
+        assert other["vis"].tobytes() == base["vis"].tobytes() and other["drawn"] == base["drawn"]
+        seen[lb] = (other["lane"], other["wave"])
+    assert seen[-1][0] == 0 and seen[64][0] > base["lane"] > seen[1][0]
+
+
+# ---- 8. the FP64 twin ------------------------------------------------------------------------------------------------------------------------
+
+def twin_scene(mesh_harness):
+    cam = look(**TWIN_CAM)
+    return box((2.5, 2.5, 2.5)), tumbled(7, seed=20261018), cam, calm_picture(mesh_harness, cam)
+
+
+def test_the_twin_alone_meets_the_scenes_conditions(mesh_harness):
+    """before anything else: of the twin's covered pixels at most 2 % are set aside and at least 1 500 remain"""
+    shape, tf, cam, bg = twin_scene(mesh_harness)
+    tw = twin_of(shape, tf, cam, None, bg)
+    covered = int(tw["covered"].sum())
+    aside = int((tw["covered"] & tw["ambiguous"]).sum())
+    print(f"covered {covered} set aside {aside}")
+    assert aside <= 0.02 * covered and covered - aside >= 1500
+
+
+def test_seven_tumbled_cubes_against_the_fp64_twin(harness, mesh_harness):
+    """Measured on the CPU build (profiles/solid_draw_margins.txt): 1 778 pixels covered, 1 set aside (0.06 %, cap 2 %); on the others the
+    largest colour difference is 3.0e-8, the largest position and t differences 2.4e-7 and 2.8e-7 of t, against TOL = 1e-4.  The figures go
+    to the file with SOLID_DRAW_WRITE_MARGINS=1."""
+    shape, tf, cam, bg = twin_scene(mesh_harness)
+    got = cpu_draw(harness, shape, tf, cam, records=bg)
+    tw = twin_of(shape, tf, cam, None, bg)
+    aside, remain, e_color, e_pos, e_t = check_against_twin(got, tw, "seven cubes")
+    print(f"covered {int(tw['covered'].sum())} remain {remain} aside {aside:.4f} color {e_color:.3e} position {e_pos:.3e} t {e_t:.3e}")
+    assert aside <= 0.02 and remain >= 1500
+    assert 0 < solid_mask(got["rec"]).sum() < tw["covered"].sum()                       # the calm sea hides part of them
+    assert set(np.unique(got["rec"]["reserved"][..., 3])) == set(range(8))
+    if os.environ.get("SOLID_DRAW_WRITE_MARGINS") == "1":
+        rows = [("seven tumbled cubes over a calm sea, 96 x 64", 7, got["drawn"], int(tw["covered"].sum()), aside, e_color, e_pos, e_t)]
+        for name, c in awkward_cases().items():
+            if c.get("twin", True):
+                g, b = run_case(harness, c)
+                t = twin_of(c["shape"], c["tf"], c["cam"], c.get("opts"), b)
+                a, _, ec, ep, et = check_against_twin(g, t, name)
+                rows.append((name, len(c["tf"]), g["drawn"], int(t["covered"].sum()), a, ec, ep, et))
+        with open(MARGINS, "w") as f:
+            f.write("The solid draw's CPU build (tests/solid/solid_harness.cpp) against the FP64 twin (tests/solid_twin.py), written by\n"
+                    "tests/test_solid_draw.py::test_seven_tumbled_cubes_against_the_fp64_twin with SOLID_DRAW_WRITE_MARGINS=1.\n"
+                    "aside: the share of covered pixels the twin calls ambiguous (a centre within 1e-3 pixel of an edge; two depths, or a depth\n"
+                    "and the background's t, within 1e-5 relative).  The differences are the largest over the other pixels: |colour - twin|,\n"
+                    "|position - twin| / t and |t - twin| / t (the tests' bound is 1e-4 for each).\n\n")
+            f.write(f"{'case':52s} {'instances':>9s} {'drawn':>6s} {'covered':>8s} {'aside':>7s} {'colour':>10s} {'position':>10s} {'t':>10s}\n")
+            for r in rows:
+                f.write(f"{r[0]:52s} {r[1]:9d} {r[2]:6d} {r[3]:8d} {r[4]:7.4f} {r[5]:10.3e} {r[6]:10.3e} {r[7]:10.3e}\n")
+
+
+def test_margins_file_holds_the_measured_figures():
+    text = open(MARGINS).read()
+    assert "seven tumbled cubes over a calm sea" in text and "aside" in text and "position" in text
+    row = [ln for ln in text.splitlines() if ln.startswith("seven tumbled cubes")][0].split()
+    assert float(row[-4]) <= 0.02 and all(float(v) <= TOL for v in row[-3:])
+
+
+# ---- 9. awkward inputs -------------------------------------------------------------------------------------------------------------------------
+
+def awkward_cases():
+    cam = level_camera(37, 21)
+    some = mixed_cubes(6)
+    broken = mixed_cubes(6)
+    broken[1, 4], broken[3, 10], broken[4, 0] = np.nan, np.inf, -np.inf
+    huge = mixed_cubes(3)
+    huge[1, :9] *= 3e38                                            # finite values whose products overflow: its vertices are not finite
+    nan_vertex = cube()[0].copy()
+    nan_vertex[7, 1] = np.nan
+    flat = (np.float32([(-2, -2, 0), (2, -2, 0), (0, 2, 0), (0, 0, 0), (1, 1, 0)]), np.int32([(0, 1, 2), (0, 0, 1), (0, 3, 4), (3, 3, 3)]))
+    nan_cam, inf_cam = level_camera(37, 21), level_camera(37, 21)
+    nan_cam.position[1] = float("nan")
+    inf_cam.basis[4] = float("inf")
+    return {
+        "1 x 1 image": dict(shape=cube(4.0), tf=transforms([((0, 0, -10),)]), cam=level_camera(1, 1), skipped=0, solid=1),
+        "37 x 21, six cubes": dict(shape=cube(), tf=some, cam=cam, skipped=0),
+        "transforms that are not finite": dict(shape=cube(), tf=broken, cam=cam, skipped=3),
+        "a transform that overflows": dict(shape=cube(), tf=huge, cam=cam, skipped=0, twin=False),
+        "a vertex with a NaN": dict(shape=(nan_vertex, cube()[1]), tf=some, cam=cam, skipped=0, twin=False),
+        "zero-area triangles": dict(shape=flat, tf=transforms([((0, 0, -8),)]), cam=cam, skipped=0, opts={"two_sided": True}),
+        "no instances": dict(shape=cube(), tf=transforms([]), cam=cam, skipped=0, nothing=True),
+        "a camera with a NaN": dict(shape=cube(), tf=some, cam=nan_cam, skipped=0, nothing=True, twin=False, dead=True),
+        "a camera with an Inf": dict(shape=cube(), tf=some, cam=inf_cam, skipped=0, nothing=True, twin=False, dead=True),
+    }
+
+
+def run_case(L, c, records="blank"):
+    rec = blank_records(c["cam"]) if records == "blank" else records
+    return cpu_draw(L, c["shape"], c["tf"], c["cam"], c.get("opts"), rec), rec
+
+
+@pytest.mark.parametrize("name", list(awkward_cases()))
+def test_awkward_inputs(harness, name):
+    """a finite picture equal to the twin's and the stated counters; where nothing is visible an untouched background"""
+    c = awkward_cases()[name]
+    got, bg = run_case(harness, c)
+    rec = got["rec"]
+    nt = len(c["shape"][1])
+    for f in ("t", "position", "normal", "albedo", "diffuse", "color"):
+        assert np.isfinite(rec[f]).all(), f
+    assert np.array_equal(got["rgba"], ST.rgba8(rec["color"])) and got["skipped"] == c["skipped"]
+    if c.get("dead"):
+        assert (got["skipped"], got["culled"], got["drawn"]) == (0, 0, 0)            # a camera that is not finite: nothing is even counted
+    else:
+        assert got["skipped"] * nt + got["culled"] + got["drawn"] == len(c["tf"]) * nt
+    if c.get("nothing"):
+        assert rec.tobytes() == bg.tobytes() and got["drawn"] == 0
+    if c.get("twin", True):
+        check_against_twin(got, twin_of(c["shape"], c["tf"], c["cam"], c.get("opts"), bg), name)
+    without, _ = run_case(harness, c, records=None)                                   # no records: the options' background
+    assert without["rec"] is None and np.array_equal(without["rgba"][..., :3].any(-1), solid_mask(rec))
+    if "solid" in c:
+        assert solid_mask(rec).sum() == c["solid"]
+    if name == "transforms that are not finite":
+        assert not np.isin(rec["reserved"][..., 3], [2, 4, 5]).any() and solid_mask(rec).any()
+    if name == "a transform that overflows":
+        assert not (rec["reserved"][..., 3] == 2).any() and got["culled"] >= 12
+    if name == "a vertex with a NaN":
+        assert got["culled"] >= 6 * 3 and solid_mask(rec).any()                      # vertex 7 is a corner of three faces of each cube
+    if name == "zero-area triangles":
+        assert got["drawn"] == 1 and got["culled"] == 3 and set(np.unique(rec["reserved"][..., 0])) == {0, 1}
+
+
+# ---- 10. the sanitizers ------------------------------------------------------------------------------------------------------------------------
+
+def write_case(path, c, records):
+    v, t, tf, fl, rec = case_arrays(c["shape"], c["tf"], records, c.get("flags"))
+    h = case_of(c["cam"], (v, t), tf.size // c.get("stride", 12), c.get("opts"), records, c.get("stride", 12), fl)
+    with open(path, "wb") as f:
+        for block in (h, v, t, tf) + ((fl,) if fl is not None else ()) + ((rec,) if rec is not None else ()):
+            f.write(block.tobytes())
+
+
+def test_stand_alone_harness_runs_clean_under_the_sanitizers(tmp_path, harness, mesh_harness):
+    """the harness as a program of its own (-DSOLID_HARNESS_MAIN), built with -fsanitize=address,undefined, on the twin's scene, the mixed
+    cubes and every awkward case: the picture it writes is the shared library's"""
+    exe = str(tmp_path / "solid_harness_main")
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                    "-Wno-unknown-pragmas", "-DSOLID_HARNESS_MAIN", "-I", CSRC, HARNESS_SRC, "-o", exe], check=True)
+    shape, tf, cam, bg = twin_scene(mesh_harness)
+    cases = dict(awkward_cases(), twin=dict(shape=shape, tf=tf, cam=cam, records=bg))
+    cases["70 mixed cubes"] = dict(shape=cube(), tf=mixed_cubes(70), cam=level_camera(64, 40))
+    padded = np.zeros((6, 24), np.float32)                      # pose records: 24 floats apart, with fault flags
+    padded[:, :12] = mixed_cubes(6)
+    cases["pose records with a raised flag"] = dict(shape=cube(), tf=padded, cam=level_camera(37, 21), stride=24, flags=np.int32([0, 0, 1, 0, 0, 0]),
+                                                    records=blank_records(level_camera(37, 21)))
+    for k, (name, c) in enumerate(cases.items()):
+        records = c["records"] if "records" in c else (None if k % 3 == 2 else blank_records(c["cam"]))
+        path, out = str(tmp_path / f"case{k}.bin"), str(tmp_path / f"case{k}.out")
+        write_case(path, c, records)
+        r = subprocess.run([exe, path, out], capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, (name, r.stdout + r.stderr)
+        assert r.stdout.endswith("ok\n") and "not_finite=0" in r.stdout and "runtime error" not in r.stderr and "Sanitizer" not in r.stderr, name
+        want = cpu_draw(harness, c["shape"], c["tf"], c["cam"], c.get("opts"), records, c.get("stride", 12), c.get("flags"))
+        raw = open(out, "rb").read()
+        counters = np.array([want["skipped"], want["culled"], want["lane"], want["wave"]], np.uint32)
+        assert raw == (want["rec"].tobytes() if records is not None else b"") + want["rgba"].tobytes() + counters.tobytes(), name
+        if "flags" in c:
+            assert want["skipped"] == 1 and not (want["rec"]["reserved"][..., 3] == 3).any()
+
+
+# ---- 11-16. on the GPU -------------------------------------------------------------------------------------------------------------------------
+
+def bare_context():
+    """the smallest context: the solid draw reads no map"""
+    return make_gen(128, [0, 1])[0]
+
+
+def gpu_instances(gen, shape, tf, cam, opts=None, records=None):
+    h = gen.solid_create(*shape)
+    rgba, rec = gen.solid_draw_instances(h, tf, cam, opts, pixels=records)
+    st = gen.solid_draw_stats()
+    gen.solid_destroy(h)
+    return dict(rgba=rgba, rec=rec, skipped=st["skipped_instances"], culled=st["culled"], drawn=st["drawn"])
+
+
+def same_counters(got, want, what):
+    assert (got["skipped"], got["culled"], got["drawn"]) == (want["skipped"], want["culled"], want["drawn"]), what
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("count", [1, 5, 6, 70])
+def test_gpu_hand_made_instances_are_the_cpu_builds_bit_for_bit(harness, count):
+    """12 triangles a cube: 5 and 6 cubes straddle one wave of 64 pairs, 70 span fourteen; cube 0 is near enough for the wave's sweep, the
+    far ones are sub-pixel on a lane's walk; 160 x 96 and 37 x 21 (partial tiles), with records and without, one- and two-sided"""
+    gen = bare_context()
+    tf = mixed_cubes(count)
+    if count == 70:
+        tf[17, 3], tf[40, 11] = np.nan, np.inf
+    for cam in (level_camera(160, 96), level_camera(37, 21)):
+        for opts in (None, {"two_sided": True, "near": 0.5, "background_color": (0.2, 0.3, 0.4), "color": (0.8, 0.7, 0.1)}):
+            for bg in (blank_records(cam), None):
+                got = gpu_instances(gen, cube(), tf, cam, opts, bg)
+                want = cpu_draw(harness, cube(), tf, cam, opts, bg)
+                what = (count, cam.width, opts is not None, bg is not None)
+                same_picture(got, want, what)
+                same_counters(got, want, what)
+                assert got["skipped"] * 12 + got["culled"] + got["drawn"] == count * 12, what
+                assert want["wave"] > 0 and (count < 6 or want["lane"] > 0), what
+    for name, c in awkward_cases().items():
+        got = gpu_instances(gen, c["shape"], c["tf"], c["cam"], c.get("opts"), blank_records(c["cam"]))
+        want, _ = run_case(harness, c)
+        same_picture(got, want, name)
+        same_counters(got, want, name)
+    gen.free()
+
+
+def eight_crates():
+    rng = np.random.default_rng(3)
+    items = []
+    for k in range(8):
+        q = rng.normal(size=4)
+        items.append(crate(origin=((k % 4 - 1.5) * 4.0 + 0.3, 0.3, 6.0 + 5.0 * (k // 4)), q=tuple(q / np.linalg.norm(q)), kl=3.0, kq=0.5))
+    return make_bodies(items)
+
+
+CRATE_CAM = dict(position=(0.4, 5.0, -9.0), yaw_deg=2.0, pitch_deg=-17.0, fov=75.0, width=160, height=96, max_distance=2000.0)
+CRATE_SHAPE = (2.0, 1.0, 2.0)
+
+
+def floating_scene(n=128, stream=None, steps=6, broken=None):
+    """128^2 x 2 maps, eight tumbling crates stepped behind a tick each (one of them overflowing in its first substep: its fault flag is
+    raised and its state frozen where it was created), a 4096-particle emitter stepped with them"""
+    gen, params = make_gen(n, [0, 1], stream=stream)
+    sc = scales_of(params)
+    gen.run(UPDATE_DELTA, params, 20)
+    st, hull = eight_crates()
+    if broken is not None:
+        st["applied_force"][broken], st["mass"][broken] = (0, 1.7e308, 0), 1e-3       # passes the host's checks, is not finite after one substep
+    bodies = gen.bodies_create(st, hull)
+    spray = gen.spray_create({"amount": 4096, "emitter_lifetime": 0.5, "lifetime": 0.25})
+    advance(gen, params, sc, bodies, spray, steps)
+    return gen, params, sc, bodies, spray
+
+
+def advance(gen, params, sc, bodies, spray, steps):
+    for _ in range(steps):
+        gen.update_all(UPDATE_DELTA, params)
+        gen.bodies_step(bodies, sc, 2, UPDATE_DELTA / 2, {"warm_start": True})
+        gen.spray_step(spray, UPDATE_DELTA, sc)
+
+
+def gpu_material(gen, mat):
+    return gen.spray_material_create(mat["albedo"], mat["dissolve"], {k: mat[k] for k in ("foam_color", "max_alpha", "albedo_srgb", "dissolve_srgb")})
+
+
+def pose_transforms(gen, bodies):
+    """the set's resident pose records as [bodies][24] floats: the transform is the first twelve"""
+    ptr, _, _ = gen.bodies_device_ptrs(bodies)
+    rec = device_read(ptr, bodies.num_bodies, W.BUOYANCY_BODY)
+    return np.frombuffer(rec.tobytes(), np.float32).reshape(bodies.num_bodies, 24).copy()
+
+
+@pytest.mark.gpu
+def test_gpu_body_set_between_a_mesh_draw_and_a_billboard_draw(harness, mesh_harness, billboard_harness):
+    """ow_mesh_draw_async, ow_solid_draw_async on the set's resident poses, ow_billboard_draw_async into the same device buffers, one
+    read-back: the CPU chain (mesh build on the maps, solid build on the pose records, billboard build on ow_spray_read's records), bit for
+    bit.  Body 5 faulted in its first substep: skipped and counted."""
+    gen, params, sc, bodies, spray = floating_scene(broken=5)
+    cam = look(**CRATE_CAM)
+    mat = material()
+    m = gpu_material(gen, mat)
+    water = grid(32, 4.0)
+    mesh = gen.mesh_create(*water)
+    shape = box(CRATE_SHAPE)
+    solid = gen.solid_create(*shape)
+    origin = W.clipmap_origin(cam.position, 4.0)
+    rgba_dev, rec_dev = device_buffers(cam)
+    gen.mesh_draw_async(mesh, cam, origin, sc, rgba_dev, rec_dev)
+    gen.solid_draw_async(solid, bodies, cam, rgba_dev, rec_dev)
+    gen.spray_draw_async(spray, m, cam, rgba_dev, rec_dev)
+    gen.sync()
+    got = buffers_to_host(cam, rgba_dev, rec_dev)
+    stats = gen.solid_draw_stats()
+    d, nm = gpu_maps(gen, 2)
+    bg = cpu_mesh_draw(mesh_harness, d, nm, sc, water, origin, cam)["rec"]
+    tf = pose_transforms(gen, bodies)
+    state = gen.bodies_state(bodies)
+    assert gen.bodies_stats(bodies)["faulted_bodies"] == 1 and np.isfinite(tf[:, :12]).all()
+    assert np.abs(tf[:, 9:12] - state["position"]).max() < 1e-3                         # the pose records are the states'
+    flags = np.zeros(8, np.int32)
+    flags[5] = 1
+    mid = cpu_draw(harness, shape, tf, cam, None, bg, stride=24, flags=flags)
+    inst, _, draw = gen.spray_read(spray)
+    time = float(np.float32(gen.spray_stats(spray)["time"]))
+    want = cpu_billboard_draw(billboard_harness, inst, cam, mat, time=time, order=draw, records=mid["rec"])
+    crates = solid_mask(mid["rec"])
+    print(f"crate pixels {int(crates.sum())} live {len(draw)} drawn triangles {mid['drawn']}")
+    assert crates.sum() > 50 and set(np.unique(mid["rec"]["reserved"][..., 3])) >= {0, 1, 2, 3, 4} and not (mid["rec"]["reserved"][..., 3] == 6).any()
+    same_picture(got, want, "mesh, solids, billboards")
+    assert (stats["skipped_instances"], stats["culled"], stats["drawn"], stats["draws"]) == (1, mid["culled"], mid["drawn"], 1)
+    host_rgba, host_rec = gen.solid_draw(solid, bodies, cam, pixels=bg)                 # the host form, and a part of the set
+    same_picture(dict(rgba=host_rgba, rec=host_rec), mid, "host form")
+    part_rgba, part_rec = gen.solid_draw(solid, bodies, cam, pixels=bg, first=2, count=3)
+    part = cpu_draw(harness, shape, tf[2:5], cam, None, bg, stride=24, flags=flags[2:5])
+    same_picture(dict(rgba=part_rgba, rec=part_rec), part, "bodies 2 .. 4")
+    only_rgba, none = gen.solid_draw(solid, bodies, cam, {"background_color": (0.2, 0.3, 0.4)})
+    flat = cpu_draw(harness, shape, tf, cam, {"background_color": (0.2, 0.3, 0.4)}, None, stride=24, flags=flags)
+    assert none is None and only_rgba.tobytes() == flat["rgba"].tobytes()
+    for bad in (dict(first=-1, count=1), dict(first=6, count=3), dict(first=0, count=-1)):
+        with pytest.raises(_lib.OceanWavesError) as e:
+            gen.solid_draw(solid, bodies, cam, pixels=bg, **bad)
+        assert e.value.status == _lib.OW_ERR_INVALID and "outside" in str(e.value)
+    gen.solid_destroy(solid)
+    gen.spray_material_destroy(m)
+    gen.mesh_destroy(mesh)
+    gen.spray_destroy(spray)
+    gen.bodies_destroy(bodies)
+    gen.free()
+
+
+def _order_case(stream=None, torch_stream=None):
+    """ticks and steps, the mesh draw and the solid draw, then more ticks and steps with no host synchronisation anywhere, against a context
+    that stopped after the first half and drew synchronously: the draw saw the poses and the maps of exactly its point of the stream; the
+    same draw again gives the same bytes"""
+    import torch
+    a, pa, sc, ba, sa = floating_scene(stream=stream, steps=2)
+    b, pb, _, bb, sb = floating_scene(steps=2)
+    cam = look(**dict(CRATE_CAM, width=96, height=64))
+    water = grid(32, 4.0)
+    ha, hb = a.mesh_create(*water), b.mesh_create(*water)
+    shape = box(CRATE_SHAPE)
+    so_a, so_b = a.solid_create(*shape), b.solid_create(*shape)
+    origin = W.clipmap_origin(cam.position, 4.0)
+    rgba_dev, rec_dev = device_buffers(cam)
+    again_rgba, again_rec = device_buffers(cam)
+    a.mesh_draw(ha, cam, origin, sc)                       # the mesh draw's visibility scratch exists from here on
+    torch.cuda.synchronize()
+    advance(a, pa, sc, ba, sa, 4)
+    advance(b, pb, sc, bb, sb, 4)
+    syncs = a.sync_stats()
+    if torch_stream is not None:
+        with torch.cuda.stream(torch_stream):
+            a.mesh_draw_async(ha, cam, origin, sc, rgba_dev, rec_dev)
+            a.solid_draw_async(so_a, ba, cam, rgba_dev, rec_dev)
+            copy = rgba_dev.to("cpu", non_blocking=False)      # the caller's own work, ordered by its stream alone
+    else:
+        a.mesh_draw_async(ha, cam, origin, sc, rgba_dev, rec_dev)
+        a.solid_draw_async(so_a, ba, cam, rgba_dev, rec_dev)
+    a.mesh_draw_async(ha, cam, origin, sc, again_rgba, again_rec)
+    a.solid_draw_async(so_a, ba, cam, again_rgba, again_rec)
+    advance(a, pa, sc, ba, sa, 6)
+    assert a.sync_stats() == syncs                         # no draw synchronised anything (the solid scratch's first allocation included)
+    a.sync()
+    got = buffers_to_host(cam, rgba_dev, rec_dev)
+    same_picture(buffers_to_host(cam, again_rgba, again_rec), got, "repeat")
+    _, bg = b.mesh_draw(hb, cam, origin, sc)
+    want_rgba, want_rec = b.solid_draw(so_b, bb, cam, pixels=bg)
+    same_picture(got, dict(rgba=want_rgba, rec=want_rec), "ordered")
+    if torch_stream is not None:
+        assert copy.numpy().tobytes() == want_rgba.tobytes()
+    assert solid_mask(want_rec).sum() > 20
+    later = a.solid_draw(so_a, ba, cam, pixels=a.mesh_draw(ha, cam, origin, sc)[1])[1]
+    assert later.tobytes() != want_rec.tobytes()            # the second half moved the maps and the crates
+    for g, s, h, so, bd in ((a, sa, ha, so_a, ba), (b, sb, hb, so_b, bb)):
+        g.solid_destroy(so)
+        g.mesh_destroy(h)
+        g.spray_destroy(s)
+        g.bodies_destroy(bd)
+        g.free()
+
+
+@pytest.mark.gpu
+def test_async_draw_is_ordered_behind_a_tick_and_a_body_step_on_the_contexts_stream():
+    _order_case()
+
+
+@pytest.mark.gpu
+def test_async_draw_is_ordered_behind_a_tick_and_a_body_step_on_a_callers_stream():
+    import torch
+    s = torch.cuda.Stream()
+    _order_case(stream=s.cuda_stream, torch_stream=s)
+
+
+@pytest.mark.gpu
+def test_solid_scratch_grows_once_and_stays_and_errors_write_nothing(harness):
+    """the first asynchronous draw allocates without synchronising, the second allocates nothing, a larger image regrows the block behind one
+    synchronisation, every picture is the CPU build's; then the asynchronous form's refusals: nothing is written, no draw is counted"""
+    import torch
+    gen, other = bare_context(), bare_context()
+    st, hull = eight_crates()
+    bodies, foreign_bodies = gen.bodies_create(st, hull), other.bodies_create(st, hull)     # never stepped: the poses of ow_bodies_create
+    shape = box(CRATE_SHAPE)
+    solid, foreign_solid = gen.solid_create(*shape), other.solid_create(*shape)
+    cams = [look(**dict(CRATE_CAM, width=64, height=40)), look(**CRATE_CAM)]
+    bufs = [device_buffers(c) for c in cams]
+    torch.cuda.synchronize()
+    syncs = gen.sync_stats()
+    assert gen.solid_draw_stats(counters=False) == {"draws": 0, "scratch_bytes": 0}
+    assert gen.solid_draw_stats() == {"draws": 0, "skipped_instances": 0, "culled": 0, "drawn": 0, "scratch_bytes": 0} and gen.sync_stats() == syncs
+    gen.solid_draw_async(solid, bodies, cams[0], *bufs[0])
+    held = gen.solid_draw_stats(counters=False)["scratch_bytes"]
+    assert held > 0 and gen.sync_stats() == syncs
+    gen.solid_draw_async(solid, bodies, cams[0], *bufs[0])
+    assert gen.solid_draw_stats(counters=False)["scratch_bytes"] == held and gen.sync_stats() == syncs
+    gen.solid_draw_async(solid, bodies, cams[1], *bufs[1])
+    grown = gen.solid_draw_stats(counters=False)["scratch_bytes"]
+    assert grown > held and gen.sync_stats() == syncs + 1
+    gen.solid_draw_async(solid, bodies, cams[0], *bufs[0])
+    gen.solid_draw_async(solid, bodies, cams[1], *bufs[1])
+    assert gen.solid_draw_stats(counters=False) == {"draws": 5, "scratch_bytes": grown} and gen.sync_stats() == syncs + 1
+    gen.sync()
+    tf = pose_transforms(gen, bodies)
+    for cam, (rgba_dev, rec_dev) in zip(cams, bufs):
+        want = cpu_draw(harness, shape, tf, cam, None, np.zeros((cam.height, cam.width), W.RENDER_PIXEL), stride=24)
+        same_picture(buffers_to_host(cam, rgba_dev, rec_dev), want, cam.width)
+        assert solid_mask(want["rec"]).sum() > 20
+    # the limits: 65536 degenerate triangles a shape take 256 instances (2^24 pairs, all culled) and no more
+    many = gen.solid_create(np.zeros((3, 3), np.float32), np.tile(np.int32([0, 1, 2]), (_lib.OW_SOLID_MAX_TRIANGLES, 1)))
+    small = level_camera(8, 8)
+    gen.solid_draw_instances(many, np.tile(transform(), (256, 1)), small, pixels=blank_records(small))
+    assert gen.solid_draw_stats()["culled"] == 1 << 24
+    with pytest.raises(_lib.OceanWavesError) as e:
+        gen.solid_draw_instances(many, np.tile(transform(), (257, 1)), small, pixels=blank_records(small))
+    assert e.value.status == _lib.OW_ERR_INVALID and "2^24" in str(e.value)
+    gen.solid_destroy(many)
+    # refusals of the asynchronous form
+    draws = gen.solid_draw_stats(counters=False)["draws"]
+    cam = level_camera(20, 12)
+    rgba_dev, rec_dev = device_buffers(cam)
+
+    def refused(*args, status=_lib.OW_ERR_INVALID, **kw):
+        with pytest.raises(_lib.OceanWavesError) as e:
+            gen.solid_draw_async(*args, **kw)
+        assert e.value.status == status
+
+    for bad in ({"near": float("inf")}, {"lane_box": 65}, {"color": (0, float("nan"), 0)}, {"light_direction": (0, 0, 0)}):
+        refused(solid, bodies, cam, rgba_dev, rec_dev, bad)
+    refused(solid, bodies, cam, None, None)
+    refused(solid, bodies, cam, rgba_dev, rec_dev.data_ptr() + 4)          # records are read and written as 16-byte vectors
+    refused(solid, bodies, cam, rgba_dev.data_ptr() + 2, rec_dev)
+    refused(foreign_solid, bodies, cam, rgba_dev, rec_dev)                  # another context's shape
+    refused(solid, foreign_bodies, cam, rgba_dev, rec_dev)                  # another context's body set
+    refused(solid, bodies, cam, rgba_dev, rec_dev, first=7, count=2)
+    refused(solid, bodies, level_camera(0, 12), rgba_dev, rec_dev)
+    torch.cuda.synchronize()
+    assert not rgba_dev.any() and not rec_dev.any() and gen.solid_draw_stats(counters=False)["draws"] == draws
+    # lifetimes: the contexts go first; an orphaned shape or set can be destroyed and is refused by everything else
+    live = bare_context()
+    live_solid = live.solid_create(*shape)
+    live_bodies = live.bodies_create(st, hull)
+    gen.free()
+    other.free()
+    lib = _lib.load()
+    args = (0, 8, C.byref(cam), None, rec_dev.data_ptr(), rgba_dev.data_ptr())
+    assert lib.ow_solid_draw_async(live.context, solid.handle, live_bodies.handle, *args) == _lib.OW_ERR_STATE       # an orphaned shape
+    assert lib.ow_solid_draw_async(live.context, live_solid.handle, bodies.handle, *args) == _lib.OW_ERR_STATE      # an orphaned set
+    assert lib.ow_solid_draw(live.context, solid.handle, live_bodies.handle, *args) == _lib.OW_ERR_STATE
+    one = transform()
+    assert lib.ow_solid_draw_instances(live.context, solid.handle, one.ctypes.data, 1, C.byref(cam), None, rec_dev.data_ptr(), rgba_dev.data_ptr()) == _lib.OW_ERR_STATE
+    assert lib.ow_solid_draw_async(None, solid.handle, bodies.handle, *args) == _lib.OW_ERR_INVALID
+    torch.cuda.synchronize()
+    assert not rgba_dev.any() and not rec_dev.any()
+    for h in (solid, foreign_solid):
+        lib.ow_solid_destroy(None, h.handle)        # still the caller's to destroy; touches no freed memory
+    for h in (bodies, foreign_bodies):
+        lib.ow_bodies_destroy(None, h.handle)
+    live.solid_destroy(live_solid)
+    live.bodies_destroy(live_bodies)
+    live.free()
+
+
+def example_crates():
+    """examples/solid_draw_host.c's crates, operation for operation"""
+    size, rho, per = (2.0, 1.0, 2.0), 1025.0, 4 * 2 * 4
+    volume = size[0] * size[1] * size[2]
+    mass = 0.5 * rho * volume
+    st = np.zeros(36, W.RIGID_BODY)
+    hull = np.zeros(36 * per, W.HULL_POINT)
+    for b in range(36):
+        st[b]["position"] = ((b % 6 - 2.5) * 6.0, 0.3, 10.0 + (b // 6 - 2.5) * 6.0)
+        st[b]["orientation"] = (0, 0, 0, 1)
+        st[b]["mass"] = mass
+        st[b]["inverse_inertia"] = (12.0 / (mass * (size[1] * size[1] + size[2] * size[2])), 12.0 / (mass * (size[0] * size[0] + size[2] * size[2])),
+                                    12.0 / (mass * (size[0] * size[0] + size[1] * size[1])))
+        st[b]["linear_drag"], st[b]["quadratic_drag"] = 3.0, 0.5
+        st[b]["point_offset"], st[b]["point_count"] = b * per, per
+        k = b * per
+        for i in range(4):
+            for j in range(2):
+                for l in range(4):
+                    hull[k]["local"] = ((i + 0.5) * (size[0] / 4) - size[0] / 2, (j + 0.5) * (size[1] / 2) - size[1] / 2, (l + 0.5) * (size[2] / 4) - size[2] / 2)
+                    hull[k]["volume"], hull[k]["half_height"], hull[k]["body"] = volume / per, size[1] / 2 / 2, b
+                    k += 1
+    return st, hull
+
+
+@pytest.mark.gpu
+def test_the_c_example_writes_the_python_wrappers_image(tmp_path):
+    """examples/solid_draw_host.c at 256^2, 96 x 64, 60 steps, 4096 particles, against the wrapper on the same scene"""
+    from test_mesh_draw import REF_BASIS
+    from test_spray_draw import example_textures
+    exe = build_example(tmp_path)
+    ppm = str(tmp_path / "solids.ppm")
+    r = subprocess.run([exe, ppm, "96", "64", "60", "256", "4096"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr
+    kv = dict(p.split("=") for p in r.stdout.split())
+    assert kv["finite"] == "1" and kv["crates"] == "36" and kv["skipped_instances"] == "0"
+    raw = open(ppm, "rb").read()
+    head = b"P6\n96 64\n255\n"
+    assert raw.startswith(head) and len(raw) == len(head) + 96 * 64 * 3
+    gen, params = make_gen(256, [0, 1, 2])
+    sc = scales_of(params)
+    spray = gen.spray_create({"amount": 4096})
+    bodies = gen.bodies_create(*example_crates())
+    for _ in range(60):
+        gen.update_all(UPDATE_DELTA, params)
+        gen.bodies_step(bodies, sc, 4, UPDATE_DELTA / 4, {"warm_start": True})
+        gen.spray_step(spray, UPDATE_DELTA, sc)
+    cam = W.camera((0.0, 10.0, -25.0), REF_BASIS, 75.0, 96, 64, 4000.0)
+    mesh = gen.mesh_create(*grid(128, 4.0))
+    _, bg = gen.mesh_draw(mesh, cam, W.clipmap_origin(cam.position, 4.0), sc, {"falloff": True, "cull_back": True})
+    solid = gen.solid_create(*box(CRATE_SHAPE))
+    _, mid = gen.solid_draw(solid, bodies, cam, pixels=bg)
+    st = gen.solid_draw_stats()
+    m = gen.spray_material_create(*example_textures())
+    rgba, rec = gen.spray_draw(spray, m, cam, pixels=mid)
+    assert np.frombuffer(raw[len(head):], np.uint8).reshape(64, 96, 3).tobytes() == rgba[..., :3].tobytes()
+    assert (int(kv["triangles_culled"]), int(kv["triangles_drawn"])) == (st["culled"], st["drawn"]) and st["culled"] + st["drawn"] == 36 * 12
+    assert int(kv["crate_pixels"]) == int(solid_mask(rec).sum()) > 20
+    assert int(kv["sprayed_pixels"]) == int((rec["reserved"][..., 1] > 0).sum())
+    gen.spray_material_destroy(m)
+    gen.solid_destroy(solid)
+    gen.mesh_destroy(mesh)
+    gen.bodies_destroy(bodies)
+    gen.spray_destroy(spray)
+    gen.free()
