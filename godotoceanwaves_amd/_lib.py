@@ -29,6 +29,11 @@ OW_RAY_HIT, OW_RAY_FROM_BELOW, OW_RAY_TRUNCATED, OW_RAY_INVALID = 1, 2, 4, 8
 OW_RAY_SOLID = 16
 OW_SOLID_TWO_SIDED = 1
 OW_SOLID_MAX_INSTANCES, OW_SOLID_MAX_TRIANGLES = 65536, 65536
+OW_RAY_ENVIRONMENT = 32
+OW_SKY_MAX_SIDE = 8192
+OW_PRESENT_MAX_DOWNSAMPLE = 4
+OW_FOG_EXPONENTIAL, OW_FOG_DEPTH = 0, 1
+OW_TONEMAP_LINEAR, OW_TONEMAP_REINHARD, OW_TONEMAP_FILMIC = 0, 1, 2
 OW_RENDER_MAX_SIDE = 8192
 OW_MESH_CULL_BACK = 1
 OW_MESH_VERTEX_NOT_FINITE = 1
@@ -230,6 +235,24 @@ class ow_solid_options(C.Structure):
                 ("reserved", C.c_uint32 * 14)]
 
 
+class ow_sky_options(C.Structure):
+    """struct ow_sky_options (32 bytes); a NULL pointer = srgb 1, energy 1"""
+    _fields_ = [("srgb", C.c_uint32), ("energy", C.c_float), ("reserved", C.c_uint32 * 6)]
+
+
+class ow_environment_options(C.Structure):
+    """struct ow_environment_options (128 bytes); a NULL pointer = ow_environment_options_default's values (the reference scene's fog)"""
+    _fields_ = [("fog_mode", C.c_int32), ("density", C.c_float), ("depth_begin", C.c_float), ("depth_end", C.c_float), ("depth_curve", C.c_float),
+                ("aerial_perspective", C.c_float), ("sun_scatter", C.c_float), ("flags", C.c_uint32), ("light_color", C.c_float * 3),
+                ("sun_color", C.c_float * 3), ("sun_direction", C.c_float * 3), ("sky_color", C.c_float * 3), ("reserved", C.c_uint32 * 12)]
+
+
+class ow_present_options(C.Structure):
+    """struct ow_present_options (64 bytes); a NULL pointer = ow_present_options_default's values (filmic, sRGB, the scene's adjustments)"""
+    _fields_ = [("downsample", C.c_int32), ("tonemap", C.c_int32), ("exposure", C.c_float), ("white", C.c_float), ("srgb", C.c_uint32),
+                ("brightness", C.c_float), ("contrast", C.c_float), ("saturation", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 7)]
+
+
 class ow_mesh_vertex(C.Structure):
     """struct ow_mesh_vertex (48 bytes): the vertex stage's record of a mesh draw"""
     _fields_ = [("position", C.c_float * 3), ("wave_height", C.c_float), ("uv", C.c_float * 2), ("distance_factor", C.c_float),
@@ -332,6 +355,15 @@ SIGNATURES = {
                                       C.c_void_p]),
     "ow_solid_draw_instances": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, _P(ow_camera), _P(ow_solid_options), C.c_void_p, C.c_void_p]),
     "ow_solid_draw_stats": (C.c_int, [C.c_void_p, _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64)]),
+    "ow_sky_options_default": (None, [_P(ow_sky_options)]),
+    "ow_environment_options_default": (None, [_P(ow_environment_options)]),
+    "ow_present_options_default": (None, [_P(ow_present_options)]),
+    "ow_sky_create": (C.c_int, [C.c_void_p, _P(ow_sky_options), C.c_void_p, C.c_int32, C.c_int32, _P(C.c_void_p)]),
+    "ow_sky_destroy": (None, [C.c_void_p, C.c_void_p]),
+    "ow_environment_apply": (C.c_int, [C.c_void_p, C.c_void_p, _P(ow_camera), _P(ow_environment_options), C.c_void_p]),
+    "ow_environment_apply_async": (C.c_int, [C.c_void_p, C.c_void_p, _P(ow_camera), _P(ow_environment_options), C.c_void_p]),
+    "ow_present": (C.c_int, [C.c_void_p, _P(ow_camera), _P(ow_present_options), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ow_present_async": (C.c_int, [C.c_void_p, _P(ow_camera), _P(ow_present_options), C.c_void_p, C.c_void_p, C.c_void_p]),
     "ow_get_maps_f32": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
     "ow_get_spectrum": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "ow_get_intermediate": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),

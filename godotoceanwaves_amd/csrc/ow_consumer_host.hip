@@ -1,10 +1,10 @@
 // ow_consumer_host.hip -- the read side of include/ocean_waves.h: host wrappers around the kernels of ow_consumer.hip, ow_velocity.hip,
-// ow_mesh.hip, ow_spray.hip, ow_spray_draw.hip and ow_solid.hip (surface samples and queries, buoyancy, floating bodies, ray casts, camera views, mesh draws,
-// the velocity layers, the sea-spray emitter and its billboards, the solids).  Plain C++ over
+// ow_mesh.hip, ow_spray.hip, ow_spray_draw.hip, ow_solid.hip and ow_environment.hip (surface samples and queries, buoyancy, floating bodies, ray casts, camera views, mesh draws,
+// the velocity layers, the sea-spray emitter and its billboards, the solids, the environment pass and the present).  Plain C++ over
 // the HIP runtime API; the context and the scheduler's services come from ow_context.h.  The synchronous calls' device halves (ow_internal.h
 // *_round_trip) also serve a group's gathered arrays (ow_group.hip).
 //
-// Each repeated thing has one owner here.  The five handle kinds (body sets, meshes, emitters, billboard materials, solid shapes) share one life cycle:
+// Each repeated thing has one owner here.  The six handle kinds (body sets, meshes, emitters, billboard materials, solid shapes, skies) share one life cycle:
 // Layout places a block's arrays, new_handle allocates, finish_create synchronises and registers, release_handle is the device half of a
 // destroy, check_handle the one ownership check.  The four picture kinds (views, mesh draws, billboard draws, solid draws) keep their launch in one
 // *_enqueue each, used by the asynchronous form directly and by the synchronous form through picture_round_trip.
@@ -1602,6 +1602,276 @@ ow_status ow_solid_draw_stats(ow_context *c, uint64_t *draws, uint64_t *skipped_
     }
     if (draws) *draws = c->solid_draws;
     if (scratch_bytes) *scratch_bytes = c->solid.bytes;
+    return OW_OK;
+}
+
+}  // extern "C"
+
+/* ---- the environment pass and the present (ow_environment.h, ow_environment.hip) ---- */
+
+namespace {
+void sky_defaults(ow_sky_options *o) {
+    std::memset(o, 0, sizeof(*o));
+    o->srgb = 1u;
+    o->energy = 1.0f;
+}
+// main.tscn:22-41 and the Sun's +Z axis (:113), a white sun of energy 1 as ow_render_options_default's light
+void environment_defaults(ow_environment_options *o) {
+    ow_render_options ro;
+    render_defaults(&ro);
+    std::memset(o, 0, sizeof(*o));
+    o->fog_mode = OW_FOG_DEPTH;
+    o->density = 1.0f;
+    o->depth_begin = 200.0f;
+    o->depth_end = 350.0f;
+    o->depth_curve = 0.25f;
+    o->aerial_perspective = 0.626f;
+    o->sun_scatter = 0.05f;
+    const float fog[3] = {0.272954f, 0.419272f, 0.484632f};
+    for (int k = 0; k < 3; ++k) {
+        o->light_color[k] = fog[k];
+        o->sun_color[k] = ro.light_color[k];
+        o->sun_direction[k] = ro.light_direction[k];
+        o->sky_color[k] = ro.sky_color[k];
+    }
+}
+void present_defaults(ow_present_options *o) {
+    std::memset(o, 0, sizeof(*o));
+    o->downsample = 1;
+    o->tonemap = OW_TONEMAP_FILMIC;
+    o->exposure = 1.0f;
+    o->white = 1.0f;
+    o->srgb = 1u;
+    o->brightness = 0.85f;
+    o->contrast = 1.07f;
+    o->saturation = 1.5f;
+}
+bool in_range(float v, float lo, float hi) { return v >= lo && v <= hi; }  // false for a NaN
+
+ow_status check_sky_options(const ow_sky_options *o) {
+    static_assert(sizeof(ow_sky_options) == sizeof(ow::SkyOptions) && offsetof(ow_sky_options, energy) == offsetof(ow::SkyOptions, energy) &&
+                      OW_SKY_MAX_SIDE == ow::kSkyMaxSide,
+                  "record layout");
+    if (o->srgb > 1u) return fail(OW_ERR_INVALID, "ow_sky_options: srgb is not 0 or 1");
+    if (!in_range(o->energy, 0.0f, ow::kEnvColorMax)) return fail(OW_ERR_INVALID, "ow_sky_options: energy outside [0,1e12]");
+    return check_reserved(o->reserved, "ow_sky_options");
+}
+
+// ow_environment_options (NULL = the defaults) -> the pass's constants; the sky's are filled in by check_environment
+ow_status resolve_environment_options(const ow_environment_options *opts, ow::EnvParams *ep) {
+    static_assert(sizeof(ow_environment_options) == sizeof(ow::EnvironmentOptions) &&
+                      offsetof(ow_environment_options, flags) == offsetof(ow::EnvironmentOptions, flags) &&
+                      offsetof(ow_environment_options, sun_direction) == offsetof(ow::EnvironmentOptions, sun_direction) &&
+                      offsetof(ow_environment_options, reserved) == offsetof(ow::EnvironmentOptions, reserved) && OW_RAY_ENVIRONMENT == ow::kRayEnvironment &&
+                      OW_FOG_EXPONENTIAL == ow::kFogExponential && OW_FOG_DEPTH == ow::kFogDepth,
+                  "record layout");
+    ow_environment_options def;
+    if (!opts) {
+        environment_defaults(&def);
+        opts = &def;
+    }
+    std::memset(ep, 0, sizeof(*ep));
+    if (opts->fog_mode != OW_FOG_EXPONENTIAL && opts->fog_mode != OW_FOG_DEPTH) return fail(OW_ERR_INVALID, "unknown fog_mode %d", opts->fog_mode);
+    if (!in_range(opts->density, 0.0f, ow::kEnvColorMax)) return fail(OW_ERR_INVALID, "ow_environment_options: density outside [0,1e12]");
+    if (!in_range(opts->depth_begin, 0.0f, ow::kEnvColorMax) || !in_range(opts->depth_end, opts->depth_begin, ow::kEnvColorMax))
+        return fail(OW_ERR_INVALID, "ow_environment_options: depth_begin and depth_end must satisfy 0 <= begin <= end <= 1e12");
+    if (!in_range(opts->depth_curve, ow::kEnvCurveMin, ow::kEnvCurveMax)) return fail(OW_ERR_INVALID, "ow_environment_options: depth_curve outside [0.01,100]");
+    if (!in_range(opts->aerial_perspective, 0.0f, 1.0f)) return fail(OW_ERR_INVALID, "ow_environment_options: aerial_perspective outside [0,1]");
+    if (!in_range(opts->sun_scatter, 0.0f, ow::kEnvColorMax)) return fail(OW_ERR_INVALID, "ow_environment_options: sun_scatter outside [0,1e12]");
+    const float *vec[4] = {opts->light_color, opts->sun_color, opts->sun_direction, opts->sky_color};
+    for (const float *v : vec)
+        for (int k = 0; k < 3; ++k)
+            if (!(std::fabs(v[k]) <= ow::kEnvColorMax)) return fail(OW_ERR_INVALID, "ow_environment_options: a colour or the sun direction is not finite (or beyond 1e12)");
+    if (opts->flags != 0u) return fail(OW_ERR_INVALID, "unknown environment flags 0x%x", opts->flags);
+    if (ow_status st = check_reserved(opts->reserved, "ow_environment_options"); st != OW_OK) return st;
+    const double lx = opts->sun_direction[0], ly = opts->sun_direction[1], lz = opts->sun_direction[2];
+    const double len = std::sqrt(lx * lx + ly * ly + lz * lz);
+    if (!(len > 0.0)) return fail(OW_ERR_INVALID, "sun_direction has zero length");
+    ep->fog_mode = opts->fog_mode;
+    ep->density = opts->density;
+    ep->begin = opts->depth_begin;
+    ep->end = opts->depth_end;
+    ep->curve = opts->depth_curve;
+    ep->aerial = opts->aerial_perspective;
+    ep->scatter = opts->sun_scatter;
+    for (int k = 0; k < 3; ++k) {
+        ep->light_color[k] = opts->light_color[k];
+        ep->sun_color[k] = opts->sun_color[k];
+        ep->sun[k] = (float)((double)opts->sun_direction[k] / len);
+        ep->sky_color[k] = opts->sky_color[k];
+    }
+    ep->camera_ok = 1;
+    ep->energy = 1.0f;
+    return OW_OK;
+}
+
+// the argument checks both forms of the pass share: ow_solid_draw's, in its order, then the context and the sky
+ow_status check_environment(const ow_context *c, const ow_sky *sky, const ow_camera *camera, const ow_environment_options *opts, const void *pixels,
+                            ow::CameraParams *cp, ow::EnvParams *ep) {
+    if (!pixels) return fail(OW_ERR_INVALID, "null argument: the records");
+    if (ow_status st = resolve_camera(camera, cp); st != OW_OK) return st;
+    if (ow_status st = resolve_environment_options(opts, ep); st != OW_OK) return st;
+    if (!c) return fail(OW_ERR_INVALID, "null context");
+    if (sky) {
+        if (ow_status st = check_handle(c, sky, "sky"); st != OW_OK) return st;
+        ep->has_sky = 1;
+        ep->sky = sky->tex;
+        ep->srgb = sky->srgb;
+        ep->energy = sky->energy;
+    }
+    ep->camera_ok = ow::mesh_camera_ok(*cp) ? 1 : 0;
+    return OW_OK;
+}
+
+// ow_present_options (NULL = the defaults) -> the present's constants and the output's size
+ow_status resolve_present_options(const ow_present_options *opts, const ow::CameraParams &cp, ow::PresentParams *pp, int *out_width, int *out_height) {
+    static_assert(sizeof(ow_present_options) == sizeof(ow::PresentOptions) && offsetof(ow_present_options, srgb) == offsetof(ow::PresentOptions, srgb) &&
+                      offsetof(ow_present_options, reserved) == offsetof(ow::PresentOptions, reserved) &&
+                      OW_PRESENT_MAX_DOWNSAMPLE == ow::kPresentMaxDownsample && OW_TONEMAP_LINEAR == ow::kTonemapLinear &&
+                      OW_TONEMAP_REINHARD == ow::kTonemapReinhard && OW_TONEMAP_FILMIC == ow::kTonemapFilmic,
+                  "record layout");
+    ow_present_options def;
+    if (!opts) {
+        present_defaults(&def);
+        opts = &def;
+    }
+    if (opts->downsample < 0 || opts->downsample > OW_PRESENT_MAX_DOWNSAMPLE)
+        return fail(OW_ERR_INVALID, "downsample %d outside [0,%d]", opts->downsample, OW_PRESENT_MAX_DOWNSAMPLE);
+    const int s = opts->downsample == 0 ? 1 : opts->downsample;
+    if (cp.width % s != 0 || cp.height % s != 0) return fail(OW_ERR_INVALID, "downsample %d does not divide %d x %d", s, cp.width, cp.height);
+    if (opts->tonemap < OW_TONEMAP_LINEAR || opts->tonemap > OW_TONEMAP_FILMIC) return fail(OW_ERR_INVALID, "unknown tonemap %d", opts->tonemap);
+    if (!in_range(opts->exposure, 0.0f, ow::kPresentScaleMax)) return fail(OW_ERR_INVALID, "ow_present_options: exposure outside [0,1e6]");
+    if (!in_range(opts->white, ow::kPresentWhiteMin, ow::kPresentScaleMax)) return fail(OW_ERR_INVALID, "ow_present_options: white outside [0.01,1e6]");
+    if (opts->srgb > 1u) return fail(OW_ERR_INVALID, "ow_present_options: srgb is not 0 or 1");
+    if (!in_range(opts->brightness, 0.0f, ow::kPresentAdjustMax) || !in_range(opts->contrast, 0.0f, ow::kPresentAdjustMax) ||
+        !in_range(opts->saturation, 0.0f, ow::kPresentAdjustMax))
+        return fail(OW_ERR_INVALID, "ow_present_options: brightness, contrast or saturation outside [0,8]");
+    if (opts->flags != 0u) return fail(OW_ERR_INVALID, "unknown present flags 0x%x", opts->flags);
+    if (ow_status st = check_reserved(opts->reserved, "ow_present_options"); st != OW_OK) return st;
+    pp->s = s;
+    pp->inv = 1.0f / (float)(s * s);
+    pp->tonemap = opts->tonemap;
+    pp->exposure = opts->exposure;
+    pp->white = opts->white;
+    pp->srgb = (int)opts->srgb;
+    pp->brightness = opts->brightness;
+    pp->contrast = opts->contrast;
+    pp->saturation = opts->saturation;
+    *out_width = cp.width / s;
+    *out_height = cp.height / s;
+    return OW_OK;
+}
+
+// the argument checks both forms of the present share: outputs and records, camera, options, context
+ow_status check_present(const ow_context *c, const ow_camera *camera, const ow_present_options *opts, const void *pixels, const void *rgba, const void *linear,
+                        ow::CameraParams *cp, ow::PresentParams *pp, int *out_width, int *out_height) {
+    if (!rgba && !linear) return fail(OW_ERR_INVALID, "null argument: both outputs");
+    if (!pixels) return fail(OW_ERR_INVALID, "null argument: the records");
+    if (ow_status st = resolve_camera(camera, cp); st != OW_OK) return st;
+    if (ow_status st = resolve_present_options(opts, *cp, pp, out_width, out_height); st != OW_OK) return st;
+    if (!c) return fail(OW_ERR_INVALID, "null context");
+    return OW_OK;
+}
+}  // namespace
+
+extern "C" {
+
+void ow_sky_options_default(ow_sky_options *out) {
+    if (out) sky_defaults(out);
+}
+void ow_environment_options_default(ow_environment_options *out) {
+    if (out) environment_defaults(out);
+}
+void ow_present_options_default(ow_present_options *out) {
+    if (out) present_defaults(out);
+}
+
+ow_status ow_sky_create(ow_context *c, const ow_sky_options *opts, const void *rgba8, int32_t width, int32_t height, ow_sky **out) {
+    if (!out) return fail(OW_ERR_INVALID, "null argument");
+    ow_sky_options def;
+    if (!opts) {
+        sky_defaults(&def);
+        opts = &def;
+    }
+    if (width < 1 || width > OW_SKY_MAX_SIDE || height < 1 || height > OW_SKY_MAX_SIDE)
+        return fail(OW_ERR_INVALID, "panorama size %d x %d outside [1,%d]", width, height, OW_SKY_MAX_SIDE);
+    if (ow_status st = check_sky_options(opts); st != OW_OK) return st;
+    if (!rgba8) return fail(OW_ERR_INVALID, "null argument");
+    if (!c) return fail(OW_ERR_INVALID, "null context");
+    float table[256];
+    ow::spray_srgb_table(table);
+    const size_t bytes = (size_t)width * height * 4;
+    Layout L;
+    const size_t t_off = L.take(sizeof(table)), p_off = L.take(bytes);
+    ow_sky *sky;
+    if (ow_status st = new_handle(c, L.total, "panorama", &sky); st != OW_OK) return st;
+    char *base = (char *)sky->block;
+    sky->srgb = (const float *)(base + t_off);
+    sky->tex = ow::SprayTexture{(const uint32_t *)(base + p_off), width, height, (int)opts->srgb};
+    sky->energy = opts->energy;
+    hipStream_t s = main_stream(c);
+    const bool enqueued = hipMemcpyAsync((void *)sky->srgb, table, sizeof(table), hipMemcpyHostToDevice, s) == hipSuccess &&
+                          hipMemcpyAsync((void *)sky->tex.texels, rgba8, bytes, hipMemcpyHostToDevice, s) == hipSuccess;
+    return finish_create(c, sky, s, enqueued, "panorama upload", out);
+}
+
+void ow_sky_destroy(ow_context *, ow_sky *sky) {
+    if (sky) release_handle(sky);
+    delete sky;
+}
+
+ow_status ow_environment_apply(ow_context *c, ow_sky *sky, const ow_camera *camera, const ow_environment_options *opts, ow_render_pixel *pixels_inout) {
+    ow::CameraParams cp;
+    ow::EnvParams ep;
+    if (ow_status st = check_environment(c, sky, camera, opts, pixels_inout, &cp, &ep); st != OW_OK) return st;
+    OW_HIP(hipSetDevice(c->device));
+    return picture_round_trip(c, (size_t)cp.width * cp.height, nullptr, pixels_inout, true, 0, [&](uint32_t *, ow::RenderPixel *pixels_dev) {
+        OW_HIP(ow::launch_environment_apply(cp, ep, pixels_dev, main_stream(c)));
+        return OW_OK;
+    });
+}
+
+ow_status ow_environment_apply_async(ow_context *c, ow_sky *sky, const ow_camera *camera, const ow_environment_options *opts, ow_render_pixel *pixels_dev) {
+    ow::CameraParams cp;
+    ow::EnvParams ep;
+    if (ow_status st = check_environment(c, sky, camera, opts, pixels_dev, &cp, &ep); st != OW_OK) return st;
+    if (ow_status st = check_pixel_alignment(nullptr, pixels_dev); st != OW_OK) return st;
+    OW_HIP(hipSetDevice(c->device));
+    OW_HIP(ow::launch_environment_apply(cp, ep, (ow::RenderPixel *)pixels_dev, main_stream(c)));
+    return OW_OK;
+}
+
+ow_status ow_present(ow_context *c, const ow_camera *camera, const ow_present_options *opts, const ow_render_pixel *pixels_in, void *rgba8_out,
+                     float *linear_out) {
+    ow::CameraParams cp;
+    ow::PresentParams pp;
+    int ow_ = 0, oh = 0;
+    if (ow_status st = check_present(c, camera, opts, pixels_in, rgba8_out, linear_out, &cp, &pp, &ow_, &oh); st != OW_OK) return st;
+    OW_HIP(hipSetDevice(c->device));
+    const size_t in_count = (size_t)cp.width * cp.height, out_count = (size_t)ow_ * oh;
+    if (ow_status st = c->render_pixels.ensure(in_count * sizeof(ow::RenderPixel), 0, sizeof(ow::RenderPixel), "pixel records"); st != OW_OK) return st;
+    if (ow_status st = c->render_rgba.ensure(out_count * (4 * sizeof(float) + sizeof(uint32_t)), 0, sizeof(uint32_t), "pixels"); st != OW_OK) return st;
+    hipStream_t s = main_stream(c);
+    ow::RenderPixel *pixels_dev = (ow::RenderPixel *)c->render_pixels.ptr;
+    float *linear_dev = (float *)c->render_rgba.ptr;
+    uint32_t *rgba_dev = (uint32_t *)(linear_dev + 4 * out_count);
+    OW_HIP(hipMemcpyAsync(pixels_dev, pixels_in, in_count * sizeof(ow::RenderPixel), hipMemcpyHostToDevice, s));
+    OW_HIP(ow::launch_present(ow_, oh, pp, pixels_dev, rgba8_out ? rgba_dev : nullptr, linear_out ? linear_dev : nullptr, s));
+    if (rgba8_out) OW_HIP(hipMemcpyAsync(rgba8_out, rgba_dev, out_count * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    if (linear_out) OW_HIP(hipMemcpyAsync(linear_out, linear_dev, out_count * 4 * sizeof(float), hipMemcpyDeviceToHost, s));
+    return sync_stream(c, 0);
+}
+
+ow_status ow_present_async(ow_context *c, const ow_camera *camera, const ow_present_options *opts, const ow_render_pixel *pixels_dev, void *rgba8_dev,
+                           float *linear_dev) {
+    ow::CameraParams cp;
+    ow::PresentParams pp;
+    int ow_ = 0, oh = 0;
+    if (ow_status st = check_present(c, camera, opts, pixels_dev, rgba8_dev, linear_dev, &cp, &pp, &ow_, &oh); st != OW_OK) return st;
+    if (ow_status st = check_pixel_alignment(rgba8_dev, pixels_dev); st != OW_OK) return st;
+    if ((uintptr_t)linear_dev & 15u) return fail(OW_ERR_INVALID, "linear_dev must be 16-byte aligned");
+    OW_HIP(hipSetDevice(c->device));
+    OW_HIP(ow::launch_present(ow_, oh, pp, (const ow::RenderPixel *)pixels_dev, (uint32_t *)rgba8_dev, linear_dev, main_stream(c)));
     return OW_OK;
 }
 

@@ -52,6 +52,13 @@ struct ow_solid : ow::Handle {
     int num_vertices = 0, num_triangles = 0;
 };
 
+// a panorama sky (ow_sky_create): the block holds the sRGB table and the texels
+struct ow_sky : ow::Handle {
+    ow::SprayTexture tex{};
+    const float *srgb = nullptr;
+    float energy = 1.0f;
+};
+
 struct ow_context {
     int n = 0, cascades = 0, layers = 0, device = 0;
     float depth = 20.0f;
@@ -169,6 +176,8 @@ struct ow_context {
     // records of the synchronous ow_render_view, ow_mesh_draw and ow_billboard_draw; mesh_vis: the draw's visibility words (both forms);
     // billboard: a billboard draw's counters, bin masks, sprite records and (ow_billboard_draw_instances) the uploaded instances;
     // solid: a solid draw's counters, transformed vertex records, visibility words and (ow_solid_draw_instances) the uploaded transforms.
+    // The synchronous ow_environment_apply uses render_pixels; the synchronous ow_present render_pixels for the records and render_rgba for both
+    // outputs (the float4 pixels first, then the RGBA8 words).  Their asynchronous forms use no scratch.
     ow::DeviceScratch query_scratch, buoy_scratch, ray_scratch, render_rgba, render_pixels, mesh_vis, billboard, solid;
     uint64_t billboard_draws = 0;  // ow_billboard_draw_stats
     uint64_t solid_draws = 0;      // ow_solid_draw_stats

@@ -5,6 +5,7 @@
 
 #include "ow_device.h"
 #include "ow_buoyancy.h"
+#include "ow_environment.h"
 #include "ow_raycast.h"
 #include "ow_mesh.h"
 #include "ow_render.h"
@@ -142,6 +143,14 @@ struct SolidArrays {
 // drawn) and / or the RGBA8 words (either may be null), all on `s`
 hipError_t launch_solid_draw(const SolidArrays &A, const SolidInstances &in, const CameraParams &cam, const SolidParams &sp, uint32_t *rgba_dev,
                              RenderPixel *pixels_dev, hipStream_t s);
+
+// the environment pass and the present (ow_environment.hip; the sky, the fog, the resolve, the tonemap and the transfer curve in ow_environment.h)
+// k_environment_apply over cam.width x cam.height records, rewritten in place, on `s`; nothing is launched for a camera that is not finite
+hipError_t launch_environment_apply(const CameraParams &cam, const EnvParams &ep, RenderPixel *pixels_dev, hipStream_t s);
+// k_present<pp.s> over out_width x out_height output pixels of (out_width pp.s) x (out_height pp.s) records, into RGBA8 words and / or float4
+// linear pixels (either may be null), on `s`
+hipError_t launch_present(int out_width, int out_height, const PresentParams &pp, const RenderPixel *pixels_dev, uint32_t *rgba_dev, float *linear_dev,
+                          hipStream_t s);
 
 bool supported_map_size(int n);
 int kernel_family(int n, int slots, int mode);  // 1 standard, 2 layer-parallel, 3 compact: what launch_pass1/2 will use
