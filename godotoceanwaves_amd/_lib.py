@@ -30,6 +30,8 @@ OW_RAY_SOLID = 16
 OW_SOLID_TWO_SIDED = 1
 OW_SOLID_MAX_INSTANCES, OW_SOLID_MAX_TRIANGLES = 65536, 65536
 OW_RAY_ENVIRONMENT = 32
+OW_RAY_SKY_LIT = 64
+OW_RADIANCE_MAX_LEVELS, OW_RADIANCE_MAX_SAMPLES, OW_RADIANCE_IRRADIANCE = 8, 256, -1
 OW_SKY_MAX_SIDE = 8192
 OW_PRESENT_MAX_DOWNSAMPLE = 4
 OW_FOG_EXPONENTIAL, OW_FOG_DEPTH = 0, 1
@@ -253,6 +255,17 @@ class ow_present_options(C.Structure):
                 ("brightness", C.c_float), ("contrast", C.c_float), ("saturation", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 7)]
 
 
+class ow_radiance_options(C.Structure):
+    """struct ow_radiance_options (32 bytes); a NULL pointer = levels 6, samples 64, base_width 1024"""
+    _fields_ = [("levels", C.c_int32), ("samples", C.c_int32), ("base_width", C.c_int32), ("reserved", C.c_uint32 * 5)]
+
+
+class ow_radiance_light_options(C.Structure):
+    """struct ow_radiance_light_options (64 bytes); a NULL pointer = ambient_energy 1, reflection_energy 1, specular 0.5"""
+    _fields_ = [("ambient_energy", C.c_float), ("reflection_energy", C.c_float), ("specular", C.c_float), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32 * 12)]
+
+
 class ow_mesh_vertex(C.Structure):
     """struct ow_mesh_vertex (48 bytes): the vertex stage's record of a mesh draw"""
     _fields_ = [("position", C.c_float * 3), ("wave_height", C.c_float), ("uv", C.c_float * 2), ("distance_factor", C.c_float),
@@ -364,6 +377,13 @@ SIGNATURES = {
     "ow_environment_apply_async": (C.c_int, [C.c_void_p, C.c_void_p, _P(ow_camera), _P(ow_environment_options), C.c_void_p]),
     "ow_present": (C.c_int, [C.c_void_p, _P(ow_camera), _P(ow_present_options), C.c_void_p, C.c_void_p, C.c_void_p]),
     "ow_present_async": (C.c_int, [C.c_void_p, _P(ow_camera), _P(ow_present_options), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ow_radiance_options_default": (None, [_P(ow_radiance_options)]),
+    "ow_radiance_light_options_default": (None, [_P(ow_radiance_light_options)]),
+    "ow_radiance_create": (C.c_int, [C.c_void_p, C.c_void_p, _P(ow_radiance_options), _P(C.c_void_p)]),
+    "ow_radiance_destroy": (None, [C.c_void_p, C.c_void_p]),
+    "ow_radiance_level": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), C.c_void_p]),
+    "ow_radiance_light_apply": (C.c_int, [C.c_void_p, C.c_void_p, _P(ow_camera), _P(ow_radiance_light_options), C.c_void_p]),
+    "ow_radiance_light_apply_async": (C.c_int, [C.c_void_p, C.c_void_p, _P(ow_camera), _P(ow_radiance_light_options), C.c_void_p]),
     "ow_get_maps_f32": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
     "ow_get_spectrum": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "ow_get_intermediate": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),

@@ -1,10 +1,10 @@
 // ow_consumer_host.hip -- the read side of include/ocean_waves.h: host wrappers around the kernels of ow_consumer.hip, ow_velocity.hip,
-// ow_mesh.hip, ow_spray.hip, ow_spray_draw.hip, ow_solid.hip and ow_environment.hip (surface samples and queries, buoyancy, floating bodies, ray casts, camera views, mesh draws,
-// the velocity layers, the sea-spray emitter and its billboards, the solids, the environment pass and the present).  Plain C++ over
+// ow_mesh.hip, ow_spray.hip, ow_spray_draw.hip, ow_solid.hip, ow_environment.hip and ow_sky_light.hip (surface samples and queries, buoyancy, floating bodies, ray casts, camera views, mesh draws,
+// the velocity layers, the sea-spray emitter and its billboards, the solids, the environment pass, the present, the radiance pyramid and its pass).  Plain C++ over
 // the HIP runtime API; the context and the scheduler's services come from ow_context.h.  The synchronous calls' device halves (ow_internal.h
 // *_round_trip) also serve a group's gathered arrays (ow_group.hip).
 //
-// Each repeated thing has one owner here.  The six handle kinds (body sets, meshes, emitters, billboard materials, solid shapes, skies) share one life cycle:
+// Each repeated thing has one owner here.  The seven handle kinds (body sets, meshes, emitters, billboard materials, solid shapes, skies, radiance pyramids) share one life cycle:
 // Layout places a block's arrays, new_handle allocates, finish_create synchronises and registers, release_handle is the device half of a
 // destroy, check_handle the one ownership check.  The four picture kinds (views, mesh draws, billboard draws, solid draws) keep their launch in one
 // *_enqueue each, used by the asynchronous form directly and by the synchronous form through picture_round_trip.
@@ -1872,6 +1872,221 @@ ow_status ow_present_async(ow_context *c, const ow_camera *camera, const ow_pres
     if ((uintptr_t)linear_dev & 15u) return fail(OW_ERR_INVALID, "linear_dev must be 16-byte aligned");
     OW_HIP(hipSetDevice(c->device));
     OW_HIP(ow::launch_present(ow_, oh, pp, (const ow::RenderPixel *)pixels_dev, (uint32_t *)rgba8_dev, linear_dev, main_stream(c)));
+    return OW_OK;
+}
+
+}  // extern "C"
+
+/* ---- light from the sky: the radiance pyramid and its pass (ow_sky_light.h, ow_sky_light.hip) ---- */
+
+namespace {
+void radiance_defaults(ow_radiance_options *o) {
+    std::memset(o, 0, sizeof(*o));
+    o->levels = ow::kRadianceDefaultLevels;
+    o->samples = ow::kRadianceDefaultSamples;
+    o->base_width = ow::kRadianceDefaultBase;
+}
+void radiance_light_defaults(ow_radiance_light_options *o) {
+    std::memset(o, 0, sizeof(*o));
+    o->ambient_energy = 1.0f;
+    o->reflection_energy = 1.0f;
+    o->specular = 0.5f;
+}
+
+// ow_radiance_options with the zeros resolved
+ow_status resolve_radiance_options(const ow_radiance_options *opts, int *levels, int *samples, int *base_width) {
+    static_assert(sizeof(ow_radiance_options) == sizeof(ow::RadianceOptions) && offsetof(ow_radiance_options, base_width) == offsetof(ow::RadianceOptions, base_width) &&
+                      OW_RADIANCE_MAX_LEVELS == ow::kRadianceMaxLevels && OW_RADIANCE_MAX_SAMPLES == ow::kRadianceMaxSamples &&
+                      OW_RADIANCE_IRRADIANCE == ow::kRadianceIrradiance,
+                  "record layout");
+    ow_radiance_options def;
+    if (!opts) {
+        radiance_defaults(&def);
+        opts = &def;
+    }
+    *levels = opts->levels == 0 ? ow::kRadianceDefaultLevels : opts->levels;
+    *samples = opts->samples == 0 ? ow::kRadianceDefaultSamples : opts->samples;
+    *base_width = opts->base_width == 0 ? ow::kRadianceDefaultBase : opts->base_width;
+    if (*levels < 2 || *levels > OW_RADIANCE_MAX_LEVELS) return fail(OW_ERR_INVALID, "ow_radiance_options: levels %d outside [2,%d]", opts->levels, OW_RADIANCE_MAX_LEVELS);
+    if (*samples < 1 || *samples > OW_RADIANCE_MAX_SAMPLES)
+        return fail(OW_ERR_INVALID, "ow_radiance_options: samples %d outside [1,%d]", opts->samples, OW_RADIANCE_MAX_SAMPLES);
+    if (*base_width < ow::kRadianceMinBase || *base_width > ow::kRadianceMaxBase || (*base_width & (*base_width - 1)))
+        return fail(OW_ERR_INVALID, "ow_radiance_options: base_width %d is not a power of two in [%d,%d]", opts->base_width, ow::kRadianceMinBase, ow::kRadianceMaxBase);
+    return check_reserved(opts->reserved, "ow_radiance_options");
+}
+
+// ow_radiance_light_options (NULL = the defaults) -> the pass's constants; the pyramid's are filled in by check_radiance_light
+ow_status resolve_radiance_light_options(const ow_radiance_light_options *opts, ow::SkyLightParams *lp) {
+    static_assert(sizeof(ow_radiance_light_options) == sizeof(ow::SkyLightOptions) &&
+                      offsetof(ow_radiance_light_options, flags) == offsetof(ow::SkyLightOptions, flags) &&
+                      offsetof(ow_radiance_light_options, reserved) == offsetof(ow::SkyLightOptions, reserved) && OW_RAY_SKY_LIT == ow::kRaySkyLit,
+                  "record layout");
+    ow_radiance_light_options def;
+    if (!opts) {
+        radiance_light_defaults(&def);
+        opts = &def;
+    }
+    std::memset(lp, 0, sizeof(*lp));
+    if (!in_range(opts->ambient_energy, 0.0f, ow::kSkyLightEnergyMax)) return fail(OW_ERR_INVALID, "ow_radiance_light_options: ambient_energy outside [0,1e12]");
+    if (!in_range(opts->reflection_energy, 0.0f, ow::kSkyLightEnergyMax))
+        return fail(OW_ERR_INVALID, "ow_radiance_light_options: reflection_energy outside [0,1e12]");
+    if (!in_range(opts->specular, 0.0f, 1.0f)) return fail(OW_ERR_INVALID, "ow_radiance_light_options: specular outside [0,1]");
+    if (opts->flags != 0u) return fail(OW_ERR_INVALID, "unknown radiance light flags 0x%x", opts->flags);
+    if (ow_status st = check_reserved(opts->reserved, "ow_radiance_light_options"); st != OW_OK) return st;
+    lp->ambient_energy = opts->ambient_energy;
+    lp->reflection_energy = opts->reflection_energy;
+    ow::sky_light_fresnel(opts->specular, lp->f0, lp->f50);
+    lp->camera_ok = 1;
+    return OW_OK;
+}
+
+// the argument checks both forms of the pass share: ow_environment_apply's, in its order, then the context and the pyramid
+ow_status check_radiance_light(const ow_context *c, const ow_radiance *radiance, const ow_camera *camera, const ow_radiance_light_options *opts,
+                               const void *pixels, ow::CameraParams *cp, ow::SkyLightParams *lp) {
+    if (!pixels) return fail(OW_ERR_INVALID, "null argument: the records");
+    if (ow_status st = resolve_camera(camera, cp); st != OW_OK) return st;
+    if (ow_status st = resolve_radiance_light_options(opts, lp); st != OW_OK) return st;
+    if (ow_status st = check_handle(c, radiance, "radiance pyramid"); st != OW_OK) return st;
+    lp->levels = radiance->plan.levels;
+    for (int k = 0; k < radiance->plan.levels; ++k) lp->R[k] = radiance->R[k];
+    lp->E = radiance->E;
+    lp->camera_ok = ow::mesh_camera_ok(*cp) ? 1 : 0;
+    return OW_OK;
+}
+}  // namespace
+
+extern "C" {
+
+void ow_radiance_options_default(ow_radiance_options *out) {
+    if (out) radiance_defaults(out);
+}
+void ow_radiance_light_options_default(ow_radiance_light_options *out) {
+    if (out) radiance_light_defaults(out);
+}
+
+ow_status ow_radiance_create(ow_context *c, ow_sky *sky, const ow_radiance_options *opts, ow_radiance **out) {
+    if (!out) return fail(OW_ERR_INVALID, "null argument");
+    int levels, samples, base_width;
+    if (ow_status st = resolve_radiance_options(opts, &levels, &samples, &base_width); st != OW_OK) return st;
+    if (ow_status st = check_handle(c, sky, "sky"); st != OW_OK) return st;
+    ow::RadianceBuild b;
+    std::memset(&b, 0, sizeof(b));
+    ow::RadiancePlan &p = b.plan;
+    if (!ow::radiance_plan(sky->tex.width, sky->tex.height, levels, base_width, &p))
+        return fail(OW_ERR_INVALID, "a %d x %d panorama has no %d exact levels at least 2 texels wide under base_width %d", sky->tex.width, sky->tex.height, levels,
+                    base_width);
+    p.samples = samples;
+    // the block: R_0 (= M_0), R_1 .., M_1 .., E, then the host's tables in one piece (uploaded with one copy)
+    constexpr size_t kTexel = 4 * sizeof(float);
+    Layout L;
+    size_t r_off[ow::kRadianceMaxLevels], m_off[ow::kRadianceMaxChain];
+    for (int k = 0; k < levels; ++k) r_off[k] = L.take((size_t)p.width[k] * p.height[k] * kTexel);
+    m_off[0] = r_off[0];
+    for (int k = 1; k < p.chain; ++k) m_off[k] = L.take((size_t)p.width[k] * p.height[k] * kTexel);
+    const size_t e_off = L.take((size_t)ow::kIrradianceWidth * ow::kIrradianceHeight * kTexel);
+    std::vector<float> tables;
+    const auto table = [&](size_t floats) {  // the offset, in floats, of a table; each starts 16-byte aligned
+        const size_t at = tables.size();
+        tables.resize(at + ((floats + 3) & ~(size_t)3));
+        return at;
+    };
+    size_t col_at[ow::kRadianceMaxChain], row_at[ow::kRadianceMaxChain], smp_at[ow::kRadianceMaxLevels] = {};
+    for (int k = 0; k < p.chain; ++k) {
+        col_at[k] = table(2 * (size_t)p.width[k]);
+        ow::radiance_dir_table(p.width[k], false, tables.data() + col_at[k]);
+        row_at[k] = table(2 * (size_t)p.height[k]);
+        ow::radiance_dir_table(p.height[k], true, tables.data() + row_at[k]);
+    }
+    for (int k = 1; k < levels; ++k) {
+        smp_at[k] = table(4 * (size_t)samples);
+        ow::radiance_sample_table((double)k / (double)(levels - 1), samples, tables.data() + smp_at[k]);
+    }
+    const size_t ecol_at = table(2 * ow::kIrradianceWidth), erow_at = table(2 * ow::kIrradianceHeight);
+    ow::radiance_dir_table(ow::kIrradianceWidth, false, tables.data() + ecol_at);
+    ow::radiance_dir_table(ow::kIrradianceHeight, true, tables.data() + erow_at);
+    const size_t t_off = L.take(tables.size() * sizeof(float));
+    ow_radiance *r;
+    if (ow_status st = new_handle(c, L.total, "radiance pyramid", &r); st != OW_OK) return st;
+    char *base = (char *)r->block;
+    const float *tab = (const float *)(base + t_off);
+    r->plan = p;
+    for (int k = 0; k < levels; ++k) {
+        b.R[k] = (float *)(base + r_off[k]);
+        b.samples[k] = tab + smp_at[k];
+        r->R[k] = ow::RadianceLevel{b.R[k], p.width[k], p.height[k]};
+    }
+    for (int k = 0; k < p.chain; ++k) {
+        b.M[k] = (float *)(base + m_off[k]);
+        b.col[k] = tab + col_at[k];
+        b.row[k] = tab + row_at[k];
+    }
+    b.E = (float *)(base + e_off);
+    b.ecol = tab + ecol_at;
+    b.erow = tab + erow_at;
+    r->E = ow::RadianceLevel{b.E, ow::kIrradianceWidth, ow::kIrradianceHeight};
+    b.sky = sky->tex;
+    b.srgb = sky->srgb;
+    b.energy = sky->energy;
+    // the sizes above level 0's live in a block of their own, freed behind the create's one synchronisation
+    void *pre = nullptr;
+    if (p.pre > 0) {
+        Layout PL;
+        size_t off[16];
+        int w = sky->tex.width, h = sky->tex.height;
+        for (int i = 0; i < p.pre; ++i, w /= 2, h /= 2) off[i] = PL.take((size_t)w * h * kTexel);
+        if (hipMalloc(&pre, PL.total) != hipSuccess) {
+            (void)hipGetLastError();
+            (void)hipFree(r->block);
+            delete r;
+            return fail(OW_ERR_NOMEM, "hipMalloc failed for %zu bytes of radiance scratch", PL.total);
+        }
+        for (int i = 0; i < p.pre; ++i) b.pre[i] = (float *)((char *)pre + off[i]);
+    }
+    hipStream_t s = main_stream(c);
+    const bool enqueued = hipMemcpyAsync(base + t_off, tables.data(), tables.size() * sizeof(float), hipMemcpyHostToDevice, s) == hipSuccess &&
+                          ow::launch_radiance_build(b, s) == hipSuccess;
+    const ow_status st = finish_create(c, r, s, enqueued, "radiance build", out);  // synchronises: `tables` and `pre` are done with
+    if (pre) (void)hipFree(pre);
+    return st;
+}
+
+void ow_radiance_destroy(ow_context *, ow_radiance *radiance) {
+    if (radiance) release_handle(radiance);
+    delete radiance;
+}
+
+ow_status ow_radiance_level(ow_context *c, ow_radiance *radiance, int32_t level, int32_t *levels, int32_t *width, int32_t *height, float *texels_out) {
+    if (ow_status st = check_handle(c, radiance, "radiance pyramid"); st != OW_OK) return st;
+    if (level != OW_RADIANCE_IRRADIANCE && (level < 0 || level >= radiance->plan.levels))
+        return fail(OW_ERR_INVALID, "level %d outside [0,%d) and not OW_RADIANCE_IRRADIANCE", level, radiance->plan.levels);
+    const ow::RadianceLevel &t = level == OW_RADIANCE_IRRADIANCE ? radiance->E : radiance->R[level];
+    if (levels) *levels = radiance->plan.levels;
+    if (width) *width = t.width;
+    if (height) *height = t.height;
+    if (!texels_out) return OW_OK;
+    return read_back(c, texels_out, t.texels, (size_t)t.width * t.height * 4 * sizeof(float));
+}
+
+ow_status ow_radiance_light_apply(ow_context *c, ow_radiance *radiance, const ow_camera *camera, const ow_radiance_light_options *opts,
+                                  ow_render_pixel *pixels_inout) {
+    ow::CameraParams cp;
+    ow::SkyLightParams lp;
+    if (ow_status st = check_radiance_light(c, radiance, camera, opts, pixels_inout, &cp, &lp); st != OW_OK) return st;
+    OW_HIP(hipSetDevice(c->device));
+    return picture_round_trip(c, (size_t)cp.width * cp.height, nullptr, pixels_inout, true, 0, [&](uint32_t *, ow::RenderPixel *pixels_dev) {
+        OW_HIP(ow::launch_sky_light_apply(cp, lp, pixels_dev, main_stream(c)));
+        return OW_OK;
+    });
+}
+
+ow_status ow_radiance_light_apply_async(ow_context *c, ow_radiance *radiance, const ow_camera *camera, const ow_radiance_light_options *opts,
+                                        ow_render_pixel *pixels_dev) {
+    ow::CameraParams cp;
+    ow::SkyLightParams lp;
+    if (ow_status st = check_radiance_light(c, radiance, camera, opts, pixels_dev, &cp, &lp); st != OW_OK) return st;
+    if (ow_status st = check_pixel_alignment(nullptr, pixels_dev); st != OW_OK) return st;
+    OW_HIP(hipSetDevice(c->device));
+    OW_HIP(ow::launch_sky_light_apply(cp, lp, (ow::RenderPixel *)pixels_dev, main_stream(c)));
     return OW_OK;
 }
 

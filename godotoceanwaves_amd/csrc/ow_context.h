@@ -59,6 +59,13 @@ struct ow_sky : ow::Handle {
     float energy = 1.0f;
 };
 
+// a radiance pyramid (ow_radiance_create): the block holds the levels, the irradiance, the unblurred chain and the host's tables
+struct ow_radiance : ow::Handle {
+    ow::RadiancePlan plan{};
+    ow::RadianceLevel R[ow::kRadianceMaxLevels] = {};
+    ow::RadianceLevel E{};
+};
+
 struct ow_context {
     int n = 0, cascades = 0, layers = 0, device = 0;
     float depth = 20.0f;

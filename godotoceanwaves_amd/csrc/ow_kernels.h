@@ -10,6 +10,7 @@
 #include "ow_mesh.h"
 #include "ow_render.h"
 #include "ow_rigid.h"
+#include "ow_sky_light.h"
 #include "ow_solid.h"
 #include "ow_spray.h"
 #include "ow_spray_draw.h"
@@ -151,6 +152,12 @@ hipError_t launch_environment_apply(const CameraParams &cam, const EnvParams &ep
 // linear pixels (either may be null), on `s`
 hipError_t launch_present(int out_width, int out_height, const PresentParams &pp, const RenderPixel *pixels_dev, uint32_t *rgba_dev, float *linear_dev,
                           hipStream_t s);
+
+// light from the sky (ow_sky_light.hip; the pyramid's and the pass's arithmetic in ow_sky_light.h)
+// k_radiance_decode, k_radiance_box down the sizes, k_radiance_prefilter per level from 1 on and k_radiance_irradiance, all on `s`
+hipError_t launch_radiance_build(const RadianceBuild &b, hipStream_t s);
+// k_sky_light_apply over cam.width x cam.height records, rewritten in place, on `s`; nothing is launched for a camera that is not finite
+hipError_t launch_sky_light_apply(const CameraParams &cam, const SkyLightParams &lp, RenderPixel *pixels_dev, hipStream_t s);
 
 bool supported_map_size(int n);
 int kernel_family(int n, int slots, int mode);  // 1 standard, 2 layer-parallel, 3 compact: what launch_pass1/2 will use

@@ -151,6 +151,13 @@ class Sky:
         self.handle, self.width, self.height = handle, width, height
 
 
+class Radiance:
+    """a device-resident radiance pyramid of a sky (ow_radiance_create): WaveGenerator.radiance_create() makes it, radiance_destroy() ends it"""
+
+    def __init__(self, handle, levels):
+        self.handle, self.levels = handle, levels
+
+
 class WaveGenerator:
     """assets/water/wave_generator.gd.  Typical use, as in water.gd:89-91,112-114:
 
@@ -1190,6 +1197,57 @@ class WaveGenerator:
         _check_device_size(linear_device, h * w, 16, "linear_device", "pixels")
         _lib.check(self._lib.ow_present_async(self.context, C.byref(camera), _ref(o), _addr(pixels_device), _addr(rgba_device, True),
                                               _addr(linear_device, True)))
+
+    _RADIANCE_OWN = ("levels", "samples", "base_width")
+    _SKY_LIGHT_OWN = ("ambient_energy", "reflection_energy", "specular")
+
+    @classmethod
+    def radiance_options(cls, options=None):
+        """None, an _lib.ow_radiance_options, or a dict of levels, samples and base_width over ow_radiance_options_default's values"""
+        return cls._options(_lib.ow_radiance_options, _lib.load().ow_radiance_options_default, cls._RADIANCE_OWN, options, "radiance")
+
+    @classmethod
+    def sky_light_options(cls, options=None):
+        """None, an _lib.ow_radiance_light_options, or a dict of ambient_energy, reflection_energy and specular over
+        ow_radiance_light_options_default's values (1, 1, 0.5)"""
+        return cls._options(_lib.ow_radiance_light_options, _lib.load().ow_radiance_light_options_default, cls._SKY_LIGHT_OWN, options, "sky light")
+
+    def radiance_create(self, sky, options=None):
+        """The roughness-blurred pyramid and the irradiance of a Sky, built once on the device; returns a Radiance (radiance_destroy() it
+        before free()).  The sky may be destroyed afterwards."""
+        o = self.radiance_options(options)
+        out, n = C.c_void_p(), C.c_int32()
+        _lib.check(self._lib.ow_radiance_create(self.context, sky.handle, _ref(o), C.byref(out)))
+        _lib.check(self._lib.ow_radiance_level(self.context, out, 0, C.byref(n), None, None, None))
+        return Radiance(out, n.value)
+
+    def radiance_destroy(self, radiance):
+        self._destroy(radiance, self._lib.ow_radiance_destroy)
+
+    def radiance_level(self, radiance, level):
+        """(H, W, 4) float32 texels of level `level` (0 .. levels - 1), or of the 16 x 32 irradiance with level="irradiance".  Synchronises."""
+        k = _lib.OW_RADIANCE_IRRADIANCE if level == "irradiance" else int(level)
+        w, h = C.c_int32(), C.c_int32()
+        _lib.check(self._lib.ow_radiance_level(self.context, radiance.handle, k, None, C.byref(w), C.byref(h), None))
+        out = np.zeros((h.value, w.value, 4), np.float32)
+        _lib.check(self._lib.ow_radiance_level(self.context, radiance.handle, k, None, None, None, out.ctypes.data))
+        return out
+
+    def sky_light_apply(self, radiance, camera, pixels, options=None):
+        """Sky ambient and sky reflection over `pixels` ((H, W) RENDER_PIXEL records of the draws, made with ambient_color 0): the records
+        with color and status rewritten (a copy).  Call it before environment_apply.  Synchronises."""
+        o = self.sky_light_options(options)
+        _, rec = self._picture(camera, pixels, False)
+        _lib.check(self._lib.ow_radiance_light_apply(self.context, radiance.handle if radiance is not None else None, C.byref(camera), _ref(o),
+                                                     rec.ctypes.data))
+        return rec
+
+    def sky_light_apply_async(self, radiance, camera, pixels_device, options=None):
+        """The pass over DEVICE records (mesh_draw_async's), in place, enqueued in the generator's stream order without synchronising"""
+        self._check_picture_buffers(camera, None, pixels_device)
+        o = self.sky_light_options(options)
+        _lib.check(self._lib.ow_radiance_light_apply_async(self.context, radiance.handle if radiance is not None else None, C.byref(camera), _ref(o),
+                                                           _addr(pixels_device)))
 
     def get_push_constants(self, cascade):
         """(spectrum[16], modulate[8], unpack[4]) uint32 words: the reference's push-constant blocks of this cascade's most recent launch"""

@@ -1,0 +1,1054 @@
+"""Light from the sky over a camera picture (include/ocean_waves.h ow_radiance_*): a roughness-blurred radiance pyramid of the panorama, built
+once on the device, and a pass over the records that adds the sky's ambient and its reflection in the water
+(godotoceanwaves_amd/csrc/ow_sky_light.h).
+
+CPU: the ABI, the documents and the argument checks without a device; ow_sky_light.h compiled as plain C++
+(tests/sky_light/sky_light_harness.cpp, g++ -ffp-contract=off) held to its exact cases (level 0 is the environment pass's sky bit for bit, a
+4 x 2 box by hand, constant skies, the ends of the option ranges and sides that do not halve, roughness 0 and 1, ambient only for solids and
+hits from below, untouched misses and finished records, idempotence, no byte outside color and status), to an FP64 twin written from the
+definition (tests/sky_light_twin.py) on every texel of every level and on every stage of the pass over a synthetic record field and over
+pictures of ow_mesh_draw's and ow_solid_draw's CPU builds, to the closed form of a hemisphere sky's irradiance, and to finite outputs on
+awkward records; the stand-alone harness runs under the sanitizers on the same inputs; the C example compiles.  GPU: the pyramid and the
+pass are the CPU build's bit for bit; a whole frame (mesh draw, solids, sky light, environment, billboards, present, all asynchronous on
+device buffers) equals the CPU chain, repeats to the byte and synchronises nothing; the asynchronous form is ordered on the context's and
+on a caller's stream; foreign and orphaned handles are refused; a destroyed sky does not disturb its pyramid; examples/sky_light_host.c
+writes the wrapper's picture."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import helpers as H
+import sky_light_twin as ST
+from godotoceanwaves_amd import _lib, build
+from godotoceanwaves_amd.presets import UPDATE_DELTA
+from godotoceanwaves_amd.wave_generator import WaveGenerator as W
+from test_environment import (FRAME_CAM, FRAME_ENV, FRAME_PRESENT, FRAME_SHAPE, FRAME_WATER, bare_context, cpu_environment, cpu_present, device_frame,
+                              example_panorama, f32_options, frame_scene, gpu_sky, gradient_panorama, harness as env_harness, pictures, records_of, rel,  # noqa: F401
+                              same_records, sky_lookup, sky_of, synthetic_records)
+from test_mesh_draw import REF_BASIS, cpu_draw as cpu_mesh_draw, grid, harness as mesh_harness  # noqa: F401
+from test_render_view import camera_words, look
+from test_solid_draw import (CRATE_CAM, CRATE_SHAPE, box, cpu_draw as cpu_solid_draw, example_crates, gpu_material, harness as solid_harness,  # noqa: F401
+                             pose_transforms, transforms)
+from test_spray_draw import cpu_draw as cpu_billboard_draw, example_textures, harness as billboard_harness, level_camera, material  # noqa: F401
+from test_surface_query import gpu_maps, make_gen, scales_of
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "godotoceanwaves_amd", "csrc")
+PKG = os.path.join(ROOT, "godotoceanwaves_amd")
+HERE = os.path.dirname(os.path.abspath(__file__))
+HARNESS_SRC = os.path.join(HERE, "sky_light", "sky_light_harness.cpp")
+MARGINS = os.path.join(ROOT, "profiles", "sky_light_margins.txt")
+# The exports are named after the handle: tests/test_environment.py pins the set of exports that begin with ow_sky, so none is added there.
+NEW_FUNCTIONS = ("ow_radiance_options_default", "ow_radiance_light_options_default", "ow_radiance_create", "ow_radiance_destroy", "ow_radiance_level",
+                 "ow_radiance_light_apply", "ow_radiance_light_apply_async")
+TOL = H.TOL_F32     # 1e-4: the project's FP32 parity tolerance
+HIT, BELOW, SOLID, ENV, LIT = _lib.OW_RAY_HIT, _lib.OW_RAY_FROM_BELOW, _lib.OW_RAY_SOLID, _lib.OW_RAY_ENVIRONMENT, _lib.OW_RAY_SKY_LIT
+RADIANCE_DEFAULTS = dict(levels=6, samples=64, base_width=1024)
+LIGHT_DEFAULTS = dict(ambient_energy=1.0, reflection_energy=1.0, specular=0.5)
+RADIANCE_CASE = np.dtype([("sky_width", np.int32), ("sky_height", np.int32), ("sky_srgb", np.int32), ("energy", np.float32), ("levels", np.int32),
+                          ("samples", np.int32), ("base_width", np.int32)])
+LIGHT_CASE = np.dtype([("width", np.int32), ("height", np.int32), ("cam", np.float32, 15), ("ambient_energy", np.float32),
+                       ("reflection_energy", np.float32), ("specular", np.float32)])
+STAGES = (("view", 0, 3), ("reflect", 3, 6), ("lod", 6, 7), ("radiance", 7, 10), ("env", 10, 12), ("irradiance", 12, 15), ("ambient", 15, 18), ("spec", 18, 21))
+
+
+# ---- panoramas, records and the CPU build -------------------------------------------------------------------------------------------------
+
+def noisy_panorama(w, h, seed=7):
+    """every texel on its own: the hardest case for a lookup (a texel's neighbours differ by up to the whole range)"""
+    img = np.random.default_rng(seed).integers(0, 256, (h, w, 4)).astype(np.uint8)
+    img[..., 3] = 255
+    return img
+
+
+def constant_panorama(w, h, rgb=(90, 140, 200)):
+    img = np.zeros((h, w, 4), np.uint8)
+    img[..., :3] = rgb
+    img[..., 3] = 255
+    return img
+
+
+@pytest.fixture(scope="module")
+def harness(tmp_path_factory):
+    so = str(tmp_path_factory.mktemp("sky_light") / "libsky_light_harness.so")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unknown-pragmas", "-I", CSRC, HARNESS_SRC, "-o", so], check=True)
+    L = C.CDLL(so)
+    V, I = C.c_void_p, C.c_int
+    L.harness_sky_light_sizes.argtypes = [V]
+    L.harness_radiance_plan.argtypes = [I, I, I, I, V]
+    L.harness_radiance_dir_table.argtypes = [I, I, V]
+    L.harness_radiance_sample_table.argtypes = [C.c_double, I, V]
+    L.harness_radiance_new.argtypes = [V, V]
+    L.harness_radiance_new.restype = V
+    L.harness_radiance_free.argtypes = [V]
+    L.harness_radiance_get.argtypes = [V, I, I, V, V]
+    L.harness_radiance_lookup.argtypes = [V, I, I, V, I, V]
+    L.harness_sky_light_apply.argtypes = [V, V, V, V]
+    return L
+
+
+def radiance_case(sky, opts=None):
+    o = dict(RADIANCE_DEFAULTS, **(opts or {}))
+    h = np.zeros(1, RADIANCE_CASE)
+    h["sky_height"], h["sky_width"], h["sky_srgb"], h["energy"] = sky["image"].shape[0], sky["image"].shape[1], sky["srgb"], sky["energy"]
+    for k in RADIANCE_DEFAULTS:
+        h[k] = o[k] or RADIANCE_DEFAULTS[k]
+    return h
+
+
+def light_case(cam, opts=None):
+    o = f32_options(LIGHT_DEFAULTS, opts)
+    h = np.zeros(1, LIGHT_CASE)
+    h["width"], h["height"], h["cam"] = cam.width, cam.height, camera_words(cam)
+    for k in LIGHT_DEFAULTS:
+        h[k] = o[k]
+    return h
+
+
+class CpuPyramid:
+    """the CPU build's pyramid of a sky (sky_of's dict): R[k], M[k], E as (h, w, 4) float32, lookups and the pass"""
+
+    def __init__(self, L, sky, opts=None):
+        self.L, self.sky = L, sky
+        self.case = radiance_case(sky, opts)
+        self.levels = int(self.case["levels"][0])
+        self.ptr = L.harness_radiance_new(self.case.ctypes.data, sky["image"].ctypes.data)
+        assert self.ptr, "the sizes are refused"
+
+    def __del__(self):
+        if getattr(self, "ptr", None):
+            self.L.harness_radiance_free(self.ptr)
+
+    def texture(self, kind, k=0):
+        size = (C.c_int * 2)()
+        if not self.L.harness_radiance_get(self.ptr, kind, k, size, None):
+            return None
+        out = np.zeros((size[1], size[0], 4), np.float32)
+        self.L.harness_radiance_get(self.ptr, kind, k, size, out.ctypes.data)
+        return out
+
+    R = lambda self, k: self.texture(0, k)    # noqa: E731
+    M = lambda self, k: self.texture(1, k)    # noqa: E731
+    E = property(lambda self: self.texture(2))
+
+    def lookup(self, kind, k, dirs):
+        d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        out = np.zeros_like(d)
+        self.L.harness_radiance_lookup(self.ptr, kind, k, d.ctypes.data, len(d), out.ctypes.data)
+        return out
+
+    def apply(self, records, cam, opts=None):
+        """dict of rec (a copy, rewritten) and the stages"""
+        rec = np.array(records, W.RENDER_PIXEL, copy=True, order="C")
+        assert rec.shape == (cam.height, cam.width)
+        h = light_case(cam, opts)
+        st = np.zeros((cam.height, cam.width, 21), np.float32)
+        self.L.harness_sky_light_apply(self.ptr, h.ctypes.data, rec.ctypes.data, st.ctypes.data)
+        out = dict(rec=rec)
+        for name, a, b in STAGES:
+            out[name] = st[..., a] if b == a + 1 else st[..., a:b]
+        return out
+
+
+def twin_pyramid(sky, opts=None):
+    o = dict(RADIANCE_DEFAULTS, **(opts or {}))
+    return ST.pyramid(sky["image"], sky["srgb"], sky["energy"], o["levels"], o["samples"], o["base_width"])
+
+
+def unit(v):
+    v = np.asarray(v, np.float64)
+    return v / np.linalg.norm(v, axis=-1, keepdims=True)
+
+
+def light_records(cam, seed=1):
+    """test_environment's synthetic field (misses of every status, water hits, hits from below, solids) with what the pass reads: positions
+    from 1 m to 1 km in front of the camera, unit normals about +Y (some tilted past the horizon), albedos, and roughness over [0, 1] with
+    both ends, values beyond them and the level boundaries among them"""
+    rng = np.random.default_rng(seed + 1000)
+    rec = synthetic_records(cam, seed, top=4.0)
+    shape = rec.shape
+    words = np.asarray(camera_words(cam), np.float64)
+    rays = ST.ET.rays(words, cam.width, cam.height)
+    dist = rng.uniform(1.0, 1000.0, shape)
+    rec["position"] = (words[0:3] + rays * dist[..., None]).astype(np.float32)
+    n = unit(np.stack([rng.normal(0, 0.4, shape), np.abs(rng.normal(1.0, 0.3, shape)) * np.where(rng.random(shape) < 0.1, -0.3, 1.0), rng.normal(0, 0.4, shape)], -1))
+    rec["normal"] = n.astype(np.float32)
+    rec["albedo"] = rng.random(shape + (3,)).astype(np.float32)
+    special = np.float32([0.0, 1.0, 0.2, 0.4, 0.6, 0.8, 1.0 / 3.0, 2.0 / 3.0, -0.5, 1.5])
+    rec["roughness"] = np.where(rng.random(shape) < 0.3, rng.choice(special, shape), rng.random(shape).astype(np.float32))
+    rec["fresnel"] = rng.random(shape).astype(np.float32)           # neighbours of what the pass reads and writes: they must not move
+    already = rng.random(shape) < 0.1
+    rec["status"] = np.where(already & ((rec["status"] & HIT) != 0), rec["status"] | rng.choice(np.int32([ENV, LIT, ENV | LIT]), shape), rec["status"])
+    return rec
+
+
+def check_pass_against_twin(got, tw, records, what):
+    """color, status and every stage the harness exposes, on every record; returns the margins"""
+    rec = got["rec"]
+    assert np.array_equal(rec["status"], tw["status"]), what
+    for f in W.RENDER_PIXEL.names:
+        if f not in ("color", "status"):
+            assert rec[f].tobytes() == records[f].tobytes(), (what, f)
+    lit, mirror = tw["lit"], tw["mirror"]
+    m = dict(color=rel(rec["color"], tw["color"]), view=rel(got["view"][lit], tw["view"][lit]), irradiance=rel(got["irradiance"][lit], tw["irradiance"][lit]),
+             ambient=rel(got["ambient"], tw["ambient"]), spec=rel(got["spec"], tw["spec"]))
+    for k in ("reflect", "lod", "radiance", "env"):
+        m[k] = rel(got[k][mirror], tw[k][mirror])
+    assert max(m.values()) <= TOL, (what, m)
+    assert np.isfinite(rec["color"]).all(), what
+    return m
+
+
+# ---- 1. the interface and the documents --------------------------------------------------------------------------------------------------
+
+HEADER = open(os.path.join(ROOT, "include", "ocean_waves.h")).read()
+
+
+def test_header_declares_the_new_calls_and_the_library_exports_them():
+    build.build_library()
+    lib = _lib.load()
+    text = re.sub(r"/\*.*?\*/", "", HEADER, flags=re.S)
+    for name in NEW_FUNCTIONS:
+        assert re.search(r"\b%s\s*\(" % name, text), name
+        assert name in _lib.SIGNATURES
+        assert getattr(lib, name)
+    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    exported = set(re.findall(r" T (ow_[a-z0-9_]+)", out))
+    assert sorted(s for s in exported if "radiance" in s) == sorted(NEW_FUNCTIONS)      # no group form
+    assert lib.ow_abi_version() == 4 and re.search(r"#define OW_ABI_VERSION 4\b", HEADER)
+    for define, value in (("OW_RAY_SKY_LIT", 64), ("OW_RADIANCE_MAX_LEVELS", 8), ("OW_RADIANCE_MAX_SAMPLES", 256)):
+        assert re.search(r"#define %s %d\b" % (define, value), HEADER) and getattr(_lib, define) == value, define
+    assert re.search(r"#define OW_RADIANCE_IRRADIANCE \(-1\)", HEADER) and _lib.OW_RADIANCE_IRRADIANCE == -1
+    section = HEADER.split("Light from the sky: prefiltered reflections and ambient")[1].split("several devices")[0]
+    for cite in ("water -> solids -> ow_radiance_light_apply -> ow_environment_apply -> billboards -> ow_present", "ow_sky_light.h", "THIS LIBRARY'S CHOICE",
+                 "Hammersley", "Karis", "A CALLER OF THIS PASS SETS IT TO 0", "OW_RAY_SKY_LIT", "no group form", "screen-space reflections", "main.tscn:16-24",
+                 "water.gdshader:93"):
+        assert cite in section, cite
+    r = _lib.ow_radiance_options()
+    lib.ow_radiance_options_default(C.byref(r))
+    assert (r.levels, r.samples, r.base_width) == (6, 64, 1024) and not any(r.reserved)
+    o = _lib.ow_radiance_light_options()
+    lib.ow_radiance_light_options_default(C.byref(o))
+    assert (o.ambient_energy, o.reflection_energy, o.specular, o.flags) == (1.0, 1.0, 0.5, 0) and not any(o.reserved)
+    for fn in (lib.ow_radiance_options_default, lib.ow_radiance_light_options_default):
+        fn(None)
+
+
+def test_option_structs_agree_in_c_ctypes_and_the_harness(tmp_path, harness):
+    got = {}
+    for S, name in ((_lib.ow_radiance_options, "ow_radiance_options"), (_lib.ow_radiance_light_options, "ow_radiance_light_options")):
+        fields = [f for f, _ in S._fields_]
+        expr = ", ".join(["sizeof(%s)" % name] + ["offsetof(%s, %s)" % (name, f) for f in fields])
+        src = ('#include <stdio.h>\n#include <stddef.h>\n#include "ocean_waves.h"\nint main(void){printf("%s\\n", ' % " ".join(["%zu"] * (1 + len(fields)))
+               + expr + ");return 0;}\n")
+        exe = str(tmp_path / (name + "_layout"))
+        subprocess.run(["gcc", "-std=c11", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-x", "c", "-", "-o", exe], input=src, text=True, check=True)
+        vals = [int(v) for v in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split()]
+        assert vals == [C.sizeof(S)] + [getattr(S, f).offset for f in fields], name
+        got[name] = dict(zip(["size"] + fields, vals))
+    assert (got["ow_radiance_options"]["size"], got["ow_radiance_light_options"]["size"]) == (32, 64)
+    sizes = (C.c_int * 9)()
+    harness.harness_sky_light_sizes(sizes)
+    p = got["ow_radiance_light_options"]
+    assert list(sizes) == [32, got["ow_radiance_options"]["reserved"], 64, p["flags"], p["reserved"], RADIANCE_CASE.itemsize, LIGHT_CASE.itemsize, 21, LIT]
+    for field, offset in (("position", 8), ("albedo", 52), ("normal", 64), ("roughness", 80), ("color", 100), ("status", 4)):
+        assert W.RENDER_PIXEL.fields[field][1] == offset, field
+
+
+def test_the_documents_name_the_new_calls():
+    import test_integration_shim as S
+    for name in NEW_FUNCTIONS:
+        assert "`%s`" % name in S.DOC.split("## 7. Index")[1], name
+    for name in ("ow_radiance_create", "ow_radiance_destroy", "ow_radiance_level", "ow_radiance_light_apply", "ow_radiance_light_apply_async"):
+        assert re.search(r"\[DllImport\(Lib\)\]\s*public static extern \w+ %s\(" % name, S.SHIM), name
+    for doc, words in (("README.md", ("ow_radiance_create", "ow_radiance_light_apply")), ("DESIGN.md", ("k_sky_light_apply", "k_radiance_prefilter", "ow_sky_light.hip")),
+                       ("INTEGRATION.md", ("ow_radiance_light_apply_async", "OW_RAY_SKY_LIT", "OwRadianceOptions", "OwRadianceLightOptions",
+                                           "water -> solids -> ow_radiance_light_apply -> ow_environment_apply -> billboards -> ow_present"))):
+        text = open(os.path.join(ROOT, doc)).read()
+        for w in words:
+            assert w in text, (doc, w)
+    note = open(os.path.join(CSRC, "ow_environment.h")).read()
+    assert "ow_sky_light.h" in note
+    for path in ("scripts/sky_light_cost.py", "examples/sky_light_host.c"):
+        assert os.path.exists(os.path.join(ROOT, path)), path
+
+
+def build_example(tmp_path):
+    exe = str(tmp_path / "sky_light_host")
+    subprocess.run(["gcc", "-O2", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "examples", "sky_light_host.c"),
+                    "-o", exe, "-L", PKG, "-locean_waves", "-L", "/opt/rocm/lib", "-lamdhip64", f"-Wl,-rpath,{PKG}", "-Wl,-rpath,/opt/rocm/lib", "-lm"],
+                   check=True)
+    return exe
+
+
+def test_example_builds_as_c99(tmp_path):
+    build.build_library()
+    build_example(tmp_path)
+
+
+# ---- 2. argument errors without a device ---------------------------------------------------------------------------------------------------
+
+def test_argument_errors_without_a_device():
+    lib = _lib.load()
+    cam = level_camera(24, 12)
+    rec = np.zeros((12, 24), W.RENDER_PIXEL)
+    fake = C.c_void_p(16)   # never read: every case fails before a handle is looked at
+
+    def light(camera, opts, rec_p=rec.ctypes.data, radiance=fake):
+        cp, op = (C.byref(camera) if camera is not None else None), (C.byref(opts) if opts is not None else None)
+        out = []
+        for fn in (lib.ow_radiance_light_apply, lib.ow_radiance_light_apply_async):
+            assert fn(None, radiance, cp, op, rec_p) == _lib.OW_ERR_INVALID
+            out.append(lib.ow_last_error().decode())
+        assert out[0] == out[1]
+        return out[0]
+
+    lo = W.sky_light_options
+    assert "null context" in light(cam, None) and "null context" in light(cam, None, radiance=None)     # everything else is in order
+    assert "null context" in light(cam, lo(dict(ambient_energy=0.0, reflection_energy=1e12, specular=1.0)))
+    assert "null context" in light(cam, lo(dict(specular=0.0)))
+    assert "the records" in light(cam, None, None)
+    assert "null camera" in light(None, None)
+    for w, h in ((0, 12), (24, 0), (_lib.OW_RENDER_MAX_SIDE + 1, 12)):
+        assert "camera size" in light(level_camera(w, h), None)
+    bad = level_camera(24, 12)
+    bad.reserved[1] = 7
+    assert "ow_camera.reserved" in light(bad, None)
+    nan, inf = float("nan"), float("inf")
+    for key, values in (("ambient_energy", (-1.0, nan, inf, 2e12)), ("reflection_energy", (-1.0, nan, inf, 2e12)), ("specular", (-0.1, 1.1, nan, inf))):
+        for v in values:
+            assert key in light(cam, lo({key: v})), (key, v)
+    # the order: the records before the camera before the options
+    assert "the records" in light(None, lo(dict(specular=2.0)), None) and "null camera" in light(None, lo(dict(specular=2.0)))
+    o = lo({})
+    o.flags = 1
+    assert "radiance light flags" in light(cam, o)
+    o = lo({})
+    o.reserved[11] = 1
+    assert "ow_radiance_light_options.reserved" in light(cam, o)
+    assert not rec.tobytes().strip(b"\0")
+
+    def create(opts=None, sky=fake):
+        out = C.c_void_p(0x5EED)
+        assert lib.ow_radiance_create(None, sky, C.byref(opts) if opts is not None else None, C.byref(out)) == _lib.OW_ERR_INVALID
+        assert out.value == 0x5EED
+        return lib.ow_last_error().decode()
+
+    ro = W.radiance_options
+    assert "null context" in create() and "null context" in create(sky=None)
+    for good in (dict(levels=0, samples=0, base_width=0), dict(levels=2, samples=1, base_width=16), dict(levels=8, samples=256, base_width=2048)):
+        assert "null context" in create(ro(good)), good                                       # both ends of every range, and the zeros
+    for v in (-1, 1, 9):
+        assert "levels" in create(ro(dict(levels=v))), v
+    for v in (-1, 257):
+        assert "samples" in create(ro(dict(samples=v))), v
+    for v in (-16, 8, 48, 1000, 4096):
+        assert "base_width" in create(ro(dict(base_width=v))), v
+    o = ro({})
+    o.reserved[4] = 1
+    assert "ow_radiance_options.reserved" in create(o)
+    assert lib.ow_radiance_create(None, fake, None, None) == _lib.OW_ERR_INVALID and "null argument" in lib.ow_last_error().decode()
+    assert lib.ow_radiance_level(None, fake, 0, None, None, None, None) == _lib.OW_ERR_INVALID and "null context" in lib.ow_last_error().decode()
+    lib.ow_radiance_destroy(None, None)
+    for bad_call in (lambda: W.radiance_options({"blur": 1}), lambda: W.sky_light_options({"energy": 2.0})):
+        with pytest.raises(ValueError):
+            bad_call()
+
+
+# ---- 3. exact cases on the CPU build -------------------------------------------------------------------------------------------------------
+
+def sphere_directions(count=4000, seed=3):
+    d = unit(np.random.default_rng(seed).normal(size=(count, 3)))
+    axes = np.array([[0, 1, 0], [0, -1, 0], [1, 0, 0], [-1, 0, 0], [0, 0, 1], [0, 0, -1], [0, 1e-7, 1], [1e-7, 0, 1], [-1e-7, 0, 1]], np.float64)
+    return np.concatenate([d, unit(axes)]).astype(np.float32)
+
+
+def test_level_0_lookup_is_the_environment_pass_sky_bit_for_bit(harness, env_harness):
+    """a sky no wider than base_width is level 0 texel for texel, so a lookup of R_0 is ow_environment.h's sky(d): energy 1 and 2 (a power of
+    two scales every texel exactly), with and without the sRGB table, on 4000 random directions, the axes and the seam"""
+    dirs = sphere_directions()
+    for image, srgb, energy, opts in ((gradient_panorama(64, 32), 1, 1.0, None), (noisy_panorama(64, 32), 0, 2.0, dict(base_width=64)),
+                                      (noisy_panorama(10, 6, 2), 1, 1.0, dict(levels=2, base_width=16))):
+        sky = sky_of(image, srgb, energy)
+        pyr = CpuPyramid(harness, sky, opts)
+        assert pyr.R(0).shape[:2] == image.shape[:2]
+        got = pyr.lookup(0, 0, dirs)
+        want = sky_lookup(env_harness, sky, dirs)
+        assert got.tobytes() == np.ascontiguousarray(want, np.float32).tobytes()
+        assert got.max() > 0.1
+
+
+def test_a_4_by_2_sky_boxes_to_2_by_1_by_hand(harness):
+    img = np.zeros((2, 4, 4), np.uint8)
+    img[..., 0] = [[10, 20, 30, 40], [50, 60, 70, 80]]
+    img[..., 1] = [[255, 0, 0, 255], [0, 0, 255, 255]]
+    img[..., 2] = 7
+    img[..., 3] = 9                                                   # alpha is not read: A is 0 in every level
+    pyr = CpuPyramid(harness, sky_of(img, 0, 1.0), dict(levels=2, samples=4, base_width=16))
+    f = np.float32
+    m0 = (img[..., :3].astype(f) / f(255.0))
+    assert pyr.M(0)[..., :3].tobytes() == m0.tobytes() and pyr.R(0).tobytes() == pyr.M(0).tobytes() and not pyr.M(0)[..., 3].any()
+    want = ((m0[0, 0::2] + m0[0, 1::2]) + (m0[1, 0::2] + m0[1, 1::2])) * f(0.25)
+    m1 = pyr.M(1)
+    assert m1.shape == (1, 2, 4) and m1[0, :, :3].tobytes() == want.astype(f).tobytes() and not m1[..., 3].any()
+    assert abs(float(m1[0, 0, 0]) - (10 + 20 + 50 + 60) / 4 / 255) < 1e-7 and float(m1[0, 1, 1]) == 0.75
+    assert pyr.M(2) is None and pyr.R(2) is None and pyr.R(1).shape == (1, 2, 4) and pyr.E.shape == (16, 32, 4)
+    # a sky wider than base_width is reduced by the same box, once per halving
+    big = noisy_panorama(64, 32, 4)
+    a, b = CpuPyramid(harness, sky_of(big, 1, 1.5), dict(levels=2, samples=1, base_width=16)), twin_pyramid(sky_of(big, 1, 1.5), dict(levels=2, samples=1, base_width=16))
+    assert a.M(0).shape == (8, 16, 4) and rel(a.M(0)[..., :3], b["M"][0]) <= 1e-6
+
+
+def test_a_constant_sky_gives_constant_levels_and_irradiance(harness):
+    sky = sky_of(constant_panorama(64, 32), 1, 1.7)
+    pyr = CpuPyramid(harness, sky, dict(levels=5, samples=32))
+    value = pyr.M(0)[0, 0, :3].astype(np.float64)
+    assert (value > 0.05).all()
+    for k in range(5):
+        assert (pyr.M(k)[..., :3] == pyr.M(0)[0, 0, :3]).all(), k        # the box of equal texels is exact
+        assert rel(pyr.R(k)[..., :3], np.broadcast_to(value, pyr.R(k)[..., :3].shape)) <= TOL, k
+        assert not pyr.R(k)[..., 3].any()
+    assert rel(pyr.E[..., :3], np.broadcast_to(value, (16, 32, 3))) <= TOL and not pyr.E[..., 3].any()
+
+
+def plan(L, w, h, levels, base):
+    out = (C.c_int * 40)()
+    if not L.harness_radiance_plan(w, h, levels, base, out):
+        return None
+    return dict(pre=out[0], chain=out[1], source=out[2], sizes=[(out[3 + 2 * k], out[4 + 2 * k]) for k in range(out[1])])
+
+
+def test_level_sizes_at_the_ends_of_the_ranges_and_sides_that_do_not_halve(harness):
+    p = plan(harness, 2048, 1024, 6, 1024)
+    assert p["pre"] == 1 and p["sizes"][:6] == [(1024 >> k, 512 >> k) for k in range(6)] and p["sizes"][p["source"]] == (64, 32)
+    p = plan(harness, 8192, 4096, 8, 2048)
+    assert p["pre"] == 2 and p["sizes"] == [(2048 >> k, 1024 >> k) for k in range(8)] and p["sizes"][p["source"]] == (64, 32)
+    p = plan(harness, 8192, 4096, 2, 2048)                             # the unblurred chain runs on past the levels, down to the irradiance's source
+    assert p["chain"] == 6 and p["sizes"][-1] == (64, 32) and p["source"] == 5
+    p = plan(harness, 8192, 8192, 2, 16)
+    assert p["pre"] == 9 and p["sizes"] == [(16, 16), (8, 8)] and p["source"] == 0
+    assert plan(harness, 64, 32, 6, 64)["sizes"][-1] == (2, 1) and plan(harness, 64, 32, 6, 1024)["source"] == 0
+    assert plan(harness, 4, 2, 2, 16)["sizes"] == [(4, 2), (2, 1)]
+    for w, h, levels, base in ((64, 32, 7, 1024),       # 1 x 0.5
+                               (66, 32, 3, 1024),       # 33 is odd before the second halving
+                               (64, 18, 3, 1024),       # 9 rows
+                               (130, 64, 2, 64),        # 65 columns after the reduction
+                               (100, 50, 2, 16),        # 25 is odd and still wider than base_width
+                               (2, 2, 2, 16), (1, 1, 2, 16), (63, 32, 2, 1024)):
+        assert plan(harness, w, h, levels, base) is None, (w, h, levels, base)
+        assert ST.level_sizes(w, h, levels, base) is None, (w, h, levels, base)
+    for w, h, levels, base in ((64, 32, 6, 1024), (256, 128, 4, 64), (96, 48, 4, 1024), (8192, 4096, 8, 2048), (32, 32, 4, 16)):
+        assert plan(harness, w, h, levels, base)["sizes"][:levels] == ST.level_sizes(w, h, levels, base)
+    # samples at both ends: one sample is the mirror direction itself (xi = 0: the texel's own direction), 256 run
+    sky = sky_of(gradient_panorama(32, 16), 1, 1.0)
+    one = CpuPyramid(harness, sky, dict(levels=2, samples=1, base_width=16))
+    assert rel(one.R(1)[..., :3], one.M(1)[..., :3]) <= 1e-5
+    many = CpuPyramid(harness, sky, dict(levels=8 - 4, samples=256))
+    assert np.isfinite(many.R(3)).all() and many.R(3).shape == (2, 4, 4)
+
+
+def test_the_hosts_tables_are_the_definitions_narrowed_once(harness):
+    """direction tables and GGX samples: FP64 values of the definition (the twin's own), rounded to FP32"""
+    for n in (2, 5, 32, 64):
+        for rows in (0, 1):
+            got = np.zeros((n, 2), np.float32)
+            harness.harness_radiance_dir_table(n, rows, got.ctypes.data)
+            a = np.pi * (np.arange(n) + 0.5) / n if rows else ((np.arange(n) + 0.5) / n - 0.5) * 2.0 * np.pi
+            assert np.abs(got - np.stack([np.sin(a), np.cos(a)], -1)).max() <= 6e-8, (n, rows)
+    for r, count in ((0.2, 16), (0.5, 64), (1.0, 256), (1.0 / 3.0, 1)):
+        got = np.zeros((count, 4), np.float32)
+        harness.harness_radiance_sample_table(r, count, got.ctypes.data)
+        l, w = ST.ggx_samples(r, count)
+        assert np.abs(got[:, :3] - l).max() <= 6e-8 and np.abs(got[:, 3] - w).max() <= 6e-8 and (got[:, 3] == got[:, 2]).all(), (r, count)
+        assert (w > 0).sum() >= count // 2                       # at roughness 1 half of the set points below the horizon and is not taken
+    d = ST.directions(8, 4)
+    assert np.abs(np.linalg.norm(d, axis=-1) - 1).max() < 1e-12 and d[0, :, 1].min() > 0.9 and abs(d[1, 3, 0]) < 0.5 and d[1, 3, 2] < 0   # +Y on top, -Z in the middle
+
+
+PASS_CAM = dict(position=(0.0, 8.0, 0.0), yaw_deg=20.0, pitch_deg=-4.0, width=40, height=24)
+
+
+def flat_records(cam, roughness, status=HIT, normal=(0.0, 1.0, 0.0)):
+    """water 30 m ahead of every pixel, facing up"""
+    rec = np.zeros((cam.height, cam.width), W.RENDER_PIXEL)
+    words = np.asarray(camera_words(cam), np.float64)
+    rec["position"] = (words[0:3] + 30.0 * ST.ET.rays(words, cam.width, cam.height)).astype(np.float32)
+    rec["status"], rec["t"], rec["roughness"] = status, 30.0, roughness
+    rec["normal"], rec["albedo"], rec["color"] = normal, (0.2, 0.3, 0.4), (0.01, 0.02, 0.03)
+    return rec
+
+
+def test_roughness_0_and_1_select_exactly_the_first_and_the_last_level(harness):
+    cam = look(**PASS_CAM)
+    pyr = CpuPyramid(harness, sky_of(noisy_panorama(64, 32), 1, 1.0), dict(levels=5, samples=16))
+    for roughness, level in ((0.0, 0), (1.0, 4), (-3.0, 0), (7.0, 4), (np.nan, 0), (0.25, 1), (0.5, 2), (0.75, 3)):
+        got = pyr.apply(flat_records(cam, roughness), cam)
+        want = pyr.lookup(0, level, got["reflect"].reshape(-1, 3)).reshape(cam.height, cam.width, 3)
+        assert got["radiance"].tobytes() == want.tobytes(), roughness
+        assert (got["lod"] == level).all() and np.abs(got["radiance"] - pyr.lookup(0, (level + 1) % 5, got["reflect"].reshape(-1, 3)).reshape(want.shape)).max() > 0.01
+    half = pyr.apply(flat_records(cam, 0.125), cam)                       # half way between levels 0 and 1
+    a, b = (pyr.lookup(0, k, half["reflect"].reshape(-1, 3)).reshape(cam.height, cam.width, 3) for k in (0, 1))
+    assert (half["lod"] == 0.5).all() and half["radiance"].tobytes() == (a * np.float32(0.5) + b * np.float32(0.5)).tobytes()
+
+
+def test_which_records_are_lit_and_which_bytes_move(harness):
+    """solids and hits from below get ambient only; misses, finished and already lit records are untouched; twice is once; nothing but color
+    and status moves; reflection_energy 0 and ambient_energy 0 take their halves out"""
+    cam = look(**PASS_CAM)
+    sky = sky_of(gradient_panorama(64, 32), 1, 1.2)
+    pyr = CpuPyramid(harness, sky, dict(levels=4, samples=16))
+    rec = light_records(cam, 5)
+    got = pyr.apply(rec, cam)
+    out = got["rec"]
+    st = rec["status"]
+    todo = ((st & HIT) != 0) & ((st & (ENV | LIT)) == 0)
+    assert 0.3 < todo.mean() < 0.9 and (~todo & ((st & HIT) != 0)).sum() > 10
+    assert out[~todo].tobytes() == rec[~todo].tobytes()                                     # misses, finished and lit records: not a byte
+    assert (out["status"][todo] == (st[todo] | LIT)).all()
+    for f in W.RENDER_PIXEL.names:
+        if f not in ("color", "status"):
+            assert out[f].tobytes() == rec[f].tobytes(), f
+    ambient_only = todo & ((st & (SOLID | BELOW)) != 0)
+    mirror = todo & ~ambient_only
+    assert ambient_only.sum() > 50 and mirror.sum() > 50
+    assert not got["spec"][ambient_only].any() and not got["radiance"][ambient_only].any() and (got["ambient"][ambient_only] > 0).all()
+    assert (got["spec"][mirror] > 0).all() and (got["ambient"][mirror] > 0).all()
+    f32 = np.float32
+    assert out["color"][todo].tobytes() == (rec["color"][todo] + (got["ambient"][todo] + got["spec"][todo])).astype(f32).tobytes()
+    assert (got["ambient"][todo] == (rec["albedo"][todo] * got["irradiance"][todo]) * f32(1.0)).all()
+    again = pyr.apply(out, cam)
+    assert again["rec"].tobytes() == out.tobytes() and not again["ambient"].any() and not again["spec"].any()
+    no_spec = pyr.apply(rec, cam, dict(reflection_energy=0.0))
+    assert no_spec["rec"]["color"][todo].tobytes() == (rec["color"][todo] + got["ambient"][todo]).astype(f32).tobytes()
+    no_amb = pyr.apply(rec, cam, dict(ambient_energy=0.0, specular=1.0))
+    assert not no_amb["ambient"].any() and (no_amb["spec"][mirror] != got["spec"][mirror]).mean() > 0.9         # f0 0.16 instead of 0.04
+    assert no_amb["rec"]["color"][todo].tobytes() == (rec["color"][todo] + no_amb["spec"][todo]).astype(f32).tobytes()
+    # applying after the fog does nothing: the environment pass marks every record
+    fogged = rec.copy()
+    fogged["status"] |= ENV
+    assert pyr.apply(fogged, cam)["rec"].tobytes() == fogged.tobytes()
+    # a camera that is not finite changes nothing
+    nan_cam = look(**PASS_CAM)
+    nan_cam.position[1] = float("nan")
+    assert pyr.apply(rec, nan_cam)["rec"].tobytes() == rec.tobytes()
+
+
+def awkward_records(cam):
+    rec = light_records(cam, 21)
+    flat = rec.reshape(-1)
+    f = np.float32
+    nan, inf = np.nan, np.inf
+    odd_n = [(nan, 1.0, 0.0), (0.0, 0.0, 0.0), (inf, 0.0, 0.0), (-0.0, 0.0, -0.0), (0.0, 1.0, nan), (3e38, 3e38, 3e38), (1e-30, 1e-30, 1e-30), (0.0, -1.0, 0.0),
+                 (0.0, 1.0, 0.0), (1e20, 1e20, -1e20)]
+    odd_c = [(1e12, 1e12, 1e12), (-1e12, 0.0, 1e12), (3e38, 3e38, 3e38), (-3e38, 0.0, 3e38), (-0.0, 1e-45, 50.0)]
+    odd_a = [(1e12, 1e12, 1e12), (nan, 0.5, 0.5), (inf, -inf, 0.0), (3e38, -3e38, 0.0)]
+    words = np.asarray(camera_words(cam), np.float32)
+    odd_p = [tuple(words[0:3]), (nan, 0.0, 0.0), (inf, 0.0, -inf), (3e38, -3e38, 3e38), (1e-30, 8.0, 0.0)]
+    for k in range(len(flat)):
+        if k % 3 == 0:
+            flat["normal"][k] = f(odd_n[(k // 3) % len(odd_n)])
+        if k % 2 == 0:
+            flat["color"][k] = f(odd_c[(k // 2) % len(odd_c)])
+        if k % 5 == 0:
+            flat["albedo"][k] = f(odd_a[(k // 5) % len(odd_a)])
+        if k % 7 == 0:
+            flat["position"][k] = f(odd_p[(k // 7) % len(odd_p)])
+        if k % 11 == 0:
+            flat["roughness"][k] = f([nan, inf, -inf, 3e38][(k // 11) % 4])
+    return rec
+
+
+def awkward_cases():
+    cam = look((0.0, 8.0, 0.0), 20.0, -4.0, width=24, height=12)
+    flat_cam = W.camera((0, 0, 0), np.zeros((3, 3)), 75.0, 24, 12, 100.0)                    # finite, but no ray has a direction
+    inf_cam = look((0.0, 8.0, 0.0), 20.0, -4.0, width=24, height=12)
+    inf_cam.basis[4] = float("inf")
+    pano = gradient_panorama(16, 8)
+    return {
+        "odd records": dict(cam=cam, sky=sky_of(pano), radiance=dict(levels=3, samples=8)),
+        "huge energies": dict(cam=cam, sky=sky_of(pano, 1, 1e12), radiance=dict(levels=2, samples=4), light=dict(ambient_energy=1e12, reflection_energy=1e12, specular=1.0)),
+        "energy 0": dict(cam=cam, sky=sky_of(pano, 0, 0.0), radiance=dict(levels=3, samples=8)),
+        "a 2 x 1 sky": dict(cam=cam, sky=sky_of(pano[:1, :2]), radiance=dict(levels=2, samples=3, base_width=16)),   # no level can be halved: refused
+        "a basis of zeros": dict(cam=flat_cam, sky=sky_of(pano), radiance=dict(levels=3, samples=8)),
+        "an infinite basis": dict(cam=inf_cam, sky=sky_of(pano), radiance=dict(levels=3, samples=8), untouched=True),
+    }
+
+
+def test_awkward_records_give_finite_outputs(harness):
+    for name, c in awkward_cases().items():
+        rec = awkward_records(c["cam"])
+        if name == "a 2 x 1 sky":
+            assert plan(harness, 2, 1, 2, 16) is None
+            continue
+        pyr = CpuPyramid(harness, c["sky"], c["radiance"])
+        for k in range(pyr.levels):
+            assert np.isfinite(pyr.R(k)).all(), (name, k)
+        assert np.isfinite(pyr.E).all(), name
+        out = pyr.apply(rec, c["cam"], c.get("light"))["rec"]
+        if c.get("untouched"):
+            assert out.tobytes() == rec.tobytes(), name
+            continue
+        todo = ((rec["status"] & HIT) != 0) & ((rec["status"] & (ENV | LIT)) == 0)
+        assert ((out["status"][todo] & LIT) != 0).all() and out[~todo].tobytes() == rec[~todo].tobytes(), name
+        assert np.isfinite(out["color"]).all(), name                                         # every colour that came in was finite
+        n = rec["normal"]
+        dead = todo & (~np.isfinite(n).all(axis=-1) | (n == 0).all(axis=-1))
+        assert dead.sum() > 10 and out["color"][dead].tobytes() == rec["color"][dead].tobytes(), name   # no contribution, the bit is set
+        assert pyr.apply(out, c["cam"], c.get("light"))["rec"].tobytes() == out.tobytes(), name
+
+
+# ---- 4. against the FP64 twin --------------------------------------------------------------------------------------------------------------
+
+PYRAMID_CASES = {"64 x 32": ((64, 32), None), "128 x 64": ((128, 64), None), "256 x 128, base_width 64": ((256, 128), dict(base_width=64))}
+_margin_lines = {}
+
+
+def write_margins():
+    """profiles/sky_light_margins.txt, from whatever the tests of this section have measured in this run (SKY_LIGHT_WRITE_MARGINS=1)"""
+    if os.environ.get("SKY_LIGHT_WRITE_MARGINS") != "1":
+        return
+    with open(MARGINS, "w") as f:
+        f.write("ow_radiance_create and ow_radiance_light_apply, CPU build against the FP64 twin (tests/test_sky_light.py): the largest |difference| / max(1, |value|)\n"
+                "per texture and per stage, every texel and every record; TOL = 1e-4.  hemisphere: E against L (1 + n.y) / 2, absolute.\n")
+        for key in sorted(_margin_lines):
+            f.write("\n".join(_margin_lines[key]) + "\n")
+
+
+@pytest.mark.parametrize("case", list(PYRAMID_CASES))
+def test_every_texel_of_every_level_against_the_fp64_twin(harness, case):
+    """M_k, R_k and E within TOL = 1e-4 relative to max(1, |value|), on every texel, for a gradient and a noisy panorama, six levels of 64
+    samples.  Measured on the CPU build (profiles/sky_light_margins.txt, written with SKY_LIGHT_WRITE_MARGINS=1): the largest difference of a
+    level is 5.4e-7 (R_1), of the chain 1.4e-7, of E 1.9e-6."""
+    (w, h), opts = PYRAMID_CASES[case]
+    lines = []
+    for name, image, srgb, energy in (("gradient", gradient_panorama(w, h), 1, 1.3), ("noisy", noisy_panorama(w, h), 0, 0.8)):
+        sky = sky_of(image, srgb, energy)
+        pyr, tw = CpuPyramid(harness, sky, opts), twin_pyramid(sky, opts)
+        m = {}
+        for k in range(6):
+            assert pyr.R(k).shape[:2] == tw["R"][k].shape[:2] == pyr.M(k).shape[:2] == tw["M"][k].shape[:2], (case, k)
+            m["M%d" % k] = rel(pyr.M(k)[..., :3], tw["M"][k])
+            m["R%d" % k] = rel(pyr.R(k)[..., :3], tw["R"][k])
+            assert not pyr.R(k)[..., 3].any()
+        m["E"] = rel(pyr.E[..., :3], tw["E"])
+        lines.append("pyramid  %-26s %-9s " % (case, name) + " ".join("%s %.2e" % kv for kv in m.items()))
+        assert max(m.values()) <= TOL, (case, name, m)
+        assert rel(pyr.R(3)[..., :3], pyr.M(3)[..., :3]) > 1e-3                            # the blur is no bystander
+    print("\n".join(lines))
+    _margin_lines["1 " + case] = lines
+    write_margins()
+    assert os.path.exists(MARGINS)
+
+
+def test_a_hemisphere_skys_irradiance_against_the_closed_form(harness):
+    """upper half L, lower half 0: E(n) = L (1 + n.y) / 2.  The bound is the twin's own deviation from the closed form on the same 64 x 32
+    grid (the quadrature's error: 2.9e-4 measured) plus TOL."""
+    L = 200.0 / 255.0
+    img = constant_panorama(64, 32, (200, 200, 200))
+    img[16:, :, :3] = 0
+    sky = sky_of(img, 0, 1.0)
+    pyr, tw = CpuPyramid(harness, sky, dict(levels=2, samples=1)), twin_pyramid(sky, dict(levels=2, samples=1))
+    ny = ST.directions(32, 16)[..., 1]
+    closed = (L * (1.0 + ny) / 2.0)[..., None]
+    twin_error = float(np.abs(tw["E"] - closed).max())
+    got_error = float(np.abs(pyr.E[..., :3].astype(np.float64) - closed).max())
+    print("hemisphere: the twin's deviation from the closed form %.3e, the CPU build's %.3e" % (twin_error, got_error))
+    _margin_lines["3 hemisphere"] = ["hemisphere  64 x 32: the twin's deviation from L (1 + n.y) / 2 is %.3e, the CPU build's %.3e (bound: the twin's + TOL)"
+                                     % (twin_error, got_error)]
+    write_margins()
+    assert twin_error < 5e-3                                          # the grid resolves the hemisphere
+    assert got_error <= twin_error + TOL
+
+
+@pytest.fixture(scope="module")
+def lit_pictures(pictures, solid_harness):
+    """test_environment's two pictures of ow_mesh_draw's CPU build (a calm and a generated sea), with three crates drawn into each by
+    ow_solid_draw's CPU build 40 m, 70 m and 110 m in front of the camera"""
+    cam = pictures["cam"]
+    words = np.asarray(camera_words(cam), np.float64)
+    basis = words[3:12].reshape(3, 3)
+    right, forward = basis[:, 0], -basis[:, 2]
+    rows = []
+    for dist, side, q in ((40.0, -6.0, (0.0, 0.2, 0.0, 1.0)), (70.0, 9.0, (0.3, 0.1, 0.2, 1.0)), (110.0, 0.0, (0.0, 0.0, 0.5, 1.0))):
+        p = words[0:3] + forward * dist + right * side
+        rows.append(((float(p[0]), 1.0, float(p[2])), q, 1.0))
+    out = {"cam": cam}
+    for name in ("calm", "sea"):
+        out[name] = cpu_solid_draw(solid_harness, box((8.0, 4.0, 8.0)), transforms(rows), cam, None, pictures[name]["rec"])["rec"]
+    return out
+
+
+def test_the_lit_pictures_meet_the_twins_conditions(lit_pictures):
+    """what the comparison below is worth: both pictures hold sky, water seen from above over the whole range of roughness, and crates"""
+    for name in ("calm", "sea"):
+        rec = lit_pictures[name]
+        st = rec["status"]
+        water = ((st & HIT) != 0) & ((st & SOLID) == 0)
+        assert 0.2 < water.mean() < 0.8 and ((st & SOLID) != 0).sum() > 20 and ((st & HIT) == 0).sum() > 100, name
+        assert rec["roughness"][water].min() < 0.5 and rec["roughness"][water].max() > 0.05, name
+
+
+def test_every_stage_of_the_pass_against_the_fp64_twin(harness, lit_pictures):
+    """color, status and V, R, lod, radiance, env, irradiance, ambient and spec within TOL = 1e-4 relative to max(1, |value|), on every
+    record of a synthetic field and of the two lit pictures, under two pyramids and two sets of options.  Measured on the CPU build
+    (profiles/sky_light_margins.txt): the largest difference is 2.3e-6 (ambient, at ambient_energy 2.5); the colours are within 1.9e-6."""
+    cam = lit_pictures["cam"]
+    fields = {"synthetic": light_records(cam, 1), "calm": lit_pictures["calm"], "sea": lit_pictures["sea"]}
+    skies = {"gradient, 6 levels": (sky_of(gradient_panorama(64, 32), 1, 1.3), None),
+             "noisy 256 x 128, 4 levels": (sky_of(noisy_panorama(256, 128), 0, 0.8), dict(levels=4, samples=16, base_width=64))}
+    variants = {"defaults": None, "strong": dict(ambient_energy=2.5, reflection_energy=0.7, specular=1.0)}
+    lines, worst = [], {}
+    for sname, (sky, ropts) in skies.items():
+        pyr, tw_pyr = CpuPyramid(harness, sky, ropts), twin_pyramid(sky, ropts)
+        for fname, rec in fields.items():
+            for vname, lopts in variants.items():
+                got = pyr.apply(rec, cam, lopts)
+                tw = ST.sky_light(rec, camera_words(cam), f32_options(LIGHT_DEFAULTS, lopts), tw_pyr)
+                m = check_pass_against_twin(got, tw, rec, (sname, fname, vname))
+                lines.append("pass     %-26s %-9s %-8s " % (sname, fname, vname) + " ".join("%s %.2e" % kv for kv in m.items()))
+                for k, v in m.items():
+                    worst[k] = max(worst.get(k, 0.0), v)
+    print("worst", worst)
+    _margin_lines["2 pass"] = ["worst    " + " ".join("%s %.2e" % kv for kv in worst.items())] + lines
+    write_margins()
+    assert os.path.exists(MARGINS)
+
+
+# ---- 5. the stand-alone program under the sanitizers ---------------------------------------------------------------------------------------
+
+def write_case(path, sky, ropts, cam, rec, lopts):
+    with open(path, "wb") as f:
+        f.write(radiance_case(sky, ropts).tobytes())
+        f.write(light_case(cam, lopts).tobytes())
+        f.write(sky["image"].tobytes())
+        f.write(np.ascontiguousarray(rec, W.RENDER_PIXEL).tobytes())
+
+
+def test_stand_alone_harness_runs_clean_under_the_sanitizers(tmp_path, harness, lit_pictures):
+    """the harness as a program of its own (-DSKY_LIGHT_HARNESS_MAIN), built with -fsanitize=address,undefined, on the twin's fields and every
+    awkward case: what it writes is the shared library's"""
+    exe = str(tmp_path / "sky_light_harness_main")
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                    "-Wno-unknown-pragmas", "-DSKY_LIGHT_HARNESS_MAIN", "-I", CSRC, HARNESS_SRC, "-o", exe], check=True)
+    cam = lit_pictures["cam"]
+    cases = [("synthetic", sky_of(gradient_panorama(64, 32), 1, 1.3), dict(levels=4, samples=16), cam, light_records(cam, 1), None),
+             ("sea, reduced noisy sky", sky_of(noisy_panorama(128, 64), 0, 0.8), dict(levels=3, samples=8, base_width=32), cam, lit_pictures["sea"],
+              dict(ambient_energy=2.5, reflection_energy=0.7, specular=1.0)),
+             ("calm, a 4 x 2 sky", sky_of(noisy_panorama(4, 2)), dict(levels=2, samples=5, base_width=16), cam, lit_pictures["calm"], None)]
+    for name, c in awkward_cases().items():
+        if name != "a 2 x 1 sky":
+            cases.append((name, c["sky"], c["radiance"], c["cam"], awkward_records(c["cam"]), c.get("light")))
+    for k, (name, sky, ropts, cam, rec, lopts) in enumerate(cases):
+        path, out = str(tmp_path / f"case{k}.bin"), str(tmp_path / f"case{k}.out")
+        write_case(path, sky, ropts, cam, rec, lopts)
+        r = subprocess.run([exe, path, out], capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, (name, r.stdout + r.stderr)
+        assert r.stdout.endswith("ok\n") and "not_finite=0" in r.stdout and "idempotent=1" in r.stdout, (name, r.stdout)
+        assert "runtime error" not in r.stderr and "Sanitizer" not in r.stderr, (name, r.stderr)
+        pyr = CpuPyramid(harness, sky, ropts)
+        want = b"".join(pyr.R(j).tobytes() for j in range(pyr.levels)) + pyr.E.tobytes() + pyr.apply(rec, cam, lopts)["rec"].tobytes()
+        assert open(out, "rb").read() == want, name
+
+
+# ---- 6-12. on the GPU -----------------------------------------------------------------------------------------------------------------------
+
+def gpu_radiance(gen, sky, ropts=None):
+    """(the Sky, the Radiance) of a sky_of dict"""
+    handle = gpu_sky(gen, sky)
+    return handle, gen.radiance_create(handle, ropts)
+
+
+def same_pyramid(gen, radiance, pyr, what):
+    assert radiance.levels == pyr.levels, what
+    for k in range(pyr.levels):
+        got = gen.radiance_level(radiance, k)
+        assert got.shape == pyr.R(k).shape and got.tobytes() == pyr.R(k).tobytes(), (what, k)
+    assert gen.radiance_level(radiance, "irradiance").tobytes() == pyr.E.tobytes(), (what, "E")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("size,base_width", [((64, 32), 0), ((256, 128), 64)])
+@pytest.mark.parametrize("levels", [4, 6])
+@pytest.mark.parametrize("samples", [16, 64])
+def test_gpu_pyramid_is_the_cpu_builds_bit_for_bit(harness, size, base_width, levels, samples):
+    """every level and E read back, for a gradient sky through the sRGB table and a noisy raw one"""
+    gen = bare_context()
+    ropts = dict(levels=levels, samples=samples, base_width=base_width)
+    for image, srgb, energy in ((gradient_panorama(*size), 1, 1.3), (noisy_panorama(*size), 0, 0.8)):
+        sky = sky_of(image, srgb, energy)
+        handle, radiance = gpu_radiance(gen, sky, ropts)
+        same_pyramid(gen, radiance, CpuPyramid(harness, sky, ropts), (size, levels, samples, srgb))
+        gen.radiance_destroy(radiance)
+        gen.sky_destroy(handle)
+    gen.free()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("width,height", [(67, 45), (160, 96)])
+def test_gpu_pass_is_the_cpu_builds_bit_for_bit(harness, width, height):
+    """67 x 45 records: partial blocks and waves on both axes; the synthetic field under two pyramids and two sets of options, then the awkward
+    records and a camera that is not finite"""
+    gen = bare_context()
+    cam = look((0.0, 8.0, 0.0), 20.0, -4.0, width=width, height=height)
+    rec = light_records(cam, 100 + width)
+    for sky, ropts in ((sky_of(gradient_panorama(64, 32), 1, 1.3), None), (sky_of(noisy_panorama(256, 128), 0, 0.8), dict(levels=4, samples=16, base_width=64))):
+        handle, radiance = gpu_radiance(gen, sky, ropts)
+        pyr = CpuPyramid(harness, sky, ropts)
+        for lopts in (None, dict(ambient_energy=2.5, reflection_energy=0.7, specular=1.0)):
+            want = pyr.apply(rec, cam, lopts)["rec"]
+            got = gen.sky_light_apply(radiance, cam, rec, lopts)
+            same_records(got, want, (ropts, lopts))
+            same_records(gen.sky_light_apply(radiance, cam, got, lopts), want, "twice")
+        odd = awkward_records(cam)
+        same_records(gen.sky_light_apply(radiance, cam, odd), pyr.apply(odd, cam)["rec"], "awkward")
+        nan_cam = look((0.0, 8.0, 0.0), 20.0, -4.0, width=width, height=height)
+        nan_cam.basis[0] = float("nan")
+        assert gen.sky_light_apply(radiance, nan_cam, rec).tobytes() == rec.tobytes()
+        gen.radiance_destroy(radiance)
+        gen.sky_destroy(handle)
+    gen.free()
+
+
+@pytest.mark.gpu
+def test_gpu_whole_frame_is_the_cpu_chain_bit_for_bit(harness, env_harness, mesh_harness, solid_harness, billboard_harness):
+    """test_environment's whole frame with the new pass in it: ow_mesh_draw_async -> ow_solid_draw_async -> ow_radiance_light_apply_async ->
+    ow_environment_apply_async -> ow_billboard_draw_async -> ow_present_async (s = 2) on device buffers, one read-back, against the CPU builds
+    chained in the same order; the frame again gives the same bytes; no call synchronised; without the pass the frame is the parent's"""
+    import torch
+    gen, params, sc, bodies, spray = frame_scene()
+    cam = look(**FRAME_CAM)
+    mat = material()
+    m = gpu_material(gen, mat)
+    water = grid(*FRAME_WATER)
+    mesh = gen.mesh_create(*water)
+    shape = box(FRAME_SHAPE)
+    solid = gen.solid_create(*shape)
+    pano = sky_of(gradient_panorama(), 1, 1.2)
+    sky, radiance = gpu_radiance(gen, pano)
+    origin = W.clipmap_origin(cam.position, 4.0)
+    frames = [device_frame(cam, 2), device_frame(cam, 2), device_frame(cam, 2)]
+    gen.mesh_draw(mesh, cam, origin, sc)                       # the draws' scratch exists from here on
+    gen.solid_draw(solid, bodies, cam, pixels=True)
+    gen.spray_draw(spray, m, cam, pixels=True)
+    torch.cuda.synchronize()
+    syncs = gen.sync_stats()
+    for k, (rec_dev, rgba_dev, lin_dev) in enumerate(frames):
+        gen.mesh_draw_async(mesh, cam, origin, sc, None, rec_dev)
+        gen.solid_draw_async(solid, bodies, cam, None, rec_dev)
+        if k < 2:
+            gen.sky_light_apply_async(radiance, cam, rec_dev)
+        gen.environment_apply_async(cam, rec_dev, sky, FRAME_ENV)
+        gen.spray_draw_async(spray, m, cam, None, rec_dev)
+        gen.present_async(cam, rec_dev, rgba_dev, lin_dev, FRAME_PRESENT)
+    assert gen.sync_stats() == syncs                           # host_syncs has not moved
+    gen.sync()
+    got = [(records_of(cam, r), a.cpu().numpy(), l.cpu().numpy()) for r, a, l in frames]
+    for a, b in zip(got[0], got[1]):
+        assert a.tobytes() == b.tobytes()                      # the frame repeats to the byte
+    d, nm = gpu_maps(gen, 3)
+    bg = cpu_mesh_draw(mesh_harness, d, nm, sc, water, origin, cam)["rec"]
+    mid = cpu_solid_draw(solid_harness, shape, pose_transforms(gen, bodies), cam, None, bg, stride=24, flags=np.zeros(8, np.int32))["rec"]
+    lit = CpuPyramid(harness, pano).apply(mid, cam)
+    inst, _, draw = gen.spray_read(spray)
+    time = float(np.float32(gen.spray_stats(spray)["time"]))
+    for source, (rec, rgba, lin) in ((lit["rec"], got[0]), (mid, got[2])):      # with the pass, and the parent's frame without it
+        env = cpu_environment(env_harness, source, cam, FRAME_ENV, pano)["rec"]
+        fin = cpu_billboard_draw(billboard_harness, inst, cam, mat, time=time, order=draw, records=env)["rec"]
+        want = cpu_present(env_harness, fin, FRAME_PRESENT)
+        same_records(rec, fin, "mesh, solids, sky light, environment, billboards")
+        assert rgba.tobytes() == want["rgba"].tobytes() and lin.tobytes() == want["linear"].tobytes()
+    st = got[0][0]["status"]
+    hit = (st & HIT) != 0
+    assert ((st & LIT) != 0)[hit].all() and not ((st & LIT) != 0)[~hit].any() and not (got[2][0]["status"] & LIT).any()
+    assert (lit["spec"] > 0).any(axis=-1).sum() > 100 and ((st & SOLID) != 0).sum() > 20 and (lit["ambient"][(st & SOLID) != 0] > 0).all()
+    assert got[0][1].tobytes() != got[2][1].tobytes()          # the pass reaches the presented bytes
+    for h, fn in ((radiance, gen.radiance_destroy), (sky, gen.sky_destroy), (solid, gen.solid_destroy), (m, gen.spray_material_destroy), (mesh, gen.mesh_destroy),
+                  (spray, gen.spray_destroy), (bodies, gen.bodies_destroy)):
+        fn(h)
+    gen.free()
+
+
+def _order_case(stream=None, torch_stream=None):
+    """ticks, then the mesh draw, the sky light, the environment pass and the present with no host synchronisation, then more ticks, against a
+    context that stopped after the first half and ran the synchronous forms: the frame saw the maps of exactly its point of the stream"""
+    import torch
+    a, pa = make_gen(128, [0, 1], stream=stream)
+    b, pb = make_gen(128, [0, 1])
+    sc = scales_of(pa)
+    cam = look(**dict(CRATE_CAM, width=48, height=32))
+    water = grid(32, 4.0)
+    ha, hb = a.mesh_create(*water), b.mesh_create(*water)
+    pano = sky_of(gradient_panorama(), 1, 1.0)
+    (sa, ra), (sb, rb) = gpu_radiance(a, pano, dict(levels=4, samples=16)), gpu_radiance(b, pano, dict(levels=4, samples=16))
+    origin = W.clipmap_origin(cam.position, 4.0)
+    rec_dev, rgba_dev, lin_dev = device_frame(cam, 2)
+    a.mesh_draw(ha, cam, origin, sc)                           # the mesh draw's visibility scratch exists from here on
+    for g, p in ((a, pa), (b, pb)):
+        g.run(UPDATE_DELTA, p, 12)
+    torch.cuda.synchronize()
+    syncs = a.sync_stats()
+
+    def frame():
+        a.mesh_draw_async(ha, cam, origin, sc, None, rec_dev)
+        a.sky_light_apply_async(ra, cam, rec_dev)
+        a.environment_apply_async(cam, rec_dev, sa, FRAME_ENV)
+        a.present_async(cam, rec_dev, rgba_dev, lin_dev, FRAME_PRESENT)
+
+    if torch_stream is not None:
+        with torch.cuda.stream(torch_stream):
+            frame()
+            copy = rgba_dev.to("cpu", non_blocking=False)       # the caller's own work, ordered by its stream alone
+    else:
+        frame()
+    for _ in range(8):
+        a.update_all(UPDATE_DELTA, pa)
+    assert a.sync_stats() == syncs
+    a.sync()
+    _, bg = b.mesh_draw(hb, cam, origin, sc)
+    lit = b.sky_light_apply(rb, cam, bg)
+    assert ((lit["status"] & LIT) != 0).sum() > 100 and lit["color"].tobytes() != bg["color"].tobytes()
+    env = b.environment_apply(cam, lit, sb, FRAME_ENV)
+    want_rgba, want_lin = b.present(cam, env, FRAME_PRESENT, linear=True)
+    same_records(records_of(cam, rec_dev), env, "ordered")
+    assert rgba_dev.cpu().numpy().tobytes() == want_rgba.tobytes() and lin_dev.cpu().numpy().tobytes() == want_lin.tobytes()
+    if torch_stream is not None:
+        assert copy.numpy().tobytes() == want_rgba.tobytes()
+    later = a.present(cam, a.environment_apply(cam, a.sky_light_apply(ra, cam, a.mesh_draw(ha, cam, origin, sc)[1]), sa, FRAME_ENV), FRAME_PRESENT)
+    assert later.tobytes() != want_rgba.tobytes()               # the second half moved the maps
+    for g, s, r, h in ((a, sa, ra, ha), (b, sb, rb, hb)):
+        g.radiance_destroy(r)
+        g.sky_destroy(s)
+        g.mesh_destroy(h)
+        g.free()
+
+
+@pytest.mark.gpu
+def test_async_form_is_ordered_behind_a_tick_on_the_contexts_stream():
+    _order_case()
+
+
+@pytest.mark.gpu
+def test_async_form_is_ordered_behind_a_tick_on_a_callers_stream():
+    import torch
+    s = torch.cuda.Stream()
+    _order_case(stream=s.cuda_stream, torch_stream=s)
+
+
+@pytest.mark.gpu
+def test_foreign_and_orphaned_handles_are_refused_and_a_destroyed_sky_does_not_disturb_its_pyramid(harness):
+    """a sky or a pyramid of another context is OW_ERR_INVALID, an orphaned one OW_ERR_STATE and still the caller's to destroy; sizes that
+    do not halve are refused with nothing written; refusals write nothing; the asynchronous form never synchronises; the pyramid outlives
+    its sky"""
+    import torch
+    gen, other = bare_context(), bare_context()
+    pano = sky_of(gradient_panorama(), 1, 1.0)
+    ropts = dict(levels=4, samples=16)
+    pyr = CpuPyramid(harness, pano, ropts)
+    (sky, radiance), (foreign_sky, foreign) = gpu_radiance(gen, pano, ropts), gpu_radiance(other, pano, ropts)
+    lib = _lib.load()
+
+    def refused(fn, *args, status=_lib.OW_ERR_INVALID, **kw):
+        with pytest.raises(_lib.OceanWavesError) as e:
+            fn(*args, **kw)
+        assert e.value.status == status
+
+    refused(gen.radiance_create, foreign_sky, ropts)                                         # another context's sky
+    refused(gen.radiance_create, sky, dict(levels=7))                                        # 64 x 32 has no seventh level
+    odd_sky = gen.sky_create(gradient_panorama(66, 32))
+    refused(gen.radiance_create, odd_sky, dict(levels=3))                                    # 33 columns do not halve
+    gen.sky_destroy(odd_sky)
+    out = C.c_void_p(0x5EED)
+    assert lib.ow_radiance_create(gen.context, None, None, C.byref(out)) == _lib.OW_ERR_INVALID and out.value == 0x5EED
+    refused(gen.radiance_level, radiance, 4)
+    refused(gen.radiance_level, foreign, 0)
+    # the sky goes: the pyramid is its own
+    gen.sky_destroy(sky)
+    filler = gen.sky_create(noisy_panorama(64, 32, 99))                                      # whatever reuses the sky's memory
+    same_pyramid(gen, radiance, pyr, "after its sky was destroyed")
+    torch.cuda.synchronize()
+    syncs = gen.sync_stats()
+    for w, h in ((24, 12), (96, 60), (24, 12)):
+        cam = level_camera(w, h)
+        rec_dev, _, _ = device_frame(cam, 1)
+        rec = light_records(cam, w)
+        rec_dev.copy_(torch.from_numpy(np.frombuffer(rec.tobytes(), np.uint8).reshape(-1, 128).copy()))
+        gen.sky_light_apply_async(radiance, cam, rec_dev)
+        assert gen.sync_stats() == syncs
+        torch.cuda.synchronize()
+        same_records(records_of(cam, rec_dev), pyr.apply(rec, cam)["rec"], (w, h))
+    cam = level_camera(24, 12)
+    rec_dev, _, _ = device_frame(cam, 1)
+    refused(gen.sky_light_apply_async, foreign, cam, rec_dev)                                # another context's pyramid
+    refused(gen.sky_light_apply, foreign, cam, np.zeros((12, 24), W.RENDER_PIXEL))
+    refused(gen.sky_light_apply_async, None, cam, rec_dev)
+    refused(gen.sky_light_apply_async, radiance, cam, rec_dev, {"specular": 2.0})
+    refused(gen.sky_light_apply_async, radiance, cam, rec_dev.data_ptr() + 4)                # records are read and written as 16-byte vectors
+    refused(gen.sky_light_apply_async, radiance, level_camera(0, 12), rec_dev)
+    torch.cuda.synchronize()
+    assert not rec_dev.any()
+    # lifetimes: the contexts go first; an orphaned pyramid can be destroyed and is refused by everything else
+    live = bare_context()
+    gen.free()
+    other.free()
+    assert lib.ow_radiance_light_apply_async(live.context, radiance.handle, C.byref(cam), None, rec_dev.data_ptr()) == _lib.OW_ERR_STATE
+    host = np.zeros((12, 24), W.RENDER_PIXEL)
+    assert lib.ow_radiance_light_apply(live.context, foreign.handle, C.byref(cam), None, host.ctypes.data) == _lib.OW_ERR_STATE
+    assert lib.ow_radiance_level(live.context, radiance.handle, 0, None, None, None, None) == _lib.OW_ERR_STATE
+    out = C.c_void_p(0x5EED)
+    assert lib.ow_radiance_create(live.context, foreign_sky.handle, None, C.byref(out)) == _lib.OW_ERR_STATE and out.value == 0x5EED
+    assert lib.ow_radiance_light_apply_async(None, radiance.handle, C.byref(cam), None, rec_dev.data_ptr()) == _lib.OW_ERR_INVALID
+    torch.cuda.synchronize()
+    assert not rec_dev.any() and not host.tobytes().strip(b"\0")
+    for h in (radiance, foreign):
+        lib.ow_radiance_destroy(None, h.handle)          # still the caller's to destroy; touches no freed memory
+    for h in (filler, foreign_sky):
+        lib.ow_sky_destroy(None, h.handle)
+    live.free()
+
+
+@pytest.mark.gpu
+def test_the_c_example_writes_the_python_wrappers_image(tmp_path):
+    """examples/sky_light_host.c at 256^2, a 48 x 32 PPM of 96 x 64 records, 40 steps, 4096 particles, against the wrapper on the same scene"""
+    exe = build_example(tmp_path)
+    ppm = str(tmp_path / "sky_light.ppm")
+    r = subprocess.run([exe, ppm, "48", "32", "40", "256", "4096", "2"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr
+    kv = dict(p.split("=") for p in r.stdout.split())
+    assert kv["finite"] == "1" and kv["environment_pixels"] == str(96 * 64) and (kv["record_width"], kv["record_height"]) == ("96", "64") and kv["levels"] == "6"
+    raw = open(ppm, "rb").read()
+    head = b"P6\n48 32\n255\n"
+    assert raw.startswith(head) and len(raw) == len(head) + 48 * 32 * 3
+    gen, params = make_gen(256, [0, 1, 2])
+    sc = scales_of(params)
+    spray = gen.spray_create({"amount": 4096})
+    bodies = gen.bodies_create(*example_crates())
+    for _ in range(40):
+        gen.update_all(UPDATE_DELTA, params)
+        gen.bodies_step(bodies, sc, 4, UPDATE_DELTA / 4, {"warm_start": True})
+        gen.spray_step(spray, UPDATE_DELTA, sc)
+    cam = W.camera((0.0, 10.0, -25.0), REF_BASIS, 75.0, 96, 64, 4000.0)
+    mesh = gen.mesh_create(*grid(128, 4.0))
+    dark = (0.0, 0.0, 0.0)
+    _, bg = gen.mesh_draw(mesh, cam, W.clipmap_origin(cam.position, 4.0), sc, {"falloff": True, "cull_back": True, "ambient_color": dark})
+    solid = gen.solid_create(*box(CRATE_SHAPE))
+    _, mid = gen.solid_draw(solid, bodies, cam, {"ambient_color": dark}, pixels=bg)
+    sky = gen.sky_create(example_panorama())
+    radiance = gen.radiance_create(sky)
+    lit = gen.sky_light_apply(radiance, cam, mid)
+    env = gen.environment_apply(cam, lit, sky)
+    m = gen.spray_material_create(*example_textures())
+    _, rec = gen.spray_draw(spray, m, cam, pixels=env)
+    rgba = gen.present(cam, rec, {"downsample": 2})
+    assert np.frombuffer(raw[len(head):], np.uint8).reshape(32, 48, 3).tobytes() == rgba[..., :3].tobytes()
+    assert int(kv["lit_pixels"]) == int(((rec["status"] & LIT) != 0).sum()) == int(((rec["status"] & HIT) != 0).sum()) > 1000
+    assert int(kv["sky_pixels"]) == int((((rec["status"] & ENV) != 0) & ((rec["status"] & HIT) == 0)).sum()) > 100
+    assert int(kv["crate_pixels"]) == int(((rec["status"] & SOLID) != 0).sum()) and int(kv["sprayed_pixels"]) == int((rec["reserved"][..., 1] > 0).sum())
+    assert rgba.tobytes() != gen.present(cam, gen.spray_draw(spray, m, cam, pixels=gen.environment_apply(cam, mid, sky))[1], {"downsample": 2}).tobytes()
+    for h, fn in ((m, gen.spray_material_destroy), (radiance, gen.radiance_destroy), (sky, gen.sky_destroy), (solid, gen.solid_destroy), (mesh, gen.mesh_destroy),
+                  (bodies, gen.bodies_destroy), (spray, gen.spray_destroy)):
+        fn(h)
+    gen.free()
