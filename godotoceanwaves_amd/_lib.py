@@ -32,6 +32,9 @@ OW_SOLID_MAX_INSTANCES, OW_SOLID_MAX_TRIANGLES = 65536, 65536
 OW_RAY_ENVIRONMENT = 32
 OW_RAY_SKY_LIT = 64
 OW_RADIANCE_MAX_LEVELS, OW_RADIANCE_MAX_SAMPLES, OW_RADIANCE_IRRADIANCE = 8, 256, -1
+OW_RAY_SHADOWED = 128
+OW_SHADOW_CAST_BOTH_SIDES, OW_SHADOW_RECEIVE_WATER = 1, 1
+OW_SHADOW_MIN_SIZE, OW_SHADOW_MAX_SIZE = 8, 8192
 OW_SKY_MAX_SIDE = 8192
 OW_PRESENT_MAX_DOWNSAMPLE = 4
 OW_FOG_EXPONENTIAL, OW_FOG_DEPTH = 0, 1
@@ -266,6 +269,18 @@ class ow_radiance_light_options(C.Structure):
                 ("reserved", C.c_uint32 * 12)]
 
 
+class ow_shadow_frame(C.Structure):
+    """struct ow_shadow_frame (64 bytes): the light's orthographic box (ow_shadow_frame_default: the scene's sun over 100 m about the origin)"""
+    _fields_ = [("light_direction", C.c_float * 3), ("half_extent", C.c_float), ("center", C.c_float * 3), ("depth_range", C.c_float),
+                ("flags", C.c_uint32), ("lane_box", C.c_int32), ("reserved", C.c_uint32 * 6)]
+
+
+class ow_shadow_options(C.Structure):
+    """struct ow_shadow_options (64 bytes); a NULL pointer = bias 0, normal_bias 6.464, opacity 0.8, 5 taps, water does not receive"""
+    _fields_ = [("bias", C.c_float), ("normal_bias", C.c_float), ("opacity", C.c_float), ("filter_taps", C.c_int32), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32 * 11)]
+
+
 class ow_mesh_vertex(C.Structure):
     """struct ow_mesh_vertex (48 bytes): the vertex stage's record of a mesh draw"""
     _fields_ = [("position", C.c_float * 3), ("wave_height", C.c_float), ("uv", C.c_float * 2), ("distance_factor", C.c_float),
@@ -384,6 +399,17 @@ SIGNATURES = {
     "ow_radiance_level": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), C.c_void_p]),
     "ow_radiance_light_apply": (C.c_int, [C.c_void_p, C.c_void_p, _P(ow_camera), _P(ow_radiance_light_options), C.c_void_p]),
     "ow_radiance_light_apply_async": (C.c_int, [C.c_void_p, C.c_void_p, _P(ow_camera), _P(ow_radiance_light_options), C.c_void_p]),
+    "ow_shadow_frame_default": (None, [_P(ow_shadow_frame)]),
+    "ow_shadow_options_default": (None, [_P(ow_shadow_options)]),
+    "ow_shadow_map_create": (C.c_int, [C.c_void_p, C.c_int32, _P(C.c_void_p)]),
+    "ow_shadow_map_destroy": (None, [C.c_void_p, C.c_void_p]),
+    "ow_shadow_map_begin": (C.c_int, [C.c_void_p, C.c_void_p, _P(ow_shadow_frame)]),
+    "ow_shadow_map_cast": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
+    "ow_shadow_map_cast_instances": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
+    "ow_shadow_map_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ow_shadow_apply": (C.c_int, [C.c_void_p, C.c_void_p, _P(ow_camera), _P(ow_shadow_options), C.c_void_p, C.c_void_p]),
+    "ow_shadow_apply_async": (C.c_int, [C.c_void_p, C.c_void_p, _P(ow_camera), _P(ow_shadow_options), C.c_void_p, C.c_void_p]),
+    "ow_shadow_stats": (C.c_int, [C.c_void_p, C.c_void_p, _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64)]),
     "ow_get_maps_f32": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
     "ow_get_spectrum": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "ow_get_intermediate": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),

@@ -11,8 +11,8 @@ LIB = os.path.join(HERE, "libocean_waves.so")
 ARCH = "gfx950"
 
 # translation unit -> extra flags.  ow_spectrum.hip is built with FP contraction off: its omega(k)
-# plane must be bit-identical to the oracle's; ow_consumer.hip, ow_mesh.hip, ow_spray.hip, ow_spray_draw.hip, ow_solid.hip, ow_environment.hip and ow_sky_light.hip likewise (the sampling,
-# raster, particle, billboard, solid, environment and sky-light arithmetic is checked operation for operation).
+# plane must be bit-identical to the oracle's; ow_consumer.hip, ow_mesh.hip, ow_spray.hip, ow_spray_draw.hip, ow_solid.hip, ow_environment.hip, ow_sky_light.hip and ow_shadow.hip likewise (the sampling,
+# raster, particle, billboard, solid, environment, sky-light and shadow arithmetic is checked operation for operation).
 UNITS = {
     "ow_frame.hip": [],
     "ow_spectrum.hip": ["-ffp-contract=off"],
@@ -27,6 +27,7 @@ UNITS = {
     "ow_solid.hip": ["-ffp-contract=off"],
     "ow_environment.hip": ["-ffp-contract=off"],
     "ow_sky_light.hip": ["-ffp-contract=off"],
+    "ow_shadow.hip": ["-ffp-contract=off"],
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-fno-fast-math", "-fvisibility=hidden", "-Wall", "-Wno-unused-function"]
 

@@ -1,10 +1,10 @@
 // ow_consumer_host.hip -- the read side of include/ocean_waves.h: host wrappers around the kernels of ow_consumer.hip, ow_velocity.hip,
-// ow_mesh.hip, ow_spray.hip, ow_spray_draw.hip, ow_solid.hip, ow_environment.hip and ow_sky_light.hip (surface samples and queries, buoyancy, floating bodies, ray casts, camera views, mesh draws,
-// the velocity layers, the sea-spray emitter and its billboards, the solids, the environment pass, the present, the radiance pyramid and its pass).  Plain C++ over
+// ow_mesh.hip, ow_spray.hip, ow_spray_draw.hip, ow_solid.hip, ow_environment.hip, ow_sky_light.hip and ow_shadow.hip (surface samples and queries, buoyancy, floating bodies, ray casts, camera views, mesh draws,
+// the velocity layers, the sea-spray emitter and its billboards, the solids, the environment pass, the present, the radiance pyramid and its pass, the sun shadows).  Plain C++ over
 // the HIP runtime API; the context and the scheduler's services come from ow_context.h.  The synchronous calls' device halves (ow_internal.h
 // *_round_trip) also serve a group's gathered arrays (ow_group.hip).
 //
-// Each repeated thing has one owner here.  The seven handle kinds (body sets, meshes, emitters, billboard materials, solid shapes, skies, radiance pyramids) share one life cycle:
+// Each repeated thing has one owner here.  The eight handle kinds (body sets, meshes, emitters, billboard materials, solid shapes, skies, radiance pyramids, shadow maps) share one life cycle:
 // Layout places a block's arrays, new_handle allocates, finish_create synchronises and registers, release_handle is the device half of a
 // destroy, check_handle the one ownership check.  The four picture kinds (views, mesh draws, billboard draws, solid draws) keep their launch in one
 // *_enqueue each, used by the asynchronous form directly and by the synchronous form through picture_round_trip.
@@ -2087,6 +2087,242 @@ ow_status ow_radiance_light_apply_async(ow_context *c, ow_radiance *radiance, co
     if (ow_status st = check_pixel_alignment(nullptr, pixels_dev); st != OW_OK) return st;
     OW_HIP(hipSetDevice(c->device));
     OW_HIP(ow::launch_sky_light_apply(cp, lp, (ow::RenderPixel *)pixels_dev, main_stream(c)));
+    return OW_OK;
+}
+
+}  // extern "C"
+
+/* ---- the sun shadows (ow_shadow.h, ow_shadow.hip) ---- */
+
+namespace {
+constexpr size_t kShadowHead = 256;  // the four counters, at the head of the map's block
+
+void shadow_frame_defaults(ow_shadow_frame *o) {
+    ow_render_options ro;
+    render_defaults(&ro);
+    std::memset(o, 0, sizeof(*o));
+    for (int k = 0; k < 3; ++k) o->light_direction[k] = ro.light_direction[k];
+    o->half_extent = 50.0f;
+    o->depth_range = 100.0f;
+}
+// main.tscn:114-116
+void shadow_defaults(ow_shadow_options *o) {
+    std::memset(o, 0, sizeof(*o));
+    o->bias = 0.0f;
+    o->normal_bias = 6.464f;
+    o->opacity = 0.8f;
+    o->filter_taps = 5;
+}
+
+// ow_shadow_frame -> the frame's constants for a map of side `size` (ow_shadow.h shadow_params), after the checks
+ow_status resolve_shadow_frame(const ow_shadow_frame *f, int size, ow::ShadowParams *P) {
+    static_assert(sizeof(ow_shadow_frame) == sizeof(ow::ShadowFrame) && offsetof(ow_shadow_frame, center) == offsetof(ow::ShadowFrame, center) &&
+                      offsetof(ow_shadow_frame, flags) == offsetof(ow::ShadowFrame, flags) &&
+                      offsetof(ow_shadow_frame, lane_box) == offsetof(ow::ShadowFrame, lane_box) &&
+                      offsetof(ow_shadow_frame, reserved) == offsetof(ow::ShadowFrame, reserved) && sizeof(ow_shadow_options) == sizeof(ow::ShadowOptions) &&
+                      offsetof(ow_shadow_options, flags) == offsetof(ow::ShadowOptions, flags) &&
+                      offsetof(ow_shadow_options, reserved) == offsetof(ow::ShadowOptions, reserved) && OW_RAY_SHADOWED == ow::kRayShadowed &&
+                      OW_RAY_ENVIRONMENT == ow::kRayEnvironmentDone && OW_SHADOW_CAST_BOTH_SIDES == ow::kShadowCastBothSides &&
+                      OW_SHADOW_RECEIVE_WATER == ow::kShadowReceiveWater && OW_SHADOW_MIN_SIZE == ow::kShadowMinSize && OW_SHADOW_MAX_SIZE == ow::kShadowMaxSize,
+                  "record layout");
+    if (!f) return fail(OW_ERR_INVALID, "null frame");
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(f->light_direction[k]) || !std::isfinite(f->center[k]))
+            return fail(OW_ERR_INVALID, "ow_shadow_frame: light_direction or center is not finite");
+    if (!(f->half_extent > 0.0f && f->half_extent <= ow::kShadowRangeMax)) return fail(OW_ERR_INVALID, "ow_shadow_frame: half_extent outside (0,1e6]");
+    if (!(f->depth_range > 0.0f && f->depth_range <= ow::kShadowRangeMax)) return fail(OW_ERR_INVALID, "ow_shadow_frame: depth_range outside (0,1e6]");
+    if (f->lane_box < -1 || f->lane_box > 64) return fail(OW_ERR_INVALID, "lane_box %d outside [-1,64]", f->lane_box);
+    if (f->flags & ~OW_SHADOW_CAST_BOTH_SIDES) return fail(OW_ERR_INVALID, "unknown shadow frame flags 0x%x", f->flags);
+    if (ow_status st = check_reserved(f->reserved, "ow_shadow_frame"); st != OW_OK) return st;
+    ow::ShadowFrame fr;
+    std::memcpy(&fr, f, sizeof(fr));
+    *P = ow::shadow_params(fr, size);
+    if (!P->ok) return fail(OW_ERR_INVALID, "light_direction has zero length");
+    return OW_OK;
+}
+
+ow_status resolve_shadow_options(const ow_shadow_options *opts, ow::ShadowApply *ap) {
+    ow_shadow_options def;
+    if (!opts) {
+        shadow_defaults(&def);
+        opts = &def;
+    }
+    if (!in_range(opts->bias, -ow::kShadowRangeMax, ow::kShadowRangeMax)) return fail(OW_ERR_INVALID, "ow_shadow_options: bias outside [-1e6,1e6]");
+    if (!in_range(opts->normal_bias, -ow::kShadowRangeMax, ow::kShadowRangeMax)) return fail(OW_ERR_INVALID, "ow_shadow_options: normal_bias outside [-1e6,1e6]");
+    if (!in_range(opts->opacity, 0.0f, 1.0f)) return fail(OW_ERR_INVALID, "ow_shadow_options: opacity outside [0,1]");
+    const int taps = opts->filter_taps == 0 ? 5 : opts->filter_taps;
+    if (taps < 1 || taps > 9 || taps % 2 == 0) return fail(OW_ERR_INVALID, "filter_taps %d is not one of 0, 1, 3, 5, 7, 9", opts->filter_taps);
+    if (opts->flags & ~OW_SHADOW_RECEIVE_WATER) return fail(OW_ERR_INVALID, "unknown shadow flags 0x%x", opts->flags);
+    if (ow_status st = check_reserved(opts->reserved, "ow_shadow_options"); st != OW_OK) return st;
+    ow::ShadowOptions so;
+    std::memcpy(&so, opts, sizeof(so));
+    *ap = ow::shadow_apply_params(so, true);
+    return OW_OK;
+}
+
+ow_status check_shadow_map(const ow_context *c, const ow_shadow_map *map) { return check_handle(c, map, "shadow map"); }
+
+// the argument checks both forms of the pass share: ow_solid_draw's, in its order, then the context and the map
+ow_status check_shadow_apply(const ow_context *c, const ow_shadow_map *map, const ow_camera *camera, const ow_shadow_options *opts, const void *pixels,
+                             ow::CameraParams *cp, ow::ShadowApply *ap) {
+    if (!pixels) return fail(OW_ERR_INVALID, "null argument: the records");
+    if (ow_status st = resolve_camera(camera, cp); st != OW_OK) return st;
+    if (ow_status st = resolve_shadow_options(opts, ap); st != OW_OK) return st;
+    if (ow_status st = check_shadow_map(c, map); st != OW_OK) return st;
+    ap->camera_ok = ow::mesh_camera_ok(*cp) ? 1 : 0;
+    return OW_OK;
+}
+
+// One cast's launches on the context's stream.  Sources as for solid_enqueue: a body set's resident records, or `upload` (copied into the
+// map's scratch first).
+ow_status shadow_cast_enqueue(ow_context *c, ow_shadow_map *map, const ow_solid *solid, const ow_bodies *set, int first, const float *upload, int count) {
+    if (!map->P.ok) return fail(OW_ERR_STATE, "the shadow map has no frame: ow_shadow_map_begin first");
+    OW_HIP(hipSetDevice(c->device));
+    Layout L;
+    const size_t v_off = L.take((size_t)count * solid->num_vertices * sizeof(ow::ShadowVertex));
+    const size_t t_off = L.take(upload ? (size_t)count * ow::kSolidTransformFloats * sizeof(float) : 0);
+    if (ow_status st = sync_before_growth(c, map->scratch, L.total); st != OW_OK) return st;
+    if (ow_status st = map->scratch.ensure(L.total, 0, 1, "bytes of shadow scratch"); st != OW_OK) return st;
+    char *base = (char *)map->scratch.ptr;
+    hipStream_t s = main_stream(c);
+    ow::ShadowArrays A;
+    A.local = solid->local;
+    A.indices = solid->indices;
+    A.num_vertices = solid->num_vertices;
+    A.num_triangles = solid->num_triangles;
+    A.counters = map->counters;
+    A.verts = (ow::ShadowVertex *)(base + v_off);
+    A.map = map->map;
+    ow::SolidInstances in;
+    in.count = count;
+    if (set) {
+        in.transforms = (const float *)(set->A.records + first);
+        in.flags = set->A.flags + first;
+        in.stride = (int)(sizeof(ow::BuoyancyBody) / sizeof(float));
+    } else {
+        in.transforms = (const float *)(base + t_off);
+        in.flags = nullptr;
+        in.stride = ow::kSolidTransformFloats;
+        if (count > 0) OW_HIP(hipMemcpyAsync(base + t_off, upload, (size_t)count * ow::kSolidTransformFloats * sizeof(float), hipMemcpyHostToDevice, s));
+    }
+    OW_HIP(ow::launch_shadow_cast(A, in, map->P, s));
+    ++map->casts;
+    map->instances_triangles += (uint64_t)count * solid->num_triangles;
+    return OW_OK;
+}
+}  // namespace
+
+extern "C" {
+
+void ow_shadow_frame_default(ow_shadow_frame *out) {
+    if (out) shadow_frame_defaults(out);
+}
+void ow_shadow_options_default(ow_shadow_options *out) {
+    if (out) shadow_defaults(out);
+}
+
+ow_status ow_shadow_map_create(ow_context *c, int32_t size, ow_shadow_map **out) {
+    if (!out) return fail(OW_ERR_INVALID, "null argument");
+    if (size < OW_SHADOW_MIN_SIZE || size > OW_SHADOW_MAX_SIZE) return fail(OW_ERR_INVALID, "shadow map size %d outside [%d,%d]", size, OW_SHADOW_MIN_SIZE, OW_SHADOW_MAX_SIZE);
+    if (!c) return fail(OW_ERR_INVALID, "null context");
+    Layout L;
+    const size_t c_off = L.take(kShadowHead), m_off = L.take((size_t)size * size * sizeof(uint32_t));
+    ow_shadow_map *map;
+    if (ow_status st = new_handle(c, L.total, "shadow map", &map); st != OW_OK) return st;
+    char *base = (char *)map->block;
+    map->size = size;
+    map->device = c->device;
+    map->counters = (uint32_t *)(base + c_off);
+    map->map = (uint32_t *)(base + m_off);
+    hipStream_t s = main_stream(c);
+    ow::ShadowArrays A{};
+    A.counters = map->counters;
+    A.map = map->map;
+    const bool enqueued = ow::launch_shadow_clear(A, size, s) == hipSuccess;
+    return finish_create(c, map, s, enqueued, "shadow map clear", out);
+}
+
+void ow_shadow_map_destroy(ow_context *, ow_shadow_map *map) {
+    if (!map) return;
+    release_handle(map);
+    (void)hipSetDevice(map->device);  // an orphan's scratch is still there: ow_destroy frees the blocks
+    map->scratch.release();
+    delete map;
+}
+
+ow_status ow_shadow_map_begin(ow_context *c, ow_shadow_map *map, const ow_shadow_frame *frame) {
+    ow::ShadowParams P;
+    if (ow_status st = resolve_shadow_frame(frame, OW_SHADOW_MIN_SIZE, &P); st != OW_OK) return st;  // the checks, before the map is looked at
+    if (ow_status st = check_shadow_map(c, map); st != OW_OK) return st;
+    if (ow_status st = resolve_shadow_frame(frame, map->size, &P); st != OW_OK) return st;
+    OW_HIP(hipSetDevice(c->device));
+    ow::ShadowArrays A{};
+    A.counters = map->counters;
+    A.map = map->map;
+    OW_HIP(ow::launch_shadow_clear(A, map->size, main_stream(c)));
+    map->P = P;
+    map->casts = map->instances_triangles = 0;
+    return OW_OK;
+}
+
+ow_status ow_shadow_map_cast(ow_context *c, ow_shadow_map *map, ow_solid *solid, ow_bodies *bodies, int32_t first_body, int32_t body_count) {
+    if (ow_status st = check_shadow_map(c, map); st != OW_OK) return st;
+    if (ow_status st = check_handle(c, solid, "solid"); st != OW_OK) return st;
+    if (ow_status st = check_solid_bodies(c, solid, bodies, first_body, body_count); st != OW_OK) return st;
+    return shadow_cast_enqueue(c, map, solid, bodies, first_body, nullptr, body_count);
+}
+
+ow_status ow_shadow_map_cast_instances(ow_context *c, ow_shadow_map *map, ow_solid *solid, const float *transforms, int32_t count) {
+    if (count < 0 || count > OW_SOLID_MAX_INSTANCES) return fail(OW_ERR_INVALID, "count %d outside [0,%d]", count, OW_SOLID_MAX_INSTANCES);
+    if (count > 0 && !transforms) return fail(OW_ERR_INVALID, "null argument");
+    if (ow_status st = check_shadow_map(c, map); st != OW_OK) return st;
+    if (ow_status st = check_handle(c, solid, "solid"); st != OW_OK) return st;
+    if (ow_status st = check_solid_count(solid, count); st != OW_OK) return st;
+    if (ow_status st = shadow_cast_enqueue(c, map, solid, nullptr, 0, transforms, count); st != OW_OK) return st;
+    return sync_stream(c, 0);
+}
+
+ow_status ow_shadow_map_read(ow_context *c, ow_shadow_map *map, float *depth_out) {
+    if (!depth_out) return fail(OW_ERR_INVALID, "null argument");
+    if (ow_status st = check_shadow_map(c, map); st != OW_OK) return st;
+    return read_back(c, depth_out, map->map, (size_t)map->size * map->size * sizeof(float));
+}
+
+ow_status ow_shadow_apply(ow_context *c, ow_shadow_map *map, const ow_camera *camera, const ow_shadow_options *opts, ow_render_pixel *pixels_inout,
+                          void *rgba8_out) {
+    ow::CameraParams cp;
+    ow::ShadowApply ap;
+    if (ow_status st = check_shadow_apply(c, map, camera, opts, pixels_inout, &cp, &ap); st != OW_OK) return st;
+    OW_HIP(hipSetDevice(c->device));
+    return picture_round_trip(c, (size_t)cp.width * cp.height, rgba8_out, pixels_inout, true, 0, [&](uint32_t *rgba_dev, ow::RenderPixel *pixels_dev) {
+        OW_HIP(ow::launch_shadow_apply(map->map, cp, map->P, ap, pixels_dev, rgba_dev, main_stream(c)));
+        return OW_OK;
+    });
+}
+
+ow_status ow_shadow_apply_async(ow_context *c, ow_shadow_map *map, const ow_camera *camera, const ow_shadow_options *opts, ow_render_pixel *pixels_dev,
+                                void *rgba8_dev) {
+    ow::CameraParams cp;
+    ow::ShadowApply ap;
+    if (ow_status st = check_shadow_apply(c, map, camera, opts, pixels_dev, &cp, &ap); st != OW_OK) return st;
+    if (ow_status st = check_pixel_alignment(rgba8_dev, pixels_dev); st != OW_OK) return st;
+    OW_HIP(hipSetDevice(c->device));
+    OW_HIP(ow::launch_shadow_apply(map->map, cp, map->P, ap, (ow::RenderPixel *)pixels_dev, (uint32_t *)rgba8_dev, main_stream(c)));
+    return OW_OK;
+}
+
+ow_status ow_shadow_stats(ow_context *c, ow_shadow_map *map, uint64_t *casts, uint64_t *skipped_instances, uint64_t *culled, uint64_t *drawn,
+                          uint64_t *scratch_bytes) {
+    if (ow_status st = check_shadow_map(c, map); st != OW_OK) return st;
+    if (skipped_instances || culled || drawn) {
+        uint32_t w[4] = {0, 0, 0, 0};
+        if (ow_status st = read_back(c, w, map->counters, sizeof(w)); st != OW_OK) return st;
+        if (skipped_instances) *skipped_instances = w[ow::kShadowSkippedInstances];
+        if (culled) *culled = w[ow::kShadowCulled];
+        if (drawn) *drawn = (uint64_t)w[ow::kShadowLane] + w[ow::kShadowWave];
+    }
+    if (casts) *casts = map->casts;
+    if (scratch_bytes) *scratch_bytes = map->scratch.bytes;
     return OW_OK;
 }
 

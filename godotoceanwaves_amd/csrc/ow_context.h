@@ -66,6 +66,16 @@ struct ow_radiance : ow::Handle {
     ow::RadianceLevel E{};
 };
 
+// a shadow map (ow_shadow_map_create): the block holds the counters and the depth words; the casters' vertex records (and uploaded
+// transforms) lie in the map's own grow-only scratch, which goes with the map
+struct ow_shadow_map : ow::Handle {
+    int size = 0, device = 0;
+    uint32_t *counters = nullptr, *map = nullptr;
+    ow::ShadowParams P{};        // the frame of the last ow_shadow_map_begin (P.ok == 0: none yet)
+    ow::DeviceScratch scratch;
+    uint64_t casts = 0, instances_triangles = 0;  // since the last begin
+};
+
 struct ow_context {
     int n = 0, cascades = 0, layers = 0, device = 0;
     float depth = 20.0f;
@@ -183,6 +193,7 @@ struct ow_context {
     // records of the synchronous ow_render_view, ow_mesh_draw and ow_billboard_draw; mesh_vis: the draw's visibility words (both forms);
     // billboard: a billboard draw's counters, bin masks, sprite records and (ow_billboard_draw_instances) the uploaded instances;
     // solid: a solid draw's counters, transformed vertex records, visibility words and (ow_solid_draw_instances) the uploaded transforms.
+    // The synchronous ow_shadow_apply uses render_pixels and render_rgba; a shadow map's scratch is the map's own (ow_shadow_map).
     // The synchronous ow_environment_apply uses render_pixels; the synchronous ow_present render_pixels for the records and render_rgba for both
     // outputs (the float4 pixels first, then the RGBA8 words).  Their asynchronous forms use no scratch.
     ow::DeviceScratch query_scratch, buoy_scratch, ray_scratch, render_rgba, render_pixels, mesh_vis, billboard, solid;

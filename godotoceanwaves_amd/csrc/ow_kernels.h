@@ -10,6 +10,7 @@
 #include "ow_mesh.h"
 #include "ow_render.h"
 #include "ow_rigid.h"
+#include "ow_shadow.h"
 #include "ow_sky_light.h"
 #include "ow_solid.h"
 #include "ow_spray.h"
@@ -158,6 +159,23 @@ hipError_t launch_present(int out_width, int out_height, const PresentParams &pp
 hipError_t launch_radiance_build(const RadianceBuild &b, hipStream_t s);
 // k_sky_light_apply over cam.width x cam.height records, rewritten in place, on `s`; nothing is launched for a camera that is not finite
 hipError_t launch_sky_light_apply(const CameraParams &cam, const SkyLightParams &lp, RenderPixel *pixels_dev, hipStream_t s);
+
+// the sun shadows (ow_shadow.hip; the frame, the coverage rule, the filter and the record's arithmetic in ow_shadow.h)
+struct ShadowArrays {
+    const float *local;      // [num_vertices][3] the casting shape, as uploaded
+    const int32_t *indices;  // [num_triangles][3]
+    int num_vertices, num_triangles;
+    uint32_t *counters;      // [4] kShadowSkippedInstances .. kShadowWave since the last clear
+    ShadowVertex *verts;     // [instances][num_vertices] scratch
+    uint32_t *map;           // [size][size] the depth words
+};
+// k_shadow_clear over the map's size x size words and the counters, on `s`
+hipError_t launch_shadow_clear(const ShadowArrays &A, int size, hipStream_t s);
+// k_shadow_vertices over in.count instances, then k_shadow_raster, on `s`; nothing is launched without a frame (P.ok == 0) or instances
+hipError_t launch_shadow_cast(const ShadowArrays &A, const SolidInstances &in, const ShadowParams &P, hipStream_t s);
+// k_shadow_apply over cam.width x cam.height records, receivers rewritten in place, and the RGBA8 words (may be null), on `s`
+hipError_t launch_shadow_apply(const uint32_t *map, const CameraParams &cam, const ShadowParams &P, const ShadowApply &ap, RenderPixel *pixels_dev,
+                               uint32_t *rgba_dev, hipStream_t s);
 
 bool supported_map_size(int n);
 int kernel_family(int n, int slots, int mode);  // 1 standard, 2 layer-parallel, 3 compact: what launch_pass1/2 will use

@@ -158,6 +158,13 @@ class Radiance:
         self.handle, self.levels = handle, levels
 
 
+class ShadowMap:
+    """a device-resident sun shadow map (ow_shadow_map_create): WaveGenerator.shadow_map_create() makes it, shadow_map_destroy() ends it"""
+
+    def __init__(self, handle, size):
+        self.handle, self.size = handle, size
+
+
 class WaveGenerator:
     """assets/water/wave_generator.gd.  Typical use, as in water.gd:89-91,112-114:
 
@@ -1248,6 +1255,89 @@ class WaveGenerator:
         o = self.sky_light_options(options)
         _lib.check(self._lib.ow_radiance_light_apply_async(self.context, radiance.handle if radiance is not None else None, C.byref(camera), _ref(o),
                                                            _addr(pixels_device)))
+
+    # ---- the floating bodies' sun shadows (include/ocean_waves.h ow_shadow_*) ----
+    _SHADOW_FRAME_OWN = ("light_direction", "half_extent", "center", "depth_range", "cast_both_sides", "lane_box")
+    _SHADOW_OWN = ("bias", "normal_bias", "opacity", "filter_taps", "receive_water")
+
+    @classmethod
+    def shadow_frame(cls, frame=None):
+        """an _lib.ow_shadow_frame, or None / a dict of light_direction, half_extent, center, depth_range, cast_both_sides and lane_box over
+        ow_shadow_frame_default's values (the scene's sun, 100 m about the origin, 100 m either side along the light)"""
+        if isinstance(frame, _lib.ow_shadow_frame):
+            return frame
+        frame = dict(frame or {})
+        flags = _lib.OW_SHADOW_CAST_BOTH_SIDES if frame.pop("cast_both_sides", False) else 0
+        o = cls._options(_lib.ow_shadow_frame, _lib.load().ow_shadow_frame_default, cls._SHADOW_FRAME_OWN, frame, "shadow frame")
+        o.flags |= flags
+        return o
+
+    @classmethod
+    def shadow_options(cls, options=None):
+        """None, an _lib.ow_shadow_options, or a dict of bias, normal_bias, opacity, filter_taps and receive_water over
+        ow_shadow_options_default's values (0, 6.464, 0.8, 5 taps, water does not receive)"""
+        if options is None or isinstance(options, _lib.ow_shadow_options):
+            return options
+        options = dict(options)
+        flags = _lib.OW_SHADOW_RECEIVE_WATER if options.pop("receive_water", False) else 0
+        o = cls._options(_lib.ow_shadow_options, _lib.load().ow_shadow_options_default, cls._SHADOW_OWN, options, "shadow")
+        o.flags |= flags
+        return o
+
+    def shadow_map_create(self, size):
+        """An empty size x size depth map from the sun, without a frame; returns a ShadowMap (shadow_map_destroy() it before free())"""
+        out = C.c_void_p()
+        _lib.check(self._lib.ow_shadow_map_create(self.context, int(size), C.byref(out)))
+        return ShadowMap(out, int(size))
+
+    def shadow_map_destroy(self, shadow_map):
+        self._destroy(shadow_map, self._lib.ow_shadow_map_destroy)
+
+    def shadow_map_begin(self, shadow_map, frame=None):
+        """Sets the frame and clears the map and its counters, enqueued in the generator's stream order without synchronising"""
+        _lib.check(self._lib.ow_shadow_map_begin(self.context, shadow_map.handle, C.byref(self.shadow_frame(frame))))
+
+    def shadow_map_cast(self, shadow_map, solid, bodies_set, first=0, count=None):
+        """Casts the shape at the resident poses of bodies [first, first + count) into the map, enqueued without synchronising"""
+        count = bodies_set.num_bodies - first if count is None else count
+        _lib.check(self._lib.ow_shadow_map_cast(self.context, shadow_map.handle, solid.handle, bodies_set.handle, int(first), int(count)))
+
+    def shadow_map_cast_instances(self, shadow_map, solid, transforms):
+        """shadow_map_cast over a host array of [count][12] transforms (basis rows, then the origin).  Synchronises."""
+        t = np.ascontiguousarray(transforms, np.float32).reshape(-1, 12)
+        _lib.check(self._lib.ow_shadow_map_cast_instances(self.context, shadow_map.handle, solid.handle, t.ctypes.data if len(t) else None, len(t)))
+
+    def shadow_map_read(self, shadow_map):
+        """(size, size) float32 depths in metres from the frame's near plane, FLT_MAX where nothing was cast.  Synchronises."""
+        out = np.zeros((shadow_map.size, shadow_map.size), np.float32)
+        _lib.check(self._lib.ow_shadow_map_read(self.context, shadow_map.handle, out.ctypes.data))
+        return out
+
+    def shadow_apply(self, shadow_map, camera, pixels, options=None, rgba=False):
+        """The sun's share of `pixels` ((H, W) RENDER_PIXEL records of the draws) darkened by the map: (the (H, W, 4) uint8 RGBA image or
+        None, the records with status, diffuse, specular and color rewritten (a copy)).  Call it after solid_draw and before
+        sky_light_apply and environment_apply.  Synchronises."""
+        o = self.shadow_options(options)
+        img, rec = self._picture(camera, pixels, rgba)
+        _lib.check(self._lib.ow_shadow_apply(self.context, shadow_map.handle if shadow_map is not None else None, C.byref(camera), _ref(o),
+                                             rec.ctypes.data, img.ctypes.data if img is not None else None))
+        return img, rec
+
+    def shadow_apply_async(self, shadow_map, camera, pixels_device, rgba_device=None, options=None):
+        """The pass over DEVICE records (mesh_draw_async's), in place, enqueued in the generator's stream order without synchronising"""
+        self._check_picture_buffers(camera, rgba_device, pixels_device)
+        o = self.shadow_options(options)
+        _lib.check(self._lib.ow_shadow_apply_async(self.context, shadow_map.handle if shadow_map is not None else None, C.byref(camera), _ref(o),
+                                                   _addr(pixels_device), _addr(rgba_device, True)))
+
+    def shadow_stats(self, shadow_map, counters=True):
+        """dict of the casts since the map's last begin, the scratch bytes held and, with counters (synchronising), the instances skipped and
+        the triangles culled and drawn"""
+        v = [C.c_uint64() for _ in range(5)]
+        _lib.check(self._lib.ow_shadow_stats(self.context, shadow_map.handle, C.byref(v[0]), *(C.byref(x) if counters else None for x in v[1:4]),
+                                             C.byref(v[4])))
+        keys = ("casts", "skipped_instances", "culled", "drawn", "scratch_bytes")
+        return {k: x.value for k, x in zip(keys, v) if counters or k in ("casts", "scratch_bytes")}
 
     def get_push_constants(self, cascade):
         """(spectrum[16], modulate[8], unpack[4]) uint32 words: the reference's push-constant blocks of this cascade's most recent launch"""

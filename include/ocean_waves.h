@@ -1368,6 +1368,126 @@ ow_status ow_radiance_light_apply(ow_context *ctx, ow_radiance *radiance, const 
 ow_status ow_radiance_light_apply_async(ow_context *ctx, ow_radiance *radiance, const ow_camera *camera, const ow_radiance_light_options *opts,
                                         ow_render_pixel *pixels_dev);
 
+/* Sun shadows of the floating bodies.  ow_solid_draw lights a crate by light_color max(n . l, 0) whatever stands between it and the sun;
+ * the reference scene's sun is low (main.tscn:113: its +Z axis is about 10.5 degrees above the horizon, a 2.5 m crate's shadow is about
+ * 13 m long), so the shadows are most of what ties the bodies to the sea.  Two things add them: a depth map of the casters as the light
+ * sees them, held by an ow_shadow_map, and a pass over the records that takes the shadowed part of the sun's share out of each -- the
+ * records keep albedo, diffuse, specular and color apart, so it comes out exactly as it went in.  Both run in the context's stream
+ * order.  Nothing is shadowed until ow_shadow_apply is called.  With it the frame order is
+ *     water -> solids -> ow_shadow_apply -> ow_radiance_light_apply -> ow_environment_apply -> billboards -> ow_present
+ * (the sky-light pass only adds to color, so the two passes commute up to rounding; this is the documented order).
+ * Everything below is THIS LIBRARY'S CHOICE modelled on the engine's directional shadow; the engine's source is not part of the
+ * reference, so this text and godotoceanwaves_amd/csrc/ow_shadow.h (the exact operations, identical in every build) are the authority.
+ * main.tscn:114-117's shadow_bias 0, shadow_normal_bias 6.464 and shadow_opacity 0.8 are the defaults; shadow_blur 5 has no unit to
+ * carry over and is replaced by filter_taps.
+ *   frame      an orthographic box: light_direction (towards the light, any finite length > 0), a square footprint of 2 half_extent
+ *              metres a side about center, depth_range metres either side of center along the light.  The host normalises the direction
+ *              in FP64 as ow_render_view normalises its light and builds the basis there, narrowed once: z = l^,
+ *              x = normalize((0,1,0) x z), or (1,0,0) where z.x^2 + z.z^2 < 1e-6, y = z x x.  For a world point w, r = w - center,
+ *              u = x . r, v = y . r, d = depth_range - z . r (metres from the frame's near plane, growing away from the light); texel
+ *              coordinates s = u k + size / 2, t = v k + size / 2 with k = size / (2 half_extent); texel (i, j) has its centre at
+ *              (i + 0.5, j + 0.5)
+ *   map        size x size 32-bit words, the FP32 bits of d (positive floats order as unsigned integers); an empty texel holds FLT_MAX
+ *   casters    the triangles of an ow_solid shape at instance transforms; the world vertex is ow_solid_draw's, to the bit, and so are the
+ *              skip rules (a transform that is not finite, a raised fault flag: skipped and counted once).  A triangle with a
+ *              light-space vertex that is not finite is culled
+ *   facing     A = (s1 - s0)(t2 - t0) - (s2 - s0)(t1 - t0) in FP64.  Only triangles whose outward side is turned AWAY from the light are
+ *              cast (A < 0): a closed body then never shadows its own lit faces whatever the bias, which is why shadow_bias 0 is safe.
+ *              OW_SHADOW_CAST_BOTH_SIDES casts every triangle with A != 0 (open shapes)
+ *   coverage   a texel centre is covered when the three 2-D edge functions (FP64 products of FP32 differences) all have A's sign or are
+ *              0: edges are inclusive on both sides, two triangles that share an edge both write and the smaller depth stays
+ *   depth      barycentrics e_k / (e_0 + e_1 + e_2) and the combination of the three d_k in FP64, narrowed once, then max(., 0): a caster
+ *              nearer the light than the near plane is flattened onto it and still casts.  Written with an atomic minimum when finite
+ *              and <= 2 depth_range.  A triangle wholly beyond that, or outside the footprint, is culled.  The map does not depend on the
+ *              order of instances, triangles or casts and is the same bytes on every run
+ *   receivers  a record with OW_RAY_HIT and with neither OW_RAY_SHADOWED nor OW_RAY_ENVIRONMENT (a fogged record has had its colour
+ *              scaled: too late).  OW_RAY_SOLID records always; water records only with OW_SHADOW_RECEIVE_WATER -- off by default
+ *              because water.gdshader:2 is shadows_disabled and the defaults render as the reference does; a host with floating bodies
+ *              sets it
+ *   point      P' = position + normal ((1 - max(n . l^, 0)) normal_bias w), w = 2 half_extent / size metres per texel;
+ *              d_r = d(P') - bias w
+ *   filter     filter_taps in {1, 3, 5, 7, 9} is the side 2 r + 1 (0 selects 5).  With i0 = floor(s - 0.5), fx = (s - 0.5) - i0 the taps run
+ *              over i0 - r .. i0 + r + 1 on each axis with the weights 1 - fx, 1 .. 1, fx; lit = d_r <= D_tap, a tap outside the map is lit;
+ *              V = sum w_x w_y lit / (2 r + 1)^2, row-major in FP32 (exactly 1 where every weighted tap is lit, exactly 0 where none is)
+ *   record     a = opacity (1 - V); per channel color -= a (albedo diffuse + specular), then diffuse *= 1 - a and specular *= 1 - a.
+ *              Only these three fields and status change.  Every receiver gets OW_RAY_SHADOWED whether or not its values changed, so
+ *              applying twice equals applying once.  A value that would not be finite keeps what it had; nothing written is NaN or Inf
+ *   finite     a camera that is not finite (ow_mesh_draw's rule), or a map that has had no ow_shadow_map_begin, leaves every record as
+ *              it was.  RGBA8 is optional, covers every pixel and is packed from color as ow_render_view packs it
+ *   not here   cascaded or split maps, fitting the frame to a camera, a penumbra search, shadows from the water or the spray (the scene
+ *              sets cast_shadow = 0 on both), shadowed fog scatter
+ * There is no group form (ow_group_*) of these calls, as for every draw. */
+#define OW_RAY_SHADOWED 128               /* ow_render_pixel.status: ow_shadow_apply has taken the pixel as a receiver */
+#define OW_SHADOW_CAST_BOTH_SIDES 1u      /* ow_shadow_frame.flags */
+#define OW_SHADOW_RECEIVE_WATER 1u        /* ow_shadow_options.flags */
+#define OW_SHADOW_MIN_SIZE 8
+#define OW_SHADOW_MAX_SIZE 8192
+typedef struct ow_shadow_map ow_shadow_map;  /* opaque; belongs to the context it was created on */
+typedef struct ow_shadow_frame {
+    float light_direction[3];   /* towards the light, world space, any finite length > 0 */
+    float half_extent;          /* metres, (0, 1e6]: half the side of the square footprint */
+    float center[3];            /* world, finite */
+    float depth_range;          /* metres, (0, 1e6]: either side of center along the light */
+    uint32_t flags;             /* OW_SHADOW_CAST_BOTH_SIDES */
+    int32_t lane_box;           /* measurement, as ow_solid_options.lane_box: 0 = the default (4), -1 = every triangle goes to the wave,
+                                   up to 64.  The map does not depend on it */
+    uint32_t reserved[6];       /* 0 */
+} ow_shadow_frame;              /* 64 bytes */
+typedef struct ow_shadow_options {
+    float bias;                 /* texels of depth, [-1e6, 1e6] */
+    float normal_bias;          /* texels along the normal at grazing light, [-1e6, 1e6] */
+    float opacity;              /* [0, 1] */
+    int32_t filter_taps;        /* 0 (= 5), 1, 3, 5, 7, 9 */
+    uint32_t flags;             /* OW_SHADOW_RECEIVE_WATER */
+    uint32_t reserved[11];      /* 0 */
+} ow_shadow_options;            /* 64 bytes; a NULL pointer = ow_shadow_options_default's values */
+typedef char ow_layout_check_shadow_frame[(sizeof(ow_shadow_frame) == 64 && offsetof(ow_shadow_frame, center) == 16 &&
+                                           offsetof(ow_shadow_frame, flags) == 32 && offsetof(ow_shadow_frame, reserved) == 40) ? 1 : -1];
+typedef char ow_layout_check_shadow_options[(sizeof(ow_shadow_options) == 64 && offsetof(ow_shadow_options, flags) == 16 &&
+                                             offsetof(ow_shadow_options, reserved) == 20) ? 1 : -1];
+
+/* The scene's sun (ow_render_options_default's light_direction), center at the origin, half_extent 50, depth_range 100, one-sided. */
+void ow_shadow_frame_default(ow_shadow_frame *out);
+/* main.tscn:114-116: bias 0, normal_bias 6.464, opacity 0.8; 5 taps, flags 0. */
+void ow_shadow_options_default(ow_shadow_options *out);
+/* A map of size x size texels, size in [OW_SHADOW_MIN_SIZE, OW_SHADOW_MAX_SIZE], empty and without a frame.  A size out of range or a
+ * null pointer is OW_ERR_INVALID and nothing is written (checked without a device; the context last).  Synchronises.  The map owns its
+ * grow-only scratch (the casters' light-space vertex records).  Destroy it before its context (one that outlives it can still be
+ * destroyed; every other call on it is OW_ERR_STATE). */
+ow_status ow_shadow_map_create(ow_context *ctx, int32_t size, ow_shadow_map **out);
+void ow_shadow_map_destroy(ow_context *ctx, ow_shadow_map *map);
+/* Sets the frame and clears the map and the counters, in the context's stream order.  Enqueue only.  The frame is checked first, without a
+ * device (a value that is not finite or out of its range, a direction of zero length, lane_box outside [-1, 64], unknown flags, reserved
+ * words not 0), then the context and the map; OW_ERR_INVALID changes nothing. */
+ow_status ow_shadow_map_begin(ow_context *ctx, ow_shadow_map *map, const ow_shadow_frame *frame);
+/* Casts the shape at bodies [first_body, first_body + body_count) of the set into the map: it reads the resident pose records and fault
+ * flags on the device, as ow_solid_draw_async does, behind everything enqueued so far.  Enqueue only; the host never reads a pose; the
+ * only allocation is the map's scratch, on first use or growth.  The limits on the counts are ow_solid_draw's.  A map without a frame is
+ * OW_ERR_STATE. */
+ow_status ow_shadow_map_cast(ow_context *ctx, ow_shadow_map *map, ow_solid *solid, ow_bodies *bodies, int32_t first_body, int32_t body_count);
+/* The same kernels over a caller's host array of count transforms (count x 12 floats, 0 .. OW_SOLID_MAX_INSTANCES).  Synchronises. */
+ow_status ow_shadow_map_cast_instances(ow_context *ctx, ow_shadow_map *map, ow_solid *solid, const float *transforms, int32_t count);
+/* The map's size * size depths as floats, rows in ascending j (FLT_MAX where empty).  Synchronises.  For tests and debugging. */
+ow_status ow_shadow_map_read(ow_context *ctx, ow_shadow_map *map, float *depth_out);
+/* Shadows a picture in host memory, after everything enqueued so far.  pixels_inout: width * height ow_render_pixel records as the draws
+ * wrote them (required); rgba8_out: width * height * 4 bytes, may be NULL.  Synchronises.  The argument checks follow ow_solid_draw's
+ * order: the records, the camera, the options (a value that is not finite or out of its range, filter_taps not one of 0, 1, 3, 5, 7, 9,
+ * unknown flags, reserved words not 0), then the context and the map (one of another context is refused); OW_ERR_INVALID writes nothing.
+ * The first three groups are checked without a device. */
+ow_status ow_shadow_apply(ow_context *ctx, ow_shadow_map *map, const ow_camera *camera, const ow_shadow_options *opts,
+                          ow_render_pixel *pixels_inout, void *rgba8_out);
+/* The same with DEVICE pointers on the context's device (rgba8_dev 4-byte aligned, pixels_dev 16-byte aligned; camera and opts are host
+ * values), ordered exactly as ow_solid_draw_async: behind everything enqueued so far -- both chains, a caller's stream included -- and
+ * ahead of whatever the context enqueues next.  No synchronisation, no copy, no allocation and no host traffic. */
+ow_status ow_shadow_apply_async(ow_context *ctx, ow_shadow_map *map, const ow_camera *camera, const ow_shadow_options *opts,
+                                ow_render_pixel *pixels_dev, void *rgba8_dev);
+/* Counters since the map's last begin (each output may be NULL): casts enqueued; the instances skipped, and of the other instances the
+ * triangles culled (facing the light, edge-on, not finite, outside the footprint or beyond 2 depth_range) and drawn --
+ * skipped_instances * num_triangles + culled + drawn = instances * num_triangles, summed over the casts --; the scratch bytes the map
+ * holds.  Synchronises when one of the three middle counters is asked for. */
+ow_status ow_shadow_stats(ow_context *ctx, ow_shadow_map *map, uint64_t *casts, uint64_t *skipped_instances, uint64_t *culled, uint64_t *drawn,
+                          uint64_t *scratch_bytes);
+
 /* ---- several devices: cascades sharded inside one process ---------------------------------------- */
 
 /* Cascades share nothing (wave_generator.gd:65-85 touches no state of another cascade; README.md:77-80), so a node's GPUs

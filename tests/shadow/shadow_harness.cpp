@@ -1,0 +1,172 @@
+// shadow_harness.cpp -- godotoceanwaves_amd/csrc/ow_shadow.h as plain C++ (g++ -ffp-contract=off): the CPU build the kernels of
+// ow_shadow.hip are held to bit for bit.  The map is the serial form of k_shadow_vertices and k_shadow_raster -- every (instance, vertex),
+// then every (instance, triangle) pair over its texel box with a plain minimum over the 32-bit words; the pass is shadow_record over every
+// record.  With -DSHADOW_HARNESS_MAIN it is a stand-alone program that reads a case file (the header below, then the arrays), casts,
+// applies and writes the outputs: the form the sanitizers run.
+#include <math.h>
+#include <stddef.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <string.h>
+
+#include <vector>
+
+#include "ow_shadow.h"
+
+using namespace ow;
+
+extern "C" {
+
+// sizes and offsets, for the layout test
+void harness_shadow_sizes(int *out) {
+    out[0] = (int)sizeof(ShadowFrame);
+    out[1] = (int)offsetof(ShadowFrame, half_extent);
+    out[2] = (int)offsetof(ShadowFrame, center);
+    out[3] = (int)offsetof(ShadowFrame, depth_range);
+    out[4] = (int)offsetof(ShadowFrame, flags);
+    out[5] = (int)offsetof(ShadowFrame, lane_box);
+    out[6] = (int)offsetof(ShadowFrame, reserved);
+    out[7] = (int)sizeof(ShadowOptions);
+    out[8] = (int)offsetof(ShadowOptions, normal_bias);
+    out[9] = (int)offsetof(ShadowOptions, opacity);
+    out[10] = (int)offsetof(ShadowOptions, filter_taps);
+    out[11] = (int)offsetof(ShadowOptions, flags);
+    out[12] = (int)offsetof(ShadowOptions, reserved);
+    out[13] = (int)sizeof(ShadowVertex);
+    out[14] = (int)kRayShadowed;
+    out[15] = (int)sizeof(RenderPixel);
+}
+
+// the resolved frame: x, y, z, center (12 floats), depth_range, max_depth, k, half, w; returns ok
+int harness_shadow_frame(const ShadowFrame *f, int size, float *out17) {
+    const ShadowParams P = shadow_params(*f, size);
+    for (int k = 0; k < 3; ++k) {
+        out17[k] = P.x[k];
+        out17[3 + k] = P.y[k];
+        out17[6 + k] = P.z[k];
+        out17[9 + k] = P.center[k];
+    }
+    out17[12] = P.depth_range;
+    out17[13] = P.max_depth;
+    out17[14] = P.k;
+    out17[15] = P.half;
+    out17[16] = P.w;
+    return P.ok;
+}
+
+// the clear: size x size words and the four counters
+void harness_shadow_clear(int size, uint32_t *map, uint32_t *counters) {
+    for (size_t i = 0; i < (size_t)size * size; ++i) map[i] = kShadowEmpty;
+    for (int k = 0; k < 4; ++k) counters[k] = 0u;
+}
+
+// one cast into a map and its counters (both accumulate, as the device's do between two begins).  flags may be null.  verts_out (may be
+// null): count x num_vertices records.
+void harness_shadow_cast(const ShadowFrame *f, int size, const float *local, int num_vertices, const int32_t *indices, int num_triangles,
+                         const float *transforms, int stride, const int32_t *flags, int count, uint32_t *map, uint32_t *counters, ShadowVertex *verts_out) {
+    const ShadowParams P = shadow_params(*f, size);
+    if (!P.ok || count <= 0) return;
+    std::vector<ShadowVertex> verts((size_t)count * num_vertices);
+    for (int i = 0; i < count; ++i) {
+        const float *t = transforms + (size_t)i * stride;
+        const bool ok = solid_instance_ok(t, flags ? flags + i : nullptr);
+        if (!ok) ++counters[kShadowSkippedInstances];
+        for (int v = 0; v < num_vertices; ++v) {
+            const float l[3] = {local[3 * (size_t)v], local[3 * (size_t)v + 1], local[3 * (size_t)v + 2]};
+            verts[(size_t)i * num_vertices + v] = shadow_vertex(t, ok, l, P);
+        }
+    }
+    if (verts_out) memcpy(verts_out, verts.data(), verts.size() * sizeof(ShadowVertex));
+    for (int i = 0; i < count; ++i)
+        for (int tri = 0; tri < num_triangles; ++tri) {
+            const ShadowVertex *base = verts.data() + (size_t)i * num_vertices;
+            const ShadowSetup S = shadow_setup(base[indices[3 * (size_t)tri]], base[indices[3 * (size_t)tri + 1]], base[indices[3 * (size_t)tri + 2]], P);
+            if (S.kind >= kShadowTriCulled) ++counters[S.kind];
+            if (S.kind != kShadowTriLane && S.kind != kShadowTriWave) continue;
+            for (int j = S.y0; j <= S.y1; ++j)
+                for (int x = S.x0; x <= S.x1; ++x) {
+                    const ShadowCover c = shadow_cover(S.s, S.t, S.d, P.max_depth, x, j);
+                    uint32_t &word = map[(size_t)j * size + x];
+                    if (c.hit && c.bits < word) word = c.bits;
+                }
+        }
+}
+
+// the pass over width x height records, in place; V_out (may be null): the visibility of every record (1 for what is no receiver);
+// rgba_out (may be null): every pixel's word
+void harness_shadow_apply(const ShadowFrame *f, int size, const ShadowOptions *o, int camera_ok, const uint32_t *map, int width, int height,
+                          RenderPixel *pixels, float *V_out, uint32_t *rgba_out) {
+    const ShadowParams P = shadow_params(*f, size);
+    const ShadowApply ap = shadow_apply_params(*o, camera_ok != 0);
+    for (size_t at = 0; at < (size_t)width * height; ++at) {
+        float V = 1.0f;
+        shadow_record(P, ap, map, pixels[at], V);
+        if (V_out) V_out[at] = V;
+        if (rgba_out) rgba_out[at] = pack_rgba8(pixels[at].color);
+    }
+}
+
+}  // extern "C"
+
+#ifdef SHADOW_HARNESS_MAIN
+// one case, every field four bytes
+struct ShadowCase {
+    int32_t size, num_vertices, num_triangles, count, stride, has_flags, width, height, camera_ok, casts;
+    ShadowFrame frame;
+    ShadowOptions options;
+};
+namespace {
+bool read_all(FILE *f, void *dst, size_t bytes) { return bytes == 0 || (dst && fread(dst, 1, bytes, f) == bytes); }
+}  // namespace
+
+// shadow_harness_main CASE OUT: reads the header and the arrays (local positions, indices, transforms, flags, records), clears, casts the
+// instances in `casts` nearly equal spans, applies, and writes the map, the counters, the records, the visibilities and the RGBA8 words
+int main(int argc, char **argv) {
+    if (argc != 3) {
+        fprintf(stderr, "usage: %s CASE OUT\n", argv[0]);
+        return 2;
+    }
+    FILE *f = fopen(argv[1], "rb");
+    if (!f) return 2;
+    ShadowCase h;
+    if (!read_all(f, &h, sizeof(h)) || h.size < kShadowMinSize || h.size > kShadowMaxSize || h.width < 1 || h.height < 1 || h.width > 8192 ||
+        h.height > 8192 || h.count < 0 || h.count > kSolidMaxInstances || h.num_vertices < 1 || h.num_triangles < 1 ||
+        h.num_triangles > kSolidMaxTriangles || h.stride < kSolidTransformFloats || h.stride > 64 || h.casts < 1 ||
+        (int64_t)h.count * h.num_vertices > kSolidMaxProduct || (int64_t)h.count * h.num_triangles > kSolidMaxProduct) {
+        fprintf(stderr, "bad case header\n");
+        fclose(f);
+        return 2;
+    }
+    const size_t count = (size_t)h.width * h.height, texels = (size_t)h.size * h.size;
+    std::vector<float> local((size_t)h.num_vertices * 3), transforms((size_t)h.count * h.stride), V(count);
+    std::vector<int32_t> indices((size_t)h.num_triangles * 3), flags(h.has_flags ? (size_t)h.count : 0);
+    std::vector<uint32_t> rgba(count), map(texels), counters(4);
+    std::vector<RenderPixel> pixels(count);
+    const bool got = read_all(f, local.data(), local.size() * 4) && read_all(f, indices.data(), indices.size() * 4) &&
+                     read_all(f, transforms.data(), transforms.size() * 4) && read_all(f, flags.data(), flags.size() * 4) &&
+                     read_all(f, pixels.data(), pixels.size() * sizeof(RenderPixel));
+    fclose(f);
+    if (!got) {
+        fprintf(stderr, "short case file\n");
+        return 2;
+    }
+    for (int32_t v : indices)
+        if (v < 0 || v >= h.num_vertices) {
+            fprintf(stderr, "bad index\n");
+            return 2;
+        }
+    harness_shadow_clear(h.size, map.data(), counters.data());
+    for (int k = 0; k < h.casts; ++k) {
+        const int a = (int)((int64_t)h.count * k / h.casts), b = (int)((int64_t)h.count * (k + 1) / h.casts);
+        harness_shadow_cast(&h.frame, h.size, local.data(), h.num_vertices, indices.data(), h.num_triangles, transforms.data() + (size_t)a * h.stride, h.stride,
+                            h.has_flags ? flags.data() + a : nullptr, b - a, map.data(), counters.data(), nullptr);
+    }
+    harness_shadow_apply(&h.frame, h.size, &h.options, h.camera_ok, map.data(), h.width, h.height, pixels.data(), V.data(), rgba.data());
+    FILE *o = fopen(argv[2], "wb");
+    if (!o) return 2;
+    const bool put = fwrite(map.data(), 4, texels, o) == texels && fwrite(counters.data(), 4, 4, o) == 4 &&
+                     fwrite(pixels.data(), sizeof(RenderPixel), count, o) == count && fwrite(V.data(), 4, count, o) == count &&
+                     fwrite(rgba.data(), 4, count, o) == count;
+    return fclose(o) == 0 && put ? 0 : 1;
+}
+#endif

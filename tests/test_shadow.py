@@ -1,0 +1,1159 @@
+"""The floating bodies' sun shadows (include/ocean_waves.h ow_shadow_*): a depth map of the casters from the light and a pass over the records
+that darkens the sun's share of each by it (godotoceanwaves_amd/csrc/ow_shadow.h).
+
+CPU: the ABI, the documents and the argument checks without a device; ow_shadow.h compiled as plain C++ (tests/shadow/shadow_harness.cpp,
+g++ -ffp-contract=off) held to its exact cases (a triangle parallel to the map texel for texel and bit for bit, a tilted one against its
+plane, facing, flattening, culling, order independence, the filter's ramp by hand at 1 and 5 taps, taps outside the map, the record's rules
+byte for byte), to an FP64 twin written from the definition (tests/shadow_twin.py) on seven tumbled cubes over a calm sea, and to finite
+outputs and consistent counters on awkward inputs; the stand-alone harness runs under the sanitizers on the same inputs; the C example
+compiles.  GPU: the map and the pass are the CPU build's bit for bit at every class boundary; a cast from a body set's resident poses equals
+a cast of the poses read back; a whole frame equals the CPU chain; the asynchronous forms are ordered on the context's and on a caller's
+stream; the map's scratch grows once; examples/shadow_host.c writes the wrapper's picture."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import helpers as H
+import shadow_twin as ST
+from godotoceanwaves_amd import _lib, build
+from godotoceanwaves_amd.presets import UPDATE_DELTA
+from godotoceanwaves_amd.wave_generator import WaveGenerator as W
+from test_mesh_draw import cpu_draw as cpu_mesh_draw, grid, harness as mesh_harness  # noqa: F401
+from test_render_view import HIT, look
+from test_solid_draw import (CRATE_CAM, CRATE_SHAPE, SUN, box, cpu_draw as cpu_solid_draw, cube, eight_crates, harness as solid_harness,  # noqa: F401
+                             pose_transforms, transform, transforms, twin_scene)
+from test_environment import harness as env_harness  # noqa: F401
+from test_sky_light import harness as sky_harness  # noqa: F401
+from test_spray_draw import harness as billboard_harness, level_camera  # noqa: F401
+from test_surface_query import gpu_maps, make_gen, scales_of
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "godotoceanwaves_amd", "csrc")
+PKG = os.path.join(ROOT, "godotoceanwaves_amd")
+HERE = os.path.dirname(os.path.abspath(__file__))
+HARNESS_SRC = os.path.join(HERE, "shadow", "shadow_harness.cpp")
+MARGINS = os.path.join(ROOT, "profiles", "shadow_margins.txt")
+NEW_FUNCTIONS = ("ow_shadow_frame_default", "ow_shadow_options_default", "ow_shadow_map_create", "ow_shadow_map_destroy", "ow_shadow_map_begin",
+                 "ow_shadow_map_cast", "ow_shadow_map_cast_instances", "ow_shadow_map_read", "ow_shadow_apply", "ow_shadow_apply_async", "ow_shadow_stats")
+TOL = H.TOL_F32     # 1e-4: the project's FP32 parity tolerance
+SOLID, ENV, SHADOWED = _lib.OW_RAY_SOLID, _lib.OW_RAY_ENVIRONMENT, _lib.OW_RAY_SHADOWED
+FLT_MAX = np.float32(3.4028235e38)
+AMBIENT = np.float32([0.05, 0.08, 0.10])
+DOWN = dict(light_direction=(0.0, 1.0, 0.0))        # the light straight down: x = (1,0,0), y = (0,0,-1), so s = X k + size/2, t = -Z k + size/2
+CASE = np.dtype([("size", np.int32), ("num_vertices", np.int32), ("num_triangles", np.int32), ("count", np.int32), ("stride", np.int32),
+                 ("has_flags", np.int32), ("width", np.int32), ("height", np.int32), ("camera_ok", np.int32), ("casts", np.int32),
+                 ("frame", np.uint8, 64), ("options", np.uint8, 64)])
+
+
+# ---- the CPU build ---------------------------------------------------------------------------------------------------------------------------
+
+@pytest.fixture(scope="module")
+def harness(tmp_path_factory):
+    so = str(tmp_path_factory.mktemp("shadow") / "libshadow_harness.so")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unknown-pragmas", "-I", CSRC, HARNESS_SRC, "-o", so], check=True)
+    L = C.CDLL(so)
+    V, I = C.c_void_p, C.c_int
+    L.harness_shadow_sizes.argtypes = [V]
+    L.harness_shadow_frame.argtypes = [V, I, V]
+    L.harness_shadow_clear.argtypes = [I, V, V]
+    L.harness_shadow_cast.argtypes = [V, I, V, I, V, I, V, I, V, I, V, V, V]
+    L.harness_shadow_apply.argtypes = [V, I, V, I, V, I, I, V, V, V]
+    return L
+
+
+def frame_of(frame=None):
+    return W.shadow_frame(frame)
+
+
+def options_of(opts=None):
+    o = W.shadow_options(opts)
+    if o is None:
+        o = _lib.ow_shadow_options()
+        _lib.load().ow_shadow_options_default(C.byref(o))
+    return o
+
+
+def cpu_clear(L, size):
+    m, c = np.zeros((size, size), np.uint32), np.zeros(4, np.uint32)
+    L.harness_shadow_clear(size, m.ctypes.data, c.ctypes.data)
+    return dict(map=m, counters=c)
+
+
+def cpu_cast(L, frame, size, shape, tf, flags=None, stride=12, into=None):
+    """the CPU build's cast into `into` (a cleared map by default): dict of map [size][size] uint32, counters, depth (the float view),
+    skipped, culled, drawn"""
+    st = into if into is not None else cpu_clear(L, size)
+    v = np.ascontiguousarray(shape[0], np.float32).reshape(-1, 3)
+    t = np.ascontiguousarray(shape[1], np.int32).reshape(-1, 3)
+    tf = np.ascontiguousarray(tf, np.float32)
+    fl = np.ascontiguousarray(flags, np.int32) if flags is not None else None
+    fr = frame_of(frame)
+    L.harness_shadow_cast(C.addressof(fr), size, v.ctypes.data, len(v), t.ctypes.data, len(t), tf.ctypes.data if tf.size else None, stride,
+                          fl.ctypes.data if fl is not None else None, tf.size // stride, st["map"].ctypes.data, st["counters"].ctypes.data, None)
+    s, c, ln, wv = (int(x) for x in st["counters"])
+    st.update(depth=st["map"].view(np.float32), skipped=s, culled=c, lane=ln, wave=wv, drawn=ln + wv)
+    return st
+
+
+def cpu_apply(L, frame, size, opts, words, records, camera_ok=1):
+    """the CPU build's pass: dict of rec (a copy, rewritten), V and rgba"""
+    rec = np.array(records, W.RENDER_PIXEL, copy=True, order="C")
+    h, w = rec.shape
+    V = np.zeros((h, w), np.float32)
+    rgba = np.zeros((h, w, 4), np.uint8)
+    fr, o = frame_of(frame), options_of(opts)
+    words = np.ascontiguousarray(words, np.uint32)
+    L.harness_shadow_apply(C.addressof(fr), size, C.addressof(o), camera_ok, words.ctypes.data, w, h, rec.ctypes.data, V.ctypes.data, rgba.ctypes.data)
+    return dict(rec=rec, V=V, rgba=rgba)
+
+
+def one_triangle(st_coords, y, size, half_extent):
+    """a triangle at height y whose light-space (s, t) under DOWN are the given three pairs"""
+    k = size / (2.0 * half_extent)
+    v = np.float32([((s - size / 2) / k, y, -(t - size / 2) / k) for s, t in st_coords])
+    return v, np.int32([(0, 1, 2)])
+
+
+def plate(s0, s1, t0, t1, y, size, half_extent):
+    """a quad at height y over [s0, s1] x [t0, t1] in light space under DOWN, two triangles"""
+    k = size / (2.0 * half_extent)
+    X = lambda s: (s - size / 2) / k    # noqa: E731
+    Z = lambda t: -(t - size / 2) / k   # noqa: E731
+    v = np.float32([(X(s0), y, Z(t0)), (X(s1), y, Z(t0)), (X(s1), y, Z(t1)), (X(s0), y, Z(t1))])
+    return v, np.int32([(0, 1, 2), (0, 2, 3)])
+
+
+IDENTITY = transforms([((0.0, 0.0, 0.0),)])
+
+
+def plane_records(s, t, size, half_extent, status=HIT, y=0.0):
+    """flat records at height y, normal up, whose light-space coordinates under DOWN are s [W] by t [H]"""
+    k = size / (2.0 * half_extent)
+    s, t = np.meshgrid(np.asarray(s, np.float64), np.asarray(t, np.float64))
+    rec = np.zeros(s.shape, W.RENDER_PIXEL)
+    rec["position"] = np.stack([(s - size / 2) / k, np.full(s.shape, y), -(t - size / 2) / k], -1).astype(np.float32)
+    rec["normal"] = (0.0, 1.0, 0.0)
+    rec["status"] = status
+    rec["t"] = 10.0
+    rec["albedo"] = (0.2, 0.3, 0.4)
+    rec["diffuse"] = (0.9, 0.8, 0.7)
+    rec["specular"] = 0.05
+    rec["color"] = rec["albedo"] * (rec["diffuse"] + AMBIENT) + rec["specular"][..., None]
+    rec["roughness"], rec["fresnel"], rec["reserved"] = 0.4, 0.3, (1, 2, 3, 4)
+    return rec
+
+
+def shadow_cubes(count, seed=11, spread=15.0):
+    """cube 0 spans many texels (the wave's sweep), the others shrink with their index down to sub-texel ones (a lane's walk), tumbled and
+    scattered over the footprint"""
+    rng = np.random.default_rng(seed)
+    rows = []
+    for k in range(count):
+        q = rng.normal(size=4)
+        scale = 12.0 if k == 0 else 4.0 * (1.0 - k / max(count - 1, 1)) ** 2 + 0.02
+        rows.append(((rng.uniform(-spread, spread), rng.uniform(-2.0, 6.0), rng.uniform(-spread, spread)), q / np.linalg.norm(q), scale))
+    return transforms(rows)
+
+
+MIXED_FRAME = dict(half_extent=20.0, depth_range=60.0, center=(0.5, 1.0, -0.25))
+
+
+# ---- 1. the interface and the documents --------------------------------------------------------------------------------------------------
+
+HEADER = open(os.path.join(ROOT, "include", "ocean_waves.h")).read()
+
+
+def test_header_declares_the_new_calls_and_the_library_exports_them():
+    build.build_library()
+    lib = _lib.load()
+    text = re.sub(r"/\*.*?\*/", "", HEADER, flags=re.S)
+    for name in NEW_FUNCTIONS:
+        assert re.search(r"\b%s\s*\(" % name, text), name
+        assert name in _lib.SIGNATURES
+        assert getattr(lib, name)
+    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    exported = set(re.findall(r" T (ow_[a-z0-9_]+)", out))
+    assert sorted(s for s in exported if "shadow" in s) == sorted(NEW_FUNCTIONS)      # no group form
+    assert lib.ow_abi_version() == 4 and re.search(r"#define OW_ABI_VERSION 4\b", HEADER)
+    for define, value in (("OW_RAY_SHADOWED", 128), ("OW_SHADOW_MIN_SIZE", 8), ("OW_SHADOW_MAX_SIZE", 8192)):
+        assert re.search(r"#define %s %d\b" % (define, value), HEADER) and getattr(_lib, define) == value, define
+    for define in ("OW_SHADOW_CAST_BOTH_SIDES", "OW_SHADOW_RECEIVE_WATER"):
+        assert re.search(r"#define %s 1u\b" % define, HEADER) and getattr(_lib, define) == 1, define
+    section = HEADER.split("Sun shadows of the floating bodies")[1].split("several devices")[0]
+    for cite in ("water -> solids -> ow_shadow_apply -> ow_radiance_light_apply -> ow_environment_apply -> billboards -> ow_present", "ow_shadow.h",
+                 "THIS LIBRARY'S CHOICE", "main.tscn:113", "main.tscn:114-117", "water.gdshader:2", "shadow_blur 5 has no unit", "shadow_bias 0 is safe",
+                 "OW_RAY_SHADOWED", "no group form", "cast_shadow = 0"):
+        assert cite in section, cite
+    note = open(os.path.join(CSRC, "ow_shadow.h")).read()
+    for cite in ("THIS LIBRARY'S CHOICE", "shadow_bias 0 is safe", "shadow_blur 5 has no", "-ffp-contract=off"):
+        assert cite in note, cite
+    f = _lib.ow_shadow_frame()
+    lib.ow_shadow_frame_default(C.byref(f))
+    assert np.allclose(list(f.light_direction), SUN, rtol=0, atol=1e-6) and list(f.center) == [0.0, 0.0, 0.0]            # main.tscn:113
+    assert (f.half_extent, f.depth_range, f.flags, f.lane_box) == (50.0, 100.0, 0, 0) and not any(f.reserved)
+    o = _lib.ow_shadow_options()
+    lib.ow_shadow_options_default(C.byref(o))
+    assert (o.bias, o.normal_bias, o.opacity, o.filter_taps, o.flags) == (0.0, float(np.float32(6.464)), float(np.float32(0.8)), 5, 0)   # main.tscn:114-116
+    assert not any(o.reserved)
+    for fn in (lib.ow_shadow_frame_default, lib.ow_shadow_options_default):
+        fn(None)
+
+
+def test_structs_agree_in_c_ctypes_and_the_harness(tmp_path, harness):
+    got = {}
+    for S, name in ((_lib.ow_shadow_frame, "ow_shadow_frame"), (_lib.ow_shadow_options, "ow_shadow_options")):
+        fields = [f for f, _ in S._fields_]
+        expr = ", ".join(["sizeof(%s)" % name] + ["offsetof(%s, %s)" % (name, f) for f in fields])
+        src = ('#include <stdio.h>\n#include <stddef.h>\n#include "ocean_waves.h"\nint main(void){printf("%s\\n", ' % " ".join(["%zu"] * (1 + len(fields)))
+               + expr + ");return 0;}\n")
+        exe = str(tmp_path / (name + "_layout"))
+        subprocess.run(["gcc", "-std=c11", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-x", "c", "-", "-o", exe], input=src, text=True, check=True)
+        vals = [int(v) for v in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split()]
+        assert vals == [C.sizeof(S)] + [getattr(S, f).offset for f in fields], name
+        got[name] = dict(zip(["size"] + fields, vals))
+    f, o = got["ow_shadow_frame"], got["ow_shadow_options"]
+    assert (f["size"], o["size"]) == (64, 64)
+    sizes = (C.c_int * 16)()
+    harness.harness_shadow_sizes(sizes)
+    assert list(sizes) == [64, f["half_extent"], f["center"], f["depth_range"], f["flags"], f["lane_box"], f["reserved"], 64, o["normal_bias"], o["opacity"],
+                           o["filter_taps"], o["flags"], o["reserved"], 16, SHADOWED, W.RENDER_PIXEL.itemsize]
+    assert CASE.itemsize == 40 + 128
+
+
+def test_the_documents_name_the_new_calls():
+    import test_integration_shim as S
+    for name in NEW_FUNCTIONS:
+        assert "`%s`" % name in S.DOC.split("## 7. Index")[1], name
+    for name in NEW_FUNCTIONS[2:]:
+        assert re.search(r"\[DllImport\(Lib\)\]\s*public static extern \w+ %s\(" % name, S.SHIM), name
+    for doc, words in (("README.md", ("ow_shadow_map_cast", "ow_shadow_apply")),
+                       ("DESIGN.md", ("k_shadow_clear", "k_shadow_vertices", "k_shadow_raster", "k_shadow_apply", "ow_shadow.hip")),
+                       ("INTEGRATION.md", ("ow_shadow_apply_async", "OW_RAY_SHADOWED", "OwShadowFrame", "OwShadowOptions",
+                                           "water -> solids -> ow_shadow_apply -> ow_radiance_light_apply -> ow_environment_apply -> billboards -> ow_present"))):
+        text = open(os.path.join(ROOT, doc)).read()
+        for w in words:
+            assert w in text, (doc, w)
+    for path in ("scripts/shadow_cost.py", "examples/shadow_host.c"):
+        assert os.path.exists(os.path.join(ROOT, path)), path
+
+
+def build_example(tmp_path):
+    exe = str(tmp_path / "shadow_host")
+    subprocess.run(["gcc", "-O2", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "examples", "shadow_host.c"),
+                    "-o", exe, "-L", PKG, "-locean_waves", "-L", "/opt/rocm/lib", "-lamdhip64", f"-Wl,-rpath,{PKG}", "-Wl,-rpath,/opt/rocm/lib", "-lm"],
+                   check=True)
+    return exe
+
+
+def test_example_builds_as_c99(tmp_path):
+    build.build_library()
+    build_example(tmp_path)
+
+
+# ---- 2. argument errors without a device ---------------------------------------------------------------------------------------------------
+
+def test_argument_errors_without_a_device():
+    lib = _lib.load()
+    cam = level_camera(24, 12)
+    rec = np.zeros((12, 24), W.RENDER_PIXEL)
+    rgba = np.zeros((12, 24, 4), np.uint8)
+    fake = C.c_void_p(16)   # never read: every case fails before a handle is looked at
+
+    def apply(camera, opts, rec_p=rec.ctypes.data, shadow_map=fake):
+        cp, op = (C.byref(camera) if camera is not None else None), (C.byref(opts) if opts is not None else None)
+        out = []
+        for fn in (lib.ow_shadow_apply, lib.ow_shadow_apply_async):
+            assert fn(None, shadow_map, cp, op, rec_p, rgba.ctypes.data) == _lib.OW_ERR_INVALID
+            out.append(lib.ow_last_error().decode())
+        assert out[0] == out[1]
+        return out[0]
+
+    so = W.shadow_options
+    assert "null context" in apply(cam, None) and "null context" in apply(cam, None, shadow_map=None)       # everything else is in order
+    assert "null context" in apply(cam, so(dict(bias=-1e6, normal_bias=1e6, opacity=1.0, filter_taps=9, receive_water=True)))
+    assert "null context" in apply(cam, so(dict(opacity=0.0, filter_taps=0)))
+    assert "the records" in apply(cam, None, None)                     # the records-free form does not exist
+    assert "null camera" in apply(None, None)
+    for w, h in ((0, 12), (24, 0), (_lib.OW_RENDER_MAX_SIDE + 1, 12)):
+        assert "camera size" in apply(level_camera(w, h), None)
+    bad = level_camera(24, 12)
+    bad.reserved[1] = 7
+    assert "ow_camera.reserved" in apply(bad, None)
+    nan, inf = float("nan"), float("inf")
+    for key, values in (("bias", (nan, inf, 2e6, -2e6)), ("normal_bias", (nan, -inf, 2e6)), ("opacity", (-0.1, 1.1, nan, inf))):
+        for v in values:
+            assert key in apply(cam, so({key: v})), (key, v)
+    for taps in (-1, 2, 4, 10, 11):
+        assert "filter_taps" in apply(cam, so(dict(filter_taps=taps))), taps
+    # the order: the records before the camera before the options
+    assert "the records" in apply(None, so(dict(opacity=2.0)), None) and "null camera" in apply(None, so(dict(opacity=2.0)))
+    o = so({})
+    o.flags = 2
+    assert "unknown shadow flags" in apply(cam, o)
+    o = so({})
+    o.reserved[10] = 1
+    assert "ow_shadow_options.reserved" in apply(cam, o)
+
+    def begin(frame, shadow_map=fake):
+        assert lib.ow_shadow_map_begin(None, shadow_map, C.byref(frame) if frame is not None else None) == _lib.OW_ERR_INVALID
+        return lib.ow_last_error().decode()
+
+    sf = W.shadow_frame
+    assert "null context" in begin(sf()) and "null context" in begin(sf(dict(half_extent=1e6, depth_range=1e-3, lane_box=-1, cast_both_sides=True)))
+    assert "null frame" in begin(None)
+    for key, values in (("half_extent", (0.0, -1.0, nan, inf, 2e6)), ("depth_range", (0.0, -1.0, nan, inf, 2e6))):
+        for v in values:
+            assert key in begin(sf({key: v})), (key, v)
+    assert "not finite" in begin(sf(dict(light_direction=(0, nan, 1)))) and "not finite" in begin(sf(dict(center=(inf, 0, 0))))
+    assert "zero length" in begin(sf(dict(light_direction=(0, 0, 0))))
+    assert "lane_box" in begin(sf(dict(lane_box=65))) and "lane_box" in begin(sf(dict(lane_box=-2)))
+    f = sf()
+    f.flags = 4
+    assert "unknown shadow frame flags" in begin(f)
+    f = sf()
+    f.reserved[5] = 1
+    assert "ow_shadow_frame.reserved" in begin(f)
+
+    def create(size, ctx=None):
+        out = C.c_void_p(0x5EED)
+        assert lib.ow_shadow_map_create(ctx, size, C.byref(out)) == _lib.OW_ERR_INVALID
+        assert out.value == 0x5EED
+        return lib.ow_last_error().decode()
+
+    assert "null context" in create(8) and "null context" in create(8192)
+    for size in (7, 0, -1, 8193):
+        assert "shadow map size" in create(size)
+    assert lib.ow_shadow_map_create(None, 64, None) == _lib.OW_ERR_INVALID
+    one = transform()
+    for st in (lib.ow_shadow_map_cast_instances(None, fake, fake, one.ctypes.data, -1), lib.ow_shadow_map_cast_instances(None, fake, fake, None, 1),
+               lib.ow_shadow_map_cast_instances(None, fake, fake, one.ctypes.data, _lib.OW_SOLID_MAX_INSTANCES + 1),
+               lib.ow_shadow_map_cast_instances(None, fake, fake, one.ctypes.data, 1), lib.ow_shadow_map_cast(None, fake, fake, fake, 0, 1),
+               lib.ow_shadow_map_read(None, fake, None), lib.ow_shadow_map_read(None, fake, rec.ctypes.data),
+               lib.ow_shadow_stats(None, fake, None, None, None, None, None)):
+        assert st == _lib.OW_ERR_INVALID
+    lib.ow_shadow_map_destroy(None, None)
+    assert not rec.tobytes().strip(b"\0") and not rgba.any()
+
+
+# ---- 3. the analytic map -----------------------------------------------------------------------------------------------------------------------
+
+def test_a_triangle_parallel_to_the_map_covers_its_centres_edges_included_at_its_depth_to_the_bit(harness):
+    size, he = 16, 8.0                                     # one texel a metre
+    frame = dict(DOWN, half_extent=he, depth_range=100.0, cast_both_sides=True)
+    words = (C.c_float * 17)()
+    assert harness.harness_shadow_frame(C.addressof(frame_of(frame)), size, words) == 1
+    assert list(words)[:9] == [1, 0, 0, 0, 0, -1, 0, 1, 0] and list(words)[12:] == [100.0, 200.0, 1.0, 8.0, 1.0]
+    for corners in (((2.5, 2.5), (10.5, 2.5), (2.5, 10.5)), ((2.5, 2.5), (2.5, 10.5), (10.5, 2.5))):      # both windings: both legs and the
+        got = cpu_cast(harness, frame, size, one_triangle(corners, 3.0, size, he), IDENTITY)              # hypotenuse run through centres
+        j, i = np.meshgrid(np.arange(size), np.arange(size), indexing="ij")
+        inside = (i >= 2) & (j >= 2) & (i + j <= 12)
+        assert np.array_equal(got["depth"] != FLT_MAX, inside) and inside.sum() == 45
+        assert (got["depth"][inside] == np.float32(97.0)).all() and (got["map"][~inside] == 0x7F7FFFFF).all()
+        assert (got["skipped"], got["culled"], got["drawn"]) == (0, 0, 1)
+    one_sided = cpu_cast(harness, dict(frame, cast_both_sides=False), size, one_triangle(((2.5, 2.5), (10.5, 2.5), (2.5, 10.5)), 3.0, size, he), IDENTITY)
+    other = cpu_cast(harness, dict(frame, cast_both_sides=False), size, one_triangle(((2.5, 2.5), (2.5, 10.5), (10.5, 2.5)), 3.0, size, he), IDENTITY)
+    assert sorted([one_sided["drawn"], other["drawn"]]) == [0, 1]                     # exactly one winding is turned away from the light
+
+
+def test_a_tilted_triangle_has_its_planes_depth(harness):
+    size, he, dr = 64, 16.0, 50.0
+    frame = dict(DOWN, half_extent=he, depth_range=dr, cast_both_sides=True)
+    v = np.float32([(-9.3, 1.0, -7.1), (11.2, 6.5, -3.3), (-2.4, -4.0, 12.6)])
+    got = cpu_cast(harness, frame, size, (v, np.int32([(0, 1, 2)])), IDENTITY)
+    covered = got["depth"] != FLT_MAX
+    assert covered.sum() > 400
+    n = np.cross(v[1].astype(np.float64) - v[0], v[2].astype(np.float64) - v[0])
+    k = size / (2 * he)
+    j, i = np.nonzero(covered)
+    X, Z = (i + 0.5 - size / 2) / k, -(j + 0.5 - size / 2) / k
+    Y = v[0][1] - (n[0] * (X - v[0][0]) + n[2] * (Z - v[0][2])) / n[1]
+    err = np.abs(got["depth"][covered] - (dr - Y)).max() / (2 * dr)
+    print(f"tilted triangle: {int(covered.sum())} texels, worst depth error {err:.3e} of 2 depth_range")
+    assert err <= TOL
+
+
+# ---- 4. facing, flattening, culling ------------------------------------------------------------------------------------------------------------
+
+def test_facing_flattening_and_culling(harness):
+    size = 64
+    frame = dict(half_extent=10.0, depth_range=100.0)                  # the scene's sun
+    z = np.float64(SUN) / np.linalg.norm(SUN)
+    tumbled = transforms([((0.3, 0.2, -0.4), (0.3, -0.5, 0.2, 0.7), 3.0)])
+    one = cpu_cast(harness, frame, size, cube(), tumbled)
+    assert (one["skipped"], one["culled"], one["drawn"]) == (0, 6, 6) and (one["depth"] != FLT_MAX).sum() > 100
+    both = cpu_cast(harness, dict(frame, cast_both_sides=True), size, cube(), tumbled)
+    assert (both["culled"], both["drawn"]) == (0, 12)
+    assert np.array_equal(both["depth"] != FLT_MAX, one["depth"] != FLT_MAX) and (both["depth"] <= one["depth"]).all() and (both["depth"] < one["depth"]).any()
+    up = (np.float32([(-2, 0, -2), (2, 0, -2), (2, 0, 2), (-2, 0, 2)]), np.int32([(0, 2, 1), (0, 3, 2)]))         # counter-clockwise seen from above
+    lone = cpu_cast(harness, frame, size, up, IDENTITY)
+    assert (lone["culled"], lone["drawn"]) == (2, 0) and (lone["map"] == 0x7F7FFFFF).all()
+    lone2 = cpu_cast(harness, dict(frame, cast_both_sides=True), size, up, IDENTITY)
+    assert lone2["drawn"] == 2 and (lone2["depth"] != FLT_MAX).sum() > 20
+    near = cpu_cast(harness, frame, size, cube(), transforms([(tuple(150.0 * z), (0, 0, 0, 1), 3.0)]))           # in front of the near plane
+    hit = near["depth"] != FLT_MAX
+    assert near["drawn"] == 6 and hit.sum() > 100 and (near["depth"][hit] == 0.0).all()
+    far = cpu_cast(harness, frame, size, cube(), transforms([(tuple(-150.0 * z), (0, 0, 0, 1), 3.0)]))           # beyond 2 depth_range
+    aside = cpu_cast(harness, frame, size, cube(), transforms([((0.0, 40.0, 0.0), (0, 0, 0, 1), 3.0)]))          # outside the footprint
+    for c in (far, aside):
+        assert (c["skipped"], c["culled"], c["drawn"]) == (0, 12, 0) and (c["map"] == 0x7F7FFFFF).all()
+
+
+# ---- 5. order independence ---------------------------------------------------------------------------------------------------------------------
+
+def test_the_map_does_not_depend_on_the_order_of_instances_or_casts(harness):
+    size = 64
+    tf = shadow_cubes(23)
+    base = cpu_cast(harness, MIXED_FRAME, size, cube(), tf)
+    assert base["lane"] > 0 and base["wave"] > 0 and base["culled"] + base["drawn"] == 23 * 12 and (base["depth"] != FLT_MAX).sum() > 500
+    back = cpu_cast(harness, MIXED_FRAME, size, cube(), tf[::-1])
+    assert back["map"].tobytes() == base["map"].tobytes() and np.array_equal(back["counters"], base["counters"])
+    split = cpu_cast(harness, MIXED_FRAME, size, cube(), tf[9:])
+    split = cpu_cast(harness, MIXED_FRAME, size, cube(), tf[:9], into=split)
+    assert split["map"].tobytes() == base["map"].tobytes() and np.array_equal(split["counters"], base["counters"])
+    for lb in (-1, 1, 64):
+        other = cpu_cast(harness, dict(MIXED_FRAME, lane_box=lb), size, cube(), tf)
+        assert other["map"].tobytes() == base["map"].tobytes() and other["drawn"] == base["drawn"], lb
+
+
+# ---- 6. the analytic pass ----------------------------------------------------------------------------------------------------------------------
+
+PLATE = dict(size=32, he=16.0)          # one texel a metre; the plate 5 m above the records, over [8, 24]^2 in light space
+
+
+def plate_scene(harness, s0=8, s1=24):
+    size, he = PLATE["size"], PLATE["he"]
+    frame = dict(DOWN, half_extent=he, depth_range=100.0, cast_both_sides=True)
+    m = cpu_cast(harness, frame, size, plate(s0, s1, 8, 24, 5.0, size, he), IDENTITY)
+    j, i = np.meshgrid(np.arange(size), np.arange(size), indexing="ij")
+    assert np.array_equal(m["depth"] != FLT_MAX, (i >= s0) & (i < s1) & (j >= 8) & (j < 24)) and (m["depth"][m["depth"] != FLT_MAX] == 95.0).all()
+    return frame, m
+
+
+@pytest.mark.parametrize("taps", [1, 5])
+def test_the_filter_is_the_hand_written_ramp(harness, taps):
+    size, he = PLATE["size"], PLATE["he"]
+    frame, m = plate_scene(harness)
+    s = 2.0 + 0.25 * np.arange(96)                          # 2 .. 25.75 in quarter texels: every weight is exact in FP32
+    rec = plane_records(s, [16.5, 16.25, 2.5], size, he)
+    got = cpu_apply(harness, frame, size, dict(filter_taps=taps, receive_water=True, normal_bias=0.0), m["map"], rec)
+    n = float(taps)
+    left, right = (8.0 + n / 2 - s) / n, (s - (24.0 - n / 2)) / n         # the box filter over the step at texel 8, and at texel 24
+    want = np.clip(np.maximum(left, right), 0.0, 1.0)
+    for row in (0, 1):
+        assert np.abs(got["V"][row] - want).max() <= 1e-6, (taps, row)
+        assert (got["V"][row][(s >= 8.0 + n / 2 + 0.5) & (s <= 24.0 - n / 2 - 0.5)] == 0.0).all()          # exactly 0 well inside
+        assert (got["V"][row][s <= 8.0 - n / 2 - 0.5] == 1.0).all()                                        # exactly 1 well outside
+    assert (got["V"][2] == 1.0).all()
+    assert ((got["V"][0] > 0) & (got["V"][0] < 1)).sum() >= 4 * taps - 2
+    a = np.float32(0.8) * (np.float32(1.0) - got["V"])
+    assert np.abs(got["rec"]["diffuse"] - rec["diffuse"] * (1 - a)[..., None]).max() <= 1e-6
+
+
+def test_taps_outside_the_map_are_lit(harness):
+    size, he = PLATE["size"], PLATE["he"]
+    frame, m = plate_scene(harness, 0, 8)                   # the plate reaches the map's edge
+    rec = plane_records([0.75, 0.5, 4.5, -1.5, -3.0, 33.0, 1e9], [16.5], size, he)
+    got = cpu_apply(harness, frame, size, dict(filter_taps=5, receive_water=True, normal_bias=0.0), m["map"], rec)["V"][0]
+    # s = 0.75: taps -2 .. 3 with the weights 0.75, 1, 1, 1, 1, 0.25: the two outside are lit, the four under the plate are not
+    assert list(got[:3]) == [np.float32(1.75) / np.float32(5.0), np.float32(2.0) / np.float32(5.0), 0.0]
+    assert got[3] == np.float32(np.float32(4.0) / np.float32(5.0)) and list(got[4:]) == [1.0, 1.0, 1.0]
+
+
+# ---- 7. the record's rules ---------------------------------------------------------------------------------------------------------------------
+
+def test_record_rules(harness):
+    size, he = PLATE["size"], PLATE["he"]
+    frame, m = plate_scene(harness)
+    s = 4.0 + 0.25 * np.arange(64)
+    rec = plane_records(s, 10.0 + 0.25 * np.arange(24), size, he)
+    kinds = np.int32([HIT, HIT | SOLID, 0, HIT | ENV, HIT | SOLID | ENV, HIT | 2, 8, HIT | SOLID | 64, HIT | SHADOWED])
+    rec["status"] = kinds[(np.arange(64)[None, :] + 3 * np.arange(24)[:, None]) % len(kinds)]
+    st = rec["status"]
+    hit, done = (st & HIT) != 0, (st & (ENV | SHADOWED)) != 0
+    solid = (st & SOLID) != 0
+    opts = dict(filter_taps=5)
+    once = cpu_apply(harness, frame, size, opts, m["map"], rec)
+    recv = hit & ~done & solid
+    assert recv.sum() > 100 and np.array_equal((once["rec"]["status"] & SHADOWED) != 0, recv | ((st & SHADOWED) != 0))
+    assert once["rec"][~recv].tobytes() == rec[~recv].tobytes()                                  # water, misses, finished records: byte for byte
+    for f in W.RENDER_PIXEL.names:
+        if f not in ("status", "diffuse", "specular", "color"):
+            assert once["rec"][f].tobytes() == rec[f].tobytes(), f
+    assert (once["rec"]["status"][recv] == (st[recv] | SHADOWED)).all() and (once["V"][~recv] == 1.0).all()
+    dark = recv & (once["V"] < 1)
+    assert dark.sum() > 50 and (once["rec"]["diffuse"][dark] < rec["diffuse"][dark]).all() and (recv & (once["V"] == 1)).sum() > 10
+    same = recv & (once["V"] == 1)
+    for f in ("diffuse", "specular", "color"):
+        assert once["rec"][f][same].tobytes() == rec[f][same].tobytes(), f                         # a lit receiver: only the flag
+    twice = cpu_apply(harness, frame, size, opts, m["map"], once["rec"])
+    assert twice["rec"].tobytes() == once["rec"].tobytes()                                       # applying twice is applying once
+    water = cpu_apply(harness, frame, size, dict(opts, receive_water=True), m["map"], rec)
+    recv_w = hit & ~done
+    assert np.array_equal((water["rec"]["status"] & SHADOWED) != 0, recv_w | ((st & SHADOWED) != 0)) and (recv_w & ~recv).sum() > 100
+    assert water["rec"][recv].tobytes() == once["rec"][recv].tobytes() and water["rec"][~recv_w].tobytes() == rec[~recv_w].tobytes()
+    clear = cpu_apply(harness, frame, size, dict(opts, receive_water=True, opacity=0.0), m["map"], rec)
+    for f in W.RENDER_PIXEL.names:
+        if f != "status":
+            assert clear["rec"][f].tobytes() == rec[f].tobytes(), f                              # opacity 0 changes only status
+    assert np.array_equal(clear["rec"]["status"], water["rec"]["status"])
+    out = water["rec"]
+    recomposed = out["albedo"].astype(np.float64) * (out["diffuse"].astype(np.float64) + AMBIENT) + out["specular"].astype(np.float64)[..., None]
+    assert np.abs(out["color"] - recomposed)[recv_w].max() <= TOL
+    assert np.array_equal(water["rgba"], _rgba8(out["color"]))
+    full = cpu_apply(harness, frame, size, dict(opts, receive_water=True, opacity=1.0), m["map"], rec)["rec"]
+    umbra = recv_w & (water["V"] == 0)
+    assert umbra.sum() > 50 and (full["diffuse"][umbra] == 0).all() and (full["specular"][umbra] == 0).all()
+    assert np.abs(full["color"][umbra] - rec["albedo"][umbra] * AMBIENT).max() <= 1e-6           # only the ambient is left
+
+
+def _rgba8(color):
+    c = np.asarray(color, np.float32)
+    v = np.where(c > 0, np.where(c < 1, c, np.float32(1)), np.float32(0))
+    out = np.full(c.shape[:-1] + (4,), 255, np.uint8)
+    out[..., :3] = (v * np.float32(255) + np.float32(0.5)).astype(np.uint8)
+    return out
+
+
+# ---- 8. awkward inputs -------------------------------------------------------------------------------------------------------------------------
+
+def awkward_cases():
+    some = shadow_cubes(6)
+    broken = shadow_cubes(6)
+    broken[1, 4], broken[3, 10], broken[4, 0] = np.nan, np.inf, -np.inf
+    huge = shadow_cubes(3)
+    huge[1, :9] *= 3e38                                            # finite values whose products overflow: its vertices are not finite
+    flat = (np.float32([(-2, 3, -2), (2, 3, -2), (0, 3, 2), (0, 3, 0), (1, 3, 1)]), np.int32([(0, 2, 1), (0, 0, 1), (0, 3, 4), (3, 3, 3)]))
+    nan_frame = dict(MIXED_FRAME, center=(0.0, float("nan"), 0.0))
+    inf_frame = dict(MIXED_FRAME, half_extent=float("inf"))
+    return {
+        "1 x 1 picture": dict(shape=cube(), tf=some, picture=(1, 1)),
+        "a map of side 8": dict(shape=cube(), tf=some, size=8),
+        "transforms that are not finite": dict(shape=cube(), tf=broken, skipped=3),
+        "a raised fault flag": dict(shape=cube(), tf=some, flags=np.int32([0, 0, 1, 0, 1, 0]), skipped=2),
+        "a transform that overflows": dict(shape=cube(), tf=huge, min_culled=12),
+        "zero-area triangles": dict(shape=flat, tf=IDENTITY, frame=dict(DOWN, half_extent=16.0, depth_range=60.0, cast_both_sides=True), drawn=1, culled=3),
+        "no instances": dict(shape=cube(), tf=transforms([]), nothing=True),
+        "a camera that is not finite": dict(shape=cube(), tf=some, camera_ok=0, untouched=True),
+        "a frame with a NaN": dict(shape=cube(), tf=some, frame=nan_frame, nothing=True, untouched=True, dead=True),
+        "a frame with an Inf": dict(shape=cube(), tf=some, frame=inf_frame, nothing=True, untouched=True, dead=True),
+    }
+
+
+def awkward_records(width=37, height=21, seed=4):
+    """records scattered over MIXED_FRAME's footprint and beyond it, of every status, some with values that are not finite"""
+    rng = np.random.default_rng(seed)
+    rec = plane_records(np.zeros(width), np.zeros(height), 64, 20.0)
+    shape = (height, width)
+    rec["position"] = np.stack([rng.uniform(-30, 30, shape), rng.uniform(-3, 1, shape), rng.uniform(-30, 30, shape)], -1).astype(np.float32)
+    n = rng.normal(size=shape + (3,))
+    rec["normal"] = (n / np.linalg.norm(n, axis=-1, keepdims=True)).astype(np.float32)
+    rec["status"] = rng.choice(np.int32([0, HIT, HIT | SOLID, HIT | SOLID, HIT | ENV, 8]), shape)
+    odd = rng.random(shape) < 0.06
+    rec["position"][odd] = rng.choice(np.float32([np.nan, np.inf, -np.inf, 3e38, -3e38]), (int(odd.sum()), 3))
+    odd = rng.random(shape) < 0.04
+    rec["normal"][odd] = rng.choice(np.float32([np.nan, np.inf, 0.0, 3e38]), (int(odd.sum()), 3))
+    big = rng.random(shape) < 0.04
+    rec["diffuse"][big] = np.float32(3e38)
+    rec["albedo"][big] = np.float32(1e20)
+    return rec
+
+
+def run_case(L, c):
+    size, frame = c.get("size", 64), c.get("frame", MIXED_FRAME)
+    m = cpu_cast(L, frame, size, c["shape"], c["tf"], c.get("flags"))
+    rec = awkward_records(*c.get("picture", (37, 21)))
+    return m, rec, cpu_apply(L, frame, size, dict(receive_water=True), m["map"], rec, c.get("camera_ok", 1))
+
+
+@pytest.mark.parametrize("name", list(awkward_cases()))
+def test_awkward_inputs(harness, name):
+    """finite outputs, counters that add up, untouched records where the definition says so"""
+    c = awkward_cases()[name]
+    m, rec, got = run_case(harness, c)
+    nt = len(c["shape"][1])
+    covered = m["depth"] != FLT_MAX
+    assert (m["depth"][covered] >= 0).all() and (m["depth"][covered] <= 2 * 60.0).all()
+    if c.get("dead"):
+        assert (m["skipped"], m["culled"], m["drawn"]) == (0, 0, 0)
+    else:
+        assert m["skipped"] * nt + m["culled"] + m["drawn"] == len(c["tf"]) * nt
+    assert m["skipped"] == c.get("skipped", 0)
+    if c.get("nothing"):
+        assert not covered.any()
+    elif "drawn" not in c:
+        assert covered.any()
+    if "drawn" in c:
+        assert (m["drawn"], m["culled"]) == (c["drawn"], c["culled"])
+    assert m["culled"] >= c.get("min_culled", 0)
+    out = got["rec"]
+    if c.get("untouched"):
+        assert out.tobytes() == rec.tobytes() and (got["V"] == 1).all()
+    recv = ST.receivers(rec["status"], True)
+    assert out[~recv].tobytes() == rec[~recv].tobytes()
+    for f in ("diffuse", "specular", "color"):
+        new = out[f] != rec[f]
+        assert np.isfinite(out[f][new]).all(), f                       # nothing written is NaN or Inf
+        assert np.array_equal(np.isfinite(out[f]), np.isfinite(rec[f])) or not c.get("untouched")
+    assert np.isfinite(got["V"]).all() and (got["V"] >= 0).all() and (got["V"] <= 1).all()
+    assert np.array_equal(got["rgba"], _rgba8(out["color"]))
+
+
+# ---- 9. the FP64 twin --------------------------------------------------------------------------------------------------------------------------
+
+TWIN_SIZE = 256
+TWIN_FRAME = dict(light_direction=SUN, half_extent=14.0, center=(0.0, 0.0, 4.0), depth_range=40.0)
+TWIN_OPTS = dict(filter_taps=5, receive_water=True)
+
+
+def shadow_twin_scene(mesh_harness, solid_harness):
+    """test_solid_draw's twin scene (seven tumbled cubes over a calm sea, 96 x 64) drawn by the solid draw's CPU build: the records the pass reads"""
+    shape, tf, cam, bg = twin_scene(mesh_harness)
+    rec = cpu_solid_draw(solid_harness, shape, tf, cam, None, bg)["rec"]
+    return shape, tf, rec
+
+
+def twin_of(shape, tf, rec):
+    fr = ST.frame(TWIN_FRAME["light_direction"], TWIN_FRAME["half_extent"], TWIN_FRAME["center"], TWIN_FRAME["depth_range"], TWIN_SIZE)
+    m = ST.cast(fr, shape[0], shape[1], tf)
+    o = options_of(TWIN_OPTS)
+    p = ST.apply(fr, m["depth"], rec, o.bias, o.normal_bias, o.opacity, o.filter_taps, True, m["ambiguous"])
+    return fr, m, p
+
+
+def twin_conditions(m, p, rec):
+    covered = int(m["covered"].sum())
+    texels_aside = int((m["covered"] & m["ambiguous"]).sum())
+    touched = int(p["touches"].sum())
+    records_aside = int((p["touches"] & p["aside"]).sum())
+    keep = p["receiver"] & ~p["aside"]
+    solid = (rec["status"] & SOLID) != 0
+    figures = dict(covered=covered, texels_aside=texels_aside, touched=touched, records_aside=records_aside, remain=int(keep.sum()),
+                   water_shadowed=int((keep & ~solid & (p["V"] < 1)).sum()), solid_shadowed=int((keep & solid & (p["V"] < 1)).sum()),
+                   lit=int((keep & (p["V"] == 1)).sum()))
+    return keep, figures
+
+
+def assert_conditions(f):
+    assert f["texels_aside"] <= 0.02 * f["covered"] and f["records_aside"] <= 0.02 * f["touched"], f
+    assert f["remain"] >= 1000 and f["water_shadowed"] >= 200 and f["solid_shadowed"] >= 100 and f["lit"] >= 200, f
+
+
+def test_the_twin_alone_meets_the_scenes_conditions(mesh_harness, solid_harness):
+    shape, tf, rec = shadow_twin_scene(mesh_harness, solid_harness)
+    _, m, p = twin_of(shape, tf, rec)
+    _, f = twin_conditions(m, p, rec)
+    print(f)
+    assert_conditions(f)
+
+
+def compare_with_twin(harness, mesh_harness, solid_harness):
+    shape, tf, rec = shadow_twin_scene(mesh_harness, solid_harness)
+    fr, m, p = twin_of(shape, tf, rec)
+    keep, f = twin_conditions(m, p, rec)
+    got_map = cpu_cast(harness, TWIN_FRAME, TWIN_SIZE, shape, tf)
+    got = cpu_apply(harness, TWIN_FRAME, TWIN_SIZE, TWIN_OPTS, got_map["map"], rec)
+    ok = ~m["ambiguous"]
+    covered = got_map["depth"] != FLT_MAX
+    assert np.array_equal(covered[ok], m["covered"][ok])
+    both = ok & covered
+    limit = 2 * TWIN_FRAME["depth_range"]
+    e = dict(depth=float((np.abs(got_map["depth"][both] - m["depth"][both]) / limit).max()),
+             V=float(np.abs(got["V"] - p["V"])[keep].max()))
+    for name in ("color", "diffuse", "specular"):
+        e[name] = float(np.abs(got["rec"][name] - p[name])[keep].max())
+    assert np.array_equal(got["rec"]["status"], p["status"])
+    return f, e, got_map
+
+
+def test_seven_tumbled_cubes_against_the_fp64_twin(harness, mesh_harness, solid_harness):
+    """Measured on the CPU build (profiles/shadow_margins.txt; the figures go to the file with SHADOW_WRITE_MARGINS=1): 3 367 texels covered,
+    1 set aside (0.03 %, cap 2 %); 2 759 records whose taps touch a covered texel, 49 set aside (1.8 %, cap 2 %); 3 826 records remain, of them
+    1 581 water and 1 080 solid records with V < 1 and 1 163 with V = 1.  On those the largest differences are 2.3e-7 of 2 depth_range in the
+    map's depth, 2.4e-6 in V, 1.0e-7 in color, 4.7e-7 in diffuse and 2.0e-8 in specular, against 1e-4 for each."""
+    f, e, got_map = compare_with_twin(harness, mesh_harness, solid_harness)
+    print(f, e)
+    assert_conditions(f)
+    assert e["depth"] <= 1e-4 and max(e["V"], e["color"], e["diffuse"], e["specular"]) <= TOL, e
+    assert got_map["drawn"] == 7 * 6 or got_map["culled"] + got_map["drawn"] == 7 * 12
+    if os.environ.get("SHADOW_WRITE_MARGINS") == "1":
+        with open(MARGINS, "w") as out:
+            out.write("The sun shadows' CPU build (tests/shadow/shadow_harness.cpp) against the FP64 twin (tests/shadow_twin.py), written by\n"
+                      "tests/test_shadow.py::test_seven_tumbled_cubes_against_the_fp64_twin with SHADOW_WRITE_MARGINS=1.\n"
+                      "Seven tumbled cubes over a calm sea, 96 x 64 records, a 256^2 map, 5 taps, water receiving.  texels aside: the share of\n"
+                      "the twin's covered texels it calls ambiguous (a centre within 1e-3 texel of a cast edge, two depths within 1e-5 of\n"
+                      "2 depth_range); records aside: the share of the records whose taps touch a covered texel that read such a texel or\n"
+                      "compare within 1e-5 of 2 depth_range.  The differences are the largest over the rest: |depth - twin| / (2 depth_range)\n"
+                      "and |V|, |color|, |diffuse|, |specular| differences (the tests' bound is 1e-4 for each).\n\n")
+            out.write(f"covered texels {f['covered']} texels aside {f['texels_aside'] / f['covered']:.4f}\n")
+            out.write(f"touching records {f['touched']} records aside {f['records_aside'] / f['touched']:.4f}\n")
+            out.write(f"records remaining {f['remain']} water shadowed {f['water_shadowed']} solid shadowed {f['solid_shadowed']} lit {f['lit']}\n")
+            out.write("margins " + " ".join(f"{k} {v:.3e}" for k, v in e.items()) + "\n")
+
+
+def test_margins_file_holds_the_measured_figures():
+    text = open(MARGINS).read()
+    num = lambda label: float(re.search(label + r" ([0-9.e+-]+)", text).group(1))    # noqa: E731
+    assert num("texels aside") <= 0.02 and num("records aside") <= 0.02
+    assert num("records remaining") >= 1000 and num("water shadowed") >= 200 and num("solid shadowed") >= 100 and num(" lit") >= 200
+    row = text.split("margins")[1].split()
+    figures = dict(zip(row[0::2], (float(v) for v in row[1::2])))
+    assert set(figures) == {"depth", "V", "color", "diffuse", "specular"} and all(v <= TOL for v in figures.values())
+
+
+# ---- 10. the sanitizers ------------------------------------------------------------------------------------------------------------------------
+
+def write_case(path, c, rec, size, frame, opts, casts=1):
+    v = np.ascontiguousarray(c["shape"][0], np.float32).reshape(-1, 3)
+    t = np.ascontiguousarray(c["shape"][1], np.int32).reshape(-1, 3)
+    tf = np.ascontiguousarray(c["tf"], np.float32)
+    fl = c.get("flags")
+    h = np.zeros(1, CASE)
+    h["size"], h["num_vertices"], h["num_triangles"], h["count"], h["stride"] = size, len(v), len(t), tf.size // 12, 12
+    h["has_flags"], h["width"], h["height"], h["camera_ok"], h["casts"] = int(fl is not None), rec.shape[1], rec.shape[0], c.get("camera_ok", 1), casts
+    h["frame"] = np.frombuffer(bytes(frame_of(frame)), np.uint8)
+    h["options"] = np.frombuffer(bytes(options_of(opts)), np.uint8)
+    with open(path, "wb") as f:
+        for block in (h, v, t, tf) + ((np.ascontiguousarray(fl, np.int32),) if fl is not None else ()) + (rec,):
+            f.write(block.tobytes())
+
+
+def test_stand_alone_harness_runs_clean_under_the_sanitizers(tmp_path, harness, mesh_harness, solid_harness):
+    """the harness as a program of its own (-DSHADOW_HARNESS_MAIN), built with -fsanitize=address,undefined, on the twin's scene, 70 mixed
+    cubes (cast in three spans) and every awkward case: what it writes is the shared library's, byte for byte"""
+    exe = str(tmp_path / "shadow_harness_main")
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                    "-Wno-unknown-pragmas", "-DSHADOW_HARNESS_MAIN", "-I", CSRC, HARNESS_SRC, "-o", exe], check=True)
+    shape, tf, rec = shadow_twin_scene(mesh_harness, solid_harness)
+    cases = {"twin": (dict(shape=shape, tf=tf), rec, TWIN_SIZE, TWIN_FRAME, TWIN_OPTS, 1),
+             "70 mixed cubes": (dict(shape=cube(), tf=shadow_cubes(70)), awkward_records(), 257, MIXED_FRAME, dict(filter_taps=9, receive_water=True), 3)}
+    for name, c in awkward_cases().items():
+        cases[name] = (c, awkward_records(*c.get("picture", (37, 21))), c.get("size", 64), c.get("frame", MIXED_FRAME), dict(receive_water=True), 1)
+    for k, (name, (c, rec, size, frame, opts, casts)) in enumerate(cases.items()):
+        path, out = str(tmp_path / f"case{k}.bin"), str(tmp_path / f"case{k}.out")
+        write_case(path, c, rec, size, frame, opts, casts)
+        r = subprocess.run([exe, path, out], capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, (name, r.stdout + r.stderr)
+        assert "runtime error" not in r.stderr and "Sanitizer" not in r.stderr, (name, r.stderr)
+        m = cpu_cast(harness, frame, size, c["shape"], c["tf"], c.get("flags"))
+        want = cpu_apply(harness, frame, size, opts, m["map"], rec, c.get("camera_ok", 1))
+        raw = open(out, "rb").read()
+        assert raw == m["map"].tobytes() + m["counters"].tobytes() + want["rec"].tobytes() + want["V"].tobytes() + want["rgba"].tobytes(), name
+
+
+# ---- 11-16. on the GPU -------------------------------------------------------------------------------------------------------------------------
+
+def bare_context():
+    """the smallest context: no map is read"""
+    return make_gen(128, [0, 1])[0]
+
+
+def gpu_cast(gen, frame, size, shape, spans):
+    """begin, one ow_shadow_map_cast_instances per span, the map and the counters read back"""
+    m, solid = gen.shadow_map_create(size), gen.solid_create(*shape)
+    gen.shadow_map_begin(m, frame)
+    for tf in spans:
+        gen.shadow_map_cast_instances(m, solid, tf)
+    depth, st = gen.shadow_map_read(m), gen.shadow_stats(m)
+    gen.solid_destroy(solid)
+    return m, dict(map=depth.view(np.uint32), depth=depth, skipped=st["skipped_instances"], culled=st["culled"], drawn=st["drawn"], casts=st["casts"])
+
+
+def same_map(got, want, what):
+    assert got["map"].tobytes() == want["map"].tobytes(), what
+    assert (got["skipped"], got["culled"], got["drawn"]) == (want["skipped"], want["culled"], want["drawn"]), what
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("count", [1, 5, 6, 70])
+def test_gpu_map_is_the_cpu_builds_bit_for_bit(harness, count):
+    """12 triangles a cube: 5 and 6 cubes straddle one wave of 64 pairs, 70 span fourteen.  Sides 16 (boxes of a few texels: the lanes' walk),
+    64 and 257 (the wave's sweep, a ragged last tile); lane_box at its default and with everything sent to the wave; one cast and two"""
+    gen = bare_context()
+    tf = shadow_cubes(count)
+    if count == 70:
+        tf[17, 3], tf[40, 11] = np.nan, np.inf
+    for size in (16, 64, 257):
+        for lane_box in (0, -1):
+            frame = dict(MIXED_FRAME, lane_box=lane_box)
+            want = cpu_cast(harness, frame, size, cube(), tf)
+            for spans in ([tf], [tf[count // 2:], tf[:count // 2]]):
+                m, got = gpu_cast(gen, frame, size, cube(), spans)
+                gen.shadow_map_destroy(m)
+                same_map(got, want, (count, size, lane_box, len(spans)))
+                assert got["casts"] == len(spans) and got["skipped"] * 12 + got["culled"] + got["drawn"] == count * 12
+            assert (want["depth"] != FLT_MAX).any() and (lane_box == 0 or want["lane"] == 0)
+            assert want["wave"] > 0 if size == 257 else (count < 5 or lane_box < 0 or want["lane"] > 0)
+    gen.free()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("width,height", [(37, 21), (96, 64)])
+def test_gpu_pass_is_the_cpu_builds_bit_for_bit(harness, width, height):
+    """ragged tiles and whole ones; 1, 5 and 9 taps; water receiving and not; records scattered beyond the footprint, so that taps leave the
+    map; with and without the RGBA8 words; awkward inputs; the records-free call is an argument error"""
+    gen = bare_context()
+    cam = level_camera(width, height)
+    rec = awkward_records(width, height)
+    tf = shadow_cubes(23)
+    want_map = cpu_cast(harness, MIXED_FRAME, 64, cube(), tf)
+    m, got_map = gpu_cast(gen, MIXED_FRAME, 64, cube(), [tf])
+    same_map(got_map, want_map, "the map")
+    for taps in (1, 5, 9):
+        for water in (False, True):
+            opts = dict(filter_taps=taps, receive_water=water, bias=0.25)
+            want = cpu_apply(harness, MIXED_FRAME, 64, opts, want_map["map"], rec)
+            for rgba in (True, False):
+                img, out = gen.shadow_apply(m, cam, rec, opts, rgba=rgba)
+                assert out.tobytes() == want["rec"].tobytes(), (taps, water, rgba)
+                assert (img is None) if not rgba else (img.tobytes() == want["rgba"].tobytes()), (taps, water)
+            assert ((want["V"] > 0) & (want["V"] < 1)).sum() > 3 and (want["V"] == 0).any() or taps == 1
+    lib = _lib.load()
+    img = np.zeros((height, width, 4), np.uint8)
+    assert lib.ow_shadow_apply(gen.context, m.handle, C.byref(cam), None, None, img.ctypes.data) == _lib.OW_ERR_INVALID and not img.any()
+    dead = level_camera(width, height)
+    dead.position[1] = float("nan")
+    _, out = gen.shadow_apply(m, dead, rec, dict(receive_water=True))
+    assert out.tobytes() == rec.tobytes()                                   # a camera that is not finite: every record as it was
+    fresh = gen.shadow_map_create(16)
+    _, out = gen.shadow_apply(fresh, cam, rec, dict(receive_water=True))     # a map without a frame: likewise
+    assert out.tobytes() == rec.tobytes()
+    gen.shadow_map_destroy(fresh)
+    gen.shadow_map_destroy(m)
+    for name, c in awkward_cases().items():
+        if c.get("dead") or "camera_ok" in c:
+            continue
+        size, frame = c.get("size", 64), c.get("frame", MIXED_FRAME)
+        wm = cpu_cast(harness, frame, size, c["shape"], c["tf"][np.asarray(c["flags"]) == 0] if "flags" in c else c["tf"])
+        m, gm = gpu_cast(gen, frame, size, c["shape"], [c["tf"][np.asarray(c["flags"]) == 0] if "flags" in c else c["tf"]])
+        same_map(gm, wm, name)
+        r = awkward_records(*c.get("picture", (37, 21)))
+        cam_c = level_camera(r.shape[1], r.shape[0])
+        img, out = gen.shadow_apply(m, cam_c, r, dict(receive_water=True), rgba=True)
+        w = cpu_apply(harness, frame, size, dict(receive_water=True), wm["map"], r)
+        assert out.tobytes() == w["rec"].tobytes() and img.tobytes() == w["rgba"].tobytes(), name
+        gen.shadow_map_destroy(m)
+    gen.free()
+
+
+@pytest.mark.gpu
+def test_gpu_cast_from_a_body_sets_resident_poses(harness):
+    """ow_shadow_map_cast reads the poses and the fault flags on the device: the CPU build on the pose records read back, and
+    ow_shadow_map_cast_instances of the same poses, byte for byte; body 5 faulted in its first substep: skipped and counted"""
+    from test_solid_draw import floating_scene
+    gen, params, sc, bodies, spray = floating_scene(broken=5)
+    shape = box(CRATE_SHAPE)
+    solid = gen.solid_create(*shape)
+    frame = dict(center=(0.3, 0.0, 8.5), half_extent=16.0, depth_range=40.0)
+    m = gen.shadow_map_create(128)
+    syncs = gen.sync_stats()
+    gen.shadow_map_begin(m, frame)
+    gen.shadow_map_cast(m, solid, bodies)
+    assert gen.sync_stats() == syncs                                        # enqueue only
+    got, st = gen.shadow_map_read(m), gen.shadow_stats(m)
+    tf = pose_transforms(gen, bodies)
+    flags = np.zeros(8, np.int32)
+    flags[5] = 1
+    assert gen.bodies_stats(bodies)["faulted_bodies"] == 1 and np.isfinite(tf[:, :12]).all()
+    want = cpu_cast(harness, frame, 128, shape, tf, flags, stride=24)
+    assert got.view(np.uint32).tobytes() == want["map"].tobytes() and (want["depth"] != FLT_MAX).sum() > 200
+    assert (st["casts"], st["skipped_instances"], st["culled"], st["drawn"]) == (1, 1, want["culled"], want["drawn"]) and want["drawn"] >= 7 * 6
+    gen.shadow_map_begin(m, frame)
+    gen.shadow_map_cast_instances(m, solid, tf[flags == 0][:, :12])
+    assert gen.shadow_map_read(m).tobytes() == got.tobytes() and gen.shadow_stats(m)["skipped_instances"] == 0
+    gen.shadow_map_begin(m, frame)                                          # a part of the set, in two casts
+    gen.shadow_map_cast(m, solid, bodies, first=4, count=4)
+    gen.shadow_map_cast(m, solid, bodies, first=0, count=4)
+    assert gen.shadow_map_read(m).tobytes() == got.tobytes() and gen.shadow_stats(m)["casts"] == 2
+    for bad in (dict(first=-1, count=1), dict(first=6, count=3), dict(first=0, count=-1)):
+        with pytest.raises(_lib.OceanWavesError) as e:
+            gen.shadow_map_cast(m, solid, bodies, **bad)
+        assert e.value.status == _lib.OW_ERR_INVALID and "outside" in str(e.value)
+    for h, fn in ((m, gen.shadow_map_destroy), (solid, gen.solid_destroy), (spray, gen.spray_destroy), (bodies, gen.bodies_destroy)):
+        fn(h)
+    gen.free()
+
+
+WHOLE_LIGHT = (0.9, 0.2, -0.3)      # a low sun from the camera's right: each crate's shadow lies along its row, over the water and its neighbour
+WHOLE_FRAME = dict(light_direction=WHOLE_LIGHT, center=(-1.0, 0.0, -34.0), half_extent=20.0, depth_range=40.0)
+
+
+@pytest.mark.gpu
+def test_gpu_whole_frame_is_the_cpu_chain_bit_for_bit(harness, mesh_harness, solid_harness, env_harness, sky_harness, billboard_harness):
+    """test_environment's whole frame with the shadows in it: ow_mesh_draw_async -> ow_solid_draw_async -> ow_shadow_map_begin / _cast /
+    ow_shadow_apply_async -> ow_radiance_light_apply_async -> ow_environment_apply_async -> ow_billboard_draw_async -> ow_present_async on
+    device buffers, one read-back, against the CPU builds chained in the same order; no call synchronised"""
+    import torch
+    from test_environment import (FRAME_CAM, FRAME_ENV, FRAME_PRESENT, FRAME_SHAPE, FRAME_WATER, cpu_environment, cpu_present, device_frame, frame_scene,
+                                  gradient_panorama, records_of, same_records, sky_of)
+    from test_sky_light import CpuPyramid, gpu_radiance
+    from test_solid_draw import gpu_material
+    from test_spray_draw import cpu_draw as cpu_billboard_draw, material
+    gen, params, sc, bodies, spray = frame_scene()
+    cam = look(**FRAME_CAM)
+    mat = material()
+    mt = gpu_material(gen, mat)
+    water = grid(*FRAME_WATER)
+    mesh = gen.mesh_create(*water)
+    shape = box(FRAME_SHAPE)
+    solid = gen.solid_create(*shape)
+    pano = sky_of(gradient_panorama(), 1, 1.2)
+    sky, radiance = gpu_radiance(gen, pano)
+    shadow = gen.shadow_map_create(256)
+    opts, light = dict(receive_water=True), dict(light_direction=WHOLE_LIGHT)
+    origin = W.clipmap_origin(cam.position, 4.0)
+    rec_dev, rgba_dev, lin_dev = device_frame(cam, 2)
+    gen.mesh_draw(mesh, cam, origin, sc)                       # the draws' scratch exists from here on
+    gen.solid_draw(solid, bodies, cam, pixels=True)
+    gen.spray_draw(spray, mt, cam, pixels=True)
+    gen.shadow_map_begin(shadow, WHOLE_FRAME)
+    gen.shadow_map_cast(shadow, solid, bodies)
+    torch.cuda.synchronize()
+    syncs = gen.sync_stats()
+    gen.mesh_draw_async(mesh, cam, origin, sc, None, rec_dev, light)
+    gen.solid_draw_async(solid, bodies, cam, None, rec_dev, light)
+    gen.shadow_map_begin(shadow, WHOLE_FRAME)
+    gen.shadow_map_cast(shadow, solid, bodies)
+    gen.shadow_apply_async(shadow, cam, rec_dev, None, opts)
+    gen.sky_light_apply_async(radiance, cam, rec_dev)
+    gen.environment_apply_async(cam, rec_dev, sky, FRAME_ENV)
+    gen.spray_draw_async(spray, mt, cam, None, rec_dev)
+    gen.present_async(cam, rec_dev, rgba_dev, lin_dev, FRAME_PRESENT)
+    assert gen.sync_stats() == syncs                           # host_syncs has not moved
+    gen.sync()
+    rec, rgba, lin = records_of(cam, rec_dev), rgba_dev.cpu().numpy(), lin_dev.cpu().numpy()
+    d, nm = gpu_maps(gen, 3)
+    bg = cpu_mesh_draw(mesh_harness, d, nm, sc, water, origin, cam, light)["rec"]
+    tf = pose_transforms(gen, bodies)
+    mid = cpu_solid_draw(solid_harness, shape, tf, cam, light, bg, stride=24, flags=np.zeros(8, np.int32))["rec"]
+    depth = cpu_cast(harness, WHOLE_FRAME, 256, shape, tf, np.zeros(8, np.int32), stride=24)
+    assert gen.shadow_map_read(shadow).view(np.uint32).tobytes() == depth["map"].tobytes()
+    dark = cpu_apply(harness, WHOLE_FRAME, 256, opts, depth["map"], mid)
+    lit = CpuPyramid(sky_harness, pano).apply(dark["rec"], cam)
+    env = cpu_environment(env_harness, lit["rec"], cam, FRAME_ENV, pano)["rec"]
+    inst, _, draw = gen.spray_read(spray)
+    time = float(np.float32(gen.spray_stats(spray)["time"]))
+    fin = cpu_billboard_draw(billboard_harness, inst, cam, mat, time=time, order=draw, records=env)["rec"]
+    want = cpu_present(env_harness, fin, FRAME_PRESENT)
+    same_records(rec, fin, "mesh, solids, shadows, sky light, environment, billboards")
+    assert rgba.tobytes() == want["rgba"].tobytes() and lin.tobytes() == want["linear"].tobytes()
+    hit, solid_px = (mid["status"] & HIT) != 0, (mid["status"] & SOLID) != 0
+    reduced = (rec["diffuse"] < mid["diffuse"]).any(-1)
+    print(f"water darkened {int((reduced & ~solid_px).sum())} of {int((hit & ~solid_px).sum())}, solid darkened {int((reduced & solid_px).sum())} of {int(solid_px.sum())}")
+    for kind in (hit & ~solid_px, solid_px):
+        assert (reduced & kind).sum() >= 5 and (~reduced & kind).sum() >= 5               # some of each kind are darkened, others are not (the
+                                                                                             # CPU build on the crates' first poses: 55 water, 18 solid)
+    changed = (rec["diffuse"] != mid["diffuse"]).any(-1) | (rec["specular"] != mid["specular"])
+    assert ((rec["status"][changed] & SHADOWED) != 0).all() and np.array_equal((rec["status"] & SHADOWED) != 0, hit)
+    for h, fn in ((shadow, gen.shadow_map_destroy), (radiance, gen.radiance_destroy), (sky, gen.sky_destroy), (solid, gen.solid_destroy),
+                  (mt, gen.spray_material_destroy), (mesh, gen.mesh_destroy), (spray, gen.spray_destroy), (bodies, gen.bodies_destroy)):
+        fn(h)
+    gen.free()
+
+
+def _order_case(stream=None, torch_stream=None):
+    """ticks and steps, the draws, the cast and the pass, then more ticks and steps with no host synchronisation anywhere, against a context
+    that stopped after the first half and ran the synchronous forms: the cast saw the poses of exactly its point of the stream"""
+    import torch
+    from test_solid_draw import advance, floating_scene
+    from test_spray_draw import buffers_to_host, device_buffers
+    a, pa, sc, ba, sa = floating_scene(stream=stream, steps=2)
+    b, pb, _, bb, sb = floating_scene(steps=2)
+    cam = look(**dict(CRATE_CAM, width=96, height=64))
+    water = grid(32, 4.0)
+    ha, hb = a.mesh_create(*water), b.mesh_create(*water)
+    shape = box(CRATE_SHAPE)
+    so_a, so_b = a.solid_create(*shape), b.solid_create(*shape)
+    ma, mb = a.shadow_map_create(128), b.shadow_map_create(128)
+    frame = dict(center=(0.3, 0.0, 8.5), half_extent=16.0, depth_range=40.0)
+    opts = dict(receive_water=True)
+    origin = W.clipmap_origin(cam.position, 4.0)
+    rgba_dev, rec_dev = device_buffers(cam)
+    a.mesh_draw(ha, cam, origin, sc)                       # the draws' scratch exists from here on
+    a.solid_draw(so_a, ba, cam, pixels=True)
+    torch.cuda.synchronize()
+    advance(a, pa, sc, ba, sa, 4)
+    advance(b, pb, sc, bb, sb, 4)
+    syncs = a.sync_stats()
+
+    def frame_async():
+        a.mesh_draw_async(ha, cam, origin, sc, None, rec_dev)
+        a.solid_draw_async(so_a, ba, cam, None, rec_dev)
+        a.shadow_map_begin(ma, frame)
+        a.shadow_map_cast(ma, so_a, ba)                    # the map's scratch: allocated here, without a synchronisation
+        a.shadow_apply_async(ma, cam, rec_dev, rgba_dev, opts)
+
+    if torch_stream is not None:
+        with torch.cuda.stream(torch_stream):
+            frame_async()
+            copy = rgba_dev.to("cpu", non_blocking=False)  # the caller's own work, ordered by its stream alone
+    else:
+        frame_async()
+    advance(a, pa, sc, ba, sa, 6)
+    assert a.sync_stats() == syncs
+    a.sync()
+    got = buffers_to_host(cam, rgba_dev, rec_dev)
+    _, bg = b.mesh_draw(hb, cam, origin, sc)
+    _, mid = b.solid_draw(so_b, bb, cam, pixels=bg)
+    b.shadow_map_begin(mb, frame)
+    b.shadow_map_cast(mb, so_b, bb)
+    want_rgba, want_rec = b.shadow_apply(mb, cam, mid, opts, rgba=True)
+    assert got["rec"].tobytes() == want_rec.tobytes() and got["rgba"].tobytes() == want_rgba.tobytes()
+    if torch_stream is not None:
+        assert copy.numpy().tobytes() == want_rgba.tobytes()
+    assert (want_rec["diffuse"] < mid["diffuse"]).any(-1).sum() > 20
+    a.shadow_map_begin(ma, frame)                          # the second half moved the crates: their shadows with them
+    a.shadow_map_cast(ma, so_a, ba)
+    assert a.shadow_map_read(ma).tobytes() != b.shadow_map_read(mb).tobytes()
+    for g, s, h, so, bd, m in ((a, sa, ha, so_a, ba, ma), (b, sb, hb, so_b, bb, mb)):
+        g.shadow_map_destroy(m)
+        g.solid_destroy(so)
+        g.mesh_destroy(h)
+        g.spray_destroy(s)
+        g.bodies_destroy(bd)
+        g.free()
+
+
+@pytest.mark.gpu
+def test_async_cast_and_pass_are_ordered_behind_a_tick_and_a_body_step_on_the_contexts_stream():
+    _order_case()
+
+
+@pytest.mark.gpu
+def test_async_cast_and_pass_are_ordered_behind_a_tick_and_a_body_step_on_a_callers_stream():
+    import torch
+    s = torch.cuda.Stream()
+    _order_case(stream=s.cuda_stream, torch_stream=s)
+
+
+@pytest.mark.gpu
+def test_map_scratch_grows_once_and_stays_and_errors_write_nothing(harness):
+    """the first cast allocates without synchronising, the second allocates nothing, a larger one regrows the block behind one
+    synchronisation; then the refusals: foreign and orphaned handles, a map without a frame, bad pointers -- the map keeps its bytes"""
+    import torch
+    from test_spray_draw import device_buffers
+    gen, other = bare_context(), bare_context()
+    st, hull = eight_crates()
+    bodies, foreign_bodies = gen.bodies_create(st, hull), other.bodies_create(st, hull)     # never stepped: the poses of ow_bodies_create
+    shape = box(CRATE_SHAPE)
+    solid, foreign_solid = gen.solid_create(*shape), other.solid_create(*shape)
+    m, foreign_map = gen.shadow_map_create(64), other.shadow_map_create(64)
+    frame = dict(center=(0.3, 0.0, 8.5), half_extent=16.0, depth_range=40.0)
+    with pytest.raises(_lib.OceanWavesError) as e:
+        gen.shadow_map_cast(m, solid, bodies)                                               # no frame yet
+    assert e.value.status == _lib.OW_ERR_STATE
+    assert (gen.shadow_map_read(m) == FLT_MAX).all()                                        # a new map is empty
+    torch.cuda.synchronize()
+    syncs = gen.sync_stats()
+    assert gen.shadow_stats(m, counters=False) == {"casts": 0, "scratch_bytes": 0}
+    gen.shadow_map_begin(m, frame)
+    gen.shadow_map_cast(m, solid, bodies, first=0, count=3)
+    held = gen.shadow_stats(m, counters=False)["scratch_bytes"]
+    assert held > 0 and gen.sync_stats() == syncs
+    gen.shadow_map_cast(m, solid, bodies, first=3, count=3)
+    assert gen.shadow_stats(m, counters=False) == {"casts": 2, "scratch_bytes": held} and gen.sync_stats() == syncs
+    gen.shadow_map_cast(m, solid, bodies)
+    grown = gen.shadow_stats(m, counters=False)["scratch_bytes"]
+    assert grown > held and gen.sync_stats() == syncs + 1
+    gen.shadow_map_cast(m, solid, bodies, first=0, count=2)
+    assert gen.shadow_stats(m, counters=False) == {"casts": 4, "scratch_bytes": grown} and gen.sync_stats() == syncs + 1
+    before, stats = gen.shadow_map_read(m), gen.shadow_stats(m)
+    want = cpu_cast(harness, frame, 64, shape, pose_transforms(gen, bodies), stride=24)
+    assert before.view(np.uint32).tobytes() == want["map"].tobytes() and stats["culled"] + stats["drawn"] == (3 + 3 + 8 + 2) * 12
+    cam = level_camera(20, 12)
+    rgba_dev, rec_dev = device_buffers(cam)
+
+    def refused(fn, *args, status=_lib.OW_ERR_INVALID, **kw):
+        with pytest.raises(_lib.OceanWavesError) as e:
+            fn(*args, **kw)
+        assert e.value.status == status
+
+    refused(gen.shadow_map_cast, foreign_map, solid, bodies)
+    refused(gen.shadow_map_cast, m, foreign_solid, bodies)
+    refused(gen.shadow_map_cast, m, solid, foreign_bodies)
+    refused(gen.shadow_map_cast, m, solid, bodies, first=7, count=2)
+    refused(gen.shadow_map_cast_instances, foreign_map, solid, transform())
+    refused(gen.shadow_map_begin, foreign_map, frame)
+    refused(gen.shadow_map_begin, m, dict(frame, half_extent=0.0))
+    refused(gen.shadow_map_read, foreign_map)
+    refused(gen.shadow_stats, foreign_map)
+    refused(gen.shadow_apply_async, foreign_map, cam, rec_dev, rgba_dev)
+    refused(gen.shadow_apply_async, m, cam, rec_dev, rgba_dev, dict(filter_taps=4))
+    refused(gen.shadow_apply_async, m, cam, rec_dev.data_ptr() + 4, rgba_dev)               # records are read and written as 16-byte vectors
+    refused(gen.shadow_apply_async, m, cam, rec_dev, rgba_dev.data_ptr() + 2)
+    refused(gen.shadow_apply_async, m, level_camera(0, 12), rec_dev, rgba_dev)
+    refused(gen.shadow_map_create, 7)
+    torch.cuda.synchronize()
+    assert not rgba_dev.any() and not rec_dev.any()
+    assert gen.shadow_map_read(m).tobytes() == before.tobytes() and gen.shadow_stats(m) == stats
+    live = bare_context()
+    gen.free()                                                                                # the context goes first: the map is an orphan
+    lib = _lib.load()
+    assert lib.ow_shadow_map_begin(live.context, m.handle, C.byref(W.shadow_frame(frame))) == _lib.OW_ERR_STATE
+    assert lib.ow_shadow_apply_async(live.context, m.handle, C.byref(cam), None, rec_dev.data_ptr(), rgba_dev.data_ptr()) == _lib.OW_ERR_STATE
+    lib.ow_shadow_map_destroy(None, m.handle)                                                 # still the caller's to destroy
+    for h in (solid,):
+        lib.ow_solid_destroy(None, h.handle)
+    lib.ow_bodies_destroy(None, bodies.handle)
+    other.shadow_map_destroy(foreign_map)
+    other.solid_destroy(foreign_solid)
+    other.bodies_destroy(foreign_bodies)
+    other.free()
+    live.free()
+
+
+@pytest.mark.gpu
+def test_the_c_example_writes_the_python_wrappers_image(tmp_path):
+    """examples/shadow_host.c at 256^2, a 48 x 32 PPM of 96 x 64 records, 40 steps, 4096 particles, a 512^2 shadow map, against the wrapper"""
+    from test_environment import example_panorama
+    from test_mesh_draw import REF_BASIS
+    from test_solid_draw import example_crates
+    from test_spray_draw import example_textures
+    exe = build_example(tmp_path)
+    ppm = str(tmp_path / "shadow.ppm")
+    r = subprocess.run([exe, ppm, "48", "32", "40", "256", "4096", "2", "512"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr
+    kv = dict(p.split("=") for p in r.stdout.split())
+    assert kv["finite"] == "1" and (kv["record_width"], kv["record_height"], kv["shadow_size"], kv["casts"], kv["skipped_instances"]) == ("96", "64", "512", "1", "0")
+    raw = open(ppm, "rb").read()
+    head = b"P6\n48 32\n255\n"
+    assert raw.startswith(head) and len(raw) == len(head) + 48 * 32 * 3
+    gen, params = make_gen(256, [0, 1, 2])
+    sc = scales_of(params)
+    spray = gen.spray_create({"amount": 4096})
+    bodies = gen.bodies_create(*example_crates())
+    for _ in range(40):
+        gen.update_all(UPDATE_DELTA, params)
+        gen.bodies_step(bodies, sc, 4, UPDATE_DELTA / 4, {"warm_start": True})
+        gen.spray_step(spray, UPDATE_DELTA, sc)
+    cam = W.camera((0.0, 10.0, -25.0), REF_BASIS, 75.0, 96, 64, 4000.0)
+    mesh = gen.mesh_create(*grid(128, 4.0))
+    dark = (0.0, 0.0, 0.0)
+    _, bg = gen.mesh_draw(mesh, cam, W.clipmap_origin(cam.position, 4.0), sc, {"falloff": True, "cull_back": True, "ambient_color": dark})
+    solid = gen.solid_create(*box(CRATE_SHAPE))
+    _, mid = gen.solid_draw(solid, bodies, cam, {"ambient_color": dark}, pixels=bg)
+    shadow = gen.shadow_map_create(512)
+    gen.shadow_map_begin(shadow, dict(center=(0.0, 0.0, 10.0), half_extent=40.0, depth_range=80.0))
+    gen.shadow_map_cast(shadow, solid, bodies)
+    st = gen.shadow_stats(shadow)
+    _, shaded = gen.shadow_apply(shadow, cam, mid, dict(receive_water=True))
+    sky = gen.sky_create(example_panorama())
+    radiance = gen.radiance_create(sky)
+    lit = gen.sky_light_apply(radiance, cam, shaded)
+    env = gen.environment_apply(cam, lit, sky)
+    m = gen.spray_material_create(*example_textures())
+    _, rec = gen.spray_draw(spray, m, cam, pixels=env)
+    rgba = gen.present(cam, rec, {"downsample": 2})
+    assert np.frombuffer(raw[len(head):], np.uint8).reshape(32, 48, 3).tobytes() == rgba[..., :3].tobytes()
+    assert (int(kv["triangles_culled"]), int(kv["triangles_cast"])) == (st["culled"], st["drawn"]) and st["culled"] + st["drawn"] == 36 * 12
+    shadowed = (rec["status"] & SHADOWED) != 0
+    assert int(kv["receivers"]) == int(shadowed.sum()) == int(((rec["status"] & HIT) != 0).sum()) > 1000
+    assert int(kv["water_receivers"]) == int((shadowed & ((rec["status"] & SOLID) == 0)).sum())
+    assert (shaded["diffuse"] < mid["diffuse"]).any(-1).sum() > 30                          # the crates' shadows are in the picture
+    for h, fn in ((m, gen.spray_material_destroy), (radiance, gen.radiance_destroy), (sky, gen.sky_destroy), (shadow, gen.shadow_map_destroy),
+                  (solid, gen.solid_destroy), (mesh, gen.mesh_destroy), (bodies, gen.bodies_destroy), (spray, gen.spray_destroy)):
+        fn(h)
+    gen.free()
