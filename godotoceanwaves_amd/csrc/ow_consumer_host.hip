@@ -68,6 +68,24 @@ ow_status read_back(ow_context *c, void *dst, const void *src, size_t bytes) {
     return OW_OK;
 }
 
+constexpr size_t kCounterHead = 256;  // the four class counters, at the head of the solid draw's scratch and of a shadow map's block
+// The four counters of a mesh draw, a solid draw or a shadow map read back into n[kTriSkipped .. kTriWave] (kSolid* and kShadow* are defined
+// as these): skipped (triangles of a mesh, instances of a solid or a cast), culled, and the two drawn classes.  Zeros, and the device is not
+// touched, where nothing is `wanted` or there are no counters yet.
+ow_status read_class_counts(ow_context *c, const void *counters_dev, bool wanted, uint64_t n[4]) {
+    uint32_t w[4] = {0, 0, 0, 0};
+    if (wanted && counters_dev)
+        if (ow_status st = read_back(c, w, counters_dev, sizeof(w)); st != OW_OK) return st;
+    for (int k = 0; k < 4; ++k) n[k] = w[k];
+    return OW_OK;
+}
+// an options record's lane_box, checked, and as a set-up reads it (ow_mesh.h mesh_lane_box; out may be null: ow_shadow.h shadow_params maps its own)
+ow_status resolve_lane_box(int32_t lane_box, int *out) {
+    if (lane_box < -1 || lane_box > 64) return fail(OW_ERR_INVALID, "lane_box %d outside [-1,64]", lane_box);
+    if (out) *out = ow::mesh_lane_box(lane_box);
+    return OW_OK;
+}
+
 ow::SurfaceScales surface_scales(const float *map_scales, int num_cascades) {
     ow::SurfaceScales sc;
     std::memset(&sc, 0, sizeof(sc));
@@ -916,11 +934,10 @@ ow_status resolve_mesh_options(const ow_mesh_options *opts, ow::MeshParams *mp, 
     if (!opts) return OW_OK;
     if (!std::isfinite(opts->near)) return fail(OW_ERR_INVALID, "near is not finite");
     if (opts->flags & ~OW_MESH_CULL_BACK) return fail(OW_ERR_INVALID, "unknown mesh flags 0x%x", opts->flags);
-    if (opts->lane_box < -1 || opts->lane_box > 64) return fail(OW_ERR_INVALID, "lane_box %d outside [-1,64]", opts->lane_box);
+    if (ow_status st = resolve_lane_box(opts->lane_box, &mp->lane_box); st != OW_OK) return st;
     if (ow_status st = check_reserved(opts->reserved, "ow_mesh_options"); st != OW_OK) return st;
     if (opts->near > 0.0f) mp->near = opts->near;
     mp->cull_back = (opts->flags & OW_MESH_CULL_BACK) ? 1 : 0;
-    mp->lane_box = opts->lane_box == 0 ? ow::kMeshLaneBox : (opts->lane_box < 0 ? 0 : opts->lane_box);
     return OW_OK;
 }
 
@@ -1061,14 +1078,12 @@ ow_status ow_mesh_draw_async(ow_context *c, ow_mesh *m, const ow_camera *camera,
 
 ow_status ow_mesh_stats(ow_context *c, ow_mesh *m, uint64_t *draws, uint64_t *skipped, uint64_t *culled, uint64_t *per_lane, uint64_t *cooperative) {
     if (ow_status st = check_mesh_handle(c, m); st != OW_OK) return st;
-    if (skipped || culled || per_lane || cooperative) {
-        uint32_t w[4] = {0, 0, 0, 0};
-        if (ow_status st = read_back(c, w, m->A.counters, sizeof(w)); st != OW_OK) return st;
-        if (skipped) *skipped = w[ow::kTriSkipped];
-        if (culled) *culled = w[ow::kTriCulled];
-        if (per_lane) *per_lane = w[ow::kTriLane];
-        if (cooperative) *cooperative = w[ow::kTriWave];
-    }
+    uint64_t n[4];
+    if (ow_status st = read_class_counts(c, m->A.counters, skipped || culled || per_lane || cooperative, n); st != OW_OK) return st;
+    if (skipped) *skipped = n[ow::kTriSkipped];
+    if (culled) *culled = n[ow::kTriCulled];
+    if (per_lane) *per_lane = n[ow::kTriLane];
+    if (cooperative) *cooperative = n[ow::kTriWave];
     if (draws) *draws = m->draws;
     return OW_OK;
 }
@@ -1389,8 +1404,6 @@ ow_status ow_billboard_draw_stats(ow_context *c, uint64_t *draws, uint64_t *cull
 /* ---- the solids (ow_solid.h, ow_solid.hip) ---- */
 
 namespace {
-constexpr size_t kSolidHead = 256;  // the four counters, at the head of the scratch block
-
 // the reference scene's sun and ambient (ow_render_options_default), near 0.05, a wooden brown
 void solid_defaults(ow_solid_options *o) {
     ow_render_options ro;
@@ -1427,7 +1440,7 @@ ow_status resolve_solid_options(const ow_solid_options *opts, ow::SolidParams *s
         for (int k = 0; k < 3; ++k)
             if (!(std::fabs(v[k]) <= ow::kSolidColorMax)) return fail(OW_ERR_INVALID, "ow_solid_options: a colour or the light direction is not finite (or beyond 1e12)");
     if (!std::isfinite(opts->near)) return fail(OW_ERR_INVALID, "near is not finite");
-    if (opts->lane_box < -1 || opts->lane_box > 64) return fail(OW_ERR_INVALID, "lane_box %d outside [-1,64]", opts->lane_box);
+    if (ow_status st = resolve_lane_box(opts->lane_box, &sp->mp.lane_box); st != OW_OK) return st;
     if (opts->flags & ~OW_SOLID_TWO_SIDED) return fail(OW_ERR_INVALID, "unknown solid flags 0x%x", opts->flags);
     if (ow_status st = check_reserved(opts->reserved, "ow_solid_options"); st != OW_OK) return st;
     const double lx = opts->light_direction[0], ly = opts->light_direction[1], lz = opts->light_direction[2];
@@ -1443,7 +1456,6 @@ ow_status resolve_solid_options(const ow_solid_options *opts, ow::SolidParams *s
     sp->two_sided = (opts->flags & OW_SOLID_TWO_SIDED) ? 1 : 0;
     sp->mp.near = opts->near > 0.0f ? opts->near : ow::kMeshDefaultNear;
     sp->mp.cull_back = sp->two_sided ? 0 : 1;
-    sp->mp.lane_box = opts->lane_box == 0 ? ow::kMeshLaneBox : (opts->lane_box < 0 ? 0 : opts->lane_box);
     sp->mp.camera_ok = 1;
     return OW_OK;
 }
@@ -1461,9 +1473,9 @@ ow_status check_solid_draw(const ow_context *c, const ow_solid *solid, const ow_
 // the number of instances of one draw against the shape
 ow_status check_solid_count(const ow_solid *solid, int64_t count) {
     if (count < 0 || count > OW_SOLID_MAX_INSTANCES) return fail(OW_ERR_INVALID, "%lld instances outside [0,%d]", (long long)count, OW_SOLID_MAX_INSTANCES);
-    if (count * solid->num_triangles > ow::kSolidMaxProduct || count * solid->num_vertices > ow::kSolidMaxProduct)
-        return fail(OW_ERR_INVALID, "%lld instances of %d triangles and %d vertices: more than 2^24 per draw", (long long)count, solid->num_triangles,
-                    solid->num_vertices);
+    if (count * solid->shape.num_triangles > ow::kSolidMaxProduct || count * solid->shape.num_vertices > ow::kSolidMaxProduct)
+        return fail(OW_ERR_INVALID, "%lld instances of %d triangles and %d vertices: more than 2^24 per draw", (long long)count, solid->shape.num_triangles,
+                    solid->shape.num_vertices);
     return OW_OK;
 }
 ow_status check_solid_bodies(const ow_context *c, const ow_solid *solid, const ow_bodies *set, int32_t first, int32_t count) {
@@ -1473,40 +1485,32 @@ ow_status check_solid_bodies(const ow_context *c, const ow_solid *solid, const o
     return check_solid_count(solid, count);
 }
 
-// The scratch of a draw and its launches on the context's stream.  Sources: a body set's resident pose records and fault flags, or `upload`
-// (host transforms, copied into the scratch first).  A block that has to grow while launches already enqueued may still read it is replaced
-// behind one synchronisation (sync_before_growth).
+// Where the instances of a draw or a shadow cast come from: a body set's resident pose records and fault flags, or `upload` (host
+// transforms: instance_upload_bytes of the caller's scratch at `staging`, copied there on `s` first).
+size_t instance_upload_bytes(const float *upload, int count) { return upload ? (size_t)count * ow::kSolidTransformFloats * sizeof(float) : 0; }
+ow_status instance_source(const ow_bodies *set, int first, const float *upload, int count, void *staging, hipStream_t s, ow::SolidInstances *in) {
+    if (set) *in = ow::SolidInstances{(const float *)(set->A.records + first), set->A.flags + first, (int)(sizeof(ow::BuoyancyBody) / sizeof(float)), count};
+    else *in = ow::SolidInstances{(const float *)staging, nullptr, ow::kSolidTransformFloats, count};
+    if (!set && count > 0) OW_HIP(hipMemcpyAsync(staging, upload, instance_upload_bytes(upload, count), hipMemcpyHostToDevice, s));
+    return OW_OK;
+}
+
+// The scratch of a draw and its launches on the context's stream, its instances from instance_source.  A block that has to grow while
+// launches already enqueued may still read it is replaced behind one synchronisation (sync_before_growth).
 ow_status solid_enqueue(ow_context *c, const ow_solid *solid, const ow::CameraParams &cp, const ow::SolidParams &sp, const ow_bodies *set, int first,
                         const float *upload, int count, ow::RenderPixel *pixels_dev, uint32_t *rgba_dev) {
     Layout L;
-    L.take(kSolidHead);  // the counters, at 0
-    const size_t v_off = L.take((size_t)count * solid->num_vertices * sizeof(ow::MeshVertex));
+    L.take(kCounterHead);  // the counters, at 0
+    const size_t v_off = L.take((size_t)count * solid->shape.num_vertices * sizeof(ow::MeshVertex));
     const size_t w_off = L.take((size_t)cp.width * cp.height * sizeof(uint64_t));
-    const size_t t_off = L.take(upload ? (size_t)count * ow::kSolidTransformFloats * sizeof(float) : 0);
+    const size_t t_off = L.take(instance_upload_bytes(upload, count));
     if (ow_status st = sync_before_growth(c, c->solid, L.total); st != OW_OK) return st;
     if (ow_status st = c->solid.ensure(L.total, 0, 1, "bytes of solid scratch"); st != OW_OK) return st;
     char *base = (char *)c->solid.ptr;
     hipStream_t s = main_stream(c);
-    ow::SolidArrays A;
-    A.local = solid->local;
-    A.indices = solid->indices;
-    A.num_vertices = solid->num_vertices;
-    A.num_triangles = solid->num_triangles;
-    A.counters = (uint32_t *)base;
-    A.verts = (ow::MeshVertex *)(base + v_off);
-    A.vis = (uint64_t *)(base + w_off);
+    const ow::SolidArrays A{solid->shape, (uint32_t *)base, (ow::MeshVertex *)(base + v_off), (uint64_t *)(base + w_off)};
     ow::SolidInstances in;
-    in.count = count;
-    if (set) {
-        in.transforms = (const float *)(set->A.records + first);
-        in.flags = set->A.flags + first;
-        in.stride = (int)(sizeof(ow::BuoyancyBody) / sizeof(float));
-    } else {
-        in.transforms = (const float *)(base + t_off);
-        in.flags = nullptr;
-        in.stride = ow::kSolidTransformFloats;
-        if (count > 0) OW_HIP(hipMemcpyAsync(base + t_off, upload, (size_t)count * ow::kSolidTransformFloats * sizeof(float), hipMemcpyHostToDevice, s));
-    }
+    if (ow_status st = instance_source(set, first, upload, count, base + t_off, s, &in); st != OW_OK) return st;
     OW_HIP(ow::launch_solid_draw(A, in, cp, sp, rgba_dev, pixels_dev, s));
     ++c->solid_draws;
     return OW_OK;
@@ -1544,13 +1548,10 @@ ow_status ow_solid_create(ow_context *c, const float *vertices_xyz, int32_t num_
     ow_solid *m;
     if (ow_status st = new_handle(c, L.total, "solid", &m); st != OW_OK) return st;
     char *base = (char *)m->block;
-    m->local = (const float *)(base + l_off);
-    m->indices = (const int32_t *)(base + i_off);
-    m->num_vertices = num_vertices;
-    m->num_triangles = num_triangles;
+    m->shape = ow::SolidShape{(const float *)(base + l_off), (const int32_t *)(base + i_off), num_vertices, num_triangles};
     hipStream_t s = main_stream(c);
-    const bool enqueued = hipMemcpyAsync((void *)m->local, vertices_xyz, nv * 3 * sizeof(float), hipMemcpyHostToDevice, s) == hipSuccess &&
-                          hipMemcpyAsync((void *)m->indices, indices, nt * 3 * sizeof(int32_t), hipMemcpyHostToDevice, s) == hipSuccess;
+    const bool enqueued = hipMemcpyAsync((void *)m->shape.local, vertices_xyz, nv * 3 * sizeof(float), hipMemcpyHostToDevice, s) == hipSuccess &&
+                          hipMemcpyAsync((void *)m->shape.indices, indices, nt * 3 * sizeof(int32_t), hipMemcpyHostToDevice, s) == hipSuccess;
     return finish_create(c, m, s, enqueued, "solid upload", out);
 }
 
@@ -1592,14 +1593,11 @@ ow_status ow_solid_draw_instances(ow_context *c, ow_solid *solid, const float *t
 
 ow_status ow_solid_draw_stats(ow_context *c, uint64_t *draws, uint64_t *skipped_instances, uint64_t *culled, uint64_t *drawn, uint64_t *scratch_bytes) {
     if (!c) return fail(OW_ERR_INVALID, "null context");
-    if (skipped_instances || culled || drawn) {
-        uint32_t w[4] = {0, 0, 0, 0};
-        if (c->solid.ptr)  // no draw yet: zeros, and the device is not touched
-            if (ow_status st = read_back(c, w, c->solid.ptr, sizeof(w)); st != OW_OK) return st;
-        if (skipped_instances) *skipped_instances = w[ow::kSolidSkippedInstances];
-        if (culled) *culled = w[ow::kSolidCulled];
-        if (drawn) *drawn = (uint64_t)w[ow::kSolidLane] + w[ow::kSolidWave];
-    }
+    uint64_t n[4];  // no draw yet, no scratch: zeros, and the device is not touched
+    if (ow_status st = read_class_counts(c, c->solid.ptr, skipped_instances || culled || drawn, n); st != OW_OK) return st;
+    if (skipped_instances) *skipped_instances = n[ow::kSolidSkippedInstances];
+    if (culled) *culled = n[ow::kSolidCulled];
+    if (drawn) *drawn = n[ow::kSolidLane] + n[ow::kSolidWave];
     if (draws) *draws = c->solid_draws;
     if (scratch_bytes) *scratch_bytes = c->solid.bytes;
     return OW_OK;
@@ -2095,8 +2093,6 @@ ow_status ow_radiance_light_apply_async(ow_context *c, ow_radiance *radiance, co
 /* ---- the sun shadows (ow_shadow.h, ow_shadow.hip) ---- */
 
 namespace {
-constexpr size_t kShadowHead = 256;  // the four counters, at the head of the map's block
-
 void shadow_frame_defaults(ow_shadow_frame *o) {
     ow_render_options ro;
     render_defaults(&ro);
@@ -2131,7 +2127,7 @@ ow_status resolve_shadow_frame(const ow_shadow_frame *f, int size, ow::ShadowPar
             return fail(OW_ERR_INVALID, "ow_shadow_frame: light_direction or center is not finite");
     if (!(f->half_extent > 0.0f && f->half_extent <= ow::kShadowRangeMax)) return fail(OW_ERR_INVALID, "ow_shadow_frame: half_extent outside (0,1e6]");
     if (!(f->depth_range > 0.0f && f->depth_range <= ow::kShadowRangeMax)) return fail(OW_ERR_INVALID, "ow_shadow_frame: depth_range outside (0,1e6]");
-    if (f->lane_box < -1 || f->lane_box > 64) return fail(OW_ERR_INVALID, "lane_box %d outside [-1,64]", f->lane_box);
+    if (ow_status st = resolve_lane_box(f->lane_box, nullptr); st != OW_OK) return st;
     if (f->flags & ~OW_SHADOW_CAST_BOTH_SIDES) return fail(OW_ERR_INVALID, "unknown shadow frame flags 0x%x", f->flags);
     if (ow_status st = check_reserved(f->reserved, "ow_shadow_frame"); st != OW_OK) return st;
     ow::ShadowFrame fr;
@@ -2173,41 +2169,23 @@ ow_status check_shadow_apply(const ow_context *c, const ow_shadow_map *map, cons
     return OW_OK;
 }
 
-// One cast's launches on the context's stream.  Sources as for solid_enqueue: a body set's resident records, or `upload` (copied into the
-// map's scratch first).
+// One cast's launches on the context's stream, its instances from instance_source (an upload is copied into the map's scratch first).
 ow_status shadow_cast_enqueue(ow_context *c, ow_shadow_map *map, const ow_solid *solid, const ow_bodies *set, int first, const float *upload, int count) {
     if (!map->P.ok) return fail(OW_ERR_STATE, "the shadow map has no frame: ow_shadow_map_begin first");
     OW_HIP(hipSetDevice(c->device));
     Layout L;
-    const size_t v_off = L.take((size_t)count * solid->num_vertices * sizeof(ow::ShadowVertex));
-    const size_t t_off = L.take(upload ? (size_t)count * ow::kSolidTransformFloats * sizeof(float) : 0);
+    const size_t v_off = L.take((size_t)count * solid->shape.num_vertices * sizeof(ow::ShadowVertex));
+    const size_t t_off = L.take(instance_upload_bytes(upload, count));
     if (ow_status st = sync_before_growth(c, map->scratch, L.total); st != OW_OK) return st;
     if (ow_status st = map->scratch.ensure(L.total, 0, 1, "bytes of shadow scratch"); st != OW_OK) return st;
     char *base = (char *)map->scratch.ptr;
     hipStream_t s = main_stream(c);
-    ow::ShadowArrays A;
-    A.local = solid->local;
-    A.indices = solid->indices;
-    A.num_vertices = solid->num_vertices;
-    A.num_triangles = solid->num_triangles;
-    A.counters = map->counters;
-    A.verts = (ow::ShadowVertex *)(base + v_off);
-    A.map = map->map;
+    const ow::ShadowArrays A{solid->shape, map->counters, (ow::ShadowVertex *)(base + v_off), map->map};
     ow::SolidInstances in;
-    in.count = count;
-    if (set) {
-        in.transforms = (const float *)(set->A.records + first);
-        in.flags = set->A.flags + first;
-        in.stride = (int)(sizeof(ow::BuoyancyBody) / sizeof(float));
-    } else {
-        in.transforms = (const float *)(base + t_off);
-        in.flags = nullptr;
-        in.stride = ow::kSolidTransformFloats;
-        if (count > 0) OW_HIP(hipMemcpyAsync(base + t_off, upload, (size_t)count * ow::kSolidTransformFloats * sizeof(float), hipMemcpyHostToDevice, s));
-    }
+    if (ow_status st = instance_source(set, first, upload, count, base + t_off, s, &in); st != OW_OK) return st;
     OW_HIP(ow::launch_shadow_cast(A, in, map->P, s));
     ++map->casts;
-    map->instances_triangles += (uint64_t)count * solid->num_triangles;
+    map->instances_triangles += (uint64_t)count * solid->shape.num_triangles;
     return OW_OK;
 }
 }  // namespace
@@ -2226,7 +2204,7 @@ ow_status ow_shadow_map_create(ow_context *c, int32_t size, ow_shadow_map **out)
     if (size < OW_SHADOW_MIN_SIZE || size > OW_SHADOW_MAX_SIZE) return fail(OW_ERR_INVALID, "shadow map size %d outside [%d,%d]", size, OW_SHADOW_MIN_SIZE, OW_SHADOW_MAX_SIZE);
     if (!c) return fail(OW_ERR_INVALID, "null context");
     Layout L;
-    const size_t c_off = L.take(kShadowHead), m_off = L.take((size_t)size * size * sizeof(uint32_t));
+    const size_t c_off = L.take(kCounterHead), m_off = L.take((size_t)size * size * sizeof(uint32_t));
     ow_shadow_map *map;
     if (ow_status st = new_handle(c, L.total, "shadow map", &map); st != OW_OK) return st;
     char *base = (char *)map->block;
@@ -2235,10 +2213,7 @@ ow_status ow_shadow_map_create(ow_context *c, int32_t size, ow_shadow_map **out)
     map->counters = (uint32_t *)(base + c_off);
     map->map = (uint32_t *)(base + m_off);
     hipStream_t s = main_stream(c);
-    ow::ShadowArrays A{};
-    A.counters = map->counters;
-    A.map = map->map;
-    const bool enqueued = ow::launch_shadow_clear(A, size, s) == hipSuccess;
+    const bool enqueued = ow::launch_shadow_clear(ow::ShadowArrays{{}, map->counters, nullptr, map->map}, size, s) == hipSuccess;
     return finish_create(c, map, s, enqueued, "shadow map clear", out);
 }
 
@@ -2256,10 +2231,7 @@ ow_status ow_shadow_map_begin(ow_context *c, ow_shadow_map *map, const ow_shadow
     if (ow_status st = check_shadow_map(c, map); st != OW_OK) return st;
     if (ow_status st = resolve_shadow_frame(frame, map->size, &P); st != OW_OK) return st;
     OW_HIP(hipSetDevice(c->device));
-    ow::ShadowArrays A{};
-    A.counters = map->counters;
-    A.map = map->map;
-    OW_HIP(ow::launch_shadow_clear(A, map->size, main_stream(c)));
+    OW_HIP(ow::launch_shadow_clear(ow::ShadowArrays{{}, map->counters, nullptr, map->map}, map->size, main_stream(c)));
     map->P = P;
     map->casts = map->instances_triangles = 0;
     return OW_OK;
@@ -2314,13 +2286,11 @@ ow_status ow_shadow_apply_async(ow_context *c, ow_shadow_map *map, const ow_came
 ow_status ow_shadow_stats(ow_context *c, ow_shadow_map *map, uint64_t *casts, uint64_t *skipped_instances, uint64_t *culled, uint64_t *drawn,
                           uint64_t *scratch_bytes) {
     if (ow_status st = check_shadow_map(c, map); st != OW_OK) return st;
-    if (skipped_instances || culled || drawn) {
-        uint32_t w[4] = {0, 0, 0, 0};
-        if (ow_status st = read_back(c, w, map->counters, sizeof(w)); st != OW_OK) return st;
-        if (skipped_instances) *skipped_instances = w[ow::kShadowSkippedInstances];
-        if (culled) *culled = w[ow::kShadowCulled];
-        if (drawn) *drawn = (uint64_t)w[ow::kShadowLane] + w[ow::kShadowWave];
-    }
+    uint64_t n[4];
+    if (ow_status st = read_class_counts(c, map->counters, skipped_instances || culled || drawn, n); st != OW_OK) return st;
+    if (skipped_instances) *skipped_instances = n[ow::kShadowSkippedInstances];
+    if (culled) *culled = n[ow::kShadowCulled];
+    if (drawn) *drawn = n[ow::kShadowLane] + n[ow::kShadowWave];
     if (casts) *casts = map->casts;
     if (scratch_bytes) *scratch_bytes = map->scratch.bytes;
     return OW_OK;

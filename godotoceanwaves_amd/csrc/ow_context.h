@@ -47,9 +47,7 @@ struct ow_billboard_material : ow::Handle {
 
 // a solid shape (ow_solid_create): the block holds local positions and indices
 struct ow_solid : ow::Handle {
-    const float *local = nullptr;
-    const int32_t *indices = nullptr;
-    int num_vertices = 0, num_triangles = 0;
+    ow::SolidShape shape{};
 };
 
 // a panorama sky (ow_sky_create): the block holds the sRGB table and the texels

@@ -133,10 +133,13 @@ hipError_t launch_billboard_draw(const BillboardArrays &A, const CameraParams &c
                                  RenderPixel *pixels_dev, hipStream_t s);
 
 // a solid draw (ow_solid.hip; the vertex stage, the winner, the depth test and the shading in ow_solid.h, the coverage rule in ow_mesh.h)
-struct SolidArrays {
+struct SolidShape {          // an ow_solid's device arrays: what the draw and the shadow cast repeat per instance
     const float *local;      // [num_vertices][3] the shape, as uploaded
     const int32_t *indices;  // [num_triangles][3]
     int num_vertices, num_triangles;
+};
+struct SolidArrays {
+    SolidShape shape;
     uint32_t *counters;      // [4] scratch: kSolidSkippedInstances .. kSolidWave of the last draw
     MeshVertex *verts;       // [instances][num_vertices] scratch
     uint64_t *vis;           // [cam.width x cam.height] scratch: the visibility words
@@ -162,9 +165,7 @@ hipError_t launch_sky_light_apply(const CameraParams &cam, const SkyLightParams 
 
 // the sun shadows (ow_shadow.hip; the frame, the coverage rule, the filter and the record's arithmetic in ow_shadow.h)
 struct ShadowArrays {
-    const float *local;      // [num_vertices][3] the casting shape, as uploaded
-    const int32_t *indices;  // [num_triangles][3]
-    int num_vertices, num_triangles;
+    SolidShape shape;        // the casting shape
     uint32_t *counters;      // [4] kShadowSkippedInstances .. kShadowWave since the last clear
     ShadowVertex *verts;     // [instances][num_vertices] scratch
     uint32_t *map;           // [size][size] the depth words

@@ -57,6 +57,8 @@ struct MeshParams {
     int lane_box;      // kMeshLaneBox, or what a measurement asks for (0: every triangle goes to the wave)
     int camera_ok;     // 0: the camera is not finite -- nothing is drawn and every pixel carries kRayInvalid
 };
+// the lane_box of an options record (-1 .. 64, checked by the host) as a set-up reads it: 0 selects the default, -1 sends every triangle to the wave
+inline int mesh_lane_box(int32_t option) { return option == 0 ? kMeshLaneBox : (option < 0 ? 0 : option); }
 
 // what the four counters of a draw add up over: every triangle is exactly one of these
 enum : int { kTriSkipped = 0, kTriCulled = 1, kTriLane = 2, kTriWave = 3 };

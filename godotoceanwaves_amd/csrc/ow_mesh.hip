@@ -20,30 +20,22 @@ namespace {
 __global__ void __launch_bounds__(256) k_mesh_vertices(const u16x4 *disp, int n, int cascades, const float *local, int count, SurfaceScales scales,
                                                        MeshParams mp, CameraParams cam, int has_camera, float ox, float oy, float oz,
                                                        MeshVertex *out) {
-    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= count) return;
     const float l[3] = {local[3 * (size_t)i], local[3 * (size_t)i + 1], local[3 * (size_t)i + 2]}, origin[3] = {ox, oy, oz};
-    const MeshVertex v = mesh_vertex(disp, n, cascades, scales, mp, cam, has_camera != 0, l, origin);
-    struct Words {
-        u32x4 v[sizeof(MeshVertex) / 16];
-    };
-    const Words w = __builtin_bit_cast(Words, v);
-    u32x4 *dst = (u32x4 *)(out + i);
-    for (int k = 0; k < (int)(sizeof(MeshVertex) / 16); ++k) dst[k] = w.v[k];
+    store_record(out + i, mesh_vertex(disp, n, cascades, scales, mp, cam, has_camera != 0, l, origin));
 }
 
 __global__ void __launch_bounds__(256) k_mesh_clear(uint64_t *vis, size_t pixels, uint32_t *counters) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < pixels) vis[i] = kMeshNoTriangle;
-    if (i < 4) counters[i] = 0u;
+    clear_words(vis, pixels, kMeshNoTriangle, counters);
 }
 
 // One 64-lane wave per 64 triangles, one wave per block.  A clipmap seen from eye height has triangles hundreds of pixels wide beside the
 // camera and sub-pixel ones towards the horizon in the same draw: each lane sets its own triangle up (tri_setup: class, planes, pixel
 // box); a lane whose box is at most lane_box centres a side walks it alone; the triangles with larger boxes are found by a ballot and
 // taken one after the other by the whole wave, their planes and box read from the owning lane (the source lane is wave-uniform: a lane
-// read, no LDS), the 64 lanes sweeping the box in 8 x 8 tiles.  The four classes are counted per wave and added once.
+// read, no LDS), the 64 lanes sweeping the box in 8 x 8 tiles: ow_raster.h's raster_wave into the visibility-buffer target, the walk
+// k_solid_raster and k_shadow_raster run.  The four classes are counted per wave and added once.
 __global__ void __launch_bounds__(64) k_mesh_raster(const int32_t *indices, int num_triangles, const MeshVertex *verts, CameraParams cam, MeshParams mp,
                                                     uint64_t *vis, uint32_t *counters) {
     const int lane = (int)threadIdx.x;
@@ -59,7 +51,7 @@ __global__ void __launch_bounds__(64) k_mesh_raster(const int32_t *indices, int 
         const uint64_t m = __ballot(s.kind == k);
         if (lane == 0 && m) atomicAdd(counters + k, (uint32_t)__popcll(m));
     }
-    raster_wave(s, lane, tri, (int)blockIdx.x * 64, cam, mp, vis);
+    raster_wave(VisTarget{cam, mp, vis}, s, lane, tri, (int)blockIdx.x * 64);
 }
 
 // One lane per pixel, one 8 x 8 tile per wave, as k_render_view: lane l is pixel (8 tx + (l & 7), 8 ty + (l >> 3)).  The barycentrics come
@@ -68,7 +60,6 @@ template <bool kRecords>
 __global__ void __launch_bounds__(64) k_mesh_shade(const u16x4 *disp, const u16x4 *norm, int n, int cascades, SurfaceScales scales, CameraParams cam,
                                                    ShadeParams sp, MeshParams mp, const uint64_t *vis, const int32_t *indices, const MeshVertex *verts,
                                                    int tiles_x, uint32_t *rgba, RenderPixel *pixels) {
-    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
     const int lane = (int)threadIdx.x;
     const int tx = (int)blockIdx.x % tiles_x, ty = (int)blockIdx.x / tiles_x;
     const int i = 8 * tx + (lane & 7), j = 8 * ty + (lane >> 3);
@@ -77,14 +68,7 @@ __global__ void __launch_bounds__(64) k_mesh_shade(const u16x4 *disp, const u16x
     uint32_t word;
     const RenderPixel px = mesh_pixel(disp, norm, n, cascades, scales, cam, sp, mp, vis[at], indices, verts, i, j, &word);
     if (rgba) rgba[at] = word;
-    if (kRecords) {
-        struct Words {
-            u32x4 v[sizeof(RenderPixel) / 16];
-        };
-        const Words w = __builtin_bit_cast(Words, px);
-        u32x4 *dst = (u32x4 *)(pixels + at);
-        for (int k = 0; k < (int)(sizeof(RenderPixel) / 16); ++k) dst[k] = w.v[k];
-    }
+    if (kRecords) store_record(pixels + at, px);
 }
 
 }  // namespace

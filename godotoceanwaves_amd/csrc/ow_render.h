@@ -50,6 +50,22 @@ struct RenderPixel {
 };
 static_assert(sizeof(RenderPixel) == 128 && offsetof(RenderPixel, dist) == 44 && offsetof(RenderPixel, color) == 100, "record layout");
 
+#if OW_DEVICE_BUILD
+// A record whose size is a multiple of 16 bytes as 16-byte vectors, and its store to a 16-byte aligned address as that many vector stores:
+// how every kernel writes a whole RenderPixel, MeshVertex or ShadowVertex.  (A kernel that touches chosen vectors only uses the type.)
+template <typename T>
+struct RecordWords {
+    typedef uint32_t Vec __attribute__((ext_vector_type(4)));
+    static_assert(sizeof(T) % 16 == 0, "whole 16-byte vectors");
+    Vec v[sizeof(T) / 16];
+};
+template <typename T>
+OW_DEV void store_record(T *dst, const T &rec) {
+    const RecordWords<T> w = __builtin_bit_cast(RecordWords<T>, rec);
+    for (int k = 0; k < (int)(sizeof(T) / 16); ++k) ((typename RecordWords<T>::Vec *)dst)[k] = w.v[k];
+}
+#endif
+
 constexpr int kRenderMaxSide = 8192;  // OW_RENDER_MAX_SIDE
 
 // the camera as the host resolves it from ow_camera

@@ -16,9 +16,8 @@
 //             r_k = w_k - center_k; u = dot3(x, r); v = dot3(y, r); d = depth_range - dot3(z, r) (metres from the frame's near plane, growing
 //             away from the light); s = u k + half, t = v k + half with k = size / (2 half_extent) narrowed once and half = size / 2.
 //             Texel (i, j) has its centre at (i + 0.5, j + 0.5).
-//   vertex    world position: solid_vertex's row product, ((T[3k] l_0 + T[3k+1] l_1) + T[3k+2] l_2) + T[9+k], the same bits as the draw's;
-//             the skip rule is solid_instance_ok's.  A vertex whose world position or (s, t, d) is not finite is flagged; its triangles
-//             are culled.
+//   vertex    world position: ow_solid.h's solid_world, the function the draw's solid_vertex calls; the skip rule is solid_instance_ok's.
+//             A vertex whose world position or (s, t, d) is not finite is flagged; its triangles are culled.
 //   facing    A = (s1 - s0)(t2 - t0) - (s2 - s0)(t1 - t0): the differences in FP32, the products and their difference in FP64.  A > 0 is a
 //             triangle whose outward side is turned towards the light.  Only A < 0 is cast unless both sides are asked for: the faces
 //             of a closed body that the light reaches never enter the map, so a body cannot shadow its own lit faces whatever the bias.
@@ -81,7 +80,7 @@ constexpr uint32_t kShadowVertexNotFinite = 1u, kShadowVertexSkipped = 2u;
 constexpr float kShadowRangeMax = 1.0e6f;       // half_extent, depth_range and the biases
 
 // what the four counters of a map hold since its last begin: skipped instances, then every triangle of the other instances as one of three
-enum : int { kShadowSkippedInstances = 0, kShadowCulled = 1, kShadowLane = 2, kShadowWave = 3 };
+enum : int { kShadowSkippedInstances = kSolidSkippedInstances, kShadowCulled = kSolidCulled, kShadowLane = kSolidLane, kShadowWave = kSolidWave };
 enum : int { kShadowTriNone = -1, kShadowTriSkipped = 0, kShadowTriCulled = 1, kShadowTriLane = 2, kShadowTriWave = 3 };
 
 // a frame as the host resolves it for a map of side `size`
@@ -135,7 +134,7 @@ inline ShadowParams shadow_params(const ShadowFrame &f, int size) {
     P.half = (float)((double)size / 2.0);
     P.w = (float)(2.0 * (double)f.half_extent / (double)size);
     P.both_sides = (f.flags & kShadowCastBothSides) ? 1 : 0;
-    P.lane_box = f.lane_box == 0 ? kMeshLaneBox : (f.lane_box < 0 ? 0 : f.lane_box);
+    P.lane_box = mesh_lane_box(f.lane_box);
     P.ok = 1;
     return P;
 }
@@ -174,12 +173,8 @@ OW_DEV ShadowVertex shadow_vertex(const float *t, bool instance_ok, const float 
         out.flags = kShadowVertexNotFinite | kShadowVertexSkipped;
         return out;
     }
-    bool ok = true;
     float w[3];
-    for (int k = 0; k < 3; ++k) {
-        w[k] = ((t[3 * k] * l[0] + t[3 * k + 1] * l[1]) + t[3 * k + 2] * l[2]) + t[9 + k];
-        ok = ok && mesh_finite(w[k]);
-    }
+    bool ok = solid_world(t, l, w);
     float s, tt, d;
     shadow_project(P, w, s, tt, d);
     ok = ok && mesh_finite(s) && mesh_finite(tt) && mesh_finite(d);

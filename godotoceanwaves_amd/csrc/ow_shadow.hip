@@ -2,12 +2,14 @@
 // kernels are held to that build bit for bit).  Built with -ffp-contract=off, like ow_solid.hip.
 //
 //   k_shadow_clear     the map's words to FLT_MAX's bits, the four counters to zero
-//   k_shadow_vertices  one lane per (instance, vertex): the instance's transform (a body set's resident pose record, or an uploaded one), the
-//                      world position, (s, t, d) in the light's frame, one 16-byte store; vertex 0's lane counts a skipped instance
+//   k_shadow_vertices  one lane per (instance, vertex), ow_raster.h's instance_vertices (the vertex stage k_solid_vertices runs): the
+//                      instance's transform (a body set's resident pose record, or an uploaded one), the world position, (s, t, d) in the
+//                      light's frame, one 16-byte store; vertex 0's lane counts a skipped instance
 //   k_shadow_raster    one wave per 64 (instance, triangle) pairs: set-up per lane (facing, the texel box, the class), then ow_raster.h's
-//                      split -- a small box is walked by its own lane, the large ones are taken one after the other by the whole wave in
-//                      8 x 8 tiles, their nine floats and four integers read from the owning lane (lane reads, no LDS).  A crate face on a
-//                      2048^2 map over 100 m is some 50 texels across: the wave class is the common case
+//                      raster_wave, the walk k_mesh_raster and k_solid_raster run, into the depth-map target below -- a small box is
+//                      walked by its own lane, the large ones are taken one after the other by the whole wave in 8 x 8 tiles, their nine
+//                      floats and four integers read from the owning lane (lane reads, no LDS).  A crate face on a 2048^2 map over 100 m
+//                      is some 50 texels across: the wave class is the common case
 //   k_shadow_apply<kRgba>  one lane per pixel, one wave per 8 x 8 tile (the records are always there; the RGBA8 words are the optional
 //                      output): the record's 16-byte vectors that are needed, the taps as plain global loads (neighbouring pixels land on
 //                      neighbouring texels only roughly: no tile is staged in LDS), and only the three vectors that hold status, diffuse,
@@ -30,23 +32,27 @@ __device__ __forceinline__ void depth_min(uint32_t *map, size_t at, uint32_t bit
     if (bits < map[at]) atomicMin(map + at, bits);
 }
 
+// The depth map as raster_wave's target: ShadowSetup's classes (its nine floats and its box are what the wave reads from the owning
+// lane), shadow_cover at a texel centre, and the depth's bits written with a min.
+struct DepthTarget {
+    typedef ShadowSetup Setup;
+    float max_depth;
+    int size;
+    uint32_t *map;
+    static constexpr int kLane = kShadowTriLane, kWave = kShadowTriWave;
+    __device__ __forceinline__ void centre(const ShadowSetup &S, int i, int j, int) const {
+        const ShadowCover c = shadow_cover(S.s, S.t, S.d, max_depth, i, j);
+        if (c.hit) depth_min(map, (size_t)j * size + i, c.bits);
+    }
+};
+
 __global__ void __launch_bounds__(256) k_shadow_clear(uint32_t *map, size_t texels, uint32_t *counters) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < texels) map[i] = kShadowEmpty;
-    if (i < 4) counters[i] = 0u;
+    clear_words(map, texels, kShadowEmpty, counters);
 }
 
 __global__ void __launch_bounds__(256) k_shadow_vertices(const float *local, int num_vertices, SolidInstances in, ShadowParams P, ShadowVertex *out,
                                                          uint32_t *counters) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;  // instances * vertices <= 2^24
-    if (i >= in.count * num_vertices) return;
-    const int instance = i / num_vertices, v = i - instance * num_vertices;
-    const float *t = in.transforms + (size_t)instance * in.stride;
-    const bool ok = solid_instance_ok(t, in.flags ? in.flags + instance : nullptr);
-    if (!ok && v == 0) atomicAdd(counters + kShadowSkippedInstances, 1u);
-    const float l[3] = {local[3 * (size_t)v], local[3 * (size_t)v + 1], local[3 * (size_t)v + 2]};
-    const ShadowVertex rec = shadow_vertex(t, ok, l, P);
-    *(u32x4 *)(out + i) = __builtin_bit_cast(u32x4, rec);
+    instance_vertices(local, num_vertices, in, out, counters + kShadowSkippedInstances, [&](const float *t, bool ok, const float l[3]) { return shadow_vertex(t, ok, l, P); });
 }
 
 __global__ void __launch_bounds__(64) k_shadow_raster(const int32_t *indices, int num_vertices, int num_triangles, int num_pairs, const ShadowVertex *verts,
@@ -57,40 +63,11 @@ __global__ void __launch_bounds__(64) k_shadow_raster(const int32_t *indices, in
     __builtin_memset(&S, 0, sizeof(S));
     S.kind = kShadowTriNone;
     if (pair < num_pairs) {
-        const int instance = pair / num_triangles, tri = pair - instance * num_triangles;
-        const ShadowVertex *base = verts + (size_t)instance * num_vertices;
-        S = shadow_setup(base[indices[3 * (size_t)tri]], base[indices[3 * (size_t)tri + 1]], base[indices[3 * (size_t)tri + 2]], P);
+        const SolidTriangle<ShadowVertex> t = solid_triangle(indices, num_vertices, num_triangles, verts, pair);
+        S = shadow_setup(*t.a, *t.b, *t.c, P);
     }
-    for (int k = kShadowTriCulled; k <= kShadowTriWave; ++k) {  // the class numbers are the counters'
-        const uint64_t m = __ballot(S.kind == k);
-        if (lane == 0 && m) atomicAdd(counters + k, (uint32_t)__popcll(m));
-    }
-    if (S.kind == kShadowTriLane) {
-        for (int j = S.y0; j <= S.y1; ++j)
-            for (int i = S.x0; i <= S.x1; ++i) {
-                const ShadowCover c = shadow_cover(S.s, S.t, S.d, P.max_depth, i, j);
-                if (c.hit) depth_min(map, (size_t)j * P.size + i, c.bits);
-            }
-    }
-    uint64_t big = __ballot(S.kind == kShadowTriWave);
-    while (big) {
-        const int src = __builtin_ctzll(big);
-        big &= big - 1;
-        float s[3], t[3], d[3];
-        for (int k = 0; k < 3; ++k) {
-            s[k] = lane_read(S.s[k], src);
-            t[k] = lane_read(S.t[k], src);
-            d[k] = lane_read(S.d[k], src);
-        }
-        const int x0 = lane_read(S.x0, src), x1 = lane_read(S.x1, src), y0 = lane_read(S.y0, src), y1 = lane_read(S.y1, src);
-        for (int ty = y0 >> 3; ty <= y1 >> 3; ++ty)
-            for (int tx = x0 >> 3; tx <= x1 >> 3; ++tx) {
-                const int i = 8 * tx + (lane & 7), j = 8 * ty + (lane >> 3);
-                if (i < x0 || i > x1 || j < y0 || j > y1) continue;  // the box lies inside the map: so does (i, j)
-                const ShadowCover c = shadow_cover(s, t, d, P.max_depth, i, j);
-                if (c.hit) depth_min(map, (size_t)j * P.size + i, c.bits);
-            }
-    }
+    count_classes(counters, lane, S.kind, kShadowTriCulled, kShadowTriWave);  // the class numbers are the counters'
+    raster_wave(DepthTarget{P.max_depth, P.size, map}, S, lane, pair, (int)blockIdx.x * 64);
 }
 
 // A lane reads 96 of its record's 128 bytes (six vectors) and rewrites 48 of them where the record is a receiver.
@@ -102,9 +79,7 @@ __global__ void __launch_bounds__(64) k_shadow_apply(int width, int height, Shad
     const int i = 8 * tx + (lane & 7), j = 8 * ty + (lane >> 3);
     if (i >= width || j >= height) return;
     const size_t at = (size_t)j * width + i;
-    struct Words {
-        u32x4 v[sizeof(RenderPixel) / 16];
-    };
+    typedef RecordWords<RenderPixel> Words;
     Words w;
     u32x4 *rec = (u32x4 *)(pixels + at);
     const u32x4 zero = {0u, 0u, 0u, 0u};
@@ -142,12 +117,12 @@ hipError_t launch_shadow_clear(const ShadowArrays &A, int size, hipStream_t s) {
 }
 
 hipError_t launch_shadow_cast(const ShadowArrays &A, const SolidInstances &in, const ShadowParams &P, hipStream_t s) {
-    const int64_t nverts = (int64_t)in.count * A.num_vertices, npairs = (int64_t)in.count * A.num_triangles;
+    const int64_t nverts = (int64_t)in.count * A.shape.num_vertices, npairs = (int64_t)in.count * A.shape.num_triangles;
     if (nverts > kSolidMaxProduct || npairs > kSolidMaxProduct) return hipErrorInvalidValue;  // the host wrappers refuse these first
     if (!P.ok || in.count <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_shadow_vertices, dim3((unsigned)((nverts + 255) / 256)), dim3(256), 0, s, A.local, A.num_vertices, in, P, A.verts, A.counters);
+    hipLaunchKernelGGL(k_shadow_vertices, dim3((unsigned)((nverts + 255) / 256)), dim3(256), 0, s, A.shape.local, A.shape.num_vertices, in, P, A.verts, A.counters);
     if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_shadow_raster, dim3((unsigned)((npairs + 63) / 64)), dim3(64), 0, s, A.indices, A.num_vertices, A.num_triangles, (int)npairs, A.verts,
+    hipLaunchKernelGGL(k_shadow_raster, dim3((unsigned)((npairs + 63) / 64)), dim3(64), 0, s, A.shape.indices, A.shape.num_vertices, A.shape.num_triangles, (int)npairs, A.verts,
                        P, A.map, A.counters);
     return hipGetLastError();
 }

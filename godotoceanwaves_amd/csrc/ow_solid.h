@@ -10,7 +10,7 @@
 // and the visibility word are ow_mesh.h's tri_setup, tri_planes, tri_cover and mesh_word, called as they are.
 //
 //   vertex    instance transform T (twelve floats, BuoyancyBody::transform's layout: basis rows [0..8], origin [9..11]), local vertex l:
-//             w_k = ((T[3k] l_0 + T[3k+1] l_1) + T[3k+2] l_2) + T[9+k]   (lever_arm's row product, then the origin)
+//             w_k = ((T[3k] l_0 + T[3k+1] l_1) + T[3k+2] l_2) + T[9+k]   (solid_world: lever_arm's row product, then the origin)
 //             V   = B^T (w - camera.position), mesh_vertex's operations in their order
 //             A vertex whose w or V is not finite carries kMeshVertexNotFinite: its triangles are culled.  Every vertex of an instance
 //             that is skipped (a transform value that is not finite, a body whose fault flag is raised) carries kSolidVertexSkipped as
@@ -58,8 +58,9 @@ constexpr uint32_t kSolidVertexSkipped = 2u;       // MeshVertex::flags: the ver
 constexpr float kSolidColorMax = 1.0e12f;          // the largest magnitude of a colour the options take: color stays finite
 constexpr int kSolidTransformFloats = 12;
 
-// what the four counters of a draw hold: skipped instances, then every triangle of the other instances as exactly one of three
-enum : int { kSolidSkippedInstances = 0, kSolidCulled = 1, kSolidLane = 2, kSolidWave = 3 };
+// what the four counters of a draw hold: skipped instances, then every triangle of the other instances as exactly one of three (in the
+// order of ow_mesh.h's classes, which the host reads all such counters by)
+enum : int { kSolidSkippedInstances = kTriSkipped, kSolidCulled = kTriCulled, kSolidLane = kTriLane, kSolidWave = kTriWave };
 
 // a draw's constants, resolved once from the options
 struct SolidParams {
@@ -79,10 +80,52 @@ struct SolidInstances {
     int count;
 };
 
+// ---- the instance front end: what the draw and the shadow cast (ow_shadow.h), on the device and in the CPU builds of both, do ahead of
+// their own arithmetic -- which (instance, vertex) or (instance, triangle) a flat index is, where that instance's transform lies, whether
+// the instance is drawn at all, and where it puts a local vertex in the world ----
+
+// flat index -> (instance, item) with `per_instance` vertices or triangles each: flat = instance * per_instance + item
+struct SolidSplit {
+    int instance, item;
+};
+OW_DEV SolidSplit solid_split(int flat, int per_instance) {
+    const int instance = flat / per_instance;
+    return SolidSplit{instance, flat - instance * per_instance};
+}
+
+OW_DEV const float *solid_transform(const SolidInstances &in, int instance) { return in.transforms + (size_t)instance * in.stride; }
+
+// drawn: every float of the transform is finite and, for a body, its fault flag is down
 OW_DEV bool solid_instance_ok(const float *t, const int32_t *flag) {
     bool ok = !flag || *flag == 0;
     for (int k = 0; k < kSolidTransformFloats; ++k) ok = ok && mesh_finite(t[k]);
     return ok;
+}
+OW_DEV bool solid_instance_ok(const SolidInstances &in, int instance) {
+    return solid_instance_ok(solid_transform(in, instance), in.flags ? in.flags + instance : nullptr);
+}
+
+// the world position of local vertex l under transform t, and whether it is finite: lever_arm's row product, then the origin.  The draw
+// and the cast both take it from here, so a caster's vertex is where the drawn one is to the bit.
+OW_DEV bool solid_world(const float *t, const float l[3], float w[3]) {
+    bool ok = true;
+    for (int k = 0; k < 3; ++k) {
+        w[k] = ((t[3 * k] * l[0] + t[3 * k + 1] * l[1]) + t[3 * k + 2] * l[2]) + t[9 + k];
+        ok = ok && mesh_finite(w[k]);
+    }
+    return ok;
+}
+
+// the three vertex records of pair `pair` (MeshVertex for the draw, ShadowVertex for the cast)
+template <typename Vertex>
+struct SolidTriangle {
+    const Vertex *a, *b, *c;
+};
+template <typename Vertex>
+OW_DEV SolidTriangle<Vertex> solid_triangle(const int32_t *indices, int num_vertices, int num_triangles, const Vertex *verts, int pair) {
+    const SolidSplit at = solid_split(pair, num_triangles);
+    const Vertex *base = verts + (size_t)at.instance * num_vertices;
+    return SolidTriangle<Vertex>{base + indices[3 * (size_t)at.item], base + indices[3 * (size_t)at.item + 1], base + indices[3 * (size_t)at.item + 2]};
 }
 
 // one (instance, vertex): the record tri_setup reads
@@ -95,13 +138,9 @@ OW_DEV MeshVertex solid_vertex(const float *t, bool instance_ok, const float l[3
         out.flags = kMeshVertexNotFinite | kSolidVertexSkipped;
         return out;
     }
-    bool ok = true;
+    bool ok = solid_world(t, l, out.position);
     float rel[3];
-    for (int k = 0; k < 3; ++k) {
-        out.position[k] = ((t[3 * k] * l[0] + t[3 * k + 1] * l[1]) + t[3 * k + 2] * l[2]) + t[9 + k];
-        ok = ok && mesh_finite(out.position[k]);
-        rel[k] = out.position[k] - cam.o[k];
-    }
+    for (int k = 0; k < 3; ++k) rel[k] = out.position[k] - cam.o[k];
     if (mp.camera_ok)
         for (int k = 0; k < 3; ++k) {
             out.view[k] = (cam.B[k] * rel[0] + cam.B[3 + k] * rel[1]) + cam.B[6 + k] * rel[2];  // column k of B
@@ -111,20 +150,6 @@ OW_DEV MeshVertex solid_vertex(const float *t, bool instance_ok, const float l[3
     if (!ok)  // the record itself stays finite: the flag says what happened
         for (int k = 0; k < 3; ++k) out.position[k] = out.view[k] = 0.0f;
     return out;
-}
-
-// the three vertex records of pair `pair`
-struct SolidTriangle {
-    const MeshVertex *a, *b, *c;
-};
-OW_DEV SolidTriangle solid_triangle(const int32_t *indices, int num_vertices, int num_triangles, const MeshVertex *verts, int pair) {
-    const int instance = pair / num_triangles, tri = pair - instance * num_triangles;
-    const MeshVertex *base = verts + (size_t)instance * num_vertices;
-    SolidTriangle t;
-    t.a = base + indices[3 * (size_t)tri];
-    t.b = base + indices[3 * (size_t)tri + 1];
-    t.c = base + indices[3 * (size_t)tri + 2];
-    return t;
 }
 
 OW_DEV bool solid_planes_finite(const TriPlanes &p) {
@@ -138,7 +163,7 @@ OW_DEV bool solid_planes_finite(const TriPlanes &p) {
 
 // tri_setup for one pair, and the counter it falls under: kSolidCulled, kSolidLane, kSolidWave, or -1 for a triangle of a skipped instance.
 // s.kind is kTriLane or kTriWave exactly where the counter is kSolidLane or kSolidWave.
-OW_DEV TriSetup solid_setup(const SolidTriangle &t, const CameraParams &cam, const MeshParams &mp, int &counter) {
+OW_DEV TriSetup solid_setup(const SolidTriangle<MeshVertex> &t, const CameraParams &cam, const MeshParams &mp, int &counter) {
     TriSetup s = tri_setup(*t.a, *t.b, *t.c, cam, mp);
     if ((s.kind == kTriLane || s.kind == kTriWave) && !solid_planes_finite(s.p)) s.kind = kTriCulled;
     counter = s.kind == kTriLane ? kSolidLane : (s.kind == kTriWave ? kSolidWave : kSolidCulled);
@@ -154,7 +179,7 @@ OW_DEV RenderPixel solid_pixel(const SolidParams &sp, const CameraParams &cam, u
     drawn = false;
     if (!sp.mp.camera_ok || word == kMeshNoTriangle) return px;
     const int pair = (int)(uint32_t)word;
-    const SolidTriangle tr = solid_triangle(indices, num_vertices, num_triangles, verts, pair);
+    const SolidTriangle<MeshVertex> tr = solid_triangle(indices, num_vertices, num_triangles, verts, pair);
     const MeshVertex a = *tr.a, b = *tr.b, c = *tr.c;
     const TriPlanes p = tri_planes(a.view, b.view, c.view);
     const TriCover cv = tri_cover(p, cam, sp.mp.near, i, j);
@@ -195,9 +220,9 @@ OW_DEV RenderPixel solid_pixel(const SolidParams &sp, const CameraParams &cam, u
         px.diffuse[k] = sp.light_color[k] * ndl;
         px.color[k] = sp.albedo[k] * (px.diffuse[k] + sp.ambient_color[k]);
     }
-    const int instance = pair / num_triangles;
-    px.reserved[0] = (uint32_t)(pair - instance * num_triangles) + 1u;
-    px.reserved[3] = (uint32_t)instance + 1u;
+    const SolidSplit at = solid_split(pair, num_triangles);
+    px.reserved[0] = (uint32_t)at.item + 1u;
+    px.reserved[3] = (uint32_t)at.instance + 1u;
     drawn = true;
     return px;
 }

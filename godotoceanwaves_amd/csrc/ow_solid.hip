@@ -2,10 +2,11 @@
 // kernels are held to that build bit for bit).  Built with -ffp-contract=off, like ow_mesh.hip.
 //
 //   k_solid_clear     the visibility buffer to all ones, the four counters to zero
-//   k_solid_vertices  one lane per (instance, vertex): the instance's transform (a body set's resident pose record, or an uploaded one),
-//                     the world and view positions, a MeshVertex-compatible record; vertex 0's lane counts a skipped instance
-//   k_solid_raster    one wave per 64 (instance, triangle) pairs: set-up per lane (ow_mesh.h tri_setup), then ow_raster.h's raster_wave,
-//                     the code k_mesh_raster runs -- small boxes per lane, large boxes by the whole wave from lane reads
+//   k_solid_vertices  one lane per (instance, vertex), ow_raster.h's instance_vertices (the vertex stage k_shadow_vertices runs): the
+//                     instance's transform (a body set's resident pose record, or an uploaded one), the world and view positions, a
+//                     MeshVertex-compatible record; vertex 0's lane counts a skipped instance
+//   k_solid_raster    one wave per 64 (instance, triangle) pairs: set-up per lane (ow_mesh.h tri_setup), then ow_raster.h's raster_wave into
+//                     the visibility-buffer target, as k_mesh_raster -- small boxes per lane, large boxes by the whole wave from lane reads
 //   k_solid_resolve   one lane per pixel, one wave per 8 x 8 tile: the pixel's word -> barycentrics -> the depth test against the record ->
 //                     the shading -> the record (eight 16-byte stores, only where a solid is drawn) and the RGBA8 word (every pixel)
 //
@@ -24,27 +25,12 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
 __global__ void __launch_bounds__(256) k_solid_clear(uint64_t *vis, size_t pixels, uint32_t *counters) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < pixels) vis[i] = kMeshNoTriangle;
-    if (i < 4) counters[i] = 0u;
+    clear_words(vis, pixels, kMeshNoTriangle, counters);
 }
 
 __global__ void __launch_bounds__(256) k_solid_vertices(const float *local, int num_vertices, SolidInstances in, CameraParams cam, MeshParams mp,
                                                         MeshVertex *out, uint32_t *counters) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;  // instances * vertices <= 2^24
-    if (i >= in.count * num_vertices) return;
-    const int instance = i / num_vertices, v = i - instance * num_vertices;
-    const float *t = in.transforms + (size_t)instance * in.stride;
-    const bool ok = solid_instance_ok(t, in.flags ? in.flags + instance : nullptr);
-    if (!ok && v == 0) atomicAdd(counters + kSolidSkippedInstances, 1u);
-    const float l[3] = {local[3 * (size_t)v], local[3 * (size_t)v + 1], local[3 * (size_t)v + 2]};
-    const MeshVertex rec = solid_vertex(t, ok, l, cam, mp);
-    struct Words {
-        u32x4 v[sizeof(MeshVertex) / 16];
-    };
-    const Words w = __builtin_bit_cast(Words, rec);
-    u32x4 *dst = (u32x4 *)(out + i);
-    for (int k = 0; k < (int)(sizeof(MeshVertex) / 16); ++k) dst[k] = w.v[k];
+    instance_vertices(local, num_vertices, in, out, counters + kSolidSkippedInstances, [&](const float *t, bool ok, const float l[3]) { return solid_vertex(t, ok, l, cam, mp); });
 }
 
 __global__ void __launch_bounds__(64) k_solid_raster(const int32_t *indices, int num_vertices, int num_triangles, int num_pairs, const MeshVertex *verts,
@@ -60,7 +46,7 @@ __global__ void __launch_bounds__(64) k_solid_raster(const int32_t *indices, int
         const uint64_t m = __ballot(counter == k);
         if (lane == 0 && m) atomicAdd(counters + k, (uint32_t)__popcll(m));
     }
-    raster_wave(s, lane, pair, (int)blockIdx.x * 64, cam, mp, vis);
+    raster_wave(VisTarget{cam, mp, vis}, s, lane, pair, (int)blockIdx.x * 64);
 }
 
 // One lane per pixel, one 8 x 8 tile per wave, as k_mesh_shade.  A lane reads 24 of its record's 128 bytes (t, status; specular, color) and
@@ -89,14 +75,7 @@ __global__ void __launch_bounds__(64) k_solid_resolve(CameraParams cam, SolidPar
     const RenderPixel px = solid_pixel(sp, cam, vis[at], indices, num_vertices, num_triangles, verts, i, j, t, status, drawn);
     if (drawn) {
         for (int k = 0; k < 3; ++k) color[k] = px.color[k];
-        if (kRecords) {
-            struct Words {
-                u32x4 v[sizeof(RenderPixel) / 16];
-            };
-            const Words w = __builtin_bit_cast(Words, px);
-            u32x4 *dst = (u32x4 *)(pixels + at);
-            for (int k = 0; k < (int)(sizeof(RenderPixel) / 16); ++k) dst[k] = w.v[k];
-        }
+        if (kRecords) store_record(pixels + at, px);
     }
     if (rgba) rgba[at] = pack_rgba8(color);
 }
@@ -110,22 +89,22 @@ hipError_t launch_solid_draw(const SolidArrays &A, const SolidInstances &in, con
     const size_t pixels = (size_t)cam.width * cam.height;
     hipLaunchKernelGGL(k_solid_clear, dim3((unsigned)((pixels + 255) / 256)), dim3(256), 0, s, A.vis, pixels, A.counters);
     if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-    const int64_t nverts = (int64_t)in.count * A.num_vertices, npairs = (int64_t)in.count * A.num_triangles;
+    const int64_t nverts = (int64_t)in.count * A.shape.num_vertices, npairs = (int64_t)in.count * A.shape.num_triangles;
     if (nverts > kSolidMaxProduct || npairs > kSolidMaxProduct) return hipErrorInvalidValue;  // the host wrappers refuse these first
     if (sp.mp.camera_ok && in.count > 0) {  // a camera that is not finite draws nothing: the counters stay 0
-        hipLaunchKernelGGL(k_solid_vertices, dim3((unsigned)((nverts + 255) / 256)), dim3(256), 0, s, A.local, A.num_vertices, in, cam, sp.mp, A.verts,
+        hipLaunchKernelGGL(k_solid_vertices, dim3((unsigned)((nverts + 255) / 256)), dim3(256), 0, s, A.shape.local, A.shape.num_vertices, in, cam, sp.mp, A.verts,
                            A.counters);
         if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-        hipLaunchKernelGGL(k_solid_raster, dim3((unsigned)((npairs + 63) / 64)), dim3(64), 0, s, A.indices, A.num_vertices, A.num_triangles, (int)npairs,
+        hipLaunchKernelGGL(k_solid_raster, dim3((unsigned)((npairs + 63) / 64)), dim3(64), 0, s, A.shape.indices, A.shape.num_vertices, A.shape.num_triangles, (int)npairs,
                            A.verts, cam, sp.mp, A.vis, A.counters);
         if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
     }
     const int tiles_x = (cam.width + 7) / 8, tiles_y = (cam.height + 7) / 8;
     if (pixels_dev)
-        hipLaunchKernelGGL(k_solid_resolve<true>, dim3(tiles_x * tiles_y), dim3(64), 0, s, cam, sp, A.vis, A.indices, A.num_vertices, A.num_triangles,
+        hipLaunchKernelGGL(k_solid_resolve<true>, dim3(tiles_x * tiles_y), dim3(64), 0, s, cam, sp, A.vis, A.shape.indices, A.shape.num_vertices, A.shape.num_triangles,
                            A.verts, tiles_x, pixels_dev, rgba_dev);
     else
-        hipLaunchKernelGGL(k_solid_resolve<false>, dim3(tiles_x * tiles_y), dim3(64), 0, s, cam, sp, A.vis, A.indices, A.num_vertices, A.num_triangles,
+        hipLaunchKernelGGL(k_solid_resolve<false>, dim3(tiles_x * tiles_y), dim3(64), 0, s, cam, sp, A.vis, A.shape.indices, A.shape.num_vertices, A.shape.num_triangles,
                            A.verts, tiles_x, pixels_dev, rgba_dev);
     return hipGetLastError();
 }

@@ -25,7 +25,20 @@ for line in r.stderr.splitlines():
     elif cur and ":" in txt:
         k, v = txt.split(":", 1)
         rows[cur][k.strip()] = v.strip()
+def kernel_name(mangled):
+    """`ow::k_mesh_shade<true>` from the mangled name: the name and its template arguments, without the anonymous namespace, the return
+    type a template instance carries and the parameter list."""
+    dem = subprocess.run(["c++filt", mangled], capture_output=True, text=True).stdout.strip().replace("(anonymous namespace)::", "")
+    depth = 0
+    for at, ch in enumerate(dem):
+        depth += (ch == "<") - (ch == ">")
+        if ch == "(" and depth == 0:
+            dem = dem[:at]
+            break
+    return dem.split(" ")[-1] if "<" not in dem else dem[dem.rfind(" ", 0, dem.index("<")) + 1:]
+
+
 for name, d in rows.items():
-    dem = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip().split("(")[0]
+    dem = kernel_name(name)
     print(f"{dem:46s} VGPR {d.get('VGPRs'):>4s} AGPR {d.get('AGPRs'):>3s} scratch {d.get('ScratchSize [bytes/lane]'):>4s} "
           f"occ {d.get('Occupancy [waves/SIMD]')} LDS {d.get('LDS Size [bytes/block]')}")

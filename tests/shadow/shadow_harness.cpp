@@ -67,29 +67,25 @@ void harness_shadow_cast(const ShadowFrame *f, int size, const float *local, int
     const ShadowParams P = shadow_params(*f, size);
     if (!P.ok || count <= 0) return;
     std::vector<ShadowVertex> verts((size_t)count * num_vertices);
+    const SolidInstances in = {transforms, flags, stride, count};
     for (int i = 0; i < count; ++i) {
-        const float *t = transforms + (size_t)i * stride;
-        const bool ok = solid_instance_ok(t, flags ? flags + i : nullptr);
+        const bool ok = solid_instance_ok(in, i);
         if (!ok) ++counters[kShadowSkippedInstances];
-        for (int v = 0; v < num_vertices; ++v) {
-            const float l[3] = {local[3 * (size_t)v], local[3 * (size_t)v + 1], local[3 * (size_t)v + 2]};
-            verts[(size_t)i * num_vertices + v] = shadow_vertex(t, ok, l, P);
-        }
+        for (int v = 0; v < num_vertices; ++v) verts[(size_t)i * num_vertices + v] = shadow_vertex(solid_transform(in, i), ok, local + 3 * (size_t)v, P);
     }
     if (verts_out) memcpy(verts_out, verts.data(), verts.size() * sizeof(ShadowVertex));
-    for (int i = 0; i < count; ++i)
-        for (int tri = 0; tri < num_triangles; ++tri) {
-            const ShadowVertex *base = verts.data() + (size_t)i * num_vertices;
-            const ShadowSetup S = shadow_setup(base[indices[3 * (size_t)tri]], base[indices[3 * (size_t)tri + 1]], base[indices[3 * (size_t)tri + 2]], P);
-            if (S.kind >= kShadowTriCulled) ++counters[S.kind];
-            if (S.kind != kShadowTriLane && S.kind != kShadowTriWave) continue;
-            for (int j = S.y0; j <= S.y1; ++j)
-                for (int x = S.x0; x <= S.x1; ++x) {
-                    const ShadowCover c = shadow_cover(S.s, S.t, S.d, P.max_depth, x, j);
-                    uint32_t &word = map[(size_t)j * size + x];
-                    if (c.hit && c.bits < word) word = c.bits;
-                }
-        }
+    for (int pair = 0; pair < count * num_triangles; ++pair) {
+        const SolidTriangle<ShadowVertex> t = solid_triangle(indices, num_vertices, num_triangles, verts.data(), pair);
+        const ShadowSetup S = shadow_setup(*t.a, *t.b, *t.c, P);
+        if (S.kind >= kShadowTriCulled) ++counters[S.kind];
+        if (S.kind != kShadowTriLane && S.kind != kShadowTriWave) continue;
+        for (int j = S.y0; j <= S.y1; ++j)
+            for (int x = S.x0; x <= S.x1; ++x) {
+                const ShadowCover c = shadow_cover(S.s, S.t, S.d, P.max_depth, x, j);
+                uint32_t &word = map[(size_t)j * size + x];
+                if (c.hit && c.bits < word) word = c.bits;
+            }
+    }
 }
 
 // the pass over width x height records, in place; V_out (may be null): the visibility of every record (1 for what is no receiver);

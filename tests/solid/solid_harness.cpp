@@ -103,11 +103,11 @@ void harness_solid_draw(const SolidCase *hp, const float *local, const int32_t *
     std::vector<MeshVertex> verts((size_t)h.count * nv);
     if (sp.mp.camera_ok && h.count > 0) {
         // k_solid_vertices
+        const SolidInstances in = {transforms, h.has_flags ? flags : nullptr, h.stride, h.count};
         for (int inst = 0; inst < h.count; ++inst) {
-            const float *t = transforms + (size_t)inst * h.stride;
-            const bool ok = solid_instance_ok(t, h.has_flags ? flags + inst : nullptr);
+            const bool ok = solid_instance_ok(in, inst);
             if (!ok) ++cnt[kSolidSkippedInstances];
-            for (int v = 0; v < nv; ++v) verts[(size_t)inst * nv + v] = solid_vertex(t, ok, local + 3 * (size_t)v, cam, sp.mp);
+            for (int v = 0; v < nv; ++v) verts[(size_t)inst * nv + v] = solid_vertex(solid_transform(in, inst), ok, local + 3 * (size_t)v, cam, sp.mp);
         }
         // k_solid_raster: a lane's walk and the wave's sweep visit the same centres of the same box
         const int pairs = h.count * nt;
