@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The frame kernels bin by bin on injected spectra (tests/frame_bins.py): for every size, input, tile and channel the figures of the FP32 oracle,
 of the CPU emulation of the device's lane code (every entry point of tests/emul/emul.cpp that takes the size) and -- unless --no-device -- of the
-device, per case of tests/test_frame_bins_gpu.py (the same runs: run_case), all against the FP64 twin; then the teeth table of
+device, per case of tests/test_frame_bins_gpu.py (the same runs: tests/frame_bins.py run_gpu_case), all against the FP64 twin; then the teeth table of
 tests/test_frame_bins.py.  Columns: the spatial figure of the seven non-foam channels (max|a - twin| over the maximum of the channel's group),
 then, on the white input, the per-bin ratio of the linear channels.
     python scripts/frame_bin_margins.py [--no-device] [n ...]     > profiles/frame_bin_margins.txt
@@ -59,13 +59,12 @@ def main(argv):
                     print(row(f"{n:5d} {tile[0]:g}x{tile[1]:g} {name:15s} {who:18s}", sp, pb), flush=True)
         print(f"# {n}^2: oracle and emulation {time.time() - t0:.1f} s", flush=True)
     if device:
-        import test_frame_bins_gpu as G
         print("# device: size x cascades path kernels family | cascade tile input | spatial | per bin (white) | wall time of the case")
-        for name, n, cascades, path, kernels, family, ticks in G._cases():
+        for name, n, cascades, path, kernels, family, ticks in FB.gpu_cases():
             if n not in sizes:
                 continue
             t0 = time.time()
-            got_family, hits, layers = G.run_case(name, n, cascades, path, kernels, ticks)
+            got_family, hits, layers = FB.run_gpu_case(name, n, cascades, path, kernels, ticks)
             kind = FB.inputs(n)[name][0]
             for i, d in enumerate(layers):
                 sp, pb = figures(d["f32"], d["twin"], n, kind)

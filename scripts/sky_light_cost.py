@@ -40,8 +40,7 @@ def child():
     from godotoceanwaves_amd import _lib
     from godotoceanwaves_amd.presets import UPDATE_DELTA
     from godotoceanwaves_amd.wave_generator import WaveGenerator as W
-    from test_mesh_draw import REF_BASIS, grid
-    from test_surface_query import make_gen, scales_of
+    from scenes import grid, make_gen, REF_BASIS, scales_of
     stream = torch.cuda.Stream()
     gen, params = make_gen(256, [0, 1, 2], stream=stream.cuda_stream)
     sc = scales_of(params)

@@ -18,7 +18,7 @@ def crates(count, spacing):
     """`count` crates on a square grid `spacing` metres apart that starts 4 m in front of the camera's foot point, dropped from 0.3 m"""
     import numpy as np
     from godotoceanwaves_amd.wave_generator import WaveGenerator as W
-    from test_bodies_step import crate, make_bodies
+    from scenes import crate, make_bodies
     side = int(round(count ** 0.5))
     items = [crate(origin=((k % side - 0.5 * (side - 1)) * spacing, 0.3, -21.0 + (k // side) * spacing), divisions=(2, 2, 2), kl=3.0, kq=0.5) for k in range(count)]
     st, hull = make_bodies(items)
@@ -34,9 +34,7 @@ def child(step):
     from godotoceanwaves_amd import _lib
     from godotoceanwaves_amd.presets import UPDATE_DELTA
     from godotoceanwaves_amd.wave_generator import WaveGenerator as W
-    from test_mesh_draw import REF_BASIS, grid
-    from test_solid_draw import box
-    from test_surface_query import make_gen, scales_of
+    from scenes import box, grid, make_gen, REF_BASIS, scales_of
     count = {"mesh": 256, "solid256": 256, "solid4096": 4096}[step]
     stream = torch.cuda.Stream()
     gen, params = make_gen(1024, [0, 1, 2], stream=stream.cuda_stream)

@@ -8,7 +8,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import torch
 from godotoceanwaves_amd.presets import UPDATE_DELTA
-from test_surface_query import make_gen, scales_of
+from scenes import make_gen, scales_of
 out = open(sys.argv[1] if len(sys.argv) > 1 else os.devnull, "w")
 def say(*a):
     line = " ".join(str(x) for x in a); print(line, flush=True); out.write(line + "\n"); out.flush()

@@ -9,6 +9,7 @@ import helpers as H
 from edge_presets import edge_presets
 from godotoceanwaves_amd.presets import UPDATE_DELTA
 from oracle import oracle as O
+from scenes import look, make_scene
 
 # (1/tile_length.x, 1/tile_length.y, displacement_scale, normal_scale) per cascade.  ow_raycast.h takes |scales.z|, so a negative
 # displacement scale is legal input.  The last cascade has pixels-per-metre * 0.1 >= 1 at every map size (water.gdshader:78's mix takes the
@@ -98,3 +99,33 @@ def far_points():
     inf, nan = np.inf, np.nan
     bad = [(inf, 0.0), (0.0, -inf), (-inf, inf), (nan, 1.0), (1.0, nan), (nan, nan), (inf, nan)]
     return np.array(pts, np.float32), np.array(bad, np.float32)
+
+
+def float_fields_finite(rec, dtype=None):
+    """every float of a structured array, nested records included, is finite"""
+    dtype = dtype or rec.dtype
+    for name in dtype.names:
+        sub = dtype.fields[name][0]
+        if sub.names:
+            float_fields_finite(rec[name], sub)
+        elif sub.base.kind == "f":
+            assert np.isfinite(rec[name]).all(), name
+
+
+def seam_camera(sc, n, **kw):
+    """a camera 12 m above a point whose tap sits on the last column and the last row of cascade 0's tile, looking down and ahead"""
+    x, z = seam_points(sc, n)[2]
+    return look((float(x), 12.0, float(z)), 30.0, -35.0, **kw)
+
+
+OPTION_SETS = [dict(), dict(falloff_center=(12.5, -40.0)), dict(max_iterations=3, tolerance=1e-4)]
+
+
+def far_bodies(points):
+    """one 2 x 2 x 2 box of eight hull points at each far point, and one body at the origin whose hull points are the far points"""
+    boxes = [dict(origin=(float(x), 0.0, float(z)), size=(2, 2, 2), divisions=(2, 2, 2), v=(1.0, 0.0, -1.0), kl=0.3, kq=0.1) for x, z in points]
+    bodies, hull = make_scene(boxes + [dict(origin=(0, 0, 0), size=(2, 2, 2), divisions=(2, 2, len(points) // 4 + 1))])
+    last = bodies[-1]
+    sl = slice(last["point_offset"], last["point_offset"] + len(points))
+    hull["local"][sl, 0], hull["local"][sl, 2] = points[:, 0], points[:, 1]
+    return bodies, hull

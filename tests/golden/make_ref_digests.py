@@ -12,8 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.join(HERE, "..", "..")
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 import helpers as H  # noqa: E402
-import test_oracle_ref as T  # noqa: E402
-import test_surface_sampling as S  # noqa: E402
+import scenes as S  # noqa: E402
 from godotoceanwaves_amd.presets import UPDATE_DELTA, cascade_preset  # noqa: E402
 from oracle import ref as R  # noqa: E402
 
@@ -22,19 +21,19 @@ def main():
     if not R.available():
         raise SystemExit("oracle/_ref/libglsl_ref.so missing: run `make -C oracle ref` where the reference checkout exists")
     out = {"cascade": {}, "edge": {}, "sampling": {}}
-    for n, ci, frames in T.CASCADE_CASES:
+    for n, ci, frames in H.CASCADE_CASES:
         rc = R.RefCascade(n, cascade_preset(ci))
         e = {"butterfly": H.digest(rc.butterfly), "frames": []}
         for _ in range(frames):
             rc.update(UPDATE_DELTA)
-            e["frames"].append({"time": rc.time, **T.stage_digests(rc)})
+            e["frames"].append({"time": rc.time, **H.stage_digests(rc)})
         out["cascade"][f"n{n}_c{ci}"] = e
         print(f"cascade n{n}_c{ci}", flush=True)
-    for name, preset in T._edge_cases():
+    for name, preset in H.edge_cases():
         rc = R.RefCascade(128, preset)
-        for _ in range(T.EDGE_FRAMES):
+        for _ in range(H.EDGE_FRAMES):
             rc.update(UPDATE_DELTA)
-        out["edge"][name] = T.stage_digests(rc)
+        out["edge"][name] = H.stage_digests(rc)
     for case in ("random_maps", "generated_maps", "spray_active", "fine_cascades"):
         d, m, sc, xz = S.sampling_case(case)
         out["sampling"][case] = S.ref_sampling_digests(*R.sample_surface(d, m, sc, xz))

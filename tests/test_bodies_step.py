@@ -19,139 +19,29 @@ import pytest
 from godotoceanwaves_amd import _lib, build
 from godotoceanwaves_amd.presets import UPDATE_DELTA
 from godotoceanwaves_amd.wave_generator import WaveGenerator as W
-from test_buoyancy import calm, cpu_buoyancy, harness as buoyancy_harness, rotation  # noqa: F401
-from test_surface_query import generated_maps, gpu_maps, make_gen, maps_u16, scales_of
+import checks as S
+from checks import check_declared_and_bound, exported_symbols, HEADER
+from cpu_builds import build_example, cpu_buoyancy, CpuSet, CSRC, layout_probe, ROOT
+from cpu_builds import bodies_harness as harness, buoyancy_harness  # noqa: F401 (fixtures)
+from scenes import calm, crate, demo_bodies, device_read, generated_maps, gpu_arrays, gpu_maps, make_bodies, quaternion, RHO, scales_of
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "godotoceanwaves_amd", "csrc")
-HERE = os.path.dirname(os.path.abspath(__file__))
-PKG = os.path.join(ROOT, "godotoceanwaves_amd")
 NEW_FUNCTIONS = ("ow_sync_stats", "ow_bodies_create", "ow_bodies_destroy", "ow_bodies_step", "ow_bodies_get_state", "ow_bodies_set_state", "ow_bodies_get_results",
                  "ow_bodies_get_device_ptrs", "ow_bodies_stats")
 STRUCTS = {"OwRigidBody": "ow_rigid_body", "OwBodiesOptions": "ow_bodies_options"}
-RHO = 1025.0
 G32 = float(np.float32(9.81))      # the gravity the integrator uses: the FP32 default of ow_buoyancy_options, widened
 U = 2.0 ** -53                     # FP64 unit roundoff
 
 
-# ---- the CPU build of ow_rigid.h -----------------------------------------------------------------------------------------------------
-
-@pytest.fixture(scope="module")
-def harness(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("bodies") / "libbodies_harness.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unknown-pragmas", "-I", CSRC,
-                    os.path.join(HERE, "bodies", "bodies_harness.cpp"), "-o", so], check=True)
-    L = C.CDLL(so)
-    V = C.c_void_p
-    L.harness_bodies_sizes.argtypes = [V]
-    L.harness_bodies_pose.argtypes = [V, C.c_int, C.c_int, V, V, V]
-    L.harness_rigid_pose.argtypes = [V, V]
-    L.harness_rigid_finish.argtypes = [V, V, V, C.c_double, C.c_double]
-    L.harness_bodies_step.argtypes = [V, V, C.c_int, C.c_int, V, V, C.c_int, V, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.c_float, C.c_float,
-                                      C.c_float, C.c_float, C.c_int, C.c_double, C.c_double, C.c_int, V, V, V, V, V, V]
-    return L
-
-
-class CpuSet:
-    """what ow_bodies_create leaves on the device, in host memory"""
-
-    def __init__(self, L, state, hull):
-        self.L = L
-        self.state = np.ascontiguousarray(state, W.RIGID_BODY).copy()
-        self.hull = np.ascontiguousarray(hull, W.HULL_POINT)
-        self.records = np.zeros(len(self.state), W.BUOYANCY_BODY)
-        self.pts = np.zeros(len(self.hull), W.BUOYANCY_POINT)
-        self.results = np.zeros(len(self.state), W.BUOYANCY_RESULT)
-        self.flags = np.zeros(len(self.state), np.int32)
-        L.harness_bodies_pose(self.state.ctypes.data, len(self.state), len(self.hull), self.records.ctypes.data, self.pts.ctypes.data, self.flags.ctypes.data)
-
-    def step(self, disp, scales, substeps, dt, options=None, vel=None, trace=False):
-        """the options resolved as the runtime resolves them; returns (per-substep results, per-substep pose records) with trace"""
-        o = dict(options or {})
-        d = maps_u16(disp)
-        v = maps_u16(vel) if vel is not None else None
-        sc = np.ascontiguousarray(scales, np.float32)
-        rho = np.float32(o.get("density", 0.0) or RHO)
-        g = np.float32(o.get("gravity", 0.0) or 9.81)
-        center = o.get("falloff_center")
-        cx, cz = center if center is not None else (0.0, 0.0)
-        tr = np.zeros((substeps, len(self.state)), W.BUOYANCY_RESULT) if trace else None
-        tb = np.zeros((substeps, len(self.state)), W.BUOYANCY_BODY) if trace else None
-        self.L.harness_bodies_step(d.ctypes.data, v.ctypes.data if v is not None else None, d.shape[1], len(sc), sc.ctypes.data, self.state.ctypes.data,
-                                   len(self.state), self.hull.ctypes.data, len(self.hull), o.get("max_iterations", 0) or 16, o.get("tolerance", 0.0) or 1e-3,
-                                   int(center is not None), cx, cz, float(rho), float(np.float32(rho * g)), o.get("water_level", 0.0),
-                                   int(bool(o.get("warm_start"))), float(g), float(dt), int(substeps), self.records.ctypes.data, self.pts.ctypes.data,
-                                   self.results.ctypes.data, self.flags.ctypes.data, tr.ctypes.data if trace else None, tb.ctypes.data if trace else None)
-        return tr, tb
-
-    def arrays(self):
-        return {"state": self.state.tobytes(), "records": self.records.tobytes(), "results": self.results.tobytes(), "points": self.pts.tobytes()}
-
-
-def quaternion(axis, angle):
-    a = np.asarray(axis, np.float64) / np.linalg.norm(axis)
-    q = np.concatenate([a * np.sin(angle / 2), [np.cos(angle / 2)]])
-    return q / np.sqrt((q * q).sum())
-
-
-def blob_hull(count, size, body, seed):
-    """`count` hull points scattered in a box of `size`: the volume shared evenly, half heights of a cell of that volume"""
-    rng = np.random.default_rng(seed)
-    h = np.zeros(count, W.HULL_POINT)
-    h["local"] = rng.uniform(-0.5, 0.5, (count, 3)) * np.asarray(size)
-    h["volume"] = np.prod(size) / max(count, 1)
-    h["half_height"] = 0.5 * (np.prod(size) / max(count, 1)) ** (1 / 3)
-    h["body"] = body
-    return h
-
-
-def make_bodies(items):
-    """items: dicts of hull (HULL_POINT records of this body), size, and optional origin, q, v, w, density (of the body; 0: kinematic), kl, kq,
-    force, torque -> (RIGID_BODY records, hull)"""
-    st = np.zeros(len(items), W.RIGID_BODY)
-    hulls, off = [], 0
-    for i, it in enumerate(items):
-        h = it["hull"].copy()
-        h["body"] = i
-        st[i]["position"] = it.get("origin", (0, 0, 0))
-        st[i]["orientation"] = it.get("q", (0, 0, 0, 1))
-        st[i]["linear_velocity"] = it.get("v", (0, 0, 0))
-        st[i]["angular_velocity"] = it.get("w", (0, 0, 0))
-        dens = it.get("density", 0.5 * RHO)
-        if dens > 0:
-            m, iinv = W.box_mass_properties(it["size"], dens)
-            st[i]["mass"], st[i]["inverse_inertia"] = m, iinv
-        st[i]["applied_force"] = it.get("force", (0, 0, 0))
-        st[i]["applied_torque"] = it.get("torque", (0, 0, 0))
-        st[i]["linear_drag"], st[i]["quadratic_drag"] = it.get("kl", 0.0), it.get("kq", 0.0)
-        st[i]["point_offset"], st[i]["point_count"] = off, len(h)
-        hulls.append(h)
-        off += len(h)
-    return st, (np.concatenate(hulls) if hulls else np.zeros(0, W.HULL_POINT))
-
-
-def crate(size=(2, 1, 2), divisions=(4, 4, 4), **kw):
-    return dict(hull=W.box_hull(size, divisions), size=size, **kw)
-
-
 # ---- 1. the ABI ----------------------------------------------------------------------------------------------------------------------
-
-HEADER = open(os.path.join(ROOT, "include", "ocean_waves.h")).read()
-
 
 def test_header_declares_the_body_set_and_the_library_exports_it():
     build.build_library()
     lib = _lib.load()
-    text = re.sub(r"/\*.*?\*/", "", HEADER, flags=re.S)
-    for name in NEW_FUNCTIONS:
-        assert re.search(r"\b%s\s*\(" % name, text), name
-        assert name in _lib.SIGNATURES
-        assert getattr(lib, name)
+    text = check_declared_and_bound(lib, NEW_FUNCTIONS)
     for struct in STRUCTS.values():
         assert re.search(r"typedef struct %s \{" % struct, text), struct
     assert re.search(r"typedef struct ow_bodies ow_bodies;", text)
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert set(NEW_FUNCTIONS) <= set(re.findall(r" T (ow_[a-z0-9_]+)", out))
+    assert set(NEW_FUNCTIONS) <= exported_symbols()
     assert lib.ow_abi_version() == 4   # symbols were added, nothing changed
     assert "NO GYROSCOPIC TERM" in open(os.path.join(CSRC, "ow_rigid.h")).read()   # the header says what the integrator leaves out
     assert "There is no group form (ow_group_*)" in HEADER
@@ -166,10 +56,7 @@ def test_body_structs_agree_in_c_ctypes_numpy_and_the_harness(tmp_path, harness)
     for c, f in fields:
         src += '    printf("%%zu\\n", %s);\n' % (f"sizeof({c})" if f is None else f"offsetof({c}, {f})")
     src += '    printf("%u %u %d\\n", OW_FLAG_BODIES_FUSED, OW_FLAG_BODIES_SPLIT, OW_BODIES_MAX_SUBSTEPS);\n    return 0;\n}\n'
-    exe = str(tmp_path / "bodies_layout")
-    subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-x", "c", "-", "-o", exe],
-                   input=src, text=True, check=True)
-    got = [int(v) for v in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split()]
+    got = layout_probe(tmp_path, "bodies_layout", src, std=("-std=c99", "-pedantic", "-Wall", "-Werror"))
     want = []
     for c, f in fields:
         ct = getattr(_lib, c)
@@ -189,7 +76,6 @@ def test_body_structs_agree_in_c_ctypes_numpy_and_the_harness(tmp_path, harness)
 
 
 def test_the_csharp_binding_shows_the_body_structs_and_functions():
-    import test_integration_shim as S
     c_sizes = dict(S.C_SIZES, ow_buoyancy_options=64)
     cs_sizes = dict(S.CS_SIZES, OwBuoyancyOptions=64)
 
@@ -314,17 +200,9 @@ def test_argument_errors_without_a_device():
     assert m == 4000.0 and np.allclose(iinv, (12 / (m * 17), 12 / (m * 20), 12 / (m * 5)))
 
 
-def build_example(tmp_path):
-    exe = str(tmp_path / "floating_bodies_host")
-    subprocess.run(["gcc", "-O2", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-I", os.path.join(ROOT, "include"),
-                    os.path.join(ROOT, "examples", "floating_bodies_host.c"), "-o", exe, "-L", PKG, "-locean_waves", "-L", "/opt/rocm/lib", "-lamdhip64",
-                    f"-Wl,-rpath,{PKG}", "-Wl,-rpath,/opt/rocm/lib", "-Wl,-rpath-link,/opt/rocm/lib", "-lm"], check=True)
-    return exe
-
-
 def test_example_builds_as_pedantic_c99(tmp_path):
     build.build_library()
-    exe = build_example(tmp_path)
+    exe = build_example(tmp_path, "floating_bodies_host")
     import torch
     if not torch.cuda.is_available():
         r = subprocess.run([exe, "10"], capture_output=True, text=True)
@@ -416,17 +294,6 @@ def test_a_box_of_half_the_waters_density_settles_at_the_archimedes_draft(harnes
 
 
 # ---- 5. demo-scene maps --------------------------------------------------------------------------------------------------------------------
-
-def demo_bodies(counts=(64, 36, 72, 48), seed=0, spread=200.0):
-    rng = np.random.default_rng(seed)
-    items = []
-    for i, c in enumerate(counts):
-        size = (rng.uniform(2, 6), rng.uniform(1, 2), rng.uniform(3, 8))
-        items.append(dict(hull=blob_hull(c, size, i, seed * 100 + i), size=size, origin=(rng.uniform(-spread, spread), rng.uniform(-0.5, 0.8), rng.uniform(-spread, spread)),
-                          q=quaternion(rng.normal(size=3), rng.uniform(-0.6, 0.6)), v=rng.normal(0, 1, 3), w=rng.normal(0, 0.3, 3), kl=0.6, kq=0.2,
-                          density=rng.uniform(300, 700), force=(rng.normal(0, 200), 0, rng.normal(0, 200)), torque=rng.normal(0, 50, 3)))
-    return make_bodies(items)
-
 
 @pytest.fixture(scope="module")
 def demo_maps():
@@ -520,33 +387,6 @@ def test_bad_input_puts_nothing_non_finite_into_any_record(harness, demo_maps):
 
 
 # ---- 7-13. on the GPU ----------------------------------------------------------------------------------------------------------------------
-
-def hip():
-    h = C.CDLL("libamdhip64.so")
-    h.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    h.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
-    h.hipStreamSynchronize.argtypes = [C.c_void_p]
-    return h
-
-
-def device_read(ptr, count, dtype, stream=None):
-    out = np.zeros(count, dtype)
-    if count == 0:
-        return out
-    if stream is None:
-        assert hip().hipMemcpy(out.ctypes.data, ptr, out.nbytes, 2) == 0
-    else:   # through the caller's stream only
-        assert hip().hipMemcpyAsync(out.ctypes.data, ptr, out.nbytes, 2, stream) == 0
-        assert hip().hipStreamSynchronize(stream) == 0
-    return out
-
-
-def gpu_arrays(gen, s):
-    state, results = gen.bodies_state(s), gen.bodies_results(s)   # both synchronise
-    b, _, p = gen.bodies_device_ptrs(s)
-    return {"state": state.tobytes(), "records": device_read(b, s.num_bodies, W.BUOYANCY_BODY).tobytes(), "results": results.tobytes(),
-            "points": device_read(p, s.num_points, W.BUOYANCY_POINT).tobytes()}
-
 
 def parity_scene():
     """bodies of 1, 63, 64, 65, 200 and 1000 hull points, tilted and moving, a kinematic one among them"""
@@ -797,7 +637,7 @@ def test_example_floats_its_crates_without_a_host_synchronisation(tmp_path):
     and a stream-ordered history of pose and result records read back once at the end: finite; afloat per crate (its mean submerged share over
     time between a fifth and four fifths, its origin within 5 m of the water above it); nothing flagged by the device; no stream
     synchronisation by the library inside the loop (ow_sync_stats before and after)"""
-    exe = build_example(tmp_path)
+    exe = build_example(tmp_path, "floating_bodies_host")
     r = subprocess.run([exe, "480"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr
     print(r.stdout)

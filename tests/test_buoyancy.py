@@ -9,143 +9,35 @@ summation order fixed), the asynchronous form is ordered like ow_query_surface_a
 form equals a single context, and examples/buoyancy_host.c floats a box."""
 import ctypes as C
 import math
-import os
 import re
 import subprocess
 
 import numpy as np
 import pytest
 
-import query_twin as T
 from godotoceanwaves_amd import _lib, build
 from godotoceanwaves_amd.presets import UPDATE_DELTA, cascade_preset
 from godotoceanwaves_amd.wave_generator import WaveGenerator as W
-from test_surface_query import (cpu_query, generated_maps, gpu_maps, harness as query_harness, make_gen, maps_u16, scales_of,  # noqa: F401
-                                smallest_context)
+import checks as S
+from checks import buoyancy_twin as twin, check_declared_and_bound, exported_symbols
+from cpu_builds import build_example, cpu_buoyancy, cpu_query, layout_probe
+from cpu_builds import buoyancy_harness as harness, query_harness  # noqa: F401 (fixtures)
+from scenes import calm, demo_scene, G, generated_maps, gpu_maps, make_gen, make_scene, maps_u16, RHO, RHO_G, rotation, scales_of, smallest_context
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "godotoceanwaves_amd", "csrc")
-HERE = os.path.dirname(os.path.abspath(__file__))
-PKG = os.path.join(ROOT, "godotoceanwaves_amd")
 NEW_FUNCTIONS = ("ow_buoyancy", "ow_buoyancy_async", "ow_group_buoyancy")
 STRUCTS = {"OwBuoyancyBody": "ow_buoyancy_body", "OwHullPoint": "ow_hull_point", "OwBuoyancyOptions": "ow_buoyancy_options",
            "OwBuoyancyPoint": "ow_buoyancy_point", "OwBuoyancyResult": "ow_buoyancy_result"}
-RHO, G = 1025.0, 9.81
-RHO_G = float(np.float32(RHO) * np.float32(G))
-
-
-# ---- the CPU build of ow_buoyancy.h --------------------------------------------------------------------------------------------------
-
-@pytest.fixture(scope="module")
-def harness(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("buoyancy") / "libbuoyancy_harness.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unknown-pragmas", "-I", CSRC,
-                    os.path.join(HERE, "buoyancy", "buoyancy_harness.cpp"), "-o", so], check=True)
-    L = C.CDLL(so)
-    V = C.c_void_p
-    L.harness_buoyancy_sizes.argtypes = [V]
-    L.harness_buoyancy.argtypes = [V, C.c_int, C.c_int, V, V, C.c_int, V, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.c_float,
-                                   C.c_float, C.c_float, C.c_float, C.c_int, V, V]
-    return L
-
-
-def cpu_buoyancy(L, disp, scales, bodies, hull, options=None, points=None):
-    """(results, points) of the CPU build, the options resolved as the runtime resolves ow_buoyancy_options; points: the previous step's
-    records (read with warm_start), updated in place"""
-    o = dict(options or {})
-    d = maps_u16(disp)
-    sc = np.ascontiguousarray(scales, np.float32)
-    b = np.ascontiguousarray(bodies, W.BUOYANCY_BODY)
-    h = np.ascontiguousarray(hull, W.HULL_POINT)
-    pts = points if points is not None else np.zeros(len(h), W.BUOYANCY_POINT)
-    res = np.zeros(len(b), W.BUOYANCY_RESULT)
-    rho = np.float32(o.get("density", 0.0) or RHO)
-    g = np.float32(o.get("gravity", 0.0) or G)
-    center = o.get("falloff_center")
-    cx, cz = center if center is not None else (0.0, 0.0)
-    L.harness_buoyancy(d.ctypes.data, d.shape[1], len(sc), sc.ctypes.data, b.ctypes.data, len(b), h.ctypes.data, len(h),
-                       o.get("max_iterations", 0) or 16, o.get("tolerance", 0.0) or 1e-3, int(center is not None), cx, cz, float(rho),
-                       float(np.float32(rho * g)), o.get("water_level", 0.0), int(bool(o.get("warm_start"))), pts.ctypes.data, res.ctypes.data)
-    return res, pts
-
-
-def rotation(axis, angle):
-    a = np.asarray(axis, np.float64) / np.linalg.norm(axis)
-    K = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
-    return np.eye(3) + math.sin(angle) * K + (1 - math.cos(angle)) * K @ K
-
-
-def make_scene(boxes):
-    """boxes: dicts of origin, basis (3x3), size, divisions and optional v / w / kl / kq -> (bodies, hull)"""
-    bodies = np.zeros(len(boxes), W.BUOYANCY_BODY)
-    hulls, off = [], 0
-    for i, bx in enumerate(boxes):
-        h = W.box_hull(bx["size"], bx["divisions"], body=i)
-        bodies[i]["transform"][:9] = np.asarray(bx.get("basis", np.eye(3)), np.float32).ravel()
-        bodies[i]["transform"][9:] = bx["origin"]
-        bodies[i]["linear_velocity"] = bx.get("v", (0, 0, 0))
-        bodies[i]["angular_velocity"] = bx.get("w", (0, 0, 0))
-        bodies[i]["linear_drag"] = bx.get("kl", 0.0)
-        bodies[i]["quadratic_drag"] = bx.get("kq", 0.0)
-        bodies[i]["point_offset"], bodies[i]["point_count"] = off, len(h)
-        hulls.append(h)
-        off += len(h)
-    return bodies, np.concatenate(hulls) if hulls else np.zeros(0, W.HULL_POINT)
-
-
-def twin(disp, scales, bodies, hull, p, options=None):
-    """The model restated in FP64 with NumPy at the undisplaced points p the solver found: per-body force, torque and submerged volume"""
-    o = dict(options or {})
-    rho, g, wl = o.get("density", RHO), o.get("gravity", G), o.get("water_level", 0.0)
-    F = np.zeros((len(bodies), 3))
-    Tq = np.zeros((len(bodies), 3))
-    SV = np.zeros(len(bodies))
-    H = T.displacement(disp, scales, p)[:, 1] * T.falloff(p, o.get("falloff_center"))
-    for b, body in enumerate(bodies):
-        sl = slice(body["point_offset"], body["point_offset"] + body["point_count"])
-        B = body["transform"][:9].astype(np.float64).reshape(3, 3)
-        org = body["transform"][9:].astype(np.float64)
-        r = hull[sl]["local"].astype(np.float64) @ B.T
-        w = r + org
-        d = wl + H[sl] - w[:, 1]
-        hh = hull[sl]["half_height"].astype(np.float64)
-        with np.errstate(divide="ignore", invalid="ignore"):
-            s = np.where(hh > 0, np.clip((d + hh) / (2 * hh), 0, 1), (d > 0).astype(np.float64))
-        sv = hull[sl]["volume"].astype(np.float64) * s
-        u = body["linear_velocity"].astype(np.float64) + np.cross(body["angular_velocity"].astype(np.float64), r)
-        un = np.linalg.norm(u, axis=1)
-        drag = (rho * sv)[:, None] * (float(body["linear_drag"]) * u + float(body["quadratic_drag"]) * un[:, None] * u)
-        f = -drag
-        f[:, 1] += rho * g * sv
-        F[b], Tq[b], SV[b] = f.sum(0), np.cross(r, f).sum(0), sv.sum()
-    return F, Tq, SV
-
-
-def calm(n=64, cascades=1):
-    """maps of any content with map_scales.z = 0: no displacement, the surface is the plane y = water_level"""
-    rng = np.random.default_rng(0)
-    d = rng.normal(0, 1, (cascades, n, n, 4)).astype(np.float16)
-    sc = np.array([(1 / 50.0, 1 / 50.0, 0.0, 1.0)] * cascades, np.float32)
-    return maps_u16(d), sc
 
 
 # ---- 1. the ABI ----------------------------------------------------------------------------------------------------------------------
 
-HEADER = open(os.path.join(ROOT, "include", "ocean_waves.h")).read()
-
-
 def test_header_declares_buoyancy_and_the_library_exports_it():
     build.build_library()
     lib = _lib.load()
-    text = re.sub(r"/\*.*?\*/", "", HEADER, flags=re.S)
-    for name in NEW_FUNCTIONS:
-        assert re.search(r"\b%s\s*\(" % name, text), name
-        assert name in _lib.SIGNATURES
-        assert getattr(lib, name)
+    text = check_declared_and_bound(lib, NEW_FUNCTIONS)
     for struct in STRUCTS.values():
         assert re.search(r"typedef struct %s \{" % struct, text), struct
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert set(NEW_FUNCTIONS) <= set(re.findall(r" T (ow_[a-z0-9_]+)", out))
+    assert set(NEW_FUNCTIONS) <= exported_symbols()
     assert lib.ow_abi_version() == 4
 
 
@@ -158,10 +50,7 @@ def test_buoyancy_structs_agree_in_c_ctypes_numpy_and_the_harness(tmp_path, harn
     for c, f in fields:
         src += '    printf("%%zu\\n", %s);\n' % (f"sizeof({c})" if f is None else f"offsetof({c}, {f})")
     src += '    printf("%u\\n", OW_BUOYANCY_WARM_START);\n    return 0;\n}\n'
-    exe = str(tmp_path / "buoyancy_layout")
-    subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-x", "c", "-", "-o", exe],
-                   input=src, text=True, check=True)
-    got = [int(v) for v in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split()]
+    got = layout_probe(tmp_path, "buoyancy_layout", src, std=("-std=c99", "-pedantic", "-Wall", "-Werror"))
     want = []
     for c, f in fields:
         ct = getattr(_lib, c)
@@ -183,7 +72,6 @@ def test_buoyancy_structs_agree_in_c_ctypes_numpy_and_the_harness(tmp_path, harn
 def test_the_csharp_binding_shows_the_buoyancy_structs_and_functions():
     """the five [StructLayout] structs list the C fields in order with the same sizes (the embedded options counted as
     their 32 bytes), the three functions are bound with the header's argument counts, and §7 names them"""
-    import test_integration_shim as S
     c_sizes = dict(S.C_SIZES, ow_query_options=32)
     cs_sizes = dict(S.CS_SIZES, OwQueryOptions=32)
 
@@ -273,17 +161,9 @@ def test_buoyancy_argument_errors_without_a_device():
     assert (o.density, o.gravity, o.water_level, o.flags, o.query.max_iterations) == (1000.0, 0.0, -2.0, _lib.OW_BUOYANCY_WARM_START, 4)
 
 
-def build_example(tmp_path):
-    exe = str(tmp_path / "buoyancy_host")
-    subprocess.run(["gcc", "-O2", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-I", os.path.join(ROOT, "include"),
-                    os.path.join(ROOT, "examples", "buoyancy_host.c"), "-o", exe, "-L", PKG, "-locean_waves", "-L", "/opt/rocm/lib", "-lamdhip64",
-                    f"-Wl,-rpath,{PKG}", "-Wl,-rpath,/opt/rocm/lib", "-Wl,-rpath-link,/opt/rocm/lib", "-lm"], check=True)
-    return exe
-
-
 def test_example_builds_as_pedantic_c99(tmp_path):
     build.build_library()
-    exe = build_example(tmp_path)
+    exe = build_example(tmp_path, "buoyancy_host")
     import torch
     if not torch.cuda.is_available():
         r = subprocess.run([exe, "calm", "10"], capture_output=True, text=True)
@@ -358,17 +238,6 @@ def test_drag_opposes_the_motion_and_scales_as_specified(harness):
 
 
 # ---- 4. the FP64 twin on the demo scene ------------------------------------------------------------------------------------------------
-
-def demo_scene(count=12, seed=0, spread=300.0, divisions=(4, 3, 6)):
-    rng = np.random.default_rng(seed)
-    boxes = []
-    for i in range(count):
-        R = rotation(rng.normal(size=3), rng.uniform(-0.6, 0.6))
-        boxes.append(dict(origin=(rng.uniform(-spread, spread), rng.uniform(-1.5, 1.0), rng.uniform(-spread, spread)), basis=R,
-                          size=(rng.uniform(2, 8), rng.uniform(1, 3), rng.uniform(4, 15)), divisions=divisions,
-                          v=rng.normal(0, 1, 3), w=rng.normal(0, 0.2, 3), kl=0.3, kq=0.1))
-    return make_scene(boxes)
-
 
 @pytest.fixture(scope="module")
 def demo_maps():
@@ -644,7 +513,7 @@ def test_group_buoyancy_equals_a_single_context():
 
 @pytest.mark.gpu
 def test_example_floats_a_box(tmp_path):
-    exe = build_example(tmp_path)
+    exe = build_example(tmp_path, "buoyancy_host")
     r = subprocess.run([exe, "calm", "400"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr
     out = dict(kv.split("=") for kv in r.stdout.split())

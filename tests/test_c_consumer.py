@@ -1,30 +1,11 @@
 """examples/c_consumer.c: the C-ABI from plain C99 (what a GDExtension / P/Invoke shim does).  CPU: it builds with
 -pedantic -Werror against include/ocean_waves.h and fails loudly without a device.  GPU: its output equals the Python
 mirror driving the same schedule (update + one cascade per frame + asynchronous hand-off + surface sampling)."""
-import math
-import os
 import subprocess
 
-import numpy as np
 import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "godotoceanwaves_amd")
-
-
-def build(tmp_path):
-    exe = str(tmp_path / "c_consumer")
-    subprocess.run(["gcc", "-O2", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-I", os.path.join(ROOT, "include"),
-                    os.path.join(ROOT, "examples", "c_consumer.c"), "-o", exe, "-L", PKG, "-locean_waves",
-                    f"-Wl,-rpath,{PKG}", "-Wl,-rpath-link,/opt/rocm/lib", "-lm"], check=True)
-    return exe
-
-
-def fnv1a(b):
-    h = 1469598103934665603
-    for x in np.frombuffer(b, np.uint8).tolist():
-        h = ((h ^ x) * 1099511628211) & 0xFFFFFFFFFFFFFFFF
-    return h
+from checks import check_against_mirror
+from cpu_builds import build_c_consumer as build
 
 
 def test_builds_as_pedantic_c99_and_fails_loudly_without_a_device(tmp_path):
@@ -33,52 +14,6 @@ def test_builds_as_pedantic_c99_and_fails_loudly_without_a_device(tmp_path):
         pytest.skip("a GPU is present: covered by the gpu test")
     r = subprocess.run([build(tmp_path)], capture_output=True, text=True)
     assert r.returncode == 1 and "no HIP device" in r.stderr and "no CPU fallback" in r.stderr
-
-
-def mirror_schedule(n, frames):
-    """the schedule of examples/c_consumer.c / examples/wave_generator_host.cpp through the Python mirror:
-    (layers handed off, checksum, surface samples along the 64-point line)"""
-    from godotoceanwaves_amd import WaveCascadeParameters, WaveGenerator
-    tile, wind, dirs = [88.0, 57.0, 16.0], [10.0, 5.0, 20.0], [20.0, 15.0, 20.0]
-    fetch, spread, whitecap, foam = [150.0, 150.0, 550.0], [0.2, 0.4, 0.4], [0.5, 0.5, 0.25], [8.0, 0.0, 3.0]
-    params = [WaveCascadeParameters(tile_length=(tile[i], tile[i]), wind_speed=wind[i], wind_direction=dirs[i], fetch_length=fetch[i],
-                                    spread=spread[i], whitecap=whitecap[i], foam_amount=foam[i],
-                                    spectrum_seed=(1000 + 17 * i, -2000 + 31 * i), time=120.0 + math.pi * i) for i in range(3)]
-    gen = WaveGenerator()
-    gen.map_size = n
-    gen.init_gpu(3)
-    total, in_flight, handed = 0, -1, 0
-
-    def take(layer):
-        d, m = gen.readback_wait(layer)
-        return (fnv1a(d.tobytes()) + 31 * fnv1a(m.tobytes()) + layer) & 0xFFFFFFFFFFFFFFFF
-
-    for _ in range(frames):
-        if gen.pass_num_cascades_remaining == 0:
-            gen.update(1.0 / 50.0, params)
-        if in_flight >= 0:
-            total ^= take(in_flight)
-            handed += 1
-        layer = gen.pass_num_cascades_remaining - 1
-        gen._process()
-        gen.readback_begin([layer])
-        in_flight = layer
-    total ^= take(in_flight)
-    handed += 1
-    xz = np.stack([-40.0 + 1.25 * np.arange(64), 7.5 + 0.5 * np.arange(64)], axis=1).astype(np.float32)
-    return handed, total, gen.sample_surface(xz, [(1 / t, 1 / t, 1.0, 1.0) for t in tile])
-
-
-def check_against_mirror(stdout, n, frames):
-    out = dict(kv.split("=") for kv in stdout.split())
-    handed, total, s = mirror_schedule(n, frames)
-    assert int(out["layers_handed_off"]) == handed == frames
-    assert int(out["checksum"], 16) == total
-    lo, hi = out["wave_height"].strip("[]").split(",")
-    assert abs(float(lo) - float(s["displacement"][:, 1].min())) < 1e-4 and abs(float(hi) - float(s["displacement"][:, 1].max())) < 1e-4
-    assert int(out["spray_active"]) == int(s["spray_active"].sum())
-    if "spectra_generated" in out:   # (examples/c_consumer.c asks ow_spectrum_stats: one spectrum per cascade, none regenerated)
-        assert int(out["spectra_generated"]) == 3 and int(out["spectra_skipped"]) == 0
 
 
 @pytest.mark.gpu

@@ -17,29 +17,14 @@ import raycast_twin as RT
 from godotoceanwaves_amd import WaveGenerator as W
 from oracle import oracle as O
 import render_twin as RD
-from test_bodies_step import CpuSet, blob_hull, harness as bodies_harness, make_bodies, quaternion  # noqa: F401 (the fixture)
-from test_buoyancy import G, RHO, cpu_buoyancy, demo_scene, harness as buoyancy_harness, make_scene, twin as buoyancy_twin  # noqa: F401 (the fixture)
-from test_raycast import SPACING, TOL, camera_rays, check_records, cpu_raycast, harness as raycast_harness, slope_factor, unit  # noqa: F401 (the fixture)
-from test_render_view import (SHADE_TOL, SUN_LOW, check_composite, compare_with_twin, cpu_render, harness as render_harness, look,  # noqa: F401 (the fixture)
-                              pixel_rays, ray_options)
-from test_surface_query import check_against_twin, cpu_query, cpu_sample, fp32_slack, harness as query_harness, maps_u16  # noqa: F401 (the fixture)
-from test_surface_sampling import query_points, sampling_case
-from test_water_velocity import bilinear64, cpu_query_velocity, harness as velocity_harness  # noqa: F401 (the fixture)
+from checks import buoyancy_twin, check_against_twin, check_composite, check_records, compare_with_twin, fp32_slack, SHADE_TOL
+from consumer_edges import far_bodies, float_fields_finite, OPTION_SETS, seam_camera
+from cpu_builds import cpu_buoyancy, cpu_query, cpu_query_velocity, cpu_raycast, cpu_render, cpu_sample, CpuSet, CSRC, HERE
+from cpu_builds import bodies_harness, buoyancy_harness, query_harness, raycast_harness, render_harness, velocity_harness  # noqa: F401 (fixtures)
+from scenes import (bilinear64, blob_hull, camera_rays, demo_scene, G, make_bodies, maps_u16, pixel_rays, quaternion, query_points,
+                    ray_options, RAY_TOL as TOL, RHO, sampling_case, slope_factor, SPACING, SUN_LOW, unit)
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-CSRC = os.path.join(os.path.dirname(HERE), "godotoceanwaves_amd", "csrc")
 REC = W.SURFACE_QUERY
-
-
-def float_fields_finite(rec, dtype=None):
-    """every float of a structured array, nested records included, is finite"""
-    dtype = dtype or rec.dtype
-    for name in dtype.names:
-        sub = dtype.fields[name][0]
-        if sub.names:
-            float_fields_finite(rec[name], sub)
-        elif sub.base.kind == "f":
-            assert np.isfinite(rec[name]).all(), name
 
 
 # ---- the seam points reach what they are built for ---------------------------------------------------------------------------------------
@@ -302,12 +287,6 @@ def height_slack(d, sc, p):
     return 2e-5 + r * 2.0 ** -21 + r * s64[:, :2].max() * D.shape[1] * 2.0 ** -22 * per_texel
 
 
-def seam_camera(sc, n, **kw):
-    """a camera 12 m above a point whose tap sits on the last column and the last row of cascade 0's tile, looking down and ahead"""
-    x, z = E.seam_points(sc, n)[2]
-    return look((float(x), 12.0, float(z)), 30.0, -35.0, **kw)
-
-
 def test_render_on_non_square_tiles_against_the_twins(render_harness, raycast_harness):
     """a view from above a seam over EDGE_SCALES at 256^2: the pixel rays against render_twin's, every pixel the ray cast's bits, the
     record's height the FP64 displacement sum at its p (ow_render.h's own lookups on non-square tiles), and the shading against
@@ -361,9 +340,6 @@ def test_a_floating_body_on_non_square_tiles_is_the_cpu_buoyancy_at_every_pose(b
 
 # ---- A5. far points ------------------------------------------------------------------------------------------------------------------------
 
-OPTION_SETS = [dict(), dict(falloff_center=(12.5, -40.0)), dict(max_iterations=3, tolerance=1e-4)]
-
-
 def test_far_points_leave_nothing_non_finite_in_a_query_record(query_harness):
     d, m, sc = E.edge_maps(128)
     far, bad = E.far_points()
@@ -384,16 +360,6 @@ def test_far_points_leave_nothing_non_finite_in_a_query_record(query_harness):
             elif f != "world_xz" and REC.fields[f][0].base.kind == "f":
                 assert np.isfinite(out[f]).all(), f
         assert (out["p"] == 0).all() and (out["converged"] == 0).all() and (out["iterations"] == 0).all()
-
-
-def far_bodies(points):
-    """one 2 x 2 x 2 box of eight hull points at each far point, and one body at the origin whose hull points are the far points"""
-    boxes = [dict(origin=(float(x), 0.0, float(z)), size=(2, 2, 2), divisions=(2, 2, 2), v=(1.0, 0.0, -1.0), kl=0.3, kq=0.1) for x, z in points]
-    bodies, hull = make_scene(boxes + [dict(origin=(0, 0, 0), size=(2, 2, 2), divisions=(2, 2, len(points) // 4 + 1))])
-    last = bodies[-1]
-    sl = slice(last["point_offset"], last["point_offset"] + len(points))
-    hull["local"][sl, 0], hull["local"][sl, 2] = points[:, 0], points[:, 1]
-    return bodies, hull
 
 
 def test_far_points_leave_nothing_non_finite_in_buoyancy_cast_or_velocity(buoyancy_harness, raycast_harness, velocity_harness, query_harness):
@@ -437,35 +403,35 @@ import numpy as np
 sys.path.insert(0, sys.argv[1]); sys.path.insert(0, os.path.dirname(sys.argv[1]))
 import consumer as K
 import consumer_edges as E
-import test_consumer_edges as TE, test_surface_query as Q, test_buoyancy as B, test_raycast as R, test_water_velocity as V
+import cpu_builds as B
 from godotoceanwaves_amd import WaveGenerator as W
-def load(mod, name):
+def load(name):
     return C.CDLL(os.path.join(sys.argv[2], "lib%s_harness.so" % name))
 d, m, sc = E.edge_maps(128)
 far, bad = E.far_points()
 pts = np.concatenate([E.seam_points(sc, 128), far, bad])
 Vp = C.c_void_p
-q = load(Q, "query")
+q = load("query")
 q.harness_sample.argtypes = [Vp, Vp, C.c_int, C.c_int, Vp, Vp, C.c_int, Vp]
 q.harness_query.argtypes = [Vp, Vp, C.c_int, C.c_int, Vp, Vp, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.c_float, Vp]
-for kw in TE.OPTION_SETS:
-    Q.cpu_query(q, d, m, sc, pts, **kw)
-Q.cpu_sample(q, d, m, sc, pts)
-b = load(B, "buoyancy")
+for kw in E.OPTION_SETS:
+    B.cpu_query(q, d, m, sc, pts, **kw)
+B.cpu_sample(q, d, m, sc, pts)
+b = load("buoyancy")
 b.harness_buoyancy.argtypes = [Vp, C.c_int, C.c_int, Vp, Vp, C.c_int, Vp, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, Vp, Vp]
-bodies, hull = TE.far_bodies(np.concatenate([E.seam_points(sc, 128)[::7], far]))
+bodies, hull = E.far_bodies(np.concatenate([E.seam_points(sc, 128)[::7], far]))
 for opts in ({}, {"falloff_center": (12.5, -40.0)}, {"warm_start": True}):
     B.cpu_buoyancy(b, d, sc, bodies, hull, opts)
-r = load(R, "raycast")
+r = load("raycast")
 r.harness_raycast.argtypes = [Vp, Vp, C.c_int, C.c_int, Vp, Vp, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, Vp, Vp]
 fin = np.concatenate([E.seam_points(sc, 128)[::5], far])
 o = np.stack([fin[:, 0], np.full(len(fin), 30.0, np.float32), fin[:, 1]], axis=1)
-R.cpu_raycast(r, d, m, sc, W.rays(o, np.tile([(0.1, -1.0, 0.2)], (len(o), 1)), 500.0))
-R.cpu_raycast(r, d, m, sc, W.rays(np.tile([(3.0, 20.0, -4.0)], (len(o), 1)), np.stack([fin[:, 0], np.full(len(fin), -1.0), fin[:, 1]], axis=1), 3e38))
-v = load(V, "velocity")
+B.cpu_raycast(r, d, m, sc, W.rays(o, np.tile([(0.1, -1.0, 0.2)], (len(o), 1)), 500.0))
+B.cpu_raycast(r, d, m, sc, W.rays(np.tile([(3.0, 20.0, -4.0)], (len(o), 1)), np.stack([fin[:, 0], np.full(len(fin), -1.0), fin[:, 1]], axis=1), 3e38))
+v = load("velocity")
 v.harness_query_velocity.argtypes = [Vp, Vp, C.c_int, C.c_int, Vp, Vp, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.c_float, Vp]
 for center in (None, (12.5, -40.0)):
-    V.cpu_query_velocity(v, d, m, sc, pts, center)
+    B.cpu_query_velocity(v, d, m, sc, pts, center)
 print("ran", len(pts), "points")
 """
 

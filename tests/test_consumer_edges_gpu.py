@@ -11,14 +11,11 @@ import consumer_edges as E
 from godotoceanwaves_amd import WaveCascadeParameters, WaveGenerator as W
 from godotoceanwaves_amd.presets import UPDATE_DELTA
 from oracle import oracle as O
-from test_bodies_step import CpuSet, demo_bodies, gpu_arrays, harness as bodies_harness  # noqa: F401 (the fixture)
-from test_buoyancy import cpu_buoyancy, harness as buoyancy_harness  # noqa: F401 (the fixture)
-from test_consumer_edges import OPTION_SETS, float_fields_finite, seam_camera
-from test_render_view import SUN_BEHIND, assert_same_image, cpu_render, harness as render_harness  # noqa: F401 (the fixture)
-from test_raycast import cpu_raycast, harness as raycast_harness, mixed_rays  # noqa: F401
-from test_surface_query import cpu_query, gpu_maps, harness as query_harness  # noqa: F401
-from test_surface_sampling import query_points
-from test_water_velocity import _vel_layers, cpu_buoyancy_moving, cpu_query_velocity, harness as velocity_harness  # noqa: F401
+from checks import assert_same_image
+from consumer_edges import float_fields_finite, OPTION_SETS, seam_camera
+from cpu_builds import cpu_buoyancy, cpu_buoyancy_moving, cpu_query, cpu_query_velocity, cpu_raycast, cpu_render, CpuSet
+from cpu_builds import bodies_harness, buoyancy_harness, query_harness, raycast_harness, render_harness, velocity_harness  # noqa: F401 (fixtures)
+from scenes import demo_bodies, gpu_arrays, gpu_maps, mixed_rays, query_points, SUN_BEHIND, velocity_layers as _vel_layers
 
 REC = W.SURFACE_QUERY
 SLAB_FLOOR = np.float32(1e-2)   # csrc/ow_raycast.h kSlabFloor

@@ -2,20 +2,12 @@
 water.gd:93-100) -- what a GDExtension node would wrap.  CPU: it builds with -Wall -Wextra -Werror as C++17 against the C header
 and fails loudly without a device.  GPU: examples/wave_generator_host.cpp (update / _process once per frame / layers delivered to a
 texture sink one frame later) produces exactly what the Python mirror produces on the same schedule."""
-import os
 import subprocess
 
 import pytest
 
-from test_c_consumer import PKG, ROOT, check_against_mirror
-
-
-def build(tmp_path):
-    exe = str(tmp_path / "wave_generator_host")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"),
-                    os.path.join(ROOT, "examples", "wave_generator_host.cpp"), "-o", exe, "-L", PKG, "-locean_waves",
-                    f"-Wl,-rpath,{PKG}", "-Wl,-rpath-link,/opt/rocm/lib"], check=True)
-    return exe
+from checks import check_against_mirror
+from cpu_builds import build_cpp_host as build
 
 
 def test_builds_and_fails_loudly_without_a_device(tmp_path):

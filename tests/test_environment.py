@@ -24,127 +24,28 @@ import helpers as H
 from godotoceanwaves_amd import _lib, build
 from godotoceanwaves_amd.presets import UPDATE_DELTA
 from godotoceanwaves_amd.wave_generator import WaveGenerator as W
-from test_mesh_draw import REF_BASIS, cpu_draw as cpu_mesh_draw, grid, harness as mesh_harness  # noqa: F401
-from test_raycast import calm_maps
-from test_render_view import camera_words, look
-from test_bodies_step import crate, make_bodies
-from test_solid_draw import (CRATE_CAM, CRATE_SHAPE, box, cpu_draw as cpu_solid_draw, example_crates, gpu_material,
-                             harness as solid_harness, pose_transforms)  # noqa: F401
-from test_spray_draw import (FOAM, MAX_ALPHA, WHITE, cpu_draw as cpu_billboard_draw, example_textures, harness as billboard_harness, instances as billboards,  # noqa: F401
-                             level_camera, material)
-from test_surface_query import generated_maps, gpu_maps, make_gen, scales_of
+import checks as S
+from checks import check_declared_and_bound, exported_symbols, HEADER, same_records
+from cpu_builds import (cpu_billboard_draw, cpu_environment, cpu_mesh_draw, cpu_present, cpu_solid_draw, CSRC, ENV_CASE, env_case, ENV_DEFAULTS,
+                        PRESENT_CASE, present_case, PRESENT_DEFAULTS, ROOT, sky_lookup)
+from cpu_builds import billboard_harness, env_harness as harness, mesh_harness, pictures, solid_harness  # noqa: F401 (fixtures)
+from scenes import (bare_context, billboards, box, camera_words, CRATE_CAM, CRATE_SHAPE, device_frame, ENV, example_crates, example_panorama,
+                    example_textures, f32_options, FOAM, FRAME_CAM, FRAME_ENV, FRAME_PRESENT, frame_scene, FRAME_SHAPE, FRAME_WATER,
+                    gpu_maps, gpu_material, gpu_sky, gradient_panorama, grid, HIT, level_camera, look, make_gen, material, MAX_ALPHA,
+                    pose_transforms, records_of, REF_BASIS, rel, scales_of, sky_of, SOLID, SUN, synthetic_records, WHITE)
+from cpu_builds import build_example, build_sanitized_harness, layout_probe
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "godotoceanwaves_amd", "csrc")
-PKG = os.path.join(ROOT, "godotoceanwaves_amd")
-HERE = os.path.dirname(os.path.abspath(__file__))
-HARNESS_SRC = os.path.join(HERE, "environment", "environment_harness.cpp")
 MARGINS = os.path.join(ROOT, "profiles", "present_margins.txt")
 NEW_FUNCTIONS = ("ow_sky_options_default", "ow_environment_options_default", "ow_present_options_default", "ow_sky_create", "ow_sky_destroy",
                  "ow_environment_apply", "ow_environment_apply_async", "ow_present", "ow_present_async")
 TOL = H.TOL_F32     # 1e-4: the project's FP32 parity tolerance
-HIT, SOLID, ENV = _lib.OW_RAY_HIT, _lib.OW_RAY_SOLID, _lib.OW_RAY_ENVIRONMENT
-SUN = (0.321197, 0.18296, 0.929171)                                 # main.tscn:113, the Sun's +Z axis
-ENV_DEFAULTS = dict(fog_mode=1, density=1.0, depth_begin=200.0, depth_end=350.0, depth_curve=0.25, aerial_perspective=0.626, sun_scatter=0.05,
-                    light_color=(0.272954, 0.419272, 0.484632), sun_color=(1.0, 1.0, 1.0), sun_direction=SUN, sky_color=(0.25, 0.40, 0.60))
-PRESENT_DEFAULTS = dict(downsample=1, tonemap=2, exposure=1.0, white=1.0, srgb=1, brightness=0.85, contrast=1.07, saturation=1.5)
 PLAIN = dict(downsample=1, tonemap=0, exposure=1.0, white=1.0, srgb=0, brightness=1.0, contrast=1.0, saturation=1.0)
-ENV_CASE = np.dtype([("width", np.int32), ("height", np.int32), ("cam", np.float32, 15), ("fog_mode", np.int32), ("density", np.float32),
-                     ("depth_begin", np.float32), ("depth_end", np.float32), ("depth_curve", np.float32), ("aerial_perspective", np.float32),
-                     ("sun_scatter", np.float32), ("light_color", np.float32, 3), ("sun_color", np.float32, 3), ("sun_direction", np.float32, 3),
-                     ("sky_color", np.float32, 3), ("has_sky", np.int32), ("sky_width", np.int32), ("sky_height", np.int32), ("sky_srgb", np.int32),
-                     ("energy", np.float32)])
-PRESENT_CASE = np.dtype([("width", np.int32), ("height", np.int32), ("downsample", np.int32), ("tonemap", np.int32), ("exposure", np.float32),
-                         ("white", np.float32), ("srgb", np.int32), ("brightness", np.float32), ("contrast", np.float32), ("saturation", np.float32)])
 ATAN2_MAX_ULP = 2.54     # measured on the CPU build over the sweep below (2.539 at y / x = -0.4148); csrc/ow_environment.h states it
 ATAN2_MAX_ABS = 3.0e-7   # ... and 2.97e-7 absolute
 ACOS_MAX_ABS = 3.2e-7    # ... and acos_f32's 3.12e-7 over [-1, 1], the poles included
 
 
 # ---- panoramas, records and the CPU build -------------------------------------------------------------------------------------------------
-
-def gradient_panorama(w=64, h=32, seed=5):
-    """a smooth sky: a vertical gradient, brighter towards one azimuth, a little noise so that no two texels are alike"""
-    j, i = np.meshgrid(np.arange(h), np.arange(w), indexing="ij")
-    rng = np.random.default_rng(seed)
-    img = np.zeros((h, w, 4), np.uint8)
-    img[..., 0] = 40 + 150 * j // max(h - 1, 1) + rng.integers(0, 8, (h, w))
-    img[..., 1] = 90 + 120 * j // max(h - 1, 1) + 20 * np.abs(2 * i - w) // max(w, 1)
-    img[..., 2] = 230 - 100 * j // max(h - 1, 1) + rng.integers(0, 8, (h, w))
-    img[..., 3] = 255
-    return img
-
-
-def sky_of(image, srgb=1, energy=1.0):
-    return dict(image=np.ascontiguousarray(image, np.uint8), srgb=int(srgb), energy=float(np.float32(energy)))
-
-
-def f32_options(defaults, opts):
-    """the options as the library sees them: every number through FP32"""
-    o = dict(defaults, **(opts or {}))
-    return {k: (tuple(float(np.float32(x)) for x in v) if isinstance(v, (tuple, list, np.ndarray)) else (int(v) if isinstance(v, (int, np.integer)) else
-                                                                                                    float(np.float32(v)))) for k, v in o.items()}
-
-
-@pytest.fixture(scope="module")
-def harness(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("environment") / "libenvironment_harness.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unknown-pragmas", "-I", CSRC, HARNESS_SRC, "-o", so], check=True)
-    L = C.CDLL(so)
-    V, I = C.c_void_p, C.c_int
-    L.harness_environment_sizes.argtypes = [V]
-    L.harness_atan2.argtypes = [V, V, I, V]
-    L.harness_acos.argtypes = [V, I, V]
-    L.harness_sky_lookup.argtypes = [V, V, V, I, V]
-    L.harness_fog_amount.argtypes = [V, V, I, V]
-    L.harness_environment_apply.argtypes = [V, V, V, V]
-    L.harness_present.argtypes = [V, V, V, V, V]
-    return L
-
-
-def env_case(cam, opts=None, sky=None):
-    o = f32_options(ENV_DEFAULTS, opts)
-    h = np.zeros(1, ENV_CASE)
-    h["width"], h["height"], h["cam"] = cam.width, cam.height, camera_words(cam)
-    for k in ENV_DEFAULTS:
-        h[k] = o[k]
-    if sky is not None:
-        h["has_sky"], h["sky_height"], h["sky_width"], h["sky_srgb"], h["energy"] = 1, sky["image"].shape[0], sky["image"].shape[1], sky["srgb"], sky["energy"]
-    return h
-
-
-def present_case(width, height, opts=None):
-    o = f32_options(PRESENT_DEFAULTS, opts)
-    h = np.zeros(1, PRESENT_CASE)
-    h["width"], h["height"] = width, height
-    for k in PRESENT_DEFAULTS:
-        h[k] = o[k]
-    return h
-
-
-def cpu_environment(L, records, cam, opts=None, sky=None):
-    """the CPU build's pass: dict of rec (a copy, rewritten) and the stages ray, sky, amount, fog"""
-    rec = np.array(records, W.RENDER_PIXEL, copy=True, order="C")
-    assert rec.shape == (cam.height, cam.width)
-    h = env_case(cam, opts, sky)
-    st = np.zeros((cam.height, cam.width, 10), np.float32)
-    L.harness_environment_apply(h.ctypes.data, sky["image"].ctypes.data if sky is not None else None, rec.ctypes.data, st.ctypes.data)
-    return dict(rec=rec, ray=st[..., 0:3], sky=st[..., 3:6], amount=st[..., 6], fog=st[..., 7:10])
-
-
-def cpu_present(L, records, opts=None):
-    """the CPU build's present: dict of rgba [H / s][W / s][4], linear [H / s][W / s][4] and the stages exposed, mapped, encoded, adjusted"""
-    rec = np.ascontiguousarray(records, W.RENDER_PIXEL)
-    hh, ww = rec.shape
-    o = f32_options(PRESENT_DEFAULTS, opts)
-    s = max(o["downsample"], 1)
-    h = present_case(ww, hh, opts)
-    rgba = np.zeros((hh // s, ww // s, 4), np.uint8)
-    lin = np.zeros((hh // s, ww // s, 4), np.float32)
-    st = np.zeros((hh // s, ww // s, 12), np.float32)
-    L.harness_present(h.ctypes.data, rec.ctypes.data, rgba.ctypes.data, lin.ctypes.data, st.ctypes.data)
-    return dict(rgba=rgba, linear=lin, exposed=st[..., 0:3], mapped=st[..., 3:6], encoded=st[..., 6:9], adjusted=st[..., 9:12])
-
 
 def twin_environment(records, cam, opts=None, sky=None):
     o = f32_options(ENV_DEFAULTS, opts)
@@ -155,34 +56,6 @@ def twin_environment(records, cam, opts=None, sky=None):
 
 def twin_present(records, opts=None):
     return ET.present(records, f32_options(PRESENT_DEFAULTS, opts))
-
-
-def synthetic_records(cam, seed=1, top=50.0):
-    """a record field with everything in it: misses of every status, water hits, hits from below and solids at t from 0 to 1000 m (the
-    fog's ends and the values next to them included), colours from 0 to `top`"""
-    rng = np.random.default_rng(seed)
-    shape = (cam.height, cam.width)
-    rec = np.zeros(shape, W.RENDER_PIXEL)
-    kind = rng.integers(0, 4, shape)
-    miss = rng.choice(np.int32([0, 2, 4, 8]), shape)
-    rec["status"] = np.where(kind == 0, miss, np.where(kind == 1, HIT, np.where(kind == 2, HIT | SOLID, HIT | 2)))
-    special = np.float32([0.0, 200.0, np.nextafter(np.float32(200), np.float32(0)), np.nextafter(np.float32(200), np.float32(400)), 275.0, 350.0,
-                          np.nextafter(np.float32(350), np.float32(0)), np.nextafter(np.float32(350), np.float32(400)), 1000.0, 1e-3])
-    t = np.where(rng.random(shape) < 0.25, rng.choice(special, shape), rng.uniform(0.0, 1000.0, shape).astype(np.float32))
-    rec["t"] = np.where(kind == 0, 0.0, t)
-    scale = np.where(rng.random(shape) < 0.5, 1.0, top)
-    rec["color"] = (rng.random(shape + (3,)) * scale[..., None]).astype(np.float32)
-    rec["color"][rng.random(shape) < 0.05] = 0.0
-    rec["specular"] = rng.random(shape).astype(np.float32)        # neighbours of the fields the pass rewrites: they must not move
-    rec["reserved"] = rng.integers(0, 1 << 30, shape + (4,))
-    return rec
-
-
-def rel(got, want):
-    """|got - want| relative to max(1, |want|), the largest over the array (0 for an empty one)"""
-    want = np.asarray(want, np.float64)
-    e = np.abs(np.asarray(got, np.float64) - want) / np.maximum(1.0, np.abs(want))
-    return float(e.max()) if e.size else 0.0
 
 
 def check_environment_against_twin(got, tw, records, sky, opts, what):
@@ -216,19 +89,11 @@ def check_present_against_twin(got, tw, what):
 
 # ---- 1. the interface and the documents --------------------------------------------------------------------------------------------------
 
-HEADER = open(os.path.join(ROOT, "include", "ocean_waves.h")).read()
-
-
 def test_header_declares_the_new_calls_and_the_library_exports_them():
     build.build_library()
     lib = _lib.load()
-    text = re.sub(r"/\*.*?\*/", "", HEADER, flags=re.S)
-    for name in NEW_FUNCTIONS:
-        assert re.search(r"\b%s\s*\(" % name, text), name
-        assert name in _lib.SIGNATURES
-        assert getattr(lib, name)
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = set(re.findall(r" T (ow_[a-z0-9_]+)", out))
+    text = check_declared_and_bound(lib, NEW_FUNCTIONS)
+    exported = exported_symbols()
     assert sorted(s for s in exported if re.search(r"ow_(sky|environment|present)", s)) == sorted(NEW_FUNCTIONS)      # no group form
     assert lib.ow_abi_version() == 4 and re.search(r"#define OW_ABI_VERSION 4\b", HEADER)
     for define, value in (("OW_RAY_ENVIRONMENT", 32), ("OW_SKY_MAX_SIDE", 8192), ("OW_PRESENT_MAX_DOWNSAMPLE", 4), ("OW_FOG_EXPONENTIAL", 0),
@@ -273,9 +138,7 @@ def test_option_structs_agree_in_c_ctypes_and_the_harness(tmp_path, harness):
         expr = ", ".join(["sizeof(%s)" % name] + ["offsetof(%s, %s)" % (name, f) for f in fields])
         src = ('#include <stdio.h>\n#include <stddef.h>\n#include "ocean_waves.h"\nint main(void){printf("%s\\n", ' % " ".join(["%zu"] * (1 + len(fields)))
                + expr + ");return 0;}\n")
-        exe = str(tmp_path / (name + "_layout"))
-        subprocess.run(["gcc", "-std=c11", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-x", "c", "-", "-o", exe], input=src, text=True, check=True)
-        vals = [int(v) for v in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split()]
+        vals = layout_probe(tmp_path, (name + "_layout"), src)
         assert vals == [C.sizeof(S)] + [getattr(S, f).offset for f in fields], name
         got[name] = dict(zip(["size"] + fields, vals))
     assert (got["ow_sky_options"]["size"], got["ow_environment_options"]["size"], got["ow_present_options"]["size"]) == (32, 128, 64)
@@ -288,7 +151,6 @@ def test_option_structs_agree_in_c_ctypes_and_the_harness(tmp_path, harness):
 
 
 def test_the_documents_name_the_new_calls():
-    import test_integration_shim as S
     for name in NEW_FUNCTIONS:
         assert "`%s`" % name in S.DOC.split("## 7. Index")[1], name
     for name in ("ow_sky_create", "ow_environment_apply_async", "ow_present_async"):
@@ -303,17 +165,9 @@ def test_the_documents_name_the_new_calls():
         assert os.path.exists(os.path.join(ROOT, path)), path
 
 
-def build_example(tmp_path):
-    exe = str(tmp_path / "present_host")
-    subprocess.run(["gcc", "-O2", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "examples", "present_host.c"),
-                    "-o", exe, "-L", PKG, "-locean_waves", "-L", "/opt/rocm/lib", "-lamdhip64", f"-Wl,-rpath,{PKG}", "-Wl,-rpath,/opt/rocm/lib", "-lm"],
-                   check=True)
-    return exe
-
-
 def test_example_builds_as_c99(tmp_path):
     build.build_library()
-    build_example(tmp_path)
+    build_example(tmp_path, "present_host")
 
 
 # ---- 2. argument errors without a device ---------------------------------------------------------------------------------------------------
@@ -540,13 +394,6 @@ def test_applying_twice_equals_applying_once(harness):
     assert got[:, :20].tobytes() == part[:, :20].tobytes() and got["color"][:, 20:].tobytes() == once["color"][:, 20:].tobytes()
 
 
-def sky_lookup(L, sky, dirs):
-    d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
-    out = np.zeros((len(d), 3), np.float32)
-    L.harness_sky_lookup(env_case(level_camera(4, 4), None, sky).ctypes.data, sky["image"].ctypes.data, d.ctypes.data, len(d), out.ctypes.data)
-    return out
-
-
 def test_a_4_by_2_panorama_returns_the_expected_texels(harness):
     """columns are centred on u = 1/8, 3/8, 5/8, 7/8 and rows on v = 1/4, 3/4: -Z (u = 1/2) falls between columns 1 and 2, +X (3/4) between 2
     and 3, +Z (the seam, u = 1 = 0) between 3 and 0, -X (1/4) between 0 and 1, each half and half and, on the horizon, half of either row; straight
@@ -618,21 +465,6 @@ def test_the_filmic_curve(harness):
 
 
 # ---- 5. against the FP64 twin --------------------------------------------------------------------------------------------------------------
-
-PICTURE_CAM = dict(position=(0.0, 20.0, 0.0), yaw_deg=15.0, pitch_deg=-1.5, fov=60.0, width=72, height=36, max_distance=4000.0)
-
-
-@pytest.fixture(scope="module")
-def pictures(mesh_harness):
-    """ow_mesh_draw's CPU build over a calm sea (a 1 km grid: hits from a few metres to beyond the fog's end, and the sky above the horizon)
-    and over a generated one (128^2 x 3 oracle maps, the shader's falloff)"""
-    cam = look(**PICTURE_CAM)
-    d, m, sc = calm_maps()
-    calm = cpu_mesh_draw(mesh_harness, d, m, sc, grid(64, 16.0), (0.0, 0.0, 0.0), cam)
-    d, m, sc = generated_maps(128, [0, 1, 2], ticks=3)
-    sea = cpu_mesh_draw(mesh_harness, d, m, sc, grid(64, 16.0), W.clipmap_origin(cam.position, 16.0), cam, {"falloff": True})
-    return dict(cam=cam, calm=dict(rec=calm["rec"], rgba=calm["rgba"]), sea=dict(rec=sea["rec"], rgba=sea["rgba"]))
-
 
 ENV_VARIANTS = {"the scene's": None, "exponential": dict(fog_mode=0, density=0.004, aerial_perspective=0.0, sun_scatter=0.0),
                 "thin, curved, bright sun": dict(density=0.6, depth_curve=2.0, depth_begin=50.0, depth_end=900.0, sun_scatter=0.8, sun_color=(3.0, 2.5, 2.0),
@@ -809,9 +641,7 @@ def write_case(path, cam, rec, env, sky, popts):
 def test_stand_alone_harness_runs_clean_under_the_sanitizers(tmp_path, harness, pictures):
     """the harness as a program of its own (-DENVIRONMENT_HARNESS_MAIN), built with -fsanitize=address,undefined, on the twin's fields and every
     awkward case: what it writes is the shared library's"""
-    exe = str(tmp_path / "environment_harness_main")
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    "-Wno-unknown-pragmas", "-DENVIRONMENT_HARNESS_MAIN", "-I", CSRC, HARNESS_SRC, "-o", exe], check=True)
+    exe = build_sanitized_harness("environment", tmp_path)
     cam = pictures["cam"]
     cases = [("synthetic", cam, synthetic_records(cam, 1), None, sky_of(gradient_panorama(), 1, 1.3), None),
              ("sea, exponential", cam, pictures["sea"]["rec"], ENV_VARIANTS["exponential"], None, PRESENT_VARIANTS["linear x3"]),
@@ -832,20 +662,6 @@ def test_stand_alone_harness_runs_clean_under_the_sanitizers(tmp_path, harness, 
 
 
 # ---- 8-12. on the GPU -----------------------------------------------------------------------------------------------------------------------
-
-def bare_context():
-    """the smallest context: neither call reads a map"""
-    return make_gen(128, [0, 1])[0]
-
-
-def same_records(a, b, what):
-    for f in W.RENDER_PIXEL.names:
-        assert a[f].tobytes() == b[f].tobytes(), (what, f)
-
-
-def gpu_sky(gen, sky):
-    return gen.sky_create(sky["image"], {"srgb": sky["srgb"], "energy": sky["energy"]}) if sky is not None else None
-
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("width,height,s", [(67, 35, 1), (69, 39, 3), (2, 2, 2)])
@@ -885,53 +701,7 @@ def test_gpu_pass_and_present_are_the_cpu_builds_bit_for_bit(harness, width, hei
     gen.free()
 
 
-def device_frame(cam, s):
-    import torch
-    count = cam.width * cam.height
-    out = (cam.width // s) * (cam.height // s)
-    return (torch.zeros((count, W.RENDER_PIXEL.itemsize), dtype=torch.uint8, device="cuda:0"), torch.zeros((out, 4), dtype=torch.uint8, device="cuda:0"),
-            torch.zeros((out, 4), dtype=torch.float32, device="cuda:0"))
-
-
-def records_of(cam, rec_dev):
-    return np.frombuffer(rec_dev.cpu().numpy().tobytes(), W.RENDER_PIXEL).reshape(cam.height, cam.width).copy()
-
-
-def advance(gen, params, sc, bodies, spray, steps):
-    for _ in range(steps):
-        gen.update_all(UPDATE_DELTA, params)
-        gen.bodies_step(bodies, sc, 2, UPDATE_DELTA / 2, {"warm_start": True})
-        gen.spray_step(spray, UPDATE_DELTA, sc)
-
-
-FRAME_CAM = dict(position=(-1.0, 12.0, -60.0), yaw_deg=0.0, pitch_deg=-10.0, fov=75.0, width=64, height=40, max_distance=4000.0)
-FRAME_WATER = (18, 4.0)          # a 72 m grid round the camera: it ends at z = -24, in the middle of the emitter's box (z from -32.5 to -17.5), so the
                                  # spray in front of that edge lies over water and the spray behind it over pixels without a hit -- the sky
-FRAME_SPRAY = {"amount": 4096, "emitter_lifetime": 0.5, "lifetime": 0.25, "particle_scale": (60.0, 25.0, 60.0)}   # three times the scene's billboards
-FRAME_SHAPE = (4.0, 2.0, 4.0)    # drawn at the crates' poses: large enough to show from 20 m at 64 x 40
-FRAME_ENV = dict(depth_begin=20.0, depth_end=120.0)      # the scene is small: fog that shows inside it
-FRAME_PRESENT = dict(downsample=2)
-
-
-def frame_crates():
-    """eight tumbled crates in two rows 18 m and 24 m in front of the camera, on the water"""
-    rng = np.random.default_rng(3)
-    items = []
-    for k in range(8):
-        q = rng.normal(size=4)
-        items.append(crate(origin=((k % 4 - 1.5) * 4.0 - 1.0, 0.3, -42.0 + 6.0 * (k // 4)), q=tuple(q / np.linalg.norm(q)), kl=3.0, kq=0.5))
-    return make_bodies(items)
-
-
-def frame_scene(n=256, ids=(0, 1, 2), ticks=100, steps=30):
-    """256^2 x 3 maps 100 ticks in (foam has built up), eight crates and the emitter stepped 30 times behind a tick each"""
-    gen, params = make_gen(n, list(ids))
-    sc = scales_of(params)
-    gen.run(UPDATE_DELTA, params, ticks)
-    bodies = gen.bodies_create(*frame_crates())
-    spray = gen.spray_create(FRAME_SPRAY)
-    advance(gen, params, sc, bodies, spray, steps)
-    return gen, params, sc, bodies, spray
 
 
 def spray_over_both(fin, amount):
@@ -1136,25 +906,10 @@ def test_skies_of_other_contexts_and_orphans_are_refused_and_errors_write_nothin
     live.free()
 
 
-def example_panorama(w=256, h=128):
-    """examples/present_host.c's make_panorama, integer for integer"""
-    half = h // 2
-    j, i = np.meshgrid(np.arange(h), np.arange(w), indexing="ij")
-    up = j < half
-    k = np.where(up, j, h - 1 - j)
-    az = (20 * np.abs(2 * i - w)) // w
-    img = np.zeros((h, w, 4), np.uint8)
-    img[..., 0] = np.where(up, 60 + (150 * k) // (half - 1), 30 + (40 * k) // (half - 1)) + az
-    img[..., 1] = np.where(up, 110 + (110 * k) // (half - 1), 50 + (50 * k) // (half - 1)) + az
-    img[..., 2] = np.where(up, 200 + (40 * k) // (half - 1), 70 + (60 * k) // (half - 1))
-    img[..., 3] = 255
-    return img
-
-
 @pytest.mark.gpu
 def test_the_c_example_writes_the_python_wrappers_image(tmp_path):
     """examples/present_host.c at 256^2, a 48 x 32 PPM of 96 x 64 records, 40 steps, 4096 particles, against the wrapper on the same scene"""
-    exe = build_example(tmp_path)
+    exe = build_example(tmp_path, "present_host")
     ppm = str(tmp_path / "present.ppm")
     r = subprocess.run([exe, ppm, "48", "32", "40", "256", "4096", "2"], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stderr

@@ -3,7 +3,6 @@ the FP64 twin in the metrics of tests/frame_bins.py -- the bounds come from the 
 tests/test_frame_bins.py), never from the device.  A context generates its spectra once (one tick of preset records on the case's tile
 lengths), gets a different input seed per cascade -- the square tile on cascade 0, the non-square one on cascade 1, so that a slot mix-up
 shows --, a zero foam plane, and runs the path under test with clean records."""
-import functools
 
 import numpy as np
 import pytest
@@ -12,122 +11,12 @@ import frame_bins as FB
 import helpers as H
 from godotoceanwaves_amd import WaveCascadeParameters, WaveGenerator, _lib
 from godotoceanwaves_amd.presets import UPDATE_DELTA, cascade_preset
+from frame_bins import _h0, _seed, _tile, gpu_cases as _cases, run_gpu_case as run_case
 
 pytestmark = pytest.mark.gpu
 
 # (n, cascades, path, kernels, family asserted, ticks of the path): the smallest shape at which each kernel exists
-PATHS = [
-    (128, 2, "update_all", "standard", "standard", 1),
-    (128, 2, "update_all", "layer_parallel", "layer_parallel", 1),
-    (256, 2, "update_all", "layer_parallel_compact", "layer_parallel_compact", 1),
-    (256, 2, "run", None, "tick_groups_compact", 3),
-    (512, 2, "update_all", "compact", "compact", 1),
-    (1024, 2, "update_all", "standard", "standard", 1),        # the 1024^2 plan
-    (1024, 2, "update_all", None, "compact", 1),
-    (1024, 2, "run", None, "tick_pairs_compact", 3),
-    (1024, 2, "lookahead", None, "compact", 4),                  # update_all x 4 with one delta: the last tick's pass 1 was computed ahead
-    (2048, 1, "update_all", None, "compact", 1),                 # split-plan pass 1, half-table pass 2
-    (2048, 1, "run", None, "tick_pairs_compact", 3),             # the split tick pairs
-]
 BINS_2048 = ("hy", "hz", "dhx_dx")
-
-
-def _inputs(n):
-    return list(FB.inputs(n)) if n in (256, 1024) else ["white", "lines"]
-
-
-def _cases():
-    """grouped by size and input, the paths innermost: the twin of an input is shared by the paths that reach the same FP32 time"""
-    out = []
-    for n in sorted({p[0] for p in PATHS}):
-        for name in _inputs(n):
-            out += [(name,) + p for p in PATHS if p[0] == n]
-    return out
-
-
-def _tile(n, cascades, i):
-    """the square tile on the even cascades, the non-square one on the odd ones (and on a lone cascade)"""
-    return FB.tiles(n)[i % 2 if cascades > 1 else 1]
-
-
-def _seed(i):
-    return FB.SEED + 10 * i
-
-
-def _context(n, cascades, kernels, ticks_after):
-    """a context whose spectra are resident (one tick of preset records on the case's tiles) and whose records are clean; the record times
-    reach FB.T_FRAME with the last tick of the path"""
-    gen = WaveGenerator()
-    gen.map_size = n
-    gen.debug_f32 = True
-    gen.kernels = kernels
-    gen.init_gpu(max(2, cascades))
-    params = [WaveCascadeParameters(**dict(cascade_preset(i), tile_length=_tile(n, cascades, i), time=FB.T_FRAME - (1 + ticks_after) * UPDATE_DELTA))
-              for i in range(cascades)]
-    gen.update_all(UPDATE_DELTA, params)
-    assert not any(p.should_generate_spectrum for p in params)
-    return gen, params
-
-
-_REFERENCES = {}
-
-
-def _reference(n, tile, name, seed, t32, om, whitecap, grow, decay):
-    """(the twin's channels, the oracle's foam) of one injected input: computed once per FP32 time and dispersion plane and left unchanged
-    (the last four are kept: the cases are ordered by input)"""
-    key = (n, tile, name, seed, np.float32(t32).tobytes(), H.digest(om), whitecap, grow, decay)
-    if key not in _REFERENCES:
-        while len(_REFERENCES) >= 4:
-            _REFERENCES.pop(next(iter(_REFERENCES)))
-        h0 = _h0(n, tile, name, seed)
-        r = FB.twin_channels(h0, om, t32, tile, whitecap, grow, decay)
-        r.setflags(write=False)
-        _REFERENCES[key] = (r, FB.oracle_channels(h0, t32, tile, whitecap, grow, decay)[..., 6].copy())
-    return _REFERENCES[key]
-
-
-@functools.lru_cache(maxsize=4)
-def _h0(n, tile, name, seed):
-    """the input, scaled with the layer's dispersion plane at FB.T_FRAME (the scale need not follow the tick's own FP32 time)"""
-    from oracle import oracle as O
-    h0 = FB.make_input(n, name, seed, O.omega(n, tile, FB.DEPTH), FB.T_FRAME, tile)
-    h0.setflags(write=False)
-    return h0
-
-
-def run_case(name, n, cascades, path, kernels, ticks):
-    """the procedure of one case -> (kernel family of the last launch, look-ahead hits of the last tick, per cascade a dict of what was read
-    back and the references); scripts/frame_bin_margins.py prints the figures of the same runs"""
-    gen, params = _context(n, cascades, kernels, ticks)
-    try:
-        h0 = []
-        for i in range(cascades):
-            h0.append(_h0(n, _tile(n, cascades, i), name, _seed(i)))
-            # (the dispersion plane: kept on cascade 0, the layer's own handed back on the others -- the twin takes what ow_get_spectrum returns)
-            gen.debug_set_spectrum(i, h0[i], None if i == 0 else gen.get_spectrum(i)[1])
-        if path == "lookahead":
-            for _ in range(ticks - 1):
-                gen.update_all(UPDATE_DELTA, params)
-        hits = gen.lookahead_stats()[0]
-        for i in range(cascades):
-            gen.set_normal_map(i, np.zeros((n, n, 4), np.float16))
-        if path == "run":
-            gen.run(UPDATE_DELTA, params, ticks)
-        else:
-            gen.update_all(UPDATE_DELTA, params)
-        gen.sync()
-        assert not any(p.should_generate_spectrum for p in params)
-        out = []
-        for i, p in enumerate(params):
-            tile = _tile(n, cascades, i)
-            spec, om = gen.get_spectrum(i)
-            disp, norm = gen.get_maps(i)
-            r, foam = _reference(n, tile, name, _seed(i), np.float32(p.time), om, float(np.float32(p.whitecap)), float(np.float32(p.foam_grow_rate)),
-                                 float(np.float32(p.foam_decay_rate)))
-            out.append(dict(tile=tile, h0=h0[i], spectrum=spec, f32=gen.get_maps_f32(i), disp=disp, norm=norm, twin=r, oracle_foam=foam))
-        return gen.last_kernel_family(), gen.lookahead_stats()[0] - hits, out
-    finally:
-        gen.free()
 
 
 @pytest.mark.parametrize("name,n,cascades,path,kernels,family,ticks", _cases(),

@@ -7,6 +7,7 @@ import helpers as H
 from godotoceanwaves_amd import WaveCascadeParameters, WaveGenerator, _lib
 from godotoceanwaves_amd.presets import DEPTH, UPDATE_DELTA, cascade_preset
 from oracle import oracle as O
+from helpers import edge_cases as _edge_cases
 
 pytestmark = pytest.mark.gpu
 
@@ -240,11 +241,6 @@ def test_baseline_configs_through_ow_run_match_the_oracle(n, count):
         assert H.fp16_close(norm[..., :3], og.normal(i)[..., :3]) <= 1.0, i
         assert np.abs(norm[..., 3].astype(np.float64) - og.normal(i)[..., 3].view(np.float16).astype(np.float64)).max() <= H.TOL_FOAM_ABS
     print(f"{n}^2 x {count} through ow_run: worst FP32 channel error {worst:.2e}")
-
-
-def _edge_cases():
-    from edge_presets import edge_presets
-    return sorted(edge_presets().items())
 
 
 @pytest.mark.parametrize("name,preset", _edge_cases(), ids=[k for k, _ in _edge_cases()])

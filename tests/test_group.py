@@ -14,8 +14,10 @@ import helpers as H
 from godotoceanwaves_amd import WaveCascadeParameters, WaveGenerator, WaveGeneratorGroup, _lib
 from godotoceanwaves_amd.presets import UPDATE_DELTA, cascade_preset
 from oracle import oracle as O
-from test_raycast import camera_rays, cpu_raycast, harness as ray_harness  # noqa: F401
-from test_surface_query import GROW_POINTS, assert_same_records, cpu_query, cpu_sample, harness as query_harness, scales_of  # noqa: F401
+from checks import assert_same_records
+from cpu_builds import cpu_query, cpu_raycast, cpu_sample
+from cpu_builds import query_harness, raycast_harness as ray_harness  # noqa: F401 (fixtures)
+from scenes import camera_rays, GROW_POINTS, scales_of
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")

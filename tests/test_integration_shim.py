@@ -2,65 +2,12 @@
 What CAN be held: that the text is a binding of THIS header -- every [DllImport] names a function include/ocean_waves.h declares, with the
 same number of arguments and a return type of the same width, and every [StructLayout] struct lists the fields of its C struct in the same
 order with types of the same size (so that LayoutKind.Sequential reproduces the C layout) -- and that §7's index names every export."""
-import os
 import re
+from checks import c_functions, c_struct_fields, cs_struct_fields, DOC, SHIM, strip_comments
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = open(os.path.join(ROOT, "include", "ocean_waves.h")).read()
-DOC = open(os.path.join(ROOT, "INTEGRATION.md")).read()
-SHIM = DOC.split("## 2. C# (P/Invoke)")[1].split("## 3. Plain C")[0]
 
-C_SIZES = {"float": 4, "double": 8, "int32_t": 4, "uint32_t": 4, "void *": 8, "size_t": 8, "uint64_t": 8}
-CS_SIZES = {"float": 4, "double": 8, "int": 4, "uint": 4, "IntPtr": 8, "nuint": 8, "ulong": 8}
 STRUCTS = {"OwCascadeParams": "ow_cascade_params", "OwConfig": "ow_config", "OwSurfaceSample": "ow_surface_sample", "OwGroupLink": "ow_group_link",
            "OwGroupConfig": "ow_group_config"}
-
-
-def strip_comments(text):
-    return re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
-
-
-def c_functions():
-    """name -> (return type, number of parameters) for every function the header declares"""
-    out = {}
-    for m in re.finditer(r"^([A-Za-z_][A-Za-z0-9_ \*]*?)\b(ow_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", strip_comments(HEADER), flags=re.M | re.S):
-        ret, name, args = m.group(1).strip(), m.group(2), " ".join(m.group(3).split())
-        out[name] = (ret, 0 if args in ("", "void") else args.count(",") + 1)
-    return out
-
-
-def c_struct_fields(name):
-    body = re.search(r"typedef struct %s \{(.*?)\}\s*%s\s*;" % (name, name), strip_comments(HEADER), flags=re.S).group(1)
-    fields = []
-    for decl in body.split(";"):
-        decl = " ".join(decl.split())
-        if not decl:
-            continue
-        m = re.match(r"(void \*|[A-Za-z_][A-Za-z0-9_]*)\s*(.*)$", decl)
-        ctype, names = m.group(1), m.group(2)
-        for n in names.split(","):
-            d = re.match(r"\s*([A-Za-z_][A-Za-z0-9_]*)(\[(\w+)\])?\s*$", n)
-            count = d.group(3)
-            if count is not None and not count.isdigit():
-                count = re.search(r"#define %s (\d+)" % count, HEADER).group(1)
-            fields.append((d.group(1), C_SIZES[ctype] * int(count or 1)))
-    return fields
-
-
-def cs_struct_fields(name):
-    body = re.search(r"struct %s \{(.*?)\n\}" % name, strip_comments(SHIM), flags=re.S).group(1)
-    fields = []
-    for decl in body.split(";"):
-        decl = " ".join(decl.replace("public", "").split())
-        if not decl:
-            continue
-        fixed = decl.startswith("fixed ")
-        decl = decl[len("fixed "):] if fixed else decl
-        ctype, names = decl.split(" ", 1)
-        for n in names.split(","):
-            m = re.match(r"\s*([A-Za-z_][A-Za-z0-9_]*)(\[(\d+)\])?\s*$", n)
-            fields.append((m.group(1), CS_SIZES[ctype] * int(m.group(3) or 1)))
-    return fields
 
 
 def test_every_dllimport_is_a_function_of_the_header_with_the_same_shape():

@@ -23,17 +23,13 @@ from godotoceanwaves_amd import _lib, build
 from godotoceanwaves_amd.presets import UPDATE_DELTA
 from godotoceanwaves_amd.wave_generator import WaveGenerator as W
 from edge_presets import edge_presets
-from test_raycast import calm_maps
-from test_render_view import (BELOW, DEFAULTS, GPU_CAM, GROW_SIZES, HIT, INVALID, assert_same_image, camera_words, cpu_render, look,  # noqa: F401
-                              render_outputs, shade_words, uniforms_of, harness as render_harness)
-from test_surface_query import (cpu_sample, generated_maps, gpu_maps, harness as query_harness, make_gen, maps_u16, scales_of,  # noqa: F401
-                                smallest_context)
+import checks as S
+from checks import assert_same_image, check_csharp_binds, check_declared_and_bound, exported_symbols, HEADER
+from cpu_builds import build_example, build_sanitized_harness, cpu_mesh_draw as cpu_draw, cpu_render, cpu_sample, HERE, layout_probe
+from cpu_builds import mesh_harness as harness, query_harness, render_harness  # noqa: F401 (fixtures)
+from scenes import (BELOW, calm_maps, camera_words, center_of, DEFAULTS, generated_maps, GPU_CAM, gpu_maps, grid, GROW_SIZES, HIT, INVALID,
+                    look, make_gen, maps_u16, REF_BASIS, render_outputs, scales_of, smallest_context, uniforms_of)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "godotoceanwaves_amd", "csrc")
-PKG = os.path.join(ROOT, "godotoceanwaves_amd")
-HERE = os.path.dirname(os.path.abspath(__file__))
-HARNESS_SRC = os.path.join(HERE, "mesh", "mesh_harness.cpp")
 NEW_FUNCTIONS = ("ow_mesh_options_default", "ow_mesh_create", "ow_mesh_destroy", "ow_mesh_displace", "ow_mesh_get_device_ptrs", "ow_mesh_draw",
                  "ow_mesh_draw_async", "ow_mesh_stats")
 PARENT_RENDER = ("ow_render_options_default", "ow_render_view", "ow_render_view_async")
@@ -41,46 +37,13 @@ PARENT_RAYCAST = ("ow_raycast_surface", "ow_raycast_surface_async", "ow_group_ra
 NO_TRIANGLE = np.uint64(0xFFFFFFFFFFFFFFFF)
 NEAR = 0.05
 TOL = H.TOL_F32    # 1e-4: the project's FP32 parity tolerance (test_render_view.py's shading tolerance)
-REF_BASIS = (-0.996195, -0.0151344, 0.0858316, 0.0, 0.984807, 0.173648, -0.0871557, 0.172987, -0.981061)   # main.tscn:120
 
 
 # ---- meshes and the CPU build --------------------------------------------------------------------------------------------------------
 
-def grid(cells=16, cell=4.0, y=0.0):
-    """(cells + 1)^2 vertices around the origin, two triangles a cell, counter-clockwise seen from above"""
-    half = 0.5 * cells * cell
-    c = np.arange(cells + 1, dtype=np.float32) * np.float32(cell) - np.float32(half)
-    x, z = np.meshgrid(c, c)
-    v = np.stack([x.ravel(), np.full(x.size, y, np.float32), z.ravel()], axis=1).astype(np.float32)
-    r, q = np.meshgrid(np.arange(cells), np.arange(cells), indexing="ij")
-    a = (r * (cells + 1) + q).ravel()
-    b, d, e = a + 1, a + cells + 1, a + cells + 2
-    t = np.stack([np.stack([a, d, b], 1), np.stack([b, d, e], 1)], 1).reshape(-1, 3).astype(np.int32)
-    return v, t
-
-
 def clipmap():
     z = np.load(os.path.join(HERE, "golden", "clipmap_low_inner.npz"))
     return z["vertices"], z["triangles"]
-
-
-@pytest.fixture(scope="module")
-def harness(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("mesh") / "libmesh_harness.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unknown-pragmas", "-I", CSRC, HARNESS_SRC, "-o", so], check=True)
-    L = C.CDLL(so)
-    V, I, F = C.c_void_p, C.c_int, C.c_float
-    L.harness_mesh_sizes.argtypes = [V]
-    L.harness_mesh_vertices.argtypes = [V, I, I, V, V, I, V, I, F, F, V, V]
-    L.harness_mesh_draw.argtypes = [V, V, I, I, V, V, I, V, I, V, V, I, I, V, I, F, F, F, I, I, V, V, V, V, V]
-    return L
-
-
-def center_of(options, cam):
-    o = options or {}
-    if o.get("falloff_center") is not None:
-        return tuple(o["falloff_center"])
-    return (cam.position[0], cam.position[2]) if o.get("falloff") and cam is not None else None
 
 
 def cpu_vertices(L, disp, scales, local, origin, options=None, cam=None):
@@ -94,26 +57,6 @@ def cpu_vertices(L, disp, scales, local, origin, options=None, cam=None):
     out = np.zeros(len(v), W.MESH_VERTEX)
     L.harness_mesh_vertices(d.ctypes.data, d.shape[1], len(sc), sc.ctypes.data, v.ctypes.data, len(v), org.ctypes.data, int(center is not None), cx, cz,
                             cw.ctypes.data if cw is not None else None, out.ctypes.data)
-    return out
-
-
-def cpu_draw(L, disp, norm, scales, mesh, origin, cam, options=None):
-    """the CPU build's draw: dict of vertices, vis [H][W] uint64, rgba [H][W][4], rec [H][W], counters (skipped, culled, per_lane, cooperative)"""
-    o = options or {}
-    d, m = maps_u16(disp), maps_u16(norm)
-    sc = np.ascontiguousarray(scales, np.float32)
-    v = np.ascontiguousarray(mesh[0], np.float32).reshape(-1, 3)
-    t = np.ascontiguousarray(mesh[1], np.int32).reshape(-1, 3)
-    org = np.ascontiguousarray(origin, np.float32)
-    center = center_of(o, cam)
-    cx, cz = center if center is not None else (0.0, 0.0)
-    cw, sw = camera_words(cam), shade_words(o)
-    out = dict(vertices=np.zeros(len(v), W.MESH_VERTEX), vis=np.zeros((cam.height, cam.width), np.uint64),
-               rgba=np.zeros((cam.height, cam.width, 4), np.uint8), rec=np.zeros((cam.height, cam.width), W.RENDER_PIXEL), counters=np.zeros(4, np.uint32))
-    L.harness_mesh_draw(d.ctypes.data, m.ctypes.data, d.shape[1], len(sc), sc.ctypes.data, v.ctypes.data, len(v), t.ctypes.data, len(t), org.ctypes.data,
-                        cw.ctypes.data, cam.width, cam.height, sw.ctypes.data, int(center is not None), cx, cz, float(o.get("near", 0.0)),
-                        int(bool(o.get("cull_back"))), int(o.get("lane_box", 0)), out["vertices"].ctypes.data, out["vis"].ctypes.data,
-                        out["rgba"].ctypes.data, out["rec"].ctypes.data, out["counters"].ctypes.data)
     return out
 
 
@@ -150,22 +93,14 @@ def oracle_maps():
 
 # ---- 1. the ABI ----------------------------------------------------------------------------------------------------------------------
 
-HEADER = open(os.path.join(ROOT, "include", "ocean_waves.h")).read()
-
-
 def test_header_declares_the_mesh_calls_and_the_library_exports_them():
     build.build_library()
     lib = _lib.load()
-    text = re.sub(r"/\*.*?\*/", "", HEADER, flags=re.S)
-    for name in NEW_FUNCTIONS:
-        assert re.search(r"\b%s\s*\(" % name, text), name
-        assert name in _lib.SIGNATURES
-        assert getattr(lib, name)
+    text = check_declared_and_bound(lib, NEW_FUNCTIONS)
     for struct in ("ow_mesh_options", "ow_mesh_vertex"):
         assert re.search(r"typedef struct %s \{" % struct, text), struct
     assert re.search(r"#define OW_MESH_CULL_BACK %du\b" % _lib.OW_MESH_CULL_BACK, HEADER)
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = set(re.findall(r" T (ow_[a-z0-9_]+)", out))
+    exported = exported_symbols()
     assert set(NEW_FUNCTIONS) <= exported
     assert sorted(s for s in exported if "mesh" in s) == sorted(NEW_FUNCTIONS)
     assert sorted(s for s in exported if "render" in s) == sorted(PARENT_RENDER)      # the names other tests pin are the parent's
@@ -186,9 +121,7 @@ def test_mesh_structs_agree_in_c_ctypes_numpy_and_the_harness(tmp_path, harness)
     expr = ", ".join(["sizeof(%s)" % s for s in names] + ["offsetof(%s, %s)" % f for f in fields])
     src = ('#include <stdio.h>\n#include <stddef.h>\n#include "ocean_waves.h"\nint main(void){printf("%s\\n", ' % " ".join(["%zu"] * (2 + len(fields)))
            + expr + ");return 0;}\n")
-    exe = str(tmp_path / "mesh_layout")
-    subprocess.run(["gcc", "-std=c11", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-x", "c", "-", "-o", exe], input=src, text=True, check=True)
-    got = [int(v) for v in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split()]
+    got = layout_probe(tmp_path, "mesh_layout", src)
     ctypes_of = {"ow_mesh_options": _lib.ow_mesh_options, "ow_mesh_vertex": _lib.ow_mesh_vertex}
     want = [C.sizeof(ctypes_of[s]) for s in names] + [getattr(ctypes_of[s], f).offset for s, f in fields]
     assert got == want
@@ -201,10 +134,7 @@ def test_mesh_structs_agree_in_c_ctypes_numpy_and_the_harness(tmp_path, harness)
 
 
 def test_the_csharp_binding_and_the_index_show_the_mesh_calls():
-    import test_integration_shim as S
-    for name in NEW_FUNCTIONS:
-        assert re.search(r"\[DllImport\(Lib\)\]\s*public static extern \w+ %s\(" % name, S.SHIM), name
-        assert "`%s`" % name in S.DOC.split("## 7. Index")[1], name
+    check_csharp_binds(NEW_FUNCTIONS)
     for cs, c, size in (("OwMeshOptions", "ow_mesh_options", 128), ("OwMeshVertex", "ow_mesh_vertex", 48)):
         want, got = S.c_struct_fields(c), S.cs_struct_fields(cs)
         assert got == want, (cs, got, want)
@@ -562,25 +492,15 @@ def test_awkward_inputs_give_finite_consistent_pictures(harness, oracle_maps):
 def test_stand_alone_harness_runs_clean_under_the_sanitizers(tmp_path):
     """the harness as a program of its own (-DMESH_HARNESS_MAIN), built with -fsanitize=address,undefined: the calm-sea cameras and the
     awkward inputs, on maps it makes itself"""
-    exe = str(tmp_path / "mesh_harness_main")
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    "-Wno-unknown-pragmas", "-DMESH_HARNESS_MAIN", "-I", CSRC, HARNESS_SRC, "-o", exe], check=True)
+    exe = build_sanitized_harness("mesh", tmp_path)
     r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "ok (0 failures)" in r.stdout and "runtime error" not in r.stderr and "Sanitizer" not in r.stderr
 
 
-def build_example(tmp_path):
-    exe = str(tmp_path / "mesh_host")
-    subprocess.run(["gcc", "-O2", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "examples", "mesh_host.c"),
-                    "-o", exe, "-L", PKG, "-locean_waves", f"-Wl,-rpath,{PKG}", "-Wl,-rpath,/opt/rocm/lib", "-Wl,-rpath-link,/opt/rocm/lib", "-lm"],
-                   check=True)
-    return exe
-
-
 def test_example_builds_as_c99(tmp_path):
     build.build_library()
-    build_example(tmp_path)
+    build_example(tmp_path, "mesh_host")
 
 
 def test_clipmap_fixture_is_the_inner_rings():
@@ -791,7 +711,7 @@ def test_async_draw_argument_errors_write_nothing():
 @pytest.mark.gpu
 def test_the_c_example_writes_the_python_wrappers_image(tmp_path):
     """examples/mesh_host.c at 256^2, 40 x 24, five ticks, against the wrapper on the same scene and the grid the example generates"""
-    exe = build_example(tmp_path)
+    exe = build_example(tmp_path, "mesh_host")
     ppm = str(tmp_path / "mesh.ppm")
     r = subprocess.run([exe, ppm, "40", "24", "5", "256"], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stderr

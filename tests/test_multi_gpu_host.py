@@ -8,7 +8,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from test_c_consumer import PKG, ROOT
+from cpu_builds import PKG, ROOT
 
 
 def build(tmp_path):

@@ -7,9 +7,7 @@ hit on a calm sea, to an FP64 twin on a height-only swell and on the demo scene 
 bit, to its own slab, and to finite records on awkward rays.  GPU: the device records (one wave per ray) are the CPU build's bit for bit,
 the asynchronous form is ordered like ow_query_surface_async, and the group form equals a single context."""
 import ctypes as C
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -18,127 +16,28 @@ import raycast_twin as RT
 from godotoceanwaves_amd import _lib, build
 from godotoceanwaves_amd.presets import UPDATE_DELTA
 from godotoceanwaves_amd.wave_generator import WaveGenerator as W
-from test_surface_query import (cpu_query, generated_maps, gpu_maps, harness as query_harness, make_gen, maps_u16, scales_of,  # noqa: F401
-                                smallest_context)
+import checks as S
+from checks import check_csharp_binds, check_declared_and_bound, check_records, exported_symbols, HEADER
+from cpu_builds import cpu_raycast, layout_probe
+from cpu_builds import query_harness, raycast_harness as harness  # noqa: F401 (fixtures)
+from scenes import (BELOW, calm_maps, camera_rays, generated_maps, gpu_maps, HIT, INVALID, make_gen, mixed_rays, RAY_TOL as TOL, scales_of,
+                    slope_factor, smallest_context, SPACING, swell_maps, TRUNC, unit)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "godotoceanwaves_amd", "csrc")
-HERE = os.path.dirname(os.path.abspath(__file__))
 NEW_FUNCTIONS = ("ow_raycast_surface", "ow_raycast_surface_async", "ow_group_raycast_surface")
 STRUCTS = {"OwRay": "ow_ray", "OwRaycastOptions": "ow_raycast_options", "OwRaycastHit": "ow_raycast_hit"}
-HIT, BELOW, TRUNC, INVALID = _lib.OW_RAY_HIT, _lib.OW_RAY_FROM_BELOW, _lib.OW_RAY_TRUNCATED, _lib.OW_RAY_INVALID
-SPACING, TOL = 0.25, 1e-3
-
-
-# ---- the CPU build of ow_raycast.h ---------------------------------------------------------------------------------------------------
-
-@pytest.fixture(scope="module")
-def harness(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("raycast") / "libraycast_harness.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unknown-pragmas", "-I", CSRC,
-                    os.path.join(HERE, "raycast", "raycast_harness.cpp"), "-o", so], check=True)
-    L = C.CDLL(so)
-    V = C.c_void_p
-    L.harness_raycast_sizes.argtypes = [V]
-    L.harness_raycast.argtypes = [V, V, C.c_int, C.c_int, V, V, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.c_float, C.c_float,
-                                  C.c_float, C.c_float, C.c_int, V, V]
-    return L
-
-
-def cpu_raycast(L, disp, norm, scales, rays, options=None, probe=False):
-    """the records of the CPU build, the options resolved as the runtime resolves ow_raycast_options; probe: also the largest |h| each
-    ray's samples saw"""
-    o = dict(options or {})
-    d, m = maps_u16(disp), maps_u16(norm)
-    sc = np.ascontiguousarray(scales, np.float32)
-    r = np.ascontiguousarray(rays, W.RAY)
-    out = np.zeros(len(r), W.RAYCAST_HIT)
-    mh = np.zeros(len(r), np.float32)
-    center = o.get("falloff_center")
-    cx, cz = center if center is not None else (0.0, 0.0)
-    L.harness_raycast(d.ctypes.data, m.ctypes.data, d.shape[1], len(sc), sc.ctypes.data, r.ctypes.data, len(r), o.get("max_iterations", 0) or 16,
-                      o.get("query_tolerance", 0.0) or 1e-3, int(center is not None), cx, cz, o.get("water_level", 0.0),
-                      o.get("sample_spacing", 0.0) or SPACING, o.get("tolerance", 0.0) or TOL, o.get("max_samples", 0) or 4096, out.ctypes.data,
-                      mh.ctypes.data)
-    return (out, mh) if probe else out
-
-
-def unit(d):
-    d = np.asarray(d, np.float32)
-    return d / np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2])[:, None]
-
-
-def camera_rays(count, heights, angles, seed, span=200.0, max_distance=2000.0):
-    """rays from (x, y, z), y in heights, x and z in [-span, span], pointing down by a depression angle in `angles` (degrees) at a random
-    azimuth"""
-    rng = np.random.default_rng(seed)
-    h = rng.uniform(*heights, count)
-    a = np.radians(rng.uniform(*angles, count))
-    az = rng.uniform(0, 2 * np.pi, count)
-    o = np.stack([rng.uniform(-span, span, count), h, rng.uniform(-span, span, count)], axis=1)
-    return W.rays(o, np.stack([np.cos(a) * np.cos(az), -np.sin(a), np.cos(a) * np.sin(az)], axis=1), max_distance)
-
-
-def calm_maps(n=64, cascades=2):
-    return np.zeros((cascades, n, n, 4), np.uint16), np.zeros((cascades, n, n, 4), np.uint16), np.array([(1 / 50.0, 1 / 50.0, 1.0, 1.0)] * cascades,
-                                                                                                            np.float32)
-
-
-def swell_maps(n=256, tile=100.0, amplitude=1.5, wavelength=20.0):
-    """D_xz = 0, D_y = A cos(k x) at the texel centres, in FP16: a height-only swell (the query's p is q)"""
-    x = (np.arange(n) + 0.5) * tile / n
-    d = np.zeros((1, n, n, 4), np.float16)
-    d[0, :, :, 1] = (amplitude * np.cos(2 * np.pi * x / wavelength))[None, :]
-    return maps_u16(d), np.zeros((1, n, n, 4), np.uint16), np.array([(1 / tile, 1 / tile, 1.0, 1.0)], np.float32)
-
-
-def slope_factor(d, max_slope):
-    """|dg/dt| <= |d.y| + max_slope |d.xz| along a unit direction: how far g can move per metre of ray"""
-    d = np.asarray(d, np.float64)
-    return np.abs(d[:, 1]) + max_slope * np.hypot(d[:, 0], d[:, 2])
-
-
-def check_records(L, qh, d, m, sc, rays, out, options=None):
-    """what every record holds: no NaN / Inf, the embedded query is harness_query's at the hit bit for bit, the residual is g there,
-    the position is o + t d^, and zeros without a hit"""
-    o = dict(options or {})
-    for f in ("t", "position", "residual", "slab_half_height", "t_enter", "t_exit"):
-        assert np.isfinite(out[f]).all(), f
-    hit = (out["status"] & HIT) != 0
-    if hit.any():
-        pos = out["position"][hit]
-        want = cpu_query(qh, d, m, sc, pos[:, [0, 2]], max_iterations=o.get("max_iterations", 0), tolerance=o.get("query_tolerance", 0.0),
-                         falloff_center=o.get("falloff_center"))
-        assert out["query"][hit].tobytes() == want.tobytes()
-        wl = np.float32(o.get("water_level", 0.0))
-        assert np.array_equal(out["residual"][hit], pos[:, 1] - (wl + want["height"]))
-        dn = unit(rays["direction"][hit])
-        assert np.array_equal(pos, rays["origin"][hit] + out["t"][hit][:, None] * dn)
-        assert ((out["t"][hit] >= out["t_enter"][hit]) & (out["t"][hit] <= out["t_exit"][hit])).all()
-    assert not out[~hit]["query"].tobytes().strip(b"\0")
-    assert (out["t"][~hit] == 0).all() and (out["residual"][~hit] == 0).all()
-    return hit
 
 
 # ---- 1. the ABI ----------------------------------------------------------------------------------------------------------------------
 
-HEADER = open(os.path.join(ROOT, "include", "ocean_waves.h")).read()
-
-
 def test_header_declares_the_ray_cast_and_the_library_exports_it():
     build.build_library()
     lib = _lib.load()
-    text = re.sub(r"/\*.*?\*/", "", HEADER, flags=re.S)
-    for name in NEW_FUNCTIONS:
-        assert re.search(r"\b%s\s*\(" % name, text), name
-        assert name in _lib.SIGNATURES
-        assert getattr(lib, name)
+    text = check_declared_and_bound(lib, NEW_FUNCTIONS)
     for struct in STRUCTS.values():
         assert re.search(r"typedef struct %s \{" % struct, text), struct
     for bit, value in (("OW_RAY_HIT", 1), ("OW_RAY_FROM_BELOW", 2), ("OW_RAY_TRUNCATED", 4), ("OW_RAY_INVALID", 8)):
         assert re.search(r"#define %s %d\b" % (bit, value), HEADER) and getattr(_lib, bit) == value
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = set(re.findall(r" T (ow_[a-z0-9_]+)", out))
+    exported = exported_symbols()
     assert set(NEW_FUNCTIONS) <= exported
     assert len([s for s in exported if "raycast" in s]) == 3
     assert lib.ow_abi_version() == 4
@@ -152,9 +51,7 @@ def test_ray_structs_agree_in_c_ctypes_numpy_and_the_harness(tmp_path, harness):
     expr = ", ".join(["sizeof(ow_ray)", "sizeof(ow_raycast_options)", "sizeof(ow_raycast_hit)"] + ["offsetof(%s, %s)" % f for f in fields])
     src = ('#include <stdio.h>\n#include <stddef.h>\n#include "ocean_waves.h"\nint main(void){printf("%s\\n", ' % " ".join(["%zu"] * (3 + len(fields)))
            + expr + ");return 0;}\n")
-    exe = str(tmp_path / "ray_layout")
-    subprocess.run(["gcc", "-std=c11", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-x", "c", "-", "-o", exe], input=src, text=True, check=True)
-    got = [int(v) for v in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split()]
+    got = layout_probe(tmp_path, "ray_layout", src)
     types = {"ow_ray": (_lib.ow_ray, W.RAY), "ow_raycast_options": (_lib.ow_raycast_options, W.RAYCAST_OPTIONS),
              "ow_raycast_hit": (_lib.ow_raycast_hit, W.RAYCAST_HIT)}
     want_ctypes = [C.sizeof(types[s][0]) for s in ("ow_ray", "ow_raycast_options", "ow_raycast_hit")]
@@ -173,7 +70,6 @@ def test_ray_structs_agree_in_c_ctypes_numpy_and_the_harness(tmp_path, harness):
 def test_the_csharp_binding_shows_the_ray_structs_and_functions():
     """the three new [StructLayout] structs list the C fields in order with the same sizes (embedded records counted as
     their bytes), the three functions are bound, §7 names them, and the intersect_ray mapping is written down"""
-    import test_integration_shim as S
     c_sizes = dict(S.C_SIZES, ow_query_options=32, ow_surface_query=128)
     cs_sizes = dict(S.CS_SIZES, OwQueryOptions=32, OwSurfaceQuery=128)
 
@@ -197,9 +93,7 @@ def test_the_csharp_binding_shows_the_ray_structs_and_functions():
         got = fields(csbody, cs_sizes, lambda d: d.replace("public", ""))
         assert got == want, (cs, got, want)
         assert sum(s for _, s in want) == {"ow_ray": 32, "ow_raycast_options": 64, "ow_raycast_hit": 192}[c]
-    for name in NEW_FUNCTIONS:
-        assert re.search(r"\[DllImport\(Lib\)\]\s*public static extern int %s\(" % name, S.SHIM), name
-        assert "`%s`" % name in S.DOC.split("## 7. Index")[1], name
+    check_csharp_binds(NEW_FUNCTIONS, returns="int")
     assert "intersect_ray" in S.DOC and "direction = to − from" in S.DOC
 
 
@@ -354,14 +248,6 @@ def test_no_nan_or_inf_on_awkward_rays(harness, query_harness, demo_maps):
 
 
 # ---- 7-10. on the GPU ------------------------------------------------------------------------------------------------------------------
-
-def mixed_rays(seed):
-    a = camera_rays(1500, (2, 300), (2, 80), seed=seed)
-    b = camera_rays(500, (2, 20), (2, 10), seed=seed + 1)
-    c = W.rays([(0, 10, 0), (0, -3, 0), (0, 0.3, 0), (np.nan, 0, 0), (4, 50, 4)], [(1, -1, 0), (0, 1, 0), (1, 0, 0), (0, -1, 0), (0, 0, 0)],
-               [100, 100, 5000, 10, 10])
-    return np.concatenate([a, b, c])
-
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("n,ids", [(1024, [0, 1, 2]), (256, [0, 1, 2, 3]), (2048, [0])])

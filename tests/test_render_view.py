@@ -9,160 +9,39 @@ records and RGBA8 words (one lane per pixel) are the CPU build's bit for bit, th
 ow_raycast_surface_async, and examples/render_host.c writes the picture the Python wrapper returns."""
 import ctypes as C
 import math
-import os
 import re
 import subprocess
 
 import numpy as np
 import pytest
 
-import helpers as H
 import render_twin as RT
 from godotoceanwaves_amd import _lib, build
 from godotoceanwaves_amd.presets import UPDATE_DELTA
 from godotoceanwaves_amd.wave_generator import WaveGenerator as W
-from test_raycast import SPACING, TOL, calm_maps, cpu_raycast, harness as ray_harness, swell_maps  # noqa: F401
-from test_surface_query import generated_maps, gpu_maps, make_gen, maps_u16, scales_of, smallest_context
+import checks as S
+from checks import assert_same_image, check_composite, check_csharp_binds, check_declared_and_bound, compare_with_twin, exported_symbols, HEADER, SHADE_TOL
+from cpu_builds import build_example, cpu_raycast, cpu_render, layout_probe
+from cpu_builds import raycast_harness as ray_harness, render_harness as harness  # noqa: F401 (fixtures)
+from scenes import (BELOW, calm_maps, DEFAULTS, generated_maps, GPU_CAM, gpu_maps, GROW_SIZES, HIT, INVALID, look, make_gen, pixel_rays,
+                    ray_options, RAY_TOL as TOL, render_outputs, scales_of, smallest_context, SUN_BEHIND, SUN_LOW, swell_maps, TRUNC,
+                    uniforms_of)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "godotoceanwaves_amd", "csrc")
-PKG = os.path.join(ROOT, "godotoceanwaves_amd")
-HERE = os.path.dirname(os.path.abspath(__file__))
 NEW_FUNCTIONS = ("ow_render_options_default", "ow_render_view", "ow_render_view_async")
 STRUCTS = {"OwCamera": "ow_camera", "OwRenderOptions": "ow_render_options", "OwRenderPixel": "ow_render_pixel"}
-HIT, BELOW, TRUNC, INVALID = _lib.OW_RAY_HIT, _lib.OW_RAY_FROM_BELOW, _lib.OW_RAY_TRUNCATED, _lib.OW_RAY_INVALID
-SHADE_KEYS = ("water_color", "foam_color", "roughness", "normal_strength", "light_direction", "light_color", "ambient_color", "sky_color")
 # ow_render_options_default's values (the reference scene's material and sun; ambient and sky are the library's)
-DEFAULTS = dict(water_color=(0.0100228256, 0.019606648, 0.0272117816), foam_color=(0.491905034, 0.406448305, 0.34239164), roughness=0.65,
-                normal_strength=1.0, light_direction=(0.321197, 0.18296, 0.929171), light_color=(1.0, 1.0, 1.0),
-                ambient_color=(0.05, 0.08, 0.10), sky_color=(0.25, 0.40, 0.60))
-SUN_LOW = (0.321197, 0.18296, 0.929171)      # main.tscn:113: 10.5 degrees above the horizon, ahead of a camera that looks towards +z
-SUN_BEHIND = (0.2, 0.5, -0.84)               # behind that camera
-
-
-# ---- the CPU build of ow_render.h / ow_shading.h -------------------------------------------------------------------------------------
-
-@pytest.fixture(scope="module")
-def harness(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("render") / "librender_harness.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unknown-pragmas", "-I", CSRC,
-                    os.path.join(HERE, "render", "render_harness.cpp"), "-o", so], check=True)
-    L = C.CDLL(so)
-    V = C.c_void_p
-    L.harness_render_sizes.argtypes = [V]
-    L.harness_log.argtypes = [V, C.c_int, V]
-    L.harness_pixel_rays.argtypes = [V, C.c_int, C.c_int, V]
-    L.harness_render.argtypes = [V, V, C.c_int, C.c_int, V, V, C.c_int, C.c_int, V, C.c_int, C.c_float, C.c_int, C.c_float, C.c_float, C.c_float,
-                                 C.c_float, C.c_float, C.c_int, V, V]
-    return L
-
-
-def look(position, yaw_deg, pitch_deg, fov=75.0, width=20, height=12, max_distance=4000.0):
-    """an ow_camera at `position` looking along yaw (0 = +z, towards +x as it grows) and pitch (degrees, negative = down), +Y up: the
-    basis columns are right, up and back, written as Godot's rows"""
-    yaw, pitch = math.radians(yaw_deg), math.radians(pitch_deg)
-    f = np.array([math.sin(yaw) * math.cos(pitch), math.sin(pitch), math.cos(yaw) * math.cos(pitch)])
-    right = np.cross(f, [0.0, 1.0, 0.0])
-    right /= np.linalg.norm(right)
-    up = np.cross(right, f)
-    return W.camera(position, np.stack([right, up, -f], axis=1), fov, width, height, max_distance)
-
-
-def camera_words(cam):
-    """the 15 floats the runtime resolves from an ow_camera: position, basis, tan(fov / 2) in FP64 narrowed, aspect, max_distance"""
-    th = np.float32(math.tan(float(cam.fov_y_degrees) * (3.14159265358979323846 / 360.0)))
-    aspect = np.float32(cam.width) / np.float32(cam.height)
-    return np.array(list(cam.position) + list(cam.basis) + [th, aspect, cam.max_distance], np.float32)
-
-
-def shade_words(options):
-    """the 22 floats of ow::ShadeParams as the runtime resolves them from ow_render_options (the uniform-only constants in FP64)"""
-    o = dict(DEFAULTS, **{k: v for k, v in (options or {}).items() if k in SHADE_KEYS})
-    f32 = lambda v: [float(np.float32(x)) for x in v]   # noqa: E731
-    r = float(np.float32(o["roughness"]))
-    lx, ly, lz = f32(o["light_direction"])
-    ln = math.sqrt(lx * lx + ly * ly + lz * lz)
-    words = f32(o["water_color"]) + f32(o["foam_color"]) + [r, o["normal_strength"], 5.0 * math.exp(-2.69 * r), 1.0 + 22.7 * math.pow(r, 1.5)]
-    words += [lx / ln, ly / ln, lz / ln] + f32(o["light_color"]) + f32(o["ambient_color"]) + f32(o["sky_color"])
-    return np.array(words, np.float32)
-
-
-def uniforms_of(options):
-    """what the twin is given: the FP32 values of the options"""
-    o = dict(DEFAULTS, **{k: v for k, v in (options or {}).items() if k in SHADE_KEYS})
-    return {k: (np.float32(v).astype(np.float64) if np.ndim(v) == 0 else np.asarray(v, np.float32).astype(np.float64)) for k, v in o.items()}
-
-
-def ray_options(options, cam):
-    """the ray cast's share of render options, as W.render_options splits them ("falloff": True = around the camera)"""
-    o = {k: v for k, v in (options or {}).items() if k not in SHADE_KEYS and k != "falloff"}
-    if (options or {}).get("falloff") and o.get("falloff_center") is None:
-        o["falloff_center"] = (cam.position[0], cam.position[2])
-    return o
-
-
-def cpu_render(L, disp, norm, scales, cam, options=None):
-    """(rgba [H][W][4], records [H][W]) of the CPU build, the options resolved as the runtime resolves them"""
-    o = ray_options(options, cam)
-    d, m = maps_u16(disp), maps_u16(norm)
-    sc = np.ascontiguousarray(scales, np.float32)
-    cw, sw = camera_words(cam), shade_words(options)
-    rgba = np.zeros((cam.height, cam.width, 4), np.uint8)
-    rec = np.zeros((cam.height, cam.width), W.RENDER_PIXEL)
-    center = o.get("falloff_center")
-    cx, cz = center if center is not None else (0.0, 0.0)
-    L.harness_render(d.ctypes.data, m.ctypes.data, d.shape[1], len(sc), sc.ctypes.data, cw.ctypes.data, cam.width, cam.height, sw.ctypes.data,
-                     o.get("max_iterations", 0) or 16, o.get("query_tolerance", 0.0) or 1e-3, int(center is not None), cx, cz,
-                     o.get("water_level", 0.0), o.get("sample_spacing", 0.0) or SPACING, o.get("tolerance", 0.0) or TOL,
-                     o.get("max_samples", 0) or 4096, rgba.ctypes.data, rec.ctypes.data)
-    return rgba, rec
-
-
-def pixel_rays(L, cam):
-    cw = camera_words(cam)
-    rays = np.zeros(cam.width * cam.height, W.RAY)
-    L.harness_pixel_rays(cw.ctypes.data, cam.width, cam.height, rays.ctypes.data)
-    return rays
-
-
-def check_composite(rgba, rec, options=None):
-    """what every image holds: finite records, sky without a hit, the composite and the RGBA8 rule"""
-    for f in W.RENDER_PIXEL.names:
-        if f not in ("status", "reserved"):
-            assert np.isfinite(rec[f]).all(), f
-    hit = (rec["status"] & HIT) != 0
-    sky = np.asarray(dict(DEFAULTS, **(options or {}))["sky_color"], np.float32)
-    amb = np.asarray(dict(DEFAULTS, **(options or {}))["ambient_color"], np.float32)
-    assert (rec["color"][~hit] == sky).all()
-    zeroed = rec[~hit].copy()
-    zeroed["status"] = 0
-    zeroed["color"] = 0
-    assert not zeroed.tobytes().strip(b"\0")
-    want = rec["albedo"] * (rec["diffuse"] + amb) + rec["specular"][..., None]
-    assert np.array_equal(rec["color"][hit], want[hit])
-    assert np.array_equal(rgba, RT.rgba8(rec["color"]))
-    assert not rec["reserved"].any()
-    return hit
 
 
 # ---- 1. the ABI ----------------------------------------------------------------------------------------------------------------------
 
-HEADER = open(os.path.join(ROOT, "include", "ocean_waves.h")).read()
-
-
 def test_header_declares_the_render_calls_and_the_library_exports_them():
     build.build_library()
     lib = _lib.load()
-    text = re.sub(r"/\*.*?\*/", "", HEADER, flags=re.S)
-    for name in NEW_FUNCTIONS:
-        assert re.search(r"\b%s\s*\(" % name, text), name
-        assert name in _lib.SIGNATURES
-        assert getattr(lib, name)
+    text = check_declared_and_bound(lib, NEW_FUNCTIONS)
     for struct in STRUCTS.values():
         assert re.search(r"typedef struct %s \{" % struct, text), struct
     assert re.search(r"#define OW_RENDER_MAX_SIDE %d\b" % _lib.OW_RENDER_MAX_SIDE, HEADER)
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = set(re.findall(r" T (ow_[a-z0-9_]+)", out))
+    exported = exported_symbols()
     assert set(NEW_FUNCTIONS) <= exported
     assert sorted(s for s in exported if "render" in s) == sorted(NEW_FUNCTIONS)      # no group form
     assert "no group form" in HEADER.split("ow_render_options_default")[0].split("Camera views of the water")[1]
@@ -184,9 +63,7 @@ def test_render_structs_agree_in_c_ctypes_numpy_and_the_harness(tmp_path, harnes
     expr = ", ".join(["sizeof(%s)" % s for s in names] + ["offsetof(%s, %s)" % f for f in fields])
     src = ('#include <stdio.h>\n#include <stddef.h>\n#include "ocean_waves.h"\nint main(void){printf("%s\\n", ' % " ".join(["%zu"] * (3 + len(fields)))
            + expr + ");return 0;}\n")
-    exe = str(tmp_path / "render_layout")
-    subprocess.run(["gcc", "-std=c11", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-x", "c", "-", "-o", exe], input=src, text=True, check=True)
-    got = [int(v) for v in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split()]
+    got = layout_probe(tmp_path, "render_layout", src)
     ctypes_of = {"ow_camera": _lib.ow_camera, "ow_render_options": _lib.ow_render_options, "ow_render_pixel": _lib.ow_render_pixel}
     want = [C.sizeof(ctypes_of[s]) for s in names] + [getattr(ctypes_of[s], f).offset for s, f in fields]
     assert got == want
@@ -201,7 +78,6 @@ def test_render_structs_agree_in_c_ctypes_numpy_and_the_harness(tmp_path, harnes
 def test_the_csharp_binding_shows_the_render_structs_and_functions():
     """the three new [StructLayout] structs list the C fields in order with the same sizes (an embedded record counted
     as its bytes), the calls are bound, and §7 names them"""
-    import test_integration_shim as S
     c_sizes = dict(S.C_SIZES, ow_raycast_options=64)
     cs_sizes = dict(S.CS_SIZES, OwRaycastOptions=64)
 
@@ -225,9 +101,7 @@ def test_the_csharp_binding_shows_the_render_structs_and_functions():
         got = fields(csbody, cs_sizes, lambda d: d.replace("public", ""))
         assert got == want, (cs, got, want)
         assert sum(s for _, s in want) == {"ow_camera": 80, "ow_render_options": 192, "ow_render_pixel": 128}[c]
-    for name in NEW_FUNCTIONS:
-        assert re.search(r"\[DllImport\(Lib\)\]\s*public static extern \w+ %s\(" % name, S.SHIM), name
-        assert "`%s`" % name in S.DOC.split("## 7. Index")[1], name
+    check_csharp_binds(NEW_FUNCTIONS)
 
 
 # ---- 2. argument checks without a device ---------------------------------------------------------------------------------------------
@@ -416,26 +290,6 @@ def test_pixels_are_the_ray_casts(harness, ray_harness, demo_maps, maps, view):
 
 # ---- 7. the shading against the FP64 twin -----------------------------------------------------------------------------------------------
 
-SHADE_TOL = H.TOL_F32   # 1e-4: the project's FP32 parity tolerance
-
-
-def compare_with_twin(rec, cam, options):
-    """every hit pixel against the twin fed the record's own inputs; absolute for the terms bounded by 1, relative to max(1, |twin|) for
-    diffuse and specular.  Returns the largest error per term."""
-    hit = (rec["status"] & HIT) != 0
-    r = rec[hit]
-    twin = RT.shade(r["gradient_fragment"], r["foam_fragment"], r["wave_height"], r["position"], list(cam.position), list(cam.basis),
-                    uniforms_of(options))
-    worst = {}
-    for k in ("foam_factor", "albedo", "normal", "fresnel", "roughness", "color", "diffuse", "specular"):
-        assert np.isfinite(twin[k]).all(), k
-        err = np.abs(r[k].astype(np.float64) - twin[k])
-        if k in ("diffuse", "specular"):
-            err = err / np.maximum(1.0, np.abs(twin[k]))
-        worst[k] = float(err.max())
-    return worst, int(hit.sum())
-
-
 @pytest.mark.parametrize("sun", [SUN_LOW, SUN_BEHIND], ids=["low_sun", "sun_behind"])
 @pytest.mark.parametrize("normal_strength", [0.0, 1.0])
 @pytest.mark.parametrize("roughness", [0.0, 0.4, 0.65, 1.0])
@@ -512,30 +366,12 @@ def test_no_nan_or_inf_on_awkward_inputs(harness, demo_maps):
 
 # ---- 9. the C example -----------------------------------------------------------------------------------------------------------------
 
-def build_example(tmp_path):
-    exe = str(tmp_path / "render_host")
-    subprocess.run(["gcc", "-O2", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "examples", "render_host.c"),
-                    "-o", exe, "-L", PKG, "-locean_waves", f"-Wl,-rpath,{PKG}", "-Wl,-rpath,/opt/rocm/lib", "-Wl,-rpath-link,/opt/rocm/lib", "-lm"],
-                   check=True)
-    return exe
-
-
 def test_example_builds_as_c99(tmp_path):
     build.build_library()
-    build_example(tmp_path)
+    build_example(tmp_path, "render_host")
 
 
 # ---- 10-13. on the GPU ------------------------------------------------------------------------------------------------------------------
-
-GPU_CAM = dict(position=(0.0, 10.0, -25.0), yaw_deg=5.0, pitch_deg=-10.0)
-
-
-def assert_same_image(got, want, what):
-    (g_rgba, g_rec), (w_rgba, w_rec) = got, want
-    for f in W.RENDER_PIXEL.names:
-        assert g_rec[f].tobytes() == w_rec[f].tobytes(), (what, f)
-    assert g_rgba.tobytes() == w_rgba.tobytes(), what
-
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("n,ids", [(256, [0, 1, 2, 3]), (1024, [0, 1, 2]), (2048, [0])])
@@ -667,7 +503,7 @@ def test_async_render_argument_errors():
 def test_the_c_example_writes_the_python_wrappers_image(tmp_path):
     """examples/render_host.c at 256^2, 40 x 24, five ticks, against the wrapper on the same scene: the reference camera (main.tscn:120),
     the default options, the falloff around the camera"""
-    exe = build_example(tmp_path)
+    exe = build_example(tmp_path, "render_host")
     ppm = str(tmp_path / "water.ppm")
     r = subprocess.run([exe, ppm, "40", "24", "5", "256"], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stderr
@@ -687,20 +523,6 @@ def test_the_c_example_writes_the_python_wrappers_image(tmp_path):
 
 
 # ---- 14. the grow-only pixel scratch -------------------------------------------------------------------------------------------------------
-
-GROW_SIZES = ((8, 8), (40, 24), (8, 8))   # the scratch is sized exactly: the second image replaces both blocks, the third fits what is there
-
-
-def render_outputs(gen, cam, sc, rgba=True, pixels=True):
-    """ow_render_view with either output left out (the wrapper always asks for the RGBA words)"""
-    sc = np.ascontiguousarray(sc, np.float32).reshape(-1, 4)
-    o = gen.render_options(None, cam)
-    img = np.zeros((cam.height, cam.width, 4), np.uint8) if rgba else None
-    rec = np.zeros((cam.height, cam.width), W.RENDER_PIXEL) if pixels else None
-    _lib.check(gen._lib.ow_render_view(gen.context, C.byref(cam), sc.ctypes.data, len(sc), C.byref(o) if o is not None else None,
-                                       img.ctypes.data if rgba else None, rec.ctypes.data if pixels else None))
-    return img, rec
-
 
 @pytest.mark.gpu
 def test_pixel_scratch_grows_and_stays_with_either_output(harness):

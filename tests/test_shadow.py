@@ -22,20 +22,16 @@ import shadow_twin as ST
 from godotoceanwaves_amd import _lib, build
 from godotoceanwaves_amd.presets import UPDATE_DELTA
 from godotoceanwaves_amd.wave_generator import WaveGenerator as W
-from test_mesh_draw import cpu_draw as cpu_mesh_draw, grid, harness as mesh_harness  # noqa: F401
-from test_render_view import HIT, look
-from test_solid_draw import (CRATE_CAM, CRATE_SHAPE, SUN, box, cpu_draw as cpu_solid_draw, cube, eight_crates, harness as solid_harness,  # noqa: F401
-                             pose_transforms, transform, transforms, twin_scene)
-from test_environment import harness as env_harness  # noqa: F401
-from test_sky_light import harness as sky_harness  # noqa: F401
-from test_spray_draw import harness as billboard_harness, level_camera  # noqa: F401
-from test_surface_query import gpu_maps, make_gen, scales_of
+import checks as S
+from checks import check_declared_and_bound, exported_symbols, HEADER, same_records
+from cpu_builds import (build_example, build_sanitized_harness, cpu_billboard_draw, cpu_environment, cpu_mesh_draw, cpu_present, cpu_solid_draw,
+                        CpuPyramid, CSRC, layout_probe, ROOT, twin_scene)
+from cpu_builds import billboard_harness, env_harness, mesh_harness, shadow_harness as harness, sky_harness, solid_harness  # noqa: F401 (fixtures)
+from scenes import (advance, bare_context, box, buffers_to_host, CRATE_CAM, CRATE_SHAPE, cube, device_buffers, device_frame, eight_crates,
+                    example_crates, example_panorama, example_textures, floating_scene, FRAME_CAM, FRAME_ENV, FRAME_PRESENT, frame_scene,
+                    FRAME_SHAPE, FRAME_WATER, gpu_maps, gpu_material, gpu_radiance, gradient_panorama, grid, HIT, level_camera, look,
+                    make_gen, material, pose_transforms, records_of, REF_BASIS, scales_of, sky_of, SUN, transform, transforms)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "godotoceanwaves_amd", "csrc")
-PKG = os.path.join(ROOT, "godotoceanwaves_amd")
-HERE = os.path.dirname(os.path.abspath(__file__))
-HARNESS_SRC = os.path.join(HERE, "shadow", "shadow_harness.cpp")
 MARGINS = os.path.join(ROOT, "profiles", "shadow_margins.txt")
 NEW_FUNCTIONS = ("ow_shadow_frame_default", "ow_shadow_options_default", "ow_shadow_map_create", "ow_shadow_map_destroy", "ow_shadow_map_begin",
                  "ow_shadow_map_cast", "ow_shadow_map_cast_instances", "ow_shadow_map_read", "ow_shadow_apply", "ow_shadow_apply_async", "ow_shadow_stats")
@@ -50,20 +46,6 @@ CASE = np.dtype([("size", np.int32), ("num_vertices", np.int32), ("num_triangles
 
 
 # ---- the CPU build ---------------------------------------------------------------------------------------------------------------------------
-
-@pytest.fixture(scope="module")
-def harness(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("shadow") / "libshadow_harness.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unknown-pragmas", "-I", CSRC, HARNESS_SRC, "-o", so], check=True)
-    L = C.CDLL(so)
-    V, I = C.c_void_p, C.c_int
-    L.harness_shadow_sizes.argtypes = [V]
-    L.harness_shadow_frame.argtypes = [V, I, V]
-    L.harness_shadow_clear.argtypes = [I, V, V]
-    L.harness_shadow_cast.argtypes = [V, I, V, I, V, I, V, I, V, I, V, V, V]
-    L.harness_shadow_apply.argtypes = [V, I, V, I, V, I, I, V, V, V]
-    return L
-
 
 def frame_of(frame=None):
     return W.shadow_frame(frame)
@@ -164,19 +146,11 @@ MIXED_FRAME = dict(half_extent=20.0, depth_range=60.0, center=(0.5, 1.0, -0.25))
 
 # ---- 1. the interface and the documents --------------------------------------------------------------------------------------------------
 
-HEADER = open(os.path.join(ROOT, "include", "ocean_waves.h")).read()
-
-
 def test_header_declares_the_new_calls_and_the_library_exports_them():
     build.build_library()
     lib = _lib.load()
-    text = re.sub(r"/\*.*?\*/", "", HEADER, flags=re.S)
-    for name in NEW_FUNCTIONS:
-        assert re.search(r"\b%s\s*\(" % name, text), name
-        assert name in _lib.SIGNATURES
-        assert getattr(lib, name)
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = set(re.findall(r" T (ow_[a-z0-9_]+)", out))
+    text = check_declared_and_bound(lib, NEW_FUNCTIONS)
+    exported = exported_symbols()
     assert sorted(s for s in exported if "shadow" in s) == sorted(NEW_FUNCTIONS)      # no group form
     assert lib.ow_abi_version() == 4 and re.search(r"#define OW_ABI_VERSION 4\b", HEADER)
     for define, value in (("OW_RAY_SHADOWED", 128), ("OW_SHADOW_MIN_SIZE", 8), ("OW_SHADOW_MAX_SIZE", 8192)):
@@ -210,9 +184,7 @@ def test_structs_agree_in_c_ctypes_and_the_harness(tmp_path, harness):
         expr = ", ".join(["sizeof(%s)" % name] + ["offsetof(%s, %s)" % (name, f) for f in fields])
         src = ('#include <stdio.h>\n#include <stddef.h>\n#include "ocean_waves.h"\nint main(void){printf("%s\\n", ' % " ".join(["%zu"] * (1 + len(fields)))
                + expr + ");return 0;}\n")
-        exe = str(tmp_path / (name + "_layout"))
-        subprocess.run(["gcc", "-std=c11", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-x", "c", "-", "-o", exe], input=src, text=True, check=True)
-        vals = [int(v) for v in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split()]
+        vals = layout_probe(tmp_path, (name + "_layout"), src)
         assert vals == [C.sizeof(S)] + [getattr(S, f).offset for f in fields], name
         got[name] = dict(zip(["size"] + fields, vals))
     f, o = got["ow_shadow_frame"], got["ow_shadow_options"]
@@ -225,7 +197,6 @@ def test_structs_agree_in_c_ctypes_and_the_harness(tmp_path, harness):
 
 
 def test_the_documents_name_the_new_calls():
-    import test_integration_shim as S
     for name in NEW_FUNCTIONS:
         assert "`%s`" % name in S.DOC.split("## 7. Index")[1], name
     for name in NEW_FUNCTIONS[2:]:
@@ -241,17 +212,9 @@ def test_the_documents_name_the_new_calls():
         assert os.path.exists(os.path.join(ROOT, path)), path
 
 
-def build_example(tmp_path):
-    exe = str(tmp_path / "shadow_host")
-    subprocess.run(["gcc", "-O2", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "examples", "shadow_host.c"),
-                    "-o", exe, "-L", PKG, "-locean_waves", "-L", "/opt/rocm/lib", "-lamdhip64", f"-Wl,-rpath,{PKG}", "-Wl,-rpath,/opt/rocm/lib", "-lm"],
-                   check=True)
-    return exe
-
-
 def test_example_builds_as_c99(tmp_path):
     build.build_library()
-    build_example(tmp_path)
+    build_example(tmp_path, "shadow_host")
 
 
 # ---- 2. argument errors without a device ---------------------------------------------------------------------------------------------------
@@ -724,9 +687,7 @@ def write_case(path, c, rec, size, frame, opts, casts=1):
 def test_stand_alone_harness_runs_clean_under_the_sanitizers(tmp_path, harness, mesh_harness, solid_harness):
     """the harness as a program of its own (-DSHADOW_HARNESS_MAIN), built with -fsanitize=address,undefined, on the twin's scene, 70 mixed
     cubes (cast in three spans) and every awkward case: what it writes is the shared library's, byte for byte"""
-    exe = str(tmp_path / "shadow_harness_main")
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    "-Wno-unknown-pragmas", "-DSHADOW_HARNESS_MAIN", "-I", CSRC, HARNESS_SRC, "-o", exe], check=True)
+    exe = build_sanitized_harness("shadow", tmp_path)
     shape, tf, rec = shadow_twin_scene(mesh_harness, solid_harness)
     cases = {"twin": (dict(shape=shape, tf=tf), rec, TWIN_SIZE, TWIN_FRAME, TWIN_OPTS, 1),
              "70 mixed cubes": (dict(shape=cube(), tf=shadow_cubes(70)), awkward_records(), 257, MIXED_FRAME, dict(filter_taps=9, receive_water=True), 3)}
@@ -745,11 +706,6 @@ def test_stand_alone_harness_runs_clean_under_the_sanitizers(tmp_path, harness, 
 
 
 # ---- 11-16. on the GPU -------------------------------------------------------------------------------------------------------------------------
-
-def bare_context():
-    """the smallest context: no map is read"""
-    return make_gen(128, [0, 1])[0]
-
 
 def gpu_cast(gen, frame, size, shape, spans):
     """begin, one ow_shadow_map_cast_instances per span, the map and the counters read back"""
@@ -844,7 +800,6 @@ def test_gpu_pass_is_the_cpu_builds_bit_for_bit(harness, width, height):
 def test_gpu_cast_from_a_body_sets_resident_poses(harness):
     """ow_shadow_map_cast reads the poses and the fault flags on the device: the CPU build on the pose records read back, and
     ow_shadow_map_cast_instances of the same poses, byte for byte; body 5 faulted in its first substep: skipped and counted"""
-    from test_solid_draw import floating_scene
     gen, params, sc, bodies, spray = floating_scene(broken=5)
     shape = box(CRATE_SHAPE)
     solid = gen.solid_create(*shape)
@@ -888,11 +843,6 @@ def test_gpu_whole_frame_is_the_cpu_chain_bit_for_bit(harness, mesh_harness, sol
     ow_shadow_apply_async -> ow_radiance_light_apply_async -> ow_environment_apply_async -> ow_billboard_draw_async -> ow_present_async on
     device buffers, one read-back, against the CPU builds chained in the same order; no call synchronised"""
     import torch
-    from test_environment import (FRAME_CAM, FRAME_ENV, FRAME_PRESENT, FRAME_SHAPE, FRAME_WATER, cpu_environment, cpu_present, device_frame, frame_scene,
-                                  gradient_panorama, records_of, same_records, sky_of)
-    from test_sky_light import CpuPyramid, gpu_radiance
-    from test_solid_draw import gpu_material
-    from test_spray_draw import cpu_draw as cpu_billboard_draw, material
     gen, params, sc, bodies, spray = frame_scene()
     cam = look(**FRAME_CAM)
     mat = material()
@@ -959,8 +909,6 @@ def _order_case(stream=None, torch_stream=None):
     """ticks and steps, the draws, the cast and the pass, then more ticks and steps with no host synchronisation anywhere, against a context
     that stopped after the first half and ran the synchronous forms: the cast saw the poses of exactly its point of the stream"""
     import torch
-    from test_solid_draw import advance, floating_scene
-    from test_spray_draw import buffers_to_host, device_buffers
     a, pa, sc, ba, sa = floating_scene(stream=stream, steps=2)
     b, pb, _, bb, sb = floating_scene(steps=2)
     cam = look(**dict(CRATE_CAM, width=96, height=64))
@@ -1035,7 +983,6 @@ def test_map_scratch_grows_once_and_stays_and_errors_write_nothing(harness):
     """the first cast allocates without synchronising, the second allocates nothing, a larger one regrows the block behind one
     synchronisation; then the refusals: foreign and orphaned handles, a map without a frame, bad pointers -- the map keeps its bytes"""
     import torch
-    from test_spray_draw import device_buffers
     gen, other = bare_context(), bare_context()
     st, hull = eight_crates()
     bodies, foreign_bodies = gen.bodies_create(st, hull), other.bodies_create(st, hull)     # never stepped: the poses of ow_bodies_create
@@ -1109,11 +1056,7 @@ def test_map_scratch_grows_once_and_stays_and_errors_write_nothing(harness):
 @pytest.mark.gpu
 def test_the_c_example_writes_the_python_wrappers_image(tmp_path):
     """examples/shadow_host.c at 256^2, a 48 x 32 PPM of 96 x 64 records, 40 steps, 4096 particles, a 512^2 shadow map, against the wrapper"""
-    from test_environment import example_panorama
-    from test_mesh_draw import REF_BASIS
-    from test_solid_draw import example_crates
-    from test_spray_draw import example_textures
-    exe = build_example(tmp_path)
+    exe = build_example(tmp_path, "shadow_host")
     ppm = str(tmp_path / "shadow.ppm")
     r = subprocess.run([exe, ppm, "48", "32", "40", "256", "4096", "2", "512"], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stderr

@@ -26,34 +26,23 @@ import sky_light_twin as ST
 from godotoceanwaves_amd import _lib, build
 from godotoceanwaves_amd.presets import UPDATE_DELTA
 from godotoceanwaves_amd.wave_generator import WaveGenerator as W
-from test_environment import (FRAME_CAM, FRAME_ENV, FRAME_PRESENT, FRAME_SHAPE, FRAME_WATER, bare_context, cpu_environment, cpu_present, device_frame,
-                              example_panorama, f32_options, frame_scene, gpu_sky, gradient_panorama, harness as env_harness, pictures, records_of, rel,  # noqa: F401
-                              same_records, sky_lookup, sky_of, synthetic_records)
-from test_mesh_draw import REF_BASIS, cpu_draw as cpu_mesh_draw, grid, harness as mesh_harness  # noqa: F401
-from test_render_view import camera_words, look
-from test_solid_draw import (CRATE_CAM, CRATE_SHAPE, box, cpu_draw as cpu_solid_draw, example_crates, gpu_material, harness as solid_harness,  # noqa: F401
-                             pose_transforms, transforms)
-from test_spray_draw import cpu_draw as cpu_billboard_draw, example_textures, harness as billboard_harness, level_camera, material  # noqa: F401
-from test_surface_query import gpu_maps, make_gen, scales_of
+import checks as S
+from checks import check_declared_and_bound, exported_symbols, HEADER, same_records
+from cpu_builds import (cpu_billboard_draw, cpu_environment, cpu_mesh_draw, cpu_present, cpu_solid_draw, CpuPyramid, CSRC, LIGHT_CASE,
+                        light_case, LIGHT_DEFAULTS, RADIANCE_CASE, radiance_case, RADIANCE_DEFAULTS, ROOT, sky_lookup)
+from cpu_builds import billboard_harness, env_harness, mesh_harness, pictures, sky_harness as harness, solid_harness  # noqa: F401 (fixtures)
+from scenes import (bare_context, box, camera_words, CRATE_CAM, CRATE_SHAPE, device_frame, example_crates, example_panorama,
+                    example_textures, f32_options, FRAME_CAM, FRAME_ENV, FRAME_PRESENT, frame_scene, FRAME_SHAPE, FRAME_WATER, gpu_maps,
+                    gpu_material, gpu_radiance, gradient_panorama, grid, level_camera, look, make_gen, material, pose_transforms, records_of,
+                    REF_BASIS, rel, scales_of, sky_of, synthetic_records, transforms)
+from cpu_builds import build_example, build_sanitized_harness, layout_probe
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "godotoceanwaves_amd", "csrc")
-PKG = os.path.join(ROOT, "godotoceanwaves_amd")
-HERE = os.path.dirname(os.path.abspath(__file__))
-HARNESS_SRC = os.path.join(HERE, "sky_light", "sky_light_harness.cpp")
 MARGINS = os.path.join(ROOT, "profiles", "sky_light_margins.txt")
 # The exports are named after the handle: tests/test_environment.py pins the set of exports that begin with ow_sky, so none is added there.
 NEW_FUNCTIONS = ("ow_radiance_options_default", "ow_radiance_light_options_default", "ow_radiance_create", "ow_radiance_destroy", "ow_radiance_level",
                  "ow_radiance_light_apply", "ow_radiance_light_apply_async")
 TOL = H.TOL_F32     # 1e-4: the project's FP32 parity tolerance
 HIT, BELOW, SOLID, ENV, LIT = _lib.OW_RAY_HIT, _lib.OW_RAY_FROM_BELOW, _lib.OW_RAY_SOLID, _lib.OW_RAY_ENVIRONMENT, _lib.OW_RAY_SKY_LIT
-RADIANCE_DEFAULTS = dict(levels=6, samples=64, base_width=1024)
-LIGHT_DEFAULTS = dict(ambient_energy=1.0, reflection_energy=1.0, specular=0.5)
-RADIANCE_CASE = np.dtype([("sky_width", np.int32), ("sky_height", np.int32), ("sky_srgb", np.int32), ("energy", np.float32), ("levels", np.int32),
-                          ("samples", np.int32), ("base_width", np.int32)])
-LIGHT_CASE = np.dtype([("width", np.int32), ("height", np.int32), ("cam", np.float32, 15), ("ambient_energy", np.float32),
-                       ("reflection_energy", np.float32), ("specular", np.float32)])
-STAGES = (("view", 0, 3), ("reflect", 3, 6), ("lod", 6, 7), ("radiance", 7, 10), ("env", 10, 12), ("irradiance", 12, 15), ("ambient", 15, 18), ("spec", 18, 21))
 
 
 # ---- panoramas, records and the CPU build -------------------------------------------------------------------------------------------------
@@ -70,88 +59,6 @@ def constant_panorama(w, h, rgb=(90, 140, 200)):
     img[..., :3] = rgb
     img[..., 3] = 255
     return img
-
-
-@pytest.fixture(scope="module")
-def harness(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("sky_light") / "libsky_light_harness.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unknown-pragmas", "-I", CSRC, HARNESS_SRC, "-o", so], check=True)
-    L = C.CDLL(so)
-    V, I = C.c_void_p, C.c_int
-    L.harness_sky_light_sizes.argtypes = [V]
-    L.harness_radiance_plan.argtypes = [I, I, I, I, V]
-    L.harness_radiance_dir_table.argtypes = [I, I, V]
-    L.harness_radiance_sample_table.argtypes = [C.c_double, I, V]
-    L.harness_radiance_new.argtypes = [V, V]
-    L.harness_radiance_new.restype = V
-    L.harness_radiance_free.argtypes = [V]
-    L.harness_radiance_get.argtypes = [V, I, I, V, V]
-    L.harness_radiance_lookup.argtypes = [V, I, I, V, I, V]
-    L.harness_sky_light_apply.argtypes = [V, V, V, V]
-    return L
-
-
-def radiance_case(sky, opts=None):
-    o = dict(RADIANCE_DEFAULTS, **(opts or {}))
-    h = np.zeros(1, RADIANCE_CASE)
-    h["sky_height"], h["sky_width"], h["sky_srgb"], h["energy"] = sky["image"].shape[0], sky["image"].shape[1], sky["srgb"], sky["energy"]
-    for k in RADIANCE_DEFAULTS:
-        h[k] = o[k] or RADIANCE_DEFAULTS[k]
-    return h
-
-
-def light_case(cam, opts=None):
-    o = f32_options(LIGHT_DEFAULTS, opts)
-    h = np.zeros(1, LIGHT_CASE)
-    h["width"], h["height"], h["cam"] = cam.width, cam.height, camera_words(cam)
-    for k in LIGHT_DEFAULTS:
-        h[k] = o[k]
-    return h
-
-
-class CpuPyramid:
-    """the CPU build's pyramid of a sky (sky_of's dict): R[k], M[k], E as (h, w, 4) float32, lookups and the pass"""
-
-    def __init__(self, L, sky, opts=None):
-        self.L, self.sky = L, sky
-        self.case = radiance_case(sky, opts)
-        self.levels = int(self.case["levels"][0])
-        self.ptr = L.harness_radiance_new(self.case.ctypes.data, sky["image"].ctypes.data)
-        assert self.ptr, "the sizes are refused"
-
-    def __del__(self):
-        if getattr(self, "ptr", None):
-            self.L.harness_radiance_free(self.ptr)
-
-    def texture(self, kind, k=0):
-        size = (C.c_int * 2)()
-        if not self.L.harness_radiance_get(self.ptr, kind, k, size, None):
-            return None
-        out = np.zeros((size[1], size[0], 4), np.float32)
-        self.L.harness_radiance_get(self.ptr, kind, k, size, out.ctypes.data)
-        return out
-
-    R = lambda self, k: self.texture(0, k)    # noqa: E731
-    M = lambda self, k: self.texture(1, k)    # noqa: E731
-    E = property(lambda self: self.texture(2))
-
-    def lookup(self, kind, k, dirs):
-        d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
-        out = np.zeros_like(d)
-        self.L.harness_radiance_lookup(self.ptr, kind, k, d.ctypes.data, len(d), out.ctypes.data)
-        return out
-
-    def apply(self, records, cam, opts=None):
-        """dict of rec (a copy, rewritten) and the stages"""
-        rec = np.array(records, W.RENDER_PIXEL, copy=True, order="C")
-        assert rec.shape == (cam.height, cam.width)
-        h = light_case(cam, opts)
-        st = np.zeros((cam.height, cam.width, 21), np.float32)
-        self.L.harness_sky_light_apply(self.ptr, h.ctypes.data, rec.ctypes.data, st.ctypes.data)
-        out = dict(rec=rec)
-        for name, a, b in STAGES:
-            out[name] = st[..., a] if b == a + 1 else st[..., a:b]
-        return out
 
 
 def twin_pyramid(sky, opts=None):
@@ -205,19 +112,11 @@ def check_pass_against_twin(got, tw, records, what):
 
 # ---- 1. the interface and the documents --------------------------------------------------------------------------------------------------
 
-HEADER = open(os.path.join(ROOT, "include", "ocean_waves.h")).read()
-
-
 def test_header_declares_the_new_calls_and_the_library_exports_them():
     build.build_library()
     lib = _lib.load()
-    text = re.sub(r"/\*.*?\*/", "", HEADER, flags=re.S)
-    for name in NEW_FUNCTIONS:
-        assert re.search(r"\b%s\s*\(" % name, text), name
-        assert name in _lib.SIGNATURES
-        assert getattr(lib, name)
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = set(re.findall(r" T (ow_[a-z0-9_]+)", out))
+    text = check_declared_and_bound(lib, NEW_FUNCTIONS)
+    exported = exported_symbols()
     assert sorted(s for s in exported if "radiance" in s) == sorted(NEW_FUNCTIONS)      # no group form
     assert lib.ow_abi_version() == 4 and re.search(r"#define OW_ABI_VERSION 4\b", HEADER)
     for define, value in (("OW_RAY_SKY_LIT", 64), ("OW_RADIANCE_MAX_LEVELS", 8), ("OW_RADIANCE_MAX_SAMPLES", 256)):
@@ -245,9 +144,7 @@ def test_option_structs_agree_in_c_ctypes_and_the_harness(tmp_path, harness):
         expr = ", ".join(["sizeof(%s)" % name] + ["offsetof(%s, %s)" % (name, f) for f in fields])
         src = ('#include <stdio.h>\n#include <stddef.h>\n#include "ocean_waves.h"\nint main(void){printf("%s\\n", ' % " ".join(["%zu"] * (1 + len(fields)))
                + expr + ");return 0;}\n")
-        exe = str(tmp_path / (name + "_layout"))
-        subprocess.run(["gcc", "-std=c11", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-x", "c", "-", "-o", exe], input=src, text=True, check=True)
-        vals = [int(v) for v in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split()]
+        vals = layout_probe(tmp_path, (name + "_layout"), src)
         assert vals == [C.sizeof(S)] + [getattr(S, f).offset for f in fields], name
         got[name] = dict(zip(["size"] + fields, vals))
     assert (got["ow_radiance_options"]["size"], got["ow_radiance_light_options"]["size"]) == (32, 64)
@@ -260,7 +157,6 @@ def test_option_structs_agree_in_c_ctypes_and_the_harness(tmp_path, harness):
 
 
 def test_the_documents_name_the_new_calls():
-    import test_integration_shim as S
     for name in NEW_FUNCTIONS:
         assert "`%s`" % name in S.DOC.split("## 7. Index")[1], name
     for name in ("ow_radiance_create", "ow_radiance_destroy", "ow_radiance_level", "ow_radiance_light_apply", "ow_radiance_light_apply_async"):
@@ -277,17 +173,9 @@ def test_the_documents_name_the_new_calls():
         assert os.path.exists(os.path.join(ROOT, path)), path
 
 
-def build_example(tmp_path):
-    exe = str(tmp_path / "sky_light_host")
-    subprocess.run(["gcc", "-O2", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "examples", "sky_light_host.c"),
-                    "-o", exe, "-L", PKG, "-locean_waves", "-L", "/opt/rocm/lib", "-lamdhip64", f"-Wl,-rpath,{PKG}", "-Wl,-rpath,/opt/rocm/lib", "-lm"],
-                   check=True)
-    return exe
-
-
 def test_example_builds_as_c99(tmp_path):
     build.build_library()
-    build_example(tmp_path)
+    build_example(tmp_path, "sky_light_host")
 
 
 # ---- 2. argument errors without a device ---------------------------------------------------------------------------------------------------
@@ -731,9 +619,7 @@ def write_case(path, sky, ropts, cam, rec, lopts):
 def test_stand_alone_harness_runs_clean_under_the_sanitizers(tmp_path, harness, lit_pictures):
     """the harness as a program of its own (-DSKY_LIGHT_HARNESS_MAIN), built with -fsanitize=address,undefined, on the twin's fields and every
     awkward case: what it writes is the shared library's"""
-    exe = str(tmp_path / "sky_light_harness_main")
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    "-Wno-unknown-pragmas", "-DSKY_LIGHT_HARNESS_MAIN", "-I", CSRC, HARNESS_SRC, "-o", exe], check=True)
+    exe = build_sanitized_harness("sky_light", tmp_path)
     cam = lit_pictures["cam"]
     cases = [("synthetic", sky_of(gradient_panorama(64, 32), 1, 1.3), dict(levels=4, samples=16), cam, light_records(cam, 1), None),
              ("sea, reduced noisy sky", sky_of(noisy_panorama(128, 64), 0, 0.8), dict(levels=3, samples=8, base_width=32), cam, lit_pictures["sea"],
@@ -755,12 +641,6 @@ def test_stand_alone_harness_runs_clean_under_the_sanitizers(tmp_path, harness, 
 
 
 # ---- 6-12. on the GPU -----------------------------------------------------------------------------------------------------------------------
-
-def gpu_radiance(gen, sky, ropts=None):
-    """(the Sky, the Radiance) of a sky_of dict"""
-    handle = gpu_sky(gen, sky)
-    return handle, gen.radiance_create(handle, ropts)
-
 
 def same_pyramid(gen, radiance, pyr, what):
     assert radiance.levels == pyr.levels, what
@@ -1013,7 +893,7 @@ def test_foreign_and_orphaned_handles_are_refused_and_a_destroyed_sky_does_not_d
 @pytest.mark.gpu
 def test_the_c_example_writes_the_python_wrappers_image(tmp_path):
     """examples/sky_light_host.c at 256^2, a 48 x 32 PPM of 96 x 64 records, 40 steps, 4096 particles, against the wrapper on the same scene"""
-    exe = build_example(tmp_path)
+    exe = build_example(tmp_path, "sky_light_host")
     ppm = str(tmp_path / "sky_light.ppm")
     r = subprocess.run([exe, ppm, "48", "32", "40", "256", "4096", "2"], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stderr

@@ -23,107 +23,24 @@ import solid_twin as ST
 from godotoceanwaves_amd import _lib, build
 from godotoceanwaves_amd.presets import UPDATE_DELTA
 from godotoceanwaves_amd.wave_generator import WaveGenerator as W
-from test_bodies_step import crate, device_read, make_bodies, quaternion
-from test_mesh_draw import cpu_draw as cpu_mesh_draw, grid, harness as mesh_harness  # noqa: F401
-from test_raycast import calm_maps
-from test_render_view import HIT, camera_words, look
-from test_spray_draw import (blank_records, cpu_draw as cpu_billboard_draw, device_buffers, buffers_to_host, flat_texture, harness as billboard_harness,  # noqa: F401
-                             instances as billboards, level_camera, material, same_picture)
-from test_surface_query import gpu_maps, make_gen, scales_of
+import checks as S
+from checks import check_csharp_binds, check_declared_and_bound, exported_symbols, HEADER, same_picture
+from cpu_builds import (calm_picture, cpu_billboard_draw, cpu_mesh_draw, cpu_solid_draw as cpu_draw, ROOT, SOLID_CASE as CASE,
+                        solid_case_arrays as case_arrays, solid_case_of as case_of, SOLID_DEFAULTS as DEFAULTS, twin_scene)
+from cpu_builds import billboard_harness, mesh_harness, solid_harness as harness  # noqa: F401 (fixtures)
+from scenes import (advance, bare_context, billboards, blank_records, box, buffers_to_host, camera_words, CRATE_CAM, CRATE_SHAPE, cube,
+                    device_buffers, eight_crates, example_crates, example_textures, flat_texture, floating_scene, gpu_maps, gpu_material,
+                    grid, HIT, level_camera, look, make_gen, material, pose_transforms, quaternion, REF_BASIS, scales_of, SOLID,
+                    SOLID_TWIN_CAM as TWIN_CAM, transform, transforms, tumbled)
+from cpu_builds import build_example, build_sanitized_harness, layout_probe
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "godotoceanwaves_amd", "csrc")
-PKG = os.path.join(ROOT, "godotoceanwaves_amd")
-HERE = os.path.dirname(os.path.abspath(__file__))
-HARNESS_SRC = os.path.join(HERE, "solid", "solid_harness.cpp")
 MARGINS = os.path.join(ROOT, "profiles", "solid_draw_margins.txt")
 NEW_FUNCTIONS = ("ow_solid_options_default", "ow_solid_create", "ow_solid_destroy", "ow_solid_draw", "ow_solid_draw_async", "ow_solid_draw_instances",
                  "ow_solid_draw_stats")
 TOL = H.TOL_F32     # 1e-4: the project's FP32 parity tolerance
-SOLID = _lib.OW_RAY_SOLID
-SUN = (0.321197, 0.18296, 0.929171)
-DEFAULTS = dict(color=(0.45, 0.30, 0.15), light_direction=SUN, light_color=(1.0, 1.0, 1.0), ambient_color=(0.05, 0.08, 0.10), background_color=(0.0, 0.0, 0.0))
-CASE = np.dtype([("width", np.int32), ("height", np.int32), ("cam", np.float32, 15), ("num_vertices", np.int32), ("num_triangles", np.int32),
-                 ("count", np.int32), ("stride", np.int32), ("has_flags", np.int32), ("near", np.float32), ("color", np.float32, 3),
-                 ("light_direction", np.float32, 3), ("light_color", np.float32, 3), ("ambient_color", np.float32, 3),
-                 ("background_color", np.float32, 3), ("two_sided", np.int32), ("lane_box", np.int32), ("has_pixels", np.int32)])
 
 
 # ---- shapes, transforms and the CPU build ------------------------------------------------------------------------------------------------
-
-def cube(side=1.0):
-    """8 vertices, 12 triangles, counter-clockwise seen from outside; triangles 2 f and 2 f + 1 are face f (-x, +x, -y, +y, -z, +z)"""
-    h = 0.5 * side
-    v = np.array([[x, y, z] for x in (-h, h) for y in (-h, h) for z in (-h, h)], np.float32)   # index = 4 ix + 2 iy + iz
-    quads = [(0, 1, 3, 2), (4, 6, 7, 5), (0, 4, 5, 1), (2, 3, 7, 6), (0, 2, 6, 4), (1, 5, 7, 3)]
-    t = np.array([tri for a, b, c, d in quads for tri in ((a, b, c), (a, c, d))], np.int32)
-    return v, t
-
-
-def box(size):
-    v, t = cube(1.0)
-    return (v * np.float32(size)).astype(np.float32), t
-
-
-def transform(origin=(0.0, 0.0, 0.0), q=(0.0, 0.0, 0.0, 1.0), scale=1.0):
-    """twelve floats: the rotation of unit quaternion q (x, y, z, w) as basis rows, times scale, then the origin"""
-    x, y, z, w = np.asarray(q, np.float64) / np.linalg.norm(q)
-    r = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
-                  [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
-                  [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]]) * scale
-    return np.concatenate([r.ravel(), np.asarray(origin, np.float64)]).astype(np.float32)
-
-
-def transforms(rows):
-    return np.stack([transform(*r) if not isinstance(r, np.ndarray) else r for r in rows]).astype(np.float32) if len(rows) else np.zeros((0, 12), np.float32)
-
-
-@pytest.fixture(scope="module")
-def harness(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("solid") / "libsolid_harness.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unknown-pragmas", "-I", CSRC, HARNESS_SRC, "-o", so], check=True)
-    L = C.CDLL(so)
-    V = C.c_void_p
-    L.harness_solid_sizes.argtypes = [V]
-    L.harness_solid_draw.argtypes = [V] * 9
-    return L
-
-
-def case_of(cam, shape, count, opts=None, records=None, stride=12, flags=None):
-    o = dict(DEFAULTS)
-    o.update(opts or {})
-    h = np.zeros(1, CASE)
-    h["width"], h["height"], h["cam"] = cam.width, cam.height, camera_words(cam)
-    h["num_vertices"], h["num_triangles"], h["count"], h["stride"], h["has_flags"] = len(shape[0]), len(shape[1]), count, stride, int(flags is not None)
-    h["near"], h["two_sided"], h["lane_box"] = o.get("near", 0.0), int(bool(o.get("two_sided"))), o.get("lane_box", 0)
-    for k in ("color", "light_direction", "light_color", "ambient_color", "background_color"):
-        h[k] = o[k]
-    h["has_pixels"] = int(records is not None)
-    return h
-
-
-def case_arrays(shape, tf, records, flags=None):
-    v = np.ascontiguousarray(shape[0], np.float32).reshape(-1, 3)
-    t = np.ascontiguousarray(shape[1], np.int32).reshape(-1, 3)
-    tf = np.ascontiguousarray(tf, np.float32)
-    fl = np.ascontiguousarray(flags, np.int32) if flags is not None else None
-    rec = np.array(records, W.RENDER_PIXEL, copy=True, order="C") if records is not None else None
-    return v, t, tf, fl, rec
-
-
-def cpu_draw(L, shape, tf, cam, opts=None, records=None, stride=12, flags=None):
-    """the CPU build's draw: dict of rgba [H][W][4], rec [H][W] or None, vis [H][W], skipped, culled, lane, wave, drawn"""
-    v, t, tf, fl, rec = case_arrays(shape, tf, records, flags)
-    count = tf.size // stride
-    h = case_of(cam, (v, t), count, opts, records, stride, fl)
-    rgba = np.zeros((cam.height, cam.width, 4), np.uint8)
-    vis = np.zeros((cam.height, cam.width), np.uint64)
-    counters = np.zeros(4, np.uint32)
-    L.harness_solid_draw(h.ctypes.data, v.ctypes.data, t.ctypes.data, tf.ctypes.data if tf.size else None, fl.ctypes.data if fl is not None else None,
-                         rec.ctypes.data if rec is not None else None, rgba.ctypes.data, counters.ctypes.data, vis.ctypes.data)
-    s, c, ln, wv = (int(x) for x in counters)
-    return dict(rgba=rgba, rec=rec, vis=vis, skipped=s, culled=c, lane=ln, wave=wv, drawn=ln + wv)
-
 
 def twin_of(shape, tf, cam, opts=None, records=None):
     return ST.draw(shape[0], shape[1], tf, cam, opts, records)
@@ -159,20 +76,12 @@ def solid_mask(rec):
 
 # ---- 1. the interface and the documents --------------------------------------------------------------------------------------------------
 
-HEADER = open(os.path.join(ROOT, "include", "ocean_waves.h")).read()
-
-
 def test_header_declares_the_solid_calls_and_the_library_exports_them():
     build.build_library()
     lib = _lib.load()
-    text = re.sub(r"/\*.*?\*/", "", HEADER, flags=re.S)
-    for name in NEW_FUNCTIONS:
-        assert re.search(r"\b%s\s*\(" % name, text), name
-        assert name in _lib.SIGNATURES
-        assert getattr(lib, name)
+    text = check_declared_and_bound(lib, NEW_FUNCTIONS)
     assert re.search(r"typedef struct ow_solid_options \{", text) and "ow_layout_check_solid_options" in HEADER
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = set(re.findall(r" T (ow_[a-z0-9_]+)", out))
+    exported = exported_symbols()
     assert sorted(s for s in exported if "solid" in s) == sorted(NEW_FUNCTIONS)      # no group form
     assert lib.ow_abi_version() == 4 and re.search(r"#define OW_ABI_VERSION 4\b", HEADER)
     for define, value in (("OW_RAY_SOLID", 16), ("OW_SOLID_TWO_SIDED", 1), ("OW_SOLID_MAX_INSTANCES", 65536), ("OW_SOLID_MAX_TRIANGLES", 65536)):
@@ -197,9 +106,7 @@ def test_solid_structs_agree_in_c_ctypes_and_the_harness(tmp_path, harness):
     expr = ", ".join(["sizeof(ow_solid_options)"] + ["offsetof(ow_solid_options, %s)" % f for f in fields])
     src = ('#include <stdio.h>\n#include <stddef.h>\n#include "ocean_waves.h"\nint main(void){printf("%s\\n", ' % " ".join(["%zu"] * (1 + len(fields)))
            + expr + ");return 0;}\n")
-    exe = str(tmp_path / "solid_layout")
-    subprocess.run(["gcc", "-std=c11", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-x", "c", "-", "-o", exe], input=src, text=True, check=True)
-    got = [int(v) for v in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split()]
+    got = layout_probe(tmp_path, "solid_layout", src)
     want = [C.sizeof(S)] + [getattr(S, f).offset for f in fields]
     assert got == want and got[0] == 128
     off = dict(zip(fields, got[1:]))
@@ -211,10 +118,7 @@ def test_solid_structs_agree_in_c_ctypes_and_the_harness(tmp_path, harness):
 
 
 def test_the_documents_and_the_csharp_binding_name_the_solid_calls():
-    import test_integration_shim as S
-    for name in NEW_FUNCTIONS:
-        assert re.search(r"\[DllImport\(Lib\)\]\s*public static extern \w+ %s\(" % name, S.SHIM), name
-        assert "`%s`" % name in S.DOC.split("## 7. Index")[1], name
+    check_csharp_binds(NEW_FUNCTIONS)
     want, got = S.c_struct_fields("ow_solid_options"), S.cs_struct_fields("OwSolidOptions")
     assert got == want and sum(s for _, s in want) == 128, (got, want)
     for doc, words in (("README.md", ("ow_solid_draw",)), ("DESIGN.md", ("k_solid_vertices", "k_solid_clear", "k_solid_raster", "k_solid_resolve")),
@@ -224,17 +128,9 @@ def test_the_documents_and_the_csharp_binding_name_the_solid_calls():
             assert w in text, (doc, w)
 
 
-def build_example(tmp_path):
-    exe = str(tmp_path / "solid_draw_host")
-    subprocess.run(["gcc", "-O2", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "examples", "solid_draw_host.c"),
-                    "-o", exe, "-L", PKG, "-locean_waves", "-L", "/opt/rocm/lib", "-lamdhip64", f"-Wl,-rpath,{PKG}", "-Wl,-rpath,/opt/rocm/lib", "-lm"],
-                   check=True)
-    return exe
-
-
 def test_example_builds_as_c99(tmp_path):
     build.build_library()
-    build_example(tmp_path)
+    build_example(tmp_path, "solid_draw_host")
 
 
 # ---- 2. argument errors without a device ---------------------------------------------------------------------------------------------------
@@ -441,18 +337,6 @@ def test_shared_edge_near_plane_and_behind_the_camera(harness):
 
 # ---- 5. the winner ---------------------------------------------------------------------------------------------------------------------------
 
-def tumbled(count, seed=5, x=(-4.7, 4.7), y=(-0.9, 1.6), z=(4.3, 9.7)):
-    rng = np.random.default_rng(seed)
-    rows = []
-    for _ in range(count):
-        q = rng.normal(size=4)
-        rows.append(((rng.uniform(*x), rng.uniform(*y), rng.uniform(*z)), q / np.linalg.norm(q)))
-    return transforms(rows)
-
-
-TWIN_CAM = dict(position=(0.37, 3.1, -1.3), yaw_deg=4.0, pitch_deg=-14.0, fov=75.0, width=96, height=64, max_distance=500.0)
-
-
 def test_the_winner_is_the_nearest_then_the_lowest_index(harness):
     cam = level_camera()
     shape = cube(4.4)
@@ -479,11 +363,6 @@ def test_the_winner_is_the_nearest_then_the_lowest_index(harness):
 
 
 # ---- 6. depth against a calm sea -------------------------------------------------------------------------------------------------------------
-
-def calm_picture(mesh_harness, cam):
-    d, m, sc = calm_maps()
-    return cpu_mesh_draw(mesh_harness, d, m, sc, grid(16, 8.0), (0.0, 0.0, 0.0), cam)["rec"]
-
 
 def test_depth_against_a_calm_sea_and_a_billboard_afterwards(harness, mesh_harness, billboard_harness):
     """The calm sea is the plane y = 0.  A pixel's ray comes down from a camera 6 m up: it meets a point of the crate with y > 0 before the
@@ -558,11 +437,6 @@ def test_back_faces_two_sides_and_lane_box(harness):
 
 
 # ---- 8. the FP64 twin ------------------------------------------------------------------------------------------------------------------------
-
-def twin_scene(mesh_harness):
-    cam = look(**TWIN_CAM)
-    return box((2.5, 2.5, 2.5)), tumbled(7, seed=20261018), cam, calm_picture(mesh_harness, cam)
-
 
 def test_the_twin_alone_meets_the_scenes_conditions(mesh_harness):
     """before anything else: of the twin's covered pixels at most 2 % are set aside and at least 1 500 remain"""
@@ -690,9 +564,7 @@ def write_case(path, c, records):
 def test_stand_alone_harness_runs_clean_under_the_sanitizers(tmp_path, harness, mesh_harness):
     """the harness as a program of its own (-DSOLID_HARNESS_MAIN), built with -fsanitize=address,undefined, on the twin's scene, the mixed
     cubes and every awkward case: the picture it writes is the shared library's"""
-    exe = str(tmp_path / "solid_harness_main")
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    "-Wno-unknown-pragmas", "-DSOLID_HARNESS_MAIN", "-I", CSRC, HARNESS_SRC, "-o", exe], check=True)
+    exe = build_sanitized_harness("solid", tmp_path)
     shape, tf, cam, bg = twin_scene(mesh_harness)
     cases = dict(awkward_cases(), twin=dict(shape=shape, tf=tf, cam=cam, records=bg))
     cases["70 mixed cubes"] = dict(shape=cube(), tf=mixed_cubes(70), cam=level_camera(64, 40))
@@ -716,11 +588,6 @@ def test_stand_alone_harness_runs_clean_under_the_sanitizers(tmp_path, harness, 
 
 
 # ---- 11-16. on the GPU -------------------------------------------------------------------------------------------------------------------------
-
-def bare_context():
-    """the smallest context: the solid draw reads no map"""
-    return make_gen(128, [0, 1])[0]
-
 
 def gpu_instances(gen, shape, tf, cam, opts=None, records=None):
     h = gen.solid_create(*shape)
@@ -759,52 +626,6 @@ def test_gpu_hand_made_instances_are_the_cpu_builds_bit_for_bit(harness, count):
         same_picture(got, want, name)
         same_counters(got, want, name)
     gen.free()
-
-
-def eight_crates():
-    rng = np.random.default_rng(3)
-    items = []
-    for k in range(8):
-        q = rng.normal(size=4)
-        items.append(crate(origin=((k % 4 - 1.5) * 4.0 + 0.3, 0.3, 6.0 + 5.0 * (k // 4)), q=tuple(q / np.linalg.norm(q)), kl=3.0, kq=0.5))
-    return make_bodies(items)
-
-
-CRATE_CAM = dict(position=(0.4, 5.0, -9.0), yaw_deg=2.0, pitch_deg=-17.0, fov=75.0, width=160, height=96, max_distance=2000.0)
-CRATE_SHAPE = (2.0, 1.0, 2.0)
-
-
-def floating_scene(n=128, stream=None, steps=6, broken=None):
-    """128^2 x 2 maps, eight tumbling crates stepped behind a tick each (one of them overflowing in its first substep: its fault flag is
-    raised and its state frozen where it was created), a 4096-particle emitter stepped with them"""
-    gen, params = make_gen(n, [0, 1], stream=stream)
-    sc = scales_of(params)
-    gen.run(UPDATE_DELTA, params, 20)
-    st, hull = eight_crates()
-    if broken is not None:
-        st["applied_force"][broken], st["mass"][broken] = (0, 1.7e308, 0), 1e-3       # passes the host's checks, is not finite after one substep
-    bodies = gen.bodies_create(st, hull)
-    spray = gen.spray_create({"amount": 4096, "emitter_lifetime": 0.5, "lifetime": 0.25})
-    advance(gen, params, sc, bodies, spray, steps)
-    return gen, params, sc, bodies, spray
-
-
-def advance(gen, params, sc, bodies, spray, steps):
-    for _ in range(steps):
-        gen.update_all(UPDATE_DELTA, params)
-        gen.bodies_step(bodies, sc, 2, UPDATE_DELTA / 2, {"warm_start": True})
-        gen.spray_step(spray, UPDATE_DELTA, sc)
-
-
-def gpu_material(gen, mat):
-    return gen.spray_material_create(mat["albedo"], mat["dissolve"], {k: mat[k] for k in ("foam_color", "max_alpha", "albedo_srgb", "dissolve_srgb")})
-
-
-def pose_transforms(gen, bodies):
-    """the set's resident pose records as [bodies][24] floats: the transform is the first twelve"""
-    ptr, _, _ = gen.bodies_device_ptrs(bodies)
-    rec = device_read(ptr, bodies.num_bodies, W.BUOYANCY_BODY)
-    return np.frombuffer(rec.tobytes(), np.float32).reshape(bodies.num_bodies, 24).copy()
 
 
 @pytest.mark.gpu
@@ -1016,37 +837,10 @@ def test_solid_scratch_grows_once_and_stays_and_errors_write_nothing(harness):
     live.free()
 
 
-def example_crates():
-    """examples/solid_draw_host.c's crates, operation for operation"""
-    size, rho, per = (2.0, 1.0, 2.0), 1025.0, 4 * 2 * 4
-    volume = size[0] * size[1] * size[2]
-    mass = 0.5 * rho * volume
-    st = np.zeros(36, W.RIGID_BODY)
-    hull = np.zeros(36 * per, W.HULL_POINT)
-    for b in range(36):
-        st[b]["position"] = ((b % 6 - 2.5) * 6.0, 0.3, 10.0 + (b // 6 - 2.5) * 6.0)
-        st[b]["orientation"] = (0, 0, 0, 1)
-        st[b]["mass"] = mass
-        st[b]["inverse_inertia"] = (12.0 / (mass * (size[1] * size[1] + size[2] * size[2])), 12.0 / (mass * (size[0] * size[0] + size[2] * size[2])),
-                                    12.0 / (mass * (size[0] * size[0] + size[1] * size[1])))
-        st[b]["linear_drag"], st[b]["quadratic_drag"] = 3.0, 0.5
-        st[b]["point_offset"], st[b]["point_count"] = b * per, per
-        k = b * per
-        for i in range(4):
-            for j in range(2):
-                for l in range(4):
-                    hull[k]["local"] = ((i + 0.5) * (size[0] / 4) - size[0] / 2, (j + 0.5) * (size[1] / 2) - size[1] / 2, (l + 0.5) * (size[2] / 4) - size[2] / 2)
-                    hull[k]["volume"], hull[k]["half_height"], hull[k]["body"] = volume / per, size[1] / 2 / 2, b
-                    k += 1
-    return st, hull
-
-
 @pytest.mark.gpu
 def test_the_c_example_writes_the_python_wrappers_image(tmp_path):
     """examples/solid_draw_host.c at 256^2, 96 x 64, 60 steps, 4096 particles, against the wrapper on the same scene"""
-    from test_mesh_draw import REF_BASIS
-    from test_spray_draw import example_textures
-    exe = build_example(tmp_path)
+    exe = build_example(tmp_path, "solid_draw_host")
     ppm = str(tmp_path / "solids.ppm")
     r = subprocess.run([exe, ppm, "96", "64", "60", "256", "4096"], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stderr

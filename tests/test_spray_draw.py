@@ -22,133 +22,24 @@ import spray_draw_twin as DT
 from godotoceanwaves_amd import _lib, build
 from godotoceanwaves_amd.presets import UPDATE_DELTA
 from godotoceanwaves_amd.wave_generator import WaveGenerator as W
-from test_mesh_draw import REF_BASIS, cpu_draw as cpu_mesh_draw, grid, harness as mesh_harness  # noqa: F401
-from test_raycast import calm_maps
-from test_render_view import DEFAULTS, HIT, camera_words, look
-from test_spray import CpuEmitter, harness as spray_harness, options as spray_options  # noqa: F401
-from test_surface_query import generated_maps, make_gen, scales_of
+import checks as S
+from checks import check_csharp_binds, check_declared_and_bound, exported_symbols, HEADER, same_picture
+from cpu_builds import (BILLBOARD_CASE as CASE, billboard_case_arrays as case_arrays, billboard_case_of as case_of, calm_picture,
+                        cpu_billboard_draw as cpu_draw, cpu_mesh_draw, CpuEmitter, ROOT)
+from cpu_builds import billboard_harness as harness, mesh_harness, spray_harness  # noqa: F401 (fixtures)
+from scenes import (bare_context, billboards as instances, blank_records, buffers_to_host, device_buffers, example_textures, flat_texture,
+                    FOAM, generated_maps, gpu_material, gradient_texture, grid, HIT, level_camera, look, make_gen, material, MAX_ALPHA,
+                    noise_texture, REF_BASIS, scales_of, spray_options, WHITE)
+from cpu_builds import build_example, build_sanitized_harness, layout_probe
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "godotoceanwaves_amd", "csrc")
-PKG = os.path.join(ROOT, "godotoceanwaves_amd")
-HERE = os.path.dirname(os.path.abspath(__file__))
-HARNESS_SRC = os.path.join(HERE, "spray_draw", "spray_draw_harness.cpp")
 MARGINS = os.path.join(ROOT, "profiles", "spray_draw_margins.txt")
 NEW_FUNCTIONS = ("ow_billboard_material_options_default", "ow_billboard_material_create", "ow_billboard_material_destroy", "ow_billboard_draw",
                  "ow_billboard_draw_async", "ow_billboard_draw_instances", "ow_billboard_draw_stats")
 STRUCTS = {"ow_billboard_material_options": _lib.ow_billboard_material_options, "ow_billboard_draw_options": _lib.ow_billboard_draw_options}
 TOL = H.TOL_F32     # 1e-4: the project's FP32 parity tolerance
-FOAM = DEFAULTS["foam_color"]
-MAX_ALPHA = 0.666
-CASE = np.dtype([("width", np.int32), ("height", np.int32), ("cam", np.float32, 15), ("count", np.int32), ("live", np.int32), ("has_list", np.int32),
-                 ("time", np.float32), ("foam", np.float32, 3), ("max_alpha", np.float32), ("aw", np.int32), ("ah", np.int32), ("asrgb", np.int32),
-                 ("dw", np.int32), ("dh", np.int32), ("dsrgb", np.int32), ("near", np.float32), ("background", np.float32, 3),
-                 ("bin_side", np.int32), ("has_pixels", np.int32)])
 
 
 # ---- textures, instances and the CPU build -------------------------------------------------------------------------------------------
-
-def gradient_texture(h=16, w=24):
-    """an albedo whose colour differs at every texel and whose alpha is a soft blob that stays above a third"""
-    j, i = np.meshgrid(np.arange(h), np.arange(w), indexing="ij")
-    t = np.zeros((h, w, 4), np.uint8)
-    t[..., 0] = 40 + 200 * i // max(w - 1, 1)
-    t[..., 1] = 250 - 190 * j // max(h - 1, 1)
-    t[..., 2] = 60 + (37 * i + 91 * j) % 190
-    r2 = ((i + 0.5) / w - 0.5) ** 2 + ((j + 0.5) / h - 0.5) ** 2
-    t[..., 3] = np.clip(255 * (1.0 - 1.3 * r2), 90, 255).astype(np.uint8)
-    return t
-
-
-def noise_texture(h=32, w=32, seed=3, hi=140):
-    """a dissolve texture: smooth noise in the red channel, low enough that (w + z) / 2 clears it for most particles"""
-    rng = np.random.default_rng(seed)
-    a = rng.uniform(0, 1, (h, w))
-    for _ in range(2):
-        a = (a + np.roll(a, 1, 0) + np.roll(a, 1, 1) + np.roll(a, -1, 0) + np.roll(a, -1, 1)) / 5.0
-    a = (a - a.min()) / (a.max() - a.min())
-    t = np.zeros((h, w, 4), np.uint8)
-    t[..., 0] = (a * hi).astype(np.uint8)
-    t[..., 1] = 255 - t[..., 0]
-    t[..., 3] = 255
-    return t
-
-
-def flat_texture(rgba, h=1, w=1):
-    return np.broadcast_to(np.asarray(rgba, np.uint8), (h, w, 4)).copy()
-
-
-def material(albedo=None, dissolve=None, **kw):
-    m = dict(foam_color=FOAM, max_alpha=MAX_ALPHA, albedo=gradient_texture() if albedo is None else albedo,
-             dissolve=noise_texture() if dissolve is None else dissolve, albedo_srgb=1, dissolve_srgb=1)
-    m.update(kw)
-    return m
-
-
-WHITE = dict(albedo=flat_texture((255, 255, 255, 255)), dissolve=flat_texture((0, 0, 0, 255)))
-
-
-def instances(rows):
-    """SPRAY_INSTANCE records from (origin, width, height, custom.z, custom.w): the basis is diag(width, height, 1)"""
-    out = np.zeros(len(rows), W.SPRAY_INSTANCE)
-    for k, (origin, sx, sy, z, w) in enumerate(rows):
-        t = np.zeros((3, 4), np.float32)
-        t[0, 0], t[1, 1], t[2, 2] = sx, sy, 1.0
-        t[:, 3] = origin
-        out["transform"][k] = t.ravel()
-        out["custom"][k] = (0.0, 0.0, z, w)
-    return out
-
-
-def level_camera(width=64, height=40, position=(0.0, 0.0, 0.0), fov=90.0, max_distance=4000.0):
-    """a camera with the identity basis: it looks down -Z, view space is world space minus the position"""
-    return W.camera(position, np.eye(3), fov, width, height, max_distance)
-
-
-@pytest.fixture(scope="module")
-def harness(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("spray_draw") / "libspray_draw_harness.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unknown-pragmas", "-I", CSRC, HARNESS_SRC, "-o", so], check=True)
-    L = C.CDLL(so)
-    V, I = C.c_void_p, C.c_int
-    L.harness_billboard_sizes.argtypes = [V]
-    L.harness_srgb_table.argtypes = [V]
-    L.harness_billboard_draw.argtypes = [V, V, V, V, V, V, V, V, V]
-    L.harness_billboard_fragment.argtypes = [V, V, V, V, I, I, C.c_float, C.c_int32, V]
-    return L
-
-
-def case_of(cam, count, mat, time=0.0, order=None, opts=None, records=None):
-    o = opts or {}
-    h = np.zeros(1, CASE)
-    h["width"], h["height"], h["cam"] = cam.width, cam.height, camera_words(cam)
-    h["count"], h["live"], h["has_list"], h["time"] = count, 0 if order is None else len(order), int(order is not None), time
-    h["foam"], h["max_alpha"] = mat["foam_color"], mat["max_alpha"]
-    h["ah"], h["aw"], h["asrgb"] = mat["albedo"].shape[0], mat["albedo"].shape[1], mat.get("albedo_srgb", 1)
-    h["dh"], h["dw"], h["dsrgb"] = mat["dissolve"].shape[0], mat["dissolve"].shape[1], mat.get("dissolve_srgb", 1)
-    h["near"], h["background"], h["bin_side"] = o.get("near", 0.0), o.get("background_color", (0, 0, 0)), o.get("bin_side", 0)
-    h["has_pixels"] = int(records is not None)
-    return h
-
-
-def case_arrays(inst, mat, order, records):
-    inst = np.ascontiguousarray(inst, W.SPRAY_INSTANCE).reshape(-1)
-    lst = np.ascontiguousarray(order if order is not None else [], np.uint32)
-    a, d = np.ascontiguousarray(mat["albedo"], np.uint8), np.ascontiguousarray(mat["dissolve"], np.uint8)
-    rec = np.array(records, W.RENDER_PIXEL, copy=True, order="C") if records is not None else None
-    return inst, lst, a, d, rec
-
-
-def cpu_draw(L, inst, cam, mat, time=0.0, order=None, opts=None, records=None):
-    """the CPU build's draw: dict of rgba [H][W][4], rec [H][W] or None, drawn, culled, bins (side, nx, ny, words)"""
-    inst, lst, a, d, rec = case_arrays(inst, mat, order, records)
-    h = case_of(cam, len(inst), mat, time, order, opts, records)
-    rgba = np.zeros((cam.height, cam.width, 4), np.uint8)
-    counters, bins = np.zeros(2, np.uint32), np.zeros(4, np.int32)
-    L.harness_billboard_draw(h.ctypes.data, inst.ctypes.data, lst.ctypes.data, a.ctypes.data, d.ctypes.data, rec.ctypes.data if rec is not None else None,
-                             rgba.ctypes.data, counters.ctypes.data, bins.ctypes.data)
-    return dict(rgba=rgba, rec=rec, drawn=int(counters[0]), culled=int(counters[1]), bins=tuple(int(b) for b in bins))
-
 
 def cpu_fragment(L, inst, cam, mat, i, j, time=0.0, opts=None, t=0.0, status=0):
     inst, _, a, d, _ = case_arrays(inst, mat, None, None)
@@ -157,12 +48,6 @@ def cpu_fragment(L, inst, cam, mat, i, j, time=0.0, opts=None, t=0.0, status=0):
     L.harness_billboard_fragment(h.ctypes.data, inst.ctypes.data, a.ctypes.data, d.ctypes.data, i, j, t, status, out.ctypes.data)
     return dict(covered=bool(out[0]), passed=bool(out[1]), u=out[2], v=out[3], dist=out[4], depth_t=out[5], albedo=out[6:9], alpha=out[9],
                 C=out[10:12], s=out[12], hx=out[13], hy=out[14], drawn=bool(out[15]))
-
-
-def blank_records(cam, color=(0.1, 0.2, 0.3)):
-    rec = np.zeros((cam.height, cam.width), W.RENDER_PIXEL)
-    rec["color"] = np.float32(color)
-    return rec
 
 
 def check_against_twin(got, tw, what, max_aside=None):
@@ -192,22 +77,14 @@ def twin_of(inst, cam, mat, time=0.0, order=None, opts=None, records=None, **kw)
 
 # ---- 1. the interface and the documents --------------------------------------------------------------------------------------------------
 
-HEADER = open(os.path.join(ROOT, "include", "ocean_waves.h")).read()
-
-
 def test_header_declares_the_billboard_calls_and_the_library_exports_them():
     build.build_library()
     lib = _lib.load()
-    text = re.sub(r"/\*.*?\*/", "", HEADER, flags=re.S)
-    for name in NEW_FUNCTIONS:
-        assert re.search(r"\b%s\s*\(" % name, text), name
-        assert name in _lib.SIGNATURES
-        assert getattr(lib, name)
+    text = check_declared_and_bound(lib, NEW_FUNCTIONS)
     for struct in STRUCTS:
         assert re.search(r"typedef struct %s \{" % struct, text), struct
         assert "ow_layout_check_%s" % struct[3:] in HEADER
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = set(re.findall(r" T (ow_[a-z0-9_]+)", out))
+    exported = exported_symbols()
     assert sorted(s for s in exported if "billboard" in s) == sorted(NEW_FUNCTIONS)      # no group form
     assert lib.ow_abi_version() == 4 and re.search(r"#define OW_ABI_VERSION 4\b", HEADER)
     section = HEADER.split("The spray billboards drawn into a camera view")[1].split("several devices")[0]
@@ -226,9 +103,7 @@ def test_billboard_structs_agree_in_c_ctypes_and_the_harness(tmp_path, harness):
     expr = ", ".join(["sizeof(%s)" % s for s in names] + ["offsetof(%s, %s)" % f for f in fields])
     src = ('#include <stdio.h>\n#include <stddef.h>\n#include "ocean_waves.h"\nint main(void){printf("%s\\n", ' % " ".join(["%zu"] * (2 + len(fields)))
            + expr + ");return 0;}\n")
-    exe = str(tmp_path / "billboard_layout")
-    subprocess.run(["gcc", "-std=c11", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-x", "c", "-", "-o", exe], input=src, text=True, check=True)
-    got = [int(v) for v in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split()]
+    got = layout_probe(tmp_path, "billboard_layout", src)
     want = [C.sizeof(STRUCTS[s]) for s in names] + [getattr(STRUCTS[s], f).offset for s, f in fields]
     assert got == want and got[:2] == [64, 64]
     off = dict(zip(fields, got[2:]))
@@ -243,10 +118,7 @@ def test_billboard_structs_agree_in_c_ctypes_and_the_harness(tmp_path, harness):
 
 
 def test_the_documents_and_the_csharp_binding_name_the_billboard_calls():
-    import test_integration_shim as S
-    for name in NEW_FUNCTIONS:
-        assert re.search(r"\[DllImport\(Lib\)\]\s*public static extern \w+ %s\(" % name, S.SHIM), name
-        assert "`%s`" % name in S.DOC.split("## 7. Index")[1], name
+    check_csharp_binds(NEW_FUNCTIONS)
     for cs, c in (("OwBillboardMaterialOptions", "ow_billboard_material_options"), ("OwBillboardDrawOptions", "ow_billboard_draw_options")):
         want, got = S.c_struct_fields(c), S.cs_struct_fields(cs)
         assert got == want and sum(s for _, s in want) == 64, (cs, got, want)
@@ -260,17 +132,9 @@ def test_the_documents_and_the_csharp_binding_name_the_billboard_calls():
     assert row12 and not any("out of scope" in ln.lower() for ln in row12)
 
 
-def build_example(tmp_path):
-    exe = str(tmp_path / "spray_draw_host")
-    subprocess.run(["gcc", "-O2", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "examples", "spray_draw_host.c"),
-                    "-o", exe, "-L", PKG, "-locean_waves", "-L", "/opt/rocm/lib", "-lamdhip64", f"-Wl,-rpath,{PKG}", "-Wl,-rpath,/opt/rocm/lib", "-lm"],
-                   check=True)
-    return exe
-
-
 def test_example_builds_as_c99(tmp_path):
     build.build_library()
-    build_example(tmp_path)
+    build_example(tmp_path, "spray_draw_host")
 
 
 def test_billboard_argument_errors_without_a_device():
@@ -415,11 +279,6 @@ def test_overlapping_billboards_blend_in_array_order(harness):
 
 # ---- 4. the depth test -------------------------------------------------------------------------------------------------------------------
 
-def calm_picture(mesh_harness, cam):
-    d, m, sc = calm_maps()
-    return cpu_mesh_draw(mesh_harness, d, m, sc, grid(16, 8.0), (0.0, 0.0, 0.0), cam)["rec"]
-
-
 def test_depth_test_against_a_calm_sea(harness, mesh_harness):
     """a camera 6 m above a flat sea, looking 20 degrees down: one billboard stands in the water 14 m ahead (its lower half is behind the
     surface as seen from the camera), another lies wholly below the surface further out"""
@@ -518,13 +377,6 @@ def scattered_instances(count, seed=11, depth=(6.0, 60.0), spread=1.2):
     rows = [((float(spread * rng.uniform(-1, 1) * s[k]), float(0.7 * spread * rng.uniform(-1, 1) * s[k]), float(-s[k])), float(rng.uniform(0.3, 4.0)),
              float(rng.uniform(0.3, 4.0)), float(rng.uniform(0.3, 1.0)), float(rng.uniform(0.2, 1.0))) for k in range(count)]
     return instances(rows)
-
-
-def same_picture(a, b, what):
-    assert a["rgba"].tobytes() == b["rgba"].tobytes(), what
-    if a["rec"] is not None or b["rec"] is not None:
-        for f in W.RENDER_PIXEL.names:
-            assert a["rec"][f].tobytes() == b["rec"][f].tobytes(), (what, f)
 
 
 def test_the_picture_does_not_depend_on_the_bins_side(harness):
@@ -665,9 +517,7 @@ def write_case(path, c, records):
 def test_stand_alone_harness_runs_clean_under_the_sanitizers(tmp_path, harness, emitter_scene):
     """the harness as a program of its own (-DSPRAY_DRAW_HARNESS_MAIN), built with -fsanitize=address,undefined, on the emitter's case and on
     every awkward case: the picture it writes is the shared library's"""
-    exe = str(tmp_path / "spray_draw_harness_main")
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    "-Wno-unknown-pragmas", "-DSPRAY_DRAW_HARNESS_MAIN", "-I", CSRC, HARNESS_SRC, "-o", exe], check=True)
+    exe = build_sanitized_harness("spray_draw", tmp_path)
     s = emitter_scene
     cases = dict(awkward_cases(), emitter=dict(inst=s["instances"], cam=s["cam"], mat=s["material"], time=s["time"], order=s["draw"], records=s["records"]))
     cases["4160 scattered, bins of 8"] = dict(inst=scattered_instances(4160), cam=level_camera(128, 72), mat=material(), time=1.25, opts={"bin_side": 8})
@@ -686,21 +536,12 @@ def test_stand_alone_harness_runs_clean_under_the_sanitizers(tmp_path, harness, 
 
 # ---- 9-15. on the GPU ------------------------------------------------------------------------------------------------------------------------
 
-def gpu_material(gen, mat):
-    return gen.spray_material_create(mat["albedo"], mat["dissolve"], {k: mat[k] for k in ("foam_color", "max_alpha", "albedo_srgb", "dissolve_srgb")})
-
-
 def gpu_case(gen, c, records):
     m = gpu_material(gen, c["mat"])
     rgba, rec = gen.spray_draw_instances(m, c["inst"], c.get("time", 0.0), c["cam"], c.get("opts"), pixels=records)
     stats = gen.spray_draw_stats()
     gen.spray_material_destroy(m)
     return dict(rgba=rgba, rec=rec, drawn=stats["drawn"], culled=stats["culled"])
-
-
-def bare_context():
-    """the smallest context: the billboard draw reads no map"""
-    return make_gen(128, [0, 1])[0]
 
 
 @pytest.mark.gpu
@@ -755,18 +596,6 @@ def emitter_on_the_device(n=256, stream=None, ticks=100, steps=EMITTER_STEPS):
         gen.update_all(UPDATE_DELTA, params)
         gen.spray_step(s, UPDATE_DELTA, sc)
     return gen, params, sc, s
-
-
-def device_buffers(cam):
-    import torch
-    count = cam.width * cam.height
-    return (torch.zeros((count, 4), dtype=torch.uint8, device="cuda:0"),
-            torch.zeros((count, W.RENDER_PIXEL.itemsize), dtype=torch.uint8, device="cuda:0"))
-
-
-def buffers_to_host(cam, rgba_dev, rec_dev):
-    return dict(rgba=rgba_dev.cpu().numpy().reshape(cam.height, cam.width, 4),
-                rec=np.frombuffer(rec_dev.cpu().numpy().tobytes(), W.RENDER_PIXEL).reshape(cam.height, cam.width).copy())
 
 
 @pytest.mark.gpu
@@ -945,30 +774,10 @@ def test_async_draw_argument_errors_write_nothing():
     lib.ow_spray_destroy(None, foreign_s.handle)
 
 
-def example_textures(size=64):
-    """examples/spray_draw_host.c's make_textures, integer for integer"""
-    s, lattice = 12345, np.zeros((8, 8), np.int64)
-    for j in range(8):
-        for i in range(8):
-            s = (s * 1664525 + 1013904223) % 2 ** 32
-            lattice[j, i] = (s >> 24) & 0xFF
-    j, i = np.meshgrid(np.arange(size), np.arange(size), indexing="ij")
-    albedo = np.full((size, size, 4), 255, np.uint8)
-    r2 = (2 * i + 1 - size) ** 2 + (2 * j + 1 - size) ** 2
-    albedo[..., 3] = np.where(r2 >= size * size, 0, 255 - (255 * r2) // (size * size)).astype(np.uint8)
-    cx, cy, fx, fy = i // 8, j // 8, i % 8, j % 8
-    top = lattice[cy, cx] * (8 - fx) + lattice[cy, (cx + 1) % 8] * fx
-    bot = lattice[(cy + 1) % 8, cx] * (8 - fx) + lattice[(cy + 1) % 8, (cx + 1) % 8] * fx
-    dissolve = np.zeros((size, size, 4), np.uint8)
-    dissolve[..., 0] = dissolve[..., 1] = dissolve[..., 2] = ((top * (8 - fy) + bot * fy) // 128).astype(np.uint8)
-    dissolve[..., 3] = 255
-    return albedo, dissolve
-
-
 @pytest.mark.gpu
 def test_the_c_example_writes_the_python_wrappers_image(tmp_path):
     """examples/spray_draw_host.c at 256^2, 96 x 64, 120 steps, 4096 particles, against the wrapper on the same scene"""
-    exe = build_example(tmp_path)
+    exe = build_example(tmp_path, "spray_draw_host")
     ppm = str(tmp_path / "spray.ppm")
     r = subprocess.run([exe, ppm, "96", "64", "120", "256", "4096"], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stderr

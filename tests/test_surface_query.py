@@ -8,126 +8,33 @@ maps.  GPU: the device records are those of the CPU build on the same maps, bit 
 square root correctly rounded; no library transcendental), the embedded sample is ow_sample_surface's, and the asynchronous form is ordered
 behind both chains of a context and ahead of its next work."""
 import ctypes as C
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
-import helpers as H
 import query_twin as T
 from godotoceanwaves_amd import _lib, build
 from godotoceanwaves_amd.presets import UPDATE_DELTA, cascade_preset
 from godotoceanwaves_amd.wave_generator import WaveGenerator
-from test_surface_sampling import SCALES3, query_points, random_maps
+import checks as S
+from checks import assert_same_records, check_against_twin, check_csharp_binds, check_declared_and_bound, exported_symbols
+from cpu_builds import cpu_query, cpu_sample, layout_probe, QUERY_REC as REC
+from cpu_builds import query_harness as harness  # noqa: F401 (fixtures)
+from scenes import generated_maps, gpu_maps, GROW_POINTS, make_gen, query_points, random_maps, SCALES3, scales_of, smallest_context
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "godotoceanwaves_amd", "csrc")
-HERE = os.path.dirname(os.path.abspath(__file__))
-REC = WaveGenerator.SURFACE_QUERY
 NEW_FUNCTIONS = ("ow_query_surface", "ow_query_surface_async", "ow_group_query_surface")
-
-
-# ---- the CPU build of the solver header ---------------------------------------------------------------------------------------------
-
-@pytest.fixture(scope="module")
-def harness(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("query") / "libquery_harness.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unknown-pragmas", "-I", CSRC,
-                    os.path.join(HERE, "query", "query_harness.cpp"), "-o", so], check=True)
-    L = C.CDLL(so)
-    V = C.c_void_p
-    L.harness_record_sizes.argtypes = [C.POINTER(C.c_int)] * 3
-    L.harness_sample.argtypes = [V, V, C.c_int, C.c_int, V, V, C.c_int, V]
-    L.harness_query.argtypes = [V, V, C.c_int, C.c_int, V, V, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.c_float, V]
-    L.harness_exp.argtypes = [V, C.c_int, V]
-    L.harness_eval.argtypes = [V, C.c_int, C.c_int, V, V, C.c_int, C.c_int, C.c_float, C.c_float, V]
-    L.harness_tap.argtypes = [V, C.c_int, C.c_int, V, V]
-    return L
-
-
-def maps_u16(maps):
-    m = np.ascontiguousarray(np.asarray(maps))
-    return m.view(np.uint16) if m.dtype != np.uint16 else m
-
-
-def cpu_query(L, disp, norm, scales, xz, max_iterations=0, tolerance=0.0, falloff_center=None):
-    """the records the CPU build writes, with the options resolved as the runtime resolves ow_query_options"""
-    d, m = maps_u16(disp), maps_u16(norm)
-    sc = np.ascontiguousarray(scales, np.float32)
-    xz = np.ascontiguousarray(xz, np.float32).reshape(-1, 2)
-    out = np.zeros(len(xz), REC)
-    it = max_iterations if max_iterations > 0 else 16
-    tol = tolerance if tolerance > 0 else 1e-3
-    cx, cz = falloff_center if falloff_center is not None else (0.0, 0.0)
-    L.harness_query(d.ctypes.data, m.ctypes.data, d.shape[1], len(sc), sc.ctypes.data, xz.ctypes.data, len(xz), it, tol,
-                    int(falloff_center is not None), cx, cz, out.ctypes.data)
-    return out
-
-
-def cpu_sample(L, disp, norm, scales, xz):
-    d, m = maps_u16(disp), maps_u16(norm)
-    sc = np.ascontiguousarray(scales, np.float32)
-    xz = np.ascontiguousarray(xz, np.float32).reshape(-1, 2)
-    out = np.zeros(len(xz), WaveGenerator.SURFACE_SAMPLE)
-    L.harness_sample(d.ctypes.data, m.ctypes.data, d.shape[1], len(sc), sc.ctypes.data, xz.ctypes.data, len(xz), out.ctypes.data)
-    return out
-
-
-def fp32_slack(disp, scales, p):
-    """how far an FP32 evaluation of |p + f D_xz(p) - q| may sit from the FP64 one at the same p: the texture coordinate p * s * N is
-    rounded twice (2^-23 relative), which moves each cascade's interpolant by that many texels times its largest texel step, plus the
-    rounding of the position and of the sums (a few ulp of |p| and of |D|)"""
-    d = T.as_f64(disp)
-    sc = np.asarray(scales, np.float64)
-    n = d.shape[1]
-    r = np.abs(np.asarray(p, np.float64)).max(axis=1)
-    per_texel = sum(sc[i, 2] * max(np.abs(np.diff(d[i][..., [0, 2]], axis=a)).max() for a in (0, 1)) for i in range(len(sc)))
-    return 2e-5 + r * 2.0 ** -21 + r * sc[:, :2].max() * n * 2.0 ** -22 * per_texel
-
-
-def generated_maps(n, ids, ticks=2):
-    g = H.oracle_generator(n, ids, native=True)
-    for _ in range(ticks):
-        g.update_all(UPDATE_DELTA)
-    d = np.stack([np.asarray(g.displacement(i)) for i in range(len(ids))])
-    m = np.stack([np.asarray(g.normal(i)) for i in range(len(ids))])
-    sc = np.array([(1 / cascade_preset(ci)["tile_length"][0], 1 / cascade_preset(ci)["tile_length"][1], 1.0, 1.0) for ci in ids], np.float32)
-    return maps_u16(d), maps_u16(m), sc
-
-
-def check_against_twin(out, disp, scales, xz, tol=1e-3, center=None):
-    assert all(np.isfinite(out[f]).all() for f in ("p", "residual", "falloff", "height", "normal"))
-    assert all(np.isfinite(out["sample"][f]).all() for f in ("displacement", "gradient", "gradient_scaled", "foam", "gradient_fragment"))
-    r64 = T.residual(disp, scales, out["p"], xz, center)
-    slack = fp32_slack(disp, scales, out["p"])
-    c = out["converged"].astype(bool)
-    assert (r64[c] <= tol + slack[c]).all(), (r64[c] - tol - slack[c]).max()
-    assert (out["residual"][c] <= tol).all()
-    assert (out["residual"][~c] > tol).all()
-    assert (np.abs(out["residual"][~c] - r64[~c]) <= slack[~c]).all()
-    assert np.array_equal(out["world_xz"], np.asarray(xz, np.float32))
-    return c
 
 
 # ---- 1. the ABI ----------------------------------------------------------------------------------------------------------------------
 
-HEADER = open(os.path.join(ROOT, "include", "ocean_waves.h")).read()
-
-
 def test_header_declares_the_query_and_the_library_exports_it():
     build.build_library()
     lib = _lib.load()
-    text = re.sub(r"/\*.*?\*/", "", HEADER, flags=re.S)
-    for name in NEW_FUNCTIONS:
-        assert re.search(r"\b%s\s*\(" % name, text), name
-        assert name in _lib.SIGNATURES
-        assert getattr(lib, name)
+    text = check_declared_and_bound(lib, NEW_FUNCTIONS)
     for struct in ("ow_query_options", "ow_surface_query"):
         assert re.search(r"typedef struct %s \{" % struct, text), struct
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    assert set(NEW_FUNCTIONS) <= set(re.findall(r" T (ow_[a-z0-9_]+)", out))
+    assert set(NEW_FUNCTIONS) <= exported_symbols()
     assert lib.ow_abi_version() == 4
 
 
@@ -139,9 +46,7 @@ def test_query_structs_agree_in_c_ctypes_numpy_and_the_solver(tmp_path, harness)
            'offsetof(ow_surface_query, converged), offsetof(ow_surface_query, falloff), offsetof(ow_surface_query, height),'
            'offsetof(ow_surface_query, normal), offsetof(ow_surface_query, world_xz), offsetof(ow_surface_query, reserved),'
            'offsetof(ow_surface_query, sample), OW_QUERY_DISTANCE_FALLOFF);return 0;}\n')
-    exe = str(tmp_path / "query_layout")
-    subprocess.run(["gcc", "-std=c11", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-x", "c", "-", "-o", exe], input=src, text=True, check=True)
-    got = [int(v) for v in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split()]
+    got = layout_probe(tmp_path, "query_layout", src)
     O, Q = _lib.ow_query_options, _lib.ow_surface_query
     want = [C.sizeof(O), O.tolerance.offset, O.flags.offset, O.falloff_center_xz.offset, O.reserved.offset, C.sizeof(Q), C.alignment(Q),
             Q.residual.offset, Q.iterations.offset, Q.evaluations.offset, Q.converged.offset, Q.falloff.offset, Q.height.offset,
@@ -158,7 +63,6 @@ def test_query_structs_agree_in_c_ctypes_numpy_and_the_solver(tmp_path, harness)
 def test_the_csharp_binding_shows_the_query_structs_and_functions():
     """the two new [StructLayout] structs list the C fields in order with the same sizes (the embedded record counted as
     its 64 bytes), and the three functions are bound; §7 names them"""
-    import test_integration_shim as S
     c_sizes = dict(S.C_SIZES, ow_surface_sample=64)
     cs_sizes = dict(S.CS_SIZES, OwSurfaceSample=64)
 
@@ -183,9 +87,7 @@ def test_the_csharp_binding_shows_the_query_structs_and_functions():
         assert got == want, (cs, got, want)
     assert sum(s for _, s in fields(re.search(r"typedef struct ow_surface_query \{(.*?)\}", S.strip_comments(S.HEADER), flags=re.S).group(1),
                                      c_sizes, lambda d: d)) == 128
-    for name in NEW_FUNCTIONS:
-        assert re.search(r"\[DllImport\(Lib\)\]\s*public static extern int %s\(" % name, S.SHIM), name
-        assert "`%s`" % name in S.DOC.split("## 7. Index")[1], name
+    check_csharp_binds(NEW_FUNCTIONS, returns="int")
 
 
 # ---- 2. argument checks without a device ---------------------------------------------------------------------------------------------
@@ -315,25 +217,6 @@ def test_convergence_rate_on_the_demo_scene(harness):
 
 
 # ---- 6-9. on the GPU -------------------------------------------------------------------------------------------------------------------
-
-def make_gen(n, ids, stream=None):
-    from godotoceanwaves_amd import WaveCascadeParameters
-    gen = WaveGenerator()
-    gen.map_size = n
-    if stream is not None:
-        gen.stream = stream
-    gen.init_gpu(max(2, len(ids)))
-    return gen, [WaveCascadeParameters(**cascade_preset(ci)) for ci in ids]
-
-
-def scales_of(params):
-    return np.array([(1 / p.tile_length[0], 1 / p.tile_length[1], p.displacement_scale, p.normal_scale) for p in params], np.float32)
-
-
-def gpu_maps(gen, count):
-    maps = [gen.get_maps(i) for i in range(count)]
-    return np.stack([mp[0] for mp in maps]), np.stack([mp[1] for mp in maps])
-
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("n,ids", [(1024, [0, 1, 2]), (256, [0, 1, 2, 3]), (2048, [0])])
@@ -473,21 +356,6 @@ def test_group_query_equals_a_single_context():
 
 
 # ---- 10. the grow-only scratch of the synchronous calls ------------------------------------------------------------------------------------
-
-GROW_POINTS = (16, 4097, 16)   # under the scratch's floor of 4 096 points, one past it (the block is replaced), under it again (the larger block stays)
-
-
-def smallest_context():
-    """128^2 x 2, three ticks in: (generator, map scales, displacement, normal maps)"""
-    gen, params = make_gen(128, [0, 1])
-    gen.run(UPDATE_DELTA, params, 3)
-    return (gen, scales_of(params)) + gpu_maps(gen, 2)
-
-
-def assert_same_records(got, want, what):
-    for f in got.dtype.names:
-        assert got[f].tobytes() == want[f].tobytes(), (what, f)
-
 
 @pytest.mark.gpu
 def test_point_scratch_grows_past_its_floor_and_stays(harness):

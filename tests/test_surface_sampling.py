@@ -12,58 +12,12 @@ from godotoceanwaves_amd import _lib
 from godotoceanwaves_amd.presets import UPDATE_DELTA, cascade_preset
 from oracle import oracle as O
 from oracle import ref as R
-
-SCALES3 = np.array([[1 / 88, 1 / 88, 1.0, 1.0], [1 / 57, 1 / 57, 0.75, 0.5], [1 / 16, 1 / 16, 0.5, 0.25]], np.float32)
-
-
-def random_maps(C, N, seed=0, foam_hi=0.6):
-    rng = np.random.default_rng(seed)
-    d = rng.standard_normal((C, N, N, 4)).astype(np.float16)
-    m = (rng.standard_normal((C, N, N, 4)) * 0.3).astype(np.float16)
-    m[..., 3] = rng.uniform(0, foam_hi, (C, N, N)).astype(np.float16)
-    return d, m
-
-
-def query_points(count, seed=1, span=700.0):
-    """random points plus the awkward ones: origin, texel centres and edges, negative coordinates, far away"""
-    rng = np.random.default_rng(seed)
-    xz = rng.uniform(-span, span, (count, 2)).astype(np.float32)
-    xz[:8] = [[0, 0], [88 / 256 * 0.5, 88 / 256 * 0.5], [88.0, 88.0], [-88.0, 57.0], [-0.001, -0.001], [1e4, -1e4], [16.0, -16.0], [44.0, 28.5]]
-    return xz
+from scenes import FIELDS_PINNED, query_points, random_maps, ref_sampling_digests, sampling_case, SCALES3
 
 
 def test_record_layout_is_the_same_on_every_side():
     from godotoceanwaves_amd import WaveGenerator
     assert O.SURFACE_SAMPLE.itemsize == 64 and WaveGenerator.SURFACE_SAMPLE == O.SURFACE_SAMPLE
-
-
-FIELDS_PINNED = ["displacement", "gradient", "foam", "normal_factor", "foam_factor", "scale_factor", "spray_active",
-                 "gradient_fragment", "foam_fragment"]
-
-
-def sampling_case(case):
-    """maps, scales and query points of one case of the test below (tests/golden/make_ref_digests.py samples the same)"""
-    sc = SCALES3
-    if case == "random_maps":
-        d, m = random_maps(3, 64)
-    elif case == "spray_active":  # foam near 1 and flat normals: ACTIVE both ways, both factor branches
-        d, m = random_maps(3, 32, seed=5, foam_hi=0.7)
-        m[..., :2] *= np.float16(0.1)
-    elif case == "fine_cascades":  # ppm * 0.1 >= 1 on every cascade: the mix takes the bilinear lookup alone
-        d, m = random_maps(3, 64, seed=7)
-        sc = np.array([[1 / 5, 1 / 4, 1.0, 1.3], [1 / 3, 1 / 6, 0.75, 0.5], [1 / 2, 1 / 2, 0.5, 0.25]], np.float32)
-    else:  # maps the pipeline itself produced (oracle generator), three cascades
-        g = H.oracle_generator(128, [0, 1, 2])
-        for _ in range(2):
-            g.update_all(UPDATE_DELTA)
-        d = np.stack([g.displacement(i) for i in range(3)])
-        m = np.stack([g.normal(i) for i in range(3)])
-    return d, m, sc, query_points(3000, seed=11)
-
-
-def ref_sampling_digests(r, dp):
-    """what the reference's shader text computed for one case: FIELDS_PINNED and the particle shader's displacement sum"""
-    return {**{f: H.digest(r[f]) for f in FIELDS_PINNED}, "particle_displacement": H.digest(dp)}
 
 
 @pytest.mark.parametrize("case", ["random_maps", "generated_maps", "spray_active", "fine_cascades"])

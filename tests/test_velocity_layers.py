@@ -17,7 +17,7 @@ from edge_presets import edge_presets
 from godotoceanwaves_amd import WaveCascadeParameters, WaveGenerator
 from godotoceanwaves_amd.presets import DEPTH, UPDATE_DELTA, cascade_preset
 from oracle import oracle as O
-from test_water_velocity import FLOOR, check_layer
+from checks import check_layer, VELOCITY_FLOOR as FLOOR
 
 SIZES = (128, 256, 512, 1024, 2048)
 CALM = "calm_min_wind_short_fetch"

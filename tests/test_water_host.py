@@ -17,7 +17,7 @@ from godotoceanwaves_amd import WaveCascadeParameters
 from godotoceanwaves_amd.presets import DEPTH, cascade_preset
 from godotoceanwaves_amd.water import Water
 from oracle import oracle as O
-from test_c_consumer import PKG, ROOT
+from cpu_builds import PKG, ROOT
 
 SCRIPT = """
 params 3

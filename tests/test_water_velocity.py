@@ -7,88 +7,25 @@ C++ (tests/velocity/velocity_harness.cpp, g++ -ffp-contract=off) against an FP64
 an FP64 NumPy twin of the derivative at every map size, against a central difference of the FP32 maps, after every schedule; the laziness;
 the device records against the CPU build bit for bit; buoyancy with and without the flag."""
 import ctypes as C
-import os
 import re
 import subprocess
 
 import numpy as np
 import pytest
 
-import helpers as H
 from godotoceanwaves_amd import _lib, build
 from godotoceanwaves_amd.presets import UPDATE_DELTA, cascade_preset
 from godotoceanwaves_amd.wave_generator import WaveGenerator as W
-from test_buoyancy import RHO, RHO_G, cpu_buoyancy, harness as buoyancy_harness, make_scene  # noqa: F401
-from test_surface_query import (GROW_POINTS, assert_same_records, cpu_query, cpu_sample, gpu_maps, harness as query_harness, make_gen, maps_u16,  # noqa: F401
-                                scales_of, smallest_context)
-from velocity_twin import phases, velocity_twin
+from checks import assert_same_records, check_layer, HEADER
+from cpu_builds import cpu_buoyancy, cpu_buoyancy_moving, cpu_query, cpu_query_velocity, cpu_sample, layout_probe, VELOCITY_REC as REC
+from cpu_builds import buoyancy_harness, query_harness, velocity_harness as harness  # noqa: F401 (fixtures)
+from scenes import bilinear64, gpu_maps, GROW_POINTS, make_gen, make_scene, RHO, RHO_G, scales_of, smallest_context, velocity_layers as _vel_layers
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "godotoceanwaves_amd", "csrc")
-HERE = os.path.dirname(os.path.abspath(__file__))
-HEADER = open(os.path.join(ROOT, "include", "ocean_waves.h")).read()
 NEW_FUNCTIONS = ("ow_update_velocity", "ow_get_velocity_ptrs", "ow_get_velocity_map", "ow_velocity_stats", "ow_query_velocity",
                  "ow_query_velocity_async")
-REC = W.SURFACE_VELOCITY
 # The twin's floor relative to a channel's largest |v| (helpers.fp16_close): the layers are FP32 transforms of an FP32 spectrum, like the
 # maps, but the derivative weighs every mode by omega, so the high wave numbers -- where the FP32 wave-vector and phase arithmetic is least
 # exact relative to the mode -- carry more of the sum than in D.  2e-5 of max|v| is still five times tighter than FP16's own 2^-11.
-FLOOR = 2e-5
-
-
-@pytest.fixture(scope="module")
-def harness(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("velocity") / "libvelocity_harness.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unknown-pragmas", "-I", CSRC,
-                    os.path.join(HERE, "velocity", "velocity_harness.cpp"), "-o", so], check=True)
-    L = C.CDLL(so)
-    V = C.c_void_p
-    L.harness_velocity_sizes.argtypes = [V]
-    L.harness_query_velocity.argtypes = [V, V, C.c_int, C.c_int, V, V, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.c_float, V]
-    L.harness_buoyancy_moving.argtypes = [V, V, C.c_int, C.c_int, V, V, C.c_int, V, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float,
-                                          C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, V, V]
-    return L
-
-
-def cpu_query_velocity(L, disp, vel, scales, xz, falloff_center=None):
-    d, v = maps_u16(disp), maps_u16(vel)
-    sc = np.ascontiguousarray(scales, np.float32)
-    xz = np.ascontiguousarray(xz, np.float32).reshape(-1, 2)
-    out = np.zeros(len(xz), REC)
-    cx, cz = falloff_center if falloff_center is not None else (0.0, 0.0)
-    L.harness_query_velocity(d.ctypes.data, v.ctypes.data, d.shape[1], len(sc), sc.ctypes.data, xz.ctypes.data, len(xz), 16, 1e-3,
-                             int(falloff_center is not None), cx, cz, out.ctypes.data)
-    return out
-
-
-def cpu_buoyancy_moving(L, disp, vel, scales, bodies, hull, water_level=0.0):
-    d, v = maps_u16(disp), maps_u16(vel)
-    sc = np.ascontiguousarray(scales, np.float32)
-    b = np.ascontiguousarray(bodies, W.BUOYANCY_BODY)
-    h = np.ascontiguousarray(hull, W.HULL_POINT)
-    pts = np.zeros(len(h), W.BUOYANCY_POINT)
-    res = np.zeros(len(b), W.BUOYANCY_RESULT)
-    L.harness_buoyancy_moving(d.ctypes.data, v.ctypes.data, d.shape[1], len(sc), sc.ctypes.data, b.ctypes.data, len(b), h.ctypes.data, len(h),
-                              16, 1e-3, 0, 0.0, 0.0, RHO, RHO_G, water_level, 0, pts.ctypes.data, res.ctypes.data)
-    return res, pts
-
-
-# ---- the FP64 twin of the derivative: tests/velocity_twin.py ---------------------------------------------------------------------------
-
-def check_layer(gen, i, floor=FLOOR, m=None, calm=False):
-    """layer i of V against the twin at the layer's own words; returns the worst ratio to the allowance.
-    floor: the record's floor where it is not FLOOR (tests/test_velocity_layers.py); m: the twin's unit phasors as a function of the FP32
-    phases (the long-session cases); calm: a sea whose layer may lie below FP16's range -- no non-triviality check"""
-    got = gen.velocity_map(i)
-    h0, om = gen.get_spectrum(i)
-    _, mod, _ = gen.get_push_constants(i)
-    want = velocity_twin(h0, om, mod, m=None if m is None else m(phases(om, mod)))
-    assert np.all(got[..., 3].view(np.uint16) == 0)
-    assert np.isfinite(got.astype(np.float32)).all()
-    r = H.fp16_close(got[..., :3], want.astype(np.float16), ulps=1, rel_floor=floor)
-    assert r <= 1.0, (i, r)
-    assert calm or np.abs(want).max() > 1e-3  # the layer is not trivially zero
-    return r
 
 
 # ---- CPU ---------------------------------------------------------------------------------------------------------------------------
@@ -98,13 +35,10 @@ def test_header_is_plain_c99_and_declares_the_velocity_entry_points(tmp_path):
     for name in NEW_FUNCTIONS:
         assert re.search(r"\b%s\s*\(" % name, text), name
     assert "#define OW_BUOYANCY_WATER_VELOCITY 2u" in HEADER
-    src = tmp_path / "v.c"
-    src.write_text('#include "ocean_waves.h"\n#include <stdio.h>\nint main(void){printf("%d %d %d %d\\n",(int)sizeof(ow_surface_velocity),'
-                   '(int)offsetof(ow_surface_velocity,height),(int)offsetof(ow_surface_velocity,p),(int)offsetof(ow_surface_velocity,converged));'
-                   'return 0;}\n')
-    exe = str(tmp_path / "v")
-    subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", exe], check=True)
-    got = [int(v) for v in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split()]
+    src = ('#include "ocean_waves.h"\n#include <stdio.h>\nint main(void){printf("%d %d %d %d\\n",(int)sizeof(ow_surface_velocity),'
+           '(int)offsetof(ow_surface_velocity,height),(int)offsetof(ow_surface_velocity,p),(int)offsetof(ow_surface_velocity,converged));'
+           'return 0;}\n')
+    got = layout_probe(tmp_path, "v", src, std=("-std=c99", "-pedantic", "-Wall", "-Werror"))
     assert got == [32, 12, 16, 24]
 
 
@@ -164,17 +98,6 @@ def synthetic(n=64, cascades=3, seed=0):
     vel[..., 3] = 0
     sc = np.array([(1 / (40.0 + 30 * i), 1 / (35.0 + 20 * i), 0.8 + 0.1 * i, 1.0) for i in range(cascades)], np.float32)
     return disp, vel, sc
-
-
-def bilinear64(layer, u, v):
-    n = layer.shape[0]
-    fx, fy = u * n - 0.5, v * n - 0.5
-    x0, y0 = np.floor(fx), np.floor(fy)
-    wx, wy = (fx - x0)[:, None], (fy - y0)[:, None]
-    c0, r0 = x0.astype(np.int64) % n, y0.astype(np.int64) % n
-    c1, r1 = (c0 + 1) % n, (r0 + 1) % n
-    L = layer.astype(np.float64)
-    return (L[r0, c0] * (1 - wx) + L[r0, c1] * wx) * (1 - wy) + (L[r1, c0] * (1 - wx) + L[r1, c1] * wx) * wy
 
 
 def test_host_velocity_and_moving_drag_against_the_fp64_twin(harness):
@@ -433,10 +356,6 @@ def test_never_computed_layers_are_refused():
 
 
 # ---- GPU: the query and buoyancy ---------------------------------------------------------------------------------------------------
-
-def _vel_layers(gen, count):
-    return np.stack([gen.velocity_map(i) for i in range(count)])
-
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("n,ids", [(1024, [0, 1, 2, 3]), (256, [0, 1, 2])])

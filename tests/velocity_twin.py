@@ -3,14 +3,11 @@ ifft2_ref / unpack conventions with hdot in place of h.  Test infrastructure: te
 scripts/velocity_margins.py."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
 import np_twin as NT
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-CSRC = os.path.join(HERE, "..", "godotoceanwaves_amd", "csrc")
+from cpu_builds import CSRC, HERE, compile_shared
 
 
 def modulate_words(tile_length, time, depth=20.0):
@@ -89,8 +86,7 @@ def emul_library():
     so = os.path.join(HERE, "velocity", "libvelocity_emul.so")
     srcs = [os.path.join(HERE, "velocity", "velocity_emul.cpp")] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unknown-pragmas", "-I", CSRC, srcs[0], "-o", so],
-                       check=True)
+        compile_shared(srcs[0], so)
     E = C.CDLL(so)
     f32p = np.ctypeslib.ndpointer(np.float32, flags="C")
     E.velemul_layer.argtypes = [C.c_int, f32p, f32p, C.c_float, C.c_float, C.c_float, C.c_void_p, np.ctypeslib.ndpointer(np.uint16, flags="C")]
