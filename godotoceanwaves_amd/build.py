@@ -17,6 +17,7 @@ UNITS = {
     "ow_frame.hip": [],
     "ow_spectrum.hip": ["-ffp-contract=off"],
     "ow_runtime.hip": [],
+    "ow_schedule.hip": [],
     "ow_consumer_host.hip": [],
     "ow_consumer.hip": ["-ffp-contract=off"],
     "ow_group.hip": [],

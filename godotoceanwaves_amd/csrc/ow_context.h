@@ -1,15 +1,35 @@
-// ow_context.h -- the context behind include/ocean_waves.h and the handles that hang off it, for the two host units that work on them:
-// ow_runtime.hip (the frame scheduler, create / destroy, hand-off, readback) and ow_consumer_host.hip (the read side).  Every handle kind
-// derives from ow::Handle and the context keeps ONE list of them: ow_consumer_host.hip holds their one life cycle, ow_destroy orphans
-// whatever is still on the list.
+// ow_context.h -- the context behind include/ocean_waves.h and the handles that hang off it, for the three host units that work on them:
+// ow_schedule.hip (the frame scheduler), ow_runtime.hip (create / destroy, status, scratch, hand-off, readback) and ow_consumer_host.hip (the
+// read side).  Every handle kind derives from ow::Handle and the context keeps ONE list of them: ow_consumer_host.hip holds their one life
+// cycle, ow_destroy orphans whatever is still on the list.
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
 #include <vector>
 
 #include "ow_internal.h"
 
 namespace ow {
+// The FP32 time a record will be processed with `updates` updates from now: one FP64 add per update, in order (wave_generator.gd:103), narrowed
+// last, by the pack (render_context.gd:131-134).
+inline float time_after(double time, double delta, int updates) {
+    for (int k = 0; k < updates; ++k) time += delta;
+    return (float)time;
+}
+// Pass 1 of one cascade AS IT WAS COMPUTED ahead of time: all it depends on besides the layer's resident spectrum.
+struct Pass1Key {
+    int cascade = 0;
+    float time = 0.0f, tile_x = 0.0f, tile_y = 0.0f;
+    bool same_tiles(const ow_cascade_params &p) const { return p.tile_length[0] == tile_x && p.tile_length[1] == tile_y; }
+    // is this what record p of `cascade` asks for `updates` updates of `delta` from now (0: as it is armed)?  FP32 times are compared bit for bit.
+    bool serves(int for_cascade, const ow_cascade_params &p, double delta = 0.0, int updates = 0) const {
+        const float t = time_after(p.time, delta, updates);
+        return cascade == for_cascade && std::memcmp(&t, &time, 4) == 0 && same_tiles(p);
+    }
+};
+inline Pass1Key pass1_key(int cascade, float time, const ow_cascade_params &p) { return Pass1Key{cascade, time, p.tile_length[0], p.tile_length[1]}; }
+
 // What every device-resident handle of a context starts with.  No virtual destructor: the typed entry points delete their own type.
 struct Handle {
     ow_context *ctx = nullptr;  // nullptr: orphaned by ow_destroy (the device block is gone, the handle is still the caller's to destroy)
@@ -118,15 +138,13 @@ struct ow_context {
     uint64_t spectra_generated = 0, spectra_skipped = 0;  // ow_spectrum_stats
     // ow_update_all's adaptive look-ahead (lookahead_tick below): a pass 1 of the NEXT tick, speculated with the caller's last delta.
     // Invariant: queued > 0 exactly while the scratch holds pass 1 of `queued` ticks that nothing has disturbed since; whatever else
-    // writes the scratch (or may have corrupted it) sets queued = 0, and no field below is read while it is 0.
+    // writes the scratch (or may have corrupted it) drops it (ow::drop_computed_ahead, ow_schedule.h), and no field below is read while it is 0.
     struct Lookahead {
         static constexpr int kMaxAhead = 4;  // ticks of pass 1 one launch may compute ahead (group kernel; the pair kernel takes one)
         int count = 0, mode = 0;       // cascades per tick; 1 = compact family (pair kernel), 2 = layer-parallel compact family (group kernel)
         int queued = 0, head = 0;      // ring of ticks computed ahead: entries head, head + 1, .. (mod kMaxAhead)
         int group[kMaxAhead] = {};     // scratch group (of `stride` launch slots) that holds each entry's intermediate
-        float time[kMaxAhead][OW_MAX_CASCADES] = {};  // the FP32 times each entry was computed with, per launch slot
-        int cascade[kMaxAhead][OW_MAX_CASCADES] = {};  // which cascades (per launch slot of the launch that will use the entry), and
-        float tile_x[kMaxAhead][OW_MAX_CASCADES] = {}, tile_y[kMaxAhead][OW_MAX_CASCADES] = {};  // the tile lengths their pass 1 was computed with
+        ow::Pass1Key p1[kMaxAhead][OW_MAX_CASCADES] = {};  // what each entry holds, per launch slot of the launch that will use the entry
         int cur_group = 0;             // group that held the most recent launch's own intermediate
         double last_delta = -1.0;      // the previous ow_update's delta, and for how many calls in a row it has been the same
         double streak_delta = -1.0;    // ... "the same" = equal to the delta that STARTED the streak (a slowly ramping delta is not one unbroken streak)
@@ -143,8 +161,8 @@ struct ow_context {
         int count = 0;               // cascades per tick of the run that computed it
         int D = 0, ticks = 0, pos = 0;  // kind 1: ticks per group of that run, ticks computed ahead, ring position (in ticks, mod 2 D) of the first of them
         int batch = 0, first = 0, size = 0, parity = 0;  // kind 2: the batch (its first launch slot, its cascades) and the half of the scratch its intermediate is in
-        float time[ow::kMaxTickGroup][OW_MAX_CASCADES] = {};  // the FP32 times it was computed with, per tick (kind 2: entry 0) and launch slot
-        float tile_x[OW_MAX_CASCADES] = {}, tile_y[OW_MAX_CASCADES] = {};  // ... and the tile lengths, per launch slot
+        ow::Pass1Key p1[ow::kMaxTickGroup][OW_MAX_CASCADES] = {};  // what it holds, per tick (kind 2: entry 0) and launch slot; kind 2 keeps the tile lengths of
+                                                                // the other batches' slots there too (the run checks them: run_resume_usable)
         bool last_was_run = false;   // the most recent tick-advancing call was an ow_run (lowered by ow_update / ow_update_all / ow_process from outside a run)
         int last_count = 0;
         double last_delta = 0.0;
@@ -212,7 +230,7 @@ struct ow_context {
     uint64_t host_syncs = 0;  // stream synchronisations made on the caller's thread since ow_create (ow_sync_stats)
 };
 
-// The scheduler's services the read side needs (ow_runtime.hip).
+// The services of the frame side the read side needs (main_stream: ow_schedule.hip, the others: ow_runtime.hip).
 namespace ow {
 // The stream everything but a first-chain launch is enqueued on or synchronised through: joins the second chain first (a no-op when none is in flight).
 hipStream_t main_stream(ow_context *c);

@@ -16,7 +16,7 @@ namespace ow {
 ow_status fail(ow_status st, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 // replaces the calling thread's ow_last_error() text (a group hands a worker thread's message to its caller; ow_runtime.hip)
 void set_last_error(const char *message);
-// every record finite, tile_length positive, time + delta finite (ow_runtime.hip; sets the error text)
+// every record finite, tile_length positive, time + delta finite (ow_schedule.hip; sets the error text)
 ow_status validate_records(const ow_cascade_params *params, int count, double delta);
 // the context's device status word without synchronising (ow_runtime.hip)
 ow_status poll_status(ow_context *c);

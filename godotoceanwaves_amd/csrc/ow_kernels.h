@@ -1,4 +1,4 @@
-// ow_kernels.h -- internal launcher interface between the host units (ow_runtime.hip: the frame launchers; ow_consumer_host.hip and
+// ow_kernels.h -- internal launcher interface between the host units (ow_schedule.hip: the frame launchers; ow_consumer_host.hip and
 // ow_group.hip: the consumer launchers) and the HIP translation units that hold the kernels.
 #pragma once
 #include <hip/hip_runtime.h>

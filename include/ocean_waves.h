@@ -109,7 +109,7 @@ typedef struct ow_config {
  *    later and re-reads its spectra and foam from the Infinity Cache: cascades are independent, the state ow_run leaves behind is the same.
  * Results are bit-identical to one launch per pass; this flag keeps ow_run on one pair of launches per tick (tests, measurements).
  * The shipped library reads NOTHING from the environment.  (A/B builds compiled with -DOW_MEASUREMENT_KNOBS read the OW_DEBUG_* variables listed
- * in ow_runtime.hip plan_tick_groups once, in ow_create; one of them, OW_DEBUG_RUN_DELTA_CHANGE_EVERY, changes the deltas the call-by-call forms
+ * in ow_schedule.hip plan_tick_groups once, in ow_create; one of them, OW_DEBUG_RUN_DELTA_CHANGE_EVERY, changes the deltas the call-by-call forms
  * of ow_run issue and with them the results.) */
 #define OW_FLAG_NO_TICK_GROUPS 16u
 /* ow_run issues its ticks exactly as an external caller of ow_update_all would, one call per tick (no merging across the ticks of the run);

@@ -3,7 +3,7 @@
 boundary; a straight-line fit region(K) = a + b K gives the fixed cost a per call (launch latency + wake-up of the synchronising host + whatever
 the call's own first / last launches waste) and the steady rate b per tick.  (Round 5: the driver times 20-tick regions; ow_run's ordinary first
 tick and the two half-filled launches at the ends of a run of tick pairs showed up there as 2 us per tick -- now a seamless stream for single-batch
-ticks, ow_runtime.hip ow_run.)
+ticks, ow_schedule.hip ow_run.)
     python scripts/run_overhead.py [n:c ...]"""
 import os, statistics, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -94,7 +94,7 @@ def spectrum_pc(preset):
 
 
 def record_pc(rec, depth=DEPTH):
-    """The spectrum push constants of one parameter record, packed as the runtime packs them (ow_runtime.hip pack_spectrum, after
+    """The spectrum push constants of one parameter record, packed as the runtime packs them (ow_schedule.hip pack_spectrum, after
     wave_generator.gd:69-71): wind speed and fetch clamped to 1e-4 (the exported setters), alpha and the peak frequency from the FP64 values,
     deg_to_rad in FP64, every scalar narrowed to FP32 only at the pack."""
     U, F = max(rec["wind_speed"], 1e-4), max(rec["fetch_length"], 1e-4) * 1e3

@@ -1,4 +1,4 @@
-"""ow_run after ow_run (include/ocean_waves.h, ow_runtime.hip run_impl): the last launch of a run that followed a run with the same delta and cascade
+"""ow_run after ow_run (include/ocean_waves.h, ow_schedule.hip run_impl): the last launch of a run that followed a run with the same delta and cascade
 count also carries pass 1 of what the next such run starts with -- the first tick group, or the next tick of the batch the cascade-major pair stream
 ended on -- and the next run resumes in the middle of the stream: no ordinary first tick, no half-filled launches at the ends.  Whatever happens in
 between, the maps are BITWISE those of a context that never merges anything (OW_FLAG_NO_TICK_GROUPS)."""

@@ -92,7 +92,7 @@ def test_tick_pairs_equal_one_launch_per_pass(n, ids, frames):
 
 @pytest.mark.parametrize("n,ids,frames", [(1024, [0, 1, 2, 3, 4], 150), (2048, [0, 1, 2], 70), (1024, [0, 1, 2, 3, 4, 5, 6, 7], 67)])
 def test_cascade_major_stream_equals_one_launch_per_pass_across_block_boundaries(n, ids, frames):
-    """A tick of several batches goes out cascade-major in blocks of 64 ticks (ow_runtime.hip run_tick_pairs): batch 0 through 64 ticks, then
+    """A tick of several batches goes out cascade-major in blocks of 64 ticks (ow_schedule.hip run_tick_pairs): batch 0 through 64 ticks, then
     batch 1 through the same 64, ...  Runs longer than a block, with a partial last block, unequal batches (3 + 2) and the split-plan kernels,
     against the same ticks one launch per pass: same bits, same times."""
     a, pa = make(n, ids, True)
