@@ -10,25 +10,31 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libocean_waves.so")
 ARCH = "gfx950"
 
-# translation unit -> extra flags.  ow_spectrum.hip is built with FP contraction off: its omega(k)
-# plane must be bit-identical to the oracle's; ow_consumer.hip, ow_mesh.hip, ow_spray.hip, ow_spray_draw.hip, ow_solid.hip, ow_environment.hip, ow_sky_light.hip and ow_shadow.hip likewise (the sampling,
-# raster, particle, billboard, solid, environment, sky-light and shadow arithmetic is checked operation for operation).
+# translation unit -> extra flags.  The rule: a unit that holds kernels whose arithmetic is checked operation for operation against its
+# reference (for ow_spectrum.hip bit for bit: SURVEY.md H1) is built with FP contraction off; host units and the other kernels take none.
+EXACT = ["-ffp-contract=off"]
 UNITS = {
     "ow_frame.hip": [],
-    "ow_spectrum.hip": ["-ffp-contract=off"],
+    "ow_spectrum.hip": EXACT,
     "ow_runtime.hip": [],
     "ow_schedule.hip": [],
     "ow_consumer_host.hip": [],
-    "ow_consumer.hip": ["-ffp-contract=off"],
+    "ow_points_host.hip": [],
+    "ow_bodies_host.hip": [],
+    "ow_mesh_host.hip": [],
+    "ow_spray_host.hip": [],
+    "ow_solid_host.hip": [],
+    "ow_sky_host.hip": [],
+    "ow_consumer.hip": EXACT,
     "ow_group.hip": [],
     "ow_velocity.hip": [],
-    "ow_mesh.hip": ["-ffp-contract=off"],
-    "ow_spray.hip": ["-ffp-contract=off"],
-    "ow_spray_draw.hip": ["-ffp-contract=off"],
-    "ow_solid.hip": ["-ffp-contract=off"],
-    "ow_environment.hip": ["-ffp-contract=off"],
-    "ow_sky_light.hip": ["-ffp-contract=off"],
-    "ow_shadow.hip": ["-ffp-contract=off"],
+    "ow_mesh.hip": EXACT,
+    "ow_spray.hip": EXACT,
+    "ow_spray_draw.hip": EXACT,
+    "ow_solid.hip": EXACT,
+    "ow_environment.hip": EXACT,
+    "ow_sky_light.hip": EXACT,
+    "ow_shadow.hip": EXACT,
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-fno-fast-math", "-fvisibility=hidden", "-Wall", "-Wno-unused-function"]
 

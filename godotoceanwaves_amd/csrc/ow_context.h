@@ -1,7 +1,7 @@
-// ow_context.h -- the context behind include/ocean_waves.h and the handles that hang off it, for the three host units that work on them:
-// ow_schedule.hip (the frame scheduler), ow_runtime.hip (create / destroy, status, scratch, hand-off, readback) and ow_consumer_host.hip (the
-// read side).  Every handle kind derives from ow::Handle and the context keeps ONE list of them: ow_consumer_host.hip holds their one life
-// cycle, ow_destroy orphans whatever is still on the list.
+// ow_context.h -- the context behind include/ocean_waves.h and the handles that hang off it, for the host units that work on them:
+// ow_schedule.hip (the frame scheduler), ow_runtime.hip (create / destroy, status, scratch, hand-off, readback) and the read side's units
+// (ow_consumer_host.h).  Every handle kind derives from ow::Handle and the context keeps ONE list of them: ow_consumer_host.hip holds their
+// one life cycle, ow_destroy orphans whatever is still on the list.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -204,7 +204,7 @@ struct ow_context {
     ow::u16x4 *snap_dev = nullptr, *snap_host = nullptr;  // [2 maps][layers][N][N]
     hipEvent_t snap_ready[OW_MAX_CASCADES] = {}, copy_done[OW_MAX_CASCADES] = {};
     bool copy_pending[OW_MAX_CASCADES] = {};
-    // The consumers' grow-only scratch (ow_consumer_host.hip).  query: the synchronous point calls' points in and records out (of the largest kind);
+    // The consumers' grow-only scratch (the read side's ow_*_host.hip).  query: the synchronous point calls' points in and records out (of the largest kind);
     // buoy: bodies, hull points, per-point records, results; ray: rays in, records out; render_rgba / render_pixels: the RGBA8 words and per-pixel
     // records of the synchronous ow_render_view, ow_mesh_draw and ow_billboard_draw; mesh_vis: the draw's visibility words (both forms);
     // billboard: a billboard draw's counters, bin masks, sprite records and (ow_billboard_draw_instances) the uploaded instances;

@@ -1,5 +1,5 @@
 // ow_internal.h -- what the translation units of libocean_waves.so share besides the public header: error reporting, and the read side's
-// host code that serves a context and a group alike (ow_consumer_host.hip).
+// host code that serves a context and a group alike (ow_points_host.hip, ow_bodies_host.hip; the scratch: ow_consumer_host.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -21,7 +21,7 @@ ow_status validate_records(const ow_cascade_params *params, int count, double de
 // the context's device status word without synchronising (ow_runtime.hip)
 ow_status poll_status(ow_context *c);
 
-// ---- the read side (ow_consumer_host.hip) ----
+// ---- the read side (points and rays: ow_points_host.hip; buoyancy: ow_bodies_host.hip) ----
 // ow_query_options (NULL = defaults) -> the solver's settings, OW_ERR_INVALID for a value out of range
 ow_status resolve_query_options(const ow_query_options *opts, QueryParams *qp);
 // ow_buoyancy_options (NULL = defaults) -> the solver's settings and the model's constants
@@ -33,7 +33,7 @@ ow_status check_buoyancy_arrays(const ow_buoyancy_body *bodies, int num_bodies, 
 
 // A grow-only device allocation on the current device.  Nothing that reads the old block may be in flight when it grows: every user but three
 // synchronises before it returns (the exceptions, the mesh draw's visibility words and the billboard and solid draws' blocks, synchronise before
-// they grow: ow_consumer_host.hip sync_before_growth).
+// they grow: ow_consumer_host.h sync_before_growth).  Defined in ow_consumer_host.hip.
 struct DeviceScratch {
     void *ptr = nullptr;
     size_t bytes = 0;  // capacity
@@ -53,7 +53,7 @@ struct MapsView {
 // The caller synchronises.  Points: the sampling kernel without qp, the velocity records with vel (the velocity layers), the query otherwise.
 ow_status points_round_trip(const MapsView &v, DeviceScratch &scratch, const float *xz, int count, const float *map_scales, int num_cascades,
                             const QueryParams *qp, const u16x4 *vel, void *out);
-// bound: the per-cascade bound words of the slab, allocated once (ray_bound_words)
+// bound: the per-cascade bound words of the slab, allocated once (ow_consumer_host.h ray_bound_words)
 ow_status rays_round_trip(const MapsView &v, DeviceScratch &scratch, uint32_t **bound, const ow_ray *rays, int count, const float *map_scales,
                           int num_cascades, const RaycastParams &rp, ow_raycast_hit *out);
 // results and, with points_inout, the per-point records come back; vel: the velocity layers (OW_BUOYANCY_WATER_VELOCITY)

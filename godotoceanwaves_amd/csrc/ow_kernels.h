@@ -1,4 +1,4 @@
-// ow_kernels.h -- internal launcher interface between the host units (ow_schedule.hip: the frame launchers; ow_consumer_host.hip and
+// ow_kernels.h -- internal launcher interface between the host units (ow_schedule.hip: the frame launchers; the read side's ow_*_host.hip and
 // ow_group.hip: the consumer launchers) and the HIP translation units that hold the kernels.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -45,7 +45,7 @@ struct LaunchTiming {
     hipEvent_t start = nullptr, stop = nullptr;
 };
 
-// The consumer launchers: called from ow_consumer_host.hip (for a context's own maps and, through its round trips, a group's gathered arrays).
+// The consumer launchers: called from the read side's ow_*_host.hip (for a context's own maps and, through its round trips, a group's gathered arrays).
 // consumer-side sampling and the inverse query (ow_consumer.hip; per-point code and records in ow_surface.h)
 hipError_t launch_sample_surface(int n, int cascades, const DeviceBuffers &buf, const float *xz_dev, int count,
                                  const SurfaceScales &scales, SurfaceSample *out_dev, hipStream_t s);

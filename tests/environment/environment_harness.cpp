@@ -76,7 +76,7 @@ CameraParams camera_of(const EnvCase &h) {
     cam.height = h.height;
     return cam;
 }
-// as the runtime resolves ow_environment_options and the sky (ow_consumer_host.hip resolve_environment_options, check_environment)
+// as the runtime resolves ow_environment_options and the sky (ow_sky_host.hip resolve_environment_options, environment_apply)
 EnvParams params_of(const EnvCase &h, const CameraParams &cam, const uint32_t *texels, const float *table) {
     EnvParams ep;
     memset(&ep, 0, sizeof(ep));

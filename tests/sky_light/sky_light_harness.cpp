@@ -156,7 +156,7 @@ CameraParams camera_of(const LightCase &h) {
     cam.height = h.height;
     return cam;
 }
-// as the runtime resolves ow_radiance_light_options and the pyramid (ow_consumer_host.hip check_radiance_light)
+// as the runtime resolves ow_radiance_light_options and the pyramid (ow_sky_host.hip resolve_radiance_light_options, radiance_light_apply)
 SkyLightParams params_of(const LightCase &h, const CameraParams &cam, const Pyramid &P) {
     SkyLightParams lp;
     memset(&lp, 0, sizeof(lp));

@@ -62,7 +62,7 @@ CameraParams camera_of(const SolidCase &h) {
     cam.height = h.height;
     return cam;
 }
-// as the runtime resolves ow_solid_options (ow_consumer_host.hip resolve_solid_options)
+// as the runtime resolves ow_solid_options (ow_solid_host.hip resolve_solid_options)
 SolidParams params_of(const SolidCase &h, const CameraParams &cam) {
     SolidParams sp;
     memset(&sp, 0, sizeof(sp));
