@@ -10,13 +10,15 @@ from . import _lib
 from ._lib import (OW_FLAG_DEBUG_F32, OW_FLAG_NO_TICK_GROUPS, OW_GROUP_FLAG_FORCE_PEER_PATH, OW_MAX_DEVICES, ow_cascade_params,
                    ow_group_config)
 from .presets import DEPTH
-from .wave_generator import WaveGenerator, _ref, _scales
+from ._points import point_calls
+from .wave_generator import WaveGenerator
 
 
-class WaveGeneratorGroup:
+class WaveGeneratorGroup(point_calls("ow_group_", "group")):
     """gen = WaveGeneratorGroup(); gen.map_size = 1024; gen.init_gpu(device_ids=[0..7], cascades_per_device=1)
     gen.update(delta, parameters)  /  gen._process()  /  gen.update_all(...)  /  gen.run(..., frames)
-    gen.gather_begin(); ...; gen.gather_wait(); gen.get_maps(g)   # layer g of the consumer's arrays = global cascade g"""
+    gen.gather_begin(); ...; gen.gather_wait(); gen.get_maps(g)   # layer g of the consumer's arrays = global cascade g
+    sample_surface / query_surface / buoyancy / raycast_surface are WaveGenerator's, over the gathered arrays on the root device"""
 
     def __init__(self):
         self.map_size = 0
@@ -133,48 +135,6 @@ class WaveGeneratorGroup:
         disp, norm = np.empty((n, n, 4), np.float16), np.empty((n, n, 4), np.float16)
         _lib.check(self._lib.ow_group_get_maps(self.group, int(cascade), disp.ctypes.data, norm.ctypes.data))
         return disp, norm
-
-    def sample_surface(self, world_xz, map_scales):
-        xz = np.ascontiguousarray(world_xz, np.float32).reshape(-1, 2)
-        sc = _scales(map_scales)
-        out = np.zeros(len(xz), WaveGenerator.SURFACE_SAMPLE)
-        _lib.check(self._lib.ow_group_sample_surface(self.group, xz.ctypes.data, len(xz), sc.ctypes.data, len(sc), out.ctypes.data))
-        return out
-
-    def query_surface(self, world_xz, map_scales, options=None):
-        """WaveGenerator.query_surface over the gathered arrays on the root device"""
-        xz = np.ascontiguousarray(world_xz, np.float32).reshape(-1, 2)
-        sc = _scales(map_scales)
-        out = np.zeros(len(xz), WaveGenerator.SURFACE_QUERY)
-        o = WaveGenerator.query_options(options)
-        _lib.check(self._lib.ow_group_query_surface(self.group, xz.ctypes.data, len(xz), sc.ctypes.data, len(sc),
-                                                    _ref(o), out.ctypes.data))
-        return out
-
-    def buoyancy(self, bodies, hull, map_scales, options=None, points=None):
-        """WaveGenerator.buoyancy over the gathered arrays on the root device"""
-        b = np.ascontiguousarray(bodies, WaveGenerator.BUOYANCY_BODY)
-        h = np.ascontiguousarray(hull, WaveGenerator.HULL_POINT)
-        sc = _scales(map_scales)
-        if points is not None and (not isinstance(points, np.ndarray) or points.dtype != WaveGenerator.BUOYANCY_POINT or len(points) != len(h)
-                                   or not points.flags.c_contiguous):
-            raise ValueError(f"points must be a contiguous BUOYANCY_POINT array of {len(h)} records")
-        out = np.zeros(len(b), WaveGenerator.BUOYANCY_RESULT)
-        o = WaveGenerator.buoyancy_options(options)
-        _lib.check(self._lib.ow_group_buoyancy(self.group, b.ctypes.data, len(b), h.ctypes.data, len(h), sc.ctypes.data, len(sc),
-                                               _ref(o), out.ctypes.data,
-                                               points.ctypes.data if points is not None else None))
-        return out
-
-    def raycast_surface(self, rays, map_scales, options=None):
-        """WaveGenerator.raycast_surface over the gathered arrays on the root device"""
-        r = np.ascontiguousarray(rays, WaveGenerator.RAY)
-        sc = _scales(map_scales)
-        out = np.zeros(len(r), WaveGenerator.RAYCAST_HIT)
-        o = WaveGenerator.raycast_options(options)
-        _lib.check(self._lib.ow_group_raycast_surface(self.group, r.ctypes.data, len(r), sc.ctypes.data, len(sc),
-                                                      _ref(o), out.ctypes.data))
-        return out
 
     def free(self):
         if self.group:
