@@ -11,9 +11,10 @@ import helpers as H
 import query_twin
 import render_twin
 from cpu_builds import cpu_query, ROOT
+from device_maps import DISP_REPORTED, half_to_f32, NORM_REPORTED
 from godotoceanwaves_amd import _lib
 from godotoceanwaves_amd.wave_generator import WaveGenerator as W
-from scenes import DEFAULTS, G, HIT, RHO, uniforms_of, unit
+from scenes import BELOW, DEFAULTS, G, HIT, NO_TRIANGLE, RAY_TOL, RHO, slope_factor, TRUNC, uniforms_of, unit
 from velocity_twin import phases, velocity_twin
 
 HEADER = open(os.path.join(ROOT, "include", "ocean_waves.h")).read()
@@ -70,6 +71,45 @@ def check_records(L, qh, d, m, sc, rays, out, options=None):
     assert not out[~hit]["query"].tobytes().strip(b"\0")
     assert (out["t"][~hit] == 0).all() and (out["residual"][~hit] == 0).all()
     return hit
+
+
+def check_texel_centres(out, disp, norm):
+    """ow_sample_surface records at the centres of every texel of one 128^2 cascade with map scales (1/128, 1/128, 1, 1), row by row: both
+    weights are 0, so the displacement, the plain gradient and the plain foam are the texel's own half-words widened, by value (a -0 may
+    come back as +0: a + b * 0 with b * 0 = +0).  Returns the patterns that came back so."""
+    d, m = np.asarray(disp, np.uint16).reshape(-1, 4), np.asarray(norm, np.uint16).reshape(-1, 4)
+    assert len(out) == len(d) == len(m)
+    got = np.concatenate([out["displacement"], out["gradient"], out["foam"][:, None]], axis=1)
+    bits = np.concatenate([d[:, DISP_REPORTED], m[:, NORM_REPORTED]], axis=1)
+    same = got == half_to_f32(bits)
+    assert same.all(), (bits[~same][:8], got[~same][:8])
+    return np.unique(bits[same])
+
+
+def check_calm_hits(out, rays, h):
+    """scenes.calm_hit_rays over a calm sea: every ray hits at the analytic t = h / -d^.y within the ray tolerance, on the slab's floor"""
+    assert (out["status"] == HIT).all()
+    dn = unit(rays["direction"]).astype(np.float64)
+    t_star = h / -dn[:, 1]
+    assert np.abs(out["t"] - t_star).max() <= RAY_TOL + 1e-6 * t_star.max()
+    assert (np.abs(out["residual"]) <= RAY_TOL * slope_factor(dn, 0.0) + 1e-5).all()
+    assert (out["slab_half_height"] == np.float32(0.01)).all() and (out["query"]["height"] == 0).all()
+    assert (out["rounds"] <= 1 + 4).all() and (out["samples"] >= 2).all()
+
+
+def check_calm_misses(out, wl):
+    """scenes.calm_miss_rays over a calm sea at water level wl = -0.5, cast with max_samples = 64"""
+    assert wl == -0.5
+    st = out["status"]
+    assert st[0] == 0 and out["samples"][0] == 0                   # upward from above the slab: never enters it
+    assert st[1] == 0 and out["samples"][1] == 0                   # horizontal, above the slab
+    assert st[2] == HIT and abs(out["t"][2] - 5.5 * np.sqrt(2)) <= RAY_TOL
+    assert st[3] == 0 and out["samples"][3] == 0                   # horizontal, just above the slab (0.01 m)
+    assert st[4] == HIT | BELOW and abs(out["t"][4] - 2.5 * np.sqrt(2)) <= RAY_TOL   # from below, surfacing
+    assert st[5] == BELOW and out["samples"][5] == 0               # from below, going down: never enters the slab
+    assert st[6] == BELOW | TRUNC and out["samples"][6] == 64 and out["rounds"][6] == 1   # inside the slab, horizontal, 5 km
+    assert st[7] == 0 and out["samples"][7] == 0                   # stops 10 m short of the water
+    assert st[8] == BELOW | TRUNC                                  # on the plane: g = 0 is not above; 100 m is 401 samples
 
 
 def buoyancy_twin(disp, scales, bodies, hull, p, options=None):
@@ -137,6 +177,61 @@ def check_composite(rgba, rec, options=None):
     assert np.array_equal(rgba, render_twin.rgba8(rec["color"]))
     assert not rec["reserved"].any()
     return hit
+
+
+def check_picture(pic, num_triangles, options=None):
+    """check_composite's rules -- finite records, sky and zeros without a hit, the composite, the RGBA8 rule -- with
+    reserved[0] the triangle's index + 1, and the counters adding up"""
+    rgba, rec, vis = pic["rgba"], pic["rec"], pic["vis"]
+    for f in W.RENDER_PIXEL.names:
+        if f not in ("status", "reserved"):
+            assert np.isfinite(rec[f]).all(), f
+    hit = (rec["status"] & HIT) != 0
+    o = dict(DEFAULTS, **{k: v for k, v in (options or {}).items() if k in DEFAULTS})
+    sky, amb = np.asarray(o["sky_color"], np.float32), np.asarray(o["ambient_color"], np.float32)
+    assert (rec["color"][~hit] == sky).all()
+    zeroed = rec[~hit].copy()
+    zeroed["status"] = 0
+    zeroed["color"] = 0
+    assert not zeroed.tobytes().strip(b"\0")
+    want = rec["albedo"] * (rec["diffuse"] + amb) + rec["specular"][..., None]
+    assert np.array_equal(rec["color"][hit], want[hit])
+    assert np.array_equal(rgba, render_twin.rgba8(rec["color"]))
+    assert not rec["reserved"][..., 1:].any()
+    assert np.array_equal(hit, vis != NO_TRIANGLE)
+    assert np.array_equal(rec["reserved"][..., 0][hit], (vis[hit] & np.uint64(0xFFFFFFFF)).astype(np.uint32) + 1) and not rec["reserved"][..., 0][~hit].any()
+    assert (rec["reserved"][..., 0] <= num_triangles).all()
+    assert int(pic["counters"].sum()) == num_triangles, pic["counters"]
+    return hit
+
+
+def calm_plane(cam, near, half=32.0):
+    """a camera over the square |x|, |z| <= half of the plane y = 0, in FP64: per pixel the ray's t to the plane (inf where it does not go
+    down) and the point there, whether the pixel is asked (its ray passes more than 1e-4 m from the square's edge, the near plane and
+    max_distance) and whether it has a hit"""
+    o = np.asarray(list(cam.position), np.float64)
+    dirs = render_twin.pixel_directions(list(cam.basis), cam.fov_y_degrees, cam.width, cam.height)
+    fwd = -np.asarray(list(cam.basis), np.float64).reshape(3, 3)[:, 2]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        t = np.where(dirs[..., 1] < 0, -o[1] / dirs[..., 1], np.inf)
+        pos = o + t[..., None] * dirs
+        depth = t * (dirs @ fwd)
+    finite = np.isfinite(t)
+    margin = np.where(finite, np.minimum.reduce([half - np.abs(pos[..., 0]), half - np.abs(pos[..., 2]), depth - near, cam.max_distance - depth]), -1.0)
+    asked = ~finite | (np.abs(margin) > 1e-4)
+    want = finite & (margin > 0)
+    return t, pos, asked, want
+
+
+def assert_same_picture(got, want, what):
+    """a mesh draw (scenes.gpu_mesh_draw, cpu_builds.cpu_mesh_draw): vertex records, visibility words, pixel records, RGBA and counters"""
+    for f in W.MESH_VERTEX.names:
+        assert got["vertices"][f].tobytes() == want["vertices"][f].tobytes(), (what, "vertex", f)
+    assert got["vis"].tobytes() == want["vis"].tobytes(), (what, "visibility words")
+    for f in W.RENDER_PIXEL.names:
+        assert got["rec"][f].tobytes() == want["rec"][f].tobytes(), (what, f)
+    assert got["rgba"].tobytes() == want["rgba"].tobytes(), what
+    assert list(got["counters"]) == list(want["counters"]), what
 
 
 SHADE_TOL = H.TOL_F32   # 1e-4: the project's FP32 parity tolerance

@@ -133,6 +133,29 @@ def calm_maps(n=64, cascades=2):
                                                                                                             np.float32)
 
 
+def calm_hit_rays(wl):
+    """400 rays onto a calm sea at water level wl, half of them at 45 degrees and half steeper, from 0.5 m to 200 m above it, their
+    directions of any length: (rays, heights above the water)"""
+    rng = np.random.default_rng(1)
+    R = 400
+    ang = np.radians(np.concatenate([np.full(R // 2, 45.0), rng.uniform(60.0, 90.0, R // 2)]))
+    az = rng.uniform(0, 2 * np.pi, R)
+    h = rng.uniform(0.5, 200.0, R)
+    o = np.stack([rng.uniform(-300, 300, R), wl + h, rng.uniform(-300, 300, R)], axis=1)
+    return W.rays(o, np.stack([np.cos(ang) * np.cos(az), -np.sin(ang), np.cos(ang) * np.sin(az)], axis=1) * rng.uniform(0.1, 30.0, (R, 1)), 1000.0), h
+
+
+def calm_miss_rays(wl):
+    """nine rays round a calm sea at water level wl: misses above and below the slab, hits from above and below, truncation inside it"""
+    return W.rays([(0, 5, 0), (3, 50, 3), (0, 5, 0), (10, 0.02 + wl, 0), (0, -3, 0), (0, -3, 0), (0, -0.005 + wl, 0), (0, 20, 0), (0, wl, 0)],
+                  [(0, 1, 0), (1, 0, 0), (1, -1, 0), (1, 0, 0), (0, 1, 1), (0, -1, 0), (1, 0, 0), (0, -1, 0), (1, 0, 0)],
+                  [100, 100, 100, 100, 100, 100, 5000, 10, 100])
+
+
+def swell_rays():
+    return camera_rays(300, (2.0, 60.0), (3.0, 80.0), seed=11, max_distance=3000.0)
+
+
 def swell_maps(n=256, tile=100.0, amplitude=1.5, wavelength=20.0):
     """D_xz = 0, D_y = A cos(k x) at the texel centres, in FP16: a height-only swell (the query's p is q)"""
     x = (np.arange(n) + 0.5) * tile / n
@@ -296,6 +319,20 @@ def device_read(ptr, count, dtype, stream=None):
     return out
 
 
+def device_array(ptr, shape, dtype):
+    return device_read(ptr, int(np.prod(shape)), dtype).reshape(shape)
+
+
+def gpu_mesh_draw(gen, mesh_handle, cam, origin, sc, options=None):
+    """ow_mesh_draw and what it left resident, in cpu_mesh_draw's form: rgba, rec, vertices, vis and the four counters"""
+    rgba, rec = gen.mesh_draw(mesh_handle, cam, origin, sc, options)
+    vptr, wptr = gen.mesh_device_ptrs(mesh_handle)
+    stats = gen.mesh_stats(mesh_handle)
+    return dict(rgba=rgba, rec=rec, vertices=device_array(vptr, mesh_handle.num_vertices, W.MESH_VERTEX),
+                vis=device_array(wptr, (cam.height, cam.width), np.uint64),
+                counters=np.array([stats[k] for k in ("skipped", "culled", "per_lane", "cooperative")], np.uint32))
+
+
 def gpu_arrays(gen, s):
     state, results = gen.bodies_state(s), gen.bodies_results(s)   # both synchronise
     b, _, p = gen.bodies_device_ptrs(s)
@@ -399,6 +436,33 @@ def grid(cells=16, cell=4.0, y=0.0):
     b, d, e = a + 1, a + cells + 1, a + cells + 2
     t = np.stack([np.stack([a, d, b], 1), np.stack([b, d, e], 1)], 1).reshape(-1, 3).astype(np.int32)
     return v, t
+
+
+def grid_with_a_fan():
+    """the 17 x 17 grid with one cell drawn as a pentagon: an extra vertex in the middle of an edge, fanned from the cell's first corner, so
+    that one of its triangles has zero area and its neighbour keeps the long edge (a T-junction, as at the clipmap's ring transitions)"""
+    v, t = grid()
+    cell = 8 * 16 + 5
+    a, d, b = t[2 * cell]
+    e = t[2 * cell + 1][2]
+    mid = len(v)
+    v = np.concatenate([v, [(v[a] + v[d]) / 2]]).astype(np.float32)
+    fan = np.array([(a, mid, d), (a, d, e), (a, e, b), (a, a, mid)], np.int32)   # (a, mid, d) is collinear; (a, a, mid) has two equal corners
+    return v, np.concatenate([t[:2 * cell], t[2 * cell + 2:], fan]).astype(np.int32)
+
+
+CALM_CAMERAS = {
+    "down": (dict(position=(1.0, 20.0, -2.0), yaw_deg=0.0, pitch_deg=-89.9, max_distance=200.0), {}),
+    "pitched": (dict(position=(0.0, 12.0, -20.0), yaw_deg=10.0, pitch_deg=-25.0, max_distance=40.0), {}),
+    "near_plane": (dict(position=(0.3, 0.5, 0.2), yaw_deg=30.0, pitch_deg=0.0, max_distance=200.0), {}),
+    "near_plane_far_cut": (dict(position=(0.3, 0.5, 0.2), yaw_deg=30.0, pitch_deg=0.0, max_distance=25.0), {"near": 3.0}),
+}
+
+
+NO_TRIANGLE = np.uint64(0xFFFFFFFFFFFFFFFF)   # a visibility word no triangle has written
+
+
+NEAR = 0.05                                  # ow_mesh_options_default's near plane, metres
 
 
 def center_of(options, cam):

@@ -24,18 +24,18 @@ from godotoceanwaves_amd.presets import UPDATE_DELTA
 from godotoceanwaves_amd.wave_generator import WaveGenerator as W
 from edge_presets import edge_presets
 import checks as S
-from checks import assert_same_image, check_csharp_binds, check_declared_and_bound, exported_symbols, HEADER
+from checks import (assert_same_image, assert_same_picture, calm_plane, check_csharp_binds, check_declared_and_bound, check_picture, exported_symbols,
+                    HEADER)
 from cpu_builds import build_example, build_sanitized_harness, cpu_mesh_draw as cpu_draw, cpu_render, cpu_sample, HERE, layout_probe
 from cpu_builds import mesh_harness as harness, query_harness, render_harness  # noqa: F401 (fixtures)
-from scenes import (BELOW, calm_maps, camera_words, center_of, DEFAULTS, generated_maps, GPU_CAM, gpu_maps, grid, GROW_SIZES, HIT, INVALID,
-                    look, make_gen, maps_u16, REF_BASIS, render_outputs, scales_of, smallest_context, uniforms_of)
+from scenes import (BELOW, CALM_CAMERAS, calm_maps, camera_words, center_of, DEFAULTS, device_array, generated_maps, GPU_CAM, gpu_maps,
+                    gpu_mesh_draw as gpu_draw, grid, grid_with_a_fan, GROW_SIZES, HIT, INVALID, look, make_gen, maps_u16, NEAR, NO_TRIANGLE, REF_BASIS,
+                    render_outputs, scales_of, smallest_context, uniforms_of)
 
 NEW_FUNCTIONS = ("ow_mesh_options_default", "ow_mesh_create", "ow_mesh_destroy", "ow_mesh_displace", "ow_mesh_get_device_ptrs", "ow_mesh_draw",
                  "ow_mesh_draw_async", "ow_mesh_stats")
 PARENT_RENDER = ("ow_render_options_default", "ow_render_view", "ow_render_view_async")
 PARENT_RAYCAST = ("ow_raycast_surface", "ow_raycast_surface_async", "ow_group_raycast_surface")
-NO_TRIANGLE = np.uint64(0xFFFFFFFFFFFFFFFF)
-NEAR = 0.05
 TOL = H.TOL_F32    # 1e-4: the project's FP32 parity tolerance (test_render_view.py's shading tolerance)
 
 
@@ -58,32 +58,6 @@ def cpu_vertices(L, disp, scales, local, origin, options=None, cam=None):
     L.harness_mesh_vertices(d.ctypes.data, d.shape[1], len(sc), sc.ctypes.data, v.ctypes.data, len(v), org.ctypes.data, int(center is not None), cx, cz,
                             cw.ctypes.data if cw is not None else None, out.ctypes.data)
     return out
-
-
-def check_picture(pic, num_triangles, options=None):
-    """test_render_view.py's check_composite rules -- finite records, sky and zeros without a hit, the composite, the RGBA8 rule -- with
-    reserved[0] the triangle's index + 1, and the counters adding up"""
-    rgba, rec, vis = pic["rgba"], pic["rec"], pic["vis"]
-    for f in W.RENDER_PIXEL.names:
-        if f not in ("status", "reserved"):
-            assert np.isfinite(rec[f]).all(), f
-    hit = (rec["status"] & HIT) != 0
-    o = dict(DEFAULTS, **{k: v for k, v in (options or {}).items() if k in DEFAULTS})
-    sky, amb = np.asarray(o["sky_color"], np.float32), np.asarray(o["ambient_color"], np.float32)
-    assert (rec["color"][~hit] == sky).all()
-    zeroed = rec[~hit].copy()
-    zeroed["status"] = 0
-    zeroed["color"] = 0
-    assert not zeroed.tobytes().strip(b"\0")
-    want = rec["albedo"] * (rec["diffuse"] + amb) + rec["specular"][..., None]
-    assert np.array_equal(rec["color"][hit], want[hit])
-    assert np.array_equal(rgba, RT.rgba8(rec["color"]))
-    assert not rec["reserved"][..., 1:].any()
-    assert np.array_equal(hit, vis != NO_TRIANGLE)
-    assert np.array_equal(rec["reserved"][..., 0][hit], (vis[hit] & np.uint64(0xFFFFFFFF)).astype(np.uint32) + 1) and not rec["reserved"][..., 0][~hit].any()
-    assert (rec["reserved"][..., 0] <= num_triangles).all()
-    assert int(pic["counters"].sum()) == num_triangles, pic["counters"]
-    return hit
 
 
 @pytest.fixture(scope="module")
@@ -285,27 +259,6 @@ def test_clipmap_origin_is_main_gds_rule():
 
 # ---- 3. a calm sea -----------------------------------------------------------------------------------------------------------------------
 
-def grid_with_a_fan():
-    """the 17 x 17 grid with one cell drawn as a pentagon: an extra vertex in the middle of an edge, fanned from the cell's first corner, so
-    that one of its triangles has zero area and its neighbour keeps the long edge (a T-junction, as at the clipmap's ring transitions)"""
-    v, t = grid()
-    cell = 8 * 16 + 5
-    a, d, b = t[2 * cell]
-    e = t[2 * cell + 1][2]
-    mid = len(v)
-    v = np.concatenate([v, [(v[a] + v[d]) / 2]]).astype(np.float32)
-    fan = np.array([(a, mid, d), (a, d, e), (a, e, b), (a, a, mid)], np.int32)   # (a, mid, d) is collinear; (a, a, mid) has two equal corners
-    return v, np.concatenate([t[:2 * cell], t[2 * cell + 2:], fan]).astype(np.int32)
-
-
-CALM_CAMERAS = {
-    "down": (dict(position=(1.0, 20.0, -2.0), yaw_deg=0.0, pitch_deg=-89.9, max_distance=200.0), {}),
-    "pitched": (dict(position=(0.0, 12.0, -20.0), yaw_deg=10.0, pitch_deg=-25.0, max_distance=40.0), {}),
-    "near_plane": (dict(position=(0.3, 0.5, 0.2), yaw_deg=30.0, pitch_deg=0.0, max_distance=200.0), {}),
-    "near_plane_far_cut": (dict(position=(0.3, 0.5, 0.2), yaw_deg=30.0, pitch_deg=0.0, max_distance=25.0), {"near": 3.0}),
-}
-
-
 @pytest.mark.parametrize("name", list(CALM_CAMERAS))
 def test_calm_sea_is_the_analytic_plane(harness, render_harness, name):
     """Zero maps: the mesh is the square |x|, |z| <= 32 of the plane y = 0.  A pixel has a hit exactly when its ray meets the plane inside
@@ -319,17 +272,7 @@ def test_calm_sea_is_the_analytic_plane(harness, render_harness, name):
     pic = cpu_draw(harness, d, m, sc, mesh, (0, 0, 0), cam, opts)
     hit = check_picture(pic, len(mesh[1]), opts)
     rec = pic["rec"]
-    o = np.asarray(list(cam.position), np.float64)
-    dirs = RT.pixel_directions(list(cam.basis), cam.fov_y_degrees, cam.width, cam.height)
-    fwd = -np.asarray(list(cam.basis), np.float64).reshape(3, 3)[:, 2]
-    with np.errstate(divide="ignore", invalid="ignore"):
-        t = np.where(dirs[..., 1] < 0, -o[1] / dirs[..., 1], np.inf)
-        pos = o + t[..., None] * dirs
-        depth = t * (dirs @ fwd)
-    finite = np.isfinite(t)
-    margin = np.where(finite, np.minimum.reduce([32 - np.abs(pos[..., 0]), 32 - np.abs(pos[..., 2]), depth - near, cam.max_distance - depth]), -1.0)
-    asked = ~finite | (np.abs(margin) > 1e-4)
-    want = finite & (margin > 0)
+    t, pos, asked, want = calm_plane(cam, near)
     assert np.array_equal(hit[asked], want[asked]) and want.any() and asked.mean() > 0.98
     both = hit & want
     rel = lambda got, ref: np.abs(got - ref) / np.maximum(1.0, np.abs(ref))   # noqa: E731
@@ -514,37 +457,6 @@ def test_clipmap_fixture_is_the_inner_rings():
 
 
 # ---- 8-11. on the GPU ----------------------------------------------------------------------------------------------------------------------
-
-def hip():
-    h = C.CDLL("libamdhip64.so")
-    h.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    return h
-
-
-def device_array(ptr, shape, dtype):
-    out = np.zeros(shape, dtype)
-    assert hip().hipMemcpy(out.ctypes.data, ptr, out.nbytes, 2) == 0   # hipMemcpyDeviceToHost
-    return out
-
-
-def gpu_draw(gen, mesh_handle, cam, origin, sc, options=None):
-    rgba, rec = gen.mesh_draw(mesh_handle, cam, origin, sc, options)
-    vptr, wptr = gen.mesh_device_ptrs(mesh_handle)
-    stats = gen.mesh_stats(mesh_handle)
-    return dict(rgba=rgba, rec=rec, vertices=device_array(vptr, mesh_handle.num_vertices, W.MESH_VERTEX),
-                vis=device_array(wptr, (cam.height, cam.width), np.uint64),
-                counters=np.array([stats[k] for k in ("skipped", "culled", "per_lane", "cooperative")], np.uint32))
-
-
-def assert_same_picture(got, want, what):
-    for f in W.MESH_VERTEX.names:
-        assert got["vertices"][f].tobytes() == want["vertices"][f].tobytes(), (what, "vertex", f)
-    assert got["vis"].tobytes() == want["vis"].tobytes(), (what, "visibility words")
-    for f in W.RENDER_PIXEL.names:
-        assert got["rec"][f].tobytes() == want["rec"][f].tobytes(), (what, f)
-    assert got["rgba"].tobytes() == want["rgba"].tobytes(), what
-    assert list(got["counters"]) == list(want["counters"]), what
-
 
 @pytest.mark.gpu
 def test_gpu_draw_is_the_cpu_builds_bit_for_bit_256(harness):

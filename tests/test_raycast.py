@@ -17,11 +17,11 @@ from godotoceanwaves_amd import _lib, build
 from godotoceanwaves_amd.presets import UPDATE_DELTA
 from godotoceanwaves_amd.wave_generator import WaveGenerator as W
 import checks as S
-from checks import check_csharp_binds, check_declared_and_bound, check_records, exported_symbols, HEADER
+from checks import check_calm_hits, check_calm_misses, check_csharp_binds, check_declared_and_bound, check_records, exported_symbols, HEADER
 from cpu_builds import cpu_raycast, layout_probe
 from cpu_builds import query_harness, raycast_harness as harness  # noqa: F401 (fixtures)
-from scenes import (BELOW, calm_maps, camera_rays, generated_maps, gpu_maps, HIT, INVALID, make_gen, mixed_rays, RAY_TOL as TOL, scales_of,
-                    slope_factor, smallest_context, SPACING, swell_maps, TRUNC, unit)
+from scenes import (BELOW, calm_hit_rays, calm_maps, calm_miss_rays, camera_rays, generated_maps, gpu_maps, HIT, INVALID, make_gen, mixed_rays,
+                    RAY_TOL as TOL, scales_of, slope_factor, smallest_context, SPACING, swell_maps, swell_rays, TRUNC, unit)
 
 NEW_FUNCTIONS = ("ow_raycast_surface", "ow_raycast_surface_async", "ow_group_raycast_surface")
 STRUCTS = {"OwRay": "ow_ray", "OwRaycastOptions": "ow_raycast_options", "OwRaycastHit": "ow_raycast_hit"}
@@ -126,43 +126,21 @@ def test_ray_cast_argument_errors_without_a_device():
 def test_calm_sea_hits_at_the_analytic_t(harness, query_harness):
     d, m, sc = calm_maps()
     wl = 1.25
-    rng = np.random.default_rng(1)
-    R = 400
-    ang = np.radians(np.concatenate([np.full(R // 2, 45.0), rng.uniform(60.0, 90.0, R // 2)]))
-    az = rng.uniform(0, 2 * np.pi, R)
-    h = rng.uniform(0.5, 200.0, R)
-    o = np.stack([rng.uniform(-300, 300, R), wl + h, rng.uniform(-300, 300, R)], axis=1)
-    rays = W.rays(o, np.stack([np.cos(ang) * np.cos(az), -np.sin(ang), np.cos(ang) * np.sin(az)], axis=1) * rng.uniform(0.1, 30.0, (R, 1)), 1000.0)
+    rays, h = calm_hit_rays(wl)
     opts = {"water_level": wl}
     out = cpu_raycast(harness, d, m, sc, rays, opts)
     hit = check_records(harness, query_harness, d, m, sc, rays, out, opts)
-    assert hit.all() and (out["status"] == HIT).all()
-    dn = unit(rays["direction"]).astype(np.float64)
-    t_star = h / -dn[:, 1]
-    assert np.abs(out["t"] - t_star).max() <= TOL + 1e-6 * t_star.max()
-    assert (np.abs(out["residual"]) <= TOL * slope_factor(dn, 0.0) + 1e-5).all()
-    assert (out["slab_half_height"] == np.float32(0.01)).all() and (out["query"]["height"] == 0).all()
-    assert (out["rounds"] <= 1 + 4).all() and (out["samples"] >= 2).all()
+    assert hit.all()
+    check_calm_hits(out, rays, h)
 
 
 def test_calm_sea_misses_from_below_and_truncation(harness):
     d, m, sc = calm_maps()
     wl = -0.5
     opts = {"water_level": wl}
-    rays = W.rays([(0, 5, 0), (3, 50, 3), (0, 5, 0), (10, 0.02 + wl, 0), (0, -3, 0), (0, -3, 0), (0, -0.005 + wl, 0), (0, 20, 0), (0, wl, 0)],
-                  [(0, 1, 0), (1, 0, 0), (1, -1, 0), (1, 0, 0), (0, 1, 1), (0, -1, 0), (1, 0, 0), (0, -1, 0), (1, 0, 0)],
-                  [100, 100, 100, 100, 100, 100, 5000, 10, 100])
+    rays = calm_miss_rays(wl)
     out = cpu_raycast(harness, d, m, sc, rays, dict(opts, max_samples=64))
-    st = out["status"]
-    assert st[0] == 0 and out["samples"][0] == 0                   # upward from above the slab: never enters it
-    assert st[1] == 0 and out["samples"][1] == 0                   # horizontal, above the slab
-    assert st[2] == HIT and abs(out["t"][2] - 5.5 * np.sqrt(2)) <= TOL
-    assert st[3] == 0 and out["samples"][3] == 0                   # horizontal, just above the slab (0.01 m)
-    assert st[4] == HIT | BELOW and abs(out["t"][4] - 2.5 * np.sqrt(2)) <= TOL   # from below, surfacing
-    assert st[5] == BELOW and out["samples"][5] == 0               # from below, going down: never enters the slab
-    assert st[6] == BELOW | TRUNC and out["samples"][6] == 64 and out["rounds"][6] == 1   # inside the slab, horizontal, 5 km
-    assert st[7] == 0 and out["samples"][7] == 0                   # stops 10 m short of the water
-    assert st[8] == BELOW | TRUNC                                  # on the plane: g = 0 is not above; 100 m is 401 samples
+    check_calm_misses(out, wl)
     full = cpu_raycast(harness, d, m, sc, rays[6:7], dict(opts, max_samples=1 << 20))
     assert full["status"][0] == BELOW and full["samples"][0] == 20001   # to t_exit = 5000 m at 0.25 m: not truncated
 
@@ -171,7 +149,7 @@ def test_calm_sea_misses_from_below_and_truncation(harness):
 
 def test_swell_against_the_fp64_twin(harness, query_harness):
     d, m, sc = swell_maps()
-    rays = camera_rays(300, (2.0, 60.0), (3.0, 80.0), seed=11, max_distance=3000.0)
+    rays = swell_rays()
     out, mh = cpu_raycast(harness, d, m, sc, rays, probe=True)
     hit = check_records(harness, query_harness, d, m, sc, rays, out)
     assert hit.all()

@@ -34,10 +34,17 @@ NEW_FUNCTIONS = ("ow_spray_options_default", "ow_spray_create", "ow_spray_destro
                  "ow_spray_stats")
 ACTIVE, HAS_STARTED, RESTARTED = _lib.OW_SPRAY_ACTIVE, _lib.OW_SPRAY_HAS_STARTED, _lib.OW_SPRAY_RESTARTED
 LIVE = ACTIVE | HAS_STARTED
-AMOUNTS = (16, 1000, 20000)     # t = 4; t = 31, 39 indices past the grid; 79 blocks: more than one wave of block counts
+AMOUNTS = (16, 1000, 20000)     # t = 4; t = 31, 39 indices past the grid; 79 blocks: more than one wave of block counts, but one trip of
+#                                 k_spray_compact's loops over the blocks (256 lanes, one block each): a second trip needs BIG_AMOUNTS
 STEPS = 40
 TIMING = dict(emitter_lifetime=0.5, lifetime=0.25)
 SHORT = dict(emitter_lifetime=0.25, lifetime=0.125)     # 0.8 s = 3.2 cycles: three wraps
+# 256, 257 and 513 blocks of kSprayBlock (spray_resolve admits every amount in [4, 1 048 576]): the last amount at which k_spray_compact's
+# loops over the blocks take one trip; the first at which the last block's loop takes a second; the first at which the prefix over the
+# earlier blocks takes two whole trips and the last block's loop a third
+BIG_AMOUNTS = (65536, 65537, 131073)
+BIG_TIMING = dict(emitter_lifetime=0.1, lifetime=0.05)  # a cycle of five steps: the restarts reach the last particle in step 5, and 12 steps
+BIG_STEPS = 12                                          # are 2.4 cycles -- every block has held live particles by then
 TOL = H.TOL_F32
 STATE_FLOATS = ("start_pos", "start_time", "particle_scale", "particle_lifetime", "custom_z", "scale_factor")
 ONE_AT = (24660377, 34085821, 59987472, 64077563)       # x with a component of hash32(x, 1) that rounds to exactly 1.0
@@ -364,6 +371,29 @@ def test_a_rotated_and_sheared_emission_transform_against_the_twin(harness, quer
     assert np.allclose(e.P["axis"], (cols / np.linalg.norm(cols, axis=0)).T, atol=1e-7)
 
 
+def live_per_block(out, amount):
+    live = (out["particles"]["flags"] & LIVE) == LIVE
+    return np.add.reduceat(live.astype(np.int64), np.arange(0, amount, 256))
+
+
+@pytest.mark.parametrize("amount", BIG_AMOUNTS)
+def test_past_256_blocks_the_high_blocks_hold_live_particles(harness, amount):
+    """what the GPU cases below rest on, on the CPU build's records: in some step the last block holds a live particle (its loop over the
+    blocks writes live_count and the totals); past 256 blocks, blocks from 256 on do; past 257, two such blocks do in one step, so the
+    base of the later one needs the second trip of the prefix loop"""
+    blocks = (amount + 255) // 256
+    assert blocks == {65536: 256, 65537: 257, 131073: 513}[amount]
+    last = high = two_high = 0
+    for e, prev, out in cpu_run(harness, amount, steps=BIG_STEPS, maps=(*gpu_spray_maps(), SCALES3), **BIG_TIMING):
+        check_draw_list(out)
+        per = live_per_block(out, amount)
+        assert len(per) == blocks and per.sum() == out["live"]
+        last += int(per[-1] > 0)
+        high += int(per[256:].sum() > 0)
+        two_high += int((per[256:] > 0).sum() >= 2)
+    assert last > 0 and (blocks <= 256 or high > 0) and (blocks <= 257 or two_high > 0), (last, high, two_high)
+
+
 # ---- 6. guard G1 ---------------------------------------------------------------------------------------------------------------------------
 
 def test_guard_g1_a_zero_column_does_not_become_nan(harness, query_harness):
@@ -458,6 +488,30 @@ def test_gpu_records_are_the_cpu_builds_bit_for_bit(harness, amount):
     st, ct = gen.spray_stats(s), cpu.stats()
     assert st == ct, (st, ct)
     assert live_total > 0 and (amount < 1000 or (ct["spawned"] > 0 and ct["rejected"] > 0))
+    gen.spray_destroy(s)
+    gen.free()
+    cpu.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("amount", BIG_AMOUNTS)
+def test_gpu_records_past_256_blocks_are_the_cpu_builds_bit_for_bit(harness, amount):
+    """k_spray_compact's prefix over more than 256 earlier blocks, and its last block's sums over more than 256 blocks: the draw list, the
+    live count and the totals (test_past_256_blocks_the_high_blocks_hold_live_particles: those blocks hold live particles)"""
+    gen, sc, d, m = crafted_context()
+    o = options(amount, **BIG_TIMING)
+    cpu = CpuEmitter(harness, o, d, m, sc)
+    s = gen.spray_create(o)
+    for k in range(BIG_STEPS):
+        gen.spray_step(s, DELTA, sc)
+        want = cpu.step()
+        inst, part, draw = gen.spray_read(s)
+        same_records((inst, part, draw), want, (amount, k))
+        live = gen.spray_live_count(s)
+        check_draw_list(dict(particles=part, instances=inst, draw=draw, live=live))
+        assert live == want["live"] == int(((part["flags"] & LIVE) == LIVE).sum())
+    st, ct = gen.spray_stats(s), cpu.stats()
+    assert st == ct and ct["spawned"] > 0 and ct["rejected"] > 0, (st, ct)
     gen.spray_destroy(s)
     gen.free()
     cpu.close()
