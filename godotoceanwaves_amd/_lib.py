@@ -29,6 +29,7 @@ OW_RAY_HIT, OW_RAY_FROM_BELOW, OW_RAY_TRUNCATED, OW_RAY_INVALID = 1, 2, 4, 8
 OW_RAY_SOLID = 16
 OW_SOLID_TWO_SIDED = 1
 OW_SOLID_MAX_INSTANCES, OW_SOLID_MAX_TRIANGLES = 65536, 65536
+OW_SOLID_CAST_TWO_SIDED = 1
 OW_RAY_ENVIRONMENT = 32
 OW_RAY_SKY_LIT = 64
 OW_RADIANCE_MAX_LEVELS, OW_RADIANCE_MAX_SAMPLES, OW_RADIANCE_IRRADIANCE = 8, 256, -1
@@ -240,6 +241,17 @@ class ow_solid_options(C.Structure):
                 ("reserved", C.c_uint32 * 14)]
 
 
+class ow_solid_cast_options(C.Structure):
+    """struct ow_solid_cast_options (32 bytes); a NULL pointer = zeros: one-sided, culled by bounding spheres"""
+    _fields_ = [("flags", C.c_uint32), ("cull", C.c_int32), ("reserved", C.c_uint32 * 6)]
+
+
+class ow_solid_hit(C.Structure):
+    """struct ow_solid_hit (64 bytes): where a ray meets the solids"""
+    _fields_ = [("t", C.c_float), ("position", C.c_float * 3), ("normal", C.c_float * 3), ("status", C.c_int32), ("instance", C.c_int32),
+                ("triangle", C.c_int32), ("barycentric", C.c_float * 2), ("reserved", C.c_uint32 * 4)]
+
+
 class ow_sky_options(C.Structure):
     """struct ow_sky_options (32 bytes); a NULL pointer = srgb 1, energy 1"""
     _fields_ = [("srgb", C.c_uint32), ("energy", C.c_float), ("reserved", C.c_uint32 * 6)]
@@ -383,6 +395,13 @@ SIGNATURES = {
                                       C.c_void_p]),
     "ow_solid_draw_instances": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, _P(ow_camera), _P(ow_solid_options), C.c_void_p, C.c_void_p]),
     "ow_solid_draw_stats": (C.c_int, [C.c_void_p, _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64)]),
+    "ow_cast_bodies": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, _P(ow_solid_cast_options),
+                                    C.c_void_p]),
+    "ow_cast_bodies_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+                                          _P(ow_solid_cast_options), C.c_void_p]),
+    "ow_cast_instances": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, _P(ow_solid_cast_options),
+                                              C.c_void_p]),
+    "ow_cast_stats": (C.c_int, [C.c_void_p, _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64)]),
     "ow_sky_options_default": (None, [_P(ow_sky_options)]),
     "ow_environment_options_default": (None, [_P(ow_environment_options)]),
     "ow_present_options_default": (None, [_P(ow_present_options)]),

@@ -32,6 +32,7 @@ UNITS = {
     "ow_spray.hip": EXACT,
     "ow_spray_draw.hip": EXACT,
     "ow_solid.hip": EXACT,
+    "ow_solid_cast.hip": EXACT,
     "ow_environment.hip": EXACT,
     "ow_sky_light.hip": EXACT,
     "ow_shadow.hip": EXACT,

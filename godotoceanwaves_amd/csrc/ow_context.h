@@ -65,9 +65,12 @@ struct ow_billboard_material : ow::Handle {
     float foam[3] = {0.0f, 0.0f, 0.0f}, max_alpha = 0.0f;
 };
 
-// a solid shape (ow_solid_create): the block holds local positions and indices
+// a solid shape (ow_solid_create): the block holds local positions, indices and the shape's bounding sphere, which the first ray cast
+// against the shape computes (ow_solid_cast.h)
 struct ow_solid : ow::Handle {
     ow::SolidShape shape{};
+    ow::SolidCastBound *bound = nullptr;
+    bool bound_enqueued = false;  // k_solid_cast_shape_bound is on the context's stream, ahead of whatever reads *bound
 };
 
 // a panorama sky (ow_sky_create): the block holds the sRGB table and the texels
@@ -209,12 +212,15 @@ struct ow_context {
     // records of the synchronous ow_render_view, ow_mesh_draw and ow_billboard_draw; mesh_vis: the draw's visibility words (both forms);
     // billboard: a billboard draw's counters, bin masks, sprite records and (ow_billboard_draw_instances) the uploaded instances;
     // solid: a solid draw's counters, transformed vertex records, visibility words and (ow_solid_draw_instances) the uploaded transforms.
+    // solid_cast: a ray cast's counters and instance spheres, the uploaded transforms (ow_cast_instances) and, in the synchronous
+    // forms, the rays, the water records and the hit records.
     // The synchronous ow_shadow_apply uses render_pixels and render_rgba; a shadow map's scratch is the map's own (ow_shadow_map).
     // The synchronous ow_environment_apply uses render_pixels; the synchronous ow_present render_pixels for the records and render_rgba for both
     // outputs (the float4 pixels first, then the RGBA8 words).  Their asynchronous forms use no scratch.
-    ow::DeviceScratch query_scratch, buoy_scratch, ray_scratch, render_rgba, render_pixels, mesh_vis, billboard, solid;
+    ow::DeviceScratch query_scratch, buoy_scratch, ray_scratch, render_rgba, render_pixels, mesh_vis, billboard, solid, solid_cast;
     uint64_t billboard_draws = 0;  // ow_billboard_draw_stats
     uint64_t solid_draws = 0;      // ow_solid_draw_stats
+    uint64_t solid_casts = 0;      // ow_cast_stats
     uint32_t *ray_bound = nullptr;  // the per-cascade bound words of the slab (ray casts and views), allocated once
     // the velocity layers (ow_update_velocity; ow_velocity_kernels.h): V in the displacement array's layout, the pipeline's own intermediate
     // (vel_slots cascades of one launch pair) and twiddle table, all allocated by the first velocity call

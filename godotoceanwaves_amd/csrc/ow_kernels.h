@@ -13,6 +13,7 @@
 #include "ow_shadow.h"
 #include "ow_sky_light.h"
 #include "ow_solid.h"
+#include "ow_solid_cast.h"
 #include "ow_spray.h"
 #include "ow_spray_draw.h"
 #include "ow_surface.h"
@@ -148,6 +149,24 @@ struct SolidArrays {
 // drawn) and / or the RGBA8 words (either may be null), all on `s`
 hipError_t launch_solid_draw(const SolidArrays &A, const SolidInstances &in, const CameraParams &cam, const SolidParams &sp, uint32_t *rgba_dev,
                              RenderPixel *pixels_dev, hipStream_t s);
+
+// a ray cast against solids (ow_solid_cast.hip; the intersection, the winner, the record and the bounding spheres in ow_solid_cast.h)
+constexpr int kSolidCastSlots = 32;          // pairs of 64-bit sums a call's waves add into, by block index
+constexpr int kSolidCastSlotWords = 16;      // 64-bit words from one pair to the next: 128 bytes
+constexpr size_t kSolidCastSumsOffset = 128;  // the skipped instances (one 32-bit word) lie at 0
+constexpr size_t kSolidCastCounterBytes = kSolidCastSumsOffset + (size_t)kSolidCastSlots * kSolidCastSlotWords * sizeof(uint64_t);
+struct SolidCastArrays {
+    SolidShape shape;
+    const SolidCastBound *shape_bound;  // the shape's local sphere (launch_solid_cast_shape_bound wrote it)
+    void *counters;                     // [kSolidCastCounterBytes] scratch: the counters of the last call
+    SolidCastBound *bounds;             // [instances] scratch
+};
+// k_solid_cast_shape_bound: the shape's local centre and radius into *bound_dev, on `s`
+hipError_t launch_solid_cast_shape_bound(const SolidShape &shape, SolidCastBound *bound_dev, hipStream_t s);
+// the clear of the counters, k_solid_cast_bounds over in.count instances, k_solid_cast over `count` rays (water_dev: their water records, or
+// null) into out_dev, all on `s`
+hipError_t launch_solid_cast(const SolidCastArrays &A, const SolidInstances &in, const SolidCastParams &cp, const Ray *rays_dev, const RaycastHit *water_dev,
+                             int count, SolidHit *out_dev, hipStream_t s);
 
 // the environment pass and the present (ow_environment.hip; the sky, the fog, the resolve, the tonemap and the transfer curve in ow_environment.h)
 // k_environment_apply over cam.width x cam.height records, rewritten in place, on `s`; nothing is launched for a camera that is not finite

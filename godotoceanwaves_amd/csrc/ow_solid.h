@@ -171,6 +171,26 @@ OW_DEV TriSetup solid_setup(const SolidTriangle<MeshVertex> &t, const CameraPara
     return s;
 }
 
+// The unit normal of the world triangle (a, b, c), times sg (-1: a back face, the side that is seen): the edges in FP32, the cross product,
+// the length and the division in FP64, narrowed once; zeros for a triangle without area.  The draw's shading normal and the ray cast's
+// (ow_solid_cast.h) are both this.
+OW_DEV void solid_normal(const float a[3], const float b[3], const float c[3], double sg, float n[3]) {
+    float e1[3], e2[3];
+    for (int k = 0; k < 3; ++k) {
+        e1[k] = b[k] - a[k];
+        e2[k] = c[k] - a[k];
+    }
+    const double ax = e1[0], ay = e1[1], az = e1[2], bx = e2[0], by = e2[1], bz = e2[2];
+    const double nx = ay * bz - az * by, ny = az * bx - ax * bz, nz = ax * by - ay * bx;
+    const double len = sqrt((nx * nx + ny * ny) + nz * nz);
+    n[0] = n[1] = n[2] = 0.0f;
+    if (len > 0.0) {
+        n[0] = (float)(sg * nx / len);
+        n[1] = (float)(sg * ny / len);
+        n[2] = (float)(sg * nz / len);
+    }
+}
+
 // One pixel from its visibility word against the record under it (bg_t, bg_status; 0, 0 without records).  drawn: a solid is drawn, and
 // what is returned is the pixel's whole record.  Otherwise the pixel keeps what it had (and zeros are returned).
 OW_DEV RenderPixel solid_pixel(const SolidParams &sp, const CameraParams &cam, uint64_t word, const int32_t *indices, int num_vertices, int num_triangles,
@@ -198,21 +218,8 @@ OW_DEV RenderPixel solid_pixel(const SolidParams &sp, const CameraParams &cam, u
     px.t = d;
     px.status = kRayHit | kRaySolid;
     for (int k = 0; k < 3; ++k) px.position[k] = (w0 * a.position[k] + w1 * b.position[k]) + w2 * c.position[k];
-    float e1[3], e2[3];
-    for (int k = 0; k < 3; ++k) {
-        e1[k] = b.position[k] - a.position[k];
-        e2[k] = c.position[k] - a.position[k];
-    }
-    const double ax = e1[0], ay = e1[1], az = e1[2], bx = e2[0], by = e2[1], bz = e2[2];
-    const double nx = ay * bz - az * by, ny = az * bx - ax * bz, nz = ax * by - ay * bx;
-    const double len = sqrt((nx * nx + ny * ny) + nz * nz);
-    const double sg = p.det > 0.0f ? -1.0 : 1.0;  // a back face (two-sided draws only): the side that is seen
-    float n[3] = {0.0f, 0.0f, 0.0f};
-    if (len > 0.0) {
-        n[0] = (float)(sg * nx / len);
-        n[1] = (float)(sg * ny / len);
-        n[2] = (float)(sg * nz / len);
-    }
+    float n[3];
+    solid_normal(a.position, b.position, c.position, p.det > 0.0f ? -1.0 : 1.0, n);  // a back face (two-sided draws only): the side that is seen
     const float ndl = fmaxf(dot3(n, sp.light), 0.0f);
     for (int k = 0; k < 3; ++k) {
         px.normal[k] = n[k];

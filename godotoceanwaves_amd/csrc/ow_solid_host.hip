@@ -1,6 +1,7 @@
-// ow_solid_host.hip -- the floating bodies as solids: the ow_solid_* shapes and draws over the kernels of ow_solid.hip (ow_solid.h), and
-// their sun shadows, the ow_shadow_* maps, casts and pass, over those of ow_shadow.hip (ow_shadow.h).  A draw and a cast take their
-// instances from the same source (instance_source).
+// ow_solid_host.hip -- the floating bodies as solids: the ow_solid_* shapes and draws over the kernels of ow_solid.hip (ow_solid.h), the
+// ray casts against them, ow_cast_*, over those of ow_solid_cast.hip (ow_solid_cast.h), and their sun shadows, the ow_shadow_*
+// maps, casts and pass, over those of ow_shadow.hip (ow_shadow.h).  A draw, a ray cast and a shadow cast take their instances from the same
+// source (instance_source).
 #include <cmath>
 #include <cstring>
 
@@ -153,11 +154,12 @@ ow_status ow_solid_create(ow_context *c, const float *vertices_xyz, int32_t num_
     if (!c) return fail(OW_ERR_INVALID, "null context");
     const size_t nv = (size_t)num_vertices, nt = (size_t)num_triangles;
     Layout L;
-    const size_t l_off = L.take(nv * 3 * sizeof(float)), i_off = L.take(nt * 3 * sizeof(int32_t));
+    const size_t l_off = L.take(nv * 3 * sizeof(float)), i_off = L.take(nt * 3 * sizeof(int32_t)), b_off = L.take(sizeof(ow::SolidCastBound));
     ow_solid *m;
     if (ow_status st = new_handle(c, L.total, "solid", &m); st != OW_OK) return st;
     char *base = (char *)m->block;
     m->shape = ow::SolidShape{(const float *)(base + l_off), (const int32_t *)(base + i_off), num_vertices, num_triangles};
+    m->bound = (ow::SolidCastBound *)(base + b_off);  // written by the shape's first ray cast
     hipStream_t s = main_stream(c);
     const bool enqueued = hipMemcpyAsync((void *)m->shape.local, vertices_xyz, nv * 3 * sizeof(float), hipMemcpyHostToDevice, s) == hipSuccess &&
                           hipMemcpyAsync((void *)m->shape.indices, indices, nt * 3 * sizeof(int32_t), hipMemcpyHostToDevice, s) == hipSuccess;
@@ -207,6 +209,143 @@ ow_status ow_solid_draw_stats(ow_context *c, uint64_t *draws, uint64_t *skipped_
     if (drawn) *drawn = n[ow::kSolidLane] + n[ow::kSolidWave];
     if (draws) *draws = c->solid_draws;
     if (scratch_bytes) *scratch_bytes = c->solid.bytes;
+    return OW_OK;
+}
+
+}  // extern "C"
+
+/* ---- ray casts against the solids (ow_solid_cast.h, ow_solid_cast.hip) ---- */
+
+namespace {
+// ow_solid_cast_options (NULL = zeros) -> the cast's constants
+ow_status resolve_solid_cast_options(const ow_solid_cast_options *opts, ow::SolidCastParams *cp) {
+    static_assert(sizeof(ow_solid_cast_options) == sizeof(ow::SolidCastOptions) && offsetof(ow_solid_cast_options, cull) == offsetof(ow::SolidCastOptions, cull) &&
+                      offsetof(ow_solid_cast_options, reserved) == offsetof(ow::SolidCastOptions, reserved) && sizeof(ow_solid_hit) == sizeof(ow::SolidHit) &&
+                      offsetof(ow_solid_hit, normal) == offsetof(ow::SolidHit, normal) && offsetof(ow_solid_hit, status) == offsetof(ow::SolidHit, status) &&
+                      offsetof(ow_solid_hit, instance) == offsetof(ow::SolidHit, instance) && offsetof(ow_solid_hit, barycentric) == offsetof(ow::SolidHit, barycentric) &&
+                      offsetof(ow_solid_hit, reserved) == offsetof(ow::SolidHit, reserved) && OW_SOLID_CAST_TWO_SIDED == ow::kSolidCastTwoSided &&
+                      sizeof(ow_raycast_hit) == sizeof(ow::RaycastHit) && offsetof(ow_raycast_hit, status) == offsetof(ow::RaycastHit, status),
+                  "record layout");
+    cp->two_sided = 0;
+    cp->cull = 1;
+    if (!opts) return OW_OK;
+    if (opts->flags & ~OW_SOLID_CAST_TWO_SIDED) return fail(OW_ERR_INVALID, "unknown solid cast flags 0x%x", opts->flags);
+    if (opts->cull != 0 && opts->cull != -1) return fail(OW_ERR_INVALID, "cull %d is neither 0 nor -1", opts->cull);
+    if (ow_status st = check_reserved(opts->reserved, "ow_solid_cast_options"); st != OW_OK) return st;
+    cp->two_sided = (opts->flags & OW_SOLID_CAST_TWO_SIDED) ? 1 : 0;
+    cp->cull = opts->cull == 0 ? 1 : 0;
+    return OW_OK;
+}
+
+// the argument checks every form of the cast shares: ow_solid_draw's, in its order -- outputs, options, then the context and the shape
+ow_status check_solid_cast(const ow_context *c, const ow_solid *solid, const void *rays, int32_t count, const ow_solid_cast_options *opts, const void *out,
+                           ow::SolidCastParams *cp) {
+    if (count < 0) return fail(OW_ERR_INVALID, "count %d is negative", count);
+    if (count > 0 && (!rays || !out)) return fail(OW_ERR_INVALID, "null argument");
+    if (ow_status st = resolve_solid_cast_options(opts, cp); st != OW_OK) return st;
+    return check_handle(c, solid, "solid");
+}
+
+// One cast's scratch and launches on the context's stream, its instances from instance_source.  With host rays the rays, the water records
+// and the hit records lie in the scratch as well: the rays (and the records) go up first, the hits come back behind the launches.
+ow_status solid_cast_enqueue(ow_context *c, ow_solid *solid, const ow::SolidCastParams &cp, const ow_bodies *set, int first, const float *upload, int instances,
+                             const ow_ray *rays, int count, const ow_raycast_hit *water, ow_solid_hit *out, bool host_rays) {
+    OW_HIP(hipSetDevice(c->device));
+    Layout L;
+    L.take(ow::kSolidCastCounterBytes);  // the counters, at 0
+    const size_t b_off = L.take((size_t)instances * sizeof(ow::SolidCastBound));
+    const size_t t_off = L.take(instance_upload_bytes(upload, instances));
+    const size_t r_off = L.take(host_rays ? (size_t)count * sizeof(ow::Ray) : 0);
+    const size_t w_off = L.take(host_rays && water ? (size_t)count * sizeof(ow::RaycastHit) : 0);
+    const size_t h_off = L.take(host_rays ? (size_t)count * sizeof(ow::SolidHit) : 0);
+    if (ow_status st = sync_before_growth(c, c->solid_cast, L.total); st != OW_OK) return st;
+    if (ow_status st = c->solid_cast.ensure(L.total, 0, 1, "bytes of solid cast scratch"); st != OW_OK) return st;
+    char *base = (char *)c->solid_cast.ptr;
+    hipStream_t s = main_stream(c);
+    if (!solid->bound_enqueued) {  // once per shape, in stream order ahead of every cast that reads it
+        OW_HIP(ow::launch_solid_cast_shape_bound(solid->shape, solid->bound, s));
+        solid->bound_enqueued = true;
+    }
+    const ow::SolidCastArrays A{solid->shape, solid->bound, base, (ow::SolidCastBound *)(base + b_off)};
+    ow::SolidInstances in;
+    if (ow_status st = instance_source(set, first, upload, instances, base + t_off, s, &in); st != OW_OK) return st;
+    const ow::Ray *rays_dev = (const ow::Ray *)rays;
+    const ow::RaycastHit *water_dev = (const ow::RaycastHit *)water;
+    ow::SolidHit *out_dev = (ow::SolidHit *)out;
+    if (host_rays) {
+        OW_HIP(hipMemcpyAsync(base + r_off, rays, (size_t)count * sizeof(ow::Ray), hipMemcpyHostToDevice, s));
+        if (water) OW_HIP(hipMemcpyAsync(base + w_off, water, (size_t)count * sizeof(ow::RaycastHit), hipMemcpyHostToDevice, s));
+        rays_dev = (const ow::Ray *)(base + r_off);
+        water_dev = water ? (const ow::RaycastHit *)(base + w_off) : nullptr;
+        out_dev = (ow::SolidHit *)(base + h_off);
+    }
+    OW_HIP(ow::launch_solid_cast(A, in, cp, rays_dev, water_dev, count, out_dev, s));
+    ++c->solid_casts;
+    if (host_rays) {
+        OW_HIP(hipMemcpyAsync(out, out_dev, (size_t)count * sizeof(ow::SolidHit), hipMemcpyDeviceToHost, s));
+        return sync_stream(c, 0);
+    }
+    return OW_OK;
+}
+}  // namespace
+
+extern "C" {
+
+ow_status ow_cast_bodies(ow_context *c, ow_solid *solid, ow_bodies *bodies, int32_t first_body, int32_t body_count, const ow_ray *rays, int32_t count,
+                            const ow_raycast_hit *water_hits, const ow_solid_cast_options *opts, ow_solid_hit *out) {
+    ow::SolidCastParams cp;
+    if (ow_status st = check_solid_cast(c, solid, rays, count, opts, out, &cp); st != OW_OK) return st;
+    if (ow_status st = check_solid_bodies(c, solid, bodies, first_body, body_count); st != OW_OK) return st;
+    if (count == 0) return OW_OK;
+    return solid_cast_enqueue(c, solid, cp, bodies, first_body, nullptr, body_count, rays, count, water_hits, out, true);
+}
+
+ow_status ow_cast_bodies_async(ow_context *c, ow_solid *solid, ow_bodies *bodies, int32_t first_body, int32_t body_count, const ow_ray *rays_dev,
+                                  int32_t count, const ow_raycast_hit *water_hits_dev, const ow_solid_cast_options *opts, ow_solid_hit *out_dev) {
+    ow::SolidCastParams cp;
+    if (ow_status st = check_solid_cast(c, solid, rays_dev, count, opts, out_dev, &cp); st != OW_OK) return st;
+    if (ow_status st = check_solid_bodies(c, solid, bodies, first_body, body_count); st != OW_OK) return st;
+    if (((uintptr_t)out_dev & 15u) || ((uintptr_t)rays_dev & 3u) || ((uintptr_t)water_hits_dev & 3u))
+        return fail(OW_ERR_INVALID, "out_dev must be 16-byte, rays_dev and water_hits_dev 4-byte aligned");
+    if (count == 0) return OW_OK;
+    return solid_cast_enqueue(c, solid, cp, bodies, first_body, nullptr, body_count, rays_dev, count, water_hits_dev, out_dev, false);
+}
+
+ow_status ow_cast_instances(ow_context *c, ow_solid *solid, const float *transforms, int32_t instance_count, const ow_ray *rays, int32_t count,
+                                      const ow_raycast_hit *water_hits, const ow_solid_cast_options *opts, ow_solid_hit *out) {
+    if (instance_count < 0 || instance_count > OW_SOLID_MAX_INSTANCES)
+        return fail(OW_ERR_INVALID, "instance_count %d outside [0,%d]", instance_count, OW_SOLID_MAX_INSTANCES);
+    if (instance_count > 0 && !transforms) return fail(OW_ERR_INVALID, "null argument");
+    ow::SolidCastParams cp;
+    if (ow_status st = check_solid_cast(c, solid, rays, count, opts, out, &cp); st != OW_OK) return st;
+    if (ow_status st = check_solid_count(solid, instance_count); st != OW_OK) return st;
+    if (count == 0) return OW_OK;
+    return solid_cast_enqueue(c, solid, cp, nullptr, 0, transforms, instance_count, rays, count, water_hits, out, true);
+}
+
+ow_status ow_cast_stats(ow_context *c, uint64_t *casts, uint64_t *skipped_instances, uint64_t *sphere_tests_passed, uint64_t *pairs_tested,
+                                  uint64_t *scratch_bytes) {
+    if (!c) return fail(OW_ERR_INVALID, "null context");
+    uint64_t skipped = 0, passed = 0, pairs = 0;  // no cast yet, no scratch: zeros, and the device is not touched
+    if (c->solid_cast.ptr && (skipped_instances || sphere_tests_passed || pairs_tested)) {
+        alignas(8) unsigned char head[ow::kSolidCastCounterBytes];
+        OW_HIP(hipSetDevice(c->device));
+        if (ow_status st = read_back(c, head, c->solid_cast.ptr, sizeof(head)); st != OW_OK) return st;
+        uint32_t sk;
+        std::memcpy(&sk, head, sizeof(sk));
+        skipped = sk;
+        for (int k = 0; k < ow::kSolidCastSlots; ++k) {
+            uint64_t two[2];
+            std::memcpy(two, head + ow::kSolidCastSumsOffset + (size_t)k * ow::kSolidCastSlotWords * sizeof(uint64_t), sizeof(two));
+            passed += two[0];
+            pairs += two[1];
+        }
+    }
+    if (skipped_instances) *skipped_instances = skipped;
+    if (sphere_tests_passed) *sphere_tests_passed = passed;
+    if (pairs_tested) *pairs_tested = pairs;
+    if (casts) *casts = c->solid_casts;
+    if (scratch_bytes) *scratch_bytes = c->solid_cast.bytes;
     return OW_OK;
 }
 

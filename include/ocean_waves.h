@@ -1152,6 +1152,81 @@ ow_status ow_solid_draw_instances(ow_context *ctx, ow_solid *solid, const float 
 ow_status ow_solid_draw_stats(ow_context *ctx, uint64_t *draws, uint64_t *skipped_instances, uint64_t *culled, uint64_t *drawn,
                               uint64_t *scratch_bytes);
 
+/* Ray casts against the solids: where a ray first meets a shape at instance transforms -- the resident poses of an ow_bodies set, or a
+ * caller's array --, for projectiles, picking and lines of sight that the floating bodies block.  ow_raycast_surface knows the water alone;
+ * a scene cast is ow_raycast_surface, then this call with the water's records.  The definition, independent of how it is computed:
+ *   ray        an ow_ray; its validity and its unit direction d^ are ow_raycast_surface's.  A ray that is not valid gives the all-zero
+ *              record with status OW_RAY_INVALID
+ *   instances  ow_solid_draw's: instance i of a body set is body first_body + i, its twelve floats the resident pose record; an instance
+ *              with a value that is not finite, or a body whose fault flag is raised, is skipped and counted.  World vertices are
+ *              ow_solid_draw's w_k to the bit; a triangle with a vertex that is not finite is skipped
+ *   meeting    per (instance, triangle) pair, with p_k = w_k - origin in FP32 and everything after that in FP64:
+ *                N = (p1 - p0) x (p2 - p0),  e0 = d^ . (p1 x p2),  e1 = d^ . (p2 x p0),  e2 = d^ . (p0 x p1),  dn = d^ . N
+ *              the cross products written so that a x b = -(b x a) to the bit: two triangles that share an edge compute its function with
+ *              opposite sign and equal magnitude.  dn < 0 is the front (outward, counter-clockwise) side.  The ray meets the triangle
+ *              when dn != 0 and none of e0, e1, e2 has the sign opposite to dn's (e_i / dn are the barycentrics of the meeting point).
+ *              Zeros pass: edges are inclusive, a ray through a shared edge or vertex of a closed mesh is never lost.
+ *              t = (p0 . N) / dn, narrowed once to FP32, -0 stored as +0; the pair qualifies when 0 <= t <= T
+ *   facing     back faces (dn > 0) are dropped unless OW_SOLID_CAST_TWO_SIDED; with it they qualify and the normal reported is negated
+ *   limit      T = max_distance; with water_hits (one ow_raycast_hit per ray, as ow_raycast_surface[_async] wrote them for the same rays),
+ *              T = the water's t wherever that record has OW_RAY_HIT and its t is smaller.  The water is opaque, as in ow_solid_draw's
+ *              depth rule: a solid counts only when it is no farther than the water
+ *   winner     of all qualifying pairs the smallest 64-bit word (bits of t << 32) | (instance * num_triangles + triangle): the record
+ *              does not depend on launch shape, order or culling and is the same bytes on every run
+ *   record     ow_solid_hit: t; position = origin + t d^ per component in FP32 (ow_raycast_surface's operations; an overflow is stored
+ *              as +-FLT_MAX); normal = ow_solid_draw's unit normal of the world triangle (zeros for a triangle without area);
+ *              status = OW_RAY_HIT | OW_RAY_SOLID; instance and triangle; barycentric = e1 / s, e2 / s with s = (e0 + e1) + e2, narrowed
+ *              once.  Without a hit: status 0, instance = triangle = -1, every other field 0.  Nothing written is NaN or Inf
+ *   culling    is no part of the definition.  Instances are culled by a bounding sphere that is conservative for every finite transform
+ *              (scaled, sheared and mirrored ones included); ow_solid_cast_options.cull = -1 switches it off, for measurements
+ * The exact operations, identical in every build, are godotoceanwaves_amd/csrc/ow_solid_cast.h's.  There is no group form (ow_group_*)
+ * of these calls, as for every call on a body set. */
+#define OW_SOLID_CAST_TWO_SIDED 1u        /* ow_solid_cast_options.flags */
+typedef struct ow_solid_cast_options {
+    uint32_t flags;             /* OW_SOLID_CAST_TWO_SIDED */
+    int32_t cull;               /* measurement: 0 = the default (bounding spheres), -1 = no culling.  The records do not depend on it */
+    uint32_t reserved[6];       /* 0 */
+} ow_solid_cast_options;        /* 32 bytes; a NULL pointer = zeros: one-sided, culled */
+typedef struct ow_solid_hit {
+    float t;                    /* metres along d^ */
+    float position[3];
+    float normal[3];            /* unit, towards the side the ray came from */
+    int32_t status;             /* OW_RAY_HIT | OW_RAY_SOLID, 0 (no hit) or OW_RAY_INVALID */
+    int32_t instance;           /* -1 without a hit */
+    int32_t triangle;           /* -1 without a hit */
+    float barycentric[2];       /* the weights of the triangle's second and third vertex */
+    uint32_t reserved[4];       /* 0 */
+} ow_solid_hit;                 /* 64 bytes */
+typedef char ow_layout_check_solid_hit[(sizeof(ow_solid_hit) == 64 && offsetof(ow_solid_hit, normal) == 16 && offsetof(ow_solid_hit, status) == 28 &&
+                                        offsetof(ow_solid_hit, barycentric) == 40 && offsetof(ow_solid_hit, reserved) == 48 &&
+                                        sizeof(ow_solid_cast_options) == 32 && offsetof(ow_solid_cast_options, reserved) == 8) ? 1 : -1];
+
+/* Casts count rays in host memory against the shape at bodies [first_body, first_body + body_count) of the set, after everything enqueued
+ * so far, and writes count records to out.  water_hits: count records of ow_raycast_surface for the same rays, or NULL.  Synchronises.
+ * count = 0 is OW_OK and writes nothing.  The argument checks follow ow_solid_draw's order: outputs (a null rays or out with count > 0, a
+ * negative count), options (unknown flags, cull outside {-1, 0}, reserved words not 0), then the context, the shape and the body set (one of
+ * another context is refused), the range (outside the set, more than OW_SOLID_MAX_INSTANCES, or beyond the 2^24 product); OW_ERR_INVALID
+ * writes nothing.  The first two groups are checked without a device. */
+ow_status ow_cast_bodies(ow_context *ctx, ow_solid *solid, ow_bodies *bodies, int32_t first_body, int32_t body_count, const ow_ray *rays,
+                            int32_t count, const ow_raycast_hit *water_hits, const ow_solid_cast_options *opts, ow_solid_hit *out);
+/* The same with DEVICE pointers on the context's device (out_dev 16-byte aligned, rays_dev and water_hits_dev 4-byte aligned; opts is a host
+ * value), ordered exactly as ow_solid_draw_async: behind everything enqueued so far -- both chains, a caller's stream included -- and ahead
+ * of whatever the context enqueues next.  It reads the set's pose records and fault flags on the device.  No synchronisation, no copy and
+ * no host traffic; the only allocation is the context's grow-only scratch (the instance spheres and the counters), on first use or growth.
+ * ow_raycast_surface_async followed by this call with the first call's out_dev as water_hits_dev is the scene cast: no host step between. */
+ow_status ow_cast_bodies_async(ow_context *ctx, ow_solid *solid, ow_bodies *bodies, int32_t first_body, int32_t body_count, const ow_ray *rays_dev,
+                                  int32_t count, const ow_raycast_hit *water_hits_dev, const ow_solid_cast_options *opts, ow_solid_hit *out_dev);
+/* The same kernels over a caller's host array of instance_count transforms (instance_count x 12 floats, 0 .. OW_SOLID_MAX_INSTANCES): for
+ * hosts with their own rigid bodies.  Host pointers as ow_cast_bodies.  Synchronises. */
+ow_status ow_cast_instances(ow_context *ctx, ow_solid *solid, const float *transforms, int32_t instance_count, const ow_ray *rays,
+                                      int32_t count, const ow_raycast_hit *water_hits, const ow_solid_cast_options *opts, ow_solid_hit *out);
+/* Counters (each output may be NULL): casts enqueued on this context; of its last cast the instances skipped, and summed over its valid rays
+ * the instances that passed the sphere test and the (instance, triangle) pairs tested -- pairs_tested = sphere_tests_passed *
+ * num_triangles, and with cull = -1 sphere_tests_passed = valid rays * (instances - skipped_instances) --; the scratch bytes the context
+ * holds for these casts.  Synchronises when one of the three middle counters is asked for. */
+ow_status ow_cast_stats(ow_context *ctx, uint64_t *casts, uint64_t *skipped_instances, uint64_t *sphere_tests_passed, uint64_t *pairs_tested,
+                                  uint64_t *scratch_bytes);
+
 /* Finishing a picture: sky, fog, tonemap, sRGB.  The draws above leave linear colours in the records, one flat sky_color where nothing
  * was hit, and RGBA8 bytes that are clamped LINEAR values.  Two calls over the records, in the context's stream order, finish it -- the
  * counterpart of the reference scene's Environment (main.tscn:16-41: a panorama sky, depth fog from 200 m to 350 m, the filmic tonemap,
