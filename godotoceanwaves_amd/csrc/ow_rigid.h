@@ -28,6 +28,7 @@
 //        q_k += (dt * 0.5) * d_k;  q_k /= sqrt((qx^2 + qy^2) + (qz^2 + qw^2))   (the new w; R above is that of the old q)
 //      THERE IS NO GYROSCOPIC TERM (w x I w is dropped, as in examples/buoyancy_host.c): a freely tumbling asymmetric body keeps its
 //      angular velocity instead of precessing.  On the water the drag torque dominates it.
+//    Steps 1 and 3 have a twin in exact rational arithmetic written from this comment (tests/rigid_twin.py), which both builds are held to.
 //
 // Bodies that are not integrated.  mass <= 0: kinematic -- its record, points and result are computed, its state stays.  A body whose state
 // or inputs are not finite, or whose quaternion has no length (rigid_ok), is FAULTED: its record is the null record (identity basis, zeros,

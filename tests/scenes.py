@@ -299,6 +299,111 @@ def demo_bodies(counts=(64, 36, 72, 48), seed=0, spread=200.0):
     return make_bodies(items)
 
 
+PARITY_COUNTS = (1, 63, 64, 65, 200, 1000, 30)   # hull points per body: one, around a wave of 64, many; seven bodies span two blocks of four
+
+
+HALF_Q = (0.5, 0.5, 0.5, 0.5)   # R = [0 0 1; 1 0 0; 0 1 0] exactly: body x -> world y, y -> z, z -> x
+
+
+def random_rigid_states(count, seed):
+    """(RIGID_BODY records, BUOYANCY_RESULT records, dt per case) for single substeps: random unit q (every sixteenth of length 0.5, every
+    sixteenth of length 2), v, w, Fa, Ta, FP32 force and torque records of both signs from 1 to 1e4, masses from 10 to 5000, distinct Iinv,
+    every fifth case with one axis locked, dt cycling through 1/240, 1/60 and 0.1.  No hull: the records stand for it"""
+    rng = np.random.default_rng(seed)
+    st, res = np.zeros(count, W.RIGID_BODY), np.zeros(count, W.BUOYANCY_RESULT)
+    q = rng.normal(size=(count, 4))
+    q /= np.linalg.norm(q, axis=1)[:, None]
+    q[3::16] *= 0.5
+    q[11::16] *= 2.0
+    st["orientation"] = q
+    st["position"] = rng.uniform(-500, 500, (count, 3))
+    st["linear_velocity"], st["angular_velocity"] = rng.normal(0, 5, (count, 3)), rng.normal(0, 2, (count, 3))
+    st["mass"] = rng.uniform(10, 5000, count)
+    st["inverse_inertia"] = 10.0 ** rng.uniform(-4, -1, (count, 3))
+    for i in range(0, count, 5):
+        st["inverse_inertia"][i, (i // 5) % 3] = 0.0
+    st["applied_force"], st["applied_torque"] = rng.normal(0, 1e3, (count, 3)), rng.normal(0, 300, (count, 3))
+    st["linear_drag"], st["quadratic_drag"] = 0.6, 0.2
+    sign = lambda: rng.choice([-1.0, 1.0], (count, 3))   # noqa: E731
+    res["force"] = (sign() * 10.0 ** rng.uniform(0, 4, (count, 3))).astype(np.float32)
+    res["torque"] = (sign() * 10.0 ** rng.uniform(0, 4, (count, 3))).astype(np.float32)
+    dts = np.array([1.0 / 240.0, 1.0 / 60.0, 0.1])[np.arange(count) % 3]
+    return st, res, dts
+
+
+def seven_bodies(seed, height=None, spread=120.0):
+    """demo_bodies with PARITY_COUNTS hull points, body 6 kinematic and body 2 with its y axis locked; height: all of them that far up"""
+    st, hull = demo_bodies(counts=PARITY_COUNTS, seed=seed, spread=spread)
+    st["mass"][6] = 0.0
+    st["inverse_inertia"][2, 1] = 0.0
+    if height is not None:
+        st["position"][:, 1] = height
+    return st, hull
+
+
+def airborne_bodies(seed=21):
+    """seven_bodies 1000 m up with any unit orientation, spinning, pushed and twisted by applied loads"""
+    st, hull = seven_bodies(seed, height=1000.0)
+    rng = np.random.default_rng(seed + 1)
+    q = rng.normal(size=(len(st), 4))
+    st["orientation"] = q / np.linalg.norm(q, axis=1)[:, None]
+    st["angular_velocity"] = rng.normal(0, 2, (len(st), 3))
+    st["applied_force"], st["applied_torque"] = rng.normal(0, 1e3, (len(st), 3)), rng.normal(0, 300, (len(st), 3))
+    return st, hull
+
+
+BASIS_IINV = (0.375, 0.0625, 1.75)      # a, b, c: distinct, and exact in binary
+
+
+BASIS_TORQUE = 123.456
+
+
+def basis_bodies():
+    """seven bodies at rest at HALF_Q, 1000 m up, one applied torque each: (states, hull, per body the world axis of the torque, the body axis
+    whose Iinv it must meet, and whether that axis is locked).  Body 6 is kinematic"""
+    st, hull = seven_bodies(5, height=1000.0)
+    cases = [(1, 0, False), (2, 1, False), (0, 2, False), (1, 0, True), (2, 1, True), (1, 0, False), (1, 0, False)]
+    for b, (world, body, locked) in enumerate(cases):
+        st["orientation"][b] = HALF_Q
+        st["linear_velocity"][b] = st["angular_velocity"][b] = st["applied_force"][b] = st["applied_torque"][b] = 0.0
+        st["inverse_inertia"][b] = BASIS_IINV
+        if locked:
+            st["inverse_inertia"][b, body] = 0.0
+        st["applied_torque"][b, world] = BASIS_TORQUE if b != 5 else -BASIS_TORQUE
+    return st, hull, cases
+
+
+SPIN_Q0, SPIN_W = ((1, 2, 3), 0.7), (1.1, -2.3, 0.7)
+
+
+def spin_bodies():
+    """seven bodies spinning freely 10^6 m up (no applied load, no contact): body 0 is SPIN_Q0 / SPIN_W, the others other axes and rates; body 2
+    has an axis locked (no torque ever meets it) and body 6 is kinematic"""
+    st, hull = seven_bodies(9, height=1e6)
+    rng = np.random.default_rng(10)
+    for b in range(len(st)):
+        st["orientation"][b] = quaternion(*SPIN_Q0) if b == 0 else quaternion(rng.normal(size=3), rng.uniform(-3, 3))
+        st["angular_velocity"][b] = SPIN_W if b == 0 else rng.normal(0, 2, 3)
+        st["linear_velocity"][b] = st["applied_force"][b] = st["applied_torque"][b] = 0.0
+    return st, hull
+
+
+def saturated_bodies():
+    """three crates whose FP64 state is finite and beyond FP32: far out, one moving and one spinning faster than FP32 holds"""
+    st, hull = make_bodies([crate(origin=(1e39, 0.0, -1e39), divisions=(2, 2, 2), kl=3.0, kq=0.5),
+                            crate(origin=(3.5e38, 0.0, 0.0), divisions=(2, 2, 2), v=(1e39, 0, 0), kl=3.0, kq=0.5),
+                            crate(origin=(0.0, -1e39, 0.0), divisions=(2, 2, 2), w=(0, -1e39, 0), kl=3.0, kq=0.5)])
+    return st, hull
+
+
+TILT_SIZE = (2.0, 0.5, 2.0)
+
+
+def tilted_box(axis, angle):
+    """a wide, flat box of half the water's density at its Archimedes draft (its centre on the calm surface), at rest, tilted about `axis`"""
+    return make_bodies([crate(size=TILT_SIZE, divisions=(6, 4, 6), origin=(0.0, 0.0, 0.0), q=quaternion(axis, angle), kl=3.0, kq=0.5)])
+
+
 def hip():
     h = C.CDLL("libamdhip64.so")
     h.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
