@@ -36,6 +36,8 @@ OW_RADIANCE_MAX_LEVELS, OW_RADIANCE_MAX_SAMPLES, OW_RADIANCE_IRRADIANCE = 8, 256
 OW_RAY_SHADOWED = 128
 OW_SHADOW_CAST_BOTH_SIDES, OW_SHADOW_RECEIVE_WATER = 1, 1
 OW_SHADOW_MIN_SIZE, OW_SHADOW_MAX_SIZE = 8, 8192
+OW_RAY_MIST = 256
+OW_MIST_MAX_SLICES = 256
 OW_SKY_MAX_SIDE = 8192
 OW_PRESENT_MAX_DOWNSAMPLE = 4
 OW_FOG_EXPONENTIAL, OW_FOG_DEPTH = 0, 1
@@ -293,6 +295,13 @@ class ow_shadow_options(C.Structure):
                 ("reserved", C.c_uint32 * 11)]
 
 
+class ow_mist_options(C.Structure):
+    """struct ow_mist_options (128 bytes); a NULL pointer = ow_mist_options_init's values (the reference scene's sea mist)"""
+    _fields_ = [("extinction", C.c_float), ("height_falloff", C.c_float), ("base_height", C.c_float), ("length", C.c_float), ("anisotropy", C.c_float),
+                ("sky_affect", C.c_float), ("slices", C.c_int32), ("flags", C.c_uint32), ("shadow_bias", C.c_float), ("albedo", C.c_float * 3),
+                ("sun_color", C.c_float * 3), ("sun_direction", C.c_float * 3), ("ambient_color", C.c_float * 3), ("reserved", C.c_uint32 * 11)]
+
+
 class ow_mesh_vertex(C.Structure):
     """struct ow_mesh_vertex (48 bytes): the vertex stage's record of a mesh draw"""
     _fields_ = [("position", C.c_float * 3), ("wave_height", C.c_float), ("uv", C.c_float * 2), ("distance_factor", C.c_float),
@@ -429,6 +438,10 @@ SIGNATURES = {
     "ow_shadow_apply": (C.c_int, [C.c_void_p, C.c_void_p, _P(ow_camera), _P(ow_shadow_options), C.c_void_p, C.c_void_p]),
     "ow_shadow_apply_async": (C.c_int, [C.c_void_p, C.c_void_p, _P(ow_camera), _P(ow_shadow_options), C.c_void_p, C.c_void_p]),
     "ow_shadow_stats": (C.c_int, [C.c_void_p, C.c_void_p, _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64)]),
+    "ow_mist_options_init": (None, [_P(ow_mist_options)]),
+    "ow_mist_apply": (C.c_int, [C.c_void_p, C.c_void_p, _P(ow_camera), _P(ow_mist_options), C.c_void_p, C.c_void_p]),
+    "ow_mist_apply_async": (C.c_int, [C.c_void_p, C.c_void_p, _P(ow_camera), _P(ow_mist_options), C.c_void_p, C.c_void_p]),
+    "ow_mist_stats": (C.c_int, [C.c_void_p, _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64)]),
     "ow_get_maps_f32": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
     "ow_get_spectrum": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "ow_get_intermediate": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),

@@ -25,6 +25,7 @@ UNITS = {
     "ow_spray_host.hip": [],
     "ow_solid_host.hip": [],
     "ow_sky_host.hip": [],
+    "ow_mist_host.hip": [],
     "ow_consumer.hip": EXACT,
     "ow_group.hip": [],
     "ow_velocity.hip": [],
@@ -36,6 +37,7 @@ UNITS = {
     "ow_environment.hip": EXACT,
     "ow_sky_light.hip": EXACT,
     "ow_shadow.hip": EXACT,
+    "ow_mist.hip": EXACT,
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-fno-fast-math", "-fvisibility=hidden", "-Wall", "-Wno-unused-function"]
 

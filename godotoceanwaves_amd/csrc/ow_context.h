@@ -217,7 +217,10 @@ struct ow_context {
     // The synchronous ow_shadow_apply uses render_pixels and render_rgba; a shadow map's scratch is the map's own (ow_shadow_map).
     // The synchronous ow_environment_apply uses render_pixels; the synchronous ow_present render_pixels for the records and render_rgba for both
     // outputs (the float4 pixels first, then the RGBA8 words).  Their asynchronous forms use no scratch.
-    ow::DeviceScratch query_scratch, buoy_scratch, ray_scratch, render_rgba, render_pixels, mesh_vis, billboard, solid, solid_cast;
+    // mist: the copies of the three 64-bit counters of the last ow_mist_apply (ow_mist.h kMistCounterBytes), allocated by the first pass in either form;
+    // the synchronous form uses render_pixels and render_rgba as well.
+    ow::DeviceScratch query_scratch, buoy_scratch, ray_scratch, render_rgba, render_pixels, mesh_vis, billboard, solid, solid_cast, mist;
+    uint64_t mist_passes = 0;      // ow_mist_stats
     uint64_t billboard_draws = 0;  // ow_billboard_draw_stats
     uint64_t solid_draws = 0;      // ow_solid_draw_stats
     uint64_t solid_casts = 0;      // ow_cast_stats

@@ -29,7 +29,7 @@
 //              color = glsl_mix(color, fog colour, amount) per channel; a channel that is not finite takes the fog colour.
 //   status     every pixel that is processed gets kRayEnvironment; a pixel that carries it already is left alone (applying twice is
 //              applying once).  Nothing but color and status changes.  A camera that is not finite (mesh_camera_ok) changes nothing.
-//   out of scope: height fog, volumetric fog, the FogVolume node; light FROM the sky on the surfaces (its irradiance, its blurred radiance
+//   out of scope: height fog, volumetric fog, the FogVolume node (ow_mist.h's pass, which goes after this one); light FROM the sky on the surfaces (its irradiance, its blurred radiance
 //              levels in the water) is ow_sky_light.h's pass, which goes before this one; this pass still reads the sky unblurred.  Spray drawn afterwards is not fogged: the emitter sits tens of metres
 //              from the camera, where the scene's depth fog (from 200 m) is 0.
 //

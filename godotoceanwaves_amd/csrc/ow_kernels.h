@@ -8,6 +8,7 @@
 #include "ow_environment.h"
 #include "ow_raycast.h"
 #include "ow_mesh.h"
+#include "ow_mist.h"
 #include "ow_render.h"
 #include "ow_rigid.h"
 #include "ow_shadow.h"
@@ -196,6 +197,12 @@ hipError_t launch_shadow_cast(const ShadowArrays &A, const SolidInstances &in, c
 // k_shadow_apply over cam.width x cam.height records, receivers rewritten in place, and the RGBA8 words (may be null), on `s`
 hipError_t launch_shadow_apply(const uint32_t *map, const CameraParams &cam, const ShadowParams &P, const ShadowApply &ap, RenderPixel *pixels_dev,
                                uint32_t *rgba_dev, hipStream_t s);
+
+// the height mist (ow_mist.hip; the medium, the slices, the depth compare and the pixel's arithmetic in ow_mist.h)
+// The pass's kMistCounters counters cleared, then k_mist_apply over cam.width x cam.height records, rewritten in place, and the RGBA8 words
+// (may be null), on `s`.  map: a shadow map's depth words, or null (no map, or one without a frame: P is not read then).
+hipError_t launch_mist_apply(const uint32_t *map, const CameraParams &cam, const ShadowParams &P, const MistParams &mp, RenderPixel *pixels_dev, uint32_t *rgba_dev,
+                             unsigned long long *counters_dev, hipStream_t s);
 
 bool supported_map_size(int n);
 int kernel_family(int n, int slots, int mode);  // 1 standard, 2 layer-parallel, 3 compact: what launch_pass1/2 will use

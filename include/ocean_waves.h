@@ -1256,7 +1256,8 @@ ow_status ow_cast_stats(ow_context *ctx, uint64_t *casts, uint64_t *skipped_inst
  *   status     every pixel the pass processes gets OW_RAY_ENVIRONMENT; one that carries it already is left alone, so applying twice
  *              equals applying once.  Nothing but color and status changes in a record
  *   finite     a camera that is not finite (ow_mesh_draw's rule) leaves every record as it was
- *   not here   height fog, volumetric fog and the FogVolume node; the ACES tonemap
+ *   not here   the ACES tonemap.  (height fog, volumetric fog and the FogVolume node are not this pass's either: they are ow_mist_apply's,
+ *              below, which goes between this pass and the billboards)
  *   present    camera.width x camera.height is the size of the RECORDS; the output is (width / s) x (height / s), s = downsample in
  *              1 .. OW_PRESENT_MAX_DOWNSAMPLE (0 selects 1; a side s does not divide is OW_ERR_INVALID).  Drawing at s times the size and
  *              presenting is the library's anti-aliasing.  Per output pixel:
@@ -1450,7 +1451,8 @@ ow_status ow_radiance_light_apply_async(ow_context *ctx, ow_radiance *radiance, 
  * records keep albedo, diffuse, specular and color apart, so it comes out exactly as it went in.  Both run in the context's stream
  * order.  Nothing is shadowed until ow_shadow_apply is called.  With it the frame order is
  *     water -> solids -> ow_shadow_apply -> ow_radiance_light_apply -> ow_environment_apply -> billboards -> ow_present
- * (the sky-light pass only adds to color, so the two passes commute up to rounding; this is the documented order).
+ * (the sky-light pass only adds to color, so the two passes commute up to rounding; this is the documented order; with the height mist,
+ * ow_mist_apply below, it becomes ... -> ow_environment_apply -> ow_mist_apply -> billboards -> ow_present).
  * Everything below is THIS LIBRARY'S CHOICE modelled on the engine's directional shadow; the engine's source is not part of the
  * reference, so this text and godotoceanwaves_amd/csrc/ow_shadow.h (the exact operations, identical in every build) are the authority.
  * main.tscn:114-117's shadow_bias 0, shadow_normal_bias 6.464 and shadow_opacity 0.8 are the defaults; shadow_blur 5 has no unit to
@@ -1490,7 +1492,7 @@ ow_status ow_radiance_light_apply_async(ow_context *ctx, ow_radiance *radiance, 
  *   finite     a camera that is not finite (ow_mesh_draw's rule), or a map that has had no ow_shadow_map_begin, leaves every record as
  *              it was.  RGBA8 is optional, covers every pixel and is packed from color as ow_render_view packs it
  *   not here   cascaded or split maps, fitting the frame to a camera, a penumbra search, shadows from the water or the spray (the scene
- *              sets cast_shadow = 0 on both), shadowed fog scatter
+ *              sets cast_shadow = 0 on both).  (Shadowed fog scatter is ow_mist_apply's, below: it reads this map)
  * There is no group form (ow_group_*) of these calls, as for every draw. */
 #define OW_RAY_SHADOWED 128               /* ow_render_pixel.status: ow_shadow_apply has taken the pixel as a receiver */
 #define OW_SHADOW_CAST_BOTH_SIDES 1u      /* ow_shadow_frame.flags */
@@ -1562,6 +1564,84 @@ ow_status ow_shadow_apply_async(ow_context *ctx, ow_shadow_map *map, const ow_ca
  * holds.  Synchronises when one of the three middle counters is asked for. */
 ow_status ow_shadow_stats(ow_context *ctx, ow_shadow_map *map, uint64_t *casts, uint64_t *skipped_instances, uint64_t *culled, uint64_t *drawn,
                           uint64_t *scratch_bytes);
+
+/* Height mist with sun shafts.  The reference scene turns volumetric fog on with length 256 (main.tscn:35-37) and puts a world-sized
+ * FogVolume in it (:100-104, :142-144) whose FogMaterial's density falls off with height (height_falloff = 0.176): the sea mist that lies
+ * on the water.  The low sun (main.tscn:113) and the crates' depth map (ow_shadow_map_*) are already resident, so the same pass cuts the
+ * crates' shadow shafts out of the mist.  With it the frame order is
+ *     water -> solids -> ow_shadow_apply -> ow_radiance_light_apply -> ow_environment_apply -> ow_mist_apply -> billboards -> ow_present
+ * Everything below is THIS LIBRARY'S CHOICE modelled on the engine's volumetric fog; the engine's source is not part of the reference,
+ * so this text and godotoceanwaves_amd/csrc/ow_mist.h (the exact operations, identical in every build) are the authority.
+ *   medium     for a camera ray from o along the unit direction d: h(t) = (o.y - base_height) + t d.y.  The weight is w(h) = 1 for h <= 0
+ *              and exp(-k h) above, k = height_falloff ln 2 (FP64 on the host, narrowed once): FogMaterial's
+ *              clamp(exp2(-height_falloff (y - y_object)), 0, 1).  I(t) = the integral of w(h(s)) over [0, t];
+ *              T(t) = exp(-extinction I(t)).  I is evaluated in closed form per segment as length x mean weight (a segment at or below
+ *              the base has mean 1; one above it exp(-k h_a) phi(k (h_b - h_a)) with phi(x) = (1 - exp(-x)) / x, by its series near 0;
+ *              one that crosses the base is split at the crossing), never as a difference of antiderivatives, which cancels for
+ *              near-horizontal rays
+ *   ray        ow_environment_apply's.  t_end = min(record.t, length) for a record with OW_RAY_HIT, length otherwise.  N = slices (0
+ *              selects 64, at most OW_MIST_MAX_SLICES); boundaries t_i = t_end (i / N)^2 (the engine's detail spread of 2 puts the
+ *              slices near the eye); midpoints m_i = (t_i + t_{i+1}) / 2
+ *   shafts     V_i is ONE depth compare of the world point o + m_i d in the shadow map: ow_shadow_map_begin's frame transform as it is,
+ *              the texel containing (s, t); the point is lit when d - shadow_bias w <= D (w metres per texel).  A point outside the
+ *              footprint, beyond 2 depth_range, with a NULL map, or with a map that has had no ow_shadow_map_begin is lit
+ *   pixel      A = 1 - T(t_end).  B = the sum over the slices with V_i = 0 of (T(t_i) - T(t_{i+1})), in ascending i in FP32, clamped
+ *              to [0, A].  S = albedo * (sun_color p(cos) (A - B) + ambient_color A) per channel, p(c) = (1 - g^2) / (q sqrt(q)),
+ *              q = 1 + g^2 - 2 g c, c = d . sun^, g = anisotropy.  color = color (1 - A) + S; a channel that is not finite takes S.
+ *              For a pixel without OW_RAY_HIT, A and S are first multiplied by sky_affect.  The shadowed share is SUBTRACTED on purpose:
+ *              a lit slice contributes exactly nothing, so a pixel with no shadowed slice is the closed form to the bit, and a NULL
+ *              map, an empty map and a map whose casters no ray passes behind give the same bytes
+ *   status     every pixel the pass processes gets OW_RAY_MIST; one that carries it already is left alone, so applying twice equals
+ *              applying once.  Only color and status change in a record.  A camera that is not finite (ow_mesh_draw's rule) leaves
+ *              everything as it was.  Nothing written is NaN or Inf.  RGBA8 is optional, covers every pixel and is packed from color
+ *              as ow_render_view packs it
+ *   not here   local fog volumes, density textures, temporal reprojection, light from the sky in the mist.  Spray drawn afterwards is
+ *              not fogged, as under ow_environment_apply
+ * There is no group form (ow_group_*) of these calls, as for every draw. */
+#define OW_RAY_MIST 256                   /* ow_render_pixel.status: ow_mist_apply has processed the pixel */
+#define OW_MIST_MAX_SLICES 256
+typedef struct ow_mist_options {
+    float extinction;           /* 1 / m at and below the base, [0, 1e3] */
+    float height_falloff;       /* FogMaterial.height_falloff, [0, 1e3]: the density halves every 1 / height_falloff metres above the base */
+    float base_height;          /* world y of the base, [-1e6, 1e6] */
+    float length;               /* metres of ray the mist is gathered over, [0, 1e6] (Environment.volumetric_fog_length) */
+    float anisotropy;           /* g of the phase function, [-0.9, 0.9] */
+    float sky_affect;           /* [0, 1]: the share of the mist a pixel without a hit takes */
+    int32_t slices;             /* 0 (= 64), 1 .. OW_MIST_MAX_SLICES */
+    uint32_t flags;             /* 0 */
+    float shadow_bias;          /* texels of depth, [-1e6, 1e6] */
+    float albedo[3];            /* linear, each in [0, 1e6] */
+    float sun_color[3];         /* colour times energy, linear, each in [0, 1e6] */
+    float sun_direction[3];     /* towards the sun, world space, any finite length > 0 */
+    float ambient_color[3];     /* linear, each in [0, 1e6] */
+    uint32_t reserved[11];      /* 0 */
+} ow_mist_options;              /* 128 bytes; a NULL pointer = ow_mist_options_init's values */
+typedef char ow_layout_check_mist_options[(sizeof(ow_mist_options) == 128 && offsetof(ow_mist_options, slices) == 24 &&
+                                           offsetof(ow_mist_options, shadow_bias) == 32 && offsetof(ow_mist_options, albedo) == 36 &&
+                                           offsetof(ow_mist_options, reserved) == 84) ? 1 : -1];
+
+/* The scene's values: height_falloff 0.176, albedo (0.988718, 0.989631, 0.989629), length 256, base 0, the Sun's +Z axis
+ * (ow_render_options_default's light, a white sun of energy 1, and its ambient colour); the engine's defaults: anisotropy 0.2, sky affect
+ * 1; 64 slices, shadow_bias 0.  extinction 0.02 / m is this library's choice: main.tscn:101's density 8.0 is in an engine unit whose
+ * scale the reference does not carry.  A NULL pointer returns without writing. */
+void ow_mist_options_init(ow_mist_options *out);
+/* Lays the mist over a picture in host memory, after everything enqueued so far.  map_or_null: the crates' depth map, or NULL for mist
+ * without shafts.  pixels_inout: width * height ow_render_pixel records (required); rgba8_out: width * height * 4 bytes, may be NULL.
+ * Synchronises.  The argument checks follow ow_shadow_apply's order: the records, the camera, the options (a value that is not finite or
+ * out of its range, slices outside [0, OW_MIST_MAX_SLICES], a sun direction of zero length, flags or reserved words not 0), then the
+ * context and the map (one of another context is refused); OW_ERR_INVALID writes nothing.  The first three groups are checked without a
+ * device. */
+ow_status ow_mist_apply(ow_context *ctx, ow_shadow_map *map_or_null, const ow_camera *camera, const ow_mist_options *opts,
+                        ow_render_pixel *pixels_inout, void *rgba8_out_or_null);
+/* The same with DEVICE pointers on the context's device (rgba8_dev 4-byte aligned, pixels_dev 16-byte aligned; camera and opts are host
+ * values), ordered exactly as ow_shadow_apply_async: behind everything enqueued so far -- both chains, a caller's stream included -- and
+ * ahead of whatever the context enqueues next.  No synchronisation, no copy and no host traffic; the only allocation is the context's
+ * counters (8 KB), by its first pass in either form. */
+ow_status ow_mist_apply_async(ow_context *ctx, ow_shadow_map *map_or_null, const ow_camera *camera, const ow_mist_options *opts,
+                              ow_render_pixel *pixels_dev, void *rgba8_dev_or_null);
+/* Counters (each output may be NULL): the passes enqueued on this context, and over the LAST pass the pixels it processed, the slices
+ * whose depth compare read the map (0 without a map) and the slices found shadowed.  Synchronises when one of the last three is asked for. */
+ow_status ow_mist_stats(ow_context *ctx, uint64_t *passes, uint64_t *pixels, uint64_t *slices_fetched, uint64_t *slices_shadowed);
 
 /* ---- several devices: cascades sharded inside one process ---------------------------------------- */
 
