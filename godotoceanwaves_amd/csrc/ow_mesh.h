@@ -49,6 +49,7 @@ constexpr uint32_t kMeshVertexNotFinite = 1u;  // OW_MESH_VERTEX_NOT_FINITE
 constexpr float kMeshDefaultNear = 0.05f;      // Camera3D.near
 constexpr int kMeshLaneBox = 4;                // a pixel box of at most this many centres a side is walked by the triangle's own lane
 constexpr uint64_t kMeshNoTriangle = ~(uint64_t)0;
+constexpr float kMeshDepthSlack = 0.000244140625f;  // 2^-12: how far tri_setup's box reaches past near and max_distance, relative to either
 
 struct MeshParams {
     QueryParams qp;    // the falloff flag and centre; the solver's settings are not read
@@ -179,7 +180,10 @@ OW_DEV uint64_t mesh_word(float depth, int tri) {
 // A triangle's set-up: its class and, for the two drawn classes, the planes and the box of pixel centres that may be covered.  The box
 // is that of the triangle's part in front of the near plane (its corners and the points where its edges cross z = -near), projected and
 // widened by what the projection's rounding can move a corner -- a sixteenth of a pixel, and for a triangle that crosses the near plane the
-// error of the crossing points magnified by 1 / near -- then clamped to the image.  A box that holds no pixel centre is culled.
+// error of the crossing points magnified by 1 / near -- then clamped to the image.  A box that holds no pixel centre is culled.  The plane
+// the box is cut at lies kMeshDepthSlack inside the near plane, and a triangle counts as beyond the far distance only that much past it:
+// with the planes themselves a triangle whose depths lie within a few ulp of near (or of max_distance) had centres covered outside its
+// box, or was culled whole, because the depth tri_cover tests is itself rounded (tests/test_raster_edges.py, the `near` and `far` families; profiles/raster_edges.txt).
 struct TriSetup {
     TriPlanes p;
     int x0, x1, y0, y1;
@@ -201,7 +205,9 @@ OW_DEV TriSetup tri_setup(const MeshVertex &a, const MeshVertex &b, const MeshVe
     s.p = tri_planes(a.view, b.view, c.view);
     if (!(s.p.det != 0.0f) || (mp.cull_back && s.p.det > 0.0f)) return s;
     const float *V[3] = {a.view, b.view, c.view};
-    const float zc = mp.near;
+    // tri_cover compares a rounded depth (det / rn in FP32) with near and max_distance, so a centre whose exact depth is a few ulp on the
+    // wrong side of either can still be covered: the box is cut at planes kMeshDepthSlack inside near and beyond max_distance
+    const float zc = mp.near * (1.0f - kMeshDepthSlack), zfar = cam.max_distance * (1.0f + kMeshDepthSlack);
     const float sxp = (float)cam.width / (2.0f * cam.aspect * cam.tan_half_fov), syp = (float)cam.height / (2.0f * cam.tan_half_fov);
     const float hx = 0.5f * (float)cam.width, hy = 0.5f * (float)cam.height;
     float lox = 3.0e38f, hix = -3.0e38f, loy = 3.0e38f, hiy = -3.0e38f, vmax = 0.0f;
@@ -209,7 +215,7 @@ OW_DEV TriSetup tri_setup(const MeshVertex &a, const MeshVertex &b, const MeshVe
     for (int k = 0; k < 3; ++k) {
         const float z = -V[k][2];
         vmax = fmaxf(vmax, fmaxf(fabsf(V[k][0]), fmaxf(fabsf(V[k][1]), fabsf(z))));
-        all_far = all_far && z > cam.max_distance;
+        all_far = all_far && z > zfar;
         if (z > zc) {
             const float cx = (V[k][0] / z) * sxp + hx, cy = hy - (V[k][1] / z) * syp;
             lox = fminf(lox, cx);

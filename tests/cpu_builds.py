@@ -307,11 +307,19 @@ def mesh_harness():
     L.harness_mesh_sizes.argtypes = [V]
     L.harness_mesh_vertices.argtypes = [V, I, I, V, V, I, V, I, F, F, V, V]
     L.harness_mesh_draw.argtypes = [V, V, I, I, V, V, I, V, I, V, V, I, I, V, I, F, F, F, I, I, V, V, V, V, V]
+    L.harness_mesh_cover_all.argtypes = L.harness_mesh_draw.argtypes + [V]
+    L.harness_mesh_setups.argtypes = L.harness_mesh_draw.argtypes[:20] + [V]
     return L
 
 
-def cpu_mesh_draw(L, disp, norm, scales, mesh, origin, cam, options=None):
-    """the CPU build's draw: dict of vertices, vis [H][W] uint64, rgba [H][W][4], rec [H][W], counters (skipped, culled, per_lane, cooperative)"""
+SETUP = np.dtype([("kind", np.int32), ("x0", np.int32), ("x1", np.int32), ("y0", np.int32), ("y1", np.int32)])   # a triangle's set-up, as the harnesses return it
+COVER = np.dtype([("covered", np.int32), ("outside", np.int32)])   # a brute pass's count per triangle: centres covered, and of those outside its box
+
+
+def cpu_mesh_draw(L, disp, norm, scales, mesh, origin, cam, options=None, brute=False):
+    """the CPU build's draw: dict of vertices, vis [H][W] uint64, rgba [H][W][4], rec [H][W], counters (skipped, culled, per_lane, cooperative).
+    brute: harness_mesh_cover_all, every centre of the picture instead of the set-up's box, and `cover` and `setups` per triangle;
+    brute="setups": the set-ups alone, nothing drawn"""
     o = options or {}
     d, m = maps_u16(disp), maps_u16(norm)
     sc = np.ascontiguousarray(scales, np.float32)
@@ -323,10 +331,17 @@ def cpu_mesh_draw(L, disp, norm, scales, mesh, origin, cam, options=None):
     cw, sw = camera_words(cam), shade_words(o)
     out = dict(vertices=np.zeros(len(v), W.MESH_VERTEX), vis=np.zeros((cam.height, cam.width), np.uint64),
                rgba=np.zeros((cam.height, cam.width, 4), np.uint8), rec=np.zeros((cam.height, cam.width), W.RENDER_PIXEL), counters=np.zeros(4, np.uint32))
-    L.harness_mesh_draw(d.ctypes.data, m.ctypes.data, d.shape[1], len(sc), sc.ctypes.data, v.ctypes.data, len(v), t.ctypes.data, len(t), org.ctypes.data,
-                        cw.ctypes.data, cam.width, cam.height, sw.ctypes.data, int(center is not None), cx, cz, float(o.get("near", 0.0)),
-                        int(bool(o.get("cull_back"))), int(o.get("lane_box", 0)), out["vertices"].ctypes.data, out["vis"].ctypes.data,
-                        out["rgba"].ctypes.data, out["rec"].ctypes.data, out["counters"].ctypes.data)
+    inputs = (d.ctypes.data, m.ctypes.data, d.shape[1], len(sc), sc.ctypes.data, v.ctypes.data, len(v), t.ctypes.data, len(t), org.ctypes.data,
+              cw.ctypes.data, cam.width, cam.height, sw.ctypes.data, int(center is not None), cx, cz, float(o.get("near", 0.0)),
+              int(bool(o.get("cull_back"))), int(o.get("lane_box", 0)))
+    outputs = (out["vertices"].ctypes.data, out["vis"].ctypes.data, out["rgba"].ctypes.data, out["rec"].ctypes.data, out["counters"].ctypes.data)
+    if not brute:
+        L.harness_mesh_draw(*inputs, *outputs)
+        return out
+    out.update(cover=np.zeros(len(t), COVER), setups=np.zeros(len(t), SETUP))
+    L.harness_mesh_setups(*inputs, out["setups"].ctypes.data)
+    if brute != "setups":
+        L.harness_mesh_cover_all(*inputs, *outputs, out["cover"].ctypes.data)
     return out
 
 
@@ -462,6 +477,8 @@ def solid_harness():
     V = C.c_void_p
     L.harness_solid_sizes.argtypes = [V]
     L.harness_solid_draw.argtypes = [V] * 9
+    L.harness_solid_cover_all.argtypes = [V] * 10
+    L.harness_solid_setups.argtypes = [V] * 6
     return L
 
 
@@ -487,18 +504,29 @@ def solid_case_arrays(shape, tf, records, flags=None):
     return v, t, tf, fl, rec
 
 
-def cpu_solid_draw(L, shape, tf, cam, opts=None, records=None, stride=12, flags=None):
-    """the CPU build's draw: dict of rgba [H][W][4], rec [H][W] or None, vis [H][W], skipped, culled, lane, wave, drawn"""
+def cpu_solid_draw(L, shape, tf, cam, opts=None, records=None, stride=12, flags=None, brute=False):
+    """the CPU build's draw: dict of rgba [H][W][4], rec [H][W] or None, vis [H][W], skipped, culled, lane, wave, drawn.  brute:
+    harness_solid_cover_all, every centre of the picture instead of the set-up's box, and `cover` and `setups` per (instance, triangle) pair;
+    brute="setups": the set-ups alone"""
     v, t, tf, fl, rec = solid_case_arrays(shape, tf, records, flags)
     count = tf.size // stride
     h = solid_case_of(cam, (v, t), count, opts, records, stride, fl)
     rgba = np.zeros((cam.height, cam.width, 4), np.uint8)
     vis = np.zeros((cam.height, cam.width), np.uint64)
     counters = np.zeros(4, np.uint32)
-    L.harness_solid_draw(h.ctypes.data, v.ctypes.data, t.ctypes.data, tf.ctypes.data if tf.size else None, fl.ctypes.data if fl is not None else None,
-                         rec.ctypes.data if rec is not None else None, rgba.ctypes.data, counters.ctypes.data, vis.ctypes.data)
+    inputs = (h.ctypes.data, v.ctypes.data, t.ctypes.data, tf.ctypes.data if tf.size else None, fl.ctypes.data if fl is not None else None)
+    outputs = (rec.ctypes.data if rec is not None else None, rgba.ctypes.data, counters.ctypes.data, vis.ctypes.data)
+    extra = {}
+    if brute:
+        extra = dict(cover=np.zeros(count * len(t), COVER), setups=np.zeros(count * len(t), SETUP))
+        L.harness_solid_setups(*inputs, extra["setups"].ctypes.data)
+        if brute == "setups":
+            return extra
+        L.harness_solid_cover_all(*inputs, *outputs, extra["cover"].ctypes.data)
+    else:
+        L.harness_solid_draw(*inputs, *outputs)
     s, c, ln, wv = (int(x) for x in counters)
-    return dict(rgba=rgba, rec=rec, vis=vis, skipped=s, culled=c, lane=ln, wave=wv, drawn=ln + wv)
+    return dict(rgba=rgba, rec=rec, vis=vis, skipped=s, culled=c, lane=ln, wave=wv, drawn=ln + wv, **extra)
 
 
 def calm_picture(mesh_harness, cam):
@@ -722,7 +750,33 @@ def shadow_harness():
     L.harness_shadow_clear.argtypes = [I, V, V]
     L.harness_shadow_cast.argtypes = [V, I, V, I, V, I, V, I, V, I, V, V, V]
     L.harness_shadow_apply.argtypes = [V, I, V, I, V, I, I, V, V, V]
+    L.harness_shadow_cover_all.argtypes = L.harness_shadow_cast.argtypes + [V]
+    L.harness_shadow_setups.argtypes = L.harness_shadow_cast.argtypes[:10] + [V]
     return L
+
+
+def cpu_shadow_cast(L, frame, size, shape, tf, brute=False):
+    """one cast of the CPU build into a cleared map: dict of map [size][size] uint32, skipped, culled, lane, wave, drawn.  brute:
+    harness_shadow_cover_all, every centre of the map instead of the set-up's box and whatever the depths, and `cover` and `setups` per
+    (instance, triangle) pair; brute="setups": the set-ups alone"""
+    v = np.ascontiguousarray(shape[0], np.float32).reshape(-1, 3)
+    t = np.ascontiguousarray(shape[1], np.int32).reshape(-1, 3)
+    tf = np.ascontiguousarray(tf, np.float32).reshape(-1, 12)
+    fr = W.shadow_frame(frame)
+    words, counters = np.zeros((size, size), np.uint32), np.zeros(4, np.uint32)
+    L.harness_shadow_clear(size, words.ctypes.data, counters.ctypes.data)
+    inputs = (C.addressof(fr), size, v.ctypes.data, len(v), t.ctypes.data, len(t), tf.ctypes.data if tf.size else None, 12, None, len(tf))
+    extra = {}
+    if brute:
+        extra = dict(cover=np.zeros(len(tf) * len(t), COVER), setups=np.zeros(len(tf) * len(t), SETUP))
+        L.harness_shadow_setups(*inputs, extra["setups"].ctypes.data)
+        if brute == "setups":
+            return extra
+        L.harness_shadow_cover_all(*inputs, words.ctypes.data, counters.ctypes.data, None, extra["cover"].ctypes.data)
+    else:
+        L.harness_shadow_cast(*inputs, words.ctypes.data, counters.ctypes.data, None)
+    s, c, ln, wv = (int(x) for x in counters)
+    return dict(map=words, skipped=s, culled=c, lane=ln, wave=wv, drawn=ln + wv, **extra)
 
 
 def build_c_consumer(tmp_path):

@@ -52,6 +52,64 @@ ow::SurfaceScales scales_of(const float *map_scales, int cascades) {
     return sc;
 }
 
+// The draw in its two forms.  brute: the box is ignored (harness_mesh_cover_all below).  setups_out: five integers a triangle; cover_out:
+// two (brute only).
+void mesh_draw(const uint16_t *disp, const uint16_t *norm, int n, int cascades, const float *map_scales, const float *local, int num_vertices,
+               const int32_t *indices, int num_triangles, const float *origin, const float *camera, int width, int height, const float *shade, int falloff,
+               float cx, float cz, float near, int cull_back, int lane_box, ow::MeshVertex *vertices_out, uint64_t *vis_out, uint32_t *rgba,
+               ow::RenderPixel *pixels, uint32_t *counters, bool brute, int32_t *setups_out, int32_t *cover_out) {
+    static_assert(sizeof(ow::ShadeParams) == 22 * sizeof(float), "ShadeParams is 22 floats");
+    const ow::SurfaceScales sc = scales_of(map_scales, cascades);
+    const ow::CameraParams cam = camera_of(camera, width, height);
+    const ow::MeshParams mp = params_of(falloff, cx, cz, near, cull_back, lane_box, cam, true);
+    ow::ShadeParams sp;
+    memcpy(&sp, shade, sizeof(sp));
+    const ow::u16x4 *d = (const ow::u16x4 *)disp;
+    std::vector<ow::MeshVertex> verts((size_t)num_vertices);
+    for (int i = 0; i < num_vertices; ++i) verts[i] = ow::mesh_vertex(d, n, cascades, sc, mp, cam, true, local + 3 * (size_t)i, origin);
+    std::vector<uint64_t> vis((size_t)width * height, ow::kMeshNoTriangle);
+    uint32_t count[4] = {0, 0, 0, 0};
+    for (int t = 0; t < num_triangles; ++t) {
+        const ow::TriSetup s = ow::tri_setup(verts[indices[3 * (size_t)t]], verts[indices[3 * (size_t)t + 1]], verts[indices[3 * (size_t)t + 2]], cam, mp);
+        ++count[s.kind];
+        if (setups_out) {
+            const int32_t five[5] = {s.kind, s.x0, s.x1, s.y0, s.y1};
+            memcpy(setups_out + 5 * (size_t)t, five, sizeof(five));
+        }
+        const bool boxed = s.kind == ow::kTriLane || s.kind == ow::kTriWave;
+        int x0 = s.x0, x1 = s.x1, y0 = s.y0, y1 = s.y1;
+        if (brute) {  // what tri_setup culls before it looks at the box: flags, a camera that is not finite (both leave det 0), det, facing
+            if (s.kind == ow::kTriSkipped || !(s.p.det != 0.0f) || (mp.cull_back && s.p.det > 0.0f)) continue;
+            x0 = y0 = 0, x1 = width - 1, y1 = height - 1;
+        } else if (!boxed) {
+            continue;
+        }
+        int32_t covered = 0, outside = 0;
+        for (int j = y0; j <= y1; ++j)
+            for (int i = x0; i <= x1; ++i) {
+                const ow::TriCover c = ow::tri_cover(s.p, cam, mp.near, i, j);
+                if (!c.hit) continue;
+                ++covered;
+                outside += !(boxed && i >= s.x0 && i <= s.x1 && j >= s.y0 && j <= s.y1);
+                const uint64_t w = ow::mesh_word(c.depth, t);
+                uint64_t &at = vis[(size_t)j * width + i];
+                if (w < at) at = w;
+            }
+        if (cover_out) cover_out[2 * (size_t)t] = covered, cover_out[2 * (size_t)t + 1] = outside;
+    }
+    for (int j = 0; j < height && (rgba || pixels); ++j)
+        for (int i = 0; i < width; ++i) {
+            const size_t at = (size_t)j * width + i;
+            uint32_t word;
+            const ow::RenderPixel px = ow::mesh_pixel(d, (const ow::u16x4 *)norm, n, cascades, sc, cam, sp, mp, vis[at], indices, verts.data(), i, j, &word);
+            if (rgba) rgba[at] = word;
+            if (pixels) pixels[at] = px;
+        }
+    if (vertices_out) memcpy(vertices_out, verts.data(), verts.size() * sizeof(ow::MeshVertex));
+    if (vis_out) memcpy(vis_out, vis.data(), vis.size() * sizeof(uint64_t));
+    if (counters) memcpy(counters, count, sizeof(count));
+}
+
 }  // namespace
 
 extern "C" {
@@ -83,41 +141,29 @@ void harness_mesh_draw(const uint16_t *disp, const uint16_t *norm, int n, int ca
                        const int32_t *indices, int num_triangles, const float *origin, const float *camera, int width, int height, const float *shade,
                        int falloff, float cx, float cz, float near, int cull_back, int lane_box, ow::MeshVertex *vertices_out, uint64_t *vis_out,
                        uint32_t *rgba, ow::RenderPixel *pixels, uint32_t *counters) {
-    static_assert(sizeof(ow::ShadeParams) == 22 * sizeof(float), "ShadeParams is 22 floats");
-    const ow::SurfaceScales sc = scales_of(map_scales, cascades);
-    const ow::CameraParams cam = camera_of(camera, width, height);
-    const ow::MeshParams mp = params_of(falloff, cx, cz, near, cull_back, lane_box, cam, true);
-    ow::ShadeParams sp;
-    memcpy(&sp, shade, sizeof(sp));
-    const ow::u16x4 *d = (const ow::u16x4 *)disp;
-    std::vector<ow::MeshVertex> verts((size_t)num_vertices);
-    for (int i = 0; i < num_vertices; ++i) verts[i] = ow::mesh_vertex(d, n, cascades, sc, mp, cam, true, local + 3 * (size_t)i, origin);
-    std::vector<uint64_t> vis((size_t)width * height, ow::kMeshNoTriangle);
-    uint32_t count[4] = {0, 0, 0, 0};
-    for (int t = 0; t < num_triangles; ++t) {
-        const ow::TriSetup s = ow::tri_setup(verts[indices[3 * (size_t)t]], verts[indices[3 * (size_t)t + 1]], verts[indices[3 * (size_t)t + 2]], cam, mp);
-        ++count[s.kind];
-        if (s.kind != ow::kTriLane && s.kind != ow::kTriWave) continue;
-        for (int j = s.y0; j <= s.y1; ++j)
-            for (int i = s.x0; i <= s.x1; ++i) {
-                const ow::TriCover c = ow::tri_cover(s.p, cam, mp.near, i, j);
-                if (!c.hit) continue;
-                const uint64_t w = ow::mesh_word(c.depth, t);
-                uint64_t &at = vis[(size_t)j * width + i];
-                if (w < at) at = w;
-            }
-    }
-    for (int j = 0; j < height; ++j)
-        for (int i = 0; i < width; ++i) {
-            const size_t at = (size_t)j * width + i;
-            uint32_t word;
-            const ow::RenderPixel px = ow::mesh_pixel(d, (const ow::u16x4 *)norm, n, cascades, sc, cam, sp, mp, vis[at], indices, verts.data(), i, j, &word);
-            if (rgba) rgba[at] = word;
-            if (pixels) pixels[at] = px;
-        }
-    if (vertices_out) memcpy(vertices_out, verts.data(), verts.size() * sizeof(ow::MeshVertex));
-    if (vis_out) memcpy(vis_out, vis.data(), vis.size() * sizeof(uint64_t));
-    if (counters) memcpy(counters, count, sizeof(count));
+    mesh_draw(disp, norm, n, cascades, map_scales, local, num_vertices, indices, num_triangles, origin, camera, width, height, shade, falloff, cx, cz, near,
+              cull_back, lane_box, vertices_out, vis_out, rgba, pixels, counters, false, NULL, NULL);
+}
+
+// The same draw without the walk's box: every triangle that its vertices' flags, det == 0 and the facing do not cull is tested with
+// tri_cover at every centre of the picture, whatever tri_setup made of its box (!any, all_far and an empty box included), and the words
+// are combined with the same min.  The reference tests/test_raster_edges.py holds the boxed draw and the device to.  The counters are the
+// set-ups' classes, as the draw counts them.  cover_out (may be NULL): per triangle, the centres it covers and how many of them lie
+// outside its set-up's box (a class that is not drawn has no box).
+void harness_mesh_cover_all(const uint16_t *disp, const uint16_t *norm, int n, int cascades, const float *map_scales, const float *local, int num_vertices,
+                            const int32_t *indices, int num_triangles, const float *origin, const float *camera, int width, int height,
+                            const float *shade, int falloff, float cx, float cz, float near, int cull_back, int lane_box, ow::MeshVertex *vertices_out,
+                            uint64_t *vis_out, uint32_t *rgba, ow::RenderPixel *pixels, uint32_t *counters, int32_t *cover_out) {
+    mesh_draw(disp, norm, n, cascades, map_scales, local, num_vertices, indices, num_triangles, origin, camera, width, height, shade, falloff, cx, cz, near,
+              cull_back, lane_box, vertices_out, vis_out, rgba, pixels, counters, true, NULL, cover_out);
+}
+
+// every triangle's set-up as the draw makes it: kind, x0, x1, y0, y1
+void harness_mesh_setups(const uint16_t *disp, const uint16_t *norm, int n, int cascades, const float *map_scales, const float *local, int num_vertices,
+                         const int32_t *indices, int num_triangles, const float *origin, const float *camera, int width, int height, const float *shade,
+                         int falloff, float cx, float cz, float near, int cull_back, int lane_box, int32_t *setups_out) {
+    mesh_draw(disp, norm, n, cascades, map_scales, local, num_vertices, indices, num_triangles, origin, camera, width, height, shade, falloff, cx, cz, near,
+              cull_back, lane_box, NULL, NULL, NULL, NULL, NULL, false, setups_out, NULL);
 }
 
 }  // extern "C"
@@ -341,6 +387,43 @@ int main() {
         bool all_invalid = p.hits == 0;
         for (const ow::RenderPixel &r : p.px) all_invalid = all_invalid && r.status == ow::kRayInvalid;
         EXPECT(all_invalid, "a camera that is not finite");
+    }
+    {   // one soup through both forms: a camera at the origin with the identity basis over zero maps, so a local position is a view
+        // position; triangles in front at any size, across the near plane and around the camera; the boxed draw is the brute one
+        const std::vector<float> eye = {0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0, 1, 1.0f, 37.0f / 21.0f, 200.0f};
+        Mesh soup;
+        uint32_t lcg = 20261021u;
+        auto next = [&lcg]() { return (float)((lcg = lcg * 1664525u + 1013904223u) >> 8) / 16777216.0f; };
+        for (int t = 0; t < 600; ++t) {
+            const float z = t % 3 == 0 ? 0.0f : -(0.06f + 40.0f * next() * next()), spread = t % 3 == 2 ? 0.1f : 3.0f * (0.05f - z) * next();
+            const float c[3] = {(2.0f * next() - 1.0f) * (1.0f - z), (2.0f * next() - 1.0f) * (1.0f - z), z};
+            for (int k = 0; k < 3; ++k) {
+                for (int a = 0; a < 3; ++a) soup.v.push_back(c[a] + (2.0f * next() - 1.0f) * (t % 3 == 0 ? 2.0f : spread));
+                soup.t.push_back(3 * t + k);
+            }
+        }
+        const float origin[3] = {0.0f, 0.0f, 0.0f};
+        const int nt = (int)(soup.t.size() / 3), nv = (int)(soup.v.size() / 3);
+        for (int lane_box : {0, -1, 1, 64}) {
+            std::vector<uint64_t> boxed(37 * 21), brute(37 * 21);
+            std::vector<int32_t> setups(5 * (size_t)nt), cover(2 * (size_t)nt, 0);
+            uint32_t cb[4], ca[4];
+            harness_mesh_draw(calm.disp.data(), calm.norm.data(), calm.n, calm.cascades, calm.scales.data(), soup.v.data(), nv, soup.t.data(), nt, origin,
+                              eye.data(), 37, 21, kShade, 0, 0.0f, 0.0f, 0.0f, 0, lane_box, NULL, boxed.data(), NULL, NULL, cb);
+            harness_mesh_cover_all(calm.disp.data(), calm.norm.data(), calm.n, calm.cascades, calm.scales.data(), soup.v.data(), nv, soup.t.data(), nt, origin,
+                                   eye.data(), 37, 21, kShade, 0, 0.0f, 0.0f, 0.0f, 0, lane_box, NULL, brute.data(), NULL, NULL, ca, cover.data());
+            harness_mesh_setups(calm.disp.data(), calm.norm.data(), calm.n, calm.cascades, calm.scales.data(), soup.v.data(), nv, soup.t.data(), nt, origin,
+                                eye.data(), 37, 21, kShade, 0, 0.0f, 0.0f, 0.0f, 0, lane_box, setups.data());
+            EXPECT(boxed == brute && memcmp(cb, ca, sizeof(cb)) == 0, "a soup: boxed and brute");
+            int outside = 0, covered = 0, drawn = 0;
+            for (int t = 0; t < nt; ++t) {
+                covered += cover[2 * (size_t)t];
+                outside += cover[2 * (size_t)t + 1];
+                drawn += setups[5 * (size_t)t] >= 2;
+            }
+            EXPECT(outside == 0 && covered > 0 && drawn == (int)(cb[2] + cb[3]), "a soup: no covered centre outside a box");
+            printf("%-44s lane_box %2d  covered %d  lane %u wave %u\n", "a soup, boxed and brute", lane_box, covered, cb[2], cb[3]);
+        }
     }
     printf("%s (%d failures)\n", g_failures ? "FAILED" : "ok", g_failures);
     return g_failures ? 1 : 0;

@@ -60,32 +60,80 @@ void harness_shadow_clear(int size, uint32_t *map, uint32_t *counters) {
     for (int k = 0; k < 4; ++k) counters[k] = 0u;
 }
 
-// one cast into a map and its counters (both accumulate, as the device's do between two begins).  flags may be null.  verts_out (may be
-// null): count x num_vertices records.
-void harness_shadow_cast(const ShadowFrame *f, int size, const float *local, int num_vertices, const int32_t *indices, int num_triangles,
-                         const float *transforms, int stride, const int32_t *flags, int count, uint32_t *map, uint32_t *counters, ShadowVertex *verts_out) {
+}  // extern "C"
+
+namespace {
+// The cast in its two forms.  brute: the box and the depth cull are ignored (harness_shadow_cover_all below).  setups_out: five integers a
+// pair; cover_out: two (brute only).
+void shadow_cast(const ShadowFrame *f, int size, const float *local, int num_vertices, const int32_t *indices, int num_triangles, const float *transforms,
+                 int stride, const int32_t *flags, int count, uint32_t *map, uint32_t *counters, ShadowVertex *verts_out, bool brute, int32_t *setups_out,
+                 int32_t *cover_out) {
     const ShadowParams P = shadow_params(*f, size);
     if (!P.ok || count <= 0) return;
     std::vector<ShadowVertex> verts((size_t)count * num_vertices);
     const SolidInstances in = {transforms, flags, stride, count};
     for (int i = 0; i < count; ++i) {
         const bool ok = solid_instance_ok(in, i);
-        if (!ok) ++counters[kShadowSkippedInstances];
+        if (!ok && counters) ++counters[kShadowSkippedInstances];
         for (int v = 0; v < num_vertices; ++v) verts[(size_t)i * num_vertices + v] = shadow_vertex(solid_transform(in, i), ok, local + 3 * (size_t)v, P);
     }
     if (verts_out) memcpy(verts_out, verts.data(), verts.size() * sizeof(ShadowVertex));
     for (int pair = 0; pair < count * num_triangles; ++pair) {
         const SolidTriangle<ShadowVertex> t = solid_triangle(indices, num_vertices, num_triangles, verts.data(), pair);
         const ShadowSetup S = shadow_setup(*t.a, *t.b, *t.c, P);
-        if (S.kind >= kShadowTriCulled) ++counters[S.kind];
-        if (S.kind != kShadowTriLane && S.kind != kShadowTriWave) continue;
-        for (int j = S.y0; j <= S.y1; ++j)
-            for (int x = S.x0; x <= S.x1; ++x) {
+        if (S.kind >= kShadowTriCulled && counters) ++counters[S.kind];
+        if (setups_out) {
+            const int32_t five[5] = {S.kind, S.x0, S.x1, S.y0, S.y1};
+            memcpy(setups_out + 5 * (size_t)pair, five, sizeof(five));
+        }
+        const bool boxed = S.kind == kShadowTriLane || S.kind == kShadowTriWave;
+        int x0 = S.x0, x1 = S.x1, y0 = S.y0, y1 = S.y1;
+        if (brute) {  // what is culled before the box and the depths are looked at: the vertices' flags and the facing
+            const double A = shadow_area(S.s, S.t);
+            if ((t.a->flags | t.b->flags | t.c->flags) || !(P.both_sides ? A != 0.0 : A < 0.0)) continue;
+            x0 = y0 = 0, x1 = y1 = size - 1;
+        } else if (!boxed) {
+            continue;
+        }
+        if (!map) continue;
+        int32_t covered = 0, outside = 0;
+        for (int j = y0; j <= y1; ++j)
+            for (int x = x0; x <= x1; ++x) {
                 const ShadowCover c = shadow_cover(S.s, S.t, S.d, P.max_depth, x, j);
+                if (!c.hit) continue;
+                ++covered;
+                outside += !(boxed && x >= S.x0 && x <= S.x1 && j >= S.y0 && j <= S.y1);
                 uint32_t &word = map[(size_t)j * size + x];
-                if (c.hit && c.bits < word) word = c.bits;
+                if (c.bits < word) word = c.bits;
             }
+        if (cover_out) cover_out[2 * (size_t)pair] = covered, cover_out[2 * (size_t)pair + 1] = outside;
     }
+}
+}  // namespace
+
+extern "C" {
+
+// one cast into a map and its counters (both accumulate, as the device's do between two begins).  flags may be null.  verts_out (may be
+// null): count x num_vertices records.
+void harness_shadow_cast(const ShadowFrame *f, int size, const float *local, int num_vertices, const int32_t *indices, int num_triangles,
+                         const float *transforms, int stride, const int32_t *flags, int count, uint32_t *map, uint32_t *counters, ShadowVertex *verts_out) {
+    shadow_cast(f, size, local, num_vertices, indices, num_triangles, transforms, stride, flags, count, map, counters, verts_out, false, nullptr, nullptr);
+}
+
+// The same cast without the walk's box: every pair that its vertices' flags and the facing do not cull is tested with shadow_cover at
+// every centre of the map, whatever shadow_setup made of its box and of its depths, and the words are combined with the same minimum: the
+// reference tests/test_raster_edges.py holds the boxed cast and the device to.  The counters are the set-ups' classes.  cover_out (may be
+// null): per pair, the centres it covers and how many of them lie outside its set-up's box (a class that is not cast has no box).
+void harness_shadow_cover_all(const ShadowFrame *f, int size, const float *local, int num_vertices, const int32_t *indices, int num_triangles,
+                              const float *transforms, int stride, const int32_t *flags, int count, uint32_t *map, uint32_t *counters,
+                              ShadowVertex *verts_out, int32_t *cover_out) {
+    shadow_cast(f, size, local, num_vertices, indices, num_triangles, transforms, stride, flags, count, map, counters, verts_out, true, nullptr, cover_out);
+}
+
+// every pair's set-up as the cast makes it: kind, x0, x1, y0, y1
+void harness_shadow_setups(const ShadowFrame *f, int size, const float *local, int num_vertices, const int32_t *indices, int num_triangles,
+                           const float *transforms, int stride, const int32_t *flags, int count, int32_t *setups_out) {
+    shadow_cast(f, size, local, num_vertices, indices, num_triangles, transforms, stride, flags, count, nullptr, nullptr, nullptr, false, setups_out, nullptr);
 }
 
 // the pass over width x height records, in place; V_out (may be null): the visibility of every record (1 for what is no receiver);
@@ -151,6 +199,26 @@ int main(int argc, char **argv) {
             fprintf(stderr, "bad index\n");
             return 2;
         }
+    {   // both forms first: the boxed map is the brute one, and no pair covers a centre outside its box
+        const int pairs = h.count * h.num_triangles;
+        std::vector<uint32_t> ma(texels), mb(texels), ca(4), cb(4);
+        std::vector<int32_t> setups(5 * (size_t)pairs, 0), cover(2 * (size_t)pairs, 0);
+        harness_shadow_clear(h.size, ma.data(), ca.data());
+        harness_shadow_clear(h.size, mb.data(), cb.data());
+        const int32_t *fl = h.has_flags ? flags.data() : nullptr;
+        harness_shadow_cast(&h.frame, h.size, local.data(), h.num_vertices, indices.data(), h.num_triangles, transforms.data(), h.stride, fl, h.count, ma.data(),
+                            ca.data(), nullptr);
+        harness_shadow_cover_all(&h.frame, h.size, local.data(), h.num_vertices, indices.data(), h.num_triangles, transforms.data(), h.stride, fl, h.count,
+                                 mb.data(), cb.data(), nullptr, cover.data());
+        harness_shadow_setups(&h.frame, h.size, local.data(), h.num_vertices, indices.data(), h.num_triangles, transforms.data(), h.stride, fl, h.count,
+                              setups.data());
+        int outside = 0, drawn = 0;
+        for (int p = 0; p < pairs; ++p) outside += cover[2 * (size_t)p + 1], drawn += setups[5 * (size_t)p] >= kShadowTriLane;
+        if (ma != mb || ca != cb || outside != 0 || drawn != (int)(ca[2] + ca[3])) {
+            fprintf(stderr, "the boxed cast is not the brute one (%d covered centres outside a box)\n", outside);
+            return 1;
+        }
+    }
     harness_shadow_clear(h.size, map.data(), counters.data());
     for (int k = 0; k < h.casts; ++k) {
         const int a = (int)((int64_t)h.count * k / h.casts), b = (int)((int64_t)h.count * (k + 1) / h.casts);

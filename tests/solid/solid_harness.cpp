@@ -84,12 +84,11 @@ SolidParams params_of(const SolidCase &h, const CameraParams &cam) {
 }
 }  // namespace
 
-extern "C" {
-
-// The draw.  pixels_inout: width x height records or null (background_color, no depth); rgba_out: width x height words or null; counters:
-// skipped instances, culled, per-lane and per-wave triangles; vis_out: width x height words or null.
-void harness_solid_draw(const SolidCase *hp, const float *local, const int32_t *indices, const float *transforms, const int32_t *flags,
-                        void *pixels_inout, void *rgba_out, uint32_t *counters, uint64_t *vis_out) {
+// The draw in its two forms.  brute: the box is ignored (harness_solid_cover_all below).  setups_out: five integers a pair; cover_out: two
+// (brute only).
+namespace {
+void solid_draw(const SolidCase *hp, const float *local, const int32_t *indices, const float *transforms, const int32_t *flags, void *pixels_inout,
+                void *rgba_out, uint32_t *counters, uint64_t *vis_out, bool brute, int32_t *setups_out, int32_t *cover_out) {
     const SolidCase &h = *hp;
     const CameraParams cam = camera_of(h);
     const SolidParams sp = params_of(h, cam);
@@ -115,19 +114,34 @@ void harness_solid_draw(const SolidCase *hp, const float *local, const int32_t *
             int counter = -1;
             const TriSetup s = solid_setup(solid_triangle(indices, nv, nt, verts.data(), pair), cam, sp.mp, counter);
             if (counter >= 0) ++cnt[counter];
-            if (s.kind != kTriLane && s.kind != kTriWave) continue;
-            for (int j = s.y0; j <= s.y1; ++j)
-                for (int i = s.x0; i <= s.x1; ++i) {
+            if (setups_out) {
+                const int32_t five[5] = {s.kind, s.x0, s.x1, s.y0, s.y1};
+                memcpy(setups_out + 5 * (size_t)pair, five, sizeof(five));
+            }
+            const bool boxed = s.kind == kTriLane || s.kind == kTriWave;
+            int x0 = s.x0, x1 = s.x1, y0 = s.y0, y1 = s.y1;
+            if (brute) {  // what is culled before the box is looked at: flags (they leave det 0), det, facing, planes that are not finite
+                if (s.kind == kTriSkipped || !(s.p.det != 0.0f) || (sp.mp.cull_back && s.p.det > 0.0f) || !solid_planes_finite(s.p)) continue;
+                x0 = y0 = 0, x1 = h.width - 1, y1 = h.height - 1;
+            } else if (!boxed) {
+                continue;
+            }
+            int32_t covered = 0, outside = 0;
+            for (int j = y0; j <= y1; ++j)
+                for (int i = x0; i <= x1; ++i) {
                     const TriCover c = tri_cover(s.p, cam, sp.mp.near, i, j);
                     if (!c.hit) continue;
+                    ++covered;
+                    outside += !(boxed && i >= s.x0 && i <= s.x1 && j >= s.y0 && j <= s.y1);
                     const uint64_t word = mesh_word(c.depth, pair);
                     uint64_t &at = vis[(size_t)j * h.width + i];
                     if (word < at) at = word;
                 }
+            if (cover_out) cover_out[2 * (size_t)pair] = covered, cover_out[2 * (size_t)pair + 1] = outside;
         }
     }
     // k_solid_resolve
-    for (int j = 0; j < h.height; ++j)
+    for (int j = 0; j < h.height && (rgba || pixels); ++j)
         for (int i = 0; i < h.width; ++i) {
             const size_t at = (size_t)j * h.width + i;
             float t = 0.0f, color[3] = {sp.background[0], sp.background[1], sp.background[2]};
@@ -147,6 +161,33 @@ void harness_solid_draw(const SolidCase *hp, const float *local, const int32_t *
         }
     if (counters) memcpy(counters, cnt, sizeof(cnt));
     if (vis_out) memcpy(vis_out, vis.data(), pixels_n * sizeof(uint64_t));
+}
+}  // namespace
+
+extern "C" {
+
+// The draw.  pixels_inout: width x height records or null (background_color, no depth); rgba_out: width x height words or null; counters:
+// skipped instances, culled, per-lane and per-wave triangles; vis_out: width x height words or null.
+void harness_solid_draw(const SolidCase *hp, const float *local, const int32_t *indices, const float *transforms, const int32_t *flags,
+                        void *pixels_inout, void *rgba_out, uint32_t *counters, uint64_t *vis_out) {
+    solid_draw(hp, local, indices, transforms, flags, pixels_inout, rgba_out, counters, vis_out, false, nullptr, nullptr);
+}
+
+// The same draw without the walk's box: every pair that its vertices' flags, det == 0, the facing and the planes rule do not cull is tested
+// with tri_cover at every centre of the picture, whatever tri_setup made of its box, and the words are combined with the same min: the
+// reference tests/test_raster_edges.py holds the boxed draw and the device to.  The counters are the set-ups' classes.  cover_out (may be
+// null): per pair, the centres it covers and how many of them lie outside its set-up's box (a class that is not drawn has no box).
+void harness_solid_cover_all(const SolidCase *hp, const float *local, const int32_t *indices, const float *transforms, const int32_t *flags,
+                             void *pixels_inout, void *rgba_out, uint32_t *counters, uint64_t *vis_out, int32_t *cover_out) {
+    solid_draw(hp, local, indices, transforms, flags, pixels_inout, rgba_out, counters, vis_out, true, nullptr, cover_out);
+}
+
+// every pair's set-up as the draw makes it: kind, x0, x1, y0, y1
+void harness_solid_setups(const SolidCase *hp, const float *local, const int32_t *indices, const float *transforms, const int32_t *flags,
+                          int32_t *setups_out) {
+    SolidCase h = *hp;
+    h.has_pixels = 0;
+    solid_draw(&h, local, indices, transforms, flags, nullptr, nullptr, nullptr, nullptr, false, setups_out, nullptr);
 }
 
 }  // extern "C"
@@ -191,6 +232,26 @@ int main(int argc, char **argv) {
             return 2;
         }
     uint32_t counters[4] = {0, 0, 0, 0};
+    // both forms on copies of the records first: the boxed picture is the brute one, and no pair covers a centre outside its box
+    {
+        const int pairs = h.count * h.num_triangles;
+        std::vector<RenderPixel> pa(pixels), pb(pixels);
+        std::vector<uint32_t> ra(count), rb(count);
+        std::vector<uint64_t> va(count), vb(count);
+        std::vector<int32_t> setups(5 * (size_t)pairs), cover(2 * (size_t)pairs, 0);
+        uint32_t ca[4] = {0, 0, 0, 0}, cb[4] = {0, 0, 0, 0};
+        harness_solid_draw(&h, local.data(), indices.data(), transforms.data(), flags.data(), pa.data(), ra.data(), ca, va.data());
+        harness_solid_cover_all(&h, local.data(), indices.data(), transforms.data(), flags.data(), pb.data(), rb.data(), cb, vb.data(), cover.data());
+        harness_solid_setups(&h, local.data(), indices.data(), transforms.data(), flags.data(), setups.data());
+        int outside = 0, drawn = 0;
+        for (int p = 0; p < pairs; ++p) outside += cover[2 * (size_t)p + 1], drawn += setups[5 * (size_t)p] >= kTriLane;
+        const bool camera_ok = mesh_camera_ok(camera_of(h)) && h.count > 0;
+        if (va != vb || ra != rb || memcmp(ca, cb, sizeof(ca)) != 0 || outside != 0 || (camera_ok && drawn != (int)(ca[2] + ca[3])) ||
+            (!pa.empty() && memcmp(pa.data(), pb.data(), pa.size() * sizeof(RenderPixel)) != 0)) {
+            fprintf(stderr, "the boxed draw is not the brute one (%d covered centres outside a box)\n", outside);
+            return 1;
+        }
+    }
     harness_solid_draw(&h, local.data(), indices.data(), transforms.data(), flags.data(), pixels.data(), rgba.data(), counters, nullptr);
     int bad = 0, solid = 0;
     for (const RenderPixel &p : pixels) {
