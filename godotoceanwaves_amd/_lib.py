@@ -38,6 +38,8 @@ OW_SHADOW_CAST_BOTH_SIDES, OW_SHADOW_RECEIVE_WATER = 1, 1
 OW_SHADOW_MIN_SIZE, OW_SHADOW_MAX_SIZE = 8, 8192
 OW_RAY_MIST = 256
 OW_MIST_MAX_SLICES = 256
+OW_RAY_MIRROR = 512
+OW_MIRROR_TWO_SIDED = 1
 OW_SKY_MAX_SIDE = 8192
 OW_PRESENT_MAX_DOWNSAMPLE = 4
 OW_FOG_EXPONENTIAL, OW_FOG_DEPTH = 0, 1
@@ -302,6 +304,13 @@ class ow_mist_options(C.Structure):
                 ("sun_color", C.c_float * 3), ("sun_direction", C.c_float * 3), ("ambient_color", C.c_float * 3), ("reserved", C.c_uint32 * 11)]
 
 
+class ow_mirror_options(C.Structure):
+    """struct ow_mirror_options (128 bytes); a NULL pointer = ow_mirror_options_init's values (the sky pass's and the solid draw's defaults)"""
+    _fields_ = [("ambient_energy", C.c_float), ("reflection_energy", C.c_float), ("specular", C.c_float), ("body_color", C.c_float * 3),
+                ("light_direction", C.c_float * 3), ("light_color", C.c_float * 3), ("ambient_color", C.c_float * 3), ("max_distance", C.c_float),
+                ("fade_begin", C.c_float), ("opacity", C.c_float), ("flags", C.c_uint32), ("cull", C.c_int32), ("reserved", C.c_uint32 * 12)]
+
+
 class ow_mesh_vertex(C.Structure):
     """struct ow_mesh_vertex (48 bytes): the vertex stage's record of a mesh draw"""
     _fields_ = [("position", C.c_float * 3), ("wave_height", C.c_float), ("uv", C.c_float * 2), ("distance_factor", C.c_float),
@@ -442,6 +451,14 @@ SIGNATURES = {
     "ow_mist_apply": (C.c_int, [C.c_void_p, C.c_void_p, _P(ow_camera), _P(ow_mist_options), C.c_void_p, C.c_void_p]),
     "ow_mist_apply_async": (C.c_int, [C.c_void_p, C.c_void_p, _P(ow_camera), _P(ow_mist_options), C.c_void_p, C.c_void_p]),
     "ow_mist_stats": (C.c_int, [C.c_void_p, _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64)]),
+    "ow_mirror_options_init": (None, [_P(ow_mirror_options)]),
+    "ow_mirror_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, _P(ow_camera), _P(ow_mirror_options), C.c_void_p,
+                                  C.c_void_p]),
+    "ow_mirror_apply_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, _P(ow_camera), _P(ow_mirror_options),
+                                        C.c_void_p, C.c_void_p]),
+    "ow_mirror_apply_instances": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, _P(ow_camera), _P(ow_mirror_options), C.c_void_p,
+                                            C.c_void_p]),
+    "ow_mirror_stats": (C.c_int, [C.c_void_p, _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64)]),
     "ow_get_maps_f32": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
     "ow_get_spectrum": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "ow_get_intermediate": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),

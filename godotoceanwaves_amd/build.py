@@ -26,6 +26,7 @@ UNITS = {
     "ow_solid_host.hip": [],
     "ow_sky_host.hip": [],
     "ow_mist_host.hip": [],
+    "ow_mirror_host.hip": [],
     "ow_consumer.hip": EXACT,
     "ow_group.hip": [],
     "ow_velocity.hip": [],
@@ -38,6 +39,7 @@ UNITS = {
     "ow_sky_light.hip": EXACT,
     "ow_shadow.hip": EXACT,
     "ow_mist.hip": EXACT,
+    "ow_mirror.hip": EXACT,
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-fno-fast-math", "-fvisibility=hidden", "-Wall", "-Wno-unused-function"]
 

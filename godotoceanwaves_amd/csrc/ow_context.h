@@ -219,7 +219,10 @@ struct ow_context {
     // outputs (the float4 pixels first, then the RGBA8 words).  Their asynchronous forms use no scratch.
     // mist: the copies of the three 64-bit counters of the last ow_mist_apply (ow_mist.h kMistCounterBytes), allocated by the first pass in either form;
     // the synchronous form uses render_pixels and render_rgba as well.
-    ow::DeviceScratch query_scratch, buoy_scratch, ray_scratch, render_rgba, render_pixels, mesh_vis, billboard, solid, solid_cast, mist;
+    // mirror: the counters of the last ow_mirror_apply and its instance spheres, the uploaded transforms (ow_mirror_apply_instances) and, in the
+    // synchronous forms, the hit records; those forms use render_pixels as well.
+    ow::DeviceScratch query_scratch, buoy_scratch, ray_scratch, render_rgba, render_pixels, mesh_vis, billboard, solid, solid_cast, mist, mirror;
+    uint64_t mirror_passes = 0;    // ow_mirror_stats
     uint64_t mist_passes = 0;      // ow_mist_stats
     uint64_t billboard_draws = 0;  // ow_billboard_draw_stats
     uint64_t solid_draws = 0;      // ow_solid_draw_stats

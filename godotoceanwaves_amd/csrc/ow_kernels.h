@@ -8,6 +8,7 @@
 #include "ow_environment.h"
 #include "ow_raycast.h"
 #include "ow_mesh.h"
+#include "ow_mirror.h"
 #include "ow_mist.h"
 #include "ow_render.h"
 #include "ow_rigid.h"
@@ -168,6 +169,26 @@ hipError_t launch_solid_cast_shape_bound(const SolidShape &shape, SolidCastBound
 // null) into out_dev, all on `s`
 hipError_t launch_solid_cast(const SolidCastArrays &A, const SolidInstances &in, const SolidCastParams &cp, const Ray *rays_dev, const RaycastHit *water_dev,
                              int count, SolidHit *out_dev, hipStream_t s);
+// k_solid_cast_bounds over in.count instances: their world spheres into bounds_dev, the skipped ones added to *skipped_dev, on `s` (the
+// mirror pass takes its spheres from here as well)
+hipError_t launch_solid_cast_bounds(const SolidInstances &in, const SolidCastBound *shape_bound, SolidCastBound *bounds_dev, uint32_t *skipped_dev, hipStream_t s);
+
+// the floating bodies' reflections (ow_mirror.hip; the arithmetic in ow_mirror.h).  The counters of a pass lie at the head of its scratch as
+// a ray cast's do: the skipped instances (one 32-bit word) at 0, then kMirrorSlots copies of the kMirrorCounters 64-bit sums, a line each.
+constexpr int kMirrorSlots = 32;
+constexpr int kMirrorSlotWords = 16;
+constexpr size_t kMirrorSumsOffset = 128;
+constexpr size_t kMirrorCounterBytes = kMirrorSumsOffset + (size_t)kMirrorSlots * kMirrorSlotWords * sizeof(uint64_t);
+struct MirrorArrays {
+    SolidShape shape;                   // zeros without a solid (no instances then)
+    const SolidCastBound *shape_bound;  // the shape's local sphere (launch_solid_cast_shape_bound wrote it)
+    void *counters;                     // [kMirrorCounterBytes] scratch: the counters of the last pass
+    SolidCastBound *bounds;             // [instances] scratch
+};
+// The clear of the counters, k_solid_cast_bounds over in.count instances, then k_mirror_apply over cam.width x cam.height records, rewritten
+// in place, and their hit records (hits_dev may be null), on `s`.
+hipError_t launch_mirror_apply(const MirrorArrays &A, const SolidInstances &in, const CameraParams &cam, const SkyLightParams &lp, const MirrorParams &mp,
+                               RenderPixel *pixels_dev, SolidHit *hits_dev, hipStream_t s);
 
 // the environment pass and the present (ow_environment.hip; the sky, the fog, the resolve, the tonemap and the transfer curve in ow_environment.h)
 // k_environment_apply over cam.width x cam.height records, rewritten in place, on `s`; nothing is launched for a camera that is not finite

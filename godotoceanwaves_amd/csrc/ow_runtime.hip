@@ -336,7 +336,7 @@ void ow_destroy(ow_context *c) {
     for (auto &e : c->copy_done)
         if (e) (void)hipEventDestroy(e);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
-    for (ow::DeviceScratch *s : {&c->query_scratch, &c->buoy_scratch, &c->ray_scratch, &c->render_rgba, &c->render_pixels, &c->mesh_vis, &c->billboard, &c->solid, &c->solid_cast, &c->mist}) s->release();
+    for (ow::DeviceScratch *s : {&c->query_scratch, &c->buoy_scratch, &c->ray_scratch, &c->render_rgba, &c->render_pixels, &c->mesh_vis, &c->billboard, &c->solid, &c->solid_cast, &c->mist, &c->mirror}) s->release();
     (void)hipFree(c->ray_bound);
     (void)hipFree(c->vel);
     (void)hipFree(c->vel_scratch);

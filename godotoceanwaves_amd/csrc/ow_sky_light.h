@@ -54,7 +54,8 @@
 //              spec = (radiance (env.x f0 + env.y f50)) reflection_energy, f0 = (0.16 specular) specular, f50 = clamp(50 f0, 0, 1).
 //     color    color + (ambient + spec) per channel; a channel whose result is not finite keeps its old value.
 //   The draws' flat ambient_color is still added by the draws: a caller of this pass sets it to 0.
-//   out of scope: screen-space reflections, reflection probes, the sky's light on spray (billboards are drawn after the pass).
+//   out of scope: screen-space reflections, reflection probes, the sky's light on spray (billboards are drawn after the pass).  (The floating
+//              bodies' image in the water is ow_mirror.h's pass, which does all of this one and takes its place in the frame order.)
 #pragma once
 
 #include <cmath>
@@ -299,9 +300,16 @@ struct SkyLightPixel {
     float env[2];
     float irradiance[3], ambient[3], spec[3];
 };
-OW_DEV SkyLightPixel sky_light_pixel(const SkyLightParams &lp, const CameraParams &cam, int i, int j, int32_t status, const float position[3],
-                                     const float albedo[3], const float normal[3], float roughness, const float color[3]) {
-    SkyLightPixel px;
+// The pass's work on one record, in two parts so that ow_mirror.h's pass can put a body's image into px.radiance between them; sky_light_pixel
+// below is the two in a row.  sky_light_begin runs up to radiance and env and says how far the record goes:
+enum : int {
+    kSkyLightLeft = 0,     // not processed: nothing is written
+    kSkyLightMarked = 1,   // processed, no contribution (the normal is zero or not finite)
+    kSkyLightAmbient = 2,  // ambient only (a solid, or water seen from below)
+    kSkyLightWater = 3     // water seen from above: reflect, lod, radiance and env are set, spec is sky_light_finish's
+};
+OW_DEV int sky_light_begin(const SkyLightParams &lp, const CameraParams &cam, int i, int j, int32_t status, const float position[3], const float albedo[3],
+                           const float normal[3], float roughness, const float color[3], SkyLightPixel &px) {
     px.changed = false;
     px.status = status;
     px.lod = 0.0f;
@@ -310,7 +318,7 @@ OW_DEV SkyLightPixel sky_light_pixel(const SkyLightParams &lp, const CameraParam
         px.color[k] = color[k];
         px.view[k] = px.reflect[k] = px.radiance[k] = px.irradiance[k] = px.ambient[k] = px.spec[k] = 0.0f;
     }
-    if (!lp.camera_ok || !(status & kRayHit) || (status & (kRayEnvironment | kRaySkyLit))) return px;
+    if (!lp.camera_ok || !(status & kRayHit) || (status & (kRayEnvironment | kRaySkyLit))) return kSkyLightLeft;
     px.changed = true;
     px.status = status | kRaySkyLit;
     bool ok = true, zero = true;
@@ -318,7 +326,7 @@ OW_DEV SkyLightPixel sky_light_pixel(const SkyLightParams &lp, const CameraParam
         ok = ok && mesh_finite(normal[k]);
         zero = zero && normal[k] == 0.0f;
     }
-    if (!ok || zero) return px;
+    if (!ok || zero) return kSkyLightMarked;
     float rel[3];
     for (int k = 0; k < 3; ++k) rel[k] = position[k] - cam.o[k];
     const float len = sqrtf(dot3(rel, rel));
@@ -331,23 +339,29 @@ OW_DEV SkyLightPixel sky_light_pixel(const SkyLightParams &lp, const CameraParam
     }
     radiance_tap(lp.E, normal, px.irradiance);
     for (int k = 0; k < 3; ++k) px.ambient[k] = (albedo[k] * px.irradiance[k]) * lp.ambient_energy;
-    if (!(status & (kRaySolid | kRayFromBelow))) {
-        const float nv = dot3(normal, px.view);
-        for (int k = 0; k < 3; ++k) px.reflect[k] = (2.0f * nv) * normal[k] - px.view[k];
-        const float rc = env_clamp01(roughness);
-        px.lod = rc * (float)(lp.levels - 1);
-        const float l0 = floorf(px.lod), frac = px.lod - l0;
-        const int i0 = (int)l0, i1 = i0 + 1 > lp.levels - 1 ? lp.levels - 1 : i0 + 1;
-        float r0[3], r1[3];
-        radiance_tap(lp.R[i0], px.reflect, r0);
-        radiance_tap(lp.R[i1], px.reflect, r1);
-        for (int k = 0; k < 3; ++k) px.radiance[k] = glsl_mix(r0[k], r1[k], frac);
-        const float rx = rc * -1.0f + 1.0f, ry = rc * -0.0275f + 0.0425f, rz = rc * -0.572f + 1.04f, rw = rc * 0.022f + -0.04f;
-        const float e = exp_f32((-9.28f * (nv > 0.0f ? nv : 0.0f)) * 0.693147182f);
-        const float rx2 = rx * rx;
-        const float a004 = (rx2 < e ? rx2 : e) * rx + ry;
-        px.env[0] = -1.04f * a004 + rz;
-        px.env[1] = 1.04f * a004 + rw;
+    if (status & (kRaySolid | kRayFromBelow)) return kSkyLightAmbient;
+    const float nv = dot3(normal, px.view);
+    for (int k = 0; k < 3; ++k) px.reflect[k] = (2.0f * nv) * normal[k] - px.view[k];
+    const float rc = env_clamp01(roughness);
+    px.lod = rc * (float)(lp.levels - 1);
+    const float l0 = floorf(px.lod), frac = px.lod - l0;
+    const int i0 = (int)l0, i1 = i0 + 1 > lp.levels - 1 ? lp.levels - 1 : i0 + 1;
+    float r0[3], r1[3];
+    radiance_tap(lp.R[i0], px.reflect, r0);
+    radiance_tap(lp.R[i1], px.reflect, r1);
+    for (int k = 0; k < 3; ++k) px.radiance[k] = glsl_mix(r0[k], r1[k], frac);
+    const float rx = rc * -1.0f + 1.0f, ry = rc * -0.0275f + 0.0425f, rz = rc * -0.572f + 1.04f, rw = rc * 0.022f + -0.04f;
+    const float e = exp_f32((-9.28f * (nv > 0.0f ? nv : 0.0f)) * 0.693147182f);
+    const float rx2 = rx * rx;
+    const float a004 = (rx2 < e ? rx2 : e) * rx + ry;
+    px.env[0] = -1.04f * a004 + rz;
+    px.env[1] = 1.04f * a004 + rw;
+    return kSkyLightWater;
+}
+// from `scale` on: spec from px.radiance and px.env (kSkyLightWater), then color
+OW_DEV void sky_light_finish(const SkyLightParams &lp, const float color[3], int stage, SkyLightPixel &px) {
+    if (stage < kSkyLightAmbient) return;
+    if (stage == kSkyLightWater) {
         const float scale = px.env[0] * lp.f0 + px.env[1] * lp.f50;
         for (int k = 0; k < 3; ++k) px.spec[k] = (px.radiance[k] * scale) * lp.reflection_energy;
     }
@@ -355,6 +369,12 @@ OW_DEV SkyLightPixel sky_light_pixel(const SkyLightParams &lp, const CameraParam
         const float v = color[k] + (px.ambient[k] + px.spec[k]);
         px.color[k] = mesh_finite(v) ? v : color[k];
     }
+}
+OW_DEV SkyLightPixel sky_light_pixel(const SkyLightParams &lp, const CameraParams &cam, int i, int j, int32_t status, const float position[3],
+                                     const float albedo[3], const float normal[3], float roughness, const float color[3]) {
+    SkyLightPixel px;
+    const int stage = sky_light_begin(lp, cam, i, j, status, position, albedo, normal, roughness, color, px);
+    sky_light_finish(lp, color, stage, px);
     return px;
 }
 

@@ -119,16 +119,19 @@ hipError_t launch_solid_cast_shape_bound(const SolidShape &shape, SolidCastBound
     return hipGetLastError();
 }
 
+hipError_t launch_solid_cast_bounds(const SolidInstances &in, const SolidCastBound *shape_bound, SolidCastBound *bounds_dev, uint32_t *skipped_dev, hipStream_t s) {
+    hipLaunchKernelGGL(k_solid_cast_bounds, dim3((unsigned)((in.count + 255) / 256)), dim3(256), 0, s, in, shape_bound, bounds_dev, skipped_dev);
+    return hipGetLastError();
+}
+
 hipError_t launch_solid_cast(const SolidCastArrays &A, const SolidInstances &in, const SolidCastParams &cp, const Ray *rays_dev, const RaycastHit *water_dev,
                              int count, SolidHit *out_dev, hipStream_t s) {
     static_assert(sizeof(SolidHit) == 64, "the record's four 16-byte vectors");
     if ((int64_t)in.count * A.shape.num_triangles > kSolidMaxProduct || in.count > kSolidMaxInstances) return hipErrorInvalidValue;  // the host wrappers refuse these first
     if (hipError_t e = hipMemsetAsync(A.counters, 0, kSolidCastCounterBytes, s); e != hipSuccess) return e;
     if (count <= 0) return hipSuccess;
-    if (in.count > 0) {
-        hipLaunchKernelGGL(k_solid_cast_bounds, dim3((unsigned)((in.count + 255) / 256)), dim3(256), 0, s, in, A.shape_bound, A.bounds, (uint32_t *)A.counters);
-        if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-    }
+    if (in.count > 0)
+        if (hipError_t e = launch_solid_cast_bounds(in, A.shape_bound, A.bounds, (uint32_t *)A.counters, s); e != hipSuccess) return e;
     const SolidCastShape shape{A.shape.local, A.shape.indices, A.shape.num_vertices, A.shape.num_triangles};
     hipLaunchKernelGGL(k_solid_cast, dim3((unsigned)count), dim3(64), 0, s, shape, in, A.bounds, cp, rays_dev, water_dev, count,
                        (unsigned long long *)((char *)A.counters + kSolidCastSumsOffset), out_dev);

@@ -1643,6 +1643,82 @@ ow_status ow_mist_apply_async(ow_context *ctx, ow_shadow_map *map_or_null, const
  * whose depth compare read the map (0 without a map) and the slices found shadowed.  Synchronises when one of the last three is asked for. */
 ow_status ow_mist_stats(ow_context *ctx, uint64_t *passes, uint64_t *pixels, uint64_t *slices_fetched, uint64_t *slices_shadowed);
 
+/* The floating bodies reflected in the water.  ow_radiance_light_apply reflects the sky, and only the sky, in every water pixel: a crate
+ * just above a mirror-like swell leaves no image in it.  ow_mirror_apply does everything that pass does and, where a water pixel's mirror
+ * ray meets a body at its resident pose, reads that body's lit colour instead of the sky pyramid.  It takes the sky pass's place:
+ *     water -> solids -> ow_shadow_apply -> ow_mirror_apply -> ow_environment_apply -> ow_mist_apply -> billboards -> ow_present
+ * Everything below is THIS LIBRARY'S CHOICE; godotoceanwaves_amd/csrc/ow_mirror.h (the exact operations, identical in every build) is
+ * the authority.
+ *   records    ow_radiance_light_apply's conditions exactly: a record with OW_RAY_HIT and with neither OW_RAY_ENVIRONMENT nor
+ *              OW_RAY_SKY_LIT is processed and gets OW_RAY_SKY_LIT; only color and status change; a camera that is not finite changes
+ *              nothing; applying the pass twice equals applying it once; applying it after ow_radiance_light_apply does nothing.  Where
+ *              no body is met the record is ow_radiance_light_apply's bit for bit
+ *   ray        only water seen from above casts (neither OW_RAY_SOLID nor OW_RAY_FROM_BELOW, a normal that is finite and not zero), and
+ *              only with at least one instance: origin = position, direction = the sky pass's mirror direction R, max_distance = the
+ *              options'
+ *   hit        ow_cast_bodies' for that ray, to the bit, with no water limit; one-sided unless OW_MIRROR_TWO_SIDED (so a ray that starts
+ *              inside a half-sunk crate sees nothing).  cull changes how the search is organised, never a byte
+ *   colour     with n the hit's normal and t its distance: C = body_color * ((light_color * max(n . l, 0) + ambient_color) +
+ *              E(n) * ambient_energy), the draw's terms plus the sky ambient the body itself receives; w = opacity * fade, fade = 1 for
+ *              t <= fade_begin and (max_distance - t) / (max_distance - fade_begin) beyond; the sky pass's radiance becomes
+ *              radiance (1 - w) + C w, the record gets OW_RAY_MIRROR, and the rest of the sky pass proceeds on it.  A C or n that is not
+ *              finite leaves the record as the sky pass writes it
+ *   hits       optional: width * height ow_solid_hit records; for a record that casts what ow_cast_bodies writes for its ray, for every
+ *              other record the no-hit record (status 0, instance = triangle = -1, the rest 0)
+ *   not here   the water reflected in itself; shadows on the mirrored body; roughness blur of the mirrored image; reflections in the
+ *              spray
+ * There is no group form (ow_group_*) of these calls, as for every draw. */
+#define OW_RAY_MIRROR 512                 /* ow_render_pixel.status: the pixel reflects a floating body */
+#define OW_MIRROR_TWO_SIDED 1u            /* ow_mirror_options.flags: back faces are met as well */
+typedef struct ow_mirror_options {
+    float ambient_energy;       /* as ow_radiance_light_options, [0, 1e12] */
+    float reflection_energy;    /* as ow_radiance_light_options, [0, 1e12] */
+    float specular;             /* as ow_radiance_light_options, [0, 1] */
+    float body_color[3];        /* ow_solid_options.color of the draw, linear, finite, each magnitude <= 1e12 */
+    float light_direction[3];   /* towards the light, world space, any finite length > 0 */
+    float light_color[3];       /* as ow_solid_options */
+    float ambient_color[3];     /* as ow_solid_options */
+    float max_distance;         /* metres of mirror ray, (0, 1e12] */
+    float fade_begin;           /* [0, max_distance): the image fades out from here to max_distance */
+    float opacity;              /* [0, 1] */
+    uint32_t flags;             /* OW_MIRROR_* */
+    int32_t cull;               /* 0: instances are culled by bounding spheres; -1: they are not (as ow_solid_cast_options) */
+    uint32_t reserved[12];      /* 0 */
+} ow_mirror_options;            /* 128 bytes; a NULL pointer = ow_mirror_options_init's values */
+typedef char ow_layout_check_mirror_options[(sizeof(ow_mirror_options) == 128 && offsetof(ow_mirror_options, body_color) == 12 &&
+                                             offsetof(ow_mirror_options, max_distance) == 60 && offsetof(ow_mirror_options, flags) == 72 &&
+                                             offsetof(ow_mirror_options, cull) == 76 && offsetof(ow_mirror_options, reserved) == 80) ? 1 : -1];
+
+/* ow_radiance_light_options_default's three values (1, 1, 0.5), ow_solid_options_default's colour, light and ambient, max_distance 200,
+ * fade_begin 100, opacity 1, one-sided, culled.  A NULL pointer returns without writing. */
+void ow_mirror_options_init(ow_mirror_options *out);
+/* The pass over a picture in host memory, after everything enqueued so far, against bodies [first_body, first_body + body_count) of a set
+ * at their resident poses.  pixels_inout: width * height records (required); hits_out_or_null: width * height ow_solid_hit records.
+ * solid_or_null and bodies_or_null may be NULL only with body_count == 0: the pass is then ow_radiance_light_apply.  Synchronises.  The
+ * argument checks follow ow_radiance_light_apply's order -- the records, the camera, the options (a value that is not finite or out of
+ * its range, a light direction of zero length, unknown flags, cull neither 0 nor -1, reserved words not 0), the context and the pyramid
+ * -- then ow_cast_bodies': the shape, the set, the range of bodies and the counts; OW_ERR_INVALID writes nothing.  The first three groups
+ * are checked without a device. */
+ow_status ow_mirror_apply(ow_context *ctx, ow_radiance *radiance, ow_solid *solid_or_null, ow_bodies *bodies_or_null, int32_t first_body,
+                          int32_t body_count, const ow_camera *camera, const ow_mirror_options *opts, ow_render_pixel *pixels_inout,
+                          ow_solid_hit *hits_out_or_null);
+/* The same with DEVICE pointers on the context's device (pixels_dev 16-byte aligned, hits_dev 4-byte aligned; camera and opts are host
+ * values), ordered exactly as ow_radiance_light_apply_async: behind everything enqueued so far and ahead of whatever the context enqueues
+ * next.  No synchronisation, no copy and no host traffic; the only allocation is the pass's scratch (its counters and one 16-byte sphere
+ * per instance), on first use or growth. */
+ow_status ow_mirror_apply_async(ow_context *ctx, ow_radiance *radiance, ow_solid *solid_or_null, ow_bodies *bodies_or_null, int32_t first_body,
+                                int32_t body_count, const ow_camera *camera, const ow_mirror_options *opts, ow_render_pixel *pixels_dev,
+                                ow_solid_hit *hits_dev_or_null);
+/* The host form against a caller's transforms (instance_count x 12 floats in host memory, as ow_cast_instances takes them). */
+ow_status ow_mirror_apply_instances(ow_context *ctx, ow_radiance *radiance, ow_solid *solid_or_null, const float *transforms, int32_t instance_count,
+                                    const ow_camera *camera, const ow_mirror_options *opts, ow_render_pixel *pixels_inout,
+                                    ow_solid_hit *hits_out_or_null);
+/* Counters (each output may be NULL): the passes enqueued on this context, and over the LAST pass the pixels it processed, the mirror rays
+ * it cast, the sphere tests those rays passed (with cull -1: every instance that is not skipped, per ray), the (ray, triangle) pairs
+ * tested and the rays that met a body.  Synchronises when one of the last five is asked for. */
+ow_status ow_mirror_stats(ow_context *ctx, uint64_t *passes, uint64_t *pixels, uint64_t *rays_cast, uint64_t *sphere_tests_passed,
+                          uint64_t *pairs_tested, uint64_t *rays_hit);
+
 /* ---- several devices: cascades sharded inside one process ---------------------------------------- */
 
 /* Cascades share nothing (wave_generator.gd:65-85 touches no state of another cascade; README.md:77-80), so a node's GPUs
