@@ -8,20 +8,7 @@
  * Prints key=value pairs: the final draft and the one Archimedes predicts, the range of heights the box's origin visited, the mean
  * submerged share, whether everything stayed finite and the box afloat, and the mean Newton evaluations per hull point of the last step
  * (the warm start's effect). */
-#include <math.h>
-#include <stddef.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include "ocean_waves.h"
-
-/* the three HIP runtime calls this host makes (libamdhip64, C linkage), declared here because the HIP headers are not C99 */
-extern int hipMalloc(void **ptr, size_t bytes);
-extern int hipFree(void *ptr);
-extern int hipMemcpy(void *dst, const void *src, size_t bytes, int kind);
-enum { HIP_HOST_TO_DEVICE = 1, HIP_DEVICE_TO_HOST = 2 };
+#include "scene.h"
 
 #define NX 4
 #define NY 4
@@ -58,33 +45,24 @@ static void rotate(double R[9], const double w[3], double dt) {
 
 int main(int argc, char **argv) {
     const int demo = argc > 1 && strcmp(argv[1], "demo") == 0, steps = argc > 2 ? atoi(argv[2]) : 300;
-    const int n = 256, cascades = 3;
+    const int n = 256, cascades = SCENE_CASCADES;
     const double dt = 1.0 / 60.0, g = 9.81, rho = 1025.0;
     const double size[3] = {2.0, 1.0, 2.0}, volume = size[0] * size[1] * size[2], mass = 0.5 * rho * volume;
     const double inertia[3] = {mass / 12.0 * (size[1] * size[1] + size[2] * size[2]), mass / 12.0 * (size[0] * size[0] + size[2] * size[2]),
                                mass / 12.0 * (size[0] * size[0] + size[1] * size[1])};
+    int status = 1;
+    void *hull_dev = NULL, *body_dev = NULL, *result_dev = NULL, *points_dev = NULL;
 
     ow_config cfg;
-    memset(&cfg, 0, sizeof cfg);
-    cfg.map_size = n; cfg.num_cascades = cascades; cfg.device_id = -1; cfg.depth = 20.0f;
+    scene_config(&cfg, n);
     ow_context *ctx = NULL;
     if (ow_create(&cfg, &ctx) != OW_OK) { fprintf(stderr, "ow_create: %s\n", ow_last_error()); return 1; }
 
-    static const float tile[3] = {88.0f, 57.0f, 16.0f}, wind[3] = {10.0f, 5.0f, 20.0f}, dir[3] = {20.0f, 15.0f, 20.0f};
-    static const float fetch[3] = {150.0f, 150.0f, 550.0f}, spread[3] = {0.2f, 0.4f, 0.4f}, whitecap[3] = {0.5f, 0.5f, 0.25f}, foam[3] = {8.0f, 0.0f, 3.0f};
-    ow_cascade_params par[3];
-    float map_scales[3][4];
-    for (int i = 0; i < cascades; ++i) {
-        ow_cascade_params_default(&par[i]);
-        par[i].tile_length[0] = par[i].tile_length[1] = tile[i];
-        par[i].wind_speed = wind[i]; par[i].wind_direction = dir[i]; par[i].fetch_length = fetch[i];
-        par[i].spread = spread[i]; par[i].whitecap = whitecap[i]; par[i].foam_amount = foam[i];
-        par[i].spectrum_seed[0] = 1000 + 17 * i; par[i].spectrum_seed[1] = -2000 + 31 * i;
-        par[i].time = 120.0 + 3.14159265358979323846 * i;
-        map_scales[i][0] = map_scales[i][1] = 1.0f / tile[i];
-        map_scales[i][2] = demo ? (float)par[i].displacement_scale : 0.0f;   /* calm: no displacement at all */
-        map_scales[i][3] = (float)par[i].normal_scale;
-    }
+    ow_cascade_params par[SCENE_CASCADES];
+    float map_scales[SCENE_CASCADES][4];
+    scene_cascades(par, map_scales);
+    if (!demo)
+        for (int i = 0; i < cascades; ++i) map_scales[i][2] = 0.0f;   /* calm: no displacement at all */
 
     /* the hull: the box voxelised into NX x NY x NZ cells, one point per cell with the cell's volume and half its height */
     ow_hull_point hull[NPOINTS];
@@ -99,15 +77,14 @@ int main(int argc, char **argv) {
                 hull[k].half_height = (float)(size[1] / NY / 2);
                 hull[k].body = 0;
             }
-    void *hull_dev = NULL, *body_dev = NULL, *result_dev = NULL, *points_dev = NULL;
     if (hipMalloc(&hull_dev, sizeof hull) || hipMalloc(&body_dev, sizeof(ow_buoyancy_body)) || hipMalloc(&result_dev, sizeof(ow_buoyancy_result)) ||
         hipMalloc(&points_dev, NPOINTS * sizeof(ow_buoyancy_point)) || hipMemcpy(hull_dev, hull, sizeof hull, HIP_HOST_TO_DEVICE)) {
         fprintf(stderr, "hipMalloc / hipMemcpy failed\n");
-        return 1;
+        goto out;
     }
     {   /* zeros: the first step starts cold */
         static ow_buoyancy_point zeros[NPOINTS];
-        if (hipMemcpy(points_dev, zeros, sizeof zeros, HIP_HOST_TO_DEVICE)) { fprintf(stderr, "hipMemcpy failed\n"); return 1; }
+        if (hipMemcpy(points_dev, zeros, sizeof zeros, HIP_HOST_TO_DEVICE)) { fprintf(stderr, "hipMemcpy failed\n"); goto out; }
     }
     ow_buoyancy_options opts;
     memset(&opts, 0, sizeof opts);
@@ -130,16 +107,16 @@ int main(int argc, char **argv) {
         }
         body.point_offset = 0; body.point_count = NPOINTS;
         body.linear_drag = 3.0f; body.quadratic_drag = 0.5f;
-        if (hipMemcpy(body_dev, &body, sizeof body, HIP_HOST_TO_DEVICE)) { fprintf(stderr, "hipMemcpy failed\n"); return 1; }
+        if (hipMemcpy(body_dev, &body, sizeof body, HIP_HOST_TO_DEVICE)) { fprintf(stderr, "hipMemcpy failed\n"); goto out; }
         if (ow_buoyancy_async(ctx, (const ow_buoyancy_body *)body_dev, 1, (const ow_hull_point *)hull_dev, NPOINTS, &map_scales[0][0], cascades, &opts,
                               (ow_buoyancy_result *)result_dev, (ow_buoyancy_point *)points_dev) != OW_OK)
             goto fail;
         if (ow_sync(ctx) != OW_OK) goto fail;
-        if (hipMemcpy(&res, result_dev, sizeof res, HIP_DEVICE_TO_HOST)) { fprintf(stderr, "hipMemcpy failed\n"); return 1; }
+        if (hipMemcpy(&res, result_dev, sizeof res, HIP_DEVICE_TO_HOST)) { fprintf(stderr, "hipMemcpy failed\n"); goto out; }
         if (step == steps - 1 || step % 50 == 0) {   /* what the warm start costs: the per-point records say */
             static ow_buoyancy_point pts[NPOINTS];
             double e = 0.0;
-            if (hipMemcpy(pts, points_dev, sizeof pts, HIP_DEVICE_TO_HOST)) { fprintf(stderr, "hipMemcpy failed\n"); return 1; }
+            if (hipMemcpy(pts, points_dev, sizeof pts, HIP_DEVICE_TO_HOST)) { fprintf(stderr, "hipMemcpy failed\n"); goto out; }
             for (int i = 0; i < NPOINTS; ++i) e += pts[i].evaluations;
             if (step == steps - 1) evals = e / NPOINTS;
         }
@@ -168,11 +145,12 @@ int main(int argc, char **argv) {
         printf("steps=%d draft=%.5f expected_draft=%.5f y_min=%.4f y_max=%.4f submerged_share=%.4f invalid_points=%d evaluations_per_point=%.3f "
                "finite=%d afloat=%d\n", steps, draft, expected, y_min, y_max, wet_share, res.invalid_points, evals, finite, afloat);
     }
-    (void)hipFree(hull_dev); (void)hipFree(body_dev); (void)hipFree(result_dev); (void)hipFree(points_dev);
-    ow_destroy(ctx);
-    return 0;
+    status = 0;
+    goto out;
 fail:
     fprintf(stderr, "ocean_waves: %s\n", ow_last_error());
+out:
+    (void)hipFree(hull_dev); (void)hipFree(body_dev); (void)hipFree(result_dev); (void)hipFree(points_dev);
     ow_destroy(ctx);
-    return 1;
+    return status;
 }

@@ -15,14 +15,7 @@
  * end; y_min / y_max: the crates' heights over the whole history), so here they are measured from the water above each crate at the end
  * (ow_query_surface; off_water_max is the largest distance).  Also: the bodies the device flagged as faulted and host_syncs, the stream
  * synchronisations the library made inside the loop (0). */
-#include <math.h>
-#include <stddef.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include "ocean_waves.h"
+#include "scene.h"
 
 #define CRATES 256
 #define NX 3
@@ -42,49 +35,29 @@ static float grid_xz[GRID * GRID][2];
 static ow_surface_query grid_water[GRID * GRID];
 #define SNAP_EVERY 4
 
-/* the HIP runtime calls this host makes (libamdhip64, C linkage), declared here because the HIP headers are not C99 */
-extern int hipMalloc(void **ptr, size_t bytes);
-extern int hipFree(void *ptr);
-extern int hipMemcpy(void *dst, const void *src, size_t bytes, int kind);
-extern int hipMemcpyAsync(void *dst, const void *src, size_t bytes, int kind, void *stream);
-extern int hipStreamCreate(void **stream);
-extern int hipStreamDestroy(void *stream);
-enum { HIP_DEVICE_TO_HOST = 2, HIP_DEVICE_TO_DEVICE = 3 };
-
 int main(int argc, char **argv) {
-    const int frames = argc > 1 ? atoi(argv[1]) : 300, substeps = 4;
-    const int n = 256, cascades = 3;
+    const int frames = scene_arg(argc, argv, 1, 300), substeps = 4;
+    const int n = 256, cascades = SCENE_CASCADES;
     const double frame_dt = 1.0 / 60.0, rho = 1025.0;
     const int snaps = frames / SNAP_EVERY;
+    int status = 1;
     uint64_t syncs_before = 0, syncs_after = 0;
     void *stream = NULL, *bodies_dev = NULL, *results_dev = NULL, *hist_bodies = NULL, *hist_results = NULL;
     ow_buoyancy_body *hb = NULL;
     ow_buoyancy_result *hr = NULL;
+    ow_context *ctx = NULL;
+    ow_bodies *set = NULL;
     if (snaps < 1) { fprintf(stderr, "at least %d frames\n", SNAP_EVERY); return 1; }
     if (hipStreamCreate(&stream)) { fprintf(stderr, "hipStreamCreate failed (this library has no CPU fallback)\n"); return 1; }
 
     ow_config cfg;
-    memset(&cfg, 0, sizeof cfg);
-    cfg.map_size = n; cfg.num_cascades = cascades; cfg.device_id = -1; cfg.depth = 20.0f;
+    scene_config(&cfg, n);
     cfg.stream = stream;
-    ow_context *ctx = NULL;
-    if (ow_create(&cfg, &ctx) != OW_OK) { fprintf(stderr, "ow_create: %s\n", ow_last_error()); return 1; }
+    if (ow_create(&cfg, &ctx) != OW_OK) { fprintf(stderr, "ow_create: %s\n", ow_last_error()); (void)hipStreamDestroy(stream); return 1; }
 
-    static const float tile[3] = {88.0f, 57.0f, 16.0f}, wind[3] = {10.0f, 5.0f, 20.0f}, dir[3] = {20.0f, 15.0f, 20.0f};
-    static const float fetch[3] = {150.0f, 150.0f, 550.0f}, spread[3] = {0.2f, 0.4f, 0.4f}, whitecap[3] = {0.5f, 0.5f, 0.25f}, foam[3] = {8.0f, 0.0f, 3.0f};
-    ow_cascade_params par[3];
-    float map_scales[3][4];
-    for (int i = 0; i < cascades; ++i) {
-        ow_cascade_params_default(&par[i]);
-        par[i].tile_length[0] = par[i].tile_length[1] = tile[i];
-        par[i].wind_speed = wind[i]; par[i].wind_direction = dir[i]; par[i].fetch_length = fetch[i];
-        par[i].spread = spread[i]; par[i].whitecap = whitecap[i]; par[i].foam_amount = foam[i];
-        par[i].spectrum_seed[0] = 1000 + 17 * i; par[i].spectrum_seed[1] = -2000 + 31 * i;
-        par[i].time = 120.0 + 3.14159265358979323846 * i;
-        map_scales[i][0] = map_scales[i][1] = 1.0f / tile[i];
-        map_scales[i][2] = (float)par[i].displacement_scale;
-        map_scales[i][3] = (float)par[i].normal_scale;
-    }
+    ow_cascade_params par[SCENE_CASCADES];
+    float map_scales[SCENE_CASCADES][4];
+    scene_cascades(par, map_scales);
 
     /* the crates: a 16 x 16 grid 12 m apart, sizes from 1 to 3 m, each of half the water's density, voxelised into NX x NY x NZ points */
     memset(bodies, 0, sizeof bodies);
@@ -114,7 +87,6 @@ int main(int argc, char **argv) {
                 }
     }
     /* launch the crates from the water: the maps of the first tick, the height above each crate (both before the loop) */
-    ow_bodies *set = NULL;
     if (ow_update_all(ctx, frame_dt, par, cascades) != OW_OK) goto fail;
     for (int b = 0; b < CRATES; ++b) {
         crate_xz[b][0] = (float)bodies[b].position[0];
@@ -127,7 +99,7 @@ int main(int argc, char **argv) {
     if (ow_bodies_get_device_ptrs(ctx, set, &bodies_dev, &results_dev, NULL) != OW_OK) goto fail;
     if (hipMalloc(&hist_bodies, (size_t)snaps * sizeof bodies_rec) || hipMalloc(&hist_results, (size_t)snaps * sizeof results)) {
         fprintf(stderr, "hipMalloc failed\n");
-        return 1;
+        goto out;
     }
 
     ow_bodies_options opts;
@@ -145,7 +117,7 @@ int main(int argc, char **argv) {
             if (hipMemcpyAsync((char *)hist_bodies + k * sizeof bodies_rec, bodies_dev, sizeof bodies_rec, HIP_DEVICE_TO_DEVICE, stream) ||
                 hipMemcpyAsync((char *)hist_results + k * sizeof results, results_dev, sizeof results, HIP_DEVICE_TO_DEVICE, stream)) {
                 fprintf(stderr, "hipMemcpyAsync failed\n");
-                return 1;
+                goto out;
             }
         }
     }
@@ -163,7 +135,7 @@ int main(int argc, char **argv) {
         if (!hb || !hr || hipMemcpy(hb, hist_bodies, (size_t)snaps * sizeof bodies_rec, HIP_DEVICE_TO_HOST) ||
             hipMemcpy(hr, hist_results, (size_t)snaps * sizeof results, HIP_DEVICE_TO_HOST)) {
             fprintf(stderr, "history read-back failed\n");
-            return 1;
+            goto out;
         }
         for (int b = 0; b < CRATES; ++b) {
             crate_xz[b][0] = (float)bodies[b].position[0];
@@ -207,15 +179,15 @@ int main(int argc, char **argv) {
                frames, (unsigned long long)taken, (unsigned long long)fused, (unsigned long long)split, (unsigned long long)faulted, snaps, share,
                share_min, share_max, off_max, y_min, y_max, water_min, water_max, finite, afloat, (unsigned long long)(syncs_after - syncs_before));
     }
+    status = 0;
+    goto out;
+fail:
+    fprintf(stderr, "ocean_waves: %s\n", ow_last_error());
+out:
     free(hb); free(hr);
     (void)hipFree(hist_bodies); (void)hipFree(hist_results);
     ow_bodies_destroy(ctx, set);
     ow_destroy(ctx);
     (void)hipStreamDestroy(stream);
-    return 0;
-fail:
-    fprintf(stderr, "ocean_waves: %s\n", ow_last_error());
-    ow_bodies_destroy(ctx, set);
-    ow_destroy(ctx);
-    return 1;
+    return status;
 }

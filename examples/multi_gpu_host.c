@@ -8,13 +8,9 @@
  * Prints: maps/s without any gather, with a gather every `gather_every` ticks (overlapped), the copy time of one gather and the
  * bytes per shard, and a checksum of the gathered arrays after the run (the same on any device list: cascades are independent). */
 #define _POSIX_C_SOURCE 199309L
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
 #include <time.h>
 
-#include "ocean_waves.h"
+#include "scene.h"
 
 static double now(void) {
     struct timespec ts;
@@ -73,8 +69,7 @@ int main(int argc, char **argv) {
         par[i].tile_length[0] = par[i].tile_length[1] = r[0];
         par[i].wind_speed = r[1]; par[i].wind_direction = r[2]; par[i].fetch_length = r[3];
         par[i].swell = r[4]; par[i].spread = r[5]; par[i].detail = r[6]; par[i].whitecap = r[7]; par[i].foam_amount = r[8];
-        par[i].spectrum_seed[0] = 1000 + 17 * i; par[i].spectrum_seed[1] = -2000 + 31 * i;
-        par[i].time = 120.0 + 3.14159265358979323846 * i;   /* water.gd:32 */
+        scene_cascade_start(&par[i], i);   /* water.gd:31-32 */
     }
     const double delta = 1.0 / 50.0;
     CHECK(ow_group_run(g, delta, par, total, 50));          /* spectra + warm-up */

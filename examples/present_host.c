@@ -6,84 +6,26 @@
  * with no synchronisation in between; the sRGB picture is copied back and written as a binary PPM.
  *   gcc -O2 -std=c99 -Iinclude examples/present_host.c -o present_host -Lgodotoceanwaves_amd -locean_waves -L/opt/rocm/lib -lamdhip64 \
  *       -Wl,-rpath,$PWD/godotoceanwaves_amd -Wl,-rpath,/opt/rocm/lib -lm && ./present_host [out.ppm [width height [steps [map_size [amount [downsample]]]]]]
- * width x height is the size of the PPM; the records are drawn at downsample (1 .. 4, default 2) times that.  The scene, the crates and
- * the two spray textures are solid_draw_host.c's.  Prints key=value pairs: the image size, the record size, the pixels the environment
+ * width x height is the size of the PPM; the records are drawn at downsample (1 .. 4, default 2) times that.  The scene, the crates, the
+ * panorama and the two spray textures are scene.h's.  Prints key=value pairs: the image size, the record size, the pixels the environment
  * pass processed, those of them that show the sky, the pixels that show a crate, the pixels that received spray and whether every
  * resolved linear colour is finite. */
-#include <math.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
+#include "scene.h"
 
-#include "ocean_waves.h"
-
-/* the HIP runtime calls this host makes (libamdhip64, C linkage), declared here because the HIP headers are not C99 */
-extern int hipMalloc(void **ptr, size_t bytes);
-extern int hipFree(void *ptr);
-extern int hipMemcpy(void *dst, const void *src, size_t bytes, int kind);
-enum { HIP_DEVICE_TO_HOST = 2 };
-
-#define CELLS 128
-#define CELL 4.0f
-#define TEX 64
-#define CRATES 36
-#define NX 4
-#define NY 2
-#define NZ 4
-#define PER_CRATE (NX * NY * NZ)
 #define SUBSTEPS 4
-#define PANO_W 256
-#define PANO_H 128
 
-static ow_rigid_body bodies[CRATES];
-static ow_hull_point hull[CRATES * PER_CRATE];
-
-/* albedo: white, alpha a puff that is 1 at the centre and 0 at the rim; dissolve: a value noise of period TEX in the red channel */
-static void make_textures(unsigned char *albedo, unsigned char *dissolve) {
-    uint32_t lattice[8][8], s = 12345u;
-    for (int j = 0; j < 8; ++j)
-        for (int i = 0; i < 8; ++i) lattice[j][i] = ((s = s * 1664525u + 1013904223u) >> 24) & 0xffu;
-    for (int j = 0; j < TEX; ++j)
-        for (int i = 0; i < TEX; ++i) {
-            unsigned char *a = albedo + 4 * (j * TEX + i), *d = dissolve + 4 * (j * TEX + i);
-            const int dx = 2 * i + 1 - TEX, dy = 2 * j + 1 - TEX;                  /* twice the distance from the centre, in texels */
-            const int r2 = dx * dx + dy * dy, rim = TEX * TEX;
-            a[0] = a[1] = a[2] = 255;
-            a[3] = (unsigned char)(r2 >= rim ? 0 : 255 - (255 * r2) / rim);
-            const int cx = i / 8, cy = j / 8, fx = i % 8, fy = j % 8;             /* bilinear over an 8 x 8 lattice, integers only */
-            const uint32_t v00 = lattice[cy][cx], v10 = lattice[cy][(cx + 1) % 8], v01 = lattice[(cy + 1) % 8][cx], v11 = lattice[(cy + 1) % 8][(cx + 1) % 8];
-            const uint32_t top = v00 * (uint32_t)(8 - fx) + v10 * (uint32_t)fx, bot = v01 * (uint32_t)(8 - fx) + v11 * (uint32_t)fx;
-            d[0] = (unsigned char)((top * (uint32_t)(8 - fy) + bot * (uint32_t)fy) / 128u);   /* 0 .. 127: most particles clear it */
-            d[1] = d[2] = d[0];
-            d[3] = 255;
-        }
-}
-
-/* the panorama: a zenith-to-horizon gradient above, a darker one below, brighter towards the seam (+Z); integers only */
-static void make_panorama(unsigned char *p) {
-    const int half = PANO_H / 2;
-    for (int j = 0; j < PANO_H; ++j)
-        for (int i = 0; i < PANO_W; ++i) {
-            unsigned char *t = p + 4 * (j * PANO_W + i);
-            const int up = j < half, k = up ? j : PANO_H - 1 - j;   /* 0 at a pole .. half - 1 at the horizon */
-            const int az = (20 * abs(2 * i - PANO_W)) / PANO_W;
-            t[0] = (unsigned char)((up ? 60 + (150 * k) / (half - 1) : 30 + (40 * k) / (half - 1)) + az);
-            t[1] = (unsigned char)((up ? 110 + (110 * k) / (half - 1) : 50 + (50 * k) / (half - 1)) + az);
-            t[2] = (unsigned char)(up ? 200 + (40 * k) / (half - 1) : 70 + (60 * k) / (half - 1));
-            t[3] = 255;
-        }
-}
+static ow_rigid_body bodies[SCENE_CRATES];
+static ow_hull_point hull[SCENE_CRATES * SCENE_PER_CRATE];
 
 int main(int argc, char **argv) {
     const char *path = argc > 1 ? argv[1] : "present.ppm";
-    const int out_width = argc > 3 ? atoi(argv[2]) : 320, out_height = argc > 3 ? atoi(argv[3]) : 200, down = argc > 7 ? atoi(argv[7]) : 2;
-    const int steps = argc > 4 ? atoi(argv[4]) : 150, n = argc > 5 ? atoi(argv[5]) : 256, cascades = 3;
+    const int out_width = argc > 3 ? atoi(argv[2]) : 320, out_height = argc > 3 ? atoi(argv[3]) : 200, down = scene_arg(argc, argv, 7, 2);
+    const int steps = scene_arg(argc, argv, 4, 150), n = scene_arg(argc, argv, 5, 256), cascades = SCENE_CASCADES;
     const double dt = 1.0 / 50.0;   /* water.gd:51 */
+    int status = 1;
 
     ow_config cfg;
-    memset(&cfg, 0, sizeof cfg);
-    cfg.map_size = n; cfg.num_cascades = cascades; cfg.device_id = -1; cfg.depth = 20.0f;
+    scene_config(&cfg, n);
     ow_context *ctx = NULL;
     ow_mesh *mesh = NULL;
     ow_spray *spray = NULL;
@@ -97,29 +39,16 @@ int main(int argc, char **argv) {
     void *rgba_dev = NULL, *px_dev = NULL, *linear_dev = NULL;
     if (ow_create(&cfg, &ctx) != OW_OK) { fprintf(stderr, "ow_create: %s\n", ow_last_error()); return 1; }
 
-    static const float tile[3] = {88.0f, 57.0f, 16.0f}, wind[3] = {10.0f, 5.0f, 20.0f}, dir[3] = {20.0f, 15.0f, 20.0f};
-    static const float fetch[3] = {150.0f, 150.0f, 550.0f}, spread[3] = {0.2f, 0.4f, 0.4f}, whitecap[3] = {0.5f, 0.5f, 0.25f}, foam[3] = {8.0f, 0.0f, 3.0f};
-    ow_cascade_params par[3];
-    float map_scales[3][4];
-    for (int i = 0; i < cascades; ++i) {
-        ow_cascade_params_default(&par[i]);
-        par[i].tile_length[0] = par[i].tile_length[1] = tile[i];
-        par[i].wind_speed = wind[i]; par[i].wind_direction = dir[i]; par[i].fetch_length = fetch[i];
-        par[i].spread = spread[i]; par[i].whitecap = whitecap[i]; par[i].foam_amount = foam[i];
-        par[i].spectrum_seed[0] = 1000 + 17 * i; par[i].spectrum_seed[1] = -2000 + 31 * i;
-        par[i].time = 120.0 + 3.14159265358979323846 * i;
-        map_scales[i][0] = map_scales[i][1] = 1.0f / tile[i];
-        map_scales[i][2] = (float)par[i].displacement_scale;
-        map_scales[i][3] = (float)par[i].normal_scale;
-    }
-    if (down < 1 || down > OW_PRESENT_MAX_DOWNSAMPLE || out_width < 1 || out_height < 1 || out_width > OW_RENDER_MAX_SIDE / down ||
-        out_height > OW_RENDER_MAX_SIDE / down) { fprintf(stderr, "bad image size\n"); goto fail_quiet; }
+    ow_cascade_params par[SCENE_CASCADES];
+    float map_scales[SCENE_CASCADES][4];
+    scene_cascades(par, map_scales);
+    if (scene_bad_size(out_width, out_height, down)) goto out;
     const int width = out_width * down, height = out_height * down;   /* the records */
 
     {   /* the sky: stands in for main.tscn's PanoramaSkyMaterial */
-        static unsigned char panorama[PANO_W * PANO_H * 4];
-        make_panorama(panorama);
-        if (ow_sky_create(ctx, NULL, panorama, PANO_W, PANO_H, &sky) != OW_OK) goto fail;
+        static unsigned char panorama[SCENE_PANO_W * SCENE_PANO_H * 4];
+        scene_panorama(panorama);
+        if (ow_sky_create(ctx, NULL, panorama, SCENE_PANO_W, SCENE_PANO_H, &sky) != OW_OK) goto fail;
     }
 
     ow_spray_options so;
@@ -128,97 +57,32 @@ int main(int argc, char **argv) {
     if (ow_spray_create(ctx, &so, &spray) != OW_OK) goto fail;
 
     {   /* the material: sea_spray.gdshader's uniforms as the scene sets them, over the two procedural textures */
-        static unsigned char albedo[TEX * TEX * 4], dissolve[TEX * TEX * 4];
+        static unsigned char albedo[SCENE_TEX * SCENE_TEX * 4], dissolve[SCENE_TEX * SCENE_TEX * 4];
         ow_billboard_material_options mo;
-        make_textures(albedo, dissolve);
+        scene_textures(albedo, dissolve);
         ow_billboard_material_options_default(&mo);
-        if (ow_billboard_material_create(ctx, &mo, albedo, TEX, TEX, dissolve, TEX, TEX, &material) != OW_OK) goto fail;
+        if (ow_billboard_material_create(ctx, &mo, albedo, SCENE_TEX, SCENE_TEX, dissolve, SCENE_TEX, SCENE_TEX, &material) != OW_OK) goto fail;
     }
 
-    {   /* the crates: the states and the voxelised hulls of floating_bodies_host.c, all of one size, and that box as a shape */
-        const double size[3] = {2.0, 1.0, 2.0}, rho = 1025.0;
-        const double volume = size[0] * size[1] * size[2], mass = 0.5 * rho * volume;
-        float corners[8][3];
-        static const int32_t quads[6][4] = {{0, 1, 3, 2}, {4, 6, 7, 5}, {0, 4, 5, 1}, {2, 3, 7, 6}, {0, 2, 6, 4}, {1, 5, 7, 3}};   /* -x +x -y +y -z +z */
-        int32_t idx[12][3];
-        memset(bodies, 0, sizeof bodies);
-        memset(hull, 0, sizeof hull);
-        for (int b = 0; b < CRATES; ++b) {
-            ow_rigid_body *B = &bodies[b];
-            B->position[0] = (b % 6 - 2.5) * 6.0; B->position[1] = 0.3; B->position[2] = 10.0 + (b / 6 - 2.5) * 6.0;
-            B->orientation[3] = 1.0;
-            B->mass = mass;
-            B->inverse_inertia[0] = 12.0 / (mass * (size[1] * size[1] + size[2] * size[2]));
-            B->inverse_inertia[1] = 12.0 / (mass * (size[0] * size[0] + size[2] * size[2]));
-            B->inverse_inertia[2] = 12.0 / (mass * (size[0] * size[0] + size[1] * size[1]));
-            B->linear_drag = 3.0f; B->quadratic_drag = 0.5f;
-            B->point_offset = b * PER_CRATE; B->point_count = PER_CRATE;
-            for (int i = 0, k = b * PER_CRATE; i < NX; ++i)
-                for (int j = 0; j < NY; ++j)
-                    for (int l = 0; l < NZ; ++l, ++k) {
-                        hull[k].local[0] = (float)((i + 0.5) * (size[0] / NX) - size[0] / 2);
-                        hull[k].local[1] = (float)((j + 0.5) * (size[1] / NY) - size[1] / 2);
-                        hull[k].local[2] = (float)((l + 0.5) * (size[2] / NZ) - size[2] / 2);
-                        hull[k].volume = (float)(volume / PER_CRATE);
-                        hull[k].half_height = (float)(size[1] / NY / 2);
-                        hull[k].body = b;
-                    }
-        }
-        if (ow_bodies_create(ctx, bodies, CRATES, hull, CRATES * PER_CRATE, &set) != OW_OK) goto fail;
-        for (int v = 0; v < 8; ++v) {   /* corner 4 ix + 2 iy + iz; every face counter-clockwise seen from outside */
-            corners[v][0] = (float)((v & 4 ? 0.5 : -0.5) * size[0]);
-            corners[v][1] = (float)((v & 2 ? 0.5 : -0.5) * size[1]);
-            corners[v][2] = (float)((v & 1 ? 0.5 : -0.5) * size[2]);
-        }
-        for (int q = 0; q < 6; ++q) {
-            idx[2 * q][0] = quads[q][0]; idx[2 * q][1] = quads[q][1]; idx[2 * q][2] = quads[q][2];
-            idx[2 * q + 1][0] = quads[q][0]; idx[2 * q + 1][1] = quads[q][2]; idx[2 * q + 1][2] = quads[q][3];
-        }
-        if (ow_solid_create(ctx, &corners[0][0], 8, &idx[0][0], 12, &solid) != OW_OK) goto fail;
+    {   /* the crates: their states and voxelised hulls, and the same box as a shape */
+        float corners[SCENE_BOX_VERTICES][3];
+        int32_t idx[SCENE_BOX_TRIANGLES][3];
+        scene_crates(bodies, hull);
+        if (ow_bodies_create(ctx, bodies, SCENE_CRATES, hull, SCENE_CRATES * SCENE_PER_CRATE, &set) != OW_OK) goto fail;
+        scene_box(corners, idx);
+        if (ow_solid_create(ctx, &corners[0][0], SCENE_BOX_VERTICES, &idx[0][0], SCENE_BOX_TRIANGLES, &solid) != OW_OK) goto fail;
     }
-
-    {   /* the grid: (CELLS + 1)^2 vertices around the node's origin, two triangles a cell */
-        const int32_t num_vertices = (CELLS + 1) * (CELLS + 1), num_triangles = 2 * CELLS * CELLS;
-        float *xyz = (float *)malloc((size_t)num_vertices * 3 * sizeof(float));
-        int32_t *idx = (int32_t *)malloc((size_t)num_triangles * 3 * sizeof(int32_t));
-        if (!xyz || !idx) { fprintf(stderr, "out of memory\n"); goto fail_quiet; }
-        for (int r = 0; r <= CELLS; ++r)
-            for (int c = 0; c <= CELLS; ++c) {
-                float *v = xyz + 3 * ((size_t)r * (CELLS + 1) + c);
-                v[0] = (float)c * CELL - 0.5f * CELLS * CELL; v[1] = 0.0f; v[2] = (float)r * CELL - 0.5f * CELLS * CELL;
-            }
-        for (int r = 0; r < CELLS; ++r)
-            for (int c = 0; c < CELLS; ++c) {
-                const int32_t a = r * (CELLS + 1) + c, b = a + 1, d = a + CELLS + 1, e = d + 1;
-                int32_t *t = idx + 6 * ((size_t)r * CELLS + c);
-                t[0] = a; t[1] = d; t[2] = b; t[3] = b; t[4] = d; t[5] = e;
-            }
-        const ow_status st = ow_mesh_create(ctx, xyz, num_vertices, idx, num_triangles, &mesh);
-        free(xyz); free(idx);
-        if (st != OW_OK) goto fail;
-    }
+    if (scene_grid_create(ctx, SCENE_CELLS, SCENE_CELL, &mesh)) goto out;
 
     ow_camera cam;
-    memset(&cam, 0, sizeof cam);
-    {   /* main.tscn:120 */
-        static const float basis[9] = {-0.996195f, -0.0151344f, 0.0858316f, 0.0f, 0.984807f, 0.173648f, -0.0871557f, 0.172987f, -0.981061f};
-        memcpy(cam.basis, basis, sizeof basis);
-        cam.position[0] = 0.0f; cam.position[1] = 10.0f; cam.position[2] = -25.0f;
-    }
-    cam.fov_y_degrees = 75.0f;
-    cam.max_distance = 4000.0f;
-    cam.width = width; cam.height = height;
-    const float origin[3] = {ceilf(cam.position[0] / CELL) * CELL, 0.0f, ceilf(cam.position[2] / CELL) * CELL};   /* main.gd:34-37 */
-
+    float origin[3];
+    scene_camera(&cam, width, height);
+    scene_clipmap_origin(&cam, SCENE_CELL, origin);
     ow_mesh_options opts;
-    ow_mesh_options_default(&opts);
-    opts.query_flags = OW_QUERY_DISTANCE_FALLOFF;   /* water.gdshader:29, around CAMERA_POSITION_WORLD.xz */
-    opts.falloff_center_xz[0] = cam.position[0];
-    opts.falloff_center_xz[1] = cam.position[2];
-    opts.flags = OW_MESH_CULL_BACK;
+    scene_mesh_options(&opts, &cam);
 
     const size_t count = (size_t)width * (size_t)height, out_count = (size_t)out_width * (size_t)out_height;
-    if (hipMalloc(&rgba_dev, out_count * 4) || hipMalloc(&linear_dev, out_count * 16) || hipMalloc(&px_dev, count * sizeof(ow_render_pixel))) { fprintf(stderr, "hipMalloc failed\n"); goto fail_quiet; }
+    if (hipMalloc(&rgba_dev, out_count * 4) || hipMalloc(&linear_dev, out_count * 16) || hipMalloc(&px_dev, count * sizeof(ow_render_pixel))) { fprintf(stderr, "hipMalloc failed\n"); goto out; }
 
     ow_bodies_options bo;
     memset(&bo, 0, sizeof bo);
@@ -233,7 +97,7 @@ int main(int argc, char **argv) {
     ow_present_options_default(&po);   /* main.tscn:25, :38-41 */
     po.downsample = down;
     if (ow_mesh_draw_async(ctx, mesh, &cam, origin, &map_scales[0][0], cascades, &opts, NULL, (ow_render_pixel *)px_dev) != OW_OK) goto fail;
-    if (ow_solid_draw_async(ctx, solid, set, 0, CRATES, &cam, NULL, (ow_render_pixel *)px_dev, NULL) != OW_OK) goto fail;
+    if (ow_solid_draw_async(ctx, solid, set, 0, SCENE_CRATES, &cam, NULL, (ow_render_pixel *)px_dev, NULL) != OW_OK) goto fail;
     if (ow_environment_apply_async(ctx, sky, &cam, NULL, (ow_render_pixel *)px_dev) != OW_OK) goto fail;   /* main.tscn:22-34 */
     if (ow_billboard_draw_async(ctx, spray, material, &cam, NULL, (ow_render_pixel *)px_dev, NULL) != OW_OK) goto fail;
     if (ow_present_async(ctx, &cam, &po, (const ow_render_pixel *)px_dev, rgba_dev, (float *)linear_dev) != OW_OK) goto fail;
@@ -242,17 +106,13 @@ int main(int argc, char **argv) {
     rgba = (unsigned char *)malloc(out_count * 4);
     linear = (float *)malloc(out_count * 16);
     px = (ow_render_pixel *)malloc(count * sizeof(ow_render_pixel));
-    if (!rgba || !px || !linear) { fprintf(stderr, "out of memory\n"); goto fail_quiet; }
+    if (!rgba || !px || !linear) { fprintf(stderr, "out of memory\n"); goto out; }
     if (hipMemcpy(rgba, rgba_dev, out_count * 4, HIP_DEVICE_TO_HOST) || hipMemcpy(linear, linear_dev, out_count * 16, HIP_DEVICE_TO_HOST) ||
         hipMemcpy(px, px_dev, count * sizeof(ow_render_pixel), HIP_DEVICE_TO_HOST)) {
         fprintf(stderr, "hipMemcpy failed\n");
-        goto fail_quiet;
+        goto out;
     }
-    FILE *f = fopen(path, "wb");
-    if (!f) { fprintf(stderr, "cannot write %s\n", path); goto fail_quiet; }
-    fprintf(f, "P6\n%d %d\n255\n", out_width, out_height);
-    for (size_t i = 0; i < out_count; ++i) fwrite(rgba + 4 * i, 1, 3, f);
-    fclose(f);
+    if (scene_write_ppm(path, rgba, out_width, out_height)) goto out;
 
     {
         size_t sprayed = 0, crate_pixels = 0, processed = 0, sky_pixels = 0;
@@ -266,22 +126,14 @@ int main(int argc, char **argv) {
         for (size_t i = 0; i < 4 * out_count; ++i) finite &= isfinite(linear[i]) != 0;
         printf("file=%s width=%d height=%d downsample=%d record_width=%d record_height=%d steps=%d crates=%d environment_pixels=%llu sky_pixels=%llu "
                "crate_pixels=%llu sprayed_pixels=%llu finite=%d\n",
-               path, out_width, out_height, down, width, height, steps, CRATES, (unsigned long long)processed, (unsigned long long)sky_pixels,
+               path, out_width, out_height, down, width, height, steps, SCENE_CRATES, (unsigned long long)processed, (unsigned long long)sky_pixels,
                (unsigned long long)crate_pixels, (unsigned long long)sprayed, finite);
     }
-    free(rgba); free(px); free(linear);
-    (void)hipFree(rgba_dev); (void)hipFree(px_dev); (void)hipFree(linear_dev);
-    ow_sky_destroy(ctx, sky);
-    ow_solid_destroy(ctx, solid);
-    ow_bodies_destroy(ctx, set);
-    ow_billboard_material_destroy(ctx, material);
-    ow_spray_destroy(ctx, spray);
-    ow_mesh_destroy(ctx, mesh);
-    ow_destroy(ctx);
-    return 0;
+    status = 0;
+    goto out;
 fail:
     fprintf(stderr, "ocean_waves: %s\n", ow_last_error());
-fail_quiet:
+out:
     free(rgba); free(px); free(linear);
     (void)hipFree(rgba_dev); (void)hipFree(px_dev); (void)hipFree(linear_dev);
     ow_sky_destroy(ctx, sky);
@@ -291,5 +143,5 @@ fail_quiet:
     ow_spray_destroy(ctx, spray);
     ow_mesh_destroy(ctx, mesh);
     ow_destroy(ctx);
-    return 1;
+    return status;
 }

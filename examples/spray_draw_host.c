@@ -4,81 +4,33 @@
  * order, with no synchronisation in between -- copies the picture back and writes a binary PPM.
  *   gcc -O2 -std=c99 -Iinclude examples/spray_draw_host.c -o spray_draw_host -Lgodotoceanwaves_amd -locean_waves -L/opt/rocm/lib -lamdhip64 \
  *       -Wl,-rpath,$PWD/godotoceanwaves_amd -Wl,-rpath,/opt/rocm/lib -lm && ./spray_draw_host [out.ppm [width height [steps [map_size [amount]]]]]
- * The scene is mesh_host.c's and spray_host.c's.  The two textures are procedural -- a round puff with a soft edge for the albedo, a
- * tiling value noise for the dissolve -- because decoding the reference's sea_spray.png and generating its NoiseTexture2D stay with the
- * host.  Prints key=value pairs: the image size, the live particles, the billboards drawn and culled, the pixels that received spray
- * and whether every colour is finite. */
-#include <math.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include "ocean_waves.h"
-
-/* the HIP runtime calls this host makes (libamdhip64, C linkage), declared here because the HIP headers are not C99 */
-extern int hipMalloc(void **ptr, size_t bytes);
-extern int hipFree(void *ptr);
-extern int hipMemcpy(void *dst, const void *src, size_t bytes, int kind);
-enum { HIP_DEVICE_TO_HOST = 2 };
-
-#define CELLS 128
-#define CELL 4.0f
-#define TEX 64
-
-/* albedo: white, alpha a puff that is 1 at the centre and 0 at the rim; dissolve: a value noise of period TEX in the red channel */
-static void make_textures(unsigned char *albedo, unsigned char *dissolve) {
-    uint32_t lattice[8][8], s = 12345u;
-    for (int j = 0; j < 8; ++j)
-        for (int i = 0; i < 8; ++i) lattice[j][i] = ((s = s * 1664525u + 1013904223u) >> 24) & 0xffu;
-    for (int j = 0; j < TEX; ++j)
-        for (int i = 0; i < TEX; ++i) {
-            unsigned char *a = albedo + 4 * (j * TEX + i), *d = dissolve + 4 * (j * TEX + i);
-            const int dx = 2 * i + 1 - TEX, dy = 2 * j + 1 - TEX;                  /* twice the distance from the centre, in texels */
-            const int r2 = dx * dx + dy * dy, rim = TEX * TEX;
-            a[0] = a[1] = a[2] = 255;
-            a[3] = (unsigned char)(r2 >= rim ? 0 : 255 - (255 * r2) / rim);
-            const int cx = i / 8, cy = j / 8, fx = i % 8, fy = j % 8;             /* bilinear over an 8 x 8 lattice, integers only */
-            const uint32_t v00 = lattice[cy][cx], v10 = lattice[cy][(cx + 1) % 8], v01 = lattice[(cy + 1) % 8][cx], v11 = lattice[(cy + 1) % 8][(cx + 1) % 8];
-            const uint32_t top = v00 * (uint32_t)(8 - fx) + v10 * (uint32_t)fx, bot = v01 * (uint32_t)(8 - fx) + v11 * (uint32_t)fx;
-            d[0] = (unsigned char)((top * (uint32_t)(8 - fy) + bot * (uint32_t)fy) / 128u);   /* 0 .. 127: most particles clear it */
-            d[1] = d[2] = d[0];
-            d[3] = 255;
-        }
-}
+ * The scene is mesh_host.c's and spray_host.c's.  The two textures are scene.h's procedural ones -- a round puff with a soft edge for the
+ * albedo, a tiling value noise for the dissolve.  Prints key=value pairs: the image size, the live particles, the billboards drawn and
+ * culled, the pixels that received spray and whether every colour is finite. */
+#include "scene.h"
 
 int main(int argc, char **argv) {
     const char *path = argc > 1 ? argv[1] : "spray.ppm";
     const int width = argc > 3 ? atoi(argv[2]) : 320, height = argc > 3 ? atoi(argv[3]) : 200;
-    const int steps = argc > 4 ? atoi(argv[4]) : 150, n = argc > 5 ? atoi(argv[5]) : 256, cascades = 3;
+    const int steps = scene_arg(argc, argv, 4, 150), n = scene_arg(argc, argv, 5, 256), cascades = SCENE_CASCADES;
     const double dt = 1.0 / 50.0;   /* water.gd:51 */
+    int status = 1;
 
     ow_config cfg;
-    memset(&cfg, 0, sizeof cfg);
-    cfg.map_size = n; cfg.num_cascades = cascades; cfg.device_id = -1; cfg.depth = 20.0f;
+    scene_config(&cfg, n);
     ow_context *ctx = NULL;
     ow_mesh *mesh = NULL;
     ow_spray *spray = NULL;
     ow_billboard_material *material = NULL;
+    unsigned char *rgba = NULL;
+    ow_render_pixel *px = NULL;
     void *rgba_dev = NULL, *px_dev = NULL;
     if (ow_create(&cfg, &ctx) != OW_OK) { fprintf(stderr, "ow_create: %s\n", ow_last_error()); return 1; }
 
-    static const float tile[3] = {88.0f, 57.0f, 16.0f}, wind[3] = {10.0f, 5.0f, 20.0f}, dir[3] = {20.0f, 15.0f, 20.0f};
-    static const float fetch[3] = {150.0f, 150.0f, 550.0f}, spread[3] = {0.2f, 0.4f, 0.4f}, whitecap[3] = {0.5f, 0.5f, 0.25f}, foam[3] = {8.0f, 0.0f, 3.0f};
-    ow_cascade_params par[3];
-    float map_scales[3][4];
-    for (int i = 0; i < cascades; ++i) {
-        ow_cascade_params_default(&par[i]);
-        par[i].tile_length[0] = par[i].tile_length[1] = tile[i];
-        par[i].wind_speed = wind[i]; par[i].wind_direction = dir[i]; par[i].fetch_length = fetch[i];
-        par[i].spread = spread[i]; par[i].whitecap = whitecap[i]; par[i].foam_amount = foam[i];
-        par[i].spectrum_seed[0] = 1000 + 17 * i; par[i].spectrum_seed[1] = -2000 + 31 * i;
-        par[i].time = 120.0 + 3.14159265358979323846 * i;
-        map_scales[i][0] = map_scales[i][1] = 1.0f / tile[i];
-        map_scales[i][2] = (float)par[i].displacement_scale;
-        map_scales[i][3] = (float)par[i].normal_scale;
-    }
-    if (width < 1 || height < 1 || width > OW_RENDER_MAX_SIDE || height > OW_RENDER_MAX_SIDE) { fprintf(stderr, "bad image size\n"); goto fail_quiet; }
+    ow_cascade_params par[SCENE_CASCADES];
+    float map_scales[SCENE_CASCADES][4];
+    scene_cascades(par, map_scales);
+    if (scene_bad_size(width, height, 1)) goto out;
 
     ow_spray_options so;
     ow_spray_options_default(&so);   /* mat_spray.tres, main.tscn:133-140 */
@@ -86,55 +38,23 @@ int main(int argc, char **argv) {
     if (ow_spray_create(ctx, &so, &spray) != OW_OK) goto fail;
 
     {   /* the material: sea_spray.gdshader's uniforms as the scene sets them, over the two procedural textures */
-        static unsigned char albedo[TEX * TEX * 4], dissolve[TEX * TEX * 4];
+        static unsigned char albedo[SCENE_TEX * SCENE_TEX * 4], dissolve[SCENE_TEX * SCENE_TEX * 4];
         ow_billboard_material_options mo;
-        make_textures(albedo, dissolve);
+        scene_textures(albedo, dissolve);
         ow_billboard_material_options_default(&mo);
-        if (ow_billboard_material_create(ctx, &mo, albedo, TEX, TEX, dissolve, TEX, TEX, &material) != OW_OK) goto fail;
+        if (ow_billboard_material_create(ctx, &mo, albedo, SCENE_TEX, SCENE_TEX, dissolve, SCENE_TEX, SCENE_TEX, &material) != OW_OK) goto fail;
     }
-
-    {   /* the grid: (CELLS + 1)^2 vertices around the node's origin, two triangles a cell */
-        const int32_t num_vertices = (CELLS + 1) * (CELLS + 1), num_triangles = 2 * CELLS * CELLS;
-        float *xyz = (float *)malloc((size_t)num_vertices * 3 * sizeof(float));
-        int32_t *idx = (int32_t *)malloc((size_t)num_triangles * 3 * sizeof(int32_t));
-        if (!xyz || !idx) { fprintf(stderr, "out of memory\n"); goto fail_quiet; }
-        for (int r = 0; r <= CELLS; ++r)
-            for (int c = 0; c <= CELLS; ++c) {
-                float *v = xyz + 3 * ((size_t)r * (CELLS + 1) + c);
-                v[0] = (float)c * CELL - 0.5f * CELLS * CELL; v[1] = 0.0f; v[2] = (float)r * CELL - 0.5f * CELLS * CELL;
-            }
-        for (int r = 0; r < CELLS; ++r)
-            for (int c = 0; c < CELLS; ++c) {
-                const int32_t a = r * (CELLS + 1) + c, b = a + 1, d = a + CELLS + 1, e = d + 1;
-                int32_t *t = idx + 6 * ((size_t)r * CELLS + c);
-                t[0] = a; t[1] = d; t[2] = b; t[3] = b; t[4] = d; t[5] = e;
-            }
-        const ow_status st = ow_mesh_create(ctx, xyz, num_vertices, idx, num_triangles, &mesh);
-        free(xyz); free(idx);
-        if (st != OW_OK) goto fail;
-    }
+    if (scene_grid_create(ctx, SCENE_CELLS, SCENE_CELL, &mesh)) goto out;
 
     ow_camera cam;
-    memset(&cam, 0, sizeof cam);
-    {   /* main.tscn:120 */
-        static const float basis[9] = {-0.996195f, -0.0151344f, 0.0858316f, 0.0f, 0.984807f, 0.173648f, -0.0871557f, 0.172987f, -0.981061f};
-        memcpy(cam.basis, basis, sizeof basis);
-        cam.position[0] = 0.0f; cam.position[1] = 10.0f; cam.position[2] = -25.0f;
-    }
-    cam.fov_y_degrees = 75.0f;
-    cam.max_distance = 4000.0f;
-    cam.width = width; cam.height = height;
-    const float origin[3] = {ceilf(cam.position[0] / CELL) * CELL, 0.0f, ceilf(cam.position[2] / CELL) * CELL};   /* main.gd:34-37 */
-
+    float origin[3];
+    scene_camera(&cam, width, height);
+    scene_clipmap_origin(&cam, SCENE_CELL, origin);
     ow_mesh_options opts;
-    ow_mesh_options_default(&opts);
-    opts.query_flags = OW_QUERY_DISTANCE_FALLOFF;   /* water.gdshader:29, around CAMERA_POSITION_WORLD.xz */
-    opts.falloff_center_xz[0] = cam.position[0];
-    opts.falloff_center_xz[1] = cam.position[2];
-    opts.flags = OW_MESH_CULL_BACK;
+    scene_mesh_options(&opts, &cam);
 
     const size_t count = (size_t)width * (size_t)height;
-    if (hipMalloc(&rgba_dev, count * 4) || hipMalloc(&px_dev, count * sizeof(ow_render_pixel))) { fprintf(stderr, "hipMalloc failed\n"); goto fail_quiet; }
+    if (hipMalloc(&rgba_dev, count * 4) || hipMalloc(&px_dev, count * sizeof(ow_render_pixel))) { fprintf(stderr, "hipMalloc failed\n"); goto out; }
 
     for (int k = 0; k < steps; ++k) {
         if (ow_update_all(ctx, dt, par, cascades) != OW_OK) goto fail;
@@ -145,23 +65,18 @@ int main(int argc, char **argv) {
     if (ow_billboard_draw_async(ctx, spray, material, &cam, NULL, (ow_render_pixel *)px_dev, rgba_dev) != OW_OK) goto fail;
     if (ow_sync(ctx) != OW_OK) goto fail;
 
-    unsigned char *rgba = (unsigned char *)malloc(count * 4);
-    ow_render_pixel *px = (ow_render_pixel *)malloc(count * sizeof(ow_render_pixel));
-    if (!rgba || !px) { fprintf(stderr, "out of memory\n"); goto fail_quiet; }
+    rgba = (unsigned char *)malloc(count * 4);
+    px = (ow_render_pixel *)malloc(count * sizeof(ow_render_pixel));
+    if (!rgba || !px) { fprintf(stderr, "out of memory\n"); goto out; }
     if (hipMemcpy(rgba, rgba_dev, count * 4, HIP_DEVICE_TO_HOST) || hipMemcpy(px, px_dev, count * sizeof(ow_render_pixel), HIP_DEVICE_TO_HOST)) {
         fprintf(stderr, "hipMemcpy failed\n");
-        goto fail_quiet;
+        goto out;
     }
     uint64_t culled = 0, drawn = 0;
     uint32_t live = 0;
     if (ow_billboard_draw_stats(ctx, NULL, &culled, &drawn, NULL) != OW_OK) goto fail;
     if (ow_spray_read(ctx, spray, NULL, NULL, NULL, &live) != OW_OK) goto fail;
-
-    FILE *f = fopen(path, "wb");
-    if (!f) { fprintf(stderr, "cannot write %s\n", path); goto fail_quiet; }
-    fprintf(f, "P6\n%d %d\n255\n", width, height);
-    for (size_t i = 0; i < count; ++i) fwrite(rgba + 4 * i, 1, 3, f);
-    fclose(f);
+    if (scene_write_ppm(path, rgba, width, height)) goto out;
 
     {
         size_t sprayed = 0, fragments = 0;
@@ -175,20 +90,16 @@ int main(int argc, char **argv) {
                height, steps, (unsigned)so.amount, (unsigned)live, (unsigned long long)drawn, (unsigned long long)culled, (unsigned long long)sprayed,
                (unsigned long long)fragments, finite);
     }
+    status = 0;
+    goto out;
+fail:
+    fprintf(stderr, "ocean_waves: %s\n", ow_last_error());
+out:
     free(rgba); free(px);
     (void)hipFree(rgba_dev); (void)hipFree(px_dev);
     ow_billboard_material_destroy(ctx, material);
     ow_spray_destroy(ctx, spray);
     ow_mesh_destroy(ctx, mesh);
     ow_destroy(ctx);
-    return 0;
-fail:
-    fprintf(stderr, "ocean_waves: %s\n", ow_last_error());
-fail_quiet:
-    (void)hipFree(rgba_dev); (void)hipFree(px_dev);
-    ow_billboard_material_destroy(ctx, material);
-    ow_spray_destroy(ctx, spray);
-    ow_mesh_destroy(ctx, mesh);
-    ow_destroy(ctx);
-    return 1;
+    return status;
 }

@@ -10,6 +10,7 @@
 #include <cstring>
 #include <string>
 
+#include "scene.h"
 #include "wave_generator.hpp"
 
 using namespace ocean_waves;
@@ -22,30 +23,28 @@ static uint64_t fnv1a(const void *data, size_t n) {
 }
 
 int main(int argc, char **argv) try {
-    const int n = argc > 1 ? atoi(argv[1]) : 256, cascades = 3, frames = argc > 2 ? atoi(argv[2]) : 12;
+    const int n = argc > 1 ? atoi(argv[1]) : 256, cascades = SCENE_CASCADES, frames = argc > 2 ? atoi(argv[2]) : 12;
     // argv[3]: every layer the sink is handed is also written to <prefix><layer>.bin (displacement bytes, then normal bytes; a later
     // hand-off of the same layer replaces the file): the bytes texture_update would get, for the tests to hold to the fixtures
     const std::string dump = argc > 3 ? argv[3] : "";
-    // the three cascades of the reference's main.tscn, seeds and time offsets as water.gd:31-32 assigns them
-    const float tile[3] = {88.0f, 57.0f, 16.0f}, wind[3] = {10.0f, 5.0f, 20.0f}, dir[3] = {20.0f, 15.0f, 20.0f};
-    const float fetch[3] = {150.0f, 150.0f, 550.0f}, spread[3] = {0.2f, 0.4f, 0.4f}, whitecap[3] = {0.5f, 0.5f, 0.25f}, foam[3] = {8.0f, 0.0f, 3.0f};
+    // the three cascades of the reference's main.tscn, seeds and time offsets as water.gd:31-32 assigns them: scene.h's records, set
+    // through the resource's setters as water.gd would
+    ow_cascade_params par[SCENE_CASCADES];
+    float map_scales[SCENE_CASCADES][4];
+    scene_cascades(par, map_scales);
     std::vector<ParametersRef> parameters;
-    float map_scales[3][4];
     for (int i = 0; i < cascades; ++i) {
         auto p = std::make_shared<WaveCascadeParameters>();
-        p->set_tile_length(tile[i], tile[i]);
-        p->set_wind_speed(wind[i]);
-        p->set_wind_direction(dir[i]);
-        p->set_fetch_length(fetch[i]);
-        p->set_spread(spread[i]);
-        p->set_whitecap(whitecap[i]);
-        p->set_foam_amount(foam[i]);
-        p->set_spectrum_seed(1000 + 17 * i, -2000 + 31 * i);
-        p->set_time(120.0 + 3.14159265358979323846 * i);
+        p->set_tile_length(par[i].tile_length[0], par[i].tile_length[1]);
+        p->set_wind_speed(par[i].wind_speed);
+        p->set_wind_direction(par[i].wind_direction);
+        p->set_fetch_length(par[i].fetch_length);
+        p->set_spread(par[i].spread);
+        p->set_whitecap(par[i].whitecap);
+        p->set_foam_amount(par[i].foam_amount);
+        p->set_spectrum_seed(par[i].spectrum_seed[0], par[i].spectrum_seed[1]);
+        p->set_time(par[i].time);
         parameters.push_back(p);
-        map_scales[i][0] = map_scales[i][1] = 1.0f / tile[i];  // water.gd:105-109
-        map_scales[i][2] = (float)p->displacement_scale();
-        map_scales[i][3] = (float)p->normal_scale();
     }
 
     WaveGenerator wave_generator;

@@ -3,8 +3,8 @@
 This is the one place that turns tests/<name>/<name>_harness.cpp (the headers of godotoceanwaves_amd/csrc compiled as plain C++, g++
 -ffp-contract=off) into a loaded library: one flag list, one build per process and source (harness_library), the argtypes of every entry
 point, and the cpu_* functions, Cpu* classes and case writers that feed them.  The *_harness fixtures hand the cached libraries to the tests;
-a test module imports the ones its tests take as arguments.  The stand-alone sanitizer programs, the C examples and the layout probes are
-built here as well.  Scenes and inputs: tests/scenes.py; the comparisons: tests/checks.py."""
+a test module imports the ones its tests take as arguments.  The stand-alone sanitizer programs, every program of examples/ (build_example:
+one table, one command) and the layout probes are built here as well.  Scenes and inputs: tests/scenes.py; the comparisons: tests/checks.py."""
 import atexit
 import ctypes as C
 import functools
@@ -59,25 +59,30 @@ def build_sanitized_harness(name, tmp_path):
     return exe
 
 
-# the C99 examples: the warning flags each was written to, and what it links besides the library
-_STRICT, _PLAIN = ["-Wall", "-Wextra", "-pedantic", "-Werror"], ["-Wall", "-Werror"]
+# the examples: the compiler and warning flags each was written to, and what it links besides the library
+_C99, _CXX17 = ["gcc", "-O2", "-std=c99"], ["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-Werror"]
+_STRICT = _C99 + ["-Wall", "-Wextra", "-pedantic", "-Werror"]
 _HIP = ["-L", "/opt/rocm/lib", "-lamdhip64"]
+_OWN = [f"-Wl,-rpath,{PKG}", "-Wl,-rpath-link,/opt/rocm/lib"]
 _RPATH = [f"-Wl,-rpath,{PKG}", "-Wl,-rpath,/opt/rocm/lib"]
 _RPATH_LINK = _RPATH + ["-Wl,-rpath-link,/opt/rocm/lib"]
 EXAMPLES = {
     "buoyancy_host": (_STRICT, _HIP + _RPATH_LINK), "floating_bodies_host": (_STRICT, _HIP + _RPATH_LINK),
-    "render_host": (_PLAIN, _RPATH_LINK), "mesh_host": (_PLAIN, _RPATH_LINK), "spray_host": (_PLAIN, _RPATH_LINK),
-    "spray_draw_host": (_PLAIN, _HIP + _RPATH), "solid_draw_host": (_PLAIN, _HIP + _RPATH), "present_host": (_PLAIN, _HIP + _RPATH),
-    "sky_light_host": (_PLAIN, _HIP + _RPATH), "shadow_host": (_PLAIN, _HIP + _RPATH),
+    "render_host": (_STRICT, _RPATH_LINK), "mesh_host": (_STRICT, _RPATH_LINK), "spray_host": (_STRICT, _RPATH_LINK),
+    "spray_draw_host": (_STRICT, _HIP + _RPATH), "solid_draw_host": (_STRICT, _HIP + _RPATH), "present_host": (_STRICT, _HIP + _RPATH),
+    "sky_light_host": (_STRICT, _HIP + _RPATH), "shadow_host": (_STRICT, _HIP + _RPATH), "mist_host": (_STRICT, _HIP + _RPATH),
+    "mirror_host": (_STRICT, _HIP + _RPATH), "c_consumer": (_STRICT, _OWN), "multi_gpu_host": (_STRICT, _OWN),
+    "wave_generator_host": (_CXX17, _OWN), "water_host": (_CXX17 + ["-I", os.path.join(ROOT, "examples")], _OWN),
 }
 
 
 def build_example(tmp_path, name):
-    """examples/<name>.c as C99 against the built library"""
-    warnings, links = EXAMPLES[name]
+    """examples/<name>.c as C99 with -lm, or <name>.cpp as C++17, against the built library"""
+    compiler, links = EXAMPLES[name]
     exe = str(tmp_path / name)
-    subprocess.run(["gcc", "-O2", "-std=c99"] + warnings + ["-I", INCLUDE, os.path.join(ROOT, "examples", name + ".c"), "-o", exe, "-L", PKG,
-                                                            "-locean_waves"] + links + ["-lm"], check=True)
+    source, libm = (".cpp", []) if compiler[0] == "g++" else (".c", ["-lm"])
+    subprocess.run(compiler + ["-I", INCLUDE, os.path.join(ROOT, "examples", name + source), "-o", exe, "-L", PKG, "-locean_waves"] + links + libm,
+                   check=True)
     return exe
 
 
@@ -779,17 +784,9 @@ def cpu_shadow_cast(L, frame, size, shape, tf, brute=False):
     return dict(map=words, skipped=s, culled=c, lane=ln, wave=wv, drawn=ln + wv, **extra)
 
 
-def build_c_consumer(tmp_path):
-    exe = str(tmp_path / "c_consumer")
-    subprocess.run(["gcc", "-O2", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-I", os.path.join(ROOT, "include"),
-                    os.path.join(ROOT, "examples", "c_consumer.c"), "-o", exe, "-L", PKG, "-locean_waves",
-                    f"-Wl,-rpath,{PKG}", "-Wl,-rpath-link,/opt/rocm/lib", "-lm"], check=True)
-    return exe
-
-
-def build_cpp_host(tmp_path):
-    exe = str(tmp_path / "wave_generator_host")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"),
-                    os.path.join(ROOT, "examples", "wave_generator_host.cpp"), "-o", exe, "-L", PKG, "-locean_waves",
-                    f"-Wl,-rpath,{PKG}", "-Wl,-rpath-link,/opt/rocm/lib"], check=True)
+def build_scene_dump(tmp_path):
+    """tests/example_scene/scene_dump.c over examples/scene.h: a program of its own under the sanitizers, nothing of the library linked"""
+    exe = str(tmp_path / "scene_dump")
+    subprocess.run(["gcc", "-O1", "-g", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-fsanitize=address,undefined",
+                    "-fno-sanitize-recover=undefined", "-I", INCLUDE, os.path.join(HERE, "example_scene", "scene_dump.c"), "-o", exe, "-lm"], check=True)
     return exe

@@ -685,7 +685,7 @@ def buffers_to_host(cam, rgba_dev, rec_dev):
 
 
 def example_textures(size=64):
-    """examples/spray_draw_host.c's make_textures, integer for integer"""
+    """examples/scene.h's scene_textures, integer for integer (tests/test_example_scene.py compares the bytes)"""
     s, lattice = 12345, np.zeros((8, 8), np.int64)
     for j in range(8):
         for i in range(8):
@@ -791,7 +791,7 @@ def pose_transforms(gen, bodies):
 
 
 def example_crates():
-    """examples/solid_draw_host.c's crates, operation for operation"""
+    """examples/scene.h's scene_crates, operation for operation (tests/test_example_scene.py compares the bytes)"""
     size, rho, per = (2.0, 1.0, 2.0), 1025.0, 4 * 2 * 4
     volume = size[0] * size[1] * size[2]
     mass = 0.5 * rho * volume
@@ -922,7 +922,7 @@ def frame_scene(n=256, ids=(0, 1, 2), ticks=100, steps=30):
 
 
 def example_panorama(w=256, h=128):
-    """examples/present_host.c's make_panorama, integer for integer"""
+    """examples/scene.h's scene_panorama, integer for integer (tests/test_example_scene.py compares the bytes)"""
     half = h // 2
     j, i = np.meshgrid(np.arange(h), np.arange(w), indexing="ij")
     up = j < half

@@ -7,12 +7,12 @@ import subprocess
 import pytest
 
 from checks import check_against_mirror
-from cpu_builds import build_cpp_host as build
+from cpu_builds import build_example
 
 
 def test_builds_and_fails_loudly_without_a_device(tmp_path):
     import torch
-    exe = build(tmp_path)
+    exe = build_example(tmp_path, "wave_generator_host")
     if torch.cuda.is_available():
         pytest.skip("a GPU is present: covered by the gpu test")
     r = subprocess.run([exe], capture_output=True, text=True)
@@ -22,6 +22,6 @@ def test_builds_and_fails_loudly_without_a_device(tmp_path):
 @pytest.mark.gpu
 @pytest.mark.parametrize("n,frames", [(256, 12), (512, 7)])
 def test_cpp_host_and_python_mirror_agree(tmp_path, n, frames):
-    r = subprocess.run([build(tmp_path), str(n), str(frames)], capture_output=True, text=True)
+    r = subprocess.run([build_example(tmp_path, "wave_generator_host"), str(n), str(frames)], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     check_against_mirror(r.stdout, n, frames)

@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 
 import helpers as H
-from cpu_builds import build_c_consumer, build_cpp_host
+from cpu_builds import build_example
 from godotoceanwaves_amd import WaveCascadeParameters, WaveGenerator, _lib
 from godotoceanwaves_amd.presets import UPDATE_DELTA, cascade_preset
 
@@ -104,9 +104,8 @@ def test_dma_buf_import_in_a_second_process_sees_the_reference_bytes(tmp_path):
 def test_compiled_hosts_hand_the_reference_bytes_to_their_sinks(tmp_path, host):
     """the reference's schedule (update + one cascade per rendered frame, wave_generator.gd:56-63,90-109): nine frames = three updates of
     the three cascades of main.tscn (presets 0, 1, 2 in layers 0, 1, 2); what the sink got LAST for each layer is the fixture's state"""
-    build = build_c_consumer if host == "c_consumer" else build_cpp_host
     prefix = str(tmp_path / "layer")
-    r = subprocess.run([build(tmp_path), str(N), str(3 * FRAMES), prefix], capture_output=True, text=True, timeout=900)
+    r = subprocess.run([build_example(tmp_path, host), str(N), str(3 * FRAMES), prefix], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr
     assert f"layers_handed_off={3 * FRAMES}" in r.stdout
     for layer in range(3):

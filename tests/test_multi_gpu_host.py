@@ -2,26 +2,17 @@
 single-process host.  CPU: builds and fails loudly without a device.  GPU (one MI355X: two / four shards on device 0, every shard
 through the peer path): its checksum of the gathered arrays equals the Python mirror's on the same schedule, whatever the device
 list (cascades are independent units)."""
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
-from cpu_builds import PKG, ROOT
-
-
-def build(tmp_path):
-    exe = str(tmp_path / "multi_gpu_host")
-    subprocess.run(["gcc", "-O2", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-I", os.path.join(ROOT, "include"),
-                    os.path.join(ROOT, "examples", "multi_gpu_host.c"), "-o", exe, "-L", PKG, "-locean_waves",
-                    f"-Wl,-rpath,{PKG}", "-Wl,-rpath-link,/opt/rocm/lib", "-lm"], check=True)
-    return exe
+from cpu_builds import build_example
 
 
 def test_builds_as_pedantic_c99_and_fails_loudly_without_a_device(tmp_path):
     import torch
-    exe = build(tmp_path)
+    exe = build_example(tmp_path, "multi_gpu_host")
     if torch.cuda.is_available():
         pytest.skip("a GPU is present: covered by the gpu test")
     r = subprocess.run([exe], capture_output=True, text=True)
@@ -40,7 +31,7 @@ def test_c_program_and_python_group_agree(tmp_path, devices, per):
     from godotoceanwaves_amd import WaveCascadeParameters, WaveGeneratorGroup
     from godotoceanwaves_amd.presets import UPDATE_DELTA, cascade_preset
     n, ticks, every = 256, 40, 8
-    r = subprocess.run([build(tmp_path), str(n), str(per), str(ticks), str(every), devices], capture_output=True, text=True)
+    r = subprocess.run([build_example(tmp_path, "multi_gpu_host"), str(n), str(per), str(ticks), str(every), devices], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     lines = r.stdout.strip().splitlines()
     # round 6: one line per shard first -- how its layers reach the root device (ow_group_link_info: peer access, link type, hops, which path)

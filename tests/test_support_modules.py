@@ -7,9 +7,9 @@ import os
 import re
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-# the modules that build something no other module builds: the ABI header checks, two example hosts, and the second build of four
-# harnesses under the undefined-behaviour sanitizer
-OWN_BUILDS = {"test_abi.py", "test_multi_gpu_host.py", "test_water_host.py", "test_consumer_edges.py"}
+# the modules that build something no other module builds: the ABI header checks, and the second build of four harnesses under the
+# undefined-behaviour sanitizer
+OWN_BUILDS = {"test_abi.py", "test_consumer_edges.py"}
 SUPPORT_BUILDS = {"cpu_builds.py"}
 
 

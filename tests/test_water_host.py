@@ -17,7 +17,7 @@ from godotoceanwaves_amd import WaveCascadeParameters
 from godotoceanwaves_amd.presets import DEPTH, cascade_preset
 from godotoceanwaves_amd.water import Water
 from oracle import oracle as O
-from cpu_builds import PKG, ROOT
+from cpu_builds import build_example
 
 SCRIPT = """
 params 3
@@ -56,17 +56,9 @@ dump {out}
 """
 
 
-def build(tmp_path):
-    exe = str(tmp_path / "water_host")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "examples"),
-                    os.path.join(ROOT, "examples", "water_host.cpp"), "-o", exe, "-L", PKG, "-locean_waves",
-                    f"-Wl,-rpath,{PKG}", "-Wl,-rpath-link,/opt/rocm/lib"], check=True)
-    return exe
-
-
 def test_builds_and_fails_loudly_without_a_device(tmp_path):
     import torch
-    exe = build(tmp_path)
+    exe = build_example(tmp_path, "water_host")
     if torch.cuda.is_available():
         pytest.skip("a GPU is present: covered by the gpu test")
     script = tmp_path / "s.txt"
@@ -142,7 +134,7 @@ def test_compiled_water_node_on_the_real_kernels_follows_the_oracle_on_the_same_
     script = SCRIPT.format(out=out)
     sfile = tmp_path / "script.txt"
     sfile.write_text(script)
-    r = subprocess.run([build(tmp_path), str(sfile)], capture_output=True, text=True)
+    r = subprocess.run([build_example(tmp_path, "water_host"), str(sfile)], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     got_updates = [tuple(float(v) for v in l.split()[1::2]) for l in r.stdout.splitlines() if l.startswith("update")]
     lines, w = run_mirror(script)
