@@ -796,6 +796,13 @@ template <int AUX = 0>
 OW_DEV void gstore16(GBuf b, uint32_t voff, uint32_t soff, f32x4 v) {
     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v), b.r, (int)voff, (int)soff, AUX);
 }
+// One aligned 32-byte record at a WAVE-UNIFORM address, read once per wave through the scalar data cache into SGPRs (no VGPR, no slot in
+// the vector memory queue).  Only for bytes that an EARLIER launch wrote: the scalar cache is not coherent with stores of the same launch.
+typedef float f32x8_t __attribute__((ext_vector_type(8)));
+OW_DEV f32x8_t sload32(const void *p) {
+    typedef const __attribute__((address_space(4))) f32x8_t *const_ptr;
+    return *(const_ptr)(uintptr_t)p;
+}
 #else
 struct GBuf {
     char *p;
@@ -1313,6 +1320,29 @@ struct Pass2 {
             OW_SCHED_FENCE();
         }
     }
+    // The same in two steps (OW_P2_EARLY & 2): pcol_issue asks for the four 16-byte pieces of one half (half as in derive_dx: 0 = blocks
+    // 8..15, 1 = blocks 0..7) and nothing else, so that the caller can place the requests of BOTH halves ahead of the first use;
+    // derive_dx_from is derive_dx's arithmetic on the sixteen values, operation for operation.
+    template <int AUX = 0>
+    static OW_DEV void pcol_issue(f32x4 *pv, int half, int t, GBuf pcol_c) {
+#pragma unroll
+        for (int i = 0; i < P / 4; ++i) pv[(P / 4) * half + i] = gload16<AUX>(pcol_c, (uint32_t)t * 128u, 16u * (uint32_t)(i + (P / 4) * (1 - half)));
+    }
+    static OW_DEV void derive_dx_from(cplx *d, const f32x4 *pv, int t, int xp, float dky) {
+        const float s = (xp & 1) ? -1.0f : 1.0f;
+#pragma unroll
+        for (int half = 0; half < 2; ++half) {
+#pragma unroll
+            for (int k = 0; k < P / 2; ++k) {
+                const int j = 8 * half + k;
+                const f32x4 v = pv[(P / 4) * half + k / 2];
+                const cplx p = (k & 1) ? cplx{v.z, v.w} : cplx{v.x, v.y};
+                const float ky = ky_of(j, t, dky);
+                d[j] = cplx{__builtin_fmaf(-ky, d[j].y, s * p.x), __builtin_fmaf(ky, d[j].x, s * p.y)};
+            }
+            OW_SCHED_FENCE();
+        }
+    }
     // C1 = (1 - ky) hz for all y of row x' from the stored half S(x', y >= N/2) = row transform of hz:
     //   slots j < 8  (y = t + T (8 + j) >= N/2):  (1 - ky) S(y)
     //   slots j >= 8 (y = t + T (j - 8) <  N/2):  (1 - ky) conj(S(N - y)),  N - y = (N - t) - T (j - 8): the lanes of the wave read
@@ -1340,6 +1370,15 @@ struct Pass2 {
     static OW_DEV void put_row0(cplx *d, int t, cplx r) {
         d[kRow0Slot] = cplx{t == 0 ? r.x : d[kRow0Slot].x, t == 0 ? r.y : d[kRow0Slot].y};
     }
+#if OW_DEVICE_BUILD
+    // the same for a wave whose lane 0 is t == 0, with r wave-uniform (in SGPRs): two lane writes; a select would first copy r into VGPRs
+    static OW_DEV void put_row0_lane0(cplx *d, cplx r) {
+        float x = d[kRow0Slot].x, y = d[kRow0Slot].y;
+        asm("v_writelane_b32 %0, %1, 0" : "+v"(x) : "s"(r.x));
+        asm("v_writelane_b32 %0, %1, 0" : "+v"(y) : "s"(r.y));
+        d[kRow0Slot] = cplx{x, y};
+    }
+#endif
     // Order of the four transforms: F2, F0, F1, F3.  C0 feeds both F0 and F1; it is loaded ONCE and a copy stays in registers
     // across F0's transform (re-reading it two transforms later would miss the L2 and put the fourth layer's bytes back on
     // the memory interface).  What waits in registers between the phases:

@@ -677,11 +677,28 @@ constexpr bool p2c_half_table(int N) { return plan_row_spans_waves(N); }
 constexpr int p2c_table_total(int N) { return p2c_half_table(N) ? plan_twh_total(N) : plan_tw_total(N); }
 template <int N>
 __device__ __forceinline__ const cplx *p2c_table(const DeviceBuffers &buf) { return p2c_half_table(N) ? buf.tw_half : buf.tw; }
+// OW_P2_EARLY: where pass 2 asks for its inputs.  Each bit moves one group of loads from the place where it is consumed to the earliest
+// place where its address is known and registers are free; nothing else changes (the same loads, the same arithmetic in the same order:
+// the maps are bit-identical for every value).  0 keeps the order of one request per point of use (A/B builds, profiles/pass2_load_order.txt).
+//   1  side rows: the three texel-row-0 entries of x' at the top of the item -- where a wave holds one x' (N >= 1024) as ONE scalar load of the
+//      32-byte record (rrow was written by an earlier launch in every kernel that calls this: by pass 1 of the same batch, which a tick-pair
+//      launch runs one launch ahead into the other scratch slot); elsewhere as three vector loads issued with C1's
+//   2  pcol: all eight 16-byte pieces before the first is used, the first four above F0's stores
+//   4  C0 above F2's epilogue          8  C2 and the foam state above F1's epilogue
+// Measured one by one at 1024^2 x 4 (profiles/pass2_load_order.txt): 1 gains 0.8 % of the tick, 2 and 4 change nothing, 8 loses 0.2 %, all four
+// together lose 0.1 %: only the side rows are on.
+#ifndef OW_P2_EARLY
+#define OW_P2_EARLY 1
+#endif
 template <int N, bool F32, int AUX_T, int AUX_O, class RS, class Issued>
 __device__ __forceinline__ void pass2c_item(const DeviceBuffers &buf, const CascadeFrame &cf, int tslot, int row0, int tau, cplx *tw_lds, cplx *rows_lds,
                                             RS &rs, Issued issued, uint32_t (&foam_pk)[kP / 2], int foam_io = 3) {
     constexpr int Tn = plan_T(N), P = kP;
     constexpr bool TWH = p2c_half_table(N);
+    // (N <= 512 runs at 128 VGPRs already: C2 there, or anything in the instantiations that also write the FP32 debug image, would spill)
+    constexpr int EARLY = (F32 && Tn < 64) ? 0 : (Tn < 64) ? (OW_P2_EARLY & 7) : OW_P2_EARLY;
+    constexpr bool SIDE_EARLY = (EARLY & 1) != 0, SIDE_SCALAR = SIDE_EARLY && Tn >= 64;
+    constexpr bool PCOL_EARLY = (EARLY & 2) != 0, C0_EARLY = (EARLY & 4) != 0, C2_EARLY = (EARLY & 8) != 0;
     const int rw = (Tn >= 64) ? __builtin_amdgcn_readfirstlane(tau / Tn) : tau / Tn, t = tau % Tn;
     const uint32_t plane = (uint32_t)N * N;
     cplx *lds_row = rows_lds + rw * plan_region_cplx(N);
@@ -696,51 +713,95 @@ __device__ __forceinline__ void pass2c_item(const DeviceBuffers &buf, const Casc
     const float dky = (2.0f * kPi) / cf.tile_y;
     // texel row 0's three transforms at this x' (ky-index 0 of F1..F3): entry q of the side buffer
     auto side_row = [&](int q) { return gload8(rrow_c, (uint32_t)xp * 32u, (uint32_t)q * 8u); };
+    cplx r1, r2, r3;
+    if constexpr (SIDE_SCALAR) {
+        const f32x8_t rec = sload32(buf.rrow + ((size_t)tslot * N + (size_t)xp) * 4);
+        r1 = cplx{rec[2], rec[3]};
+        r2 = cplx{rec[4], rec[5]};
+        r3 = cplx{rec[6], rec[7]};
+    }
+    auto put_row0 = [&](cplx *d, int tq, cplx r) {
+        if constexpr (SIDE_SCALAR) {
+            if (Tn == 64 || __builtin_amdgcn_readfirstlane(t) == 0) Pass2<N>::put_row0_lane0(d, r);  // (a row's second wave holds no t == 0)
+        } else {
+            Pass2<N>::put_row0(d, tq, r);
+        }
+    };
 
     uint32_t hz_pk[P / 2];
     float c2[P];
+    cplx c0[P];  // C0, loaded once: transformed as it is (F0) and, from this copy, as i ky C0 + P (F1)
     {
         cplx f2[P];
         OW_SCHED_FENCE();
+        if constexpr (SIDE_EARLY && !SIDE_SCALAR) {
+            r1 = side_row(1);
+            r2 = side_row(2);
+            r3 = side_row(3);
+        }
         Pass2<N>::template load_c1<AUX_T>(f2, t, xp, dky, T_c);
-        const cplx r2 = side_row(2);
+        if constexpr (!SIDE_EARLY) r2 = side_row(2);
         issued();
-        Pass2<N>::put_row0(f2, t, r2);
+        put_row0(f2, t, r2);
         row_ifft<N, false, TWH>(f2, opaque(t), lds_row, tw_lds, rs);
         OW_SCHED_FENCE();
+        if constexpr (C0_EARLY) {  // (live here: f2 32 + c0 32; hz_pk 8 + c2 16 take f2's place pair by pair)
+            Pass2<N>::template load_layer<AUX_T>(c0, opaque(t), xp, 0, T_c);
+            OW_SCHED_FENCE();
+        }
         Pass2<N>::template after_f2<F32>(f2, hz_pk, c2, (uint32_t)(xp * N + opaque(t)), f32_c);
     }
-    cplx c0[P];  // C0, loaded once: transformed as it is (F0) and, from this copy, as i ky C0 + P (F1)
+    f32x4 pv[P / 2];  // P(ky) of this lane's sixteen rows (PCOL_EARLY)
     {
         cplx f0[P];
         OW_SCHED_FENCE();
         const int tq = opaque(t);  // per phase: offsets derived from the lane index are recomputed, not carried through the transforms
-        Pass2<N>::template load_layer<AUX_T>(c0, tq, xp, 0, T_c);
+        if constexpr (!C0_EARLY) Pass2<N>::template load_layer<AUX_T>(c0, tq, xp, 0, T_c);
 #pragma unroll
         for (int j = 0; j < P; ++j) f0[j] = c0[j];
         row_ifft<N, false, TWH>(f0, opaque(t), lds_row, tw_lds, rs);
         OW_SCHED_FENCE();
         const int tr = opaque(t);
+        if constexpr (PCOL_EARLY) {  // (live here: f0 32 + c0 32 + c2 16 + hz_pk 8, + these 16)
+            Pass2<N>::pcol_issue(pv, 0, tr, pcol_c);
+            OW_SCHED_FENCE();
+        }
         Pass2<N>::template after_f0<F32, AUX_O>(f0, hz_pk, tr, xp, (uint32_t)(xp * N + tr), disp_c, f32_c);
     }
     float dhx_dx[P];
     uint32_t gx_pk[P / 2];
+    cplx f3[P];
     {
         OW_SCHED_FENCE();
         const int tq = opaque(t);
-        Pass2<N>::derive_dx(c0, tq, xp, dky, pcol_c);
-        Pass2<N>::put_row0(c0, tq, side_row(1));
+        if constexpr (PCOL_EARLY) {
+            Pass2<N>::pcol_issue(pv, 1, tq, pcol_c);
+            OW_SCHED_FENCE();
+            Pass2<N>::derive_dx_from(c0, pv, tq, xp, dky);
+        } else {
+            Pass2<N>::derive_dx(c0, tq, xp, dky, pcol_c);
+        }
+        if constexpr (!SIDE_EARLY) r1 = side_row(1);
+        put_row0(c0, tq, r1);
         row_ifft<N, false, TWH>(c0, opaque(t), lds_row, tw_lds, rs);
         OW_SCHED_FENCE();
+        if constexpr (C2_EARLY) {  // (live here: f1 32 + c2 16 + f3 32 + foam 8; dhx_dx 16 + gx_pk 8 take f1's place pair by pair)
+            const int tr = opaque(t);
+            Pass2<N>::template load_layer<AUX_T>(f3, tr, xp, 2, T_c);
+            if (foam_io & 1) Pass2<N>::load_foam(foam_pk, tr, xp, foam_c);
+            OW_SCHED_FENCE();
+        }
         Pass2<N>::template after_f1<F32>(c0, dhx_dx, gx_pk, (uint32_t)(xp * N + opaque(t)), f32_c);
     }
     {
-        cplx f3[P];
         OW_SCHED_FENCE();
         const int tq = opaque(t);
-        Pass2<N>::template load_layer<AUX_T>(f3, tq, xp, 2, T_c);
-        Pass2<N>::put_row0(f3, tq, side_row(3));
-        if (foam_io & 1) Pass2<N>::load_foam(foam_pk, tq, xp, foam_c);
+        if constexpr (!C2_EARLY) Pass2<N>::template load_layer<AUX_T>(f3, tq, xp, 2, T_c);
+        if constexpr (!SIDE_EARLY) r3 = side_row(3);
+        put_row0(f3, tq, r3);
+        if constexpr (!C2_EARLY) {
+            if (foam_io & 1) Pass2<N>::load_foam(foam_pk, tq, xp, foam_c);
+        }
         row_ifft<N, false, TWH>(f3, opaque(t), lds_row, tw_lds, rs);
         OW_SCHED_FENCE();
         const int tr = opaque(t);
