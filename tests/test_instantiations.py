@@ -12,7 +12,8 @@ from godotoceanwaves_amd.presets import UPDATE_DELTA, cascade_preset
 
 pytestmark = pytest.mark.gpu
 
-BASELINE_CONFIGS = [(256, 4), (1024, 4), (1024, 8), (2048, 4)]   # C2, C3 (headline), C4 (per node), C5
+BASELINE_CONFIGS = [(256, 4), (1024, 4), (1024, 8), (2048, 4),   # C2, C3 (headline), C4 (per node), C5
+                    (512, 8)]   # tick_pairs_compact at N <= 512: pass2c_item takes EARLY = 0 in the debug instantiation and EARLY = 1 in the production one
 
 
 def make(n, count, debug, **kw):
@@ -57,10 +58,11 @@ def test_debug_and_production_instantiations_leave_the_same_bits(n, count):
         assert H.quantisation_exact(dbg.get_maps_f32(i), *prod.get_maps(i)), i
 
 
-@pytest.mark.parametrize("n,count", [(1024, 4), (2048, 4), (256, 4)], ids=lambda v: str(v))
-def test_one_launch_per_pass_instantiations_too(n, count):
-    dbg, pd = make(n, count, True, tick_groups=False)
-    prod, pp = make(n, count, False, tick_groups=False)
+@pytest.mark.parametrize("n,count,kernels", [(1024, 4, None), (2048, 4, None), (256, 4, None), (512, 8, None), (256, 2, "compact")],
+                         ids=["1024-4", "2048-4", "256-4", "512-8", "256-2-compact"])
+def test_one_launch_per_pass_instantiations_too(n, count, kernels):
+    dbg, pd = make(n, count, True, tick_groups=False, kernels=kernels)
+    prod, pp = make(n, count, False, tick_groups=False, kernels=kernels)
     dbg.run(UPDATE_DELTA, pd, 4); prod.run(UPDATE_DELTA, pp, 4)
     assert prod.last_kernel_family() in ("compact", "layer_parallel_compact")
     same_bits(dbg, prod, count, "one launch per pass")

@@ -1,5 +1,5 @@
 """Where the suite's shared scaffolding lives: test modules import the support modules (tests/scenes.py, tests/cpu_builds.py,
-tests/checks.py, tests/helpers.py, tests/device_maps.py, tests/raster_soups.py, the twins), never one another, and so do the programs under scripts/; and a compiler is started from the
+tests/checks.py, tests/helpers.py, tests/device_maps.py, tests/raster_soups.py, tests/foam_exact.py, the twins), never one another, and so do the programs under scripts/; and a compiler is started from the
 support modules only, apart from the few test modules whose builds are their subject."""
 import ast
 import glob
